@@ -11,6 +11,16 @@ final gather to rank 0 in its two halves (tracy_amd/shard.py Resul
 collective, then the traceback strings -- packed on the device (tracyhip_pack_ragged_multi) -- in one grouped exchange sized from the
 records' length column.  `gather_ms_per_step` is that part of `ms_per_step`.
 
+A plain run (`--gpus N --steps K --warmup W`) does what the headline needs and nothing else: inputs, W warm-up steps, the K timed steps of
+leg (1) below, the `--dump-outputs DIR` arrays if asked for, the line.  `--full` adds everything else this file measures or checks (legs
+2-4, the dominant kernel alone, the decompose / all-pairs / seed-extend / CLI workloads, the CPU baseline and its parity sample, the
+check of the gathered block) with the defaults those options always had; an option given by name is honoured either way.
+
+`--dump-outputs DIR` writes what rank 0 holds after the last timed step's gather: one float64 file per record column (`score_fwd.npy`
+... `ops_len.npy`, `forward.npy`), the traceback strings back to back as byte values (`ops.npy`, float32, trace i's `ops_len` bytes),
+and `trace_index.npy`, the traces they belong to -- every trace, or, where that would pass 64 MB, a sample of them seeded by the batch
+size alone.  The inputs are seeded, so two builds run with the same arguments can be compared file for file.
+
 Legs (each: W warm-up + K timed steps between barriers): (1) the headline -- one lane, exact gsFwd AND gsRev (`value`, `roofline`: what
 a zero-initialised job gets): the strand a k-mer vote does not pick is swept in full, the voted one by its first 128 rows over the
 window and a certified band below them (front.h; swept in full where the certificate fails); (2) the strand-by-certificate mode
@@ -19,7 +29,7 @@ voted one continued on its band, the other one decided by its bound; (3), (4) th
 flight.  Legs 2-4 are checked to return the headline leg's alignments and are reported beside it;
 `--certificate-leg 0 --lanes-leg 0` runs the headline alone (what the rocprofv3 passes under profiles/ use).
 
-Beside the headline the default run also times BASELINE.json configs[2] (`tracy decompose`, 100 000 traces sharded over the
+Beside the headline a `--full` run also times BASELINE.json configs[2] (`tracy decompose`, 100 000 traces sharded over the
 ranks) configs[4] (all-pairs profile x profile scoring of 1000 traces, pair list sharded over the ranks, score slices
 all-gathered) and configs[3] in miniature (host seeding + device extend) -- tools/legs.py -- each with its own roofline, cpu_baseline and in-run parity sample, reported as the
 `decompose`, `allpairs` and `seedextend` objects of the same line (`--workload align|decompose|allpairs|seedextend` runs one of them alone, which
@@ -28,7 +38,7 @@ is what the rocprofv3 passes under profiles/ use).  `value` is always the align 
 `--gpus N` without a torch.distributed environment starts the N ranks itself (torch.distributed.run, 127.0.0.1) after checking
 that the box has N GPUs; every rank asserts that the process group really has N members.
 
-Prints ONE JSON line on rank 0, cut to what the driver's record keeps (finish_line: < 8 KB, the figures of every leg as scalars at the
+Prints ONE JSON line on rank 0; with --full (or --full-line) it is cut to what the driver's record keeps (finish_line: < 8 KB, the figures of every leg as scalars at the
 top level and in `config` / `roofline`); the unabridged line goes to --full-line (default gpurun_out/bench_line_full.json).
 """
 import argparse
@@ -206,11 +216,43 @@ def finish_line(line, args):
     return out
 
 
+DUMP_LIMIT = 64 << 20  # bytes: --dump-outputs writes at most this much
+
+
+def dump_outputs(path, names, records, ops, ops_cap, seed=20260):
+    """--dump-outputs: `records` int32 [n, len(names)] (host), `ops` uint8 (host): the traceback strings of the n traces back to back,
+    trace i's records[i, ops_len] bytes.  Every trace where the files fit in DUMP_LIMIT, else a sample of traces chosen by `seed` and n
+    alone (sized for strings of ops_cap bytes), so that the files of two builds cover the same traces."""
+    os.makedirs(path, exist_ok=True)
+    n = int(records.shape[0])
+    lens = records[:, names.index("ops_len")].astype(np.int64)
+    if int(lens.sum()) != int(ops.size):
+        raise RuntimeError("--dump-outputs: the strings hold %d bytes, the records announce %d" % (ops.size, int(lens.sum())))
+    per_trace = (len(names) + 1) * 8  # a float64 per record column + the trace's index
+    if n * per_trace + int(ops.size) * 4 <= DUMP_LIMIT:
+        idx = np.arange(n, dtype=np.int64)
+        sel = ops
+    else:
+        k = max(1, min(n, DUMP_LIMIT // (per_trace + 4 * ops_cap)))
+        idx = np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False)).astype(np.int64)
+        off = np.concatenate([[0], np.cumsum(lens)])
+        sel = np.concatenate([ops[off[i]:off[i] + lens[i]] for i in idx]) if k else ops[:0]
+    for j, name in enumerate(names):
+        np.save(os.path.join(path, name + ".npy"), records[idx, j].astype(np.float64))
+    np.save(os.path.join(path, "ops.npy"), sel.astype(np.float32))
+    np.save(os.path.join(path, "trace_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--workload", default="all", choices=("all", "align", "decompose", "allpairs", "seedextend", "cli"),
-                    help="all: the align headline + the decompose and all-pairs legs; one name: that workload alone (profiling)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else this benchmark measures or checks (the defaults marked [--full] below)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step of the headline computed to DIR/<name>.npy (at most 64 MB)")
+    ap.add_argument("--workload", default=None, choices=("all", "align", "decompose", "allpairs", "seedextend", "cli"),
+                    help="all: the align headline + the decompose, all-pairs, seed-extend and CLI legs; one name: that workload alone "
+                         "(profiling).  Default: align [--full: all]")
     ap.add_argument("--decompose-traces", type=int, default=100000, help="configs[2]: traces of the whole decompose job (sharded over the ranks)")
     ap.add_argument("--decompose-steps", type=int, default=3)
     ap.add_argument("--allpairs-traces", type=int, default=1000, help="configs[4]: traces of the all-pairs job (pair list sharded over the ranks)")
@@ -234,16 +276,25 @@ def main():
     ap.add_argument("--trace-len", type=int, default=1000)
     ap.add_argument("--lanes", type=int, default=1,
                     help="headline leg: chunks of the batch in flight inside one tracyhip_align_traces call (tracyhip_set_lanes)")
-    ap.add_argument("--lanes-leg", type=int, default=2,
-                    help="also time the batch split over this many lanes (reported beside the headline; 0/1 = skip)")
-    ap.add_argument("--certificate-leg", type=int, default=1,
-                    help="1: also time the library's default strand-by-certificate mode after the headline leg (reported beside it)")
-    ap.add_argument("--alone-steps", type=int, default=3, help="untimed extra steps with option sweeps_alone: the dominant kernel on a device of its own (0 = skip)")
+    ap.add_argument("--lanes-leg", type=int, default=None,
+                    help="also time the batch split over this many lanes (reported beside the headline; 0/1 = skip).  Default: 0 [--full: 2]")
+    ap.add_argument("--certificate-leg", type=int, default=None,
+                    help="1: also time the library's default strand-by-certificate mode after the headline leg (reported beside it).  "
+                         "Default: 0 [--full: 1]")
+    ap.add_argument("--alone-steps", type=int, default=None,
+                    help="untimed extra steps with option sweeps_alone: the dominant kernel on a device of its own (0 = skip).  Default: 0 [--full: 3]")
     ap.add_argument("--full-line", default=None, help="also write the unabridged line (every leg's detail) to this file (default: gpurun_out/bench_line_full.json when that directory exists)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="traces for the CPU baseline (-1: 2 per thread, capped)")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="traces for the CPU baseline (-1: 2 per thread, capped; 0 = skip).  Default: 0 [--full: -1]")
     args = ap.parse_args()
+    for name, plain, full in (("workload", "align", "all"), ("lanes_leg", 0, 2), ("certificate_leg", 0, 1), ("alone_steps", 0, 3), ("cpu_sample", 0, -1)):
+        if getattr(args, name) is None:
+            setattr(args, name, full if args.full else plain)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and args.workload not in ("all", "align"):
+        raise SystemExit("--dump-outputs writes the align headline's results: not with --workload %s" % args.workload)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))
 
@@ -425,6 +476,15 @@ def main():
         return dt, read_timers()
 
     elapsed, rl = timed_leg()
+    if args.dump_outputs and rank == 0:  # (before any other leg reuses the result buffers)
+        if gathered["out"] is not None and gathered["out"][0] is not None:  # what the job's gather handed rank 0 in the last timed step
+            allrec, got = gathered["out"]
+            rec_h, ops_h = allrec.cpu().numpy(), got[0].cpu().numpy()
+        else:  # no process group: this rank's results as the library call left them
+            rec_h = torch.stack([r_i32[k] for k in REC_KEYS] + [r_fwd.to(torch.int32)], dim=1).cpu().numpy()
+            ops_all, lens = r_ops.cpu().numpy(), rec_h[:, REC_KEYS.index("ops_len")]
+            ops_h = np.concatenate([ops_all[i * ops_cap:i * ops_cap + int(lens[i])] for i in range(nt)])
+        dump_outputs(args.dump_outputs, list(REC_KEYS) + ["forward"], rec_h, ops_h, ops_cap)
     gather_ms = gathered["seconds"] / max(args.steps, 1) * 1e3  # (rank 0's share of a timed step spent behind the library call)
     call_stats = ctx.last_call_stats()
     slice_len = r_i32["slice_len"].cpu().numpy().astype(np.int64)
@@ -469,7 +529,7 @@ def main():
         finally:
             ctx.set_option("sweeps_alone", 0)
 
-    if dist is not None:
+    if args.full and dist is not None:
         step()  # (the legs above ran other modes: one more headline step, untimed, whose gather is checked below)
 
     # ---- work done: DP cells of the four Gotoh calls per trace ----
@@ -496,7 +556,7 @@ def main():
     # what rank 0 holds after the step's gather must be what the ranks computed: its own block, bit for bit (the other ranks' blocks are
     # compared with the single-process results in tests/test_shard_gloo.py and tests/test_gpu_bench_ranks.py)
     gather_ok = None
-    if rank == 0 and gathered["out"] is not None and gathered["out"][0] is not None:
+    if args.full and rank == 0 and gathered["out"] is not None and gathered["out"][0] is not None:
         allrec, got = gathered["out"]
         mine = torch.stack([r_i32[k] for k in REC_KEYS] + [r_fwd.to(torch.int32)], dim=1)
         gather_ok = gatherer.check_own_block(allrec, got, mine, [(r_ops, ops_cap, REC_KEYS.index("ops_len"))])
@@ -631,7 +691,8 @@ def main():
     if args.share_device:
         line["shared_device"] = True  # (a test of the N-rank code path on one GPU: not a measurement)
         line["backend"] = "gloo"
-    line = finish_line(line, args)
+    if args.full or args.full_line:
+        line = finish_line(line, args)
     print(json.dumps(line))
     if dist is not None:
         dist.destroy_process_group()

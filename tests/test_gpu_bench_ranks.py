@@ -23,7 +23,7 @@ def run(args, timeout=900):
 
 
 def test_two_ranks_headline_line():
-    line = run(["--gpus", "2", "--share-device", "--workload", "align", "--traces", "384", "--ref-len", "3000", "--steps", "2", "--warmup", "1",
+    line = run(["--gpus", "2", "--share-device", "--full", "--workload", "align", "--traces", "384", "--ref-len", "3000", "--steps", "2", "--warmup", "1",
                 "--cpu-sample", "8", "--lanes-leg", "0"])
     assert line["n_gpus"] == 2 and line["backend"] == "gloo" and line["rccl_ranks"] == 0 and line["shared_device"] is True  # (two ranks on one GPU: gloo, RCCL saw none)
     assert line["scaling"] == "weak" and line["config"]["traces_per_gpu"] == 384
@@ -43,7 +43,7 @@ def test_two_ranks_headline_line():
 
 
 def test_two_ranks_decompose_leg_shards_one_job():
-    line = run(["--gpus", "2", "--share-device", "--workload", "decompose", "--decompose-traces", "600", "--decompose-steps", "2", "--extra-legs", "0"])
+    line = run(["--gpus", "2", "--share-device", "--full", "--workload", "decompose", "--decompose-traces", "600", "--decompose-steps", "2", "--extra-legs", "0"])
     assert line["n_gpus"] == 2 and line["backend"] == "gloo" and line["rccl_ranks"] == 0 and line["scaling"] == "strong"
     assert line["config"]["traces_total"] == 600 and line["pipeline"]["traces_per_rank"] == 300
     assert line["pipeline"]["stream_ordered"] == 1

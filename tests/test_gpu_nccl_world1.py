@@ -29,7 +29,7 @@ def rank_env():
 
 def test_bench_rank_under_a_torchrun_environment_uses_nccl():
     for args, check in (
-        (["--workload", "align", "--traces", "512", "--ref-len", "3000", "--steps", "2", "--warmup", "1", "--cpu-sample", "8", "--lanes-leg", "0", "--certificate-leg", "0"],
+        (["--full", "--workload", "align", "--traces", "512", "--ref-len", "3000", "--steps", "2", "--warmup", "1", "--cpu-sample", "8", "--lanes-leg", "0", "--certificate-leg", "0"],
          lambda ln: ln["config"]["traces_per_gpu"] == 512 and ln["value"] > 0 and ln["config"]["gcups_swept_cells"] > 0 and ln["gather_checked"] is True
          and ln["gathered_bytes_per_step"] > 512 * 900),
         (["--workload", "decompose", "--decompose-traces", "400", "--decompose-steps", "2", "--extra-legs", "0", "--cpu-sample", "0"],

@@ -5,7 +5,7 @@ import subprocess
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for n in [int(x) for x in (sys.argv[1] if len(sys.argv) > 1 else "10000").split(",")]:
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "align", "--traces", str(n), "--steps", "6", "--warmup", "2", "--certificate-leg", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "align", "--traces", str(n), "--steps", "6", "--warmup", "2", "--certificate-leg", "0",
                         "--lanes-leg", "0", "--cpu-sample", "0"] + sys.argv[2:], capture_output=True, text=True)
     try:
         d = json.loads([l for l in r.stdout.split("\n") if l.startswith("{")][-1])

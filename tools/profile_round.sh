@@ -12,11 +12,11 @@ OUT=/root/repo/gpurun_out/prof_round
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 B=/root/repo/bench.py
-AL="--workload align --steps 3 --warmup 1 --certificate-leg 0 --lanes-leg 0"
-DE="--workload decompose --decompose-steps 2 --extra-legs 0"
-DEX="--workload decompose --decompose-steps 3"  # the line kept for the record: with the certificate / two-lane / small-batch legs
-AP="--workload allpairs --allpairs-steps 2"
-SE="--workload seedextend --seedextend-steps 1 --seedextend-traces 31250"
+AL="--full --workload align --steps 3 --warmup 1 --certificate-leg 0 --lanes-leg 0"
+DE="--full --workload decompose --decompose-steps 2 --extra-legs 0"
+DEX="--full --workload decompose --decompose-steps 3"  # the line kept for the record: with the certificate / two-lane / small-batch legs
+AP="--full --workload allpairs --allpairs-steps 2"
+SE="--full --workload seedextend --seedextend-steps 1 --seedextend-traces 31250"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_stats" -- python $B $AL > "$OUT/bench_line.json" 2> "$OUT/bench.err"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/dec_stats" -- python $B $DE > "$OUT/dec_line_under_rocprof.json" 2> "$OUT/dec.err"
 python $B $DEX > "$OUT/dec_line.json" 2> "$OUT/dec_plain.err"
@@ -37,8 +37,8 @@ for w in bench dec; do
     --output-format csv -d "$OUT/pmc_${w}_stallB" -- python $B $ARGS > /dev/null 2> "$OUT/pmc_${w}_stallB.err"
   rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE --output-format csv -d "$OUT/pmc_${w}_clock" -- python $B $ARGS > /dev/null 2> "$OUT/pmc_${w}_clock.err"
 done
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_default_stats" -- python $B --workload align --steps 3 --warmup 1 > "$OUT/bench_default_line.json" 2> "$OUT/bench_default.err"
-python $B --full-line "$OUT/bench_plain_full.json" > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/bench_default_stats" -- python $B --full --workload align --steps 3 --warmup 1 > "$OUT/bench_default_line.json" 2> "$OUT/bench_default.err"
+python $B --full --full-line "$OUT/bench_plain_full.json" > "$OUT/bench_plain.json" 2> "$OUT/bench_plain.err"
 # where the GPU waits for the host: kernel + memory-copy timelines of one step of each pipeline (tools/timeline_gaps.py)
 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$OUT/tl_dec" -- python $B $DE --cpu-sample 0 > /dev/null 2> "$OUT/tl_dec.err"
 # (steps-back 1: the last timed step, from its first kernel to the first kernel of the step after it -- the run ends with one more,

@@ -4,11 +4,11 @@ TAG=${1:-r06}
 OUT=/root/repo/gpurun_out/prof_round
 cd /tmp && export TMPDIR=/tmp
 B=/root/repo/bench.py
-AL="--workload align --steps 3 --warmup 1 --certificate-leg 0 --lanes-leg 0"
-DE="--workload decompose --decompose-steps 2 --extra-legs 0"
-DEX="--workload decompose --decompose-steps 3"  # the line kept for the record: with the certificate / two-lane / small-batch legs
-AP="--workload allpairs --allpairs-steps 2"
-SE="--workload seedextend --seedextend-steps 1 --seedextend-traces 31250"
+AL="--full --workload align --steps 3 --warmup 1 --certificate-leg 0 --lanes-leg 0"
+DE="--full --workload decompose --decompose-steps 2 --extra-legs 0"
+DEX="--full --workload decompose --decompose-steps 3"  # the line kept for the record: with the certificate / two-lane / small-batch legs
+AP="--full --workload allpairs --allpairs-steps 2"
+SE="--full --workload seedextend --seedextend-steps 1 --seedextend-traces 31250"
 mkdir -p "$OUT"
 # where the GPU waits for the host: kernel + memory-copy timelines of one step of each pipeline (tools/timeline_gaps.py)
 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$OUT/tl_dec" -- python $B $DE --cpu-sample 0 > /dev/null 2> "$OUT/tl_dec.err"
