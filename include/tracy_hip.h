@@ -22,6 +22,7 @@
  *   generateSecondaryDecomposed            decompose.h:378-410              tracyhip_secondary_decomposed
  *   allelicFraction                        decompose.h:412-621              tracyhip_allelic_fraction
  *   trimReferenceSlice                     fmindex.h:429-463                tracyhip_trim_reference_slice
+ *   getReferenceSlice (indexed genome)     fmindex.h:236-326                tracyhip_seed_traces
  *
  * Conventions
  *   - plain C types only; the caller owns every buffer passed in; nothing is retained after return.
@@ -116,6 +117,8 @@ int tracyhip_synchronize(tracyhip_ctx* ctx);
      no_band, no_band16, no_front, no_prefix, no_vote, no_origin, no_subwindow, no_prelim_origin, no_cq, no_fused_walk, no_cont16, no_quads, no_fork, no_decomp_wave, no_af_split, no_front_lists, no_origin_band, sweeps_alone (measurement: the full sweeps of the orientation stage on a device of their own)   "0" / "1"
      band_w  (half width of the certified band of the final alignments; -1 = from the preliminary alignment, 0 = whole matrices)
      ckpt_b  (steps between wavefront checkpoints, 32 .. 1024)      verbose  (one line per pipeline stage on stderr)
+     seed_vote_cap  (tracyhip_seed_traces: votes one trace may collect per strand and pass on the device, 1 .. 2048, default 2048;
+                    a trace with more is DEFERRED to host seeding -- the caller's results stay the same)
      quad_tier_min  (stream-ordered pipelines: traces / alleles from which a pruned sweep gets its narrow first tier; default 32768)
      front_list_min (... from which its later tiers, and the allele prefixes of `tracy decompose`, run over device-side lists of the units
                     that are left instead of skipping the others in place; default 1024)
@@ -364,6 +367,70 @@ typedef struct {
 
 int tracyhip_decompose_traces(tracyhip_ctx* ctx, const tracyhip_decompose_job* job, const tracyhip_params* prm, int mem,
                               const tracyhip_decompose_result* out);
+
+/* ---- k-mer seeding in an indexed genome (getReferenceSlice, fmindex.h:236-326) on the device ----------------------------
+ * The index is tracy_amd/host/seed.hpp's GenomeIndex (tracyhost_genome_view gives its arrays): every k-mer over ACGT of the text is
+ * filed under the smaller of its code and its reverse complement's; the table is sorted by bucket (the low bucket_bits bits of that
+ * code), code, strand part, position; dir[b] .. dir[b + 1] is bucket b's range of the table. */
+typedef struct {
+  uint32_t k;                /* 1 .. 32 */
+  uint32_t bucket_bits;      /* <= min(2k, 24) */
+  const uint64_t* dir;       /* [2^bucket_bits + 1], monotone, dir[0] = 0, last = ntab */
+  const uint64_t* tab;       /* [2 * ntab]: {code, pos} pairs; bit 63 of pos set: the text holds the code's reverse complement there */
+  uint64_t ntab;
+  const char* text;          /* the upper-cased contigs joined by '\n' */
+  uint64_t text_len;
+  const uint64_t* starts;    /* [ncontigs] offset of contig i in the text */
+  const uint32_t* lengths;   /* [ncontigs] */
+  uint32_t ncontigs;         /* >= 1 */
+  const uint32_t* contig_id; /* [ncontigs] or NULL (= identity): the contig index reported for a hit in contig i (the first contig
+                                with contig i's name: tracyhost_seed_batch's convention for duplicate names) */
+} tracyhip_genome_desc;
+typedef struct tracyhip_genome tracyhip_genome;
+/* Checks a descriptor on the host (no device is touched): k in 1 .. 32, bucket_bits <= min(2k, 24), a monotone directory from 0 to
+ * ntab, contigs inside the text in order, contig_id entries < ncontigs.  TRACYHIP_ERR_ARG (with the reason) otherwise. */
+int tracyhip_genome_validate(const tracyhip_genome_desc* desc);
+/* validates (tracyhip_genome_validate), then copies the arrays once into device memory owned by the handle (all HOST pointers) */
+int tracyhip_genome_upload(tracyhip_ctx* ctx, const tracyhip_genome_desc* desc, tracyhip_genome** genome);
+int tracyhip_genome_free(tracyhip_genome* genome);
+/* device bytes the handle holds */
+uint64_t tracyhip_genome_bytes(const tracyhip_genome* genome);
+
+#define TRACYHIP_SEED_UNANCHORED 0
+#define TRACYHIP_SEED_ANCHORED 1
+#define TRACYHIP_SEED_DEFERRED 2 /* outside what the device answers: seed the trace on the host (tracyhost_seed_batch) */
+
+/* the argument meanings of tracyhost_seed_batch; each value is truncated to 16 bits as SageConfig holds it */
+typedef struct {
+  uint32_t trim_left;
+  uint32_t trim_right;
+  uint32_t kmer;             /* must be the index's k (every trace is deferred otherwise) */
+  uint32_t min_support;
+  uint32_t maxindel;
+} tracyhip_seed_params;
+
+/* per trace t: status[t] (TRACYHIP_SEED_*); for anchored traces forward, kmersupport, pos (window start in the contig), contig and
+ * the ORIENTED window, slice_len[t] bytes at slices + t * slice_cap (at most slice_cap) -- the layout tracyhost_seed_batch fills.
+ * status, forward, kmersupport, pos, contig and slice_len are HOST arrays; slices is payload (where `mem` says).  Traces that are not
+ * anchored get status and slice_len = 0 only; the other fields (and window bytes past slice_len) are left as they were. */
+typedef struct {
+  int32_t* status;
+  uint8_t* forward;
+  uint32_t* kmersupport;
+  uint32_t* pos;
+  uint32_t* contig;
+  uint32_t* slice_len;
+  uint8_t* slices;
+  uint64_t slice_cap;
+} tracyhip_seed_result;
+
+/* getReferenceSlice (fmindex.h:236-326, the one-pass form of tracy_amd/host/seed.hpp scanBothStrands) for a batch of consensus strings
+ * (kind CHAR; offsets / lengths HOST arrays, bytes where `mem` says).  Results are identical to tracyhost_seed_batch's for every trace
+ * the device answers.  DEFERRED: letters other than A C G T N among the windows, |consensus| + k >= 65536, a trim shorter than k - 1,
+ * a consensus shorter than a trim, a kmer that is not the index's, or more votes on one strand in one pass than the option
+ * seed_vote_cap allows (default and maximum 2048: the vote lists live in LDS). */
+int tracyhip_seed_traces(tracyhip_ctx* ctx, const tracyhip_genome* genome, const tracyhip_seqset* consensus, const tracyhip_seed_params* prm,
+                         int mem, const tracyhip_seed_result* out);
 
 /* ---- asynchronous forms (SURVEY.md 8b "Threading": synchronous by default with an async variant) ---------------------
  * Same arguments and results as the call without the suffix; the call returns as soon as the work is queued on the

@@ -708,3 +708,51 @@ Context.decompose_traces = _decompose_traces
 Context.align_banded = _align_banded
 Group.align_traces = _align_traces
 Group.decompose_traces = _decompose_traces
+
+
+# ---- k-mer seeding in an indexed genome on the device (tracyhip_genome_upload / tracyhip_seed_traces) ----------------------------
+SEED_UNANCHORED, SEED_ANCHORED, SEED_DEFERRED = 0, 1, 2
+
+
+class GenomeDesc(C.Structure):
+    _fields_ = [("k", C.c_uint32), ("bucket_bits", C.c_uint32), ("dir", C.c_void_p), ("tab", C.c_void_p), ("ntab", C.c_uint64),
+                ("text", C.c_void_p), ("text_len", C.c_uint64), ("starts", C.c_void_p), ("lengths", C.c_void_p), ("ncontigs", C.c_uint32),
+                ("contig_id", C.c_void_p)]
+
+
+class SeedParams(C.Structure):
+    _fields_ = [("trim_left", C.c_uint32), ("trim_right", C.c_uint32), ("kmer", C.c_uint32), ("min_support", C.c_uint32),
+                ("maxindel", C.c_uint32)]
+
+
+class SeedResult(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("forward", C.c_void_p), ("kmersupport", C.c_void_p), ("pos", C.c_void_p), ("contig", C.c_void_p),
+                ("slice_len", C.c_void_p), ("slices", C.c_void_p), ("slice_cap", C.c_uint64)]
+
+
+def genome_validate(desc):
+    """tracyhip_genome_validate: host-side check of an index descriptor (no device needed); raises TracyHipError"""
+    _check(lib().tracyhip_genome_validate(C.byref(desc)))
+
+
+def genome_upload(ctx, desc):
+    """tracyhip_genome_upload -> handle (c_void_p); the descriptor's arrays are copied once"""
+    h = C.c_void_p()
+    _check(lib().tracyhip_genome_upload(ctx._h, C.byref(desc), C.byref(h)))
+    return h
+
+
+def genome_free(h):
+    if h:
+        lib().tracyhip_genome_free(h)
+
+
+def genome_bytes(h):
+    fn = lib().tracyhip_genome_bytes
+    fn.restype = C.c_uint64
+    return int(fn(h))
+
+
+def seed_traces(ctx, genome_h, seqset, params, mem, result):
+    """tracyhip_seed_traces on prepared structs"""
+    _check(lib().tracyhip_seed_traces(ctx._h, genome_h, C.byref(seqset), C.byref(params), int(mem), C.byref(result)))

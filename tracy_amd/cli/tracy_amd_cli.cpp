@@ -13,8 +13,8 @@
 // CPU fallback: without a GPU the command fails with the library's error text.
 // Both commands also take an indexed genome (gzip-compressed multi-FASTA): the trace is anchored by k-mer votes
 // (seed.hpp, fmindex.h:173-326) and aligned against the window around the hit.
-// Not built: --annotate (needs the network), BCF output (no htslib).  Variants (-v) are written as
-// VCF text because htslib (BCF) is not available.
+// Not built: --annotate (needs the network).  Variants (-v) are written as VCF text and as <prefix>.bcf (+ .csi) by
+// bcf_out.hpp, a writer of this repository's own (no htslib).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>

@@ -293,6 +293,12 @@ bool knobs_set(CtxKnobs& k, const char* name, const char* value) {
     k.front_list_min = (uint32_t)std::min<long>(v, 0x7fffffffl);
     return true;
   }
+  if (same_name(name, "seed_vote_cap")) {
+    const long v = atol(value);
+    if (v < 1 || v > 2048) return false;
+    k.seed_vote_cap = (uint32_t)v;
+    return true;
+  }
   if (same_name(name, "ckpt_b")) {
     const long v = atol(value);
     if (v < 32 || v > 1024) return false;
@@ -318,6 +324,7 @@ void knobs_from_env(CtxKnobs& k) {
   if (const char* e = getenv("TRACYHIP_CKPT_B")) knobs_set(k, "ckpt_b", e);
   if (const char* e = getenv("TRACYHIP_QUAD_TIER_MIN")) knobs_set(k, "quad_tier_min", e);
   if (const char* e = getenv("TRACYHIP_FRONT_LIST_MIN")) knobs_set(k, "front_list_min", e);
+  if (const char* e = getenv("TRACYHIP_SEED_VOTE_CAP")) knobs_set(k, "seed_vote_cap", e);
 }
 std::string knobs_describe(const CtxKnobs& k) {
   std::string s;
@@ -326,6 +333,7 @@ std::string knobs_describe(const CtxKnobs& k) {
   s += "ckpt_b=" + std::to_string(k.ckpt_b) + "\n";
   s += "quad_tier_min=" + std::to_string(k.quad_tier_min) + "\n";
   s += "front_list_min=" + std::to_string(k.front_list_min) + "\n";
+  s += "seed_vote_cap=" + std::to_string(k.seed_vote_cap) + "\n";
   s += "host_threads=" + std::to_string(host_pool_threads()) + "\n";
   return s;
 }

@@ -69,6 +69,7 @@ struct CtxKnobs {
                                   // 0 = whole matrices, else [1, 4096]
   uint32_t ckpt_b = 256;
   uint32_t front_list_min = 1024; // stream-ordered pipelines: units from which the later tiers of a pruned sweep (and the allele prefixes) run over device-side lists
+  uint32_t seed_vote_cap = 2048;  // tracyhip_seed_traces: votes per trace, strand and pass held in LDS (seed.hip); more: the trace is deferred
   uint32_t quad_tier_min = 32768;  // stream-ordered pipelines: units (traces, or alleles) from which the pruned sweeps get their narrow quad tier          // steps between wavefront checkpoints [32, 1024]
 };
 void knobs_from_env(CtxKnobs& k);
@@ -122,6 +123,7 @@ struct tracyhip_ctx {
   tracyhip::B16Fork b16_fork;                  // side streams of the band stages (stream.hip band_stage), created with the context
   bool b16_fork_ok = false;
   tracyhip::DevBuf d_stream;                   // everything the stream-ordered pipelines keep on the device between their stages (stream.hip)
+  tracyhip::DevBuf d_seed[3];                  // tracyhip_seed_traces (seed.hip): per-trace inputs / results, staged consensus, staged windows
   hipError_t ensure_codes(size_t bytes, hipStream_t st) {
     hipError_t e = d_codes.ensure(bytes + 2 * tracyhip::kCodePad);
     if (e != hipSuccess) return e;
@@ -182,6 +184,7 @@ struct tracyhip_ctx {
     d_front.release();
     d_pre.release();
     d_stream.release();
+    for (auto& b : d_seed) b.release();
     h_desc.release();
     h_off.release();
     h_tmp.release();

@@ -321,6 +321,23 @@ class GenomeIndex {
     hi = i;
   }
   uint64_t position(std::size_t i) const { return tab_[i].pos & ~kFlipped; }
+  // read-only view of the index as its arrays (device upload, tracyhip_genome_upload): the table as {code, pos} pairs of u64 (bit 63 of
+  // pos: the flipped part of a run), the directory of 2^bucket_bits + 1 table indices, the text, the contig table
+  struct View {
+    uint32_t k, bucket_bits;
+    const uint64_t* bkt;
+    const uint64_t* tab;
+    uint64_t ntab;
+    const char* text;
+    uint64_t text_len;
+    const uint64_t* starts;
+    const uint32_t* lengths;
+    uint32_t ncontigs;
+  };
+  View view() const {
+    return View{k, bucket_bits_, bkt_, reinterpret_cast<const uint64_t*>(tab_), (uint64_t)ntab_, text.p, (uint64_t)text.n, starts.data(), lengths.data(),
+                (uint32_t)names.size()};
+  }
   // cache warm-up for a batch of look-ups: the directory slot first, then (once that is in cache) the table run
   void prefetch_slot(uint64_t code) const { prefetch_slot_key(key_of(code).code); }
   void prefetch_run(uint64_t code) const { prefetch_run_key(key_of(code).code); }

@@ -361,6 +361,31 @@ int tracyhost_genome_save(const void* h, const char* path) { return static_cast<
 void tracyhost_genome_free(void* h) { delete static_cast<GenomeIndex*>(h); }
 uint32_t tracyhost_genome_contigs(const void* h) { return (uint32_t)static_cast<const GenomeIndex*>(h)->names.size(); }
 uint64_t tracyhost_genome_count(const void* h, const char* pat, size_t n) { return static_cast<const GenomeIndex*>(h)->count(std::string(pat, n)); }
+// the index's arrays (GenomeIndex::view) for a device upload: the layout of tracyhip_genome_desc (include/tracy_hip.h), pointers into the
+// index (valid while it is open); an in-memory build and a mapped index file alike.  Returns -1 when the index has no table.
+struct tracyhost_genome_view_t {
+  uint32_t k, bucket_bits;
+  const uint64_t* bkt;
+  const uint64_t* tab;
+  uint64_t ntab;
+  const char* text;
+  uint64_t text_len;
+  const uint64_t* starts;
+  const uint32_t* lengths;
+  uint32_t ncontigs;
+};
+int tracyhost_genome_view(const void* h, tracyhost_genome_view_t* out) {
+  const GenomeIndex* g = static_cast<const GenomeIndex*>(h);
+  if (!g || !out || !g->has_table()) return -1;
+  const GenomeIndex::View v = g->view();
+  *out = tracyhost_genome_view_t{v.k, v.bucket_bits, v.bkt, v.tab, v.ntab, v.text, v.text_len, v.starts, v.lengths, v.ncontigs};
+  return 0;
+}
+// name of contig i (NUL-terminated, valid while the index is open)
+const char* tracyhost_genome_contig_name(const void* h, uint32_t i) {
+  const GenomeIndex* g = static_cast<const GenomeIndex*>(h);
+  return i < g->names.size() ? g->names[i].c_str() : nullptr;
+}
 
 // getReferenceSlice for a batch of consensus strings (trace t: consensus + cons_off[t], cons_len[t] bytes), one
 // thread per stripe of traces.  Per trace: status 1 = anchored, 0 = not; forward, kmersupport, pos (window start
