@@ -395,6 +395,18 @@ int tracyhip_genome_upload(tracyhip_ctx* ctx, const tracyhip_genome_desc* desc, 
 int tracyhip_genome_free(tracyhip_genome* genome);
 /* device bytes the handle holds */
 uint64_t tracyhip_genome_bytes(const tracyhip_genome* genome);
+/* Checks a descriptor a table is to be built from, on the host (no device is touched): k in 1 .. 32, bucket_bits <= min(2k, 24), dir and
+ * tab NULL and ntab 0, contigs inside the text in order, contig_id entries < ncontigs.  TRACYHIP_ERR_ARG (with the reason) otherwise. */
+int tracyhip_genome_validate_text(const tracyhip_genome_desc* desc);
+/* GenomeIndex::build on the device: validates (tracyhip_genome_validate_text), copies the text and contig table once, then builds dir and
+ * tab on the device of `ctx` -- word for word what the host builds for the same text, k and bucket_bits (tracyhost_default_bucket_bits(k)
+ * is the host's choice).  The handle is one tracyhip_genome_upload would give: tracyhip_seed_traces, _bytes and _free take it.  Device
+ * temporaries are freed before the call returns; TRACYHIP_ERR_OOM when device memory runs out (nothing is left allocated). */
+int tracyhip_genome_build(tracyhip_ctx* ctx, const tracyhip_genome_desc* desc, tracyhip_genome** genome);
+/* table entries of a device genome (built or uploaded) */
+int tracyhip_genome_ntab(const tracyhip_genome* genome, uint64_t* ntab);
+/* copies the device directory and table to HOST arrays in the tracyhip_genome_desc layout: dir [2^bucket_bits + 1], tab [2 * ntab] */
+int tracyhip_genome_download(const tracyhip_genome* genome, uint64_t* dir, uint64_t* tab);
 
 #define TRACYHIP_SEED_UNANCHORED 0
 #define TRACYHIP_SEED_ANCHORED 1

@@ -756,3 +756,29 @@ def genome_bytes(h):
 def seed_traces(ctx, genome_h, seqset, params, mem, result):
     """tracyhip_seed_traces on prepared structs"""
     _check(lib().tracyhip_seed_traces(ctx._h, genome_h, C.byref(seqset), C.byref(params), int(mem), C.byref(result)))
+
+
+def genome_validate_text(desc):
+    """tracyhip_genome_validate_text: host-side check of a descriptor a table is to be built from (no device needed); raises TracyHipError"""
+    _check(lib().tracyhip_genome_validate_text(C.byref(desc)))
+
+
+def genome_build(ctx, desc):
+    """tracyhip_genome_build -> handle (c_void_p): the text and contigs copied once, dir and tab built on the device"""
+    h = C.c_void_p()
+    _check(lib().tracyhip_genome_build(ctx._h, C.byref(desc), C.byref(h)))
+    return h
+
+
+def genome_ntab(h):
+    n = C.c_uint64()
+    _check(lib().tracyhip_genome_ntab(h, C.byref(n)))
+    return int(n.value)
+
+
+def genome_download(h, bucket_bits):
+    """tracyhip_genome_download -> (dir uint64 [2^bits + 1], tab uint64 [ntab][2]) as numpy arrays"""
+    d = np.empty((1 << bucket_bits) + 1, dtype=np.uint64)
+    t = np.empty((genome_ntab(h), 2), dtype=np.uint64)
+    _check(lib().tracyhip_genome_download(h, C.c_void_p(d.ctypes.data), C.c_void_p(t.ctypes.data if t.size else 0)))
+    return d, t

@@ -1470,10 +1470,44 @@ int basecall_main(int argc, char** argv) {
   return 0;
 }
 
+// the table of a loaded genome built on GPU `device` (tracyhip_genome_build) and copied back: the same table as g.build(kmer)
+bool build_index_on_device(GenomeIndex& g, uint32_t kmer, int device) {
+  tracyhip_ctx* ctx = nullptr;
+  tracyhip_genome* dg = nullptr;
+  auto fail = [&](const char* what) {
+    std::cerr << "tracy_amd: " << what << ": " << tracyhip_last_error() << std::endl;
+    if (dg) tracyhip_genome_free(dg);
+    if (ctx) tracyhip_destroy(ctx);
+    return false;
+  };
+  if (tracyhip_create(device, &ctx) != TRACYHIP_OK) return fail("cannot open the device");
+  const GenomeIndex::View v = g.view();
+  tracyhip_genome_desc d{};  // (contig_id NULL: the handle only builds the table here, it seeds nothing)
+  d.k = kmer;
+  d.bucket_bits = GenomeIndex::default_bucket_bits(kmer);
+  d.text = v.text; d.text_len = v.text_len;
+  d.starts = v.starts; d.lengths = v.lengths; d.ncontigs = v.ncontigs;
+  if (tracyhip_genome_build(ctx, &d, &dg) != TRACYHIP_OK) return fail("device index build failed");
+  uint64_t ntab = 0;
+  if (tracyhip_genome_ntab(dg, &ntab) != TRACYHIP_OK) return fail("device index build failed");
+  std::vector<uint64_t> dir(((std::size_t)1 << d.bucket_bits) + 1), tab(2 * (std::size_t)ntab);
+  if (tracyhip_genome_download(dg, dir.data(), tab.data()) != TRACYHIP_OK) return fail("cannot copy the index back");
+  tracyhip_genome_free(dg);
+  dg = nullptr;
+  tracyhip_destroy(ctx);
+  ctx = nullptr;
+  if (!g.adopt(kmer, d.bucket_bits, dir.data(), tab.data(), (std::size_t)ntab)) {
+    std::cerr << "tracy_amd: the device-built index was refused" << std::endl;
+    return false;
+  }
+  return true;
+}
+
 // ---- `tracy index` (index.h:36-124): the genome's k-mer table on disk ---------------------------------------------------
 int index_main(int argc, char** argv) {
   std::string outfile, genome;
   uint32_t kmer = 15;
+  int device = -1;  // -d: build the table on this GPU (the same file as the host build)
   bool bad = false;
   for (int i = 1; i < argc && !bad; ++i) {
     const std::string a = argv[i];
@@ -1481,6 +1515,13 @@ int index_main(int argc, char** argv) {
     std::string v;
     if (a == "-o" || a == "--output") value(outfile);
     else if (a == "-k" || a == "--kmer") { value(v); kmer = (uint32_t)std::atoi(v.c_str()); }
+    else if (a == "-d" || a == "--device") {
+      value(v);
+      char* end = nullptr;
+      const long d = std::strtol(v.c_str(), &end, 10);
+      if (v.empty() || *end != '\0' || d < 0 || d > 1024) bad = true;
+      else device = (int)d;
+    }
     else if (a == "-?" || a == "--help") bad = true;
     else if (!a.empty() && a[0] == '-') bad = true;
     else genome = a;
@@ -1489,6 +1530,7 @@ int index_main(int argc, char** argv) {
     std::cout << "Usage: tracy index [OPTIONS] genome.fa.gz" << std::endl;
     std::cout << "  -o [ --output ] arg      output file (default: <genome>.tidx, found by align / decompose -r <genome>)" << std::endl;
     std::cout << "  -k [ --kmer ] arg (=15)  k-mer size of the table (align / decompose -k must match)" << std::endl;
+    std::cout << "  -d [ --device ] arg      build the table on this GPU (ordinal); the file is the same as without -d" << std::endl;
     return -1;
   }
   if (!regular_nonempty(genome)) {
@@ -1504,7 +1546,8 @@ int index_main(int argc, char** argv) {
     return 1;
   }
   std::cout << stamp() << "Create index" << std::endl;
-  g.build(kmer);
+  if (device < 0) g.build(kmer);
+  else if (!build_index_on_device(g, kmer, device)) return 1;
   if (!g.save(outfile)) {
     std::cerr << "Cannot write " << outfile << std::endl;
     return 1;
@@ -1531,6 +1574,6 @@ int main(int argc, char** argv) {
   std::cout << "       tracy_amd_cli assemble [OPTIONS] [-r reference.fa] trace1.ab1 trace2.ab1 ..." << std::endl;
   std::cout << "       tracy_amd_cli basecall [OPTIONS] trace.ab1" << std::endl;
   std::cout << "       tracy_amd_cli consensus [OPTIONS] trace1.ab1 trace2.ab1" << std::endl;
-  std::cout << "       tracy_amd_cli index [-o genome.tidx] [-k 15] genome.fa.gz" << std::endl;
+  std::cout << "       tracy_amd_cli index [-o genome.tidx] [-k 15] [-d 0] genome.fa.gz" << std::endl;
   return argc < 2 ? 0 : 1;
 }

@@ -139,5 +139,25 @@ inline int seed_validate(const tracyhip_genome_desc* d, char* why, size_t cap) {
   return TRACYHIP_OK;
 }
 
+// The host-side check of a descriptor a table is to be BUILT from (tracyhip_genome_validate_text): the k / bucket_bits and contig rules of
+// seed_validate, no directory or table given.
+inline int seed_validate_text(const tracyhip_genome_desc* d, char* why, size_t cap) {
+  auto fail = [&](const char* m) { std::snprintf(why, cap, "%s", m); return TRACYHIP_ERR_ARG; };
+  if (!d) return fail("null genome descriptor");
+  if (d->k < 1 || d->k > 32) return fail("k must be 1 .. 32");
+  if (d->bucket_bits > 24 || d->bucket_bits > 2 * d->k) return fail("bucket_bits must be <= min(2k, 24)");
+  if (d->dir || d->tab || d->ntab) return fail("dir, tab and ntab must be NULL / 0: the table is built");
+  if (!d->text || !d->starts || !d->lengths) return fail("null array in the genome descriptor");
+  if (d->ncontigs < 1) return fail("a genome needs at least one contig");
+  uint64_t end = 0;
+  for (uint32_t i = 0; i < d->ncontigs; ++i) {
+    if (d->starts[i] < end || d->starts[i] > d->text_len || d->lengths[i] > d->text_len - d->starts[i])
+      return fail("contig outside the text (or out of order)");
+    end = d->starts[i] + d->lengths[i];
+    if (d->contig_id && d->contig_id[i] >= d->ncontigs) return fail("contig_id out of range");
+  }
+  return TRACYHIP_OK;
+}
+
 }  // namespace tracyhip
 #endif

@@ -1,6 +1,7 @@
 // seed.hip -- tracyhip_genome_upload / tracyhip_seed_traces: k-mer seeding of a batch of traces in an indexed genome on the device
 // (getReferenceSlice, fmindex.h:236-326), bit-identical to the host's one-pass form (tracy_amd/host/seed.hpp scanBothStrands +
-// getReferenceSlice) for every trace it answers; the rest is DEFERRED to the host.
+// getReferenceSlice) for every trace it answers; the rest is DEFERRED to the host.  tracyhip_genome_build: the same handle with the
+// table built on the device from the text (index_build.hip).
 //
 // One workgroup of 256 threads per trace.  A look-up is two dependent random reads into a gigabyte of directory + table; the
 // look-ups of a trace are independent, so every lane takes four windows at once: their keys, then their four directory loads,
@@ -16,6 +17,7 @@
 
 #include "../../include/tracy_hip.h"
 #include "capi_internal.h"
+#include "index_build.h"
 #include "seed.h"
 
 using namespace tracyhip;
@@ -285,6 +287,21 @@ hipError_t upload(tracyhip_genome* h, const T* src, uint64_t count, const T** ds
   return e;
 }
 
+// the text and contig table of a descriptor, plus the cumulative length + 1 offsets and the contig_id map (identity when NULL)
+hipError_t upload_text(tracyhip_genome* h, const tracyhip_genome_desc* d, const uint8_t** text) {
+  std::vector<int64_t> cum(d->ncontigs, 0);
+  for (uint32_t i = 1; i < d->ncontigs; ++i) cum[i] = cum[i - 1] + (int64_t)d->lengths[i - 1] + 1;
+  std::vector<uint32_t> cid(d->ncontigs);
+  for (uint32_t i = 0; i < d->ncontigs; ++i) cid[i] = d->contig_id ? d->contig_id[i] : i;
+  SeedGenome& g = h->g;
+  hipError_t e = upload(h, reinterpret_cast<const uint8_t*>(d->text), d->text_len, text);
+  if (e == hipSuccess) e = upload(h, cum.data(), cum.size(), &g.cum);
+  if (e == hipSuccess) e = upload(h, d->starts, d->ncontigs, &g.starts);
+  if (e == hipSuccess) e = upload(h, d->lengths, d->ncontigs, &g.lengths);
+  if (e == hipSuccess) e = upload(h, cid.data(), cid.size(), &g.contig_id);
+  return e;
+}
+
 }  // namespace
 
 extern "C" {
@@ -315,19 +332,11 @@ int tracyhip_genome_upload(tracyhip_ctx* ctx, const tracyhip_genome_desc* d, tra
   tracyhip_genome* h = new tracyhip_genome();
   h->device = ctx->device;
   h->k = d->k; h->bucket_bits = d->bucket_bits; h->nc = d->ncontigs; h->ntab = d->ntab; h->text_len = d->text_len;
-  std::vector<int64_t> cum(d->ncontigs, 0);
-  for (uint32_t i = 1; i < d->ncontigs; ++i) cum[i] = cum[i - 1] + (int64_t)d->lengths[i - 1] + 1;
-  std::vector<uint32_t> cid(d->ncontigs);
-  for (uint32_t i = 0; i < d->ncontigs; ++i) cid[i] = d->contig_id ? d->contig_id[i] : i;
   SeedGenome& g = h->g;
   const uint8_t* text = nullptr;
   hipError_t e = upload(h, d->dir, (1ull << d->bucket_bits) + 1, &g.dir);
   if (e == hipSuccess) e = upload(h, d->tab, 2 * d->ntab, &g.tab);
-  if (e == hipSuccess) e = upload(h, reinterpret_cast<const uint8_t*>(d->text), d->text_len, &text);
-  if (e == hipSuccess) e = upload(h, cum.data(), cum.size(), &g.cum);
-  if (e == hipSuccess) e = upload(h, d->starts, d->ncontigs, &g.starts);
-  if (e == hipSuccess) e = upload(h, d->lengths, d->ncontigs, &g.lengths);
-  if (e == hipSuccess) e = upload(h, cid.data(), cid.size(), &g.contig_id);
+  if (e == hipSuccess) e = upload_text(h, d, &text);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     tracyhip_genome_free(h);
@@ -340,6 +349,64 @@ int tracyhip_genome_upload(tracyhip_ctx* ctx, const tracyhip_genome_desc* d, tra
   g.k = d->k;
   g.bucket_bits = d->bucket_bits;
   *out = h;
+  return TRACYHIP_OK;
+}
+
+int tracyhip_genome_validate_text(const tracyhip_genome_desc* desc) {
+  char why[256];
+  const int rc = seed_validate_text(desc, why, sizeof(why));
+  return rc == TRACYHIP_OK ? rc : set_error(rc, "tracyhip_genome_build: %s", why);
+}
+
+int tracyhip_genome_build(tracyhip_ctx* ctx, const tracyhip_genome_desc* d, tracyhip_genome** out) {
+  if (!out) return set_error(TRACYHIP_ERR_ARG, "null out pointer");
+  *out = nullptr;
+  const int rc = tracyhip_genome_validate_text(d);  // before any device call
+  if (rc != TRACYHIP_OK) return rc;
+  const int rb = ctx_begin(ctx);
+  if (rb != TRACYHIP_OK) return rb;
+  tracyhip_genome* h = new tracyhip_genome();
+  h->device = ctx->device;
+  h->k = d->k; h->bucket_bits = d->bucket_bits; h->nc = d->ncontigs; h->text_len = d->text_len;
+  SeedGenome& g = h->g;
+  const uint8_t* text = nullptr;
+  const uint64_t ndir = (1ull << d->bucket_bits) + 1;
+  uint64_t* dir = nullptr;
+  hipError_t e = hipMalloc(&dir, ndir * sizeof(uint64_t));
+  if (e == hipSuccess) { h->mem.push_back(dir); h->bytes += ndir * sizeof(uint64_t); }
+  if (e == hipSuccess) e = upload_text(h, d, &text);
+  uint64_t* tab = nullptr;
+  uint64_t ntab = 0;
+  if (e == hipSuccess) e = index_build(ctx->stream, text, d->text_len, d->k, d->bucket_bits, dir, &tab, &ntab);
+  if (e == hipSuccess) { h->mem.push_back(tab); h->bytes += std::max<uint64_t>(ntab, 1) * 2 * sizeof(uint64_t); }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    tracyhip_genome_free(h);
+    return set_error(e == hipErrorOutOfMemory ? TRACYHIP_ERR_OOM : TRACYHIP_ERR_HIP, "tracyhip_genome_build: %s", hipGetErrorString(e));
+  }
+  g.dir = dir;
+  g.tab = tab;
+  g.text = text;
+  g.ntab = h->ntab = ntab;
+  g.text_len = d->text_len;
+  g.nc = d->ncontigs;
+  g.k = d->k;
+  g.bucket_bits = d->bucket_bits;
+  *out = h;
+  return TRACYHIP_OK;
+}
+
+int tracyhip_genome_ntab(const tracyhip_genome* h, uint64_t* ntab) {
+  if (!h || !ntab) return set_error(TRACYHIP_ERR_ARG, "null genome / ntab");
+  *ntab = h->ntab;
+  return TRACYHIP_OK;
+}
+
+int tracyhip_genome_download(const tracyhip_genome* h, uint64_t* dir, uint64_t* tab) {
+  if (!h || !dir || (h->ntab && !tab)) return set_error(TRACYHIP_ERR_ARG, "null genome / dir / tab");
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipMemcpy(dir, h->g.dir, ((1ull << h->bucket_bits) + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (h->ntab) HIP_TRY(hipMemcpy(tab, h->g.tab, h->ntab * 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return TRACYHIP_OK;
 }
 

@@ -154,21 +154,40 @@ class GenomeIndex {
     // directory size: 2^24 slots = 128 MB (three table entries per slot for a 50 Mb genome: one line of the table per look-up, but the
     // directory itself misses every cache); TRACY_AMD_SEED_BUCKET_BITS (development knob, read when an index is BUILT) trades longer
     // buckets -- consecutive lines of the table -- for a directory an L3 holds
-    bucket_bits_ = std::min<uint32_t>(2 * k, 24);
-    if (const char* e = std::getenv("TRACY_AMD_SEED_BUCKET_BITS")) { const long v = std::atol(e); if (v >= 8 && v <= 24) bucket_bits_ = std::min<uint32_t>(2 * k, (uint32_t)v); }
+    bucket_bits_ = default_bucket_bits(k);
     sort_table(nthreads);
     bucket_.assign(((std::size_t)1 << bucket_bits_) + 1, 0);
     for (Entry const& e : table_) ++bucket_[slot_of(e.code) + 1];
     for (std::size_t b = 1; b < bucket_.size(); ++b) bucket_[b] += bucket_[b - 1];
     tab_ = table_.data(); ntab_ = table_.size(); bkt_ = bucket_.data();
-#ifdef MADV_HUGEPAGE
-    auto advise = [](const void* p, std::size_t bytes) {  // (the heap blocks of the two vectors: whole 2 MB pages inside them)
-      const uintptr_t huge = (uintptr_t)2 << 20, lo = ((uintptr_t)p + huge - 1) & ~(huge - 1), hi = ((uintptr_t)p + bytes) & ~(huge - 1);
-      if (hi > lo) madvise(reinterpret_cast<void*>(lo), hi - lo, MADV_HUGEPAGE);
-    };
-    advise(tab_, ntab_ * sizeof(Entry));
-    advise(bkt_, bucket_.size() * sizeof(uint64_t));
-#endif
+    advise_owned();
+  }
+  // the directory size build() picks for k-mers of k letters (min(2k, 24), or the TRACY_AMD_SEED_BUCKET_BITS knob within 8 .. 24): one rule
+  // for host and device builds
+  static uint32_t default_bucket_bits(uint32_t kmer) {
+    uint32_t bits = std::min<uint32_t>(2 * kmer, 24);
+    if (const char* e = std::getenv("TRACY_AMD_SEED_BUCKET_BITS")) { const long v = std::atol(e); if (v >= 8 && v <= 24) bits = std::min<uint32_t>(2 * kmer, (uint32_t)v); }
+    return bits;
+  }
+  // A table built elsewhere (tracyhip_genome_build + tracyhip_genome_download) over this index's text, copied into the owned vectors:
+  // dir [2^bucket_bits + 1], tab [2 * ntab] ({code, pos} pairs) in build()'s layout.  view(), save(), count() and seeding then work as
+  // after build().  The text must be owned (load(), not a mapped index file).
+  bool adopt(uint32_t kmer, uint32_t bits, const uint64_t* dir, const uint64_t* tab, std::size_t ntab) {
+    if (kmer == 0 || kmer > 32 || bits > 24 || bits > 2 * kmer || map_ || text.p != owned_text_.data() || !dir || (ntab && !tab)) return false;
+    const std::size_t nb = (std::size_t)1 << bits;
+    if (dir[0] != 0 || dir[nb] != ntab) return false;
+    for (std::size_t b = 0; b < nb; ++b)
+      if (dir[b] > dir[b + 1]) return false;
+    k = kmer;
+    bucket_bits_ = bits;
+    owned_table_.clear();
+    owned_table_.reserve(std::max<std::size_t>(ntab, 1));  // (a table without entries still is one: build() reserves too)
+    owned_table_.resize(ntab);
+    if (ntab) std::memcpy(owned_table_.data(), tab, ntab * sizeof(Entry));
+    owned_bucket_.assign(dir, dir + nb + 1);
+    tab_ = owned_table_.data(); ntab_ = owned_table_.size(); bkt_ = owned_bucket_.data();
+    advise_owned();
+    return true;
   }
 
   // ---- persistence: `tracy index` (index.h:79-124) -------------------------------------------------------------
@@ -443,6 +462,17 @@ class GenomeIndex {
     map_ = nullptr; map_bytes_ = 0;
     if (text.p != owned_text_.data()) { text.p = nullptr; text.n = 0; }
     tab_ = nullptr; ntab_ = 0; bkt_ = nullptr;
+  }
+
+  void advise_owned() {
+#ifdef MADV_HUGEPAGE
+    auto advise = [](const void* p, std::size_t bytes) {  // (the heap blocks of the two vectors: whole 2 MB pages inside them)
+      const uintptr_t huge = (uintptr_t)2 << 20, lo = ((uintptr_t)p + huge - 1) & ~(huge - 1), hi = ((uintptr_t)p + bytes) & ~(huge - 1);
+      if (hi > lo) madvise(reinterpret_cast<void*>(lo), hi - lo, MADV_HUGEPAGE);
+    };
+    advise(tab_, ntab_ * sizeof(Entry));
+    advise(bkt_, owned_bucket_.size() * sizeof(uint64_t));
+#endif
   }
 
   static int base2(char c) {  // (a table, not a chain of comparisons: on sequence data every comparison is a coin toss for the branch predictor)

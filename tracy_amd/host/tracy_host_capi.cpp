@@ -381,6 +381,31 @@ int tracyhost_genome_view(const void* h, tracyhost_genome_view_t* out) {
   *out = tracyhost_genome_view_t{v.k, v.bucket_bits, v.bkt, v.tab, v.ntab, v.text, v.text_len, v.starts, v.lengths, v.ncontigs};
   return 0;
 }
+// A (gzip-compressed) multi-FASTA loaded WITHOUT a table: the text and contig table a device build starts from (tracyhost_genome_text,
+// tracyhip_genome_build); tracyhost_genome_adopt then gives it the table.  An index file is refused (NULL).
+void* tracyhost_genome_load(const char* path) {
+  if (GenomeIndex::is_index_file(path) || GenomeIndex::is_stale_index_file(path)) return nullptr;
+  GenomeIndex* g = new GenomeIndex();
+  if (!g->load(path)) { delete g; return nullptr; }
+  return g;
+}
+// the text and contig table of a loaded genome (the view's table fields NULL / 0 when it has no table), for tracyhip_genome_build
+int tracyhost_genome_text(const void* h, tracyhost_genome_view_t* out) {
+  const GenomeIndex* g = static_cast<const GenomeIndex*>(h);
+  if (!g || !out || !g->text.p) return -1;
+  const GenomeIndex::View v = g->view();
+  const bool t = g->has_table();
+  *out = tracyhost_genome_view_t{v.k, t ? v.bucket_bits : 0, t ? v.bkt : nullptr, t ? v.tab : nullptr, t ? v.ntab : 0, v.text, v.text_len,
+                                 v.starts, v.lengths, v.ncontigs};
+  return 0;
+}
+// GenomeIndex::adopt: a table built elsewhere (dir [2^bucket_bits + 1], tab [2 * ntab], the layout tracyhip_genome_download writes) copied
+// into a genome loaded by tracyhost_genome_load.  -1: not a loaded FASTA, or k / bucket_bits / a directory that is not a table's.
+int tracyhost_genome_adopt(void* h, uint32_t kmer, uint32_t bucket_bits, const uint64_t* dir, const uint64_t* tab, uint64_t ntab) {
+  return h && static_cast<GenomeIndex*>(h)->adopt(kmer, bucket_bits, dir, tab, (std::size_t)ntab) ? 0 : -1;
+}
+// the bucket_bits an in-memory build picks for k (min(2k, 24), or the TRACY_AMD_SEED_BUCKET_BITS knob)
+uint32_t tracyhost_default_bucket_bits(uint32_t kmer) { return GenomeIndex::default_bucket_bits(kmer); }
 // name of contig i (NUL-terminated, valid while the index is open)
 const char* tracyhost_genome_contig_name(const void* h, uint32_t i) {
   const GenomeIndex* g = static_cast<const GenomeIndex*>(h);

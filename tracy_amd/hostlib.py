@@ -248,6 +248,16 @@ def genome_desc(view, contig_id=None):
     return d
 
 
+def default_bucket_bits(kmer):
+    """tracyhost_default_bucket_bits: the directory size an in-memory build picks for k (min(2k, 24) or the TRACY_AMD_SEED_BUCKET_BITS knob)"""
+    return int(lib().tracyhost_default_bucket_bits(C.c_uint32(kmer)))
+
+
+def _contig_ids(names):
+    first = {}
+    return np.array([first.setdefault(nm, i) for i, nm in enumerate(names)], dtype=np.uint32)  # duplicate names: the first contig
+
+
 class Genome:
     """indexed genome for k-mer seeding (tracy_amd/host/seed.hpp): plain or gzip-compressed multi-FASTA (table built in memory), or an
     index file written by save() / `tracy_amd_cli index` (mapped read-only; ranks of one node share the page cache's copy)"""
@@ -261,6 +271,46 @@ class Genome:
             raise IOError("tracy_amd: cannot read genome %s" % path)
         self._h = C.c_void_p(h)
         self.kmer = kmer
+
+    @classmethod
+    def from_fasta_on_device(cls, path, ctx, kmer=15, bucket_bits=None, copy_back=True):
+        """the index built on the device of `ctx` (tracyhip_genome_build) from a plain or gzip-compressed multi-FASTA -> (Genome, DeviceGenome).
+        The Genome holds the text; with copy_back it also holds the device-built table (tracyhip_genome_download + tracyhost_genome_adopt:
+        word for word the table Genome(path, kmer) builds), so save(), view() and host seeding work and DeviceGenome seeds DEFERRED traces
+        on the host as usual.  Without copy_back the Genome has no table and DeviceGenome.seed raises on a deferred trace.
+        bucket_bits: None = the host build's choice (tracyhost_default_bucket_bits)."""
+        from . import capi
+        fn = lib().tracyhost_genome_load
+        fn.restype = C.c_void_p
+        h = fn(os.fsencode(path))
+        if not h:
+            raise IOError("tracy_amd: cannot read genome %s (a FASTA file, not an index)" % path)
+        g = cls.__new__(cls)
+        g._h, g.kmer = C.c_void_p(h), kmer
+        bits = default_bucket_bits(kmer) if bucket_bits is None else int(bucket_bits)
+        v = GenomeView()
+        if lib().tracyhost_genome_text(g._h, C.byref(v)) != 0:
+            raise IOError("tracy_amd: genome %s has no text" % path)
+        d = capi.GenomeDesc()
+        d.k, d.bucket_bits, d.dir, d.tab, d.ntab = kmer, bits, None, None, 0
+        d.text, d.text_len, d.starts, d.lengths, d.ncontigs = v.text, v.text_len, v.starts, v.lengths, v.ncontigs
+        cid = _contig_ids(g.contig_names())
+        d.contig_id = cid.ctypes.data
+        dh = capi.genome_build(ctx, d)
+        try:
+            if copy_back:
+                dirs, tab = capi.genome_download(dh, bits)
+                if lib().tracyhost_genome_adopt(g._h, C.c_uint32(kmer), C.c_uint32(bits), C.c_void_p(dirs.ctypes.data),
+                                                C.c_void_p(tab.ctypes.data if tab.size else 0), C.c_uint64(len(tab))) != 0:
+                    raise IOError("tracy_amd: the device-built table was refused")
+        except Exception:
+            capi.genome_free(dh)
+            raise
+        return g, DeviceGenome.wrap(g, ctx, dh, host_table=copy_back)
+
+    def has_table(self):
+        v = GenomeView()
+        return lib().tracyhost_genome_view(self._h, C.byref(v)) == 0
 
     def close(self):
         if self._h:
@@ -372,11 +422,21 @@ class DeviceGenome:
         self._h = None
         self.genome, self.ctx, self.kmer = genome, ctx, genome.kmer
         v = genome.view()
-        names = genome.contig_names()
-        first = {}
-        cid = np.array([first.setdefault(nm, i) for i, nm in enumerate(names)], dtype=np.uint32)  # duplicate names: the first contig
-        self._h = capi.genome_upload(ctx, genome_desc(v, cid))
+        self._h = capi.genome_upload(ctx, genome_desc(v, _contig_ids(genome.contig_names())))
         self.bytes = capi.genome_bytes(self._h)
+        self.host_table = True
+
+    @classmethod
+    def wrap(cls, genome, ctx, handle, host_table=True):
+        """a DeviceGenome over an existing device handle (tracyhip_genome_build / _upload), which it then owns and frees.  host_table: whether
+        `genome` holds the same table, for the host seeding of DEFERRED traces (False: seed() raises on a deferred trace)"""
+        from . import capi
+        self = cls.__new__(cls)
+        self._h = handle
+        self.genome, self.ctx, self.kmer = genome, ctx, genome.kmer
+        self.bytes = capi.genome_bytes(handle)
+        self.host_table = bool(host_table)
+        return self
 
     def close(self):
         if self._h:
@@ -430,6 +490,9 @@ class DeviceGenome:
         capi.seed_traces(self.ctx, self._h, ss, prm, mem, r)
         dfr = np.nonzero(out["status"][:n] == capi.SEED_DEFERRED)[0]
         out["n_deferred"] = int(len(dfr))
+        if len(dfr) and not self.host_table:
+            raise RuntimeError("tracy_amd: %d trace(s) deferred to host seeding, but the genome was built on the device without "
+                               "copy_back: there is no host table to seed them with" % len(dfr))
         if len(dfr):  # the host's answer for exactly those traces
             sub = Genome.pack_consensus([blob[int(packed["offs"][i]):int(packed["offs"][i]) + int(packed["lens"][i])] for i in dfr])
             h = self.genome.seed_packed(sub, trim_left, trim_right, min_support, maxindel, nthreads)
