@@ -23,6 +23,8 @@
  *   allelicFraction                        decompose.h:412-621              tracyhip_allelic_fraction
  *   trimReferenceSlice                     fmindex.h:429-463                tracyhip_trim_reference_slice
  *   getReferenceSlice (indexed genome)     fmindex.h:236-326                tracyhip_seed_traces
+ *   consensus() hot section                consensus.h:501-577              tracyhip_consensus_traces
+ *     gtLetter / pairwiseConsensus         consensus.h:94-171 / 189-238     (consensus_kernel, same call)
  *
  * Conventions
  *   - plain C types only; the caller owns every buffer passed in; nothing is retained after return.
@@ -151,6 +153,8 @@ typedef struct {
   uint32_t allele_repeated[3];
   uint32_t allele_shared_prefix; /* stream-ordered `tracy decompose`: traces whose second allele begins with the same 128 characters as the first and
                                     reads the prefix row kept for it (counted in allele_pruned[1] as well) */
+  uint32_t cons_fixup_columns;   /* tracyhip_consensus_traces: consensus columns the device screen handed to the host gtLetter */
+  uint32_t cons_chunks;          /* ... chunks the batch was cut into to fit the workspace limit */
 } tracyhip_call_stats;
 int tracyhip_last_call_stats(tracyhip_ctx* ctx, tracyhip_call_stats* out);
 const char* tracyhip_last_error(void);
@@ -444,6 +448,49 @@ typedef struct {
 int tracyhip_seed_traces(tracyhip_ctx* ctx, const tracyhip_genome* genome, const tracyhip_seqset* consensus, const tracyhip_seed_params* prm,
                          int mem, const tracyhip_seed_result* out);
 
+/* ---- two-trace consensus (`tracy consensus`, consensus.h:501-577) for a batch of trace pairs -----------------------------
+ * Per pair i:  first[i]  = createProfile(tr1, bc1, ., trimLeft1, trimRight1), the trimmed profile of trace 1
+ *              second[i] = the trimmed FORWARD profile of trace 2; its reverse complement (profile.h:74-90) is made on the device
+ * Steps (all on the device): gotohScore(first, second) and gotohScore(first, revcomp) (gsFwd / gsRev); forward iff gsFwd > gsRev
+ * (consensus.h:545); gotoh(first, chosen) and its _createAlignment rows; numAligned / numMatch and the overlap test (:540-549:
+ * NO_OVERLAP when numAligned < min_overlap or numMatch / numAligned < match_fraction, compared in double); pairwiseConsensus with
+ * gtLetter per column (consensus.h:94-171, 189-238).  Letters and qualities are those of the host gtLetter bit for bit: columns whose
+ * device log10 could decide differently are screened and recomputed by the host before the call returns.
+ * prm: any scoring tracyhip_gotoh_align accepts; the command uses {match, mismatch, go, ge, 1, 1} (AlignConfig<true,true>). */
+#define TRACYHIP_CONS_OK 0
+#define TRACYHIP_CONS_NO_OVERLAP 1
+typedef struct {
+  uint32_t npairs;
+  tracyhip_seqset first;     /* kind PROFILE, pair i = profile i (count >= npairs, every length >= 1) */
+  tracyhip_seqset second;    /* kind PROFILE, forward strand */
+  uint32_t compute_union;    /* ConsensusConfig computeUnion (1: unaligned columns of either trace are kept; 0: -i, intersection) */
+  uint32_t iupac;            /* useIUPAC (-a) */
+  uint32_t min_overlap;      /* minOverlap (-c, default 25) */
+  float match_fraction;      /* matchFraction (-f, default 0.5), promoted to double for the comparison */
+} tracyhip_consensus_job;
+
+/* per-pair arrays and payloads where `mem` says; offset is a HOST array.  Pair i owns m + n elements (m, n = its two profile lengths) of
+ * rows0, rows1, cons and qual from offset[i] on.  A NO_OVERLAP pair gets its scores, rows and counts, and cons_len 0. */
+typedef struct {
+  int32_t* score_fwd;        /* [npairs] gsFwd */
+  int32_t* score_rev;        /* [npairs] gsRev */
+  uint8_t* forward;          /* [npairs] 1 = gsFwd > gsRev */
+  int32_t* score;            /* [npairs] score of gotoh(first, chosen strand) */
+  uint32_t* num_aligned;     /* [npairs] columns with a letter in both rows */
+  uint32_t* num_match;       /* [npairs] ... of which equal */
+  int32_t* status;           /* [npairs] TRACYHIP_CONS_OK / TRACYHIP_CONS_NO_OVERLAP */
+  uint8_t* rows0;            /* _createAlignment row of first, ops_len[i] bytes at offset[i] */
+  uint8_t* rows1;            /* ... of the chosen strand of second */
+  uint32_t* ops_len;         /* [npairs] alignment columns */
+  uint8_t* cons;             /* consensus letters, cons_len[i] bytes at offset[i] */
+  uint16_t* qual;            /* their qualities (gq <= 10000), cons_len[i] values at offset[i] */
+  uint32_t* cons_len;        /* [npairs] */
+  const uint64_t* offset;    /* HOST array */
+} tracyhip_consensus_result;
+
+int tracyhip_consensus_traces(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tracyhip_params* prm, int mem,
+                              const tracyhip_consensus_result* out);
+
 /* ---- asynchronous forms (SURVEY.md 8b "Threading": synchronous by default with an async variant) ---------------------
  * Same arguments and results as the call without the suffix; the call returns as soon as the work is queued on the
  * context.  A context executes its calls in issue order on its own worker thread and stream (the pipelines need the
@@ -459,6 +506,8 @@ int tracyhip_align_traces_async(tracyhip_ctx* ctx, const tracyhip_align_job* job
                                 const tracyhip_align_result* out);
 int tracyhip_decompose_traces_async(tracyhip_ctx* ctx, const tracyhip_decompose_job* job, const tracyhip_params* prm, int mem,
                                     const tracyhip_decompose_result* out);
+int tracyhip_consensus_traces_async(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tracyhip_params* prm, int mem,
+                                    const tracyhip_consensus_result* out);
 
 /* ---- device groups: the GPUs of one node behind one handle (north star: "batches of traces shard embarrassingly across
  * the 8 GPUs of one node") ------------------------------------------------------------------------------------------

@@ -54,7 +54,7 @@ class CallStats(C.Structure):
                 ("pruned", C.c_uint32), ("pruned_uncertified", C.c_uint32), ("prelim_banded", C.c_uint32), ("prelim_repeated", C.c_uint32),
                 ("final_banded", C.c_uint32), ("final_repeated", C.c_uint32), ("allele_pruned", C.c_uint32 * 2),
                 ("allele_uncertified", C.c_uint32 * 2), ("allele_banded", C.c_uint32 * 3), ("allele_repeated", C.c_uint32 * 3),
-                ("allele_shared_prefix", C.c_uint32)]
+                ("allele_shared_prefix", C.c_uint32), ("cons_fixup_columns", C.c_uint32), ("cons_chunks", C.c_uint32)]
 
 
 def library_path():
@@ -360,6 +360,113 @@ def _align_traces_async(self, job, prm, out, mem=MEM_DEVICE):
 
 
 Context.align_traces_async = _align_traces_async
+
+
+CONS_OK, CONS_NO_OVERLAP = 0, 1
+
+
+class ConsensusJob(C.Structure):
+    _fields_ = [("npairs", C.c_uint32), ("first", SeqSet), ("second", SeqSet), ("compute_union", C.c_uint32), ("iupac", C.c_uint32),
+                ("min_overlap", C.c_uint32), ("match_fraction", C.c_float)]
+
+
+class ConsensusResult(C.Structure):
+    _fields_ = [("score_fwd", C.c_void_p), ("score_rev", C.c_void_p), ("forward", C.c_void_p), ("score", C.c_void_p),
+                ("num_aligned", C.c_void_p), ("num_match", C.c_void_p), ("status", C.c_void_p), ("rows0", C.c_void_p),
+                ("rows1", C.c_void_p), ("ops_len", C.c_void_p), ("cons", C.c_void_p), ("qual", C.c_void_p), ("cons_len", C.c_void_p),
+                ("offset", C.POINTER(C.c_uint64))]
+
+
+class PreparedConsensus:
+    """host-buffer job / result structs of tracyhip_consensus_traces (everything they point to is kept alive by this object).
+    first / second: lists of float32 [6][len] (the trimmed profile of trace 1, the trimmed FORWARD profile of trace 2)."""
+
+    _PAIR = (("score_fwd", np.int32), ("score_rev", np.int32), ("forward", np.uint8), ("score", np.int32), ("num_aligned", np.uint32),
+             ("num_match", np.uint32), ("status", np.int32), ("ops_len", np.uint32), ("cons_len", np.uint32))
+
+    def __init__(self, first, second, params, union=True, iupac=False, min_overlap=25, match_fraction=0.5):
+        p1 = first if isinstance(first, PackedSeqs) else PackedSeqs(first, SEQ_PROFILE)
+        p2 = second if isinstance(second, PackedSeqs) else PackedSeqs(second, SEQ_PROFILE)
+        if p1.count != p2.count:
+            raise ValueError("first and second need one profile per pair")
+        n = self.n = p1.count
+        self.keep = [p1, p2]
+        job = self.job = ConsensusJob()
+        job.npairs = n
+        job.first = p1.seqset()
+        job.second = p2.seqset()
+        job.compute_union = 1 if union else 0
+        job.iupac = 1 if iupac else 0
+        job.min_overlap = int(min_overlap)
+        job.match_fraction = float(match_fraction)
+        cap = p1.length[:n].astype(np.uint64) + p2.length[:n].astype(np.uint64)
+        off = self.off = np.zeros(max(n, 1), dtype=np.uint64)
+        if n:
+            off[1:n] = np.cumsum(cap)[:-1]
+        total = max(int(cap.sum()) if n else 0, 1)
+        res = self.res = {k: np.zeros(max(n, 1), dt) for k, dt in self._PAIR}
+        res.update(rows0=np.zeros(total, np.uint8), rows1=np.zeros(total, np.uint8), cons=np.zeros(total, np.uint8),
+                   qual=np.zeros(total, np.uint16))
+        out = self.out = ConsensusResult()
+        for k, v in res.items():
+            setattr(out, k, v.ctypes.data)
+        out.offset = off.ctypes.data_as(C.POINTER(C.c_uint64))
+        self.prm = Params(*params) if len(params) == 6 else Params(params[0], params[1], params[2], params[3], 1, 1)
+
+    def to_device(self):
+        """payloads and result arrays as torch tensors on the current device; returns the tensors that must stay alive"""
+        import torch
+        p1, p2 = self.keep[0], self.keep[1]
+        d1, d2 = torch.from_numpy(p1.data).cuda(), torch.from_numpy(p2.data).cuda()
+        self.job.first = p1.seqset(d1.data_ptr())
+        self.job.second = p2.seqset(d2.data_ptr())
+        self.dres = {k: torch.zeros(v.nbytes, dtype=torch.uint8, device="cuda") for k, v in self.res.items()}
+        for k, v in self.dres.items():
+            setattr(self.out, k, v.data_ptr())
+        self.dkeep = [d1, d2]
+        torch.cuda.synchronize()
+
+    def from_device(self):
+        for k, v in self.dres.items():
+            self.res[k] = v.cpu().numpy().view(self.res[k].dtype)
+
+    def results(self):
+        """per-pair arrays, and lists rows (row0, row1 bytes), cons (bytes), qual (uint16 arrays)"""
+        res, off, n = self.res, self.off, self.n
+        out = {k: res[k][:n].copy() for k, _ in self._PAIR}
+        out["rows"] = [(res["rows0"][int(off[i]):int(off[i]) + int(res["ops_len"][i])].tobytes(),
+                        res["rows1"][int(off[i]):int(off[i]) + int(res["ops_len"][i])].tobytes()) for i in range(n)]
+        out["cons"] = [res["cons"][int(off[i]):int(off[i]) + int(res["cons_len"][i])].tobytes() for i in range(n)]
+        out["qual"] = [res["qual"][int(off[i]):int(off[i]) + int(res["cons_len"][i])].copy() for i in range(n)]
+        return out
+
+
+def _consensus_traces(self, first, second, params, union=True, iupac=False, min_overlap=25, match_fraction=0.5, device=False):
+    """tracyhip_consensus_traces: `tracy consensus` for a batch of trace pairs.  params: (match, mismatch, go, ge) with free end gaps
+    on both axes (the command's AlignConfig<true,true>), or all six tracyhip_params fields.  device=True: payloads and results in
+    device memory (TRACYHIP_MEM_DEVICE), copied back afterwards."""
+    p = PreparedConsensus(first, second, params, union, iupac, min_overlap, match_fraction)
+    if device:
+        import torch
+        p.to_device()
+        _check(lib().tracyhip_consensus_traces(self._h, C.byref(p.job), C.byref(p.prm), MEM_DEVICE, C.byref(p.out)))
+        torch.cuda.synchronize()
+        p.from_device()
+    else:
+        _check(lib().tracyhip_consensus_traces(self._h, C.byref(p.job), C.byref(p.prm), MEM_HOST, C.byref(p.out)))
+    return p.results()
+
+
+Context.consensus_traces = _consensus_traces
+
+
+def _consensus_traces_async(self, job, prm, out, mem=MEM_HOST):
+    """tracyhip_consensus_traces_async on prepared structs (PreparedConsensus: they, and everything they point to, must outlive
+    synchronize())"""
+    _check(lib().tracyhip_consensus_traces_async(self._h, C.byref(job), C.byref(prm), mem, C.byref(out)))
+
+
+Context.consensus_traces_async = _consensus_traces_async
 
 
 class RaggedSrc(C.Structure):

@@ -1574,6 +1574,7 @@ int main(int argc, char** argv) {
   std::cout << "       tracy_amd_cli assemble [OPTIONS] [-r reference.fa] trace1.ab1 trace2.ab1 ..." << std::endl;
   std::cout << "       tracy_amd_cli basecall [OPTIONS] trace.ab1" << std::endl;
   std::cout << "       tracy_amd_cli consensus [OPTIONS] trace1.ab1 trace2.ab1" << std::endl;
+  std::cout << "       tracy_amd_cli consensus [OPTIONS] --batch manifest.tsv" << std::endl;
   std::cout << "       tracy_amd_cli index [-o genome.tidx] [-k 15] [-d 0] genome.fa.gz" << std::endl;
   return argc < 2 ? 0 : 1;
 }

@@ -124,6 +124,8 @@ struct tracyhip_ctx {
   bool b16_fork_ok = false;
   tracyhip::DevBuf d_stream;                   // everything the stream-ordered pipelines keep on the device between their stages (stream.hip)
   tracyhip::DevBuf d_seed[3];                  // tracyhip_seed_traces (seed.hip): per-trace inputs / results, staged consensus, staged windows
+  tracyhip::DevBuf d_cons[12];                 // tracyhip_consensus_traces (consensus.hip): both strands, classes, scores, ops, staged results, fix-ups, gq table
+  bool cons_gq_ready = false;                  // d_cons holds the gq table of consensus.h
   hipError_t ensure_codes(size_t bytes, hipStream_t st) {
     hipError_t e = d_codes.ensure(bytes + 2 * tracyhip::kCodePad);
     if (e != hipSuccess) return e;
@@ -185,6 +187,8 @@ struct tracyhip_ctx {
     d_pre.release();
     d_stream.release();
     for (auto& b : d_seed) b.release();
+    for (auto& b : d_cons) b.release();
+    cons_gq_ready = false;
     h_desc.release();
     h_off.release();
     h_tmp.release();
@@ -283,6 +287,8 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
            int32_t* d_scores, uint8_t* d_ops, const uint64_t* d_ops_off, uint32_t* d_ops_len, int stage = DP_PLAIN,
            DpCkpt* ck = nullptr);
 bool narrow_ok(const tracyhip_params* prm, uint32_t maxm, int K, int64_t Q = 0);
+// profile x profile score kernel with 16-bit cells for pairs of at most max_mn = m + n (Q: largest substitution score, 0 = a priori)
+bool arith16_ok(const tracyhip_params* prm, uint64_t max_mn, int64_t Q);
 int32_t sub_limit(const tracyhip_params* prm);
 // largest |match| / |mismatch| whose table entries x 32 (tagged tracebacks, band kernels) fit int16; wider scorings take slower forms
 constexpr int32_t kWideScore = 1000;
