@@ -128,7 +128,7 @@ TR_HD int b16_pick_k(int32_t dmin, int32_t dmax) {
   return 0;
 }
 // value ranges of the origin-tracking sweep on the band kernels (packed 14-bit score field, 13-bit origin) for m rows / n columns,
-// AlignConfig<true,false> (capi_internal.h origin16_ok: the same test with a tracyhip_params)
+// AlignConfig<true,false> (stream_plan.h origin16_ok: the same test with a tracyhip_params)
 TR_HD bool b16_origin_ok(int32_t match, int32_t mismatch, int32_t go, int32_t ge, uint32_t maxm, uint32_t maxn) {
   if (go > 0 || ge >= 0) return false;
   if ((uint64_t)maxn + 64 >= (1u << kOriginBits)) return false;

@@ -24,6 +24,7 @@
 #include "../../include/tracy_hip.h"
 #include "capi_internal.h"
 #include "launch.h"
+#include "stream_plan.h"
 
 using namespace tracyhip;
 
@@ -777,13 +778,6 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
 }
 
 // ---- band kernels (band16.h) ----------------------------------------------------------------------------------------
-int band16_pick_k(int32_t dmin, int32_t dmax) { return b16_pick_k(dmin, dmax); }
-
-bool origin16_ok(const tracyhip_params* prm, uint32_t maxm, uint32_t maxn) {
-  if (!prm->hfree || prm->vfree) return false;
-  return b16_origin_ok(prm->match, prm->mismatch, prm->go, prm->ge, maxm, maxn);
-}
-
 int build_b16_tables(tracyhip_ctx* ctx, DevBuf& buf, const void* d_a1, bool strings, std::vector<B16TableDesc>& desc, const tracyhip_params* prm) {
   const uint32_t ns = (uint32_t)desc.size();
   if (ns == 0) return TRACYHIP_OK;
@@ -1663,7 +1657,7 @@ int tracyhip_gotoh_banded(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, const 
     PairDesc d = pb.desc[i];
     if (d.m == 0 || d.n == 0) return set_error(TRACYHIP_ERR_ARG, "pair %u: empty sequence", i);
     const uint32_t i1 = pairs->a1_index ? pairs->a1_index[i] : i;
-    const int K = band16_pick_k(band_lo[i], band_hi[i]);
+    const int K = b16_pick_k(band_lo[i], band_hi[i]);
     if (K == 0) return set_error(TRACYHIP_ERR_RANGE, "pair %u: band of %lld diagonals is wider than the band kernels sweep (<= %u)", i,
                                  (long long)band_hi[i] - band_lo[i] + 1, b16_max_window(12) - 12 + 1);
     if (origin && !origin16_ok(prm, d.m, d.n)) return set_error(TRACYHIP_ERR_RANGE, "pair %u outside the origin-tracking sweep's packed fields", i);

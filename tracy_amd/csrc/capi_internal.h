@@ -304,7 +304,7 @@ int build_problem(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, int mem, bool 
 
 // ---- band kernels (band16.h): Gotoh on a diagonal band, four pairs per wave ----
 // a batch for them: descriptors whose a1_off / a1_stride point into the substitution tables d_qp (build_b16_tables), a2_off into
-// d_codes (codes 0..5), ckpt_off = band_pack(dmin, dmax); k[i] = strip height of pair i (band16_pick_k)
+// d_codes (codes 0..5), ckpt_off = band_pack(dmin, dmax); k[i] = strip height of pair i (b16_pick_k)
 struct Band16Job {
   int kind = 0;                 // 0: traceback words + walk (scores, ops); 1: origin-tracking sweep (scores, ends)
   const int16_t* d_qp = nullptr;
@@ -312,10 +312,6 @@ struct Band16Job {
   std::vector<PairDesc> desc;
   std::vector<int> k;           // 4 / 8 / 12; 0: the pair is not part of the job (callers fill both vectors for every trace, in order)
 };
-// smallest strip height whose lanes are done with a strip before the next one is due (K + width <= 15 (K + 1)); 0: the band is too wide
-int band16_pick_k(int32_t dmin, int32_t dmax);
-// value ranges of the origin-tracking sweep (packed 14-bit score field, 13-bit origin) for m rows / n columns
-bool origin16_ok(const tracyhip_params* prm, uint32_t maxm, uint32_t maxn);
 // substitution tables of `desc.size()` sequences (b16_table_kernel): entries are scores << kTagShift; desc[i].out_off / stride are
 // filled in here, the buffer is (re)sized.  strings: a1 holds bytes, else float profiles.
 int build_b16_tables(tracyhip_ctx* ctx, DevBuf& buf, const void* d_a1, bool strings, std::vector<B16TableDesc>& desc, const tracyhip_params* prm);
@@ -329,8 +325,6 @@ struct FrontResult {
   std::vector<int32_t> score;
   std::vector<uint32_t> ce;
 };
-constexpr int kFrontK = 12;
-constexpr int32_t kFrontHalfW = 90;  // 2 * 90 + 12 <= 15 * 13: the widest band one period of the K = 12 strips holds
 // d_codes: the codes the band kernels read (null: the context's); keep_err: the error words hold the flags of a launch that has
 // not been read yet (run_prefix_keep_cq) -- they are not cleared, and reported with this call's
 int run_front(tracyhip_ctx* ctx, const std::vector<FrontDesc>& fd, const int16_t* d_qp, const uint32_t* d_row, const tracyhip_params* prm,

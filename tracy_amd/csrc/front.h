@@ -24,6 +24,9 @@
 
 namespace tracyhip {
 
+constexpr int kFrontK = 12;
+constexpr int32_t kFrontHalfW = 90;  // 2 * 90 + 12 <= 15 * 13: the widest band one period of the K = 12 strips holds
+
 struct FrontDesc {
   uint64_t row_off;     // row R of the prefix sweep: column c at row[row_off + c] (PAIR_KEEP_ROW layout)
   uint64_t a2_off;      // the window's codes

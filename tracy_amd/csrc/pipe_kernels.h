@@ -7,33 +7,10 @@
 #include <hip/hip_runtime.h>
 
 #include "capi_internal.h"
+#include "stream_plan.h"
 
 namespace {
 using namespace tracyhip;
-
-struct TrimOut {
-  uint32_t ri;       // offset of the trimmed slice in the oriented reference
-  uint32_t len;      // its length after std::string::substr clamping
-  uint32_t pos;      // rs.pos after the update (rs.pos starts at 0)
-  uint32_t pad;
-};
-
-// the widening / clamping / rs.pos part of trimReferenceSlice (fmindex.h:443-461)
-__device__ inline TrimOut trim_finish(uint32_t ri, uint32_t risize, uint32_t n, uint32_t trim_left, uint32_t trim_right, bool forward) {
-  if (ri >= trim_left) { ri -= trim_left; risize += trim_left; }
-  if ((uint32_t)(ri + risize + trim_right) < n) risize += trim_right;
-  TrimOut r;
-  r.ri = ri;
-  r.len = (ri <= n) ? ((risize < n - ri) ? risize : n - ri) : 0;  // substr(ri, risize)
-  r.pos = 0;
-  if (forward) r.pos = ri;
-  else {
-    const int32_t offset = (int32_t)n - (int32_t)ri - (int32_t)risize;
-    if (offset >= 0) r.pos = (uint32_t)offset;  // negative: the reference only warns (fmindex.h:457-459)
-  }
-  r.pad = 0;
-  return r;
-}
 
 // trimReferenceSlice (fmindex.h:429-463) evaluated directly on the traceback string.  ops are in push
 // order (end -> start); alignment column j (forward) is ops[L-1-j].  Row 0 holds a trace base unless
@@ -45,7 +22,7 @@ __device__ inline TrimOut trim_finish(uint32_t ri, uint32_t risize, uint32_t n, 
 __global__ __launch_bounds__(64) void trim_kernel(const uint8_t* __restrict__ ops, const uint64_t* __restrict__ ops_off,
                                                   const uint32_t* __restrict__ ops_len, const uint32_t* __restrict__ ref_len,
                                                   const uint8_t* __restrict__ forward, uint32_t trim_left,
-                                                  uint32_t trim_right, uint32_t ntraces, TrimOut* __restrict__ out) {
+                                                  uint32_t trim_right, uint32_t ntraces, TrimRec* __restrict__ out) {
   const uint32_t t = blockIdx.x;
   if (t >= ntraces) return;
   const uint8_t* o = ops + ops_off[t];
@@ -87,7 +64,7 @@ __global__ __launch_bounds__(64) void trim_kernel(const uint8_t* __restrict__ op
     else { for (int32_t j = s; j < e; ++j) refcols += (o[L - 1 - j] != 'v'); inside = refcols; }
     risize = inside;
   }
-  out[t] = trim_finish(ri, risize, n, trim_left, trim_right, forward[t] != 0);
+  out[t] = s_trim_finish(ri, risize, n, trim_left, trim_right, forward[t] != 0);
 }
 
 // trimReferenceSlice from the two ends of the alignment alone (origin-tracking sweep, dp_kernels.h gotoh_origin_body):
@@ -95,11 +72,11 @@ __global__ __launch_bounds__(64) void trim_kernel(const uint8_t* __restrict__ op
 // belongs to the slice.
 __global__ void trim_from_ends_kernel(const uint32_t* __restrict__ ends, const uint32_t* __restrict__ ref_len,
                                       const uint8_t* __restrict__ forward, uint32_t trim_left, uint32_t trim_right, uint32_t ntraces,
-                                      TrimOut* __restrict__ out) {
+                                      TrimRec* __restrict__ out) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= ntraces) return;
   const uint32_t lead = ends[2 * t], ce = ends[2 * t + 1];
-  out[t] = trim_finish(lead, ce >= lead ? ce - lead : 0u, ref_len[t], trim_left, trim_right, forward[t] != 0);
+  out[t] = s_trim_finish(lead, ce >= lead ? ce - lead : 0u, ref_len[t], trim_left, trim_right, forward[t] != 0);
 }
 
 // c_e of a pair from the row-m values the 16-bit sweep left behind ({H, E - goe} per column): the last column whose H(m, c) is
@@ -129,7 +106,7 @@ __global__ void ends_shift_kernel(uint32_t* __restrict__ ends, const uint32_t* _
 struct TrimRowsDesc { uint64_t off; uint32_t L, n; uint8_t forward, pad[7]; };
 __global__ __launch_bounds__(64) void trim_rows_kernel(const TrimRowsDesc* __restrict__ desc, const uint8_t* __restrict__ rows0,
                                                        const uint8_t* __restrict__ rows1, uint32_t trim_left, uint32_t trim_right,
-                                                       uint32_t ntraces, TrimOut* __restrict__ out) {
+                                                       uint32_t ntraces, TrimRec* __restrict__ out) {
   const uint32_t t = blockIdx.x;
   if (t >= ntraces) return;
   const TrimRowsDesc d = desc[t];
@@ -164,7 +141,7 @@ __global__ __launch_bounds__(64) void trim_rows_kernel(const TrimRowsDesc* __res
       risize += (uint32_t)__popcll(__ballot(j < (uint32_t)e && r1[j] != '-'));
     }
   }
-  if (lane == 0) out[t] = trim_finish(ri, risize, d.n, trim_left, trim_right, d.forward != 0);
+  if (lane == 0) out[t] = s_trim_finish(ri, risize, d.n, trim_left, trim_right, d.forward != 0);
 }
 
 // (loadSingleFasta hands over upper-case [ACGTN] only (fasta.h:54-95); anything else makes the string and profile reverse

@@ -85,6 +85,15 @@ struct OrientOut {
 
 constexpr int kNoEnds = 2;  // orient_and_align_impl: the ends path met a pair outside the origin-tracking sweep's range
 
+// c_e = 0 (a junk trace): H(m, c) == E(m, c) in every column, and the reference's traceback (gotoh.h:143-167) runs along row m to
+// column 0 and up column 0 -- n 'h', then m 'v' -- so both ends are 0 (the all-gap path is optimal).  Column 1 alone reproduces
+// that: H(m, 1) == E(m, 1), opened from H(m, 0), whose origin is 0.  (stream.hip marks such traces SD_JUNK instead.)
+void junk_to_column1(PairDesc& d, bool rc) {
+  d.a2_off += rc ? (uint64_t)(d.n - 1u) : 0ull;
+  d.n = 1;
+  d.a2_stride = 1;
+}
+
 // One run of the orientation stage + preliminary alignment over a batch (orient_and_align below repeats it on wider kernels when a
 // launch reports values outside its proven range): what the stages share lives here, each stage is a method.
 struct OrientRun {
@@ -322,15 +331,11 @@ struct OrientRun {
     parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t tid) {
       Cnt c{0, 0, 0};
       for (uint32_t t = lo; t < hi; ++t) {
-        const uint32_t vf = h_votes[2 * t], vr = h_votes[2 * t + 1];
-        guess[t] = vf >= vr ? 0 : 1;
-        const uint32_t hi_v = vf >= vr ? vf : vr, lo_v = vf >= vr ? vr : vf;
-        both[t] = (mt[t] > R && hi_v >= 32 && hi_v >= 2 * lo_v) ? 0 : 1;  // a clear majority of shared k-mers, or both sweeps
-        const bool front = !both[t] && mt[t] - R > 2u * (uint32_t)kFrontK && rn[t] >= 1 &&
-                           origin16_ok(&p, mt[t], mt[t] - R + 2u * (uint32_t)kFrontHalfW + 16u);
-        if (front) { cls[t] = 0; c.fr += 1; c.pre += exact ? 1 : 2; c.full += exact ? 1 : 0; }
-        else if (exact || both[t]) { cls[t] = 1; c.full += 2; }
-        else { cls[t] = 2; c.full += 1; c.pre += 1; }
+        const SOrient o = s_orient_class(h_votes[2 * t], h_votes[2 * t + 1], mt[t], s_front_ok(&p, mt[t], rn[t]), exact);
+        guess[t] = (int8_t)o.g; both[t] = (int8_t)o.both; cls[t] = (int8_t)o.cls;
+        if (o.cls == 0) { c.fr += 1; c.pre += exact ? 1 : 2; c.full += exact ? 1 : 0; }
+        else if (o.cls == 1) c.full += 2;
+        else { c.full += 1; c.pre += 1; }
       }
       cnt[tid] = c;
     });
@@ -679,7 +684,6 @@ struct OrientRun {
         // band kernels sweep (band16.h), where the band fits them; other pairs take the origin-tracking sweep over the whole
         // sub-window (ends_path) or the whole matrix (tb16_path).
         sco.mark("o.g stage2 band plan");
-        const int64_t age = -(int64_t)p.ge;
         std::vector<int32_t> h_pre(nt);
         o.gap.assign(nt, 0);
         Band16Job j16;
@@ -698,43 +702,26 @@ struct OrientRun {
             if (tb16_path) wholes[t] = whole;
             PairDesc& d = pb.desc[t];
             h_pre[t] = h_rc[t] ? h_sc2[nt + t] : h_sc2[t];
-            const int64_t ce = h_ce[t];
-            if (ce <= 0) {
-              // H(m, c) == E(m, c) in every column: the reference's traceback (gotoh.h:143-167) runs along row m to column 0 and
-              // up column 0 -- n 'h', then m 'v' -- so both ends are 0 (a junk trace: the all-gap path is optimal).  Column 1 alone
-              // reproduces that: H(m, 1) == E(m, 1), opened from H(m, 0), whose origin is 0.
-              if (ends_path) {
-                d.a2_off += h_rc[t] ? (uint64_t)(d.n - 1u) : 0ull;
-                d.n = 1;
-                d.a2_stride = 1;
-              }
+            const uint32_t ce = h_ce[t];
+            if (ce == 0) {
+              if (ends_path) junk_to_column1(d, h_rc[t]);
               continue;
             }
-            const int64_t loss = (int64_t)h_top[t] - (int64_t)h_pre[t];
-            const int64_t g = loss > 0 ? loss / age : 0;
-            o.gap[t] = (uint32_t)std::min<int64_t>(g, 0x7fffffff);
-            int64_t a = ce - (int64_t)d.m - g - 2;
-            if (a < 0) a = 0;
-            shift[t] = (uint32_t)a;
-            d.a2_off += h_rc[t] ? (uint64_t)(d.n - (uint32_t)ce) : (uint64_t)a;  // reverse view: column c is byte n - c
-            d.n = (uint32_t)(ce - a);
+            const SubWindow sw = s_sub_window(d.m, ce, h_top[t], h_pre[t], p.ge);
+            o.gap[t] = (uint32_t)std::min<int64_t>(sw.g, 0x7fffffff);
+            shift[t] = sw.a;
+            d.a2_off += h_rc[t] ? (uint64_t)(d.n - ce) : (uint64_t)sw.a;  // reverse view: column c is byte n - c
+            d.n = sw.n;
             d.a2_stride = d.n;
-            int K = 0;
-            int32_t dlo = 0, dhi = 0;
-            if (b16 && g < (1 << 20)) {
-              const int32_t d1 = (int32_t)d.n - (int32_t)d.m;
-              dlo = d1 - (int32_t)g - 1;
-              dhi = d1 + (int32_t)g + 1;
-              K = band16_pick_k(dlo, dhi);
-              if (K && ends_path && !origin16_ok(&p, d.m, d.n)) K = 0;
-              if (K && 4ull * ((d.n + 7u) & ~3u) + b16_table_bytes(K) > 60u * 1024u) K = 0;  // (the codes of four pairs are staged in LDS)
-            }
+            int K = b16 ? sw.K : 0;
+            if (K && ends_path && !origin16_ok(&p, d.m, d.n)) K = 0;
+            if (K && !s_fits_lds(d.n, K)) K = 0;
             if (K) {
               PairDesc q = d;
               q.a1_off = in.td[t].out_off + in.row0[t];
               q.a1_stride = in.td[t].stride;
-              q.ckpt_off = band_pack(dlo, dhi);
-              q.lastrow_off = ends_path ? 0ull : ((uint64_t)(whole.n - (uint32_t)ce) | ((uint64_t)(uint32_t)a << 32));  // 'h' right / left of the sub-window
+              q.ckpt_off = band_pack(sw.dlo, sw.dhi);
+              q.lastrow_off = ends_path ? 0ull : ((uint64_t)(whole.n - ce) | ((uint64_t)sw.a << 32));  // 'h' right / left of the sub-window
               j16.desc[t] = q;
               j16.k[t] = K;
             }
@@ -875,7 +862,7 @@ struct AlignRun {
   std::vector<B16TableDesc> td;  // substitution tables of the full profiles (band kernels)
   bool b16 = false;
   OrientOut oo;
-  std::vector<TrimOut> h_trim;
+  std::vector<TrimRec> h_trim;
   void *d_final_sc = nullptr, *d_ops = nullptr, *d_olen = nullptr;
   uint64_t ops_total = 0;
 
@@ -966,7 +953,7 @@ struct AlignRun {
 
   int trim() {
     // ---- 3. trimReferenceSlice (sage.h:259) ----
-    HIP_TRY(ctx->d_tmp[5].ensure(sizeof(TrimOut) * (size_t)nt));
+    HIP_TRY(ctx->d_tmp[5].ensure(sizeof(TrimRec) * (size_t)nt));
     HIP_TRY(ctx->d_tmp[6].ensure(sizeof(uint32_t) * (size_t)nt + (size_t)nt));
     uint32_t* d_rn = static_cast<uint32_t*>(ctx->d_tmp[6].p);
     uint8_t* d_fwd = reinterpret_cast<uint8_t*>(d_rn + nt);
@@ -978,14 +965,14 @@ struct AlignRun {
     }
     if (oo.d_ends)  // the two ends of the preliminary alignment (origin-tracking sweep) instead of its ops
       hipLaunchKernelGGL(trim_from_ends_kernel, dim3((nt + 255) / 256), dim3(256), 0, st, oo.d_ends, static_cast<const uint32_t*>(d_rn),
-                         static_cast<const uint8_t*>(d_fwd), (uint32_t)job->trim_left, (uint32_t)job->trim_right, nt, static_cast<TrimOut*>(ctx->d_tmp[5].p));
+                         static_cast<const uint8_t*>(d_fwd), (uint32_t)job->trim_left, (uint32_t)job->trim_right, nt, static_cast<TrimRec*>(ctx->d_tmp[5].p));
     else
       hipLaunchKernelGGL(trim_kernel, dim3(nt), dim3(64), 0, st, static_cast<const uint8_t*>(ctx->d_tmp[1].p),
                          static_cast<const uint64_t*>(ctx->d_tmp[2].p), static_cast<const uint32_t*>(ctx->d_tmp[3].p), d_rn, d_fwd,
-                         job->trim_left, job->trim_right, nt, static_cast<TrimOut*>(ctx->d_tmp[5].p));
+                         job->trim_left, job->trim_right, nt, static_cast<TrimRec*>(ctx->d_tmp[5].p));
     HIP_TRY(hipGetLastError());
     h_trim.resize(nt);
-    HIP_TRY(hipMemcpyAsync(h_trim.data(), ctx->d_tmp[5].p, sizeof(TrimOut) * (size_t)nt, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_trim.data(), ctx->d_tmp[5].p, sizeof(TrimRec) * (size_t)nt, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx_sync(ctx));
 
     return TRACYHIP_OK;
@@ -1020,8 +1007,8 @@ struct AlignRun {
       // certify are repeated on the whole matrix.  W = 48 by default (TRACYHIP_BAND_W=<W>; 0 = whole matrices): the traceback
       // launch takes 3.5 instead of 4.5 ms per 10 000 traces.  The traceback words keep the whole-matrix layout (four passes of
       // n + 63 steps, of which a pass writes a third); a compact layout would shrink the workspace, not the work.
-      // Without the variable every pair gets the width its preliminary alignment suggests: the gap columns that alignment's score
-      // allowed (OrientOut::gap) + 48 for what the trimmed ends add, within [32, 96]; 48 where that is not known.  (A pair that does not
+      // Without the variable every pair gets the width its preliminary alignment suggests (s_final_width of OrientOut::gap); 48 where
+      // that is not known.  (A pair that does not
       // certify costs a launch of its own at the end of the step -- 0.7 ms for a single pair -- so the width errs on the wide side.)
       const bool band_env = ctx->knobs.band_w >= 0;
       // (developer knob band_w, tracyhip_set_option: clamped to [0, 4096] -- widths the band forms cannot hold simply leave the pair on
@@ -1029,7 +1016,7 @@ struct AlignRun {
       const int32_t bandW = (p.ge < 0 && p.go <= 0 && sub_limit(&p) <= kWideScore) ? (band_env ? ctx->knobs.band_w : 48) : 0;
       std::vector<int32_t> band_of(nt, bandW);
       if (!band_env && bandW > 0 && oo.gap.size() == nt)
-        for (uint32_t t = 0; t < nt; ++t) band_of[t] = (int32_t)std::min<uint32_t>(96u, std::max<uint32_t>(32u, oo.gap[t] + 48u));
+        for (uint32_t t = 0; t < nt; ++t) band_of[t] = (int32_t)s_final_width(oo.gap[t]);
       constexpr int kBandK = 4;
       std::vector<uint8_t> banded(nt, 0);  // 1: multi-pass form of the whole-matrix kernel (PAIR_BANDED), 2: band kernels
       uint32_t nbanded = 0;
@@ -1055,18 +1042,13 @@ struct AlignRun {
         d.out = t;
         whole[t] = d;
         int kt = choose_k(d.m, MODE_QP);
-        if (b16 && bandW > 0 && d.m && d.n && 4ull * ((d.n + 7u) & ~3u) + b16_table_bytes(12) <= 60u * 1024u) {
-          const int64_t over = (int64_t)d.n - (int64_t)d.m, aover = over < 0 ? -over : over;
-          int64_t bw = band_of[t];
-          const int64_t fit = ((int64_t)b16_max_window(12) - 12 - aover) / 2;  // the widest band the kernels sweep
-          if (bw > fit && fit >= 24) bw = fit;
-          const int32_t dlo = (int32_t)(-bw - (over < 0 ? -over : 0)), dhi = (int32_t)(bw + (over > 0 ? over : 0));
-          const int K = band16_pick_k(dlo, dhi);
-          if (K) {
-            band_of[t] = (int32_t)bw;
+        if (b16 && bandW > 0) {
+          const SFinalBand fb = s_final_band(d.m, d.n, band_of[t]);
+          if (fb.K) {
+            band_of[t] = (int32_t)fb.w;
             PairDesc q = d;
-            q.a1_off = td[t].out_off; q.a1_stride = td[t].stride; q.ckpt_off = band_pack(dlo, dhi); q.lastrow_off = 0;
-            j16.desc.push_back(q); j16.k.push_back(K);
+            q.a1_off = td[t].out_off; q.a1_stride = td[t].stride; q.ckpt_off = band_pack(fb.dlo, fb.dhi); q.lastrow_off = 0;
+            j16.desc.push_back(q); j16.k.push_back(fb.K);
             banded[t] = 2;
             ++nbanded;
             continue;
@@ -1148,8 +1130,7 @@ struct AlignRun {
         std::vector<PairDesc> again;
         std::vector<int> again_k;
         for (uint32_t t = 0; t < nt; ++t) {
-          const int64_t lose = (int64_t)(-(int64_t)p.ge) * ((int64_t)band_of[t] + 1);
-          if (!banded[t] || ((int64_t)h_sb[t] > (int64_t)h_top[t] - lose && h_ol[t] != 0)) continue;
+          if (!banded[t] || s_final_certified(h_sb[t], h_top[t], p.ge, band_of[t], h_ol[t])) continue;
           again.push_back(whole[t]);
           again_k.push_back(choose_k(whole[t].m, MODE_QP));
         }
@@ -1450,7 +1431,7 @@ struct DecomposeRun {
   int cq_codes = 6;
   std::vector<int32_t> h_hst, h_strim, h_status;
   std::vector<uint32_t> h_len1;
-  std::vector<TrimOut> h_trimA[2];
+  std::vector<TrimRec> h_trimA[2];
   std::vector<B16TableDesc> td_pri;  // substitution tables of the primary alleles (band kernels), kept for allele 1 vs allele 2
   void *d_scoreK[3] = {}, *d_opsK[3] = {}, *d_lenK[3] = {};
 
@@ -1820,7 +1801,7 @@ struct DecomposeRun {
     HIP_TRY(b_ends.ensure(sizeof(uint32_t) * 2 * (size_t)nt));
     HIP_TRY(b_opsA.ensure(tot1 + 2ull * TL * nt + 16));
     HIP_TRY(b_lenA.ensure(sizeof(uint32_t) * (size_t)nt));
-    HIP_TRY(b_trimA.ensure(sizeof(TrimOut) * (size_t)nt));
+    HIP_TRY(b_trimA.ensure(sizeof(TrimRec) * (size_t)nt));
     HIP_TRY(b_rnfw.ensure(sizeof(uint32_t) * (size_t)nt + nt));
     {
       std::vector<uint8_t> tmp(sizeof(uint32_t) * (size_t)nt + nt);
@@ -1953,8 +1934,7 @@ struct DecomposeRun {
       parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t tid) {
         uint32_t c = 0;
         for (uint32_t t = lo; t < hi; ++t) {
-          const PairDesc& d = pb.desc[t];
-          elig6[t] = d.m > R + 2u * (uint32_t)kFrontK && d.n >= 1 && origin16_ok(&p, d.m, d.m - R + 2u * (uint32_t)kFrontHalfW + 16u);
+          elig6[t] = s_front_ok(&p, pb.desc[t].m, pb.desc[t].n);
           c += elig6[t];
         }
         cnt6[tid] = c;
@@ -2031,28 +2011,20 @@ struct DecomposeRun {
       if (!fscore.empty())
         for (uint32_t t = 0; t < nt; ++t)
           if (pruned[t]) { h_s[t] = fscore[t]; h_ce[t] = fce[t]; }
-      const int64_t best = std::max<int64_t>(std::max<int64_t>(p.match, p.mismatch), 0), age = -(int64_t)p.ge;
+      const int64_t best = std::max<int64_t>(std::max<int64_t>(p.match, p.mismatch), 0);
       parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
         for (uint32_t t = lo; t < hi; ++t) {
           PairDesc& d = pb.desc[t];
-          const int64_t ce = h_ce[t];
+          const uint32_t ce = h_ce[t];
           if (d.m == 0 || d.n == 0) continue;
-          if (ce <= 0) {  // H(m, c) == E(m, c) everywhere: n 'h' then m 'v', both ends 0 -- column 1 alone reproduces it (see orient_and_align_impl)
-            d.a2_off += h_rc[t] ? (uint64_t)(d.n - 1u) : 0ull;
-            d.n = 1;
-            d.a2_stride = 1;
-            continue;
-          }
-          const int64_t loss = best * (int64_t)d.m - (int64_t)h_s[t];
-          const int64_t g = loss > 0 ? loss / age : 0;
-          int64_t a = ce - (int64_t)d.m - g - 2;
-          if (a < 0) a = 0;
-          shift[t] = (uint32_t)a;
-          d.a2_off += h_rc[t] ? (uint64_t)(d.n - (uint32_t)ce) : (uint64_t)a;  // reverse view: column c is byte n - c
-          d.n = (uint32_t)(ce - a);
+          if (ce == 0) { junk_to_column1(d, h_rc[t]); continue; }
+          const SubWindow sw = s_sub_window(d.m, ce, best * (int64_t)d.m, h_s[t], p.ge);
+          shift[t] = sw.a;
+          d.a2_off += h_rc[t] ? (uint64_t)(d.n - ce) : (uint64_t)sw.a;  // reverse view: column c is byte n - c
+          d.n = sw.n;
           d.a2_stride = d.n;
           h_s1[t] = h_s[t];
-          gap_of[t] = g;
+          gap_of[t] = sw.g;
         }
       });
       HIP_TRY(hipMemcpyAsync(d_shift, shift.data(), sizeof(uint32_t) * (size_t)nt, hipMemcpyHostToDevice, st));
@@ -2089,13 +2061,11 @@ struct DecomposeRun {
         for (uint32_t t = lo; t < hi; ++t) {
           PairDesc d = pb.desc[t];
           const int64_t g = gap_of[t];
-          const int32_t d1 = (int32_t)d.n - (int32_t)d.m;
-          const int32_t dlo = d1 - (int32_t)std::min<int64_t>(g, 1 << 20) - 1, dhi = d1 + (int32_t)std::min<int64_t>(g, 1 << 20) + 1;
-          const int K = g >= 0 ? band16_pick_k(dlo, dhi) : 0;
-          if (K && origin16_ok(&p, d.m, d.n)) {
-            d.a1_off = td[t].out_off; d.a1_stride = td[t].stride; d.ckpt_off = band_pack(dlo, dhi); d.lastrow_off = 0;
+          const SBand b = g >= 0 ? s_end_band(d.m, d.n, g) : SBand{0, 0, 0};  // (d.n: the sub-window's n' = c_e - a)
+          if (b.K && origin16_ok(&p, d.m, d.n)) {
+            d.a1_off = td[t].out_off; d.a1_stride = td[t].stride; d.ckpt_off = band_pack(b.dlo, b.dhi); d.lastrow_off = 0;
             jo.desc[t] = d;
-            jo.k[t] = K;
+            jo.k[t] = b.K;
           }
         }
       });
@@ -2110,7 +2080,7 @@ struct DecomposeRun {
     }
     hipLaunchKernelGGL(trim_from_ends_kernel, dim3((nt + 255) / 256), dim3(256), 0, st, static_cast<const uint32_t*>(b_ends.p),
                        static_cast<const uint32_t*>(b_rnfw.p), reinterpret_cast<const uint8_t*>(static_cast<const uint32_t*>(b_rnfw.p) + nt),
-                       TL, TR, nt, static_cast<TrimOut*>(b_trimA.p));
+                       TL, TR, nt, static_cast<TrimRec*>(b_trimA.p));
     return TRACYHIP_OK;
   }
 
@@ -2131,7 +2101,7 @@ struct DecomposeRun {
     hipLaunchKernelGGL(trim_kernel, dim3(nt), dim3(64), 0, st, static_cast<const uint8_t*>(b_opsA.p), d_offA,
                        static_cast<const uint32_t*>(b_lenA.p), static_cast<const uint32_t*>(b_rnfw.p),
                        reinterpret_cast<const uint8_t*>(static_cast<const uint32_t*>(b_rnfw.p) + nt), TL, TR, nt,
-                       static_cast<TrimOut*>(b_trimA.p));
+                       static_cast<TrimRec*>(b_trimA.p));
     return TRACYHIP_OK;
   }
 
@@ -2152,7 +2122,7 @@ struct DecomposeRun {
     HIP_TRY(hipGetLastError());
     h_trimA[k].resize(nt);
     std::vector<uint32_t> h_ends;
-    HIP_TRY(hipMemcpyAsync(h_trimA[k].data(), b_trimA.p, sizeof(TrimOut) * (size_t)nt, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_trimA[k].data(), b_trimA.p, sizeof(TrimRec) * (size_t)nt, hipMemcpyDeviceToHost, st));
     if (b16 && A.use_origin) {
       h_ends.resize(2 * (size_t)nt);
       HIP_TRY(hipMemcpyAsync(h_ends.data(), b_ends.p, sizeof(uint32_t) * 2 * (size_t)nt, hipMemcpyDeviceToHost, st));
@@ -2181,20 +2151,12 @@ struct DecomposeRun {
       parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
         for (uint32_t t = lo; t < hi; ++t) {
           PairDesc d = pb.desc[t];
-          const int64_t g = gap_of[t];
           const int64_t ce = (int64_t)h_ends[2 * t + 1] - (int64_t)h_trimA[k][t].ri;  // last column of the alignment, in the slice
-          int K = 0;
-          int32_t dlo = 0, dhi = 0;
-          if (g >= 0 && d.m && d.n && ce >= 1 && ce <= (int64_t)d.n) {
-            const int32_t d1 = (int32_t)ce - (int32_t)d.m;
-            dlo = d1 - (int32_t)std::min<int64_t>(g, 1 << 20) - 1;
-            dhi = d1 + (int32_t)std::min<int64_t>(g, 1 << 20) + 1;
-            K = band16_pick_k(dlo, dhi);
-          }
-          if (K) {
-            d.a1_off = td[t].out_off; d.a1_stride = td[t].stride; d.ckpt_off = band_pack(dlo, dhi); d.lastrow_off = 0;
+          const SBand b = s_slice_band(d.m, d.n, ce, gap_of[t], false, 0u, 0u);
+          if (b.K) {
+            d.a1_off = td[t].out_off; d.a1_stride = td[t].stride; d.ckpt_off = band_pack(b.dlo, b.dhi); d.lastrow_off = 0;
             jt.desc[t] = d;
-            jt.k[t] = K;
+            jt.k[t] = b.K;
           }
         }
       });
@@ -2251,11 +2213,8 @@ struct DecomposeRun {
       const uint64_t* d_offK;
       std::vector<uint64_t> offK(out->ops_offset[2], out->ops_offset[2] + nt);
       if ((rc = upload(ctx, buf(), offK, &d_offK))) return rc;
-      // On a band (band16.h) where it can be certified afterwards.  Both ends are fixed here: a path that leaves the diagonals
-      // [-W - (m-n)+, W + (n-m)+] makes at least v = W + 1 + (m-n)+ vertical and h = W + 1 + (n-m)+ horizontal gap steps in two runs, so
-      // it scores at most best (m - v) - |ge| (v + h) - 2 |go|; a banded score above that is the optimum and bits and path are the
-      // whole matrix's.  W is guessed from what the two alleles lost against the reference (they differ from each other by about
-      // as much as both differ from it); pairs that do not certify are repeated on the whole matrix.
+      // On a band (band16.h) where it can be certified afterwards (s_a12_band: the band and the bound a banded score has to beat for
+      // bits and path to be the whole matrix's); pairs that do not certify are repeated on the whole matrix.
       Band16Job jg;
       Band16Lease<Band16Job> jg_lease(ctx, jg);
       DpProblem rest;
@@ -2267,30 +2226,18 @@ struct DecomposeRun {
         for (int k = 0; k < 2; ++k) HIP_TRY(hipMemcpyAsync(h_a[k].data(), d_scoreK[k], sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx_sync(ctx));
         jg.kind = 0; jg.d_qp = static_cast<const int16_t*>(ctx->d_b16tab[0].p); jg.d_codes = d_cq_sd;
-        const int64_t best = std::max<int64_t>(std::max<int64_t>(pglobal.match, pglobal.mismatch), 0), age = -(int64_t)pglobal.ge, ago = -(int64_t)pglobal.go;
+        const int64_t best = std::max<int64_t>(std::max<int64_t>(pglobal.match, pglobal.mismatch), 0);
         jg.desc.resize(nt);
         jg.k.assign(nt, 0);
         parallel_for(nt, [&](uint32_t lo_, uint32_t hi_, uint32_t) {
          for (uint32_t t = lo_; t < hi_; ++t) {
-          PairDesc d = pb.desc[t];
-          int K = 0;
-          int32_t dlo = 0, dhi = 0;
-          if (d.m && d.n) {
-            const int64_t lost = std::max<int64_t>(0, best * d.m - h_a[0][t]) + std::max<int64_t>(0, best * d.m - h_a[1][t]);
-            const int64_t per = best + 2 * age;
-            int64_t W = (5 * lost / 2 + 40) / (per > 0 ? per : 1) + 2;
-            const int64_t over = (int64_t)d.n - (int64_t)d.m;
-            if (W > 90) W = 90;
-            dlo = (int32_t)(-W - (over < 0 ? -over : 0));
-            dhi = (int32_t)(W + (over > 0 ? over : 0));
-            K = band16_pick_k(dlo, dhi);
-            const int64_t v = W + 1 + (over < 0 ? -over : 0), h = W + 1 + (over > 0 ? over : 0);
-            bound_of[t] = best * ((int64_t)d.m - v) - age * (v + h) - 2 * ago;
-          }
-          if (K) {
-            d.a1_off = td_pri[t].out_off; d.a1_stride = td_pri[t].stride; d.ckpt_off = band_pack(dlo, dhi); d.lastrow_off = 0;
+          PairDesc d = pb.desc[t];  // (d.m = d.n = sl[t])
+          const SA12Band b = s_a12_band(d.m, best, pglobal.go, pglobal.ge, h_a[0][t], h_a[1][t]);
+          bound_of[t] = b.bound;
+          if (b.K) {
+            d.a1_off = td_pri[t].out_off; d.a1_stride = td_pri[t].stride; d.ckpt_off = band_pack(b.dlo, b.dhi); d.lastrow_off = 0;
             jg.desc[t] = d;
-            jg.k[t] = K;
+            jg.k[t] = b.K;
           }
          }
         });
@@ -2609,13 +2556,13 @@ extern "C" int tracyhip_trim_reference_slice(tracyhip_ctx* ctx, uint32_t ntraces
   if ((rc = stage_in(ctx, ctx->d_rows1, rows1, ext, mem, &d_r1))) return rc;
   HIP_TRY(ctx->d_desc.ensure(sizeof(TrimRowsDesc) * (size_t)ntraces));
   HIP_TRY(hipMemcpyAsync(ctx->d_desc.p, hd.data(), sizeof(TrimRowsDesc) * (size_t)ntraces, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx->d_tmp[5].ensure(sizeof(TrimOut) * (size_t)ntraces));
+  HIP_TRY(ctx->d_tmp[5].ensure(sizeof(TrimRec) * (size_t)ntraces));
   hipLaunchKernelGGL(trim_rows_kernel, dim3(ntraces), dim3(64), 0, st, static_cast<const TrimRowsDesc*>(ctx->d_desc.p),
                      static_cast<const uint8_t*>(d_r0), static_cast<const uint8_t*>(d_r1), trim_left, trim_right, ntraces,
-                     static_cast<TrimOut*>(ctx->d_tmp[5].p));
+                     static_cast<TrimRec*>(ctx->d_tmp[5].p));
   HIP_TRY(hipGetLastError());
-  std::vector<TrimOut> h(ntraces);
-  HIP_TRY(hipMemcpyAsync(h.data(), ctx->d_tmp[5].p, sizeof(TrimOut) * (size_t)ntraces, hipMemcpyDeviceToHost, st));
+  std::vector<TrimRec> h(ntraces);
+  HIP_TRY(hipMemcpyAsync(h.data(), ctx->d_tmp[5].p, sizeof(TrimRec) * (size_t)ntraces, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx_sync(ctx));  // (hd is pageable: the upload above has completed by now as well)
   std::vector<uint32_t> b(ntraces), l(ntraces), p(ntraces);
   for (uint32_t t = 0; t < ntraces; ++t) { b[t] = h[t].ri; l[t] = h[t].len; p[t] = h[t].pos; }

@@ -10,7 +10,7 @@
 // sizes from the device, Band16Args::count), the certificates.  Lists have fixed slots (PAIR_SKIP for the empty ones) or worst-case
 // grids whose surplus waves leave at once: nothing the host has to know before it launches.
 //
-// Exactness: every shortcut is certified per trace exactly as in pipeline.hip; a trace whose certificate fails, or whose band is
+// Exactness: every shortcut is certified per trace by the rules pipeline.hip calls (stream_plan.h); a trace whose certificate fails, or whose band is
 // wider than the band kernels hold, is marked dead (SD_* reasons), skipped by everything after it, and re-done afterwards by the
 // host-planned pipeline -- all its tiers -- on the list of dead traces (restoring the basecalls `tracy decompose` rewrites in
 // place).  Value-range reports of the 16-bit kernels (un-normalised profiles) send the whole call there.  Results are the
@@ -99,7 +99,7 @@ __device__ __forceinline__ PairDesc s_stage1_desc(const SGeom& G, uint32_t t, ui
   return d;
 }
 
-// ---- orientation stage, step 1 (pipeline.hip "o.b"): class of every trace from its vote; the sweep / prefix / pruned-sweep slots ----
+// ---- orientation stage, step 1 (pipeline.hip "o.b"): class of every trace from its vote (s_orient_class); the sweep / prefix / pruned-sweep slots ----
 // cls 0: pruned sweep of the voted strand g (prefix with the row kept + band), the other strand swept in full (exact) or bounded by
 // its prefix; cls 1: both strands in full; cls 2 (strand by certificate only): g in full, prefix of the other
 __global__ void s_orient_plan_kernel(SParams p, const SGeom* __restrict__ geom, const uint32_t* __restrict__ votes, const int32_t* __restrict__ ub,
@@ -110,12 +110,8 @@ __global__ void s_orient_plan_kernel(SParams p, const SGeom* __restrict__ geom, 
   if (t >= p.nt) return;
   const SGeom G = geom[t];
   const uint32_t R = kFrontRows;
-  const uint32_t vf = votes[2 * t], vr = votes[2 * t + 1];
-  const uint32_t g = vf >= vr ? 0u : 1u;
-  const uint32_t hi_v = vf >= vr ? vf : vr, lo_v = vf >= vr ? vr : vf;
-  const bool both = !(G.mt > R && hi_v >= 32u && hi_v >= 2u * lo_v);  // a clear majority of shared k-mers, or both sweeps
-  const bool front = !both && (G.flags & SG_FRONT_OK);
-  const uint32_t cls = front ? 0u : (p.exact || both) ? 1u : 2u;
+  const SOrient o = s_orient_class(votes[2 * t], votes[2 * t + 1], G.mt, (G.flags & SG_FRONT_OK) != 0u, p.exact != 0u);
+  const uint32_t g = o.g, cls = o.cls;
   PairDesc fa = s_skip_pair(t), fb = s_skip_pair(t), pa = s_skip_pair(t), pb = s_skip_pair(t);
   FrontDesc f{};
   f.flags = PAIR_SKIP;
@@ -231,7 +227,7 @@ __global__ void s_orient_decide_kernel(SParams p, const SGeom* __restrict__ geom
   });
 }
 
-// ---- preliminary alignment (pipeline.hip "o.g"): the sub-window and band its score allows around c_e, as an origin-tracking sweep
+// ---- preliminary alignment (pipeline.hip "o.g"): the sub-window and band its score allows around c_e (s_sub_window), as an origin-tracking sweep
 // (mode 0, `tracy align`: only its two ends are read) or a traceback completed with the free end-gap columns (mode 1) ----
 __global__ void s_prelim_plan_kernel(SParams p, int mode, const SGeom* __restrict__ geom, STrace* __restrict__ tr, const uint32_t* __restrict__ d_ce,
                                      const int32_t* __restrict__ top, uint32_t* __restrict__ dead, PairDesc* __restrict__ cand,
@@ -389,7 +385,7 @@ __global__ __launch_bounds__(kScanBlock) void s_scan_place_kernel(PairDesc* __re
 }
 
 // ---- `tracy align`: trimReferenceSlice from the two ends (sage.h:259) and the plan of the final alignment gotoh(full profile,
-// trimmed slice) on its certified band (sage.h:311; pipeline.hip step 4) ----
+// trimmed slice) on its certified band (sage.h:311; pipeline.hip step 4; s_final_band, s_final_certified) ----
 __global__ void s_align_final_plan_kernel(SParams p, const SGeom* __restrict__ geom, STrace* __restrict__ tr, const uint32_t* __restrict__ ends,
                                           uint32_t* __restrict__ dead, PairDesc* __restrict__ cand, uint8_t* __restrict__ kc,
                                           unsigned long long* __restrict__ cnt) {
@@ -404,24 +400,12 @@ __global__ void s_align_final_plan_kernel(SParams p, const SGeom* __restrict__ g
   S.trim = s_trim_finish(lead, ce >= lead ? ce - lead : 0u, G.rn, p.trim_left, p.trim_right, S.fwd != 0);
   s_count(lc, SC_PRELIM_BANDED);
   const uint32_t m = G.mf, n = S.trim.len;
-  int K = 0;
-  int32_t dlo = 0, dhi = 0;
-  int64_t bw = 0;
-  if (m && n && 4ull * ((n + 7u) & ~3u) + b16_table_bytes(12) <= 60u * 1024u) {
-    const int64_t over = (int64_t)n - (int64_t)m, aover = over < 0 ? -over : over;
-    bw = (int64_t)S.gap + 48;  // the gap columns the preliminary alignment's score allowed + 48 for what the trimmed ends add, within [32, 96]
-    bw = bw < 32 ? 32 : bw > 96 ? 96 : bw;
-    const int64_t fit = ((int64_t)b16_max_window(12) - 12 - aover) / 2;  // the widest band the kernels sweep
-    if (bw > fit && fit >= 24) bw = fit;
-    dlo = (int32_t)(-bw - (over < 0 ? -over : 0));
-    dhi = (int32_t)(bw + (over > 0 ? over : 0));
-    K = b16_pick_k(dlo, dhi);
-  }
+  const SFinalBand fb = s_final_band(m, n, s_final_width(S.gap));
   uint32_t dd = 0;
-  if (!K) dd = SD_FINAL_BAND;
+  if (!fb.K) dd = SD_FINAL_BAND;
   else if (n > p.ncap) dd = SD_SHAPE;
   else {
-    S.bw = (int32_t)bw;
+    S.bw = (int32_t)fb.w;
     PairDesc q{};
     q.a1_off = G.tab_off;
     q.a1_stride = G.tab_stride;
@@ -432,9 +416,9 @@ __global__ void s_align_final_plan_kernel(SParams p, const SGeom* __restrict__ g
     q.a2_off = G.ref_off + (S.rc ? G.rn - S.trim.ri - S.trim.len : S.trim.ri);
     q.flags = S.rc ? PAIR_A2_REVCOMP : 0u;
     q.out = t;
-    q.ckpt_off = band_pack(dlo, dhi);
+    q.ckpt_off = band_pack(fb.dlo, fb.dhi);
     cand[t] = q;
-    kc[t] = (uint8_t)K;
+    kc[t] = (uint8_t)fb.K;
     s_count(lc, SC_FINAL_BANDED);
   }
   tr[t] = S;
@@ -455,8 +439,7 @@ __global__ void s_align_finish_kernel(SParams p, const STrace* __restrict__ tr, 
   if (t >= p.nt) return;
   if (dead[t]) return;
   const STrace S = tr[t];
-  const int64_t lose = (-(int64_t)p.ge) * ((int64_t)S.bw + 1);
-  if (!((int64_t)o.score_final[t] > (int64_t)top_full[t] - lose && o.ops_len[t] != 0u)) {
+  if (!s_final_certified(o.score_final[t], top_full[t], p.ge, S.bw, o.ops_len[t])) {
     dead[t] |= SD_FINAL_CHECK;
     s_count(lc, SC_FINAL_REPEATED);
     return;
@@ -1015,7 +998,7 @@ int plan_common(tracyhip_ctx* ctx, const tracyhip_params& p, const tracyhip_seqs
     G.mf = h.mf[t]; G.mt = h.mt[t]; G.tl = h.tl[t]; G.rn = h.rn[t];
     G.full_a = 2 * cls->lo + (i - cls->lo);
     G.full_b = 2 * cls->lo + (cls->hi - cls->lo) + (i - cls->lo);
-    const bool front_ok = G.mt > kFrontRows + 2u * (uint32_t)kFrontK && G.rn >= 1 && origin16_ok(&p, G.mt, G.mt - kFrontRows + 2u * (uint32_t)kFrontHalfW + 16u);
+    const bool front_ok = s_front_ok(&p, G.mt, G.rn);
     G.flags = front_ok ? SG_FRONT_OK : 0u;
     if (front_ok) max_rest = std::max(max_rest, G.mt - kFrontRows);
     if (in_trace_order) {  // (the sweeps run in the traces' own order: a slice's workspace offsets are its running sums)
@@ -1428,7 +1411,8 @@ __global__ void s_allele_plan0_kernel(SParams p, SParamsD pd, const SGeom* __res
   });
 }
 
-// the verdict of the pruned sweep; S*, c_e bound the alignment: the origin-tracking sweep over its sub-window, on its band (pipeline.hip 6.c, 6.d)
+// the verdict of the pruned sweep; S*, c_e bound the alignment: the origin-tracking sweep over its sub-window, on its band (pipeline.hip 6.c, 6.d;
+// s_sub_window)
 __global__ void s_allele_plan1_kernel(SParams p, SParamsD pd, const SGeom* __restrict__ geom, const SGeomD* __restrict__ geomd, const STrace* __restrict__ tr,
                                       const FrontOut* __restrict__ fo1, const int32_t* __restrict__ fs1, const uint32_t* __restrict__ fe1,
                                       const FrontOut* __restrict__ fo2, const int32_t* __restrict__ fs2, const uint32_t* __restrict__ fe2,
@@ -1471,7 +1455,8 @@ __global__ void s_allele_plan1_kernel(SParams p, SParamsD pd, const SGeom* __res
   });
 }
 
-// trimReferenceSlice (indigo.h:360) from the two ends; gotoh(allele, trimmed slice) (indigo.h:365) on the band around its known end (pipeline.hip 6.f)
+// trimReferenceSlice (indigo.h:360) from the two ends; gotoh(allele, trimmed slice) (indigo.h:365) on the band around its known end (pipeline.hip 6.f;
+// s_slice_band, narrowed to the walked path unless option no_origin_band)
 __global__ void s_allele_plan2_kernel(SParams p, const SGeom* __restrict__ geom, const SGeomD* __restrict__ geomd, const STrace* __restrict__ tr,
                                       const uint32_t* __restrict__ ends, SAllele* __restrict__ al, uint32_t* __restrict__ dead, PairDesc* __restrict__ cand,
                                       uint8_t* __restrict__ kc, int narrow_by_origin, unsigned long long* __restrict__ cnt) {
@@ -1490,30 +1475,8 @@ __global__ void s_allele_plan2_kernel(SParams p, const SGeom* __restrict__ geom,
   al[q] = A;
   const uint32_t m = D.sl, n = A.trim.len;
   const int64_t ce = (int64_t)cend - (int64_t)A.trim.ri;  // last column of the alignment, in the slice
-  int K = 0;
-  int32_t dlo = 0, dhi = 0;
-  if (A.gap >= 0 && m && n && ce >= 1 && ce <= (int64_t)n) {
-    const int64_t gg = A.gap < (1 << 20) ? A.gap : (1 << 20);
-    const int32_t d1 = (int32_t)ce - (int32_t)m;
-    dlo = d1 - (int32_t)gg - 1;
-    dhi = d1 + (int32_t)gg + 1;
-    // The origin sweep followed the very path the traceback will walk (the same predecessor at every maximum): it starts at row 0 in
-    // column `lead` of the window, i.e. on diagonal d0 of the slice, and ends on d1.  With v vertical and h horizontal gap steps,
-    // h - v = d1 - d0 and h + v <= g, so the path stays on [min(d0, d1) - s, max(d0, d1) + s], s = (g - |d1 - d0|) / 2 -- and a band
-    // that holds THIS path reproduces its walk: every cell of the path keeps its value (its own prefix is inside), every other value
-    // is a lower bound, so whatever lost a comparison in the full matrix loses it in the band, and what won or tied with preference
-    // is on the path.  (The other co-optimal paths, which d1 +- g would hold as well, are never walked.)  g + 3 diagonals instead of 2 g + 3.
-    if (narrow_by_origin && lead >= A.trim.ri) {
-      const int32_t d0 = (int32_t)(lead - A.trim.ri);
-      const int64_t delta = d1 > d0 ? (int64_t)d1 - d0 : (int64_t)d0 - d1;
-      if (delta <= gg) {
-        const int32_t sdev = (int32_t)((gg - delta) / 2);
-        dlo = (d0 < d1 ? d0 : d1) - sdev - 1;
-        dhi = (d0 < d1 ? d1 : d0) + sdev + 1;
-      }
-    }
-    K = b16_pick_k(dlo, dhi);
-  }
+  const SBand b = s_slice_band(m, n, ce, A.gap, narrow_by_origin != 0, lead, A.trim.ri);
+  int K = b.K;
   if (K && !s_fits_lds(n, K)) K = 0;
   if (!K) { atomicOr(dead + t, SD_ALLELE_BAND); return; }
   if (n > p.ncap) { atomicOr(dead + t, SD_SHAPE); return; }
@@ -1524,7 +1487,7 @@ __global__ void s_allele_plan2_kernel(SParams p, const SGeom* __restrict__ geom,
   d.a2_off = G.ref_off + (S.rc ? G.rn - A.trim.ri - A.trim.len : A.trim.ri);
   d.flags = S.rc ? PAIR_A2_REVCOMP : 0u;
   d.out = q;
-  d.ckpt_off = band_pack(dlo, dhi);
+  d.ckpt_off = band_pack(b.dlo, b.dhi);
   cand[q] = d;
   kc[q] = (uint8_t)K;
   s_count(lc, SC_ALLELE_BANDED0 + (int)k);
@@ -1543,7 +1506,7 @@ __global__ void s_allele_check_kernel(SParams p, const SAllele* __restrict__ al,
 }
 
 // allele 1 vs allele 2, global (indigo.h:379-387): the band guessed from what the two alleles lost against the reference, the bound
-// its score has to beat (pipeline.hip 6.i)
+// its score has to beat (pipeline.hip 6.i; s_a12_band)
 __global__ void s_a12_plan_kernel(SParams p, SParamsD pd, const SGeomD* __restrict__ geomd, const int32_t* __restrict__ ascore, uint32_t* __restrict__ dead,
                                   PairDesc* __restrict__ cand, uint8_t* __restrict__ kc, long long* __restrict__ bound, unsigned long long* __restrict__ cnt) {
   with_counters(cnt, [&](unsigned long long* lc) {
@@ -1553,21 +1516,9 @@ __global__ void s_a12_plan_kernel(SParams p, SParamsD pd, const SGeomD* __restri
   if (dead[t]) return;
   const SGeomD D = geomd[t];
   const uint32_t m = D.sl;
-  int K = 0;
-  int32_t dlo = 0, dhi = 0;
-  if (m) {
-    const int64_t best = pd.best, age = -(int64_t)p.ge, ago = -(int64_t)p.go;
-    const int64_t l0 = best * m - ascore[t], l1 = best * m - ascore[p.nt + t];
-    const int64_t lost = (l0 > 0 ? l0 : 0) + (l1 > 0 ? l1 : 0);
-    const int64_t per = best + 2 * age;
-    int64_t W = (5 * lost / 2 + 40) / (per > 0 ? per : 1) + 2;
-    if (W > 90) W = 90;
-    dlo = (int32_t)-W;
-    dhi = (int32_t)W;
-    K = b16_pick_k(dlo, dhi);
-    const int64_t v = W + 1, h = W + 1;
-    bound[t] = best * ((int64_t)m - v) - age * (v + h) - 2 * ago;
-  }
+  const SA12Band b = s_a12_band(m, pd.best, p.go, p.ge, ascore[t], ascore[p.nt + t]);
+  if (m) bound[t] = b.bound;
+  int K = b.K;
   if (K && !s_fits_lds(m, K)) K = 0;
   if (!K) { dead[t] |= SD_A12_BAND; return; }
   PairDesc d{};
@@ -1575,7 +1526,7 @@ __global__ void s_a12_plan_kernel(SParams p, SParamsD pd, const SGeomD* __restri
   d.m = m; d.n = m; d.a2_stride = m;
   d.a2_off = D.bc_off + D.soff;
   d.out = t;
-  d.ckpt_off = band_pack(dlo, dhi);
+  d.ckpt_off = band_pack(b.dlo, b.dhi);
   cand[t] = d;
   kc[t] = (uint8_t)K;
   s_count(lc, SC_ALLELE_BANDED2);
@@ -1814,9 +1765,7 @@ struct DecStream {
       if ((uint64_t)(uint32_t)(TL + TR + 1) >= (uint64_t)h.mf[t]) { soff = 0; sl = h.mf[t]; }
       else { soff = TL; sl = h.mf[t] - TL - TR; }
     };
-    auto front_ok = [&](uint32_t t, uint32_t sl) {
-      return sl > kFrontRows + 2u * (uint32_t)kFrontK && h.rn[t] >= 1 && origin16_ok(&p, sl, sl - kFrontRows + 2u * (uint32_t)kFrontHalfW + 16u);
-    };
+    auto front_ok = [&](uint32_t t, uint32_t sl) { return s_front_ok(&p, sl, h.rn[t]); };
     uint64_t base_atab[kHostThreads], base_alr[kHostThreads], base_tot1[kHostThreads];
     uint64_t rows_traces = 0;
     PlanHooks hooks;

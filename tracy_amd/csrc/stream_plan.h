@@ -1,12 +1,14 @@
-// stream_plan.h -- what the stream-ordered pipelines (stream.hip) keep on the device between two launches, and the planning steps
-// that used to run on the host between two synchronisations (pipeline.hip) as functions of that state: which strand to prune,
-// which band an alignment's score allows, which strip height sweeps it, whether a certificate held.  One thread per trace; the
-// arithmetic is the host planner's, line by line (cited where it is), so that a trace takes the same tier on either path -- and a
-// trace whose tier the device cannot give it (a failed certificate, a band wider than the band kernels hold) is marked `dead` and
-// handed to the host-planned tiers afterwards.  TR_HD: the same functions compile for the host (tests).
+// stream_plan.h -- what the stream-ordered pipelines (stream.hip) keep on the device between two launches, and the per-trace planning
+// rules of both pipelines: which strand to prune, which band an alignment's score allows, whether a band fits the band kernels,
+// whether a certificate held, trimReferenceSlice's last step.  Each rule is written once here, as a TR_HD function: the planning
+// kernels of stream.hip (one thread per trace) and the host-planned tiers of pipeline.hip call the same ones, so that a trace takes
+// the same tier on either path -- and a trace whose tier the device cannot give it (a failed certificate, a band wider than the band
+// kernels hold) is marked `dead` and handed to the host-planned tiers afterwards.  Where the two planners differ on purpose, the
+// difference is an argument.  The header compiles for the host alone (tests/cpp/plan_rules.cpp).
 #ifndef TRACY_AMD_STREAM_PLAN_H
 #define TRACY_AMD_STREAM_PLAN_H
 
+#include "../../include/tracy_hip.h"
 #include "band16.h"
 #include "front.h"
 
@@ -75,7 +77,12 @@ struct SGeomD {         // `tracy decompose`: the rest
   uint32_t flags[2];     // SG_FRONT_OK per allele
 };
 
-struct TrimRec { uint32_t ri, len, pos, pad; };  // trimReferenceSlice's three numbers (pipe_kernels.h TrimOut)
+struct TrimRec {        // trimReferenceSlice's three numbers
+  uint32_t ri;          // offset of the trimmed slice in the oriented reference
+  uint32_t len;         // its length after std::string::substr clamping
+  uint32_t pos;         // rs.pos after the update (rs.pos starts at 0)
+  uint32_t pad;
+};
 
 struct STrace {         // one trace: what the stages leave for each other
   int32_t sc[2];        // gsFwd, gsRev (the loser's may be its certified bound)
@@ -109,7 +116,7 @@ struct SParams {        // scoring + switches every planning kernel sees
 TR_HD int64_t s_abs64(int32_t x) { return x < 0 ? -(int64_t)x : (int64_t)x; }
 TR_HD int64_t s_best(const SParams& p) { const int64_t b = p.match > p.mismatch ? p.match : p.mismatch; return b > 0 ? b : 0; }
 
-// the widening / clamping / rs.pos part of trimReferenceSlice (fmindex.h:443-461)
+// R9. the widening / clamping / rs.pos part of trimReferenceSlice (fmindex.h:443-461)
 TR_HD TrimRec s_trim_finish(uint32_t ri, uint32_t risize, uint32_t n, uint32_t trim_left, uint32_t trim_right, bool forward) {
   if (ri >= trim_left) { ri -= trim_left; risize += trim_left; }
   if ((uint32_t)(ri + risize + trim_right) < n) risize += trim_right;
@@ -126,9 +133,48 @@ TR_HD TrimRec s_trim_finish(uint32_t ri, uint32_t risize, uint32_t n, uint32_t t
   return r;
 }
 
-// A path that ends at (m, c_e) with score S* and can collect at most `top` on its diagonal steps has at most g = (top - S*) / |ge|
-// gap columns: it lies in the columns (a, c_e], a = c_e - m - g - 2 (pipeline.hip, stage 2 of orient_and_align and the allele
-// stage), on the diagonals (n' - m) +- (g + 1) of that sub-window of n' = c_e - a columns.
+// value ranges of the origin-tracking sweep on the band kernels (b16_origin_ok) for m rows / n columns, in the domain they take
+// (AlignConfig<true,false>)
+TR_HD bool origin16_ok(const tracyhip_params* prm, uint32_t maxm, uint32_t maxn) {
+  if (!prm->hfree || prm->vfree) return false;
+  return b16_origin_ok(prm->match, prm->mismatch, prm->go, prm->ge, maxm, maxn);
+}
+
+// R2. a pruned sweep (front.h) of m rows against n columns is eligible: two strips of kFrontK rows below the prefix's kFrontRows, a
+// column, and the value ranges of the origin-tracking sweep over the widest sub-window the placement can give it
+TR_HD bool s_front_ok(const tracyhip_params* prm, uint32_t m, uint32_t n) {
+  return m > kFrontRows + 2u * (uint32_t)kFrontK && n >= 1 && origin16_ok(prm, m, m - kFrontRows + 2u * (uint32_t)kFrontHalfW + 16u);
+}
+
+// R1. class of a trace from its k-mer votes vf / vr for the two strands.  g: the voted strand.  both: no clear majority of shared k-mers
+// (or no rows below the prefix), both strands are swept.  cls 0: pruned sweep of g (front_ok: R2); 1: both strands in full (`exact`:
+// both scores are needed exactly); 2: g in full + the prefix of the other (strand by certificate)
+struct SOrient { uint32_t g, both, cls; };
+TR_HD SOrient s_orient_class(uint32_t vf, uint32_t vr, uint32_t m, bool front_ok, bool exact) {
+  SOrient o;
+  o.g = vf >= vr ? 0u : 1u;
+  const uint32_t hi_v = vf >= vr ? vf : vr, lo_v = vf >= vr ? vr : vf;
+  o.both = (m > kFrontRows && hi_v >= 32u && hi_v >= 2u * lo_v) ? 0u : 1u;
+  o.cls = (!o.both && front_ok) ? 0u : (exact || o.both) ? 1u : 2u;
+  return o;
+}
+
+// diagonals [dlo, dhi] of a band and the strip height that sweeps it (b16_pick_k; 0: too wide)
+struct SBand { int32_t dlo, dhi; int K; };
+// the band around an alignment that ends in column ce of row m with at most g gap steps: diagonals (ce - m) +- (g + 1)
+TR_HD SBand s_end_band(uint32_t m, int64_t ce, int64_t g) {
+  const int64_t gg = g < (1 << 20) ? g : (1 << 20);
+  const int32_t d1 = (int32_t)ce - (int32_t)m;
+  SBand b;
+  b.dlo = d1 - (int32_t)gg - 1;
+  b.dhi = d1 + (int32_t)gg + 1;
+  b.K = b16_pick_k(b.dlo, b.dhi);
+  return b;
+}
+
+// R3. A path that ends at (m, c_e) with score S* and can collect at most `top` on its diagonal steps has at most g = (top - S*) / |ge|
+// gap columns: it lies in the columns (a, c_e], a = c_e - m - g - 2, on the band s_end_band(m, n', g) of that sub-window of
+// n' = c_e - a columns (preliminary alignment of `tracy align`, gotoh(allele, window) of `tracy decompose`).
 struct SubWindow { int64_t g; uint32_t a, n; int32_t dlo, dhi; int K; };
 TR_HD SubWindow s_sub_window(uint32_t m, uint32_t ce, int64_t top, int64_t sstar, int32_t ge) {
   SubWindow s;
@@ -138,15 +184,89 @@ TR_HD SubWindow s_sub_window(uint32_t m, uint32_t ce, int64_t top, int64_t sstar
   if (a < 0) a = 0;
   s.a = (uint32_t)a;
   s.n = (uint32_t)((int64_t)ce - a);
-  const int64_t gg = s.g < (1 << 20) ? s.g : (1 << 20);
-  const int32_t d1 = (int32_t)s.n - (int32_t)m;
-  s.dlo = d1 - (int32_t)gg - 1;
-  s.dhi = d1 + (int32_t)gg + 1;
-  s.K = s.g < (1 << 20) ? b16_pick_k(s.dlo, s.dhi) : 0;
+  const SBand b = s_end_band(m, s.n, s.g);
+  s.dlo = b.dlo;
+  s.dhi = b.dhi;
+  s.K = b.K;
   return s;
 }
-// LDS of a band launch: the codes of four pairs + the tables (run_band16's staging limit, as the host planners test it)
+// R4. LDS of a band launch: the codes of four pairs + the tables (the planners' limit; run_band16 refuses a launch past 64 KiB)
 TR_HD bool s_fits_lds(uint32_t n, int K) { return 4ull * ((n + 7u) & ~3u) + b16_table_bytes(K) <= 60u * 1024u; }
+
+// R5. `tracy align`, final alignment gotoh(full profile, trimmed slice) of m x n on a band of half width w: the gap columns the
+// preliminary alignment's score allowed + 48 for what the trimmed ends add, within [32, 96] ...
+TR_HD int64_t s_final_width(uint32_t gap) {
+  const int64_t w = (int64_t)gap + 48;
+  return w < 32 ? 32 : w > 96 ? 96 : w;
+}
+// ... or the width the caller wants (host planner: option band_w), narrowed to what one period of the K = 12 strips holds when that
+// leaves at least 24; diagonals [-w - (m-n)+, w + (n-m)+].  K = 0: no band (an empty pair, a slice past the LDS limit, too wide)
+struct SFinalBand { int64_t w; int32_t dlo, dhi; int K; };
+TR_HD SFinalBand s_final_band(uint32_t m, uint32_t n, int64_t want) {
+  SFinalBand f{0, 0, 0, 0};
+  if (!(m && n && s_fits_lds(n, 12))) return f;
+  const int64_t over = (int64_t)n - (int64_t)m, aover = over < 0 ? -over : over;
+  const int64_t fit = ((int64_t)b16_max_window(12) - 12 - aover) / 2;  // the widest band the kernels sweep
+  f.w = want > fit && fit >= 24 ? fit : want;
+  f.dlo = (int32_t)(-f.w - (over < 0 ? -over : 0));
+  f.dhi = (int32_t)(f.w + (over > 0 ? over : 0));
+  f.K = b16_pick_k(f.dlo, f.dhi);
+  return f;
+}
+// R6. its certificate: a path that leaves the band makes more than w interior gap steps and scores at most top - |ge| (w + 1); a banded
+// score S_b above that (and a walk that stayed inside: ops_len != 0) is the optimum
+TR_HD bool s_final_certified(int32_t sb, int32_t top, int32_t ge, int64_t w, uint32_t ops_len) {
+  return (int64_t)sb > (int64_t)top - (-(int64_t)ge) * (w + 1) && ops_len != 0u;
+}
+
+// R7. gotoh(allele, trimmed slice) of m x n: the alignment ends in slice column ce of row m with at most g gap steps (g < 0: not
+// known), on the diagonals s_end_band(m, ce, g).  narrow (stream.hip, unless option no_origin_band): the origin sweep followed the
+// very path the traceback will walk (the same predecessor at every maximum); it starts at row 0 in column `lead` of the window, i.e.
+// on diagonal d0 = lead - ri of the slice (ri: where the slice begins; lead < ri: unknown), and ends on d1.  With v vertical and h
+// horizontal gap steps, h - v = d1 - d0 and h + v <= g, so the path stays on [min(d0, d1) - s, max(d0, d1) + s], s = (g - |d1 - d0|) / 2
+// -- and a band that holds THIS path reproduces its walk: every cell of the path keeps its value (its own prefix is inside), every
+// other value is a lower bound, so whatever lost a comparison in the full matrix loses it in the band, and what won or tied with
+// preference is on the path.  (The other co-optimal paths, which d1 +- g would hold as well, are never walked.)  g + 3 diagonals
+// instead of 2 g + 3.  The host planner does not narrow.
+TR_HD SBand s_slice_band(uint32_t m, uint32_t n, int64_t ce, int64_t g, bool narrow, uint32_t lead, uint32_t ri) {
+  SBand b{0, 0, 0};
+  if (!(g >= 0 && m && n && ce >= 1 && ce <= (int64_t)n)) return b;
+  b = s_end_band(m, ce, g);
+  if (narrow && lead >= ri) {
+    const int64_t gg = g < (1 << 20) ? g : (1 << 20);
+    const int32_t d0 = (int32_t)(lead - ri), d1 = (int32_t)ce - (int32_t)m;
+    const int64_t delta = d1 > d0 ? (int64_t)d1 - d0 : (int64_t)d0 - d1;
+    if (delta <= gg) {
+      const int32_t sdev = (int32_t)((gg - delta) / 2);
+      b.dlo = (d0 < d1 ? d0 : d1) - sdev - 1;
+      b.dhi = (d0 < d1 ? d1 : d0) + sdev + 1;
+      b.K = b16_pick_k(b.dlo, b.dhi);
+    }
+  }
+  return b;
+}
+
+// R8. allele 1 vs allele 2, global (indigo.h:379-387), both of `len` bases (the trimmed trace).  W is guessed from what the two alleles
+// lost against the reference (scores sc1, sc2; they differ from each other by about as much as both differ from it), at most 90.  Both
+// ends are fixed: a path that leaves the diagonals [-W, W] makes at least W + 1 vertical and W + 1 horizontal gap steps in two runs,
+// so it scores at most `bound` = best (len - W - 1) - |ge| 2 (W + 1) - 2 |go|; a banded score above that is the optimum.  (For
+// alleles of different lengths the band and the bound would widen by (m - n)+ / (n - m)+; here they are always the same length.)
+struct SA12Band { int32_t dlo, dhi; int K; int64_t bound; };
+TR_HD SA12Band s_a12_band(uint32_t len, int64_t best, int32_t go, int32_t ge, int32_t sc1, int32_t sc2) {
+  SA12Band r{0, 0, 0, 0};
+  if (len == 0) return r;
+  const int64_t age = -(int64_t)ge, ago = -(int64_t)go;
+  const int64_t l0 = best * len - sc1, l1 = best * len - sc2;
+  const int64_t lost = (l0 > 0 ? l0 : 0) + (l1 > 0 ? l1 : 0);
+  const int64_t per = best + 2 * age;
+  int64_t W = (5 * lost / 2 + 40) / (per > 0 ? per : 1) + 2;
+  if (W > 90) W = 90;
+  r.dlo = (int32_t)-W;
+  r.dhi = (int32_t)W;
+  r.K = b16_pick_k(r.dlo, r.dhi);
+  r.bound = best * ((int64_t)len - (W + 1)) - age * 2 * (W + 1) - 2 * ago;
+  return r;
+}
 
 // what the first tier of a pruned sweep over m_rest rows below the kept row and n columns is credited with (run_front_once's sums)
 TR_HD uint64_t s_front_cells(uint32_t m_rest) { return (uint64_t)b16_strips(m_rest, 8) * 8u * (8u + 2u * 60u); }
