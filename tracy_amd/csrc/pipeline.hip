@@ -16,6 +16,7 @@
 #include "launch.h"
 #include "pipe_internal.h"
 #include "pipe_kernels.h"
+#include "stream_fields.h"
 
 using namespace tracyhip;
 
@@ -1308,10 +1309,8 @@ struct AlignChunk {
     else { sub_seqset(job->refs, lo, k, 1, sr); j.refs = sr.s; }
     j.oriented = shifted(job->oriented, lo);
     sub_offsets(out->ops_offset, lo, k, so);
-    o.score_fwd = shifted(out->score_fwd, lo); o.score_rev = shifted(out->score_rev, lo); o.forward = shifted(out->forward, lo);
-    o.score_prelim = shifted(out->score_prelim, lo); o.slice_begin = shifted(out->slice_begin, lo);
-    o.slice_len = shifted(out->slice_len, lo); o.ref_pos = shifted(out->ref_pos, lo); o.score_final = shifted(out->score_final, lo);
-    o.ops = shifted(out->ops, so.base); o.ops_offset = so.off.data(); o.ops_len = shifted(out->ops_len, lo);
+    AlignFields::each(o, *out, [&](auto& mine, auto& theirs, uint32_t per) { mine = shifted(theirs, (uint64_t)per * lo); });
+    o.ops = shifted(out->ops, so.base); o.ops_offset = so.off.data();
   }
 };
 }  // namespace
@@ -2361,18 +2360,14 @@ struct DecomposeChunk {
     j.bc.primary = shifted(job->bc.primary, bco.base);
     j.bc.secondary = shifted(job->bc.secondary, bco.base); j.bc.bc_offset = bco.off.data(); j.bc.bc_len = job->bc.bc_len + lo;
     // results
-    o.bp = shifted(out->bp, lo); o.status = shifted(out->status, lo); o.score_fwd = shifted(out->score_fwd, lo);
-    o.score_rev = shifted(out->score_rev, lo); o.forward = shifted(out->forward, lo); o.score_trim = shifted(out->score_trim, lo);
+    DecompFields::each(o, *out, [&](auto& mine, auto& theirs, uint32_t per) { mine = shifted(theirs, (uint64_t)per * lo); });
     sub_offsets(out->dcp_offset, lo, k, dcp);
     o.dcp_indel = shifted(out->dcp_indel, dcp.base); o.dcp_err = shifted(out->dcp_err, dcp.base); o.dcp_offset = dcp.off.data();
-    o.dstatus = shifted(out->dstatus, lo); o.secdecomp = shifted(out->secdecomp, bco.base); o.fractions = shifted(out->fractions, 2ull * lo);
-    for (int a = 0; a < 2; ++a) {
-      o.slice_begin[a] = shifted(out->slice_begin[a], lo); o.slice_len[a] = shifted(out->slice_len[a], lo); o.ref_pos[a] = shifted(out->ref_pos[a], lo);
-    }
+    o.secdecomp = shifted(out->secdecomp, bco.base);
     for (int a = 0; a < 3; ++a) {
       sub_offsets(out->ops_offset[a], lo, k, ops[a]);
-      o.score[a] = shifted(out->score[a], lo); o.ops[a] = shifted(out->ops[a], ops[a].base);
-      o.ops_offset[a] = ops[a].off.data(); o.ops_len[a] = shifted(out->ops_len[a], lo);
+      o.ops[a] = shifted(out->ops[a], ops[a].base);
+      o.ops_offset[a] = ops[a].off.data();
     }
   }
 };

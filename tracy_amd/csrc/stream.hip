@@ -20,6 +20,8 @@
 #include <algorithm>
 #include <cstring>
 #include <numeric>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/tracy_hip.h"
@@ -28,6 +30,7 @@
 #include "launch.h"
 #include "pipe_internal.h"
 #include "pipe_kernels.h"
+#include "stream_fields.h"
 #include "stream_plan.h"
 
 using namespace tracyhip;
@@ -54,6 +57,8 @@ struct Arena {
     off += sizeof(T) * (count ? count : 1);
     return p;
   }
+  template <class T>
+  void take_into(T*& p, size_t count) { p = take<T>(count); }
 };
 
 // Counters of a planning kernel: summed per workgroup in LDS, one global atomic per counter and workgroup at the end (10^5 threads
@@ -455,6 +460,7 @@ __global__ void s_align_finish_kernel(SParams p, const STrace* __restrict__ tr, 
 }
 
 // results of the dead traces, computed by the host-planned pipeline into compact arrays, back to their places
+struct Frac2 { double a, b; };  // (allelicFraction's two doubles of a trace move as one element)
 template <class T>
 __global__ void s_scatter_kernel(const uint32_t* __restrict__ list, uint32_t n, const T* __restrict__ src, T* __restrict__ dst) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1067,6 +1073,208 @@ void stats_from_counters(tracyhip_ctx* ctx, const unsigned long long* c, const u
     }
 }
 
+// ---- the frame of a stream-ordered call: what stream_align and stream_decompose do AROUND their stages, written once ----
+
+// a reason a call marks traces dead with (SD_*) and its name in the call's verbose line
+struct DeadReason { uint32_t bit; const char* name; };
+
+// The pinned block the call's one read-back lands in: verdict words, counters, band statistics, dead flags, then `extra_bytes` of the
+// call's own (align: the slice lengths; decompose: the verdict of the case-sensitive encoders).  The copies are queued in two parts
+// because the calls put their own copy at different places of the sequence.
+struct ReadBack {
+  int32_t* herr = nullptr;
+  unsigned long long *hcnt = nullptr, *hbst = nullptr;
+  uint32_t* hdead = nullptr;
+  void* extra = nullptr;
+  int carve(tracyhip_ctx* ctx, uint32_t nt, size_t extra_bytes) {
+    HIP_TRY(ctx->h_res.ensure(kErrBytes + sizeof(unsigned long long) * (SC_COUNT + SB_COUNT * 8) + sizeof(uint32_t) * (size_t)nt + extra_bytes));
+    herr = static_cast<int32_t*>(ctx->h_res.p);
+    hcnt = reinterpret_cast<unsigned long long*>(herr + kErrWords + 4);
+    hbst = hcnt + SC_COUNT;
+    hdead = reinterpret_cast<uint32_t*>(hbst + SB_COUNT * 8);
+    extra = hdead + nt;
+    return TRACYHIP_OK;
+  }
+  int queue_verdict(tracyhip_ctx* ctx, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(herr, ctx->d_err.p, kErrBytes, hipMemcpyDeviceToHost, st));
+    return TRACYHIP_OK;
+  }
+  int queue_counters(const StreamCommon& sc, uint32_t nt, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(hcnt, sc.cnt, sizeof(unsigned long long) * SC_COUNT, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hbst, sc.bstat, sizeof(unsigned long long) * SB_COUNT * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hdead, sc.dead, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
+    return TRACYHIP_OK;
+  }
+};
+
+// every per-trace result array of the list Fields (stream_fields.h) ...
+// ... carved from the arena (in list order; every take is rounded to 256 bytes, so the block's size does not depend on the order)
+template <class Fields, class Out>
+void carve_all(Arena& a, uint32_t nt, Out& x) {
+  Fields::each(x, x, [&](auto& p, auto&, uint32_t per) { a.take_into(p, (size_t)per * nt); });
+}
+// ... pointed where another struct's is
+template <class Fields, class To, class From>
+void point_all(To& to, const From& from) {
+  Fields::each(to, from, [](auto& t, auto& f, uint32_t) { t = f; });
+}
+// ... of the dead traces (compact, from the host-planned pipeline) back to their places
+template <class Fields, class Out>
+int scatter_all(hipStream_t st, const uint32_t* d_list, uint32_t n, Out& compact, Out& o) {
+  int rc = TRACYHIP_OK;
+  Fields::each(compact, o, [&](auto* src, auto* dst, uint32_t per) {
+    if (rc != TRACYHIP_OK) return;
+    if constexpr (std::is_same_v<decltype(src), double*>)  // (allelicFraction: the two doubles of a trace move as one element)
+      rc = scatter(st, d_list, n, reinterpret_cast<const Frac2*>(src), reinterpret_cast<Frac2*>(dst));
+    else
+      rc = scatter(st, d_list, n, src, dst);
+  });
+  return rc;
+}
+// ... to the caller's host memory
+int copy_to_host(hipStream_t st, void* user, const void* dev, size_t bytes) {
+  if (user && bytes) HIP_TRY(hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, st));
+  return TRACYHIP_OK;
+}
+template <class Fields, class Result, class Out>
+int copy_back_all(hipStream_t st, uint32_t nt, const Result& user, Out& o) {
+  int rc = TRACYHIP_OK;
+  Fields::each(user, o, [&](auto& u, auto& d, uint32_t per) {
+    if (rc == TRACYHIP_OK) rc = copy_to_host(st, u, d, sizeof(*d) * per * (size_t)nt);
+  });
+  return rc;
+}
+
+// What both calls keep of a call, and the sections both queue.  The stages themselves -- and everything the calls do differently on
+// purpose -- are the derived structs' (AlignStream, DecStream).
+struct StreamCall {
+  tracyhip_ctx* ctx;
+  const tracyhip_params* prm;
+  const int mem;
+  const CtxKnobs& kn;
+  const uint32_t nt;
+  const tracyhip_seqset &sp, &sr;
+  hipStream_t st;
+  tracyhip_params p;
+  const uint32_t TL, TR;
+  const bool exact, host;
+  StreamHost& h;
+  SGeom* geom = nullptr;
+  uint32_t ncap = 0;
+  uint64_t words_cap = 0;
+  SParams spm{};
+  dim3 g256, b256;
+  const int16_t* d_qp = nullptr;
+  int32_t* d_lastrow = nullptr;
+  ReadBack rb;
+  std::vector<uint32_t> dl;  // the traces the device could not give their tier
+  std::vector<uint64_t> sub_poff;  // ... as a sub-job: profile offsets, lengths, reference indices
+  std::vector<uint32_t> sub_plen, sub_ridx;
+
+  template <class Job>
+  StreamCall(tracyhip_ctx* c, const Job* j, const tracyhip_params* q, int m, uint32_t trim_l, uint32_t trim_r, StreamHost& h_)
+      : ctx(c), prm(q), mem(m), kn(c->knobs), nt(j->ntraces), sp(j->profiles), sr(j->refs), st(c->stream), p(*q), TL(trim_l), TR(trim_r),
+        exact(j->strand_by_certificate == 0), host(m == TRACYHIP_MEM_HOST), h(h_), g256((j->ntraces + 255) / 256), b256(256) {
+    p.hfree = 1;  // AlignConfig<true,false> semiglobal (sage.h:165, indigo.h:164)
+    p.vfree = 0;
+  }
+
+  // columns the band launches stage per pair (the longest trace and its margins): beside the widest substitution table they must fit the LDS
+  int size_ncap() {
+    ncap = (h.maxmf + 200u + 7u) & ~3u;
+    return 4ull * ncap + b16_table_bytes(12) > 64u * 1024u ? kStreamNo : TRACYHIP_OK;
+  }
+
+  // verdict words cleared, the reference windows encoded to profile-row codes (with their block map and the validation verdict)
+  int encode_references(const uint8_t* refs, uint64_t er) {
+    HIP_TRY(ctx->d_err.ensure(kErrBytes));
+    HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, kErrBytes, st));
+    int32_t* d_verr = static_cast<int32_t*>(ctx->d_err.p) + kErrVerdictWord;
+    HIP_TRY(ctx->ensure_codes(er ? er : 1, st));
+    if (er) {
+      hipLaunchKernelGGL(encode_codes_kernel, dim3((unsigned)((er + 4095) / 4096)), dim3(256), 0, st, refs, ctx->codes(), er, ctx->special_blocks(), d_verr);
+      HIP_TRY(hipGetLastError());
+    }
+    return TRACYHIP_OK;
+  }
+
+  // the records: one pinned block (SGeom per trace, then the call's own array), two copies; the per-call arrays cleared
+  int upload_records(StreamCommon& sc, void* d_own, size_t own_bytes) {
+    HIP_TRY(hipMemcpyAsync(sc.geom, geom, sizeof(SGeom) * (size_t)nt, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_own, geom + nt, own_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(sc.dead, 0, sizeof(uint32_t) * (size_t)nt, st));
+    HIP_TRY(hipMemsetAsync(sc.cnt, 0, sizeof(unsigned long long) * SC_COUNT, st));
+    HIP_TRY(hipMemsetAsync(sc.bstat, 0, sizeof(unsigned long long) * SB_COUNT * 8, st));
+    return TRACYHIP_OK;
+  }
+
+  // what the planning kernels know of the call, and the buffers every stage reads
+  void fill_params() {
+    spm.match = p.match; spm.mismatch = p.mismatch; spm.go = p.go; spm.ge = p.ge; spm.nt = nt; spm.exact = exact ? 1u : 0u; spm.ncap = ncap - 8u;
+    spm.trim_left = TL; spm.trim_right = TR; spm.use_votes = 1u;
+    spm.split_prefix = kn.sweeps_alone ? 1u : 0u;
+    d_qp = static_cast<const int16_t*>(ctx->d_b16tab[2].p);
+    d_lastrow = static_cast<int32_t*>(ctx->d_lastrow.p);
+  }
+
+  // The call's one synchronisation, then what its launches reported: lower-case reference windows are the caller's error, values
+  // outside the 16-bit kernels' range hand the call to the host-planned pipeline.  give_up(rc) is what the call does before it returns
+  // a verdict (decompose: DecStream::give_up; align has nothing to put back).
+  template <class GiveUp>
+  int await_verdict(GiveUp give_up) {
+    HIP_TRY(ctx_sync(ctx));
+    timing_collect(ctx);
+    if (rb.herr[kErrVerdictWord] & 4) {
+      (void)give_up(kStreamNo);
+      return set_error(TRACYHIP_ERR_ARG, "reference windows must be upper-case [ACGTN] (loadSingleFasta, fasta.h:54-95)");
+    }
+    return give_up(stream_range_verdict(p, rb.herr, h));
+  }
+
+  // the call's statistics from its counters; the traces the device could not give their tier, and (verbose) why
+  template <size_t NS, size_t NR>
+  void list_dead(const char* what, const int (&stage_timer)[NS], const DeadReason (&reasons)[NR]) {
+    stats_from_counters(ctx, rb.hcnt, rb.hbst, (int)NS, stage_timer);
+    ctx->stats.stream_ordered = 1;
+    dl.clear();
+    for (uint32_t t = 0; t < nt; ++t)
+      if (rb.hdead[t]) dl.push_back(t);
+    ctx->stats.fallback_traces += (uint32_t)dl.size();
+    if (kn.verbose) {
+      std::string why;
+      for (const DeadReason& r : reasons) {
+        uint32_t n = 0;
+        for (uint32_t t : dl) n += (rb.hdead[t] & r.bit) != 0u;
+        why += (why.empty() ? "" : ", ") + std::string(r.name) + " " + std::to_string(n);
+      }
+      fprintf(stderr, "stream-ordered %s: %u traces, %zu to the host-planned tiers (%s)\n", what, nt, dl.size(), why.c_str());
+    }
+  }
+
+  // the dead traces as a job of their own for the host-planned pipeline: payloads where they lie on the device, offsets by the list
+  template <class Job>
+  void sub_job(Job& j, const void* d_prof, const void* d_ref) {
+    const uint32_t nd = (uint32_t)dl.size();
+    sub_poff.resize(nd); sub_plen.resize(nd); sub_ridx.resize(nd);
+    for (uint32_t i = 0; i < nd; ++i) { const uint32_t t = dl[i]; sub_poff[i] = sp.offset[t]; sub_plen[i] = sp.length[t]; sub_ridx[i] = h.ridx[t]; }
+    j.ntraces = nd;
+    j.profiles.data = d_prof; j.profiles.offset = sub_poff.data(); j.profiles.length = sub_plen.data(); j.profiles.count = nd;
+    j.refs.data = d_ref;
+    j.ref_index = sub_ridx.data();
+  }
+
+  // run() is the host-planned pipeline on the sub-job: the call's statistics stay the stream-ordered call's, only its synchronisations count
+  template <class Run>
+  int host_planned(Run run) {
+    const tracyhip_call_stats keep = ctx->stats;
+    TRY(run());
+    const uint32_t syncs = ctx->stats.host_syncs;
+    ctx->stats = keep;
+    ctx->stats.host_syncs = syncs;
+    return TRACYHIP_OK;
+  }
+};
+
 }  // namespace
 
 // =====================================================================================================================
@@ -1085,204 +1293,169 @@ struct AlignArena {
   void layout(Arena& a, uint32_t nt, bool exact, bool host_results, uint64_t ops_bound) {
     sc.layout(a, nt, nt, exact, true);
     ops_off = a.take<uint64_t>(nt);
-    auto per_trace = [&](AlignOutDev& x) {
-      x.score_fwd = a.take<int32_t>(nt); x.score_rev = a.take<int32_t>(nt); x.score_prelim = a.take<int32_t>(nt); x.score_final = a.take<int32_t>(nt);
-      x.forward = a.take<uint8_t>(nt); x.slice_begin = a.take<uint32_t>(nt); x.slice_len = a.take<uint32_t>(nt); x.ref_pos = a.take<uint32_t>(nt);
-      x.ops_len = a.take<uint32_t>(nt);
-    };
     o = AlignOutDev{};
     ops = nullptr;
-    if (host_results) { per_trace(o); ops = a.take<uint8_t>(ops_bound); }
-    per_trace(f);
+    if (host_results) { carve_all<AlignFields>(a, nt, o); ops = a.take<uint8_t>(ops_bound); }
+    carve_all<AlignFields>(a, nt, f);
     dead_list = a.take<uint32_t>(nt);
   }
 };
-}  // namespace
 
-int tracyhip::stream_align(tracyhip_ctx* ctx, const tracyhip_align_job* job, const tracyhip_params* prm, int mem, const tracyhip_align_result* out) {
-  const CtxKnobs& kn = ctx->knobs;
-  if (!stream_options_ok(kn) || job->oriented) return kStreamNo;
-  const uint32_t nt = job->ntraces;
-  const tracyhip_seqset& sp = job->profiles;
-  const tracyhip_seqset& sr = job->refs;
-  hipStream_t st = ctx->stream;
-  tracyhip_params p = *prm;
-  p.hfree = 1;  // AlignConfig<true,false> semiglobal (sage.h:165)
-  p.vfree = 0;
-  static thread_local StreamHost h;
-  // geometry and the ops offsets are laid out in the pinned block they travel from: one copy, no staging
-  HIP_TRY(ctx->h_desc.ensure(sizeof(SGeom) * (size_t)nt + sizeof(uint64_t) * (size_t)nt));
-  SGeom* geom = static_cast<SGeom*>(ctx->h_desc.p);
-  { TRACYHIP_HOST_SCOPE(hsa, "stream_align.plan_common"); TRY(plan_common(ctx, p, sp, sr, job->ref_index, nt, job->trim_left, job->trim_right, h, geom)); }
-  TRACYHIP_HOST_SCOPE(hsb, "stream_align.rest_of_call");
-  const bool exact = job->strand_by_certificate == 0;
-  const bool host_results = mem == TRACYHIP_MEM_HOST;
+// One stream-ordered tracyhip_align_traces call: one method per section (queued in this order), as DecStream below
+struct AlignStream : StreamCall {
+  const tracyhip_align_job* job;
+  const tracyhip_align_result* out;
   uint64_t ops_bound = 1;
-  for (uint32_t t = 0; t < nt; ++t) {
-    geom[t].ops_off = out->ops_offset[t];
-    ops_bound = std::max<uint64_t>(ops_bound, out->ops_offset[t] + h.mf[t] + h.rn[t]);
-  }
-  const uint32_t ncap = (h.maxmf + 200u + 7u) & ~3u;
-  if (4ull * ncap + b16_table_bytes(12) > 64u * 1024u) return kStreamNo;
-
-  // ---- workspace ----
-  uint64_t rows_total = 0;
-  for (uint32_t t = 0; t < nt; ++t) rows_total += h.mf[t];
-  Arena sizing;
   AlignArena A;
-  A.layout(sizing, nt, exact, host_results, ops_bound);
-  uint64_t words_cap = 0;
-  TRY(with_fresh_budget(ctx, [&](bool* from_cache) -> int {
-    uint64_t budget = 0;
-    TRY(workspace_budget(ctx, ctx->d_lastrow.cap + ctx->d_bits.cap + ctx->d_stream.cap + ctx->d_b16tab[2].cap, &budget, from_cache));
-    const uint64_t fixed = h.lr_tot * 4 + 64 + h.tab_tot * 2 + 64 + sizing.off;
-    if (fixed > budget) return kStreamNo;
-    words_cap = band_words_cap(rows_total, nt, budget - fixed);
-    HIP_TRY(ctx->d_lastrow.ensure(h.lr_tot * 4 + 64));
-    HIP_TRY(ctx->d_b16tab[2].ensure(h.tab_tot * sizeof(int16_t) + 64));
-    HIP_TRY(ctx->d_bits.ensure(words_cap + 64));
-    HIP_TRY(ctx->d_stream.ensure(sizing.off + 256));
+  const void *d_prof = nullptr, *d_ref = nullptr;
+  AlignOutDev o{};
+  uint8_t* d_ops = nullptr;
+  uint32_t* hlen = nullptr;  // the slice lengths (host-memory results: they size the copy of the ops)
+
+  AlignStream(tracyhip_ctx* c, const tracyhip_align_job* j, const tracyhip_params* q, int m, const tracyhip_align_result* o_, StreamHost& h_)
+      : StreamCall(c, j, q, m, j->trim_left, j->trim_right, h_), job(j), out(o_) {}
+
+  // geometry and the ops offsets are laid out in the pinned block they travel from: one copy, no staging
+  int pin_records() {
+    HIP_TRY(ctx->h_desc.ensure(sizeof(SGeom) * (size_t)nt + sizeof(uint64_t) * (size_t)nt));
+    geom = static_cast<SGeom*>(ctx->h_desc.p);
     return TRACYHIP_OK;
-  }));
-  Arena arena;
-  arena.base = static_cast<char*>(ctx->d_stream.p);
-  A.layout(arena, nt, exact, host_results, ops_bound);
-  StreamCommon& sc = A.sc;
+  }
+  int plan_geometry() { return plan_common(ctx, p, sp, sr, job->ref_index, nt, TL, TR, h, geom); }
 
-  // ---- payloads, the references encoded once ----
-  const uint64_t ep = seqset_extent(sp), er = seqset_extent(sr);
-  const void *d_prof, *d_ref;
-  TRY(stage_in(ctx, ctx->d_in1, sp.data, ep * 4, mem, &d_prof));
-  TRY(stage_in(ctx, ctx->d_in2, sr.data, er, mem, &d_ref));
-  HIP_TRY(ctx->d_err.ensure(kErrBytes));
-  HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, kErrBytes, st));
-  int32_t* d_verr = static_cast<int32_t*>(ctx->d_err.p) + kErrVerdictWord;
-  HIP_TRY(ctx->ensure_codes(er ? er : 1, st));
-  if (er) {
-    hipLaunchKernelGGL(encode_codes_kernel, dim3((unsigned)((er + 4095) / 4096)), dim3(256), 0, st, static_cast<const uint8_t*>(d_ref), ctx->codes(), er,
-                       ctx->special_blocks(), d_verr);
+  // what the host knows before anything runs, beside the geometry: where the ops go, the workspace
+  int plan() {
+    for (uint32_t t = 0; t < nt; ++t) {
+      geom[t].ops_off = out->ops_offset[t];
+      ops_bound = std::max<uint64_t>(ops_bound, out->ops_offset[t] + h.mf[t] + h.rn[t]);
+    }
+    TRY(size_ncap());
+
+    // ---- workspace ----
+    uint64_t rows_total = 0;
+    for (uint32_t t = 0; t < nt; ++t) rows_total += h.mf[t];
+    Arena sizing;
+    A.layout(sizing, nt, exact, host, ops_bound);
+    TRY(with_fresh_budget(ctx, [&](bool* from_cache) -> int {
+      uint64_t budget = 0;
+      TRY(workspace_budget(ctx, ctx->d_lastrow.cap + ctx->d_bits.cap + ctx->d_stream.cap + ctx->d_b16tab[2].cap, &budget, from_cache));
+      const uint64_t fixed = h.lr_tot * 4 + 64 + h.tab_tot * 2 + 64 + sizing.off;
+      if (fixed > budget) return kStreamNo;
+      words_cap = band_words_cap(rows_total, nt, budget - fixed);
+      HIP_TRY(ctx->d_lastrow.ensure(h.lr_tot * 4 + 64));
+      HIP_TRY(ctx->d_b16tab[2].ensure(h.tab_tot * sizeof(int16_t) + 64));
+      HIP_TRY(ctx->d_bits.ensure(words_cap + 64));
+      HIP_TRY(ctx->d_stream.ensure(sizing.off + 256));
+      return TRACYHIP_OK;
+    }));
+    Arena arena;
+    arena.base = static_cast<char*>(ctx->d_stream.p);
+    A.layout(arena, nt, exact, host, ops_bound);
+    return TRACYHIP_OK;
+  }
+
+  // payloads and result arrays: the caller's (device memory) or staged; references encoded once; records uploaded
+  int bind() {
+    const uint64_t ep = seqset_extent(sp), er = seqset_extent(sr);
+    TRY(stage_in(ctx, ctx->d_in1, sp.data, ep * 4, mem, &d_prof));
+    TRY(stage_in(ctx, ctx->d_in2, sr.data, er, mem, &d_ref));
+    TRY(encode_references(static_cast<const uint8_t*>(d_ref), er));
+    std::memcpy(geom + nt, out->ops_offset, sizeof(uint64_t) * (size_t)nt);
+    TRY(upload_records(A.sc, A.ops_off, sizeof(uint64_t) * (size_t)nt));
+    fill_params();
+    o = A.o;
+    d_ops = A.ops;
+    if (!host) { point_all<AlignFields>(o, *out); d_ops = out->ops; }
+    return TRACYHIP_OK;
+  }
+
+  int queue_stages() {
+    StreamCommon& sc = A.sc;
+    // ---- 1. orientation (sage.h:239-247) ----
+    OrientStage os{d_prof, d_qp, d_lastrow, exact, nullptr};
+    TRY(queue_orientation(ctx, p, spm, h, sc, os));
+    // ---- 2. preliminary alignment (sage.h:258) by its two ends, 3. trimReferenceSlice (sage.h:259) ----
+    hipLaunchKernelGGL(s_prelim_plan_kernel, g256, b256, 0, st, spm, 0, sc.geom, sc.tr, sc.ce, sc.top_trim, sc.dead, sc.cand, sc.kc);
     HIP_TRY(hipGetLastError());
+    BandLaunch b1;
+    b1.kind = 1; b1.qp = d_qp; b1.codes = ctx->codes(); b1.ends = sc.ends; b1.code_cap = ncap; b1.hfree = 1;
+    TRY(band_stage(ctx, p, sc, nt, nt, 0, b1, ~0ull));
+    // ---- 4. final alignment gotoh(full profile, trimmed slice) (sage.h:311) on its certified band ----
+    hipLaunchKernelGGL(s_align_final_plan_kernel, g256, b256, 0, st, spm, sc.geom, sc.tr, sc.ends, sc.dead, sc.cand, sc.kc, sc.cnt);
+    HIP_TRY(hipGetLastError());
+    BandLaunch b2;
+    b2.kind = 0; b2.qp = d_qp; b2.codes = ctx->codes(); b2.scores = o.score_final; b2.ops = d_ops; b2.ops_off = A.ops_off; b2.ops_len = o.ops_len; b2.code_cap = ncap;
+    b2.hfree = 1;
+    TRY(band_stage(ctx, p, sc, nt, nt, 1, b2, words_cap));
+    hipLaunchKernelGGL(s_align_finish_kernel, g256, b256, 0, st, spm, sc.tr, sc.top_full, sc.dead, o, sc.cnt);
+    HIP_TRY(hipGetLastError());
+    return TRACYHIP_OK;
   }
-  std::memcpy(static_cast<char*>(ctx->h_desc.p) + sizeof(SGeom) * (size_t)nt, out->ops_offset, sizeof(uint64_t) * (size_t)nt);
-  HIP_TRY(hipMemcpyAsync(sc.geom, ctx->h_desc.p, sizeof(SGeom) * (size_t)nt, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(A.ops_off, static_cast<char*>(ctx->h_desc.p) + sizeof(SGeom) * (size_t)nt, sizeof(uint64_t) * (size_t)nt, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(sc.dead, 0, sizeof(uint32_t) * (size_t)nt, st));
-  HIP_TRY(hipMemsetAsync(sc.cnt, 0, sizeof(unsigned long long) * SC_COUNT, st));
-  HIP_TRY(hipMemsetAsync(sc.bstat, 0, sizeof(unsigned long long) * SB_COUNT * 8, st));
 
-  SParams spm{};
-  spm.match = p.match; spm.mismatch = p.mismatch; spm.go = p.go; spm.ge = p.ge; spm.nt = nt; spm.exact = exact ? 1u : 0u; spm.ncap = ncap - 8u;
-  spm.trim_left = job->trim_left; spm.trim_right = job->trim_right; spm.use_votes = 1u;
-  spm.split_prefix = kn.sweeps_alone ? 1u : 0u;
-
-  // ---- 1. orientation (sage.h:239-247) ----
-  const int16_t* d_qp = static_cast<const int16_t*>(ctx->d_b16tab[2].p);
-  int32_t* d_lastrow = static_cast<int32_t*>(ctx->d_lastrow.p);
-  OrientStage os{d_prof, d_qp, d_lastrow, exact, nullptr};
-  TRY(queue_orientation(ctx, p, spm, h, sc, os));
-  const dim3 g256((nt + 255) / 256), b256(256);
-  // ---- 2. preliminary alignment (sage.h:258) by its two ends, 3. trimReferenceSlice (sage.h:259) ----
-  hipLaunchKernelGGL(s_prelim_plan_kernel, g256, b256, 0, st, spm, 0, sc.geom, sc.tr, sc.ce, sc.top_trim, sc.dead, sc.cand, sc.kc);
-  HIP_TRY(hipGetLastError());
-  BandLaunch b1;
-  b1.kind = 1; b1.qp = d_qp; b1.codes = ctx->codes(); b1.ends = sc.ends; b1.code_cap = ncap; b1.hfree = 1;
-  TRY(band_stage(ctx, p, sc, nt, nt, 0, b1, ~0ull));
-  // ---- 4. final alignment gotoh(full profile, trimmed slice) (sage.h:311) on its certified band ----
-  AlignOutDev o = A.o;
-  uint8_t* d_ops = A.ops;
-  if (!host_results) {
-    o.score_fwd = out->score_fwd; o.score_rev = out->score_rev; o.score_prelim = out->score_prelim; o.score_final = out->score_final; o.forward = out->forward;
-    o.slice_begin = out->slice_begin; o.slice_len = out->slice_len; o.ref_pos = out->ref_pos; o.ops_len = out->ops_len;
-    d_ops = out->ops;
+  // the one read-back: verdict words, counters, dead flags (+ the slice lengths when the ops go to host memory)
+  int read_back() {
+    TRY(rb.carve(ctx, nt, host ? sizeof(uint32_t) * (size_t)nt : 0));
+    hlen = static_cast<uint32_t*>(rb.extra);
+    TRY(rb.queue_verdict(ctx, st));
+    TRY(rb.queue_counters(A.sc, nt, st));
+    if (host) HIP_TRY(hipMemcpyAsync(hlen, o.slice_len, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
+    TRY(await_verdict([](int rc) { return rc; }));
+    static const int stage_timer[2] = {TRACYHIP_TIMER_ORIGIN, TRACYHIP_TIMER_TRACE};
+    static const DeadReason reasons[] = {{SD_FRONT, "front"}, {SD_STRAND, "strand"}, {SD_LOSER_WON, "loser won"}, {SD_JUNK, "junk"}, {SD_PRELIM_BAND, "prelim band"},
+                                         {SD_FINAL_BAND, "final band"}, {SD_FINAL_CHECK, "final check"}, {SD_MEM, "mem"}, {SD_SHAPE, "shape"}};
+    list_dead("align", stage_timer, reasons);
+    return TRACYHIP_OK;
   }
-  hipLaunchKernelGGL(s_align_final_plan_kernel, g256, b256, 0, st, spm, sc.geom, sc.tr, sc.ends, sc.dead, sc.cand, sc.kc, sc.cnt);
-  HIP_TRY(hipGetLastError());
-  BandLaunch b2;
-  b2.kind = 0; b2.qp = d_qp; b2.codes = ctx->codes(); b2.scores = o.score_final; b2.ops = d_ops; b2.ops_off = A.ops_off; b2.ops_len = o.ops_len; b2.code_cap = ncap;
-  b2.hfree = 1;
-  TRY(band_stage(ctx, p, sc, nt, nt, 1, b2, words_cap));
-  hipLaunchKernelGGL(s_align_finish_kernel, g256, b256, 0, st, spm, sc.tr, sc.top_full, sc.dead, o, sc.cnt);
-  HIP_TRY(hipGetLastError());
 
-  // ---- the one read-back: verdict words, dead flags, counters (+ the slice lengths when the ops go to host memory) ----
-  const size_t rb = sizeof(int32_t) * (kErrWords + 4) + sizeof(unsigned long long) * (SC_COUNT + SB_COUNT * 8) + sizeof(uint32_t) * 2 * (size_t)nt;
-  HIP_TRY(ctx->h_res.ensure(rb));
-  char* hp = static_cast<char*>(ctx->h_res.p);
-  int32_t* herr = reinterpret_cast<int32_t*>(hp);
-  unsigned long long* hcnt = reinterpret_cast<unsigned long long*>(hp + sizeof(int32_t) * (kErrWords + 4));
-  unsigned long long* hbst = hcnt + SC_COUNT;
-  uint32_t* hdead = reinterpret_cast<uint32_t*>(hbst + SB_COUNT * 8);
-  uint32_t* hlen = hdead + nt;
-  HIP_TRY(hipMemcpyAsync(herr, ctx->d_err.p, sizeof(int32_t) * (kErrWords + 4), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(hcnt, sc.cnt, sizeof(unsigned long long) * SC_COUNT, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(hbst, sc.bstat, sizeof(unsigned long long) * SB_COUNT * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(hdead, sc.dead, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-  if (host_results) HIP_TRY(hipMemcpyAsync(hlen, o.slice_len, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx_sync(ctx));
-  timing_collect(ctx);
-  if (herr[kErrVerdictWord] & 4) return set_error(TRACYHIP_ERR_ARG, "reference windows must be upper-case [ACGTN] (loadSingleFasta, fasta.h:54-95)");
-  TRY(stream_range_verdict(p, herr, h));
-  static const int stage_timer[2] = {TRACYHIP_TIMER_ORIGIN, TRACYHIP_TIMER_TRACE};
-  stats_from_counters(ctx, hcnt, hbst, 2, stage_timer);
-  ctx->stats.stream_ordered = 1;
-
-  // ---- traces the device could not give their tier: the host-planned pipeline, every tier of it, on the list ----
-  std::vector<uint32_t> dl;
-  for (uint32_t t = 0; t < nt; ++t)
-    if (hdead[t]) dl.push_back(t);
-  ctx->stats.fallback_traces += (uint32_t)dl.size();
-  if (kn.verbose) {
-    uint32_t why[16] = {};
-    for (uint32_t t : dl) for (int b = 0; b < 16; ++b) why[b] += (hdead[t] >> b) & 1u;
-    fprintf(stderr, "stream-ordered align: %u traces, %zu to the host-planned tiers (front %u, strand %u, loser won %u, junk %u, prelim band %u, final band %u, final check %u, mem %u, shape %u)\n",
-            nt, dl.size(), why[0], why[1], why[2], why[3], why[4], why[6], why[7], why[8], why[15]);
-  }
-  if (!dl.empty()) {
+  // traces the device could not give their tier: the host-planned pipeline, every tier of it, on the list
+  int redo_dead_traces() {
+    if (dl.empty()) return TRACYHIP_OK;
     const uint32_t nd = (uint32_t)dl.size();
-    std::vector<uint64_t> poff(nd), ooff(nd);
-    std::vector<uint32_t> plen(nd), ridx(nd);
-    for (uint32_t i = 0; i < nd; ++i) { const uint32_t t = dl[i]; poff[i] = sp.offset[t]; plen[i] = sp.length[t]; ridx[i] = h.ridx[t]; ooff[i] = out->ops_offset[t]; }
+    std::vector<uint64_t> ooff(nd);
+    for (uint32_t i = 0; i < nd; ++i) ooff[i] = out->ops_offset[dl[i]];
     tracyhip_align_job j = *job;
-    j.ntraces = nd;
-    j.profiles.data = d_prof; j.profiles.offset = poff.data(); j.profiles.length = plen.data(); j.profiles.count = nd;
-    j.refs.data = d_ref;
-    j.ref_index = ridx.data();
+    sub_job(j, d_prof, d_ref);
     tracyhip_align_result r{};
-    r.score_fwd = A.f.score_fwd; r.score_rev = A.f.score_rev; r.forward = A.f.forward; r.score_prelim = A.f.score_prelim; r.slice_begin = A.f.slice_begin;
-    r.slice_len = A.f.slice_len; r.ref_pos = A.f.ref_pos; r.score_final = A.f.score_final; r.ops = d_ops; r.ops_offset = ooff.data(); r.ops_len = A.f.ops_len;
-    const tracyhip_call_stats keep = ctx->stats;
-    TRY(align_traces_legacy(ctx, &j, prm, TRACYHIP_MEM_DEVICE, &r));
-    const uint32_t syncs = ctx->stats.host_syncs;
-    ctx->stats = keep;
-    ctx->stats.host_syncs = syncs;
+    point_all<AlignFields>(r, A.f);
+    r.ops = d_ops; r.ops_offset = ooff.data();
+    TRY(host_planned([&]() { return align_traces_legacy(ctx, &j, prm, TRACYHIP_MEM_DEVICE, &r); }));
     HIP_TRY(hipMemcpyAsync(A.dead_list, dl.data(), sizeof(uint32_t) * nd, hipMemcpyHostToDevice, st));
-    TRY(scatter(st, A.dead_list, nd, A.f.score_fwd, o.score_fwd)); TRY(scatter(st, A.dead_list, nd, A.f.score_rev, o.score_rev));
-    TRY(scatter(st, A.dead_list, nd, A.f.forward, o.forward)); TRY(scatter(st, A.dead_list, nd, A.f.score_prelim, o.score_prelim));
-    TRY(scatter(st, A.dead_list, nd, A.f.slice_begin, o.slice_begin)); TRY(scatter(st, A.dead_list, nd, A.f.slice_len, o.slice_len));
-    TRY(scatter(st, A.dead_list, nd, A.f.ref_pos, o.ref_pos)); TRY(scatter(st, A.dead_list, nd, A.f.score_final, o.score_final));
-    TRY(scatter(st, A.dead_list, nd, A.f.ops_len, o.ops_len));
-    if (host_results) {  // (the host-planned pipeline may have re-allocated the pinned blocks: a fresh one for the lengths)
+    TRY(scatter_all<AlignFields>(st, A.dead_list, nd, A.f, o));
+    if (host) {  // (the host-planned pipeline may have re-allocated the pinned blocks: a fresh one for the lengths)
       HIP_TRY(ctx->h_res.ensure(sizeof(uint32_t) * (size_t)nt));
       hlen = static_cast<uint32_t*>(ctx->h_res.p);
       HIP_TRY(hipMemcpyAsync(hlen, o.slice_len, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(ctx_sync(ctx));  // (dl is pageable)
+    return TRACYHIP_OK;
   }
-  if (host_results) {
+
+  // results to the caller's host arrays
+  int copy_back() {
+    if (!host) return TRACYHIP_OK;
     uint64_t ops_total = 0;
     for (uint32_t t = 0; t < nt; ++t) ops_total = std::max<uint64_t>(ops_total, out->ops_offset[t] + h.mf[t] + hlen[t]);
-    auto back = [&](void* user, const void* dev, size_t bytes) -> int {
-      if (user && bytes) HIP_TRY(hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, st));
-      return TRACYHIP_OK;
-    };
-    TRY(back(out->score_fwd, o.score_fwd, sizeof(int32_t) * (size_t)nt)); TRY(back(out->score_rev, o.score_rev, sizeof(int32_t) * (size_t)nt));
-    TRY(back(out->forward, o.forward, nt)); TRY(back(out->score_prelim, o.score_prelim, sizeof(int32_t) * (size_t)nt));
-    TRY(back(out->slice_begin, o.slice_begin, sizeof(uint32_t) * (size_t)nt)); TRY(back(out->slice_len, o.slice_len, sizeof(uint32_t) * (size_t)nt));
-    TRY(back(out->ref_pos, o.ref_pos, sizeof(uint32_t) * (size_t)nt)); TRY(back(out->score_final, o.score_final, sizeof(int32_t) * (size_t)nt));
-    TRY(back(out->ops_len, o.ops_len, sizeof(uint32_t) * (size_t)nt)); TRY(back(out->ops, d_ops, ops_total));
+    TRY(copy_back_all<AlignFields>(st, nt, *out, o));
+    TRY(copy_to_host(st, out->ops, d_ops, ops_total));
     HIP_TRY(ctx_sync(ctx));
+    return TRACYHIP_OK;
   }
-  return TRACYHIP_OK;
+};
+}  // namespace
+
+int tracyhip::stream_align(tracyhip_ctx* ctx, const tracyhip_align_job* job, const tracyhip_params* prm, int mem, const tracyhip_align_result* out) {
+  if (!stream_options_ok(ctx->knobs) || job->oriented) return kStreamNo;
+  static thread_local StreamHost h;
+  AlignStream s(ctx, job, prm, mem, out, h);
+  TRY(s.pin_records());
+  { TRACYHIP_HOST_SCOPE(hsa, "stream_align.plan_common"); TRY(s.plan_geometry()); }
+  TRACYHIP_HOST_SCOPE(hsb, "stream_align.rest_of_call");
+  TRY(s.plan());
+  TRY(s.bind());
+  TRY(s.queue_stages());  // 1. .. 4. (sage.h:239-311)
+  TRY(s.read_back());     // the call's one synchronisation
+  TRY(s.redo_dead_traces());
+  return s.copy_back();
 }
 
 // =====================================================================================================================
@@ -1540,6 +1713,12 @@ struct DecompOutDev {
   int32_t* score[3];
   uint32_t* ops_len[3];
 };
+// ... with the per-trace results the decompose kernels write themselves (host side only: DecompFields walks all of them)
+struct DecompResDev : DecompOutDev {
+  tracyhip_breakpoint* bp;
+  tracyhip_decomp_status* dstatus;
+  double* fractions;
+};
 // the certificate of the allele 1 vs allele 2 band, and the per-trace results
 __global__ void s_decompose_finish_kernel(SParams p, const STrace* __restrict__ tr, const SAllele* __restrict__ al, const int32_t* __restrict__ ascore,
                                           const uint32_t* __restrict__ alen, const long long* __restrict__ bound, uint32_t* __restrict__ dead, DecompOutDev o,
@@ -1592,12 +1771,11 @@ struct DecompArena {
   float* in_prof; uint8_t* in_ref; int32_t *in_sig, *in_pos;
   int32_t* peaks;          // the peak table of the batch (decompose_kernels.hip): built from the chromatograms, or the caller's staged here (host memory)
   uint8_t *pri, *sec, *secdecomp;
-  tracyhip_breakpoint* bp; double* fractions; int32_t *dcp_indel, *dcp_err; tracyhip_decomp_status* dstatus;
-  DecompOutDev o;
+  int32_t *dcp_indel, *dcp_err;
+  DecompResDev o;
   uint8_t* ops[3];
   // compact results of the dead traces
-  DecompOutDev f;
-  tracyhip_breakpoint* f_bp; double* f_fr; tracyhip_decomp_status* f_dst;
+  DecompResDev f;
   uint32_t* dead_list;
   struct Sizes { uint32_t nt; bool exact, host, own_peaks; uint64_t tot1, bext, er, ep, sext, dext, opscap[3]; };  // own_peaks: no table from the caller, or one in host memory
   void layout(Arena& a, const Sizes& z) {
@@ -1618,57 +1796,36 @@ struct DecompArena {
     ascore = a.take<int32_t>(2 * (size_t)nt); alen = a.take<uint32_t>(2 * (size_t)nt);
     bound = a.take<long long>(nt);
     peaks = z.own_peaks ? a.take<int32_t>(4 * z.bext + 4) : nullptr;
-    auto per_trace = [&](DecompOutDev& x) {
-      x.status = a.take<int32_t>(nt); x.score_fwd = a.take<int32_t>(nt); x.score_rev = a.take<int32_t>(nt); x.score_trim = a.take<int32_t>(nt);
-      x.forward = a.take<uint8_t>(nt);
-      for (int k = 0; k < 2; ++k) { x.slice_begin[k] = a.take<uint32_t>(nt); x.slice_len[k] = a.take<uint32_t>(nt); x.ref_pos[k] = a.take<uint32_t>(nt); }
-      for (int k = 0; k < 3; ++k) { x.score[k] = a.take<int32_t>(nt); x.ops_len[k] = a.take<uint32_t>(nt); }
-    };
-    o = DecompOutDev{};
+    o = DecompResDev{};
     if (z.host) {
       in_prof = a.take<float>(z.ep); in_ref = a.take<uint8_t>(z.er); in_sig = a.take<int32_t>(z.sext); in_pos = a.take<int32_t>(z.sext ? z.bext : 0);  // (sext = 0: the caller passed the peak table)
       pri = a.take<uint8_t>(z.bext); sec = a.take<uint8_t>(z.bext); secdecomp = a.take<uint8_t>(z.bext);
-      bp = a.take<tracyhip_breakpoint>(nt); fractions = a.take<double>(2 * (size_t)nt);
-      dcp_indel = a.take<int32_t>(z.dext); dcp_err = a.take<int32_t>(z.dext); dstatus = a.take<tracyhip_decomp_status>(nt);
-      per_trace(o);
+      dcp_indel = a.take<int32_t>(z.dext); dcp_err = a.take<int32_t>(z.dext);
+      carve_all<DecompFields>(a, nt, o);
       // (the three ops buffers back to back: the offsets of alleles 1 and 2 are taken relative to the first)
       for (int k = 0; k < 3; ++k) ops[k] = a.take<uint8_t>(z.opscap[k]);
     }
-    per_trace(f);
-    f_bp = a.take<tracyhip_breakpoint>(nt); f_fr = a.take<double>(2 * (size_t)nt); f_dst = a.take<tracyhip_decomp_status>(nt);
+    carve_all<DecompFields>(a, nt, f);
     dead_list = a.take<uint32_t>(nt);
   }
 };
 
 static_assert(sizeof(tracyhip_breakpoint) == sizeof(BreakpointOut) && sizeof(tracyhip_decomp_status) == sizeof(DecompOut), "result records of the C ABI are the kernels'");
-struct Frac2 { double a, b; };
 
 }  // namespace
 
 namespace {
 // One stream-ordered tracyhip_decompose_traces call: what its sections share, one method per section (queued in this order)
-struct DecStream {
-  tracyhip_ctx* ctx;
+struct DecStream : StreamCall {
   const tracyhip_decompose_job* job;
-  const tracyhip_params* prm;
-  const int mem;
   const tracyhip_decompose_result* out;
-  const CtxKnobs& kn;
-  const uint32_t nt;
-  const tracyhip_seqset& sp;
-  const tracyhip_seqset& sr;
   const tracyhip_basecalls& bc;
   const tracyhip_decomp_params& dp;
-  hipStream_t st;
-  tracyhip_params p, pglobal;
-  const uint32_t TL, TR;
-  const bool exact, host;
-  StreamHost& h;
-  SGeom* geom = nullptr;
+  tracyhip_params pglobal;
   SGeomD* geomd = nullptr;
   DecompArena::Sizes z{};
-  uint32_t maxbc = 0, maxsl = 0, max_arest = 0, ncap = 0;
-  uint64_t atab_tot = 0, alr_tot = 0, rows_alleles = 0, words_cap = 0;
+  uint32_t maxbc = 0, maxsl = 0, max_arest = 0;
+  uint64_t atab_tot = 0, alr_tot = 0, rows_alleles = 0;
   DecompArena A;
   const float* d_prof = nullptr;
   const uint8_t* d_ref = nullptr;
@@ -1676,22 +1833,14 @@ struct DecStream {
   bool build_peaks = false;   // no table from the caller: peaks_kernel fills A.peaks (beside the sweeps when the context has side streams)
   bool peaks_forked = false;  // ... on side[3]; the call's stream waits for ready[1] before generateSecondaryDecomposed
   uint8_t *d_pri = nullptr, *d_sec = nullptr, *d_sd = nullptr;
-  tracyhip_breakpoint* d_bp = nullptr;
-  double* d_fr = nullptr;
   int32_t *d_di = nullptr, *d_de = nullptr;
-  tracyhip_decomp_status* d_dst = nullptr;
-  DecompOutDev o{};
+  DecompResDev o{};
   uint8_t* d_opsK[3] = {nullptr, nullptr, nullptr};
-  SParams spm{};
   SParamsD spd{};
-  dim3 g256, g256x2, b256;
-  const int16_t *d_qp = nullptr, *d_aqp = nullptr;
-  int32_t* d_lastrow = nullptr;
+  dim3 g256x2;
+  const int16_t* d_aqp = nullptr;
   uint8_t *d_cq_ref = nullptr, *d_cq_sd = nullptr;
-  int32_t *herr = nullptr, *hcq = nullptr;
-  unsigned long long *hcnt = nullptr, *hbst = nullptr;
-  uint32_t* hdead = nullptr;
-  std::vector<uint32_t> dl;  // the traces the device could not give their tier
+  int32_t* hcq = nullptr;  // the verdict of the case-sensitive encoders
   bool af_forked = false;    // allelicFraction is on a side stream (joined before the read-back)
   bool af_pending = false;   // ... not queued yet (queue_allelic_fraction)
   bool bp_early = false;     // findBreakpoint and the windows' case-sensitive codes were queued behind the full sweeps (OrientStage::filler)
@@ -1699,11 +1848,8 @@ struct DecStream {
   bool encoded_early = false;
 
   DecStream(tracyhip_ctx* c, const tracyhip_decompose_job* j, const tracyhip_params* q, int m, const tracyhip_decompose_result* o_, StreamHost& h_)
-      : ctx(c), job(j), prm(q), mem(m), out(o_), kn(c->knobs), nt(j->ntraces), sp(j->profiles), sr(j->refs), bc(j->bc), dp(j->dprm), st(c->stream), p(*q),
-        pglobal(*q), TL((uint32_t)j->dprm.trim_left), TR((uint32_t)j->dprm.trim_right), exact(j->strand_by_certificate == 0), host(m == TRACYHIP_MEM_HOST), h(h_),
-        g256((j->ntraces + 255) / 256), g256x2((2 * j->ntraces + 255) / 256), b256(256) {
-    p.hfree = 1;  // AlignConfig<true,false> semiglobal (indigo.h:164)
-    p.vfree = 0;
+      : StreamCall(c, j, q, m, (uint32_t)j->dprm.trim_left, (uint32_t)j->dprm.trim_right, h_), job(j), out(o_), bc(j->bc), dp(j->dprm), pglobal(*q),
+        g256x2((2 * j->ntraces + 255) / 256) {
     pglobal.hfree = 0;  // AlignConfig<false,false> (indigo.h:381)
     pglobal.vfree = 0;
   }
@@ -1724,18 +1870,6 @@ struct DecStream {
     return rc;
   }
 
-  // verdict words cleared, the reference windows encoded to profile-row codes (with their block map and the validation verdict)
-  int encode_references(const uint8_t* refs, uint64_t er) {
-    HIP_TRY(ctx->d_err.ensure(kErrBytes));
-    HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, kErrBytes, st));
-    int32_t* d_verr = static_cast<int32_t*>(ctx->d_err.p) + kErrVerdictWord;
-    HIP_TRY(ctx->ensure_codes(er ? er : 1, st));
-    if (er) {
-      hipLaunchKernelGGL(encode_codes_kernel, dim3((unsigned)((er + 4095) / 4096)), dim3(256), 0, st, refs, ctx->codes(), er, ctx->special_blocks(), d_verr);
-      HIP_TRY(hipGetLastError());
-    }
-    return TRACYHIP_OK;
-  }
   // payloads in device memory: the encoder needs nothing the planner makes -- it runs while the host lays out the geometry records
   // (2 ms for 100 000 traces during which the device had nothing to do).  Harmless should the planner hand the call back.
   int encode_early() {
@@ -1838,8 +1972,7 @@ struct DecStream {
     if (max_arest == 0 || !front_tiers_fit(max_arest)) return kStreamNo;
     TRY(decompose_limits(dp.maxindel, maxbc));
     z.ep = seqset_extent(sp); z.er = seqset_extent(sr);
-    ncap = (h.maxmf + 200u + 7u) & ~3u;
-    if (4ull * ncap + b16_table_bytes(12) > 64u * 1024u) return kStreamNo;
+    TRY(size_ncap());
 
     // ---- workspace ----
     TRACYHIP_HOST_SCOPE(hs6, "plan.workspace");
@@ -1876,10 +2009,7 @@ struct DecStream {
     d_peaks = bc.peaks ? bc.peaks : A.peaks;
     build_peaks = !bc.peaks;
     d_pri = bc.primary; d_sec = bc.secondary; d_sd = out->secdecomp;
-    d_bp = out->bp;
-    d_fr = out->fractions;
     d_di = out->dcp_indel; d_de = out->dcp_err;
-    d_dst = out->dstatus;
     o = A.o;
     for (int k = 0; k < 3; ++k) d_opsK[k] = out->ops[k];
     if (host) {
@@ -1892,30 +2022,20 @@ struct DecStream {
       else { TRY(up(A.in_sig, bc.signal, z.sext * 4)); TRY(up(A.in_pos, bc.bcpos, z.bext * 4)); }
       TRY(up(A.pri, bc.primary, z.bext)); TRY(up(A.sec, bc.secondary, z.bext));
       d_prof = A.in_prof; d_ref = A.in_ref; d_sig = A.in_sig; d_pos = A.in_pos; d_pri = A.pri; d_sec = A.sec; d_sd = A.secdecomp;
-      d_bp = A.bp; d_fr = A.fractions; d_di = A.dcp_indel; d_de = A.dcp_err; d_dst = A.dstatus;
+      d_di = A.dcp_indel; d_de = A.dcp_err;
       for (int k = 0; k < 3; ++k) d_opsK[k] = A.ops[k];
     } else {
-      o.status = out->status; o.score_fwd = out->score_fwd; o.score_rev = out->score_rev; o.score_trim = out->score_trim; o.forward = out->forward;
-      for (int k = 0; k < 2; ++k) { o.slice_begin[k] = out->slice_begin[k]; o.slice_len[k] = out->slice_len[k]; o.ref_pos[k] = out->ref_pos[k]; }
-      for (int k = 0; k < 3; ++k) { o.score[k] = out->score[k]; o.ops_len[k] = out->ops_len[k]; }
+      point_all<DecompFields>(o, *out);
     }
     HIP_TRY(hipMemcpyAsync(A.pri_bak, d_pri, z.bext, hipMemcpyDeviceToDevice, st));  // decomposeAlleles rewrites the basecalls in place
     HIP_TRY(hipMemcpyAsync(A.sec_bak, d_sec, z.bext, hipMemcpyDeviceToDevice, st));
 
     // ---- references encoded once (unless encode_early did it while the host planned); the records: one pinned block, two copies ----
     if (!encoded_early) TRY(encode_references(d_ref, z.er));
-    {
-      // (the offset arrays of the band launches are filled from these records on the device: s_expand_d_kernel)
-      HIP_TRY(hipMemcpyAsync(sc.geom, ctx->h_desc.p, sizeof(SGeom) * (size_t)nt, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(A.geomd, geomd, sizeof(SGeomD) * (size_t)nt, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipMemsetAsync(sc.dead, 0, sizeof(uint32_t) * (size_t)nt, st));
-    HIP_TRY(hipMemsetAsync(sc.cnt, 0, sizeof(unsigned long long) * SC_COUNT, st));
-    HIP_TRY(hipMemsetAsync(sc.bstat, 0, sizeof(unsigned long long) * SB_COUNT * 8, st));
+    // (the offset arrays of the band launches are filled from these records on the device: s_expand_d_kernel)
+    TRY(upload_records(sc, A.geomd, sizeof(SGeomD) * (size_t)nt));
 
-    spm.match = p.match; spm.mismatch = p.mismatch; spm.go = p.go; spm.ge = p.ge; spm.nt = nt; spm.exact = exact ? 1u : 0u; spm.ncap = ncap - 8u;
-    spm.trim_left = TL; spm.trim_right = TR; spm.use_votes = 1u;
-    spm.split_prefix = kn.sweeps_alone ? 1u : 0u;
+    fill_params();
     spd.bext = z.bext;
     spd.best = (int32_t)std::max<int64_t>(std::max<int64_t>(p.match, p.mismatch), 0);
 
@@ -1925,8 +2045,6 @@ struct DecStream {
   int queue_trace_stages() {
     StreamCommon& sc = A.sc;
     // ---- 2. orientation (indigo.h:235-247), 3. gotoh(trimmed trace, window) (indigo.h:302) by traceback on its band ----
-    d_qp = static_cast<const int16_t*>(ctx->d_b16tab[2].p);
-    d_lastrow = static_cast<int32_t*>(ctx->d_lastrow.p);
     OrientStage os{d_prof, d_qp, d_lastrow, exact, A.desc_trim};
     // the descriptors of the decompose stages need nothing but the geometry records; findBreakpoint (indigo.h:196) nothing but the profiles:
     // it runs on a side stream beside the sweeps and is waited for where its result is first read (findHomozygousBreakpoint)
@@ -1952,7 +2070,7 @@ struct DecStream {
     bp_early = ctx->b16_fork_ok && !ctx->knobs.no_fork;
     if (bp_early)
       os.filler = [&]() -> int {
-        TRY(launch_breakpoint(ctx, A.bpd, nt, h.maxmt, d_prof, reinterpret_cast<BreakpointOut*>(d_bp)));
+        TRY(launch_breakpoint(ctx, A.bpd, nt, h.maxmt, d_prof, reinterpret_cast<BreakpointOut*>(o.bp)));
         return encode_windows_cq();
       };
     TRY(give_up(queue_orientation(ctx, p, spm, h, sc, os)));
@@ -1964,7 +2082,7 @@ struct DecStream {
     hipLaunchKernelGGL(s_prelim_check_kernel, g256, b256, 0, st, spm, sc.tr, A.sb, A.len1, sc.kc, o.score_trim, sc.dead, sc.cnt);
     HIP_TRY(hipGetLastError());
     // ---- 1. findBreakpoint (indigo.h:196), unless it already ran behind the full sweeps ----
-    BreakpointOut* bpo = reinterpret_cast<BreakpointOut*>(d_bp);
+    BreakpointOut* bpo = reinterpret_cast<BreakpointOut*>(o.bp);
     if (!bp_early) TRY(launch_breakpoint(ctx, A.bpd, nt, h.maxmt, d_prof, bpo));
     {
       RowsArgs ra{};
@@ -1989,7 +2107,7 @@ struct DecStream {
       a.rows0 = A.rows0; a.rows1 = A.rows1;
       a.primary = d_pri; a.secondary = d_sec;
       a.dcp_indel = d_di; a.dcp_err = d_de;
-      a.out = reinterpret_cast<DecompOut*>(d_dst);
+      a.out = reinterpret_cast<DecompOut*>(o.dstatus);
       a.prm = DecompParams{dp.trim_left, dp.trim_right, dp.maxindel, dp.madc};
       a.ntraces = nt;
       a.lens = A.len1;
@@ -2033,7 +2151,7 @@ struct DecStream {
       HIP_TRY(hipStreamWaitEvent(ctx->b16_fork.side[3], ctx->b16_fork.ready[0], 0));
       ctx->stream = ctx->b16_fork.side[3];
     }
-    const int rc = launch_allelic_fraction(ctx, A.bcd, nt, maxbc, d_peaks, d_pri, d_sd, TL, TR, d_fr, 18ull * std::accumulate(h.mf.begin(), h.mf.end(), 0ull), z.bext);
+    const int rc = launch_allelic_fraction(ctx, A.bcd, nt, maxbc, d_peaks, d_pri, d_sd, TL, TR, o.fractions, 18ull * std::accumulate(h.mf.begin(), h.mf.end(), 0ull), z.bext);
     ctx->stream = st;
     if (fork) {
       HIP_TRY(hipEventRecord(ctx->b16_fork.joined[3], ctx->b16_fork.side[3]));
@@ -2112,7 +2230,8 @@ struct DecStream {
     BandLaunch b3;
     b3.kind = 0; b3.qp = d_aqp; b3.codes = d_cq_sd; b3.scores = o.score[2]; b3.ops = d_opsK[2]; b3.ops_off = A.ops2_off; b3.ops_len = o.ops_len[2]; b3.code_cap = ncap; b3.hfree = 0;
     TRY(band_stage(ctx, pglobal, sc, nt, nt, 3, b3, words_cap));
-    hipLaunchKernelGGL(s_decompose_finish_kernel, g256, b256, 0, st, spm, sc.tr, A.al, A.ascore, A.alen, A.bound, sc.dead, o, sc.cnt);
+    const DecompOutDev& ko = o;  // (the kernels' part of o: bp / dstatus / fractions are written by the decompose kernels through their own arguments)
+    hipLaunchKernelGGL(s_decompose_finish_kernel, g256, b256, 0, st, spm, sc.tr, A.al, A.ascore, A.alen, A.bound, sc.dead, ko, sc.cnt);
     HIP_TRY(hipGetLastError());
 
     return TRACYHIP_OK;
@@ -2120,120 +2239,70 @@ struct DecStream {
 
   // the one read-back: verdict words, counters, dead flags
   int read_back() {
-    StreamCommon& sc = A.sc;
     if (af_pending) TRY(queue_allelic_fraction());
     if (af_forked) HIP_TRY(hipStreamWaitEvent(st, ctx->b16_fork.joined[3], 0));
     // ---- the one read-back ----
-    const size_t rb = sizeof(int32_t) * (kErrWords + 4) + sizeof(int32_t) * 4 + sizeof(unsigned long long) * (SC_COUNT + SB_COUNT * 8) + sizeof(uint32_t) * (size_t)nt;
-    HIP_TRY(ctx->h_res.ensure(rb));
-    char* hp = static_cast<char*>(ctx->h_res.p);
-    herr = reinterpret_cast<int32_t*>(hp);
-    hcq = herr + (kErrWords + 4);
-    hcnt = reinterpret_cast<unsigned long long*>(hcq + 4);
-    hbst = hcnt + SC_COUNT;
-    hdead = reinterpret_cast<uint32_t*>(hbst + SB_COUNT * 8);
-    HIP_TRY(hipMemcpyAsync(herr, ctx->d_err.p, sizeof(int32_t) * (kErrWords + 4), hipMemcpyDeviceToHost, st));
+    TRY(rb.carve(ctx, nt, sizeof(int32_t) * 4));
+    hcq = static_cast<int32_t*>(rb.extra);
+    TRY(rb.queue_verdict(ctx, st));
     HIP_TRY(hipMemcpyAsync(hcq, A.cq_flag, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(hcnt, sc.cnt, sizeof(unsigned long long) * SC_COUNT, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(hbst, sc.bstat, sizeof(unsigned long long) * SB_COUNT * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(hdead, sc.dead, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx_sync(ctx));
-    timing_collect(ctx);
-    if (herr[kErrVerdictWord] & 4) {
-      (void)give_up(kStreamNo);
-      return set_error(TRACYHIP_ERR_ARG, "reference windows must be upper-case [ACGTN] (loadSingleFasta, fasta.h:54-95)");
-    }
-    TRY(give_up(stream_range_verdict(p, herr, h)));
+    TRY(rb.queue_counters(A.sc, nt, st));
+    TRY(await_verdict([this](int rc) { return give_up(rc); }));
     if (hcq[0] & 1) return give_up(kStreamNo);  // a basecall string holds something else than A C G T N: the byte-compare kernels (pipeline.hip)
     static const int stage_timer[4] = {TRACYHIP_TIMER_TRACE, TRACYHIP_TIMER_ORIGIN, TRACYHIP_TIMER_TRACE, TRACYHIP_TIMER_TRACE};
-    stats_from_counters(ctx, hcnt, hbst, 4, stage_timer);
-    ctx->stats.stream_ordered = 1;
-
-    // ---- traces the device could not give their tier: the host-planned pipeline on the list, from the basecalls as they were ----
-    dl.clear();
-    for (uint32_t t = 0; t < nt; ++t)
-      if (hdead[t]) dl.push_back(t);
-    ctx->stats.fallback_traces += (uint32_t)dl.size();
-    if (kn.verbose) {
-      uint32_t why[16] = {};
-      for (uint32_t t : dl) for (int b = 0; b < 16; ++b) why[b] += (hdead[t] >> b) & 1u;
-      fprintf(stderr, "stream-ordered decompose: %u traces, %zu to the host-planned tiers (front %u, strand %u, loser won %u, junk %u, prelim band %u / check %u, mem %u, allele front %u / origin %u / band %u / check %u, a12 band %u / check %u, shape %u)\n",
-              nt, dl.size(), why[0], why[1], why[2], why[3], why[4], why[5], why[8], why[9], why[10], why[11], why[12], why[13], why[14], why[15]);
-    }
+    static const DeadReason reasons[] = {{SD_FRONT, "front"}, {SD_STRAND, "strand"}, {SD_LOSER_WON, "loser won"}, {SD_JUNK, "junk"}, {SD_PRELIM_BAND, "prelim band"},
+                                         {SD_PRELIM_CHECK, "prelim check"}, {SD_MEM, "mem"}, {SD_ALLELE_FRONT, "allele front"}, {SD_ALLELE_ORIGIN, "allele origin"},
+                                         {SD_ALLELE_BAND, "allele band"}, {SD_ALLELE_CHECK, "allele check"}, {SD_A12_BAND, "a12 band"}, {SD_A12_CHECK, "a12 check"},
+                                         {SD_SHAPE, "shape"}};
+    list_dead("decompose", stage_timer, reasons);
     return TRACYHIP_OK;
   }
 
   // the traces the device could not give their tier: the host-planned pipeline on the list, from the basecalls as they were
   int redo_dead_traces() {
-    StreamCommon& sc = A.sc;
-    if (!dl.empty()) {
-      const uint32_t nd = (uint32_t)dl.size();
-      HIP_TRY(hipMemcpyAsync(A.dead_list, dl.data(), sizeof(uint32_t) * nd, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(s_restore_kernel, dim3(nd), dim3(64), 0, st, A.dead_list, sc.geom, A.geomd, A.pri_bak, A.sec_bak, d_pri, d_sec);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(ctx_sync(ctx));
-      std::vector<uint64_t> poff(nd), bcoff(nd), dcpoff(nd), ooff[3];
-      std::vector<uint32_t> plen(nd), ridx(nd), bclen(nd);
-      for (int k = 0; k < 3; ++k) ooff[k].resize(nd);
-      for (uint32_t i = 0; i < nd; ++i) {
-        const uint32_t t = dl[i];
-        poff[i] = sp.offset[t]; plen[i] = sp.length[t]; ridx[i] = h.ridx[t];
-        bcoff[i] = bc.bc_offset[t]; bclen[i] = bc.bc_len[t];
-        dcpoff[i] = out->dcp_offset[t];
-        for (int k = 0; k < 3; ++k) ooff[k][i] = out->ops_offset[k][t];
-      }
-      tracyhip_decompose_job j = *job;
-      j.ntraces = nd;
-      j.profiles.data = d_prof; j.profiles.offset = poff.data(); j.profiles.length = plen.data(); j.profiles.count = nd;
-      j.refs.data = d_ref;
-      j.ref_index = ridx.data();
-      j.bc.ntraces = nd;
-      // (the peak table of the batch is on the device by now, the caller's or the one built from the chromatograms: the sub-job reads it)
-      j.bc.signal = nullptr; j.bc.signal_offset = nullptr; j.bc.nsamples = nullptr; j.bc.bcpos = nullptr; j.bc.peaks = d_peaks;
-      j.bc.primary = d_pri; j.bc.secondary = d_sec; j.bc.bc_offset = bcoff.data(); j.bc.bc_len = bclen.data();
-      tracyhip_decompose_result r{};
-      r.bp = A.f_bp; r.status = A.f.status; r.score_fwd = A.f.score_fwd; r.score_rev = A.f.score_rev; r.forward = A.f.forward; r.score_trim = A.f.score_trim;
-      r.dcp_indel = d_di; r.dcp_err = d_de; r.dcp_offset = dcpoff.data();
-      r.dstatus = A.f_dst; r.secdecomp = d_sd; r.fractions = A.f_fr;
-      for (int k = 0; k < 2; ++k) { r.slice_begin[k] = A.f.slice_begin[k]; r.slice_len[k] = A.f.slice_len[k]; r.ref_pos[k] = A.f.ref_pos[k]; }
-      for (int k = 0; k < 3; ++k) { r.score[k] = A.f.score[k]; r.ops[k] = d_opsK[k]; r.ops_offset[k] = ooff[k].data(); r.ops_len[k] = A.f.ops_len[k]; }
-      const tracyhip_call_stats keep = ctx->stats;
-      TRY(decompose_traces_legacy(ctx, &j, prm, TRACYHIP_MEM_DEVICE, &r));
-      const uint32_t syncs = ctx->stats.host_syncs;
-      ctx->stats = keep;
-      ctx->stats.host_syncs = syncs;
-      const uint32_t* L = A.dead_list;
-      TRY(scatter(st, L, nd, A.f_bp, d_bp)); TRY(scatter(st, L, nd, A.f_dst, d_dst));
-      TRY(scatter(st, L, nd, reinterpret_cast<const Frac2*>(A.f_fr), reinterpret_cast<Frac2*>(d_fr)));
-      TRY(scatter(st, L, nd, A.f.status, o.status)); TRY(scatter(st, L, nd, A.f.score_fwd, o.score_fwd)); TRY(scatter(st, L, nd, A.f.score_rev, o.score_rev));
-      TRY(scatter(st, L, nd, A.f.forward, o.forward)); TRY(scatter(st, L, nd, A.f.score_trim, o.score_trim));
-      for (int k = 0; k < 2; ++k) {
-        TRY(scatter(st, L, nd, A.f.slice_begin[k], o.slice_begin[k])); TRY(scatter(st, L, nd, A.f.slice_len[k], o.slice_len[k]));
-        TRY(scatter(st, L, nd, A.f.ref_pos[k], o.ref_pos[k]));
-      }
-      for (int k = 0; k < 3; ++k) { TRY(scatter(st, L, nd, A.f.score[k], o.score[k])); TRY(scatter(st, L, nd, A.f.ops_len[k], o.ops_len[k])); }
-      HIP_TRY(ctx_sync(ctx));
+    if (dl.empty()) return TRACYHIP_OK;
+    const uint32_t nd = (uint32_t)dl.size();
+    HIP_TRY(hipMemcpyAsync(A.dead_list, dl.data(), sizeof(uint32_t) * nd, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(s_restore_kernel, dim3(nd), dim3(64), 0, st, A.dead_list, A.sc.geom, A.geomd, A.pri_bak, A.sec_bak, d_pri, d_sec);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(ctx_sync(ctx));
+    std::vector<uint64_t> bcoff(nd), dcpoff(nd), ooff[3];
+    std::vector<uint32_t> bclen(nd);
+    for (int k = 0; k < 3; ++k) ooff[k].resize(nd);
+    for (uint32_t i = 0; i < nd; ++i) {
+      const uint32_t t = dl[i];
+      bcoff[i] = bc.bc_offset[t]; bclen[i] = bc.bc_len[t];
+      dcpoff[i] = out->dcp_offset[t];
+      for (int k = 0; k < 3; ++k) ooff[k][i] = out->ops_offset[k][t];
     }
+    tracyhip_decompose_job j = *job;
+    sub_job(j, d_prof, d_ref);
+    j.bc.ntraces = nd;
+    // (the peak table of the batch is on the device by now, the caller's or the one built from the chromatograms: the sub-job reads it)
+    j.bc.signal = nullptr; j.bc.signal_offset = nullptr; j.bc.nsamples = nullptr; j.bc.bcpos = nullptr; j.bc.peaks = d_peaks;
+    j.bc.primary = d_pri; j.bc.secondary = d_sec; j.bc.bc_offset = bcoff.data(); j.bc.bc_len = bclen.data();
+    tracyhip_decompose_result r{};
+    point_all<DecompFields>(r, A.f);
+    r.dcp_indel = d_di; r.dcp_err = d_de; r.dcp_offset = dcpoff.data();
+    r.secdecomp = d_sd;
+    for (int k = 0; k < 3; ++k) { r.ops[k] = d_opsK[k]; r.ops_offset[k] = ooff[k].data(); }
+    TRY(host_planned([&]() { return decompose_traces_legacy(ctx, &j, prm, TRACYHIP_MEM_DEVICE, &r); }));
+    TRY(scatter_all<DecompFields>(st, A.dead_list, nd, A.f, o));
+    HIP_TRY(ctx_sync(ctx));
     return TRACYHIP_OK;
   }
 
-  // results to the caller's host arrays
+  // Results to the caller's host arrays.  The per-trace arrays go in the order of DecompFields -- the order of the scatters -- between the
+  // arrays laid out by offsets: one list cannot give both the order the scatters had and the order these copies had (bp, fractions, the
+  // tables, dstatus, ..., ops[k] behind score[k] / ops_len[k]).  The copies are independent, on one stream, and end in the one
+  // synchronisation below: what arrives, and host_syncs, do not depend on their order.
   int copy_back() {
-    if (host) {
-      auto back = [&](void* user, const void* dev, size_t bytes) -> int {
-        if (user && bytes) HIP_TRY(hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, st));
-        return TRACYHIP_OK;
-      };
-      const size_t n4 = sizeof(int32_t) * (size_t)nt;
-      TRY(back(bc.primary, d_pri, z.bext)); TRY(back(bc.secondary, d_sec, z.bext)); TRY(back(out->secdecomp, d_sd, z.bext));
-      TRY(back(out->bp, d_bp, sizeof(tracyhip_breakpoint) * (size_t)nt)); TRY(back(out->fractions, d_fr, sizeof(double) * 2 * (size_t)nt));
-      TRY(back(out->dcp_indel, d_di, z.dext * 4)); TRY(back(out->dcp_err, d_de, z.dext * 4)); TRY(back(out->dstatus, d_dst, sizeof(tracyhip_decomp_status) * (size_t)nt));
-      TRY(back(out->status, o.status, n4)); TRY(back(out->score_fwd, o.score_fwd, n4)); TRY(back(out->score_rev, o.score_rev, n4));
-      TRY(back(out->score_trim, o.score_trim, n4)); TRY(back(out->forward, o.forward, nt));
-      for (int k = 0; k < 2; ++k) { TRY(back(out->slice_begin[k], o.slice_begin[k], n4)); TRY(back(out->slice_len[k], o.slice_len[k], n4)); TRY(back(out->ref_pos[k], o.ref_pos[k], n4)); }
-      for (int k = 0; k < 3; ++k) { TRY(back(out->score[k], o.score[k], n4)); TRY(back(out->ops_len[k], o.ops_len[k], n4)); TRY(back(out->ops[k], d_opsK[k], z.opscap[k])); }
-      HIP_TRY(ctx_sync(ctx));
-    }
+    if (!host) return TRACYHIP_OK;
+    TRY(copy_to_host(st, bc.primary, d_pri, z.bext)); TRY(copy_to_host(st, bc.secondary, d_sec, z.bext)); TRY(copy_to_host(st, out->secdecomp, d_sd, z.bext));
+    TRY(copy_to_host(st, out->dcp_indel, d_di, z.dext * 4)); TRY(copy_to_host(st, out->dcp_err, d_de, z.dext * 4));
+    TRY(copy_back_all<DecompFields>(st, nt, *out, o));
+    for (int k = 0; k < 3; ++k) TRY(copy_to_host(st, out->ops[k], d_opsK[k], z.opscap[k]));
+    HIP_TRY(ctx_sync(ctx));
     return TRACYHIP_OK;
   }
 };
