@@ -116,7 +116,7 @@ int tracyhip_synchronize(tracyhip_ctx* ctx);
 /* Options.  Every switch of the library is read from the environment ONCE, when a context is created (TRACYHIP_<NAME>, e.g.
    TRACYHIP_NO_STREAM=1), and changed afterwards only through this call; name is the variable without the prefix, in any case:
      no_stream (pipelines planned by the host between launches instead of stream-ordered), no_narrow, no_compact, no_screen,
-     no_band, no_band16, no_front, no_prefix, no_vote, no_origin, no_subwindow, no_prelim_origin, no_cq, no_fused_walk, no_cont16, no_quads, no_fork, no_decomp_wave, no_af_split, no_front_lists, no_origin_band, sweeps_alone (measurement: the full sweeps of the orientation stage on a device of their own)   "0" / "1"
+     no_band, no_band16, no_front, no_prefix, no_vote, no_origin, no_subwindow, no_prelim_origin, no_cq, no_fused_walk, no_cont16, no_quads, no_fork, no_early_tail (`tracy align`: no alignment queued before both orientation scores are known), no_decomp_wave, no_af_split, no_front_lists, no_origin_band, sweeps_alone (measurement: the full sweeps of the orientation stage on a device of their own)   "0" / "1"
      band_w  (half width of the certified band of the final alignments; -1 = from the preliminary alignment, 0 = whole matrices)
      ckpt_b  (steps between wavefront checkpoints, 32 .. 1024)      verbose  (one line per pipeline stage on stderr)
      seed_vote_cap  (tracyhip_seed_traces: votes one trace may collect per strand and pass on the device, 1 .. 2048, default 2048;
@@ -232,7 +232,9 @@ typedef struct {
   uint32_t* slice_len;    /* [ntraces] length of the trimmed slice (after substr clamping) */
   uint32_t* ref_pos;      /* [ntraces] rs.pos after trimReferenceSlice (rs.pos starts at 0, sage.h:244) */
   int32_t* score_final;   /* [ntraces] score of the final alignment (sage.h:311) */
-  uint8_t* ops;           /* final alignment, push order, at ops + ops_offset[t] (capacity mf + slice) */
+  uint8_t* ops;           /* final alignment, push order, at ops + ops_offset[t] (capacity mf + slice).  Only the first ops_len[t]
+                             bytes are defined: the rest of a trace's region may hold bytes of an alignment that was begun for the
+                             voted strand and discarded when the other strand's exact score won */
   const uint64_t* ops_offset; /* HOST array */
   uint32_t* ops_len;      /* [ntraces] */
 } tracyhip_align_result;

@@ -56,6 +56,8 @@ struct CtxKnobs {
   bool no_fused_walk = false;     // a separate walk launch after a traceback sweep
   bool no_quads = false;          // stream-ordered pipelines: narrow bands on sixteen lanes per pair like the rest (band16.h b16_narrow_ok)
   bool no_fork = false;           // stream-ordered pipelines: the launches of a band stage in a row on the call's stream instead of side by side
+  bool no_early_tail = false;     // `tracy align`, stream-ordered: no trace's preliminary / final alignment is queued on the voted strand's side stream before the
+                                  // other strand's full sweep has confirmed the vote -- every trace takes the pass behind the decision (the order before the early tail)
   bool sweeps_alone = false;      // MEASUREMENT mode of the stream-ordered orientation stage: the voted strand's chain finishes BEFORE the other strand's full sweeps
                                   // start and its prefix cells are credited to the front timer -- TRACYHIP_TIMER_SCORE then times the full sweeps on a device
                                   // of their own (bench.py roofline.dominant_kernel_alone_frac); slower, same results

@@ -167,8 +167,45 @@ __global__ void s_orient_plan_kernel(SParams p, const SGeom* __restrict__ geom, 
   });
 }
 
+// what the tiers of a pruned sweep certified for unit t: c_e (window column, 1-based; 0: no tier certified it) and the score
+__device__ __forceinline__ uint32_t s_front_result(uint32_t t, const FrontOut* __restrict__ fo1, const int32_t* __restrict__ fs1, const uint32_t* __restrict__ fe1,
+                                                   const FrontOut* __restrict__ fo2, const int32_t* __restrict__ fs2, const uint32_t* __restrict__ fe2, int64_t* s_g) {
+  if (fo1[t].ok) { *s_g = fs1[t]; return fe1[2 * t + 1] ? fe1[2 * t + 1] + fo1[t].shift : 0u; }
+  if (fo2[t].ok) { *s_g = fs2[t]; return fe2[2 * t + 1] ? fe2[2 * t + 1] + fo2[t].shift : 0u; }
+  return 0u;
+}
+
+// ---- orientation stage, step 2 ahead of time (`tracy align`, on the voted strand's side stream behind its tiers): a trace of class 0
+// that a tier certified gets the decision "the voted strand g won" -- S.fwd / rc / sstar / ce as s_orient_decide_kernel will leave them
+// if gsFwd > gsRev comes out that way -- and the mark ST_EARLY, so that its preliminary and final alignment can be queued beside the
+// other strand's full sweep.  Assumed, not known: S.sc[1 - g] stays open until that sweep has ended, and s_orient_decide_kernel then
+// confirms the trace or gives it SD_LOSER_WON, the verdict a clear vote's loser that wins has always had (its sweep kept no row m).
+// Only queued when both scores are exact: by certificate there is no full sweep to run beside (no trace is marked, the order before).
+// Every other trace is left alone: it is decided, and its alignments are queued, behind the sweeps. ----
+__global__ void s_orient_early_kernel(SParams p, const FrontOut* __restrict__ fo1,
+                                      const int32_t* __restrict__ fs1, const uint32_t* __restrict__ fe1, const FrontOut* __restrict__ fo2,
+                                      const int32_t* __restrict__ fs2, const uint32_t* __restrict__ fe2, STrace* __restrict__ tr) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= p.nt) return;
+  STrace S = tr[t];
+  if (S.cls != 0u || !p.use_votes || !p.exact) return;
+  const uint32_t g = S.g;
+  int64_t s_g = 0;
+  const uint32_t fce = s_front_result(t, fo1, fs1, fe1, fo2, fs2, fe2, &s_g);
+  if (fce == 0u) return;
+  S.sc[g] = (int32_t)s_g;
+  S.fwd = g == 0u ? 1 : 0;
+  S.rc = (uint8_t)g;
+  S.sstar = (int32_t)s_g;
+  S.ce = fce;
+  S.mark = ST_EARLY;
+  tr[t] = S;
+}
+
 // ---- orientation stage, step 2 (pipeline.hip "o.e" .. "o.f"): scores of both strands, the decision gsFwd > gsRev (sage.h:247), the
-// winner's c_e from the pruned sweep or (RowEndDesc) from its row m ----
+// winner's c_e from the pruned sweep or (RowEndDesc) from its row m.  For a trace marked ST_EARLY this is the confirmation: the rule is
+// the same, and where it names the voted strand every field comes out as s_orient_early_kernel set it (the fields the early stages
+// have added since are kept); where it does not, the trace is dead and what its early stages counted is taken back ----
 __global__ void s_orient_decide_kernel(SParams p, const SGeom* __restrict__ geom, const uint32_t* __restrict__ votes, const int32_t* __restrict__ ub,
                                        const int32_t* __restrict__ sc2, const FrontOut* __restrict__ fo1, const int32_t* __restrict__ fs1,
                                        const uint32_t* __restrict__ fe1, const FrontOut* __restrict__ fo2, const int32_t* __restrict__ fs2,
@@ -191,8 +228,7 @@ __global__ void s_orient_decide_kernel(SParams p, const SGeom* __restrict__ geom
   };
   if (S.cls == 0u) {
     s_count(lc, SC_PRUNED);
-    if (fo1[t].ok) { s_g = fs1[t]; fce = fe1[2 * t + 1] ? fe1[2 * t + 1] + fo1[t].shift : 0u; }
-    else if (fo2[t].ok) { s_g = fs2[t]; fce = fe2[2 * t + 1] ? fe2[2 * t + 1] + fo2[t].shift : 0u; }
+    fce = s_front_result(t, fo1, fs1, fe1, fo2, fs2, fe2, &s_g);
     if (fce == 0u) { dd |= SD_FRONT; s_count(lc, SC_PRUNED_UNCERT); }
     else if (p.exact) s_o = sc2[o * nt + t];
     else by_bound();
@@ -220,7 +256,11 @@ __global__ void s_orient_decide_kernel(SParams p, const SGeom* __restrict__ geom
   S.ce = from_front ? fce : 0u;
   re[t] = RowEndDesc{G.lr_off[w], (from_front || dd) ? 0u : G.rn, 0u};
   tr[t] = S;
-  if (dd) dead[t] |= dd;
+  if (dd && (S.mark & ST_EARLY)) {  // refuted: today's verdict alone, whatever its early stages found on the wrong strand
+    dead[t] = dd;
+    if (S.mark & ST_COUNTED_PRELIM) s_count(lc, SC_PRELIM_BANDED, ~0ull);  // (- 1: the counters are sums modulo 2^64)
+    if (S.mark & ST_COUNTED_FINAL) s_count(lc, SC_FINAL_BANDED, ~0ull);
+  } else if (dd) dead[t] |= dd;
   if (desc_trim) {  // `tracy decompose`: the pair alignment_rows_kernel reads (indigo.h:302)
     PairDesc d{};
     d.a1_off = G.prof_off + G.tl; d.a1_stride = G.mf; d.m = G.mt;
@@ -233,16 +273,18 @@ __global__ void s_orient_decide_kernel(SParams p, const SGeom* __restrict__ geom
 }
 
 // ---- preliminary alignment (pipeline.hip "o.g"): the sub-window and band its score allows around c_e (s_sub_window), as an origin-tracking sweep
-// (mode 0, `tracy align`: only its two ends are read) or a traceback completed with the free end-gap columns (mode 1) ----
-__global__ void s_prelim_plan_kernel(SParams p, int mode, const SGeom* __restrict__ geom, STrace* __restrict__ tr, const uint32_t* __restrict__ d_ce,
+// (mode 0, `tracy align`: only its two ends are read) or a traceback completed with the free end-gap columns (mode 1).
+// early: the pass over the traces marked ST_EARLY (1) or over all the others (0); a trace of the other pass is an empty slot ----
+__global__ void s_prelim_plan_kernel(SParams p, int mode, int early, const SGeom* __restrict__ geom, STrace* __restrict__ tr, const uint32_t* __restrict__ d_ce,
                                      const int32_t* __restrict__ top, uint32_t* __restrict__ dead, PairDesc* __restrict__ cand,
                                      uint8_t* __restrict__ kc) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= p.nt) return;
   kc[t] = 0;
+  STrace S = tr[t];
+  if (((S.mark & ST_EARLY) != 0u) != (early != 0)) return;
   if (dead[t]) return;
   const SGeom G = geom[t];
-  STrace S = tr[t];
   const bool from_front = S.cls == 0 && S.rc == S.g;
   const uint32_t ce = from_front ? S.ce : d_ce[t];
   S.ce = ce;
@@ -390,20 +432,22 @@ __global__ __launch_bounds__(kScanBlock) void s_scan_place_kernel(PairDesc* __re
 }
 
 // ---- `tracy align`: trimReferenceSlice from the two ends (sage.h:259) and the plan of the final alignment gotoh(full profile,
-// trimmed slice) on its certified band (sage.h:311; pipeline.hip step 4; s_final_band, s_final_certified) ----
-__global__ void s_align_final_plan_kernel(SParams p, const SGeom* __restrict__ geom, STrace* __restrict__ tr, const uint32_t* __restrict__ ends,
+// trimmed slice) on its certified band (sage.h:311; pipeline.hip step 4; s_final_band, s_final_certified); `early` as above ----
+__global__ void s_align_final_plan_kernel(SParams p, int early, const SGeom* __restrict__ geom, STrace* __restrict__ tr, const uint32_t* __restrict__ ends,
                                           uint32_t* __restrict__ dead, PairDesc* __restrict__ cand, uint8_t* __restrict__ kc,
                                           unsigned long long* __restrict__ cnt) {
   with_counters(cnt, [&](unsigned long long* lc) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= p.nt) return;
   kc[t] = 0;
+  STrace S = tr[t];
+  if (((S.mark & ST_EARLY) != 0u) != (early != 0)) return;
   if (dead[t]) return;
   const SGeom G = geom[t];
-  STrace S = tr[t];
   const uint32_t lead = ends[2 * t] + S.shift, ce = ends[2 * t + 1] + S.shift;
   S.trim = s_trim_finish(lead, ce >= lead ? ce - lead : 0u, G.rn, p.trim_left, p.trim_right, S.fwd != 0);
   s_count(lc, SC_PRELIM_BANDED);
+  if (early) S.mark |= ST_COUNTED_PRELIM;
   const uint32_t m = G.mf, n = S.trim.len;
   const SFinalBand fb = s_final_band(m, n, s_final_width(S.gap));
   uint32_t dd = 0;
@@ -425,6 +469,7 @@ __global__ void s_align_final_plan_kernel(SParams p, const SGeom* __restrict__ g
     cand[t] = q;
     kc[t] = (uint8_t)fb.K;
     s_count(lc, SC_FINAL_BANDED);
+    if (early) S.mark |= ST_COUNTED_FINAL;
   }
   tr[t] = S;
   if (dd) dead[t] |= dd;
@@ -801,6 +846,12 @@ struct OrientStage {
   // the stream waits for the voted strand's chain -- whose band tiers, launches of a few waves' depth, only get going when the sweeps drain
   // (they need 15-20 KB of LDS per workgroup; the sweeps' 7.5 KB workgroups leave no such hole) and leave the device nearly idle for 3-4 ms
   std::function<int()> filler;
+  // or stages of the call that need nothing of a trace but its voted strand's certified pruned sweep (`tracy align`: the preliminary and
+  // final alignments of the traces s_orient_early_kernel marks): queued on the voted strand's side stream behind its tiers, with the
+  // context's stream set to it, BEFORE the call's stream waits for that chain -- so they run beside the end of the full sweeps instead
+  // of on a drained device behind them.  Only called with side streams; the caller queues the same stages for the other traces itself,
+  // behind the decision.
+  std::function<int()> early_tail;
 };
 int queue_orientation(tracyhip_ctx* ctx, const tracyhip_params& p, const SParams& sp, const StreamHost& h, StreamCommon& sc, const OrientStage& os) {
   hipStream_t st = ctx->stream;
@@ -870,6 +921,11 @@ int queue_orientation(tracyhip_ctx* ctx, const tracyhip_params& p, const SParams
     int rc = TRACYHIP_OK;
     if (launch_gotoh_ckpt_front(h.classes[0].K, a, 0u, ap, npre_all, fk.side[0]) != hipSuccess) rc = set_error(TRACYHIP_ERR_HIP, "prefix launch failed");
     if (!rc) rc = front_tiers();
+    if (!rc && os.early_tail) {
+      hipLaunchKernelGGL(s_orient_early_kernel, g256, b256, 0, fk.side[0], sp, sc.fo1, sc.fs1, sc.fe1, sc.fo2, sc.fs2, sc.fe2, sc.tr);
+      if (hipGetLastError() != hipSuccess) rc = set_error(TRACYHIP_ERR_HIP, "early decision launch failed");
+      else rc = os.early_tail();
+    }
     ctx->stream = st;
     HIP_TRY(hipEventRecord(fk.joined[0], fk.side[0]));
     if (rc) {  // (whoever takes the call from here finds nothing of it running beside the call's stream)
@@ -1369,24 +1425,36 @@ struct AlignStream : StreamCall {
     return TRACYHIP_OK;
   }
 
-  int queue_stages() {
+  // stages 2 - 4 on the context's stream for the traces marked ST_EARLY (early = 1) or for all the others (0)
+  int queue_alignments(int early) {
     StreamCommon& sc = A.sc;
-    // ---- 1. orientation (sage.h:239-247) ----
-    OrientStage os{d_prof, d_qp, d_lastrow, exact, nullptr};
-    TRY(queue_orientation(ctx, p, spm, h, sc, os));
+    hipStream_t s = ctx->stream;
     // ---- 2. preliminary alignment (sage.h:258) by its two ends, 3. trimReferenceSlice (sage.h:259) ----
-    hipLaunchKernelGGL(s_prelim_plan_kernel, g256, b256, 0, st, spm, 0, sc.geom, sc.tr, sc.ce, sc.top_trim, sc.dead, sc.cand, sc.kc);
+    hipLaunchKernelGGL(s_prelim_plan_kernel, g256, b256, 0, s, spm, 0, early, sc.geom, sc.tr, sc.ce, sc.top_trim, sc.dead, sc.cand, sc.kc);
     HIP_TRY(hipGetLastError());
     BandLaunch b1;
     b1.kind = 1; b1.qp = d_qp; b1.codes = ctx->codes(); b1.ends = sc.ends; b1.code_cap = ncap; b1.hfree = 1;
     TRY(band_stage(ctx, p, sc, nt, nt, 0, b1, ~0ull));
     // ---- 4. final alignment gotoh(full profile, trimmed slice) (sage.h:311) on its certified band ----
-    hipLaunchKernelGGL(s_align_final_plan_kernel, g256, b256, 0, st, spm, sc.geom, sc.tr, sc.ends, sc.dead, sc.cand, sc.kc, sc.cnt);
+    hipLaunchKernelGGL(s_align_final_plan_kernel, g256, b256, 0, s, spm, early, sc.geom, sc.tr, sc.ends, sc.dead, sc.cand, sc.kc, sc.cnt);
     HIP_TRY(hipGetLastError());
     BandLaunch b2;
     b2.kind = 0; b2.qp = d_qp; b2.codes = ctx->codes(); b2.scores = o.score_final; b2.ops = d_ops; b2.ops_off = A.ops_off; b2.ops_len = o.ops_len; b2.code_cap = ncap;
     b2.hfree = 1;
-    TRY(band_stage(ctx, p, sc, nt, nt, 1, b2, words_cap));
+    return band_stage(ctx, p, sc, nt, nt, 1, b2, words_cap);
+  }
+
+  // The order of the call.  Side stream: the voted strands' prefixes and tiers, the early decision, stages 2 - 4 of the early traces.
+  // Call's stream: the other strands' full sweeps; then, behind both, the decision with both exact scores (which confirms or kills an
+  // early trace), stages 2 - 4 once more over the traces that were not early (the same kernels and the same lists, workspace and
+  // counters, which the first pass has finished with: the two passes' counters add up), and the certificates of all of them.
+  int queue_stages() {
+    StreamCommon& sc = A.sc;
+    // ---- 1. orientation (sage.h:239-247) ----
+    OrientStage os{d_prof, d_qp, d_lastrow, exact, nullptr};
+    if (!kn.no_early_tail && exact) os.early_tail = [this]() { return queue_alignments(1); };
+    TRY(queue_orientation(ctx, p, spm, h, sc, os));
+    TRY(queue_alignments(0));
     hipLaunchKernelGGL(s_align_finish_kernel, g256, b256, 0, st, spm, sc.tr, sc.top_full, sc.dead, o, sc.cnt);
     HIP_TRY(hipGetLastError());
     return TRACYHIP_OK;
@@ -2074,7 +2142,7 @@ struct DecStream : StreamCall {
         return encode_windows_cq();
       };
     TRY(give_up(queue_orientation(ctx, p, spm, h, sc, os)));
-    hipLaunchKernelGGL(s_prelim_plan_kernel, g256, b256, 0, st, spm, 1, sc.geom, sc.tr, sc.ce, sc.top_trim, sc.dead, sc.cand, sc.kc);
+    hipLaunchKernelGGL(s_prelim_plan_kernel, g256, b256, 0, st, spm, 1, 0, sc.geom, sc.tr, sc.ce, sc.top_trim, sc.dead, sc.cand, sc.kc);
     HIP_TRY(hipGetLastError());
     BandLaunch b0;
     b0.kind = 0; b0.qp = d_qp; b0.codes = ctx->codes(); b0.scores = A.sb; b0.ops = A.ops1; b0.ops_off = A.off1; b0.ops_len = A.len1; b0.code_cap = ncap; b0.hfree = 1;

@@ -92,8 +92,13 @@ struct STrace {         // one trace: what the stages leave for each other
   uint32_t shift;       // columns of the window left of the sub-window
   int32_t bw;           // `tracy align`: half width of the final alignment's band
   uint8_t g, cls, rc, fwd;
+  uint32_t mark;        // ST_* (`tracy align`: the early tail)
   TrimRec trim;
 };
+// STrace::mark.  A trace is EARLY when its stages behind the orientation decision were queued for the voted strand before the other
+// strand's exact score was there (s_orient_early_kernel); the decision then confirms it, or gives it the verdict SD_LOSER_WON.  The
+// two COUNTED bits say which of the call's counters its early stages added to: a refuted trace takes them back.
+enum : uint32_t { ST_EARLY = 1u, ST_COUNTED_PRELIM = 2u, ST_COUNTED_FINAL = 4u };
 struct SAllele {        // one allele of one trace (`tracy decompose`)
   int32_t sstar;
   uint32_t ce;
