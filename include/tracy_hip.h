@@ -24,6 +24,8 @@
  *   trimReferenceSlice                     fmindex.h:429-463                tracyhip_trim_reference_slice
  *   getReferenceSlice (indexed genome)     fmindex.h:236-326                tracyhip_seed_traces
  *   consensus() hot section                consensus.h:501-577              tracyhip_consensus_traces
+ *   basecall + estimateQualities           abif.h:408-511, 164-253          tracyhip_basecall_traces
+ *     trimTrace / createProfile(tr, bc)    trim.h:35-73 / profile.h:21-52   (same call)
  *     gtLetter / pairwiseConsensus         consensus.h:94-171 / 189-238     (consensus_kernel, same call)
  *
  * Conventions
@@ -493,6 +495,63 @@ typedef struct {
 int tracyhip_consensus_traces(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tracyhip_params* prm, int mem,
                               const tracyhip_consensus_result* out);
 
+/* ---- basecalling of raw chromatograms (what every command runs first) for a batch of traces --------------------------------
+ * Per trace, from the four channels of the chromatogram and the file's call positions (Trace::traceACGT, Trace::basecallpos, abif.h:28-43):
+ *   basecall(tr, bc, sigratio)             abif.h:408-511 (window peaks abif.h:77-97): primary / secondary / consensus letters, bcPos
+ *   estimateQualities(bc)                  abif.h:232-253 over findBestTraceSection abif.h:164-220: estQual
+ *   findBestTraceSection(bc)               abif.h:222-229: best_section (what nearestSNP, trim.h:10-33, starts from)
+ *   trimTrace(stringency, bc, l, r)        trim.h:35-73, when trim_stringency is not 0
+ *   createProfile(tr, bc, p)               profile.h:21-52: the untrimmed profile float[6][bc_len]
+ *   the peak table                         peaks[4 * i + k] = traceACGT[k][bcPos[i]] (tracyhip_basecalls::peaks)
+ * A window of two equal borders gives no basecall (abif.h:80), so bc_len[t] <= npos[t]; the results of a trace are packed from the start of
+ * its region.  Every result equals the host chain's (tracy_amd/host/tracy_host.hpp, sage_out.hpp) bit for bit, the profile's floats included.
+ * The reference indexes the chromatogram unchecked; the device answers a trace only when npos is in 1 .. 131071, nsamples in 3 .. 2^23 and
+ * the positions are non-decreasing inside [0, nsamples).  Any other trace is DEFERRED: status and bc_len = 0 are written, nothing else, and
+ * the caller runs the host chain for it (the convention of tracyhip_seed_traces). */
+#define TRACYHIP_BASECALL_OK 0
+#define TRACYHIP_BASECALL_DEFERRED 1 /* outside what the device answers: basecall the trace on the host */
+typedef struct {
+  uint32_t ntraces;
+  const void* signal;            /* payload: int32_t or int16_t samples; trace t: channels A,C,G,T at element signal_offset[t] + k*nsamples[t]
+                                    (the layout of tracyhip_basecalls::signal) */
+  const uint64_t* signal_offset; /* HOST array, elements */
+  const uint32_t* nsamples;      /* HOST array */
+  uint32_t sample_bytes;         /* 4: int32_t (what the readers produce); 2: int16_t (what ABIF DATA9..12 stores: half the upload) */
+  const int32_t* basecallpos;    /* payload: Trace::basecallpos of trace t at basecallpos + pos_offset[t] */
+  const uint64_t* pos_offset;    /* HOST array */
+  const uint32_t* npos;          /* HOST array */
+  float sigratio;                /* -p, default 0.33 */
+  float trim_stringency;         /* -t: 0 = no trimming (trim_left = trim_right = 0), else clamped to 1 .. 9 as the commands do */
+} tracyhip_basecall_job;
+
+/* Payload results (where `mem` says; each may be NULL = not wanted): trace t owns npos[t] entries from pos_offset[t] on (peaks: 4 per entry,
+ * from 4 * pos_offset[t]; profiles: 6 * npos[t] floats from 6 * pos_offset[t], element (k, j) at k * bc_len[t] + j, rows 4 and 5 zero), of
+ * which the first bc_len[t] are written.  Per-trace results are HOST arrays [ntraces] and required.  With TRACYHIP_MEM_DEVICE the payloads
+ * are, as they stand, the `profiles` set of tracyhip_align_job / tracyhip_consensus_job / tracyhip_decompose_job (offset 6 * pos_offset[t],
+ * length bc_len[t]) and the bcpos / primary / secondary / peaks of tracyhip_basecalls (bc_offset = pos_offset, bc_len). */
+typedef struct {
+  int32_t* status;        /* TRACYHIP_BASECALL_* */
+  uint32_t* bc_len;       /* bc.primary.size() */
+  uint32_t* trim_left;    /* trimTrace's leftTrim, truncated to 16 bits as SageConfig holds it (sage.h:39-40) */
+  uint32_t* trim_right;
+  uint32_t* best_section; /* findBestTraceSection(bc) */
+  uint8_t* primary;
+  uint8_t* secondary;
+  uint8_t* consensus;
+  int32_t* bcpos;
+  uint8_t* estqual;
+  int32_t* peaks;
+  float* profiles;
+} tracyhip_basecall_result;
+
+/* what tracyhip_basecall_traces checks before it touches a device (none is needed here): NULL job / result / required arrays, mem,
+ * sample_bytes other than 2 or 4, a sigratio or trim_stringency that is not a number, a negative trim_stringency, misaligned payloads.
+ * TRACYHIP_ERR_ARG (with the reason) otherwise TRACYHIP_OK. */
+int tracyhip_basecall_validate(const tracyhip_basecall_job* job, int mem, const tracyhip_basecall_result* out);
+/* One launch and ONE host synchronisation per call with device payloads (bc_len is metadata the caller needs on the host to build the next
+ * job); host payloads are staged in chunks of about 256 MB of chromatogram, with a second synchronisation each for the copy back. */
+int tracyhip_basecall_traces(tracyhip_ctx* ctx, const tracyhip_basecall_job* job, int mem, const tracyhip_basecall_result* out);
+
 /* ---- asynchronous forms (SURVEY.md 8b "Threading": synchronous by default with an async variant) ---------------------
  * Same arguments and results as the call without the suffix; the call returns as soon as the work is queued on the
  * context.  A context executes its calls in issue order on its own worker thread and stream (the pipelines need the
@@ -510,6 +569,7 @@ int tracyhip_decompose_traces_async(tracyhip_ctx* ctx, const tracyhip_decompose_
                                     const tracyhip_decompose_result* out);
 int tracyhip_consensus_traces_async(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tracyhip_params* prm, int mem,
                                     const tracyhip_consensus_result* out);
+int tracyhip_basecall_traces_async(tracyhip_ctx* ctx, const tracyhip_basecall_job* job, int mem, const tracyhip_basecall_result* out);
 
 /* ---- device groups: the GPUs of one node behind one handle (north star: "batches of traces shard embarrassingly across
  * the 8 GPUs of one node") ------------------------------------------------------------------------------------------

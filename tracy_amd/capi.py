@@ -738,17 +738,47 @@ class DecomposeResult(C.Structure):
 
 
 def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_right=50, maxindel=1000, madc=5, oriented=None,
-                      ref_profiles=None, exact_scores=True, peaks_only=False):
+                      ref_profiles=None, exact_scores=True, peaks_only=False, device_bc=None):
     """tracyhip_decompose_traces with host buffers; hbc: HostBaseCalls (primary/secondary rewritten in place);
-    oriented: None, or rs.forward per trace when the references are already oriented (indexed-genome path)"""
-    pp = profiles if isinstance(profiles, PackedSeqs) else PackedSeqs(profiles, SEQ_PROFILE)
+    oriented: None, or rs.forward per trace when the references are already oriented (indexed-genome path).
+    device_bc: a PreparedBasecall(device=True) that has run -- profiles, basecalls and peak table are taken from its device tensors as they
+    stand (profiles and hbc may be None), references and results live on the device too (TRACYHIP_MEM_DEVICE) and are copied back."""
+    dev = device_bc is not None
+    mirrors = []
+    if dev:
+        import torch
+
+    def put(holder, key, buf):  # a result array: the host buffer, or with device_bc its mirror on the device
+        addr = C.addressof(buf) if isinstance(buf, C.Array) else buf.ctypes.data
+        if dev:
+            nbytes = C.sizeof(buf) if isinstance(buf, C.Array) else buf.nbytes
+            t = torch.zeros(max(nbytes, 1), dtype=torch.uint8, device="cuda")
+            mirrors.append((t, addr, nbytes))
+            addr = t.data_ptr()
+        if isinstance(key, int):
+            holder[key] = addr
+        else:
+            setattr(holder, key, addr)
+
     pr = refs if isinstance(refs, PackedSeqs) else PackedSeqs(refs, SEQ_CHAR)
-    nt = pp.count
     job = DecomposeJob()
+    if dev:
+        nt = device_bc.nt
+        job.profiles = device_bc.profiles_seqset()
+        job.bc = device_bc.basecalls_struct(peaks_only=True)
+        d_refs = torch.from_numpy(pr.data).cuda()
+        job.refs = pr.seqset(d_refs.data_ptr())
+        mf = device_bc.meta["bc_len"][:nt].astype(np.uint64)
+        nbases = device_bc.total
+    else:
+        pp = profiles if isinstance(profiles, PackedSeqs) else PackedSeqs(profiles, SEQ_PROFILE)
+        nt = pp.count
+        job.profiles = pp.seqset()
+        job.bc = hbc.struct(peaks_only)  # (peaks_only: the peak table instead of the chromatograms, tracyhip_basecalls::peaks)
+        job.refs = pr.seqset()
+        mf = pp.length[:nt].astype(np.uint64)
+        nbases = len(hbc.primary)
     job.ntraces = nt
-    job.profiles = pp.seqset()
-    job.bc = hbc.struct(peaks_only)  # (peaks_only: the peak table instead of the chromatograms, tracyhip_basecalls::peaks)
-    job.refs = pr.seqset()
     job.dprm = DecompParams(trim_left, trim_right, maxindel, madc)
     job.strand_by_certificate = 0 if exact_scores else 1  # opt-in: the losing strand may carry a certified upper bound
     if oriented is not None:
@@ -759,21 +789,18 @@ def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_righ
         job.ref_profiles = prp.seqset()
     cap = 2 * maxindel + 2
     doff = np.arange(max(nt, 1), dtype=np.uint64) * np.uint64(cap)
-    mf = pp.length[:nt].astype(np.uint64)
     rn = pr.length[:nt].astype(np.uint64)
     res = {
         "bp": (Breakpoint * max(nt, 1))(), "status": np.zeros(max(nt, 1), np.int32),
         "score_fwd": np.zeros(max(nt, 1), np.int32), "score_rev": np.zeros(max(nt, 1), np.int32),
         "forward": np.zeros(max(nt, 1), np.uint8), "score_trim": np.zeros(max(nt, 1), np.int32),
         "dcp_indel": np.zeros(max(nt, 1) * cap, np.int32), "dcp_err": np.zeros(max(nt, 1) * cap, np.int32),
-        "dstatus": (DecompStatus * max(nt, 1))(), "secdecomp": np.zeros(max(len(hbc.primary), 1), np.uint8),
+        "dstatus": (DecompStatus * max(nt, 1))(), "secdecomp": np.zeros(max(nbases, 1), np.uint8),
         "fractions": np.zeros(2 * max(nt, 1), np.float64),
     }
     out = DecomposeResult()
-    out.bp = C.addressof(res["bp"])
-    out.dstatus = C.addressof(res["dstatus"])
-    for k in ("status", "score_fwd", "score_rev", "forward", "score_trim", "dcp_indel", "dcp_err", "secdecomp", "fractions"):
-        setattr(out, k, res[k].ctypes.data)
+    for k in ("bp", "dstatus", "status", "score_fwd", "score_rev", "forward", "score_trim", "dcp_indel", "dcp_err", "secdecomp", "fractions"):
+        put(out, k, res[k])
     out.dcp_offset = _u64p(doff)
     keep = []
     for k in range(3):
@@ -784,19 +811,26 @@ def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_righ
         ops = np.zeros(max(int(caps.sum()), 1), np.uint8)
         olen = np.zeros(max(nt, 1), np.uint32)
         sc = np.zeros(max(nt, 1), np.int32)
-        out.score[k] = sc.ctypes.data
-        out.ops[k] = ops.ctypes.data
+        put(out.score, k, sc)
+        put(out.ops, k, ops)
         out.ops_offset[k] = _u64p(off)
-        out.ops_len[k] = olen.ctypes.data
+        put(out.ops_len, k, olen)
         res["score%d" % k] = sc
         keep.append((off, ops, olen))
         if k < 2:
             for nm in ("slice_begin", "slice_len", "ref_pos"):
                 a = np.zeros(max(nt, 1), np.uint32)
-                getattr(out, nm)[k] = a.ctypes.data
+                put(getattr(out, nm), k, a)
                 res["%s%d" % (nm, k)] = a
     prm = Params(params[0], params[1], params[2], params[3], 1, 0)
-    if isinstance(self, Group):
+    if dev:
+        torch.cuda.synchronize()
+        _check(lib().tracyhip_decompose_traces(self._h, C.byref(job), C.byref(prm), MEM_DEVICE, C.byref(out)))
+        torch.cuda.synchronize()
+        for t, addr, nbytes in mirrors:
+            h = t.cpu().numpy()  # (held while its bytes are copied)
+            C.memmove(addr, h.ctypes.data, nbytes)
+    elif isinstance(self, Group):
         _check(lib().tracyhip_group_decompose_traces(self._g, C.byref(job), C.byref(prm), C.byref(out)))
     else:
         _check(lib().tracyhip_decompose_traces(self._h, C.byref(job), C.byref(prm), MEM_HOST, C.byref(out)))
@@ -805,6 +839,12 @@ def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_righ
         res["btr%d" % k] = [ops[int(off[i]):int(off[i]) + int(olen[i])].tobytes() for i in range(nt)]
     res["dcp"] = [[(int(res["dcp_indel"][i * cap + j]), int(res["dcp_err"][i * cap + j])) for j in range(res["dstatus"][i].dcp_n)]
                   for i in range(nt)]
+    if dev:  # the decomposed basecalls as the call left them in the device tensors
+        rows = device_bc.results(fill_deferred=False)
+        res["primary"] = [r["primary"] for r in rows]
+        res["secondary"] = [r["secondary"] for r in rows]
+        res["secdecomp_list"] = [res["secdecomp"][int(device_bc.pos_off[i]):int(device_bc.pos_off[i]) + rows[i]["bc_len"]].tobytes() for i in range(nt)]
+        return res
     res["primary"] = hbc.split(hbc.primary)
     res["secondary"] = hbc.split(hbc.secondary)
     res["secdecomp_list"] = hbc.split(res["secdecomp"])
@@ -889,3 +929,148 @@ def genome_download(h, bucket_bits):
     t = np.empty((genome_ntab(h), 2), dtype=np.uint64)
     _check(lib().tracyhip_genome_download(h, C.c_void_p(d.ctypes.data), C.c_void_p(t.ctypes.data if t.size else 0)))
     return d, t
+
+
+# ---- basecalling of raw chromatograms on the device (tracyhip_basecall_traces) -------------------------------------------------------
+BASECALL_OK, BASECALL_DEFERRED = 0, 1
+
+
+class BasecallJob(C.Structure):
+    _fields_ = [("ntraces", C.c_uint32), ("signal", C.c_void_p), ("signal_offset", C.POINTER(C.c_uint64)), ("nsamples", C.POINTER(C.c_uint32)),
+                ("sample_bytes", C.c_uint32), ("basecallpos", C.c_void_p), ("pos_offset", C.POINTER(C.c_uint64)), ("npos", C.POINTER(C.c_uint32)),
+                ("sigratio", C.c_float), ("trim_stringency", C.c_float)]
+
+
+class BasecallResult(C.Structure):
+    _fields_ = [("status", C.POINTER(C.c_int32)), ("bc_len", C.POINTER(C.c_uint32)), ("trim_left", C.POINTER(C.c_uint32)),
+                ("trim_right", C.POINTER(C.c_uint32)), ("best_section", C.POINTER(C.c_uint32)), ("primary", C.c_void_p), ("secondary", C.c_void_p),
+                ("consensus", C.c_void_p), ("bcpos", C.c_void_p), ("estqual", C.c_void_p), ("peaks", C.c_void_p), ("profiles", C.c_void_p)]
+
+
+_BC_PAYLOADS = (("primary", np.uint8, 1), ("secondary", np.uint8, 1), ("consensus", np.uint8, 1), ("bcpos", np.int32, 1), ("estqual", np.uint8, 1),
+                ("peaks", np.int32, 4), ("profiles", np.float32, 6))
+
+
+class PreparedBasecall:
+    """job / result structs of tracyhip_basecall_traces over packed signals (int32 or int16 [4][ns] per trace) and call positions; with
+    device=True the payloads are torch tensors on the GPU and stay there: profiles_seqset() / basecalls_struct() hand them to the align,
+    consensus and decompose jobs without a host copy.  Everything the structs point to is kept alive by this object."""
+
+    def __init__(self, signals, positions, sigratio=0.33, trim_stringency=0, device=False, sample_dtype=None):
+        nt = self.nt = len(signals)
+        if sample_dtype is None:
+            sample_dtype = np.int16 if nt and all(np.asarray(s).dtype == np.int16 for s in signals) else np.int32
+        self.sample_dtype = np.dtype(sample_dtype)
+        self.device = device
+        self.nsamples = np.array([np.asarray(s).shape[1] for s in signals] + [0], dtype=np.uint32)[:max(nt, 1)]
+        self.npos = np.array([len(p) for p in positions] + [0], dtype=np.uint32)[:max(nt, 1)]
+        self.sig_off = np.zeros(max(nt, 1), np.uint64)
+        self.pos_off = np.zeros(max(nt, 1), np.uint64)
+        if nt:
+            self.sig_off[1:nt] = np.cumsum(4 * self.nsamples[:nt].astype(np.uint64))[:-1]
+            self.pos_off[1:nt] = np.cumsum(self.npos[:nt].astype(np.uint64))[:-1]
+        self.signal = (np.concatenate([np.ascontiguousarray(s, dtype=self.sample_dtype).reshape(-1) for s in signals])
+                       if nt else np.zeros(1, self.sample_dtype))
+        self.positions = np.concatenate([np.ascontiguousarray(p, dtype=np.int32) for p in positions] + [np.zeros(1, np.int32)])
+        total = self.total = int(self.npos[:nt].sum()) if nt else 0
+        self.meta = {k: np.zeros(max(nt, 1), np.int32 if k == "status" else np.uint32)
+                     for k in ("status", "bc_len", "trim_left", "trim_right", "best_section")}
+        job = self.job = BasecallJob()
+        job.ntraces = nt
+        job.signal_offset, job.nsamples = _u64p(self.sig_off), _u32p(self.nsamples)
+        job.pos_offset, job.npos = _u64p(self.pos_off), _u32p(self.npos)
+        job.sample_bytes = self.sample_dtype.itemsize
+        job.sigratio = sigratio
+        job.trim_stringency = trim_stringency
+        out = self.out = BasecallResult()
+        out.status = self.meta["status"].ctypes.data_as(C.POINTER(C.c_int32))
+        for k in ("bc_len", "trim_left", "trim_right", "best_section"):
+            setattr(out, k, _u32p(self.meta[k]))
+        if device:
+            import torch
+            self.d_signal = torch.from_numpy(self.signal).cuda()
+            self.d_positions = torch.from_numpy(self.positions).cuda()
+            self.payload = {k: torch.zeros(max(total, 1) * w, dtype=getattr(torch, np.dtype(dt).name), device="cuda") for k, dt, w in _BC_PAYLOADS}
+            job.signal, job.basecallpos = self.d_signal.data_ptr(), self.d_positions.data_ptr()
+            for k, _, _ in _BC_PAYLOADS:
+                setattr(out, k, self.payload[k].data_ptr())
+            torch.cuda.synchronize()
+        else:
+            self.payload = {k: np.zeros(max(total, 1) * w, dt) for k, dt, w in _BC_PAYLOADS}
+            job.signal, job.basecallpos = self.signal.ctypes.data, self.positions.ctypes.data
+            for k, _, _ in _BC_PAYLOADS:
+                setattr(out, k, self.payload[k].ctypes.data)
+        self.mem = MEM_DEVICE if device else MEM_HOST
+
+    def run(self, ctx, asynchronous=False):
+        fn = lib().tracyhip_basecall_traces_async if asynchronous else lib().tracyhip_basecall_traces
+        _check(fn(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
+        return self
+
+    def profiles_seqset(self):
+        """the `profiles` set of AlignJob / ConsensusJob / DecomposeJob: trace t = bc_len[t] columns at 6 * pos_offset[t]"""
+        self._prof_off = (6 * self.pos_off).astype(np.uint64)
+        s = SeqSet()
+        s.kind = SEQ_PROFILE
+        s.data = self.payload["profiles"].data_ptr() if self.device else self.payload["profiles"].ctypes.data
+        s.offset, s.length, s.count = _u64p(self._prof_off), _u32p(self.meta["bc_len"]), self.nt
+        return s
+
+    def basecalls_struct(self, peaks_only=True):
+        """tracyhip_basecalls of the batch (bcpos / primary / secondary / the peak table as the call left them)"""
+        ptr = (lambda a: a.data_ptr()) if self.device else (lambda a: a.ctypes.data)
+        b = BaseCallsBatch()
+        b.ntraces = self.nt
+        if not peaks_only:
+            b.signal = ptr(self.d_signal if self.device else self.signal)
+            if self.sample_dtype != np.int32:
+                raise ValueError("tracyhip_basecalls::signal holds int32 samples: pass peaks_only=True")
+            b.signal_offset, b.nsamples = _u64p(self.sig_off), _u32p(self.nsamples)
+            b.bcpos = ptr(self.payload["bcpos"])
+        b.primary, b.secondary, b.peaks = ptr(self.payload["primary"]), ptr(self.payload["secondary"]), ptr(self.payload["peaks"])
+        b.bc_offset, b.bc_len = _u64p(self.pos_off), _u32p(self.meta["bc_len"])
+        return b
+
+    def results(self, fill_deferred=True):
+        """per trace: dict of numpy views (device payloads are copied back); deferred traces are filled in from the host chain, except those
+        with a position outside their chromatogram (`unreadable`: status stays DEFERRED, bc_len 0)"""
+        from . import hostlib
+        pay = {k: (v.cpu().numpy() if self.device else v) for k, v in self.payload.items()}
+        out = []
+        for t in range(self.nt):
+            o, n = int(self.pos_off[t]), int(self.meta["bc_len"][t])
+            r = dict(status=int(self.meta["status"][t]), bc_len=n, trim_left=int(self.meta["trim_left"][t]),
+                     trim_right=int(self.meta["trim_right"][t]), best_section=int(self.meta["best_section"][t]))
+            if r["status"] == BASECALL_DEFERRED and fill_deferred:
+                ns = int(self.nsamples[t])
+                sig = self.signal[int(self.sig_off[t]):int(self.sig_off[t]) + 4 * ns].reshape(4, ns).astype(np.int32)
+                pos = self.positions[o:o + int(self.npos[t])]
+                if len(pos) and (int(pos.min()) < 0 or int(pos.max()) >= ns):  # the reference indexes the chromatogram unchecked: nobody can call these
+                    r.update(unreadable=True, primary=b"", secondary=b"", consensus=b"", bcpos=pos[:0], estqual=np.zeros(0, np.uint8),
+                             peaks=np.zeros((0, 4), np.int32), profile=np.zeros((6, 0), np.float32))
+                    out.append(r)
+                    continue
+                pri, sec, con, bcpos, q = hostlib.basecall_qual(sig, pos, self.job.sigratio)
+                s = float(self.job.trim_stringency)
+                tl, tr = hostlib.trim_trace(sig, pos, self.job.sigratio, min(max(s, 1.0), 9.0)) if s else (0, 0)
+                r.update(bc_len=len(pri), trim_left=tl & 0xFFFF, trim_right=tr & 0xFFFF, best_section=None, primary=pri, secondary=sec, consensus=con,
+                         bcpos=bcpos, estqual=q, peaks=np.ascontiguousarray(sig[:, bcpos].T) if len(pri) else np.zeros((0, 4), np.int32),
+                         profile=hostlib.create_profile(sig, bcpos, pri, sec) if len(pri) else np.zeros((6, 0), np.float32))
+            else:
+                r.update(primary=pay["primary"][o:o + n].tobytes(), secondary=pay["secondary"][o:o + n].tobytes(),
+                         consensus=pay["consensus"][o:o + n].tobytes(), bcpos=pay["bcpos"][o:o + n], estqual=pay["estqual"][o:o + n],
+                         peaks=pay["peaks"][4 * o:4 * (o + n)].reshape(n, 4), profile=pay["profiles"][6 * o:6 * (o + n)].reshape(6, n))
+            out.append(r)
+        return out
+
+
+def _basecall_traces(self, signals, positions, sigratio=0.33, trim_stringency=0, device=False):
+    """tracyhip_basecall_traces.  signals: int32 or int16 [4][ns] per trace (all int16: uploaded as int16); positions: Trace::basecallpos per
+    trace.  device=False: host buffers, returns the per-trace results (PreparedBasecall.results).  device=True: returns the PreparedBasecall
+    holding torch tensors on the GPU; .profiles_seqset() / .basecalls_struct() feed the align / consensus / decompose jobs, .results()
+    copies back."""
+    p = PreparedBasecall(signals, positions, sigratio, trim_stringency, device).run(self)
+    return p if device else p.results()
+
+
+Context.basecall_traces = _basecall_traces

@@ -126,6 +126,7 @@ struct tracyhip_ctx {
   bool b16_fork_ok = false;
   tracyhip::DevBuf d_stream;                   // everything the stream-ordered pipelines keep on the device between their stages (stream.hip)
   tracyhip::DevBuf d_seed[3];                  // tracyhip_seed_traces (seed.hip): per-trace inputs / results, staged consensus, staged windows
+  tracyhip::DevBuf d_bcall[5];                 // tracyhip_basecall_traces (basecall.hip): per-trace inputs / results, scratch, staged signal, positions, payload results
   tracyhip::DevBuf d_cons[12];                 // tracyhip_consensus_traces (consensus.hip): both strands, classes, scores, ops, staged results, fix-ups, gq table
   bool cons_gq_ready = false;                  // d_cons holds the gq table of consensus.h
   hipError_t ensure_codes(size_t bytes, hipStream_t st) {
@@ -189,6 +190,7 @@ struct tracyhip_ctx {
     d_pre.release();
     d_stream.release();
     for (auto& b : d_seed) b.release();
+    for (auto& b : d_bcall) b.release();
     for (auto& b : d_cons) b.release();
     cons_gq_ready = false;
     h_desc.release();

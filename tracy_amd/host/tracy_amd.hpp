@@ -23,6 +23,7 @@
 #ifndef TRACY_AMD_HPP
 #define TRACY_AMD_HPP
 
+#include <algorithm>
 #include <iostream>
 #include <stdexcept>
 #include <string>
@@ -275,6 +276,48 @@ inline void trimReferenceSlice(TConfig const& c, TAlign const& align, ReferenceS
   // bases the alignment holds, which are all of rs.refslice)
   rs.refslice = rs.refslice.substr(ri, rl);
   rs.pos += dp;
+}
+
+// basecall(tr, bc, sigratio) (abif.h:408-511, with estimateQualities) and createProfile(tr, bc, p) (profile.h:21-52) of one trace on the
+// device: tracyhip_basecall_traces with a batch of one.  The host functions of the same names (tracy_host.hpp) stay what the commands
+// call; this is the per-call form of the batched entry point, for a caller that holds a Trace.  A trace the device defers (positions
+// outside the chromatogram or out of order, no positions) is handed to the host functions, as the ABI asks.  Returns true when the device
+// answered.
+inline bool basecallOnDevice(Trace const& tr, BaseCalls& bc, float sigratio, Profile* profile = nullptr) {
+  const uint32_t np = (uint32_t)tr.basecallpos.size();
+  const uint32_t ns = tr.traceACGT.size() == 4 ? (uint32_t)tr.traceACGT[0].size() : 0;
+  bool usable = ns > 0 && np > 0;
+  for (std::size_t k = 0; usable && k < 4; ++k) usable = tr.traceACGT[k].size() == ns;
+  int32_t status = TRACYHIP_BASECALL_DEFERRED;
+  uint32_t bc_len = 0, tl = 0, trr = 0, best = 0;
+  std::vector<uint8_t> pri(np + 1), sec(np + 1), con(np + 1), q(np + 1);
+  std::vector<int32_t> pos(np + 1);
+  std::vector<float> prof(6 * (std::size_t)np + 1);
+  if (usable) {
+    std::vector<int32_t> sig(4 * (std::size_t)ns);
+    for (std::size_t k = 0; k < 4; ++k) std::copy(tr.traceACGT[k].begin(), tr.traceACGT[k].end(), sig.begin() + k * ns);
+    const uint64_t zero = 0;
+    tracyhip_basecall_job job{1, sig.data(), &zero, &ns, 4, tr.basecallpos.data(), &zero, &np, sigratio, 0.0f};
+    tracyhip_basecall_result out{&status, &bc_len, &tl, &trr, &best, pri.data(), sec.data(), con.data(), pos.data(), q.data(), nullptr,
+                                 profile ? prof.data() : nullptr};
+    detail::check(tracyhip_basecall_traces(detail::context(), &job, TRACYHIP_MEM_HOST, &out));
+  }
+  if (status != TRACYHIP_BASECALL_OK) {
+    basecall(tr, bc, sigratio);
+    if (profile) createProfile(tr, bc, *profile);
+    return false;
+  }
+  bc = BaseCalls();
+  bc.primary.assign(pri.begin(), pri.begin() + bc_len);
+  bc.secondary.assign(sec.begin(), sec.begin() + bc_len);
+  bc.consensus.assign(con.begin(), con.begin() + bc_len);
+  bc.bcPos.assign(pos.begin(), pos.begin() + bc_len);
+  bc.estQual.assign(q.begin(), q.begin() + bc_len);
+  if (profile) {
+    profile->resize(bc_len);
+    std::copy(prof.begin(), prof.begin() + 6 * (std::size_t)bc_len, profile->v.begin());
+  }
+  return true;
 }
 
 }  // namespace tracy_amd

@@ -2,6 +2,7 @@
 // by bench.py and the parity tests.  Host-only library (libtracy_host.so):
 // basecalling / profile creation are host stages in the reference too.
 #include <algorithm>
+#include <chrono>
 #include <cstring>
 #include <thread>
 #include <vector>
@@ -623,6 +624,53 @@ static void synth_decompose_batch_mix(uint64_t seed0, uint32_t nt, uint32_t n, u
   std::vector<std::thread> th;
   for (uint32_t t = 0; t < nthreads; ++t) th.emplace_back(work, t);
   for (auto& t : th) t.join();
+}
+
+// The host chain in front of every command -- basecall (+ estimateQualities), trimTrace when stringency >= 1, createProfile -- for a batch
+// of equally shaped traces on `nthreads` threads: signal [nt][4][ns], basecallpos [nt][np]; results [nt][np] (profiles [nt][6][np], the
+// first 6 * bc_len[i] floats of a trace's region used), trims [nt][2].  Any result pointer may be null.  Returns the seconds the slowest
+// thread spent in the chain itself: every thread first copies its traces into Trace objects (what a file reader leaves), untimed.
+double tracyhost_basecall_batch(const int32_t* signal, uint32_t nt, uint32_t ns, const int32_t* basecallpos, uint32_t np, float sigratio,
+                                float stringency, uint32_t nthreads, uint8_t* primary, uint8_t* secondary, int32_t* bcpos, uint8_t* estqual,
+                                float* profiles, uint32_t* bc_len, uint32_t* trims) {
+  if (nthreads == 0) nthreads = tracy_amd::usable_threads();
+  std::vector<double> spent(nthreads, 0.0);
+  auto work = [&](uint32_t tid) {
+    const uint32_t lo = (uint32_t)((uint64_t)nt * tid / nthreads), hi = (uint32_t)((uint64_t)nt * (tid + 1) / nthreads);
+    std::vector<Trace> trs(hi - lo);
+    for (uint32_t i = lo; i < hi; ++i) {
+      Trace& tr = trs[i - lo];
+      tr.traceACGT.resize(4);
+      const int32_t* sig = signal + (size_t)i * 4 * ns;
+      for (int k = 0; k < 4; ++k) tr.traceACGT[k].assign(sig + (size_t)k * ns, sig + (size_t)(k + 1) * ns);
+      tr.basecallpos.assign(basecallpos + (size_t)i * np, basecallpos + (size_t)(i + 1) * np);
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint32_t i = lo; i < hi; ++i) {
+      Trace const& tr = trs[i - lo];
+      BaseCalls bc;
+      basecall(tr, bc, sigratio);
+      uint32_t l = 0, r = 0;
+      if (stringency >= 1) trimTrace(stringency, bc, l, r);
+      Profile p;
+      createProfile(tr, bc, p, 0, 0);
+      const size_t n = bc.primary.size();
+      if (primary) std::memcpy(primary + (size_t)i * np, bc.primary.data(), n);
+      if (secondary) std::memcpy(secondary + (size_t)i * np, bc.secondary.data(), n);
+      if (bcpos) std::memcpy(bcpos + (size_t)i * np, bc.bcPos.data(), n * sizeof(int32_t));
+      if (estqual) std::memcpy(estqual + (size_t)i * np, bc.estQual.data(), n);
+      if (profiles) std::memcpy(profiles + (size_t)i * 6 * np, p.data(), sizeof(float) * 6 * n);
+      if (bc_len) bc_len[i] = (uint32_t)n;
+      if (trims) { trims[2 * i] = (uint16_t)l; trims[2 * i + 1] = (uint16_t)r; }
+    }
+    spent[tid] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  };
+  std::vector<std::thread> th;
+  for (uint32_t t = 0; t < nthreads; ++t) th.emplace_back(work, t);
+  for (auto& t : th) t.join();
+  double worst = 0;
+  for (double v : spent) worst = std::max(worst, v);
+  return worst;
 }
 
 // threads the batch entry points start when the caller passes nthreads = 0

@@ -108,6 +108,28 @@ def basecall_qual(trace, basecallpos, sigratio=0.33):
     return pri.raw[:k], sec.raw[:k], con.raw[:k], bc[:k].copy(), q[:k].copy()
 
 
+def basecall_batch(signal, basecallpos, sigratio=0.33, stringency=0.0, nthreads=0, want=True):
+    """the host chain (basecall + qualities, trimTrace when stringency >= 1, createProfile) of a batch of equally shaped traces on
+    `nthreads` threads: signal int32 [nt][4][ns], basecallpos int32 [nt][np].  Returns (seconds the slowest thread spent in the chain,
+    dict of results or None when want is False)."""
+    signal = np.ascontiguousarray(signal, dtype=np.int32)
+    pos = np.ascontiguousarray(basecallpos, dtype=np.int32)
+    nt, _, ns = signal.shape
+    npos = pos.shape[1]
+    res = None
+    ptr = [None] * 7
+    if want:
+        res = dict(primary=np.zeros((nt, npos), np.uint8), secondary=np.zeros((nt, npos), np.uint8), bcpos=np.zeros((nt, npos), np.int32),
+                   estqual=np.zeros((nt, npos), np.uint8), profiles=np.zeros((nt, 6 * npos), np.float32), bc_len=np.zeros(nt, np.uint32),
+                   trims=np.zeros((nt, 2), np.uint32))
+        ptr = [C.c_void_p(res[k].ctypes.data) for k in ("primary", "secondary", "bcpos", "estqual", "profiles", "bc_len", "trims")]
+    fn = lib().tracyhost_basecall_batch
+    fn.restype = C.c_double
+    secs = fn(C.c_void_p(signal.ctypes.data), C.c_uint32(nt), C.c_uint32(ns), C.c_void_p(pos.ctypes.data), C.c_uint32(npos), C.c_float(sigratio),
+              C.c_float(stringency), C.c_uint32(nthreads), *ptr)
+    return secs, res
+
+
 def _read_trace_with(l, prefix, path, with_format):
     rd = getattr(l, prefix + "trace_read")
     rd.restype = C.c_void_p
