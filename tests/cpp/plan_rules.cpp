@@ -1,4 +1,4 @@
-// plan_rules.cpp -- host build of the per-trace planning rules of tracy_amd/csrc/stream_plan.h (the functions both planners call)
+// plan_rules.cpp -- host build of the per-trace planning rules of tracy_amd/csrc/stream_plan.h and dp_lane.h (the functions both planners call)
 // for tests/test_plan_rules_host.py.  Every entry point takes n rows of int64 arguments (row-major, cast to the rule's parameter
 // types as a caller's would be) and writes n rows of int64 results.
 #include <cstdint>
@@ -45,6 +45,23 @@ void pr_orient_class(uint64_t n, const int64_t* in, int64_t* out) {
   for (uint64_t i = 0; i < n; ++i, in += 5, out += 3) {
     const SOrient o = s_orient_class((uint32_t)in[0], (uint32_t)in[1], (uint32_t)in[2], in[3] != 0, in[4] != 0);
     out[0] = o.g; out[1] = o.both; out[2] = o.cls;
+  }
+}
+
+// in: vf vr -> g clear; orient -> vote_skips_checkpoints (the sweep kernels' use of the same vote)
+void pr_clear_vote(uint64_t n, const int64_t* in, int64_t* out) {
+  for (uint64_t i = 0; i < n; ++i, in += 3, out += 3) {
+    const ClearVote v = s_clear_vote((uint32_t)in[0], (uint32_t)in[1]);
+    out[0] = v.g; out[1] = v.clear;
+    out[2] = vote_skips_checkpoints((uint32_t)in[0], (uint32_t)in[1], (uint32_t)in[2]);
+  }
+}
+
+// in: g prefix ub s_g -> certified bound
+void pr_strand_by_bound(uint64_t n, const int64_t* in, int64_t* out) {
+  for (uint64_t i = 0; i < n; ++i, in += 4, out += 2) {
+    const SStrand c = s_strand_by_bound((uint32_t)in[0], (int32_t)in[1], (int32_t)in[2], in[3]);
+    out[0] = c.certified; out[1] = c.bound;
   }
 }
 

@@ -372,6 +372,47 @@ def test_strand_by_certificate(ctx):
     assert nb >= 12  # most losers were decided by their bound
 
 
+def test_strand_by_certificate_voted_strand_in_full_planned_by_the_host(ctx):
+    """The form of the host-planned pipeline between the pruned sweep and the two-stage form (pipeline.hip, orient_vote; options
+    no_stream + no_front, one strip height in the batch): the strand the k-mers vote for swept in full, the prefix bound of the
+    other in the same launch.  (Every trimmed trace here has 600 rows, so the batch has one strip height, which is what makes the
+    pipeline take this form and not the two-stage one of test_strand_by_certificate.)  Every decision, the slice and both alignments are the oracle's and those of the default path, array
+    for array; the winner's score is exact, the loser's entry bounds its score from above without reaching the winner's."""
+    import sage_oracle as so
+    from tracy_amd import hostlib
+    refs, profs, rev = hostlib.synth_align(8100, 24, 4000, 700, 2)
+    profs = list(profs)
+    rng = np.random.default_rng(3)
+    profs[5] = rand_profile(rng, 700)  # unrelated to its window: no clear vote, both strands in full
+    refl = [r.tobytes() for r in refs]
+    default = ctx.align_traces(profs, refl, SC, 50, 50, exact_scores=False)
+    ctx.set_option("no_stream", 1)
+    ctx.set_option("no_front", 1)
+    try:
+        voted = ctx.align_traces(profs, refl, SC, 50, 50, exact_scores=False)
+        said = ctx.last_call_stats()
+    finally:
+        ctx.set_option("no_front", 0)
+        ctx.set_option("no_stream", 0)
+    assert said["stream_ordered"] == 0 and said["pruned"] == 0, said
+    for k in ("forward", "score_prelim", "slice_begin", "slice_len", "ref_pos", "score_final"):
+        assert np.array_equal(np.asarray(voted[k]), np.asarray(default[k])), k
+    assert voted["btr"] == default["btr"]
+    nb = 0
+    for i in range(24):
+        want = so.align_trace(profs[i], refl[i], SC, 50, 50)
+        for k in ("forward", "score_prelim", "slice_begin", "slice_len", "ref_pos", "score_final"):
+            assert int(voted[k][i]) == int(want[k]), (i, k)
+        assert voted["btr"][i] == want["btr"], i
+        w, l = ("score_fwd", "score_rev") if want["forward"] else ("score_rev", "score_fwd")
+        assert int(voted[w][i]) == want[w] and int(voted[l][i]) >= want[l], i
+        assert (int(voted[l][i]) < int(voted[w][i])) if want["forward"] else (int(voted[l][i]) <= int(voted[w][i])), i
+        nb += int(voted[l][i]) != want[l]
+        if i == 5:  # (no 32 shared 11-mers with a random window: both scores exact)
+            assert int(voted[l][i]) == want[l]
+    assert nb >= 12  # most losers were decided by their bound
+
+
 def test_align_traces_lanes(ctx):
     """tracyhip_set_lanes: the batch split over concurrent chunks gives the arrays of the single-lane call, in host and
     in shared-reference (ref_index) form, in both orientation modes"""

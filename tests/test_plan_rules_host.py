@@ -1,7 +1,8 @@
 """The per-trace planning rules both pipelines call (tracy_amd/csrc/stream_plan.h: the host-planned tiers of pipeline.hip and the
 planning kernels of stream.hip), built for the host with their own small g++ step and checked against a direct statement of the
 arithmetic in their comments: on 10^5 seeded random inputs per rule and on the edges (g at 2^20, no loss, a clamped to 0, empty
-pairs, the LDS limit, the final band's clamps, W at its cap, the trim's left edge and negative reverse offset)."""
+pairs, the LDS limit, the final band's clamps, W at its cap, the trim's left edge and negative reverse offset, the vote's ties and
+thresholds, a strand's bound equal to the other's score and at INT32_MAX)."""
 import ctypes as C
 import os
 import subprocess
@@ -154,6 +155,48 @@ def test_orient_class(pr):
     cls = np.where((both == 0) & (fok != 0), 0, np.where((exact != 0) | (both != 0), 1, 2))
     check(got, g, both, cls)
     assert list(got[N:, 2]) == [0, 1, 1, 0, 1, 1, 1, 2]
+
+
+# ---- R10 / R11: the clear vote, strand by certificate ----
+
+def test_clear_vote(pr):
+    """every (vf, vr) of a grid that holds the ties hi == 32, hi == 2 lo and vf == vr, for both strands a sweep can ask about"""
+    v = np.concatenate([np.arange(0, 140), [255, 256, 1000, 2000, 2001, (1 << 31) - 1, 1 << 31, (1 << 32) - 1]])
+    vf, vr, orient = (a.ravel() for a in np.meshgrid(v, v, [0, 1], indexing="ij"))
+    got = call(pr, "pr_clear_vote", [vf, vr, orient], 3)
+    g = np.where(vf >= vr, 0, 1)  # a tie votes forward
+    hi, lo = np.maximum(vf, vr), np.minimum(vf, vr)
+    clear = (hi >= 32) & (hi >= u32(2 * lo))  # (32-bit unsigned arithmetic, as the kernels')
+    check(got, g, clear, clear & (orient != g))
+    at = {(int(a), int(b)): i for i, (a, b, o) in enumerate(zip(vf, vr, orient)) if o == 0}
+    for (a, b), want in {(32, 16): (0, 1), (16, 32): (1, 1), (31, 0): (0, 0), (32, 17): (0, 0), (64, 32): (0, 1), (64, 33): (0, 0),
+                         (40, 40): (0, 0), (0, 0): (0, 0), (33, 16): (0, 1), (32, 0): (0, 1), (0, 32): (1, 1)}.items():
+        assert tuple(got[at[(a, b)], :2]) == want, (a, b)
+
+
+def test_strand_by_bound(pr):
+    """voted forward: bound < S_g; voted reverse: bound <= S_g (gsFwd > gsRev, sage.h:247: the tie goes to reverse); the stored
+    bound is min(prefix + ub, INT32_MAX).  Around bound == S_g for both g, with negative scores, and at the clamp."""
+    rng = np.random.default_rng(12)
+    big = (1 << 31) - 1
+    pre = np.concatenate([rng.integers(-4000, 4000, N), [-1000000, -1, 0, 1, big - 1, big, big, big, -(1 << 31)]])
+    ub = np.concatenate([rng.integers(0, 3000, N), [0, 0, 0, 0, 1, 0, 1, big, big]])
+    n = pre.size
+    cols, want_c, want_b = [], [], []
+    for g in (0, 1):
+        for delta in (-2, -1, 0, 1, 2):  # S_g - bound
+            s_g = pre + ub + delta
+            cols.append([np.full(n, g), pre, ub, s_g])
+            want_c.append(np.full(n, delta > 0 if g == 0 else delta >= 0))
+            want_b.append(np.minimum(pre + ub, big))
+    cols = [np.concatenate([c[j] for c in cols]) for j in range(4)]
+    got = call(pr, "pr_strand_by_bound", cols, 2)
+    check(got, np.concatenate(want_c), np.concatenate(want_b))
+    one = lambda *row: list(call(pr, "pr_strand_by_bound", [[x] for x in row], 2)[0])
+    assert one(0, -50, 10, -40) == [0, -40] and one(1, -50, 10, -40) == [1, -40]  # the tie, negative scores
+    assert one(0, -50, 10, -39) == [1, -40] and one(1, -50, 10, -41) == [0, -40]
+    assert one(0, big, 5, 1 << 40) == [1, big] and one(1, big, 1, big) == [0, big]  # the stored bound is clamped, the comparison is not
+    assert one(1, big, 0, big) == [1, big]
 
 
 # ---- R3 / R4: sub-window and band from a score; LDS fit ----

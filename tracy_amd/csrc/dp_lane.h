@@ -449,14 +449,20 @@ TR_HD void needle_step(NeedleLane<K>& s, int32_t up_s, int32_t diag, int32_t vy,
 }
 
 // ---- orientation vote (pipeline.hip kmer_vote_kernel): shared 11-mers of a trace with its window read forward (vf) and as
-// the reverse complement (vr).  A clear majority marks the other strand as the likely loser: its sweep leaves no
+// the reverse complement (vr).
+// The clear vote (rule R10 of stream_plan.h; it lives here because the sweep kernels read it too): g is the voted strand, forward
+// on a tie; the majority is clear from 32 shared k-mers that are at least twice the other strand's.
+struct ClearVote { uint32_t g; bool clear; };
+TR_HD ClearVote s_clear_vote(uint32_t vf, uint32_t vr) {
+  const uint32_t hi = vf >= vr ? vf : vr, lo = vf >= vr ? vr : vf;
+  return ClearVote{vf >= vr ? 0u : 1u, hi >= 32u && hi >= 2u * lo};
+}
+// A clear majority marks the other strand as the likely loser: its sweep leaves no
 // checkpoints / row-m values behind (nobody will trace back from them).  Only a guess about which work is worth keeping:
 // when the likely loser wins after all, the pipeline sweeps it once more, with checkpoints.
 TR_HD bool vote_skips_checkpoints(uint32_t vf, uint32_t vr, uint32_t orient /*0 forward, 1 reverse*/) {
-  const uint32_t hi = vf >= vr ? vf : vr, lo = vf >= vr ? vr : vf;
-  const bool clear = hi >= 32u && hi >= 2u * lo;
-  const uint32_t likely = vf >= vr ? 0u : 1u;
-  return clear && orient != likely;
+  const ClearVote v = s_clear_vote(vf, vr);
+  return v.clear && orient != v.g;
 }
 
 // ---- geometry shared by the DP kernels and the traceback walker ---------------------------------

@@ -128,7 +128,8 @@ struct OrientRun {
       : ctx(c), p(p_), in(in_), o(o_), force_wide(wide), no_ends(noends), st(c->stream), kn(c->knobs), nt(in_.nt), d_prof(in_.d_prof), mf(in_.mf),
         mt(in_.mt), rn(in_.rn), d_verr(in_.d_verr), h_sc2(o_.sc2), h_fwd(o_.fwd), h_rc(o_.rc) {}
 
-  PairDesc stage1_desc(uint32_t t, int orient) const {  // orient 0 = forward, 1 = reverse complement
+  // trace t against its window read in `orient` (0 = forward, 1 = reverse complement), with that sweep's checkpoints and row m
+  PairDesc pair_desc(uint32_t t, int orient, uint32_t out) const {
     PairDesc d{};
     d.a1_off = in.a1_off[t];
     d.a1_stride = mf[t];
@@ -136,12 +137,13 @@ struct OrientRun {
     d.a2_off = in.a2_off[t];
     d.n = rn[t];
     d.a2_stride = rn[t];
-    d.out = (uint32_t)orient * nt + t;
+    d.out = out;
     d.flags = orient ? PAIR_A2_REVCOMP : 0;
     d.ckpt_off = ck_off[(size_t)orient * nt + t];
     d.lastrow_off = lr_off[(size_t)orient * nt + t];
     return d;
   }
+  PairDesc stage1_desc(uint32_t t, int orient) const { return pair_desc(t, orient, (uint32_t)orient * nt + t); }  // (its slot of d_sc2)
   int run_stage1(std::vector<std::pair<uint32_t, int>> const& what, int stage) {
     DpProblem pb;
     DpProblemLease lease(ctx, pb);
@@ -157,12 +159,98 @@ struct OrientRun {
     }
     return run_dp(ctx, pb, &p, false, false, d_sc2, nullptr, nullptr, nullptr, stage, stage == DP_CKPT ? &ck : nullptr);
   }
-  int fetch_scores() {
-    HIP_TRY(hipMemcpyAsync(h_sc2.data(), d_sc2, sizeof(int32_t) * 2 * (size_t)nt, hipMemcpyDeviceToHost, st));
+  // every wait of the orientation stage on a read-back: the verdict of the reference validation rides with the first one
+  int sync_verdict() {
     if (d_verr && !verr_fetched) HIP_TRY(hipMemcpyAsync(&h_verr, d_verr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx_sync(ctx));
     verr_fetched = true;
     if (h_verr & 4) return set_error(TRACYHIP_ERR_ARG, "reference windows must be upper-case [ACGTN] (loadSingleFasta, fasta.h:54-95)");
+    return TRACYHIP_OK;
+  }
+  int fetch_scores() {
+    HIP_TRY(hipMemcpyAsync(h_sc2.data(), d_sc2, sizeof(int32_t) * 2 * (size_t)nt, hipMemcpyDeviceToHost, st));
+    return sync_verdict();
+  }
+  // sweep these (trace, strand) entries once more in full, with checkpoints, and merge their scores into the host copy (the launch
+  // overwrites d_sc2 at its own entries only)
+  int repeat_full(std::vector<std::pair<uint32_t, int>> const& what) {
+    if (what.empty()) return TRACYHIP_OK;
+    int rc;
+    if ((rc = run_stage1(what, DP_CKPT))) return rc;
+    std::vector<int32_t> got(2 * (size_t)nt);
+    HIP_TRY(hipMemcpyAsync(got.data(), d_sc2, sizeof(int32_t) * 2 * (size_t)nt, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx_sync(ctx));
+    for (auto const& r : what) h_sc2[(size_t)r.second * nt + r.first] = got[(size_t)r.second * nt + r.first];
+    return TRACYHIP_OK;
+  }
+  // Strand by certificate (s_strand_by_bound) for the traces whose other strand holds its prefix maximum (!both): the bound decides
+  // (the entry then holds it), or that strand is swept in full after all.  ub[t]: what the rows below the prefix can add
+  int decide_by_bound(std::vector<int8_t> const& guess, std::vector<int8_t> const& both, const int32_t* ub) {
+    std::vector<std::pair<uint32_t, int>> retry;
+    for (uint32_t t = 0; t < nt; ++t) {
+      if (both[t]) continue;
+      const int g = guess[t];
+      const size_t w = (size_t)g * nt + t, l = (size_t)(1 - g) * nt + t;
+      const SStrand c = s_strand_by_bound((uint32_t)g, h_sc2[l], ub[t], h_sc2[w]);
+      if (c.certified) h_sc2[l] = c.bound;
+      else retry.emplace_back(t, 1 - g);
+    }
+    return repeat_full(retry);
+  }
+
+  // Votes of the two strands from shared k-mers (kmer_vote_kernel) and / or the bound on what the rows below a prefix can add
+  // (rowmax_rest_kernel).  The device block and the pinned block share one layout -- [VoteDesc nt][RowMaxDesc nt][ub nt][votes 2 nt]
+  // [ub1 nt] -- so the descriptors go up in one copy and the results come back in one.  The host pointers point into ctx->h_res and
+  // are good from the wait behind fetch_vote_block until prelim() stages through that block: decide_by_bound reads ub there after
+  // two or three launches, so nothing between vote_block and prelim() may use ctx->h_res (run_dp, run_ckpt_prefix, run_front do not).
+  struct VoteBlock {
+    const uint32_t* votes = nullptr;          // host [2 nt]: vf, vr per trace
+    const int32_t *ub = nullptr, *ub1 = nullptr;  // host [nt]: the bound; the same with the rows clamped at -1 (front.h, second certificate)
+    uint32_t* d_votes = nullptr;              // device: the votes, for the sweeps that read them (DpCkpt::d_votes)
+    void *h_back = nullptr, *d_back = nullptr;  // what fetch_vote_block copies
+    size_t back_bytes = 0;
+  };
+  // the rows whose bound is wanted: none, those below each trace's prefix of kPrefixLanes strips, those below the pruned sweep's kFrontRows
+  enum class Below { none, strip_prefix, front_prefix };
+  int vote_block(bool want_votes, Below below, bool want_ub1, VoteBlock& vb) {
+    const bool want_ub = below != Below::none;
+    const size_t need = (sizeof(VoteDesc) + sizeof(RowMaxDesc) + 4 * sizeof(uint32_t)) * (size_t)nt;
+    HIP_TRY(ctx->d_tmp[7].ensure(need));
+    HIP_TRY(ctx->h_res.ensure(need));
+    struct Lay { VoteDesc* vd; RowMaxDesc* rm; int32_t* ub; uint32_t* votes; int32_t* ub1; };
+    auto lay = [&](void* base) {
+      Lay l;
+      l.vd = static_cast<VoteDesc*>(base);
+      l.rm = reinterpret_cast<RowMaxDesc*>(l.vd + nt);
+      l.ub = reinterpret_cast<int32_t*>(l.rm + nt);
+      l.votes = reinterpret_cast<uint32_t*>(l.ub + nt);
+      l.ub1 = reinterpret_cast<int32_t*>(l.votes + 2 * (size_t)nt);
+      return l;
+    };
+    const Lay d = lay(ctx->d_tmp[7].p), h = lay(ctx->h_res.p);
+    parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
+      for (uint32_t t = lo; t < hi; ++t) {
+        if (want_votes) h.vd[t] = VoteDesc{in.a1_off[t], in.a2_off[t], mf[t], mt[t], rn[t], 0u};
+        if (want_ub) h.rm[t] = RowMaxDesc{in.a1_off[t], mf[t], mt[t], below == Below::front_prefix ? kFrontRows : (uint32_t)kPrefixLanes * choose_k(mt[t], MODE_QP)};
+      }
+    });
+    const size_t up_bytes = ((want_votes ? sizeof(VoteDesc) : 0) + (want_ub ? sizeof(RowMaxDesc) : 0)) * (size_t)nt;
+    HIP_TRY(hipMemcpyAsync(want_votes ? (void*)d.vd : (void*)d.rm, want_votes ? (void*)h.vd : (void*)h.rm, up_bytes, hipMemcpyHostToDevice, st));
+    if (want_votes) hipLaunchKernelGGL(kmer_vote_kernel, dim3(nt), dim3(64), 0, st, d.vd, static_cast<const float*>(d_prof), ctx->codes(), d.votes);
+    if (want_ub)
+      hipLaunchKernelGGL(rowmax_rest_kernel, dim3(nt), dim3(64), 0, st, d.rm, static_cast<const float*>(d_prof), (float)p.match, (float)p.mismatch, d.ub,
+                         want_ub1 ? d.ub1 : (int32_t*)nullptr);
+    HIP_TRY(hipGetLastError());
+    vb.votes = h.votes; vb.ub = h.ub; vb.ub1 = h.ub1; vb.d_votes = d.votes;
+    uint32_t* const h_lo = want_ub ? reinterpret_cast<uint32_t*>(h.ub) : h.votes;
+    uint32_t* const h_hi = want_ub1 ? reinterpret_cast<uint32_t*>(h.ub1) + nt : want_votes ? h.votes + 2 * (size_t)nt : h.votes;
+    vb.h_back = h_lo;
+    vb.d_back = want_ub ? (void*)d.ub : (void*)d.votes;
+    vb.back_bytes = sizeof(uint32_t) * (size_t)(h_hi - h_lo);
+    return TRACYHIP_OK;
+  }
+  int fetch_vote_block(const VoteBlock& vb) {  // queues the read-back; the caller's next wait (sync_verdict, fetch_scores) delivers it
+    HIP_TRY(hipMemcpyAsync(vb.h_back, vb.d_back, vb.back_bytes, hipMemcpyDeviceToHost, st));
     return TRACYHIP_OK;
   }
 
@@ -279,37 +367,10 @@ struct OrientRun {
     int rc;
     sco.mark("o.a votes+rowmax descs/launch/readback");
     const uint32_t R = kFrontRows;  // every prefix of this branch has the 16 x 8 shape
-    const size_t need = (sizeof(VoteDesc) + sizeof(RowMaxDesc) + 4 * sizeof(uint32_t)) * (size_t)nt;
-    HIP_TRY(ctx->d_tmp[7].ensure(need));
-    VoteDesc* d_vd = static_cast<VoteDesc*>(ctx->d_tmp[7].p);
-    RowMaxDesc* d_rm = reinterpret_cast<RowMaxDesc*>(d_vd + nt);
-    int32_t* d_ub = reinterpret_cast<int32_t*>(d_rm + nt);
-    uint32_t* d_votes = reinterpret_cast<uint32_t*>(d_ub + nt);
-    int32_t* d_ub1 = reinterpret_cast<int32_t*>(d_votes + 2 * (size_t)nt);  // rows clamped at -1 (front.h, second certificate)
-    // both descriptor lists in one pinned block (laid out like the device block: one copy), the bounds and the votes back in one
-    HIP_TRY(ctx->h_res.ensure(need));
-    VoteDesc* hv = static_cast<VoteDesc*>(ctx->h_res.p);
-    RowMaxDesc* hrm = reinterpret_cast<RowMaxDesc*>(hv + nt);
-    parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
-      for (uint32_t t = lo; t < hi; ++t) {
-        hv[t] = VoteDesc{in.a1_off[t], in.a2_off[t], mf[t], mt[t], rn[t], 0u};
-        hrm[t] = RowMaxDesc{in.a1_off[t], mf[t], mt[t], R};
-      }
-    });
-    HIP_TRY(hipMemcpyAsync(d_vd, hv, (sizeof(VoteDesc) + sizeof(RowMaxDesc)) * (size_t)nt, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(kmer_vote_kernel, dim3(nt), dim3(64), 0, st, d_vd, static_cast<const float*>(d_prof), ctx->codes(), d_votes);
-    hipLaunchKernelGGL(rowmax_rest_kernel, dim3(nt), dim3(64), 0, st, d_rm, static_cast<const float*>(d_prof), (float)p.match, (float)p.mismatch, d_ub, d_ub1);
-    HIP_TRY(hipGetLastError());
-    const int32_t* h_ub = reinterpret_cast<const int32_t*>(hrm + nt);  // (the tail of the pinned block: [bounds nt][votes 2 nt][bounds, rows clamped at -1, nt])
-    const uint32_t* h_votes = reinterpret_cast<const uint32_t*>(h_ub + nt);
-    const int32_t* h_ub1 = reinterpret_cast<const int32_t*>(h_votes + 2 * (size_t)nt);
-    HIP_TRY(hipMemcpyAsync(const_cast<int32_t*>(h_ub), d_ub, sizeof(uint32_t) * 4 * (size_t)nt, hipMemcpyDeviceToHost, st));
-    if (d_verr && !verr_fetched) HIP_TRY(hipMemcpyAsync(&h_verr, d_verr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx_sync(ctx));
-    if (d_verr) {
-      verr_fetched = true;
-      if (h_verr & 4) return set_error(TRACYHIP_ERR_ARG, "reference windows must be upper-case [ACGTN] (loadSingleFasta, fasta.h:54-95)");
-    }
+    VoteBlock vb;
+    if ((rc = vote_block(true, Below::front_prefix, true, vb)) || (rc = fetch_vote_block(vb)) || (rc = sync_verdict())) return rc;
+    const uint32_t* h_votes = vb.votes;
+    const int32_t *h_ub = vb.ub, *h_ub1 = vb.ub1;  // (ub1: rows clamped at -1, front.h's second certificate)
     sco.mark("o.b build front descs");
     // the lists of the combined launch, laid out by a few threads in trace order (class per trace, a scan, the fill); the vectors
     // are the context's (megabytes per call: no fresh pages)
@@ -390,17 +451,6 @@ struct OrientRun {
     if ((rc = run_front(ctx, fd, in.d_qp, reinterpret_cast<const uint32_t*>(ck.d_lastrow), &p, fres))) return rc;
     sco.mark("o.e fetch+merge");
     if ((rc = fetch_scores())) return rc;
-    // merge the scores of a repeat launch (which overwrites d_sc2 at the repeated entries only) into the host copy
-    auto repeat_full = [&](std::vector<std::pair<uint32_t, int>> const& what) -> int {
-      if (what.empty()) return TRACYHIP_OK;
-      int rr;
-      if ((rr = run_stage1(what, DP_CKPT))) return rr;
-      std::vector<int32_t> got(2 * (size_t)nt);
-      HIP_TRY(hipMemcpyAsync(got.data(), d_sc2, sizeof(int32_t) * 2 * (size_t)nt, hipMemcpyDeviceToHost, st));
-      HIP_TRY(ctx_sync(ctx));
-      for (auto const& r : what) h_sc2[(size_t)r.second * nt + r.first] = got[(size_t)r.second * nt + r.first];
-      return TRACYHIP_OK;
-    };
     std::vector<std::pair<uint32_t, int>> retry;
     for (size_t i = 0; i < ft.size(); ++i) {
       const uint32_t t = ft[i];
@@ -416,60 +466,22 @@ struct OrientRun {
     ctx->stats.pruned += (uint32_t)ft.size(); ctx->stats.pruned_uncertified += (uint32_t)retry.size();
     if (ctx->knobs.verbose) fprintf(stderr, "pruned orientation sweep: %zu of %u traces, %zu not certified\n", ft.size(), nt, retry.size());
     if ((rc = repeat_full(retry))) return rc;
-    if (!in.exact) {  // the other strand of a clear vote holds its prefix maximum: decided by its bound, or swept in full
-      retry.clear();
-      for (uint32_t t = 0; t < nt; ++t) {
-        if (both[t]) continue;
-        const size_t w = (size_t)guess[t] * nt + t, l = (size_t)(1 - guess[t]) * nt + t;
-        const int64_t bound_l = (int64_t)h_sc2[l] + h_ub[t];
-        const bool certified = guess[t] == 0 ? bound_l < (int64_t)h_sc2[w] : bound_l <= (int64_t)h_sc2[w];
-        if (certified) h_sc2[l] = (int32_t)std::min<int64_t>(bound_l, 0x7fffffff);
-        else retry.emplace_back(t, 1 - guess[t]);
-      }
-      if ((rc = repeat_full(retry))) return rc;
-    }
-    return TRACYHIP_OK;
+    return in.exact ? TRACYHIP_OK : decide_by_bound(guess, both, h_ub);
   }
 
   // the strand voted from shared k-mers swept in full, prefix bounds of the other strand in the same launch
   int orient_vote() {
     int rc;
-    std::vector<VoteDesc> hv(nt);
-    std::vector<RowMaxDesc> hrm(nt);
-    for (uint32_t t = 0; t < nt; ++t) {
-      hv[t] = VoteDesc{in.a1_off[t], in.a2_off[t], mf[t], mt[t], rn[t], 0u};
-      hrm[t] = RowMaxDesc{in.a1_off[t], mf[t], mt[t], (uint32_t)kPrefixLanes * K0};
-    }
-    const size_t need = (sizeof(VoteDesc) + sizeof(RowMaxDesc) + 3 * sizeof(uint32_t)) * (size_t)nt;
-    HIP_TRY(ctx->d_tmp[7].ensure(need));
-    VoteDesc* d_vd = static_cast<VoteDesc*>(ctx->d_tmp[7].p);
-    RowMaxDesc* d_rm = reinterpret_cast<RowMaxDesc*>(d_vd + nt);
-    int32_t* d_ub = reinterpret_cast<int32_t*>(d_rm + nt);
-    uint32_t* d_votes = reinterpret_cast<uint32_t*>(d_ub + nt);
-    HIP_TRY(hipMemcpyAsync(d_vd, hv.data(), sizeof(VoteDesc) * (size_t)nt, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_rm, hrm.data(), sizeof(RowMaxDesc) * (size_t)nt, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(kmer_vote_kernel, dim3(nt), dim3(64), 0, st, d_vd, static_cast<const float*>(d_prof), ctx->codes(), d_votes);
-    hipLaunchKernelGGL(rowmax_rest_kernel, dim3(nt), dim3(64), 0, st, d_rm, static_cast<const float*>(d_prof), (float)p.match, (float)p.mismatch, d_ub);
-    HIP_TRY(hipGetLastError());
-    std::vector<int32_t> h_ub(nt);
-    std::vector<uint32_t> h_votes(2 * (size_t)nt);
-    HIP_TRY(hipMemcpyAsync(h_ub.data(), d_ub, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_votes.data(), d_votes, sizeof(uint32_t) * 2 * (size_t)nt, hipMemcpyDeviceToHost, st));
-    if (d_verr && !verr_fetched) HIP_TRY(hipMemcpyAsync(&h_verr, d_verr, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx_sync(ctx));
-    if (d_verr) {
-      verr_fetched = true;
-      if (h_verr & 4) return set_error(TRACYHIP_ERR_ARG, "reference windows must be upper-case [ACGTN] (loadSingleFasta, fasta.h:54-95)");
-    }
+    VoteBlock vb;
+    if ((rc = vote_block(true, Below::strip_prefix, false, vb)) || (rc = fetch_vote_block(vb)) || (rc = sync_verdict())) return rc;
     std::vector<int8_t> guess(nt, 0), both(nt, 1);
     std::vector<PairDesc> fullv, prev;
     fullv.reserve(nt + nt / 8);
     prev.reserve(nt);
     for (uint32_t t = 0; t < nt; ++t) {
-      const uint32_t vf = h_votes[2 * t], vr = h_votes[2 * t + 1];
-      guess[t] = vf >= vr ? 0 : 1;
-      const uint32_t hi = vf >= vr ? vf : vr, lo = vf >= vr ? vr : vf;
-      both[t] = (elig[t] && hi >= 32 && hi >= 2 * lo) ? 0 : 1;  // a clear majority of shared k-mers, or both sweeps
+      const ClearVote v = s_clear_vote(vb.votes[2 * t], vb.votes[2 * t + 1]);
+      guess[t] = (int8_t)v.g;
+      both[t] = (elig[t] && v.clear) ? 0 : 1;  // a clear majority of shared k-mers (and rows below the prefix of the batch's strip height), or both sweeps
       fullv.push_back(stage1_desc(t, (int)guess[t]));
       if (both[t]) fullv.push_back(stage1_desc(t, 1 - guess[t]));
       else prev.push_back(stage1_desc(t, 1 - guess[t]));
@@ -477,25 +489,7 @@ struct OrientRun {
     DpCkpt ckv = ck;
     if ((rc = run_ckpt_prefix(ctx, d_prof, ctx->codes(), fullv, std::vector<int>(fullv.size(), K0), prev, &p, d_sc2, &ckv, false))) return rc;
     if ((rc = fetch_scores())) return rc;
-    std::vector<std::pair<uint32_t, int>> retry;
-    for (uint32_t t = 0; t < nt; ++t) {
-      if (both[t]) continue;
-      const size_t w = (size_t)guess[t] * nt + t, l = (size_t)(1 - guess[t]) * nt + t;
-      const int64_t bound_l = (int64_t)h_sc2[l] + h_ub[t];
-      const bool certified = guess[t] == 0 ? bound_l < (int64_t)h_sc2[w] : bound_l <= (int64_t)h_sc2[w];
-      if (certified) h_sc2[l] = (int32_t)std::min<int64_t>(bound_l, 0x7fffffff);
-      else retry.emplace_back(t, 1 - guess[t]);
-    }
-    if (!retry.empty()) {
-      std::vector<int32_t> keep = h_sc2;
-      if ((rc = run_stage1(retry, DP_CKPT))) return rc;
-      std::vector<int32_t> got(2 * (size_t)nt);
-      HIP_TRY(hipMemcpyAsync(got.data(), d_sc2, sizeof(int32_t) * 2 * (size_t)nt, hipMemcpyDeviceToHost, st));
-      HIP_TRY(ctx_sync(ctx));
-      h_sc2 = keep;
-      for (auto const& r : retry) h_sc2[(size_t)r.second * nt + r.first] = got[(size_t)r.second * nt + r.first];
-    }
-    return TRACYHIP_OK;
+    return decide_by_bound(guess, both, vb.ub);
   }
 
   // the two-stage form: prefix bounds of both strands, then the likely winner (no_vote)
@@ -506,26 +500,14 @@ struct OrientRun {
       for (uint32_t t = 0; t < nt; ++t)
         if (elig[t]) all2.emplace_back(t, o);
     if ((rc = run_stage1(all2, DP_PREFIX))) return rc;
-    std::vector<RowMaxDesc> hrm(nt);
-    for (uint32_t t = 0; t < nt; ++t)
-      hrm[t] = RowMaxDesc{in.a1_off[t], mf[t], mt[t], (uint32_t)kPrefixLanes * choose_k(mt[t], MODE_QP)};
-    HIP_TRY(ctx->d_tmp[7].ensure(sizeof(RowMaxDesc) * (size_t)nt + sizeof(int32_t) * (size_t)nt));
-    RowMaxDesc* d_rm = static_cast<RowMaxDesc*>(ctx->d_tmp[7].p);
-    int32_t* d_ub = reinterpret_cast<int32_t*>(d_rm + nt);
-    HIP_TRY(hipMemcpyAsync(d_rm, hrm.data(), sizeof(RowMaxDesc) * (size_t)nt, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(rowmax_rest_kernel, dim3(nt), dim3(64), 0, st, d_rm, static_cast<const float*>(d_prof), (float)p.match, (float)p.mismatch, d_ub);
-    HIP_TRY(hipGetLastError());
-    std::vector<int32_t> h_ub(nt);
-    HIP_TRY(hipMemcpyAsync(h_ub.data(), d_ub, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-    if ((rc = fetch_scores())) return rc;
-    std::vector<int64_t> bound(2 * (size_t)nt);
-    for (uint32_t t = 0; t < nt; ++t)
-      for (int o = 0; o < 2; ++o) bound[(size_t)o * nt + t] = (int64_t)h_sc2[(size_t)o * nt + t] + h_ub[t];
-    // full passes: the likely winner of every trace; both orientations where the bounds are within 10 % of each other
+    VoteBlock vb;
+    if ((rc = vote_block(false, Below::strip_prefix, false, vb)) || (rc = fetch_vote_block(vb)) || (rc = fetch_scores())) return rc;
+    // full passes: the likely winner of every trace; both orientations where the bounds are within 10 % of each other (a launch
+    // heuristic: which sweeps are worth queueing at once.  What a bound decides is decide_by_bound's)
     std::vector<std::pair<uint32_t, int>> full;
     std::vector<int8_t> guess(nt), both(nt, 0);
     for (uint32_t t = 0; t < nt; ++t) {
-      const int64_t bf = bound[t], br = bound[nt + t];
+      const int64_t bf = (int64_t)h_sc2[t] + vb.ub[t], br = (int64_t)h_sc2[nt + t] + vb.ub[t];
       guess[t] = bf >= br ? 0 : 1;
       const int64_t bw = guess[t] ? br : bf, bl = guess[t] ? bf : br;
       both[t] = (!elig[t] || bw <= 0 || bl * 10 > bw * 9) ? 1 : 0;
@@ -533,29 +515,8 @@ struct OrientRun {
       if (both[t]) full.emplace_back(t, 1 - guess[t]);
     }
     if ((rc = run_stage1(full, DP_CKPT))) return rc;
-    std::vector<int32_t> pref = h_sc2;
-    if ((rc = fetch_scores())) return rc;
-    std::vector<std::pair<uint32_t, int>> retry;
-    for (uint32_t t = 0; t < nt; ++t) {
-      if (both[t]) continue;
-      const size_t w = (size_t)guess[t] * nt + t, l = (size_t)(1 - guess[t]) * nt + t;
-      // guess forward: forward iff gsFwd > gsRev, certified by bound(rev) < gsFwd; guess reverse: certified by bound(fwd) <= gsRev
-      const bool certified = guess[t] == 0 ? bound[l] < (int64_t)h_sc2[w] : bound[l] <= (int64_t)h_sc2[w];
-      if (certified) h_sc2[l] = (int32_t)std::min<int64_t>(bound[l], 0x7fffffff);
-      else retry.emplace_back(t, 1 - guess[t]);
-    }
-    if (!retry.empty()) {
-      std::vector<int32_t> keep = h_sc2;
-      // d_sc2 is overwritten only at the retried entries; merge them into the host copy
-      if ((rc = run_stage1(retry, DP_CKPT))) return rc;
-      std::vector<int32_t> got(2 * (size_t)nt);
-      HIP_TRY(hipMemcpyAsync(got.data(), d_sc2, sizeof(int32_t) * 2 * (size_t)nt, hipMemcpyDeviceToHost, st));
-      HIP_TRY(ctx_sync(ctx));
-      h_sc2 = keep;
-      for (auto const& r : retry) h_sc2[(size_t)r.second * nt + r.first] = got[(size_t)r.second * nt + r.first];
-    }
-    (void)pref;
-    return TRACYHIP_OK;
+    if ((rc = fetch_scores())) return rc;  // (the strand not swept still holds its prefix maximum: a launch writes its own entries only)
+    return decide_by_bound(guess, both, vb.ub);
   }
 
   // both orientations swept in full (exact gsFwd / gsRev), or the one the caller gave
@@ -570,31 +531,21 @@ struct OrientRun {
     // (Also on the ends path, where only row m is kept: the sweep of the likely loser is 2 % faster without its row-m stores,
     // which is more than the vote costs.)
     const bool vote_ckpt = !given && use_band && ck.narrow && !kn.no_vote;
-    std::vector<uint32_t> h_votes;
+    VoteBlock vb;
     if (vote_ckpt) {
-      std::vector<VoteDesc> hv(nt);
-      for (uint32_t t = 0; t < nt; ++t) hv[t] = VoteDesc{in.a1_off[t], in.a2_off[t], mf[t], mt[t], rn[t], 0u};
-      HIP_TRY(ctx->d_tmp[7].ensure((sizeof(VoteDesc) + 2 * sizeof(uint32_t)) * (size_t)nt));
-      VoteDesc* d_vd = static_cast<VoteDesc*>(ctx->d_tmp[7].p);
-      uint32_t* d_votes = reinterpret_cast<uint32_t*>(d_vd + nt);
-      HIP_TRY(ctx->h_res.ensure(sizeof(VoteDesc) * (size_t)nt));  // pinned staging (free until the results go out): no host wait
-      std::memcpy(ctx->h_res.p, hv.data(), sizeof(VoteDesc) * (size_t)nt);
-      HIP_TRY(hipMemcpyAsync(d_vd, ctx->h_res.p, sizeof(VoteDesc) * (size_t)nt, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(kmer_vote_kernel, dim3(nt), dim3(64), 0, st, d_vd, static_cast<const float*>(d_prof), ctx->codes(), d_votes);
-      HIP_TRY(hipGetLastError());
-      ck.d_votes = d_votes;
+      if ((rc = vote_block(true, Below::none, false, vb))) return rc;
+      ck.d_votes = vb.d_votes;
       ck.vote_nt = nt;
-      h_votes.resize(2 * (size_t)nt);
     }
     if ((rc = run_stage1(all, use_band ? DP_CKPT : DP_PLAIN))) return rc;
-    if (vote_ckpt) HIP_TRY(hipMemcpyAsync(h_votes.data(), ck.d_votes, sizeof(uint32_t) * 2 * (size_t)nt, hipMemcpyDeviceToHost, st));
+    if (vote_ckpt && (rc = fetch_vote_block(vb))) return rc;  // (behind the sweeps: nothing waited for the votes before they were queued)
     ck.d_votes = nullptr;
     if ((rc = fetch_scores())) return rc;
     if (vote_ckpt) {
       std::vector<std::pair<uint32_t, int>> retry;
       for (uint32_t t = 0; t < nt; ++t) {
         const int w = h_sc2[t] > h_sc2[nt + t] ? 0 : 1;  // forward iff gsFwd > gsRev (sage.h:247)
-        if (vote_skips_checkpoints(h_votes[2 * t], h_votes[2 * t + 1], (uint32_t)w)) retry.emplace_back(t, w);
+        if (vote_skips_checkpoints(vb.votes[2 * t], vb.votes[2 * t + 1], (uint32_t)w)) retry.emplace_back(t, w);
       }
       if (!retry.empty() && (rc = run_stage1(retry, DP_CKPT))) return rc;  // same scores, now with checkpoints
     }
@@ -625,20 +576,8 @@ struct OrientRun {
       pb.k.resize(nt);
       parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
         for (uint32_t t = lo; t < hi; ++t) {
-          PairDesc d{};
-          d.a1_off = in.a1_off[t];
-          d.a1_stride = mf[t];
-          d.m = mt[t];
-          d.a2_off = in.a2_off[t];
-          d.n = rn[t];
-          d.a2_stride = rn[t];
-          d.out = t;
-          d.flags = h_rc[t] ? PAIR_A2_REVCOMP : 0;
-          const size_t o = h_rc[t] ? (size_t)nt + t : t;  // the winning orientation's checkpoints
-          d.ckpt_off = ck_off[o];
-          d.lastrow_off = lr_off[o];
-          pb.desc[t] = d;
-          pb.k[t] = choose_k(d.m, MODE_QP);
+          pb.desc[t] = pair_desc(t, h_rc[t] ? 1 : 0, t);  // the winning orientation, its checkpoints
+          pb.k[t] = choose_k(mt[t], MODE_QP);
         }
       });
       if (ends_path || tb16_path) {

@@ -220,10 +220,9 @@ __global__ void s_orient_decide_kernel(SParams p, const SGeom* __restrict__ geom
   uint32_t dd = 0;
   int64_t s_g = 0, s_o = 0;
   uint32_t fce = 0;
-  auto by_bound = [&]() {  // the other strand holds its prefix maximum: decided by its bound, or its full sweep is needed
-    const int64_t bound_l = (int64_t)sc2[o * nt + t] + ub[t];
-    const bool certified = g == 0u ? bound_l < s_g : bound_l <= s_g;
-    if (certified) s_o = bound_l < 0x7fffffffLL ? bound_l : 0x7fffffffLL;
+  auto by_bound = [&]() {  // the other strand holds its prefix maximum: decided by its bound (s_strand_by_bound), or its full sweep is needed
+    const SStrand c = s_strand_by_bound(g, sc2[o * nt + t], ub[t], s_g);
+    if (c.certified) s_o = c.bound;
     else dd |= SD_STRAND;
   };
   if (S.cls == 0u) {

@@ -1,10 +1,11 @@
 // stream_plan.h -- what the stream-ordered pipelines (stream.hip) keep on the device between two launches, and the per-trace planning
-// rules of both pipelines: which strand to prune, which band an alignment's score allows, whether a band fits the band kernels,
-// whether a certificate held, trimReferenceSlice's last step.  Each rule is written once here, as a TR_HD function: the planning
-// kernels of stream.hip (one thread per trace) and the host-planned tiers of pipeline.hip call the same ones, so that a trace takes
-// the same tier on either path -- and a trace whose tier the device cannot give it (a failed certificate, a band wider than the band
-// kernels hold) is marked `dead` and handed to the host-planned tiers afterwards.  Where the two planners differ on purpose, the
-// difference is an argument.  The header compiles for the host alone (tests/cpp/plan_rules.cpp).
+// rules of both pipelines: which strand the k-mers vote for (R10, in dp_lane.h, where the sweep kernels see it too), which strand to
+// prune (R1, R2), whether a strand's bound decides it (R11), which band an alignment's score allows (R3, R5, R7, R8), whether a band
+// fits the band kernels (R4), whether a certificate held (R6), trimReferenceSlice's last step (R9).  Each rule is written once, as a
+// TR_HD function: the planning kernels of stream.hip (one thread per trace) and the host-planned tiers of pipeline.hip call the same
+// ones, so that a trace takes the same tier on either path -- and a trace whose tier the device cannot give it (a failed
+// certificate, a band wider than the band kernels hold) is marked `dead` and handed to the host-planned tiers afterwards.  Where the
+// two planners differ on purpose, the difference is an argument.  The header compiles for the host alone (tests/cpp/plan_rules.cpp).
 #ifndef TRACY_AMD_STREAM_PLAN_H
 #define TRACY_AMD_STREAM_PLAN_H
 
@@ -153,15 +154,27 @@ TR_HD bool s_front_ok(const tracyhip_params* prm, uint32_t m, uint32_t n) {
 
 // R1. class of a trace from its k-mer votes vf / vr for the two strands.  g: the voted strand.  both: no clear majority of shared k-mers
 // (or no rows below the prefix), both strands are swept.  cls 0: pruned sweep of g (front_ok: R2); 1: both strands in full (`exact`:
-// both scores are needed exactly); 2: g in full + the prefix of the other (strand by certificate)
+// both scores are needed exactly); 2: g in full + the prefix of the other (strand by certificate: R11).  The vote itself is R10
+// (s_clear_vote, dp_lane.h).  What makes a trace eligible beside it differs on purpose and stays with the caller: here rows below the
+// pruned sweep's prefix (m > kFrontRows); in pipeline.hip's orient_vote rows below the prefix of the batch's strip height (its elig[t]).
 struct SOrient { uint32_t g, both, cls; };
 TR_HD SOrient s_orient_class(uint32_t vf, uint32_t vr, uint32_t m, bool front_ok, bool exact) {
+  const ClearVote v = s_clear_vote(vf, vr);
   SOrient o;
-  o.g = vf >= vr ? 0u : 1u;
-  const uint32_t hi_v = vf >= vr ? vf : vr, lo_v = vf >= vr ? vr : vf;
-  o.both = (m > kFrontRows && hi_v >= 32u && hi_v >= 2u * lo_v) ? 0u : 1u;
+  o.g = v.g;
+  o.both = (m > kFrontRows && v.clear) ? 0u : 1u;
   o.cls = (!o.both && front_ok) ? 0u : (exact || o.both) ? 1u : 2u;
   return o;
+}
+
+// R11. strand by certificate.  The voted strand g has its exact score S_g; the other strand has only the maximum of its prefix rows,
+// and the rows below them add at most ub: its score is at most bound = prefix + ub.  The reference decides forward iff gsFwd > gsRev
+// (sage.h:247), so a voted forward strand needs bound < S_g and a voted reverse strand bound <= S_g: the tie goes to reverse either way.
+// A certified loser's score array holds the bound (at most INT32_MAX); without the certificate its full sweep is needed.
+struct SStrand { bool certified; int32_t bound; };
+TR_HD SStrand s_strand_by_bound(uint32_t g, int32_t prefix, int32_t ub, int64_t s_g) {
+  const int64_t b = (int64_t)prefix + ub;
+  return SStrand{g == 0u ? b < s_g : b <= s_g, (int32_t)(b < 0x7fffffffLL ? b : 0x7fffffffLL)};
 }
 
 // diagonals [dlo, dhi] of a band and the strip height that sweeps it (b16_pick_k; 0: too wide)
