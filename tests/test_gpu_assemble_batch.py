@@ -1,0 +1,339 @@
+"""tracyhip_assemble_traces (the reference-guided chain of `tracy assemble -r` for a batch of trace groups) against the chain of
+tests/assemble_oracle.py::assemble_ref_guided restated over profiles (pyoracle / msa_oracle), every group and every field, and
+`tracy_amd_cli assemble -r --batch` against the one-group command, byte by byte."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLI = os.path.join(ROOT, "tracy_amd", "bin", "tracy_amd_cli")
+SCORE = (3, -5, -10, -4)
+FRACMATCH, CALLED = 0.5, 0.1
+KS = (1, 2, 3, 5, 8)
+
+
+def column_profile(rng, seq, noise=0.06):
+    """a trace-like profile of a base string (test_gpu_consensus_batch.py::column_profile): the called base carries most of each
+    column, rows 4 (N) and 5 (gap) are zero"""
+    n = len(seq)
+    p = np.zeros((6, n), np.float32)
+    w = rng.random((4, n), dtype=np.float32) * noise
+    idx = np.array([b"ACGT".index(c) for c in seq])
+    w[idx, np.arange(n)] += rng.uniform(0.75, 1.0, n).astype(np.float32)
+    p[:4] = w / w.sum(0, keepdims=True)
+    return p
+
+
+def bases(rng, n):
+    return bytes(rng.choice(list(b"ACGT"), size=n).tolist())
+
+
+def mutate(rng, seq, rate):
+    s = bytearray(seq)
+    for k in range(len(s)):
+        if rng.random() < rate:
+            s[k] = int(rng.choice(list(b"ACGT")))
+    return bytes(s)
+
+
+def make_groups(seed=4242, ngroups=40):
+    """groups of K in {1, 2, 3, 5, 8} traces (1 .. 300 columns) over references of 50 .. 600 columns; the kinds the test asserts on
+    the oracle's results are built in by construction"""
+    import pyoracle as orc
+    rng = np.random.default_rng(seed)
+    groups, refs, kinds = [], [], []
+    for g in range(ngroups):
+        kind = ("plain", "excluded", "single", "tie", "insertion", "cross64", "cross256", "onecol")[g % 8]
+        K = KS[g % len(KS)]
+        nref = int(rng.integers(50, 601))
+        if kind == "cross64":
+            nref, K = 60, max(K, 2)
+        elif kind == "cross256":
+            nref, K = 250, max(K, 3)
+        elif kind in ("tie", "insertion"):
+            K = max(K, 3)
+        elif kind == "single":
+            K = min(K, 2)
+        region = bases(rng, nref)
+        traces = []
+        for i in range(K):
+            ln = int(rng.integers(20, min(nref, 300) + 1))
+            st = int(rng.integers(0, nref - ln + 1))
+            seq = mutate(rng, region[st:st + ln], 0.03)
+            if kind == "excluded" or (kind == "single" and i == 1):
+                seq = bases(rng, int(rng.integers(100, 301)))  # unrelated
+            elif kind == "tie" and i == 2:
+                traces.append(traces[0].copy())  # the same trace twice: equal scores, the input index orders them
+                continue
+            elif kind in ("insertion", "cross64", "cross256") and i >= 1:
+                # a later (shorter, so lower-scoring) trace carrying bases the reference lacks
+                ln = int(rng.integers(40, min(nref, 200) + 1))  # (flanks long enough that the gap beats a shifted half)
+                st = int(rng.integers(0, nref - ln + 1))
+                seq = region[st:st + ln]
+                at = ln // 2
+                seq = seq[:at] + bases(rng, 8 if kind != "cross256" else 10) + seq[at:]
+            elif kind == "onecol" and i == 0:
+                seq = region[nref // 2:nref // 2 + 1]
+            p = column_profile(rng, seq)
+            if (g + i) % 3 == 1:  # read from the other strand
+                p = np.ascontiguousarray(orc.revcomp_profile(p))
+            traces.append(p)
+        if kind in ("insertion", "cross64", "cross256"):  # the best trace: the whole region, so that the inserted ones come later
+            traces[0] = column_profile(rng, region[:min(nref, 300)])
+        groups.append(traces)
+        refs.append(orc.create_profile_str(region))
+        kinds.append(kind)
+    return groups, refs, kinds
+
+
+def oracle_group(traces, pref, score, fracmatch, called, incref):
+    """assemble_oracle.assemble_ref_guided from the profiles on"""
+    import assemble_oracle as ao
+    import msa_oracle as mo
+    import pyoracle as orc
+    f32 = np.float32
+    res = dict(score_fwd=[], score_rev=[], forward=[], rank=[0xffffffff] * len(traces), steps=[])
+    profiles, score_idx = [], []
+    for i, p in enumerate(traces):
+        rev = np.ascontiguousarray(orc.revcomp_profile(p))
+        gf = orc.gotoh_score_prof(p, pref, 1, 0, score)
+        gr = orc.gotoh_score_prof(rev, pref, 1, 0, score)
+        res["score_fwd"].append(gf)
+        res["score_rev"].append(gr)
+        res["forward"].append(int(gf >= gr))
+        size = float(p.shape[1])
+        thr = size * float(f32(fracmatch)) * score[0] + size * float(f32(1) - f32(fracmatch)) * score[1]
+        if gf > thr or gr > thr:
+            score_idx.append(dict(score=max(gf, gr), idx=i, newidx=len(score_idx)))
+            profiles.append(p if gf >= gr else rev)
+    score_idx.sort(key=lambda s: (-s["score"], s["idx"]))
+    for k, s in enumerate(score_idx):
+        res["rank"][s["idx"]] = k
+    res["order"] = score_idx
+    if not score_idx:
+        res.update(nrows=0, ncol=0, rows=[], gapped=b"", cons=b"", qual=b"")
+        return res
+    p0 = profiles[score_idx[0]["newidx"]]
+    _, btr = orc.gotoh_prof(p0, pref, 1, 0, score)
+    r0, r1, ops = ao.rows_of(p0, pref, btr)
+    align = [r0, r1]
+    res["steps"].append((ops, len(r0)))
+    for s in score_idx[1:]:
+        ap = np.ascontiguousarray(mo.profile_of_alignment(align))
+        pn = profiles[s["newidx"]]
+        _, btr = orc.gotoh_prof(pn, ap, 1, 0, score)
+        new0, _, ops = ao.rows_of(pn, ap, btr)
+        comb = [list(new0)] + [[] for _ in align]
+        a = 0
+        for op in ops:
+            for k in range(len(align)):
+                comb[k + 1].append(align[k][a] if op != "v" else "-")
+            a += op != "v"
+        align = ["".join(r) for r in comb]
+        res["steps"].append((ops, len(align[0])))
+    gapped, cs, qs = mo.consensus(align, called, not incref)
+    res.update(nrows=len(align), ncol=len(align[0]), rows=[r.encode() for r in align], gapped=gapped.encode(), cons=cs.encode(), qual=qs.encode())
+    return res
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import tracy_amd
+    c = tracy_amd.Context(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def batch():
+    groups, refs, kinds = make_groups()
+    want = {inc: [oracle_group(t, r, SCORE, FRACMATCH, CALLED, inc) for t, r in zip(groups, refs)] for inc in (False, True)}
+    return groups, refs, kinds, want
+
+
+def check(got, want, groups):
+    t = 0
+    for g, w in enumerate(want):
+        for i in range(len(groups[g])):
+            for k in ("score_fwd", "score_rev", "forward", "rank"):
+                assert int(got[k][t]) == int(w[k][i]), (g, i, k, int(got[k][t]), w[k][i])
+            t += 1
+        assert int(got["nrows"][g]) == w["nrows"], g
+        assert int(got["ncol"][g]) == w["ncol"], g
+        assert got["rows"][g] == w["rows"], g
+        assert got["gapped"][g] == w["gapped"], g
+        assert got["cons"][g] == w["cons"] and int(got["cons_len"][g]) == len(w["cons"]), g
+        assert got["qual"][g] == w["qual"], g
+
+
+def same(a, b):
+    for k in ("score_fwd", "score_rev", "forward", "rank", "nrows", "ncol", "cons_len"):
+        assert np.array_equal(a[k], b[k]), k
+    for k in ("rows", "gapped", "cons", "qual"):
+        assert a[k] == b[k], k
+
+
+def test_the_inputs_hold_every_case(batch):
+    """asserted on the oracle's own results: the test cannot pass on easy inputs"""
+    groups, refs, kinds, want = batch
+    w = want[False]
+    assert len(groups) == 40 and {len(g) for g in groups} == set(KS)
+    assert all(50 <= r.shape[1] <= 600 for r in refs) and all(1 <= p.shape[1] <= 300 for g in groups for p in g)
+    assert any(x["nrows"] == 0 and len(groups[g]) > 1 for g, x in enumerate(w))            # every trace excluded
+    assert any(x["nrows"] == 2 for x in w)                                                  # one matching trace
+    assert any(x["nrows"] == 2 and len(groups[g]) == 2 for g, x in enumerate(w))            # ... beside an excluded one
+    assert sum(1 for x in w for i, f in enumerate(x["forward"]) if not f and x["rank"][i] != 0xffffffff) >= 10  # reverse strand chosen
+    ties = [x for x in w if any(a["score"] == b["score"] and a["idx"] < b["idx"] for a, b in zip(x["order"], x["order"][1:]))]
+    assert ties                                                                             # equal scores: the input index decides
+    assert any("v" in ops for x in w for ops, _ in x["steps"][1:])                          # old rows gain gap columns at a step k >= 1
+    cross = lambda lim: any(a[1] <= lim < b[1] for x in w for a, b in zip(x["steps"], x["steps"][1:]))
+    assert cross(64) and cross(256)                                                         # ncol crosses a round / four rounds between steps
+    assert any(p.shape[1] == 1 and x["rank"][i] != 0xffffffff for g, x in enumerate(w) for i, p in enumerate(groups[g]))  # a one-column trace, matching
+    assert max(x["nrows"] for x in w) == 9
+    assert any(a["gapped"] != b["gapped"] for a, b in zip(want[False], want[True]))         # include_reference changes a consensus
+
+
+@pytest.mark.parametrize("include_reference", [False, True])
+@pytest.mark.parametrize("device", [False, True])
+def test_batch_matches_oracle(ctx, batch, device, include_reference):
+    groups, refs, kinds, want = batch
+    got = ctx.assemble_traces(groups, refs, SCORE, FRACMATCH, CALLED, include_reference, device=device)
+    check(got, want[include_reference], groups)
+    stats = ctx.last_call_stats()
+    assert stats["traces"] == sum(len(g) for g in groups) and stats["asm_chunks"] == 1 and stats["asm_steps"] == 8
+    assert stats["host_syncs"] == 2 + 8 + 1  # classes, scores, one per chain step, the end
+
+
+def test_async_and_chunks_give_the_same(ctx, batch):
+    from tracy_amd import capi
+    groups, refs, kinds, want = batch
+    base = ctx.assemble_traces(groups, refs, SCORE, FRACMATCH, CALLED, False)
+    p = capi.PreparedAssemble(groups[:20], refs[:20], SCORE, FRACMATCH, CALLED, False)
+    q = capi.PreparedAssemble(groups[20:], refs[20:], SCORE, FRACMATCH, CALLED, True)
+    ctx.assemble_traces_async(p.job, p.prm, p.out)
+    ctx.assemble_traces_async(q.job, q.prm, q.out)
+    ctx.synchronize()
+    check(p.results(), want[False][:20], groups[:20])
+    check(q.results(), want[True][20:], groups[20:])
+    # a workspace limit that fits a few groups at a time: the batch runs in chunks of groups, same results
+    ctx.set_workspace_limit(4 << 20)
+    try:
+        got = ctx.assemble_traces(groups, refs, SCORE, FRACMATCH, CALLED, False)
+        stats = ctx.last_call_stats()
+        assert stats["asm_chunks"] > 1 and stats["asm_steps"] > 8
+        dev = ctx.assemble_traces(groups, refs, SCORE, FRACMATCH, CALLED, False, device=True)
+    finally:
+        ctx.set_workspace_limit(0)
+    same(got, base)
+    same(dev, base)
+
+
+def test_shared_reference_empty_batch_and_bad_input(ctx, batch):
+    from tracy_amd import capi
+    groups, refs, kinds, want = batch
+    # two groups on one reference through ref_index, a group without traces between them
+    got = ctx.assemble_traces([groups[0], [], groups[0]], [refs[0]], SCORE, FRACMATCH, CALLED, ref_index=[0, 0, 0])
+    assert got["rows"][0] == want[False][0]["rows"] and got["rows"][2] == want[False][0]["rows"] and int(got["nrows"][1]) == 0
+    z = ctx.assemble_traces([], [], SCORE)
+    assert len(z["rows"]) == 0
+    with pytest.raises(capi.TracyHipError) as e:
+        ctx.assemble_traces([[np.zeros((6, 0), np.float32)]], [refs[0]], SCORE)
+    assert e.value.code == capi.ERR_ARG
+    with pytest.raises(capi.TracyHipError) as e:
+        ctx.assemble_traces([groups[0]], [refs[0]], (40000, -5, -10, -4))
+    assert e.value.code == capi.ERR_RANGE
+
+
+# ---- the command line -------------------------------------------------------------------------------------------------
+
+
+def tiled_traces(rng, tmp, n, region_len=1500, tlen=420, some_reverse=True, noisy_ends=True):
+    """ABIF files of n reads tiled over a random region (tests/test_gpu_cli.py::tiled_traces): every third one from the other strand"""
+    import sage_oracle as so
+    from tracy_amd import hostlib
+    region = bytes(rng.choice(list(b"ACGT"), size=region_len).tolist())
+    paths = []
+    for i in range(n):
+        start = int(i * (region_len - tlen) / max(n - 1, 1))
+        seq = bytearray(region[start:start + tlen])
+        for k in range(len(seq)):
+            if rng.random() < 0.01:
+                seq[k] = int(rng.choice(list(b"ACGT")))
+        seq = bytes(seq)
+        if some_reverse and i % 3 == 1:
+            seq = so.revcomp(seq)
+        nb = len(seq)
+        tr = np.zeros((4, 12 * nb + 12), np.int32)
+        pos = 6 + 12 * np.arange(nb, dtype=np.int32)
+        tri = 1.0 - np.abs(np.arange(-5, 6)) / 6.0
+        for j, ch in enumerate(seq):
+            amp = rng.uniform(500, 1100)
+            tr[b"ACGT".index(ch), pos[j] - 5:pos[j] + 6] += (amp * tri).astype(np.int32)
+            noisy = noisy_ends and (j < 25 or j > nb - 30)
+            tr[int(rng.integers(0, 4)), pos[j] - 5:pos[j] + 6] += (amp * (0.6 if noisy else 0.06) * tri).astype(np.int32)
+        p = os.path.join(tmp, "tile%02d.ab1" % i)
+        hostlib.write_abif(p, tr, pos, seq, np.full(nb, 40, np.uint8))
+        paths.append(p)
+    return region, paths
+
+
+def run_cli(args, cwd, timeout=600):
+    return subprocess.run([CLI, "assemble"] + args, cwd=cwd, capture_output=True, text=True, timeout=timeout)
+
+
+def test_cli_batch_matches_one_group_command(tmp_path):
+    sizes = (2, 5, 3)
+    groups = []
+    for k, n in enumerate(sizes):
+        d = tmp_path / ("g%d" % k)
+        d.mkdir()
+        region, paths = tiled_traces(np.random.default_rng(100 + k), str(d), n, region_len=700, tlen=260)
+        ref = str(d / "region.fa")
+        open(ref, "w").write(">region%d\n%s\n" % (k, region.decode()))
+        groups.append([ref, paths])
+    (tmp_path / "junk").mkdir()
+    _, junk = tiled_traces(np.random.default_rng(9), str(tmp_path / "junk"), 1, region_len=400, tlen=260)
+    groups[1][1].insert(2, junk[0])  # a trace that matches nothing: the warning path
+    single, batch = tmp_path / "single", tmp_path / "batch"
+    single.mkdir()
+    batch.mkdir()
+    opts = ["-i", "-a", "fastq", "-g", "-9", "-e", "-3"]
+    for k, (ref, paths) in enumerate(groups):
+        r = run_cli(opts + ["-r", ref, "-o", str(single / ("a%d" % k))] + paths, str(tmp_path))
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert ("is not matching to the reference" in r.stderr) == (k == 1)
+    man = tmp_path / "manifest.tsv"
+    lines = [(p, ref, str(batch / ("a%d" % k))) for k, (ref, paths) in enumerate(groups) for p in paths]
+    lines = lines[0::2] + lines[1::2]  # the lines of the groups interleaved: a group is the lines of one outprefix, in manifest order
+    order = {k: [p for p, _, pre in lines if pre.endswith("a%d" % k)] for k in range(3)}
+    with open(man, "w") as f:
+        f.write("# trace\treference\toutprefix\n")
+        for p, ref, pre in lines:
+            f.write("%s\t%s\t%s\n" % (p, "-" if ref == groups[0][0] else ref, pre))
+    # (the one-group runs above took the traces in their own order; run them again in the manifest's where that differs)
+    for k, (ref, paths) in enumerate(groups):
+        if order[k] != paths:
+            r = run_cli(opts + ["-r", ref, "-o", str(single / ("a%d" % k))] + order[k], str(tmp_path))
+            assert r.returncode == 0, r.stderr[-2000:]
+    r = run_cli(opts + ["-r", groups[0][0], "--batch", str(man)], str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stderr.count("is not matching to the reference! Trace file will be excluded!") == 1 and "Warning: tile00 " in r.stderr
+    for k in range(3):
+        for ext in (".align.fa", ".json", ".vertical", ".cons.fq", ".cons.fa"):
+            s, b = single / ("a%d%s" % (k, ext)), batch / ("a%d%s" % (k, ext))
+            assert s.exists() == b.exists(), (k, ext)
+            if s.exists():
+                assert s.read_bytes() == b.read_bytes(), (k, ext)
+        assert (batch / ("a%d.json" % k)).stat().st_size > 1000
+    # two references under one outprefix: refused, the message names the line
+    with open(man, "a") as f:
+        f.write("%s\t%s\t%s\n" % (groups[0][1][0], groups[1][0], batch / "a0"))
+    r = run_cli(opts + ["-r", groups[0][0], "--batch", str(man)], str(tmp_path))
+    assert r.returncode == 1 and "line %d" % (len(lines) + 2) in r.stderr, r.stderr[-2000:]
+    # no reference: refused (de novo assembly has no batch mode)
+    r = run_cli(opts + ["--batch", str(man)], str(tmp_path))
+    assert r.returncode == 1 and "-r" in r.stderr

@@ -15,6 +15,8 @@ struct AssembleConfig {  // assemble.h:12-30
   std::string outprefix = "out", format = "fasta", reference;
   std::vector<std::string> ab;
   int device = 0;
+  std::string batch;     // --batch: manifest of trace <TAB> reference <TAB> outprefix lines (reference-guided only)
+  uint32_t threads = 0;  // --threads: host threads of the --batch stages; 0 = every core this process may use
 };
 
 struct TraceScore {  // assemble.h:32-41
@@ -26,7 +28,8 @@ struct TraceScore {  // assemble.h:32-41
 int parse_assemble(int argc, char** argv, AssembleConfig& c) {
   static const std::map<std::string, char> longs = {{"help", '?'}, {"reference", 'r'}, {"pratio", 'p'}, {"trim", 't'}, {"fracmatch", 'f'},
                                                     {"gapopen", 'g'}, {"gapext", 'e'}, {"match", 'm'}, {"mismatch", 'n'}, {"called", 'd'},
-                                                    {"outprefix", 'o'}, {"format", 'a'}, {"inccons", 'i'}, {"incref", 'j'}, {"device", 'D'}};
+                                                    {"outprefix", 'o'}, {"format", 'a'}, {"inccons", 'i'}, {"incref", 'j'}, {"device", 'D'},
+                                                    {"batch", 'B'}, {"threads", 'T'}};
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i], val;
     char opt = 0;
@@ -65,10 +68,12 @@ int parse_assemble(int argc, char** argv, AssembleConfig& c) {
       case 'o': c.outprefix = val; break;
       case 'a': c.format = val; break;
       case 'D': c.device = std::atoi(val.c_str()); break;
+      case 'B': c.batch = val; break;
+      case 'T': c.threads = (uint32_t)std::max(0, std::atoi(val.c_str())); break;
       default: std::cerr << "unrecognised option '" << a << "'" << std::endl; return 1;
     }
   }
-  return c.ab.empty() ? 1 : 0;
+  return (c.ab.empty() == c.batch.empty()) ? 1 : 0;  // trace files, or a manifest
 }
 
 struct AsmTrace {  // one input trace: what the alignment stage and the output stage need
@@ -176,10 +181,253 @@ void gapped_trace_json(std::ostream& out, AsmTrace const& t, bool forward, std::
   assemblyTrace(out, padded, name);
 }
 
+// .align.fa and .json of a reference-guided assembly (assemble.h:290-372); scoreIdx in TraceScore order, the trace of rank i is row n - 1 - i
+void write_ref_guided_outputs(AssembleConfig const& c, std::vector<AsmTrace> const& traces, std::vector<TraceScore> const& scoreIdx,
+                              CharAlign const& align, std::string const& gapped, std::string const& cs) {
+  const std::size_t n = scoreIdx.size();
+  {
+    std::ofstream v((c.outprefix + ".align.fa").c_str());
+    for (std::size_t i = 0; i < n; ++i) {
+      v << ">" << stem(c.ab[scoreIdx[i].idx]) << (scoreIdx[i].forward ? " (forward)" : " (reverse)") << std::endl;
+      v << align[n - i - 1] << std::endl;
+    }
+    v << ">Reference" << std::endl << align[n] << std::endl;
+    if (c.incCons) v << ">Consensus" << std::endl << gapped << std::endl;
+  }
+  std::ofstream r((c.outprefix + ".json").c_str());
+  r << "{" << std::endl;
+  r << "\"gapFreeConsensus\": \"" << cs << "\"," << std::endl;
+  r << "\"gappedConsensus\": \"" << gapped << "\"," << std::endl;
+  r << "\"msa\": " << std::endl << "[" << std::endl;
+  for (std::size_t i = 0; i < n; ++i) {
+    if (i) r << ',' << std::endl;
+    alignedTraceByRow(r, align, (uint32_t)(n - i - 1), stem(c.ab[scoreIdx[i].idx]), scoreIdx[i].forward, false);
+  }
+  r << ',' << std::endl;
+  alignedTraceByRow(r, align, (uint32_t)n, "", true, true);
+  r << "]," << std::endl;
+  r << "\"gappedTraces\": " << std::endl << "[" << std::endl;
+  for (std::size_t i = 0; i < n; ++i) {
+    if (i) r << ", ";
+    gapped_trace_json(r, traces[scoreIdx[i].idx], scoreIdx[i].forward, align[n - i - 1], stem(c.ab[scoreIdx[i].idx]));
+  }
+  r << "]" << std::endl << "}" << std::endl;
+}
+
+// ---- --batch: many reference-guided assemblies, every chain on the device in one tracyhip_assemble_traces call per block -------------
+struct AsmGroup {  // the manifest lines of one outprefix, in manifest order
+  AssembleConfig c;  // the command's options with this group's outprefix and trace files
+  uint32_t ref = 0;  // index into the loaded references
+  std::vector<AsmTrace> traces;
+  bool ok = false;
+  std::vector<TraceScore> scoreIdx;
+  std::vector<uint32_t> excluded;  // input indices of the traces that do not match
+  CharAlign align;
+  std::string gapped, cs, qstr;
+};
+
+// all chains of `gs` (every one loaded) through one device call; fills scoreIdx / excluded / align / gapped / cs / qstr
+bool assemble_device(tracyhip_ctx* ctx, AssembleConfig const& c, detail::ProfilePack& refs, std::vector<AsmGroup*> const& gs) {
+  const uint32_t ng = (uint32_t)gs.size();
+  if (ng == 0) return true;
+  detail::ProfilePack tp;
+  std::vector<uint32_t> first(ng + 1, 0), ridx(ng);
+  std::vector<uint64_t> roff(ng), coff(ng);
+  uint64_t rtot = 0, ctot = 0;
+  for (uint32_t g = 0; g < ng; ++g) {
+    uint64_t bound = refs.len[gs[g]->ref];  // capacities of tracy_hip.h: (K + 1) * (n_ref + sum len) row bytes, n_ref + sum len columns
+    for (AsmTrace const& t : gs[g]->traces) { tp.add(t.prof); bound += t.prof.cols; }
+    first[g + 1] = (uint32_t)tp.off.size();
+    ridx[g] = gs[g]->ref;
+    roff[g] = rtot;
+    coff[g] = ctot;
+    rtot += (gs[g]->traces.size() + 1) * bound;
+    ctot += bound;
+  }
+  const uint32_t nt = first[ng];
+  tracyhip_assemble_job job{};
+  job.ngroups = ng;
+  job.traces = tp.set();
+  job.group_first = first.data();
+  job.references = refs.set();
+  job.ref_index = ridx.data();
+  job.match_fraction = c.matchFraction;
+  job.fraction_called = c.fractionCalled;
+  job.include_reference = c.incRef ? 1u : 0u;
+  std::vector<int32_t> sf(nt), sr(nt);
+  std::vector<uint8_t> fwd(nt), rows(std::max<uint64_t>(rtot, 1)), gapped(std::max<uint64_t>(ctot, 1)), cons(gapped.size()), qual(gapped.size());
+  std::vector<uint32_t> rank(nt), nrows(ng), ncol(ng), clen(ng);
+  tracyhip_assemble_result res{sf.data(), sr.data(), fwd.data(), rank.data(), nrows.data(), ncol.data(), rows.data(), gapped.data(),
+                               cons.data(), qual.data(), clen.data(), roff.data(), coff.data()};
+  tracyhip_params semi{c.match, c.mismatch, c.gapopen, c.gapext, 1, 0};  // AlignConfig<true,false>
+  if (tracyhip_assemble_traces(ctx, &job, &semi, TRACYHIP_MEM_HOST, &res) != TRACYHIP_OK) {
+    gpu_fail("assembly");
+    return false;
+  }
+  for (uint32_t g = 0; g < ng; ++g) {
+    AsmGroup& a = *gs[g];
+    const uint32_t K = first[g + 1] - first[g];
+    a.scoreIdx.assign(nrows[g] ? nrows[g] - 1 : 0, TraceScore{0, 0, 0, true});
+    for (uint32_t i = 0; i < K; ++i) {
+      const uint32_t t = first[g] + i;
+      if (rank[t] == UINT32_MAX) a.excluded.push_back(i);
+      else a.scoreIdx[rank[t]] = TraceScore{std::max(sf[t], sr[t]), (int32_t)i, (int32_t)rank[t], fwd[t] != 0};
+    }
+    a.align.assign(nrows[g], std::string());
+    for (uint32_t r = 0; r < nrows[g]; ++r)
+      a.align[r].assign(reinterpret_cast<const char*>(rows.data() + roff[g] + (uint64_t)r * ncol[g]), ncol[g]);
+    if (nrows[g]) {
+      a.gapped.assign(reinterpret_cast<const char*>(gapped.data() + coff[g]), ncol[g]);
+      a.cs.assign(reinterpret_cast<const char*>(cons.data() + coff[g]), clen[g]);
+      a.qstr.assign(reinterpret_cast<const char*>(qual.data() + coff[g]), clen[g]);
+    }
+    for (AsmTrace& t : a.traces) t.prof = Profile();
+  }
+  return true;
+}
+
+int assemble_batch(AssembleConfig const& c, int argc, char** argv) {
+  std::vector<AsmGroup> groups;
+  std::vector<std::string> ref_paths;
+  {
+    std::ifstream mf(c.batch.c_str());
+    if (!mf) {
+      std::cerr << "Manifest is missing: " << c.batch << std::endl;
+      return 1;
+    }
+    std::map<std::string, uint32_t> by_prefix, by_ref;
+    std::string line;
+    uint32_t lineno = 0;
+    while (std::getline(mf, line)) {
+      ++lineno;
+      if (line.empty() || line[0] == '#') continue;
+      std::istringstream ss(line);
+      std::string trace, ref, prefix;
+      if (!std::getline(ss, trace, '\t') || !std::getline(ss, ref, '\t') || !std::getline(ss, prefix, '\t') || trace.empty() || prefix.empty()) {
+        std::cerr << "Malformed manifest line " << lineno << ": " << line << std::endl;
+        return 1;
+      }
+      if (ref.empty() || ref == "-") ref = c.reference;
+      auto r = by_ref.find(ref);
+      if (r == by_ref.end()) {
+        r = by_ref.emplace(ref, (uint32_t)ref_paths.size()).first;
+        ref_paths.push_back(ref);
+      }
+      auto it = by_prefix.find(prefix);
+      if (it == by_prefix.end()) {
+        it = by_prefix.emplace(prefix, (uint32_t)groups.size()).first;
+        groups.emplace_back();
+        groups.back().c = c;
+        groups.back().c.outprefix = prefix;
+        groups.back().c.ab.clear();
+        groups.back().ref = r->second;
+      } else if (groups[it->second].ref != r->second) {
+        std::cerr << "Manifest line " << lineno << ": outprefix " << prefix << " already has the reference " << ref_paths[groups[it->second].ref]
+                  << ", not " << ref << std::endl;
+        return 1;
+      }
+      groups[it->second].c.ab.push_back(trace);
+    }
+  }
+  for (AsmGroup const& g : groups)
+    for (auto const& p : g.c.ab)
+      if (!regular_nonempty(p)) {
+        std::cerr << "Trace file is missing: " << p << std::endl;
+        return 1;
+      }
+  echo_command(argc, argv);
+  detail::ProfilePack refs;
+  for (std::string const& path : ref_paths) {
+    std::string faname, seq;
+    if (!loadSingleFasta(path, faname, seq)) return -1;
+    if (seq.size() > kMaxSingleFasta) {
+      std::cerr << "Reference is larger than 50Kbp. Please use a smaller reference slice!" << std::endl;
+      return -1;
+    }
+    Profile p;
+    createProfile(seq, p);
+    refs.add(p);
+  }
+  std::cout << stamp() << "Load ab1 files" << std::endl;
+  const uint32_t nthreads = c.threads ? c.threads : usable_cores();
+  StageTimes times;
+  std::atomic<int> failed(0);
+  auto prep = [&](uint32_t lo, uint32_t hi) {
+    Stopwatch sw;
+    std::vector<std::pair<uint32_t, uint32_t>> work;  // (group, trace)
+    for (uint32_t g = lo; g < hi; ++g) {
+      groups[g].traces.assign(groups[g].c.ab.size(), AsmTrace());
+      for (uint32_t i = 0; i < groups[g].c.ab.size(); ++i) work.emplace_back(g, i);
+    }
+    std::vector<int> rcs(work.size(), 0);
+    for_each_index((uint32_t)work.size(), nthreads, [&](uint32_t w) {
+      AsmGroup& g = groups[work[w].first];
+      rcs[w] = load_asm_trace(g.c, g.c.ab[work[w].second], g.traces[work[w].second]);
+    });
+    for (uint32_t g = lo; g < hi; ++g) groups[g].ok = true;
+    for (std::size_t w = 0; w < work.size(); ++w)
+      if (rcs[w] != 0) groups[work[w].first].ok = false;
+    for (uint32_t g = lo; g < hi; ++g)
+      if (!groups[g].ok) {  // (too stringent trimming, no basecalls, unreadable: what ends the one-group command)
+        std::cerr << "skipping " << groups[g].c.outprefix << std::endl;
+        groups[g].traces.clear();
+        ++failed;
+      }
+    times.add("read_basecall_profile_s", sw.seconds());
+  };
+  Device dev;
+  std::future<int> dev_ready = std::async(std::launch::async, [&]() {
+    Stopwatch sw;
+    const int rc = tracyhip_create(c.device, &dev.ctx) == TRACYHIP_OK ? 0 : -1;
+    times.add("gpu_init_s", sw.seconds());
+    return rc;
+  });
+  bool dev_open = false;
+  auto device = [&](uint32_t lo, uint32_t hi) -> bool {
+    if (!dev_open) {
+      if (dev_ready.get() != 0) {
+        gpu_fail("no usable GPU");
+        return false;
+      }
+      dev_open = true;
+      std::cout << stamp() << "Align ab1 files" << std::endl;
+    }
+    Stopwatch sw;
+    std::vector<AsmGroup*> gs;
+    for (uint32_t g = lo; g < hi; ++g)
+      if (groups[g].ok) gs.push_back(&groups[g]);
+    const bool ok = assemble_device(dev.ctx, c, refs, gs);
+    times.add("device_s", sw.seconds());
+    return ok;
+  };
+  auto write = [&](uint32_t lo, uint32_t hi) {
+    Stopwatch sw;
+    for (uint32_t g = lo; g < hi; ++g)  // (the warnings in manifest order)
+      for (uint32_t i : groups[g].excluded)
+        std::cerr << "Warning: " << stem(groups[g].c.ab[i]) << " is not matching to the reference! Trace file will be excluded!" << std::endl;
+    for_each_index(hi - lo, nthreads, [&](uint32_t i) {
+      AsmGroup& g = groups[lo + i];
+      if (g.ok) {
+        if (!g.scoreIdx.empty()) write_ref_guided_outputs(g.c, g.traces, g.scoreIdx, g.align, g.gapped, g.cs);
+        write_assembly_outputs(g.c, g.align, g.gapped, g.cs, g.qstr);
+      }
+      AsmGroup done;
+      done.ok = g.ok;
+      g = std::move(done);  // the block's traces and rows are released here
+    });
+    times.add("writers_s", sw.seconds());
+  };
+  if (!run_blocks((uint32_t)groups.size(), block_size(), prep, device, write)) return -1;
+  times.report((uint32_t)groups.size(), nthreads);
+  std::cout << stamp() << "Done." << std::endl;
+  end_process(failed ? 2 : 0);
+}
+
 int assemble_main(int argc, char** argv) {
   AssembleConfig c;
   if (parse_assemble(argc, argv, c)) {
     std::cout << "Usage: tracy " << argv[0] << " [OPTIONS] trace1.ab1 trace2.ab1 ..." << std::endl;
+    std::cout << "       tracy " << argv[0] << " [OPTIONS] -r reference.fa --batch manifest.tsv" << std::endl;
     std::cout << "Generic options:\n"
                  "  -? [ --help ]                    show help message\n"
                  "  -r [ --reference ] arg           reference-guided assembly (optional)\n"
@@ -196,7 +444,12 @@ int assemble_main(int argc, char** argv) {
                  "  -o [ --outprefix ] arg (=out)    output prefix\n"
                  "  -a [ --format ] arg (=fasta)     consensus output format [fasta|fastq]\n"
                  "  -i [ --inccons ]                 include consensus in FASTA align\n"
-                 "  -j [ --incref ]                  include reference in consensus computation (req. --reference)\n\n";
+                 "  -j [ --incref ]                  include reference in consensus computation (req. --reference)\n"
+                 "\nBatch options:\n"
+                 "  --batch arg                      manifest: trace<TAB>reference<TAB>outprefix per line; the lines of one outprefix\n"
+                 "                                   are one assembly (all of them on the GPU in one call; requires --reference,\n"
+                 "                                   which an empty or '-' reference field stands for)\n"
+                 "  --threads arg (=0)               host threads of the --batch stages (0 = all usable cores)\n\n";
     return -1;
   }
   for (auto const& p : c.ab)
@@ -210,6 +463,13 @@ int assemble_main(int argc, char** argv) {
   }
   if (c.matchFraction < 0) c.matchFraction = 0;
   else if (c.matchFraction > 1) c.matchFraction = 1;
+  if (!c.batch.empty()) {
+    if (!c.hasReference) {
+      std::cerr << "--batch needs a reference (-r): only reference-guided assemblies have a batch mode, de novo assembly runs one per command" << std::endl;
+      return 1;
+    }
+    return assemble_batch(c, argc, argv);
+  }
   echo_command(argc, argv);
 
   Device dev;
@@ -303,34 +563,7 @@ int assemble_main(int argc, char** argv) {
         align.swap(combined);
       }
       consensus(c.fractionCalled, align, gapped, cs, qstr, !c.incRef);
-      const std::size_t n = scoreIdx.size();
-      {
-        std::ofstream v((c.outprefix + ".align.fa").c_str());
-        for (std::size_t i = 0; i < n; ++i) {
-          v << ">" << stem(c.ab[scoreIdx[i].idx]) << (scoreIdx[i].forward ? " (forward)" : " (reverse)") << std::endl;
-          v << align[n - i - 1] << std::endl;
-        }
-        v << ">Reference" << std::endl << align[n] << std::endl;
-        if (c.incCons) v << ">Consensus" << std::endl << gapped << std::endl;
-      }
-      std::ofstream r((c.outprefix + ".json").c_str());
-      r << "{" << std::endl;
-      r << "\"gapFreeConsensus\": \"" << cs << "\"," << std::endl;
-      r << "\"gappedConsensus\": \"" << gapped << "\"," << std::endl;
-      r << "\"msa\": " << std::endl << "[" << std::endl;
-      for (std::size_t i = 0; i < n; ++i) {
-        if (i) r << ',' << std::endl;
-        alignedTraceByRow(r, align, (uint32_t)(n - i - 1), stem(c.ab[scoreIdx[i].idx]), scoreIdx[i].forward, false);
-      }
-      r << ',' << std::endl;
-      alignedTraceByRow(r, align, (uint32_t)n, "", true, true);
-      r << "]," << std::endl;
-      r << "\"gappedTraces\": " << std::endl << "[" << std::endl;
-      for (std::size_t i = 0; i < n; ++i) {
-        if (i) r << ", ";
-        gapped_trace_json(r, traces[scoreIdx[i].idx], scoreIdx[i].forward, align[n - i - 1], stem(c.ab[scoreIdx[i].idx]));
-      }
-      r << "]" << std::endl << "}" << std::endl;
+      write_ref_guided_outputs(c, traces, scoreIdx, align, gapped, cs);
     }
   } else {
     std::cout << stamp() << "Load ab1 files" << std::endl;

@@ -1,0 +1,641 @@
+// assemble.hip -- tracyhip_assemble_traces: the reference-guided chain of `tracy assemble` (assemble.h:219-288) for a batch of groups.
+//
+// Per group: revcomp of every trace on the device (profile.h:74-90); gotohScore of both strands against the group's reference in ONE
+// profile x profile score launch for the whole batch; the matching traces, their strands and their order on the host (bookkeeping, as
+// UPGMA is in msa.hpp); then the chain, STEP-BATCHED: step k of every group of a chunk that has more than k matching traces is one
+// batch -- msa_profile of the rows so far (written at the end of step k - 1), gotoh(trace_k, that profile) through the traceback
+// kernels of tracyhip_gotoh_align (fused walk), msa_merge with the trace as row 0.  Step 0 is gotoh(best, reference): both sides of
+// its merge are input profiles, shown as their _profileConsChar rows.  msa_consensus closes a chunk.
+//
+// The columns of step k are the op count of step k - 1, which only the device knows: the host reads the op counts back once per step
+// and builds the next step's descriptors from them.  Workspaces are sized from the bound  columns <= n_ref + sum of the trace lengths
+// (every step adds at most its trace's length), which is also the capacity the caller provides per group.
+// Host synchronisations: classes, scores, one per chain step of a chunk, one at the end.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/tracy_hip.h"
+#include "assemble_wave.h"
+#include "capi_internal.h"
+#include "launch.h"
+
+using namespace tracyhip;
+
+#define HIP_TRY(expr)                                                                               \
+  do {                                                                                              \
+    hipError_t _e = (expr);                                                                         \
+    if (_e != hipSuccess)                                                                           \
+      return set_error(_e == hipErrorOutOfMemory ? TRACYHIP_ERR_OOM : TRACYHIP_ERR_HIP, "%s failed: %s (%s:%d)", \
+                       #expr, hipGetErrorString(_e), __FILE__, __LINE__);                           \
+  } while (0)
+
+namespace {
+
+struct AsmSeq {  // one profile of the batch: float offset and columns
+  uint64_t off;
+  uint32_t len, pad;
+};
+
+struct AsmDevWave {
+  __device__ __forceinline__ uint32_t lane() const { return threadIdx.x; }
+  __device__ __forceinline__ uint64_t ballot(bool p) const { return __ballot(p); }
+};
+
+// revcomp of every trace (profile.h:74-90): rows A<->T, C<->G swapped, N and gap kept, columns reversed; trace s is written at
+// rev_base + its own offset.  One workgroup per trace.
+__global__ __launch_bounds__(256) void asm_revcomp_kernel(const AsmSeq* __restrict__ seqs, const float* __restrict__ in, float* __restrict__ out,
+                                                          uint64_t rev_base) {
+  const AsmSeq s = seqs[blockIdx.x];
+  const float* p = in + s.off;
+  float* q = out + rev_base + s.off;
+  const uint64_t n = s.len;
+  for (uint32_t j = threadIdx.x; j < s.len; j += blockDim.x) {
+    const uint64_t src = n - 1 - j;
+    q[0 * n + j] = p[3 * n + src];
+    q[1 * n + j] = p[2 * n + src];
+    q[2 * n + j] = p[1 * n + src];
+    q[3 * n + j] = p[0 * n + src];
+    q[4 * n + j] = p[4 * n + src];
+    q[5 * n + j] = p[5 * n + src];
+  }
+}
+
+// row 4 ('N') zero over a whole profile (chooses the 16-term score body); colclass (or null): the class of every column, for the
+// screened substitution scores.  One wave per profile.
+__global__ __launch_bounds__(64) void asm_classify_kernel(const AsmSeq* __restrict__ seqs, const float* __restrict__ data, uint8_t* __restrict__ zero,
+                                                          uint8_t* __restrict__ colclass) {
+  const AsmSeq s = seqs[blockIdx.x];
+  bool nz = false;
+  for (uint32_t j = threadIdx.x; j < s.len; j += 64) {
+    nz |= !(data[s.off + 4ull * s.len + j] == 0.0f);
+    if (colclass) colclass[s.off + j] = (uint8_t)column_class(data + s.off, s.len, j);
+  }
+  const unsigned long long any = __ballot(nz);
+  if (threadIdx.x == 0) zero[blockIdx.x] = any ? 0 : 1;
+}
+
+struct AsmStep {       // one group at one chain step
+  MsaSide left, right; // the new trace (always a profile); the reference profile (step 0) or the rows so far
+  uint64_t ops_off;    // the group's op string in the ops buffer
+  uint32_t slot;       // its entry of ops_len (PairDesc::out)
+  uint32_t cap;        // left.c + right.c: more ops than that cannot be (nothing is written otherwise)
+  uint8_t* dst;        // (left.n + right.n) rows x ops_len columns
+  int32_t* span;       // 2 per row of dst
+  float* prof;         // msa_profile of dst, 6 x ops_len -- or null: this was the group's last step
+  uint8_t* colclass;   // classes of its columns
+};
+
+struct AsmFinal {      // one finished group
+  const uint8_t* rows;
+  const int32_t* span;
+  uint32_t rows_used;  // the rows consensus() looks at
+  uint32_t slot;
+  int32_t cov_threshold;
+  uint32_t cap;
+  uint8_t *gapped, *cons, *qual;
+  uint32_t* cons_len;
+};
+
+// one wave per (group, row of the merged block)
+__global__ __launch_bounds__(64) void msa_merge_kernel(const AsmStep* __restrict__ steps, const uint8_t* __restrict__ ops, const uint32_t* __restrict__ ops_len) {
+  const AsmStep s = steps[blockIdx.x];
+  const uint32_t r = blockIdx.y;
+  if (r >= s.left.n + s.right.n) return;
+  const uint32_t L = ops_len[s.slot];
+  if (L > s.cap) return;
+  AsmDevWave w;
+  const bool left = r < s.left.n;
+  msa_merge_row_wave(w, ops + s.ops_off, L, left ? s.left : s.right, left ? r : r - s.left.n, left, s.dst + (uint64_t)r * L, s.span + 2 * r);
+}
+
+// one wave per (group, 64 columns); the grid covers the longest capacity, waves past a group's columns leave
+__global__ __launch_bounds__(64) void msa_profile_kernel(const AsmStep* __restrict__ steps, const uint32_t* __restrict__ ops_len) {
+  const AsmStep s = steps[blockIdx.x];
+  if (!s.prof) return;
+  const uint32_t L = ops_len[s.slot];
+  const uint32_t b = blockIdx.y * 64u;
+  if (b >= L || L > s.cap) return;
+  AsmDevWave w;
+  msa_profile_wave(w, s.dst, s.left.n + s.right.n, L, s.span, b, s.prof);
+  const uint32_t j = b + threadIdx.x;
+  if (j < L) s.colclass[j] = (uint8_t)column_class(s.prof, L, j);  // (this lane's own six stores)
+}
+
+// one wave per finished group
+__global__ __launch_bounds__(64) void msa_consensus_kernel(const AsmFinal* __restrict__ fin, const uint32_t* __restrict__ ops_len) {
+  const AsmFinal f = fin[blockIdx.x];
+  const uint32_t L = ops_len[f.slot];
+  if (L > f.cap) return;
+  AsmDevWave w;
+  msa_consensus_wave(w, f.rows, f.rows_used, L, f.span, f.cov_threshold, f.gapped, f.cons, f.qual, f.cons_len);
+}
+
+bool check_set(const tracyhip_seqset& s, const char* name) {
+  if (s.kind != TRACYHIP_SEQ_PROFILE) return set_error(TRACYHIP_ERR_ARG, "%s: kind must be PROFILE", name), false;
+  if (!s.offset || !s.length || !s.data) return set_error(TRACYHIP_ERR_ARG, "%s: null data / offset / length arrays", name), false;
+  return true;
+}
+
+int assemble_validate(const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem, const tracyhip_assemble_result* out) {
+  if (mem != TRACYHIP_MEM_HOST && mem != TRACYHIP_MEM_DEVICE) return set_error(TRACYHIP_ERR_ARG, "bad mem kind");
+  if (!job || !out) return set_error(TRACYHIP_ERR_ARG, "null job / result");
+  if (!prm) return set_error(TRACYHIP_ERR_ARG, "null params");
+  if (std::isnan(job->match_fraction)) return set_error(TRACYHIP_ERR_ARG, "match_fraction is not a number");
+  if (std::isnan(job->fraction_called)) return set_error(TRACYHIP_ERR_ARG, "fraction_called is not a number");
+  const uint32_t ng = job->ngroups;
+  if (ng == 0) return TRACYHIP_OK;
+  if (!job->group_first) return set_error(TRACYHIP_ERR_ARG, "null group_first");
+  if (!check_set(job->traces, "traces") || !check_set(job->references, "references")) return TRACYHIP_ERR_ARG;
+  if (!out->score_fwd || !out->score_rev || !out->forward || !out->rank || !out->nrows || !out->ncol || !out->rows || !out->gapped ||
+      !out->cons || !out->qual || !out->cons_len || !out->rows_offset || !out->col_offset)
+    return set_error(TRACYHIP_ERR_ARG, "null result arrays");
+  for (uint32_t g = 0; g < ng; ++g) {
+    if (job->group_first[g + 1] < job->group_first[g]) return set_error(TRACYHIP_ERR_ARG, "group_first decreases at group %u", g);
+    if (job->group_first[g + 1] > job->traces.count)
+      return set_error(TRACYHIP_ERR_ARG, "group %u ends at trace %u, the set holds %u", g, job->group_first[g + 1], job->traces.count);
+    const uint32_t r = job->ref_index ? job->ref_index[g] : g;
+    if (r >= job->references.count) return set_error(TRACYHIP_ERR_ARG, "group %u: reference %u of %u", g, r, job->references.count);
+    if (job->references.length[r] == 0) return set_error(TRACYHIP_ERR_ARG, "references: profile %u has no columns", r);
+  }
+  for (uint32_t i = job->group_first[0]; i < job->group_first[ng]; ++i)
+    if (job->traces.length[i] == 0) return set_error(TRACYHIP_ERR_ARG, "traces: profile %u has no columns", i);
+  return TRACYHIP_OK;
+}
+
+// the buffers of one call: indices into tracyhip_ctx::d_asm
+enum { AB_TR = 0, AB_SEQS, AB_CLASS, AB_REFCLASS, AB_SC2, AB_OPS, AB_OFF, AB_LEN, AB_W0, AB_W1, AB_SPAN, AB_PROF, AB_PCLASS, AB_STEP, AB_PAY };
+
+struct Match { int32_t score; uint32_t idx; bool forward; };  // TraceScore (assemble.h:32-41)
+
+int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem, const tracyhip_assemble_result* out,
+                 bool wide) {
+  const uint32_t ng = job->ngroups;
+  const uint32_t* gf = job->group_first;
+  const uint32_t t0 = gf[0], nt = gf[ng] - gf[0];
+  hipStream_t st = ctx->stream;
+  const tracyhip_seqset& sT = job->traces;
+  const tracyhip_seqset& sR = job->references;
+  DevBuf* B = ctx->d_asm;
+  auto ref_of = [&](uint32_t g) { return job->ref_index ? job->ref_index[g] : g; };
+
+  // ---- geometry: the column bound of every group and where its pieces live in the call's own buffers ----
+  std::vector<uint64_t> bound(ng), cg(ng + 1, 0), rg(ng + 1, 0), sg(ng + 1, 0);  // columns; prefix sums of columns, row bytes, span pairs
+  uint64_t eT = 0, eR = 0, max_mn = 0, ext_rows = 0, ext_col = 0;
+  for (uint32_t g = 0; g < ng; ++g) {
+    const uint32_t r = ref_of(g);
+    uint64_t b = sR.length[r];
+    eR = std::max<uint64_t>(eR, sR.offset[r] + 6ull * sR.length[r]);
+    for (uint32_t i = gf[g]; i < gf[g + 1]; ++i) {
+      b += sT.length[i];
+      eT = std::max<uint64_t>(eT, sT.offset[i] + 6ull * sT.length[i]);
+    }
+    const uint64_t K = gf[g + 1] - gf[g];
+    bound[g] = b;
+    cg[g + 1] = cg[g] + b;
+    rg[g + 1] = rg[g] + (K + 1) * b;
+    sg[g + 1] = sg[g] + (K + 1);
+    max_mn = std::max(max_mn, b);
+    if (K) {
+      ext_rows = std::max(ext_rows, out->rows_offset[g] + (K + 1) * b);
+      ext_col = std::max(ext_col, out->col_offset[g] + b);
+    }
+  }
+  int rc;
+  if ((rc = check_params(prm, max_mn))) return rc;
+  if (max_mn > 0xffffffffull) return set_error(TRACYHIP_ERR_RANGE, "a group's column bound exceeds 2^32");
+  if (nt == 0) {  // groups without traces: nrows 0 everywhere
+    if (mem == TRACYHIP_MEM_HOST) {
+      std::memset(out->nrows, 0, 4 * (size_t)ng); std::memset(out->ncol, 0, 4 * (size_t)ng); std::memset(out->cons_len, 0, 4 * (size_t)ng);
+    } else {
+      HIP_TRY(hipMemsetAsync(out->nrows, 0, 4 * (size_t)ng, st)); HIP_TRY(hipMemsetAsync(out->ncol, 0, 4 * (size_t)ng, st));
+      HIP_TRY(hipMemsetAsync(out->cons_len, 0, 4 * (size_t)ng, st));
+      HIP_TRY(ctx_sync(ctx));
+    }
+    return TRACYHIP_OK;
+  }
+
+  // ---- inputs: traces = [forward | revcomp] in one buffer, references where the caller has them (or staged) ----
+  HIP_TRY(B[AB_TR].ensure(2 * eT * 4));
+  float* d_tr = static_cast<float*>(B[AB_TR].p);
+  HIP_TRY(hipMemcpyAsync(d_tr, sT.data, eT * 4, mem == TRACYHIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+  const uint64_t rev_base = eT;
+  const void* d_refv = nullptr;
+  if ((rc = stage_in(ctx, ctx->d_in2, sR.data, eR * 4, mem, &d_refv))) return rc;
+  const float* d_ref = static_cast<const float*>(d_refv);
+  const uint32_t nref = sR.count;
+  std::vector<AsmSeq> hs((size_t)nt + nref, AsmSeq{0, 0, 0});  // (references no group uses keep length 0: nothing of them is read)
+  for (uint32_t i = 0; i < nt; ++i) hs[i] = AsmSeq{sT.offset[t0 + i], sT.length[t0 + i], 0};
+  for (uint32_t g = 0; g < ng; ++g) hs[(size_t)nt + ref_of(g)] = AsmSeq{sR.offset[ref_of(g)], sR.length[ref_of(g)], 0};
+  HIP_TRY(B[AB_SEQS].ensure(sizeof(AsmSeq) * hs.size()));
+  HIP_TRY(hipMemcpyAsync(B[AB_SEQS].p, hs.data(), sizeof(AsmSeq) * hs.size(), hipMemcpyHostToDevice, st));
+  const AsmSeq* d_seqs = static_cast<const AsmSeq*>(B[AB_SEQS].p);
+  int trc;
+  if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 2 * 4ull * eT))) return trc;
+  hipLaunchKernelGGL(asm_revcomp_kernel, dim3(nt), dim3(256), 0, st, d_seqs, (const float*)d_tr, d_tr, rev_base);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(B[AB_CLASS].ensure((size_t)nt + nref));
+  uint8_t* d_zero = static_cast<uint8_t*>(B[AB_CLASS].p);
+  uint8_t* d_refclass = nullptr;
+  const bool screen = !ctx->knobs.no_screen;
+  if (screen) {
+    HIP_TRY(B[AB_REFCLASS].ensure(std::max<uint64_t>(eR, 1)));
+    d_refclass = static_cast<uint8_t*>(B[AB_REFCLASS].p);
+  }
+  hipLaunchKernelGGL(asm_classify_kernel, dim3(nt), dim3(64), 0, st, d_seqs, (const float*)d_tr, d_zero, (uint8_t*)nullptr);
+  hipLaunchKernelGGL(asm_classify_kernel, dim3(nref), dim3(64), 0, st, d_seqs + nt, d_ref, d_zero + nt, d_refclass);
+  HIP_TRY(hipGetLastError());
+  if ((trc = timing_end(ctx))) return trc;
+  std::vector<uint8_t> hz((size_t)nt + nref);
+  HIP_TRY(hipMemcpyAsync(hz.data(), d_zero, hz.size(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx_sync(ctx));  // (the classes choose the score bodies)
+
+  uint64_t limit = ctx->ws_limit;
+  if (limit == 0) {
+    size_t fr = 0, tot = 0;
+    HIP_TRY(hipMemGetInfo(&fr, &tot));
+    limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->d_bits.cap + ctx->d_scratch.cap;
+  }
+
+  // ---- both strand scores of every trace: one launch per run of equal strip height / term count ----
+  std::vector<uint32_t> grp(nt);
+  for (uint32_t g = 0; g < ng; ++g)
+    for (uint32_t i = gf[g]; i < gf[g + 1]; ++i) grp[i - t0] = g;
+  std::vector<int> KS(nt);
+  for (uint32_t i = 0; i < nt; ++i) KS[i] = choose_k(sT.length[t0 + i], MODE_PROF);
+  auto row4 = [&](uint32_t i) { return hz[i] && hz[(size_t)nt + ref_of(grp[i])]; };
+  std::vector<uint32_t> order(nt);
+  for (uint32_t i = 0; i < nt; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+    if (KS[x] != KS[y]) return KS[x] > KS[y];
+    return row4(x) > row4(y);
+  });
+  const size_t ndesc = std::max<size_t>(2 * (size_t)nt, ng);
+  HIP_TRY(ctx->h_desc.ensure(sizeof(PairDesc) * ndesc));
+  HIP_TRY(ctx->d_desc.ensure(sizeof(PairDesc) * ndesc));
+  PairDesc* hd = static_cast<PairDesc*>(ctx->h_desc.p);
+  PairDesc* dd = static_cast<PairDesc*>(ctx->d_desc.p);
+  uint64_t sc_scratch = 0;
+  for (uint32_t j = 0; j < nt; ++j) {
+    const uint32_t i = order[j], r = ref_of(grp[i]);
+    const uint32_t m = sT.length[t0 + i], n = sR.length[r];
+    const uint32_t P = num_passes(m, KS[i]);
+    PairDesc d{};
+    d.a1_off = sT.offset[t0 + i];
+    d.a2_off = sR.offset[r];
+    d.m = m; d.n = n;
+    d.a1_stride = m; d.a2_stride = n;
+    d.flags = row4(i) ? PAIR_ROW4_ZERO : 0u;
+    for (uint32_t s = 0; s < 2; ++s) {
+      d.a1_off = sT.offset[t0 + i] + (s ? rev_base : 0);
+      d.scratch_off = sc_scratch;
+      d.out = 2 * i + s;
+      hd[2 * (size_t)j + s] = d;
+      if (P > 1) sc_scratch += (uint64_t)n + 2;
+    }
+  }
+  if (sc_scratch * 8 > limit)
+    return set_error(TRACYHIP_ERR_OOM, "the strand scores need %llu bytes of boundary rows, workspace limit is %llu", (unsigned long long)(sc_scratch * 8),
+                     (unsigned long long)limit);
+  HIP_TRY(hipMemcpyAsync(dd, hd, sizeof(PairDesc) * 2 * (size_t)nt, hipMemcpyHostToDevice, st));
+  if (sc_scratch) HIP_TRY(ctx->d_scratch.ensure(sc_scratch * 8));
+  HIP_TRY(ctx->d_err.ensure(kErrBytes));
+  HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, sizeof(int32_t) * kErrWords, st));
+  HIP_TRY(B[AB_SC2].ensure(sizeof(int32_t) * 2 * (size_t)nt));
+  int32_t* d_sc2 = static_cast<int32_t*>(B[AB_SC2].p);
+
+  DpArgs a{};
+  a.a1 = d_tr;
+  a.a2 = d_ref;
+  a.scratch = static_cast<int32_t*>(ctx->d_scratch.p);
+  a.err = static_cast<int32_t*>(ctx->d_err.p);
+  a.match = prm->match; a.mismatch = prm->mismatch; a.go = prm->go; a.ge = prm->ge;
+  a.hfree = prm->hfree; a.vfree = prm->vfree;
+  a.qlimit = sub_limit(prm);
+  a.screen = screen ? 1 : 0;
+  a.colcode = d_refclass;
+  a.scores = d_sc2;
+  std::vector<std::pair<uint32_t, int>> narrow_launches;
+  for (uint32_t j = 0; j < nt;) {
+    uint32_t e = j;
+    const int k = KS[order[j]];
+    const uint32_t r4 = hd[2 * (size_t)j].flags & PAIR_ROW4_ZERO;
+    uint64_t mn = 0, cells = 0;
+    while (e < nt && KS[order[e]] == k && (hd[2 * (size_t)e].flags & PAIR_ROW4_ZERO) == r4) {
+      mn = std::max<uint64_t>(mn, (uint64_t)hd[2 * (size_t)e].m + hd[2 * (size_t)e].n);
+      cells += 2ull * hd[2 * (size_t)e].m * hd[2 * (size_t)e].n;
+      ++e;
+    }
+    const bool a16 = !wide && !ctx->knobs.no_narrow && arith16_ok(prm, mn, 0);
+    if (a16) narrow_launches.emplace_back((uint32_t)mn, 0);
+    a.pairs = dd + 2 * (size_t)j;
+    if ((trc = timing_begin(ctx, TRACYHIP_TIMER_SCORE, cells, 0))) return trc;
+    HIP_TRY(launch_gotoh_prof(k, false, r4 != 0, a16, a, 2 * (e - j), st));
+    if ((trc = timing_end(ctx))) return trc;
+    j = e;
+  }
+  std::vector<int32_t> sc2(2 * (size_t)nt);
+  int32_t herr[kErrWords] = {};
+  HIP_TRY(hipMemcpyAsync(sc2.data(), d_sc2, sizeof(int32_t) * sc2.size(), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(herr, ctx->d_err.p, sizeof(herr), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx_sync(ctx));
+  {
+    const int verdict = range_verdict(prm, herr, narrow_launches, max_mn, kTagShift);
+    if (verdict != TRACYHIP_OK) return verdict;  // (kWiden: a 16-bit score launch met an un-normalised profile; the caller repeats on int32)
+  }
+
+  // ---- which traces match, their strands, their order (assemble.h:228-247) ----
+  std::vector<int32_t> h_sf(nt), h_sr(nt);
+  std::vector<uint8_t> h_fwd(nt);
+  std::vector<uint32_t> h_rank(nt, 0xffffffffu), h_nrows(ng, 0), h_ncol(ng, 0);
+  std::vector<std::vector<Match>> matched(ng);
+  for (uint32_t i = 0; i < nt; ++i) {
+    const int32_t gsFwd = sc2[2 * (size_t)i], gsRev = sc2[2 * (size_t)i + 1];
+    h_sf[i] = gsFwd; h_sr[i] = gsRev;
+    h_fwd[i] = gsFwd >= gsRev ? 1 : 0;
+    const double seqsize = (double)sT.length[t0 + i];
+    const double thr = seqsize * job->match_fraction * prm->match + seqsize * (1 - job->match_fraction) * prm->mismatch;
+    if (gsFwd > thr || gsRev > thr) matched[grp[i]].push_back(Match{std::max(gsFwd, gsRev), i, gsFwd >= gsRev});
+  }
+  for (uint32_t g = 0; g < ng; ++g) {
+    std::vector<Match>& v = matched[g];
+    std::sort(v.begin(), v.end(), [](const Match& x, const Match& y) { return x.score > y.score || (x.score == y.score && x.idx < y.idx); });
+    for (size_t k = 0; k < v.size(); ++k) h_rank[v[k].idx] = (uint32_t)k;
+    h_nrows[g] = v.empty() ? 0u : (uint32_t)v.size() + 1u;
+  }
+
+  // ---- chunks of groups: the traceback planes (and boundary rows) of a step of all its groups fit the workspace ----
+  struct Chunk { uint32_t lo, hi; uint64_t words, scratch; uint32_t steps; };
+  std::vector<Chunk> chunks;
+  {
+    Chunk c{0, 0, 0, 0, 0};
+    for (uint32_t g = 0; g < ng; ++g) {
+      if (matched[g].empty()) { c.hi = g + 1; continue; }
+      uint64_t words = 0, scr = 0;
+      for (const Match& mt : matched[g]) {
+        const uint32_t m = sT.length[t0 + mt.idx];
+        const uint32_t P = num_passes(m, KS[mt.idx]);
+        words = std::max(words, (uint64_t)P * steps_per_pass((uint32_t)bound[g]) * 64);
+        if (P > 1) scr = bound[g] + 2;
+      }
+      const uint64_t need = words * 8 + scr * 8;
+      if (need > limit)
+        return set_error(TRACYHIP_ERR_OOM, "group %u needs %llu bytes of traceback planes, workspace limit is %llu", g, (unsigned long long)need,
+                         (unsigned long long)limit);
+      if (c.steps && (c.words + words) * 8 + (c.scratch + scr) * 8 > limit) {
+        c.hi = g;
+        chunks.push_back(c);
+        c = Chunk{g, g, 0, 0, 0};
+      }
+      c.words += words;
+      c.scratch += scr;
+      c.steps = std::max<uint32_t>(c.steps, (uint32_t)matched[g].size());
+      c.hi = g + 1;
+    }
+    chunks.push_back(c);
+  }
+  uint64_t max_words = 0, max_scr = sc_scratch;
+  for (const Chunk& c : chunks) { max_words = std::max(max_words, c.words); max_scr = std::max(max_scr, c.scratch); }
+  HIP_TRY(ctx->d_bits.ensure(std::max<uint64_t>(max_words * 8, 8)));
+  if (max_scr) HIP_TRY(ctx->d_scratch.ensure(max_scr * 8));
+
+  // ---- the call's own buffers: ops, their offsets / counts, two row blocks, spans, the profile of the rows and its classes ----
+  const uint64_t ncols = std::max<uint64_t>(cg[ng], 1), nrowb = std::max<uint64_t>(rg[ng], 1);
+  HIP_TRY(B[AB_OPS].ensure(ncols));
+  HIP_TRY(B[AB_OFF].ensure(sizeof(uint64_t) * (size_t)ng));
+  HIP_TRY(B[AB_LEN].ensure(sizeof(uint32_t) * (size_t)ng));
+  HIP_TRY(B[AB_W0].ensure(nrowb));
+  HIP_TRY(B[AB_W1].ensure(nrowb));
+  HIP_TRY(B[AB_SPAN].ensure(sizeof(int32_t) * 2 * (size_t)sg[ng]));
+  HIP_TRY(B[AB_PROF].ensure(sizeof(float) * 6 * ncols));
+  HIP_TRY(B[AB_PCLASS].ensure(6 * ncols));
+  HIP_TRY(B[AB_STEP].ensure((sizeof(AsmStep) + sizeof(AsmFinal)) * (size_t)ng));
+  uint8_t* d_ops = static_cast<uint8_t*>(B[AB_OPS].p);
+  uint32_t* d_len = static_cast<uint32_t*>(B[AB_LEN].p);
+  uint8_t* d_w[2] = {static_cast<uint8_t*>(B[AB_W0].p), static_cast<uint8_t*>(B[AB_W1].p)};
+  int32_t* d_span = static_cast<int32_t*>(B[AB_SPAN].p);
+  float* d_prof = static_cast<float*>(B[AB_PROF].p);
+  uint8_t* d_pclass = static_cast<uint8_t*>(B[AB_PCLASS].p);
+  AsmStep* d_step = static_cast<AsmStep*>(B[AB_STEP].p);
+  AsmFinal* d_fin = reinterpret_cast<AsmFinal*>(d_step + ng);
+  HIP_TRY(ctx->h_off.ensure(sizeof(uint64_t) * (size_t)ng));
+  std::memcpy(ctx->h_off.p, cg.data(), sizeof(uint64_t) * (size_t)ng);
+  HIP_TRY(hipMemcpyAsync(B[AB_OFF].p, ctx->h_off.p, sizeof(uint64_t) * (size_t)ng, hipMemcpyHostToDevice, st));
+  const uint64_t* d_off = static_cast<const uint64_t*>(B[AB_OFF].p);
+  HIP_TRY(hipMemsetAsync(d_len, 0, sizeof(uint32_t) * (size_t)ng, st));
+  HIP_TRY(ctx->h_tmp.ensure((sizeof(AsmStep) + sizeof(AsmFinal)) * (size_t)ng));
+  AsmStep* h_step = static_cast<AsmStep*>(ctx->h_tmp.p);
+  AsmFinal* h_fin = reinterpret_cast<AsmFinal*>(h_step + ng);
+  HIP_TRY(ctx->h_res.ensure(sizeof(uint32_t) * (size_t)ng));
+  uint32_t* h_len = static_cast<uint32_t*>(ctx->h_res.p);
+
+  // payload results: the caller's (MEM_DEVICE) or staged in the caller's layout (MEM_HOST)
+  uint8_t *o_rows = out->rows, *o_gapped = out->gapped, *o_cons = out->cons, *o_qual = out->qual;
+  uint32_t* o_clen = out->cons_len;
+  if (mem == TRACYHIP_MEM_HOST) {
+    const uint64_t er = (std::max<uint64_t>(ext_rows, 1) + 255) & ~255ull, ec = (std::max<uint64_t>(ext_col, 1) + 255) & ~255ull;
+    HIP_TRY(B[AB_PAY].ensure(er + 3 * ec + sizeof(uint32_t) * (size_t)ng));
+    uint8_t* q = static_cast<uint8_t*>(B[AB_PAY].p);
+    o_rows = q; o_gapped = q + er; o_cons = q + er + ec; o_qual = q + er + 2 * ec;
+    o_clen = reinterpret_cast<uint32_t*>(q + er + 3 * ec);
+  }
+  HIP_TRY(hipMemsetAsync(o_clen, 0, sizeof(uint32_t) * (size_t)ng, st));
+
+  a.bits = static_cast<uint64_t*>(ctx->d_bits.p);
+  a.bits32 = static_cast<uint32_t*>(ctx->d_bits.p);
+  a.scratch = static_cast<int32_t*>(ctx->d_scratch.p);
+  a.scores = nullptr;
+  const bool fused_walk = !ctx->knobs.no_fused_walk;
+  const int32_t ignore_last = job->include_reference ? 0 : 1;
+  uint32_t total_steps = 0;
+  std::vector<uint32_t> act;
+
+  for (const Chunk& c : chunks) {
+    for (uint32_t k = 0; k < c.steps; ++k) {
+      // the groups with a trace of rank k, by strip height and term count (one launch per run)
+      act.clear();
+      for (uint32_t g = c.lo; g < c.hi; ++g)
+        if (matched[g].size() > k) act.push_back(g);
+      auto flags_of = [&](uint32_t g) { return (k == 0 && row4(matched[g][0].idx)) ? (uint32_t)PAIR_ROW4_ZERO : 0u; };
+      std::stable_sort(act.begin(), act.end(), [&](uint32_t x, uint32_t y) {
+        const int kx = KS[matched[x][k].idx], ky = KS[matched[y][k].idx];
+        if (kx != ky) return kx > ky;
+        return flags_of(x) > flags_of(y);
+      });
+      const uint32_t na = (uint32_t)act.size();
+      uint64_t words = 0, scr = 0, max_cap = 0;
+      bool any_prof = false;
+      for (uint32_t j = 0; j < na; ++j) {
+        const uint32_t g = act[j];
+        const Match& mt = matched[g][k];
+        const uint32_t r = ref_of(g);
+        const uint32_t m = sT.length[t0 + mt.idx];
+        const uint32_t n = k == 0 ? sR.length[r] : h_ncol[g];
+        const uint32_t P = num_passes(m, KS[mt.idx]);
+        const uint32_t nm = (uint32_t)matched[g].size();
+        const bool last = k + 1 == nm;
+        PairDesc d{};
+        d.a1_off = sT.offset[t0 + mt.idx] + (mt.forward ? 0 : rev_base);
+        d.a2_off = k == 0 ? sR.offset[r] : 6 * cg[g];
+        d.m = m; d.n = n;
+        d.a1_stride = m; d.a2_stride = n;
+        d.flags = flags_of(g);
+        d.bits_off = words;
+        d.scratch_off = scr;
+        d.out = g;
+        hd[j] = d;
+        words += (uint64_t)P * steps_per_pass(n) * 64;
+        if (P > 1) scr += (uint64_t)n + 2;
+        AsmStep s{};
+        s.left = MsaSide{nullptr, d_tr + d.a1_off, 1u, m, m};
+        if (k == 0) s.right = MsaSide{nullptr, d_ref + d.a2_off, 1u, n, n};
+        else s.right = MsaSide{d_w[(k - 1) & 1] + rg[g], nullptr, k + 1, n, 0u};
+        s.ops_off = cg[g];
+        s.slot = g;
+        s.cap = m + n;
+        s.dst = last ? o_rows + out->rows_offset[g] : d_w[k & 1] + rg[g];
+        s.span = d_span + 2 * sg[g];
+        s.prof = last ? nullptr : d_prof + 6 * cg[g];
+        s.colclass = d_pclass + 6 * cg[g];
+        h_step[j] = s;
+        any_prof |= !last;
+        max_cap = std::max<uint64_t>(max_cap, s.cap);
+      }
+      HIP_TRY(hipMemcpyAsync(dd, hd, sizeof(PairDesc) * na, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(d_step, h_step, sizeof(AsmStep) * na, hipMemcpyHostToDevice, st));
+      a.a2 = k == 0 ? (const void*)d_ref : (const void*)d_prof;
+      a.colcode = !screen ? nullptr : k == 0 ? d_refclass : d_pclass;
+      for (uint32_t j = 0; j < na;) {
+        uint32_t e = j;
+        const int kk = KS[matched[act[j]][k].idx];
+        const uint32_t r4 = hd[j].flags & PAIR_ROW4_ZERO;
+        uint64_t cells = 0;
+        while (e < na && KS[matched[act[e]][k].idx] == kk && (hd[e].flags & PAIR_ROW4_ZERO) == r4) { cells += (uint64_t)hd[e].m * hd[e].n; ++e; }
+        a.pairs = dd + j;
+        if (fused_walk) { a.walk_ops = d_ops; a.walk_ops_off = d_off; a.walk_ops_len = d_len; }
+        if ((trc = timing_begin(ctx, TRACYHIP_TIMER_TRACE, cells, cells / 2))) return trc;
+        HIP_TRY(launch_gotoh_prof(kk, true, r4 != 0, false, a, e - j, st));
+        if ((trc = timing_end(ctx))) return trc;
+        if (!fused_walk) {
+          WalkArgs wa{};
+          wa.pairs = dd + j; wa.bits = a.bits; wa.ops = d_ops; wa.ops_off = d_off; wa.ops_len = d_len; wa.err = a.err; wa.npairs = e - j; wa.K = kk;
+          if ((trc = timing_begin(ctx, TRACYHIP_TIMER_WALK, 0, 0))) return trc;
+          HIP_TRY(launch_gotoh_walk(wa, st));
+          if ((trc = timing_end(ctx))) return trc;
+        }
+        j = e;
+      }
+      if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 0))) return trc;
+      hipLaunchKernelGGL(msa_merge_kernel, dim3(na, k + 2), dim3(64), 0, st, (const AsmStep*)d_step, (const uint8_t*)d_ops, (const uint32_t*)d_len);
+      if (any_prof)
+        hipLaunchKernelGGL(msa_profile_kernel, dim3(na, (uint32_t)((max_cap + 63) / 64)), dim3(64), 0, st, (const AsmStep*)d_step, (const uint32_t*)d_len);
+      HIP_TRY(hipGetLastError());
+      if ((trc = timing_end(ctx))) return trc;
+      // the op counts: the columns of the next step (and the group's ncol)
+      HIP_TRY(hipMemcpyAsync(h_len, d_len, sizeof(uint32_t) * (size_t)ng, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx_sync(ctx));
+      for (uint32_t j = 0; j < na; ++j) {
+        const uint32_t g = act[j];
+        if (h_len[g] > h_step[j].cap)
+          return set_error(TRACYHIP_ERR_RANGE, "group %u, step %u: the traceback gave %u ops for %u rows and columns", g, k, h_len[g], h_step[j].cap);
+        h_ncol[g] = h_len[g];
+      }
+      ++total_steps;
+    }
+    // msa_consensus of the chunk's groups
+    uint32_t nf = 0;
+    for (uint32_t g = c.lo; g < c.hi; ++g) {
+      if (matched[g].empty()) continue;
+      const uint32_t nm = (uint32_t)matched[g].size();
+      const int64_t rows = (int64_t)nm + 1 - ignore_last;
+      AsmFinal f{};
+      f.rows = o_rows + out->rows_offset[g];
+      f.span = d_span + 2 * sg[g];
+      f.rows_used = (uint32_t)rows;
+      f.slot = g;
+      f.cov_threshold = (int32_t)(job->fraction_called * (float)(size_t)rows);  // float x size_t, msa.h:196
+      f.cap = (uint32_t)bound[g];
+      f.gapped = o_gapped + out->col_offset[g];
+      f.cons = o_cons + out->col_offset[g];
+      f.qual = o_qual + out->col_offset[g];
+      f.cons_len = o_clen + g;
+      h_fin[nf++] = f;
+    }
+    if (nf) {
+      HIP_TRY(hipMemcpyAsync(d_fin, h_fin, sizeof(AsmFinal) * nf, hipMemcpyHostToDevice, st));
+      if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 0))) return trc;
+      hipLaunchKernelGGL(msa_consensus_kernel, dim3(nf), dim3(64), 0, st, (const AsmFinal*)d_fin, (const uint32_t*)d_len);
+      HIP_TRY(hipGetLastError());
+      if ((trc = timing_end(ctx))) return trc;
+      // (h_fin is filled again at the end of the next chunk that has groups to finish: behind the synchronisations of its steps)
+    }
+  }
+
+  // ---- the last synchronisation: error words, results ----
+  HIP_TRY(hipMemcpyAsync(herr, ctx->d_err.p, sizeof(herr), hipMemcpyDeviceToHost, st));
+  if (mem == TRACYHIP_MEM_HOST) {
+    std::memcpy(out->score_fwd + t0, h_sf.data(), 4 * (size_t)nt);
+    std::memcpy(out->score_rev + t0, h_sr.data(), 4 * (size_t)nt);
+    std::memcpy(out->forward + t0, h_fwd.data(), (size_t)nt);
+    std::memcpy(out->rank + t0, h_rank.data(), 4 * (size_t)nt);
+    std::memcpy(out->nrows, h_nrows.data(), 4 * (size_t)ng);
+    std::memcpy(out->ncol, h_ncol.data(), 4 * (size_t)ng);
+    HIP_TRY(hipMemcpyAsync(out->cons_len, o_clen, 4 * (size_t)ng, hipMemcpyDeviceToHost, st));
+    for (uint32_t g = 0; g < ng; ++g) {  // only what the group wrote (the columns past cons_len hold no result)
+      if (!h_nrows[g]) continue;
+      const uint64_t ro = out->rows_offset[g], co = out->col_offset[g];
+      HIP_TRY(hipMemcpyAsync(out->rows + ro, o_rows + ro, (uint64_t)h_nrows[g] * h_ncol[g], hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(out->gapped + co, o_gapped + co, h_ncol[g], hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(out->cons + co, o_cons + co, h_ncol[g], hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(out->qual + co, o_qual + co, h_ncol[g], hipMemcpyDeviceToHost, st));
+    }
+  } else {
+    HIP_TRY(hipMemcpyAsync(out->score_fwd + t0, h_sf.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(out->score_rev + t0, h_sr.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(out->forward + t0, h_fwd.data(), (size_t)nt, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(out->rank + t0, h_rank.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(out->nrows, h_nrows.data(), 4 * (size_t)ng, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(out->ncol, h_ncol.data(), 4 * (size_t)ng, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(ctx_sync(ctx));
+  timing_collect(ctx);
+  ctx->stats.asm_chunks = (uint32_t)chunks.size();
+  ctx->stats.asm_steps = total_steps;
+  return range_verdict(prm, herr, narrow_launches, max_mn, kTagShift);
+}
+
+}  // namespace
+
+extern "C" {
+
+int tracyhip_assemble_validate(const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem, const tracyhip_assemble_result* out) {
+  return assemble_validate(job, prm, mem, out);
+}
+
+int tracyhip_assemble_traces(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem,
+                             const tracyhip_assemble_result* out) {
+  int rc = assemble_validate(job, prm, mem, out);  // (before any device is touched)
+  if (rc) return rc;
+  if ((rc = ctx_begin(ctx))) return rc;
+  ctx->stats = tracyhip_call_stats{};
+  ctx->stats.traces = job->ngroups ? job->group_first[job->ngroups] - job->group_first[0] : 0;
+  ctx->stats.stream_ordered = 1;
+  if (job->ngroups == 0) return check_params(prm, 0);
+  rc = assemble_run(ctx, job, prm, mem, out, false);
+  if (rc == kWiden) rc = assemble_run(ctx, job, prm, mem, out, true);
+  return rc;
+}
+
+int tracyhip_assemble_traces_async(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem,
+                                   const tracyhip_assemble_result* out) {
+  if (!ctx || !job || !prm || !out) return set_error(TRACYHIP_ERR_ARG, "null context / job / params / result");
+  const tracyhip_assemble_job j = *job;
+  const tracyhip_params q = *prm;
+  const tracyhip_assemble_result o = *out;
+  return async_submit(ctx, [=]() { return tracyhip_assemble_traces(ctx, &j, &q, mem, &o); });
+}
+
+}  // extern "C"

@@ -129,6 +129,7 @@ struct tracyhip_ctx {
   tracyhip::DevBuf d_bcall[5];                 // tracyhip_basecall_traces (basecall.hip): per-trace inputs / results, scratch, staged signal, positions, payload results
   tracyhip::DevBuf d_cons[12];                 // tracyhip_consensus_traces (consensus.hip): both strands, classes, scores, ops, staged results, fix-ups, gq table
   bool cons_gq_ready = false;                  // d_cons holds the gq table of consensus.h
+  tracyhip::DevBuf d_asm[16];                  // tracyhip_assemble_traces (assemble.hip): both strands, classes, scores, ops, row blocks, spans, profiles, staged results
   hipError_t ensure_codes(size_t bytes, hipStream_t st) {
     hipError_t e = d_codes.ensure(bytes + 2 * tracyhip::kCodePad);
     if (e != hipSuccess) return e;
@@ -192,6 +193,7 @@ struct tracyhip_ctx {
     for (auto& b : d_seed) b.release();
     for (auto& b : d_bcall) b.release();
     for (auto& b : d_cons) b.release();
+    for (auto& b : d_asm) b.release();
     cons_gq_ready = false;
     h_desc.release();
     h_off.release();

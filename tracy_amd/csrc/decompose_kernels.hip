@@ -1194,6 +1194,10 @@ int tracyhip_decompose_alleles(tracyhip_ctx* ctx, const tracyhip_basecalls* bc, 
   if ((rc = stage_io(ctx, ctx->d_tmp[2], bc->secondary, bext, mem, true, &d_sec))) return rc;
   if ((rc = stage_io(ctx, ctx->d_tmp[3], dcp_indel, dext * 4, mem, false, &d_di))) return rc;
   if ((rc = stage_io(ctx, ctx->d_tmp[4], dcp_err, dext * 4, mem, false, &d_de))) return rc;
+  if (mem == TRACYHIP_MEM_HOST) {  // (staged tables go back whole: the entries behind dcp_n are zero, not what the buffer held)
+    HIP_TRY(hipMemsetAsync(d_di, 0, dext * 4, ctx->stream));
+    HIP_TRY(hipMemsetAsync(d_de, 0, dext * 4, ctx->stream));
+  }
   if ((rc = stage_io(ctx, ctx->d_tmp[5], status, sizeof(DecompOut) * (size_t)n, mem, false, &d_stat))) return rc;
   const DecompDesc* dd;
   if ((rc = to_device(ctx, ctx->d_desc, hd, &dd))) return rc;

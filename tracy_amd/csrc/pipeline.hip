@@ -1478,6 +1478,10 @@ struct DecomposeRun {
     if ((rc = io(out->fractions, sizeof(double) * 2 * (size_t)nt, false, &d_fr))) return rc;
     if ((rc = io(out->dcp_indel, dext * 4, false, &d_di))) return rc;
     if ((rc = io(out->dcp_err, dext * 4, false, &d_de))) return rc;
+    if (mem == TRACYHIP_MEM_HOST) {  // (staged tables go back whole: the entries behind dcp_n are zero, not what the buffer held)
+      HIP_TRY(hipMemsetAsync(d_di, 0, dext * 4, st));
+      HIP_TRY(hipMemsetAsync(d_de, 0, dext * 4, st));
+    }
     if ((rc = io(out->dstatus, sizeof(DecompOut) * (size_t)nt, false, &d_dst))) return rc;
     if ((rc = io(out->score_trim, sizeof(int32_t) * (size_t)nt, false, &d_strim))) return rc;
 

@@ -2090,6 +2090,8 @@ struct DecStream : StreamCall {
       TRY(up(A.pri, bc.primary, z.bext)); TRY(up(A.sec, bc.secondary, z.bext));
       d_prof = A.in_prof; d_ref = A.in_ref; d_sig = A.in_sig; d_pos = A.in_pos; d_pri = A.pri; d_sec = A.sec; d_sd = A.secdecomp;
       d_di = A.dcp_indel; d_de = A.dcp_err;
+      // a table holds dcp_n entries of its 2 maxindel + 2 and the whole region goes back to the caller: the rest is zero, not what the arena held
+      HIP_TRY(hipMemsetAsync(d_di, 0, z.dext * 4, st)); HIP_TRY(hipMemsetAsync(d_de, 0, z.dext * 4, st));
       for (int k = 0; k < 3; ++k) d_opsK[k] = A.ops[k];
     } else {
       point_all<DecompFields>(o, *out);
