@@ -166,9 +166,6 @@ int assemble_validate(const tracyhip_assemble_job* job, const tracyhip_params* p
   return TRACYHIP_OK;
 }
 
-// the buffers of one call: indices into tracyhip_ctx::d_asm
-enum { AB_TR = 0, AB_SEQS, AB_CLASS, AB_REFCLASS, AB_SC2, AB_OPS, AB_OFF, AB_LEN, AB_W0, AB_W1, AB_SPAN, AB_PROF, AB_PCLASS, AB_STEP, AB_PAY };
-
 struct Match { int32_t score; uint32_t idx; bool forward; };  // TraceScore (assemble.h:32-41)
 
 int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem, const tracyhip_assemble_result* out,
@@ -179,7 +176,7 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   hipStream_t st = ctx->stream;
   const tracyhip_seqset& sT = job->traces;
   const tracyhip_seqset& sR = job->references;
-  DevBuf* B = ctx->d_asm;
+  DevBuf* const B = ctx->dev;  // indexed by the AB_* roles (capi_internal.h)
   auto ref_of = [&](uint32_t g) { return job->ref_index ? job->ref_index[g] : g; };
 
   // ---- geometry: the column bound of every group and where its pieces live in the call's own buffers ----
@@ -219,32 +216,26 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   }
 
   // ---- inputs: traces = [forward | revcomp] in one buffer, references where the caller has them (or staged) ----
-  HIP_TRY(B[AB_TR].ensure(2 * eT * 4));
-  float* d_tr = static_cast<float*>(B[AB_TR].p);
+  float* d_tr; HIP_TRY(ensure_into(B[AB_TR], 2 * eT, d_tr));
   HIP_TRY(hipMemcpyAsync(d_tr, sT.data, eT * 4, mem == TRACYHIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
   const uint64_t rev_base = eT;
   const void* d_refv = nullptr;
-  if ((rc = stage_in(ctx, ctx->d_in2, sR.data, eR * 4, mem, &d_refv))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_IN2], sR.data, eR * 4, mem, &d_refv))) return rc;
   const float* d_ref = static_cast<const float*>(d_refv);
   const uint32_t nref = sR.count;
   std::vector<AsmSeq> hs((size_t)nt + nref, AsmSeq{0, 0, 0});  // (references no group uses keep length 0: nothing of them is read)
   for (uint32_t i = 0; i < nt; ++i) hs[i] = AsmSeq{sT.offset[t0 + i], sT.length[t0 + i], 0};
   for (uint32_t g = 0; g < ng; ++g) hs[(size_t)nt + ref_of(g)] = AsmSeq{sR.offset[ref_of(g)], sR.length[ref_of(g)], 0};
-  HIP_TRY(B[AB_SEQS].ensure(sizeof(AsmSeq) * hs.size()));
-  HIP_TRY(hipMemcpyAsync(B[AB_SEQS].p, hs.data(), sizeof(AsmSeq) * hs.size(), hipMemcpyHostToDevice, st));
-  const AsmSeq* d_seqs = static_cast<const AsmSeq*>(B[AB_SEQS].p);
+  AsmSeq* d_seqs; HIP_TRY(ensure_into(B[AB_SEQS], hs.size(), d_seqs));
+  HIP_TRY(hipMemcpyAsync(d_seqs, hs.data(), sizeof(AsmSeq) * hs.size(), hipMemcpyHostToDevice, st));
   int trc;
   if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 2 * 4ull * eT))) return trc;
   hipLaunchKernelGGL(asm_revcomp_kernel, dim3(nt), dim3(256), 0, st, d_seqs, (const float*)d_tr, d_tr, rev_base);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(B[AB_CLASS].ensure((size_t)nt + nref));
-  uint8_t* d_zero = static_cast<uint8_t*>(B[AB_CLASS].p);
+  uint8_t* d_zero; HIP_TRY(ensure_into(B[AB_CLASS], (size_t)nt + nref, d_zero));
   uint8_t* d_refclass = nullptr;
   const bool screen = !ctx->knobs.no_screen;
-  if (screen) {
-    HIP_TRY(B[AB_REFCLASS].ensure(std::max<uint64_t>(eR, 1)));
-    d_refclass = static_cast<uint8_t*>(B[AB_REFCLASS].p);
-  }
+  if (screen) HIP_TRY(ensure_into(B[AB_REFCLASS], std::max<uint64_t>(eR, 1), d_refclass));
   hipLaunchKernelGGL(asm_classify_kernel, dim3(nt), dim3(64), 0, st, d_seqs, (const float*)d_tr, d_zero, (uint8_t*)nullptr);
   hipLaunchKernelGGL(asm_classify_kernel, dim3(nref), dim3(64), 0, st, d_seqs + nt, d_ref, d_zero + nt, d_refclass);
   HIP_TRY(hipGetLastError());
@@ -257,7 +248,7 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   if (limit == 0) {
     size_t fr = 0, tot = 0;
     HIP_TRY(hipMemGetInfo(&fr, &tot));
-    limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->d_bits.cap + ctx->d_scratch.cap;
+    limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->dev[DB_BITS].cap + ctx->dev[DB_SCRATCH].cap;
   }
 
   // ---- both strand scores of every trace: one launch per run of equal strip height / term count ----
@@ -274,10 +265,9 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
     return row4(x) > row4(y);
   });
   const size_t ndesc = std::max<size_t>(2 * (size_t)nt, ng);
-  HIP_TRY(ctx->h_desc.ensure(sizeof(PairDesc) * ndesc));
-  HIP_TRY(ctx->d_desc.ensure(sizeof(PairDesc) * ndesc));
-  PairDesc* hd = static_cast<PairDesc*>(ctx->h_desc.p);
-  PairDesc* dd = static_cast<PairDesc*>(ctx->d_desc.p);
+  PairDesc *hd, *dd;
+  HIP_TRY(ensure_into(ctx->pin[PB_DESC], ndesc, hd));
+  HIP_TRY(ensure_into(ctx->dev[DB_DESC], ndesc, dd));
   uint64_t sc_scratch = 0;
   for (uint32_t j = 0; j < nt; ++j) {
     const uint32_t i = order[j], r = ref_of(grp[i]);
@@ -301,17 +291,16 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
     return set_error(TRACYHIP_ERR_OOM, "the strand scores need %llu bytes of boundary rows, workspace limit is %llu", (unsigned long long)(sc_scratch * 8),
                      (unsigned long long)limit);
   HIP_TRY(hipMemcpyAsync(dd, hd, sizeof(PairDesc) * 2 * (size_t)nt, hipMemcpyHostToDevice, st));
-  if (sc_scratch) HIP_TRY(ctx->d_scratch.ensure(sc_scratch * 8));
-  HIP_TRY(ctx->d_err.ensure(kErrBytes));
-  HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, sizeof(int32_t) * kErrWords, st));
-  HIP_TRY(B[AB_SC2].ensure(sizeof(int32_t) * 2 * (size_t)nt));
-  int32_t* d_sc2 = static_cast<int32_t*>(B[AB_SC2].p);
+  if (sc_scratch) HIP_TRY(ctx->dev[DB_SCRATCH].ensure(sc_scratch * 8));
+  HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
+  HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
+  int32_t* d_sc2; HIP_TRY(ensure_into(B[AB_SC2], 2 * (size_t)nt, d_sc2));
 
   DpArgs a{};
   a.a1 = d_tr;
   a.a2 = d_ref;
-  a.scratch = static_cast<int32_t*>(ctx->d_scratch.p);
-  a.err = static_cast<int32_t*>(ctx->d_err.p);
+  a.scratch = static_cast<int32_t*>(ctx->dev[DB_SCRATCH].p);
+  a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
   a.match = prm->match; a.mismatch = prm->mismatch; a.go = prm->go; a.ge = prm->ge;
   a.hfree = prm->hfree; a.vfree = prm->vfree;
   a.qlimit = sub_limit(prm);
@@ -340,7 +329,7 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   std::vector<int32_t> sc2(2 * (size_t)nt);
   int32_t herr[kErrWords] = {};
   HIP_TRY(hipMemcpyAsync(sc2.data(), d_sc2, sizeof(int32_t) * sc2.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(herr, ctx->d_err.p, sizeof(herr), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(herr, ctx->dev[DB_ERR].p, sizeof(herr), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx_sync(ctx));
   {
     const int verdict = range_verdict(prm, herr, narrow_launches, max_mn, kTagShift);
@@ -399,54 +388,50 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   }
   uint64_t max_words = 0, max_scr = sc_scratch;
   for (const Chunk& c : chunks) { max_words = std::max(max_words, c.words); max_scr = std::max(max_scr, c.scratch); }
-  HIP_TRY(ctx->d_bits.ensure(std::max<uint64_t>(max_words * 8, 8)));
-  if (max_scr) HIP_TRY(ctx->d_scratch.ensure(max_scr * 8));
+  HIP_TRY(ctx->dev[DB_BITS].ensure(std::max<uint64_t>(max_words * 8, 8)));
+  if (max_scr) HIP_TRY(ctx->dev[DB_SCRATCH].ensure(max_scr * 8));
 
   // ---- the call's own buffers: ops, their offsets / counts, two row blocks, spans, the profile of the rows and its classes ----
   const uint64_t ncols = std::max<uint64_t>(cg[ng], 1), nrowb = std::max<uint64_t>(rg[ng], 1);
-  HIP_TRY(B[AB_OPS].ensure(ncols));
+  uint8_t *d_ops, *d_w[2], *d_pclass;
+  uint32_t* d_len;
+  int32_t* d_span;
+  float* d_prof;
+  HIP_TRY(ensure_into(B[AB_OPS], ncols, d_ops));
   HIP_TRY(B[AB_OFF].ensure(sizeof(uint64_t) * (size_t)ng));
-  HIP_TRY(B[AB_LEN].ensure(sizeof(uint32_t) * (size_t)ng));
-  HIP_TRY(B[AB_W0].ensure(nrowb));
-  HIP_TRY(B[AB_W1].ensure(nrowb));
-  HIP_TRY(B[AB_SPAN].ensure(sizeof(int32_t) * 2 * (size_t)sg[ng]));
-  HIP_TRY(B[AB_PROF].ensure(sizeof(float) * 6 * ncols));
-  HIP_TRY(B[AB_PCLASS].ensure(6 * ncols));
+  HIP_TRY(ensure_into(B[AB_LEN], ng, d_len));
+  HIP_TRY(ensure_into(B[AB_W0], nrowb, d_w[0]));
+  HIP_TRY(ensure_into(B[AB_W1], nrowb, d_w[1]));
+  HIP_TRY(ensure_into(B[AB_SPAN], 2 * (size_t)sg[ng], d_span));
+  HIP_TRY(ensure_into(B[AB_PROF], 6 * ncols, d_prof));
+  HIP_TRY(ensure_into(B[AB_PCLASS], 6 * ncols, d_pclass));
   HIP_TRY(B[AB_STEP].ensure((sizeof(AsmStep) + sizeof(AsmFinal)) * (size_t)ng));
-  uint8_t* d_ops = static_cast<uint8_t*>(B[AB_OPS].p);
-  uint32_t* d_len = static_cast<uint32_t*>(B[AB_LEN].p);
-  uint8_t* d_w[2] = {static_cast<uint8_t*>(B[AB_W0].p), static_cast<uint8_t*>(B[AB_W1].p)};
-  int32_t* d_span = static_cast<int32_t*>(B[AB_SPAN].p);
-  float* d_prof = static_cast<float*>(B[AB_PROF].p);
-  uint8_t* d_pclass = static_cast<uint8_t*>(B[AB_PCLASS].p);
   AsmStep* d_step = static_cast<AsmStep*>(B[AB_STEP].p);
   AsmFinal* d_fin = reinterpret_cast<AsmFinal*>(d_step + ng);
-  HIP_TRY(ctx->h_off.ensure(sizeof(uint64_t) * (size_t)ng));
-  std::memcpy(ctx->h_off.p, cg.data(), sizeof(uint64_t) * (size_t)ng);
-  HIP_TRY(hipMemcpyAsync(B[AB_OFF].p, ctx->h_off.p, sizeof(uint64_t) * (size_t)ng, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx->pin[PB_OFF].ensure(sizeof(uint64_t) * (size_t)ng));
+  std::memcpy(ctx->pin[PB_OFF].p, cg.data(), sizeof(uint64_t) * (size_t)ng);
+  HIP_TRY(hipMemcpyAsync(B[AB_OFF].p, ctx->pin[PB_OFF].p, sizeof(uint64_t) * (size_t)ng, hipMemcpyHostToDevice, st));
   const uint64_t* d_off = static_cast<const uint64_t*>(B[AB_OFF].p);
   HIP_TRY(hipMemsetAsync(d_len, 0, sizeof(uint32_t) * (size_t)ng, st));
-  HIP_TRY(ctx->h_tmp.ensure((sizeof(AsmStep) + sizeof(AsmFinal)) * (size_t)ng));
-  AsmStep* h_step = static_cast<AsmStep*>(ctx->h_tmp.p);
+  HIP_TRY(ctx->pin[PB_TMP].ensure((sizeof(AsmStep) + sizeof(AsmFinal)) * (size_t)ng));
+  AsmStep* h_step = static_cast<AsmStep*>(ctx->pin[PB_TMP].p);
   AsmFinal* h_fin = reinterpret_cast<AsmFinal*>(h_step + ng);
-  HIP_TRY(ctx->h_res.ensure(sizeof(uint32_t) * (size_t)ng));
-  uint32_t* h_len = static_cast<uint32_t*>(ctx->h_res.p);
+  uint32_t* h_len; HIP_TRY(ensure_into(ctx->pin[PB_RES], (size_t)ng, h_len));
 
   // payload results: the caller's (MEM_DEVICE) or staged in the caller's layout (MEM_HOST)
   uint8_t *o_rows = out->rows, *o_gapped = out->gapped, *o_cons = out->cons, *o_qual = out->qual;
   uint32_t* o_clen = out->cons_len;
   if (mem == TRACYHIP_MEM_HOST) {
     const uint64_t er = (std::max<uint64_t>(ext_rows, 1) + 255) & ~255ull, ec = (std::max<uint64_t>(ext_col, 1) + 255) & ~255ull;
-    HIP_TRY(B[AB_PAY].ensure(er + 3 * ec + sizeof(uint32_t) * (size_t)ng));
-    uint8_t* q = static_cast<uint8_t*>(B[AB_PAY].p);
+    uint8_t* q; HIP_TRY(ensure_into(B[AB_PAY], er + 3 * ec + sizeof(uint32_t) * (size_t)ng, q));
     o_rows = q; o_gapped = q + er; o_cons = q + er + ec; o_qual = q + er + 2 * ec;
     o_clen = reinterpret_cast<uint32_t*>(q + er + 3 * ec);
   }
   HIP_TRY(hipMemsetAsync(o_clen, 0, sizeof(uint32_t) * (size_t)ng, st));
 
-  a.bits = static_cast<uint64_t*>(ctx->d_bits.p);
-  a.bits32 = static_cast<uint32_t*>(ctx->d_bits.p);
-  a.scratch = static_cast<int32_t*>(ctx->d_scratch.p);
+  a.bits = static_cast<uint64_t*>(ctx->dev[DB_BITS].p);
+  a.bits32 = static_cast<uint32_t*>(ctx->dev[DB_BITS].p);
+  a.scratch = static_cast<int32_t*>(ctx->dev[DB_SCRATCH].p);
   a.scores = nullptr;
   const bool fused_walk = !ctx->knobs.no_fused_walk;
   const int32_t ignore_last = job->include_reference ? 0 : 1;
@@ -575,7 +560,7 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   }
 
   // ---- the last synchronisation: error words, results ----
-  HIP_TRY(hipMemcpyAsync(herr, ctx->d_err.p, sizeof(herr), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(herr, ctx->dev[DB_ERR].p, sizeof(herr), hipMemcpyDeviceToHost, st));
   if (mem == TRACYHIP_MEM_HOST) {
     std::memcpy(out->score_fwd + t0, h_sf.data(), 4 * (size_t)nt);
     std::memcpy(out->score_rev + t0, h_sr.data(), 4 * (size_t)nt);

@@ -148,10 +148,9 @@ int tracyhip_basecall_traces(tracyhip_ctx* ctx, const tracyhip_basecall_job* job
       if (answerable(t)) scratch_words += 3ull * job->npos[t] + 1;
     }
     const size_t b_meta = 0, b_out = (b_meta + sizeof(BasecallTrace) * m + 15) & ~size_t(15), b_end = b_out + sizeof(BasecallOut) * m;
-    HIP_TRY(ctx->d_bcall[0].ensure(b_end));
-    uint8_t* d0 = static_cast<uint8_t*>(ctx->d_bcall[0].p);
+    uint8_t* d0; HIP_TRY(ensure_into(ctx->dev[DB_BCALL_TRACES], b_end, d0));
     HIP_TRY(hipMemcpyAsync(d0 + b_meta, meta.data(), sizeof(BasecallTrace) * m, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx->d_bcall[1].ensure(std::max<uint64_t>(scratch_words, 1) * 4));
+    HIP_TRY(ctx->dev[DB_BCALL_SCRATCH].ensure(std::max<uint64_t>(scratch_words, 1) * 4));
     BasecallArgs a{};
     a.signal = job->signal;
     a.pos = job->basecallpos;
@@ -161,15 +160,14 @@ int tracyhip_basecall_traces(tracyhip_ctx* ctx, const tracyhip_basecall_job* job
     const uint32_t widths[7] = {1, 1, 1, 1, 4, 16, 24};
     uint64_t at[8] = {0};
     if (host) {
-      HIP_TRY(ctx->d_bcall[2].ensure((shi - slo) * sb + 16));
-      HIP_TRY(hipMemcpyAsync(ctx->d_bcall[2].p, static_cast<const uint8_t*>(job->signal) + slo * sb, (shi - slo) * sb, hipMemcpyHostToDevice, ctx->stream));
-      a.signal = ctx->d_bcall[2].p;
-      HIP_TRY(ctx->d_bcall[3].ensure(span * 4 + 16));
-      if (span) HIP_TRY(hipMemcpyAsync(ctx->d_bcall[3].p, job->basecallpos + plo, span * 4, hipMemcpyHostToDevice, ctx->stream));
-      a.pos = static_cast<const int32_t*>(ctx->d_bcall[3].p);
+      HIP_TRY(ctx->dev[DB_BCALL_SIGNAL].ensure((shi - slo) * sb + 16));
+      HIP_TRY(hipMemcpyAsync(ctx->dev[DB_BCALL_SIGNAL].p, static_cast<const uint8_t*>(job->signal) + slo * sb, (shi - slo) * sb, hipMemcpyHostToDevice, ctx->stream));
+      a.signal = ctx->dev[DB_BCALL_SIGNAL].p;
+      HIP_TRY(ctx->dev[DB_BCALL_POS].ensure(span * 4 + 16));
+      if (span) HIP_TRY(hipMemcpyAsync(ctx->dev[DB_BCALL_POS].p, job->basecallpos + plo, span * 4, hipMemcpyHostToDevice, ctx->stream));
+      a.pos = static_cast<const int32_t*>(ctx->dev[DB_BCALL_POS].p);
       for (int k = 0; k < 7; ++k) at[k + 1] = at[k] + (wanted[k] ? ((span * widths[k] + 15) & ~15ull) : 0);
-      HIP_TRY(ctx->d_bcall[4].ensure(at[7] + 16));
-      uint8_t* d4 = static_cast<uint8_t*>(ctx->d_bcall[4].p);
+      uint8_t* d4; HIP_TRY(ensure_into(ctx->dev[DB_BCALL_PAY], at[7] + 16, d4));
       if (out->primary) pl.primary = d4 + at[0];
       if (out->secondary) pl.secondary = d4 + at[1];
       if (out->consensus) pl.consensus = d4 + at[2];
@@ -183,7 +181,7 @@ int tracyhip_basecall_traces(tracyhip_ctx* ctx, const tracyhip_basecall_job* job
     }
     a.tr = reinterpret_cast<const BasecallTrace*>(d0 + b_meta);
     a.out = reinterpret_cast<BasecallOut*>(d0 + b_out);
-    a.scratch = static_cast<uint32_t*>(ctx->d_bcall[1].p);
+    a.scratch = static_cast<uint32_t*>(ctx->dev[DB_BCALL_SCRATCH].p);
     a.primary = pl.primary; a.secondary = pl.secondary; a.consensus = pl.consensus; a.estqual = pl.estqual;
     a.bcpos = pl.bcpos; a.peaks = pl.peaks; a.profiles = pl.profiles;
     a.ntraces = m;
@@ -204,7 +202,7 @@ int tracyhip_basecall_traces(tracyhip_ctx* ctx, const tracyhip_basecall_job* job
     auto flush = [&]() -> hipError_t {
       for (int k = 0; k < 7 && run_len; ++k) {
         if (!dsts[k]) continue;
-        const hipError_t e = hipMemcpyAsync(dsts[k] + run_dst * widths[k], static_cast<uint8_t*>(ctx->d_bcall[4].p) + at[k] + run_rel * widths[k],
+        const hipError_t e = hipMemcpyAsync(dsts[k] + run_dst * widths[k], static_cast<uint8_t*>(ctx->dev[DB_BCALL_PAY].p) + at[k] + run_rel * widths[k],
                                             run_len * widths[k], hipMemcpyDeviceToHost, ctx->stream);
         if (e != hipSuccess) return e;
       }

@@ -439,6 +439,18 @@ int stage_in(tracyhip_ctx* ctx, DevBuf& buf, const void* src, uint64_t bytes, in
   *dev = buf.p;
   return TRACYHIP_OK;
 }
+int stage_out(tracyhip_ctx* ctx, DevBuf& buf, void* user, uint64_t bytes, int mem, bool upload, void** dev) {
+  if (mem == TRACYHIP_MEM_DEVICE) { *dev = user; return TRACYHIP_OK; }
+  HIP_TRY(buf.ensure(bytes ? bytes : 1));
+  if (upload && bytes) HIP_TRY(hipMemcpyAsync(buf.p, user, bytes, hipMemcpyHostToDevice, ctx->stream));
+  *dev = buf.p;
+  return TRACYHIP_OK;
+}
+int unstage(tracyhip_ctx* ctx, void* user, const void* dev, uint64_t bytes, int mem) {
+  if (mem == TRACYHIP_MEM_DEVICE || bytes == 0) return TRACYHIP_OK;
+  HIP_TRY(hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  return TRACYHIP_OK;
+}
 
 int check_params(const tracyhip_params* prm, uint64_t max_mn) {
   if (!prm) return set_error(TRACYHIP_ERR_ARG, "null params");
@@ -560,12 +572,11 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
   if (limit == 0 && trace && stage == DP_PLAIN) {  // only the full-matrix traceback needs a workspace plan
     size_t fr = 0, tot = 0;
     HIP_TRY(hipMemGetInfo(&fr, &tot));
-    limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->d_bits.cap;  // this context's share of what is free now plus what it already holds
+    limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->dev[DB_BITS].cap;  // this context's share of what is free now plus what it already holds
   } else if (limit == 0) {
     limit = ~0ull;
   }
-  HIP_TRY(ctx->h_desc.ensure(sizeof(PairDesc) * (size_t)np));
-  PairDesc* hd = static_cast<PairDesc*>(ctx->h_desc.p);
+  PairDesc* hd; HIP_TRY(ensure_into(ctx->pin[PB_DESC], (size_t)np, hd));
   struct Chunk { uint32_t lo, hi; uint64_t words, scratch; };
   std::vector<Chunk> chunks;
   if (!(trace && stage == DP_PLAIN) && np >= (1u << 16)) {
@@ -628,17 +639,17 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
   hs_plan.reset();  // the planning part ends here
   uint64_t max_words = 0, max_scr = 0;
   for (const Chunk& c : chunks) { max_words = std::max(max_words, c.words); max_scr = std::max(max_scr, c.scratch); }
-  HIP_TRY(ctx->d_desc.ensure(sizeof(PairDesc) * (size_t)np));
-  HIP_TRY(hipMemcpyAsync(ctx->d_desc.p, hd, sizeof(PairDesc) * (size_t)np, hipMemcpyHostToDevice, st));
-  if (trace && stage == DP_PLAIN) HIP_TRY(ctx->d_bits.ensure(max_words * word_bytes));
+  HIP_TRY(ctx->dev[DB_DESC].ensure(sizeof(PairDesc) * (size_t)np));
+  HIP_TRY(hipMemcpyAsync(ctx->dev[DB_DESC].p, hd, sizeof(PairDesc) * (size_t)np, hipMemcpyHostToDevice, st));
+  if (trace && stage == DP_PLAIN) HIP_TRY(ctx->dev[DB_BITS].ensure(max_words * word_bytes));
   if (stage == DP_BAND) {
     uint32_t maxrun = 0;
     for (const Chunk& c : chunks) maxrun = std::max(maxrun, c.hi - c.lo);
-    HIP_TRY(ctx->d_band.ensure((size_t)maxrun * ck->B * 64 * 8));
+    HIP_TRY(ctx->dev[DB_BAND].ensure((size_t)maxrun * ck->B * 64 * 8));
   }
-  if (max_scr) HIP_TRY(ctx->d_scratch.ensure(max_scr * 8));
-  HIP_TRY(ctx->d_err.ensure(kErrBytes));
-  HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, sizeof(int32_t) * kErrWords, st));
+  if (max_scr) HIP_TRY(ctx->dev[DB_SCRATCH].ensure(max_scr * 8));
+  HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
+  HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
   std::vector<std::pair<uint32_t, int>> narrow_launches;  // (tallest problem, K) of every 16-bit launch, for range_verdict
   uint64_t band_cells_credited = 0;                       // m * n of the band launches (replaced by the swept cells after the sync)
   uint64_t max_mn = 0;
@@ -647,11 +658,11 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
   DpArgs a{};
   a.a1 = pb.d_a1;
   a.a2 = pb.d_a2;
-  a.bits = static_cast<uint64_t*>(ctx->d_bits.p);
-  a.bits32 = static_cast<uint32_t*>(ctx->d_bits.p);
-  a.scratch = static_cast<int32_t*>(ctx->d_scratch.p);
+  a.bits = static_cast<uint64_t*>(ctx->dev[DB_BITS].p);
+  a.bits32 = static_cast<uint32_t*>(ctx->dev[DB_BITS].p);
+  a.scratch = static_cast<int32_t*>(ctx->dev[DB_SCRATCH].p);
   a.scores = d_scores;
-  a.err = static_cast<int32_t*>(ctx->d_err.p);
+  a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
   a.match = prm->match; a.mismatch = prm->mismatch; a.go = prm->go; a.ge = prm->ge;
   a.hfree = prm->hfree; a.vfree = prm->vfree;
   a.qlimit = sub_limit(prm);
@@ -663,13 +674,13 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
   if (pb.mode == MODE_QP && pb.d_a2 == ctx->codes() && !ctx->knobs.no_compact) a.special_blocks = ctx->special_blocks();
   if (pb.mode == MODE_CQ && !ctx->knobs.no_compact) a.special_blocks = pb.d_special;
   if (stage == DP_BAND && ctx->timing) {
-    a.swept = reinterpret_cast<unsigned long long*>(static_cast<int32_t*>(ctx->d_err.p) + kErrSweptWord);
+    a.swept = reinterpret_cast<unsigned long long*>(static_cast<int32_t*>(ctx->dev[DB_ERR].p) + kErrSweptWord);
     HIP_TRY(hipMemsetAsync(a.swept, 0, sizeof(unsigned long long), st));
   }
   if (ck) a.ends = ck->d_ends;
   if (ck && stage == DP_CKPT) { a.votes = ck->d_votes; a.vote_nt = ck->vote_nt; }
-  if (ck) { a.ckpt = ck->d_ckpt; a.lastrow = ck->d_lastrow; a.ckpt_B = ck->B; a.band = static_cast<uint64_t*>(ctx->d_band.p); a.ckpt_narrow = ck->narrow ? 1 : 0; }
-  const PairDesc* dd = static_cast<const PairDesc*>(ctx->d_desc.p);
+  if (ck) { a.ckpt = ck->d_ckpt; a.lastrow = ck->d_lastrow; a.ckpt_B = ck->B; a.band = static_cast<uint64_t*>(ctx->dev[DB_BAND].p); a.ckpt_narrow = ck->narrow ? 1 : 0; }
+  const PairDesc* dd = static_cast<const PairDesc*>(ctx->dev[DB_DESC].p);
 
   for (const Chunk& c : chunks) {
     uint32_t j = c.lo;
@@ -756,7 +767,7 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
   }
   int32_t herr[kErrWords] = {};
   unsigned long long h_swept = 0;
-  HIP_TRY(hipMemcpyAsync(herr, ctx->d_err.p, sizeof(herr), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(herr, ctx->dev[DB_ERR].p, sizeof(herr), hipMemcpyDeviceToHost, st));
   if (a.swept) HIP_TRY(hipMemcpyAsync(&h_swept, a.swept, sizeof(h_swept), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx_sync(ctx));
   timing_collect(ctx);
@@ -789,18 +800,18 @@ int build_b16_tables(tracyhip_ctx* ctx, DevBuf& buf, const void* d_a1, bool stri
   }
   hipStream_t st = ctx->stream;
   HIP_TRY(buf.ensure(tot * sizeof(int16_t) + 64));
-  HIP_TRY(ctx->d_b16desc.ensure(sizeof(B16TableDesc) * (size_t)ns));
+  HIP_TRY(ctx->dev[DB_B16DESC].ensure(sizeof(B16TableDesc) * (size_t)ns));
   // (staging blocks of their own, four in rotation: no host wait for an upload, and the pipelines synchronise several times between
   // one build and the fourth after it)
-  PinBuf& stage = ctx->h_b16desc[ctx->b16_round++ & 3u];
+  PinBuf& stage = ctx->pin[PB_B16DESC0 + (ctx->b16_round++ & 3u)];
   HIP_TRY(stage.ensure(sizeof(B16TableDesc) * (size_t)ns));
   std::memcpy(stage.p, desc.data(), sizeof(B16TableDesc) * (size_t)ns);
-  HIP_TRY(hipMemcpyAsync(ctx->d_b16desc.p, stage.p, sizeof(B16TableDesc) * (size_t)ns, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx->d_err.ensure(kErrBytes));
+  HIP_TRY(hipMemcpyAsync(ctx->dev[DB_B16DESC].p, stage.p, sizeof(B16TableDesc) * (size_t)ns, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
   int trc;
   if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, tot * 2))) return trc;
-  HIP_TRY(launch_b16_tables(static_cast<const B16TableDesc*>(ctx->d_b16desc.p), ns, d_a1, strings, prm->match, prm->mismatch, sub_limit(prm), kTagShift,
-                            static_cast<int16_t*>(buf.p), static_cast<int32_t*>(ctx->d_err.p), st));
+  HIP_TRY(launch_b16_tables(static_cast<const B16TableDesc*>(ctx->dev[DB_B16DESC].p), ns, d_a1, strings, prm->match, prm->mismatch, sub_limit(prm), kTagShift,
+                            static_cast<int16_t*>(buf.p), static_cast<int32_t*>(ctx->dev[DB_ERR].p), st));
   if ((trc = timing_end(ctx))) return trc;
   return TRACYHIP_OK;  // (no host wait: the staging block is the tables' own)
 }
@@ -851,15 +862,14 @@ int run_band16(tracyhip_ctx* ctx, Band16Job& job, const tracyhip_params* prm, in
   const uint32_t np = bn[0] + bn[1] + bn[2];
   if (np == 0) { return TRACYHIP_OK; }
   if (limit == 0) {
-    if (job.kind != 0 || total_bytes + 64 <= ctx->d_bits.cap) limit = ~0ull;  // (the words fit what is there: no driver call)
+    if (job.kind != 0 || total_bytes + 64 <= ctx->dev[DB_BITS].cap) limit = ~0ull;  // (the words fit what is there: no driver call)
     else {
       size_t fr = 0, tot = 0;
       HIP_TRY(hipMemGetInfo(&fr, &tot));
-      limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->d_bits.cap;
+      limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->dev[DB_BITS].cap;
     }
   }
-  HIP_TRY(ctx->h_desc.ensure(sizeof(PairDesc) * (size_t)np));
-  PairDesc* hd = static_cast<PairDesc*>(ctx->h_desc.p);
+  PairDesc* hd; HIP_TRY(ensure_into(ctx->pin[PB_DESC], (size_t)np, hd));
   std::vector<int> hk(np);
   struct Chunk { uint32_t lo, hi; uint64_t bytes; };
   std::vector<Chunk> chunks;
@@ -916,16 +926,16 @@ int run_band16(tracyhip_ctx* ctx, Band16Job& job, const tracyhip_params* prm, in
   uint64_t max_bytes = 0;
   for (const Chunk& ch : chunks) max_bytes = std::max(max_bytes, ch.bytes);
   hs_plan.reset();  // the planning part ends here
-  HIP_TRY(ctx->d_desc.ensure(sizeof(PairDesc) * (size_t)np));
-  HIP_TRY(hipMemcpyAsync(ctx->d_desc.p, hd, sizeof(PairDesc) * (size_t)np, hipMemcpyHostToDevice, st));
-  if (job.kind == 0) HIP_TRY(ctx->d_bits.ensure(max_bytes + 64));
-  HIP_TRY(ctx->d_err.ensure(kErrBytes));
+  HIP_TRY(ctx->dev[DB_DESC].ensure(sizeof(PairDesc) * (size_t)np));
+  HIP_TRY(hipMemcpyAsync(ctx->dev[DB_DESC].p, hd, sizeof(PairDesc) * (size_t)np, hipMemcpyHostToDevice, st));
+  if (job.kind == 0) HIP_TRY(ctx->dev[DB_BITS].ensure(max_bytes + 64));
+  HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
   // (the error words are NOT cleared here: the table kernel of this stage may have reported into them; the caller cleared them)
   Band16Args a{};
-  a.qp = job.d_qp; a.codes = job.d_codes; a.bits = static_cast<uint8_t*>(ctx->d_bits.p); a.scores = d_scores; a.ends = d_ends;
-  a.err = static_cast<int32_t*>(ctx->d_err.p); a.go = prm->go; a.ge = prm->ge; a.hfree = prm->hfree;
+  a.qp = job.d_qp; a.codes = job.d_codes; a.bits = static_cast<uint8_t*>(ctx->dev[DB_BITS].p); a.scores = d_scores; a.ends = d_ends;
+  a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p); a.go = prm->go; a.ge = prm->ge; a.hfree = prm->hfree;
   a.ops = d_ops; a.ops_off = d_ops_off; a.ops_len = d_ops_len;
-  const PairDesc* dd = static_cast<const PairDesc*>(ctx->d_desc.p);
+  const PairDesc* dd = static_cast<const PairDesc*>(ctx->dev[DB_DESC].p);
   if (chunks.size() == 1) {
     // the whole job at once: per strip height the pairs [first, first + count) and the sums of the planning pass (no walk over the list)
     uint32_t first[NB];
@@ -1008,7 +1018,7 @@ int run_band16(tracyhip_ctx* ctx, Band16Job& job, const tracyhip_params* prm, in
     }
   }
   int32_t herr[kErrWords] = {};
-  HIP_TRY(hipMemcpyAsync(herr, ctx->d_err.p, sizeof(herr), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(herr, ctx->dev[DB_ERR].p, sizeof(herr), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx_sync(ctx));
   timing_collect(ctx);
   if (herr[0] & 1) return set_error(TRACYHIP_ERR_RANGE, "a query-profile score does not fit the int16 table (profile values too large)");
@@ -1020,12 +1030,11 @@ int run_prefix_keep_cq(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, co
                        const tracyhip_params* prm, int32_t* d_lastrow) {
   hipStream_t st = ctx->stream;
   const size_t np = pre.size();
-  HIP_TRY(ctx->d_err.ensure(kErrBytes));
-  HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, sizeof(int32_t) * kErrWords, st));
+  HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
+  HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
   if (np == 0) return TRACYHIP_OK;
   // (a staging block of its own: run_front fills h_desc while this copy may still be queued)
-  HIP_TRY(ctx->h_pre.ensure(sizeof(PairDesc) * np));
-  PairDesc* hd = static_cast<PairDesc*>(ctx->h_pre.p);
+  PairDesc* hd; HIP_TRY(ensure_into(ctx->pin[PB_PRE], np, hd));
   uint64_t cells[kHostThreads] = {}, bytes[kHostThreads] = {};
   parallel_for((uint32_t)np, [&](uint32_t lo, uint32_t hi, uint32_t tid) {
     uint64_t c = 0, b = 0;
@@ -1036,11 +1045,11 @@ int run_prefix_keep_cq(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, co
     }
     cells[tid] = c; bytes[tid] = b;
   });
-  HIP_TRY(ctx->d_pre.ensure(sizeof(PairDesc) * np));
-  HIP_TRY(hipMemcpyAsync(ctx->d_pre.p, hd, sizeof(PairDesc) * np, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx->dev[DB_PRE].ensure(sizeof(PairDesc) * np));
+  HIP_TRY(hipMemcpyAsync(ctx->dev[DB_PRE].p, hd, sizeof(PairDesc) * np, hipMemcpyHostToDevice, st));
   DpArgs a{};
-  a.pairs = static_cast<const PairDesc*>(ctx->d_pre.p);
-  a.a1 = d_a1; a.a2 = d_a2; a.scores = nullptr; a.err = static_cast<int32_t*>(ctx->d_err.p);
+  a.pairs = static_cast<const PairDesc*>(ctx->dev[DB_PRE].p);
+  a.a1 = d_a1; a.a2 = d_a2; a.scores = nullptr; a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
   a.match = prm->match; a.mismatch = prm->mismatch; a.go = prm->go; a.ge = prm->ge; a.hfree = prm->hfree; a.vfree = prm->vfree;
   a.qlimit = sub_limit(prm);
   a.special_blocks = d_special;
@@ -1064,17 +1073,17 @@ static int run_front_once(tracyhip_ctx* ctx, const std::vector<FrontDesc>& fd, c
   out.ce.assign(nf, 0);
   if (nf == 0) return TRACYHIP_OK;
   const size_t per = sizeof(FrontDesc) + sizeof(PairDesc) + sizeof(FrontOut) + sizeof(int32_t) + 2 * sizeof(uint32_t);
-  HIP_TRY(ctx->d_front.ensure(per * nf + 64));
-  PairDesc* d_pairs = static_cast<PairDesc*>(ctx->d_front.p);
+  HIP_TRY(ctx->dev[DB_FRONT].ensure(per * nf + 64));
+  PairDesc* d_pairs = static_cast<PairDesc*>(ctx->dev[DB_FRONT].p);
   FrontDesc* d_fd = reinterpret_cast<FrontDesc*>(d_pairs + nf);
   FrontOut* d_fo = reinterpret_cast<FrontOut*>(d_fd + nf);
   int32_t* d_fs = reinterpret_cast<int32_t*>(d_fo + nf);
   uint32_t* d_fe = reinterpret_cast<uint32_t*>(d_fs + nf);
-  HIP_TRY(ctx->h_desc.ensure(sizeof(FrontDesc) * nf));
-  std::memcpy(ctx->h_desc.p, fd.data(), sizeof(FrontDesc) * nf);
-  HIP_TRY(hipMemcpyAsync(d_fd, ctx->h_desc.p, sizeof(FrontDesc) * nf, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx->d_err.ensure(kErrBytes));
-  if (!keep_err) HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, sizeof(int32_t) * kErrWords, st));
+  HIP_TRY(ctx->pin[PB_DESC].ensure(sizeof(FrontDesc) * nf));
+  std::memcpy(ctx->pin[PB_DESC].p, fd.data(), sizeof(FrontDesc) * nf);
+  HIP_TRY(hipMemcpyAsync(d_fd, ctx->pin[PB_DESC].p, sizeof(FrontDesc) * nf, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
+  if (!keep_err) HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
   uint32_t max_rest = 0;
   uint64_t cells = 0, bytes = 0;
   {
@@ -1095,7 +1104,7 @@ static int run_front_once(tracyhip_ctx* ctx, const std::vector<FrontDesc>& fd, c
   }
   Band16Args a{};
   a.pairs = d_pairs; a.npairs = (uint32_t)nf; a.qp = d_qp; a.codes = d_codes ? d_codes : ctx->codes(); a.scores = d_fs; a.ends = d_fe;
-  a.err = static_cast<int32_t*>(ctx->d_err.p); a.go = prm->go; a.ge = prm->ge; a.hfree = 1; a.row = d_row;
+  a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p); a.go = prm->go; a.ge = prm->ge; a.hfree = 1; a.row = d_row;
   a.code_cap = (max_rest + 2u * (uint32_t)halfw + 16u) & ~3u;  // front_place_body: a sub-window is at most m_rest + 2 halfw + 2 columns
   if (4ull * a.code_cap + b16_table_bytes(KB) + 32ull * kB16RowCap > 64u * 1024u)
     return set_error(TRACYHIP_ERR_RANGE, "run_front: traces of %u rows do not fit the staging area", max_rest);
@@ -1110,7 +1119,7 @@ static int run_front_once(tracyhip_ctx* ctx, const std::vector<FrontDesc>& fd, c
   HIP_TRY(hipMemcpyAsync(out.fo.data(), d_fo, sizeof(FrontOut) * nf, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(out.score.data(), d_fs, sizeof(int32_t) * nf, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(h_fe.data(), d_fe, sizeof(uint32_t) * 2 * nf, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(herr, ctx->d_err.p, sizeof(herr), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(herr, ctx->dev[DB_ERR].p, sizeof(herr), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx_sync(ctx));
   timing_collect(ctx);
   if (herr[0] & 1) return set_error(TRACYHIP_ERR_RANGE, "a query-profile score does not fit the int16 table (profile values too large)");
@@ -1154,8 +1163,8 @@ int build_problem(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, int mem, bool 
   const uint64_t e1 = seqset_extent(s1), e2 = seqset_extent(s2);
   if ((e1 && !s1.data) || (e2 && !s2.data)) return set_error(TRACYHIP_ERR_ARG, "null sequence data");
   int rc;
-  if ((rc = stage_in(ctx, ctx->d_in1, s1.data, e1 * (pb.a1_profile ? 4 : 1), mem, &pb.d_a1))) return rc;
-  if ((rc = stage_in(ctx, ctx->d_in2, s2.data, e2 * (pb.a2_profile ? 4 : 1), mem, &pb.d_a2))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_IN1], s1.data, e1 * (pb.a1_profile ? 4 : 1), mem, &pb.d_a1))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_IN2], s2.data, e2 * (pb.a2_profile ? 4 : 1), mem, &pb.d_a2))) return rc;
   pb.d_a2_chars = pb.d_a2;
   if (pb.mode == MODE_QP && e2) {  // reference characters -> profile-row codes (align.h:121-136)
     HIP_TRY(ctx->ensure_codes(e2, ctx->stream));
@@ -1172,8 +1181,8 @@ int build_problem(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, int mem, bool 
     std::vector<Row4Desc> hd(n1 + n2);
     for (uint32_t i = 0; i < n1; ++i) hd[i] = Row4Desc{s1.offset[i], s1.length[i], 0};
     for (uint32_t i = 0; i < n2; ++i) hd[n1 + i] = Row4Desc{s2.offset[i], s2.length[i], 0};
-    HIP_TRY(ctx->d_tmp[0].ensure(sizeof(Row4Desc) * hd.size() + hd.size()));
-    Row4Desc* dd = static_cast<Row4Desc*>(ctx->d_tmp[0].p);
+    HIP_TRY(ctx->dev[DB_ROW4DESC].ensure(sizeof(Row4Desc) * hd.size() + hd.size()));
+    Row4Desc* dd = static_cast<Row4Desc*>(ctx->dev[DB_ROW4DESC].p);
     uint8_t* dz = reinterpret_cast<uint8_t*>(dd + hd.size());
     HIP_TRY(hipMemcpyAsync(dd, hd.data(), sizeof(Row4Desc) * hd.size(), hipMemcpyHostToDevice, ctx->stream));
     // column classes of the a2 set for the screened substitution score (one byte per float of the set: indexed like row 0)
@@ -1250,8 +1259,7 @@ int run_ckpt_prefix(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, const
   const size_t nf = full.size(), np = pre.size();
   if (nf + np == 0) return TRACYHIP_OK;
   auto hs1 = std::make_unique<HostScope>("run_ckpt_prefix.plan");
-  HIP_TRY(ctx->h_desc.ensure(sizeof(PairDesc) * (nf + np)));
-  PairDesc* hd = static_cast<PairDesc*>(ctx->h_desc.p);
+  PairDesc* hd; HIP_TRY(ensure_into(ctx->pin[PB_DESC], nf + np, hd));
   // the sweeps by strip height (one launch each; the prefix workgroups ride with the first), longest first inside a launch, as
   // run_dp orders them
   std::vector<uint32_t> order(nf);
@@ -1263,19 +1271,19 @@ int run_ckpt_prefix(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, const
   if (!std::is_sorted(order.begin(), order.end(), before)) std::stable_sort(order.begin(), order.end(), before);
   for (size_t i = 0; i < nf; ++i) hd[i] = full[order[i]];
   for (size_t i = 0; i < np; ++i) hd[nf + i] = pre[i];
-  HIP_TRY(ctx->d_desc.ensure(sizeof(PairDesc) * (nf + np)));
-  HIP_TRY(hipMemcpyAsync(ctx->d_desc.p, hd, sizeof(PairDesc) * (nf + np), hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx->d_err.ensure(kErrBytes));
-  HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, sizeof(int32_t) * kErrWords, st));
+  HIP_TRY(ctx->dev[DB_DESC].ensure(sizeof(PairDesc) * (nf + np)));
+  HIP_TRY(hipMemcpyAsync(ctx->dev[DB_DESC].p, hd, sizeof(PairDesc) * (nf + np), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
+  HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
   hs1.reset();
   DpArgs a{};
-  a.a1 = d_a1; a.a2 = d_a2; a.scores = d_scores; a.err = static_cast<int32_t*>(ctx->d_err.p);
+  a.a1 = d_a1; a.a2 = d_a2; a.scores = d_scores; a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
   a.match = prm->match; a.mismatch = prm->mismatch; a.go = prm->go; a.ge = prm->ge; a.hfree = prm->hfree; a.vfree = prm->vfree;
   a.qlimit = sub_limit(prm);
   if (d_a2 == ctx->codes() && !ctx->knobs.no_compact) a.special_blocks = ctx->special_blocks();
   a.ckpt = ck->d_ckpt; a.lastrow = ck->d_lastrow; a.ckpt_B = ck->B; a.ckpt_narrow = 1;
   DpArgs ap = a;
-  ap.pairs = static_cast<const PairDesc*>(ctx->d_desc.p) + nf;
+  ap.pairs = static_cast<const PairDesc*>(ctx->dev[DB_DESC].p) + nf;
   std::vector<std::pair<uint32_t, int>> narrow_launches;
   uint64_t max_mn = 0;
   int trc;
@@ -1297,7 +1305,7 @@ int run_ckpt_prefix(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, const
     for (size_t i = lo; i < hi; ++i) { maxm = std::max(maxm, hd[i].m); max_mn = std::max<uint64_t>(max_mn, (uint64_t)hd[i].m + hd[i].n); }
     for (size_t i = 0; i < npre; ++i) max_mn = std::max<uint64_t>(max_mn, (uint64_t)hd[nf + i].m + hd[nf + i].n);
     DpArgs af = a;
-    af.pairs = static_cast<const PairDesc*>(ctx->d_desc.p) + lo;
+    af.pairs = static_cast<const PairDesc*>(ctx->dev[DB_DESC].p) + lo;
     if (front_shape) HIP_TRY(launch_gotoh_ckpt_front(K, af, (uint32_t)(hi - lo), ap, npre, st));
     else HIP_TRY(launch_gotoh_ckpt_prefix(K, af, (uint32_t)(hi - lo), ap, npre, st));
     if ((trc = timing_end(ctx))) return trc;
@@ -1307,7 +1315,7 @@ int run_ckpt_prefix(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, const
     lo = hi;
   }
   int32_t herr[kErrWords] = {};
-  HIP_TRY(hipMemcpyAsync(herr, ctx->d_err.p, sizeof(herr), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(herr, ctx->dev[DB_ERR].p, sizeof(herr), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx_sync(ctx));
   timing_collect(ctx);
   return range_verdict(prm, herr, narrow_launches, max_mn, 0);  // kWiden: the pipeline restarts on the int32 kernels
@@ -1558,31 +1566,23 @@ static int dp_entry(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, const tracyh
   if (trace)
     for (uint32_t i = 0; i < np; ++i) ops_total = std::max<uint64_t>(ops_total, ops_offset[i] + pb.desc[i].m + pb.desc[i].n);
   if (mem == TRACYHIP_MEM_HOST) {
-    if (scores) { HIP_TRY(ctx->d_scores.ensure(sizeof(int32_t) * (size_t)np)); d_scores = static_cast<int32_t*>(ctx->d_scores.p); }
+    if (scores) HIP_TRY(ensure_into(ctx->dev[DB_SCORES], np, d_scores));
     if (trace) {
-      HIP_TRY(ctx->d_ops.ensure(ops_total ? ops_total : 1));
-      HIP_TRY(ctx->d_ops_len.ensure(sizeof(uint32_t) * (size_t)np));
-      d_ops = static_cast<uint8_t*>(ctx->d_ops.p);
-      d_len = static_cast<uint32_t*>(ctx->d_ops_len.p);
+      HIP_TRY(ensure_into(ctx->dev[DB_OPS], ops_total ? ops_total : 1, d_ops));
+      HIP_TRY(ensure_into(ctx->dev[DB_OPS_LEN], np, d_len));
     }
   }
   const uint64_t* d_off = nullptr;
   if (trace) {
-    HIP_TRY(ctx->h_off.ensure(sizeof(uint64_t) * (size_t)np));
-    std::memcpy(ctx->h_off.p, ops_offset, sizeof(uint64_t) * (size_t)np);
-    HIP_TRY(ctx->d_ops_off.ensure(sizeof(uint64_t) * (size_t)np));
-    HIP_TRY(hipMemcpyAsync(ctx->d_ops_off.p, ctx->h_off.p, sizeof(uint64_t) * (size_t)np, hipMemcpyHostToDevice, st));
-    d_off = static_cast<const uint64_t*>(ctx->d_ops_off.p);
+    HIP_TRY(ctx->pin[PB_OFF].ensure(sizeof(uint64_t) * (size_t)np));
+    std::memcpy(ctx->pin[PB_OFF].p, ops_offset, sizeof(uint64_t) * (size_t)np);
+    HIP_TRY(ensure_into(ctx->dev[DB_OPS_OFF], np, d_off));
+    HIP_TRY(hipMemcpyAsync(ctx->dev[DB_OPS_OFF].p, ctx->pin[PB_OFF].p, sizeof(uint64_t) * (size_t)np, hipMemcpyHostToDevice, st));
   }
   if ((rc = run_dp(ctx, pb, prm, needle, trace, d_scores, d_ops, d_off, d_len))) return rc;
-  if (mem == TRACYHIP_MEM_HOST) {
-    if (scores) HIP_TRY(hipMemcpyAsync(scores, d_scores, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, st));
-    if (trace) {
-      if (ops_total) HIP_TRY(hipMemcpyAsync(ops, d_ops, ops_total, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(ops_len, d_len, sizeof(uint32_t) * (size_t)np, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(ctx_sync(ctx));
-  }
+  if (scores && (rc = unstage(ctx, scores, d_scores, sizeof(int32_t) * (size_t)np, mem))) return rc;
+  if (trace && ((rc = unstage(ctx, ops, d_ops, ops_total, mem)) || (rc = unstage(ctx, ops_len, d_len, sizeof(uint32_t) * (size_t)np, mem)))) return rc;
+  if (mem == TRACYHIP_MEM_HOST) HIP_TRY(ctx_sync(ctx));
   return TRACYHIP_OK;
 }
 
@@ -1632,8 +1632,8 @@ int tracyhip_gotoh_banded(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, const 
     // (lower case, IUPAC, '-') would mismatch an identical column byte, where gotoh.h compares bytes (align.h:96-101) -- refused here,
     // tracyhip_gotoh_align takes such strings (the pipelines run the same test before they use this form: cq_rows_kernel)
     const uint64_t e1 = seqset_extent(s1);
-    HIP_TRY(ctx->d_err.ensure(kErrBytes));
-    int32_t* d_flag = static_cast<int32_t*>(ctx->d_err.p) + kErrVerdictWord;
+    HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
+    int32_t* d_flag = static_cast<int32_t*>(ctx->dev[DB_ERR].p) + kErrVerdictWord;
     HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int32_t), st));
     if (e1) hipLaunchKernelGGL(cq_rows_check_kernel, dim3((unsigned)((e1 + 255) / 256)), dim3(256), 0, st, static_cast<const uint8_t*>(pb.d_a1), e1, d_flag);
     HIP_TRY(hipGetLastError());
@@ -1644,12 +1644,12 @@ int tracyhip_gotoh_banded(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, const 
   }
   std::vector<B16TableDesc> td(s1.count);
   for (uint32_t i = 0; i < s1.count; ++i) td[i] = B16TableDesc{s1.offset[i], 0, s1.length[i], s1.length[i], 0, 0};
-  HIP_TRY(ctx->d_err.ensure(kErrBytes));
-  HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, sizeof(int32_t) * kErrWords, st));
-  if ((rc = build_b16_tables(ctx, ctx->d_b16tab[0], pb.d_a1, strings, td, prm))) return rc;
+  HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
+  HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
+  if ((rc = build_b16_tables(ctx, ctx->dev[DB_B16TAB_ALLELE0], pb.d_a1, strings, td, prm))) return rc;
   Band16Job job;
   job.kind = origin ? 1 : 0;
-  job.d_qp = static_cast<const int16_t*>(ctx->d_b16tab[0].p);
+  job.d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_ALLELE0].p);
   job.d_codes = d_codes;
   job.desc.resize(np); job.k.resize(np);
   uint64_t ops_total = 0;
@@ -1670,35 +1670,27 @@ int tracyhip_gotoh_banded(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, const 
   uint32_t* d_len = ops_len;
   uint32_t* d_ends = ends;
   if (mem == TRACYHIP_MEM_HOST) {
-    if (scores) { HIP_TRY(ctx->d_scores.ensure(sizeof(int32_t) * (size_t)np)); d_scores = static_cast<int32_t*>(ctx->d_scores.p); }
-    if (origin) { HIP_TRY(ctx->d_ends.ensure(sizeof(uint32_t) * 2 * (size_t)np)); d_ends = static_cast<uint32_t*>(ctx->d_ends.p); }
+    if (scores) HIP_TRY(ensure_into(ctx->dev[DB_SCORES], np, d_scores));
+    if (origin) HIP_TRY(ensure_into(ctx->dev[DB_ENDS], 2 * (size_t)np, d_ends));
     else {
-      HIP_TRY(ctx->d_ops.ensure(ops_total ? ops_total : 1));
-      HIP_TRY(ctx->d_ops_len.ensure(sizeof(uint32_t) * (size_t)np));
-      d_ops = static_cast<uint8_t*>(ctx->d_ops.p);
-      d_len = static_cast<uint32_t*>(ctx->d_ops_len.p);
+      HIP_TRY(ensure_into(ctx->dev[DB_OPS], ops_total ? ops_total : 1, d_ops));
+      HIP_TRY(ensure_into(ctx->dev[DB_OPS_LEN], np, d_len));
     }
   }
   const uint64_t* d_off = nullptr;
   if (!origin) {
-    HIP_TRY(ctx->h_off.ensure(sizeof(uint64_t) * (size_t)np));
-    std::memcpy(ctx->h_off.p, ops_offset, sizeof(uint64_t) * (size_t)np);
-    HIP_TRY(ctx->d_ops_off.ensure(sizeof(uint64_t) * (size_t)np));
-    HIP_TRY(hipMemcpyAsync(ctx->d_ops_off.p, ctx->h_off.p, sizeof(uint64_t) * (size_t)np, hipMemcpyHostToDevice, st));
-    d_off = static_cast<const uint64_t*>(ctx->d_ops_off.p);
+    HIP_TRY(ctx->pin[PB_OFF].ensure(sizeof(uint64_t) * (size_t)np));
+    std::memcpy(ctx->pin[PB_OFF].p, ops_offset, sizeof(uint64_t) * (size_t)np);
+    HIP_TRY(ensure_into(ctx->dev[DB_OPS_OFF], np, d_off));
+    HIP_TRY(hipMemcpyAsync(ctx->dev[DB_OPS_OFF].p, ctx->pin[PB_OFF].p, sizeof(uint64_t) * (size_t)np, hipMemcpyHostToDevice, st));
   }
   rc = run_band16(ctx, job, prm, d_scores, d_ends, d_ops, d_off, d_len);
   if (rc == kWiden) rc = set_error(TRACYHIP_ERR_RANGE, "profile values outside the range of the band kernels");
   if (rc) return rc;
-  if (mem == TRACYHIP_MEM_HOST) {
-    if (scores) HIP_TRY(hipMemcpyAsync(scores, d_scores, sizeof(int32_t) * (size_t)np, hipMemcpyDeviceToHost, st));
-    if (origin) HIP_TRY(hipMemcpyAsync(ends, d_ends, sizeof(uint32_t) * 2 * (size_t)np, hipMemcpyDeviceToHost, st));
-    else {
-      if (ops_total) HIP_TRY(hipMemcpyAsync(ops, d_ops, ops_total, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(ops_len, d_len, sizeof(uint32_t) * (size_t)np, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(ctx_sync(ctx));
-  }
+  if (scores && (rc = unstage(ctx, scores, d_scores, sizeof(int32_t) * (size_t)np, mem))) return rc;
+  if (origin && (rc = unstage(ctx, ends, d_ends, sizeof(uint32_t) * 2 * (size_t)np, mem))) return rc;
+  if (!origin && ((rc = unstage(ctx, ops, d_ops, ops_total, mem)) || (rc = unstage(ctx, ops_len, d_len, sizeof(uint32_t) * (size_t)np, mem)))) return rc;
+  if (mem == TRACYHIP_MEM_HOST) HIP_TRY(ctx_sync(ctx));
   return TRACYHIP_OK;
 }
 
@@ -1731,10 +1723,9 @@ int tracyhip_alignment_rows(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, int 
   const bool p1 = s1.kind == TRACYHIP_SEQ_PROFILE, p2 = s2.kind == TRACYHIP_SEQ_PROFILE;
   hipStream_t st = ctx->stream;
   const void *d_a1, *d_a2;
-  if ((rc = stage_in(ctx, ctx->d_in1, s1.data, seqset_extent(s1) * (p1 ? 4 : 1), mem, &d_a1))) return rc;
-  if ((rc = stage_in(ctx, ctx->d_in2, s2.data, seqset_extent(s2) * (p2 ? 4 : 1), mem, &d_a2))) return rc;
-  HIP_TRY(ctx->h_desc.ensure(sizeof(PairDesc) * (size_t)np));
-  PairDesc* hd = static_cast<PairDesc*>(ctx->h_desc.p);
+  if ((rc = stage_in(ctx, ctx->dev[DB_IN1], s1.data, seqset_extent(s1) * (p1 ? 4 : 1), mem, &d_a1))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_IN2], s2.data, seqset_extent(s2) * (p2 ? 4 : 1), mem, &d_a2))) return rc;
+  PairDesc* hd; HIP_TRY(ensure_into(ctx->pin[PB_DESC], (size_t)np, hd));
   uint64_t total = 0;
   for (uint32_t i = 0; i < np; ++i) {
     const uint32_t i1 = pairs->a1_index ? pairs->a1_index[i] : i;
@@ -1750,30 +1741,30 @@ int tracyhip_alignment_rows(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, int 
       total = std::max<uint64_t>(total, ops_offset[i] + ops_len[i]);
     }
   }
-  HIP_TRY(ctx->d_desc.ensure(sizeof(PairDesc) * (size_t)np));
-  HIP_TRY(hipMemcpyAsync(ctx->d_desc.p, hd, sizeof(PairDesc) * (size_t)np, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx->h_off.ensure(sizeof(uint64_t) * (size_t)np));
-  std::memcpy(ctx->h_off.p, ops_offset, sizeof(uint64_t) * (size_t)np);
-  HIP_TRY(ctx->d_ops_off.ensure(sizeof(uint64_t) * (size_t)np));
-  HIP_TRY(hipMemcpyAsync(ctx->d_ops_off.p, ctx->h_off.p, sizeof(uint64_t) * (size_t)np, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx->dev[DB_DESC].ensure(sizeof(PairDesc) * (size_t)np));
+  HIP_TRY(hipMemcpyAsync(ctx->dev[DB_DESC].p, hd, sizeof(PairDesc) * (size_t)np, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx->pin[PB_OFF].ensure(sizeof(uint64_t) * (size_t)np));
+  std::memcpy(ctx->pin[PB_OFF].p, ops_offset, sizeof(uint64_t) * (size_t)np);
+  HIP_TRY(ctx->dev[DB_OPS_OFF].ensure(sizeof(uint64_t) * (size_t)np));
+  HIP_TRY(hipMemcpyAsync(ctx->dev[DB_OPS_OFF].p, ctx->pin[PB_OFF].p, sizeof(uint64_t) * (size_t)np, hipMemcpyHostToDevice, st));
   RowsArgs ra{};
-  ra.pairs = static_cast<const PairDesc*>(ctx->d_desc.p);
+  ra.pairs = static_cast<const PairDesc*>(ctx->dev[DB_DESC].p);
   ra.a1 = d_a1; ra.a2 = d_a2;
   ra.a1_profile = p1; ra.a2_profile = p2;
   ra.a2_onehot = (p1 && !p2);  // gotoh(profile, _createProfile(string)): row 1 shows consensus chars of the one-hot profile
-  ra.ops_off = static_cast<const uint64_t*>(ctx->d_ops_off.p);
+  ra.ops_off = static_cast<const uint64_t*>(ctx->dev[DB_OPS_OFF].p);
   ra.npairs = np;
   if (mem == TRACYHIP_MEM_HOST) {
-    HIP_TRY(ctx->d_ops.ensure(total ? total : 1));
-    HIP_TRY(ctx->d_ops_len.ensure(sizeof(uint32_t) * (size_t)np));
-    HIP_TRY(ctx->d_rows0.ensure(total ? total : 1));
-    HIP_TRY(ctx->d_rows1.ensure(total ? total : 1));
-    if (total) HIP_TRY(hipMemcpyAsync(ctx->d_ops.p, ops, total, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ctx->d_ops_len.p, ops_len, sizeof(uint32_t) * (size_t)np, hipMemcpyHostToDevice, st));
-    ra.ops = static_cast<const uint8_t*>(ctx->d_ops.p);
-    ra.ops_len = static_cast<const uint32_t*>(ctx->d_ops_len.p);
-    ra.rows0 = static_cast<uint8_t*>(ctx->d_rows0.p);
-    ra.rows1 = static_cast<uint8_t*>(ctx->d_rows1.p);
+    HIP_TRY(ctx->dev[DB_OPS].ensure(total ? total : 1));
+    HIP_TRY(ctx->dev[DB_OPS_LEN].ensure(sizeof(uint32_t) * (size_t)np));
+    HIP_TRY(ctx->dev[DB_ROWS0].ensure(total ? total : 1));
+    HIP_TRY(ctx->dev[DB_ROWS1].ensure(total ? total : 1));
+    if (total) HIP_TRY(hipMemcpyAsync(ctx->dev[DB_OPS].p, ops, total, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->dev[DB_OPS_LEN].p, ops_len, sizeof(uint32_t) * (size_t)np, hipMemcpyHostToDevice, st));
+    ra.ops = static_cast<const uint8_t*>(ctx->dev[DB_OPS].p);
+    ra.ops_len = static_cast<const uint32_t*>(ctx->dev[DB_OPS_LEN].p);
+    ra.rows0 = static_cast<uint8_t*>(ctx->dev[DB_ROWS0].p);
+    ra.rows1 = static_cast<uint8_t*>(ctx->dev[DB_ROWS1].p);
   } else {
     ra.ops = ops; ra.ops_len = ops_len; ra.rows0 = rows0; ra.rows1 = rows1;
   }

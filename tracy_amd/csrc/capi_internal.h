@@ -27,11 +27,126 @@ struct DevBuf {  // grow-only device buffer
   hipError_t ensure(size_t bytes);
   void release();
 };
+// `count` elements of T in a grow-only buffer (DevBuf or PinBuf), and the typed pointer to them
+template <class Buf, class T>
+hipError_t ensure_into(Buf& b, size_t count, T*& p) { const hipError_t e = b.ensure(sizeof(T) * count); p = static_cast<T*>(b.p); return e; }
 struct PinBuf {  // grow-only pinned host buffer (descriptor uploads)
   void* p = nullptr;
   size_t cap = 0;
   hipError_t ensure(size_t bytes);
   void release();
+};
+// Every device buffer a context keeps between calls: tracyhip_ctx::dev[].  One slot, one role; where two roles share a slot the
+// second is written as an alias with the reason why the two are never live in one call (DevBuf::ensure frees what it outgrows).
+enum CtxDev : int {
+  // ---- the generic DP launches (capi.hip run_dp / run_band16 / run_front) and what every pipeline stages through them ----
+  DB_DESC,     // PairDesc / per-trace descriptors: uploaded by run_dp, run_ckpt_prefix, the decompose entry points, consensus_run, assemble_run; read by their kernels
+  DB_BITS,     // traceback words: written by the traceback sweeps of run_dp / run_band16 and the stream-ordered band stages, read by their walks; LDS spill of breakpoint / allelicFraction
+  DB_SCRATCH,  // strip hand-over rows of multi-pass sweeps: written and read inside one run_dp / consensus_run / assemble_run launch
+  DB_IN1,      // first payload of a call staged from the host (stage_in): profiles / a1 / signal / peaks; read by that call's kernels
+  DB_IN2,      // second payload staged from the host: references / a2 / bcpos
+  DB_CODES,    // encoded reference codes with kCodePad on both sides: written by the encode kernels (ensure_codes), read by every MODE_QP / band sweep
+  DB_SCORES,   // staged score results of tracyhip_score / align / band16 and score_final of align_traces (no_stream), host arrays only
+  DB_OPS,      // staged traceback strings of the same calls; the ops uploaded by tracyhip_alignment_rows
+  DB_OPS_OFF,  // offsets of the traceback strings, uploaded per call, read by the walks
+  DB_OPS_LEN,  // staged lengths of the traceback strings
+  DB_ERR,      // kErrBytes of error / verdict words: cleared by the host, set by kernels, read back once per stage
+  DB_ROWS0,    // alignment rows: staged in by the decompose entry points and trim_reference_slice, written by tracyhip_alignment_rows
+  DB_ROWS1,    // the second row of each pair, as DB_ROWS0
+  DB_SPECIAL,  // one byte per 256 code bytes: set by the encoders (ensure_codes), read by the compact 16-bit sweeps
+  DB_ENDS,     // ends of the preliminary alignments + scratch of that stage: OrientRun::prelim; staged ends of tracyhip_band16
+  DB_CKPT,     // wavefront checkpoints: written by the DP_CKPT sweeps of OrientRun, read by its DP_BAND traceback
+  DB_LASTROW,  // last-row values / kept prefix rows: written by the DP_CKPT and prefix sweeps, read by row_m_end, the pruned sweeps and both stream-ordered calls
+  DB_BAND,     // band traceback words of run_dp(DP_BAND); scan state of decompose_kernel_global
+  DB_B16TAB_ALLELE0,  // substitution tables (band16.h) of allele k = 0: build_b16_tables in decompose / tracyhip_band16, read by the band kernels
+  DB_B16TAB_ALLELE1,  // the same for allele k = 1 of decompose (indexed DB_B16TAB_ALLELE0 + k)
+  DB_B16TAB_PROFILE,  // substitution tables of the full trace profiles: align_traces and decompose_traces in both forms
+  DB_B16DESC,  // B16TableDesc list of build_b16_tables, read by b16_table_kernel
+  DB_FRONT,    // descriptors / pairs / results of the pruned orientation sweep: run_front
+  DB_PRE,      // descriptors of its prefix launch over string x code pairs: run_prefix_keep_cq
+  DB_STREAM,   // the Arena of the stream-ordered pipelines (stream.hip): everything they keep between their stages
+  DB_AFTAB,    // allelicFraction grid enumeration, uploaded once (aftab_ready), read by the af kernels
+  DB_AFSCRATCH,  // af_prepare_kernel -> af_search_kernel: tp, class bytes, headers
+  DB_DECLUT,   // decompose_wave.h class table, uploaded once (declut_ready)
+  DB_DECTODO,  // per trace "left to decompose_kernel": written by decompose_wave_kernel, read by decompose_kernel
+  // ---- scratch of the host-planned pipelines and the single-step entry points (one call at a time per context) ----
+  DB_ORIENT_SC2,    // both orientation scores per trace: written by OrientRun's sweeps (align_traces no_stream), read back by fetch_scores
+  DB_PRELIM_OPS,    // ops of the preliminary alignment: written by OrientRun::prelim for AlignRun, read by trim_kernel
+  DB_PRELIM_OFF,    // their offsets: uploaded by AlignRun::orient
+  DB_PRELIM_LEN,    // their lengths: written with the ops, read by trim_kernel
+  DB_PRELIM_SCORE,  // preliminary scores: written by OrientRun::prelim, copied out by AlignRun::results
+  DB_TRIMREC,       // TrimRec per trace: written by the trim kernels of AlignRun::trim and tracyhip_trim_reference_slice, read back at once
+  DB_TRIM_IN,       // reference lengths + strands: uploaded by AlignRun::trim, read by its trim kernel
+  DB_VOTE,          // vote block of OrientRun::vote_block: descriptors up, votes / bounds written by kmer_vote / rowmax_rest, read by the sweeps and fetch_vote_block
+  // build_problem runs in tracyhip_score / tracyhip_align only, never inside a pipeline: no OrientRun is alive beside it
+  DB_ROW4DESC = DB_ORIENT_SC2,  // Row4Desc list of the profile x profile column classes: build_problem
+  // the decompose entry points below are calls of their own; each waits for its stream before it returns
+  DB_BP_STAGE = DB_ORIENT_SC2,         // staged tracyhip_breakpoint array: find_breakpoint (out), find_homozygous_breakpoint (in / out), decompose_alleles (in)
+  DB_HZ_STATUS_STAGE = DB_PRELIM_OPS,  // staged status of find_homozygous_breakpoint
+  DB_PRIMARY_STAGE = DB_PRELIM_OPS,    // staged primary basecalls: decompose_alleles (in / out), secondary_decomposed, allelic_fraction (in); never with DB_HZ_STATUS_STAGE
+  DB_SECONDARY_STAGE = DB_PRELIM_OFF,  // staged secondary basecalls / secdecomp of the same three calls
+  DB_DCP_INDEL_STAGE = DB_PRELIM_LEN,  // staged dcp_indel table of decompose_alleles
+  DB_BC_RESULT_STAGE = DB_PRELIM_LEN,  // staged result of secondary_decomposed (secdecomp) / allelic_fraction (fractions): one of the three per call
+  DB_DCP_ERR_STAGE = DB_PRELIM_SCORE,  // staged dcp_err table of decompose_alleles
+  DB_DECOMP_STATUS_STAGE = DB_TRIMREC, // staged status of decompose_alleles (takes a caller's peak-free basecalls: bc_descs does not run)
+  DB_PEAKS = DB_TRIMREC,               // peak table built by bc_descs for secondary_decomposed / allelic_fraction, read by their one kernel; neither stages a status
+  // AlignRun::trim ends on ctx_sync: its trim kernel has read DB_TRIM_IN before final_alignment writes here
+  DB_FINAL_TOP = DB_TRIM_IN,  // RowMaxDesc + bound tops of the banded final alignments: AlignRun::final_alignment
+  // prelim() runs behind the wait of fetch_scores / sync_verdict, and ck.d_votes is cleared before it: no sweep or copy still reads a vote block
+  DB_BAND_SCORES = DB_VOTE,   // scores of the banded preliminary tracebacks: OrientRun::prelim (tb16_path)
+  // tracyhip_pack_ragged is a call of its own and waits for its stream
+  DB_PACK_SCAN = DB_VOTE,     // scan scratch of pack.hip
+  // ---- tracyhip_decompose_traces (no_stream): DecomposeRun hands these out in order (buf()), fourteen fixed roles first ----
+  DB_PIPE0 = DB_VOTE + 1,
+  DB_PIPE_END = DB_PIPE0 + 64,
+  DB_SEED_TRACES = DB_PIPE_END,  // tracyhip_seed_traces (seed.hip): per-trace inputs up, results of seed_traces_kernel back
+  DB_SEED_CONS,     // consensus staged from the host, read by the seeding kernels
+  DB_SEED_WINDOWS,  // reference windows written by the seeding kernels for a host caller, copied back
+  DB_BCALL_TRACES,   // tracyhip_basecall_traces (basecall.hip): per-trace inputs up, per-trace results back
+  DB_BCALL_SCRATCH,  // working words of basecall_kernel
+  DB_BCALL_SIGNAL,   // signal staged from the host
+  DB_BCALL_POS,      // basecall positions staged from the host
+  DB_BCALL_PAY,      // payload results staged for a host caller
+  // ---- tracyhip_consensus_traces (consensus.hip consensus_run) ----
+  CB_A2,        // both strands of the second profile of each pair: copied in, the reverse written by cons_revcomp_kernel; read by the sweeps
+  CB_SEQS,      // ConsSeq list, uploaded
+  CB_CLASS,     // "row 4 is all zero" byte per profile: written by cons_classify_kernel, read back
+  CB_COLCLASS,  // column classes of both strands: written by cons_classify_kernel, read by the screened score sweeps
+  CB_SC2,       // both strand scores per pair, read back
+  CB_OPS,       // traceback strings: written by the traceback walk, read by consensus_kernel
+  CB_OFF,       // their offsets, uploaded
+  CB_PAIR,      // per-pair results staged for a host caller
+  CB_PAY,       // payload results (consensus, qualities, ...) staged for a host caller
+  CB_FIX,       // ConsFixup list + its counter: written by consensus_kernel, read back
+  CB_PATCH,     // ConsPatch list, uploaded for cons_patch_kernel
+  CB_GQ,        // gq table of consensus.h, uploaded once (cons_gq_ready)
+  // ---- tracyhip_assemble_traces (assemble.hip assemble_run) ----
+  AB_TR,        // both strands of every trace profile: copied in, the reverse written by asm_revcomp_kernel; read by the sweeps
+  AB_SEQS,      // AsmSeq list, uploaded
+  AB_CLASS,     // "row 4 is all zero" byte per trace and reference: written by asm_classify_kernel, read back
+  AB_REFCLASS,  // column classes of the references: written by asm_classify_kernel, read by the screened score sweeps
+  AB_SC2,       // both strand scores per trace, read back
+  AB_OPS,       // traceback string of the current step of every group
+  AB_OFF,       // their offsets, uploaded
+  AB_LEN,       // their lengths, read back per step
+  AB_W0,        // row blocks of the growing alignments, ping
+  AB_W1,        // ... pong
+  AB_SPAN,      // first / last column of every row
+  AB_PROF,      // profile of the alignment so far: written by msa_profile_kernel, read by the next step's sweep
+  AB_PCLASS,    // its column classes
+  AB_STEP,      // AsmStep + AsmFinal per group, uploaded per step
+  AB_PAY,       // results staged for a host caller
+  DB_COUNT
+};
+// pinned host buffers of a context: tracyhip_ctx::pin[]
+enum CtxPin : int {
+  PB_DESC,      // descriptor uploads of run_dp and the batch calls
+  PB_OFF,       // offset uploads (DB_OPS_OFF, CB_OFF, AB_OFF)
+  PB_TMP,       // per-stage uploads of AlignRun and assemble_run
+  PB_RES,       // small result read-backs and the vote block's host side
+  PB_PRE,       // descriptors of run_prefix_keep_cq
+  PB_B16DESC0,  // ring of four B16TableDesc uploads (build_b16_tables, b16_round)
+  PB_COUNT = PB_B16DESC0 + 4
 };
 
 int set_error(int code, const char* fmt, ...);
@@ -79,7 +194,7 @@ void knobs_from_env(CtxKnobs& k);
 bool knobs_set(CtxKnobs& k, const char* name, const char* value);
 std::string knobs_describe(const CtxKnobs& k);
 
-// Reference codes (MODE_QP a2) live in ctx->d_codes with tracyhip::kCodePad spare bytes on both sides: the sweep kernels
+// Reference codes (MODE_QP a2) live in ctx->dev[DB_CODES] with tracyhip::kCodePad spare bytes on both sides: the sweep kernels
 // prefetch the column two steps ahead of every lane without clamping it, so idle lanes read up to 64 + 3 bytes
 // before the first / behind the last base of a sequence (any byte value is a valid table row selector).
 constexpr size_t kCodePad = 128;
@@ -107,30 +222,18 @@ struct tracyhip_ctx {
   hipStream_t stream = nullptr;
   hipStream_t own_stream = nullptr;
   uint64_t ws_limit = 0;
-  tracyhip::DevBuf d_desc, d_bits, d_scratch, d_in1, d_in2, d_codes, d_scores, d_ops, d_ops_off, d_ops_len, d_err,
-      d_rows0, d_rows1;
-  tracyhip::DevBuf d_special;
-  tracyhip::DevBuf d_ends;  // tracy align: ends of the preliminary alignments + scratch of that stage (orient_and_align)
+  tracyhip::DevBuf dev[tracyhip::DB_COUNT];  // every device buffer the context keeps, by role (CtxDev)
+  tracyhip::PinBuf pin[tracyhip::PB_COUNT];
   std::vector<tracyhip::PairDesc> cache_desc;  // descriptor / strip-height vectors of the generic DP entry points, kept between
   std::vector<int> cache_k;                    // calls (an all-pairs list is 36 MB: allocating it afresh costs 6 ms of page faults)
   std::vector<tracyhip::PairDesc> cache_full, cache_pre, cache_b16;  // the same for the orientation stage's sweep / prefix lists and the band jobs
   std::vector<tracyhip::FrontDesc> cache_fd;
   std::vector<int> cache_fullk, cache_b16k;
-  tracyhip::DevBuf d_tmp[8];
-  tracyhip::DevBuf d_pipe[64];
-  tracyhip::DevBuf d_ckpt, d_lastrow, d_band;  // pipeline intermediates (align_traces / decompose)
-  tracyhip::DevBuf d_b16tab[4], d_b16desc;     // substitution tables of the band kernels (band16.h), their descriptors
-  tracyhip::DevBuf d_front;                    // descriptors / pairs / results of the pruned orientation sweep (front.h)
-  tracyhip::DevBuf d_pre;                      // descriptors of its prefix launch over string x code pairs (run_prefix_keep_cq)
   tracyhip::B16Fork b16_fork;                  // side streams of the band stages (stream.hip band_stage), created with the context
   bool b16_fork_ok = false;
-  tracyhip::DevBuf d_stream;                   // everything the stream-ordered pipelines keep on the device between their stages (stream.hip)
-  tracyhip::DevBuf d_seed[3];                  // tracyhip_seed_traces (seed.hip): per-trace inputs / results, staged consensus, staged windows
-  tracyhip::DevBuf d_bcall[5];                 // tracyhip_basecall_traces (basecall.hip): per-trace inputs / results, scratch, staged signal, positions, payload results
-  tracyhip::DevBuf d_cons[12];                 // tracyhip_consensus_traces (consensus.hip): both strands, classes, scores, ops, staged results, fix-ups, gq table
-  bool cons_gq_ready = false;                  // d_cons holds the gq table of consensus.h
-  tracyhip::DevBuf d_asm[16];                  // tracyhip_assemble_traces (assemble.hip): both strands, classes, scores, ops, row blocks, spans, profiles, staged results
+  bool cons_gq_ready = false;                  // CB_GQ holds the gq table of consensus.h
   hipError_t ensure_codes(size_t bytes, hipStream_t st) {
+    tracyhip::DevBuf &d_codes = dev[tracyhip::DB_CODES], &d_special = dev[tracyhip::DB_SPECIAL];
     hipError_t e = d_codes.ensure(bytes + 2 * tracyhip::kCodePad);
     if (e != hipSuccess) return e;
     // pads hold code 0 ('A'): an ordinary column for every kernel
@@ -140,16 +243,12 @@ struct tracyhip_ctx {
     if ((e = d_special.ensure((bytes >> 8) + 2)) != hipSuccess) return e;
     return hipMemsetAsync(d_special.p, 0, (bytes >> 8) + 2, st);
   }
-  uint8_t* special_blocks() const { return static_cast<uint8_t*>(d_special.p); }
-  uint8_t* codes() const { return static_cast<uint8_t*>(d_codes.p) + tracyhip::kCodePad; }
-  tracyhip::DevBuf d_aftab;                    // allelicFraction grid enumeration (trace independent)
+  uint8_t* special_blocks() const { return static_cast<uint8_t*>(dev[tracyhip::DB_SPECIAL].p); }
+  uint8_t* codes() const { return static_cast<uint8_t*>(dev[tracyhip::DB_CODES].p) + tracyhip::kCodePad; }
   bool aftab_ready = false;
   uint64_t ws_cache_budget = 0, ws_cache_held = 0;  // stream.hip workspace_budget: the last answer and what the context held then
   uint32_t ws_cache_share = 0;
-  tracyhip::DevBuf d_afscratch;                // af_prepare_kernel -> af_search_kernel: tp, class bytes, headers
-  tracyhip::DevBuf d_declut, d_dectodo;        // decompose_wave.h: the (primary, secondary) class table; per trace "left to decompose_kernel"
   bool declut_ready = false;
-  tracyhip::PinBuf h_desc, h_off, h_tmp, h_res, h_b16desc[4], h_pre;
   uint32_t b16_round = 0;
   // kernel timing
   struct Pending { int which; hipEvent_t e0, e1; uint64_t cells, bytes; };
@@ -176,31 +275,9 @@ struct tracyhip_ctx {
   };
   AsyncState* async = nullptr;
   void release_all() {
-    tracyhip::DevBuf* all[] = {&d_desc, &d_bits, &d_scratch, &d_in1, &d_in2, &d_codes, &d_scores, &d_ops,
-                               &d_ops_off, &d_ops_len, &d_err, &d_rows0, &d_rows1};
-    for (auto* b : all) b->release();
-    for (auto& b : d_tmp) b.release();
-    for (auto& b : d_pipe) b.release();
-    d_ckpt.release(); d_lastrow.release(); d_band.release(); d_special.release(); d_ends.release();
-    d_aftab.release(); aftab_ready = false;
-    d_declut.release(); d_dectodo.release(); declut_ready = false;
-    d_afscratch.release();
-    for (auto& b : d_b16tab) b.release();
-    d_b16desc.release();
-    d_front.release();
-    d_pre.release();
-    d_stream.release();
-    for (auto& b : d_seed) b.release();
-    for (auto& b : d_bcall) b.release();
-    for (auto& b : d_cons) b.release();
-    for (auto& b : d_asm) b.release();
-    cons_gq_ready = false;
-    h_desc.release();
-    h_off.release();
-    h_tmp.release();
-    h_res.release();
-    h_pre.release();
-    for (auto& b : h_b16desc) b.release();
+    for (auto& b : dev) b.release();
+    for (auto& b : pin) b.release();
+    aftab_ready = declut_ready = cons_gq_ready = false;  // what the freed buffers held
   }
 };
 
@@ -268,7 +345,13 @@ int ctx_begin(tracyhip_ctx* ctx);
 inline hipError_t ctx_sync(tracyhip_ctx* ctx) { ctx->stats.host_syncs += 1; return hipStreamSynchronize(ctx->stream); }
 int async_submit(tracyhip_ctx* ctx, std::function<int()> fn);  // queue a call on the context's worker thread
 int async_drain(tracyhip_ctx* ctx);                           // wait for the queue; returns (and clears) the first error
+// Staging of a caller's array.  MEM_DEVICE: it is used in place.  MEM_HOST: it goes through a grow-only buffer of the context.
+// stage_in: a read-only input, uploaded (zero bytes: the caller's pointer, nothing allocated).
+// stage_out: a result array, optionally uploaded first (zero bytes: one byte allocated, so the pointer is a device pointer);
+// unstage copies it back after the launches.  Nothing here waits for the stream.
 int stage_in(tracyhip_ctx* ctx, DevBuf& buf, const void* src, uint64_t bytes, int mem, const void** dev);
+int stage_out(tracyhip_ctx* ctx, DevBuf& buf, void* user, uint64_t bytes, int mem, bool upload, void** dev);
+int unstage(tracyhip_ctx* ctx, void* user, const void* dev, uint64_t bytes, int mem);
 int check_params(const tracyhip_params* prm, uint64_t max_mn);
 // stage: DP_PLAIN = score-only or full-matrix traceback; DP_CKPT = score-only pass that also writes wavefront
 // checkpoints + last-row values (PairDesc::ckpt_off / lastrow_off set by the caller); DP_BAND = band traceback

@@ -209,16 +209,13 @@ bool check_profiles(const tracyhip_seqset& s, uint32_t np, const char* name) {
   return true;
 }
 
-// the buffers of one call (ctx->d_cons): indices into tracyhip_ctx::d_cons
-enum { CB_A2 = 0, CB_SEQS, CB_CLASS, CB_COLCLASS, CB_SC2, CB_OPS, CB_OFF, CB_PAIR, CB_PAY, CB_FIX, CB_PATCH, CB_GQ };
-
 int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tracyhip_params* prm, int mem,
                   const tracyhip_consensus_result* out, bool wide) {
   const uint32_t np = job->npairs;
   hipStream_t st = ctx->stream;
   const tracyhip_seqset& s1 = job->first;
   const tracyhip_seqset& s2 = job->second;
-  DevBuf* B = ctx->d_cons;
+  DevBuf* const B = ctx->dev;  // indexed by the CB_* roles (capi_internal.h)
 
   // ---- inputs: a1 where the caller has it (or staged), a2 = [second | revcomp(second)] in one buffer ----
   uint64_t e1 = 0, e2 = 0, max_mn = 0, ext = 0;
@@ -231,10 +228,9 @@ int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tr
   int rc;
   if ((rc = check_params(prm, max_mn))) return rc;
   const void* d_a1v = nullptr;
-  if ((rc = stage_in(ctx, ctx->d_in1, s1.data, e1 * 4, mem, &d_a1v))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_IN1], s1.data, e1 * 4, mem, &d_a1v))) return rc;
   const float* d_a1 = static_cast<const float*>(d_a1v);
-  HIP_TRY(B[CB_A2].ensure(2 * e2 * 4));
-  float* d_a2 = static_cast<float*>(B[CB_A2].p);
+  float* d_a2; HIP_TRY(ensure_into(B[CB_A2], 2 * e2, d_a2));
   HIP_TRY(hipMemcpyAsync(d_a2, s2.data, e2 * 4, mem == TRACYHIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
   const uint64_t rev_base = e2;
   {
@@ -252,12 +248,10 @@ int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tr
   hipLaunchKernelGGL(cons_revcomp_kernel, dim3(np), dim3(256), 0, st, d_seqs + np, d_a2, d_a2, rev_base);
   HIP_TRY(hipGetLastError());
   // classes: row 4 of first, second (revcomp has the same row 4), column classes of both strands
-  HIP_TRY(B[CB_CLASS].ensure(2 * (size_t)np));
-  uint8_t* d_zero = static_cast<uint8_t*>(B[CB_CLASS].p);
+  uint8_t* d_zero; HIP_TRY(ensure_into(B[CB_CLASS], 2 * (size_t)np, d_zero));
   uint8_t* d_colclass = nullptr;
   if (!ctx->knobs.no_screen) {
-    HIP_TRY(B[CB_COLCLASS].ensure(2 * e2));
-    d_colclass = static_cast<uint8_t*>(B[CB_COLCLASS].p);
+    HIP_TRY(ensure_into(B[CB_COLCLASS], 2 * e2, d_colclass));
   }
   hipLaunchKernelGGL(cons_classify_kernel, dim3(np), dim3(64), 0, st, d_seqs, d_a1, (uint64_t)0, d_zero, (uint8_t*)nullptr);
   hipLaunchKernelGGL(cons_classify_kernel, dim3(np), dim3(64), 0, st, d_seqs + np, (const float*)d_a2, (uint64_t)0, d_zero + np, d_colclass);
@@ -294,11 +288,10 @@ int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tr
   if (limit == 0) {
     size_t fr = 0, tot = 0;
     HIP_TRY(hipMemGetInfo(&fr, &tot));
-    limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->d_bits.cap + ctx->d_scratch.cap;
+    limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->dev[DB_BITS].cap + ctx->dev[DB_SCRATCH].cap;
   }
   // descriptors: score pairs (2 per pair, in chunk order) then traceback pairs (1 per pair)
-  HIP_TRY(ctx->h_desc.ensure(sizeof(PairDesc) * 3 * (size_t)np));
-  PairDesc* hsd = static_cast<PairDesc*>(ctx->h_desc.p);
+  PairDesc* hsd; HIP_TRY(ensure_into(ctx->pin[PB_DESC], 3 * (size_t)np, hsd));
   PairDesc* htd = hsd + 2 * (size_t)np;
   struct Chunk { uint32_t lo, hi; uint64_t words, scratch; };
   std::vector<Chunk> chunks;
@@ -346,23 +339,19 @@ int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tr
   }
   uint64_t max_words = 0, max_scr = 0;
   for (const Chunk& c : chunks) { max_words = std::max(max_words, c.words); max_scr = std::max(max_scr, c.scratch); }
-  HIP_TRY(ctx->d_desc.ensure(sizeof(PairDesc) * 3 * (size_t)np));
-  HIP_TRY(hipMemcpyAsync(ctx->d_desc.p, hsd, sizeof(PairDesc) * 3 * (size_t)np, hipMemcpyHostToDevice, st));
-  PairDesc* dsd = static_cast<PairDesc*>(ctx->d_desc.p);
+  PairDesc* dsd; HIP_TRY(ensure_into(ctx->dev[DB_DESC], 3 * (size_t)np, dsd));
+  HIP_TRY(hipMemcpyAsync(dsd, hsd, sizeof(PairDesc) * 3 * (size_t)np, hipMemcpyHostToDevice, st));
   PairDesc* dtd = dsd + 2 * (size_t)np;
-  HIP_TRY(ctx->d_bits.ensure(std::max<uint64_t>(max_words * 8, 8)));
-  if (max_scr) HIP_TRY(ctx->d_scratch.ensure(max_scr * 8));
-  HIP_TRY(ctx->d_err.ensure(kErrBytes));
-  HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, sizeof(int32_t) * kErrWords, st));
-  HIP_TRY(B[CB_SC2].ensure(sizeof(int32_t) * 2 * (size_t)np));
-  int32_t* d_sc2 = static_cast<int32_t*>(B[CB_SC2].p);
-  HIP_TRY(B[CB_OPS].ensure(std::max<uint64_t>(ext, 1)));
-  uint8_t* d_ops = static_cast<uint8_t*>(B[CB_OPS].p);
-  HIP_TRY(B[CB_OFF].ensure(sizeof(uint64_t) * (size_t)np));
-  HIP_TRY(ctx->h_off.ensure(sizeof(uint64_t) * (size_t)np));
-  std::memcpy(ctx->h_off.p, out->offset, sizeof(uint64_t) * (size_t)np);
-  HIP_TRY(hipMemcpyAsync(B[CB_OFF].p, ctx->h_off.p, sizeof(uint64_t) * (size_t)np, hipMemcpyHostToDevice, st));
-  const uint64_t* d_off = static_cast<const uint64_t*>(B[CB_OFF].p);
+  HIP_TRY(ctx->dev[DB_BITS].ensure(std::max<uint64_t>(max_words * 8, 8)));
+  if (max_scr) HIP_TRY(ctx->dev[DB_SCRATCH].ensure(max_scr * 8));
+  HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
+  HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
+  int32_t* d_sc2; HIP_TRY(ensure_into(B[CB_SC2], 2 * (size_t)np, d_sc2));
+  uint8_t* d_ops; HIP_TRY(ensure_into(B[CB_OPS], std::max<uint64_t>(ext, 1), d_ops));
+  uint64_t* d_off; HIP_TRY(ensure_into(B[CB_OFF], np, d_off));
+  HIP_TRY(ctx->pin[PB_OFF].ensure(sizeof(uint64_t) * (size_t)np));
+  std::memcpy(ctx->pin[PB_OFF].p, out->offset, sizeof(uint64_t) * (size_t)np);
+  HIP_TRY(hipMemcpyAsync(d_off, ctx->pin[PB_OFF].p, sizeof(uint64_t) * (size_t)np, hipMemcpyHostToDevice, st));
 
   // per-pair results and payloads: the caller's (MEM_DEVICE) or staged (MEM_HOST)
   int32_t *o_sf = out->score_fwd, *o_sr = out->score_rev, *o_score = out->score, *o_status = out->status;
@@ -372,14 +361,12 @@ int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tr
   uint16_t* o_qual = out->qual;
   if (mem == TRACYHIP_MEM_HOST) {
     const size_t per = 4 * (size_t)np;
-    HIP_TRY(B[CB_PAIR].ensure(9 * per));
-    uint8_t* p = static_cast<uint8_t*>(B[CB_PAIR].p);
+    uint8_t* p; HIP_TRY(ensure_into(B[CB_PAIR], 9 * per, p));
     o_sf = reinterpret_cast<int32_t*>(p); o_sr = reinterpret_cast<int32_t*>(p + per); o_score = reinterpret_cast<int32_t*>(p + 2 * per);
     o_status = reinterpret_cast<int32_t*>(p + 3 * per); o_na = reinterpret_cast<uint32_t*>(p + 4 * per); o_nm = reinterpret_cast<uint32_t*>(p + 5 * per);
     o_len = reinterpret_cast<uint32_t*>(p + 6 * per); o_clen = reinterpret_cast<uint32_t*>(p + 7 * per); o_fwd = p + 8 * per;
     const uint64_t ea = (ext + 255) & ~255ull;  // (aligned sub-buffers)
-    HIP_TRY(B[CB_PAY].ensure(5 * std::max<uint64_t>(ea, 256)));
-    uint8_t* q = static_cast<uint8_t*>(B[CB_PAY].p);
+    uint8_t* q; HIP_TRY(ensure_into(B[CB_PAY], 5 * std::max<uint64_t>(ea, 256), q));
     o_r0 = q; o_r1 = q + ea; o_cons = q + 2 * ea; o_qual = reinterpret_cast<uint16_t*>(q + 3 * ea);
   }
   const uint32_t fix_cap = std::max<uint32_t>(65536u, np * 4u);
@@ -391,10 +378,10 @@ int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tr
   DpArgs a{};
   a.a1 = d_a1;
   a.a2 = d_a2;
-  a.bits = static_cast<uint64_t*>(ctx->d_bits.p);
-  a.bits32 = static_cast<uint32_t*>(ctx->d_bits.p);
-  a.scratch = static_cast<int32_t*>(ctx->d_scratch.p);
-  a.err = static_cast<int32_t*>(ctx->d_err.p);
+  a.bits = static_cast<uint64_t*>(ctx->dev[DB_BITS].p);
+  a.bits32 = static_cast<uint32_t*>(ctx->dev[DB_BITS].p);
+  a.scratch = static_cast<int32_t*>(ctx->dev[DB_SCRATCH].p);
+  a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
   a.match = prm->match; a.mismatch = prm->mismatch; a.go = prm->go; a.ge = prm->ge;
   a.hfree = prm->hfree; a.vfree = prm->vfree;
   a.qlimit = sub_limit(prm);
@@ -484,7 +471,7 @@ int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tr
   // ---- one synchronisation: error words, fix-up count, results (MEM_HOST) ----
   int32_t herr[kErrWords] = {};
   uint32_t nfix = 0;
-  HIP_TRY(hipMemcpyAsync(herr, ctx->d_err.p, sizeof(herr), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(herr, ctx->dev[DB_ERR].p, sizeof(herr), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(&nfix, d_nfix, sizeof(nfix), hipMemcpyDeviceToHost, st));
   if (mem == TRACYHIP_MEM_HOST) {
     const size_t n4 = 4 * (size_t)np;

@@ -869,20 +869,6 @@ int to_device(tracyhip_ctx* ctx, DevBuf& b, const std::vector<T>& v, const T** o
   return TRACYHIP_OK;
 }
 
-// stage an in/out or output payload: DEVICE -> use as is; HOST -> device buffer (+ optional upload)
-int stage_io(tracyhip_ctx* ctx, DevBuf& b, void* user, uint64_t bytes, int mem, bool upload, void** dev) {
-  if (mem == TRACYHIP_MEM_DEVICE) { *dev = user; return TRACYHIP_OK; }
-  HIP_TRY(b.ensure(bytes ? bytes : 1));
-  if (upload && bytes) HIP_TRY(hipMemcpyAsync(b.p, user, bytes, hipMemcpyHostToDevice, ctx->stream));
-  *dev = b.p;
-  return TRACYHIP_OK;
-}
-int unstage(tracyhip_ctx* ctx, void* user, const void* dev, uint64_t bytes, int mem) {
-  if (mem == TRACYHIP_MEM_DEVICE || bytes == 0) return TRACYHIP_OK;
-  HIP_TRY(hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  return TRACYHIP_OK;
-}
-
 uint64_t extent64(const uint64_t* off, const uint32_t* len, uint32_t n, uint64_t mult = 1) {
   uint64_t e = 0;
   for (uint32_t i = 0; i < n; ++i) e = std::max<uint64_t>(e, off[i] + mult * len[i]);
@@ -899,8 +885,8 @@ int launch_breakpoint(tracyhip_ctx* ctx, const BpDesc* d_desc, uint32_t n, uint3
   const bool global = lds > kLdsStageLimit;  // staging of a profile too long for LDS: a slice of a global scratch buffer per profile
   { int trc_ = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 0); if (trc_) return trc_; }
   if (global) {
-    HIP_TRY(ctx->d_bits.ensure(lds * (size_t)n));
-    hipLaunchKernelGGL(breakpoint_kernel<true>, dim3(n), dim3(64), 0, ctx->stream, d_desc, d_prof, d_out, static_cast<char*>(ctx->d_bits.p), lds);
+    HIP_TRY(ctx->dev[DB_BITS].ensure(lds * (size_t)n));
+    hipLaunchKernelGGL(breakpoint_kernel<true>, dim3(n), dim3(64), 0, ctx->stream, d_desc, d_prof, d_out, static_cast<char*>(ctx->dev[DB_BITS].p), lds);
   } else {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(breakpoint_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(breakpoint_kernel<false>, dim3(n), dim3(64), lds, ctx->stream, d_desc, d_prof, d_out, nullptr, (size_t)0);
@@ -948,18 +934,18 @@ int launch_decompose(tracyhip_ctx* ctx, const DecompArgs& a, const BreakpointOut
   if (wave) {
     if (!ctx->declut_ready) {
       static const std::vector<uint8_t> lut = [] { std::vector<uint8_t> t(kLutBytes); decomp_lut_build(t.data()); return t; }();
-      HIP_TRY(ctx->d_declut.ensure(kLutBytes));
-      HIP_TRY(hipMemcpyAsync(ctx->d_declut.p, lut.data(), kLutBytes, hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx->dev[DB_DECLUT].ensure(kLutBytes));
+      HIP_TRY(hipMemcpyAsync(ctx->dev[DB_DECLUT].p, lut.data(), kLutBytes, hipMemcpyHostToDevice, ctx->stream));
       ctx->declut_ready = true;
     }
-    HIP_TRY(ctx->d_dectodo.ensure(sizeof(uint32_t) * (size_t)a.ntraces + 8 + sizeof(unsigned long long) * kDecompWaveStages * kDecompWaveClockRows));
+    HIP_TRY(ctx->dev[DB_DECTODO].ensure(sizeof(uint32_t) * (size_t)a.ntraces + 8 + sizeof(unsigned long long) * kDecompWaveStages * kDecompWaveClockRows));
     wa.a = a;
     wa.bps = d_bps;
-    wa.lut = static_cast<const uint8_t*>(ctx->d_declut.p);
-    wa.todo = static_cast<uint32_t*>(ctx->d_dectodo.p);
+    wa.lut = static_cast<const uint8_t*>(ctx->dev[DB_DECLUT].p);
+    wa.todo = static_cast<uint32_t*>(ctx->dev[DB_DECTODO].p);
     rest.only = wa.todo;
 #ifdef TRACY_PHASE_CLOCKS
-    wa.clocks = reinterpret_cast<unsigned long long*>(static_cast<char*>(ctx->d_dectodo.p) + ((sizeof(uint32_t) * (size_t)a.ntraces + 7) & ~(size_t)7));
+    wa.clocks = reinterpret_cast<unsigned long long*>(static_cast<char*>(ctx->dev[DB_DECTODO].p) + ((sizeof(uint32_t) * (size_t)a.ntraces + 7) & ~(size_t)7));
     HIP_TRY(hipMemsetAsync(wa.clocks, 0, sizeof(unsigned long long) * kDecompWaveStages * kDecompWaveClockRows, ctx->stream));
 #endif
   }
@@ -985,8 +971,8 @@ int launch_decompose(tracyhip_ctx* ctx, const DecompArgs& a, const BreakpointOut
   if (global) {
     // scan state in global memory: up to 512 workgroups in flight, each with a slot of its own (0.7 GB)
     const uint32_t slots = std::min<uint32_t>(a.ntraces, 512u);
-    HIP_TRY(ctx->d_band.ensure((size_t)slots * sizeof(DecompSharedT<kMaxIndelGlobal>)));
-    hipLaunchKernelGGL(decompose_kernel_global, dim3(slots), dim3(64), 0, ctx->stream, a_, d_bps, static_cast<char*>(ctx->d_band.p));
+    HIP_TRY(ctx->dev[DB_BAND].ensure((size_t)slots * sizeof(DecompSharedT<kMaxIndelGlobal>)));
+    hipLaunchKernelGGL(decompose_kernel_global, dim3(slots), dim3(64), 0, ctx->stream, a_, d_bps, static_cast<char*>(ctx->dev[DB_BAND].p));
   } else if (large) {
     const size_t lds = sizeof(DecompSharedT<kMaxIndelLarge>);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(decompose_kernel<kMaxIndelLarge>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1050,17 +1036,16 @@ static int ensure_af_grid(tracyhip_ctx* ctx, AfGrid& g) {
   }();
   const size_t pair_bytes = (tab.size() * sizeof(uint32_t) + 7) & ~(size_t)7, vals_bytes = vals.size() * sizeof(double);
   if (!ctx->aftab_ready) {
-    HIP_TRY(ctx->d_aftab.ensure(2 * pair_bytes + vals_bytes));
-    char* base = static_cast<char*>(ctx->d_aftab.p);
+    char* base; HIP_TRY(ensure_into(ctx->dev[DB_AFTAB], 2 * pair_bytes + vals_bytes, base));
     HIP_TRY(hipMemcpyAsync(base, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(base + pair_bytes, vals.data(), vals_bytes, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(base + pair_bytes + vals_bytes, tab8.data(), tab8.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     ctx->aftab_ready = true;
   }
   g.npairs = (uint32_t)tab.size();
-  g.pair = static_cast<const uint32_t*>(ctx->d_aftab.p);
-  g.vals = reinterpret_cast<const double*>(static_cast<const char*>(ctx->d_aftab.p) + pair_bytes);
-  g.pair8 = reinterpret_cast<const uint32_t*>(static_cast<const char*>(ctx->d_aftab.p) + pair_bytes + vals_bytes);
+  g.pair = static_cast<const uint32_t*>(ctx->dev[DB_AFTAB].p);
+  g.vals = reinterpret_cast<const double*>(static_cast<const char*>(ctx->dev[DB_AFTAB].p) + pair_bytes);
+  g.pair8 = reinterpret_cast<const uint32_t*>(static_cast<const char*>(ctx->dev[DB_AFTAB].p) + pair_bytes + vals_bytes);
   return TRACYHIP_OK;
 }
 
@@ -1078,9 +1063,9 @@ int launch_allelic_fraction(tracyhip_ctx* ctx, const BcDesc* d_desc, uint32_t n,
   AfScratch sc{};
   if (split) {
     const size_t tp_bytes = (size_t)bext * 32, cls_bytes = ((size_t)bext * 4 + 63) & ~(size_t)63, hdr_bytes = sizeof(AfHeader) * (size_t)n;
-    if (ctx->d_afscratch.ensure(tp_bytes + cls_bytes + hdr_bytes) != hipSuccess) { (void)hipGetLastError(); split = false; }
+    if (ctx->dev[DB_AFSCRATCH].ensure(tp_bytes + cls_bytes + hdr_bytes) != hipSuccess) { (void)hipGetLastError(); split = false; }
     else {
-      char* p = static_cast<char*>(ctx->d_afscratch.p);
+      char* p = static_cast<char*>(ctx->dev[DB_AFSCRATCH].p);
       sc.tp = reinterpret_cast<double*>(p);
       sc.cls = reinterpret_cast<uint8_t*>(p + tp_bytes);
       sc.hdr = reinterpret_cast<AfHeader*>(p + tp_bytes + cls_bytes);
@@ -1091,9 +1076,9 @@ int launch_allelic_fraction(tracyhip_ctx* ctx, const BcDesc* d_desc, uint32_t n,
     hipLaunchKernelGGL(af_prepare_kernel, dim3(n), dim3(64), 0, ctx->stream, d_desc, d_peaks, d_pri, d_sec, trim_left, trim_right, sc, d_out);
     hipLaunchKernelGGL(af_search_kernel, dim3(n), dim3(64), 0, ctx->stream, d_desc, sc.tp, sc.cls, sc.hdr, grid, d_out);
   } else if (global) {
-    HIP_TRY(ctx->d_bits.ensure(lds * (size_t)n));
+    HIP_TRY(ctx->dev[DB_BITS].ensure(lds * (size_t)n));
     hipLaunchKernelGGL(allelic_fraction_kernel<true>, dim3(n), dim3(AF_THREADS), 0, ctx->stream, d_desc, d_peaks, d_pri, d_sec, trim_left,
-                       trim_right, grid, d_out, static_cast<char*>(ctx->d_bits.p), lds);
+                       trim_right, grid, d_out, static_cast<char*>(ctx->dev[DB_BITS].p), lds);
   } else {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(allelic_fraction_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(allelic_fraction_kernel<false>, dim3(n), dim3(AF_THREADS), lds, ctx->stream, d_desc, d_peaks, d_pri, d_sec, trim_left,
@@ -1118,14 +1103,14 @@ int tracyhip_find_breakpoint(tracyhip_ctx* ctx, const tracyhip_seqset* profiles,
   static_assert(sizeof(tracyhip_breakpoint) == sizeof(BreakpointOut), "layout");
   hipStream_t st = ctx->stream;
   const void* d_prof;
-  if ((rc = stage_in(ctx, ctx->d_in1, profiles->data, seqset_extent(*profiles) * 4, mem, &d_prof))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_IN1], profiles->data, seqset_extent(*profiles) * 4, mem, &d_prof))) return rc;
   std::vector<BpDesc> hd(n);
   uint32_t maxcol = 0;
   for (uint32_t i = 0; i < n; ++i) { hd[i] = BpDesc{profiles->offset[i], profiles->length[i], profiles->length[i]}; maxcol = std::max(maxcol, profiles->length[i]); }
   const BpDesc* dd;
-  if ((rc = to_device(ctx, ctx->d_desc, hd, &dd))) return rc;
+  if ((rc = to_device(ctx, ctx->dev[DB_DESC], hd, &dd))) return rc;
   void* d_out;
-  if ((rc = stage_io(ctx, ctx->d_tmp[0], out, sizeof(BreakpointOut) * (size_t)n, mem, false, &d_out))) return rc;
+  if ((rc = stage_out(ctx, ctx->dev[DB_BP_STAGE], out, sizeof(BreakpointOut) * (size_t)n, mem, false, &d_out))) return rc;
   if ((rc = launch_breakpoint(ctx, dd, n, maxcol, static_cast<const float*>(d_prof), static_cast<BreakpointOut*>(d_out)))) return rc;
   if ((rc = unstage(ctx, out, d_out, sizeof(BreakpointOut) * (size_t)n, mem))) return rc;
   HIP_TRY(hipStreamSynchronize(st));
@@ -1142,15 +1127,15 @@ int tracyhip_find_homozygous_breakpoint(tracyhip_ctx* ctx, uint32_t ntraces, con
   hipStream_t st = ctx->stream;
   const uint64_t ext = extent64(rows_offset, rows_len, ntraces);
   const void *d_r0, *d_r1;
-  if ((rc = stage_in(ctx, ctx->d_rows0, rows0, ext, mem, &d_r0))) return rc;
-  if ((rc = stage_in(ctx, ctx->d_rows1, rows1, ext, mem, &d_r1))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_ROWS0], rows0, ext, mem, &d_r0))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_ROWS1], rows1, ext, mem, &d_r1))) return rc;
   std::vector<RowsDesc> hd(ntraces);
   for (uint32_t i = 0; i < ntraces; ++i) hd[i] = RowsDesc{rows_offset[i], rows_len[i], 0};
   const RowsDesc* dd;
-  if ((rc = to_device(ctx, ctx->d_desc, hd, &dd))) return rc;
+  if ((rc = to_device(ctx, ctx->dev[DB_DESC], hd, &dd))) return rc;
   void *d_bp, *d_stat;
-  if ((rc = stage_io(ctx, ctx->d_tmp[0], bps, sizeof(BreakpointOut) * (size_t)ntraces, mem, true, &d_bp))) return rc;
-  if ((rc = stage_io(ctx, ctx->d_tmp[1], status, sizeof(int32_t) * (size_t)ntraces, mem, false, &d_stat))) return rc;
+  if ((rc = stage_out(ctx, ctx->dev[DB_BP_STAGE], bps, sizeof(BreakpointOut) * (size_t)ntraces, mem, true, &d_bp))) return rc;
+  if ((rc = stage_out(ctx, ctx->dev[DB_HZ_STATUS_STAGE], status, sizeof(int32_t) * (size_t)ntraces, mem, false, &d_stat))) return rc;
   if ((rc = launch_homozygous(ctx, dd, static_cast<const uint8_t*>(d_r0), static_cast<const uint8_t*>(d_r1), ntraces,
                               static_cast<BreakpointOut*>(d_bp), static_cast<int32_t*>(d_stat))))
     return rc;
@@ -1186,21 +1171,21 @@ int tracyhip_decompose_alleles(tracyhip_ctx* ctx, const tracyhip_basecalls* bc, 
     dext = std::max<uint64_t>(dext, dcp_offset[i] + 2ull * prm->maxindel + 2);
   }
   const void *d_r0, *d_r1, *d_bp;
-  if ((rc = stage_in(ctx, ctx->d_rows0, rows0, rext, mem, &d_r0))) return rc;
-  if ((rc = stage_in(ctx, ctx->d_rows1, rows1, rext, mem, &d_r1))) return rc;
-  if ((rc = stage_in(ctx, ctx->d_tmp[0], bps, sizeof(BreakpointOut) * (size_t)n, mem, &d_bp))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_ROWS0], rows0, rext, mem, &d_r0))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_ROWS1], rows1, rext, mem, &d_r1))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_BP_STAGE], bps, sizeof(BreakpointOut) * (size_t)n, mem, &d_bp))) return rc;
   void *d_pri, *d_sec, *d_di, *d_de, *d_stat;
-  if ((rc = stage_io(ctx, ctx->d_tmp[1], bc->primary, bext, mem, true, &d_pri))) return rc;
-  if ((rc = stage_io(ctx, ctx->d_tmp[2], bc->secondary, bext, mem, true, &d_sec))) return rc;
-  if ((rc = stage_io(ctx, ctx->d_tmp[3], dcp_indel, dext * 4, mem, false, &d_di))) return rc;
-  if ((rc = stage_io(ctx, ctx->d_tmp[4], dcp_err, dext * 4, mem, false, &d_de))) return rc;
+  if ((rc = stage_out(ctx, ctx->dev[DB_PRIMARY_STAGE], bc->primary, bext, mem, true, &d_pri))) return rc;
+  if ((rc = stage_out(ctx, ctx->dev[DB_SECONDARY_STAGE], bc->secondary, bext, mem, true, &d_sec))) return rc;
+  if ((rc = stage_out(ctx, ctx->dev[DB_DCP_INDEL_STAGE], dcp_indel, dext * 4, mem, false, &d_di))) return rc;
+  if ((rc = stage_out(ctx, ctx->dev[DB_DCP_ERR_STAGE], dcp_err, dext * 4, mem, false, &d_de))) return rc;
   if (mem == TRACYHIP_MEM_HOST) {  // (staged tables go back whole: the entries behind dcp_n are zero, not what the buffer held)
     HIP_TRY(hipMemsetAsync(d_di, 0, dext * 4, ctx->stream));
     HIP_TRY(hipMemsetAsync(d_de, 0, dext * 4, ctx->stream));
   }
-  if ((rc = stage_io(ctx, ctx->d_tmp[5], status, sizeof(DecompOut) * (size_t)n, mem, false, &d_stat))) return rc;
+  if ((rc = stage_out(ctx, ctx->dev[DB_DECOMP_STATUS_STAGE], status, sizeof(DecompOut) * (size_t)n, mem, false, &d_stat))) return rc;
   const DecompDesc* dd;
-  if ((rc = to_device(ctx, ctx->d_desc, hd, &dd))) return rc;
+  if ((rc = to_device(ctx, ctx->dev[DB_DESC], hd, &dd))) return rc;
   DecompArgs a{};
   a.desc = dd;
   a.rows0 = static_cast<const uint8_t*>(d_r0);
@@ -1238,19 +1223,20 @@ static int bc_descs(tracyhip_ctx* ctx, const tracyhip_basecalls* bc, int mem, co
   }
   *bext = extent64(bc->bc_offset, bc->bc_len, n);
   int rc;
-  if ((rc = to_device(ctx, ctx->d_desc, hd, dd))) return rc;
+  if ((rc = to_device(ctx, ctx->dev[DB_DESC], hd, dd))) return rc;
   const void* p = nullptr;
   if (bc->peaks) {
-    if ((rc = stage_in(ctx, ctx->d_in1, bc->peaks, *bext * 16, mem, &p))) return rc;
+    if ((rc = stage_in(ctx, ctx->dev[DB_IN1], bc->peaks, *bext * 16, mem, &p))) return rc;
     *d_peaks = static_cast<const int32_t*>(p);
     return TRACYHIP_OK;
   }
   const void *d_sig, *d_pos;
-  if ((rc = stage_in(ctx, ctx->d_in1, bc->signal, sext * 4, mem, &d_sig))) return rc;
-  if ((rc = stage_in(ctx, ctx->d_in2, bc->bcpos, *bext * 4, mem, &d_pos))) return rc;
-  HIP_TRY(ctx->d_tmp[5].ensure(*bext * 16 + 16));
-  if ((rc = launch_peaks(ctx, *dd, n, maxbc, static_cast<const int32_t*>(d_sig), static_cast<const int32_t*>(d_pos), static_cast<int32_t*>(ctx->d_tmp[5].p)))) return rc;
-  *d_peaks = static_cast<const int32_t*>(ctx->d_tmp[5].p);
+  if ((rc = stage_in(ctx, ctx->dev[DB_IN1], bc->signal, sext * 4, mem, &d_sig))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_IN2], bc->bcpos, *bext * 4, mem, &d_pos))) return rc;
+  int32_t* peaks;
+  HIP_TRY(ensure_into(ctx->dev[DB_PEAKS], *bext * 4 + 4, peaks));
+  if ((rc = launch_peaks(ctx, *dd, n, maxbc, static_cast<const int32_t*>(d_sig), static_cast<const int32_t*>(d_pos), peaks))) return rc;
+  *d_peaks = peaks;
   return TRACYHIP_OK;
 }
 
@@ -1266,10 +1252,10 @@ int tracyhip_secondary_decomposed(tracyhip_ctx* ctx, const tracyhip_basecalls* b
   const int32_t* d_peaks;
   uint64_t bext;
   if ((rc = bc_descs(ctx, bc, mem, &dd, &d_peaks, &bext))) return rc;
-  if ((rc = stage_in(ctx, ctx->d_tmp[1], bc->primary, bext, mem, &d_pri))) return rc;
-  if ((rc = stage_in(ctx, ctx->d_tmp[2], bc->secondary, bext, mem, &d_sec))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_PRIMARY_STAGE], bc->primary, bext, mem, &d_pri))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_SECONDARY_STAGE], bc->secondary, bext, mem, &d_sec))) return rc;
   void* d_out;
-  if ((rc = stage_io(ctx, ctx->d_tmp[3], secdecomp, bext, mem, false, &d_out))) return rc;
+  if ((rc = stage_out(ctx, ctx->dev[DB_BC_RESULT_STAGE], secdecomp, bext, mem, false, &d_out))) return rc;
   uint32_t maxbc = 0;
   for (uint32_t i = 0; i < n; ++i) maxbc = std::max(maxbc, bc->bc_len[i]);
   if ((rc = launch_secdecomp(ctx, dd, n, maxbc, d_peaks,
@@ -1293,10 +1279,10 @@ int tracyhip_allelic_fraction(tracyhip_ctx* ctx, const tracyhip_basecalls* bc, c
   const int32_t* d_peaks;
   uint64_t bext;
   if ((rc = bc_descs(ctx, bc, mem, &dd, &d_peaks, &bext))) return rc;
-  if ((rc = stage_in(ctx, ctx->d_tmp[1], bc->primary, bext, mem, &d_pri))) return rc;
-  if ((rc = stage_in(ctx, ctx->d_tmp[2], secdecomp, bext, mem, &d_sec))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_PRIMARY_STAGE], bc->primary, bext, mem, &d_pri))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_SECONDARY_STAGE], secdecomp, bext, mem, &d_sec))) return rc;
   void* d_out;
-  if ((rc = stage_io(ctx, ctx->d_tmp[3], fractions, sizeof(double) * 2 * (size_t)n, mem, false, &d_out))) return rc;
+  if ((rc = stage_out(ctx, ctx->dev[DB_BC_RESULT_STAGE], fractions, sizeof(double) * 2 * (size_t)n, mem, false, &d_out))) return rc;
   uint32_t maxbc = 0;
   for (uint32_t i = 0; i < n; ++i) maxbc = std::max(maxbc, bc->bc_len[i]);
   if ((rc = launch_allelic_fraction(ctx, dd, n, maxbc, d_peaks,

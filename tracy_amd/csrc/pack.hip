@@ -134,15 +134,13 @@ int pack_multi(tracyhip_ctx* ctx, const tracyhip_ragged_src* kinds, uint32_t nki
   }
   hipStream_t st = ctx->stream;
   const uint32_t wpk = (n + kScanBlock - 1) / kScanBlock, nw = wpk * nkinds;  // scan workgroups per kind, in all
-  HIP_TRY(ctx->d_tmp[7].ensure(sizeof(unsigned long long) * ((size_t)nw * kScanBlock + nw + kMaxKinds)));
-  unsigned long long* d_local = static_cast<unsigned long long*>(ctx->d_tmp[7].p);
+  unsigned long long* d_local; HIP_TRY(ensure_into(ctx->dev[DB_PACK_SCAN], (size_t)nw * kScanBlock + nw + kMaxKinds, d_local));
   unsigned long long* d_bsum = d_local + (size_t)nw * kScanBlock;
   unsigned long long* d_kend = d_bsum + nw;
   hipLaunchKernelGGL(pack_local_kernel, dim3(wpk, nkinds), dim3(kScanBlock), 0, st, a, d_local, d_bsum);
   hipLaunchKernelGGL(pack_top_kernel, dim3(1), dim3(kScanThreads), 0, st, d_bsum, nw, wpk, nkinds, d_kend);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(ctx->h_res.ensure(sizeof(unsigned long long) * kMaxKinds));
-  unsigned long long* h_kend = static_cast<unsigned long long*>(ctx->h_res.p);
+  unsigned long long* h_kend; HIP_TRY(ensure_into(ctx->pin[PB_RES], kMaxKinds, h_kend));
   HIP_TRY(hipMemcpyAsync(h_kend, d_kend, sizeof(unsigned long long) * nkinds, hipMemcpyDeviceToHost, st));
   auto report = [&]() {
     for (uint32_t k = 0; k < nkinds; ++k) kind_bytes[k] = h_kend[k] - (k ? h_kend[k - 1] : 0ull);

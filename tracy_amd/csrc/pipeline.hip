@@ -40,13 +40,6 @@ struct StageClock {  // TRACYHIP_HOST_TIMERS: wall time from one mark to the nex
   ~StageClock() { delete cur; }
 };
 
-template <class T>
-int copy_out(tracyhip_ctx* ctx, int mem, T* user, const T* dev, size_t count) {
-  if (!user || count == 0 || user == dev) return TRACYHIP_OK;
-  HIP_TRY(hipMemcpyAsync(user, dev, sizeof(T) * count, mem == TRACYHIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ctx->stream));
-  return TRACYHIP_OK;
-}
-
 // =====================================================================================================
 // Orientation + preliminary alignment of trimmed traces against their reference windows: the part `tracy align`
 // (sage.h:223-258) and `tracy decompose` (indigo.h:235-302, FASTA / indexed reference) have in common.
@@ -200,9 +193,9 @@ struct OrientRun {
 
   // Votes of the two strands from shared k-mers (kmer_vote_kernel) and / or the bound on what the rows below a prefix can add
   // (rowmax_rest_kernel).  The device block and the pinned block share one layout -- [VoteDesc nt][RowMaxDesc nt][ub nt][votes 2 nt]
-  // [ub1 nt] -- so the descriptors go up in one copy and the results come back in one.  The host pointers point into ctx->h_res and
+  // [ub1 nt] -- so the descriptors go up in one copy and the results come back in one.  The host pointers point into ctx->pin[PB_RES] and
   // are good from the wait behind fetch_vote_block until prelim() stages through that block: decide_by_bound reads ub there after
-  // two or three launches, so nothing between vote_block and prelim() may use ctx->h_res (run_dp, run_ckpt_prefix, run_front do not).
+  // two or three launches, so nothing between vote_block and prelim() may use ctx->pin[PB_RES] (run_dp, run_ckpt_prefix, run_front do not).
   struct VoteBlock {
     const uint32_t* votes = nullptr;          // host [2 nt]: vf, vr per trace
     const int32_t *ub = nullptr, *ub1 = nullptr;  // host [nt]: the bound; the same with the rows clamped at -1 (front.h, second certificate)
@@ -215,8 +208,8 @@ struct OrientRun {
   int vote_block(bool want_votes, Below below, bool want_ub1, VoteBlock& vb) {
     const bool want_ub = below != Below::none;
     const size_t need = (sizeof(VoteDesc) + sizeof(RowMaxDesc) + 4 * sizeof(uint32_t)) * (size_t)nt;
-    HIP_TRY(ctx->d_tmp[7].ensure(need));
-    HIP_TRY(ctx->h_res.ensure(need));
+    HIP_TRY(ctx->dev[DB_VOTE].ensure(need));
+    HIP_TRY(ctx->pin[PB_RES].ensure(need));
     struct Lay { VoteDesc* vd; RowMaxDesc* rm; int32_t* ub; uint32_t* votes; int32_t* ub1; };
     auto lay = [&](void* base) {
       Lay l;
@@ -227,7 +220,7 @@ struct OrientRun {
       l.ub1 = reinterpret_cast<int32_t*>(l.votes + 2 * (size_t)nt);
       return l;
     };
-    const Lay d = lay(ctx->d_tmp[7].p), h = lay(ctx->h_res.p);
+    const Lay d = lay(ctx->dev[DB_VOTE].p), h = lay(ctx->pin[PB_RES].p);
     parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
       for (uint32_t t = lo; t < hi; ++t) {
         if (want_votes) h.vd[t] = VoteDesc{in.a1_off[t], in.a2_off[t], mf[t], mt[t], rn[t], 0u};
@@ -261,8 +254,7 @@ struct OrientRun {
     // When every trimmed profile fits one pass of its strip height, the score pass also leaves wavefront
     // checkpoints and the last-row values, and stage 2 recomputes only the bands its path crosses
     // (band traceback) instead of storing the whole traceback matrix.
-    HIP_TRY(ctx->d_tmp[0].ensure(sizeof(int32_t) * 2 * (size_t)nt));
-    d_sc2 = static_cast<int32_t*>(ctx->d_tmp[0].p);
+    HIP_TRY(ensure_into(ctx->dev[DB_ORIENT_SC2], 2 * (size_t)nt, d_sc2));
     use_band = !kn.no_band && p.ge < 0 && p.go <= 0 && sub_limit(&p) <= kWideScore;  // hfree = 1, vfree = 0 here
     ck.B = kn.ckpt_b;  // (developer knob, 256)
     // ends_path: the preliminary alignment is only trimmed from (OrientIn::ends_only).  The sweep's score S* and the end c_e of
@@ -310,18 +302,16 @@ struct OrientRun {
       if (use_band) {
         const uint64_t band_bytes = ends_path ? 0 : (uint64_t)nt * ck.B * 64 * 8;  // (no band traceback on the ends path)
         const uint64_t need = (ck_tot + lr_tot) * 4 + band_bytes;
-        const bool have = ctx->d_ckpt.cap >= ck_tot * 4 + 64 && ctx->d_lastrow.cap >= lr_tot * 4 + 64 && ctx->d_band.cap >= band_bytes;
+        const bool have = ctx->dev[DB_CKPT].cap >= ck_tot * 4 + 64 && ctx->dev[DB_LASTROW].cap >= lr_tot * 4 + 64 && ctx->dev[DB_BAND].cap >= band_bytes;
         size_t fr = 0, tot = 0;
         if (!have) HIP_TRY(hipMemGetInfo(&fr, &tot));  // (a driver call: skipped when the grow-only buffers already fit)
-        if (!have && need > (uint64_t)(fr * 0.8 / ctx->mem_share) + ctx->d_ckpt.cap + ctx->d_lastrow.cap + ctx->d_band.cap) use_band = false;
+        if (!have && need > (uint64_t)(fr * 0.8 / ctx->mem_share) + ctx->dev[DB_CKPT].cap + ctx->dev[DB_LASTROW].cap + ctx->dev[DB_BAND].cap) use_band = false;
         else {
-          HIP_TRY(ctx->d_ckpt.ensure(ck_tot * 4 + 64));
-          HIP_TRY(ctx->d_lastrow.ensure(lr_tot * 4 + 64));
+          HIP_TRY(ensure_into(ctx->dev[DB_CKPT], ck_tot + 16, ck.d_ckpt));
+          HIP_TRY(ensure_into(ctx->dev[DB_LASTROW], lr_tot + 16, ck.d_lastrow));
           uint32_t maxmt = 0;
           for (uint32_t t = 0; t < nt; ++t) maxmt = std::max(maxmt, mt[t]);
           ck.narrow = !force_wide && !kn.no_narrow && narrow_ok(&p, maxmt, 16);  // conservative: the tallest strip
-          ck.d_ckpt = static_cast<int32_t*>(ctx->d_ckpt.p);
-          ck.d_lastrow = static_cast<int32_t*>(ctx->d_lastrow.p);
         }
       }
     }
@@ -583,16 +573,16 @@ struct OrientRun {
       if (ends_path || tb16_path) {
         // c_e from the winner's row m, the sub-window from S* and c_e; over it the origin-tracking sweep delivers the two ends (ends_path)
         // or the band kernels the traceback (tb16_path)
-        HIP_TRY(ctx->d_ends.ensure((sizeof(uint32_t) * 5 + sizeof(RowEndDesc) + sizeof(RowMaxDesc)) * (size_t)nt));
-        uint32_t* d_ends = static_cast<uint32_t*>(ctx->d_ends.p);
+        HIP_TRY(ctx->dev[DB_ENDS].ensure((sizeof(uint32_t) * 5 + sizeof(RowEndDesc) + sizeof(RowMaxDesc)) * (size_t)nt));
+        uint32_t* d_ends = static_cast<uint32_t*>(ctx->dev[DB_ENDS].p);
         uint32_t* d_ce = d_ends + 2 * (size_t)nt;
         uint32_t* d_shift = d_ce + nt;
         int32_t* d_top = reinterpret_cast<int32_t*>(d_shift + nt);
         RowEndDesc* d_re = reinterpret_cast<RowEndDesc*>(d_top + nt);
         RowMaxDesc* d_rm = reinterpret_cast<RowMaxDesc*>(d_re + nt);
         // both descriptor lists in one pinned block laid out like the device block (one copy); c_e and top come back into its tail
-        HIP_TRY(ctx->h_res.ensure((sizeof(RowEndDesc) + sizeof(RowMaxDesc) + 2 * sizeof(uint32_t)) * (size_t)nt));
-        RowEndDesc* hre = static_cast<RowEndDesc*>(ctx->h_res.p);
+        HIP_TRY(ctx->pin[PB_RES].ensure((sizeof(RowEndDesc) + sizeof(RowMaxDesc) + 2 * sizeof(uint32_t)) * (size_t)nt));
+        RowEndDesc* hre = static_cast<RowEndDesc*>(ctx->pin[PB_RES].p);
         RowMaxDesc* hrm = reinterpret_cast<RowMaxDesc*>(hre + nt);
         auto from_front = [&](uint32_t t) { return front_strand[t] >= 0 && (front_strand[t] != 0) == (h_rc[t] != 0); };  // (else the winner was swept in full)
         parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
@@ -677,7 +667,7 @@ struct OrientRun {
           DpCkpt oc;
           oc.d_ends = d_ends;
           if (rest.desc.size() < nt) {
-            HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, sizeof(int32_t) * kErrWords, st));
+            HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
             if ((rc = run_band16(ctx, j16, &p, nullptr, d_ends, nullptr, nullptr, nullptr))) return rc;
           }
           if ((rc = run_dp(ctx, rest, &p, false, false, nullptr, nullptr, nullptr, nullptr, DP_ORIGIN, &oc))) return rc;  // (kWiden: the caller restarts wide)
@@ -688,9 +678,9 @@ struct OrientRun {
           sco.mark("o.h stage2 run_band16 + check");
           // traceback on the band; a pair whose banded score is not S* (or whose walk left the band: no ops) is repeated with the rest
           if (rest.desc.size() < nt) {
-            HIP_TRY(ctx->d_tmp[7].ensure(sizeof(int32_t) * (size_t)nt));
-            int32_t* d_sb = static_cast<int32_t*>(ctx->d_tmp[7].p);
-            HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, sizeof(int32_t) * kErrWords, st));
+            int32_t* d_sb;
+            HIP_TRY(ensure_into(ctx->dev[DB_BAND_SCORES], nt, d_sb));
+            HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
             if ((rc = run_band16(ctx, j16, &p, d_sb, nullptr, in.d_ops, in.d_ops_off, in.d_ops_len))) return rc;
             std::vector<int32_t> h_sb(nt);
             std::vector<uint32_t> h_ol(nt);
@@ -811,25 +801,18 @@ struct AlignRun {
     p.hfree = 1;  // AlignConfig<true,false> semiglobal (sage.h:165)
     p.vfree = 0;
   }
-  // device result arrays (user's in DEVICE mode, ours in HOST mode)
-  int dev_arr(DevBuf& b, void* user, size_t bytes, void** dptr) {
-    if (mem == TRACYHIP_MEM_DEVICE) { *dptr = user; return TRACYHIP_OK; }
-    HIP_TRY(b.ensure(bytes));
-    *dptr = b.p;
-    return TRACYHIP_OK;
-  }
 
   int setup() {
     int rc;
     // ---- stage payloads, encode the references once ----
     const uint64_t ep = seqset_extent(sp), er = seqset_extent(sr);
-    if ((rc = stage_in(ctx, ctx->d_in1, sp.data, ep * 4, mem, &d_prof))) return rc;
-    if ((rc = stage_in(ctx, ctx->d_in2, sr.data, er, mem, &d_ref))) return rc;
+    if ((rc = stage_in(ctx, ctx->dev[DB_IN1], sp.data, ep * 4, mem, &d_prof))) return rc;
+    if ((rc = stage_in(ctx, ctx->dev[DB_IN2], sr.data, er, mem, &d_ref))) return rc;
     // The validation verdict (second word of d_err; run_dp owns the first) is read back together with the orientation
     // scores: no host round trip between the encode and the first score pass.
-    HIP_TRY(ctx->d_err.ensure(kErrBytes));
-    HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, kErrBytes, st));
-    d_verr = static_cast<int32_t*>(ctx->d_err.p) + kErrVerdictWord;
+    HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
+    HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, kErrBytes, st));
+    d_verr = static_cast<int32_t*>(ctx->dev[DB_ERR].p) + kErrVerdictWord;
     HIP_TRY(ctx->ensure_codes(er ? er : 1, st));
     if (er) {
       // Windows oriented by the caller (indexed genome) are never reverse-complemented here, and every other letter scores as
@@ -863,13 +846,14 @@ struct AlignRun {
     std::vector<uint64_t> off1(nt);
     uint64_t tot1 = 0;
     for (uint32_t t = 0; t < nt; ++t) { off1[t] = tot1; tot1 += (uint64_t)mt[t] + rn[t]; }
-    HIP_TRY(ctx->d_tmp[1].ensure(tot1 ? tot1 : 1));                       // ops of the preliminary alignment
-    HIP_TRY(ctx->d_tmp[2].ensure(sizeof(uint64_t) * (size_t)nt));          // their offsets
-    HIP_TRY(ctx->d_tmp[3].ensure(sizeof(uint32_t) * (size_t)nt));          // their lengths
-    HIP_TRY(ctx->d_tmp[4].ensure(sizeof(int32_t) * (size_t)nt));           // preliminary scores
-    HIP_TRY(ctx->h_tmp.ensure(sizeof(uint64_t) * (size_t)nt + (size_t)nt * 8));
-    std::memcpy(ctx->h_tmp.p, off1.data(), sizeof(uint64_t) * (size_t)nt);
-    HIP_TRY(hipMemcpyAsync(ctx->d_tmp[2].p, ctx->h_tmp.p, sizeof(uint64_t) * (size_t)nt, hipMemcpyHostToDevice, st));
+    OrientIn oi{};
+    HIP_TRY(ensure_into(ctx->dev[DB_PRELIM_OPS], tot1 ? tot1 : 1, oi.d_ops));  // ops of the preliminary alignment
+    HIP_TRY(ensure_into(ctx->dev[DB_PRELIM_OFF], nt, oi.d_ops_off));           // their offsets
+    HIP_TRY(ensure_into(ctx->dev[DB_PRELIM_LEN], nt, oi.d_ops_len));           // their lengths
+    HIP_TRY(ensure_into(ctx->dev[DB_PRELIM_SCORE], nt, oi.d_score));           // preliminary scores
+    HIP_TRY(ctx->pin[PB_TMP].ensure(sizeof(uint64_t) * (size_t)nt + (size_t)nt * 8));
+    std::memcpy(ctx->pin[PB_TMP].p, off1.data(), sizeof(uint64_t) * (size_t)nt);
+    HIP_TRY(hipMemcpyAsync(ctx->dev[DB_PRELIM_OFF].p, ctx->pin[PB_TMP].p, sizeof(uint64_t) * (size_t)nt, hipMemcpyHostToDevice, st));
     std::vector<uint64_t> a1o(nt), a2o(nt);
     for (uint32_t t = 0; t < nt; ++t) { a1o[t] = sp.offset[t] + tl[t]; a2o[t] = sr.offset[ridx[t]]; }
     // substitution tables of the full profiles for the band kernels (band16.h): the preliminary alignment (rows tl .. tl + mt) and the
@@ -878,14 +862,11 @@ struct AlignRun {
     if (b16) {
       td.resize(nt);
       for (uint32_t t = 0; t < nt; ++t) td[t] = B16TableDesc{sp.offset[t], 0, mf[t], mf[t], 0, 0};
-      if ((rc = build_b16_tables(ctx, ctx->d_b16tab[2], d_prof, false, td, &p))) return rc;
+      if ((rc = build_b16_tables(ctx, ctx->dev[DB_B16TAB_PROFILE], d_prof, false, td, &p))) return rc;
     }
-    OrientIn oi{};
     oi.nt = nt; oi.d_prof = d_prof; oi.a1_off = a1o.data(); oi.mf = mf.data(); oi.mt = mt.data(); oi.a2_off = a2o.data(); oi.rn = rn.data();
     oi.oriented = job->oriented; oi.exact = job->strand_by_certificate == 0; oi.d_verr = d_verr; oi.ends_only = true;
-    if (b16) { oi.d_qp = static_cast<const int16_t*>(ctx->d_b16tab[2].p); oi.td = td.data(); oi.row0 = tl.data(); }
-    oi.d_ops = static_cast<uint8_t*>(ctx->d_tmp[1].p); oi.d_ops_off = static_cast<const uint64_t*>(ctx->d_tmp[2].p);
-    oi.d_ops_len = static_cast<uint32_t*>(ctx->d_tmp[3].p); oi.d_score = static_cast<int32_t*>(ctx->d_tmp[4].p);
+    if (b16) { oi.d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_PROFILE].p); oi.td = td.data(); oi.row0 = tl.data(); }
     if ((rc = orient_and_align(ctx, p, oi, oo))) return rc;
 
     return TRACYHIP_OK;
@@ -893,26 +874,26 @@ struct AlignRun {
 
   int trim() {
     // ---- 3. trimReferenceSlice (sage.h:259) ----
-    HIP_TRY(ctx->d_tmp[5].ensure(sizeof(TrimRec) * (size_t)nt));
-    HIP_TRY(ctx->d_tmp[6].ensure(sizeof(uint32_t) * (size_t)nt + (size_t)nt));
-    uint32_t* d_rn = static_cast<uint32_t*>(ctx->d_tmp[6].p);
+    HIP_TRY(ctx->dev[DB_TRIMREC].ensure(sizeof(TrimRec) * (size_t)nt));
+    HIP_TRY(ctx->dev[DB_TRIM_IN].ensure(sizeof(uint32_t) * (size_t)nt + (size_t)nt));
+    uint32_t* d_rn = static_cast<uint32_t*>(ctx->dev[DB_TRIM_IN].p);
     uint8_t* d_fwd = reinterpret_cast<uint8_t*>(d_rn + nt);
     {
-      uint8_t* hp = static_cast<uint8_t*>(ctx->h_tmp.p) + sizeof(uint64_t) * (size_t)nt;
+      uint8_t* hp = static_cast<uint8_t*>(ctx->pin[PB_TMP].p) + sizeof(uint64_t) * (size_t)nt;
       std::memcpy(hp, rn.data(), sizeof(uint32_t) * (size_t)nt);
       std::memcpy(hp + sizeof(uint32_t) * (size_t)nt, oo.fwd.data(), nt);
       HIP_TRY(hipMemcpyAsync(d_rn, hp, sizeof(uint32_t) * (size_t)nt + nt, hipMemcpyHostToDevice, st));
     }
     if (oo.d_ends)  // the two ends of the preliminary alignment (origin-tracking sweep) instead of its ops
       hipLaunchKernelGGL(trim_from_ends_kernel, dim3((nt + 255) / 256), dim3(256), 0, st, oo.d_ends, static_cast<const uint32_t*>(d_rn),
-                         static_cast<const uint8_t*>(d_fwd), (uint32_t)job->trim_left, (uint32_t)job->trim_right, nt, static_cast<TrimRec*>(ctx->d_tmp[5].p));
+                         static_cast<const uint8_t*>(d_fwd), (uint32_t)job->trim_left, (uint32_t)job->trim_right, nt, static_cast<TrimRec*>(ctx->dev[DB_TRIMREC].p));
     else
-      hipLaunchKernelGGL(trim_kernel, dim3(nt), dim3(64), 0, st, static_cast<const uint8_t*>(ctx->d_tmp[1].p),
-                         static_cast<const uint64_t*>(ctx->d_tmp[2].p), static_cast<const uint32_t*>(ctx->d_tmp[3].p), d_rn, d_fwd,
-                         job->trim_left, job->trim_right, nt, static_cast<TrimRec*>(ctx->d_tmp[5].p));
+      hipLaunchKernelGGL(trim_kernel, dim3(nt), dim3(64), 0, st, static_cast<const uint8_t*>(ctx->dev[DB_PRELIM_OPS].p),
+                         static_cast<const uint64_t*>(ctx->dev[DB_PRELIM_OFF].p), static_cast<const uint32_t*>(ctx->dev[DB_PRELIM_LEN].p), d_rn, d_fwd,
+                         job->trim_left, job->trim_right, nt, static_cast<TrimRec*>(ctx->dev[DB_TRIMREC].p));
     HIP_TRY(hipGetLastError());
     h_trim.resize(nt);
-    HIP_TRY(hipMemcpyAsync(h_trim.data(), ctx->d_tmp[5].p, sizeof(TrimRec) * (size_t)nt, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_trim.data(), ctx->dev[DB_TRIMREC].p, sizeof(TrimRec) * (size_t)nt, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx_sync(ctx));
 
     return TRACYHIP_OK;
@@ -922,13 +903,13 @@ struct AlignRun {
     int rc;
     // ---- 4. final alignment gotoh(full profile, profile of the trimmed slice) (sage.h:260, 311) ----
     for (uint32_t t = 0; t < nt; ++t) ops_total = std::max<uint64_t>(ops_total, out->ops_offset[t] + mf[t] + h_trim[t].len);
-    if ((rc = dev_arr(ctx->d_scores, out->score_final, sizeof(int32_t) * (size_t)nt, &d_final_sc))) return rc;
-    if ((rc = dev_arr(ctx->d_ops, out->ops, ops_total ? ops_total : 1, &d_ops))) return rc;
-    if ((rc = dev_arr(ctx->d_ops_len, out->ops_len, sizeof(uint32_t) * (size_t)nt, &d_olen))) return rc;
-    HIP_TRY(ctx->h_off.ensure(sizeof(uint64_t) * (size_t)nt));
-    std::memcpy(ctx->h_off.p, out->ops_offset, sizeof(uint64_t) * (size_t)nt);
-    HIP_TRY(ctx->d_ops_off.ensure(sizeof(uint64_t) * (size_t)nt));
-    HIP_TRY(hipMemcpyAsync(ctx->d_ops_off.p, ctx->h_off.p, sizeof(uint64_t) * (size_t)nt, hipMemcpyHostToDevice, st));
+    if ((rc = stage_out(ctx, ctx->dev[DB_SCORES], out->score_final, sizeof(int32_t) * (size_t)nt, mem, false, &d_final_sc))) return rc;
+    if ((rc = stage_out(ctx, ctx->dev[DB_OPS], out->ops, ops_total, mem, false, &d_ops))) return rc;
+    if ((rc = stage_out(ctx, ctx->dev[DB_OPS_LEN], out->ops_len, sizeof(uint32_t) * (size_t)nt, mem, false, &d_olen))) return rc;
+    HIP_TRY(ctx->pin[PB_OFF].ensure(sizeof(uint64_t) * (size_t)nt));
+    std::memcpy(ctx->pin[PB_OFF].p, out->ops_offset, sizeof(uint64_t) * (size_t)nt);
+    HIP_TRY(ctx->dev[DB_OPS_OFF].ensure(sizeof(uint64_t) * (size_t)nt));
+    HIP_TRY(hipMemcpyAsync(ctx->dev[DB_OPS_OFF].p, ctx->pin[PB_OFF].p, sizeof(uint64_t) * (size_t)nt, hipMemcpyHostToDevice, st));
     {
       DpProblem pb;
       DpProblemLease lease(ctx, pb);
@@ -963,7 +944,7 @@ struct AlignRun {
       // band kernels (band16.h) where the band fits them: four pairs per wave, only the band's cells swept and stored
       Band16Job j16;
       j16.kind = 0;
-      j16.d_qp = static_cast<const int16_t*>(ctx->d_b16tab[2].p);
+      j16.d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_PROFILE].p);
       j16.d_codes = ctx->codes();
       std::vector<PairDesc> whole(nt);  // every pair as a whole-matrix problem (what a pair that does not certify is repeated as)
       pb.desc.clear();
@@ -1019,7 +1000,7 @@ struct AlignRun {
         if (limit == 0) {
           size_t fr = 0, tot = 0;
           HIP_TRY(hipMemGetInfo(&fr, &tot));
-          limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->d_bits.cap;
+          limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->dev[DB_BITS].cap;
         }
         uint64_t bytes = 0;
         bool unband_all = false;
@@ -1038,12 +1019,12 @@ struct AlignRun {
       }
       int32_t* d_top = nullptr;
       if (nbanded) {  // the bound's top, per trace, while the DP runs
-        DevBuf& b = ctx->d_tmp[6];
+        DevBuf& b = ctx->dev[DB_FINAL_TOP];
         HIP_TRY(b.ensure((sizeof(RowMaxDesc) + sizeof(int32_t)) * (size_t)nt));
         RowMaxDesc* d_rm = static_cast<RowMaxDesc*>(b.p);
         d_top = reinterpret_cast<int32_t*>(d_rm + nt);
-        HIP_TRY(ctx->h_tmp.ensure(sizeof(RowMaxDesc) * (size_t)nt));  // (pinned, free at this point of the call: no host wait)
-        RowMaxDesc* hrm = static_cast<RowMaxDesc*>(ctx->h_tmp.p);
+        HIP_TRY(ctx->pin[PB_TMP].ensure(sizeof(RowMaxDesc) * (size_t)nt));  // (pinned, free at this point of the call: no host wait)
+        RowMaxDesc* hrm = static_cast<RowMaxDesc*>(ctx->pin[PB_TMP].p);
         for (uint32_t t = 0; t < nt; ++t) hrm[t] = RowMaxDesc{sp.offset[t], mf[t], mf[t], 0u};
         HIP_TRY(hipMemcpyAsync(d_rm, hrm, sizeof(RowMaxDesc) * (size_t)nt, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(rowmax_rest_kernel, dim3(nt), dim3(64), 0, st, static_cast<const RowMaxDesc*>(d_rm), static_cast<const float*>(d_prof),
@@ -1051,14 +1032,14 @@ struct AlignRun {
         HIP_TRY(hipGetLastError());
       }
       if (!j16.desc.empty()) {
-        HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, sizeof(int32_t) * kErrWords, st));
-        rc = run_band16(ctx, j16, &p, static_cast<int32_t*>(d_final_sc), nullptr, static_cast<uint8_t*>(d_ops), static_cast<const uint64_t*>(ctx->d_ops_off.p),
+        HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
+        rc = run_band16(ctx, j16, &p, static_cast<int32_t*>(d_final_sc), nullptr, static_cast<uint8_t*>(d_ops), static_cast<const uint64_t*>(ctx->dev[DB_OPS_OFF].p),
                         static_cast<uint32_t*>(d_olen));
         if (rc == kWiden) rc = set_error(TRACYHIP_ERR_RANGE, "profile values outside the range of the traceback kernels");
         if (rc) return rc;
       }
       if ((rc = run_dp(ctx, pb, &p, false, true, static_cast<int32_t*>(d_final_sc), static_cast<uint8_t*>(d_ops),
-                       static_cast<const uint64_t*>(ctx->d_ops_off.p), static_cast<uint32_t*>(d_olen))))
+                       static_cast<const uint64_t*>(ctx->dev[DB_OPS_OFF].p), static_cast<uint32_t*>(d_olen))))
         return rc;
       if (nbanded) {
         std::vector<int32_t> h_top(nt), h_sb(nt);
@@ -1088,7 +1069,7 @@ struct AlignRun {
           pb.desc.swap(again);
           pb.k.swap(again_k);
           if ((rc = run_dp(ctx, pb, &p, false, true, static_cast<int32_t*>(d_final_sc), static_cast<uint8_t*>(d_ops),
-                           static_cast<const uint64_t*>(ctx->d_ops_off.p), static_cast<uint32_t*>(d_olen))))
+                           static_cast<const uint64_t*>(ctx->dev[DB_OPS_OFF].p), static_cast<uint32_t*>(d_olen))))
             return rc;
         }
       }
@@ -1102,8 +1083,8 @@ struct AlignRun {
     // ---- results ----
     // host-decided arrays go out from one pinned staging block (copies from pageable memory are staged by the runtime and
     // cost a host round trip each)
-    HIP_TRY(ctx->h_res.ensure((size_t)nt * (5 * sizeof(uint32_t) + 1)));
-    uint32_t* r32 = static_cast<uint32_t*>(ctx->h_res.p);
+    HIP_TRY(ctx->pin[PB_RES].ensure((size_t)nt * (5 * sizeof(uint32_t) + 1)));
+    uint32_t* r32 = static_cast<uint32_t*>(ctx->pin[PB_RES].p);
     uint8_t* r8 = reinterpret_cast<uint8_t*>(r32 + 5 * (size_t)nt);
     if (job->oriented != nullptr) std::copy(oo.sc2.begin(), oo.sc2.begin() + nt, oo.sc2.begin() + nt);  // one orientation: both arrays report its score
     for (uint32_t t = 0; t < nt; ++t) {
@@ -1121,14 +1102,11 @@ struct AlignRun {
     HIP_TRY(hipMemcpyAsync(out->slice_len, r32 + 3 * (size_t)nt, sizeof(uint32_t) * (size_t)nt, up, st));
     HIP_TRY(hipMemcpyAsync(out->ref_pos, r32 + 4 * (size_t)nt, sizeof(uint32_t) * (size_t)nt, up, st));
     HIP_TRY(hipMemcpyAsync(out->forward, r8, nt, up, st));
-    if (out->score_prelim) {
-      if ((rc = copy_out(ctx, mem, out->score_prelim, static_cast<const int32_t*>(ctx->d_tmp[4].p), nt))) return rc;
-    }
-    if (mem == TRACYHIP_MEM_HOST) {
-      if ((rc = copy_out(ctx, mem, out->score_final, static_cast<const int32_t*>(d_final_sc), nt))) return rc;
-      if ((rc = copy_out(ctx, mem, out->ops, static_cast<const uint8_t*>(d_ops), ops_total))) return rc;
-      if ((rc = copy_out(ctx, mem, out->ops_len, static_cast<const uint32_t*>(d_olen), nt))) return rc;
-    }
+    if (out->score_prelim)  // (kept in a buffer of the context in both modes)
+      HIP_TRY(hipMemcpyAsync(out->score_prelim, ctx->dev[DB_PRELIM_SCORE].p, sizeof(int32_t) * (size_t)nt, mem == TRACYHIP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    if ((rc = unstage(ctx, out->score_final, d_final_sc, sizeof(int32_t) * (size_t)nt, mem))) return rc;
+    if ((rc = unstage(ctx, out->ops, d_ops, ops_total, mem))) return rc;
+    if ((rc = unstage(ctx, out->ops_len, d_olen, sizeof(uint32_t) * (size_t)nt, mem))) return rc;
     HIP_TRY(ctx_sync(ctx));
     return TRACYHIP_OK;
   }
@@ -1390,25 +1368,21 @@ struct DecomposeRun {
   DecomposeRun(tracyhip_ctx* c, const tracyhip_decompose_job* j, const tracyhip_params* q, int m, const tracyhip_decompose_result* o)
       : ctx(c), job(j), prm(q), mem(m), out(o), nt(j->ntraces), sp(j->profiles), sr(j->refs), bc(j->bc), dp(j->dprm), srp(j->ref_profiles), st(c->stream),
         p(*q), pglobal(*q), TL((uint32_t)j->dprm.trim_left), TR((uint32_t)j->dprm.trim_right), wildtype(j->ref_profiles.data != nullptr),
-        given(j->oriented != nullptr), shared_stages(j->ref_profiles.data == nullptr), b_sc2(c->d_pipe[0]), b_ops1(c->d_pipe[1]), b_len1(c->d_pipe[2]),
-        b_r0(c->d_pipe[3]), b_r1(c->d_pipe[4]), b_hst(c->d_pipe[5]), b_cq1(c->d_pipe[6]), b_cq2(c->d_pipe[7]), b_cqf(c->d_pipe[8]), b_opsA(c->d_pipe[9]),
-        b_lenA(c->d_pipe[10]), b_trimA(c->d_pipe[11]), b_rnfw(c->d_pipe[12]), b_ends(c->d_pipe[13]) {
-    nbuf = 14;
+        given(j->oriented != nullptr), shared_stages(j->ref_profiles.data == nullptr), b_sc2(buf()), b_ops1(buf()), b_len1(buf()),
+        b_r0(buf()), b_r1(buf()), b_hst(buf()), b_cq1(buf()), b_cq2(buf()), b_cqf(buf()), b_opsA(buf()),
+        b_lenA(buf()), b_trimA(buf()), b_rnfw(buf()), b_ends(buf()) {  // (the first fourteen of the range, in the order of their declaration)
     p.hfree = 1;  // AlignConfig<true,false> semiglobal (indigo.h:164)
     p.vfree = 0;
     pglobal.hfree = 0;  // AlignConfig<false,false> (indigo.h:381)
     pglobal.vfree = 0;
   }
-  DevBuf& buf() { return ctx->d_pipe[nbuf++]; }
+  DevBuf& buf() { return ctx->dev[DB_PIPE0 + nbuf++]; }  // the next buffer of the DB_PIPE range
   // a result array: the user's (DEVICE) or a staging buffer (HOST) copied back at the end
   int io(void* user, size_t bytes, bool upload_first, void** dptr) {
-    if (mem == TRACYHIP_MEM_DEVICE) { *dptr = user; return TRACYHIP_OK; }
-    DevBuf& b = buf();
-    HIP_TRY(b.ensure(bytes ? bytes : 1));
-    if (upload_first && bytes) HIP_TRY(hipMemcpyAsync(b.p, user, bytes, hipMemcpyHostToDevice, st));
-    *dptr = b.p;
-    outs.push_back(DevOut{b.p, user, bytes});
-    return TRACYHIP_OK;
+    if (mem == TRACYHIP_MEM_DEVICE) { *dptr = user; return TRACYHIP_OK; }  // (takes no buffer of the range)
+    const int rc = stage_out(ctx, buf(), user, bytes, mem, upload_first, dptr);
+    if (!rc) outs.push_back(DevOut{*dptr, user, bytes});
+    return rc;
   }
   PairDesc qp_desc(uint32_t t, bool trimmed) const {
     PairDesc d{};
@@ -1486,11 +1460,11 @@ struct DecomposeRun {
     if ((rc = io(out->score_trim, sizeof(int32_t) * (size_t)nt, false, &d_strim))) return rc;
 
     // references: validate + encode
-    HIP_TRY(ctx->d_err.ensure(kErrBytes));
-    HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, kErrBytes, st));
+    HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
+    HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, kErrBytes, st));
     HIP_TRY(ctx->ensure_codes(er ? er : 1, st));
     if (er) {
-      int32_t* d_verr = static_cast<int32_t*>(ctx->d_err.p) + kErrVerdictWord;
+      int32_t* d_verr = static_cast<int32_t*>(ctx->dev[DB_ERR].p) + kErrVerdictWord;
       // (as in tracyhip_align_traces: caller-oriented windows are taken as they are, no validation)
       hipLaunchKernelGGL(encode_codes_kernel, dim3((unsigned)((er + 4095) / 4096)), dim3(256), 0, st, static_cast<const uint8_t*>(d_ref),
                          ctx->codes(), er, ctx->special_blocks(), job->oriented ? (int32_t*)nullptr : d_verr);
@@ -1564,9 +1538,9 @@ struct DecomposeRun {
       if (p.ge < 0 && p.go <= 0 && sub_limit(&p) <= kWideScore && !ctx->knobs.no_band16) {
         tdp.resize(nt);
         for (uint32_t t = 0; t < nt; ++t) tdp[t] = B16TableDesc{sp.offset[t], 0, mf[t], mf[t], 0, 0};
-        HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, sizeof(int32_t) * kErrWords, st));
-        if ((rc = build_b16_tables(ctx, ctx->d_b16tab[2], d_prof, false, tdp, &p))) return rc;
-        oi.d_qp = static_cast<const int16_t*>(ctx->d_b16tab[2].p); oi.td = tdp.data(); oi.row0 = tl.data();
+        HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
+        if ((rc = build_b16_tables(ctx, ctx->dev[DB_B16TAB_PROFILE], d_prof, false, tdp, &p))) return rc;
+        oi.d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_PROFILE].p); oi.td = tdp.data(); oi.row0 = tl.data();
       }
       OrientOut oo;
       if ((rc = orient_and_align(ctx, p, oi, oo))) return rc;
@@ -1799,8 +1773,8 @@ struct DecomposeRun {
     if (b16) {
       td.resize(nt);
       for (uint32_t t = 0; t < nt; ++t) td[t] = B16TableDesc{bc.bc_offset[t] + soff[t], 0, 0, sl[t], 0, 0};
-      HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, sizeof(int32_t) * kErrWords, st));
-      if ((rc = build_b16_tables(ctx, ctx->d_b16tab[k], seq, true, td, &p))) return rc;
+      HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
+      if ((rc = build_b16_tables(ctx, ctx->dev[DB_B16TAB_ALLELE0 + k], seq, true, td, &p))) return rc;
       if (k == 0) td_pri = td;
     }
     A.h_s1.assign(nt, 0);
@@ -1842,7 +1816,7 @@ struct DecomposeRun {
     std::vector<RowEndDesc> hre(nt);
     uint64_t lr_tot = 0;
     for (uint32_t t = 0; t < nt; ++t) { pb.desc[t].lastrow_off = lr_tot; hre[t] = RowEndDesc{lr_tot, rn[t], 0}; lr_tot += (uint64_t)rn[t] + 2; }
-    HIP_TRY(ctx->d_lastrow.ensure(lr_tot * 4 + 64));
+    HIP_TRY(ctx->dev[DB_LASTROW].ensure(lr_tot * 4 + 64));
     DevBuf &b_sw = buf(), &b_zero = buf();
     HIP_TRY(b_sw.ensure(sizeof(int32_t) * (size_t)nt + sizeof(uint32_t) * 2 * (size_t)nt));
     int32_t* d_swscore = static_cast<int32_t*>(b_sw.p);
@@ -1856,8 +1830,8 @@ struct DecomposeRun {
     DpCkpt sc;
     sc.B = 0x7fffffffu;  // row m only: no wavefront checkpoints
     sc.narrow = true;
-    sc.d_ckpt = static_cast<int32_t*>(ctx->d_lastrow.p);  // (never written)
-    sc.d_lastrow = static_cast<int32_t*>(ctx->d_lastrow.p);
+    sc.d_ckpt = static_cast<int32_t*>(ctx->dev[DB_LASTROW].p);  // (never written)
+    sc.d_lastrow = static_cast<int32_t*>(ctx->dev[DB_LASTROW].p);
     sc6.mark("6.b sweep run_dp");
     // The pruned sweep (front.h), as for the orientation of the trace: rows 1 .. R of the allele over the whole window (row R kept),
     // the rows below them on the diagonals around the best column of row R, and a certificate per pair that no path outside those
@@ -1910,9 +1884,9 @@ struct DecomposeRun {
         }
       });
       if (!fd.empty()) {
-        if ((rc = run_prefix_keep_cq(ctx, pb.d_a1, pb.d_a2, pb.d_special, pre, &p, static_cast<int32_t*>(ctx->d_lastrow.p)))) return rc;
+        if ((rc = run_prefix_keep_cq(ctx, pb.d_a1, pb.d_a2, pb.d_special, pre, &p, static_cast<int32_t*>(ctx->dev[DB_LASTROW].p)))) return rc;
         FrontResult fres;
-        if ((rc = run_front(ctx, fd, static_cast<const int16_t*>(ctx->d_b16tab[k].p), static_cast<const uint32_t*>(ctx->d_lastrow.p), &p, fres, d_cq_ref, true)))
+        if ((rc = run_front(ctx, fd, static_cast<const int16_t*>(ctx->dev[DB_B16TAB_ALLELE0 + k].p), static_cast<const uint32_t*>(ctx->dev[DB_LASTROW].p), &p, fres, d_cq_ref, true)))
           return rc;
         fscore.assign(nt, 0);
         fce.assign(nt, 0);
@@ -1944,7 +1918,7 @@ struct DecomposeRun {
       if (npruned < nt) {  // (every allele pruned -- the usual case: nothing to read off row m, no round trip)
         const RowEndDesc* d_re;
         if ((rc = upload(ctx, buf(), hre, &d_re))) return rc;
-        hipLaunchKernelGGL(row_m_end_kernel, dim3(nt), dim3(64), 0, st, d_re, static_cast<const int32_t*>(ctx->d_lastrow.p), p.go + p.ge, d_ce);
+        hipLaunchKernelGGL(row_m_end_kernel, dim3(nt), dim3(64), 0, st, d_re, static_cast<const int32_t*>(ctx->dev[DB_LASTROW].p), p.go + p.ge, d_ce);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(h_s.data(), d_swscore, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(h_ce.data(), d_ce, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
@@ -1995,7 +1969,7 @@ struct DecomposeRun {
     Band16Lease<Band16Job> jo_lease(ctx, jo);
     DpProblem rest;
     if (b16) {
-      jo.kind = 1; jo.d_qp = static_cast<const int16_t*>(ctx->d_b16tab[k].p); jo.d_codes = d_cq_ref;
+      jo.kind = 1; jo.d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_ALLELE0 + k].p); jo.d_codes = d_cq_ref;
       rest.mode = pb.mode; rest.d_a1 = pb.d_a1; rest.d_a2 = pb.d_a2; rest.cq_codes = pb.cq_codes;
       jo.desc.resize(nt);
       jo.k.assign(nt, 0);
@@ -2087,7 +2061,7 @@ struct DecomposeRun {
     DpProblem rest;
     rest.mode = pb.mode; rest.d_a1 = pb.d_a1; rest.d_a2 = pb.d_a2; rest.cq_codes = pb.cq_codes;
     if (!h_ends.empty()) {
-      jt.kind = 0; jt.d_qp = static_cast<const int16_t*>(ctx->d_b16tab[k].p); jt.d_codes = d_cq_ref;
+      jt.kind = 0; jt.d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_ALLELE0 + k].p); jt.d_codes = d_cq_ref;
       jt.desc.resize(nt);
       jt.k.assign(nt, 0);
       parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
@@ -2167,7 +2141,7 @@ struct DecomposeRun {
         std::vector<int32_t> h_a[2] = {std::vector<int32_t>(nt), std::vector<int32_t>(nt)};
         for (int k = 0; k < 2; ++k) HIP_TRY(hipMemcpyAsync(h_a[k].data(), d_scoreK[k], sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx_sync(ctx));
-        jg.kind = 0; jg.d_qp = static_cast<const int16_t*>(ctx->d_b16tab[0].p); jg.d_codes = d_cq_sd;
+        jg.kind = 0; jg.d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_ALLELE0].p); jg.d_codes = d_cq_sd;
         const int64_t best = std::max<int64_t>(std::max<int64_t>(pglobal.match, pglobal.mismatch), 0);
         jg.desc.resize(nt);
         jg.k.assign(nt, 0);
@@ -2186,7 +2160,7 @@ struct DecomposeRun {
         for (uint32_t t = 0; t < nt; ++t)
           if (jg.k[t] == 0) { rest.desc.push_back(pb.desc[t]); rest.k.push_back(pb.k[t]); }
         const size_t nb16 = nt - rest.desc.size();
-        HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, sizeof(int32_t) * kErrWords, st));
+        HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
         sc6.mark("6.j allele1v2 run_band16");
         if ((rc = run_band16(ctx, jg, &pglobal, static_cast<int32_t*>(d_scoreK[2]), nullptr, static_cast<uint8_t*>(d_opsK[2]), d_offK, static_cast<uint32_t*>(d_lenK[2])))) return rc;
         if (nb16) {
@@ -2227,7 +2201,7 @@ struct DecomposeRun {
     HIP_TRY(hipMemcpyAsync(out->forward, h_fwd.data(), nt, up, st));
     HIP_TRY(hipMemcpyAsync(out->status, h_status.data(), sizeof(int32_t) * (size_t)nt, up, st));
     for (const DevOut& o : outs)
-      if (o.bytes) HIP_TRY(hipMemcpyAsync(o.user, o.dev, o.bytes, hipMemcpyDeviceToHost, st));
+      if (const int rc = unstage(ctx, o.user, o.dev, o.bytes, mem)) return rc;
     HIP_TRY(ctx_sync(ctx));
     timing_collect(ctx);
     return TRACYHIP_OK;
@@ -2490,17 +2464,17 @@ extern "C" int tracyhip_trim_reference_slice(tracyhip_ctx* ctx, uint32_t ntraces
     hd[t] = TrimRowsDesc{rows_offset[t], rows_len[t], refslice_len[t], (uint8_t)(forward[t] ? 1 : 0), {0, 0, 0, 0, 0, 0, 0}};
   }
   const void *d_r0, *d_r1;
-  if ((rc = stage_in(ctx, ctx->d_rows0, rows0, ext, mem, &d_r0))) return rc;
-  if ((rc = stage_in(ctx, ctx->d_rows1, rows1, ext, mem, &d_r1))) return rc;
-  HIP_TRY(ctx->d_desc.ensure(sizeof(TrimRowsDesc) * (size_t)ntraces));
-  HIP_TRY(hipMemcpyAsync(ctx->d_desc.p, hd.data(), sizeof(TrimRowsDesc) * (size_t)ntraces, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx->d_tmp[5].ensure(sizeof(TrimRec) * (size_t)ntraces));
-  hipLaunchKernelGGL(trim_rows_kernel, dim3(ntraces), dim3(64), 0, st, static_cast<const TrimRowsDesc*>(ctx->d_desc.p),
+  if ((rc = stage_in(ctx, ctx->dev[DB_ROWS0], rows0, ext, mem, &d_r0))) return rc;
+  if ((rc = stage_in(ctx, ctx->dev[DB_ROWS1], rows1, ext, mem, &d_r1))) return rc;
+  HIP_TRY(ctx->dev[DB_DESC].ensure(sizeof(TrimRowsDesc) * (size_t)ntraces));
+  HIP_TRY(hipMemcpyAsync(ctx->dev[DB_DESC].p, hd.data(), sizeof(TrimRowsDesc) * (size_t)ntraces, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx->dev[DB_TRIMREC].ensure(sizeof(TrimRec) * (size_t)ntraces));
+  hipLaunchKernelGGL(trim_rows_kernel, dim3(ntraces), dim3(64), 0, st, static_cast<const TrimRowsDesc*>(ctx->dev[DB_DESC].p),
                      static_cast<const uint8_t*>(d_r0), static_cast<const uint8_t*>(d_r1), trim_left, trim_right, ntraces,
-                     static_cast<TrimRec*>(ctx->d_tmp[5].p));
+                     static_cast<TrimRec*>(ctx->dev[DB_TRIMREC].p));
   HIP_TRY(hipGetLastError());
   std::vector<TrimRec> h(ntraces);
-  HIP_TRY(hipMemcpyAsync(h.data(), ctx->d_tmp[5].p, sizeof(TrimRec) * (size_t)ntraces, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h.data(), ctx->dev[DB_TRIMREC].p, sizeof(TrimRec) * (size_t)ntraces, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx_sync(ctx));  // (hd is pageable: the upload above has completed by now as well)
   std::vector<uint32_t> b(ntraces), l(ntraces), p(ntraces);
   for (uint32_t t = 0; t < ntraces; ++t) { b[t] = h[t].ri; l[t] = h[t].len; p[t] = h[t].pos; }

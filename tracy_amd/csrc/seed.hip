@@ -441,9 +441,9 @@ int tracyhip_seed_traces(tracyhip_ctx* ctx, const tracyhip_genome* genome, const
     }
     const uint8_t* d_cons = static_cast<const uint8_t*>(cons->data);
     if (mem == TRACYHIP_MEM_HOST) {
-      HIP_TRY(ctx->d_seed[1].ensure(hi - lo + 1));
-      HIP_TRY(hipMemcpyAsync(ctx->d_seed[1].p, d_cons + lo, hi - lo, hipMemcpyHostToDevice, ctx->stream));
-      d_cons = static_cast<const uint8_t*>(ctx->d_seed[1].p);
+      HIP_TRY(ctx->dev[DB_SEED_CONS].ensure(hi - lo + 1));
+      HIP_TRY(hipMemcpyAsync(ctx->dev[DB_SEED_CONS].p, d_cons + lo, hi - lo, hipMemcpyHostToDevice, ctx->stream));
+      d_cons = static_cast<const uint8_t*>(ctx->dev[DB_SEED_CONS].p);
     } else {
       lo = 0;
     }
@@ -452,13 +452,11 @@ int tracyhip_seed_traces(tracyhip_ctx* ctx, const tracyhip_genome* genome, const
     off.resize((size_t)m + (m + 1) / 2);
     for (uint32_t i = 0; i < m; ++i) off[i] = cons->offset[t0 + i] - lo;
     std::memcpy(off.data() + m, cons->length + t0, 4ull * m);
-    HIP_TRY(ctx->d_seed[0].ensure(b_end));
-    uint8_t* d0 = static_cast<uint8_t*>(ctx->d_seed[0].p);
+    uint8_t* d0; HIP_TRY(ensure_into(ctx->dev[DB_SEED_TRACES], b_end, d0));
     HIP_TRY(hipMemcpyAsync(d0, off.data(), 12ull * m, hipMemcpyHostToDevice, ctx->stream));
     uint8_t* d_slices = out->slices + (uint64_t)t0 * out->slice_cap;
     if (mem == TRACYHIP_MEM_HOST) {
-      HIP_TRY(ctx->d_seed[2].ensure((uint64_t)m * row));
-      d_slices = static_cast<uint8_t*>(ctx->d_seed[2].p);
+      HIP_TRY(ensure_into(ctx->dev[DB_SEED_WINDOWS], (uint64_t)m * row, d_slices));
       HIP_TRY(hipMemsetAsync(d_slices, 0, (uint64_t)m * out->slice_cap, ctx->stream));
     }
     SeedArgs a;

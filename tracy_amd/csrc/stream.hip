@@ -668,7 +668,7 @@ int with_fresh_budget(tracyhip_ctx* ctx, Plan plan) {
 
 DpArgs sweep_args(tracyhip_ctx* ctx, const tracyhip_params& p, const void* d_a1, const void* d_a2, int32_t* d_scores, int32_t* d_lastrow) {
   DpArgs a{};
-  a.a1 = d_a1; a.a2 = d_a2; a.scores = d_scores; a.err = static_cast<int32_t*>(ctx->d_err.p);
+  a.a1 = d_a1; a.a2 = d_a2; a.scores = d_scores; a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
   a.match = p.match; a.mismatch = p.mismatch; a.go = p.go; a.ge = p.ge; a.hfree = p.hfree; a.vfree = p.vfree;
   a.qlimit = sub_limit(&p);
   a.ckpt = d_lastrow;  // (never written: row m only)
@@ -694,7 +694,7 @@ int front_tier(tracyhip_ctx* ctx, const tracyhip_params& p, const FrontDesc* fd,
   hipStream_t st = ctx->stream;
   Band16Args a{};
   a.pairs = pairs; a.npairs = n; a.index = list; a.count = list_count; a.qp = d_qp; a.codes = d_codes; a.scores = fs; a.ends = fe;
-  a.err = static_cast<int32_t*>(ctx->d_err.p); a.go = p.go; a.ge = p.ge; a.hfree = 1; a.row = d_row;
+  a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p); a.go = p.go; a.ge = p.ge; a.hfree = 1; a.row = d_row;
   a.code_cap = (max_rest + 2u * (uint32_t)halfw + 16u) & ~3u;  // front_place_body: a sub-window is at most m_rest + 2 halfw + 2 columns
   if (KB == 0) {
     if (b16_cont_quad_lds(a.code_cap) > 64u * 1024u) return kStreamNo;  // (front_tiers_run goes on with the wide tiers: nothing was queued for this one)
@@ -814,8 +814,8 @@ int band_stage(tracyhip_ctx* ctx, const tracyhip_params& p, StreamCommon& sc, ui
                      sc.bstat + SB_COUNT * stage_no);
   HIP_TRY(hipGetLastError());
   Band16Args a{};
-  a.pairs = sc.cand; a.npairs = n; a.qp = bl.qp; a.codes = bl.codes; a.bits = static_cast<uint8_t*>(ctx->d_bits.p); a.scores = bl.scores; a.ends = bl.ends;
-  a.err = static_cast<int32_t*>(ctx->d_err.p); a.go = p.go; a.ge = p.ge; a.hfree = bl.hfree;
+  a.pairs = sc.cand; a.npairs = n; a.qp = bl.qp; a.codes = bl.codes; a.bits = static_cast<uint8_t*>(ctx->dev[DB_BITS].p); a.scores = bl.scores; a.ends = bl.ends;
+  a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p); a.go = p.go; a.ge = p.ge; a.hfree = bl.hfree;
   a.ops = bl.ops; a.ops_off = bl.ops_off; a.ops_len = bl.ops_len; a.code_cap = bl.code_cap;
   Band16Args ak[4] = {a, a, a, a};  // 12, 8, 4, 4 in quads
   for (int b = 0; b < 4; ++b) { ak[b].index = sc.idx + (size_t)b * n; ak[b].count = count + b; }
@@ -874,7 +874,7 @@ int queue_orientation(tracyhip_ctx* ctx, const tracyhip_params& p, const SParams
     hipError_t e = hipSuccess;
     if (!rc) {
       e = launch_b16_tables(sc.td, nt, os.d_prof, false, p.match, p.mismatch, sub_limit(&p), kTagShift, const_cast<int16_t*>(os.d_qp),
-                            static_cast<int32_t*>(ctx->d_err.p), sp1);
+                            static_cast<int32_t*>(ctx->dev[DB_ERR].p), sp1);
       rc = timing_end(ctx);
     }
     ctx->stream = st;
@@ -1142,8 +1142,8 @@ struct ReadBack {
   uint32_t* hdead = nullptr;
   void* extra = nullptr;
   int carve(tracyhip_ctx* ctx, uint32_t nt, size_t extra_bytes) {
-    HIP_TRY(ctx->h_res.ensure(kErrBytes + sizeof(unsigned long long) * (SC_COUNT + SB_COUNT * 8) + sizeof(uint32_t) * (size_t)nt + extra_bytes));
-    herr = static_cast<int32_t*>(ctx->h_res.p);
+    HIP_TRY(ctx->pin[PB_RES].ensure(kErrBytes + sizeof(unsigned long long) * (SC_COUNT + SB_COUNT * 8) + sizeof(uint32_t) * (size_t)nt + extra_bytes));
+    herr = static_cast<int32_t*>(ctx->pin[PB_RES].p);
     hcnt = reinterpret_cast<unsigned long long*>(herr + kErrWords + 4);
     hbst = hcnt + SC_COUNT;
     hdead = reinterpret_cast<uint32_t*>(hbst + SB_COUNT * 8);
@@ -1151,7 +1151,7 @@ struct ReadBack {
     return TRACYHIP_OK;
   }
   int queue_verdict(tracyhip_ctx* ctx, hipStream_t st) {
-    HIP_TRY(hipMemcpyAsync(herr, ctx->d_err.p, kErrBytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(herr, ctx->dev[DB_ERR].p, kErrBytes, hipMemcpyDeviceToHost, st));
     return TRACYHIP_OK;
   }
   int queue_counters(const StreamCommon& sc, uint32_t nt, hipStream_t st) {
@@ -1242,9 +1242,9 @@ struct StreamCall {
 
   // verdict words cleared, the reference windows encoded to profile-row codes (with their block map and the validation verdict)
   int encode_references(const uint8_t* refs, uint64_t er) {
-    HIP_TRY(ctx->d_err.ensure(kErrBytes));
-    HIP_TRY(hipMemsetAsync(ctx->d_err.p, 0, kErrBytes, st));
-    int32_t* d_verr = static_cast<int32_t*>(ctx->d_err.p) + kErrVerdictWord;
+    HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
+    HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, kErrBytes, st));
+    int32_t* d_verr = static_cast<int32_t*>(ctx->dev[DB_ERR].p) + kErrVerdictWord;
     HIP_TRY(ctx->ensure_codes(er ? er : 1, st));
     if (er) {
       hipLaunchKernelGGL(encode_codes_kernel, dim3((unsigned)((er + 4095) / 4096)), dim3(256), 0, st, refs, ctx->codes(), er, ctx->special_blocks(), d_verr);
@@ -1268,8 +1268,8 @@ struct StreamCall {
     spm.match = p.match; spm.mismatch = p.mismatch; spm.go = p.go; spm.ge = p.ge; spm.nt = nt; spm.exact = exact ? 1u : 0u; spm.ncap = ncap - 8u;
     spm.trim_left = TL; spm.trim_right = TR; spm.use_votes = 1u;
     spm.split_prefix = kn.sweeps_alone ? 1u : 0u;
-    d_qp = static_cast<const int16_t*>(ctx->d_b16tab[2].p);
-    d_lastrow = static_cast<int32_t*>(ctx->d_lastrow.p);
+    d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_PROFILE].p);
+    d_lastrow = static_cast<int32_t*>(ctx->dev[DB_LASTROW].p);
   }
 
   // The call's one synchronisation, then what its launches reported: lower-case reference windows are the caller's error, values
@@ -1372,8 +1372,8 @@ struct AlignStream : StreamCall {
 
   // geometry and the ops offsets are laid out in the pinned block they travel from: one copy, no staging
   int pin_records() {
-    HIP_TRY(ctx->h_desc.ensure(sizeof(SGeom) * (size_t)nt + sizeof(uint64_t) * (size_t)nt));
-    geom = static_cast<SGeom*>(ctx->h_desc.p);
+    HIP_TRY(ctx->pin[PB_DESC].ensure(sizeof(SGeom) * (size_t)nt + sizeof(uint64_t) * (size_t)nt));
+    geom = static_cast<SGeom*>(ctx->pin[PB_DESC].p);
     return TRACYHIP_OK;
   }
   int plan_geometry() { return plan_common(ctx, p, sp, sr, job->ref_index, nt, TL, TR, h, geom); }
@@ -1393,18 +1393,18 @@ struct AlignStream : StreamCall {
     A.layout(sizing, nt, exact, host, ops_bound);
     TRY(with_fresh_budget(ctx, [&](bool* from_cache) -> int {
       uint64_t budget = 0;
-      TRY(workspace_budget(ctx, ctx->d_lastrow.cap + ctx->d_bits.cap + ctx->d_stream.cap + ctx->d_b16tab[2].cap, &budget, from_cache));
+      TRY(workspace_budget(ctx, ctx->dev[DB_LASTROW].cap + ctx->dev[DB_BITS].cap + ctx->dev[DB_STREAM].cap + ctx->dev[DB_B16TAB_PROFILE].cap, &budget, from_cache));
       const uint64_t fixed = h.lr_tot * 4 + 64 + h.tab_tot * 2 + 64 + sizing.off;
       if (fixed > budget) return kStreamNo;
       words_cap = band_words_cap(rows_total, nt, budget - fixed);
-      HIP_TRY(ctx->d_lastrow.ensure(h.lr_tot * 4 + 64));
-      HIP_TRY(ctx->d_b16tab[2].ensure(h.tab_tot * sizeof(int16_t) + 64));
-      HIP_TRY(ctx->d_bits.ensure(words_cap + 64));
-      HIP_TRY(ctx->d_stream.ensure(sizing.off + 256));
+      HIP_TRY(ctx->dev[DB_LASTROW].ensure(h.lr_tot * 4 + 64));
+      HIP_TRY(ctx->dev[DB_B16TAB_PROFILE].ensure(h.tab_tot * sizeof(int16_t) + 64));
+      HIP_TRY(ctx->dev[DB_BITS].ensure(words_cap + 64));
+      HIP_TRY(ctx->dev[DB_STREAM].ensure(sizing.off + 256));
       return TRACYHIP_OK;
     }));
     Arena arena;
-    arena.base = static_cast<char*>(ctx->d_stream.p);
+    arena.base = static_cast<char*>(ctx->dev[DB_STREAM].p);
     A.layout(arena, nt, exact, host, ops_bound);
     return TRACYHIP_OK;
   }
@@ -1412,8 +1412,8 @@ struct AlignStream : StreamCall {
   // payloads and result arrays: the caller's (device memory) or staged; references encoded once; records uploaded
   int bind() {
     const uint64_t ep = seqset_extent(sp), er = seqset_extent(sr);
-    TRY(stage_in(ctx, ctx->d_in1, sp.data, ep * 4, mem, &d_prof));
-    TRY(stage_in(ctx, ctx->d_in2, sr.data, er, mem, &d_ref));
+    TRY(stage_in(ctx, ctx->dev[DB_IN1], sp.data, ep * 4, mem, &d_prof));
+    TRY(stage_in(ctx, ctx->dev[DB_IN2], sr.data, er, mem, &d_ref));
     TRY(encode_references(static_cast<const uint8_t*>(d_ref), er));
     std::memcpy(geom + nt, out->ops_offset, sizeof(uint64_t) * (size_t)nt);
     TRY(upload_records(A.sc, A.ops_off, sizeof(uint64_t) * (size_t)nt));
@@ -1489,8 +1489,7 @@ struct AlignStream : StreamCall {
     HIP_TRY(hipMemcpyAsync(A.dead_list, dl.data(), sizeof(uint32_t) * nd, hipMemcpyHostToDevice, st));
     TRY(scatter_all<AlignFields>(st, A.dead_list, nd, A.f, o));
     if (host) {  // (the host-planned pipeline may have re-allocated the pinned blocks: a fresh one for the lengths)
-      HIP_TRY(ctx->h_res.ensure(sizeof(uint32_t) * (size_t)nt));
-      hlen = static_cast<uint32_t*>(ctx->h_res.p);
+      HIP_TRY(ensure_into(ctx->pin[PB_RES], nt, hlen));
       HIP_TRY(hipMemcpyAsync(hlen, o.slice_len, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(ctx_sync(ctx));  // (dl is pageable)
@@ -1949,8 +1948,8 @@ struct DecStream : StreamCall {
   // what the host knows before anything runs: geometry of every trace (laid out in the pinned block it travels from), workspace
   int plan() {
     // geometry and offsets are laid out in the pinned block they travel from
-    HIP_TRY(ctx->h_desc.ensure((sizeof(SGeom) + sizeof(SGeomD)) * (size_t)nt));
-    geom = static_cast<SGeom*>(ctx->h_desc.p);
+    HIP_TRY(ctx->pin[PB_DESC].ensure((sizeof(SGeom) + sizeof(SGeomD)) * (size_t)nt));
+    geom = static_cast<SGeom*>(ctx->pin[PB_DESC].p);
     geomd = reinterpret_cast<SGeomD*>(geom + nt);
     // ---- geometry of the decompose stages (decompose_traces_legacy's, trace by trace): sums, extents and checks per slice of the batch, then
     // the records with their running offsets from the slices' bases -- inside plan_common's two passes (PlanHooks) ----
@@ -2047,20 +2046,20 @@ struct DecStream : StreamCall {
     A.layout(sizing, z);
     TRY(with_fresh_budget(ctx, [&](bool* from_cache) -> int {
       uint64_t budget = 0;
-      TRY(workspace_budget(ctx, ctx->d_lastrow.cap + ctx->d_bits.cap + ctx->d_stream.cap + ctx->d_b16tab[2].cap + ctx->d_b16tab[0].cap, &budget, from_cache));
+      TRY(workspace_budget(ctx, ctx->dev[DB_LASTROW].cap + ctx->dev[DB_BITS].cap + ctx->dev[DB_STREAM].cap + ctx->dev[DB_B16TAB_PROFILE].cap + ctx->dev[DB_B16TAB_ALLELE0].cap, &budget, from_cache));
       const uint64_t lr_words = std::max(h.lr_tot, alr_tot);
       const uint64_t fixed = lr_words * 4 + 64 + h.tab_tot * 2 + atab_tot * 2 + 128 + sizing.off;
       if (fixed > budget) return kStreamNo;
       words_cap = band_words_cap(std::max(rows_traces, rows_alleles), 2ull * nt, budget - fixed);
-      HIP_TRY(ctx->d_lastrow.ensure(lr_words * 4 + 64));
-      HIP_TRY(ctx->d_b16tab[2].ensure(h.tab_tot * sizeof(int16_t) + 64));
-      HIP_TRY(ctx->d_b16tab[0].ensure(atab_tot * sizeof(int16_t) + 64));
-      HIP_TRY(ctx->d_bits.ensure(words_cap + 64));
-      HIP_TRY(ctx->d_stream.ensure(sizing.off + 256));
+      HIP_TRY(ctx->dev[DB_LASTROW].ensure(lr_words * 4 + 64));
+      HIP_TRY(ctx->dev[DB_B16TAB_PROFILE].ensure(h.tab_tot * sizeof(int16_t) + 64));
+      HIP_TRY(ctx->dev[DB_B16TAB_ALLELE0].ensure(atab_tot * sizeof(int16_t) + 64));
+      HIP_TRY(ctx->dev[DB_BITS].ensure(words_cap + 64));
+      HIP_TRY(ctx->dev[DB_STREAM].ensure(sizing.off + 256));
       return TRACYHIP_OK;
     }));
     Arena arena;
-    arena.base = static_cast<char*>(ctx->d_stream.p);
+    arena.base = static_cast<char*>(ctx->dev[DB_STREAM].p);
     A.layout(arena, z);
 
     return TRACYHIP_OK;
@@ -2246,9 +2245,9 @@ struct DecStream : StreamCall {
       hipLaunchKernelGGL(cq_rows_kernel, dim3((unsigned)((2 * z.bext + 4095) / 4096)), dim3(256), 0, st, static_cast<const uint8_t*>(A.seqs2), 2 * z.bext, A.cq_flag);
     }
     HIP_TRY(hipGetLastError());
-    d_aqp = static_cast<const int16_t*>(ctx->d_b16tab[0].p);
+    d_aqp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_ALLELE0].p);
     TRY(timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, atab_tot * 2));
-    HIP_TRY(launch_b16_tables(A.atd, 2 * nt, A.seqs2, true, p.match, p.mismatch, sub_limit(&p), kTagShift, const_cast<int16_t*>(d_aqp), static_cast<int32_t*>(ctx->d_err.p), st));
+    HIP_TRY(launch_b16_tables(A.atd, 2 * nt, A.seqs2, true, p.match, p.mismatch, sub_limit(&p), kTagShift, const_cast<int16_t*>(d_aqp), static_cast<int32_t*>(ctx->dev[DB_ERR].p), st));
     TRY(timing_end(ctx));
     // (shared kept rows leave holes in the prefix launch: its pairs as a list, as for the later tiers)
     const bool share = !kn.no_front_lists && 2 * nt >= kn.front_list_min;
@@ -2264,7 +2263,7 @@ struct DecStream : StreamCall {
       DpArgs a{};
       a.pairs = sc.pre;
       if (share) { a.index = sc.flist; a.count = sc.fcount + 2; }
-      a.a1 = A.seqs2; a.a2 = d_cq_ref; a.err = static_cast<int32_t*>(ctx->d_err.p);
+      a.a1 = A.seqs2; a.a2 = d_cq_ref; a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
       a.match = p.match; a.mismatch = p.mismatch; a.go = p.go; a.ge = p.ge; a.hfree = p.hfree; a.vfree = p.vfree;
       a.qlimit = sub_limit(&p);
       a.special_blocks = kn.no_compact ? nullptr : A.cq_special;
