@@ -121,4 +121,14 @@ void pr_a12_band(uint64_t n, const int64_t* in, int64_t* out) {
   }
 }
 
+// in: sb sstar ops_len -> certified
+void pr_exact_certified(uint64_t n, const int64_t* in, int64_t* out) {
+  for (uint64_t i = 0; i < n; ++i, in += 3, out += 1) out[0] = s_exact_certified((int32_t)in[0], (int32_t)in[1], (uint32_t)in[2]);
+}
+
+// in: sb bound ops_len -> certified (sb: an int32 score, as both callers hold it; the bound is 64-bit)
+void pr_a12_certified(uint64_t n, const int64_t* in, int64_t* out) {
+  for (uint64_t i = 0; i < n; ++i, in += 3, out += 1) out[0] = s_a12_certified((int32_t)in[0], in[1], (uint32_t)in[2]);
+}
+
 }  // extern "C"

@@ -271,11 +271,17 @@ def test_align_final_alignment_on_the_certified_band(monkeypatch):
     try:
         c.set_option("band_w", 0)  # whole matrices
         ref = c.align_traces(list(profs), refl, SC, 50, 50, exact_scores=True)
+        assert c.last_call_stats()["final_banded"] == 0
         for wband in ("48", "12", "2", None):  # None: the default (and the stream-ordered pipeline)
             c.set_option("band_w", -1 if wband is None else wband)
             for lanes in (1, 2):
                 c.set_lanes(lanes)
                 got = c.align_traces(list(profs), refl, SC, 50, 50, exact_scores=True)
+                said = c.last_call_stats()
+                if wband == "2":  # trace 2, the unrelated profile, is hundreds below what R6 asks of W = 2: repeated in every implementation
+                    assert said["final_banded"] >= 1 and 1 <= said["final_repeated"] <= said["final_banded"], (said, lanes)
+                elif wband is not None:
+                    assert said["final_repeated"] <= said["final_banded"], (said, wband, lanes)
                 for k in keys:
                     assert np.array_equal(got[k], ref[k]), (k, wband, lanes)
                 assert got["btr"] == ref["btr"], (wband, lanes)

@@ -237,6 +237,54 @@ def test_decompose_beyond_the_default_size_class(ctx):
                 assert int(got["score%d" % k][i]) == w["score%d" % k] and got["btr%d" % k][i] == w["btr%d" % k], (maxindel, i, k)
 
 
+def test_allele1_vs_allele2_repeats_what_its_band_cannot_certify(ctx):
+    """Allele 1 against allele 2 runs on the diagonals [-W, W] of s_a12_band and is kept only where its score beats the band's bound
+    (s_a12_certified); a het indel longer than the band leaves the optimum at or below that bound, and a banded score is never above
+    the optimum, so those pairs MUST fail the certificate and be repeated on the whole matrix.  Results against the oracle on both
+    pipelines; the host-planned one counts the repeats, the stream-ordered one hands these traces over (SD_A12_CHECK)."""
+    from indigo_oracle import decompose_trace, trimmed_seq
+    from test_plan_rules_host import a12_band_ref
+    from tracy_amd import capi, hostlib
+    sigs, refs, bcs = [], [], []
+    for seed in range(700, 716):
+        ref, sig, pos, indel = hostlib.synth_decompose(seed, 900, 420, 200, 0, 0.6)
+        pri, sec, con, bcpos = hostlib.basecall(sig, pos, 0.33)
+        sigs.append(sig); refs.append(ref); bcs.append((pri, sec, bcpos))
+    nd = len(sigs)
+    profs = [hostlib.create_profile(sigs[i], bcs[i][2], bcs[i][0], bcs[i][1], 0, 0) for i in range(nd)]
+    want = [decompose_trace(sigs[i], bcs[i][2], bcs[i][0], bcs[i][1], refs[i], SC, maxindel=1000) for i in range(nd)]
+    must = 0  # traces whose optimum does not beat the bound of their band
+    for w in want:
+        assert w["status"] == 0
+        ln = len(trimmed_seq(w["primary"], 50, 50))
+        W, bound = a12_band_ref(np.int64(ln), max(SC[0], SC[1], 0), SC[2], SC[3], w["score0"], w["score1"])
+        must += int(w["score2"] <= bound)
+    assert 1 <= must < nd
+
+    def run():
+        hbc = capi.HostBaseCalls(sigs, [b[2] for b in bcs], [b[0] for b in bcs], [b[1] for b in bcs])
+        got = ctx.decompose_traces(profs, hbc, refs, SC, maxindel=1000)
+        for i, w in enumerate(want):
+            assert int(got["status"][i]) == w["status"], i
+            assert got["primary"][i] == w["primary"] and got["secondary"][i] == w["secondary"], i
+            assert got["secdecomp_list"][i] == w["secdecomp"], i
+            assert got["dcp"][i] == w["dcp"], i
+            assert (float(got["fractions"][2 * i]), float(got["fractions"][2 * i + 1])) == w["af"], i
+            for k in range(3):
+                assert int(got["score%d" % k][i]) == w["score%d" % k] and got["btr%d" % k][i] == w["btr%d" % k], (i, k)
+        return ctx.last_call_stats()
+    ctx.set_option("no_stream", 1)
+    try:
+        said = run()
+    finally:
+        ctx.set_option("no_stream", 0)
+    assert said["allele_repeated"][2] >= must, (said, must)
+    assert said["allele_repeated"][2] <= said["allele_banded"][2] <= nd, said
+    assert said["allele_banded"][2] >= must, (said, must)
+    said = run()
+    assert said["fallback_traces"] >= must, (said, must)
+
+
 def test_staging_in_global_memory():
     """findBreakpoint / allelicFraction stage per-trace arrays in LDS; traces too long for it use a global scratch slice.  Forced
     here by lowering the limit (TRACYHIP_LDS_STAGE_LIMIT, read once per process): the chain tests in a child process."""

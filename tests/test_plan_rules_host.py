@@ -355,6 +355,14 @@ def test_slice_band(pr):
 
 # ---- R8: allele 1 vs allele 2 ----
 
+def a12_band_ref(ln, best, go, ge, sc1, sc2):
+    """W, bound of s_a12_band for alleles of ln > 0 bases (also what test_gpu_decompose.py expects of the band's certificate)"""
+    lost = np.maximum(best * ln - sc1, 0) + np.maximum(best * ln - sc2, 0)
+    per = best - 2 * ge
+    W = np.minimum((5 * lost // 2 + 40) // np.where(per > 0, per, 1) + 2, 90)
+    return W, best * (ln - (W + 1)) + ge * 2 * (W + 1) + 2 * go
+
+
 def test_a12_band(pr):
     rng = np.random.default_rng(11)
     ln = rng.integers(0, 3000, N)
@@ -367,13 +375,61 @@ def test_a12_band(pr):
     cols = [np.concatenate([c, edges[:, j]]) for j, c in enumerate((ln, best, go, ge, sc1, sc2))]
     ln, best, go, ge, sc1, sc2 = cols
     got = call(pr, "pr_a12_band", cols, 4)
-    lost = np.maximum(best * ln - sc1, 0) + np.maximum(best * ln - sc2, 0)
-    per = best - 2 * ge
-    W = np.minimum((5 * lost // 2 + 40) // np.where(per > 0, per, 1) + 2, 90)
-    bound = best * (ln - (W + 1)) + ge * 2 * (W + 1) + 2 * go
+    W, bound = a12_band_ref(ln, best, go, ge, sc1, sc2)
     z = ln == 0
     check(got, np.where(z, 0, -W), np.where(z, 0, W), np.where(z, 0, pick_k(-W, W)), np.where(z, 0, bound))
     e = got[N:]
     assert list(e[0]) == [0, 0, 0, 0]
     assert list(e[1][:3]) == [-90, 90, 12] and e[1, 3] == 1000 - 91 - 4 * 2 * 91 - 20
     assert list(e[2][:3]) == [-6, 6, 4]  # nothing lost: W = 40 // (1 + 2 * 4) + 2
+
+
+# ---- R12 / R13: the certificates of the bands whose score is known beforehand / bounded (both also need a walk that stayed inside) ----
+
+I32_MIN, I32_MAX = -(1 << 31), (1 << 31) - 1
+
+
+def test_exact_certified(pr):
+    """sb == S* and ops_len != 0: every S* of a grid with negative scores and the ends of the int32 range, the banded score at it and
+    at both neighbours (where they are int32 values), and INT32_MIN / INT32_MAX as banded scores against every S*"""
+    rng = np.random.default_rng(13)
+    sstar = np.concatenate([rng.integers(-5000, 5000, 1000), [-1, 0, 1, -300, I32_MIN, I32_MIN + 1, I32_MAX - 1, I32_MAX]])
+    cols = []
+    for delta in (-1, 0, 1):
+        sb = sstar + delta
+        keep = (sb >= I32_MIN) & (sb <= I32_MAX)
+        cols.append((sb[keep], sstar[keep]))
+    for edge in (I32_MIN, I32_MAX):
+        cols.append((np.full(sstar.size, edge), sstar))
+    sb, sstar = (np.concatenate([c[j] for c in cols]) for j in range(2))
+    for ops in (0, 1, 4000):
+        got = call(pr, "pr_exact_certified", [sb, sstar, np.full(sb.size, ops)], 1)
+        check(got, (sb == sstar) & (ops != 0))
+    one = lambda *row: int(call(pr, "pr_exact_certified", [[x] for x in row], 1)[0, 0])
+    assert one(-40, -40, 1) == 1 and one(-40, -40, 0) == 0 and one(-41, -40, 1) == 0 and one(-39, -40, 1) == 0
+    assert one(I32_MIN, I32_MIN, 1) == 1 and one(I32_MAX, I32_MAX, 1) == 1 and one(I32_MIN, I32_MAX, 1) == 0 and one(I32_MAX, I32_MIN, 1) == 0
+
+
+def test_a12_certified(pr):
+    """sb > bound and ops_len != 0 (the bound is 64-bit: the comparison must not narrow it): the banded score at the bound and at both
+    neighbours, negative scores, INT32_MIN / INT32_MAX as banded scores, bounds just outside and far outside the int32 range"""
+    rng = np.random.default_rng(14)
+    bound = np.concatenate([rng.integers(-5000, 5000, 1000), [-61, -1, 0, 1, I32_MIN, I32_MIN + 1, I32_MAX - 1, I32_MAX]])
+    cols = []
+    for delta in (-1, 0, 1):
+        sb = bound + delta
+        keep = (sb >= I32_MIN) & (sb <= I32_MAX)
+        cols.append((sb[keep], bound[keep]))
+    wide = np.array([I32_MIN - 1, I32_MIN - (1 << 32), -(1 << 62), I32_MAX + 1, I32_MAX + (1 << 32), 1 << 62,
+                     (1 << 32) - 5, -(1 << 32) + 5])  # (the last two: what a 32-bit comparison would read as -5 / 5)
+    for edge in (I32_MIN, -108, -5, 0, 5, I32_MAX):
+        cols.append((np.full(bound.size, edge), bound))
+        cols.append((np.full(wide.size, edge), wide))
+    sb, bound = (np.concatenate([c[j] for c in cols]) for j in range(2))
+    for ops in (0, 1, 4000):
+        got = call(pr, "pr_a12_certified", [sb, bound, np.full(sb.size, ops)], 1)
+        check(got, (sb > bound) & (ops != 0))
+    one = lambda *row: int(call(pr, "pr_a12_certified", [[x] for x in row], 1)[0, 0])
+    assert one(-60, -61, 1) == 1 and one(-61, -61, 1) == 0 and one(-62, -61, 1) == 0 and one(-60, -61, 0) == 0
+    assert one(I32_MIN, I32_MIN - 1, 1) == 1 and one(I32_MAX, I32_MAX + 1, 1) == 0 and one(I32_MAX, I32_MAX, 1) == 0
+    assert one(0, (1 << 32) - 5, 1) == 0 and one(0, -(1 << 32) + 5, 1) == 1

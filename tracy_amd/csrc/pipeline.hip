@@ -40,6 +40,61 @@ struct StageClock {  // TRACYHIP_HOST_TIMERS: wall time from one mark to the nex
   ~StageClock() { delete cur; }
 };
 
+constexpr auto kNoHook = [](const DpProblem&) { return TRACYHIP_OK; };  // BandStage::run: nothing to do between verdict and rest
+// One band stage of the host-planned pipelines.  The pairs a band form takes (on[t] != 0) run there and are checked afterwards; `rest`
+// collects what runs on the whole-matrix kernels instead, cut from the problem `from`: first the pairs that are not on the band
+// (partition), then those whose banded result fails its certificate (verdict) -- pair t as whole(t), on the strip height k[t].
+template <class Whole>
+struct BandStage {
+  tracyhip_ctx* ctx;
+  const std::vector<int>& k;
+  Whole whole;
+  DpProblem rest;
+  uint32_t nbanded = 0;
+  std::vector<int32_t> h_sc;   // what the verdict read back: scores ...
+  std::vector<uint32_t> h_ol;  // ... and op lengths of every pair
+  BandStage(tracyhip_ctx* c, const DpProblem& from, const std::vector<int>& k_, Whole w) : ctx(c), k(k_), whole(w) {
+    rest.mode = from.mode; rest.a1_profile = from.a1_profile; rest.d_a1 = from.d_a1; rest.d_a2 = from.d_a2; rest.cq_codes = from.cq_codes;
+  }
+  void add(uint32_t t) { rest.desc.push_back(whole(t)); rest.k.push_back(k[t]); }
+  void partition(const std::vector<int>& on) {  // (a filled Band16Job::k: 0 = not on the band)
+    for (uint32_t t = 0; t < on.size(); ++t)
+      if (on[t] == 0) add(t);
+    nbanded = (uint32_t)(on.size() - rest.desc.size());
+  }
+  // Scores and op lengths of the band launch come back in one wait; a pair on the band whose certificate ok(t, score, ops_len) fails
+  // joins the rest.  Adds to the stage's two counters.
+  template <class On, class Ok>
+  int verdict(const int32_t* d_score, const uint32_t* d_len, const On& on, Ok ok, uint32_t& banded, uint32_t& repeated, uint32_t& nfail) {
+    const size_t nt = on.size();
+    h_sc.resize(nt);
+    h_ol.resize(nt);
+    HIP_TRY(hipMemcpyAsync(h_sc.data(), d_score, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(h_ol.data(), d_len, sizeof(uint32_t) * nt, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx_sync(ctx));
+    nfail = 0;
+    for (uint32_t t = 0; t < nt; ++t)
+      if (on[t] && !ok(t, h_sc[t], h_ol[t])) { add(t); ++nfail; }
+    banded += nbanded; repeated += nfail;
+    return TRACYHIP_OK;
+  }
+  // band, check, repeat: the traceback on the band (scores to d_band_score), its verdict, and the rest -- after before_rest(rest) --
+  // through run_dp (scores to d_score).  No pair on the band: the rest alone.
+  template <class Ok, class Hook>
+  int run(Band16Job& job, const tracyhip_params* prm, int32_t* d_band_score, int32_t* d_score, uint8_t* d_ops, const uint64_t* d_off, uint32_t* d_len,
+          Ok ok, uint32_t& banded, uint32_t& repeated, const char* who, const char* how, Hook before_rest, int stage = DP_PLAIN, DpCkpt* ck = nullptr) {
+    int rc;
+    if (nbanded) {
+      if ((rc = run_band16(ctx, job, prm, d_band_score, nullptr, d_ops, d_off, d_len))) return rc;
+      uint32_t nfail;
+      if ((rc = verdict(d_band_score, d_len, job.k, ok, banded, repeated, nfail))) return rc;
+      if (ctx->knobs.verbose) fprintf(stderr, "%s: %u of %zu %s, %u repeated\n", who, nbanded, job.k.size(), how, nfail);
+    }
+    if ((rc = before_rest(rest))) return rc;
+    return run_dp(ctx, rest, prm, false, true, d_score, d_ops, d_off, d_len, stage, ck);
+  }
+};
+
 // =====================================================================================================
 // Orientation + preliminary alignment of trimmed traces against their reference windows: the part `tracy align`
 // (sage.h:223-258) and `tracy decompose` (indigo.h:235-302, FASTA / indexed reference) have in common.
@@ -623,9 +678,10 @@ struct OrientRun {
         j16.d_codes = ctx->codes();
         j16.desc.resize(nt);
         j16.k.assign(nt, 0);
-        DpProblem rest;
-        rest.mode = pb.mode; rest.a1_profile = pb.a1_profile; rest.d_a1 = pb.d_a1; rest.d_a2 = pb.d_a2;
         std::vector<PairDesc> wholes(tb16_path ? nt : 0);
+        // what the band kernels do not take: the origin-tracking sweep over the sub-window / the band traceback
+        BandStage bs(ctx, pb, pb.k, [&](uint32_t t) { return ends_path ? pb.desc[t] : wholes[t]; });
+        DpProblem& rest = bs.rest;
         parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
           for (uint32_t t = lo; t < hi; ++t) {
             const PairDesc whole = pb.desc[t];
@@ -657,8 +713,7 @@ struct OrientRun {
             }
           }
         });
-        for (uint32_t t = 0; t < nt; ++t)  // what the band kernels do not take: the origin-tracking sweep over the sub-window / the band traceback
-          if (j16.k[t] == 0) { rest.desc.push_back(ends_path ? pb.desc[t] : wholes[t]); rest.k.push_back(pb.k[t]); }
+        bs.partition(j16.k);
         if (ends_path) {
           bool fits = true;  // (the pre-check used an upper bound of the sub-window; windows cut at c_e can only be shorter)
           for (size_t q = 0; q < rest.desc.size() && fits; ++q) fits = origin_ok(&p, rest.desc[q].m, rest.desc[q].n, rest.k[q]);
@@ -666,7 +721,7 @@ struct OrientRun {
           HIP_TRY(hipMemcpyAsync(d_shift, shift.data(), sizeof(uint32_t) * (size_t)nt, hipMemcpyHostToDevice, st));
           DpCkpt oc;
           oc.d_ends = d_ends;
-          if (rest.desc.size() < nt) {
+          if (bs.nbanded) {
             HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
             if ((rc = run_band16(ctx, j16, &p, nullptr, d_ends, nullptr, nullptr, nullptr))) return rc;
           }
@@ -677,29 +732,22 @@ struct OrientRun {
         } else {
           sco.mark("o.h stage2 run_band16 + check");
           // traceback on the band; a pair whose banded score is not S* (or whose walk left the band: no ops) is repeated with the rest
-          if (rest.desc.size() < nt) {
-            int32_t* d_sb;
+          int32_t* d_sb = nullptr;
+          if (bs.nbanded) {
             HIP_TRY(ensure_into(ctx->dev[DB_BAND_SCORES], nt, d_sb));
             HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
-            if ((rc = run_band16(ctx, j16, &p, d_sb, nullptr, in.d_ops, in.d_ops_off, in.d_ops_len))) return rc;
-            std::vector<int32_t> h_sb(nt);
-            std::vector<uint32_t> h_ol(nt);
-            HIP_TRY(hipMemcpyAsync(h_sb.data(), d_sb, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(h_ol.data(), in.d_ops_len, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx_sync(ctx));
-            uint32_t nfail = 0;
-            const size_t nb16 = nt - rest.desc.size();
-            for (uint32_t t = 0; t < nt; ++t)
-              if (j16.k[t] && (h_sb[t] != h_pre[t] || h_ol[t] == 0)) { rest.desc.push_back(wholes[t]); rest.k.push_back(pb.k[t]); ++nfail; }
-            ctx->stats.prelim_banded += (uint32_t)nb16; ctx->stats.prelim_repeated += nfail;
-            if (ctx->knobs.verbose) fprintf(stderr, "preliminary alignment: %zu of %u on the band, %u repeated\n", nb16, nt, nfail);
           }
-          if (use_front) {  // the orientation stage of the pruned sweep leaves no wavefront checkpoints: sweep the pair's strand before its band traceback
+          // the orientation stage of the pruned sweep leaves no wavefront checkpoints: sweep the pair's strand before its band traceback
+          auto resweep_rest = [&](const DpProblem& left) {
             std::vector<std::pair<uint32_t, int>> resweep;
-            for (auto const& d : rest.desc) resweep.emplace_back(d.out, h_rc[d.out] ? 1 : 0);
-            if (!resweep.empty() && (rc = run_stage1(resweep, DP_CKPT))) return rc;
-          }
-          if ((rc = run_dp(ctx, rest, &p, false, true, nullptr, in.d_ops, in.d_ops_off, in.d_ops_len, DP_BAND, &ck))) return rc;
+            if (use_front)
+              for (auto const& d : left.desc) resweep.emplace_back(d.out, h_rc[d.out] ? 1 : 0);
+            return resweep.empty() ? (int)TRACYHIP_OK : run_stage1(resweep, DP_CKPT);
+          };
+          if ((rc = bs.run(j16, &p, d_sb, nullptr, in.d_ops, in.d_ops_off, in.d_ops_len,
+                           [&](uint32_t t, int32_t sb, uint32_t len) { return s_exact_certified(sb, h_pre[t], len); }, ctx->stats.prelim_banded,
+                           ctx->stats.prelim_repeated, "preliminary alignment", "on the band", resweep_rest, DP_BAND, &ck)))
+            return rc;
         }
         if (in.d_score) HIP_TRY(hipMemcpy(in.d_score, h_pre.data(), sizeof(int32_t) * (size_t)nt, hipMemcpyHostToDevice));
       } else if (use_band) {
@@ -947,6 +995,7 @@ struct AlignRun {
       j16.d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_PROFILE].p);
       j16.d_codes = ctx->codes();
       std::vector<PairDesc> whole(nt);  // every pair as a whole-matrix problem (what a pair that does not certify is repeated as)
+      std::vector<int> whole_k(nt);
       pb.desc.clear();
       pb.k.clear();
       for (uint32_t t = 0; t < nt; ++t) {
@@ -962,7 +1011,7 @@ struct AlignRun {
         d.flags = oo.rc[t] ? PAIR_A2_REVCOMP : 0;
         d.out = t;
         whole[t] = d;
-        int kt = choose_k(d.m, MODE_QP);
+        int kt = whole_k[t] = choose_k(d.m, MODE_QP);
         if (b16 && bandW > 0) {
           const SFinalBand fb = s_final_band(d.m, d.n, band_of[t]);
           if (fb.K) {
@@ -1042,36 +1091,29 @@ struct AlignRun {
                        static_cast<const uint64_t*>(ctx->dev[DB_OPS_OFF].p), static_cast<uint32_t*>(d_olen))))
         return rc;
       if (nbanded) {
-        std::vector<int32_t> h_top(nt), h_sb(nt);
-        std::vector<uint32_t> h_ol(nt);
+        // both band forms are certified together (the top rides with the verdict's wait); what fails is a launch of its own
+        std::vector<int32_t> h_top(nt);
         HIP_TRY(hipMemcpyAsync(h_top.data(), d_top, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_sb.data(), d_final_sc, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_ol.data(), d_olen, sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx_sync(ctx));
-        std::vector<PairDesc> again;
-        std::vector<int> again_k;
-        for (uint32_t t = 0; t < nt; ++t) {
-          if (!banded[t] || s_final_certified(h_sb[t], h_top[t], p.ge, band_of[t], h_ol[t])) continue;
-          again.push_back(whole[t]);
-          again_k.push_back(choose_k(whole[t].m, MODE_QP));
-        }
-        ctx->stats.final_banded += nbanded; ctx->stats.final_repeated += (uint32_t)again.size();
+        BandStage again(ctx, pb, whole_k, [&](uint32_t t) { return whole[t]; });
+        again.nbanded = nbanded;
+        uint32_t nfail;
+        if ((rc = again.verdict(static_cast<const int32_t*>(d_final_sc), static_cast<const uint32_t*>(d_olen), banded,
+                                [&](uint32_t t, int32_t sb, uint32_t len) { return s_final_certified(sb, h_top[t], p.ge, band_of[t], len); },
+                                ctx->stats.final_banded, ctx->stats.final_repeated, nfail)))
+          return rc;
         if (ctx->knobs.verbose) {
+          const std::vector<int32_t>& h_sb = again.h_sc;
           int64_t wsum = 0, lsum = 0, lmax = 0, xmax = -1000000;
           for (uint32_t t = 0; t < nt; ++t) {
             wsum += band_of[t]; const int64_t l = (int64_t)h_top[t] - h_sb[t]; lsum += l; lmax = std::max(lmax, l);
             if (oo.gap.size() == nt) xmax = std::max<int64_t>(xmax, l / (-(int64_t)p.ge) - (int64_t)oo.gap[t]);
           }
-          fprintf(stderr, "band: %u of %u pairs banded (%zu on the band kernels), %zu repeated; mean W %.1f, mean top - S_b %.1f, max %lld; max needed W - gap of the trimmed alignment %lld\n", nbanded, nt,
-                  j16.desc.size(), again.size(), (double)wsum / nt, (double)lsum / nt, (long long)lmax, (long long)xmax);
+          fprintf(stderr, "band: %u of %u pairs banded (%zu on the band kernels), %u repeated; mean W %.1f, mean top - S_b %.1f, max %lld; max needed W - gap of the trimmed alignment %lld\n", nbanded, nt,
+                  j16.desc.size(), nfail, (double)wsum / nt, (double)lsum / nt, (long long)lmax, (long long)xmax);
         }
-        if (!again.empty()) {
-          pb.desc.swap(again);
-          pb.k.swap(again_k);
-          if ((rc = run_dp(ctx, pb, &p, false, true, static_cast<int32_t*>(d_final_sc), static_cast<uint8_t*>(d_ops),
-                           static_cast<const uint64_t*>(ctx->dev[DB_OPS_OFF].p), static_cast<uint32_t*>(d_olen))))
-            return rc;
-        }
+        if (nfail && (rc = run_dp(ctx, again.rest, &p, false, true, static_cast<int32_t*>(d_final_sc), static_cast<uint8_t*>(d_ops),
+                                  static_cast<const uint64_t*>(ctx->dev[DB_OPS_OFF].p), static_cast<uint32_t*>(d_olen))))
+          return rc;
       }
     }
 
@@ -1738,7 +1780,6 @@ struct DecomposeRun {
       if ((rc = io(out->ops[k], cap ? cap : 1, false, &d_opsK[k]))) return rc;
       if ((rc = io(out->ops_len[k], sizeof(uint32_t) * (size_t)nt, false, &d_lenK[k]))) return rc;
     }
-    StageClock sc6;
     return TRACYHIP_OK;
   }
 
@@ -1803,16 +1844,7 @@ struct DecomposeRun {
   // 6.b, 6.c: S* and c_e of gotoh(allele, window) by the pruned sweep (what fails: swept in full), the sub-window they allow
   int allele_locate(Allele& A, int k) {
     int rc;
-    const void* seq = A.seq;
     DpProblem& pb = A.pb;
-    const bool b16 = A.b16;
-    std::vector<B16TableDesc>& td = A.td;
-    std::vector<int32_t>& h_s1 = A.h_s1;
-    std::vector<int64_t>& gap_of = A.gap_of;
-    std::vector<uint32_t>& shift = A.shift;
-    uint32_t*& d_shift = A.d_shift;
-    bool& subwin = A.subwin;
-    (void)seq; (void)b16; (void)td; (void)h_s1; (void)gap_of; (void)shift; (void)d_shift; (void)subwin;
     std::vector<RowEndDesc> hre(nt);
     uint64_t lr_tot = 0;
     for (uint32_t t = 0; t < nt; ++t) { pb.desc[t].lastrow_off = lr_tot; hre[t] = RowEndDesc{lr_tot, rn[t], 0}; lr_tot += (uint64_t)rn[t] + 2; }
@@ -1821,7 +1853,7 @@ struct DecomposeRun {
     HIP_TRY(b_sw.ensure(sizeof(int32_t) * (size_t)nt + sizeof(uint32_t) * 2 * (size_t)nt));
     int32_t* d_swscore = static_cast<int32_t*>(b_sw.p);
     uint32_t* d_ce = reinterpret_cast<uint32_t*>(d_swscore + nt);
-    d_shift = d_ce + nt;
+    A.d_shift = d_ce + nt;
     if (pb.cq_codes == 4) {  // every column is one of A C G T: an all-clear block map sends every pair to the compact form
       HIP_TRY(b_zero.ensure((er >> 8) + 2));
       HIP_TRY(hipMemsetAsync(b_zero.p, 0, (er >> 8) + 2, st));
@@ -1841,7 +1873,7 @@ struct DecomposeRun {
     std::vector<int8_t> pruned(nt, 0);
     std::vector<int32_t> fscore;
     std::vector<uint32_t> fce;
-    if (b16 && !ctx->knobs.no_front) {
+    if (A.b16 && !ctx->knobs.no_front) {
       const uint32_t R = kFrontRows;
       const int64_t bestq = std::max<int64_t>(std::max<int64_t>(p.match, p.mismatch), 0);
       // (laid out by a few threads in trace order: eligibility per trace, a scan, the fill)
@@ -1871,8 +1903,8 @@ struct DecomposeRun {
           FrontDesc f{};
           f.row_off = d.lastrow_off;
           f.a2_off = d.a2_off;
-          f.tab_off = td[t].out_off + R;
-          f.tab_stride = td[t].stride;
+          f.tab_off = A.td[t].out_off + R;
+          f.tab_stride = A.td[t].stride;
           f.m_rest = d.m - R;
           f.n = d.n;
           f.flags = d.flags & PAIR_A2_REVCOMP;
@@ -1906,10 +1938,10 @@ struct DecomposeRun {
       rc = full.desc.empty() ? TRACYHIP_OK : run_dp(ctx, full, &p, false, false, d_swscore, nullptr, nullptr, nullptr, DP_CKPT, &sc);
     }
     pb.d_special = nullptr;
-    if (rc == kWiden) subwin = false;
+    if (rc == kWiden) A.subwin = false;
     else if (rc) return rc;
     sc6.mark("6.c rowend+subwindow");
-    if (subwin) {
+    if (A.subwin) {
       uint32_t npruned = 0;
       for (uint32_t t = 0; t < nt; ++t)
         if (pruned[t]) { hre[t].n = 0; ++npruned; }  // (row m of a pruned pair was never written: its c_e is the band's)
@@ -1935,15 +1967,15 @@ struct DecomposeRun {
           if (d.m == 0 || d.n == 0) continue;
           if (ce == 0) { junk_to_column1(d, h_rc[t]); continue; }
           const SubWindow sw = s_sub_window(d.m, ce, best * (int64_t)d.m, h_s[t], p.ge);
-          shift[t] = sw.a;
+          A.shift[t] = sw.a;
           d.a2_off += h_rc[t] ? (uint64_t)(d.n - ce) : (uint64_t)sw.a;  // reverse view: column c is byte n - c
           d.n = sw.n;
           d.a2_stride = d.n;
-          h_s1[t] = h_s[t];
-          gap_of[t] = sw.g;
+          A.h_s1[t] = h_s[t];
+          A.gap_of[t] = sw.g;
         }
       });
-      HIP_TRY(hipMemcpyAsync(d_shift, shift.data(), sizeof(uint32_t) * (size_t)nt, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(A.d_shift, A.shift.data(), sizeof(uint32_t) * (size_t)nt, hipMemcpyHostToDevice, st));
     }
     return TRACYHIP_OK;
   }
@@ -1951,48 +1983,37 @@ struct DecomposeRun {
   // 6.d: the two ends of gotoh(allele, window) by the origin-tracking sweep (on its band where that fits), trimReferenceSlice
   int allele_origin(Allele& A, int k) {
     int rc;
-    const void* seq = A.seq;
     DpProblem& pb = A.pb;
-    const bool b16 = A.b16;
-    std::vector<B16TableDesc>& td = A.td;
-    std::vector<int32_t>& h_s1 = A.h_s1;
-    std::vector<int64_t>& gap_of = A.gap_of;
-    std::vector<uint32_t>& shift = A.shift;
-    uint32_t*& d_shift = A.d_shift;
-    bool& subwin = A.subwin;
-    (void)seq; (void)b16; (void)td; (void)h_s1; (void)gap_of; (void)shift; (void)d_shift; (void)subwin;
     sc6.mark("6.d origin band plan+launch");
     DpCkpt oc;
     oc.d_ends = static_cast<uint32_t*>(b_ends.p);
     // the alignment ends in the last column of its sub-window with at most g gap steps behind it: diagonals n' - m - g .. n' - m + g
     Band16Job jo;
     Band16Lease<Band16Job> jo_lease(ctx, jo);
-    DpProblem rest;
-    if (b16) {
+    BandStage bs(ctx, pb, pb.k, [&](uint32_t t) { return pb.desc[t]; });
+    if (A.b16) {
       jo.kind = 1; jo.d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_ALLELE0 + k].p); jo.d_codes = d_cq_ref;
-      rest.mode = pb.mode; rest.d_a1 = pb.d_a1; rest.d_a2 = pb.d_a2; rest.cq_codes = pb.cq_codes;
       jo.desc.resize(nt);
       jo.k.assign(nt, 0);
       parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
         for (uint32_t t = lo; t < hi; ++t) {
           PairDesc d = pb.desc[t];
-          const int64_t g = gap_of[t];
+          const int64_t g = A.gap_of[t];
           const SBand b = g >= 0 ? s_end_band(d.m, d.n, g) : SBand{0, 0, 0};  // (d.n: the sub-window's n' = c_e - a)
           if (b.K && origin16_ok(&p, d.m, d.n)) {
-            d.a1_off = td[t].out_off; d.a1_stride = td[t].stride; d.ckpt_off = band_pack(b.dlo, b.dhi); d.lastrow_off = 0;
+            d.a1_off = A.td[t].out_off; d.a1_stride = A.td[t].stride; d.ckpt_off = band_pack(b.dlo, b.dhi); d.lastrow_off = 0;
             jo.desc[t] = d;
             jo.k[t] = b.K;
           }
         }
       });
-      for (uint32_t t = 0; t < nt; ++t)
-        if (jo.k[t] == 0) { rest.desc.push_back(pb.desc[t]); rest.k.push_back(pb.k[t]); }
+      bs.partition(jo.k);
       if ((rc = run_band16(ctx, jo, &p, nullptr, oc.d_ends, nullptr, nullptr, nullptr))) return rc;
     }
-    if ((rc = run_dp(ctx, b16 ? rest : pb, &p, false, false, nullptr, nullptr, nullptr, nullptr, DP_ORIGIN, &oc))) return rc;
-    if (subwin) {
+    if ((rc = run_dp(ctx, A.b16 ? bs.rest : pb, &p, false, false, nullptr, nullptr, nullptr, nullptr, DP_ORIGIN, &oc))) return rc;
+    if (A.subwin) {
       hipLaunchKernelGGL(ends_shift_kernel, dim3((nt + 255) / 256), dim3(256), 0, st, static_cast<uint32_t*>(b_ends.p),
-                         static_cast<const uint32_t*>(d_shift), nt);
+                         static_cast<const uint32_t*>(A.d_shift), nt);
     }
     hipLaunchKernelGGL(trim_from_ends_kernel, dim3((nt + 255) / 256), dim3(256), 0, st, static_cast<const uint32_t*>(b_ends.p),
                        static_cast<const uint32_t*>(b_rnfw.p), reinterpret_cast<const uint8_t*>(static_cast<const uint32_t*>(b_rnfw.p) + nt),
@@ -2001,19 +2022,9 @@ struct DecomposeRun {
   }
 
   // (no origin-tracking sweep for these pairs: the whole-matrix traceback, trimReferenceSlice on its string)
-  int allele_plain(Allele& A, int k) {
+  int allele_plain(Allele& A) {
     int rc;
-    const void* seq = A.seq;
-    DpProblem& pb = A.pb;
-    const bool b16 = A.b16;
-    std::vector<B16TableDesc>& td = A.td;
-    std::vector<int32_t>& h_s1 = A.h_s1;
-    std::vector<int64_t>& gap_of = A.gap_of;
-    std::vector<uint32_t>& shift = A.shift;
-    uint32_t*& d_shift = A.d_shift;
-    bool& subwin = A.subwin;
-    (void)seq; (void)b16; (void)td; (void)h_s1; (void)gap_of; (void)shift; (void)d_shift; (void)subwin;
-    if ((rc = run_dp(ctx, pb, &p, false, true, nullptr, static_cast<uint8_t*>(b_opsA.p), d_offA, static_cast<uint32_t*>(b_lenA.p)))) return rc;
+    if ((rc = run_dp(ctx, A.pb, &p, false, true, nullptr, static_cast<uint8_t*>(b_opsA.p), d_offA, static_cast<uint32_t*>(b_lenA.p)))) return rc;
     hipLaunchKernelGGL(trim_kernel, dim3(nt), dim3(64), 0, st, static_cast<const uint8_t*>(b_opsA.p), d_offA,
                        static_cast<const uint32_t*>(b_lenA.p), static_cast<const uint32_t*>(b_rnfw.p),
                        reinterpret_cast<const uint8_t*>(static_cast<const uint32_t*>(b_rnfw.p) + nt), TL, TR, nt,
@@ -2024,22 +2035,13 @@ struct DecomposeRun {
   // 6.e - 6.h: gotoh(allele, trimmed slice) (indigo.h:365) on the band around its known end
   int allele_slice(Allele& A, int k) {
     int rc;
-    const void* seq = A.seq;
     DpProblem& pb = A.pb;
-    const bool b16 = A.b16;
-    std::vector<B16TableDesc>& td = A.td;
-    std::vector<int32_t>& h_s1 = A.h_s1;
-    std::vector<int64_t>& gap_of = A.gap_of;
-    std::vector<uint32_t>& shift = A.shift;
-    uint32_t*& d_shift = A.d_shift;
-    bool& subwin = A.subwin;
-    (void)seq; (void)b16; (void)td; (void)h_s1; (void)gap_of; (void)shift; (void)d_shift; (void)subwin;
     sc6.mark("6.e trim readback (waits for origin)");
     HIP_TRY(hipGetLastError());
     h_trimA[k].resize(nt);
     std::vector<uint32_t> h_ends;
     HIP_TRY(hipMemcpyAsync(h_trimA[k].data(), b_trimA.p, sizeof(TrimRec) * (size_t)nt, hipMemcpyDeviceToHost, st));
-    if (b16 && A.use_origin) {
+    if (A.b16 && A.use_origin) {
       h_ends.resize(2 * (size_t)nt);
       HIP_TRY(hipMemcpyAsync(h_ends.data(), b_ends.p, sizeof(uint32_t) * 2 * (size_t)nt, hipMemcpyDeviceToHost, st));
     }
@@ -2053,135 +2055,104 @@ struct DecomposeRun {
     const uint64_t* d_offK;
     std::vector<uint64_t> offK(out->ops_offset[k], out->ops_offset[k] + nt);
     if ((rc = upload(ctx, buf(), offK, &d_offK))) return rc;
+    int32_t* const d_sc = static_cast<int32_t*>(d_scoreK[k]);
+    uint8_t* const d_ops = static_cast<uint8_t*>(d_opsK[k]);
+    uint32_t* const d_len = static_cast<uint32_t*>(d_lenK[k]);
+    if (h_ends.empty()) return run_dp(ctx, pb, &p, false, true, d_sc, d_ops, d_offK, d_len);
     // gotoh(seq, trimmed slice) (indigo.h:365): the slice holds the alignment just located, so its score is S* again, it ends in
     // column c_e - slice_begin of row m and every optimal path stays within g gap steps of that diagonal.  Banded pairs are
-    // checked against S* afterwards (a walk that left its band reports no ops); what fails goes to the whole matrix with the rest.
+    // checked against S* afterwards (s_exact_certified); what fails goes to the whole matrix with the rest.
     Band16Job jt;
     Band16Lease<Band16Job> jt_lease(ctx, jt);
-    DpProblem rest;
-    rest.mode = pb.mode; rest.d_a1 = pb.d_a1; rest.d_a2 = pb.d_a2; rest.cq_codes = pb.cq_codes;
-    if (!h_ends.empty()) {
-      jt.kind = 0; jt.d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_ALLELE0 + k].p); jt.d_codes = d_cq_ref;
-      jt.desc.resize(nt);
-      jt.k.assign(nt, 0);
-      parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
-        for (uint32_t t = lo; t < hi; ++t) {
-          PairDesc d = pb.desc[t];
-          const int64_t ce = (int64_t)h_ends[2 * t + 1] - (int64_t)h_trimA[k][t].ri;  // last column of the alignment, in the slice
-          const SBand b = s_slice_band(d.m, d.n, ce, gap_of[t], false, 0u, 0u);
-          if (b.K) {
-            d.a1_off = td[t].out_off; d.a1_stride = td[t].stride; d.ckpt_off = band_pack(b.dlo, b.dhi); d.lastrow_off = 0;
-            jt.desc[t] = d;
-            jt.k[t] = b.K;
-          }
+    jt.kind = 0; jt.d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_ALLELE0 + k].p); jt.d_codes = d_cq_ref;
+    jt.desc.resize(nt);
+    jt.k.assign(nt, 0);
+    parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
+      for (uint32_t t = lo; t < hi; ++t) {
+        PairDesc d = pb.desc[t];
+        const int64_t ce = (int64_t)h_ends[2 * t + 1] - (int64_t)h_trimA[k][t].ri;  // last column of the alignment, in the slice
+        const SBand b = s_slice_band(d.m, d.n, ce, A.gap_of[t], false, 0u, 0u);
+        if (b.K) {
+          d.a1_off = A.td[t].out_off; d.a1_stride = A.td[t].stride; d.ckpt_off = band_pack(b.dlo, b.dhi); d.lastrow_off = 0;
+          jt.desc[t] = d;
+          jt.k[t] = b.K;
         }
-      });
-      for (uint32_t t = 0; t < nt; ++t)
-        if (jt.k[t] == 0) { rest.desc.push_back(pb.desc[t]); rest.k.push_back(pb.k[t]); }
-      const size_t nb16 = nt - rest.desc.size();
-      sc6.mark("6.g run_band16 traceback");
-      if ((rc = run_band16(ctx, jt, &p, static_cast<int32_t*>(d_scoreK[k]), nullptr, static_cast<uint8_t*>(d_opsK[k]), d_offK, static_cast<uint32_t*>(d_lenK[k])))) return rc;
-      sc6.mark("6.h check readback (waits for traceback)");
-      if (nb16) {
-        std::vector<int32_t> h_sc(nt);
-        std::vector<uint32_t> h_ol(nt);
-        HIP_TRY(hipMemcpyAsync(h_sc.data(), d_scoreK[k], sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(h_ol.data(), d_lenK[k], sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx_sync(ctx));
-        uint32_t nfail = 0;
-        for (uint32_t t = 0; t < nt; ++t)
-          if (jt.k[t] && (h_sc[t] != h_s1[t] || h_ol[t] == 0)) {
-            if (ctx->knobs.verbose && nfail < 6)
-              fprintf(stderr, "  fail t=%u m=%u n=%u S1=%d got=%d len=%u g=%lld ends=(%u,%u) ri=%u rc=%d\n", t, pb.desc[t].m, pb.desc[t].n, h_s1[t], h_sc[t], h_ol[t],
-                      (long long)gap_of[t], h_ends[2 * t], h_ends[2 * t + 1], h_trimA[k][t].ri, (int)h_rc[t]);
-            rest.desc.push_back(pb.desc[t]); rest.k.push_back(pb.k[t]); ++nfail;
-          }
-        ctx->stats.allele_banded[k] += (uint32_t)nb16; ctx->stats.allele_repeated[k] += nfail;
-        if (ctx->knobs.verbose) fprintf(stderr, "decompose allele %d: %zu of %u slices banded, %u repeated\n", k, nb16, nt, nfail);
       }
-    }
-    if ((rc = run_dp(ctx, h_ends.empty() ? pb : rest, &p, false, true, static_cast<int32_t*>(d_scoreK[k]), static_cast<uint8_t*>(d_opsK[k]), d_offK,
-                     static_cast<uint32_t*>(d_lenK[k]))))
-      return rc;
-    return TRACYHIP_OK;
+    });
+    BandStage bs(ctx, pb, pb.k, [&](uint32_t t) { return pb.desc[t]; });
+    bs.partition(jt.k);
+    sc6.mark("6.g run_band16 traceback + check (waits for it)");
+    uint32_t shown = 0;
+    auto certified = [&](uint32_t t, int32_t sb, uint32_t len) {
+      const bool ok = s_exact_certified(sb, A.h_s1[t], len);
+      if (!ok && ctx->knobs.verbose && shown++ < 6)
+        fprintf(stderr, "  fail t=%u m=%u n=%u S1=%d got=%d len=%u g=%lld ends=(%u,%u) ri=%u rc=%d\n", t, pb.desc[t].m, pb.desc[t].n, A.h_s1[t], sb, len,
+                (long long)A.gap_of[t], h_ends[2 * t], h_ends[2 * t + 1], h_trimA[k][t].ri, (int)h_rc[t]);
+      return ok;
+    };
+    char who[32];
+    snprintf(who, sizeof who, "decompose allele %d", k);
+    // (no clearing of the error words in front of this launch: as it has been)
+    return bs.run(jt, &p, d_sc, d_sc, d_ops, d_offK, d_len, certified, ctx->stats.allele_banded[k], ctx->stats.allele_repeated[k], who, "slices banded", kNoHook);
   }
 
   // allele 1 vs allele 2, global (indigo.h:379-387)
   int allele12() {
     int rc;
     sc6.mark("6.i allele1v2 setup");
-    {  // allele 1 vs allele 2, global (indigo.h:379-387)
-      DpProblem pb;
-      DpProblemLease lease(ctx, pb);
-      pb.mode = use_cq ? MODE_CQ : MODE_CHAR; pb.d_a1 = d_pri; pb.d_a2 = use_cq ? static_cast<const void*>(d_cq_sd) : d_sd;
-      pb.desc.resize(nt); pb.k.resize(nt);
-      parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
-        for (uint32_t t = lo; t < hi; ++t) {
-          PairDesc d{};
-          d.a1_off = bc.bc_offset[t] + soff[t];
-          d.a2_off = bc.bc_offset[t] + soff[t];
-          d.m = sl[t]; d.n = sl[t]; d.a1_stride = sl[t]; d.a2_stride = sl[t];
-          d.out = t;
-          pb.desc[t] = d;
-          pb.k[t] = choose_k(d.m, MODE_CHAR);
-        }
-      });
-      const uint64_t* d_offK;
-      std::vector<uint64_t> offK(out->ops_offset[2], out->ops_offset[2] + nt);
-      if ((rc = upload(ctx, buf(), offK, &d_offK))) return rc;
-      // On a band (band16.h) where it can be certified afterwards (s_a12_band: the band and the bound a banded score has to beat for
-      // bits and path to be the whole matrix's); pairs that do not certify are repeated on the whole matrix.
-      Band16Job jg;
-      Band16Lease<Band16Job> jg_lease(ctx, jg);
-      DpProblem rest;
-      rest.mode = pb.mode; rest.d_a1 = pb.d_a1; rest.d_a2 = pb.d_a2; rest.cq_codes = pb.cq_codes;
-      const bool b16g = use_cq && !td_pri.empty() && pglobal.ge < 0 && pglobal.go <= 0 && !ctx->knobs.no_band16;
-      std::vector<int64_t> bound_of(nt, 0);
-      if (b16g) {
-        std::vector<int32_t> h_a[2] = {std::vector<int32_t>(nt), std::vector<int32_t>(nt)};
-        for (int k = 0; k < 2; ++k) HIP_TRY(hipMemcpyAsync(h_a[k].data(), d_scoreK[k], sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx_sync(ctx));
-        jg.kind = 0; jg.d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_ALLELE0].p); jg.d_codes = d_cq_sd;
-        const int64_t best = std::max<int64_t>(std::max<int64_t>(pglobal.match, pglobal.mismatch), 0);
-        jg.desc.resize(nt);
-        jg.k.assign(nt, 0);
-        parallel_for(nt, [&](uint32_t lo_, uint32_t hi_, uint32_t) {
-         for (uint32_t t = lo_; t < hi_; ++t) {
-          PairDesc d = pb.desc[t];  // (d.m = d.n = sl[t])
-          const SA12Band b = s_a12_band(d.m, best, pglobal.go, pglobal.ge, h_a[0][t], h_a[1][t]);
-          bound_of[t] = b.bound;
-          if (b.K) {
-            d.a1_off = td_pri[t].out_off; d.a1_stride = td_pri[t].stride; d.ckpt_off = band_pack(b.dlo, b.dhi); d.lastrow_off = 0;
-            jg.desc[t] = d;
-            jg.k[t] = b.K;
-          }
-         }
-        });
-        for (uint32_t t = 0; t < nt; ++t)
-          if (jg.k[t] == 0) { rest.desc.push_back(pb.desc[t]); rest.k.push_back(pb.k[t]); }
-        const size_t nb16 = nt - rest.desc.size();
-        HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
-        sc6.mark("6.j allele1v2 run_band16");
-        if ((rc = run_band16(ctx, jg, &pglobal, static_cast<int32_t*>(d_scoreK[2]), nullptr, static_cast<uint8_t*>(d_opsK[2]), d_offK, static_cast<uint32_t*>(d_lenK[2])))) return rc;
-        if (nb16) {
-          std::vector<int32_t> h_sc(nt);
-          std::vector<uint32_t> h_ol(nt);
-          HIP_TRY(hipMemcpyAsync(h_sc.data(), d_scoreK[2], sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-          HIP_TRY(hipMemcpyAsync(h_ol.data(), d_lenK[2], sizeof(uint32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
-          HIP_TRY(ctx_sync(ctx));
-          uint32_t nfail = 0;
-          for (uint32_t t = 0; t < nt; ++t)
-            if (jg.k[t] && ((int64_t)h_sc[t] <= bound_of[t] || h_ol[t] == 0)) { rest.desc.push_back(pb.desc[t]); rest.k.push_back(pb.k[t]); ++nfail; }
-          ctx->stats.allele_banded[2] += (uint32_t)nb16; ctx->stats.allele_repeated[2] += nfail;
-          if (ctx->knobs.verbose) fprintf(stderr, "decompose allele 1 vs 2: %zu of %u pairs banded, %u repeated\n", nb16, nt, nfail);
+    DpProblem pb;
+    DpProblemLease lease(ctx, pb);
+    pb.mode = use_cq ? MODE_CQ : MODE_CHAR; pb.d_a1 = d_pri; pb.d_a2 = use_cq ? static_cast<const void*>(d_cq_sd) : d_sd;
+    pb.desc.resize(nt); pb.k.resize(nt);
+    parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
+      for (uint32_t t = lo; t < hi; ++t) {
+        PairDesc d{};
+        d.a1_off = bc.bc_offset[t] + soff[t];
+        d.a2_off = bc.bc_offset[t] + soff[t];
+        d.m = sl[t]; d.n = sl[t]; d.a1_stride = sl[t]; d.a2_stride = sl[t];
+        d.out = t;
+        pb.desc[t] = d;
+        pb.k[t] = choose_k(d.m, MODE_CHAR);
+      }
+    });
+    const uint64_t* d_offK;
+    std::vector<uint64_t> offK(out->ops_offset[2], out->ops_offset[2] + nt);
+    if ((rc = upload(ctx, buf(), offK, &d_offK))) return rc;
+    int32_t* const d_sc = static_cast<int32_t*>(d_scoreK[2]);
+    uint8_t* const d_ops = static_cast<uint8_t*>(d_opsK[2]);
+    uint32_t* const d_len = static_cast<uint32_t*>(d_lenK[2]);
+    const bool b16g = use_cq && !td_pri.empty() && pglobal.ge < 0 && pglobal.go <= 0 && !ctx->knobs.no_band16;
+    if (!b16g) return run_dp(ctx, pb, &pglobal, false, true, d_sc, d_ops, d_offK, d_len);
+    // On a band (band16.h) where it can be certified afterwards (s_a12_band: the band and the bound a banded score has to beat for
+    // bits and path to be the whole matrix's; s_a12_certified); pairs that do not certify are repeated on the whole matrix.
+    Band16Job jg;
+    Band16Lease<Band16Job> jg_lease(ctx, jg);
+    std::vector<int64_t> bound_of(nt, 0);
+    std::vector<int32_t> h_a[2] = {std::vector<int32_t>(nt), std::vector<int32_t>(nt)};
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipMemcpyAsync(h_a[k].data(), d_scoreK[k], sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx_sync(ctx));
+    jg.kind = 0; jg.d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_ALLELE0].p); jg.d_codes = d_cq_sd;
+    const int64_t best = std::max<int64_t>(std::max<int64_t>(pglobal.match, pglobal.mismatch), 0);
+    jg.desc.resize(nt);
+    jg.k.assign(nt, 0);
+    parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t) {
+      for (uint32_t t = lo; t < hi; ++t) {
+        PairDesc d = pb.desc[t];  // (d.m = d.n = sl[t])
+        const SA12Band b = s_a12_band(d.m, best, pglobal.go, pglobal.ge, h_a[0][t], h_a[1][t]);
+        bound_of[t] = b.bound;
+        if (b.K) {
+          d.a1_off = td_pri[t].out_off; d.a1_stride = td_pri[t].stride; d.ckpt_off = band_pack(b.dlo, b.dhi); d.lastrow_off = 0;
+          jg.desc[t] = d;
+          jg.k[t] = b.K;
         }
       }
-      if ((rc = run_dp(ctx, b16g ? rest : pb, &pglobal, false, true, static_cast<int32_t*>(d_scoreK[2]), static_cast<uint8_t*>(d_opsK[2]), d_offK,
-                       static_cast<uint32_t*>(d_lenK[2]))))
-        return rc;
-    }
-
-    return TRACYHIP_OK;
+    });
+    BandStage bs(ctx, pb, pb.k, [&](uint32_t t) { return pb.desc[t]; });
+    bs.partition(jg.k);
+    HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
+    sc6.mark("6.j allele1v2 run_band16 + check");
+    return bs.run(jg, &pglobal, d_sc, d_sc, d_ops, d_offK, d_len, [&](uint32_t t, int32_t sb, uint32_t len) { return s_a12_certified(sb, bound_of[t], len); },
+                  ctx->stats.allele_banded[2], ctx->stats.allele_repeated[2], "decompose allele 1 vs 2", "pairs banded", kNoHook);
   }
 
   int results() {
@@ -2227,7 +2198,7 @@ int tracyhip::decompose_traces_legacy(tracyhip_ctx* ctx, const tracyhip_decompos
     if (A.use_origin) {
       if (A.subwin && (rc = r.allele_locate(A, k))) return rc;
       if ((rc = r.allele_origin(A, k))) return rc;
-    } else if ((rc = r.allele_plain(A, k))) return rc;
+    } else if ((rc = r.allele_plain(A))) return rc;
     if ((rc = r.allele_slice(A, k))) return rc;
   }
   if ((rc = r.allele12())) return rc;

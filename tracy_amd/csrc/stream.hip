@@ -1563,7 +1563,7 @@ __global__ void s_prelim_check_kernel(SParams p, const STrace* __restrict__ tr, 
   if (t >= p.nt) return;
   if (!dead[t] && kc[t]) {
     s_count(lc, SC_PRELIM_BANDED);
-    if (sb[t] != tr[t].sstar || len1[t] == 0u) { dead[t] |= SD_PRELIM_CHECK; s_count(lc, SC_PRELIM_REPEATED); }
+    if (!s_exact_certified(sb[t], tr[t].sstar, len1[t])) { dead[t] |= SD_PRELIM_CHECK; s_count(lc, SC_PRELIM_REPEATED); }
   }
   if (dead[t]) { len1[t] = 0u; return; }  // (nothing downstream walks its rows)
   strim[t] = tr[t].sstar;
@@ -1740,7 +1740,7 @@ __global__ void s_allele_check_kernel(SParams p, const SAllele* __restrict__ al,
   if (q >= 2u * p.nt) return;
   const uint32_t k = q / p.nt, t = q % p.nt;
   if (dead[t]) return;
-  if (score[q] != al[q].sstar || len[q] == 0u) { atomicOr(dead + t, SD_ALLELE_CHECK); s_count(lc, SC_ALLELE_REPEATED0 + (int)k); }
+  if (!s_exact_certified(score[q], al[q].sstar, len[q])) { atomicOr(dead + t, SD_ALLELE_CHECK); s_count(lc, SC_ALLELE_REPEATED0 + (int)k); }
   });
 }
 
@@ -1792,7 +1792,7 @@ __global__ void s_decompose_finish_kernel(SParams p, const STrace* __restrict__ 
   with_counters(cnt, [&](unsigned long long* lc) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= p.nt || dead[t]) return;
-  if (!((long long)o.score[2][t] > bound[t] && o.ops_len[2][t] != 0u)) { dead[t] |= SD_A12_CHECK; s_count(lc, SC_ALLELE_REPEATED2); return; }
+  if (!s_a12_certified(o.score[2][t], bound[t], o.ops_len[2][t])) { dead[t] |= SD_A12_CHECK; s_count(lc, SC_ALLELE_REPEATED2); return; }
   const STrace S = tr[t];
   o.score_fwd[t] = S.sc[0];
   o.score_rev[t] = S.sc[1];

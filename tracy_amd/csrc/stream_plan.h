@@ -1,7 +1,7 @@
 // stream_plan.h -- what the stream-ordered pipelines (stream.hip) keep on the device between two launches, and the per-trace planning
 // rules of both pipelines: which strand the k-mers vote for (R10, in dp_lane.h, where the sweep kernels see it too), which strand to
 // prune (R1, R2), whether a strand's bound decides it (R11), which band an alignment's score allows (R3, R5, R7, R8), whether a band
-// fits the band kernels (R4), whether a certificate held (R6), trimReferenceSlice's last step (R9).  Each rule is written once, as a
+// fits the band kernels (R4), whether a certificate held (R6, R12, R13), trimReferenceSlice's last step (R9).  Each rule is written once, as a
 // TR_HD function: the planning kernels of stream.hip (one thread per trace) and the host-planned tiers of pipeline.hip call the same
 // ones, so that a trace takes the same tier on either path -- and a trace whose tier the device cannot give it (a failed
 // certificate, a band wider than the band kernels hold) is marked `dead` and handed to the host-planned tiers afterwards.  Where the
@@ -285,6 +285,14 @@ TR_HD SA12Band s_a12_band(uint32_t len, int64_t best, int32_t go, int32_t ge, in
   r.bound = best * ((int64_t)len - (W + 1)) - age * 2 * (W + 1) - 2 * ago;
   return r;
 }
+
+// R12. certificate of a banded traceback whose exact score S* is known beforehand: the sub-window (preliminary alignment) or the
+// trimmed slice (gotoh(allele, slice)) holds the alignment just located, so its score is S* again -- a banded score is never above
+// the optimum, and one that reaches it is it.  A banded walk that left its band reports no ops.
+TR_HD bool s_exact_certified(int32_t sb, int32_t sstar, uint32_t ops_len) { return sb == sstar && ops_len != 0u; }
+// R13. certificate of allele 1 vs allele 2: the banded score beats the bound of s_a12_band (R8) -- what any path that leaves the band
+// scores at most -- and the walk stayed inside (ops_len != 0)
+TR_HD bool s_a12_certified(int64_t sb, int64_t bound, uint32_t ops_len) { return sb > bound && ops_len != 0u; }
 
 // what the first tier of a pruned sweep over m_rest rows below the kept row and n columns is credited with (run_front_once's sums)
 TR_HD uint64_t s_front_cells(uint32_t m_rest) { return (uint64_t)b16_strips(m_rest, 8) * 8u * (8u + 2u * 60u); }
