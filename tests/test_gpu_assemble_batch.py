@@ -248,6 +248,139 @@ def test_shared_reference_empty_batch_and_bad_input(ctx, batch):
     assert e.value.code == capi.ERR_RANGE
 
 
+# ---- the launch loops: long traces (sweeps of several passes), N rows (the 25-term body), the repeat on int32 ----------------
+
+LONG_TRACES = (700, 520, 300, 130)  # columns, over a reference of 900
+WIDE = 4.0
+
+
+def strip_height(m):
+    """choose_k for profile x profile (capi.hip): the cheaper of 8 and 4 rows per lane by passes x height, 8 on a tie"""
+    return min((8, 4), key=lambda k: -(-m // (64 * k)) * k)
+
+
+def passes(m):
+    return -(-m // (64 * strip_height(m)))
+
+
+def arith16_holds(mn, q):
+    """arith16_ok (capi.hip) for scoring 3/-5/-10/-4 and a largest substitution score q"""
+    return 3 * 10 + (mn + 2) * 4 + q < 20000 - 1000 and (mn // 2 + 1) * q < 30000
+
+
+def make_long_groups(seed=77):
+    import pyoracle as orc
+    rng = np.random.default_rng(seed)
+    # the long group: four traces over 900 columns, the second with N columns, the third read from the other strand
+    region = bases(rng, 900)
+    long_group = []
+    for ln, st in zip(LONG_TRACES, (60, 330, 120, 700)):
+        p = column_profile(rng, mutate(rng, region[st:st + ln], 0.02))
+        if ln == 520:
+            cols = np.arange(3, ln, 9)
+            p[:4, cols] *= np.float32(0.5)
+            p[4, cols] = np.float32(0.5)
+        if ln == 300:
+            p = np.ascontiguousarray(orc.revcomp_profile(p))
+        long_group.append(p)
+    # a reference that holds N bases: step 0 of this group takes the 25-term body
+    nregion = bytearray(bases(rng, 400))
+    for at in (50, 51, 200, 333):
+        nregion[at] = ord("N")
+    nregion = bytes(nregion)
+    clean = nregion.replace(b"N", b"A")
+    n_group = [column_profile(rng, mutate(rng, clean[st:st + ln], 0.02)) for ln, st in ((280, 20), (150, 180), (90, 300))]
+    # a small group of the kind make_groups builds
+    sregion = bases(rng, 200)
+    s_group = [column_profile(rng, mutate(rng, sregion[st:st + ln], 0.03)) for ln, st in ((150, 10), (60, 120))]
+    s_group[1] = np.ascontiguousarray(orc.revcomp_profile(s_group[1]))
+    groups = [long_group, n_group, s_group]
+    refs = [orc.create_profile_str(region), orc.create_profile_str(nregion), orc.create_profile_str(sregion)]
+    return groups, refs
+
+
+@pytest.fixture(scope="module")
+def long_batch():
+    groups, refs = make_long_groups()
+    want = [oracle_group(t, r, SCORE, FRACMATCH, CALLED, False) for t, r in zip(groups, refs)]
+    return groups, refs, want
+
+
+def scaled(profiles):
+    return [np.ascontiguousarray(p * np.float32(WIDE)) for p in profiles]
+
+
+@pytest.fixture(scope="module")
+def wide_batch(long_batch):
+    """[0]: the same traces x 4.0 over the same references; [1]: the references x 4.0 as well"""
+    groups, refs, _ = long_batch
+    out = []
+    for r in (refs, scaled(refs)):
+        g = [scaled(t) for t in groups]
+        out.append((g, r, [oracle_group(t, p, SCORE, FRACMATCH, CALLED, False) for t, p in zip(g, r)]))
+    return out
+
+
+def test_the_long_inputs_hold_every_case(long_batch, wide_batch):
+    """asserted on the inputs and on the oracle's own results (no GPU).  The rules of capi.hip are restated above: strip height 4 up to
+    256 rows, 8 up to 512, 4 again (three passes) up to 768; a pair takes the 16-term body iff row 4 of both profiles is zero, and
+    only at step 0 (later steps align against the profile of the rows so far and always take the 25-term body)."""
+    groups, refs, want = long_batch
+    assert [p.shape[1] for p in groups[0]] == list(LONG_TRACES) and refs[0].shape[1] == 900
+    assert [strip_height(m) for m in LONG_TRACES] == [4, 4, 8, 4] and [passes(m) for m in LONG_TRACES] == [3, 3, 1, 1]
+    assert groups[0][1][4].any() and not any(groups[0][i][4].any() for i in (0, 2, 3)) and not refs[0][4].any()
+    w = want[0]
+    assert w["nrows"] == 5 and w["forward"] == [1, 1, 0, 1] and w["ncol"] >= 900    # all four match, the third on the other strand
+    assert [s["idx"] for s in w["order"]] == [0, 1, 2, 3]                            # longest first: steps 0 and 1 sweep in three passes
+    assert refs[1][4].any() and not any(p[4].any() for p in groups[1]) and want[1]["nrows"] == 4  # N in the reference only
+    assert not refs[2][4].any() and want[2]["nrows"] == 3
+    # the score launches hold runs of both strip heights and both term counts; so does step 0 (long: 16 terms, N reference: 25)
+    zero = lambda p: not p[4].any()
+    runs = {(strip_height(p.shape[1]), zero(p) and zero(refs[g])) for g, t in enumerate(groups) for p in t}
+    assert runs == {(4, True), (4, False), (8, True), (8, False)}
+    first = [groups[g][want[g]["order"][0]["idx"]] for g in range(3)]
+    assert {(strip_height(p.shape[1]), zero(p) and zero(refs[g])) for g, p in enumerate(first)} == {(4, True), (8, False)}
+    # the repeat on int32.  Traces x 4.0 over normalised references: range_verdict sees Q = (int)(4 * 1.001 * 5 * 1.0001 + 1) + 1 = 22, which
+    # arith16_ok takes at every length here -- no repeat.  References x 4.0 as well: Q = 82, refused from m + n = 730 on -- a repeat.
+    assert int(WIDE * 1.001 * 5 * 1.0001 + 1.0) + 1 == 22 and int(WIDE * WIDE * 5 * 1.0001 + 1.0) + 1 == 82
+    mn = [p.shape[1] + refs[g].shape[1] for g, t in enumerate(groups) for p in t]
+    assert all(arith16_holds(x, 5) and arith16_holds(x, 22) for x in mn)
+    assert min(mn) < 730 <= max(mn) and not arith16_holds(730, 82) and arith16_holds(729, 82)
+    bound = max(refs[g].shape[1] + sum(p.shape[1] for p in t) for g, t in enumerate(groups))
+    assert (bound + 2) * (14 + 82) + 1000000 < 1 << 26
+    for g, r, ww in wide_batch:
+        assert ww[0]["nrows"] == 5 and ww[1]["nrows"] == 4 and ww[2]["nrows"] == 3
+
+
+@pytest.mark.parametrize("device", [False, True])
+@pytest.mark.parametrize("option", [None, "no_fused_walk", "no_screen"])
+def test_long_groups_match_oracle(ctx, long_batch, option, device):
+    groups, refs, want = long_batch
+    if option:
+        ctx.set_option(option, 1)
+    try:
+        got = ctx.assemble_traces(groups, refs, SCORE, FRACMATCH, CALLED, False, device=device)
+    finally:
+        if option:
+            ctx.set_option(option, 0)
+    check(got, want, groups)
+    stats = ctx.last_call_stats()
+    assert stats["asm_chunks"] == 1 and stats["asm_steps"] == 4
+    assert stats["host_syncs"] == 2 + stats["asm_steps"] + 1  # classes, scores, one per chain step, the end
+
+
+@pytest.mark.parametrize("refs_too", [False, True])
+def test_long_groups_repeat_on_int32(ctx, wide_batch, refs_too):
+    """un-normalised profiles.  Both sides x 4.0: the 16-bit score launches are refused at the score synchronisation (kWiden) and the call
+    runs again on int32 -- the first run adds its two synchronisations.  Traces alone x 4.0: the 16-bit range still holds (Q = 22)."""
+    groups, refs, want = wide_batch[int(refs_too)]
+    got = ctx.assemble_traces(groups, refs, SCORE, FRACMATCH, CALLED, False)
+    check(got, want, groups)
+    stats = ctx.last_call_stats()
+    assert stats["asm_steps"] == 4
+    assert stats["host_syncs"] == (2 if refs_too else 0) + (2 + stats["asm_steps"] + 1)
+
+
 # ---- the command line -------------------------------------------------------------------------------------------------
 
 

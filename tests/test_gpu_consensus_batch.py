@@ -83,15 +83,18 @@ def oracle_pair(p1, f2, score, union, iupac, min_overlap, frac):
                 num_match=matches, status=0 if ok else 1, cons=cons.encode(), qual=list(qual))
 
 
+def check_pair(got, i, want):
+    for k in ("score_fwd", "score_rev", "forward", "score", "num_aligned", "num_match", "status"):
+        assert int(got[k][i]) == int(want[k]), (i, k, int(got[k][i]), want[k])
+    assert got["rows"][i] == want["rows"], i
+    assert got["cons"][i] == want["cons"], i
+    assert [int(q) for q in got["qual"][i]] == want["qual"], i
+
+
 def check(got, first, second, score, union=True, iupac=False, min_overlap=25, frac=0.5, sample=None):
     idx = range(len(first)) if sample is None else sample
     for i in idx:
-        want = oracle_pair(first[i], second[i], score, union, iupac, min_overlap, frac)
-        for k in ("score_fwd", "score_rev", "forward", "score", "num_aligned", "num_match", "status"):
-            assert int(got[k][i]) == int(want[k]), (i, k, int(got[k][i]), want[k])
-        assert got["rows"][i] == want["rows"], i
-        assert got["cons"][i] == want["cons"], i
-        assert [int(q) for q in got["qual"][i]] == want["qual"], i
+        check_pair(got, i, oracle_pair(first[i], second[i], score, union, iupac, min_overlap, frac))
 
 
 @pytest.fixture(scope="module")
@@ -173,6 +176,127 @@ def test_bad_input(ctx):
     with pytest.raises(capi.TracyHipError) as e:
         ctx.consensus_traces([p2], [p2], (40000, -5, -10, -4))
     assert e.value.code == capi.ERR_RANGE
+
+
+# ---- the launch loops: runs of equal strip height and term count, sweeps of several passes, the repeat on int32 ----------
+
+RUN_LENGTHS = (40, 250, 256, 257, 300, 512, 513, 600, 700, 120, 400, 800)  # columns of the first profile
+N_FIRST, N_SECOND = (250, 300, 700), (40, 512, 600)                        # pairs whose first / second profile has a non-zero N row
+WIDE = 4.0  # every column x 4.0: substitution scores x 16, range_verdict sees Q = (int)(4 * 4 * 5 * 1.0001 + 1) + 1 = 82
+
+
+def strip_height(m):
+    """choose_k for profile x profile (capi.hip): the cheaper of 8 and 4 rows per lane by passes x height, 8 on a tie"""
+    return min((8, 4), key=lambda k: -(-m // (64 * k)) * k)
+
+
+def passes(m):
+    return -(-m // (64 * strip_height(m)))
+
+
+def arith16_holds(mn, q):
+    """arith16_ok (capi.hip) for scoring 3/-5/-10/-4 and a largest substitution score q"""
+    return 3 * 10 + (mn + 2) * 4 + q < 20000 - 1000 and (mn // 2 + 1) * q < 30000
+
+
+def with_n_row(rng, p, every=7):
+    """half of every `every`-th column moved to row 4 ('N'): column sums stay 1"""
+    p = p.copy()
+    cols = np.arange(int(rng.integers(0, every)), p.shape[1], every)
+    p[:4, cols] *= np.float32(0.5)
+    p[4, cols] = np.float32(0.5)
+    return p
+
+
+def make_runs(seed=913):
+    import pyoracle as orc
+    rng = np.random.default_rng(seed)
+    first, second = [], []
+    for i, L in enumerate(RUN_LENGTHS):
+        g = bytes(rng.choice(list(b"ACGT"), size=2 * L).tolist())
+        L2 = L - int(rng.integers(0, L // 8 + 1))
+        p1 = column_profile(rng, mutate(rng, g[:L], 0.02))
+        s2 = int(rng.integers(0, L // 4 + 1))
+        p2 = column_profile(rng, mutate(rng, g[s2:s2 + L2], 0.02))
+        if L in N_FIRST:
+            p1 = with_n_row(rng, p1)
+        if L in N_SECOND:
+            p2 = with_n_row(rng, p2)
+        if i % 2:  # the second trace read from the other strand
+            p2 = np.ascontiguousarray(orc.revcomp_profile(p2))
+        first.append(p1)
+        second.append(p2)
+    return first, second
+
+
+@pytest.fixture(scope="module")
+def runs():
+    first, second = make_runs()
+    want = [oracle_pair(a, b, SCORE, True, False, 25, 0.5) for a, b in zip(first, second)]
+    return first, second, want
+
+
+@pytest.fixture(scope="module")
+def wide_runs(runs):
+    first = [np.ascontiguousarray(p * np.float32(WIDE)) for p in runs[0]]
+    second = [np.ascontiguousarray(p * np.float32(WIDE)) for p in runs[1]]
+    want = [oracle_pair(a, b, SCORE, True, False, 25, 0.5) for a, b in zip(first, second)]
+    return first, second, want
+
+
+def test_the_runs_hold_every_case(runs, wide_runs):
+    """asserted on the inputs and on the oracle's own results (no GPU): every case the launch loops can go wrong on is present.
+    The rules of capi.hip are restated above: strip height 4 up to 256 rows, 8 up to 512, 4 again (three passes) up to 768, 8 (two
+    passes) from 769 on; a pair takes the 16-term body iff row 4 of both profiles is zero."""
+    first, second, want = runs
+    assert [p.shape[1] for p in first] == list(RUN_LENGTHS)
+    assert [strip_height(m) for m in (40, 256, 257, 512, 513, 768, 769, 800)] == [4, 4, 8, 8, 4, 4, 8, 8]
+    assert [passes(m) for m in (256, 257, 512, 513, 700, 800)] == [1, 1, 1, 3, 3, 2]
+    assert all(abs(a.shape[1] - b.shape[1]) <= a.shape[1] // 8 for a, b in zip(first, second))
+    zero = lambda p: not p[4].any()
+    terms = {(strip_height(a.shape[1]), zero(a) and zero(b)) for a, b in zip(first, second)}
+    assert terms == {(4, True), (4, False), (8, True), (8, False)}                  # each strip height holds both term counts
+    assert any(not zero(a) for a in first) and any(not zero(b) for b in second)     # an N row on either side
+    for k in (4, 8):                                                                # one pass and several, at each strip height
+        assert {passes(a.shape[1]) > 1 for a in first if strip_height(a.shape[1]) == k} == {False, True}
+    assert any(passes(a.shape[1]) > 1 and not (zero(a) and zero(b)) for a, b in zip(first, second))  # boundary rows under the 25-term body
+    assert {w["forward"] for w in want} == {0, 1} and sum(w["status"] == 0 for w in want) >= 10
+    # the repeat on int32: Q = 82 where every column is x 4.0; a 16-bit launch is refused from m + n = 730 on and the batch lies on both
+    # sides of it; a priori (Q = 5) every launch is narrow; the int32 kernels hold the values ((m + n + 2) (14 + Q) + 10^6 < 2^26)
+    assert int(WIDE * WIDE * 5 * 1.0001 + 1.0) + 1 == 82  # range_verdict: column masses x largest |score| x 1.0001 + 1, rounded up
+    assert arith16_holds(729, 82) and not arith16_holds(730, 82)
+    mn = [a.shape[1] + b.shape[1] for a, b in zip(first, second)]
+    assert min(mn) < 730 <= max(mn) and all(arith16_holds(x, 5) for x in mn)
+    assert (max(mn) + 2) * (14 + 82) + 1000000 < 1 << 26
+    assert all(np.array_equal(w, np.float32(WIDE) * p) for w, p in zip(wide_runs[0], first))
+
+
+@pytest.mark.parametrize("option", [None, "no_fused_walk", "no_screen", "no_narrow"])
+def test_runs_match_oracle(ctx, runs, option):
+    first, second, want = runs
+    if option:
+        ctx.set_option(option, 1)
+    try:
+        got = ctx.consensus_traces(first, second, SCORE)
+    finally:
+        if option:
+            ctx.set_option(option, 0)
+    for i, w in enumerate(want):
+        check_pair(got, i, w)
+    assert ctx.last_call_stats()["host_syncs"] == 2  # the classes, the end
+
+
+def test_runs_repeat_on_int32(ctx, runs, wide_runs):
+    """un-normalised profiles: the first run's 16-bit score launches are refused by range_verdict at the end of the call (kWiden) and
+    the call runs again on int32 -- twice the synchronisations of the unscaled call"""
+    first, second, want = wide_runs
+    ctx.consensus_traces(runs[0], runs[1], SCORE)
+    plain = ctx.last_call_stats()["host_syncs"]
+    got = ctx.consensus_traces(first, second, SCORE)
+    syncs = ctx.last_call_stats()["host_syncs"]
+    for i, w in enumerate(want):
+        check_pair(got, i, w)
+    assert (plain, syncs) == (2, 4)
 
 
 # ---- the command line -------------------------------------------------------------------------------------------------

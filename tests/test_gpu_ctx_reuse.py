@@ -98,7 +98,7 @@ def run(ctx, b, name):
         return ctx.secondary_decomposed(hbc())
     if name == "allelic_fraction":
         return ctx.allelic_fraction(hbc(), np.concatenate([np.frombuffer(c["sec"], dtype=np.uint8) for c in cs]), 50, 50)
-    if name == "score":  # profile x profile: the Row4Desc list of build_problem
+    if name == "score":  # profile x profile: the ProfSeq list of build_problem
         return ctx.score(b["first"], b["second"], SC + (1, 1))
     if name == "consensus_traces":
         return ctx.consensus_traces(b["first"], b["second"], SC)

@@ -1,11 +1,12 @@
 // assemble.hip -- tracyhip_assemble_traces: the reference-guided chain of `tracy assemble` (assemble.h:219-288) for a batch of groups.
 //
-// Per group: revcomp of every trace on the device (profile.h:74-90); gotohScore of both strands against the group's reference in ONE
-// profile x profile score launch for the whole batch; the matching traces, their strands and their order on the host (bookkeeping, as
-// UPGMA is in msa.hpp); then the chain, STEP-BATCHED: step k of every group of a chunk that has more than k matching traces is one
-// batch -- msa_profile of the rows so far (written at the end of step k - 1), gotoh(trace_k, that profile) through the traceback
-// kernels of tracyhip_gotoh_align (fused walk), msa_merge with the trace as row 0.  Step 0 is gotoh(best, reference): both sides of
-// its merge are input profiles, shown as their _profileConsChar rows.  msa_consensus closes a chunk.
+// Per group: revcomp of every trace on the device (profile.h:74-90, prof_batch.hip); gotohScore of both strands against the group's
+// reference in ONE profile x profile score launch for the whole batch (the launch loops are prof_batch.hip's); the matching traces,
+// their strands and their order on the host (bookkeeping, as UPGMA is in msa.hpp); then the chain, STEP-BATCHED: step k of every
+// group of a chunk that has more than k matching traces is one batch -- msa_profile of the rows so far (written at the end of step
+// k - 1), gotoh(trace_k, that profile) through the traceback kernels of tracyhip_gotoh_align (fused walk), msa_merge with the trace
+// as row 0.  Step 0 is gotoh(best, reference): both sides of its merge are input profiles, shown as their _profileConsChar rows.
+// msa_consensus closes a chunk.
 //
 // The columns of step k are the op count of step k - 1, which only the device knows: the host reads the op counts back once per step
 // and builds the next step's descriptors from them.  Workspaces are sized from the bound  columns <= n_ref + sum of the trace lengths
@@ -25,58 +26,12 @@
 
 using namespace tracyhip;
 
-#define HIP_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess)                                                                           \
-      return set_error(_e == hipErrorOutOfMemory ? TRACYHIP_ERR_OOM : TRACYHIP_ERR_HIP, "%s failed: %s (%s:%d)", \
-                       #expr, hipGetErrorString(_e), __FILE__, __LINE__);                           \
-  } while (0)
-
 namespace {
-
-struct AsmSeq {  // one profile of the batch: float offset and columns
-  uint64_t off;
-  uint32_t len, pad;
-};
 
 struct AsmDevWave {
   __device__ __forceinline__ uint32_t lane() const { return threadIdx.x; }
   __device__ __forceinline__ uint64_t ballot(bool p) const { return __ballot(p); }
 };
-
-// revcomp of every trace (profile.h:74-90): rows A<->T, C<->G swapped, N and gap kept, columns reversed; trace s is written at
-// rev_base + its own offset.  One workgroup per trace.
-__global__ __launch_bounds__(256) void asm_revcomp_kernel(const AsmSeq* __restrict__ seqs, const float* __restrict__ in, float* __restrict__ out,
-                                                          uint64_t rev_base) {
-  const AsmSeq s = seqs[blockIdx.x];
-  const float* p = in + s.off;
-  float* q = out + rev_base + s.off;
-  const uint64_t n = s.len;
-  for (uint32_t j = threadIdx.x; j < s.len; j += blockDim.x) {
-    const uint64_t src = n - 1 - j;
-    q[0 * n + j] = p[3 * n + src];
-    q[1 * n + j] = p[2 * n + src];
-    q[2 * n + j] = p[1 * n + src];
-    q[3 * n + j] = p[0 * n + src];
-    q[4 * n + j] = p[4 * n + src];
-    q[5 * n + j] = p[5 * n + src];
-  }
-}
-
-// row 4 ('N') zero over a whole profile (chooses the 16-term score body); colclass (or null): the class of every column, for the
-// screened substitution scores.  One wave per profile.
-__global__ __launch_bounds__(64) void asm_classify_kernel(const AsmSeq* __restrict__ seqs, const float* __restrict__ data, uint8_t* __restrict__ zero,
-                                                          uint8_t* __restrict__ colclass) {
-  const AsmSeq s = seqs[blockIdx.x];
-  bool nz = false;
-  for (uint32_t j = threadIdx.x; j < s.len; j += 64) {
-    nz |= !(data[s.off + 4ull * s.len + j] == 0.0f);
-    if (colclass) colclass[s.off + j] = (uint8_t)column_class(data + s.off, s.len, j);
-  }
-  const unsigned long long any = __ballot(nz);
-  if (threadIdx.x == 0) zero[blockIdx.x] = any ? 0 : 1;
-}
 
 struct AsmStep {       // one group at one chain step
   MsaSide left, right; // the new trace (always a profile); the reference profile (step 0) or the rows so far
@@ -134,12 +89,6 @@ __global__ __launch_bounds__(64) void msa_consensus_kernel(const AsmFinal* __res
   msa_consensus_wave(w, f.rows, f.rows_used, L, f.span, f.cov_threshold, f.gapped, f.cons, f.qual, f.cons_len);
 }
 
-bool check_set(const tracyhip_seqset& s, const char* name) {
-  if (s.kind != TRACYHIP_SEQ_PROFILE) return set_error(TRACYHIP_ERR_ARG, "%s: kind must be PROFILE", name), false;
-  if (!s.offset || !s.length || !s.data) return set_error(TRACYHIP_ERR_ARG, "%s: null data / offset / length arrays", name), false;
-  return true;
-}
-
 int assemble_validate(const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem, const tracyhip_assemble_result* out) {
   if (mem != TRACYHIP_MEM_HOST && mem != TRACYHIP_MEM_DEVICE) return set_error(TRACYHIP_ERR_ARG, "bad mem kind");
   if (!job || !out) return set_error(TRACYHIP_ERR_ARG, "null job / result");
@@ -149,7 +98,7 @@ int assemble_validate(const tracyhip_assemble_job* job, const tracyhip_params* p
   const uint32_t ng = job->ngroups;
   if (ng == 0) return TRACYHIP_OK;
   if (!job->group_first) return set_error(TRACYHIP_ERR_ARG, "null group_first");
-  if (!check_set(job->traces, "traces") || !check_set(job->references, "references")) return TRACYHIP_ERR_ARG;
+  if (!check_profile_set(job->traces, "traces") || !check_profile_set(job->references, "references")) return TRACYHIP_ERR_ARG;
   if (!out->score_fwd || !out->score_rev || !out->forward || !out->rank || !out->nrows || !out->ncol || !out->rows || !out->gapped ||
       !out->cons || !out->qual || !out->cons_len || !out->rows_offset || !out->col_offset)
     return set_error(TRACYHIP_ERR_ARG, "null result arrays");
@@ -159,10 +108,9 @@ int assemble_validate(const tracyhip_assemble_job* job, const tracyhip_params* p
       return set_error(TRACYHIP_ERR_ARG, "group %u ends at trace %u, the set holds %u", g, job->group_first[g + 1], job->traces.count);
     const uint32_t r = job->ref_index ? job->ref_index[g] : g;
     if (r >= job->references.count) return set_error(TRACYHIP_ERR_ARG, "group %u: reference %u of %u", g, r, job->references.count);
-    if (job->references.length[r] == 0) return set_error(TRACYHIP_ERR_ARG, "references: profile %u has no columns", r);
+    if (!check_profile_columns(job->references, "references", r, r + 1)) return TRACYHIP_ERR_ARG;
   }
-  for (uint32_t i = job->group_first[0]; i < job->group_first[ng]; ++i)
-    if (job->traces.length[i] == 0) return set_error(TRACYHIP_ERR_ARG, "traces: profile %u has no columns", i);
+  if (!check_profile_columns(job->traces, "traces", job->group_first[0], job->group_first[ng])) return TRACYHIP_ERR_ARG;
   return TRACYHIP_OK;
 }
 
@@ -223,33 +171,27 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   if ((rc = stage_in(ctx, ctx->dev[DB_IN2], sR.data, eR * 4, mem, &d_refv))) return rc;
   const float* d_ref = static_cast<const float*>(d_refv);
   const uint32_t nref = sR.count;
-  std::vector<AsmSeq> hs((size_t)nt + nref, AsmSeq{0, 0, 0});  // (references no group uses keep length 0: nothing of them is read)
-  for (uint32_t i = 0; i < nt; ++i) hs[i] = AsmSeq{sT.offset[t0 + i], sT.length[t0 + i], 0};
-  for (uint32_t g = 0; g < ng; ++g) hs[(size_t)nt + ref_of(g)] = AsmSeq{sR.offset[ref_of(g)], sR.length[ref_of(g)], 0};
-  AsmSeq* d_seqs; HIP_TRY(ensure_into(B[AB_SEQS], hs.size(), d_seqs));
-  HIP_TRY(hipMemcpyAsync(d_seqs, hs.data(), sizeof(AsmSeq) * hs.size(), hipMemcpyHostToDevice, st));
+  std::vector<ProfSeq> hs((size_t)nt + nref, ProfSeq{0, 0, 0});  // (references no group uses keep length 0: nothing of them is read)
+  for (uint32_t i = 0; i < nt; ++i) hs[i] = ProfSeq{sT.offset[t0 + i], sT.length[t0 + i], 0};
+  for (uint32_t g = 0; g < ng; ++g) hs[(size_t)nt + ref_of(g)] = ProfSeq{sR.offset[ref_of(g)], sR.length[ref_of(g)], 0};
+  ProfSeq* d_seqs; HIP_TRY(ensure_into(B[AB_SEQS], hs.size(), d_seqs));
+  HIP_TRY(hipMemcpyAsync(d_seqs, hs.data(), sizeof(ProfSeq) * hs.size(), hipMemcpyHostToDevice, st));
   int trc;
   if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 2 * 4ull * eT))) return trc;
-  hipLaunchKernelGGL(asm_revcomp_kernel, dim3(nt), dim3(256), 0, st, d_seqs, (const float*)d_tr, d_tr, rev_base);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_prof_revcomp(d_seqs, nt, d_tr, d_tr, rev_base, st));
   uint8_t* d_zero; HIP_TRY(ensure_into(B[AB_CLASS], (size_t)nt + nref, d_zero));
   uint8_t* d_refclass = nullptr;
   const bool screen = !ctx->knobs.no_screen;
   if (screen) HIP_TRY(ensure_into(B[AB_REFCLASS], std::max<uint64_t>(eR, 1), d_refclass));
-  hipLaunchKernelGGL(asm_classify_kernel, dim3(nt), dim3(64), 0, st, d_seqs, (const float*)d_tr, d_zero, (uint8_t*)nullptr);
-  hipLaunchKernelGGL(asm_classify_kernel, dim3(nref), dim3(64), 0, st, d_seqs + nt, d_ref, d_zero + nt, d_refclass);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_prof_classify(d_seqs, nt, d_tr, d_zero, nullptr, st));
+  HIP_TRY(launch_prof_classify(d_seqs + nt, nref, d_ref, d_zero + nt, d_refclass, st));
   if ((trc = timing_end(ctx))) return trc;
   std::vector<uint8_t> hz((size_t)nt + nref);
   HIP_TRY(hipMemcpyAsync(hz.data(), d_zero, hz.size(), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx_sync(ctx));  // (the classes choose the score bodies)
 
-  uint64_t limit = ctx->ws_limit;
-  if (limit == 0) {
-    size_t fr = 0, tot = 0;
-    HIP_TRY(hipMemGetInfo(&fr, &tot));
-    limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->dev[DB_BITS].cap + ctx->dev[DB_SCRATCH].cap;
-  }
+  uint64_t limit;
+  if ((rc = workspace_limit(ctx, ctx->dev[DB_BITS].cap + ctx->dev[DB_SCRATCH].cap, &limit))) return rc;
 
   // ---- both strand scores of every trace: one launch per run of equal strip height / term count ----
   std::vector<uint32_t> grp(nt);
@@ -264,6 +206,8 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
     if (KS[x] != KS[y]) return KS[x] > KS[y];
     return row4(x) > row4(y);
   });
+  std::vector<int> k_score(nt);  // strip heights of the score launches, in launch order
+  for (uint32_t j = 0; j < nt; ++j) k_score[j] = KS[order[j]];
   const size_t ndesc = std::max<size_t>(2 * (size_t)nt, ng);
   PairDesc *hd, *dd;
   HIP_TRY(ensure_into(ctx->pin[PB_DESC], ndesc, hd));
@@ -296,36 +240,15 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
   int32_t* d_sc2; HIP_TRY(ensure_into(B[AB_SC2], 2 * (size_t)nt, d_sc2));
 
-  DpArgs a{};
+  DpArgs a = scoring_args(ctx, prm);
   a.a1 = d_tr;
   a.a2 = d_ref;
   a.scratch = static_cast<int32_t*>(ctx->dev[DB_SCRATCH].p);
-  a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
-  a.match = prm->match; a.mismatch = prm->mismatch; a.go = prm->go; a.ge = prm->ge;
-  a.hfree = prm->hfree; a.vfree = prm->vfree;
-  a.qlimit = sub_limit(prm);
   a.screen = screen ? 1 : 0;
   a.colcode = d_refclass;
   a.scores = d_sc2;
   std::vector<std::pair<uint32_t, int>> narrow_launches;
-  for (uint32_t j = 0; j < nt;) {
-    uint32_t e = j;
-    const int k = KS[order[j]];
-    const uint32_t r4 = hd[2 * (size_t)j].flags & PAIR_ROW4_ZERO;
-    uint64_t mn = 0, cells = 0;
-    while (e < nt && KS[order[e]] == k && (hd[2 * (size_t)e].flags & PAIR_ROW4_ZERO) == r4) {
-      mn = std::max<uint64_t>(mn, (uint64_t)hd[2 * (size_t)e].m + hd[2 * (size_t)e].n);
-      cells += 2ull * hd[2 * (size_t)e].m * hd[2 * (size_t)e].n;
-      ++e;
-    }
-    const bool a16 = !wide && !ctx->knobs.no_narrow && arith16_ok(prm, mn, 0);
-    if (a16) narrow_launches.emplace_back((uint32_t)mn, 0);
-    a.pairs = dd + 2 * (size_t)j;
-    if ((trc = timing_begin(ctx, TRACYHIP_TIMER_SCORE, cells, 0))) return trc;
-    HIP_TRY(launch_gotoh_prof(k, false, r4 != 0, a16, a, 2 * (e - j), st));
-    if ((trc = timing_end(ctx))) return trc;
-    j = e;
-  }
+  if ((rc = prof_score_runs(ctx, prm, wide, a, hd, dd, k_score.data(), 0, nt, narrow_launches))) return rc;
   std::vector<int32_t> sc2(2 * (size_t)nt);
   int32_t herr[kErrWords] = {};
   HIP_TRY(hipMemcpyAsync(sc2.data(), d_sc2, sizeof(int32_t) * sc2.size(), hipMemcpyDeviceToHost, st));
@@ -433,10 +356,10 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   a.bits32 = static_cast<uint32_t*>(ctx->dev[DB_BITS].p);
   a.scratch = static_cast<int32_t*>(ctx->dev[DB_SCRATCH].p);
   a.scores = nullptr;
-  const bool fused_walk = !ctx->knobs.no_fused_walk;
   const int32_t ignore_last = job->include_reference ? 0 : 1;
   uint32_t total_steps = 0;
   std::vector<uint32_t> act;
+  std::vector<int> k_step;  // strip heights of a step's launches, in launch order
 
   for (const Chunk& c : chunks) {
     for (uint32_t k = 0; k < c.steps; ++k) {
@@ -451,6 +374,7 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
         return flags_of(x) > flags_of(y);
       });
       const uint32_t na = (uint32_t)act.size();
+      k_step.resize(na);
       uint64_t words = 0, scr = 0, max_cap = 0;
       bool any_prof = false;
       for (uint32_t j = 0; j < na; ++j) {
@@ -472,6 +396,7 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
         d.scratch_off = scr;
         d.out = g;
         hd[j] = d;
+        k_step[j] = KS[mt.idx];
         words += (uint64_t)P * steps_per_pass(n) * 64;
         if (P > 1) scr += (uint64_t)n + 2;
         AsmStep s{};
@@ -493,26 +418,7 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
       HIP_TRY(hipMemcpyAsync(d_step, h_step, sizeof(AsmStep) * na, hipMemcpyHostToDevice, st));
       a.a2 = k == 0 ? (const void*)d_ref : (const void*)d_prof;
       a.colcode = !screen ? nullptr : k == 0 ? d_refclass : d_pclass;
-      for (uint32_t j = 0; j < na;) {
-        uint32_t e = j;
-        const int kk = KS[matched[act[j]][k].idx];
-        const uint32_t r4 = hd[j].flags & PAIR_ROW4_ZERO;
-        uint64_t cells = 0;
-        while (e < na && KS[matched[act[e]][k].idx] == kk && (hd[e].flags & PAIR_ROW4_ZERO) == r4) { cells += (uint64_t)hd[e].m * hd[e].n; ++e; }
-        a.pairs = dd + j;
-        if (fused_walk) { a.walk_ops = d_ops; a.walk_ops_off = d_off; a.walk_ops_len = d_len; }
-        if ((trc = timing_begin(ctx, TRACYHIP_TIMER_TRACE, cells, cells / 2))) return trc;
-        HIP_TRY(launch_gotoh_prof(kk, true, r4 != 0, false, a, e - j, st));
-        if ((trc = timing_end(ctx))) return trc;
-        if (!fused_walk) {
-          WalkArgs wa{};
-          wa.pairs = dd + j; wa.bits = a.bits; wa.ops = d_ops; wa.ops_off = d_off; wa.ops_len = d_len; wa.err = a.err; wa.npairs = e - j; wa.K = kk;
-          if ((trc = timing_begin(ctx, TRACYHIP_TIMER_WALK, 0, 0))) return trc;
-          HIP_TRY(launch_gotoh_walk(wa, st));
-          if ((trc = timing_end(ctx))) return trc;
-        }
-        j = e;
-      }
+      if ((rc = prof_trace_runs(ctx, a, hd, dd, k_step.data(), 0, na, d_ops, d_off, d_len))) return rc;
       if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 0))) return trc;
       hipLaunchKernelGGL(msa_merge_kernel, dim3(na, k + 2), dim3(64), 0, st, (const AsmStep*)d_step, (const uint8_t*)d_ops, (const uint32_t*)d_len);
       if (any_prof)

@@ -26,14 +26,6 @@
 
 using namespace tracyhip;
 
-#define HIP_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess)                                                                           \
-      return set_error(_e == hipErrorOutOfMemory ? TRACYHIP_ERR_OOM : TRACYHIP_ERR_HIP, "%s failed: %s (%s:%d)", \
-                       #expr, hipGetErrorString(_e), __FILE__, __LINE__);                           \
-  } while (0)
-
 static_assert(TRACYHIP_BASECALL_OK == kBcStatusOk && TRACYHIP_BASECALL_DEFERRED == kBcStatusDeferred, "status codes");
 
 namespace {

@@ -118,29 +118,6 @@ __global__ void encode_kernel(const uint8_t* __restrict__ in, uint8_t* __restric
   }
 }
 
-// profile x profile: is row 4 ('N') zero over a whole profile?  (NaN counts as non-zero.)  One wave per sequence.  colclass (a2 set
-// only): the class of every column (dp_kernels.h column_class), stored at the index of the column's row-0 element.
-struct Row4Desc { uint64_t off; uint32_t len, pad; };
-__global__ __launch_bounds__(64) void row4_zero_kernel(const Row4Desc* __restrict__ d, const float* __restrict__ data, uint8_t* __restrict__ out,
-                                                       uint8_t* __restrict__ colclass) {
-  const Row4Desc s = d[blockIdx.x];
-  bool nz = false;
-  for (uint32_t j = threadIdx.x; j < s.len; j += 64) {
-    nz |= !(data[s.off + 4ull * s.len + j] == 0.0f);
-    if (colclass) colclass[s.off + j] = (uint8_t)tracyhip::column_class(data + s.off, s.len, j);
-  }
-  const unsigned long long any = __ballot(nz);
-  if (threadIdx.x == 0) out[blockIdx.x] = any ? 0 : 1;
-}
-
-#define HIP_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess)                                                                           \
-      return set_error(_e == hipErrorOutOfMemory ? TRACYHIP_ERR_OOM : TRACYHIP_ERR_HIP, "%s failed: %s (%s:%d)", \
-                       #expr, hipGetErrorString(_e), __FILE__, __LINE__);                           \
-  } while (0)
-
 namespace tracyhip {
 
 static hipError_t get_event(tracyhip_ctx* ctx, hipEvent_t* e) {
@@ -468,6 +445,36 @@ int check_params(const tracyhip_params* prm, uint64_t max_mn) {
 static int64_t iabs64(int32_t x) { return x < 0 ? -(int64_t)x : (int64_t)x; }
 int32_t sub_limit(const tracyhip_params* prm) { return (int32_t)std::max(iabs64(prm->match), iabs64(prm->mismatch)); }
 
+DpArgs scoring_args(tracyhip_ctx* ctx, const tracyhip_params* prm) {
+  DpArgs a{};
+  a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
+  a.match = prm->match; a.mismatch = prm->mismatch; a.go = prm->go; a.ge = prm->ge;
+  a.hfree = prm->hfree; a.vfree = prm->vfree;
+  a.qlimit = sub_limit(prm);
+  return a;
+}
+
+int workspace_limit(tracyhip_ctx* ctx, uint64_t held, uint64_t* limit) {
+  *limit = ctx->ws_limit;
+  if (*limit) return TRACYHIP_OK;
+  size_t fr = 0, tot = 0;
+  HIP_TRY(hipMemGetInfo(&fr, &tot));
+  *limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + held;
+  return TRACYHIP_OK;
+}
+
+bool check_profile_set(const tracyhip_seqset& s, const char* name) {
+  if (s.kind != TRACYHIP_SEQ_PROFILE) return set_error(TRACYHIP_ERR_ARG, "%s: kind must be PROFILE", name), false;
+  if (!s.offset || !s.length || !s.data) return set_error(TRACYHIP_ERR_ARG, "%s: null data / offset / length arrays", name), false;
+  return true;
+}
+
+bool check_profile_columns(const tracyhip_seqset& s, const char* name, uint32_t lo, uint32_t hi) {
+  for (uint32_t i = lo; i < hi; ++i)
+    if (s.length[i] == 0) return set_error(TRACYHIP_ERR_ARG, "%s: profile %u has no columns", name, i), false;
+  return true;
+}
+
 // 16-bit score kernel: every real DP value must fit int16 with room below for the sentinel.  Q bounds the absolute value of
 // a substitution score: max(|match|, |mismatch|) for strings and normalised profiles (the a-priori call, Q = 0), the
 // device-reported maximum when a launch has seen a larger query-profile entry (range_verdict).
@@ -568,13 +575,10 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
 
   // workspace plan: chunks of consecutive (sorted) pairs whose traceback words fit the limit
   const uint64_t word_bytes = needle ? 4 : 8;
-  uint64_t limit = ctx->ws_limit;
-  if (limit == 0 && trace && stage == DP_PLAIN) {  // only the full-matrix traceback needs a workspace plan
-    size_t fr = 0, tot = 0;
-    HIP_TRY(hipMemGetInfo(&fr, &tot));
-    limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->dev[DB_BITS].cap;  // this context's share of what is free now plus what it already holds
-  } else if (limit == 0) {
-    limit = ~0ull;
+  uint64_t limit = ~0ull;
+  if (ctx->ws_limit || (trace && stage == DP_PLAIN)) {  // without a caller's limit only the full-matrix traceback needs a workspace plan
+    const int lrc = workspace_limit(ctx, ctx->dev[DB_BITS].cap, &limit);
+    if (lrc) return lrc;
   }
   PairDesc* hd; HIP_TRY(ensure_into(ctx->pin[PB_DESC], (size_t)np, hd));
   struct Chunk { uint32_t lo, hi; uint64_t words, scratch; };
@@ -655,17 +659,13 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
   uint64_t max_mn = 0;
   for (uint32_t j = 0; j < np; ++j) max_mn = std::max<uint64_t>(max_mn, (uint64_t)pb.desc[j].m + pb.desc[j].n);
 
-  DpArgs a{};
+  DpArgs a = scoring_args(ctx, prm);
   a.a1 = pb.d_a1;
   a.a2 = pb.d_a2;
   a.bits = static_cast<uint64_t*>(ctx->dev[DB_BITS].p);
   a.bits32 = static_cast<uint32_t*>(ctx->dev[DB_BITS].p);
   a.scratch = static_cast<int32_t*>(ctx->dev[DB_SCRATCH].p);
   a.scores = d_scores;
-  a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
-  a.match = prm->match; a.mismatch = prm->mismatch; a.go = prm->go; a.ge = prm->ge;
-  a.hfree = prm->hfree; a.vfree = prm->vfree;
-  a.qlimit = sub_limit(prm);
   // Gotoh tracebacks: the sweep's workgroup walks its pair itself (TRACYHIP_NO_FUSED_WALK=1: the separate walk launch)
   const bool fused_walk = trace && stage == DP_PLAIN && !needle && !ctx->knobs.no_fused_walk;
   if (fused_walk) { a.walk_ops = d_ops; a.walk_ops_off = d_ops_off; a.walk_ops_len = d_ops_len; }
@@ -862,12 +862,9 @@ int run_band16(tracyhip_ctx* ctx, Band16Job& job, const tracyhip_params* prm, in
   const uint32_t np = bn[0] + bn[1] + bn[2];
   if (np == 0) { return TRACYHIP_OK; }
   if (limit == 0) {
+    int lrc;
     if (job.kind != 0 || total_bytes + 64 <= ctx->dev[DB_BITS].cap) limit = ~0ull;  // (the words fit what is there: no driver call)
-    else {
-      size_t fr = 0, tot = 0;
-      HIP_TRY(hipMemGetInfo(&fr, &tot));
-      limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->dev[DB_BITS].cap;
-    }
+    else if ((lrc = workspace_limit(ctx, ctx->dev[DB_BITS].cap, &limit))) return lrc;
   }
   PairDesc* hd; HIP_TRY(ensure_into(ctx->pin[PB_DESC], (size_t)np, hd));
   std::vector<int> hk(np);
@@ -1047,11 +1044,9 @@ int run_prefix_keep_cq(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, co
   });
   HIP_TRY(ctx->dev[DB_PRE].ensure(sizeof(PairDesc) * np));
   HIP_TRY(hipMemcpyAsync(ctx->dev[DB_PRE].p, hd, sizeof(PairDesc) * np, hipMemcpyHostToDevice, st));
-  DpArgs a{};
+  DpArgs a = scoring_args(ctx, prm);
   a.pairs = static_cast<const PairDesc*>(ctx->dev[DB_PRE].p);
-  a.a1 = d_a1; a.a2 = d_a2; a.scores = nullptr; a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
-  a.match = prm->match; a.mismatch = prm->mismatch; a.go = prm->go; a.ge = prm->ge; a.hfree = prm->hfree; a.vfree = prm->vfree;
-  a.qlimit = sub_limit(prm);
+  a.a1 = d_a1; a.a2 = d_a2; a.scores = nullptr;
   a.special_blocks = d_special;
   a.lastrow = d_lastrow;
   uint64_t tc = 0, tb = 0;
@@ -1178,13 +1173,13 @@ int build_problem(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, int mem, bool 
   std::vector<uint8_t> z1, z2;
   if (pb.mode == MODE_PROF && !needle && pairs->npairs) {
     const uint32_t n1 = s1.count, n2 = s2.count;
-    std::vector<Row4Desc> hd(n1 + n2);
-    for (uint32_t i = 0; i < n1; ++i) hd[i] = Row4Desc{s1.offset[i], s1.length[i], 0};
-    for (uint32_t i = 0; i < n2; ++i) hd[n1 + i] = Row4Desc{s2.offset[i], s2.length[i], 0};
-    HIP_TRY(ctx->dev[DB_ROW4DESC].ensure(sizeof(Row4Desc) * hd.size() + hd.size()));
-    Row4Desc* dd = static_cast<Row4Desc*>(ctx->dev[DB_ROW4DESC].p);
+    std::vector<ProfSeq> hd(n1 + n2);
+    for (uint32_t i = 0; i < n1; ++i) hd[i] = ProfSeq{s1.offset[i], s1.length[i], 0};
+    for (uint32_t i = 0; i < n2; ++i) hd[n1 + i] = ProfSeq{s2.offset[i], s2.length[i], 0};
+    HIP_TRY(ctx->dev[DB_ROW4DESC].ensure(sizeof(ProfSeq) * hd.size() + hd.size()));
+    ProfSeq* dd = static_cast<ProfSeq*>(ctx->dev[DB_ROW4DESC].p);
     uint8_t* dz = reinterpret_cast<uint8_t*>(dd + hd.size());
-    HIP_TRY(hipMemcpyAsync(dd, hd.data(), sizeof(Row4Desc) * hd.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dd, hd.data(), sizeof(ProfSeq) * hd.size(), hipMemcpyHostToDevice, ctx->stream));
     // column classes of the a2 set for the screened substitution score (one byte per float of the set: indexed like row 0)
     uint8_t* colclass = nullptr;
     if (n2 && e2 && !ctx->knobs.no_screen) {
@@ -1192,9 +1187,8 @@ int build_problem(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, int mem, bool 
       colclass = ctx->codes();
       pb.d_colclass = colclass;
     }
-    if (n1) hipLaunchKernelGGL(row4_zero_kernel, dim3(n1), dim3(64), 0, ctx->stream, dd, static_cast<const float*>(pb.d_a1), dz, (uint8_t*)nullptr);
-    if (n2) hipLaunchKernelGGL(row4_zero_kernel, dim3(n2), dim3(64), 0, ctx->stream, dd + n1, static_cast<const float*>(pb.d_a2), dz + n1, colclass);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_prof_classify(dd, n1, static_cast<const float*>(pb.d_a1), dz, nullptr, ctx->stream));
+    HIP_TRY(launch_prof_classify(dd + n1, n2, static_cast<const float*>(pb.d_a2), dz + n1, colclass, ctx->stream));
     std::vector<uint8_t> hz(n1 + n2);
     HIP_TRY(hipMemcpyAsync(hz.data(), dz, hz.size(), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx_sync(ctx));
@@ -1276,10 +1270,8 @@ int run_ckpt_prefix(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, const
   HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
   HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
   hs1.reset();
-  DpArgs a{};
-  a.a1 = d_a1; a.a2 = d_a2; a.scores = d_scores; a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
-  a.match = prm->match; a.mismatch = prm->mismatch; a.go = prm->go; a.ge = prm->ge; a.hfree = prm->hfree; a.vfree = prm->vfree;
-  a.qlimit = sub_limit(prm);
+  DpArgs a = scoring_args(ctx, prm);
+  a.a1 = d_a1; a.a2 = d_a2; a.scores = d_scores;
   if (d_a2 == ctx->codes() && !ctx->knobs.no_compact) a.special_blocks = ctx->special_blocks();
   a.ckpt = ck->d_ckpt; a.lastrow = ck->d_lastrow; a.ckpt_B = ck->B; a.ckpt_narrow = 1;
   DpArgs ap = a;

@@ -79,7 +79,7 @@ enum CtxDev : int {
   DB_TRIM_IN,       // reference lengths + strands: uploaded by AlignRun::trim, read by its trim kernel
   DB_VOTE,          // vote block of OrientRun::vote_block: descriptors up, votes / bounds written by kmer_vote / rowmax_rest, read by the sweeps and fetch_vote_block
   // build_problem runs in tracyhip_score / tracyhip_align only, never inside a pipeline: no OrientRun is alive beside it
-  DB_ROW4DESC = DB_ORIENT_SC2,  // Row4Desc list of the profile x profile column classes: build_problem
+  DB_ROW4DESC = DB_ORIENT_SC2,  // ProfSeq list of the profile x profile column classes: build_problem
   // the decompose entry points below are calls of their own; each waits for its stream before it returns
   DB_BP_STAGE = DB_ORIENT_SC2,         // staged tracyhip_breakpoint array: find_breakpoint (out), find_homozygous_breakpoint (in / out), decompose_alleles (in)
   DB_HZ_STATUS_STAGE = DB_PRELIM_OPS,  // staged status of find_homozygous_breakpoint
@@ -108,10 +108,10 @@ enum CtxDev : int {
   DB_BCALL_POS,      // basecall positions staged from the host
   DB_BCALL_PAY,      // payload results staged for a host caller
   // ---- tracyhip_consensus_traces (consensus.hip consensus_run) ----
-  CB_A2,        // both strands of the second profile of each pair: copied in, the reverse written by cons_revcomp_kernel; read by the sweeps
-  CB_SEQS,      // ConsSeq list, uploaded
-  CB_CLASS,     // "row 4 is all zero" byte per profile: written by cons_classify_kernel, read back
-  CB_COLCLASS,  // column classes of both strands: written by cons_classify_kernel, read by the screened score sweeps
+  CB_A2,        // both strands of the second profile of each pair: copied in, the reverse written by prof_revcomp_kernel; read by the sweeps
+  CB_SEQS,      // ProfSeq list, uploaded
+  CB_CLASS,     // "row 4 is all zero" byte per profile: written by prof_classify_kernel, read back
+  CB_COLCLASS,  // column classes of both strands: written by prof_classify_kernel, read by the screened score sweeps
   CB_SC2,       // both strand scores per pair, read back
   CB_OPS,       // traceback strings: written by the traceback walk, read by consensus_kernel
   CB_OFF,       // their offsets, uploaded
@@ -121,10 +121,10 @@ enum CtxDev : int {
   CB_PATCH,     // ConsPatch list, uploaded for cons_patch_kernel
   CB_GQ,        // gq table of consensus.h, uploaded once (cons_gq_ready)
   // ---- tracyhip_assemble_traces (assemble.hip assemble_run) ----
-  AB_TR,        // both strands of every trace profile: copied in, the reverse written by asm_revcomp_kernel; read by the sweeps
-  AB_SEQS,      // AsmSeq list, uploaded
-  AB_CLASS,     // "row 4 is all zero" byte per trace and reference: written by asm_classify_kernel, read back
-  AB_REFCLASS,  // column classes of the references: written by asm_classify_kernel, read by the screened score sweeps
+  AB_TR,        // both strands of every trace profile: copied in, the reverse written by prof_revcomp_kernel; read by the sweeps
+  AB_SEQS,      // ProfSeq list, uploaded
+  AB_CLASS,     // "row 4 is all zero" byte per trace and reference: written by prof_classify_kernel, read back
+  AB_REFCLASS,  // column classes of the references: written by prof_classify_kernel, read by the screened score sweeps
   AB_SC2,       // both strand scores per trace, read back
   AB_OPS,       // traceback string of the current step of every group
   AB_OFF,       // their offsets, uploaded
@@ -150,6 +150,14 @@ enum CtxPin : int {
 };
 
 int set_error(int code, const char* fmt, ...);
+// a HIP call inside a function that returns a status of the C ABI: on failure the last error is set and the function returns
+#define HIP_TRY(expr)                                                                               \
+  do {                                                                                              \
+    hipError_t _e = (expr);                                                                         \
+    if (_e != hipSuccess)                                                                           \
+      return set_error(_e == hipErrorOutOfMemory ? TRACYHIP_ERR_OOM : TRACYHIP_ERR_HIP, "%s failed: %s (%s:%d)", \
+                       #expr, hipGetErrorString(_e), __FILE__, __LINE__);                           \
+  } while (0)
 
 // Every switch of the library in one place.  Read from the environment ONCE, when a context is created (TRACYHIP_<NAME IN CAPITALS>),
 // changed afterwards only through tracyhip_set_option(ctx, "<name>", "<value>"); tracyhip_describe() prints them.  Every one selects
@@ -353,6 +361,14 @@ int stage_in(tracyhip_ctx* ctx, DevBuf& buf, const void* src, uint64_t bytes, in
 int stage_out(tracyhip_ctx* ctx, DevBuf& buf, void* user, uint64_t bytes, int mem, bool upload, void** dev);
 int unstage(tracyhip_ctx* ctx, void* user, const void* dev, uint64_t bytes, int mem);
 int check_params(const tracyhip_params* prm, uint64_t max_mn);
+// The workspace a context may plan with: the caller's limit (tracyhip_set_workspace_limit), else this context's share of 70 % of what
+// is free on the device now plus `held`, the bytes it already holds for the purpose.  (A driver call: each site has its own
+// precondition for asking at all.)
+int workspace_limit(tracyhip_ctx* ctx, uint64_t held, uint64_t* limit);
+// a seqset of profiles as the batch calls take one: its kind and arrays; then that the profiles [lo, hi) have columns.  false: the
+// error is set (`name` opens the message)
+bool check_profile_set(const tracyhip_seqset& s, const char* name);
+bool check_profile_columns(const tracyhip_seqset& s, const char* name, uint32_t lo, uint32_t hi);
 // stage: DP_PLAIN = score-only or full-matrix traceback; DP_CKPT = score-only pass that also writes wavefront
 // checkpoints + last-row values (PairDesc::ckpt_off / lastrow_off set by the caller); DP_BAND = band traceback
 // from those checkpoints (trace must be true); DP_PREFIX = prefix bound of the semiglobal score (rows 1 .. kPrefixLanes*K of
@@ -379,6 +395,8 @@ bool narrow_ok(const tracyhip_params* prm, uint32_t maxm, int K, int64_t Q = 0);
 // profile x profile score kernel with 16-bit cells for pairs of at most max_mn = m + n (Q: largest substitution score, 0 = a priori)
 bool arith16_ok(const tracyhip_params* prm, uint64_t max_mn, int64_t Q);
 int32_t sub_limit(const tracyhip_params* prm);
+// sweep arguments with what a tracyhip_params decides: the scoring fields, qlimit and the context's error words
+DpArgs scoring_args(tracyhip_ctx* ctx, const tracyhip_params* prm);
 // largest |match| / |mismatch| whose table entries x 32 (tagged tracebacks, band kernels) fit int16; wider scorings take slower forms
 constexpr int32_t kWideScore = 1000;
 // device error block (DpArgs::err): kErrWords words owned by the DP launches + one verdict word of the pipelines' reference check
@@ -390,6 +408,28 @@ constexpr int kWiden = 1;
 int range_verdict(const tracyhip_params* prm, const int32_t* herr, const std::vector<std::pair<uint32_t, int>>& narrow_launches,
                   uint64_t max_mn, int value_shift);
 int build_problem(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, int mem, bool needle, DpProblem& pb, uint64_t* max_mn);
+
+// ---- profile batches (prof_batch.hip): what build_problem, consensus_run and assemble_run share ----
+struct ProfSeq {  // one profile of a batch: float offset and columns
+  uint64_t off;
+  uint32_t len, pad;
+};
+// revcomp of n profiles (profile.h:74-90): profile s is read at in + off and written at out + rev_base + off
+hipError_t launch_prof_revcomp(const ProfSeq* seqs, uint32_t n, const float* in, float* out, uint64_t rev_base, hipStream_t st);
+// zero[s] = row 4 ('N') of profile s is all zero (chooses the 16-term score body); colclass (or null) receives the class of every
+// column, indexed like row 0 of `data`
+hipError_t launch_prof_classify(const ProfSeq* seqs, uint32_t n, const float* data, uint8_t* zero, uint8_t* colclass, hipStream_t st);
+// The launch loop of the batch calls over units [lo, hi) of a sorted descriptor list (hd: host copy, dd: device copy, k[u]: strip
+// height of unit u): one launch per run of equal strip height and PAIR_ROW4_ZERO.  `args` carries everything but the pairs and the
+// walk pointers.
+// score form, two descriptors per unit (both strands): 16-bit cells where !wide, !no_narrow and arith16_ok hold for the run's largest
+// m + n, which is then appended to narrow_launches for range_verdict; timed as TRACYHIP_TIMER_SCORE
+int prof_score_runs(tracyhip_ctx* ctx, const tracyhip_params* prm, bool wide, const DpArgs& args, const PairDesc* hd, const PairDesc* dd,
+                    const int* k, uint32_t lo, uint32_t hi, std::vector<std::pair<uint32_t, int>>& narrow_launches);
+// traceback form, one descriptor per unit: the sweep walks its pairs itself (ops / ops_off / ops_len by PairDesc::out), or with
+// no_fused_walk a walk launch follows each sweep; timed as TRACYHIP_TIMER_TRACE / TRACYHIP_TIMER_WALK
+int prof_trace_runs(tracyhip_ctx* ctx, const DpArgs& args, const PairDesc* hd, const PairDesc* dd, const int* k, uint32_t lo, uint32_t hi,
+                    uint8_t* ops, const uint64_t* ops_off, uint32_t* ops_len);
 
 // ---- band kernels (band16.h): Gotoh on a diagonal band, four pairs per wave ----
 // a batch for them: descriptors whose a1_off / a1_stride point into the substitution tables d_qp (build_b16_tables), a2_off into

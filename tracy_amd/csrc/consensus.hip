@@ -1,11 +1,12 @@
 // consensus.hip -- tracyhip_consensus_traces: the hot section of `tracy consensus` (consensus.h:501-577) for a batch of trace pairs.
 //
-// Per pair: revcomp(second) on the device (profile.h:74-90); gotohScore(first, second) and gotohScore(first, revcomp) in one profile x
-// profile score launch; forward iff gsFwd > gsRev (decided on the device: cons_decide_kernel patches the traceback descriptors); gotoh of
-// the chosen strand (traceback, fused walk); _createAlignment rows; the overlap test and pairwiseConsensus / gtLetter in
-// consensus_kernel, one wave per pair.  Everything after the profile classes is queued on the stream without the host in between;
-// the call synchronises once at its end (plus once for the classes, which choose the score kernels), then the host recomputes the
-// columns the consensus screen flagged (consensus.h) and patches them in.
+// Per pair: revcomp(second) on the device (profile.h:74-90, prof_batch.hip); gotohScore(first, second) and gotohScore(first,
+// revcomp) in one profile x profile score launch (the launch loops are prof_batch.hip's); forward iff gsFwd > gsRev (decided on the
+// device: cons_decide_kernel patches the traceback descriptors); gotoh of the chosen strand (traceback, fused walk);
+// _createAlignment rows; the overlap test and pairwiseConsensus / gtLetter in consensus_kernel, one wave per pair.  Everything
+// after the profile classes is queued on the stream without the host in between; the call synchronises once at its end (plus once
+// for the classes, which choose the score kernels), then the host recomputes the columns the consensus screen flagged (consensus.h)
+// and patches them in.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,54 +21,7 @@
 
 using namespace tracyhip;
 
-#define HIP_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess)                                                                           \
-      return set_error(_e == hipErrorOutOfMemory ? TRACYHIP_ERR_OOM : TRACYHIP_ERR_HIP, "%s failed: %s (%s:%d)", \
-                       #expr, hipGetErrorString(_e), __FILE__, __LINE__);                           \
-  } while (0)
-
 namespace {
-
-struct ConsSeq {  // one profile of the batch: float offset and columns
-  uint64_t off;
-  uint32_t len, pad;
-};
-
-// revcomp of every `second` profile (orc_revcomp_profile / profile.h:74-90): rows A<->T, C<->G swapped, N and gap kept, columns
-// reversed; sequence s is written at rev_base + its own offset.  One workgroup per sequence.
-__global__ __launch_bounds__(256) void cons_revcomp_kernel(const ConsSeq* __restrict__ seqs, const float* __restrict__ in, float* __restrict__ out,
-                                                           uint64_t rev_base) {
-  const ConsSeq s = seqs[blockIdx.x];
-  const float* p = in + s.off;
-  float* q = out + rev_base + s.off;
-  const uint64_t n = s.len;
-  for (uint32_t j = threadIdx.x; j < s.len; j += blockDim.x) {
-    const uint64_t src = n - 1 - j;
-    q[0 * n + j] = p[3 * n + src];
-    q[1 * n + j] = p[2 * n + src];
-    q[2 * n + j] = p[1 * n + src];
-    q[3 * n + j] = p[0 * n + src];
-    q[4 * n + j] = p[4 * n + src];
-    q[5 * n + j] = p[5 * n + src];
-  }
-}
-
-// row 4 ('N') zero over a whole profile (chooses the 16-term score body, as build_problem does); colclass: the class of every
-// column of the a2 buffer (screened substitution scores), null for the a1 set.  One wave per sequence.
-__global__ __launch_bounds__(64) void cons_classify_kernel(const ConsSeq* __restrict__ seqs, const float* __restrict__ data, uint64_t base,
-                                                           uint8_t* __restrict__ zero, uint8_t* __restrict__ colclass) {
-  const ConsSeq s = seqs[blockIdx.x];
-  const uint64_t off = base + s.off;
-  bool nz = false;
-  for (uint32_t j = threadIdx.x; j < s.len; j += 64) {
-    nz |= !(data[off + 4ull * s.len + j] == 0.0f);
-    if (colclass) colclass[off + j] = (uint8_t)column_class(data + off, s.len, j);
-  }
-  const unsigned long long any = __ballot(nz);
-  if (threadIdx.x == 0) zero[blockIdx.x] = any ? 0 : 1;
-}
 
 // strand of every pair of a chunk from the two orientation scores (consensus.h:545: forward iff gsFwd > gsRev); the traceback
 // descriptor then reads the reverse complement
@@ -201,12 +155,9 @@ __global__ void cons_patch_kernel(const ConsPatch* __restrict__ p, uint32_t n, u
 }
 
 bool check_profiles(const tracyhip_seqset& s, uint32_t np, const char* name) {
-  if (s.kind != TRACYHIP_SEQ_PROFILE) return set_error(TRACYHIP_ERR_ARG, "%s: kind must be PROFILE", name), false;
-  if (!s.offset || !s.length || !s.data) return set_error(TRACYHIP_ERR_ARG, "%s: null data / offset / length arrays", name), false;
+  if (!check_profile_set(s, name)) return false;
   if (s.count < np) return set_error(TRACYHIP_ERR_ARG, "%s: %u profiles for %u pairs", name, s.count, np), false;
-  for (uint32_t i = 0; i < np; ++i)
-    if (s.length[i] == 0) return set_error(TRACYHIP_ERR_ARG, "%s: profile %u has no columns", name, i), false;
-  return true;
+  return check_profile_columns(s, name, 0, np);
 }
 
 int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tracyhip_params* prm, int mem,
@@ -234,30 +185,28 @@ int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tr
   HIP_TRY(hipMemcpyAsync(d_a2, s2.data, e2 * 4, mem == TRACYHIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
   const uint64_t rev_base = e2;
   {
-    std::vector<ConsSeq> hs(2 * (size_t)np);
+    std::vector<ProfSeq> hs(2 * (size_t)np);
     for (uint32_t i = 0; i < np; ++i) {
-      hs[i] = ConsSeq{s1.offset[i], s1.length[i], 0};
-      hs[np + i] = ConsSeq{s2.offset[i], s2.length[i], 0};
+      hs[i] = ProfSeq{s1.offset[i], s1.length[i], 0};
+      hs[np + i] = ProfSeq{s2.offset[i], s2.length[i], 0};
     }
-    HIP_TRY(B[CB_SEQS].ensure(sizeof(ConsSeq) * hs.size()));
-    HIP_TRY(hipMemcpyAsync(B[CB_SEQS].p, hs.data(), sizeof(ConsSeq) * hs.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(B[CB_SEQS].ensure(sizeof(ProfSeq) * hs.size()));
+    HIP_TRY(hipMemcpyAsync(B[CB_SEQS].p, hs.data(), sizeof(ProfSeq) * hs.size(), hipMemcpyHostToDevice, st));
   }
-  const ConsSeq* d_seqs = static_cast<const ConsSeq*>(B[CB_SEQS].p);
+  const ProfSeq* d_seqs = static_cast<const ProfSeq*>(B[CB_SEQS].p);
   int trc;
   if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 2 * 24ull * (e2 / 6)))) return trc;
-  hipLaunchKernelGGL(cons_revcomp_kernel, dim3(np), dim3(256), 0, st, d_seqs + np, d_a2, d_a2, rev_base);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_prof_revcomp(d_seqs + np, np, d_a2, d_a2, rev_base, st));
   // classes: row 4 of first, second (revcomp has the same row 4), column classes of both strands
   uint8_t* d_zero; HIP_TRY(ensure_into(B[CB_CLASS], 2 * (size_t)np, d_zero));
   uint8_t* d_colclass = nullptr;
   if (!ctx->knobs.no_screen) {
     HIP_TRY(ensure_into(B[CB_COLCLASS], 2 * e2, d_colclass));
   }
-  hipLaunchKernelGGL(cons_classify_kernel, dim3(np), dim3(64), 0, st, d_seqs, d_a1, (uint64_t)0, d_zero, (uint8_t*)nullptr);
-  hipLaunchKernelGGL(cons_classify_kernel, dim3(np), dim3(64), 0, st, d_seqs + np, (const float*)d_a2, (uint64_t)0, d_zero + np, d_colclass);
+  HIP_TRY(launch_prof_classify(d_seqs, np, d_a1, d_zero, nullptr, st));
+  HIP_TRY(launch_prof_classify(d_seqs + np, np, d_a2, d_zero + np, d_colclass, st));
   if (d_colclass)  // (the zero flags of the reverse strand land on the forward ones again: same row 4)
-    hipLaunchKernelGGL(cons_classify_kernel, dim3(np), dim3(64), 0, st, d_seqs + np, (const float*)d_a2, rev_base, d_zero + np, d_colclass);
-  HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_prof_classify(d_seqs + np, np, d_a2 + rev_base, d_zero + np, d_colclass + rev_base, st));
   if ((trc = timing_end(ctx))) return trc;
   std::vector<uint8_t> hz(2 * (size_t)np);
   HIP_TRY(hipMemcpyAsync(hz.data(), d_zero, hz.size(), hipMemcpyDeviceToHost, st));
@@ -284,12 +233,10 @@ int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tr
     if (K[x] != K[y]) return K[x] > K[y];
     return row4(x) > row4(y);
   });
-  uint64_t limit = ctx->ws_limit;
-  if (limit == 0) {
-    size_t fr = 0, tot = 0;
-    HIP_TRY(hipMemGetInfo(&fr, &tot));
-    limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->dev[DB_BITS].cap + ctx->dev[DB_SCRATCH].cap;
-  }
+  std::vector<int> k_sorted(np);  // strip heights in launch order
+  for (uint32_t j = 0; j < np; ++j) k_sorted[j] = K[order[j]];
+  uint64_t limit;
+  if ((rc = workspace_limit(ctx, ctx->dev[DB_BITS].cap + ctx->dev[DB_SCRATCH].cap, &limit))) return rc;
   // descriptors: score pairs (2 per pair, in chunk order) then traceback pairs (1 per pair)
   PairDesc* hsd; HIP_TRY(ensure_into(ctx->pin[PB_DESC], 3 * (size_t)np, hsd));
   PairDesc* htd = hsd + 2 * (size_t)np;
@@ -375,19 +322,14 @@ int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tr
   uint32_t* d_nfix = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(B[CB_FIX].p) + sizeof(ConsFixup) * (size_t)fix_cap);
   HIP_TRY(hipMemsetAsync(d_nfix, 0, sizeof(uint32_t), st));
 
-  DpArgs a{};
+  DpArgs a = scoring_args(ctx, prm);
   a.a1 = d_a1;
   a.a2 = d_a2;
   a.bits = static_cast<uint64_t*>(ctx->dev[DB_BITS].p);
   a.bits32 = static_cast<uint32_t*>(ctx->dev[DB_BITS].p);
   a.scratch = static_cast<int32_t*>(ctx->dev[DB_SCRATCH].p);
-  a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
-  a.match = prm->match; a.mismatch = prm->mismatch; a.go = prm->go; a.ge = prm->ge;
-  a.hfree = prm->hfree; a.vfree = prm->vfree;
-  a.qlimit = sub_limit(prm);
   a.screen = ctx->knobs.no_screen ? 0 : 1;
   a.colcode = d_colclass;
-  const bool fused_walk = !ctx->knobs.no_fused_walk;
   std::vector<std::pair<uint32_t, int>> narrow_launches;
 
   ConsArgs ca{};
@@ -405,53 +347,16 @@ int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tr
 
   for (const Chunk& c : chunks) {
     // orientation scores: both strands of every pair of the chunk, one launch per run of equal strip height / term count
-    for (uint32_t j = c.lo; j < c.hi;) {
-      uint32_t e = j;
-      const int k = K[order[j]];
-      const uint32_t r4 = htd[j].flags & PAIR_ROW4_ZERO;
-      uint64_t mn = 0, cells = 0;
-      while (e < c.hi && K[order[e]] == k && (htd[e].flags & PAIR_ROW4_ZERO) == r4) {
-        mn = std::max<uint64_t>(mn, (uint64_t)htd[e].m + htd[e].n);
-        cells += 2ull * htd[e].m * htd[e].n;
-        ++e;
-      }
-      const bool a16 = !wide && !ctx->knobs.no_narrow && arith16_ok(prm, mn, 0);
-      if (a16) narrow_launches.emplace_back((uint32_t)mn, 0);
-      a.pairs = dsd + 2 * (size_t)j;
-      a.scores = d_sc2;
-      a.walk_ops = nullptr; a.walk_ops_off = nullptr; a.walk_ops_len = nullptr;
-      if ((trc = timing_begin(ctx, TRACYHIP_TIMER_SCORE, cells, 0))) return trc;
-      HIP_TRY(launch_gotoh_prof(k, false, r4 != 0, a16, a, 2 * (e - j), st));
-      if ((trc = timing_end(ctx))) return trc;
-      j = e;
-    }
+    a.scores = d_sc2;
+    if ((rc = prof_score_runs(ctx, prm, wide, a, hsd, dsd, k_sorted.data(), c.lo, c.hi, narrow_launches))) return rc;
     const uint32_t cn = c.hi - c.lo;
     if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 0))) return trc;
     hipLaunchKernelGGL(cons_decide_kernel, dim3((cn + 255) / 256), dim3(256), 0, st, dtd + c.lo, cn, (const int32_t*)d_sc2, rev_base, o_sf, o_sr, o_fwd);
     HIP_TRY(hipGetLastError());
     if ((trc = timing_end(ctx))) return trc;
     // gotoh(first, chosen strand): traceback planes + walk
-    for (uint32_t j = c.lo; j < c.hi;) {
-      uint32_t e = j;
-      const int k = K[order[j]];
-      const uint32_t r4 = htd[j].flags & PAIR_ROW4_ZERO;
-      uint64_t cells = 0;
-      while (e < c.hi && K[order[e]] == k && (htd[e].flags & PAIR_ROW4_ZERO) == r4) { cells += (uint64_t)htd[e].m * htd[e].n; ++e; }
-      a.pairs = dtd + j;
-      a.scores = o_score;
-      if (fused_walk) { a.walk_ops = d_ops; a.walk_ops_off = d_off; a.walk_ops_len = o_len; }
-      if ((trc = timing_begin(ctx, TRACYHIP_TIMER_TRACE, cells, cells / 2))) return trc;
-      HIP_TRY(launch_gotoh_prof(k, true, r4 != 0, false, a, e - j, st));
-      if ((trc = timing_end(ctx))) return trc;
-      if (!fused_walk) {
-        WalkArgs wa{};
-        wa.pairs = dtd + j; wa.bits = a.bits; wa.ops = d_ops; wa.ops_off = d_off; wa.ops_len = o_len; wa.err = a.err; wa.npairs = e - j; wa.K = k;
-        if ((trc = timing_begin(ctx, TRACYHIP_TIMER_WALK, 0, 0))) return trc;
-        HIP_TRY(launch_gotoh_walk(wa, st));
-        if ((trc = timing_end(ctx))) return trc;
-      }
-      j = e;
-    }
+    a.scores = o_score;
+    if ((rc = prof_trace_runs(ctx, a, htd, dtd, k_sorted.data(), c.lo, c.hi, d_ops, d_off, o_len))) return rc;
     // rows, then the consensus of the chunk
     RowsArgs ra{};
     ra.pairs = dtd + c.lo;

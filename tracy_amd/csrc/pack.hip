@@ -12,14 +12,6 @@
 
 using namespace tracyhip;
 
-#define HIP_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess)                                                                           \
-      return set_error(_e == hipErrorOutOfMemory ? TRACYHIP_ERR_OOM : TRACYHIP_ERR_HIP, "%s failed: %s (%s:%d)", \
-                       #expr, hipGetErrorString(_e), __FILE__, __LINE__);                           \
-  } while (0)
-
 namespace {
 constexpr uint32_t kScanThreads = 1024;
 constexpr uint32_t kMaxKinds = 16;

@@ -20,14 +20,6 @@
 
 using namespace tracyhip;
 
-#define HIP_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess)                                                                           \
-      return set_error(_e == hipErrorOutOfMemory ? TRACYHIP_ERR_OOM : TRACYHIP_ERR_HIP, "%s failed: %s (%s:%d)", \
-                       #expr, hipGetErrorString(_e), __FILE__, __LINE__);                           \
-  } while (0)
-
 namespace {
 void reset_call_stats(tracyhip_ctx* ctx, uint32_t ntraces) {
   ctx->stats = tracyhip_call_stats{};
@@ -1045,12 +1037,9 @@ struct AlignRun {
       // plain form.  It stays within the limit run_dp plans with (the caller's workspace limit, or this context's share of the free
       // memory): a pair whose banded words exceed it, and the whole batch if the sum does, go back to whole matrices.
       {
-        uint64_t limit = ctx->ws_limit;
-        if (limit == 0) {
-          size_t fr = 0, tot = 0;
-          HIP_TRY(hipMemGetInfo(&fr, &tot));
-          limit = (uint64_t)(fr * 0.70 / ctx->mem_share) + ctx->dev[DB_BITS].cap;
-        }
+        uint64_t limit;
+        const int lrc = workspace_limit(ctx, ctx->dev[DB_BITS].cap, &limit);
+        if (lrc) return lrc;
         uint64_t bytes = 0;
         bool unband_all = false;
         for (PairDesc& d : pb.desc) {

@@ -35,13 +35,6 @@
 
 using namespace tracyhip;
 
-#define HIP_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess)                                                                           \
-      return set_error(_e == hipErrorOutOfMemory ? TRACYHIP_ERR_OOM : TRACYHIP_ERR_HIP, "%s failed: %s (%s:%d)", \
-                       #expr, hipGetErrorString(_e), __FILE__, __LINE__);                           \
-  } while (0)
 #define TRY(expr) do { const int _rc = (expr); if (_rc) return _rc; } while (0)
 
 namespace {
@@ -646,9 +639,7 @@ int workspace_budget(tracyhip_ctx* ctx, uint64_t held, uint64_t* out, bool* from
     if (from_cache) *from_cache = true;
     return TRACYHIP_OK;
   }
-  size_t fr = 0, tot = 0;
-  HIP_TRY(hipMemGetInfo(&fr, &tot));
-  *out = (uint64_t)(fr * 0.70 / ctx->mem_share) + held;
+  TRY(workspace_limit(ctx, held, out));
   ctx->ws_cache_budget = *out; ctx->ws_cache_held = held; ctx->ws_cache_share = ctx->mem_share;
   return TRACYHIP_OK;
 }
@@ -667,10 +658,8 @@ int with_fresh_budget(tracyhip_ctx* ctx, Plan plan) {
 }
 
 DpArgs sweep_args(tracyhip_ctx* ctx, const tracyhip_params& p, const void* d_a1, const void* d_a2, int32_t* d_scores, int32_t* d_lastrow) {
-  DpArgs a{};
-  a.a1 = d_a1; a.a2 = d_a2; a.scores = d_scores; a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
-  a.match = p.match; a.mismatch = p.mismatch; a.go = p.go; a.ge = p.ge; a.hfree = p.hfree; a.vfree = p.vfree;
-  a.qlimit = sub_limit(&p);
+  DpArgs a = scoring_args(ctx, &p);
+  a.a1 = d_a1; a.a2 = d_a2; a.scores = d_scores;
   a.ckpt = d_lastrow;  // (never written: row m only)
   a.lastrow = d_lastrow;
   a.ckpt_B = 0x7fffffffu;
@@ -2260,12 +2249,10 @@ struct DecStream : StreamCall {
       HIP_TRY(hipGetLastError());
     }
     {
-      DpArgs a{};
+      DpArgs a = scoring_args(ctx, &p);
       a.pairs = sc.pre;
       if (share) { a.index = sc.flist; a.count = sc.fcount + 2; }
-      a.a1 = A.seqs2; a.a2 = d_cq_ref; a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p);
-      a.match = p.match; a.mismatch = p.mismatch; a.go = p.go; a.ge = p.ge; a.hfree = p.hfree; a.vfree = p.vfree;
-      a.qlimit = sub_limit(&p);
+      a.a1 = A.seqs2; a.a2 = d_cq_ref;
       a.special_blocks = kn.no_compact ? nullptr : A.cq_special;
       a.lastrow = d_lastrow;
       // (the side stream starts where the call's stream is NOW: allelicFraction begins with the prefixes, not with the fills and copies)
