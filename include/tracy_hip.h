@@ -28,6 +28,7 @@
  *     trimTrace / createProfile(tr, bc)    trim.h:35-73 / profile.h:21-52   (same call)
  *     gtLetter / pairwiseConsensus         consensus.h:94-171 / 189-238     (consensus_kernel, same call)
  *   assemble(), reference-guided chain     assemble.h:219-288               tracyhip_assemble_traces
+ *   assemble(), de novo                    assemble.h:378-471, msa.h:33-368 tracyhip_denovo_traces
  *     _createProfile(char MSA) / consensus align.h:138-180 / msa.h:165-254   (msa_profile / msa_consensus kernels, same call)
  *
  * Conventions
@@ -161,6 +162,9 @@ typedef struct {
   uint32_t cons_chunks;          /* ... chunks the batch was cut into to fit the workspace limit */
   uint32_t asm_chunks;           /* tracyhip_assemble_traces: chunks of groups the batch was cut into to fit the workspace limit */
   uint32_t asm_steps;            /* ... chain steps launched, summed over the chunks (a chunk runs as many as its largest group has matching traces) */
+  uint32_t denovo_chunks;        /* tracyhip_denovo_traces: chunks of groups the batch was cut into to fit the workspace limit */
+  uint32_t denovo_rounds;        /* ... overlap rounds launched, summed over the chunks (a chunk runs as many as its slowest trace tries partners) */
+  uint32_t denovo_steps;         /* ... tree heights launched, summed over the chunks (a chunk runs as many as its tallest tree has) */
 } tracyhip_call_stats;
 int tracyhip_last_call_stats(tracyhip_ctx* ctx, tracyhip_call_stats* out);
 const char* tracyhip_last_error(void);
@@ -614,6 +618,70 @@ int tracyhip_assemble_validate(const tracyhip_assemble_job* job, const tracyhip_
 int tracyhip_assemble_traces(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem,
                              const tracyhip_assemble_result* out);
 
+/* ---- de novo assembly (`tracy assemble` without -r, assemble.h:378-471 -> msa.h) for a batch of trace groups ---------------------
+ * Group g owns the traces group_first[g] .. group_first[g + 1] - 1 (K of them).  Per group:
+ *   1. the reverse complement of every trace (profile.h:74-90) and the strand table
+ *          T[i][j][oi][oj] = gotohScore(strand oi of trace i as a1, strand oj of trace j as a2)
+ *      for every ordered pair i != j and all four strand combinations: 4 K (K - 1) pairs, ONE family of score launches for the
+ *      whole batch.  (No entry follows from another: the 25-term fp32 sum changes its order under reverse complement and under
+ *      swapping the sides.)  The sequential loop of the reference scores K (K - 1) / 2 + iterations * K (K - 1) pairs, with at least
+ *      two iterations on any input with a positive score: the table is at most about 1.6 x those cells, removes iterations * K
+ *      dependent launches and supplies every score of steps 3 and 4.
+ *   2. revSeqBasedOnDist (msa.h:258-323) on the host, from the table: one strand bit per trace (a double flip is the original
+ *      profile bit for bit)
+ *   3. the overlap test of assemble.h:425-456, in rounds: every undecided trace i aligns with its next partner j (gotoh with
+ *      traceback), numAligned = the 's' ops, gs = T[i][j][o_i][o_j]; the trace stays when
+ *          numAligned / len_i > 0.1 && numAligned > 25 && gs > numAligned * match_fraction * match + numAligned * (1 - match_fraction) * mismatch
+ *      (int x float products, a float sum, then promoted: assemble.h:441); a trace that runs out of partners is excluded
+ *   4. msa() (msa.h:326-368) of the traces that stay, when there are at least two: the distance matrix comes from the table, UPGMA
+ *      and the node heights run on the host, the merges of one height are one batch -- gotoh(left, right), the rows of the left
+ *      child above those of the right one (msa.h:121-150), _createProfile (align.h:138-180) of every node below the root
+ *   5. consensus() (msa.h:165-254) over all rows
+ * Rows, profiles and consensus equal the per-group host path's (tracy_amd/host/msa.hpp) bit for bit.
+ * prm: any scoring tracyhip_gotoh_align accepts; the command uses {match, mismatch, go, ge, 1, 1} (AlignConfig<true,true>). */
+typedef struct {
+  uint32_t ngroups;
+  tracyhip_seqset traces;        /* kind PROFILE: the trimmed FORWARD profile of every trace (assemble.h:384-417), every length >= 1,
+                                    count >= group_first[ngroups] */
+  const uint32_t* group_first;   /* HOST array [ngroups + 1], non-decreasing */
+  float match_fraction;          /* matchFraction (-f, default 0.5) */
+  float fraction_called;         /* fractionCalled (-d, default 0.1): covThreshold = (int32_t)(fraction_called * (float)rows), msa.h:196 */
+} tracyhip_denovo_job;
+
+/* Result arrays where `mem` says; rows_offset / col_offset are HOST arrays.  With K traces in group g and sum_len the sum of their
+ * lengths the caller provides
+ *     K * sum_len bytes of `rows` from rows_offset[g] on, and
+ *     sum_len elements of gapped / cons / qual from col_offset[g] on
+ * (every merge adds at most the columns of its two sides). */
+typedef struct {
+  uint8_t* forward;          /* [group_first[ngroups]], indexed like the traces set: fwdProfiles[i] after revSeqBasedOnDist */
+  uint32_t* partner;         /* ... the index within the group of the first j that passed the overlap test; UINT32_MAX: excluded */
+  uint32_t* row;             /* ... the trace's row in the group's alignment; UINT32_MAX: none (excluded -- or UPGMA stopped on negative
+                                scores before the trace was joined, msa.h:86: the alignment is then the last node made) */
+  uint32_t* nrows;           /* [ngroups] 0: fewer than two traces stay ("At least 2 traces are required") -- ncol and cons_len are 0 and
+                                no payload is written */
+  uint32_t* ncol;            /* [ngroups] alignment columns */
+  uint8_t* rows;             /* nrows x ncol bytes, packed, at rows_offset[g], in the order msa() returns them */
+  uint8_t* gapped;           /* as tracyhip_assemble_result */
+  uint8_t* cons;
+  uint8_t* qual;
+  uint32_t* cons_len;        /* [ngroups] */
+  const uint64_t* rows_offset;  /* HOST array [ngroups] */
+  const uint64_t* col_offset;   /* HOST array [ngroups] */
+} tracyhip_denovo_result;
+
+/* what tracyhip_denovo_traces checks before it touches a device (none is needed here): what tracyhip_assemble_validate checks,
+ * without the references.  An empty batch, a group without traces and a group of one trace are fine (nrows 0). */
+int tracyhip_denovo_validate(const tracyhip_denovo_job* job, const tracyhip_params* prm, int mem, const tracyhip_denovo_result* out);
+/* The batch is cut into chunks of groups whose traceback planes fit the workspace limit (tracyhip_set_workspace_limit); a chunk runs
+ * its overlap rounds, then its tree heights, then its consensus.  Host synchronisations (tracyhip_call_stats::host_syncs):
+ *     1 (profile classes) + 1 (strand table) + denovo_rounds + denovo_steps + 1 (the end)
+ * where a chunk adds to denovo_rounds the largest number of partners any of its traces tries and to denovo_steps the height of its
+ * tallest tree -- neither depends on how many groups the chunk holds.  Un-normalised profiles that leave the 16-bit score range
+ * repeat the call on int32 after the table: 2 more. */
+int tracyhip_denovo_traces(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip_params* prm, int mem,
+                           const tracyhip_denovo_result* out);
+
 /* ---- asynchronous forms (SURVEY.md 8b "Threading": synchronous by default with an async variant) ---------------------
  * Same arguments and results as the call without the suffix; the call returns as soon as the work is queued on the
  * context.  A context executes its calls in issue order on its own worker thread and stream (the pipelines need the
@@ -634,6 +702,8 @@ int tracyhip_consensus_traces_async(tracyhip_ctx* ctx, const tracyhip_consensus_
 int tracyhip_basecall_traces_async(tracyhip_ctx* ctx, const tracyhip_basecall_job* job, int mem, const tracyhip_basecall_result* out);
 int tracyhip_assemble_traces_async(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem,
                                    const tracyhip_assemble_result* out);
+int tracyhip_denovo_traces_async(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip_params* prm, int mem,
+                                 const tracyhip_denovo_result* out);
 
 /* ---- device groups: the GPUs of one node behind one handle (north star: "batches of traces shard embarrassingly across
  * the 8 GPUs of one node") ------------------------------------------------------------------------------------------

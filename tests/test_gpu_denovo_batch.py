@@ -1,0 +1,179 @@
+"""tracyhip_denovo_traces (de novo `tracy assemble` for a batch of trace groups) against the oracle chain of tests/denovo_cases.py --
+msa_oracle.rev_seq_based_on_dist, the overlap filter, upgma / palign / consensus -- every group and every field, and
+`tracy_amd_cli assemble --denovo --batch` against the one-group command, byte by byte.  tests/test_denovo_cases.py asserts (without
+a GPU) that the inputs hold the cases they are named for."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import denovo_cases as dc
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLI = os.path.join(ROOT, "tracy_amd", "bin", "tracy_amd_cli")
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import tracy_amd
+    c = tracy_amd.Context(0)
+    yield c
+    c.close()
+
+
+def same(a, b):
+    for k in ("forward", "partner", "row", "nrows", "ncol", "cons_len"):
+        assert np.array_equal(a[k], b[k]), k
+    for k in ("rows", "gapped", "cons", "qual"):
+        assert a[k] == b[k], k
+
+
+@pytest.mark.parametrize("fracmatch", dc.FRACTIONS)
+@pytest.mark.parametrize("device", [False, True])
+@pytest.mark.parametrize("option", [None, "no_fused_walk", "no_screen"])
+def test_batch_matches_oracle(ctx, option, device, fracmatch):
+    groups, want = list(dc.groups()), dc.oracle(fracmatch)
+    if option:
+        ctx.set_option(option, 1)
+    try:
+        got = ctx.denovo_traces(groups, dc.SCORE, fracmatch, dc.CALLED, device=device)
+    finally:
+        if option:
+            ctx.set_option(option, 0)
+    dc.check(got, want, groups)
+    stats = ctx.last_call_stats()
+    assert stats["traces"] == sum(len(g) for g in groups) and stats["denovo_chunks"] == 1
+    assert stats["denovo_rounds"] == max(w["rounds"] for w in want) and stats["denovo_steps"] == max(w["heights"] for w in want)
+    assert stats["host_syncs"] == dc.expected_syncs(want)
+
+
+def test_chunks_async_and_the_synchronisation_count(ctx):
+    from tracy_amd import capi
+    groups, want = list(dc.groups()), dc.oracle(0.5)
+    base = ctx.denovo_traces(groups, dc.SCORE, 0.5, dc.CALLED)
+    syncs = ctx.last_call_stats()["host_syncs"]
+    assert syncs == dc.expected_syncs(want)
+    # every group twice, in one chunk: the same number of synchronisations
+    twice = [g for g in groups for _ in range(2)]
+    got2 = ctx.denovo_traces(twice, dc.SCORE, 0.5, dc.CALLED)
+    stats = ctx.last_call_stats()
+    assert stats["denovo_chunks"] == 1 and stats["host_syncs"] == syncs
+    dc.check(got2, [w for w in want for _ in range(2)], twice)
+    # the async form: two calls queued on one context
+    half = len(groups) // 2
+    p = capi.PreparedDenovo(groups[:half], dc.SCORE, 0.5, dc.CALLED)
+    q = capi.PreparedDenovo(groups[half:], dc.SCORE, 0.75, dc.CALLED)
+    ctx.denovo_traces_async(p.job, p.prm, p.out)
+    ctx.denovo_traces_async(q.job, q.prm, q.out)
+    ctx.synchronize()
+    dc.check(p.results(), want[:half], groups[:half])
+    dc.check(q.results(), dc.oracle(0.75)[half:], groups[half:])
+    # a workspace limit that fits a few groups at a time: the batch runs in chunks of groups, same results
+    ctx.set_workspace_limit(4 << 20)
+    try:
+        got = ctx.denovo_traces(groups, dc.SCORE, 0.5, dc.CALLED)
+        stats = ctx.last_call_stats()
+        assert stats["denovo_chunks"] > 1
+        assert stats["host_syncs"] == 2 + stats["denovo_rounds"] + stats["denovo_steps"] + 1
+        dev = ctx.denovo_traces(groups, dc.SCORE, 0.5, dc.CALLED, device=True)
+        ctx.set_workspace_limit(64 << 10)  # no group of several hundred columns fits alone: the error names the group
+        with pytest.raises(capi.TracyHipError) as e:
+            ctx.denovo_traces(groups, dc.SCORE, 0.5, dc.CALLED)
+        assert e.value.code == capi.ERR_OOM and "group" in str(e.value)
+    finally:
+        ctx.set_workspace_limit(0)
+    same(got, base)
+    same(dev, base)
+
+
+def test_unnormalised_profiles_repeat_on_int32(ctx):
+    """the groups longleft, ncols and long2 with every profile x 4.0.  range_verdict sees Q = (int)(4 * 4 * 5 * 1.0001 + 1) + 1 = 82, which
+    the 16-bit score launches hold up to m + n = 729 (test_gpu_assemble_batch.arith16_holds): long2 (400 + 400 columns) is refused at the
+    table's synchronisation and the call runs again on int32 -- the first run adds its two synchronisations."""
+    from test_gpu_assemble_batch import arith16_holds
+    groups, want = dc.wide()
+    mn = [a.shape[1] + b.shape[1] for g in groups for a in g for b in g if a is not b]
+    assert max(mn) == 800 and not arith16_holds(max(mn), 82) and arith16_holds(729, 82)
+    got = ctx.denovo_traces(list(groups), dc.SCORE, 0.5, dc.CALLED)
+    dc.check(got, want, groups)
+    assert ctx.last_call_stats()["host_syncs"] == 2 + dc.expected_syncs(want)
+    # without long2 every launch stays in range: no repeat
+    got = ctx.denovo_traces(list(groups[:2]), dc.SCORE, 0.5, dc.CALLED)
+    dc.check(got, want[:2], groups[:2])
+    assert ctx.last_call_stats()["host_syncs"] == dc.expected_syncs(want[:2])
+
+
+def test_empty_batch_and_bad_input(ctx):
+    from tracy_amd import capi
+    z = ctx.denovo_traces([], dc.SCORE)
+    assert len(z["rows"]) == 0 and len(z["forward"]) == 0
+    z = ctx.denovo_traces([[], []], dc.SCORE, device=True)
+    assert z["nrows"].tolist() == [0, 0] and z["rows"] == [[], []]
+    with pytest.raises(capi.TracyHipError) as e:
+        ctx.denovo_traces([[np.zeros((6, 0), np.float32), np.full((6, 5), 0.1, np.float32)]], dc.SCORE)
+    assert e.value.code == capi.ERR_ARG and "no columns" in str(e.value)
+    with pytest.raises(capi.TracyHipError) as e:
+        ctx.denovo_traces([list(dc.groups()[0])], dc.SCORE, match_fraction=float("nan"))
+    assert e.value.code == capi.ERR_ARG and "match_fraction" in str(e.value)
+    with pytest.raises(capi.TracyHipError) as e:
+        ctx.denovo_traces([list(dc.groups()[0])], (40000, -5, -10, -4))
+    assert e.value.code == capi.ERR_RANGE
+
+
+# ---- the command line -------------------------------------------------------------------------------------------------
+
+
+def run_cli(args, cwd, timeout=600):
+    return subprocess.run([CLI, "assemble"] + args, cwd=cwd, capture_output=True, text=True, timeout=timeout)
+
+
+WARNING = "is not matching to any of the other traces! Trace file will be excluded!"
+
+
+def test_cli_batch_matches_one_group_command(tmp_path):
+    from test_gpu_assemble_batch import tiled_traces
+    sizes = (3, 5, 2)
+    groups = []
+    for k, n in enumerate(sizes):
+        d = tmp_path / ("g%d" % k)
+        d.mkdir()
+        _, paths = tiled_traces(np.random.default_rng(300 + k), str(d), n, region_len=260 + 110 * n, tlen=260)
+        groups.append(paths)
+    (tmp_path / "junk").mkdir()
+    _, junk = tiled_traces(np.random.default_rng(19), str(tmp_path / "junk"), 2, region_len=900, tlen=260)
+    groups[1].insert(2, junk[0])  # a trace that matches nothing: the warning path
+    groups.append([junk[1], groups[2][0]])  # ... and a group of which it leaves one trace: skipped
+    single, batch = tmp_path / "single", tmp_path / "batch"
+    single.mkdir()
+    batch.mkdir()
+    opts = ["-i", "-a", "fastq", "-g", "-9", "-e", "-3"]
+    lines = [(p, str(batch / ("a%d" % k))) for k, paths in enumerate(groups) for p in paths]
+    lines = lines[0::2] + lines[1::2]  # the lines of the groups interleaved: a group is the lines of one outprefix, in manifest order
+    order = {k: [p for p, pre in lines if pre.endswith("a%d" % k)] for k in range(len(groups))}
+    warned = []
+    for k in range(len(groups)):
+        r = run_cli(opts + ["-o", str(single / ("a%d" % k))] + order[k], str(tmp_path))
+        assert (r.returncode == 0) == (k < 3), (k, r.stderr[-2000:])
+        warned.append([ln for ln in r.stderr.splitlines() if WARNING in ln])
+        assert ("At least 2 traces are required" in r.stderr) == (k == 3)
+    assert [len(w) for w in warned] == [0, 1, 0, 2]
+    man = tmp_path / "manifest.tsv"
+    with open(man, "w") as f:
+        f.write("# trace\treference\toutprefix\n")
+        for n, (p, pre) in enumerate(lines):
+            f.write("%s\t%s\t%s\n" % (p, "-" if n % 2 else "", pre))
+    r = run_cli(opts + ["--denovo", "--batch", str(man)], str(tmp_path))
+    assert r.returncode == 2, r.stderr[-2000:]
+    assert [ln for ln in r.stderr.splitlines() if WARNING in ln] == [ln for w in warned for ln in w]  # manifest order = group order here
+    assert "At least 2 traces are required for de novo assembly!" in r.stderr and "skipping %s" % (batch / "a3") in r.stderr
+    for k in range(len(groups)):
+        for ext in (".align.fa", ".json", ".vertical", ".cons.fq", ".cons.fa"):
+            s, b = single / ("a%d%s" % (k, ext)), batch / ("a%d%s" % (k, ext))
+            assert s.exists() == b.exists(), (k, ext)
+            if s.exists():
+                assert s.read_bytes() == b.read_bytes(), (k, ext)
+        assert (batch / ("a%d.json" % k)).exists() == (k < 3)
+    assert (batch / "a1.json").stat().st_size > 1000

@@ -55,7 +55,8 @@ class CallStats(C.Structure):
                 ("final_banded", C.c_uint32), ("final_repeated", C.c_uint32), ("allele_pruned", C.c_uint32 * 2),
                 ("allele_uncertified", C.c_uint32 * 2), ("allele_banded", C.c_uint32 * 3), ("allele_repeated", C.c_uint32 * 3),
                 ("allele_shared_prefix", C.c_uint32), ("cons_fixup_columns", C.c_uint32), ("cons_chunks", C.c_uint32),
-                ("asm_chunks", C.c_uint32), ("asm_steps", C.c_uint32)]
+                ("asm_chunks", C.c_uint32), ("asm_steps", C.c_uint32),
+                ("denovo_chunks", C.c_uint32), ("denovo_rounds", C.c_uint32), ("denovo_steps", C.c_uint32)]
 
 
 def library_path():
@@ -596,6 +597,121 @@ def _assemble_traces_async(self, job, prm, out, mem=MEM_HOST):
 
 
 Context.assemble_traces_async = _assemble_traces_async
+
+
+class DenovoJob(C.Structure):
+    _fields_ = [("ngroups", C.c_uint32), ("traces", SeqSet), ("group_first", C.POINTER(C.c_uint32)), ("match_fraction", C.c_float),
+                ("fraction_called", C.c_float)]
+
+
+class DenovoResult(C.Structure):
+    _fields_ = [("forward", C.c_void_p), ("partner", C.c_void_p), ("row", C.c_void_p), ("nrows", C.c_void_p), ("ncol", C.c_void_p),
+                ("rows", C.c_void_p), ("gapped", C.c_void_p), ("cons", C.c_void_p), ("qual", C.c_void_p), ("cons_len", C.c_void_p),
+                ("rows_offset", C.POINTER(C.c_uint64)), ("col_offset", C.POINTER(C.c_uint64))]
+
+
+class PreparedDenovo:
+    """host-buffer job / result structs of tracyhip_denovo_traces (everything they point to is kept alive by this object).
+    groups: one list of float32 [6][len] trace profiles (trimmed, forward) per group."""
+
+    _TRACE = (("forward", np.uint8), ("partner", np.uint32), ("row", np.uint32))
+    _GROUP = (("nrows", np.uint32), ("ncol", np.uint32), ("cons_len", np.uint32))
+
+    def __init__(self, groups, params, match_fraction=0.5, fraction_called=0.1):
+        ng = self.ng = len(groups)
+        pt = PackedSeqs([p for g in groups for p in g], SEQ_PROFILE)
+        nt = self.nt = pt.count
+        first = self.first = np.zeros(ng + 1, np.uint32)
+        first[1:] = np.cumsum([len(g) for g in groups], dtype=np.int64) if ng else 0
+        self.keep = [pt]
+        job = self.job = DenovoJob()
+        job.ngroups = ng
+        job.traces = pt.seqset()
+        job.group_first = first.ctypes.data_as(C.POINTER(C.c_uint32))
+        job.match_fraction = float(match_fraction)
+        job.fraction_called = float(fraction_called)
+        # capacities (tracy_hip.h): K * sum len row bytes, sum len columns
+        bound = np.zeros(max(ng, 1), np.uint64)
+        rowcap = np.zeros(max(ng, 1), np.uint64)
+        for g in range(ng):
+            bound[g] = int(pt.length[int(first[g]):int(first[g + 1])].sum())
+            rowcap[g] = len(groups[g]) * bound[g]
+        self.roff = np.zeros(max(ng, 1), np.uint64)
+        self.coff = np.zeros(max(ng, 1), np.uint64)
+        if ng:
+            self.roff[1:ng] = np.cumsum(rowcap[:ng])[:-1]
+            self.coff[1:ng] = np.cumsum(bound[:ng])[:-1]
+        res = self.res = {k: np.zeros(max(nt, 1), dt) for k, dt in self._TRACE}
+        res.update({k: np.zeros(max(ng, 1), dt) for k, dt in self._GROUP})
+        ctot = max(int(bound[:ng].sum()) if ng else 0, 1)
+        res.update(rows=np.zeros(max(int(rowcap[:ng].sum()) if ng else 0, 1), np.uint8), gapped=np.zeros(ctot, np.uint8),
+                   cons=np.zeros(ctot, np.uint8), qual=np.zeros(ctot, np.uint8))
+        out = self.out = DenovoResult()
+        for k, v in res.items():
+            setattr(out, k, v.ctypes.data)
+        out.rows_offset = self.roff.ctypes.data_as(C.POINTER(C.c_uint64))
+        out.col_offset = self.coff.ctypes.data_as(C.POINTER(C.c_uint64))
+        self.prm = Params(*params) if len(params) == 6 else Params(params[0], params[1], params[2], params[3], 1, 1)
+
+    def to_device(self):
+        """payload and result arrays as torch tensors on the current device"""
+        import torch
+        pt, = self.keep
+        d1 = torch.from_numpy(pt.data).cuda()
+        self.job.traces = pt.seqset(d1.data_ptr())
+        self.dres = {k: torch.zeros(v.nbytes, dtype=torch.uint8, device="cuda") for k, v in self.res.items()}
+        for k, v in self.dres.items():
+            setattr(self.out, k, v.data_ptr())
+        self.dkeep = [d1]
+        torch.cuda.synchronize()
+
+    def from_device(self):
+        for k, v in self.dres.items():
+            self.res[k] = v.cpu().numpy().view(self.res[k].dtype)
+
+    def results(self):
+        """per-trace and per-group arrays, and per group: rows (list of bytes, [] when nrows is 0), gapped, cons, qual (bytes)"""
+        res, ng, nt = self.res, self.ng, self.nt
+        out = {k: res[k][:nt].copy() for k, _ in self._TRACE}
+        out.update({k: res[k][:ng].copy() for k, _ in self._GROUP})
+        rows, gapped, cons, qual = [], [], [], []
+        for g in range(ng):
+            nr, nc, cl = int(res["nrows"][g]), int(res["ncol"][g]), int(res["cons_len"][g])
+            ro, co = int(self.roff[g]), int(self.coff[g])
+            rows.append([res["rows"][ro + i * nc:ro + (i + 1) * nc].tobytes() for i in range(nr)])
+            gapped.append(res["gapped"][co:co + (nc if nr else 0)].tobytes())
+            cons.append(res["cons"][co:co + (cl if nr else 0)].tobytes())
+            qual.append(res["qual"][co:co + (cl if nr else 0)].tobytes())
+        out.update(rows=rows, gapped=gapped, cons=cons, qual=qual)
+        return out
+
+
+def _denovo_traces(self, groups, params, match_fraction=0.5, fraction_called=0.1, device=False):
+    """tracyhip_denovo_traces: de novo `tracy assemble` (strands, overlap filter, UPGMA tree, consensus) for a batch of trace groups.
+    params: (match, mismatch, go, ge) with the command's AlignConfig<true,true>, or all six tracyhip_params fields.  device=True:
+    payloads and results in device memory (TRACYHIP_MEM_DEVICE), copied back afterwards."""
+    p = PreparedDenovo(groups, params, match_fraction, fraction_called)
+    if device:
+        import torch
+        p.to_device()
+        _check(lib().tracyhip_denovo_traces(self._h, C.byref(p.job), C.byref(p.prm), MEM_DEVICE, C.byref(p.out)))
+        torch.cuda.synchronize()
+        p.from_device()
+    else:
+        _check(lib().tracyhip_denovo_traces(self._h, C.byref(p.job), C.byref(p.prm), MEM_HOST, C.byref(p.out)))
+    return p.results()
+
+
+Context.denovo_traces = _denovo_traces
+
+
+def _denovo_traces_async(self, job, prm, out, mem=MEM_HOST):
+    """tracyhip_denovo_traces_async on prepared structs (PreparedDenovo: they, and everything they point to, must outlive
+    synchronize())"""
+    _check(lib().tracyhip_denovo_traces_async(self._h, C.byref(job), C.byref(prm), mem, C.byref(out)))
+
+
+Context.denovo_traces_async = _denovo_traces_async
 
 
 class RaggedSrc(C.Structure):

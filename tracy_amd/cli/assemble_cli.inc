@@ -2,6 +2,8 @@
 // anonymous namespace (uses stamp(), stem(), regular_nonempty(), load_trace(), Device, gpu_fail()).
 //
 //   tracy_amd_cli assemble [options] [-r reference.fa] trace1.ab1 trace2.ab1 ...
+//   tracy_amd_cli assemble [options] -r reference.fa --batch manifest.tsv
+//   tracy_amd_cli assemble [options] --denovo --batch manifest.tsv
 //
 // Reference-guided: every trace is scored in both strands against the reference (one device batch), the matching
 // traces join the alignment one by one, best first (each step one profile x profile Gotoh on the device).
@@ -15,7 +17,8 @@ struct AssembleConfig {  // assemble.h:12-30
   std::string outprefix = "out", format = "fasta", reference;
   std::vector<std::string> ab;
   int device = 0;
-  std::string batch;     // --batch: manifest of trace <TAB> reference <TAB> outprefix lines (reference-guided only)
+  std::string batch;     // --batch: manifest of trace <TAB> reference <TAB> outprefix lines
+  bool denovo = false;   // --denovo: the groups of the manifest are assembled de novo (no reference anywhere)
   uint32_t threads = 0;  // --threads: host threads of the --batch stages; 0 = every core this process may use
 };
 
@@ -29,7 +32,7 @@ int parse_assemble(int argc, char** argv, AssembleConfig& c) {
   static const std::map<std::string, char> longs = {{"help", '?'}, {"reference", 'r'}, {"pratio", 'p'}, {"trim", 't'}, {"fracmatch", 'f'},
                                                     {"gapopen", 'g'}, {"gapext", 'e'}, {"match", 'm'}, {"mismatch", 'n'}, {"called", 'd'},
                                                     {"outprefix", 'o'}, {"format", 'a'}, {"inccons", 'i'}, {"incref", 'j'}, {"device", 'D'},
-                                                    {"batch", 'B'}, {"threads", 'T'}};
+                                                    {"batch", 'B'}, {"threads", 'T'}, {"denovo", 'N'}};
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i], val;
     char opt = 0;
@@ -51,6 +54,7 @@ int parse_assemble(int argc, char** argv, AssembleConfig& c) {
     if (opt == '?') return 1;
     if (opt == 'i') { c.incCons = true; continue; }
     if (opt == 'j') { c.incRef = true; continue; }
+    if (opt == 'N' && a == "--denovo") { c.denovo = true; continue; }
     if (!has_val) {
       if (i + 1 >= argc) { std::cerr << "the required argument for option '" << a << "' is missing" << std::endl; return 1; }
       val = argv[++i];
@@ -214,7 +218,36 @@ void write_ref_guided_outputs(AssembleConfig const& c, std::vector<AsmTrace> con
   r << "]" << std::endl << "}" << std::endl;
 }
 
-// ---- --batch: many reference-guided assemblies, every chain on the device in one tracyhip_assemble_traces call per block -------------
+// .align.fa and .json of a de novo assembly (assemble.h:473-545): row i of the alignment is trace idxMap[seqidx[i]] of the input
+void write_denovo_outputs(AssembleConfig const& c, std::vector<AsmTrace> const& traces, std::vector<uint32_t> const& idxMap, std::vector<bool> const& fwd,
+                          std::vector<uint32_t> const& seqidx, CharAlign const& align, std::string const& gapped, std::string const& cs) {
+  {
+    std::ofstream v((c.outprefix + ".align.fa").c_str());
+    for (std::size_t i = 0; i < align.size(); ++i) {
+      v << ">" << stem(c.ab[idxMap[seqidx[i]]]) << (fwd[seqidx[i]] ? " (forward)" : " (reverse)") << std::endl;
+      v << align[i] << std::endl;
+    }
+    if (c.incCons) v << ">Consensus" << std::endl << gapped << std::endl;
+  }
+  std::ofstream r((c.outprefix + ".json").c_str());
+  r << "{" << std::endl;
+  r << "\"gapFreeConsensus\": \"" << cs << "\"," << std::endl;
+  r << "\"gappedConsensus\": \"" << gapped << "\"," << std::endl;
+  r << "\"msa\": " << std::endl << "[" << std::endl;
+  for (std::size_t i = 0; i < align.size(); ++i) {
+    if (i) r << ',' << std::endl;
+    alignedTraceByRow(r, align, (uint32_t)i, stem(c.ab[idxMap[seqidx[i]]]), fwd[seqidx[i]], false);
+  }
+  r << "]," << std::endl;
+  r << "\"gappedTraces\": " << std::endl << "[" << std::endl;
+  for (std::size_t i = 0; i < align.size(); ++i) {
+    if (i) r << ", ";
+    gapped_trace_json(r, traces[idxMap[seqidx[i]]], fwd[seqidx[i]], align[i], stem(c.ab[idxMap[seqidx[i]]]));
+  }
+  r << "]" << std::endl << "}" << std::endl;
+}
+
+// ---- --batch: many assemblies, every chain (-r) or tree (--denovo) on the device in one call per block ---------------------------------
 struct AsmGroup {  // the manifest lines of one outprefix, in manifest order
   AssembleConfig c;  // the command's options with this group's outprefix and trace files
   uint32_t ref = 0;  // index into the loaded references
@@ -222,6 +255,8 @@ struct AsmGroup {  // the manifest lines of one outprefix, in manifest order
   bool ok = false;
   std::vector<TraceScore> scoreIdx;
   std::vector<uint32_t> excluded;  // input indices of the traces that do not match
+  std::vector<uint32_t> idxMap, seqidx;  // --denovo: the traces that stay, and which of them each row of the alignment is
+  std::vector<bool> fwd;                 // ... their strands, indexed like idxMap
   CharAlign align;
   std::string gapped, cs, qstr;
 };
@@ -286,6 +321,63 @@ bool assemble_device(tracyhip_ctx* ctx, AssembleConfig const& c, detail::Profile
   return true;
 }
 
+// all trees of `gs` (every one loaded) through one device call; fills excluded / idxMap / fwd / seqidx / align / gapped / cs / qstr
+bool denovo_device(tracyhip_ctx* ctx, AssembleConfig const& c, std::vector<AsmGroup*> const& gs) {
+  const uint32_t ng = (uint32_t)gs.size();
+  if (ng == 0) return true;
+  detail::ProfilePack tp;
+  std::vector<uint32_t> first(ng + 1, 0);
+  std::vector<uint64_t> roff(ng), coff(ng);
+  uint64_t rtot = 0, ctot = 0;
+  for (uint32_t g = 0; g < ng; ++g) {
+    uint64_t bound = 0;  // capacities of tracy_hip.h: K * sum len row bytes, sum len columns
+    for (AsmTrace const& t : gs[g]->traces) { tp.add(t.prof); bound += t.prof.cols; }
+    first[g + 1] = (uint32_t)tp.off.size();
+    roff[g] = rtot;
+    coff[g] = ctot;
+    rtot += gs[g]->traces.size() * bound;
+    ctot += bound;
+  }
+  const uint32_t nt = first[ng];
+  tracyhip_denovo_job job{};
+  job.ngroups = ng;
+  job.traces = tp.set();
+  job.group_first = first.data();
+  job.match_fraction = c.matchFraction;
+  job.fraction_called = c.fractionCalled;
+  std::vector<uint8_t> fwd(nt), rows(std::max<uint64_t>(rtot, 1)), gapped(std::max<uint64_t>(ctot, 1)), cons(gapped.size()), qual(gapped.size());
+  std::vector<uint32_t> partner(nt), row(nt), nrows(ng), ncol(ng), clen(ng);
+  tracyhip_denovo_result res{fwd.data(), partner.data(), row.data(), nrows.data(), ncol.data(), rows.data(), gapped.data(),
+                             cons.data(), qual.data(), clen.data(), roff.data(), coff.data()};
+  tracyhip_params endfree{c.match, c.mismatch, c.gapopen, c.gapext, 1, 1};  // AlignConfig<true,true>
+  if (tracyhip_denovo_traces(ctx, &job, &endfree, TRACYHIP_MEM_HOST, &res) != TRACYHIP_OK) {
+    gpu_fail("assembly");
+    return false;
+  }
+  for (uint32_t g = 0; g < ng; ++g) {
+    AsmGroup& a = *gs[g];
+    const uint32_t K = first[g + 1] - first[g];
+    a.seqidx.assign(nrows[g], 0);
+    for (uint32_t i = 0; i < K; ++i) {
+      const uint32_t t = first[g] + i;
+      if (partner[t] == UINT32_MAX) { a.excluded.push_back(i); continue; }
+      if (row[t] != UINT32_MAX && row[t] < nrows[g]) a.seqidx[row[t]] = (uint32_t)a.idxMap.size();
+      a.idxMap.push_back(i);
+      a.fwd.push_back(fwd[t] != 0);
+    }
+    a.align.assign(nrows[g], std::string());
+    for (uint32_t r = 0; r < nrows[g]; ++r)
+      a.align[r].assign(reinterpret_cast<const char*>(rows.data() + roff[g] + (uint64_t)r * ncol[g]), ncol[g]);
+    if (nrows[g]) {
+      a.gapped.assign(reinterpret_cast<const char*>(gapped.data() + coff[g]), ncol[g]);
+      a.cs.assign(reinterpret_cast<const char*>(cons.data() + coff[g]), clen[g]);
+      a.qstr.assign(reinterpret_cast<const char*>(qual.data() + coff[g]), clen[g]);
+    }
+    for (AsmTrace& t : a.traces) t.prof = Profile();
+  }
+  return true;
+}
+
 int assemble_batch(AssembleConfig const& c, int argc, char** argv) {
   std::vector<AsmGroup> groups;
   std::vector<std::string> ref_paths;
@@ -305,6 +397,10 @@ int assemble_batch(AssembleConfig const& c, int argc, char** argv) {
       std::string trace, ref, prefix;
       if (!std::getline(ss, trace, '\t') || !std::getline(ss, ref, '\t') || !std::getline(ss, prefix, '\t') || trace.empty() || prefix.empty()) {
         std::cerr << "Malformed manifest line " << lineno << ": " << line << std::endl;
+        return 1;
+      }
+      if (c.denovo && !ref.empty() && ref != "-") {
+        std::cerr << "Manifest line " << lineno << ": --denovo takes no reference, the line names " << ref << std::endl;
         return 1;
       }
       if (ref.empty() || ref == "-") ref = c.reference;
@@ -338,6 +434,7 @@ int assemble_batch(AssembleConfig const& c, int argc, char** argv) {
   echo_command(argc, argv);
   detail::ProfilePack refs;
   for (std::string const& path : ref_paths) {
+    if (c.denovo) break;  // (one entry: the empty path every line stands for)
     std::string faname, seq;
     if (!loadSingleFasta(path, faname, seq)) return -1;
     if (seq.size() > kMaxSingleFasta) {
@@ -396,19 +493,28 @@ int assemble_batch(AssembleConfig const& c, int argc, char** argv) {
     std::vector<AsmGroup*> gs;
     for (uint32_t g = lo; g < hi; ++g)
       if (groups[g].ok) gs.push_back(&groups[g]);
-    const bool ok = assemble_device(dev.ctx, c, refs, gs);
+    const bool ok = c.denovo ? denovo_device(dev.ctx, c, gs) : assemble_device(dev.ctx, c, refs, gs);
     times.add("device_s", sw.seconds());
     return ok;
   };
   auto write = [&](uint32_t lo, uint32_t hi) {
     Stopwatch sw;
-    for (uint32_t g = lo; g < hi; ++g)  // (the warnings in manifest order)
+    for (uint32_t g = lo; g < hi; ++g) {  // (the warnings in manifest order)
       for (uint32_t i : groups[g].excluded)
-        std::cerr << "Warning: " << stem(groups[g].c.ab[i]) << " is not matching to the reference! Trace file will be excluded!" << std::endl;
+        std::cerr << "Warning: " << stem(groups[g].c.ab[i]) << (c.denovo ? " is not matching to any of the other traces!" : " is not matching to the reference!")
+                  << " Trace file will be excluded!" << std::endl;
+      if (c.denovo && groups[g].ok && groups[g].align.empty()) {  // (what ends the one-group command, assemble.h:459-462)
+        std::cerr << "At least 2 traces are required for de novo assembly!" << std::endl;
+        std::cerr << "skipping " << groups[g].c.outprefix << std::endl;
+        groups[g].ok = false;
+        ++failed;
+      }
+    }
     for_each_index(hi - lo, nthreads, [&](uint32_t i) {
       AsmGroup& g = groups[lo + i];
       if (g.ok) {
-        if (!g.scoreIdx.empty()) write_ref_guided_outputs(g.c, g.traces, g.scoreIdx, g.align, g.gapped, g.cs);
+        if (c.denovo) write_denovo_outputs(g.c, g.traces, g.idxMap, g.fwd, g.seqidx, g.align, g.gapped, g.cs);
+        else if (!g.scoreIdx.empty()) write_ref_guided_outputs(g.c, g.traces, g.scoreIdx, g.align, g.gapped, g.cs);
         write_assembly_outputs(g.c, g.align, g.gapped, g.cs, g.qstr);
       }
       AsmGroup done;
@@ -428,6 +534,7 @@ int assemble_main(int argc, char** argv) {
   if (parse_assemble(argc, argv, c)) {
     std::cout << "Usage: tracy " << argv[0] << " [OPTIONS] trace1.ab1 trace2.ab1 ..." << std::endl;
     std::cout << "       tracy " << argv[0] << " [OPTIONS] -r reference.fa --batch manifest.tsv" << std::endl;
+    std::cout << "       tracy " << argv[0] << " [OPTIONS] --denovo --batch manifest.tsv" << std::endl;
     std::cout << "Generic options:\n"
                  "  -? [ --help ]                    show help message\n"
                  "  -r [ --reference ] arg           reference-guided assembly (optional)\n"
@@ -449,8 +556,18 @@ int assemble_main(int argc, char** argv) {
                  "  --batch arg                      manifest: trace<TAB>reference<TAB>outprefix per line; the lines of one outprefix\n"
                  "                                   are one assembly (all of them on the GPU in one call; requires --reference,\n"
                  "                                   which an empty or '-' reference field stands for)\n"
+                 "  --denovo                         with --batch: every assembly of the manifest is de novo (all of them on the GPU in\n"
+                 "                                   one call; the reference field of every line is empty or '-', no --reference)\n"
                  "  --threads arg (=0)               host threads of the --batch stages (0 = all usable cores)\n\n";
     return -1;
+  }
+  if (c.denovo && c.batch.empty()) {
+    std::cerr << "--denovo needs --batch: one de novo assembly per command is the default without -r" << std::endl;
+    return 1;
+  }
+  if (c.denovo && c.hasReference) {
+    std::cerr << "--denovo takes no reference (-r): a reference-guided batch is -r with --batch" << std::endl;
+    return 1;
   }
   for (auto const& p : c.ab)
     if (!regular_nonempty(p)) {
@@ -464,7 +581,7 @@ int assemble_main(int argc, char** argv) {
   if (c.matchFraction < 0) c.matchFraction = 0;
   else if (c.matchFraction > 1) c.matchFraction = 1;
   if (!c.batch.empty()) {
-    if (!c.hasReference) {
+    if (!c.hasReference && !c.denovo) {
       std::cerr << "--batch needs a reference (-r): only reference-guided assemblies have a batch mode, de novo assembly runs one per command" << std::endl;
       return 1;
     }
@@ -624,30 +741,7 @@ int assemble_main(int argc, char** argv) {
     std::vector<uint32_t> seqidx;
     if (msa(dev.ctx, endfree, seqProfiles, align, seqidx) != TRACYHIP_OK) return gpu_fail("msa"), -1;
     consensus(c.fractionCalled, align, gapped, cs, qstr, false);
-    {
-      std::ofstream v((c.outprefix + ".align.fa").c_str());
-      for (std::size_t i = 0; i < align.size(); ++i) {
-        v << ">" << stem(c.ab[idxMap[seqidx[i]]]) << (fwd[seqidx[i]] ? " (forward)" : " (reverse)") << std::endl;
-        v << align[i] << std::endl;
-      }
-      if (c.incCons) v << ">Consensus" << std::endl << gapped << std::endl;
-    }
-    std::ofstream r((c.outprefix + ".json").c_str());
-    r << "{" << std::endl;
-    r << "\"gapFreeConsensus\": \"" << cs << "\"," << std::endl;
-    r << "\"gappedConsensus\": \"" << gapped << "\"," << std::endl;
-    r << "\"msa\": " << std::endl << "[" << std::endl;
-    for (std::size_t i = 0; i < align.size(); ++i) {
-      if (i) r << ',' << std::endl;
-      alignedTraceByRow(r, align, (uint32_t)i, stem(c.ab[idxMap[seqidx[i]]]), fwd[seqidx[i]], false);
-    }
-    r << "]," << std::endl;
-    r << "\"gappedTraces\": " << std::endl << "[" << std::endl;
-    for (std::size_t i = 0; i < align.size(); ++i) {
-      if (i) r << ", ";
-      gapped_trace_json(r, traces[idxMap[seqidx[i]]], fwd[seqidx[i]], align[i], stem(c.ab[idxMap[seqidx[i]]]));
-    }
-    r << "]" << std::endl << "}" << std::endl;
+    write_denovo_outputs(c, traces, idxMap, fwd, seqidx, align, gapped, cs);
   }
   write_assembly_outputs(c, align, gapped, cs, qstr);
   std::cout << stamp() << "Done." << std::endl;

@@ -6,7 +6,7 @@
 // group of a chunk that has more than k matching traces is one batch -- msa_profile of the rows so far (written at the end of step
 // k - 1), gotoh(trace_k, that profile) through the traceback kernels of tracyhip_gotoh_align (fused walk), msa_merge with the trace
 // as row 0.  Step 0 is gotoh(best, reference): both sides of its merge are input profiles, shown as their _profileConsChar rows.
-// msa_consensus closes a chunk.
+// msa_consensus closes a chunk.  (The three row-block kernels are msa_batch.hip's, shared with denovo.hip.)
 //
 // The columns of step k are the op count of step k - 1, which only the device knows: the host reads the op counts back once per step
 // and builds the next step's descriptors from them.  Workspaces are sized from the bound  columns <= n_ref + sum of the trace lengths
@@ -27,67 +27,6 @@
 using namespace tracyhip;
 
 namespace {
-
-struct AsmDevWave {
-  __device__ __forceinline__ uint32_t lane() const { return threadIdx.x; }
-  __device__ __forceinline__ uint64_t ballot(bool p) const { return __ballot(p); }
-};
-
-struct AsmStep {       // one group at one chain step
-  MsaSide left, right; // the new trace (always a profile); the reference profile (step 0) or the rows so far
-  uint64_t ops_off;    // the group's op string in the ops buffer
-  uint32_t slot;       // its entry of ops_len (PairDesc::out)
-  uint32_t cap;        // left.c + right.c: more ops than that cannot be (nothing is written otherwise)
-  uint8_t* dst;        // (left.n + right.n) rows x ops_len columns
-  int32_t* span;       // 2 per row of dst
-  float* prof;         // msa_profile of dst, 6 x ops_len -- or null: this was the group's last step
-  uint8_t* colclass;   // classes of its columns
-};
-
-struct AsmFinal {      // one finished group
-  const uint8_t* rows;
-  const int32_t* span;
-  uint32_t rows_used;  // the rows consensus() looks at
-  uint32_t slot;
-  int32_t cov_threshold;
-  uint32_t cap;
-  uint8_t *gapped, *cons, *qual;
-  uint32_t* cons_len;
-};
-
-// one wave per (group, row of the merged block)
-__global__ __launch_bounds__(64) void msa_merge_kernel(const AsmStep* __restrict__ steps, const uint8_t* __restrict__ ops, const uint32_t* __restrict__ ops_len) {
-  const AsmStep s = steps[blockIdx.x];
-  const uint32_t r = blockIdx.y;
-  if (r >= s.left.n + s.right.n) return;
-  const uint32_t L = ops_len[s.slot];
-  if (L > s.cap) return;
-  AsmDevWave w;
-  const bool left = r < s.left.n;
-  msa_merge_row_wave(w, ops + s.ops_off, L, left ? s.left : s.right, left ? r : r - s.left.n, left, s.dst + (uint64_t)r * L, s.span + 2 * r);
-}
-
-// one wave per (group, 64 columns); the grid covers the longest capacity, waves past a group's columns leave
-__global__ __launch_bounds__(64) void msa_profile_kernel(const AsmStep* __restrict__ steps, const uint32_t* __restrict__ ops_len) {
-  const AsmStep s = steps[blockIdx.x];
-  if (!s.prof) return;
-  const uint32_t L = ops_len[s.slot];
-  const uint32_t b = blockIdx.y * 64u;
-  if (b >= L || L > s.cap) return;
-  AsmDevWave w;
-  msa_profile_wave(w, s.dst, s.left.n + s.right.n, L, s.span, b, s.prof);
-  const uint32_t j = b + threadIdx.x;
-  if (j < L) s.colclass[j] = (uint8_t)column_class(s.prof, L, j);  // (this lane's own six stores)
-}
-
-// one wave per finished group
-__global__ __launch_bounds__(64) void msa_consensus_kernel(const AsmFinal* __restrict__ fin, const uint32_t* __restrict__ ops_len) {
-  const AsmFinal f = fin[blockIdx.x];
-  const uint32_t L = ops_len[f.slot];
-  if (L > f.cap) return;
-  AsmDevWave w;
-  msa_consensus_wave(w, f.rows, f.rows_used, L, f.span, f.cov_threshold, f.gapped, f.cons, f.qual, f.cons_len);
-}
 
 int assemble_validate(const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem, const tracyhip_assemble_result* out) {
   if (mem != TRACYHIP_MEM_HOST && mem != TRACYHIP_MEM_DEVICE) return set_error(TRACYHIP_ERR_ARG, "bad mem kind");
@@ -420,10 +359,8 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
       a.colcode = !screen ? nullptr : k == 0 ? d_refclass : d_pclass;
       if ((rc = prof_trace_runs(ctx, a, hd, dd, k_step.data(), 0, na, d_ops, d_off, d_len))) return rc;
       if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 0))) return trc;
-      hipLaunchKernelGGL(msa_merge_kernel, dim3(na, k + 2), dim3(64), 0, st, (const AsmStep*)d_step, (const uint8_t*)d_ops, (const uint32_t*)d_len);
-      if (any_prof)
-        hipLaunchKernelGGL(msa_profile_kernel, dim3(na, (uint32_t)((max_cap + 63) / 64)), dim3(64), 0, st, (const AsmStep*)d_step, (const uint32_t*)d_len);
-      HIP_TRY(hipGetLastError());
+      HIP_TRY(launch_msa_merge(d_step, na, k + 2, d_ops, d_len, st));
+      if (any_prof) HIP_TRY(launch_msa_profile(d_step, na, max_cap, d_len, st));
       if ((trc = timing_end(ctx))) return trc;
       // the op counts: the columns of the next step (and the group's ncol)
       HIP_TRY(hipMemcpyAsync(h_len, d_len, sizeof(uint32_t) * (size_t)ng, hipMemcpyDeviceToHost, st));
@@ -458,8 +395,7 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
     if (nf) {
       HIP_TRY(hipMemcpyAsync(d_fin, h_fin, sizeof(AsmFinal) * nf, hipMemcpyHostToDevice, st));
       if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 0))) return trc;
-      hipLaunchKernelGGL(msa_consensus_kernel, dim3(nf), dim3(64), 0, st, (const AsmFinal*)d_fin, (const uint32_t*)d_len);
-      HIP_TRY(hipGetLastError());
+      HIP_TRY(launch_msa_consensus(d_fin, nf, d_len, st));
       if ((trc = timing_end(ctx))) return trc;
       // (h_fin is filled again at the end of the next chunk that has groups to finish: behind the synchronisations of its steps)
     }

@@ -62,6 +62,19 @@ TR_HD void msa_span_wave(W& w, const uint8_t* row, uint32_t ncol, int32_t* span)
   if (lane == 0) { span[0] = first; span[1] = last; }
 }
 
+// numAligned of the overlap test of de novo assembly (assemble.h:436-439): the columns of an alignment that hold a character on both
+// sides, which are the 's' ops of its op string (either order).  Every lane returns the count.
+template <class W>
+TR_HD uint32_t msa_count_aligned_wave(W& w, const uint8_t* ops, uint32_t L) {
+  const uint32_t lane = w.lane();
+  uint32_t n = 0;
+  for (uint32_t b = 0; b < L; b += 64) {
+    const uint32_t j = b + lane;
+    n += msa_popc(w.ballot(j < L && ops[j] == 's'));
+  }
+  return n;
+}
+
 // One row of a merged block.  ops: the op string in the reference's PUSH order (the end of the alignment first, as
 // tracyhip_gotoh_align writes it), L of them; column j of the result belongs to ops[L - 1 - j].  The row comes from the LEFT block
 // (column taken unless the op is 'h') or the right one (unless 'v'); a skipped column is '-'.  The source column is the number of

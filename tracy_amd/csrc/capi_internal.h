@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/tracy_hip.h"
+#include "assemble_wave.h"
 #include "dp_kernels.h"
 #include "band16_launch.h"
 #include "front.h"
@@ -136,8 +137,25 @@ enum CtxDev : int {
   AB_PCLASS,    // its column classes
   AB_STEP,      // AsmStep + AsmFinal per group, uploaded per step
   AB_PAY,       // results staged for a host caller
+  // ---- tracyhip_denovo_traces (denovo.hip denovo_run) ----
+  // a context runs one call at a time, and neither call keeps anything in these between calls: the roles that match share a slot
+  DN_PROF = AB_TR,      // [forward | revcomp] of every trace, then the node profiles: both sides of every dynamic program
+  DN_SEQS = AB_SEQS,    // ProfSeq list of both strands, uploaded
+  DN_CLASS = AB_CLASS,  // "row 4 is all zero" byte per profile, read back
+  DN_COLCLASS = AB_PCLASS,  // column classes, indexed like DN_PROF: the inputs by prof_classify_kernel, the nodes by msa_profile_kernel
+  DN_TABLE = AB_SC2,    // the strand table T[i][j][oi][oj] of every group, read back
+  DN_OPS = AB_OPS,      // traceback strings: one per trace in an overlap round, one per node at a tree height
+  DN_OFF = AB_OFF,      // their offsets: uploaded once for the rounds, once per chunk for the tree
+  DN_LEN = AB_LEN,      // their lengths, read back per round / height
+  DN_ROWS = AB_W0,      // row blocks of the nodes below the roots (the roots write into the caller's rows)
+  DN_SPAN = AB_SPAN,    // first / last column of every row of every node
+  DN_STEP = AB_STEP,    // AsmStep per node of a height + AsmFinal per group, uploaded per height / chunk
+  DN_PAY = AB_PAY,      // results staged for a host caller
+  DN_CNT,       // 's' ops of every overlap alignment of a round: written by denovo_count_kernel, read back per round (a slot of its own,
+                // and the last enumerator before DB_COUNT: the aliases above do not advance the count)
   DB_COUNT
 };
+static_assert(DN_CNT + 1 == DB_COUNT && DN_PAY < DB_COUNT, "an alias does not advance the count: every slot of its own comes after the aliases");
 // pinned host buffers of a context: tracyhip_ctx::pin[]
 enum CtxPin : int {
   PB_DESC,      // descriptor uploads of run_dp and the batch calls
@@ -430,6 +448,37 @@ int prof_score_runs(tracyhip_ctx* ctx, const tracyhip_params* prm, bool wide, co
 // no_fused_walk a walk launch follows each sweep; timed as TRACYHIP_TIMER_TRACE / TRACYHIP_TIMER_WALK
 int prof_trace_runs(tracyhip_ctx* ctx, const DpArgs& args, const PairDesc* hd, const PairDesc* dd, const int* k, uint32_t lo, uint32_t hi,
                     uint8_t* ops, const uint64_t* ops_off, uint32_t* ops_len);
+
+// ---- row blocks of `tracy assemble` (msa_batch.hip over assemble_wave.h): what assemble_run and denovo_run share ----
+struct MsaDevWave {    // the wave of assemble_wave.h on the device: one workgroup of 64 threads
+  __device__ __forceinline__ uint32_t lane() const { return threadIdx.x; }
+  __device__ __forceinline__ uint64_t ballot(bool p) const { return __ballot(p); }
+};
+struct AsmStep {       // one merge: a chain step of a group (assemble.hip) or a tree node (denovo.hip)
+  MsaSide left, right; // the rows above / below in the merged block: an input profile (rows == null) or a block of rows
+  uint64_t ops_off;    // the merge's op string in the ops buffer
+  uint32_t slot;       // its entry of ops_len (PairDesc::out)
+  uint32_t cap;        // left.c + right.c: more ops than that cannot be (nothing is written otherwise)
+  uint8_t* dst;        // (left.n + right.n) rows x ops_len columns
+  int32_t* span;       // 2 per row of dst
+  float* prof;         // msa_profile of dst, 6 x ops_len -- or null: nothing aligns against this block
+  uint8_t* colclass;   // classes of its columns
+};
+struct AsmFinal {      // one finished group
+  const uint8_t* rows;
+  const int32_t* span;
+  uint32_t rows_used;  // the rows consensus() looks at
+  uint32_t slot;
+  int32_t cov_threshold;
+  uint32_t cap;
+  uint8_t *gapped, *cons, *qual;
+  uint32_t* cons_len;
+};
+// steps / fin: device arrays of n entries; ops_len is indexed by their slots.  One wave per (step, row of the merged block) with
+// max_rows the largest left.n + right.n; one wave per (step, 64 columns) with max_cap the largest cap; one wave per finished group.
+hipError_t launch_msa_merge(const AsmStep* steps, uint32_t n, uint32_t max_rows, const uint8_t* ops, const uint32_t* ops_len, hipStream_t st);
+hipError_t launch_msa_profile(const AsmStep* steps, uint32_t n, uint64_t max_cap, const uint32_t* ops_len, hipStream_t st);
+hipError_t launch_msa_consensus(const AsmFinal* fin, uint32_t n, const uint32_t* ops_len, hipStream_t st);
 
 // ---- band kernels (band16.h): Gotoh on a diagonal band, four pairs per wave ----
 // a batch for them: descriptors whose a1_off / a1_stride point into the substitution tables d_qp (build_b16_tables), a2_off into
