@@ -22,6 +22,8 @@
  *   generateSecondaryDecomposed            decompose.h:378-410              tracyhip_secondary_decomposed
  *   allelicFraction                        decompose.h:412-621              tracyhip_allelic_fraction
  *   trimReferenceSlice                     fmindex.h:429-463                tracyhip_trim_reference_slice
+ *   callVariants / insertVariant           variants.h:34-126                tracyhip_call_variants
+ *   indigo() variant section               indigo.h:397-423, 442-443        tracyhip_decompose_variants
  *   getReferenceSlice (indexed genome)     fmindex.h:236-326                tracyhip_seed_traces
  *   consensus() hot section                consensus.h:501-577              tracyhip_consensus_traces
  *   basecall + estimateQualities           abif.h:408-511, 164-253          tracyhip_basecall_traces
@@ -165,6 +167,10 @@ typedef struct {
   uint32_t denovo_chunks;        /* tracyhip_denovo_traces: chunks of groups the batch was cut into to fit the workspace limit */
   uint32_t denovo_rounds;        /* ... overlap rounds launched, summed over the chunks (a chunk runs as many as its slowest trace tries partners) */
   uint32_t denovo_steps;         /* ... tree heights launched, summed over the chunks (a chunk runs as many as its tallest tree has) */
+  uint32_t var_traces;           /* tracyhip_decompose_variants: traces whose variants were called (status 0) */
+  uint32_t var_realigned;        /* ... of which on the reverse strand: both alleles re-aligned as reverse complements (indigo.h:408-422) */
+  uint32_t var_truncated;        /* ... traces whose events did not fit max_variants / max_text (var_flags bit 0) */
+  uint32_t var_chunks;           /* ... chunks of traces the batch was cut into to fit the workspace limit */
 } tracyhip_call_stats;
 int tracyhip_last_call_stats(tracyhip_ctx* ctx, tracyhip_call_stats* out);
 const char* tracyhip_last_error(void);
@@ -383,6 +389,75 @@ typedef struct {
 
 int tracyhip_decompose_traces(tracyhip_ctx* ctx, const tracyhip_decompose_job* job, const tracyhip_params* prm, int mem,
                               const tracyhip_decompose_result* out);
+
+/* ---- variant calling of `tracy decompose -v` (indigo.h:397-443 over variants.h:34-126) -----------------------------------
+ * One variant of a trace: what the reference's Variant holds, with the basecall it sits on.  ref is the ref_len bytes at
+ * text + t * max_text + ref_off, alt the alt_len bytes at ... + alt_off (no terminators; offsets into the trace's OWN text region).
+ * gt: 1 = seen on one allele ("0/1"), 2 = the same (pos, ref, alt) on both ("1/1").  call_index = variantCallIndex (variants.h:205):
+ * forward traces trim_left + basenum - 1, reverse traces bc_len - (trim_right + basenum) -- the index of estQual / bcPos the writers read. */
+typedef struct {
+  int32_t pos;
+  int32_t basenum;
+  int32_t gt;
+  uint32_t call_index;
+  uint32_t ref_off;
+  uint32_t ref_len;
+  uint32_t alt_off;
+  uint32_t alt_len;
+} tracyhip_variant;
+
+/* callVariants (variants.h:56-126) of both allele alignments of every trace, insertVariant (:34-53) across the two, the sort of
+ * indigo.h:442 and variantCallIndex.  rows0 / rows1 / rows_offset / rows_len describe 2 * ntraces two-row alignments as
+ * tracyhip_trim_reference_slice takes them (row 0 the allele, row 1 its reference slice); alignments 2t and 2t + 1 are allele 1 and
+ * allele 2 of trace t.  HOST arrays: pos[2 * ntraces] (rs.pos of each alignment), forward[ntraces], bc_len[ntraces]
+ * (bc.primary.size()).  max_variants in 1 .. 1024 (TRACYHIP_ERR_RANGE beyond), max_text in bytes.
+ * Results where `mem` says: trace t's records at var + t * max_variants, its text at text + t * max_text, var_n[t] records.
+ *   - Order: by (pos, basenum); ties -- which Variant::operator< leaves open -- allele 1's events before allele 2's, each allele in
+ *     the order callVariants pushes them.  That is what std::stable_sort gives the host writers.
+ *   - Text: record r's ref then its alt, records back to back from offset 0.
+ *   - A trace whose events do not fit (more than max_variants on either allele or after the merge, or more than max_text bytes of
+ *     ref + alt) returns var_n[t] = 0 and var_flags[t] = 1 (0 otherwise); the call still returns TRACYHIP_OK.
+ *   - Of var and text only the first var_n[t] records of a trace and the text bytes they point to are ever written, in both kinds of
+ *     `mem`: with host arrays everything else in the caller's arrays keeps the bytes it had. */
+int tracyhip_call_variants(tracyhip_ctx* ctx, uint32_t ntraces, const uint8_t* rows0, const uint8_t* rows1, const uint64_t* rows_offset,
+                           const uint32_t* rows_len, const int32_t* pos, const uint8_t* forward, const uint32_t* bc_len, uint32_t trim_left,
+                           uint32_t trim_right, uint32_t max_variants, uint32_t max_text, int mem, tracyhip_variant* var, uint8_t* text,
+                           uint32_t* var_n, uint32_t* var_flags);
+
+/* the four result arrays of the two calls, with their capacities per trace */
+typedef struct {
+  tracyhip_variant* var;   /* [ntraces * max_variants] */
+  uint8_t* text;           /* [ntraces * max_text] */
+  uint32_t* var_n;         /* [ntraces] */
+  uint32_t* var_flags;     /* [ntraces] bit 0: truncated */
+  uint32_t max_variants;   /* 1 .. 1024 */
+  uint32_t max_text;       /* >= 2 */
+} tracyhip_variants_result;
+
+/* indigo.h:397-423, 442-443 for a batch: the variant list of every trace of a tracyhip_decompose_traces call.  job: the job of that
+ * call; res: the result it filled (same `mem`; bp, scores, tables and fractions are not read); slice_pos: HOST array [ntraces], rs.pos
+ * of each trace's reference window (0 for a single FASTA); prm: the scoring of that call (hfree / vfree ignored).
+ *   - status[t] != 0: var_n[t] = 0.
+ *   - forward traces: the rows of allele alignment k = 0, 1 from ops[k], the trimmed primary / secdecomp and
+ *     oriented reference[slice_begin[k] .. + slice_len[k]); pos = slice_pos[t] + ref_pos[k][t].
+ *   - reverse traces (indigo.h:408-422): reverseComplement of the trimmed allele and of its slice (letters outside ACGTNacgtn keep the
+ *     byte of their OUTPUT position, as the reference's table leaves them), gotoh(rc allele, rc slice) semi-global with free horizontal
+ *     ends through the internal path of tracyhip_gotoh_align -- all reverse traces of a chunk as one batch of pairs --, then rows and
+ *     scan with the same pos.
+ * Results as tracyhip_call_variants describes them.  The batch is cut into chunks of consecutive traces whose rows, reverse
+ * complements and op strings fit the workspace limit (tracyhip_set_workspace_limit); the traceback planes of a chunk's
+ * re-alignments are planned under the same limit by the DP driver, on top of that.  Host synchronisations
+ * (tracyhip_call_stats::host_syncs):
+ *     the number of chunks BEFORE THE LAST that hold a usable reverse trace   (such a chunk is waited for behind its scan: the
+ *                                                     traceback batch of the next one reuses the context's descriptor staging)
+ *   + TRACYHIP_MEM_DEVICE: 1 (one read of forward / status / slice_* / ref_pos / ops_len, from which the host plans) + 1 (the end)
+ *     TRACYHIP_MEM_HOST:   1 (counts, flags and where the packed records begin) + 1 (the packed records and text; not when no trace
+ *                          has a variant) -- the plan is read from the caller's arrays
+ * -- two for a call of one chunk, at most one more per further chunk, whatever ntraces is. */
+int tracyhip_decompose_variants_validate(const tracyhip_decompose_job* job, const tracyhip_decompose_result* res, const uint32_t* slice_pos,
+                                         const tracyhip_params* prm, int mem, const tracyhip_variants_result* out);
+int tracyhip_decompose_variants(tracyhip_ctx* ctx, const tracyhip_decompose_job* job, const tracyhip_decompose_result* res,
+                                const uint32_t* slice_pos, const tracyhip_params* prm, int mem, const tracyhip_variants_result* out);
 
 /* ---- k-mer seeding in an indexed genome (getReferenceSlice, fmindex.h:236-326) on the device ----------------------------
  * The index is tracy_amd/host/seed.hpp's GenomeIndex (tracyhost_genome_view gives its arrays): every k-mer over ACGT of the text is
@@ -704,6 +779,9 @@ int tracyhip_assemble_traces_async(tracyhip_ctx* ctx, const tracyhip_assemble_jo
                                    const tracyhip_assemble_result* out);
 int tracyhip_denovo_traces_async(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip_params* prm, int mem,
                                  const tracyhip_denovo_result* out);
+/* (slice_pos is copied too: it need not outlive the call) */
+int tracyhip_decompose_variants_async(tracyhip_ctx* ctx, const tracyhip_decompose_job* job, const tracyhip_decompose_result* res,
+                                      const uint32_t* slice_pos, const tracyhip_params* prm, int mem, const tracyhip_variants_result* out);
 
 /* ---- device groups: the GPUs of one node behind one handle (north star: "batches of traces shard embarrassingly across
  * the 8 GPUs of one node") ------------------------------------------------------------------------------------------

@@ -59,6 +59,14 @@ class CallStats(C.Structure):
                 ("denovo_chunks", C.c_uint32), ("denovo_rounds", C.c_uint32), ("denovo_steps", C.c_uint32)]
 
 
+class CallStatsVariants(CallStats):
+    """THE mirror of tracyhip_call_stats, and the only one to hand to tracyhip_last_call_stats: CallStats (the counters through
+    denovo_steps, kept as it was: tests pin its tail) with the four counters of tracyhip_decompose_variants appended -- ctypes lays a
+    subclass's fields out behind its base's, as the C struct grew.  A bare CallStats is 16 bytes SHORTER than what the library writes:
+    passing one to tracyhip_last_call_stats is an out-of-bounds write.  Context.last_call_stats uses this class."""
+    _fields_ = [("var_traces", C.c_uint32), ("var_realigned", C.c_uint32), ("var_truncated", C.c_uint32), ("var_chunks", C.c_uint32)]
+
+
 def library_path():
     return os.path.join(_HERE, "lib", "libtracy_hip.so")
 
@@ -171,10 +179,10 @@ class Context:
 
     def last_call_stats(self):
         """tiers the traces of the last align_traces / decompose_traces call took (tracyhip_last_call_stats)"""
-        st = CallStats()
+        st = CallStatsVariants()
         _check(lib().tracyhip_last_call_stats(self._h, C.byref(st)))
         out = {}
-        for name, ty in CallStats._fields_:
+        for name, ty in CallStats._fields_ + CallStatsVariants._fields_:
             v = getattr(st, name)
             out[name] = list(v) if hasattr(v, "__len__") else int(v)
         return out
@@ -982,6 +990,12 @@ class DecomposeResult(C.Structure):
                 ("ops_offset", C.POINTER(C.c_uint64) * 3), ("ops_len", C.c_void_p * 3)]
 
 
+class DecomposeOutcome(dict):
+    """what Context.decompose_traces returns: the result arrays by name; `call` keeps the job / result structs of the call alive for
+    Context.decompose_variants"""
+    call = None
+
+
 def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_right=50, maxindel=1000, madc=5, oriented=None,
                       ref_profiles=None, exact_scores=True, peaks_only=False, device_bc=None):
     """tracyhip_decompose_traces with host buffers; hbc: HostBaseCalls (primary/secondary rewritten in place);
@@ -990,6 +1004,7 @@ def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_righ
     stand (profiles and hbc may be None), references and results live on the device too (TRACYHIP_MEM_DEVICE) and are copied back."""
     dev = device_bc is not None
     mirrors = []
+    pp = prp = d_refs = None
     if dev:
         import torch
 
@@ -1084,6 +1099,10 @@ def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_righ
         res["btr%d" % k] = [ops[int(off[i]):int(off[i]) + int(olen[i])].tobytes() for i in range(nt)]
     res["dcp"] = [[(int(res["dcp_indel"][i * cap + j]), int(res["dcp_err"][i * cap + j])) for j in range(res["dstatus"][i].dcp_n)]
                   for i in range(nt)]
+    res = DecomposeOutcome(res)
+    # what Context.decompose_variants needs of this call: the structs and everything they point to
+    res.call = dict(job=job, out=out, prm=prm, mem=MEM_DEVICE if dev else MEM_HOST, nt=nt,
+                    keep=(pr, pp, prp, d_refs, hbc, doff, keep, oriented, mirrors, device_bc, dict(res)))
     if dev:  # the decomposed basecalls as the call left them in the device tensors
         rows = device_bc.results(fill_deferred=False)
         res["primary"] = [r["primary"] for r in rows]
@@ -1098,6 +1117,117 @@ def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_righ
 
 Context.decompose_traces = _decompose_traces
 Context.align_banded = _align_banded
+
+
+# ---- variant calling of `tracy decompose -v` (tracyhip_call_variants / tracyhip_decompose_variants) ------------------------------
+class Variant(C.Structure):
+    _fields_ = [("pos", C.c_int32), ("basenum", C.c_int32), ("gt", C.c_int32), ("call_index", C.c_uint32), ("ref_off", C.c_uint32),
+                ("ref_len", C.c_uint32), ("alt_off", C.c_uint32), ("alt_len", C.c_uint32)]
+
+
+VARIANT_DTYPE = np.dtype([(n, "<i4" if t is C.c_int32 else "<u4") for n, t in Variant._fields_])
+
+
+class VariantsResult(C.Structure):
+    _fields_ = [("var", C.c_void_p), ("text", C.c_void_p), ("var_n", C.c_void_p), ("var_flags", C.c_void_p),
+                ("max_variants", C.c_uint32), ("max_text", C.c_uint32)]
+
+
+class VariantBuffers:
+    """the four result arrays of the two variant calls for nt traces, on the host or (device=True) in torch tensors, filled with `fill` so
+    that what a call leaves alone can be told; lists() decodes them"""
+
+    def __init__(self, nt, max_variants, max_text, device=False, fill=0):
+        self.nt, self.max_variants, self.max_text, self.device = nt, max_variants, max_text, device
+        shapes = (("var", max(nt, 1) * max_variants * VARIANT_DTYPE.itemsize), ("text", max(nt, 1) * max_text), ("var_n", max(nt, 1) * 4),
+                  ("var_flags", max(nt, 1) * 4))
+        if device:
+            import torch
+            self.t = {k: torch.full((n,), fill, dtype=torch.uint8, device="cuda") for k, n in shapes}
+            torch.cuda.synchronize()
+            ptr = {k: v.data_ptr() for k, v in self.t.items()}
+        else:
+            self.h = {k: np.full(n, fill, np.uint8) for k, n in shapes}
+            ptr = {k: v.ctypes.data for k, v in self.h.items()}
+        self.struct = VariantsResult(ptr["var"], ptr["text"], ptr["var_n"], ptr["var_flags"], max_variants, max_text)
+
+    def arrays(self):
+        """(records [nt][max_variants], text [nt][max_text], var_n, var_flags) as numpy arrays on the host"""
+        if self.device:
+            import torch
+            torch.cuda.synchronize()
+            self.h = {k: v.cpu().numpy() for k, v in self.t.items()}
+        n = max(self.nt, 1)
+        return (self.h["var"].view(VARIANT_DTYPE).reshape(n, self.max_variants), self.h["text"].reshape(n, self.max_text),
+                self.h["var_n"].view(np.uint32), self.h["var_flags"].view(np.uint32))
+
+    def lists(self):
+        """per trace the list of dict(pos, basenum, gt, ref, alt, call_index), and the flags"""
+        rec, text, n, flags = self.arrays()
+        out = []
+        for t in range(self.nt):
+            out.append([dict(pos=int(r["pos"]), basenum=int(r["basenum"]), gt=int(r["gt"]),
+                             ref=text[t, int(r["ref_off"]):int(r["ref_off"]) + int(r["ref_len"])].tobytes(),
+                             alt=text[t, int(r["alt_off"]):int(r["alt_off"]) + int(r["alt_len"])].tobytes(), call_index=int(r["call_index"]))
+                        for r in rec[t, :int(n[t])]])
+        return out, flags[:self.nt].copy()
+
+
+def _call_variants(self, rows, pos, forward, bc_len, trim_left=50, trim_right=50, max_variants=256, max_text=4096, device=False, buffers=None):
+    """tracyhip_call_variants: rows = (row0, row1) of 2 * ntraces alignments (2t, 2t + 1: the alleles of trace t), pos = rs.pos of each,
+    forward / bc_len per trace.  Returns (per trace the list of dict(pos, basenum, gt, ref, alt, call_index), flags); device=True: rows
+    and results live in device memory (TRACYHIP_MEM_DEVICE)."""
+    nt = len(forward)
+    assert len(rows) == 2 * nt and len(pos) == 2 * nt and len(bc_len) == nt
+    r0, r1, off, lens = _pack_rows(rows)
+    pos = np.ascontiguousarray(pos, dtype=np.int32)
+    fwd = np.ascontiguousarray(forward, dtype=np.uint8)
+    bl = np.ascontiguousarray(bc_len, dtype=np.uint32)
+    b = buffers if buffers is not None else VariantBuffers(nt, max_variants, max_text, device)
+    p0, p1 = r0.ctypes.data, r1.ctypes.data
+    if device:
+        import torch
+        d0, d1 = torch.from_numpy(r0).cuda(), torch.from_numpy(r1).cuda()
+        torch.cuda.synchronize()
+        p0, p1 = d0.data_ptr(), d1.data_ptr()
+    s = b.struct
+    _check(lib().tracyhip_call_variants(self._h, C.c_uint32(nt), C.c_void_p(p0), C.c_void_p(p1), _u64p(off), _u32p(lens),
+                                        pos.ctypes.data_as(C.POINTER(C.c_int32)), fwd.ctypes.data_as(C.POINTER(C.c_uint8)), _u32p(bl),
+                                        C.c_uint32(trim_left), C.c_uint32(trim_right), C.c_uint32(s.max_variants), C.c_uint32(s.max_text),
+                                        MEM_DEVICE if device else MEM_HOST, C.c_void_p(s.var), C.c_void_p(s.text), C.c_void_p(s.var_n),
+                                        C.c_void_p(s.var_flags)))
+    return b.lists()
+
+
+def _decompose_variants(self, outcome, slice_pos=None, max_variants=256, max_text=4096, buffers=None):
+    """tracyhip_decompose_variants on what Context.decompose_traces returned (host buffers, or device payloads when that call ran with
+    device_bc): per trace the list of dict(pos, basenum, gt, ref, alt, call_index), and the flags (bit 0: truncated).  slice_pos: rs.pos of
+    every trace's reference window (None: zeros, a single FASTA)."""
+    c = outcome.call
+    nt = c["nt"]
+    sp = np.zeros(max(nt, 1), np.uint32) if slice_pos is None else np.ascontiguousarray(slice_pos, dtype=np.uint32)
+    b = buffers if buffers is not None else VariantBuffers(nt, max_variants, max_text, c["mem"] == MEM_DEVICE)
+    _check(lib().tracyhip_decompose_variants(self._h, C.byref(c["job"]), C.byref(c["out"]), _u32p(sp), C.byref(c["prm"]), c["mem"],
+                                             C.byref(b.struct)))
+    return b.lists()
+
+
+def _decompose_variants_async(self, job, res, slice_pos, prm, out, mem=MEM_HOST):
+    """tracyhip_decompose_variants_async on prepared structs (they, and everything they point to, must outlive Context.synchronize();
+    slice_pos is copied by the call)"""
+    _check(lib().tracyhip_decompose_variants_async(self._h, C.byref(job), C.byref(res), _u32p(slice_pos), C.byref(prm), mem, C.byref(out)))
+
+
+def decompose_variants_validate(job, res, slice_pos, prm, out, mem=MEM_HOST):
+    """tracyhip_decompose_variants_validate: the argument checks of the call (no device needed); raises TracyHipError"""
+    _check(lib().tracyhip_decompose_variants_validate(C.byref(job) if job is not None else None, C.byref(res) if res is not None else None,
+                                                      _u32p(slice_pos) if slice_pos is not None else None,
+                                                      C.byref(prm) if prm is not None else None, mem, C.byref(out) if out is not None else None))
+
+
+Context.call_variants = _call_variants
+Context.decompose_variants = _decompose_variants
+Context.decompose_variants_async = _decompose_variants_async
 Group.align_traces = _align_traces
 Group.decompose_traces = _decompose_traces
 

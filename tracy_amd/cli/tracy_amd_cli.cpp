@@ -1122,9 +1122,42 @@ struct DecomposeGroup {
     }
     return true;
   }
+
+  // Variants of both alleles (indigo.h:397-423, 442-443) from the arrays run() still holds: tracyhip_decompose_variants returns the
+  // sorted records and their text, rep.var is filled from them.  A trace whose events did not fit the capacities is left for the host
+  // code (`rest`).  TRACY_AMD_CLI_VARIANT_CAPS=<records>,<text bytes> sets the capacities (tests: "1,2" sends every trace with two
+  // events to the host code).
+  bool variants(tracyhip_ctx* ctx, tracyhip_params const& prm, uint32_t nthreads, std::vector<Job*>& rest, uint32_t& called) {
+    uint32_t maxv = 256, maxt = 4096;
+    if (const char* e = getenv("TRACY_AMD_CLI_VARIANT_CAPS")) {
+      unsigned a = 0, b = 0;
+      if (std::sscanf(e, "%u,%u", &a, &b) == 2 && a >= 1 && a <= 1024 && b >= 2) { maxv = a; maxt = b; }
+    }
+    std::vector<uint32_t> spos(nt), vn(nt, 0), vf(nt, 0);
+    for (uint32_t i = 0; i < nt; ++i) spos[i] = jobs[i]->slice_start;
+    std::unique_ptr<tracyhip_variant[]> var(new tracyhip_variant[(std::size_t)nt * maxv]);  // (written by the call: no zero fill)
+    std::unique_ptr<uint8_t[]> text(new uint8_t[(std::size_t)nt * maxt]);
+    const tracyhip_variants_result vr{var.get(), text.get(), vn.data(), vf.data(), maxv, maxt};
+    if (tracyhip_decompose_variants(ctx, &job, &res, spos.data(), &prm, TRACYHIP_MEM_HOST, &vr) != TRACYHIP_OK) return gpu_fail("variants");
+    for_each_index(nt, nthreads, [&](uint32_t i) {
+      Job& j = *jobs[i];
+      j.rep.var.clear();
+      const tracyhip_variant* v = var.get() + (std::size_t)i * maxv;
+      const char* tx = reinterpret_cast<const char*>(text.get()) + (std::size_t)i * maxt;
+      for (uint32_t r = 0; r < vn[i]; ++r)
+        j.rep.var.push_back(Variant{v[r].pos, v[r].basenum, v[r].gt, j.rs.chr, std::string(tx + v[r].ref_off, v[r].ref_len),
+                                    std::string(tx + v[r].alt_off, v[r].alt_len), "."});
+    });
+    for (uint32_t i = 0; i < nt; ++i) {
+      if (vf[i] & 1u) rest.push_back(jobs[i]);
+      else if (status[i] == 0) ++called;
+    }
+    return true;
+  }
 };
 
-// variants of both alleles (indigo.h:393-421); reverse-strand traces are re-aligned as reverse complements
+// variants of both alleles (indigo.h:393-421) on the host, for the traces DecomposeGroup::variants leaves (their events did not fit the
+// device call's capacities); reverse-strand traces are re-aligned as reverse complements
 bool call_variants(tracyhip_ctx* ctx, tracyhip_params const& prm, std::vector<Job*> const& jobs, uint32_t nthreads = 1) {
   // traces on the reverse strand are called on re-aligned reverse complements (two pairs each, one device batch); the rest
   // straight from their allele alignments -- every trace on its own, on the host threads
@@ -1159,7 +1192,7 @@ bool call_variants(tracyhip_ctx* ctx, tracyhip_params const& prm, std::vector<Jo
     Job& j = *jobs[i];
     if (!j.rs.forward)
       for (int k = 0; k < 2; ++k) callVariants(rows[2 * (std::size_t)slot[i] + k], rev[2 * (std::size_t)slot[i] + k], j.rep.var);
-    std::sort(j.rep.var.begin(), j.rep.var.end());
+    std::stable_sort(j.rep.var.begin(), j.rep.var.end());  // (ties by (pos, basenum) in push order: the order the device call defines)
   });
   return true;
 }
@@ -1305,7 +1338,6 @@ int decompose_main(int argc, char** argv) {
     say("Alignment");
     for (auto& g : block_groups[lo / blk])
       if (!g->run(dev, c, prm, nthreads)) return false;
-    block_groups[lo / blk].clear();  // (the packed batch and the raw results: everything the writers need is in the jobs now)
     say("InDel Search");
     std::vector<Job*> good;
     for (uint32_t i = lo; i < hi; ++i) {
@@ -1340,9 +1372,16 @@ int decompose_main(int argc, char** argv) {
     if (c.callvariants) {
       say("Variant Calling");
       PhaseClock pv;
-      if (!call_variants(dev.ctx, prm, good, nthreads)) return false;
+      std::vector<Job*> rest;
+      uint32_t called = 0;
+      for (auto& g : block_groups[lo / blk])
+        if (!g->variants(dev.ctx, prm, nthreads, rest, called)) return false;
+      if (!rest.empty() && !call_variants(dev.ctx, prm, rest, nthreads)) return false;
+      times.add("var_traces", (double)called);  // called by the device path / left to the host code
+      times.add("var_fallback", (double)rest.size());
       pv.lap(CpuPhases::VARIANTS);
     }
+    block_groups[lo / blk].clear();  // (the packed batch and the raw results: everything the writers need is in the jobs now)
     fatal = 0;
     ++blocks_done;
     times.add("device_s", sw.seconds());

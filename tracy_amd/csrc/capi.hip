@@ -541,7 +541,7 @@ int range_verdict(const tracyhip_params* prm, const int32_t* herr, const std::ve
 }
 
 int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, bool needle, bool trace,
-           int32_t* d_scores, uint8_t* d_ops, const uint64_t* d_ops_off, uint32_t* d_ops_len, int stage, DpCkpt* ck) {
+           int32_t* d_scores, uint8_t* d_ops, const uint64_t* d_ops_off, uint32_t* d_ops_len, int stage, DpCkpt* ck, int32_t* defer_herr) {
   const uint32_t np = (uint32_t)pb.desc.size();
   if (np == 0) return TRACYHIP_OK;
   if (sub_limit(prm) > kWideScore && ((trace && pb.mode == MODE_CQ) || stage == DP_BAND))
@@ -764,6 +764,10 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
       }
       j = e;
     }
+  }
+  if (defer_herr) {  // the caller waits and judges (strings, traceback: nothing here can ask for the wider kernels)
+    HIP_TRY(hipMemcpyAsync(defer_herr, ctx->dev[DB_ERR].p, sizeof(int32_t) * kErrWords, hipMemcpyDeviceToHost, st));
+    return TRACYHIP_OK;
   }
   int32_t herr[kErrWords] = {};
   unsigned long long h_swept = 0;

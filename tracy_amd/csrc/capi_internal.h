@@ -152,10 +152,33 @@ enum CtxDev : int {
   DN_STEP = AB_STEP,    // AsmStep per node of a height + AsmFinal per group, uploaded per height / chunk
   DN_PAY = AB_PAY,      // results staged for a host caller
   DN_CNT,       // 's' ops of every overlap alignment of a round: written by denovo_count_kernel, read back per round (a slot of its own,
-                // and the last enumerator before DB_COUNT: the aliases above do not advance the count)
+                // and the last enumerator before the next family: the aliases above do not advance the count)
+  // ---- tracyhip_call_variants / tracyhip_decompose_variants (variants.hip) ----
+  // rows live in DB_ROWS0 / DB_ROWS1 (staged in by the stage, written by the alignment_rows launches of the pipeline)
+  VB_DESC,      // VarDesc per trace of a chunk, uploaded; read by variants_kernel
+  VB_EVENTS,    // 2 x max_variants VarEvent per resident wave: the two per-allele lists of variants_wave
+  VB_LEN,       // column counts of the alignments: uploaded by the stage; the pipeline's copy of a host caller's ops_len[0 | 1]
+  VB_PAIRS,     // PairDesc lists of the pipeline's alignment_rows launches, uploaded per chunk
+  VB_RCDESC,    // VarRcDesc list of var_revcomp_kernel, uploaded per chunk
+  VB_SEQ,       // reverse complements of the trimmed alleles and their slices (reverse traces): both sides of the re-alignments
+  VB_OPS,       // op strings of the re-alignments, written by the traceback batch, read by alignment_rows
+  VB_OPS_OFF,   // their offsets (the rows of a re-alignment sit at the same offset in the reverse region of DB_ROWS0 / 1), uploaded
+  VB_OPS_LEN,   // their lengths, written with the ops, read by alignment_rows and variants_kernel
+  VB_IN_PRIMARY,    // a host caller's primary / secdecomp / references / ops[0] / ops[1] of the pipeline, staged in once per call
+  VB_IN_SECDECOMP,
+  VB_IN_REFS,
+  VB_IN_OPS0,
+  VB_IN_OPS1,
+  VB_OUT_REC,   // records / text / counts + flags staged for a host caller
+  VB_OUT_TEXT,
+  VB_OUT_N,
+  VB_PACK_OFF,  // var_pack_scan_kernel: where every trace's records and text begin in the packed copies
+  VB_PACK_REC,  // the used records of every trace back to back: written by var_pack_copy_kernel, copied to the host
+  VB_PACK_TEXT, // the used text likewise
   DB_COUNT
 };
-static_assert(DN_CNT + 1 == DB_COUNT && DN_PAY < DB_COUNT, "an alias does not advance the count: every slot of its own comes after the aliases");
+static_assert(DN_CNT + 1 == VB_DESC && VB_PACK_TEXT + 1 == DB_COUNT && DN_PAY < DB_COUNT,
+              "an alias does not advance the count: every slot of its own comes after the aliases");
 // pinned host buffers of a context: tracyhip_ctx::pin[]
 enum CtxPin : int {
   PB_DESC,      // descriptor uploads of run_dp and the batch calls
@@ -406,9 +429,12 @@ struct DpCkpt {
 bool origin_ok(const tracyhip_params* prm, uint32_t maxm, uint32_t maxn, int K);
 int run_ckpt_prefix(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, const std::vector<PairDesc>& full, const std::vector<int>& fullk,
                     const std::vector<PairDesc>& pre, const tracyhip_params* prm, int32_t* d_scores, DpCkpt* ck, bool front_shape = false);
+// defer_herr (kErrWords host words that live until the caller has waited for the stream; traceback of strings only): the launches are
+// queued and the error words copied there WITHOUT a wait -- the caller synchronises behind its own launches and passes the words to
+// range_verdict itself (no narrow launches; max_mn, kTagShift).  The pinned descriptors are the context's: no second run_dp before that wait.
 int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, bool needle, bool trace,
            int32_t* d_scores, uint8_t* d_ops, const uint64_t* d_ops_off, uint32_t* d_ops_len, int stage = DP_PLAIN,
-           DpCkpt* ck = nullptr);
+           DpCkpt* ck = nullptr, int32_t* defer_herr = nullptr);
 bool narrow_ok(const tracyhip_params* prm, uint32_t maxm, int K, int64_t Q = 0);
 // profile x profile score kernel with 16-bit cells for pairs of at most max_mn = m + n (Q: largest substitution score, 0 = a priori)
 bool arith16_ok(const tracyhip_params* prm, uint64_t max_mn, int64_t Q);

@@ -335,7 +335,7 @@ int32_t tracyhost_decompose_outputs(const tracyhost_decompose_report* rp) {
       if (!rs.forward) reverseReferenceSlice(*slot[k], vrs);
       callVariants(v, vrs, r.var);
     }
-    std::sort(r.var.begin(), r.var.end());
+    std::stable_sort(r.var.begin(), r.var.end());  // (ties by (pos, basenum) keep push order, as tracyhip_decompose_variants orders them)
     std::ofstream f((pre + ".vcf").c_str());
     vcfTextOutput(f, rc, bc, r.var, rs);
     if (!bcfOutput(pre + ".bcf", rc, bc, r.var, rs)) return -2;
@@ -671,6 +671,75 @@ double tracyhost_basecall_batch(const int32_t* signal, uint32_t nt, uint32_t ns,
   double worst = 0;
   for (double v : spent) worst = std::max(worst, v);
   return worst;
+}
+
+// ---- the host side of the variant section of `tracy decompose -v` as tracy_amd_cli's call_variants runs it (the path behind
+// tracyhip_decompose_variants' truncated traces; tools/variants_device_line.py times it beside the device call) ----
+// reverseComplement of n strings: string i is src[off[i] .. + len[i]) and goes to dst + dst_off[i]
+int tracyhost_revcomp_batch(const uint8_t* src, const uint64_t* off, const uint32_t* len, uint32_t n, uint8_t* dst, const uint64_t* dst_off, uint32_t nthreads) {
+  if (n && (!src || !off || !len || !dst || !dst_off)) return -1;
+  if (nthreads == 0) nthreads = tracy_amd::usable_threads();
+  std::vector<std::thread> th;
+  for (uint32_t w = 0; w < nthreads; ++w)
+    th.emplace_back([=]() {
+      std::string s;
+      for (uint32_t i = (uint32_t)((uint64_t)n * w / nthreads); i < (uint32_t)((uint64_t)n * (w + 1) / nthreads); ++i) {
+        s.assign(reinterpret_cast<const char*>(src) + off[i], len[i]);
+        reverseComplement(s);
+        std::memcpy(dst + dst_off[i], s.data(), s.size());
+      }
+    });
+  for (auto& t : th) t.join();
+  return 0;
+}
+// callVariants of both allele alignments of every trace (alignments 2t and 2t + 1: rows0 / rows1 + off[i], len[i] columns, rs.pos pos[i]),
+// std::stable_sort, variantCallIndex.  Results in the layout of tracyhip_call_variants: 8 words per record (pos, basenum, gt, call_index,
+// ref_off, ref_len, alt_off, alt_len), max_variants records and max_text bytes per trace; a trace that does not fit: var_n 0, flag 1.
+int tracyhost_call_variants_batch(uint32_t n, const uint8_t* rows0, const uint8_t* rows1, const uint64_t* off, const uint32_t* len, const int32_t* pos,
+                                  const uint8_t* forward, const uint32_t* bc_len, uint32_t trim_left, uint32_t trim_right, uint32_t max_variants,
+                                  uint32_t max_text, uint32_t* rec, uint8_t* text, uint32_t* var_n, uint32_t* var_flags, uint32_t nthreads) {
+  if (n && (!rows0 || !rows1 || !off || !len || !pos || !forward || !bc_len || !rec || !text || !var_n || !var_flags)) return -1;
+  if (nthreads == 0) nthreads = tracy_amd::usable_threads();
+  std::vector<std::thread> th;
+  for (uint32_t w = 0; w < nthreads; ++w)
+    th.emplace_back([=]() {
+      std::vector<Variant> var;
+      AlignRows al;
+      ReferenceSlice rs;
+      rs.chr = "chr";
+      for (uint32_t t = (uint32_t)((uint64_t)n * w / nthreads); t < (uint32_t)((uint64_t)n * (w + 1) / nthreads); ++t) {
+        var.clear();
+        for (uint32_t k = 0; k < 2; ++k) {
+          const std::size_t i = 2 * (std::size_t)t + k;
+          al.row0.assign(reinterpret_cast<const char*>(rows0) + off[i], len[i]);
+          al.row1.assign(reinterpret_cast<const char*>(rows1) + off[i], len[i]);
+          rs.pos = pos[i];
+          callVariants(al, rs, var);
+        }
+        std::stable_sort(var.begin(), var.end());
+        std::size_t bytes = 0;
+        for (Variant const& v : var) bytes += v.ref.size() + v.alt.size();
+        var_n[t] = 0;
+        var_flags[t] = (var.size() > max_variants || bytes > max_text) ? 1u : 0u;
+        if (var_flags[t]) continue;
+        uint32_t at = 0;
+        uint32_t* r = rec + 8 * (std::size_t)t * max_variants;
+        uint8_t* tx = text + (std::size_t)t * max_text;
+        for (Variant const& v : var) {
+          const uint32_t call = forward[t] ? trim_left + (uint32_t)v.basenum - 1u : bc_len[t] - (trim_right + (uint32_t)v.basenum);
+          const uint32_t rl = (uint32_t)v.ref.size(), alen = (uint32_t)v.alt.size();
+          const uint32_t w8[8] = {(uint32_t)v.pos, (uint32_t)v.basenum, (uint32_t)v.gt, call, at, rl, at + rl, alen};
+          std::memcpy(r, w8, sizeof(w8));
+          std::memcpy(tx + at, v.ref.data(), rl);
+          std::memcpy(tx + at + rl, v.alt.data(), alen);
+          at += rl + alen;
+          r += 8;
+        }
+        var_n[t] = (uint32_t)var.size();
+      }
+    });
+  for (auto& t : th) t.join();
+  return 0;
 }
 
 // threads the batch entry points start when the caller passes nthreads = 0
