@@ -123,7 +123,8 @@ int tracyhip_synchronize(tracyhip_ctx* ctx);
 /* Options.  Every switch of the library is read from the environment ONCE, when a context is created (TRACYHIP_<NAME>, e.g.
    TRACYHIP_NO_STREAM=1), and changed afterwards only through this call; name is the variable without the prefix, in any case:
      no_stream (pipelines planned by the host between launches instead of stream-ordered), no_narrow, no_compact, no_screen,
-     no_band, no_band16, no_front, no_prefix, no_vote, no_origin, no_subwindow, no_prelim_origin, no_cq, no_fused_walk, no_cont16, no_quads, no_fork, no_early_tail (`tracy align`: no alignment queued before both orientation scores are known), no_decomp_wave, no_af_split, no_front_lists, no_origin_band, sweeps_alone (measurement: the full sweeps of the orientation stage on a device of their own)   "0" / "1"
+     no_band, no_band16, no_front, no_prefix, no_vote, no_origin, no_subwindow, no_prelim_origin, no_cq, no_fused_walk, no_cont16, no_quads, no_fork, no_early_tail (`tracy align`: no alignment queued before both orientation scores are known), no_decomp_wave, no_af_split, no_front_lists, no_origin_band, sweeps_alone (measurement: the full sweeps of the orientation stage on a device of their own), no_sweep_diag (16-bit sweeps on values as they are instead of the diagonal-offset form)   "0" / "1"
+     sweep_diag_period  (steps between re-bases of the offset form: 0 = what the range rule allows, else a multiple of 4 from 64 on, clamped to that)
      band_w  (half width of the certified band of the final alignments; -1 = from the preliminary alignment, 0 = whole matrices)
      ckpt_b  (steps between wavefront checkpoints, 32 .. 1024)      verbose  (one line per pipeline stage on stderr)
      seed_vote_cap  (tracyhip_seed_traces: votes one trace may collect per strand and pass on the device, 1 .. 2048, default 2048;
@@ -171,6 +172,8 @@ typedef struct {
   uint32_t var_realigned;        /* ... of which on the reverse strand: both alleles re-aligned as reverse complements (indigo.h:408-422) */
   uint32_t var_truncated;        /* ... traces whose events did not fit max_variants / max_text (var_flags bit 0) */
   uint32_t var_chunks;           /* ... chunks of traces the batch was cut into to fit the workspace limit */
+  uint32_t sweep_diag_launches;  /* 16-bit full sweeps launched in the offset form (six operations per cell; 0 with no_sweep_diag or where the range rule finds no room) */
+  uint32_t prefix_diag_launches; /* ... launches of prefix sweeps in the offset form */
 } tracyhip_call_stats;
 int tracyhip_last_call_stats(tracyhip_ctx* ctx, tracyhip_call_stats* out);
 const char* tracyhip_last_error(void);

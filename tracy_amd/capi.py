@@ -60,11 +60,17 @@ class CallStats(C.Structure):
 
 
 class CallStatsVariants(CallStats):
-    """THE mirror of tracyhip_call_stats, and the only one to hand to tracyhip_last_call_stats: CallStats (the counters through
-    denovo_steps, kept as it was: tests pin its tail) with the four counters of tracyhip_decompose_variants appended -- ctypes lays a
-    subclass's fields out behind its base's, as the C struct grew.  A bare CallStats is 16 bytes SHORTER than what the library writes:
-    passing one to tracyhip_last_call_stats is an out-of-bounds write.  Context.last_call_stats uses this class."""
+    """CallStats (the counters through denovo_steps, kept as it was: tests pin its tail) with the four counters of
+    tracyhip_decompose_variants appended -- ctypes lays a subclass's fields out behind its base's, as the C struct grew.  The struct
+    has grown once more since: CallStatsSweeps below is THE mirror of tracyhip_call_stats, and the only one to hand to
+    tracyhip_last_call_stats -- anything shorter is an out-of-bounds write.  Context.last_call_stats uses it."""
     _fields_ = [("var_traces", C.c_uint32), ("var_realigned", C.c_uint32), ("var_truncated", C.c_uint32), ("var_chunks", C.c_uint32)]
+
+
+class CallStatsSweeps(CallStatsVariants):
+    """CallStatsVariants with the two counters of the offset-form sweeps behind it, as the C struct grew: what
+    Context.last_call_stats hands to the library."""
+    _fields_ = [("sweep_diag_launches", C.c_uint32), ("prefix_diag_launches", C.c_uint32)]
 
 
 def library_path():
@@ -179,10 +185,10 @@ class Context:
 
     def last_call_stats(self):
         """tiers the traces of the last align_traces / decompose_traces call took (tracyhip_last_call_stats)"""
-        st = CallStatsVariants()
+        st = CallStatsSweeps()
         _check(lib().tracyhip_last_call_stats(self._h, C.byref(st)))
         out = {}
-        for name, ty in CallStats._fields_ + CallStatsVariants._fields_:
+        for name, ty in CallStats._fields_ + CallStatsVariants._fields_ + CallStatsSweeps._fields_:
             v = getattr(st, name)
             out[name] = list(v) if hasattr(v, "__len__") else int(v)
         return out

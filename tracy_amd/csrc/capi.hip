@@ -25,6 +25,7 @@
 #include "capi_internal.h"
 #include "launch.h"
 #include "stream_plan.h"
+#include "sweep_range.h"
 
 using namespace tracyhip;
 
@@ -243,7 +244,7 @@ const KnobField kKnobFlags[] = {
     {"no_screen", &CtxKnobs::no_screen}, {"no_band", &CtxKnobs::no_band}, {"no_band16", &CtxKnobs::no_band16},
     {"no_front", &CtxKnobs::no_front}, {"no_prefix", &CtxKnobs::no_prefix}, {"no_vote", &CtxKnobs::no_vote},
     {"no_origin", &CtxKnobs::no_origin}, {"no_subwindow", &CtxKnobs::no_subwindow}, {"no_prelim_origin", &CtxKnobs::no_prelim_origin},
-    {"no_cq", &CtxKnobs::no_cq}, {"no_fused_walk", &CtxKnobs::no_fused_walk}, {"no_cont16", &CtxKnobs::no_cont16}, {"no_decomp_wave", &CtxKnobs::no_decomp_wave}, {"no_af_split", &CtxKnobs::no_af_split}, {"no_front_lists", &CtxKnobs::no_front_lists}, {"no_origin_band", &CtxKnobs::no_origin_band}, {"no_quads", &CtxKnobs::no_quads}, {"no_fork", &CtxKnobs::no_fork}, {"no_early_tail", &CtxKnobs::no_early_tail}, {"sweeps_alone", &CtxKnobs::sweeps_alone}, {"verbose", &CtxKnobs::verbose}};
+    {"no_cq", &CtxKnobs::no_cq}, {"no_fused_walk", &CtxKnobs::no_fused_walk}, {"no_cont16", &CtxKnobs::no_cont16}, {"no_decomp_wave", &CtxKnobs::no_decomp_wave}, {"no_af_split", &CtxKnobs::no_af_split}, {"no_front_lists", &CtxKnobs::no_front_lists}, {"no_origin_band", &CtxKnobs::no_origin_band}, {"no_quads", &CtxKnobs::no_quads}, {"no_fork", &CtxKnobs::no_fork}, {"no_early_tail", &CtxKnobs::no_early_tail}, {"sweeps_alone", &CtxKnobs::sweeps_alone}, {"no_sweep_diag", &CtxKnobs::no_sweep_diag}, {"verbose", &CtxKnobs::verbose}};
 bool same_name(const char* a, const char* b) {
   for (; *a && *b; ++a, ++b)
     if (std::tolower((unsigned char)*a) != std::tolower((unsigned char)*b)) return false;
@@ -277,6 +278,12 @@ bool knobs_set(CtxKnobs& k, const char* name, const char* value) {
     k.seed_vote_cap = (uint32_t)v;
     return true;
   }
+  if (same_name(name, "sweep_diag_period")) {  // 0 = the range rule's own; else a multiple of 4 from 64 on, clamped to the rule's at a launch
+    const long v = atol(value);
+    if (v != 0 && (v < 64 || v > 32768 || v % 4 != 0)) return false;
+    k.sweep_diag_period = (uint32_t)v;
+    return true;
+  }
   if (same_name(name, "ckpt_b")) {
     const long v = atol(value);
     if (v < 32 || v > 1024) return false;
@@ -303,6 +310,7 @@ void knobs_from_env(CtxKnobs& k) {
   if (const char* e = getenv("TRACYHIP_QUAD_TIER_MIN")) knobs_set(k, "quad_tier_min", e);
   if (const char* e = getenv("TRACYHIP_FRONT_LIST_MIN")) knobs_set(k, "front_list_min", e);
   if (const char* e = getenv("TRACYHIP_SEED_VOTE_CAP")) knobs_set(k, "seed_vote_cap", e);
+  if (const char* e = getenv("TRACYHIP_SWEEP_DIAG_PERIOD")) knobs_set(k, "sweep_diag_period", e);
 }
 std::string knobs_describe(const CtxKnobs& k) {
   std::string s;
@@ -312,6 +320,7 @@ std::string knobs_describe(const CtxKnobs& k) {
   s += "quad_tier_min=" + std::to_string(k.quad_tier_min) + "\n";
   s += "front_list_min=" + std::to_string(k.front_list_min) + "\n";
   s += "seed_vote_cap=" + std::to_string(k.seed_vote_cap) + "\n";
+  s += "sweep_diag_period=" + std::to_string(k.sweep_diag_period) + "\n";
   s += "host_threads=" + std::to_string(host_pool_threads()) + "\n";
   return s;
 }
@@ -475,17 +484,29 @@ bool check_profile_columns(const tracyhip_seqset& s, const char* name, uint32_t 
   return true;
 }
 
-// 16-bit score kernel: every real DP value must fit int16 with room below for the sentinel.  Q bounds the absolute value of
-// a substitution score: max(|match|, |mismatch|) for strings and normalised profiles (the a-priori call, Q = 0), the
-// device-reported maximum when a launch has seen a larger query-profile entry (range_verdict).
-bool narrow_ok(const tracyhip_params* prm, uint32_t maxm, int K, int64_t Q) {
-  // free end gaps on the first/last row only, strictly negative extension, one pass of the strip height
-  if (!prm->hfree || prm->vfree || prm->go > 0 || prm->ge >= 0 || num_passes(maxm ? maxm : 1, K) != 1) return false;
-  Q = std::max<int64_t>(Q, sub_limit(prm));
-  const int64_t rows = (int64_t)num_passes(maxm ? maxm : 1, K) * 64 * K;
-  const int64_t low = iabs64(prm->go) + rows * iabs64(prm->ge) + 2 * (iabs64(prm->go) + iabs64(prm->ge)) + 2 * Q;
-  const int64_t high = rows * Q;
-  return (low < -(int64_t)kNegInf16 - iabs64(prm->ge) - 64) && (high < 30000);
+// the value-range rules of the 16-bit sweeps live in sweep_range.h (plain C++, so that a test can build them alone)
+bool narrow_ok(const tracyhip_params* prm, uint32_t maxm, int K, int64_t Q) { return narrow_ok_rule(prm, maxm, K, Q); }
+uint32_t sweep_diag_period(const tracyhip_params* prm, int K, int lanes, int64_t Q) { return sweep_diag_period_rule(prm, K, lanes, Q); }
+// ... of a launch of this context: the shape the offset form is written for (whole-wave sweeps of fifteen / sixteen rows), the two options
+uint32_t ctx_sweep_diag(const tracyhip_ctx* ctx, const tracyhip_params* prm, int K, int lanes) {
+  if (ctx->knobs.no_sweep_diag || lanes != 64 || (K != 15 && K != 16)) return 0;
+  const uint32_t rule = sweep_diag_period(prm, K, lanes, 0);
+  return (rule && ctx->knobs.sweep_diag_period) ? std::min(rule, ctx->knobs.sweep_diag_period) : rule;
+}
+
+// A launch of full sweeps and prefix groups (launch_gotoh_ckpt_front / _prefix) is one kernel and takes one form: both periods, or
+// neither.  front_shape: the prefix rows as sixteen lanes of eight rows or eight of sixteen (the launcher decides; the smaller period
+// serves both); otherwise eight lanes of K rows.
+void launch_diag_periods(tracyhip_ctx* ctx, const tracyhip_params* prm, int K, uint32_t nfull, uint32_t npre, bool front_shape, DpArgs& full, DpArgs& pre) {
+  full.diag_period = pre.diag_period = 0;
+  if (ctx->knobs.no_sweep_diag || (K != 15 && K != 16) || nfull + npre == 0) return;
+  uint32_t pf = sweep_diag_period(prm, K, 64, 0);
+  uint32_t pp = front_shape ? std::min(sweep_diag_period(prm, kFrontPrefixK, kFrontPrefixLanes, 0), sweep_diag_period(prm, 16, (int)kFrontRows / 16, 0))
+                            : sweep_diag_period(prm, K, kPrefixLanes, 0);
+  if (const uint32_t cap = ctx->knobs.sweep_diag_period) { pf = std::min(pf, cap); pp = std::min(pp, cap); }
+  if ((nfull && !pf) || (npre && !pp)) return;
+  if (nfull) { full.diag_period = pf; ++ctx->stats.sweep_diag_launches; }
+  if (npre) { pre.diag_period = pp; ++ctx->stats.prefix_diag_launches; }
 }
 
 // profile x profile score kernel with 16-bit cells (any AlignConfig, any number of passes).  Every H, E, F of the matrix is at least
@@ -531,8 +552,12 @@ int range_verdict(const tracyhip_params* prm, const int32_t* herr, const std::ve
     seen = true;
   }
   if (!seen) return TRACYHIP_OK;
-  for (auto const& nl : narrow_launches)  // (K = 0 marks a launch of the 16-bit profile x profile kernel: first = its largest m + n)
-    if (nl.second == 0 ? !arith16_ok(prm, nl.first, Q) : !narrow_ok(prm, nl.first, nl.second, Q)) return kWiden;
+  for (auto const& nl : narrow_launches) {  // (K = 0 marks a launch of the 16-bit profile x profile kernel: first = its largest m + n)
+    const int K = nl.second & 0xff;
+    const uint32_t diag = (uint32_t)nl.second >> 8;  // a sweep in the offset form: its period (narrow_launch_diag)
+    if (K == 0 ? !arith16_ok(prm, nl.first, Q) : !narrow_ok(prm, nl.first, K, Q)) return kWiden;
+    if (diag && sweep_diag_period(prm, K, 64, Q) < diag) return kWiden;  // the offsets had less room than the launch assumed
+  }
   const int64_t c = iabs64(prm->go) + iabs64(prm->ge) + Q;
   if ((int64_t)(max_mn + 2) * c + 1000000 >= (1ll << (31 - value_shift)))
     return set_error(TRACYHIP_ERR_RANGE, "un-normalised profile: (m+n) * (gap cost + largest substitution score %lld) exceeds the exact range of the int32 kernels",
@@ -717,10 +742,12 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
         for (uint32_t q = j; q < e; ++q) maxm = std::max(maxm, hd[q].m);
         narrow = narrow_ok(prm, maxm, K);
       }
+      a.diag_period = 0;
       if (stage == DP_PREFIX || (stage == DP_CKPT && ck->narrow) || (stage == DP_PLAIN && narrow)) {
         uint32_t maxm = 0;
         for (uint32_t q = j; q < e; ++q) maxm = std::max(maxm, hd[q].m);
-        narrow_launches.emplace_back(maxm, K);
+        if (stage != DP_PREFIX && pb.mode == MODE_QP && (a.diag_period = ctx_sweep_diag(ctx, prm, K, 64))) ++ctx->stats.sweep_diag_launches;
+        narrow_launches.emplace_back(maxm, narrow_launch_diag(K, a.diag_period));
       }
       if (stage == DP_PREFIX) {
         HIP_TRY(launch_gotoh_prefix(K, a, e - j, st));
@@ -1302,11 +1329,14 @@ int run_ckpt_prefix(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, const
     for (size_t i = 0; i < npre; ++i) max_mn = std::max<uint64_t>(max_mn, (uint64_t)hd[nf + i].m + hd[nf + i].n);
     DpArgs af = a;
     af.pairs = static_cast<const PairDesc*>(ctx->dev[DB_DESC].p) + lo;
-    if (front_shape) HIP_TRY(launch_gotoh_ckpt_front(K, af, (uint32_t)(hi - lo), ap, npre, st));
-    else HIP_TRY(launch_gotoh_ckpt_prefix(K, af, (uint32_t)(hi - lo), ap, npre, st));
+    DpArgs apl = ap;
+    launch_diag_periods(ctx, prm, K, (uint32_t)(hi - lo), npre, front_shape, af, apl);
+    if (front_shape) HIP_TRY(launch_gotoh_ckpt_front(K, af, (uint32_t)(hi - lo), apl, npre, st));
+    else HIP_TRY(launch_gotoh_ckpt_prefix(K, af, (uint32_t)(hi - lo), apl, npre, st));
     if ((trc = timing_end(ctx))) return trc;
-    if (hi > lo) narrow_launches.emplace_back(maxm, K);
-    if (npre) narrow_launches.emplace_back(prows, front_shape ? kFrontPrefixK : K);  // (the prefix is a sweep of its own rows)
+    if (hi > lo) narrow_launches.emplace_back(maxm, narrow_launch_diag(K, af.diag_period));
+    // (the prefix is a sweep of its own rows; range_verdict re-evaluates an offset form's period for a whole wave of such strips, which is the wider span)
+    if (npre) narrow_launches.emplace_back(prows, narrow_launch_diag(front_shape ? kFrontPrefixK : K, apl.diag_period));
     pre_done = true;
     lo = hi;
   }

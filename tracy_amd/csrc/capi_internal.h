@@ -225,6 +225,7 @@ struct CtxKnobs {
   bool sweeps_alone = false;      // MEASUREMENT mode of the stream-ordered orientation stage: the voted strand's chain finishes BEFORE the other strand's full sweeps
                                   // start and its prefix cells are credited to the front timer -- TRACYHIP_TIMER_SCORE then times the full sweeps on a device
                                   // of their own (bench.py roofline.dominant_kernel_alone_frac); slower, same results
+  bool no_sweep_diag = false;     // the 16-bit query-profile sweeps on values as they are (eight operations per cell) instead of the offset form (six)
   bool no_origin_band = false;    // `tracy decompose`, gotoh(allele, slice): the band d1 +- (g + 1) of every co-optimal path instead of the g + 3 diagonals of the walked one
   bool no_front_lists = false;    // pruned sweeps: later tiers skip what an earlier one certified in place instead of running over a list of the rest
   bool no_af_split = false;       // allelicFraction by the one-launch kernel (tp / cls in LDS, every grid point screened) instead of prepare + search
@@ -234,6 +235,7 @@ struct CtxKnobs {
   int32_t band_w = -1;            // half width of the certified band of the final alignments: -1 = from the preliminary alignment (default),
                                   // 0 = whole matrices, else [1, 4096]
   uint32_t ckpt_b = 256;
+  uint32_t sweep_diag_period = 0; // offset form of the sweeps: steps between re-bases, clamped to what sweep_diag_period() allows; 0 = that
   uint32_t front_list_min = 1024; // stream-ordered pipelines: units from which the later tiers of a pruned sweep (and the allele prefixes) run over device-side lists
   uint32_t seed_vote_cap = 2048;  // tracyhip_seed_traces: votes per trace, strand and pass held in LDS (seed.hip); more: the trace is deferred
   uint32_t quad_tier_min = 32768;  // stream-ordered pipelines: units (traces, or alleles) from which the pruned sweeps get their narrow quad tier          // steps between wavefront checkpoints [32, 1024]
@@ -436,6 +438,14 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
            int32_t* d_scores, uint8_t* d_ops, const uint64_t* d_ops_off, uint32_t* d_ops_len, int stage = DP_PLAIN,
            DpCkpt* ck = nullptr, int32_t* defer_herr = nullptr);
 bool narrow_ok(const tracyhip_params* prm, uint32_t maxm, int K, int64_t Q = 0);
+// the offset form of the 16-bit query-profile sweeps: steps between re-bases for strips of K rows on `lanes` lanes per pair, 0 = no room
+uint32_t sweep_diag_period(const tracyhip_params* prm, int K, int lanes, int64_t Q = 0);
+// ... for a launch of this context (options no_sweep_diag / sweep_diag_period; 0: the launch takes the form without offsets)
+uint32_t ctx_sweep_diag(const tracyhip_ctx* ctx, const tracyhip_params* prm, int K, int lanes);
+// ... for a launch of full sweeps and prefix groups, which takes one form: sets both periods or neither, and counts the launch in the statistics
+void launch_diag_periods(tracyhip_ctx* ctx, const tracyhip_params* prm, int K, uint32_t nfull, uint32_t npre, bool front_shape, tracyhip::DpArgs& full, tracyhip::DpArgs& pre);
+// entry of a narrow_launches list for a sweep that ran in the offset form: range_verdict re-evaluates the period with the Q it finds
+inline int narrow_launch_diag(int K, uint32_t period) { return K | (int)(period << 8); }
 // profile x profile score kernel with 16-bit cells for pairs of at most max_mn = m + n (Q: largest substitution score, 0 = a priori)
 bool arith16_ok(const tracyhip_params* prm, uint64_t max_mn, int64_t Q);
 int32_t sub_limit(const tracyhip_params* prm);

@@ -103,6 +103,8 @@ struct DpArgs {
   unsigned long long* swept;  // band traceback: DP cells actually re-swept, summed over the launch (or null)
   const uint32_t* index;  // prefix sweeps (gotoh_prefix_body): pair i of the launch is pairs[index[i]] and only *count of them exist -- a list
   const uint32_t* count;  // laid out on the device, the grid sized for its worst case (null: pairs[i], npairs)
+  uint32_t diag_period;   // 16-bit query-profile sweeps: 0 = values as they are; otherwise the offset form (gotoh_narrow_qp_body, DIAG) with
+                          // a re-base every diag_period steps (a multiple of 4, at least 64: sweep_diag_period in capi.hip)
   const uint32_t* votes;  // checkpointed 16-bit sweep of both orientations (PairDesc::out = orientation * vote_nt + trace): {vf, vr} per
   uint32_t vote_nt;       // trace, or null.  Sweeps of the likely losing strand (vote_skips_checkpoints) write no checkpoints / row m
 };
@@ -326,7 +328,7 @@ TR_HD uint64_t ckpt_index(uint32_t j /*1-based*/, uint32_t field, uint32_t lane,
   return ((uint64_t)(j - 1) * ckpt_fields(K) + field) * 64u + lane;
 }
 
-template <class W, int K, bool CKPT, bool COMPACT, bool STRINGS>
+template <class W, int K, bool CKPT, bool COMPACT, bool STRINGS, bool DIAG = false>
 TR_HD void gotoh_narrow_qp_body(W& w, const DpArgs& a, uint32_t pair_idx);  // the 16-bit query-profile sweep, below
 
 // NT (profile x profile only): 5 = the 25-term substitution score, 4 = the 16-term one (row 4 zero in both profiles of every
@@ -334,8 +336,10 @@ TR_HD void gotoh_narrow_qp_body(W& w, const DpArgs& a, uint32_t pair_idx);  // t
 // COMPACT selects the second form of two kernels: the 16-bit query-profile sweep with the four-code table (NARROW, MODE_QP), and
 // the profile x profile score kernel with 16-bit cells (MODE_PROF, !TRACE: any AlignConfig, any number of passes; v_add_u16 /
 // v_max_i16 instead of int32 maxima, which issue at half the rate -- arith16_ok in capi.hip admits the launch)
-template <class W, int K, int MODE, bool TRACE, bool NARROW = false, bool CKPT = false, int NT = 0, bool COMPACT = false>
+// DIAG: the 16-bit query-profile sweep in its offset form (six operations per cell)
+template <class W, int K, int MODE, bool TRACE, bool NARROW = false, bool CKPT = false, int NT = 0, bool COMPACT = false, bool DIAG = false>
 TR_HD void gotoh_body(W& w, const DpArgs& a, uint32_t pair_idx) {
+  static_assert(!DIAG || (NARROW && qp_like(MODE)), "the offset form exists for the 16-bit query-profile sweep");
   static_assert(!(NARROW && TRACE), "the 16-bit formulation exists for the score-only kernel");
   constexpr bool A16 = MODE == MODE_PROF && !TRACE && !NARROW && !CKPT && COMPACT;
   // traceback with table scores (TRACE, MODE_QP / MODE_CQ) and COMPACT: the table holds the scores as they are and a cell shifts its
@@ -347,7 +351,7 @@ TR_HD void gotoh_body(W& w, const DpArgs& a, uint32_t pair_idx) {
   // NARROW / CKPT kernels: single pass, free end gaps on the first/last row only, rows anchored at the bottom
   constexpr bool BOTTOM = NARROW || CKPT;
   if constexpr (NARROW && qp_like(MODE)) {  // the hot kernel of `tracy align` has its own body (MODE_CQ: its rows are characters)
-    gotoh_narrow_qp_body<W, K, CKPT, COMPACT, MODE == MODE_CQ>(w, a, pair_idx);
+    gotoh_narrow_qp_body<W, K, CKPT, COMPACT, MODE == MODE_CQ, DIAG>(w, a, pair_idx);
     return;
   }
   const PairDesc d = a.pairs[pair_idx];
@@ -815,7 +819,21 @@ TR_HD int32_t lastrow_e(const int32_t* lr, uint32_t c, bool narrow, int32_t goe)
 
 // STRINGS: a1 is a string over A C G T N and a2 holds case-sensitive codes (MODE_CQ): table entry = match / mismatch by byte
 // equality (align.h:96-101), a column of any other letter mismatches every row
-template <class W, int K, bool CKPT, bool COMPACT, bool STRINGS>
+//
+// DIAG: the offset form.  With g = |ge| every value is kept as
+//     H~(i,j) = H(i,j) + (i+j) g - base     E~(i,j) = E'(i,j) + (i+j-1) g - base     F~(i,j) = F'(i,j) + (i+j-1) g - base
+// and the recurrences lose their extension adds:
+//     E~ = max(H~_left, E~_left)   F~ = max(H~_up, F~_up)   H~ = max(H~_diag + (sub - goe + g), E~, F~) + go
+// six operations per cell instead of eight.  The candidates of one maximum all carry the same offset, so every true value is what
+// it was.  Column 0 is H~ = go in every real row (E~: today's sentinel under the same offset); a padding slot above row 1 holds
+// H~ = (i+j) g, a fixpoint of the recurrence under the table entry 0 - goe + g.  Row 0 is no longer the zero a DPP shift brings: lane 0
+// needs H~(0,j) = j g - base (and an F~ that does not beat it), kept in one register that is zero in every other lane and grows
+// by g per step -- the two hand-off moves become DPP adds of it.  (i+j) g outgrows int16, hence `base`: every diag_period steps, at
+// a round boundary and in every lane, busy or not, diag_period * g comes off all state registers, so one wave-uniform base
+// describes the wave.  Whatever goes to memory (score, row m, checkpoints) is converted at the store and keeps today's bits in the
+// lanes that hold rows of the pair.  Domain: sweep_diag_period (capi.hip) -- the spread of i+j across a wave and one period on
+// top of narrow_ok's interval.
+template <class W, int K, bool CKPT, bool COMPACT, bool STRINGS, bool DIAG>
 TR_HD void gotoh_narrow_qp_body(W& w, const DpArgs& a, uint32_t pair_idx) {
   const PairDesc d = a.pairs[pair_idx];
   if (d.flags & PAIR_SKIP) return;
@@ -845,11 +863,15 @@ TR_HD void gotoh_narrow_qp_body(W& w, const DpArgs& a, uint32_t pair_idx) {
 #pragma unroll
   for (int i = 0; i < K; ++i) {
     const uint32_t r = L * K + i + 1 - pad;
-    if (L * K + i < pad) { Hl[i] = 0; El[i] = -goe; }  // padding slots above row 1 reproduce row 0: H = 0 in every column
+    if constexpr (DIAG) {
+      const int32_t rr = (int32_t)(L * K + i + 1) - (int32_t)pad;  // (<= 0: a padding slot, true values H = 0, E' = -goe)
+      if (rr <= 0) { Hl[i] = rr * -ge; El[i] = -goe + (rr - 1) * -ge; }
+      else { Hl[i] = go; El[i] = kNegInf16 + (rr - 1) * -ge; }  // (today's sentinel under the offset: below go wherever narrow_ok holds)
+    } else if (L * K + i < pad) { Hl[i] = 0; El[i] = -goe; }  // padding slots above row 1 reproduce row 0: H = 0 in every column
     else { Hl[i] = edge_value(false, go, ge, (int32_t)r); El[i] = kNegInf16; }
   }
-  int32_t gev = ge, goev = goe;
-  int32_t hext_last = lastlane ? 0 : ge;      // row m: horizontal gaps are free (AlignConfig<true,.>)
+  int32_t gev = ge, goev = DIAG ? go : goe;
+  int32_t hext_last = lastlane ? (DIAG ? -ge : 0) : (DIAG ? 0 : ge);  // row m: horizontal gaps are free (AlignConfig<true,.>)
   int32_t delta_last = lastlane ? -goe : 0;   // ... so E' = max(H - goe, E') there
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("" : "+v"(gev), "+v"(goev), "+v"(hext_last), "+v"(delta_last));  // four live VGPRs for the whole sweep, not re-materialised per step
@@ -879,13 +901,13 @@ TR_HD void gotoh_narrow_qp_body(W& w, const DpArgs& a, uint32_t pair_idx) {
 #pragma unroll
       for (uint32_t b = 0; b < (COMPACT ? 4u : 5u); ++b) {
         const int32_t q = !real ? 0 : STRINGS ? (rch == (uint8_t)"ACGTN"[b] ? a.match : a.mismatch) : onehot_score(pr, b, fmatch, fmis);
-        const int32_t qs = q - goe;
+        const int32_t qs = q - (DIAG ? goe + ge : goe);  // (offset form: sub - goe + |ge|)
         overflow |= (qs > 32767) || (qs < -32768) || (q > 32767) || (q < -32768);
         qabs = imax(qabs, q < 0 ? -q : q);
         const uint32_t row = (rcflag && b < 4u) ? 3u - b : b;  // reverse-complement view: the complement is folded into the table
         qp_tab[qp16_byte<NC>(row, (uint32_t)i, Lc) >> 1] = (int16_t)qs;
       }
-      if (!COMPACT) qp_tab[qp16_byte<NC>(5u, (uint32_t)i, Lc) >> 1] = (int16_t)(((STRINGS && real) ? a.mismatch : 0) - goe);
+      if (!COMPACT) qp_tab[qp16_byte<NC>(5u, (uint32_t)i, Lc) >> 1] = (int16_t)(((STRINGS && real) ? a.mismatch : 0) - (DIAG ? goe + ge : goe));
     }
     if (overflow) flag_error(a.err, 1);
     if (!STRINGS && qabs > a.qlimit) flag_max(a.err, 1, qabs);
@@ -921,12 +943,43 @@ TR_HD void gotoh_narrow_qp_body(W& w, const DpArgs& a, uint32_t pair_idx) {
   // the H received from the strip above: the two registers alternate between "this column's upper neighbour" and "the diagonal"
   const uint32_t row_above = (L * K > pad) ? L * K - pad : 0u;
   int32_t upA = 0, upB = (row_above == 0) ? 0 : edge_value(false, go, ge, (int32_t)row_above);
+  // offset form: the row above lane 0 is row 0 seen from `pad` slots higher, H~ = (t - pad) g - base at step t
+  const int32_t g = -ge;
+  int32_t row0 = 0, row0_step = 0;    // lane 0: that value and its growth per step; zero in every other lane
+  int32_t base = 0;                   // what has been taken off every value so far (wave-uniform)
+  const uint32_t period = DIAG ? a.diag_period : 0u;
+  uint32_t rb_left = period;          // steps until the next re-base (wave-uniform)
+  if constexpr (DIAG) {
+    upB = (L == 0) ? -(int32_t)pad * g : go;
+    row0 = (L == 0) ? (1 - (int32_t)pad) * g : 0;
+    row0_step = (L == 0) ? g : 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(row0_step));
+#endif
+  }
+  // A slot's true H is H~ - (row + column) g + base.  For the lane's first slot on column t - L that is H~ + (base - t g) - lane_rc:
+  // a scalar of the step and one constant of the lane; slot i, and E' / F', are multiples of g away.
+  const int32_t lane_rc = ((int32_t)(L * K + 1) - (int32_t)pad - (int32_t)L) * g;
 
   // `row_m` receives this step's {H, E'} pair of row m (last lane only); the caller stores it
   auto step = [&](auto guard, uint32_t t, QpStrip<K>& q, int32_t& up_cur, const int32_t& diag, uint32_t& row_m) {
     constexpr bool GUARD = decltype(guard)::value;
+    if constexpr (DIAG) {
+      // lane 0 receives row 0: H~(0, t), and an F~ equal to it, which changes no maximum
+#if defined(__HIP_DEVICE_COMPILE__)
+      asm("s_nop 1\n\tv_add_u16_dpp %0, %3, %2 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+          "v_add_u16_dpp %1, %1, %2 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+          "v_add_u16 %2, %2, %4"
+          : "=&v"(up_cur), "+v"(f), "+v"(row0) : "v"(Hl[K - 1]), "v"(row0_step));
+#else
+      up_cur = add16(w.shift_up(Hl[K - 1]), row0);
+      f = add16(w.shift_up(f), row0);
+      row0 = add16(row0, row0_step);
+#endif
+    } else {
     up_cur = w.shift_up(Hl[K - 1]);  // lane 0 receives 0 = H(0, t)
     f = w.shift_up(f);               // ... and F' = 0, which loses against H(0, t) + 0 as -inf would
+    }
     qp_wait6<K>(q);
     const bool active = !GUARD || (uint32_t)(t - 1u - L) < n;
     if (active) {
@@ -934,25 +987,30 @@ TR_HD void gotoh_narrow_qp_body(W& w, const DpArgs& a, uint32_t pair_idx) {
 #pragma unroll
       for (int i = 0; i < K; ++i) sub[i] = q.lo16(i);
       if constexpr (K == 15) {
-        strip_left16<7, true>(Hl + 8, El + 8, sub + 8, Hl[7], gev, hext_last, delta_last);
-        strip_left16<8, false>(Hl, El, sub, diag, gev, hext_last, delta_last);
-        strip_down16<8>(Hl, El, up_cur, f, gev, goev);
-        strip_down16<7>(Hl + 8, El + 8, Hl[7], f, gev, goev);
+        strip_left16<7, true, DIAG>(Hl + 8, El + 8, sub + 8, Hl[7], gev, hext_last, delta_last);
+        strip_left16<8, false, DIAG>(Hl, El, sub, diag, gev, hext_last, delta_last);
+        strip_down16<8, DIAG>(Hl, El, up_cur, f, gev, goev);
+        strip_down16<7, DIAG>(Hl + 8, El + 8, Hl[7], f, gev, goev);
       } else if constexpr (K == 16) {
-        strip_left16<8, true>(Hl + 8, El + 8, sub + 8, Hl[7], gev, hext_last, delta_last);
-        strip_left16<8, false>(Hl, El, sub, diag, gev, hext_last, delta_last);
-        strip_down16<8>(Hl, El, up_cur, f, gev, goev);
-        strip_down16<8>(Hl + 8, El + 8, Hl[7], f, gev, goev);
+        strip_left16<8, true, DIAG>(Hl + 8, El + 8, sub + 8, Hl[7], gev, hext_last, delta_last);
+        strip_left16<8, false, DIAG>(Hl, El, sub, diag, gev, hext_last, delta_last);
+        strip_down16<8, DIAG>(Hl, El, up_cur, f, gev, goev);
+        strip_down16<8, DIAG>(Hl + 8, El + 8, Hl[7], f, gev, goev);
       } else {
 #pragma unroll
         for (int i = K - 1; i >= 0; --i) {
           const int32_t dg = i == 0 ? diag : Hl[i - 1];
           if (i == K - 1) cell_left16_last(Hl[i], El[i], hext_last, dg, sub[i], delta_last);
+          else if constexpr (DIAG) cell_left16d(Hl[i], El[i], dg, sub[i]);
           else cell_left16(Hl[i], El[i], gev, dg, sub[i]);
         }
         int32_t uh = up_cur;
 #pragma unroll
-        for (int i = 0; i < K; ++i) { cell_down16(Hl[i], El[i], uh, f, gev, goev); uh = Hl[i]; }
+        for (int i = 0; i < K; ++i) {
+          if constexpr (DIAG) cell_down16d(Hl[i], El[i], uh, f, goev);
+          else cell_down16(Hl[i], El[i], uh, f, gev, goev);
+          uh = Hl[i];
+        }
       }
     }
     // a sweep that keeps nothing (the likely losing strand of a checkpointed launch) skips the row-m pack and the checkpoint test
@@ -960,7 +1018,10 @@ TR_HD void gotoh_narrow_qp_body(W& w, const DpArgs& a, uint32_t pair_idx) {
     if (CKPT && keep) {
       TRACY_KEEP_BRANCH();
       if (active) {
-        row_m = ((uint32_t)El[K - 1] << 16) | ((uint32_t)Hl[K - 1] & 0xffffu);
+        if constexpr (DIAG) {  // (an active lane: its column is t - L)
+          const int32_t oh = (base - ((int32_t)t + K - 1) * g) - lane_rc;
+          row_m = ((uint32_t)(El[K - 1] + oh + g) << 16) | ((uint32_t)(Hl[K - 1] + oh) & 0xffffu);
+        } else row_m = ((uint32_t)El[K - 1] << 16) | ((uint32_t)Hl[K - 1] & 0xffffu);
         if (GUARD && lastlane)  // ramp phases: row m column by column (the steady state stores four columns at once)
           *reinterpret_cast<uint32_t*>(lrb + (uint32_t)(4 * (int32_t)t + lr_lane)) = row_m;
       }
@@ -968,9 +1029,28 @@ TR_HD void gotoh_narrow_qp_body(W& w, const DpArgs& a, uint32_t pair_idx) {
         ck_left = B;
         int32_t* ck = ck_next;
         ck_next += ckpt_fields_qp16(K) * 64u;
+        if constexpr (DIAG) {
+          // today's record: a lane off the columns holds its column-0 (or column-n) state, an F' of 0 and, in lane 0, an H of 0 from above
+          // (the state registers are converted in place, stored as the other form stores them, and converted back: no second set of them)
+          const int32_t c = (int32_t)t - (int32_t)L, ce = c < 0 ? 0 : c > (int32_t)n ? (int32_t)n : c;
+          const bool on = c >= 1 && c <= (int32_t)n;
+          const int32_t o0 = (base - (int32_t)t * g) - lane_rc + (c - ce) * g;  // (a lane off the columns: its state is that of column ce)
+          int32_t oh = o0, oe = o0 + g;
+#pragma unroll
+          for (int i = 0; i < K; ++i) {
+            add16_to(Hl[i], oh); add16_to(El[i], oe);
+            ck[(uint32_t)i * 64u] = (int32_t)(((uint32_t)El[i] << 16) | ((uint32_t)Hl[i] & 0xffffu));
+            add16_to(Hl[i], -oh); add16_to(El[i], -oe);
+            oh -= g; oe -= g;
+          }
+          const int32_t fv = on ? f + o0 - (K - 2) * g : 0;             // F' of the strip's last row: slot K - 1, one g up
+          const int32_t uv = L == 0 ? 0 : up_cur + o0 + g;              // H of the row above the strip: "slot -1"
+          ck[(uint32_t)K * 64u] = (int32_t)(((uint32_t)fv << 16) | ((uint32_t)uv & 0xffffu));
+        } else {
 #pragma unroll
         for (int i = 0; i < K; ++i) ck[(uint32_t)i * 64u] = (int32_t)(((uint32_t)El[i] << 16) | ((uint32_t)Hl[i] & 0xffffu));
         ck[(uint32_t)K * 64u] = (int32_t)(((uint32_t)f << 16) | ((uint32_t)up_cur & 0xffffu));
+        }
       }
     }
   };
@@ -1055,12 +1135,25 @@ TR_HD void gotoh_narrow_qp_body(W& w, const DpArgs& a, uint32_t pair_idx) {
     cw_cur = cw_next;
     cw_next = cw_pend;
     t += 4;
+    if constexpr (DIAG) {
+      if ((rb_left -= 4u) == 0u) {  // re-base: every lane, busy or not, so that one base describes the wave
+        rb_left = period;
+        const int32_t off = -(int32_t)period * g;
+        base -= off;
+#pragma unroll
+        for (int i = 0; i < K; ++i) { add16_to(Hl[i], off); add16_to(El[i], off); }
+        add16_to(f, off);
+        add16_to(upA, off);
+        add16_to(upB, off);
+        add16_to(row0, L == 0 ? off : 0);
+      }
+    }
   };
   while (t < lanes_used && t <= t_end) four_steps(Guarded{});  // ramp-up
   while (t + 3 <= n) four_steps(Free{});                       // every used lane is on a column of the reference
   while (t <= t_end) four_steps(Guarded{});                    // ramp-down (steps past t_end find no lane on a column)
 
-  if (a.scores && lastlane) a.scores[d.out] = sext16(Hl[K - 1]);
+  if (a.scores && lastlane) a.scores[d.out] = sext16(DIAG ? Hl[K - 1] - (int32_t)(m + n) * g + base : Hl[K - 1]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1263,7 +1356,11 @@ constexpr uint32_t kFrontRows = (uint32_t)kFrontPrefixLanes * kFrontPrefixK;
 // same pairs and every group of lanes works on its pair in the form the reference calls for (DpArgs::special_blocks)
 // STRINGS: the rows are characters (gotoh(allele, window) of `tracy decompose`, indigo.h:359): match / mismatch by byte equality
 // (align.h:96-101) against the codes A C G T N, mismatch against '-' / any other letter -- the table of the MODE_CQ sweeps
-template <class W, int K, int GL, bool COMPACT = false, bool STRINGS = false>
+// DIAG: the offset form of the cells (gotoh_narrow_qp_body): H~ = H + (i+j) g - base, six operations per cell, DpArgs::diag_period steps
+// between re-bases.  Row 0 reaches the first lane of every group through one register (j g - base there, zero elsewhere) that the
+// hand-off adds; the kept row and the reported bound are converted where they are formed -- the packed add that forms {H + goe, F}
+// takes the step's offsets along, and one packed maximum of the converted pair stands for the two running maxima.
+template <class W, int K, int GL, bool COMPACT = false, bool STRINGS = false, bool DIAG = false>
 TR_HD void gotoh_prefix_body(W& w, const DpArgs& a, uint32_t group_base, uint32_t npairs) {
   static_assert(64 % GL == 0, "whole groups per wave");
   constexpr uint32_t NCODES = COMPACT ? 4u : 5u;
@@ -1319,16 +1416,28 @@ TR_HD void gotoh_prefix_body(W& w, const DpArgs& a, uint32_t group_base, uint32_
   int32_t Hl[K], El[K];
 #pragma unroll
   for (int i = 0; i < K; ++i) {
-    Hl[i] = edge_value(false, go, ge, (int32_t)(Lg * K + i + 1));
-    El[i] = kNegInf16;
+    Hl[i] = DIAG ? go : edge_value(false, go, ge, (int32_t)(Lg * K + i + 1));  // (offset form: H~(r, 0) = go, and E~ may start equal to it)
+    El[i] = DIAG ? go : kNegInf16;
   }
-  int32_t gev = ge, goev = goe;
+  int32_t gev = ge, goev = DIAG ? go : goe;
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("" : "+v"(gev), "+v"(goev));  // live VGPRs for the whole sweep, not re-materialised per step
 #endif
   const uint32_t row_above = Lg * K;
-  int32_t upA = 0, upB = (row_above == 0) ? 0 : edge_value(false, go, ge, (int32_t)row_above);
+  int32_t upA = 0, upB = (row_above == 0) ? 0 : DIAG ? go : edge_value(false, go, ge, (int32_t)row_above);
   int32_t f = 0;
+  // offset form: row 0 as the first lane of a group sees it at step t, H~(0, t) = t g - base, and its growth per step (zero in the other lanes)
+  const int32_t g = -ge;
+  int32_t row0 = (DIAG && Lg == 0) ? g : 0, row0_step = row0;
+  const uint32_t period = DIAG ? a.diag_period : 0u;
+  uint32_t rb_left = period;  // steps until the next re-base (wave-uniform)
+  // what turns {F~, H~} of row R at this step's column t - Lg into {F, H + goe}: goe + base - (R + t - Lg) g, one g more for F~
+  const int32_t conv0 = goe - ((int32_t)R - (int32_t)Lg) * g;
+  uint32_t conv2 = pk16(conv0 + g, conv0);
+  const uint32_t conv_step = pk16(-g, -g);
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (DIAG) asm volatile("" : "+v"(row0_step));
+#endif
   const bool rcflag = (d.flags & PAIR_A2_REVCOMP) != 0;
 
   // query profile (qp16_byte): entry = score - (go+ge); the complement of a reverse-complement view is folded into the table
@@ -1352,14 +1461,14 @@ TR_HD void gotoh_prefix_body(W& w, const DpArgs& a, uint32_t group_base, uint32_
       for (uint32_t b = 0; b < NCODES; ++b) {
         int32_t q = 0;
         if (real) q = STRINGS ? (rch == (uint8_t)"ACGTN"[b] ? a.match : a.mismatch) : onehot_score(pr, b, fmatch, fmis);
-        const int32_t qs = q - goe;
+        const int32_t qs = q - (DIAG ? goe + ge : goe);  // (offset form: sub - goe + |ge|)
         overflow |= (qs > 32767) || (qs < -32768) || (q > 32767) || (q < -32768);
         qabs = imax(qabs, q < 0 ? -q : q);
         const uint32_t row = (rcflag && b < 4u) ? 3u - b : b;
         qp_tab[qp16_byte<NC>(row, (uint32_t)i, Lc) >> 1] = (int16_t)qs;
       }
       // '-' / any other letter: an all-zero profile column scores 0, a string column that no row can equal mismatches
-      if (!COMPACT) qp_tab[qp16_byte<NC>(5u, (uint32_t)i, Lc) >> 1] = (int16_t)((STRINGS ? a.mismatch : 0) - goe);
+      if (!COMPACT) qp_tab[qp16_byte<NC>(5u, (uint32_t)i, Lc) >> 1] = (int16_t)((STRINGS ? a.mismatch : 0) - (DIAG ? goe + ge : goe));
     }
     if (overflow) flag_error(a.err, 1);
     if (!STRINGS && qabs > a.qlimit) flag_max(a.err, 1, qabs);
@@ -1417,12 +1526,32 @@ TR_HD void gotoh_prefix_body(W& w, const DpArgs& a, uint32_t group_base, uint32_
   // running maxima of H and F' of row R, and the row itself (PAIR_KEEP_ROW): the last slot of the group's last lane
   const bool lastlane = Lg == GL - 1;
   int32_t mx_h = edge_value(false, go, ge, (int32_t)R), mx_f = kNegInf16;
+  uint32_t mx2 = pk16(kNegInf16, mx_h + goe);  // offset form: the running maximum of the kept pairs {F, H + goe}
   uint32_t* keep_row = (valid && lastlane && (d.flags & PAIR_KEEP_ROW) && a.lastrow) ? reinterpret_cast<uint32_t*>(a.lastrow + d.lastrow_off) : nullptr;
   const uint32_t goe2 = ((uint32_t)goe << 16) | ((uint32_t)goe & 0xffffu);
   // the lane above: inside a row of sixteen lanes (a group is a row, or half of one whose first lane is masked)
   const int32_t gmask = (GL < 16 && Lg == 0) ? 0 : -1;
   // (one DPP instruction each: the mask rides in the shift -- v_and_b32_dpp; a VALU write needs two wait states before a DPP read)
   auto shift_group = [&](int32_t h, int32_t fv, int32_t& h_up, int32_t& f_up) {
+    if constexpr (DIAG) {  // ... and a group's first lane receives row 0: H~(0, t), and an F~ equal to it, which changes no maximum
+#if defined(__HIP_DEVICE_COMPILE__)
+      if constexpr (GL == 16)
+        asm("s_nop 1\n\tv_add_u16_dpp %0, %3, %2 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+            "v_add_u16_dpp %1, %1, %2 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+            "v_add_u16 %2, %2, %4"
+            : "=&v"(h_up), "+v"(f_up), "+v"(row0) : "v"(h), "v"(row0_step));
+      else
+        asm("s_nop 1\n\tv_and_b32_dpp %0, %3, %5 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+            "v_and_b32_dpp %1, %1, %5 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+            "v_add_u16 %0, %0, %2\n\tv_add_u16 %1, %1, %2\n\tv_add_u16 %2, %2, %4"
+            : "=&v"(h_up), "+v"(f_up), "+v"(row0) : "v"(h), "v"(row0_step), "v"(gmask));
+#else
+      h_up = add16(w.shift_up_row(h) & gmask, row0);
+      f_up = add16(w.shift_up_row(fv) & gmask, row0);
+      row0 = add16(row0, row0_step);
+#endif
+      return;
+    }
 #if defined(__HIP_DEVICE_COMPILE__)
     asm("s_nop 1\n\tv_and_b32_dpp %0, %2, %4 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
         "v_and_b32_dpp %1, %3, %4 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
@@ -1436,7 +1565,12 @@ TR_HD void gotoh_prefix_body(W& w, const DpArgs& a, uint32_t group_base, uint32_
   // `kept`: {H + goe, F} of row R at this step's column, the format the stages below the kept row read (front.h, band16.h CONT)
   auto step = [&](auto guard, uint32_t t, QpStrip<K>& q, int32_t& up_cur, const int32_t& diag, uint32_t& kept) {
     constexpr bool GUARD = decltype(guard)::value;
+    if constexpr (DIAG) {
+      shift_group(Hl[K - 1], f, up_cur, f);
+      conv2 = pk_add16(conv2, conv_step);  // (every lane, on a column or not: the offsets follow the step)
+    } else {
     shift_group(Hl[K - 1], f, up_cur, f);
+    }
     qp_wait6<K>(q);
     const bool active = !GUARD || (uint32_t)(t - 1u - Lg) < n;
     if (active) {
@@ -1444,25 +1578,41 @@ TR_HD void gotoh_prefix_body(W& w, const DpArgs& a, uint32_t group_base, uint32_
 #pragma unroll
       for (int i = 0; i < K; ++i) sub[i] = q.lo16(i);
       if constexpr (K == 8) {
-        strip_left16<8, false>(Hl, El, sub, diag, gev, gev, 0);
-        strip_down16<8>(Hl, El, up_cur, f, gev, goev);
+        strip_left16<8, false, DIAG>(Hl, El, sub, diag, gev, gev, 0);
+        strip_down16<8, DIAG>(Hl, El, up_cur, f, gev, goev);
       } else if constexpr (K == 16) {
-        strip_left16<8, false>(Hl + 8, El + 8, sub + 8, Hl[7], gev, gev, 0);
-        strip_left16<8, false>(Hl, El, sub, diag, gev, gev, 0);
-        strip_down16<8>(Hl, El, up_cur, f, gev, goev);
-        strip_down16<8>(Hl + 8, El + 8, Hl[7], f, gev, goev);
+        strip_left16<8, false, DIAG>(Hl + 8, El + 8, sub + 8, Hl[7], gev, gev, 0);
+        strip_left16<8, false, DIAG>(Hl, El, sub, diag, gev, gev, 0);
+        strip_down16<8, DIAG>(Hl, El, up_cur, f, gev, goev);
+        strip_down16<8, DIAG>(Hl + 8, El + 8, Hl[7], f, gev, goev);
       } else if constexpr (K == 15) {
-        strip_left16<7, false>(Hl + 8, El + 8, sub + 8, Hl[7], gev, gev, 0);
-        strip_left16<8, false>(Hl, El, sub, diag, gev, gev, 0);
-        strip_down16<8>(Hl, El, up_cur, f, gev, goev);
-        strip_down16<7>(Hl + 8, El + 8, Hl[7], f, gev, goev);
+        strip_left16<7, false, DIAG>(Hl + 8, El + 8, sub + 8, Hl[7], gev, gev, 0);
+        strip_left16<8, false, DIAG>(Hl, El, sub, diag, gev, gev, 0);
+        strip_down16<8, DIAG>(Hl, El, up_cur, f, gev, goev);
+        strip_down16<7, DIAG>(Hl + 8, El + 8, Hl[7], f, gev, goev);
       } else {
 #pragma unroll
-        for (int i = K - 1; i >= 0; --i) cell_left16(Hl[i], El[i], gev, i == 0 ? diag : Hl[i - 1], sub[i]);
+        for (int i = K - 1; i >= 0; --i) {
+          if constexpr (DIAG) cell_left16d(Hl[i], El[i], i == 0 ? diag : Hl[i - 1], sub[i]);
+          else cell_left16(Hl[i], El[i], gev, i == 0 ? diag : Hl[i - 1], sub[i]);
+        }
         int32_t uh = up_cur;
 #pragma unroll
-        for (int i = 0; i < K; ++i) { cell_down16(Hl[i], El[i], uh, f, gev, goev); uh = Hl[i]; }
+        for (int i = 0; i < K; ++i) {
+          if constexpr (DIAG) cell_down16d(Hl[i], El[i], uh, f, goev);
+          else cell_down16(Hl[i], El[i], uh, f, gev, goev);
+          uh = Hl[i];
+        }
       }
+      if constexpr (DIAG) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm("v_perm_b32 %0, %2, %3, %4\n\tv_pk_add_u16 %0, %0, %5\n\tv_pk_max_i16 %1, %1, %0"
+            : "=&v"(kept), "+v"(mx2) : "v"(f), "v"(Hl[K - 1]), "s"(0x05040100u), "v"(conv2));
+#else
+        kept = pk_add16(pk16(f, Hl[K - 1]), conv2);
+        mx2 = pk_max16(mx2, kept);
+#endif
+      } else {
       mx_h = max16(mx_h, Hl[K - 1]);
       mx_f = max16(mx_f, f);
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1470,6 +1620,7 @@ TR_HD void gotoh_prefix_body(W& w, const DpArgs& a, uint32_t group_base, uint32_
 #else
       kept = ((uint32_t)(Hl[K - 1] + goe) & 0xffffu) | ((uint32_t)(f + goe) << 16);
 #endif
+      }
       if (GUARD && keep_row) keep_row[t - Lg] = kept;  // ramp phases: column by column (the steady state stores four at once)
     }
   };
@@ -1509,6 +1660,19 @@ TR_HD void gotoh_prefix_body(W& w, const DpArgs& a, uint32_t group_base, uint32_
     cw_cur = cw_next;
     cw_next = cw_pend;
     t += 4;
+    if constexpr (DIAG) {
+      if ((rb_left -= 4u) == 0u) {  // re-base: every lane of every group, so that one base describes the wave
+        rb_left = period;
+        const int32_t off = -(int32_t)period * g;
+#pragma unroll
+        for (int i = 0; i < K; ++i) { add16_to(Hl[i], off); add16_to(El[i], off); }
+        add16_to(f, off);
+        add16_to(upA, off);
+        add16_to(upB, off);
+        add16_to(row0, Lg == 0 ? off : 0);
+        conv2 = pk_add16(conv2, pk16(-off, -off));
+      }
+    }
   };
   while (t < (uint32_t)GL && t <= t_end) four_steps(Guarded{});  // ramp-up
   if (nmin != 0xffffffffu && t + 3 <= nmin) {
@@ -1517,7 +1681,8 @@ TR_HD void gotoh_prefix_body(W& w, const DpArgs& a, uint32_t group_base, uint32_
   }
   while (t <= t_end) four_steps(Guarded{});  // ramp-down: the windows end one after the other
   if (valid && lastlane && a.scores) {
-    const int32_t h = sext16(mx_h), fm = sext16(mx_f) + goe;
+    const int32_t h = DIAG ? sext16((int32_t)(mx2 & 0xffffu)) - goe : sext16(mx_h);
+    const int32_t fm = DIAG ? sext16((int32_t)(mx2 >> 16)) : sext16(mx_f) + goe;
     a.scores[d.out] = h > fm ? h : fm;
   }
 }

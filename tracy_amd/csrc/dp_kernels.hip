@@ -61,10 +61,11 @@ __device__ __forceinline__ void walk_own_pair(DeviceWave& w, const DpArgs& a, in
   gotoh_walk_wave<DeviceWave>(w, wa, blockIdx.x);
 }
 
-template <int K, int MODE, bool TRACE, bool NARROW = false, bool COMPACT = false>
+// DIAG (the 16-bit query-profile sweeps, K = 15 / 16): the offset form of the cells, DpArgs::diag_period (sweep_uses_diag below)
+template <int K, int MODE, bool TRACE, bool NARROW = false, bool COMPACT = false, bool DIAG = false>
 __global__ __launch_bounds__(64) void gotoh_kernel(DpArgs a) {
   DeviceWave w;
-  gotoh_body<DeviceWave, K, MODE, TRACE, NARROW, false, 0, COMPACT>(w, a, blockIdx.x);
+  gotoh_body<DeviceWave, K, MODE, TRACE, NARROW, false, 0, COMPACT, DIAG>(w, a, blockIdx.x);
   if constexpr (TRACE) walk_own_pair(w, a, K);
 }
 // profile x profile with the number of substitution terms fixed per launch (NT = 4: PAIR_ROW4_ZERO pairs, 5: the rest): one
@@ -78,10 +79,10 @@ __global__ __launch_bounds__(64) void gotoh_prof_kernel(DpArgs a) {
 }
 
 // checkpointed score pass (wavefront checkpoints + last row) and the band traceback that consumes them
-template <int K, int MODE, bool NARROW, bool COMPACT = false>
+template <int K, int MODE, bool NARROW, bool COMPACT = false, bool DIAG = false>
 __global__ __launch_bounds__(64) void gotoh_ckpt_kernel(DpArgs a) {
   DeviceWave w;
-  gotoh_body<DeviceWave, K, MODE, false, NARROW, true, 0, COMPACT>(w, a, blockIdx.x);
+  gotoh_body<DeviceWave, K, MODE, false, NARROW, true, 0, COMPACT, DIAG>(w, a, blockIdx.x);
 }
 // origin-tracking sweep (string x string): score + the two ends of the alignment, no traceback words
 template <int K, int TABLE = 0, int NC = 6>
@@ -97,17 +98,17 @@ __global__ __launch_bounds__(64) void gotoh_origin_kernel(DpArgs a) {
 #else
 #define TRACY_SWEEP_ATTR
 #endif
-template <int K, int GL, bool COMPACT = false, int KP = K>
+template <int K, int GL, bool COMPACT = false, int KP = K, bool DIAG = false>
 __global__ __launch_bounds__(64) TRACY_SWEEP_ATTR void gotoh_ckpt_prefix_kernel(DpArgs full, uint32_t nfull, DpArgs pre, uint32_t npre) {
   DeviceWave w;
   const uint32_t ngroups = (npre + 64u / GL - 1u) / (64u / GL);
-  if (blockIdx.x < ngroups) gotoh_prefix_body<DeviceWave, KP, GL, COMPACT>(w, pre, blockIdx.x * (64u / GL), npre);
+  if (blockIdx.x < ngroups) gotoh_prefix_body<DeviceWave, KP, GL, COMPACT, false, DIAG>(w, pre, blockIdx.x * (64u / GL), npre);
   else {
 #ifdef TRACY_SWEEP_STAGGER
     // (experiment: the waves of a launch's first round start within microseconds of each other and run the same instruction stream)
     for (uint32_t h = (blockIdx.x * 2654435761u) >> 27; h; --h) __builtin_amdgcn_s_sleep(TRACY_SWEEP_STAGGER);
 #endif
-    gotoh_body<DeviceWave, K, MODE_QP, false, true, true, 0, COMPACT>(w, full, blockIdx.x - ngroups);
+    gotoh_body<DeviceWave, K, MODE_QP, false, true, true, 0, COMPACT, DIAG>(w, full, blockIdx.x - ngroups);
   }
 }
 // prefix bound of the semiglobal score: GL lanes per pair, 64/GL pairs per workgroup
@@ -301,8 +302,27 @@ __global__ __launch_bounds__(64) void alignment_rows_kernel(RowsArgs a) {
 }
 
 // ---- launchers ---------------------------------------------------------------------------------
+// the offset form of the 16-bit query-profile sweeps exists for the strip heights the strips are written for
+template <int K>
+static bool sweep_uses_diag(const DpArgs& a) { return (K == 15 || K == 16) && a.diag_period != 0; }
+// a launch of sweeps and prefix groups is one kernel, so one form: the offset form where every body that has work was given a period
+// (the callers see to it that a launch's two periods are both set or both zero: launch_diag_periods in capi.hip)
+template <int K>
+static bool combo_uses_diag(const DpArgs& full, uint32_t nfull, const DpArgs& pre, uint32_t npre) {
+  if ((K != 15 && K != 16) || nfull + npre == 0) return false;
+  return (nfull == 0 || full.diag_period != 0) && (npre == 0 || pre.diag_period != 0);
+}
+
 template <int K, int MODE, bool TRACE, bool NARROW = false>
 static hipError_t launch_gotoh_t(const DpArgs& a, uint32_t npairs, hipStream_t s) {
+  if constexpr (NARROW && MODE == MODE_QP && !TRACE && (K == 15 || K == 16)) {
+    if (sweep_uses_diag<K>(a)) {
+      if (a.special_blocks)
+        hipLaunchKernelGGL((gotoh_kernel<K, MODE, TRACE, true, true, true>), dim3(npairs), dim3(64), lds_bytes_sweep16(K, true) + lds_pad(), s, a);
+      hipLaunchKernelGGL((gotoh_kernel<K, MODE, TRACE, true, false, true>), dim3(npairs), dim3(64), lds_bytes_sweep16(K, false), s, a);
+      return hipGetLastError();
+    }
+  }
   if constexpr (NARROW && MODE == MODE_QP) {
     // the 16-bit query-profile sweep: both forms over the same pairs, every pair is swept by the one its reference calls for
     // (a workgroup of the other form leaves at once); without the block map only the six-code form knows what to do
@@ -418,6 +438,14 @@ template <int MODE>
 static hipError_t launch_ckpt_m(int K, bool narrow, const DpArgs& a, uint32_t npairs, hipStream_t s) {
 #define TRACY_CK(KK)                                                                                                   \
   case KK:                                                                                                              \
+    if constexpr (MODE == MODE_QP && (KK == 15 || KK == 16)) {                                                          \
+      if (narrow && sweep_uses_diag<KK>(a)) {                                                                           \
+        if (a.special_blocks)                                                                                           \
+          hipLaunchKernelGGL((gotoh_ckpt_kernel<KK, MODE, true, true, true>), dim3(npairs), dim3(64), lds_bytes_sweep16(KK, true) + lds_pad(), s, a); \
+        hipLaunchKernelGGL((gotoh_ckpt_kernel<KK, MODE, true, false, true>), dim3(npairs), dim3(64), lds_bytes_sweep16(KK, false), s, a);             \
+        return hipGetLastError();                                                                                       \
+      }                                                                                                                 \
+    }                                                                                                                   \
     if (narrow && qp_like(MODE)) {                                                                                      \
       if (a.special_blocks)                                                                                             \
         hipLaunchKernelGGL((gotoh_ckpt_kernel<KK, MODE, true, true>), dim3(npairs), dim3(64), lds_bytes_sweep16(KK, true) + lds_pad(), s, a); \
@@ -523,6 +551,14 @@ hipError_t launch_gotoh_ckpt_prefix(int K, const DpArgs& full, uint32_t nfull, c
   // both forms over the same sweeps and prefix groups: each is worked on in the form its reference calls for
 #define TRACY_COMBO_CASE(KK)                                                                                            \
   case KK:                                                                                                              \
+    if constexpr (KK == 15 || KK == 16) {                                                                               \
+      if (combo_uses_diag<KK>(full, nfull, pre, npre)) {                                                                \
+        if (full.special_blocks)                                                                                        \
+          hipLaunchKernelGGL((gotoh_ckpt_prefix_kernel<KK, GL, true, KK, true>), grid, dim3(64), lds_combo(KK, true), s, full, nfull, pre, npre); \
+        hipLaunchKernelGGL((gotoh_ckpt_prefix_kernel<KK, GL, false, KK, true>), grid, dim3(64), lds_combo(KK, false), s, full, nfull, pre, npre); \
+        break;                                                                                                          \
+      }                                                                                                                 \
+    }                                                                                                                   \
     if (full.special_blocks) {                                                                                          \
       hipLaunchKernelGGL((gotoh_ckpt_prefix_kernel<KK, GL, true>), grid, dim3(64), lds_combo(KK, true), s, full, nfull, pre, npre); \
       hipLaunchKernelGGL((gotoh_ckpt_prefix_kernel<KK, GL, false>), grid, dim3(64), lds_combo(KK, false), s, full, nfull, pre, npre); \
@@ -557,6 +593,14 @@ static hipError_t launch_gotoh_ckpt_front_t(int K, const DpArgs& full, uint32_t 
   };
 #define TRACY_FRONT_CASE(KK)                                                                                            \
   case KK:                                                                                                              \
+    if constexpr (KK == 15 || KK == 16) {                                                                               \
+      if (combo_uses_diag<KK>(full, nfull, pre, npre)) {                                                                \
+        if (full.special_blocks)                                                                                        \
+          hipLaunchKernelGGL((gotoh_ckpt_prefix_kernel<KK, GL, true, KP, true>), grid, dim3(64), lds(KK, true), s, full, nfull, pre, npre); \
+        hipLaunchKernelGGL((gotoh_ckpt_prefix_kernel<KK, GL, false, KP, true>), grid, dim3(64), lds(KK, false), s, full, nfull, pre, npre); \
+        break;                                                                                                          \
+      }                                                                                                                 \
+    }                                                                                                                   \
     if (full.special_blocks) {                                                                                          \
       /* (the six-code form usually has nothing to do -- references of A C G T --, but its 12 KB workgroups find no room while the   */ \
       /* four-code form's 7.5 KB workgroups fill the CUs: it goes last, where the device drains; first was measured and waits as long) */ \

@@ -222,6 +222,14 @@ TR_HD int32_t add16(int32_t a, int32_t b) {
   return (int32_t)(uint16_t)((uint32_t)a + (uint32_t)b);
 #endif
 }
+// x += y in place (a tied operand: no second register for the result)
+TR_HD void add16_to(int32_t& x, int32_t y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("v_add_u16 %0, %0, %1" : "+v"(x) : "v"(y));
+#else
+  x = (int32_t)(uint16_t)((uint32_t)x + (uint32_t)y);
+#endif
+}
 TR_HD int32_t max16(int32_t a, int32_t b) {
 #if defined(__HIP_DEVICE_COMPILE__)
   int32_t d;
@@ -233,6 +241,27 @@ TR_HD int32_t max16(int32_t a, int32_t b) {
 #endif
 }
 TR_HD int32_t sext16(int32_t a) { return (int32_t)(int16_t)(uint16_t)a; }
+
+// two int16 lanes in one register: sums / maxima of the halves (v_pk_add_u16, v_pk_max_i16)
+TR_HD uint32_t pk16(int32_t hi, int32_t lo) { return ((uint32_t)hi << 16) | ((uint32_t)lo & 0xffffu); }
+TR_HD uint32_t pk_add16(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint32_t d;
+  asm("v_pk_add_u16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+  return d;
+#else
+  return pk16((int32_t)((a >> 16) + (b >> 16)), (int32_t)((a & 0xffffu) + (b & 0xffffu)));
+#endif
+}
+TR_HD uint32_t pk_max16(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  uint32_t d;
+  asm("v_pk_max_i16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+  return d;
+#else
+  return pk16(max16((int32_t)(a >> 16), (int32_t)(b >> 16)), max16((int32_t)(a & 0xffffu), (int32_t)(b & 0xffffu)));
+#endif
+}
 
 // max(a, b + c) in one asm statement (see chain16)
 TR_HD int32_t maxadd16(int32_t a, int32_t b, int32_t c) {
@@ -323,6 +352,28 @@ TR_HD void cell_down16(int32_t& hl, int32_t el, int32_t up_hg, int32_t& up_f, in
 #endif
 }
 
+// The same two cells on diagonal-offset values (dp_kernels.h gotoh_narrow_qp_body, DIAG): every value carries (row + column) * |ge|
+// minus a running base, so an extension is the value itself and the two extension adds are gone.  `go` closes the cell: (go+ge) + |ge|.
+//   cell_left16d:  E = max(H, E);  H <- H(row above, previous column) + sub          (2 ops; row m keeps cell_left16_last)
+//   cell_down16d:  f = max(up, f);  H <- max(max(H, E), f) + go                       (4 ops)
+TR_HD void cell_left16d(int32_t& hl, int32_t& el, int32_t diag_h, int32_t sub) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("v_max_i16 %1, %0, %1\n\tv_add_u16 %0, %2, %3" : "+v"(hl), "+v"(el) : "v"(diag_h), "v"(sub));
+#else
+  el = max16(hl, el);
+  hl = add16(diag_h, sub);
+#endif
+}
+TR_HD void cell_down16d(int32_t& hl, int32_t el, int32_t up_h, int32_t& up_f, int32_t go) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("v_max_i16 %0, %0, %2\n\tv_max_i16 %1, %3, %1\n\tv_max_i16 %0, %0, %1\n\tv_add_u16 %0, %0, %4"
+      : "+v"(hl), "+v"(up_f) : "v"(el), "v"(up_h), "v"(go));
+#else
+  up_f = max16(up_h, up_f);
+  hl = add16(max16(max16(hl, el), up_f), go);
+#endif
+}
+
 // ---- whole strips in a few asm statements (the 16-bit query-profile sweep, dp_kernels.h gotoh_narrow_qp_body) ----------------
 // The compiler cannot see what an asm statement writes and puts an s_nop between dependent statements; with one statement
 // per cell that is ~16 wasted issue cycles per step.  These helpers run N cells per statement (operand limit: 30).
@@ -331,9 +382,15 @@ TR_HD void cell_down16(int32_t& hl, int32_t el, int32_t up_hg, int32_t& up_f, in
 //     dg_in = that H for slot 0 of the chunk.  LAST: slot N-1 is the strip's last slot -- it uses its own extension cost
 //     hext_last and first adds delta_last to H (row m: free horizontal gaps, dp_kernels.h).
 //   strip_down16<N>:  top-down:  f <- max(up, f + vext);  H <- max(max(H, E), f) + goe;  up <- H.
-template <int N, bool LAST>
+// DIAG: the cells of the offset form (cell_left16d / cell_down16d): no extension add; `hext` is not read, `goe` is the closing go.
+template <int N, bool LAST, bool DIAG = false>
 TR_HD void strip_left16(int32_t* hl, int32_t* el, const int32_t* sub, int32_t dg_in, int32_t hext, int32_t hext_last, int32_t delta_last) {
 #if defined(__HIP_DEVICE_COMPILE__)
+#define TR_LCELL_D(i, dg) "v_max_i16 %[e" #i "], %[h" #i "], %[e" #i "]\n\tv_add_u16 %[h" #i "], %[" dg "], %[s" #i "]\n\t"
+#define TR_LIN8_D [s0] "v"(sub[0]), [s1] "v"(sub[1]), [s2] "v"(sub[2]), [s3] "v"(sub[3]), [s4] "v"(sub[4]), [s5] "v"(sub[5]), [s6] "v"(sub[6]), [s7] "v"(sub[7]), \
+                  [dg] "v"(dg_in)
+#define TR_LIN7_D [s0] "v"(sub[0]), [s1] "v"(sub[1]), [s2] "v"(sub[2]), [s3] "v"(sub[3]), [s4] "v"(sub[4]), [s5] "v"(sub[5]), [s6] "v"(sub[6]), \
+                  [dg] "v"(dg_in)
 #define TR_LCELL(i, dg) "v_add_u16 %[e" #i "], %[e" #i "], %[hx]\n\tv_max_i16 %[e" #i "], %[h" #i "], %[e" #i "]\n\tv_add_u16 %[h" #i "], %[" dg "], %[s" #i "]\n\t"
 #define TR_LCELL_LAST(i, dg) "v_add_u16 %[h" #i "], %[h" #i "], %[dl]\n\tv_add_u16 %[e" #i "], %[e" #i "], %[hl]\n\tv_max_i16 %[e" #i "], %[h" #i "], %[e" #i "]\n\tv_add_u16 %[h" #i "], %[" dg "], %[s" #i "]\n\t"
 #define TR_LOPS8 [h0] "+v"(hl[0]), [h1] "+v"(hl[1]), [h2] "+v"(hl[2]), [h3] "+v"(hl[3]), [h4] "+v"(hl[4]), [h5] "+v"(hl[5]), [h6] "+v"(hl[6]), [h7] "+v"(hl[7]), \
@@ -345,7 +402,19 @@ TR_HD void strip_left16(int32_t* hl, int32_t* el, const int32_t* sub, int32_t dg
 #define TR_LIN7 [s0] "v"(sub[0]), [s1] "v"(sub[1]), [s2] "v"(sub[2]), [s3] "v"(sub[3]), [s4] "v"(sub[4]), [s5] "v"(sub[5]), [s6] "v"(sub[6]), \
                 [dg] "v"(dg_in), [hx] "v"(hext)
   static_assert(N == 7 || N == 8, "chunks of 7 or 8 cells");
-  if constexpr (N == 8 && !LAST) {
+  if constexpr (DIAG && N == 8 && !LAST) {
+    asm(TR_LCELL_D(7, "h6") TR_LCELL_D(6, "h5") TR_LCELL_D(5, "h4") TR_LCELL_D(4, "h3") TR_LCELL_D(3, "h2") TR_LCELL_D(2, "h1") TR_LCELL_D(1, "h0") TR_LCELL_D(0, "dg")
+        : TR_LOPS8 : TR_LIN8_D);
+  } else if constexpr (DIAG && N == 8 && LAST) {
+    asm(TR_LCELL_LAST(7, "h6") TR_LCELL_D(6, "h5") TR_LCELL_D(5, "h4") TR_LCELL_D(4, "h3") TR_LCELL_D(3, "h2") TR_LCELL_D(2, "h1") TR_LCELL_D(1, "h0") TR_LCELL_D(0, "dg")
+        : TR_LOPS8 : TR_LIN8_D, [hl] "v"(hext_last), [dl] "v"(delta_last));
+  } else if constexpr (DIAG && N == 7 && !LAST) {
+    asm(TR_LCELL_D(6, "h5") TR_LCELL_D(5, "h4") TR_LCELL_D(4, "h3") TR_LCELL_D(3, "h2") TR_LCELL_D(2, "h1") TR_LCELL_D(1, "h0") TR_LCELL_D(0, "dg")
+        : TR_LOPS7 : TR_LIN7_D);
+  } else if constexpr (DIAG) {
+    asm(TR_LCELL_LAST(6, "h5") TR_LCELL_D(5, "h4") TR_LCELL_D(4, "h3") TR_LCELL_D(3, "h2") TR_LCELL_D(2, "h1") TR_LCELL_D(1, "h0") TR_LCELL_D(0, "dg")
+        : TR_LOPS7 : TR_LIN7_D, [hl] "v"(hext_last), [dl] "v"(delta_last));
+  } else if constexpr (N == 8 && !LAST) {
     asm(TR_LCELL(7, "h6") TR_LCELL(6, "h5") TR_LCELL(5, "h4") TR_LCELL(4, "h3") TR_LCELL(3, "h2") TR_LCELL(2, "h1") TR_LCELL(1, "h0") TR_LCELL(0, "dg")
         : TR_LOPS8 : TR_LIN8);
   } else if constexpr (N == 8 && LAST) {
@@ -364,21 +433,36 @@ TR_HD void strip_left16(int32_t* hl, int32_t* el, const int32_t* sub, int32_t dg
 #undef TR_LOPS7
 #undef TR_LIN8
 #undef TR_LIN7
+#undef TR_LCELL_D
+#undef TR_LIN8_D
+#undef TR_LIN7_D
 #else
   for (int i = N - 1; i >= 0; --i) {
     const int32_t dg = i == 0 ? dg_in : hl[i - 1];
     if (LAST && i == N - 1) cell_left16_last(hl[i], el[i], hext_last, dg, sub[i], delta_last);
+    else if (DIAG) cell_left16d(hl[i], el[i], dg, sub[i]);
     else cell_left16(hl[i], el[i], hext, dg, sub[i]);
   }
 #endif
 }
 
-template <int N>
+template <int N, bool DIAG = false>
 TR_HD void strip_down16(int32_t* hl, const int32_t* el, int32_t up_in, int32_t& f, int32_t vext, int32_t goe) {
 #if defined(__HIP_DEVICE_COMPILE__)
+#define TR_DCELL_D(i, up) "v_max_i16 %[h" #i "], %[h" #i "], %[e" #i "]\n\tv_max_i16 %[f], %[" up "], %[f]\n\tv_max_i16 %[h" #i "], %[h" #i "], %[f]\n\tv_add_u16 %[h" #i "], %[h" #i "], %[go]\n\t"
 #define TR_DCELL(i, up) "v_max_i16 %[h" #i "], %[h" #i "], %[e" #i "]\n\tv_add_u16 %[f], %[f], %[vx]\n\tv_max_i16 %[f], %[" up "], %[f]\n\tv_max_i16 %[h" #i "], %[h" #i "], %[f]\n\tv_add_u16 %[h" #i "], %[h" #i "], %[go]\n\t"
   static_assert(N == 7 || N == 8, "chunks of 7 or 8 cells");
-  if constexpr (N == 8) {
+  if constexpr (DIAG && N == 8) {
+    asm(TR_DCELL_D(0, "up") TR_DCELL_D(1, "h0") TR_DCELL_D(2, "h1") TR_DCELL_D(3, "h2") TR_DCELL_D(4, "h3") TR_DCELL_D(5, "h4") TR_DCELL_D(6, "h5") TR_DCELL_D(7, "h6")
+        : [h0] "+v"(hl[0]), [h1] "+v"(hl[1]), [h2] "+v"(hl[2]), [h3] "+v"(hl[3]), [h4] "+v"(hl[4]), [h5] "+v"(hl[5]), [h6] "+v"(hl[6]), [h7] "+v"(hl[7]), [f] "+v"(f)
+        : [e0] "v"(el[0]), [e1] "v"(el[1]), [e2] "v"(el[2]), [e3] "v"(el[3]), [e4] "v"(el[4]), [e5] "v"(el[5]), [e6] "v"(el[6]), [e7] "v"(el[7]),
+          [up] "v"(up_in), [go] "v"(goe));
+  } else if constexpr (DIAG) {
+    asm(TR_DCELL_D(0, "up") TR_DCELL_D(1, "h0") TR_DCELL_D(2, "h1") TR_DCELL_D(3, "h2") TR_DCELL_D(4, "h3") TR_DCELL_D(5, "h4") TR_DCELL_D(6, "h5")
+        : [h0] "+v"(hl[0]), [h1] "+v"(hl[1]), [h2] "+v"(hl[2]), [h3] "+v"(hl[3]), [h4] "+v"(hl[4]), [h5] "+v"(hl[5]), [h6] "+v"(hl[6]), [f] "+v"(f)
+        : [e0] "v"(el[0]), [e1] "v"(el[1]), [e2] "v"(el[2]), [e3] "v"(el[3]), [e4] "v"(el[4]), [e5] "v"(el[5]), [e6] "v"(el[6]),
+          [up] "v"(up_in), [go] "v"(goe));
+  } else if constexpr (N == 8) {
     asm(TR_DCELL(0, "up") TR_DCELL(1, "h0") TR_DCELL(2, "h1") TR_DCELL(3, "h2") TR_DCELL(4, "h3") TR_DCELL(5, "h4") TR_DCELL(6, "h5") TR_DCELL(7, "h6")
         : [h0] "+v"(hl[0]), [h1] "+v"(hl[1]), [h2] "+v"(hl[2]), [h3] "+v"(hl[3]), [h4] "+v"(hl[4]), [h5] "+v"(hl[5]), [h6] "+v"(hl[6]), [h7] "+v"(hl[7]), [f] "+v"(f)
         : [e0] "v"(el[0]), [e1] "v"(el[1]), [e2] "v"(el[2]), [e3] "v"(el[3]), [e4] "v"(el[4]), [e5] "v"(el[5]), [e6] "v"(el[6]), [e7] "v"(el[7]),
@@ -390,9 +474,11 @@ TR_HD void strip_down16(int32_t* hl, const int32_t* el, int32_t up_in, int32_t& 
           [up] "v"(up_in), [vx] "v"(vext), [go] "v"(goe));
   }
 #undef TR_DCELL
+#undef TR_DCELL_D
 #else
   for (int i = 0; i < N; ++i) {
-    cell_down16(hl[i], el[i], up_in, f, vext, goe);
+    if (DIAG) cell_down16d(hl[i], el[i], up_in, f, goe);
+    else cell_down16(hl[i], el[i], up_in, f, vext, goe);
     up_in = hl[i];
   }
 #endif

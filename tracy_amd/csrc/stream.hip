@@ -907,7 +907,11 @@ int queue_orientation(tracyhip_ctx* ctx, const tracyhip_params& p, const SParams
     // (the prefixes are not timed on their own: they begin with the sweeps and end inside them, and their cells stay credited to the
     // sweep timer, whose interval covers both launches as it covered the one)
     int rc = TRACYHIP_OK;
-    if (launch_gotoh_ckpt_front(h.classes[0].K, a, 0u, ap, npre_all, fk.side[0]) != hipSuccess) rc = set_error(TRACYHIP_ERR_HIP, "prefix launch failed");
+    {
+      DpArgs af = a, apl = ap;
+      launch_diag_periods(ctx, &p, h.classes[0].K, 0u, npre_all, true, af, apl);
+      if (launch_gotoh_ckpt_front(h.classes[0].K, af, 0u, apl, npre_all, fk.side[0]) != hipSuccess) rc = set_error(TRACYHIP_ERR_HIP, "prefix launch failed");
+    }
     if (!rc) rc = front_tiers();
     if (!rc && os.early_tail) {
       hipLaunchKernelGGL(s_orient_early_kernel, g256, b256, 0, fk.side[0], sp, sc.fo1, sc.fs1, sc.fe1, sc.fo2, sc.fs2, sc.fe2, sc.tr);
@@ -925,8 +929,10 @@ int queue_orientation(tracyhip_ctx* ctx, const tracyhip_params& p, const SParams
       for (const SweepClass& c : h.classes) {
         DpArgs af = a;
         af.pairs = sc.full + 2 * (size_t)c.lo;
+        DpArgs apl = ap;
+        launch_diag_periods(ctx, &p, c.K, 2 * (c.hi - c.lo), 0u, true, af, apl);
         TRY(timing_begin(ctx, TRACYHIP_TIMER_SCORE, 0, 0));
-        const hipError_t e = launch_gotoh_ckpt_front(c.K, af, 2 * (c.hi - c.lo), ap, 0u, st);
+        const hipError_t e = launch_gotoh_ckpt_front(c.K, af, 2 * (c.hi - c.lo), apl, 0u, st);
         TRY(timing_end(ctx));
         HIP_TRY(e);
       }
@@ -940,8 +946,10 @@ int queue_orientation(tracyhip_ctx* ctx, const tracyhip_params& p, const SParams
     for (const SweepClass& c : h.classes) {
       DpArgs af = a;
       af.pairs = sc.full + 2 * (size_t)c.lo;
+      DpArgs apl = ap;
+      launch_diag_periods(ctx, &p, c.K, 2 * (c.hi - c.lo), pre_done ? 0u : npre_all, true, af, apl);
       TRY(timing_begin(ctx, TRACYHIP_TIMER_SCORE, 0, 0));
-      HIP_TRY(launch_gotoh_ckpt_front(c.K, af, 2 * (c.hi - c.lo), ap, pre_done ? 0u : npre_all, st));
+      HIP_TRY(launch_gotoh_ckpt_front(c.K, af, 2 * (c.hi - c.lo), apl, pre_done ? 0u : npre_all, st));
       TRY(timing_end(ctx));
       pre_done = true;
     }
