@@ -88,6 +88,33 @@ def test_full_sweep_offset_form(K, period):
                 assert sd.sweep(a1, ref, SC, K, period, ckpt=False, revcomp=rc)[0] == want, (K, period, m, n)
 
 
+def test_sixteen_row_strips_with_every_lane_full():
+    """K = 16 at the heights it is chosen for (961 to 1 024 rows): 61 lanes, one row in the last lane (1 009 = 63 x 16 + 1), all 64
+    lanes full -- the grid above runs K = 16 on heights of at most 960 rows, so its last four lanes never hold a row.  References
+    longer than the traces too (n = 1 100 > m).  Score, row m and the checkpoints of the lanes that hold rows, at both periods,
+    against the form on values as they are and the oracle."""
+    K = 16
+    for im, m in enumerate((961, 1009, 1024)):
+        for jn, n in enumerate((1, 64, 65, 700, 1100)):
+            rng = np.random.default_rng(16000 + 10 * im + jn)
+            rc = (im + jn) % 2 == 1
+            a1 = rand_profile(rng, m, sharp=jn != 3 or im != 1)  # (one flat profile; the others sharp)
+            ref = rand_seq(rng, n, b"ACGTNn-x" if (im + jn) % 4 else b"ACGT")
+            p2 = orc.create_profile_str(ref)
+            want = orc.gotoh_score_prof(a1, orc.revcomp_profile(p2) if rc else p2, 1, 0, SC)
+            today = sd.sweep(a1, ref, SC, K, 0, ckpt=True, B=B, revcomp=rc)
+            assert today[0] == want and today[1] == (0, 0), (m, n)
+            lanes = (m + K - 1) // K
+            nrec = (n + lanes - 1) // B
+            for period in (64, 128):
+                score, err, rowm, rec = sd.sweep(a1, ref, SC, K, period, ckpt=True, B=B, revcomp=rc)
+                assert score == want and err == (0, 0), (period, m, n)
+                assert np.array_equal(rowm[1:n + 1], today[2][1:n + 1]), (period, m, n)
+                assert np.array_equal(rec[:nrec, :, :lanes], today[3][:nrec, :, :lanes]), (period, m, n)
+                assert np.array_equal(rec[nrec:], today[3][nrec:]), (period, m, n)
+            assert sd.sweep(a1, ref, SC, K, 64 << (jn % 2), ckpt=False, revcomp=rc)[0] == want, (m, n)  # the sweep that keeps nothing
+
+
 @pytest.mark.parametrize("K,GL", [(8, 16), (8, 8)])
 def test_prefix_rows_offset_form(K, GL):
     """four (eight) pairs per wave with references of different lengths, one group without a pair, both views: the reported bound

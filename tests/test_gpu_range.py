@@ -3,10 +3,16 @@ reference (align.h:103-118, gotoh.h:124-139) computes in int32 without limits.  
 oracle's exact result or TRACYHIP_ERR_RANGE -- never a wrapped score.  The 16-bit score sweeps and the 14-bit origin
 field rest on bounds that hold for NORMALISED profiles; kernels report larger query-profile entries / column masses and
 the host re-checks the range with the real bound (capi.hip range_verdict), repeating the work on the int32 kernels."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 import pyoracle as orc
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
+import emu_sweep_diag as sd  # noqa: E402  (the host emulator of the 16-bit sweeps, and the range rules of sweep_range.h)
 
 pytestmark = pytest.mark.gpu
 
@@ -110,6 +116,81 @@ def test_unnormalised_profiles_through_align_traces(ctx, scale):
             assert got["btr"][i] == want["btr"], (scale, exact, i)
             if exact:
                 assert (int(got["score_fwd"][i]), int(got["score_rev"][i])) == (int(want["score_fwd"]), int(want["score_rev"]))
+
+
+def test_reported_q_shrinks_the_offset_period(ctx):
+    """Un-normalised profiles whose reported Q still passes narrow_ok but leaves the offset form of the 16-bit sweeps less room than
+    the launch assumed: the second condition of range_verdict (capi.hip: sweep_diag_period(prm, K, 64, Q) < diag -> widen).
+
+    5/-5/-10/-4: sweep_diag_period_rule gives 4 096 a priori for strips of fifteen and of sixteen rows, and the largest entry of the
+    scoring is the match entry, so rows A against columns A reach rows x Q.  Scaling the rows moves Q through three regimes, and the
+    list is asserted to hold all of them for both K: the rule still gives a period for Q, but a shorter one than the launch took;
+    the rule gives none though narrow_ok holds; narrow_ok fails (the first condition -- the scale 6.6 is there for it).
+
+    Why this fails when that line is wrong: on the host emulator rows A x 960 times 5.4 (Q = 27, the rule allows 64) against A x 1 100
+    return 25 920 = the oracle's score at period 64, and 24 501 at the launched period of 4 096: the offsets wrap.  A x 1 024 times
+    5.0 (Q = 25, the rule allows 128): 25 600 at period 64, 24 245 at 4 096.  Only the verdict stands between these pairs and those
+    numbers.  What the suite cannot tell is whether an exact score came from the repeat on the int32 kernels or from an offset form
+    that happened to stay in range: the ABI counts launches, not verdicts.
+
+    Q is computed on the host: the second error word of the emulated sweep.  It is the largest entry of the query profile, which
+    the sweep builds from the rows before the first column, so the emulator runs each case's rows against the first 64 columns of
+    its reference (the references hold ACGT only: the same four-code table)."""
+    from sage_oracle import align_trace
+    sc = (5, -5, -10, -4)
+    rng = np.random.default_rng(4096)
+    cases = []  # (K, rows, columns)
+    for K, m, scales in ((15, 960, (2.2, 4.0, 5.4, 5.8, 6.6)), (16, 1024, (2.2, 4.0, 5.0, 5.4, 6.6))):
+        assert sd.diag_period(sc, K) == 4096
+        for s in scales:
+            onehot = orc.create_profile_str(b"A" * m) * np.float32(s)
+            cases += [(K, onehot, b"A" * 1100), (K, onehot, b"A" * 2000)]
+            seq = rand_seq(rng, m)
+            cases.append((K, profile_of(rng, seq, s), noisy_window(rng, seq, 1500)))
+    regimes = set()
+    for K, p, r in cases:
+        Q = sd.sweep(p, r[:64], sc, K, 0)[1][1]
+        rule, ok = sd.diag_period(sc, K, 64, Q), sd.narrow_ok(sc, p.shape[1], K, Q)
+        assert Q > 5 and (ok or rule == 0), (K, Q, rule, ok)  # (every case reports a Q beyond the scoring's own)
+        regimes.add((K, "kept" if rule >= 4096 else "shorter" if rule >= 64 else "none" if ok else "narrow"))
+    assert regimes >= {(K, w) for K in (15, 16) for w in ("shorter", "none", "narrow")}, regimes
+    profs, refs = [c[1] for c in cases], [c[2] for c in cases]
+    want = [orc.gotoh_score_prof(p, orc.create_profile_str(r), 1, 0, sc) for p, r in zip(profs, refs)]
+    assert want[2 * 3] == 25920 and want[(5 + 2) * 3] == 25600  # (the two pairs of the docstring)
+    for name, opt in (("auto", {}), ("period64", {"sweep_diag_period": 64}), ("plain", {"no_sweep_diag": 1})):
+        for k, v in opt.items():
+            ctx.set_option(k, v)
+        try:
+            assert exact_or_range(lambda: [int(x) for x in ctx.score(profs, refs, sc + (1, 0))], want, True) == "exact", name
+            # one pair at a time too: the verdict is taken per call, over every launch of the call.  The counter says that the pair
+            # was launched in the offset form (a priori nothing speaks against it), so the number that came back passed the verdict.
+            for i in (2 * 3, (5 + 2) * 3):
+                before = ctx.last_call_stats()["sweep_diag_launches"]
+                assert exact_or_range(lambda: int(ctx.score([profs[i]], [refs[i]], sc + (1, 0))[0]), want[i], True) == "exact", (name, i)
+                assert (ctx.last_call_stats()["sweep_diag_launches"] > before) == (name != "plain"), (name, i)
+        finally:
+            for k in opt:
+                ctx.set_option(k, 0)
+    # tracebacks and the pipeline: the rows the offset form wraps on (Q = 27 at 960 rows, Q = 25 at 1 024), not one-hot
+    for K, m, s in ((15, 960, 5.4), (16, 1024, 5.0)):
+        seq = rand_seq(rng, m + 100)
+        full = profile_of(rng, seq, s)
+        p = np.ascontiguousarray(full[:, 50:m + 50])
+        ref = noisy_window(rng, seq, 2000)
+        w = orc.gotoh_prof(p, orc.create_profile_str(ref), 1, 0, sc)
+
+        def aligned():
+            sc_, b = ctx.align([p], [ref], sc + (1, 0))
+            return (int(sc_[0]), b[0])
+        assert exact_or_range(aligned, w, True) == "exact", K
+        refs2 = [ref, ref[::-1].translate(bytes.maketrans(b"ACGT", b"TGCA"))]
+        keys = ("score_fwd", "score_rev", "forward", "score_prelim", "slice_begin", "slice_len", "ref_pos", "score_final")
+        wt = [align_trace(full, r, sc, 50, 50) for r in refs2]
+
+        def traced():
+            g = ctx.align_traces([full, full], refs2, sc, 50, 50, exact_scores=True)
+            return [tuple(int(g[k][i]) for k in keys) + (g["btr"][i],) for i in range(2)]
+        assert exact_or_range(traced, [tuple(int(x[k]) for k in keys) + (x["btr"],) for x in wt], True) == "exact", K
 
 
 def test_negative_profile_entries(ctx):
