@@ -132,6 +132,8 @@ int tracyhip_synchronize(tracyhip_ctx* ctx);
      quad_tier_min  (stream-ordered pipelines: traces / alleles from which a pruned sweep gets its narrow first tier; default 32768)
      front_list_min (... from which its later tiers, and the allele prefixes of `tracy decompose`, run over device-side lists of the units
                     that are left instead of skipping the others in place; default 1024)
+     b16_multi_max  (stream-ordered pipelines: units up to which a band stage is ONE launch over its four lists; above, strip height 12 gets a
+                    launch of its own beside the other three; 0 .. 2147483647, default 49152, 0 = every band stage takes the large form)
    Every option selects another EXACT path (A/B measurements, tests of the fallback tiers); none changes a result.  Lanes inherit.
    TRACYHIP_HOST_THREADS, TRACYHIP_HOST_TIMERS, TRACYHIP_LDS_PAD and TRACYHIP_LDS_STAGE_LIMIT are per process (read once).
    tracyhip_describe writes the current settings as "name=value" lines (at most cap - 1 bytes) and returns the length needed. */
@@ -174,6 +176,9 @@ typedef struct {
   uint32_t var_chunks;           /* ... chunks of traces the batch was cut into to fit the workspace limit */
   uint32_t sweep_diag_launches;  /* 16-bit full sweeps launched in the offset form (six operations per cell; 0 with no_sweep_diag or where the range rule finds no room) */
   uint32_t prefix_diag_launches; /* ... launches of prefix sweeps in the offset form */
+  uint32_t band_list_pairs[2][4]; /* stream-ordered pipelines: pairs the scan of a band stage filed under strip height 12 / 8 / 4 / the quad form, summed
+                                     over the call's band stages; [0]: traceback stages, [1]: origin sweeps.  0 in a call planned by the host */
+  uint32_t band_large_launches;  /* ... band stages of more than b16_multi_max units: strip height 12 in a launch of its own beside the other three lists */
 } tracyhip_call_stats;
 int tracyhip_last_call_stats(tracyhip_ctx* ctx, tracyhip_call_stats* out);
 const char* tracyhip_last_error(void);

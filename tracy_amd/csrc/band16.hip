@@ -214,7 +214,8 @@ void B16Fork::destroy() {
 }
 
 hipError_t launch_band16_counted(int kind, const Band16Args& a12, const Band16Args& a8, const Band16Args& a4, const Band16Args& aq, hipStream_t s,
-                                 const B16Fork* fork) {
+                                 const B16Fork* fork, uint32_t multi_max, bool* large) {
+  if (large) *large = false;
   uint32_t most = a12.npairs;
   for (uint32_t x : {a8.npairs, a4.npairs, aq.npairs}) most = x > most ? x : most;
   if (most == 0) return hipSuccess;
@@ -225,10 +226,8 @@ hipError_t launch_band16_counted(int kind, const Band16Args& a12, const Band16Ar
   // own beside the other three (side stream), which then run three waves per SIMD instead of two.  Measured per decompose step of
   // 12 500 / 25 000 / 100 000 traces: one launch 20.0 / 35.9-36.8 / 131.8-132.0 ms, three + one 20.8 (two stages of it) / 35.5-35.7 /
   // 129.9-130.6 ms, four launches side by side 20.8 / 37.3 / 132.9 ms.
-#ifndef TRACY_B16_MULTI_MAX
-#define TRACY_B16_MULTI_MAX 49152u
-#endif
-  if (most <= TRACY_B16_MULTI_MAX) {
+  // (multi_max: TRACY_B16_MULTI_MAX unless the caller's option b16_multi_max says otherwise)
+  if (most <= multi_max) {
     const uint32_t lds16 = 4u * a12.code_cap + b16_table_bytes(12), ldsq = aq.npairs ? b16_quad_lds(aq.code_cap) : 0u;
     const uint32_t lds = lds16 > ldsq ? lds16 : ldsq;
     const dim3 grid((most + 3u) / 4u + 4u);  // (the four jobs together hold at most `most` pairs: every pair is in one of them)
@@ -236,6 +235,7 @@ hipError_t launch_band16_counted(int kind, const Band16Args& a12, const Band16Ar
     else hipLaunchKernelGGL((band16_multi_counted_kernel<1>), grid, dim3(64), lds, s, a12, a8, a4, aq);
     return hipGetLastError();
   }
+  if (large) *large = true;
   const uint32_t lds16 = 4u * a8.code_cap + b16_table_bytes(8), ldsq = aq.npairs ? b16_quad_lds(aq.code_cap) : 0u;
   const uint32_t lds = lds16 > ldsq ? lds16 : ldsq;
   const dim3 grid((most + 3u) / 4u + 3u);

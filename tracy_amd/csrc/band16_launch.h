@@ -40,8 +40,13 @@ struct B16Fork {
   void destroy();
 };
 // aq: the pairs of narrow bands (b16_narrow_ok) swept four lanes to a pair; aq.npairs = 0 when the launch's code_cap leaves no room (b16_quad_lds)
+// multi_max: units up to which the four lists share ONE launch (option b16_multi_max); above, strip height 12 gets a launch of its own
+// beside the other three, and *large (where given) says so
+#ifndef TRACY_B16_MULTI_MAX
+#define TRACY_B16_MULTI_MAX 49152u
+#endif
 hipError_t launch_band16_counted(int kind, const Band16Args& a12, const Band16Args& a8, const Band16Args& a4, const Band16Args& aq, hipStream_t s,
-                                 const B16Fork* fork = nullptr);
+                                 const B16Fork* fork = nullptr, uint32_t multi_max = TRACY_B16_MULTI_MAX, bool* large = nullptr);
 // the sweep below a stored prefix row (Band16Args::row; K = 8 or 12), and the two kernels of front.h around it
 // narrow: every DP value of the launch fits int16 (narrow_ok for the tallest pair, rows above the stored one included): the 16-bit cells
 hipError_t launch_band16_cont(int K, const Band16Args& a, hipStream_t s, bool narrow = false);

@@ -272,6 +272,13 @@ bool knobs_set(CtxKnobs& k, const char* name, const char* value) {
     k.front_list_min = (uint32_t)std::min<long>(v, 0x7fffffffl);
     return true;
   }
+  if (same_name(name, "b16_multi_max")) {
+    char* end = nullptr;
+    const long v = strtol(value, &end, 10);
+    if (end == value || *end || v < 0 || v > 0x7fffffffl) return false;
+    k.b16_multi_max = (uint32_t)v;
+    return true;
+  }
   if (same_name(name, "seed_vote_cap")) {
     const long v = atol(value);
     if (v < 1 || v > 2048) return false;
@@ -309,6 +316,7 @@ void knobs_from_env(CtxKnobs& k) {
   if (const char* e = getenv("TRACYHIP_CKPT_B")) knobs_set(k, "ckpt_b", e);
   if (const char* e = getenv("TRACYHIP_QUAD_TIER_MIN")) knobs_set(k, "quad_tier_min", e);
   if (const char* e = getenv("TRACYHIP_FRONT_LIST_MIN")) knobs_set(k, "front_list_min", e);
+  if (const char* e = getenv("TRACYHIP_B16_MULTI_MAX")) knobs_set(k, "b16_multi_max", e);
   if (const char* e = getenv("TRACYHIP_SEED_VOTE_CAP")) knobs_set(k, "seed_vote_cap", e);
   if (const char* e = getenv("TRACYHIP_SWEEP_DIAG_PERIOD")) knobs_set(k, "sweep_diag_period", e);
 }
@@ -319,6 +327,7 @@ std::string knobs_describe(const CtxKnobs& k) {
   s += "ckpt_b=" + std::to_string(k.ckpt_b) + "\n";
   s += "quad_tier_min=" + std::to_string(k.quad_tier_min) + "\n";
   s += "front_list_min=" + std::to_string(k.front_list_min) + "\n";
+  s += "b16_multi_max=" + std::to_string(k.b16_multi_max) + "\n";
   s += "seed_vote_cap=" + std::to_string(k.seed_vote_cap) + "\n";
   s += "sweep_diag_period=" + std::to_string(k.sweep_diag_period) + "\n";
   s += "host_threads=" + std::to_string(host_pool_threads()) + "\n";

@@ -236,6 +236,7 @@ struct CtxKnobs {
                                   // 0 = whole matrices, else [1, 4096]
   uint32_t ckpt_b = 256;
   uint32_t sweep_diag_period = 0; // offset form of the sweeps: steps between re-bases, clamped to what sweep_diag_period() allows; 0 = that
+  uint32_t b16_multi_max = TRACY_B16_MULTI_MAX; // stream-ordered pipelines: units up to which a band stage is one launch over its four lists (launch_band16_counted)
   uint32_t front_list_min = 1024; // stream-ordered pipelines: units from which the later tiers of a pruned sweep (and the allele prefixes) run over device-side lists
   uint32_t seed_vote_cap = 2048;  // tracyhip_seed_traces: votes per trace, strand and pass held in LDS (seed.hip); more: the trace is deferred
   uint32_t quad_tier_min = 32768;  // stream-ordered pipelines: units (traces, or alleles) from which the pruned sweeps get their narrow quad tier          // steps between wavefront checkpoints [32, 1024]

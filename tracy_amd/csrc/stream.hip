@@ -342,8 +342,10 @@ __global__ __launch_bounds__(kScanBlock) void s_scan_partial_kernel(const PairDe
   __syncthreads();
   if (threadIdx.x == 0) part[blockIdx.x] = ScanPart{{s_n[0], s_n[1], s_n[2], s_n[3]}, s_b};
 }
-// exclusive scan over the blocks' totals (in place), the lists' sizes
-__global__ __launch_bounds__(kScanTop) void s_scan_top_kernel(ScanPart* __restrict__ part, uint32_t nb, uint32_t* __restrict__ count) {
+// exclusive scan over the blocks' totals (in place), the lists' sizes (count: for the launch; stat: added up for the call's statistics --
+// `tracy align` runs a stage twice, over the early traces and over the rest)
+__global__ __launch_bounds__(kScanTop) void s_scan_top_kernel(ScanPart* __restrict__ part, uint32_t nb, uint32_t* __restrict__ count,
+                                                              unsigned long long* __restrict__ stat) {
   __shared__ uint32_t s_n[4][kScanTop];
   __shared__ unsigned long long s_b[kScanTop];
   const uint32_t tid = threadIdx.x;
@@ -373,16 +375,20 @@ __global__ __launch_bounds__(kScanTop) void s_scan_top_kernel(ScanPart* __restri
     for (int b = 0; b < 4; ++b) at[b] += x.n[b];
     off += x.bytes;
   }
-  if (tid == 0) for (int b = 0; b < 4; ++b) count[b] = s_n[b][kScanTop - 1];
+  if (tid == 0)
+    for (int b = 0; b < 4; ++b) {
+      count[b] = s_n[b][kScanTop - 1];
+      stat[SB_LIST + b] += s_n[b][kScanTop - 1];
+    }
 }
 __global__ __launch_bounds__(kScanBlock) void s_scan_place_kernel(PairDesc* __restrict__ cand, uint8_t* __restrict__ kc, uint32_t n, uint32_t unit_mod, int kind,
                                                                   int quads, unsigned long long cap_bytes, const ScanPart* __restrict__ part, uint32_t* __restrict__ idx,
                                                                   uint32_t* __restrict__ dead, unsigned long long* __restrict__ stat) {
   __shared__ uint32_t s_n[4][kScanBlock];
   __shared__ unsigned long long s_b[kScanBlock];
-  __shared__ unsigned long long s_stat[SB_COUNT];
+  __shared__ unsigned long long s_stat[SB_LIST];  // (the lists' sizes are the top kernel's)
   const uint32_t tid = threadIdx.x;
-  if (tid < SB_COUNT) s_stat[tid] = 0;
+  if (tid < SB_LIST) s_stat[tid] = 0;
   const uint32_t i = blockIdx.x * kScanBlock + tid;
   const int K = i < n ? kc[i] : 0;
   PairDesc d{};
@@ -420,7 +426,7 @@ __global__ __launch_bounds__(kScanBlock) void s_scan_place_kernel(PairDesc* __re
     }
   }
   __syncthreads();
-  if (tid < SB_COUNT && s_stat[tid]) atomicAdd(stat + tid, s_stat[tid]);
+  if (tid < SB_LIST && s_stat[tid]) atomicAdd(stat + tid, s_stat[tid]);
 }
 
 // ---- `tracy align`: trimReferenceSlice from the two ends (sage.h:259) and the plan of the final alignment gotoh(full profile,
@@ -540,6 +546,7 @@ struct StreamCommon {  // device arrays of the orientation stage + preliminary a
   unsigned long long* cnt;   // [SC_COUNT]
   unsigned long long* bstat; // [SB_COUNT] per band stage
   uint32_t* ends;
+  uint32_t large_stages = 0; // (host) band stages of the call that took the large form (launch_band16_counted)
   void layout(Arena& a, uint32_t nt, uint32_t nunits, bool exact, bool want_full_top) {
     geom = a.take<SGeom>(nt);
     vd = a.take<VoteDesc>(nt);
@@ -798,7 +805,7 @@ int band_stage(tracyhip_ctx* ctx, const tracyhip_params& p, StreamCommon& sc, ui
   const uint32_t nb = (n + kScanBlock - 1) / kScanBlock;
   const int quads = (!ctx->knobs.no_quads && b16_quad_lds(bl.code_cap) <= 64u * 1024u) ? 1 : 0;  // the narrow bands four lanes to a pair, where sixteen code rows fit
   hipLaunchKernelGGL(s_scan_partial_kernel, dim3(nb), dim3(kScanBlock), 0, st, sc.cand, sc.kc, n, bl.kind, quads, sc.part);
-  hipLaunchKernelGGL(s_scan_top_kernel, dim3(1), dim3(kScanTop), 0, st, sc.part, nb, count);
+  hipLaunchKernelGGL(s_scan_top_kernel, dim3(1), dim3(kScanTop), 0, st, sc.part, nb, count, sc.bstat + SB_COUNT * stage_no);
   hipLaunchKernelGGL(s_scan_place_kernel, dim3(nb), dim3(kScanBlock), 0, st, sc.cand, sc.kc, n, unit_mod, bl.kind, quads, (unsigned long long)cap_bytes, sc.part, sc.idx, sc.dead,
                      sc.bstat + SB_COUNT * stage_no);
   HIP_TRY(hipGetLastError());
@@ -810,7 +817,10 @@ int band_stage(tracyhip_ctx* ctx, const tracyhip_params& p, StreamCommon& sc, ui
   for (int b = 0; b < 4; ++b) { ak[b].index = sc.idx + (size_t)b * n; ak[b].count = count + b; }
   if (!quads) ak[3].npairs = 0;
   TRY(timing_begin(ctx, bl.kind == 0 ? TRACYHIP_TIMER_TRACE : TRACYHIP_TIMER_ORIGIN, 0, 0));  // (cells / bytes: the scan's sums, added after the call's synchronisation)
-  HIP_TRY(launch_band16_counted(bl.kind, ak[0], ak[1], ak[2], ak[3], st, (ctx->b16_fork_ok && !ctx->knobs.no_fork) ? &ctx->b16_fork : nullptr));
+  bool large = false;
+  HIP_TRY(launch_band16_counted(bl.kind, ak[0], ak[1], ak[2], ak[3], st, (ctx->b16_fork_ok && !ctx->knobs.no_fork) ? &ctx->b16_fork : nullptr,
+                                ctx->knobs.b16_multi_max, &large));
+  if (large) ++sc.large_stages;
   TRY(timing_end(ctx));
   return TRACYHIP_OK;
 }
@@ -1097,7 +1107,8 @@ int stream_range_verdict(const tracyhip_params& p, const int32_t* herr, const St
   return TRACYHIP_OK;
 }
 
-void stats_from_counters(tracyhip_ctx* ctx, const unsigned long long* c, const unsigned long long* bstat, int nstages, const int* stage_timer) {
+void stats_from_counters(tracyhip_ctx* ctx, const unsigned long long* c, const unsigned long long* bstat, int nstages, const int* stage_timer,
+                         uint32_t large_stages) {
   tracyhip_call_stats& s = ctx->stats;
   s.pruned += (uint32_t)c[SC_PRUNED]; s.pruned_uncertified += (uint32_t)c[SC_PRUNED_UNCERT];
   s.prelim_banded += (uint32_t)c[SC_PRELIM_BANDED]; s.prelim_repeated += (uint32_t)c[SC_PRELIM_REPEATED];
@@ -1105,6 +1116,9 @@ void stats_from_counters(tracyhip_ctx* ctx, const unsigned long long* c, const u
   for (int k = 0; k < 2; ++k) { s.allele_pruned[k] += (uint32_t)c[SC_ALLELE_PRUNED0 + k]; s.allele_uncertified[k] += (uint32_t)c[SC_ALLELE_UNCERT0 + k]; }
   for (int k = 0; k < 3; ++k) { s.allele_banded[k] += (uint32_t)c[SC_ALLELE_BANDED0 + k]; s.allele_repeated[k] += (uint32_t)c[SC_ALLELE_REPEATED0 + k]; }
   s.allele_shared_prefix += (uint32_t)c[SC_ALLELE_SHARED];
+  for (int i = 0; i < nstages; ++i)  // (a stage's kind by its timer: tracebacks, origin sweeps)
+    for (int b = 0; b < SB_LIST_N; ++b) s.band_list_pairs[stage_timer[i] == TRACYHIP_TIMER_TRACE ? 0 : 1][b] += (uint32_t)bstat[SB_COUNT * i + SB_LIST + b];
+  s.band_large_launches += large_stages;
   if (ctx->timing) {
     ctx->acc[TRACYHIP_TIMER_SCORE].cells += c[SC_SWEEP_CELLS];
     ctx->acc[TRACYHIP_TIMER_SCORE].bytes += c[SC_SWEEP_BYTES];
@@ -1120,8 +1134,9 @@ void stats_from_counters(tracyhip_ctx* ctx, const unsigned long long* c, const u
   if (ctx->knobs.verbose)
     for (int i = 0; i < nstages; ++i) {
       const unsigned long long* hst = bstat + SB_COUNT * i + SB_HIST;
-      fprintf(stderr, "tracyhip: band stage %d: pairs by diagonals <=8 %llu <=16 %llu <=24 %llu <=32 %llu <=48 %llu <=64 %llu <=96 %llu more %llu\n", i, hst[0], hst[1], hst[2],
-              hst[3], hst[4], hst[5], hst[6], hst[7]);
+      const unsigned long long* lst = bstat + SB_COUNT * i + SB_LIST;
+      fprintf(stderr, "tracyhip: band stage %d: pairs by diagonals <=8 %llu <=16 %llu <=24 %llu <=32 %llu <=48 %llu <=64 %llu <=96 %llu more %llu; "
+              "by strip height 12: %llu 8: %llu 4: %llu quads: %llu\n", i, hst[0], hst[1], hst[2], hst[3], hst[4], hst[5], hst[6], hst[7], lst[0], lst[1], lst[2], lst[3]);
     }
 }
 
@@ -1257,6 +1272,7 @@ struct StreamCall {
     HIP_TRY(hipMemsetAsync(sc.dead, 0, sizeof(uint32_t) * (size_t)nt, st));
     HIP_TRY(hipMemsetAsync(sc.cnt, 0, sizeof(unsigned long long) * SC_COUNT, st));
     HIP_TRY(hipMemsetAsync(sc.bstat, 0, sizeof(unsigned long long) * SB_COUNT * 8, st));
+    sc.large_stages = 0;
     return TRACYHIP_OK;
   }
 
@@ -1285,8 +1301,8 @@ struct StreamCall {
 
   // the call's statistics from its counters; the traces the device could not give their tier, and (verbose) why
   template <size_t NS, size_t NR>
-  void list_dead(const char* what, const int (&stage_timer)[NS], const DeadReason (&reasons)[NR]) {
-    stats_from_counters(ctx, rb.hcnt, rb.hbst, (int)NS, stage_timer);
+  void list_dead(const char* what, const StreamCommon& sc, const int (&stage_timer)[NS], const DeadReason (&reasons)[NR]) {
+    stats_from_counters(ctx, rb.hcnt, rb.hbst, (int)NS, stage_timer, sc.large_stages);
     ctx->stats.stream_ordered = 1;
     dl.clear();
     for (uint32_t t = 0; t < nt; ++t)
@@ -1467,7 +1483,7 @@ struct AlignStream : StreamCall {
     static const int stage_timer[2] = {TRACYHIP_TIMER_ORIGIN, TRACYHIP_TIMER_TRACE};
     static const DeadReason reasons[] = {{SD_FRONT, "front"}, {SD_STRAND, "strand"}, {SD_LOSER_WON, "loser won"}, {SD_JUNK, "junk"}, {SD_PRELIM_BAND, "prelim band"},
                                          {SD_FINAL_BAND, "final band"}, {SD_FINAL_CHECK, "final check"}, {SD_MEM, "mem"}, {SD_SHAPE, "shape"}};
-    list_dead("align", stage_timer, reasons);
+    list_dead("align", A.sc, stage_timer, reasons);
     return TRACYHIP_OK;
   }
 
@@ -2317,7 +2333,7 @@ struct DecStream : StreamCall {
                                          {SD_PRELIM_CHECK, "prelim check"}, {SD_MEM, "mem"}, {SD_ALLELE_FRONT, "allele front"}, {SD_ALLELE_ORIGIN, "allele origin"},
                                          {SD_ALLELE_BAND, "allele band"}, {SD_ALLELE_CHECK, "allele check"}, {SD_A12_BAND, "a12 band"}, {SD_A12_CHECK, "a12 check"},
                                          {SD_SHAPE, "shape"}};
-    list_dead("decompose", stage_timer, reasons);
+    list_dead("decompose", A.sc, stage_timer, reasons);
     return TRACYHIP_OK;
   }
 
