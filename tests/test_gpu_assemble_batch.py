@@ -248,6 +248,45 @@ def test_shared_reference_empty_batch_and_bad_input(ctx, batch):
     assert e.value.code == capi.ERR_RANGE
 
 
+def run_traceless(ctx, p, symbol, device):
+    """a prepared batch whose groups hold no trace, through `symbol` with nrows / ncol / cons_len prefilled where the call finds them;
+    returns results() and the call's host_syncs"""
+    import ctypes as C
+    from tracy_amd import capi
+    counts = ("nrows", "ncol", "cons_len")
+    if device:
+        import torch
+        p.to_device()
+        for k in counts:
+            p.dres[k].fill_(0xa5)
+        torch.cuda.synchronize()
+    else:
+        for k in counts:
+            p.res[k][:] = 0xa5a5a5a5
+    mem = capi.MEM_DEVICE if device else capi.MEM_HOST
+    capi._check(getattr(capi.lib(), symbol)(ctx._h, C.byref(p.job), C.byref(p.prm), mem, C.byref(p.out)))
+    if device:
+        torch.cuda.synchronize()
+        p.from_device()
+    else:
+        assert all(int(x) == 0 for k in counts for x in p.res[k])
+    return p.results(), ctx.last_call_stats()["host_syncs"]
+
+
+@pytest.mark.parametrize("device", [False, True])
+def test_a_batch_without_any_trace_clears_the_counts(ctx, batch, device):
+    """[[], []] over two references: nrows / ncol / cons_len come back zero whatever they held, nothing else runs.  The call does
+    not wait for the device over host arrays and waits once, behind its three clears, over device arrays: 0 and 1 are what the
+    library reported for this call before the group plumbing of assemble and de novo became one copy."""
+    from tracy_amd import capi
+    groups, refs, kinds, want = batch
+    got, syncs = run_traceless(ctx, capi.PreparedAssemble([[], []], refs[:2], SCORE, FRACMATCH, CALLED), "tracyhip_assemble_traces", device)
+    for k in ("nrows", "ncol", "cons_len"):
+        assert got[k].tolist() == [0, 0], k
+    assert got["rows"] == [[], []] and got["gapped"] == [b"", b""] and len(got["rank"]) == 0
+    assert syncs == (1 if device else 0)
+
+
 # ---- the launch loops: long traces (sweeps of several passes), N rows (the 25-term body), the repeat on int32 ----------------
 
 LONG_TRACES = (700, 520, 300, 130)  # columns, over a reference of 900

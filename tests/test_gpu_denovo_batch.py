@@ -123,6 +123,19 @@ def test_empty_batch_and_bad_input(ctx):
     assert e.value.code == capi.ERR_RANGE
 
 
+@pytest.mark.parametrize("device", [False, True])
+def test_a_batch_without_any_trace_clears_the_counts(ctx, device):
+    """[[], []]: nrows / ncol / cons_len come back zero whatever they held, with no wait for the device over host arrays and one over
+    device arrays (test_gpu_assemble_batch.py has the same case for the chain)"""
+    from tracy_amd import capi
+    from test_gpu_assemble_batch import run_traceless
+    got, syncs = run_traceless(ctx, capi.PreparedDenovo([[], []], dc.SCORE), "tracyhip_denovo_traces", device)
+    for k in ("nrows", "ncol", "cons_len"):
+        assert got[k].tolist() == [0, 0], k
+    assert got["rows"] == [[], []] and got["gapped"] == [b"", b""] and len(got["forward"]) == 0
+    assert syncs == (1 if device else 0)
+
+
 # ---- the command line -------------------------------------------------------------------------------------------------
 
 

@@ -401,10 +401,52 @@ class ConsensusResult(C.Structure):
                 ("offset", C.POINTER(C.c_uint64))]
 
 
-class PreparedConsensus:
+class _Prepared:
+    """what the prepared batch objects share: `job` / `prm` / `out` structs over host arrays -- `keep`, the payload PackedSeqs, one per
+    job field of _PAYLOADS; `res`, the result arrays by the field of `out` that points to them -- and their device form"""
+
+    _PAYLOADS = ()
+
+    def _bind_results(self, out, res):
+        self.out, self.res = out, res
+        for k, v in res.items():
+            setattr(out, k, v.ctypes.data)
+
+    def to_device(self):
+        """payloads and result arrays as torch tensors on the current device (kept alive by this object)"""
+        import torch
+        self.dkeep = [torch.from_numpy(p.data).cuda() for p in self.keep]
+        for name, p, d in zip(self._PAYLOADS, self.keep, self.dkeep):
+            setattr(self.job, name, p.seqset(d.data_ptr()))
+        self.dres = {k: torch.zeros(v.nbytes, dtype=torch.uint8, device="cuda") for k, v in self.res.items()}
+        for k, v in self.dres.items():
+            setattr(self.out, k, v.data_ptr())
+        torch.cuda.synchronize()
+
+    def from_device(self):
+        for k, v in self.dres.items():
+            self.res[k] = v.cpu().numpy().view(self.res[k].dtype)
+
+
+def _run_prepared(ctx, symbol, p, device):
+    """one call of the library on a prepared batch, over host arrays or (device=True) over device memory copied back afterwards"""
+    fn = getattr(lib(), symbol)
+    if device:
+        import torch
+        p.to_device()
+        _check(fn(ctx._h, C.byref(p.job), C.byref(p.prm), MEM_DEVICE, C.byref(p.out)))
+        torch.cuda.synchronize()
+        p.from_device()
+    else:
+        _check(fn(ctx._h, C.byref(p.job), C.byref(p.prm), MEM_HOST, C.byref(p.out)))
+    return p.results()
+
+
+class PreparedConsensus(_Prepared):
     """host-buffer job / result structs of tracyhip_consensus_traces (everything they point to is kept alive by this object).
     first / second: lists of float32 [6][len] (the trimmed profile of trace 1, the trimmed FORWARD profile of trace 2)."""
 
+    _PAYLOADS = ("first", "second")
     _PAIR = (("score_fwd", np.int32), ("score_rev", np.int32), ("forward", np.uint8), ("score", np.int32), ("num_aligned", np.uint32),
              ("num_match", np.uint32), ("status", np.int32), ("ops_len", np.uint32), ("cons_len", np.uint32))
 
@@ -428,31 +470,12 @@ class PreparedConsensus:
         if n:
             off[1:n] = np.cumsum(cap)[:-1]
         total = max(int(cap.sum()) if n else 0, 1)
-        res = self.res = {k: np.zeros(max(n, 1), dt) for k, dt in self._PAIR}
+        res = {k: np.zeros(max(n, 1), dt) for k, dt in self._PAIR}
         res.update(rows0=np.zeros(total, np.uint8), rows1=np.zeros(total, np.uint8), cons=np.zeros(total, np.uint8),
                    qual=np.zeros(total, np.uint16))
-        out = self.out = ConsensusResult()
-        for k, v in res.items():
-            setattr(out, k, v.ctypes.data)
-        out.offset = off.ctypes.data_as(C.POINTER(C.c_uint64))
+        self._bind_results(ConsensusResult(), res)
+        self.out.offset = off.ctypes.data_as(C.POINTER(C.c_uint64))
         self.prm = Params(*params) if len(params) == 6 else Params(params[0], params[1], params[2], params[3], 1, 1)
-
-    def to_device(self):
-        """payloads and result arrays as torch tensors on the current device; returns the tensors that must stay alive"""
-        import torch
-        p1, p2 = self.keep[0], self.keep[1]
-        d1, d2 = torch.from_numpy(p1.data).cuda(), torch.from_numpy(p2.data).cuda()
-        self.job.first = p1.seqset(d1.data_ptr())
-        self.job.second = p2.seqset(d2.data_ptr())
-        self.dres = {k: torch.zeros(v.nbytes, dtype=torch.uint8, device="cuda") for k, v in self.res.items()}
-        for k, v in self.dres.items():
-            setattr(self.out, k, v.data_ptr())
-        self.dkeep = [d1, d2]
-        torch.cuda.synchronize()
-
-    def from_device(self):
-        for k, v in self.dres.items():
-            self.res[k] = v.cpu().numpy().view(self.res[k].dtype)
 
     def results(self):
         """per-pair arrays, and lists rows (row0, row1 bytes), cons (bytes), qual (uint16 arrays)"""
@@ -470,15 +493,7 @@ def _consensus_traces(self, first, second, params, union=True, iupac=False, min_
     on both axes (the command's AlignConfig<true,true>), or all six tracyhip_params fields.  device=True: payloads and results in
     device memory (TRACYHIP_MEM_DEVICE), copied back afterwards."""
     p = PreparedConsensus(first, second, params, union, iupac, min_overlap, match_fraction)
-    if device:
-        import torch
-        p.to_device()
-        _check(lib().tracyhip_consensus_traces(self._h, C.byref(p.job), C.byref(p.prm), MEM_DEVICE, C.byref(p.out)))
-        torch.cuda.synchronize()
-        p.from_device()
-    else:
-        _check(lib().tracyhip_consensus_traces(self._h, C.byref(p.job), C.byref(p.prm), MEM_HOST, C.byref(p.out)))
-    return p.results()
+    return _run_prepared(self, "tracyhip_consensus_traces", p, device)
 
 
 Context.consensus_traces = _consensus_traces
@@ -505,75 +520,38 @@ class AssembleResult(C.Structure):
                 ("cons_len", C.c_void_p), ("rows_offset", C.POINTER(C.c_uint64)), ("col_offset", C.POINTER(C.c_uint64))]
 
 
-class PreparedAssemble:
-    """host-buffer job / result structs of tracyhip_assemble_traces (everything they point to is kept alive by this object).
-    groups: one list of float32 [6][len] trace profiles (trimmed, forward) per group; references: one float32 [6][len] profile per
-    group, or fewer with ref_index."""
+class _PreparedGroups(_Prepared):
+    """the two calls over groups of traces: group_first, the per-group capacities and offsets of tracy_hip.h, the per-group results"""
 
-    _TRACE = (("score_fwd", np.int32), ("score_rev", np.int32), ("forward", np.uint8), ("rank", np.uint32))
     _GROUP = (("nrows", np.uint32), ("ncol", np.uint32), ("cons_len", np.uint32))
 
-    def __init__(self, groups, references, params, match_fraction=0.5, fraction_called=0.1, include_reference=False, ref_index=None):
+    def _pack_groups(self, groups):
+        """the traces of every group in one PackedSeqs, and the summed trace length of every group; sets ng, nt, first"""
         ng = self.ng = len(groups)
-        flat = [p for g in groups for p in g]
-        pt = PackedSeqs(flat, SEQ_PROFILE)
-        pr = references if isinstance(references, PackedSeqs) else PackedSeqs(references, SEQ_PROFILE)
-        nt = self.nt = pt.count
+        pt = PackedSeqs([p for g in groups for p in g], SEQ_PROFILE)
+        self.nt = pt.count
         first = self.first = np.zeros(ng + 1, np.uint32)
         first[1:] = np.cumsum([len(g) for g in groups], dtype=np.int64) if ng else 0
-        ridx = self.ridx = None if ref_index is None else np.ascontiguousarray(ref_index, dtype=np.uint32)
-        self.keep = [pt, pr]
-        job = self.job = AssembleJob()
-        job.ngroups = ng
-        job.traces = pt.seqset()
-        job.group_first = first.ctypes.data_as(C.POINTER(C.c_uint32))
-        job.references = pr.seqset()
-        if ridx is not None:
-            job.ref_index = ridx.ctypes.data_as(C.POINTER(C.c_uint32))
-        job.match_fraction = float(match_fraction)
-        job.fraction_called = float(fraction_called)
-        job.include_reference = 1 if include_reference else 0
-        # capacities (tracy_hip.h): (K + 1) * (n_ref + sum len) row bytes, n_ref + sum len columns
-        bound = np.zeros(max(ng, 1), np.uint64)
-        rowcap = np.zeros(max(ng, 1), np.uint64)
-        for g in range(ng):
-            r = g if ridx is None else int(ridx[g])
-            n_ref = int(pr.length[r]) if r < pr.count else 0
-            bound[g] = n_ref + int(pt.length[int(first[g]):int(first[g + 1])].sum())
-            rowcap[g] = (len(groups[g]) + 1) * bound[g]
+        return pt, [int(pt.length[int(first[g]):int(first[g + 1])].sum()) for g in range(ng)]
+
+    def _bind_groups(self, out, bounds):
+        """the result arrays of `out`; bounds: per group the (rows, columns) its alignment can reach at most"""
+        ng, nt = self.ng, self.nt
+        rowcap = np.array([r * c for r, c in bounds], np.uint64)
+        colcap = np.array([c for _, c in bounds], np.uint64)
         self.roff = np.zeros(max(ng, 1), np.uint64)
         self.coff = np.zeros(max(ng, 1), np.uint64)
         if ng:
-            self.roff[1:ng] = np.cumsum(rowcap[:ng])[:-1]
-            self.coff[1:ng] = np.cumsum(bound[:ng])[:-1]
-        res = self.res = {k: np.zeros(max(nt, 1), dt) for k, dt in self._TRACE}
+            self.roff[1:] = np.cumsum(rowcap)[:-1]
+            self.coff[1:] = np.cumsum(colcap)[:-1]
+        res = {k: np.zeros(max(nt, 1), dt) for k, dt in self._TRACE}
         res.update({k: np.zeros(max(ng, 1), dt) for k, dt in self._GROUP})
-        ctot = max(int(bound[:ng].sum()) if ng else 0, 1)
-        res.update(rows=np.zeros(max(int(rowcap[:ng].sum()) if ng else 0, 1), np.uint8), gapped=np.zeros(ctot, np.uint8),
+        ctot = max(int(colcap.sum()), 1)
+        res.update(rows=np.zeros(max(int(rowcap.sum()), 1), np.uint8), gapped=np.zeros(ctot, np.uint8),
                    cons=np.zeros(ctot, np.uint8), qual=np.zeros(ctot, np.uint8))
-        out = self.out = AssembleResult()
-        for k, v in res.items():
-            setattr(out, k, v.ctypes.data)
+        self._bind_results(out, res)
         out.rows_offset = self.roff.ctypes.data_as(C.POINTER(C.c_uint64))
         out.col_offset = self.coff.ctypes.data_as(C.POINTER(C.c_uint64))
-        self.prm = Params(*params) if len(params) == 6 else Params(params[0], params[1], params[2], params[3], 1, 0)
-
-    def to_device(self):
-        """payloads and result arrays as torch tensors on the current device"""
-        import torch
-        pt, pr = self.keep
-        d1, d2 = torch.from_numpy(pt.data).cuda(), torch.from_numpy(pr.data).cuda()
-        self.job.traces = pt.seqset(d1.data_ptr())
-        self.job.references = pr.seqset(d2.data_ptr())
-        self.dres = {k: torch.zeros(v.nbytes, dtype=torch.uint8, device="cuda") for k, v in self.res.items()}
-        for k, v in self.dres.items():
-            setattr(self.out, k, v.data_ptr())
-        self.dkeep = [d1, d2]
-        torch.cuda.synchronize()
-
-    def from_device(self):
-        for k, v in self.dres.items():
-            self.res[k] = v.cpu().numpy().view(self.res[k].dtype)
 
     def results(self):
         """per-trace and per-group arrays, and per group: rows (list of bytes, [] when nrows is 0), gapped, cons, qual (bytes)"""
@@ -592,21 +570,46 @@ class PreparedAssemble:
         return out
 
 
+class PreparedAssemble(_PreparedGroups):
+    """host-buffer job / result structs of tracyhip_assemble_traces (everything they point to is kept alive by this object).
+    groups: one list of float32 [6][len] trace profiles (trimmed, forward) per group; references: one float32 [6][len] profile per
+    group, or fewer with ref_index."""
+
+    _PAYLOADS = ("traces", "references")
+    _TRACE = (("score_fwd", np.int32), ("score_rev", np.int32), ("forward", np.uint8), ("rank", np.uint32))
+
+    def __init__(self, groups, references, params, match_fraction=0.5, fraction_called=0.1, include_reference=False, ref_index=None):
+        pt, sums = self._pack_groups(groups)
+        pr = references if isinstance(references, PackedSeqs) else PackedSeqs(references, SEQ_PROFILE)
+        ridx = self.ridx = None if ref_index is None else np.ascontiguousarray(ref_index, dtype=np.uint32)
+        self.keep = [pt, pr]
+        job = self.job = AssembleJob()
+        job.ngroups = self.ng
+        job.traces = pt.seqset()
+        job.group_first = self.first.ctypes.data_as(C.POINTER(C.c_uint32))
+        job.references = pr.seqset()
+        if ridx is not None:
+            job.ref_index = ridx.ctypes.data_as(C.POINTER(C.c_uint32))
+        job.match_fraction = float(match_fraction)
+        job.fraction_called = float(fraction_called)
+        job.include_reference = 1 if include_reference else 0
+        # capacities (tracy_hip.h): (K + 1) * (n_ref + sum len) row bytes, n_ref + sum len columns
+        bounds = []
+        for g, s in enumerate(sums):
+            r = g if ridx is None else int(ridx[g])
+            n_ref = int(pr.length[r]) if r < pr.count else 0
+            bounds.append((len(groups[g]) + 1, n_ref + s))
+        self._bind_groups(AssembleResult(), bounds)
+        self.prm = Params(*params) if len(params) == 6 else Params(params[0], params[1], params[2], params[3], 1, 0)
+
+
 def _assemble_traces(self, groups, references, params, match_fraction=0.5, fraction_called=0.1, include_reference=False, ref_index=None,
                      device=False):
     """tracyhip_assemble_traces: the reference-guided chain of `tracy assemble -r` for a batch of trace groups.  params: (match,
     mismatch, go, ge) with the command's AlignConfig<true,false>, or all six tracyhip_params fields.  device=True: payloads and
     results in device memory (TRACYHIP_MEM_DEVICE), copied back afterwards."""
     p = PreparedAssemble(groups, references, params, match_fraction, fraction_called, include_reference, ref_index)
-    if device:
-        import torch
-        p.to_device()
-        _check(lib().tracyhip_assemble_traces(self._h, C.byref(p.job), C.byref(p.prm), MEM_DEVICE, C.byref(p.out)))
-        torch.cuda.synchronize()
-        p.from_device()
-    else:
-        _check(lib().tracyhip_assemble_traces(self._h, C.byref(p.job), C.byref(p.prm), MEM_HOST, C.byref(p.out)))
-    return p.results()
+    return _run_prepared(self, "tracyhip_assemble_traces", p, device)
 
 
 Context.assemble_traces = _assemble_traces
@@ -632,80 +635,25 @@ class DenovoResult(C.Structure):
                 ("rows_offset", C.POINTER(C.c_uint64)), ("col_offset", C.POINTER(C.c_uint64))]
 
 
-class PreparedDenovo:
+class PreparedDenovo(_PreparedGroups):
     """host-buffer job / result structs of tracyhip_denovo_traces (everything they point to is kept alive by this object).
     groups: one list of float32 [6][len] trace profiles (trimmed, forward) per group."""
 
+    _PAYLOADS = ("traces",)
     _TRACE = (("forward", np.uint8), ("partner", np.uint32), ("row", np.uint32))
-    _GROUP = (("nrows", np.uint32), ("ncol", np.uint32), ("cons_len", np.uint32))
 
     def __init__(self, groups, params, match_fraction=0.5, fraction_called=0.1):
-        ng = self.ng = len(groups)
-        pt = PackedSeqs([p for g in groups for p in g], SEQ_PROFILE)
-        nt = self.nt = pt.count
-        first = self.first = np.zeros(ng + 1, np.uint32)
-        first[1:] = np.cumsum([len(g) for g in groups], dtype=np.int64) if ng else 0
+        pt, sums = self._pack_groups(groups)
         self.keep = [pt]
         job = self.job = DenovoJob()
-        job.ngroups = ng
+        job.ngroups = self.ng
         job.traces = pt.seqset()
-        job.group_first = first.ctypes.data_as(C.POINTER(C.c_uint32))
+        job.group_first = self.first.ctypes.data_as(C.POINTER(C.c_uint32))
         job.match_fraction = float(match_fraction)
         job.fraction_called = float(fraction_called)
         # capacities (tracy_hip.h): K * sum len row bytes, sum len columns
-        bound = np.zeros(max(ng, 1), np.uint64)
-        rowcap = np.zeros(max(ng, 1), np.uint64)
-        for g in range(ng):
-            bound[g] = int(pt.length[int(first[g]):int(first[g + 1])].sum())
-            rowcap[g] = len(groups[g]) * bound[g]
-        self.roff = np.zeros(max(ng, 1), np.uint64)
-        self.coff = np.zeros(max(ng, 1), np.uint64)
-        if ng:
-            self.roff[1:ng] = np.cumsum(rowcap[:ng])[:-1]
-            self.coff[1:ng] = np.cumsum(bound[:ng])[:-1]
-        res = self.res = {k: np.zeros(max(nt, 1), dt) for k, dt in self._TRACE}
-        res.update({k: np.zeros(max(ng, 1), dt) for k, dt in self._GROUP})
-        ctot = max(int(bound[:ng].sum()) if ng else 0, 1)
-        res.update(rows=np.zeros(max(int(rowcap[:ng].sum()) if ng else 0, 1), np.uint8), gapped=np.zeros(ctot, np.uint8),
-                   cons=np.zeros(ctot, np.uint8), qual=np.zeros(ctot, np.uint8))
-        out = self.out = DenovoResult()
-        for k, v in res.items():
-            setattr(out, k, v.ctypes.data)
-        out.rows_offset = self.roff.ctypes.data_as(C.POINTER(C.c_uint64))
-        out.col_offset = self.coff.ctypes.data_as(C.POINTER(C.c_uint64))
+        self._bind_groups(DenovoResult(), [(len(g), s) for g, s in zip(groups, sums)])
         self.prm = Params(*params) if len(params) == 6 else Params(params[0], params[1], params[2], params[3], 1, 1)
-
-    def to_device(self):
-        """payload and result arrays as torch tensors on the current device"""
-        import torch
-        pt, = self.keep
-        d1 = torch.from_numpy(pt.data).cuda()
-        self.job.traces = pt.seqset(d1.data_ptr())
-        self.dres = {k: torch.zeros(v.nbytes, dtype=torch.uint8, device="cuda") for k, v in self.res.items()}
-        for k, v in self.dres.items():
-            setattr(self.out, k, v.data_ptr())
-        self.dkeep = [d1]
-        torch.cuda.synchronize()
-
-    def from_device(self):
-        for k, v in self.dres.items():
-            self.res[k] = v.cpu().numpy().view(self.res[k].dtype)
-
-    def results(self):
-        """per-trace and per-group arrays, and per group: rows (list of bytes, [] when nrows is 0), gapped, cons, qual (bytes)"""
-        res, ng, nt = self.res, self.ng, self.nt
-        out = {k: res[k][:nt].copy() for k, _ in self._TRACE}
-        out.update({k: res[k][:ng].copy() for k, _ in self._GROUP})
-        rows, gapped, cons, qual = [], [], [], []
-        for g in range(ng):
-            nr, nc, cl = int(res["nrows"][g]), int(res["ncol"][g]), int(res["cons_len"][g])
-            ro, co = int(self.roff[g]), int(self.coff[g])
-            rows.append([res["rows"][ro + i * nc:ro + (i + 1) * nc].tobytes() for i in range(nr)])
-            gapped.append(res["gapped"][co:co + (nc if nr else 0)].tobytes())
-            cons.append(res["cons"][co:co + (cl if nr else 0)].tobytes())
-            qual.append(res["qual"][co:co + (cl if nr else 0)].tobytes())
-        out.update(rows=rows, gapped=gapped, cons=cons, qual=qual)
-        return out
 
 
 def _denovo_traces(self, groups, params, match_fraction=0.5, fraction_called=0.1, device=False):
@@ -713,15 +661,7 @@ def _denovo_traces(self, groups, params, match_fraction=0.5, fraction_called=0.1
     params: (match, mismatch, go, ge) with the command's AlignConfig<true,true>, or all six tracyhip_params fields.  device=True:
     payloads and results in device memory (TRACYHIP_MEM_DEVICE), copied back afterwards."""
     p = PreparedDenovo(groups, params, match_fraction, fraction_called)
-    if device:
-        import torch
-        p.to_device()
-        _check(lib().tracyhip_denovo_traces(self._h, C.byref(p.job), C.byref(p.prm), MEM_DEVICE, C.byref(p.out)))
-        torch.cuda.synchronize()
-        p.from_device()
-    else:
-        _check(lib().tracyhip_denovo_traces(self._h, C.byref(p.job), C.byref(p.prm), MEM_HOST, C.byref(p.out)))
-    return p.results()
+    return _run_prepared(self, "tracyhip_denovo_traces", p, device)
 
 
 Context.denovo_traces = _denovo_traces

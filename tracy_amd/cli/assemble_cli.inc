@@ -261,39 +261,67 @@ struct AsmGroup {  // the manifest lines of one outprefix, in manifest order
   std::string gapped, cs, qstr;
 };
 
+// What both device calls take and give per group: the traces of `gs` in one pack with group_first, and the per-group result arrays
+// with every group's offset.  bound(group, summed columns of its traces): the columns tracy_hip.h asks for it, over K + more_rows rows.
+struct GroupPack {
+  detail::ProfilePack tp;
+  std::vector<uint32_t> first, nrows, ncol, clen;
+  std::vector<uint64_t> roff, coff;
+  std::vector<uint8_t> rows, gapped, cons, qual;
+  template <class Bound>
+  GroupPack(std::vector<AsmGroup*> const& gs, uint64_t more_rows, Bound bound) : first(1, 0), nrows(gs.size()), ncol(gs.size()), clen(gs.size()) {
+    uint64_t rtot = 0, ctot = 0;
+    for (AsmGroup const* a : gs) {
+      uint64_t sum = 0;
+      for (AsmTrace const& t : a->traces) { tp.add(t.prof); sum += t.prof.cols; }
+      first.push_back((uint32_t)tp.off.size());
+      roff.push_back(rtot);
+      coff.push_back(ctot);
+      rtot += (a->traces.size() + more_rows) * bound(*a, sum);
+      ctot += bound(*a, sum);
+    }
+    rows.resize(std::max<uint64_t>(rtot, 1));
+    gapped = cons = qual = std::vector<uint8_t>(std::max<uint64_t>(ctot, 1));
+  }
+  // align / gapped / cs / qstr of every group from the arrays; the profiles of its traces are released
+  void unpack(std::vector<AsmGroup*> const& gs) const {
+    for (std::size_t g = 0; g < gs.size(); ++g) {
+      AsmGroup& a = *gs[g];
+      a.align.assign(nrows[g], std::string());
+      for (uint32_t r = 0; r < nrows[g]; ++r)
+        a.align[r].assign(reinterpret_cast<const char*>(rows.data() + roff[g] + (uint64_t)r * ncol[g]), ncol[g]);
+      if (nrows[g]) {
+        a.gapped.assign(reinterpret_cast<const char*>(gapped.data() + coff[g]), ncol[g]);
+        a.cs.assign(reinterpret_cast<const char*>(cons.data() + coff[g]), clen[g]);
+        a.qstr.assign(reinterpret_cast<const char*>(qual.data() + coff[g]), clen[g]);
+      }
+      for (AsmTrace& t : a.traces) t.prof = Profile();
+    }
+  }
+};
+
 // all chains of `gs` (every one loaded) through one device call; fills scoreIdx / excluded / align / gapped / cs / qstr
 bool assemble_device(tracyhip_ctx* ctx, AssembleConfig const& c, detail::ProfilePack& refs, std::vector<AsmGroup*> const& gs) {
   const uint32_t ng = (uint32_t)gs.size();
   if (ng == 0) return true;
-  detail::ProfilePack tp;
-  std::vector<uint32_t> first(ng + 1, 0), ridx(ng);
-  std::vector<uint64_t> roff(ng), coff(ng);
-  uint64_t rtot = 0, ctot = 0;
-  for (uint32_t g = 0; g < ng; ++g) {
-    uint64_t bound = refs.len[gs[g]->ref];  // capacities of tracy_hip.h: (K + 1) * (n_ref + sum len) row bytes, n_ref + sum len columns
-    for (AsmTrace const& t : gs[g]->traces) { tp.add(t.prof); bound += t.prof.cols; }
-    first[g + 1] = (uint32_t)tp.off.size();
-    ridx[g] = gs[g]->ref;
-    roff[g] = rtot;
-    coff[g] = ctot;
-    rtot += (gs[g]->traces.size() + 1) * bound;
-    ctot += bound;
-  }
-  const uint32_t nt = first[ng];
+  GroupPack p(gs, 1, [&](AsmGroup const& a, uint64_t sum) { return (uint64_t)refs.len[a.ref] + sum; });  // (K + 1) x (n_ref + sum len)
+  std::vector<uint32_t> ridx(ng);
+  for (uint32_t g = 0; g < ng; ++g) ridx[g] = gs[g]->ref;
+  const uint32_t nt = p.first[ng];
   tracyhip_assemble_job job{};
   job.ngroups = ng;
-  job.traces = tp.set();
-  job.group_first = first.data();
+  job.traces = p.tp.set();
+  job.group_first = p.first.data();
   job.references = refs.set();
   job.ref_index = ridx.data();
   job.match_fraction = c.matchFraction;
   job.fraction_called = c.fractionCalled;
   job.include_reference = c.incRef ? 1u : 0u;
   std::vector<int32_t> sf(nt), sr(nt);
-  std::vector<uint8_t> fwd(nt), rows(std::max<uint64_t>(rtot, 1)), gapped(std::max<uint64_t>(ctot, 1)), cons(gapped.size()), qual(gapped.size());
-  std::vector<uint32_t> rank(nt), nrows(ng), ncol(ng), clen(ng);
-  tracyhip_assemble_result res{sf.data(), sr.data(), fwd.data(), rank.data(), nrows.data(), ncol.data(), rows.data(), gapped.data(),
-                               cons.data(), qual.data(), clen.data(), roff.data(), coff.data()};
+  std::vector<uint8_t> fwd(nt);
+  std::vector<uint32_t> rank(nt);
+  tracyhip_assemble_result res{sf.data(), sr.data(), fwd.data(), rank.data(), p.nrows.data(), p.ncol.data(), p.rows.data(), p.gapped.data(),
+                               p.cons.data(), p.qual.data(), p.clen.data(), p.roff.data(), p.coff.data()};
   tracyhip_params semi{c.match, c.mismatch, c.gapopen, c.gapext, 1, 0};  // AlignConfig<true,false>
   if (tracyhip_assemble_traces(ctx, &job, &semi, TRACYHIP_MEM_HOST, &res) != TRACYHIP_OK) {
     gpu_fail("assembly");
@@ -301,23 +329,14 @@ bool assemble_device(tracyhip_ctx* ctx, AssembleConfig const& c, detail::Profile
   }
   for (uint32_t g = 0; g < ng; ++g) {
     AsmGroup& a = *gs[g];
-    const uint32_t K = first[g + 1] - first[g];
-    a.scoreIdx.assign(nrows[g] ? nrows[g] - 1 : 0, TraceScore{0, 0, 0, true});
-    for (uint32_t i = 0; i < K; ++i) {
-      const uint32_t t = first[g] + i;
+    a.scoreIdx.assign(p.nrows[g] ? p.nrows[g] - 1 : 0, TraceScore{0, 0, 0, true});
+    for (uint32_t t = p.first[g]; t < p.first[g + 1]; ++t) {
+      const uint32_t i = t - p.first[g];
       if (rank[t] == UINT32_MAX) a.excluded.push_back(i);
       else a.scoreIdx[rank[t]] = TraceScore{std::max(sf[t], sr[t]), (int32_t)i, (int32_t)rank[t], fwd[t] != 0};
     }
-    a.align.assign(nrows[g], std::string());
-    for (uint32_t r = 0; r < nrows[g]; ++r)
-      a.align[r].assign(reinterpret_cast<const char*>(rows.data() + roff[g] + (uint64_t)r * ncol[g]), ncol[g]);
-    if (nrows[g]) {
-      a.gapped.assign(reinterpret_cast<const char*>(gapped.data() + coff[g]), ncol[g]);
-      a.cs.assign(reinterpret_cast<const char*>(cons.data() + coff[g]), clen[g]);
-      a.qstr.assign(reinterpret_cast<const char*>(qual.data() + coff[g]), clen[g]);
-    }
-    for (AsmTrace& t : a.traces) t.prof = Profile();
   }
+  p.unpack(gs);
   return true;
 }
 
@@ -325,30 +344,18 @@ bool assemble_device(tracyhip_ctx* ctx, AssembleConfig const& c, detail::Profile
 bool denovo_device(tracyhip_ctx* ctx, AssembleConfig const& c, std::vector<AsmGroup*> const& gs) {
   const uint32_t ng = (uint32_t)gs.size();
   if (ng == 0) return true;
-  detail::ProfilePack tp;
-  std::vector<uint32_t> first(ng + 1, 0);
-  std::vector<uint64_t> roff(ng), coff(ng);
-  uint64_t rtot = 0, ctot = 0;
-  for (uint32_t g = 0; g < ng; ++g) {
-    uint64_t bound = 0;  // capacities of tracy_hip.h: K * sum len row bytes, sum len columns
-    for (AsmTrace const& t : gs[g]->traces) { tp.add(t.prof); bound += t.prof.cols; }
-    first[g + 1] = (uint32_t)tp.off.size();
-    roff[g] = rtot;
-    coff[g] = ctot;
-    rtot += gs[g]->traces.size() * bound;
-    ctot += bound;
-  }
-  const uint32_t nt = first[ng];
+  GroupPack p(gs, 0, [](AsmGroup const&, uint64_t sum) { return sum; });  // K x sum len
+  const uint32_t nt = p.first[ng];
   tracyhip_denovo_job job{};
   job.ngroups = ng;
-  job.traces = tp.set();
-  job.group_first = first.data();
+  job.traces = p.tp.set();
+  job.group_first = p.first.data();
   job.match_fraction = c.matchFraction;
   job.fraction_called = c.fractionCalled;
-  std::vector<uint8_t> fwd(nt), rows(std::max<uint64_t>(rtot, 1)), gapped(std::max<uint64_t>(ctot, 1)), cons(gapped.size()), qual(gapped.size());
-  std::vector<uint32_t> partner(nt), row(nt), nrows(ng), ncol(ng), clen(ng);
-  tracyhip_denovo_result res{fwd.data(), partner.data(), row.data(), nrows.data(), ncol.data(), rows.data(), gapped.data(),
-                             cons.data(), qual.data(), clen.data(), roff.data(), coff.data()};
+  std::vector<uint8_t> fwd(nt);
+  std::vector<uint32_t> partner(nt), row(nt);
+  tracyhip_denovo_result res{fwd.data(), partner.data(), row.data(), p.nrows.data(), p.ncol.data(), p.rows.data(), p.gapped.data(),
+                             p.cons.data(), p.qual.data(), p.clen.data(), p.roff.data(), p.coff.data()};
   tracyhip_params endfree{c.match, c.mismatch, c.gapopen, c.gapext, 1, 1};  // AlignConfig<true,true>
   if (tracyhip_denovo_traces(ctx, &job, &endfree, TRACYHIP_MEM_HOST, &res) != TRACYHIP_OK) {
     gpu_fail("assembly");
@@ -356,25 +363,16 @@ bool denovo_device(tracyhip_ctx* ctx, AssembleConfig const& c, std::vector<AsmGr
   }
   for (uint32_t g = 0; g < ng; ++g) {
     AsmGroup& a = *gs[g];
-    const uint32_t K = first[g + 1] - first[g];
-    a.seqidx.assign(nrows[g], 0);
-    for (uint32_t i = 0; i < K; ++i) {
-      const uint32_t t = first[g] + i;
+    a.seqidx.assign(p.nrows[g], 0);
+    for (uint32_t t = p.first[g]; t < p.first[g + 1]; ++t) {
+      const uint32_t i = t - p.first[g];
       if (partner[t] == UINT32_MAX) { a.excluded.push_back(i); continue; }
-      if (row[t] != UINT32_MAX && row[t] < nrows[g]) a.seqidx[row[t]] = (uint32_t)a.idxMap.size();
+      if (row[t] != UINT32_MAX && row[t] < p.nrows[g]) a.seqidx[row[t]] = (uint32_t)a.idxMap.size();
       a.idxMap.push_back(i);
       a.fwd.push_back(fwd[t] != 0);
     }
-    a.align.assign(nrows[g], std::string());
-    for (uint32_t r = 0; r < nrows[g]; ++r)
-      a.align[r].assign(reinterpret_cast<const char*>(rows.data() + roff[g] + (uint64_t)r * ncol[g]), ncol[g]);
-    if (nrows[g]) {
-      a.gapped.assign(reinterpret_cast<const char*>(gapped.data() + coff[g]), ncol[g]);
-      a.cs.assign(reinterpret_cast<const char*>(cons.data() + coff[g]), clen[g]);
-      a.qstr.assign(reinterpret_cast<const char*>(qual.data() + coff[g]), clen[g]);
-    }
-    for (AsmTrace& t : a.traces) t.prof = Profile();
   }
+  p.unpack(gs);
   return true;
 }
 

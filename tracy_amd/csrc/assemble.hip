@@ -6,7 +6,9 @@
 // group of a chunk that has more than k matching traces is one batch -- msa_profile of the rows so far (written at the end of step
 // k - 1), gotoh(trace_k, that profile) through the traceback kernels of tracyhip_gotoh_align (fused walk), msa_merge with the trace
 // as row 0.  Step 0 is gotoh(best, reference): both sides of its merge are input profiles, shown as their _profileConsChar rows.
-// msa_consensus closes a chunk.  (The three row-block kernels are msa_batch.hip's, shared with denovo.hip.)
+// msa_consensus closes a chunk.  The three row-block kernels are msa_batch.hip's, shared with denovo.hip, and so is the host code
+// around them (GroupOut, TraceBatch, msa_merge_batch, msa_consensus_batch, prof_score_stage); what stays here is the chain's own
+// plan: who matches, in which order, which groups share a chunk, what step k of a group aligns against.
 //
 // The columns of step k are the op count of step k - 1, which only the device knows: the host reads the op counts back once per step
 // and builds the next step's descriptors from them.  Workspaces are sized from the bound  columns <= n_ref + sum of the trace lengths
@@ -68,12 +70,14 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
 
   // ---- geometry: the column bound of every group and where its pieces live in the call's own buffers ----
   std::vector<uint64_t> bound(ng), cg(ng + 1, 0), rg(ng + 1, 0), sg(ng + 1, 0);  // columns; prefix sums of columns, row bytes, span pairs
+  std::vector<uint32_t> grp(nt);  // trace to group
   uint64_t eT = 0, eR = 0, max_mn = 0, ext_rows = 0, ext_col = 0;
   for (uint32_t g = 0; g < ng; ++g) {
     const uint32_t r = ref_of(g);
     uint64_t b = sR.length[r];
     eR = std::max<uint64_t>(eR, sR.offset[r] + 6ull * sR.length[r]);
     for (uint32_t i = gf[g]; i < gf[g + 1]; ++i) {
+      grp[i - t0] = g;
       b += sT.length[i];
       eT = std::max<uint64_t>(eT, sT.offset[i] + 6ull * sT.length[i]);
     }
@@ -91,16 +95,8 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   int rc;
   if ((rc = check_params(prm, max_mn))) return rc;
   if (max_mn > 0xffffffffull) return set_error(TRACYHIP_ERR_RANGE, "a group's column bound exceeds 2^32");
-  if (nt == 0) {  // groups without traces: nrows 0 everywhere
-    if (mem == TRACYHIP_MEM_HOST) {
-      std::memset(out->nrows, 0, 4 * (size_t)ng); std::memset(out->ncol, 0, 4 * (size_t)ng); std::memset(out->cons_len, 0, 4 * (size_t)ng);
-    } else {
-      HIP_TRY(hipMemsetAsync(out->nrows, 0, 4 * (size_t)ng, st)); HIP_TRY(hipMemsetAsync(out->ncol, 0, 4 * (size_t)ng, st));
-      HIP_TRY(hipMemsetAsync(out->cons_len, 0, 4 * (size_t)ng, st));
-      HIP_TRY(ctx_sync(ctx));
-    }
-    return TRACYHIP_OK;
-  }
+  GroupOut go(ng, *out);
+  if (nt == 0) return go.clear_counts(ctx, mem);  // groups without traces: nrows 0 everywhere
 
   // ---- inputs: traces = [forward | revcomp] in one buffer, references where the caller has them (or staged) ----
   float* d_tr; HIP_TRY(ensure_into(B[AB_TR], 2 * eT, d_tr));
@@ -133,9 +129,6 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   if ((rc = workspace_limit(ctx, ctx->dev[DB_BITS].cap + ctx->dev[DB_SCRATCH].cap, &limit))) return rc;
 
   // ---- both strand scores of every trace: one launch per run of equal strip height / term count ----
-  std::vector<uint32_t> grp(nt);
-  for (uint32_t g = 0; g < ng; ++g)
-    for (uint32_t i = gf[g]; i < gf[g + 1]; ++i) grp[i - t0] = g;
   std::vector<int> KS(nt);
   for (uint32_t i = 0; i < nt; ++i) KS[i] = choose_k(sT.length[t0 + i], MODE_PROF);
   auto row4 = [&](uint32_t i) { return hz[i] && hz[(size_t)nt + ref_of(grp[i])]; };
@@ -156,12 +149,7 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
     const uint32_t i = order[j], r = ref_of(grp[i]);
     const uint32_t m = sT.length[t0 + i], n = sR.length[r];
     const uint32_t P = num_passes(m, KS[i]);
-    PairDesc d{};
-    d.a1_off = sT.offset[t0 + i];
-    d.a2_off = sR.offset[r];
-    d.m = m; d.n = n;
-    d.a1_stride = m; d.a2_stride = n;
-    d.flags = row4(i) ? PAIR_ROW4_ZERO : 0u;
+    PairDesc d = prof_pair_desc(sT.offset[t0 + i], m, sR.offset[r], n, row4(i));
     for (uint32_t s = 0; s < 2; ++s) {
       d.a1_off = sT.offset[t0 + i] + (s ? rev_base : 0);
       d.scratch_off = sc_scratch;
@@ -175,8 +163,6 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
                      (unsigned long long)limit);
   HIP_TRY(hipMemcpyAsync(dd, hd, sizeof(PairDesc) * 2 * (size_t)nt, hipMemcpyHostToDevice, st));
   if (sc_scratch) HIP_TRY(ctx->dev[DB_SCRATCH].ensure(sc_scratch * 8));
-  HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
-  HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
   int32_t* d_sc2; HIP_TRY(ensure_into(B[AB_SC2], 2 * (size_t)nt, d_sc2));
 
   DpArgs a = scoring_args(ctx, prm);
@@ -187,16 +173,8 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   a.colcode = d_refclass;
   a.scores = d_sc2;
   std::vector<std::pair<uint32_t, int>> narrow_launches;
-  if ((rc = prof_score_runs(ctx, prm, wide, a, hd, dd, k_score.data(), 0, nt, narrow_launches))) return rc;
   std::vector<int32_t> sc2(2 * (size_t)nt);
-  int32_t herr[kErrWords] = {};
-  HIP_TRY(hipMemcpyAsync(sc2.data(), d_sc2, sizeof(int32_t) * sc2.size(), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(herr, ctx->dev[DB_ERR].p, sizeof(herr), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx_sync(ctx));
-  {
-    const int verdict = range_verdict(prm, herr, narrow_launches, max_mn, kTagShift);
-    if (verdict != TRACYHIP_OK) return verdict;  // (kWiden: a 16-bit score launch met an un-normalised profile; the caller repeats on int32)
-  }
+  if ((rc = prof_score_stage(ctx, prm, wide, a, hd, dd, k_score.data(), nt, sc2.data(), sc2.size(), max_mn, narrow_launches))) return rc;
 
   // ---- which traces match, their strands, their order (assemble.h:228-247) ----
   std::vector<int32_t> h_sf(nt), h_sr(nt);
@@ -280,25 +258,13 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   AsmFinal* h_fin = reinterpret_cast<AsmFinal*>(h_step + ng);
   uint32_t* h_len; HIP_TRY(ensure_into(ctx->pin[PB_RES], (size_t)ng, h_len));
 
-  // payload results: the caller's (MEM_DEVICE) or staged in the caller's layout (MEM_HOST)
-  uint8_t *o_rows = out->rows, *o_gapped = out->gapped, *o_cons = out->cons, *o_qual = out->qual;
-  uint32_t* o_clen = out->cons_len;
-  if (mem == TRACYHIP_MEM_HOST) {
-    const uint64_t er = (std::max<uint64_t>(ext_rows, 1) + 255) & ~255ull, ec = (std::max<uint64_t>(ext_col, 1) + 255) & ~255ull;
-    uint8_t* q; HIP_TRY(ensure_into(B[AB_PAY], er + 3 * ec + sizeof(uint32_t) * (size_t)ng, q));
-    o_rows = q; o_gapped = q + er; o_cons = q + er + ec; o_qual = q + er + 2 * ec;
-    o_clen = reinterpret_cast<uint32_t*>(q + er + 3 * ec);
-  }
-  HIP_TRY(hipMemsetAsync(o_clen, 0, sizeof(uint32_t) * (size_t)ng, st));
+  if ((rc = go.bind(ctx, mem, ext_rows, ext_col))) return rc;
 
-  a.bits = static_cast<uint64_t*>(ctx->dev[DB_BITS].p);
-  a.bits32 = static_cast<uint32_t*>(ctx->dev[DB_BITS].p);
-  a.scratch = static_cast<int32_t*>(ctx->dev[DB_SCRATCH].p);
   a.scores = nullptr;
   const int32_t ignore_last = job->include_reference ? 0 : 1;
   uint32_t total_steps = 0;
   std::vector<uint32_t> act;
-  std::vector<int> k_step;  // strip heights of a step's launches, in launch order
+  TraceBatch tb{hd, dd, d_ops, d_off, d_len, limit};  // (the planes above hold every step of every chunk: its upload grows nothing)
 
   for (const Chunk& c : chunks) {
     for (uint32_t k = 0; k < c.steps; ++k) {
@@ -313,58 +279,33 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
         return flags_of(x) > flags_of(y);
       });
       const uint32_t na = (uint32_t)act.size();
-      k_step.resize(na);
-      uint64_t words = 0, scr = 0, max_cap = 0;
-      bool any_prof = false;
+      tb.clear();
       for (uint32_t j = 0; j < na; ++j) {
         const uint32_t g = act[j];
         const Match& mt = matched[g][k];
         const uint32_t r = ref_of(g);
         const uint32_t m = sT.length[t0 + mt.idx];
         const uint32_t n = k == 0 ? sR.length[r] : h_ncol[g];
-        const uint32_t P = num_passes(m, KS[mt.idx]);
-        const uint32_t nm = (uint32_t)matched[g].size();
-        const bool last = k + 1 == nm;
-        PairDesc d{};
-        d.a1_off = sT.offset[t0 + mt.idx] + (mt.forward ? 0 : rev_base);
-        d.a2_off = k == 0 ? sR.offset[r] : 6 * cg[g];
-        d.m = m; d.n = n;
-        d.a1_stride = m; d.a2_stride = n;
-        d.flags = flags_of(g);
-        d.bits_off = words;
-        d.scratch_off = scr;
-        d.out = g;
-        hd[j] = d;
-        k_step[j] = KS[mt.idx];
-        words += (uint64_t)P * steps_per_pass(n) * 64;
-        if (P > 1) scr += (uint64_t)n + 2;
+        const bool last = k + 1 == (uint32_t)matched[g].size();
+        const uint64_t a1_off = sT.offset[t0 + mt.idx] + (mt.forward ? 0 : rev_base), a2_off = k == 0 ? sR.offset[r] : 6 * cg[g];
+        tb.add(a1_off, m, a2_off, n, flags_of(g) != 0, KS[mt.idx], g);
         AsmStep s{};
-        s.left = MsaSide{nullptr, d_tr + d.a1_off, 1u, m, m};
-        if (k == 0) s.right = MsaSide{nullptr, d_ref + d.a2_off, 1u, n, n};
+        s.left = MsaSide{nullptr, d_tr + a1_off, 1u, m, m};
+        if (k == 0) s.right = MsaSide{nullptr, d_ref + a2_off, 1u, n, n};
         else s.right = MsaSide{d_w[(k - 1) & 1] + rg[g], nullptr, k + 1, n, 0u};
         s.ops_off = cg[g];
         s.slot = g;
         s.cap = m + n;
-        s.dst = last ? o_rows + out->rows_offset[g] : d_w[k & 1] + rg[g];
+        s.dst = last ? go.d_rows + go.rows_offset[g] : d_w[k & 1] + rg[g];
         s.span = d_span + 2 * sg[g];
         s.prof = last ? nullptr : d_prof + 6 * cg[g];
         s.colclass = d_pclass + 6 * cg[g];
         h_step[j] = s;
-        any_prof |= !last;
-        max_cap = std::max<uint64_t>(max_cap, s.cap);
       }
-      HIP_TRY(hipMemcpyAsync(dd, hd, sizeof(PairDesc) * na, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(d_step, h_step, sizeof(AsmStep) * na, hipMemcpyHostToDevice, st));
       a.a2 = k == 0 ? (const void*)d_ref : (const void*)d_prof;
       a.colcode = !screen ? nullptr : k == 0 ? d_refclass : d_pclass;
-      if ((rc = prof_trace_runs(ctx, a, hd, dd, k_step.data(), 0, na, d_ops, d_off, d_len))) return rc;
-      if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 0))) return trc;
-      HIP_TRY(launch_msa_merge(d_step, na, k + 2, d_ops, d_len, st));
-      if (any_prof) HIP_TRY(launch_msa_profile(d_step, na, max_cap, d_len, st));
-      if ((trc = timing_end(ctx))) return trc;
       // the op counts: the columns of the next step (and the group's ncol)
-      HIP_TRY(hipMemcpyAsync(h_len, d_len, sizeof(uint32_t) * (size_t)ng, hipMemcpyDeviceToHost, st));
-      HIP_TRY(ctx_sync(ctx));
+      if ((rc = msa_merge_batch(ctx, a, tb, h_step, d_step, h_len, 0, ng))) return rc;
       for (uint32_t j = 0; j < na; ++j) {
         const uint32_t g = act[j];
         if (h_len[g] > h_step[j].cap)
@@ -377,56 +318,22 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
     uint32_t nf = 0;
     for (uint32_t g = c.lo; g < c.hi; ++g) {
       if (matched[g].empty()) continue;
-      const uint32_t nm = (uint32_t)matched[g].size();
-      const int64_t rows = (int64_t)nm + 1 - ignore_last;
-      AsmFinal f{};
-      f.rows = o_rows + out->rows_offset[g];
-      f.span = d_span + 2 * sg[g];
-      f.rows_used = (uint32_t)rows;
-      f.slot = g;
-      f.cov_threshold = (int32_t)(job->fraction_called * (float)(size_t)rows);  // float x size_t, msa.h:196
-      f.cap = (uint32_t)bound[g];
-      f.gapped = o_gapped + out->col_offset[g];
-      f.cons = o_cons + out->col_offset[g];
-      f.qual = o_qual + out->col_offset[g];
-      f.cons_len = o_clen + g;
-      h_fin[nf++] = f;
+      const uint32_t rows = (uint32_t)matched[g].size() + 1 - ignore_last;
+      h_fin[nf++] = go.final_entry(g, d_span + 2 * sg[g], rows, g, (uint32_t)bound[g], job->fraction_called);
     }
-    if (nf) {
-      HIP_TRY(hipMemcpyAsync(d_fin, h_fin, sizeof(AsmFinal) * nf, hipMemcpyHostToDevice, st));
-      if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 0))) return trc;
-      HIP_TRY(launch_msa_consensus(d_fin, nf, d_len, st));
-      if ((trc = timing_end(ctx))) return trc;
-      // (h_fin is filled again at the end of the next chunk that has groups to finish: behind the synchronisations of its steps)
-    }
+    // (h_fin is filled again at the end of the next chunk that has groups to finish: behind the synchronisations of its steps)
+    if ((rc = msa_consensus_batch(ctx, h_fin, d_fin, nf, d_len))) return rc;
   }
 
   // ---- the last synchronisation: error words, results ----
+  int32_t herr[kErrWords] = {};
   HIP_TRY(hipMemcpyAsync(herr, ctx->dev[DB_ERR].p, sizeof(herr), hipMemcpyDeviceToHost, st));
-  if (mem == TRACYHIP_MEM_HOST) {
-    std::memcpy(out->score_fwd + t0, h_sf.data(), 4 * (size_t)nt);
-    std::memcpy(out->score_rev + t0, h_sr.data(), 4 * (size_t)nt);
-    std::memcpy(out->forward + t0, h_fwd.data(), (size_t)nt);
-    std::memcpy(out->rank + t0, h_rank.data(), 4 * (size_t)nt);
-    std::memcpy(out->nrows, h_nrows.data(), 4 * (size_t)ng);
-    std::memcpy(out->ncol, h_ncol.data(), 4 * (size_t)ng);
-    HIP_TRY(hipMemcpyAsync(out->cons_len, o_clen, 4 * (size_t)ng, hipMemcpyDeviceToHost, st));
-    for (uint32_t g = 0; g < ng; ++g) {  // only what the group wrote (the columns past cons_len hold no result)
-      if (!h_nrows[g]) continue;
-      const uint64_t ro = out->rows_offset[g], co = out->col_offset[g];
-      HIP_TRY(hipMemcpyAsync(out->rows + ro, o_rows + ro, (uint64_t)h_nrows[g] * h_ncol[g], hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(out->gapped + co, o_gapped + co, h_ncol[g], hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(out->cons + co, o_cons + co, h_ncol[g], hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(out->qual + co, o_qual + co, h_ncol[g], hipMemcpyDeviceToHost, st));
-    }
-  } else {
-    HIP_TRY(hipMemcpyAsync(out->score_fwd + t0, h_sf.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(out->score_rev + t0, h_sr.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(out->forward + t0, h_fwd.data(), (size_t)nt, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(out->rank + t0, h_rank.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(out->nrows, h_nrows.data(), 4 * (size_t)ng, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(out->ncol, h_ncol.data(), 4 * (size_t)ng, hipMemcpyHostToDevice, st));
-  }
+  if ((rc = put_result(ctx, mem, out->score_fwd + t0, h_sf.data(), 4 * (size_t)nt)) ||
+      (rc = put_result(ctx, mem, out->score_rev + t0, h_sr.data(), 4 * (size_t)nt)) ||
+      (rc = put_result(ctx, mem, out->forward + t0, h_fwd.data(), (size_t)nt)) ||
+      (rc = put_result(ctx, mem, out->rank + t0, h_rank.data(), 4 * (size_t)nt)) ||
+      (rc = go.copy_back(ctx, mem, h_nrows.data(), h_ncol.data())))
+    return rc;
   HIP_TRY(ctx_sync(ctx));
   timing_collect(ctx);
   ctx->stats.asm_chunks = (uint32_t)chunks.size();

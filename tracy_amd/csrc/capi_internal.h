@@ -136,7 +136,7 @@ enum CtxDev : int {
   AB_PROF,      // profile of the alignment so far: written by msa_profile_kernel, read by the next step's sweep
   AB_PCLASS,    // its column classes
   AB_STEP,      // AsmStep + AsmFinal per group, uploaded per step
-  AB_PAY,       // results staged for a host caller
+  AB_PAY,       // payload results staged for a host caller in the caller's layout (GroupOut::bind, for both group calls)
   // ---- tracyhip_denovo_traces (denovo.hip denovo_run) ----
   // a context runs one call at a time, and neither call keeps anything in these between calls: the roles that match share a slot
   DN_PROF = AB_TR,      // [forward | revcomp] of every trace, then the node profiles: both sides of every dynamic program
@@ -516,6 +516,62 @@ struct AsmFinal {      // one finished group
 hipError_t launch_msa_merge(const AsmStep* steps, uint32_t n, uint32_t max_rows, const uint8_t* ops, const uint32_t* ops_len, hipStream_t st);
 hipError_t launch_msa_profile(const AsmStep* steps, uint32_t n, uint64_t max_cap, const uint32_t* ops_len, hipStream_t st);
 hipError_t launch_msa_consensus(const AsmFinal* fin, uint32_t n, const uint32_t* ops_len, hipStream_t st);
+
+// ---- group batches (msa_batch.hip): the host code around those kernels that assemble_run and denovo_run share ----
+// The result fields tracyhip_assemble_result and tracyhip_denovo_result have in common, and where the kernels write the payload
+// arrays: the caller's own (MEM_DEVICE) or one staging buffer in the caller's layout (MEM_HOST: AB_PAY, which DN_PAY aliases).
+struct GroupOut {
+  uint32_t ng;
+  uint32_t *nrows, *ncol, *cons_len;
+  uint8_t *rows, *gapped, *cons, *qual;
+  const uint64_t *rows_offset, *col_offset;
+  uint8_t *d_rows = nullptr, *d_gapped = nullptr, *d_cons = nullptr, *d_qual = nullptr;  // set by bind()
+  uint32_t* d_clen = nullptr;
+  template <class Result>
+  GroupOut(uint32_t ng_, const Result& r)
+      : ng(ng_), nrows(r.nrows), ncol(r.ncol), cons_len(r.cons_len), rows(r.rows), gapped(r.gapped), cons(r.cons), qual(r.qual),
+        rows_offset(r.rows_offset), col_offset(r.col_offset) {}
+  // a call whose groups hold no trace: nrows, ncol and cons_len are 0 everywhere (MEM_DEVICE: one synchronisation)
+  int clear_counts(tracyhip_ctx* ctx, int mem) const;
+  // the payload pointers; ext_rows / ext_col: the largest offset + capacity over the groups that hold a trace.  d_clen is cleared
+  int bind(tracyhip_ctx* ctx, int mem, uint64_t ext_rows, uint64_t ext_col);
+  // the entry of a finished group for msa_consensus: its rows are the first rows_used of the block at rows_offset[g]
+  AsmFinal final_entry(uint32_t g, const int32_t* span, uint32_t rows_used, uint32_t slot, uint32_t cap, float fraction_called) const;
+  // queued behind the last launch: nrows / ncol from the host's h_nrows / h_ncol, and for a host caller cons_len and what every group
+  // wrote of rows / gapped / cons / qual.  The caller synchronises
+  int copy_back(tracyhip_ctx* ctx, int mem, const uint32_t* h_nrows, const uint32_t* h_ncol) const;
+};
+// `bytes` of a result array the host computed, into the caller's array: copied (MEM_HOST) or queued as an upload (MEM_DEVICE)
+int put_result(tracyhip_ctx* ctx, int mem, void* user, const void* host, size_t bytes);
+// One batch of traceback sweeps through prof_trace_runs: the descriptors in launch order (the caller sorts by strip height and row-4
+// flag), where each sweep's planes and boundary rows start, and the op strings the walks write (indexed by PairDesc::out).
+struct TraceBatch {
+  PairDesc *hd = nullptr, *dd = nullptr;  // PB_DESC / DB_DESC, sized by the caller
+  uint8_t* ops = nullptr;                 // the op strings: string PairDesc::out at ops + ops_off[out], ops_len[out] bytes
+  const uint64_t* ops_off = nullptr;
+  uint32_t* ops_len = nullptr;
+  uint64_t limit = 0;                     // workspace_limit: what the planes and boundary rows of one batch may take
+  std::vector<int> k;                     // strip heights, in launch order
+  uint64_t words = 0, scr = 0;            // running sums: traceback words, boundary-row pairs
+  void clear() { k.clear(); words = scr = 0; }
+  // gotoh(a1, a2): m rows at float offset a1_off of DpArgs::a1 against n columns at a2_off of DpArgs::a2, strips of K rows
+  void add(uint64_t a1_off, uint32_t m, uint64_t a2_off, uint32_t n, bool row4_zero, int K, uint32_t out);
+  // DB_BITS / DB_SCRATCH hold the batch (grown if need be, refused above the limit) and are bound to `a`; the descriptors are uploaded
+  int upload(tracyhip_ctx* ctx, DpArgs& a) const;
+};
+// the descriptor of one profile x profile pair (bits_off / scratch_off / out are the caller's)
+PairDesc prof_pair_desc(uint64_t a1_off, uint32_t m, uint64_t a2_off, uint32_t n, bool row4_zero);
+// One batch of merges: the sweeps of `tb` (entry j is the pair of h_step[j]: left x right), msa_merge, msa_profile where a step has a
+// profile, then ops_len[lo, hi) read back into h_len[lo, hi) and ONE synchronisation.  The caller checks h_len against the caps.
+int msa_merge_batch(tracyhip_ctx* ctx, DpArgs& a, const TraceBatch& tb, const AsmStep* h_step, AsmStep* d_step, uint32_t* h_len, uint32_t lo,
+                    uint32_t hi);
+// msa_consensus of the nf finished groups of a chunk (h_fin: pinned, filled through GroupOut::final_entry); nothing is waited for
+int msa_consensus_batch(tracyhip_ctx* ctx, const AsmFinal* h_fin, AsmFinal* d_fin, uint32_t nf, const uint32_t* ops_len);
+// The tail of the strand-score stage over nu sorted units (two descriptors each, uploaded by the caller; `a` carries the payload
+// pointers): DB_ERR cleared, prof_score_runs, the nscores scores of a.scores and the error words read back, one synchronisation,
+// range_verdict -- kWiden: a 16-bit launch met an un-normalised profile, the caller repeats on int32
+int prof_score_stage(tracyhip_ctx* ctx, const tracyhip_params* prm, bool wide, DpArgs& a, const PairDesc* hd, const PairDesc* dd, const int* k,
+                     uint32_t nu, int32_t* h_scores, size_t nscores, uint64_t max_mn, std::vector<std::pair<uint32_t, int>>& narrow_launches);
 
 // ---- band kernels (band16.h): Gotoh on a diagonal band, four pairs per wave ----
 // a batch for them: descriptors whose a1_off / a1_stride point into the substitution tables d_qp (build_b16_tables), a2_off into

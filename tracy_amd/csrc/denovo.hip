@@ -12,6 +12,8 @@
 // merge.  The columns of a node are the op count of its merge, which only the device knows: the host reads the op counts back once
 // per height.  Workspaces are sized from  columns of a node <= the summed lengths of its leaves.
 // Host synchronisations: classes, table, one per overlap round and one per tree height of a chunk, one at the end.
+// The host code both group calls run around the kernels is msa_batch.hip's, shared with assemble.hip (GroupOut, TraceBatch,
+// msa_merge_batch, msa_consensus_batch, prof_score_stage); what stays here is the plan: strands, overlap verdicts, trees, chunks.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -94,11 +96,13 @@ int denovo_run(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip
 
   // ---- geometry: per group the summed length S (the column bound of every node), and where its pieces live ----
   std::vector<uint64_t> S(ng), maxlen(ng, 0), tb(ng + 1, 0), ob(ng + 1, 0), pb(ng + 1, 0), sb(ng + 1, 0);
+  std::vector<uint32_t> grp(nt);  // trace to group
   uint64_t eT = 0, max_mn = 0, ext_rows = 0, ext_col = 0;
   for (uint32_t g = 0; g < ng; ++g) {
     const uint64_t K = gf[g + 1] - gf[g];
     uint64_t s = 0;
     for (uint32_t i = gf[g]; i < gf[g + 1]; ++i) {
+      grp[i - t0] = g;
       s += sT.length[i];
       maxlen[g] = std::max<uint64_t>(maxlen[g], sT.length[i]);
       eT = std::max<uint64_t>(eT, sT.offset[i] + 6ull * sT.length[i]);
@@ -117,19 +121,8 @@ int denovo_run(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip
   int rc;
   if ((rc = check_params(prm, max_mn))) return rc;
   if (max_mn > 0xffffffffull) return set_error(TRACYHIP_ERR_RANGE, "a group's column bound exceeds 2^32");
-  if (nt == 0) {  // groups without traces: nrows 0 everywhere
-    if (mem == TRACYHIP_MEM_HOST) {
-      std::memset(out->nrows, 0, 4 * (size_t)ng); std::memset(out->ncol, 0, 4 * (size_t)ng); std::memset(out->cons_len, 0, 4 * (size_t)ng);
-    } else {
-      HIP_TRY(hipMemsetAsync(out->nrows, 0, 4 * (size_t)ng, st)); HIP_TRY(hipMemsetAsync(out->ncol, 0, 4 * (size_t)ng, st));
-      HIP_TRY(hipMemsetAsync(out->cons_len, 0, 4 * (size_t)ng, st));
-      HIP_TRY(ctx_sync(ctx));
-    }
-    return TRACYHIP_OK;
-  }
-  std::vector<uint32_t> grp(nt);
-  for (uint32_t g = 0; g < ng; ++g)
-    for (uint32_t i = gf[g]; i < gf[g + 1]; ++i) grp[i - t0] = g;
+  GroupOut go(ng, *out);
+  if (nt == 0) return go.clear_counts(ctx, mem);  // groups without traces: nrows 0 everywhere
 
   // ---- inputs: [forward | revcomp | node profiles] in one buffer, the classes of both strands ----
   const uint64_t rev_base = eT, node_base = 2 * eT, nfloat = 2 * eT + 6 * pb[ng];
@@ -187,11 +180,7 @@ int denovo_run(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip
     const uint32_t g = grp[x.i], K = gf[g + 1] - gf[g], base = gf[g] - t0;
     const uint32_t m = len_of(x.i), n = len_of(x.j);
     k_score[u] = KS[x.i];
-    PairDesc d{};
-    d.a1_off = strand_off(x.i, x.oi);
-    d.m = m; d.n = n;
-    d.a1_stride = m; d.a2_stride = n;
-    d.flags = row4(x.i, x.j) ? PAIR_ROW4_ZERO : 0u;
+    PairDesc d = prof_pair_desc(strand_off(x.i, x.oi), m, 0, n, row4(x.i, x.j));
     for (uint32_t oj = 0; oj < 2; ++oj) {
       d.a2_off = strand_off(x.j, oj);
       d.scratch_off = sc_scratch;
@@ -206,8 +195,6 @@ int denovo_run(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip
                      (unsigned long long)limit);
   HIP_TRY(hipMemcpyAsync(dd, hd, sizeof(PairDesc) * 2 * (size_t)nu, hipMemcpyHostToDevice, st));
   if (sc_scratch) HIP_TRY(ctx->dev[DB_SCRATCH].ensure(sc_scratch * 8));
-  HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
-  HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
   int32_t* d_table; HIP_TRY(ensure_into(B[DN_TABLE], std::max<uint64_t>(tb[ng], 1), d_table));
 
   DpArgs a = scoring_args(ctx, prm);
@@ -218,17 +205,8 @@ int denovo_run(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip
   a.colcode = screen ? d_cls : nullptr;
   a.scores = d_table;
   std::vector<std::pair<uint32_t, int>> narrow_launches;
-  if ((rc = prof_score_runs(ctx, prm, wide, a, hd, dd, k_score.data(), 0, nu, narrow_launches))) return rc;
   std::vector<int32_t> table(std::max<uint64_t>(tb[ng], 1), 0);
-  int32_t herr[kErrWords] = {};
-  if (tb[ng]) HIP_TRY(hipMemcpyAsync(table.data(), d_table, sizeof(int32_t) * tb[ng], hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(herr, ctx->dev[DB_ERR].p, sizeof(herr), hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx_sync(ctx));
-  {
-    const int verdict = range_verdict(prm, herr, narrow_launches, max_mn, kTagShift);
-    if (verdict != TRACYHIP_OK) return verdict;  // (kWiden: a 16-bit score launch met an un-normalised profile; the caller repeats on int32)
-  }
-
+  if ((rc = prof_score_stage(ctx, prm, wide, a, hd, dd, k_score.data(), nu, table.data(), tb[ng], max_mn, narrow_launches))) return rc;
   stage_ms[1] = since(t_stage);
 
   // ---- strands (revSeqBasedOnDist) ----
@@ -301,37 +279,15 @@ int denovo_run(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip
   HIP_TRY(hipMemsetAsync(d_len, 0, sizeof(uint32_t) * (size_t)nt, st));
   HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * (size_t)nt, st));
 
-  // payload results: the caller's (MEM_DEVICE) or staged in the caller's layout (MEM_HOST)
-  uint8_t *o_rows = out->rows, *o_gapped = out->gapped, *o_cons = out->cons, *o_qual = out->qual;
-  uint32_t* o_clen = out->cons_len;
-  if (mem == TRACYHIP_MEM_HOST) {
-    const uint64_t er = (std::max<uint64_t>(ext_rows, 1) + 255) & ~255ull, ec = (std::max<uint64_t>(ext_col, 1) + 255) & ~255ull;
-    uint8_t* q; HIP_TRY(ensure_into(B[DN_PAY], er + 3 * ec + sizeof(uint32_t) * (size_t)ng, q));
-    o_rows = q; o_gapped = q + er; o_cons = q + er + ec; o_qual = q + er + 2 * ec;
-    o_clen = reinterpret_cast<uint32_t*>(q + er + 3 * ec);
-  }
-  HIP_TRY(hipMemsetAsync(o_clen, 0, sizeof(uint32_t) * (size_t)ng, st));
+  if ((rc = go.bind(ctx, mem, ext_rows, ext_col))) return rc;
 
   a.scores = nullptr;
   std::vector<uint32_t> h_partner(nt, 0xffffffffu), h_row(nt, 0xffffffffu), h_nrows(ng, 0), h_ncol(ng, 0);
   std::vector<uint32_t> next(nt, 0), act;
   std::vector<int8_t> state(nt, 0);  // 0 undecided, 1 kept, -1 excluded
-  std::vector<int> k_step;           // strip heights of a batch's launches, in launch order
   std::vector<GroupPlan> plan(ng);
   uint32_t total_rounds = 0, total_steps = 0;
-  // the planes and boundary rows of one batch of traceback sweeps, by what the batch needs
-  auto planes = [&](uint64_t words, uint64_t scr) -> int {
-    const uint64_t need = words * 8 + scr * 8;
-    if (need > limit)
-      return set_error(TRACYHIP_ERR_OOM, "a batch of tracebacks needs %llu bytes of planes, workspace limit is %llu", (unsigned long long)need,
-                       (unsigned long long)limit);
-    HIP_TRY(ctx->dev[DB_BITS].ensure(std::max<uint64_t>(words * 8, 8)));
-    if (scr) HIP_TRY(ctx->dev[DB_SCRATCH].ensure(scr * 8));
-    a.bits = static_cast<uint64_t*>(ctx->dev[DB_BITS].p);
-    a.bits32 = static_cast<uint32_t*>(ctx->dev[DB_BITS].p);
-    a.scratch = static_cast<int32_t*>(ctx->dev[DB_SCRATCH].p);
-    return TRACYHIP_OK;
-  };
+  TraceBatch batch{hd, dd, d_ops, d_off, d_len, limit};  // the sweeps of an overlap round or a tree height: upload() sizes the planes for them
 
   for (const Chunk& c : chunks) {
     const uint32_t clo = gf[c.lo] - t0, chi = gf[c.hi] - t0;  // the chunk's traces
@@ -358,29 +314,13 @@ int denovo_run(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip
         return row4(x, partner(x)) > row4(y, partner(y));
       });
       const uint32_t na = (uint32_t)act.size();
-      k_step.resize(na);
-      uint64_t words = 0, scr = 0;
+      batch.clear();
       for (uint32_t u = 0; u < na; ++u) {
         const uint32_t i = act[u], j = partner(i);
-        const uint32_t m = len_of(i), n = len_of(j);
-        const uint32_t P = num_passes(m, KS[i]);
-        PairDesc d{};
-        d.a1_off = strand_off(i, rev[i]);
-        d.a2_off = strand_off(j, rev[j]);
-        d.m = m; d.n = n;
-        d.a1_stride = m; d.a2_stride = n;
-        d.flags = row4(i, j) ? PAIR_ROW4_ZERO : 0u;
-        d.bits_off = words;
-        d.scratch_off = scr;
-        d.out = i;
-        hd[u] = d;
-        k_step[u] = KS[i];
-        words += (uint64_t)P * steps_per_pass(n) * 64;
-        if (P > 1) scr += (uint64_t)n + 2;
+        batch.add(strand_off(i, rev[i]), len_of(i), strand_off(j, rev[j]), len_of(j), row4(i, j), KS[i], i);
       }
-      if ((rc = planes(words, scr))) return rc;
-      HIP_TRY(hipMemcpyAsync(dd, hd, sizeof(PairDesc) * na, hipMemcpyHostToDevice, st));
-      if ((rc = prof_trace_runs(ctx, a, hd, dd, k_step.data(), 0, na, d_ops, d_off, d_len))) return rc;
+      if ((rc = batch.upload(ctx, a))) return rc;
+      if ((rc = prof_trace_runs(ctx, a, hd, dd, batch.k.data(), 0, na, d_ops, d_off, d_len))) return rc;
       if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 0))) return trc;
       hipLaunchKernelGGL(denovo_count_kernel, dim3(na), dim3(64), 0, st, (const PairDesc*)dd, (const uint8_t*)d_ops, (const uint64_t*)d_off,
                          (const uint32_t*)d_len, d_cnt);
@@ -479,7 +419,7 @@ int denovo_run(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip
       s.ops_off = ob[g];
       s.slot = slot;
       s.cap = leaf.ncol;
-      s.dst = o_rows + out->rows_offset[g];
+      s.dst = go.d_rows + go.rows_offset[g];
       s.span = d_span + 2 * leaf.span_off;
       h_step[nt + nleafroot++] = s;
       h_ncol[g] = leaf.ncol;
@@ -510,31 +450,13 @@ int denovo_run(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip
         return flags_of(x) > flags_of(y);
       });
       const uint32_t na = (uint32_t)items.size();
-      k_step.resize(na);
-      uint64_t words = 0, scr = 0, max_cap = 0;
-      uint32_t max_rows = 0;
-      bool any_prof = false;
+      batch.clear();
       for (uint32_t u = 0; u < na; ++u) {
         const Item& x = items[u];
         const GroupPlan& gp = plan[x.g];
         const TreeNode &nd = gp.node[x.v], &l = left_of(x), &r = right_of(x);
         const bool root = x.v == gp.tree.root;
-        const uint32_t m = l.ncol, n = r.ncol;
-        const int k = choose_k(m, MODE_PROF);
-        const uint32_t P = num_passes(m, k);
-        PairDesc d{};
-        d.a1_off = l.prof_off;
-        d.a2_off = r.prof_off;
-        d.m = m; d.n = n;
-        d.a1_stride = m; d.a2_stride = n;
-        d.flags = flags_of(x);
-        d.bits_off = words;
-        d.scratch_off = scr;
-        d.out = nd.slot;
-        hd[u] = d;
-        k_step[u] = k;
-        words += (uint64_t)P * steps_per_pass(n) * 64;
-        if (P > 1) scr += (uint64_t)n + 2;
+        batch.add(l.prof_off, l.ncol, r.prof_off, r.ncol, flags_of(x) != 0, choose_k(l.ncol, MODE_PROF), nd.slot);
         auto side = [&](const TreeNode& s, int32_t idx) {
           return idx < gp.tree.num ? MsaSide{nullptr, d_prof + s.prof_off, 1u, s.ncol, s.ncol} : MsaSide{d_rows + s.rows_off, nullptr, s.n, s.ncol, 0u};
         };
@@ -543,27 +465,15 @@ int denovo_run(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip
         s.right = side(r, gp.tree.p[x.v][2]);
         s.ops_off = nd.ops_off;
         s.slot = nd.slot;
-        s.cap = m + n;
-        s.dst = root ? o_rows + out->rows_offset[x.g] : d_rows + nd.rows_off;
+        s.cap = l.ncol + r.ncol;
+        s.dst = root ? go.d_rows + go.rows_offset[x.g] : d_rows + nd.rows_off;
         s.span = d_span + 2 * nd.span_off;
         s.prof = root ? nullptr : d_prof + nd.prof_off;
         s.colclass = root ? nullptr : d_cls + nd.prof_off;
         h_step[u] = s;
-        any_prof |= !root;
-        max_cap = std::max<uint64_t>(max_cap, s.cap);
-        max_rows = std::max(max_rows, nd.n);
       }
-      if ((rc = planes(words, scr))) return rc;
-      HIP_TRY(hipMemcpyAsync(dd, hd, sizeof(PairDesc) * na, hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(d_step, h_step, sizeof(AsmStep) * na, hipMemcpyHostToDevice, st));
-      if ((rc = prof_trace_runs(ctx, a, hd, dd, k_step.data(), 0, na, d_ops, d_off, d_len))) return rc;
-      if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 0))) return trc;
-      HIP_TRY(launch_msa_merge(d_step, na, max_rows, d_ops, d_len, st));
-      if (any_prof) HIP_TRY(launch_msa_profile(d_step, na, max_cap, d_len, st));
-      if ((trc = timing_end(ctx))) return trc;
       // the op counts: the columns of the nodes (and, for a root, the group's ncol)
-      HIP_TRY(hipMemcpyAsync(h_len + clo, d_len + clo, sizeof(uint32_t) * (chi - clo), hipMemcpyDeviceToHost, st));
-      HIP_TRY(ctx_sync(ctx));
+      if ((rc = msa_merge_batch(ctx, a, batch, h_step, d_step, h_len, clo, chi))) return rc;
       for (uint32_t u = 0; u < na; ++u) {
         const Item& x = items[u];
         GroupPlan& gp = plan[x.g];
@@ -586,25 +496,9 @@ int denovo_run(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip
       const GroupPlan& gp = plan[g];
       if (!h_nrows[g]) continue;
       const TreeNode& root = gp.node[gp.tree.root];
-      AsmFinal f{};
-      f.rows = o_rows + out->rows_offset[g];
-      f.span = d_span + 2 * root.span_off;
-      f.rows_used = root.n;
-      f.slot = root.slot;
-      f.cov_threshold = (int32_t)(job->fraction_called * (float)(size_t)root.n);  // float x size_t, msa.h:196
-      f.cap = root.cap;
-      f.gapped = o_gapped + out->col_offset[g];
-      f.cons = o_cons + out->col_offset[g];
-      f.qual = o_qual + out->col_offset[g];
-      f.cons_len = o_clen + g;
-      h_fin[nf++] = f;
+      h_fin[nf++] = go.final_entry(g, d_span + 2 * root.span_off, root.n, root.slot, root.cap, job->fraction_called);
     }
-    if (nf) {
-      HIP_TRY(hipMemcpyAsync(d_fin, h_fin, sizeof(AsmFinal) * nf, hipMemcpyHostToDevice, st));
-      if ((trc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, 0))) return trc;
-      HIP_TRY(launch_msa_consensus(d_fin, nf, d_len, st));
-      if ((trc = timing_end(ctx))) return trc;
-    }
+    if ((rc = msa_consensus_batch(ctx, h_fin, d_fin, nf, d_len))) return rc;
     stage_ms[4] += since(t_stage);
     // (the pinned h_step / h_fin / hd are filled again by the next chunk behind the synchronisations of its rounds; its entries of
     // h_off / h_len are its own traces')
@@ -612,29 +506,13 @@ int denovo_run(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip
 
   // ---- the last synchronisation: error words, results ----
   t_stage = clock_now();
+  int32_t herr[kErrWords] = {};
   HIP_TRY(hipMemcpyAsync(herr, ctx->dev[DB_ERR].p, sizeof(herr), hipMemcpyDeviceToHost, st));
-  if (mem == TRACYHIP_MEM_HOST) {
-    std::memcpy(out->forward + t0, h_fwd.data(), (size_t)nt);
-    std::memcpy(out->partner + t0, h_partner.data(), 4 * (size_t)nt);
-    std::memcpy(out->row + t0, h_row.data(), 4 * (size_t)nt);
-    std::memcpy(out->nrows, h_nrows.data(), 4 * (size_t)ng);
-    std::memcpy(out->ncol, h_ncol.data(), 4 * (size_t)ng);
-    HIP_TRY(hipMemcpyAsync(out->cons_len, o_clen, 4 * (size_t)ng, hipMemcpyDeviceToHost, st));
-    for (uint32_t g = 0; g < ng; ++g) {  // only what the group wrote (the columns past cons_len hold no result)
-      if (!h_nrows[g]) continue;
-      const uint64_t ro = out->rows_offset[g], co = out->col_offset[g];
-      HIP_TRY(hipMemcpyAsync(out->rows + ro, o_rows + ro, (uint64_t)h_nrows[g] * h_ncol[g], hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(out->gapped + co, o_gapped + co, h_ncol[g], hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(out->cons + co, o_cons + co, h_ncol[g], hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(out->qual + co, o_qual + co, h_ncol[g], hipMemcpyDeviceToHost, st));
-    }
-  } else {
-    HIP_TRY(hipMemcpyAsync(out->forward + t0, h_fwd.data(), (size_t)nt, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(out->partner + t0, h_partner.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(out->row + t0, h_row.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(out->nrows, h_nrows.data(), 4 * (size_t)ng, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(out->ncol, h_ncol.data(), 4 * (size_t)ng, hipMemcpyHostToDevice, st));
-  }
+  if ((rc = put_result(ctx, mem, out->forward + t0, h_fwd.data(), (size_t)nt)) ||
+      (rc = put_result(ctx, mem, out->partner + t0, h_partner.data(), 4 * (size_t)nt)) ||
+      (rc = put_result(ctx, mem, out->row + t0, h_row.data(), 4 * (size_t)nt)) ||
+      (rc = go.copy_back(ctx, mem, h_nrows.data(), h_ncol.data())))
+    return rc;
   HIP_TRY(ctx_sync(ctx));
   timing_collect(ctx);
   ctx->stats.denovo_chunks = (uint32_t)chunks.size();
