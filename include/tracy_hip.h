@@ -245,7 +245,25 @@ typedef struct {
                                does (forward iff gsFwd > gsRev), but the LOSING orientation may be represented by a certified
                                upper bound of its score instead of the score itself (a prefix of its DP suffices to prove that
                                it cannot win; see pipeline.hip) -- fewer cells, same decision, same alignments. */
+  const uint32_t* trim_left_each;  /* HOST arrays [ntraces], or both NULL (what a zero-initialised job gets: every trace takes the */
+  const uint32_t* trim_right_each; /* scalars above).  Given: trace t uses trim_left_each[t] / trim_right_each[t] wherever the scalars
+                               are used, and the scalars are ignored (per-trace trims, below).  One without the other: TRACYHIP_ERR_ARG. */
 } tracyhip_align_job;
+
+/* ---- per-trace trims (`-t`: trimTrace gives every trace its own trimLeft / trimRight, sage.h:39-40, trim.h:35-73) ----------------
+ * tracyhip_align_job, tracyhip_decompose_job (which tracyhip_decompose_variants reads) and tracyhip_seed_params carry two optional
+ * HOST arrays beside their scalar pair.  Every rule below is the scalar rule, applied with the trace's own (l, r):
+ *   1. trimmed profile: createProfile's clamp (profile.h:24-27): l + r >= mf gives trims 0 / 0.
+ *   2. trimReferenceSlice widening (fmindex.h:443-461): takes the REQUESTED (l, r), not the clamped ones.
+ *   3. allele strings and allelic fraction: trimmedSeq (abif.h:68-75): l + r + 1 >= len gives the whole string (one off from rule 1).
+ *   4. allelic fraction index: bcPos[i + l], clamped to the last basecall (decompose.h:445).
+ *   5. decomposeAlleles: nbc - r in size_t arithmetic, breakpoint + l (decompose.h:216).
+ *   6. variants: call_index = l + basenum - 1 forward, bc_len - (r + basenum) reverse (variants.h:205).
+ *   7. k-mer orientation vote: the profile columns [l, mf - r) of rule 1.
+ *   8. seeding: the trace's k-mers from [l, len - r); a trim shorter than k - 1 or a consensus shorter than a trim defers THAT trace.
+ * The requested pairs travel to the device inside the per-trace records a call uploads anyway: no further copy, no further
+ * synchronisation.  The stage calls (tracyhip_decompose_alleles, tracyhip_allelic_fraction, tracyhip_trim_reference_slice,
+ * tracyhip_call_variants) keep their scalar trims. */
 
 typedef struct {
   int32_t* score_fwd;     /* [ntraces] gsFwd (with strand_by_certificate: exact for the winning orientation only) */
@@ -263,6 +281,10 @@ typedef struct {
   uint32_t* ops_len;      /* [ntraces] */
 } tracyhip_align_result;
 
+/* what tracyhip_align_traces checks before it plans, on the host (no device is touched): job / prm / out and the result arrays it
+ * always writes non-NULL, `mem` one of the two kinds, ops_offset given, both or neither of trim_left_each / trim_right_each.
+ * TRACYHIP_ERR_ARG (with the reason) otherwise.  The compute call runs it first. */
+int tracyhip_align_validate(const tracyhip_align_job* job, const tracyhip_params* prm, int mem, const tracyhip_align_result* out);
 int tracyhip_align_traces(tracyhip_ctx* ctx, const tracyhip_align_job* job, const tracyhip_params* prm,
                           int mem, const tracyhip_align_result* out);
 
@@ -367,6 +389,8 @@ typedef struct {
                                     wildtype's (oriented) primary basecalls = rs.refslice */
   uint32_t strand_by_certificate; /* as in tracyhip_align_job: 0 (default) = both orientation scores exact; 1 = the losing
                                     orientation's score may be a certified upper bound */
+  const uint32_t* trim_left_each;  /* HOST arrays [ntraces], or both NULL: as in tracyhip_align_job, in place of dprm.trim_left / */
+  const uint32_t* trim_right_each; /* dprm.trim_right.  A value above INT32_MAX is TRACYHIP_ERR_ARG (a negative trim, per trace). */
 } tracyhip_decompose_job;
 
 typedef struct {
@@ -395,6 +419,10 @@ typedef struct {
   uint32_t* ops_len[3];
 } tracyhip_decompose_result;
 
+/* what tracyhip_decompose_traces checks before it plans, on the host (no device is touched): NULL arguments and result arrays,
+ * `mem`, the basecall arrays, maxindel (TRACYHIP_ERR_RANGE), both or neither of the per-trace trim arrays and their range.
+ * TRACYHIP_ERR_ARG (with the reason) otherwise.  The compute call runs it first. */
+int tracyhip_decompose_validate(const tracyhip_decompose_job* job, const tracyhip_params* prm, int mem, const tracyhip_decompose_result* out);
 int tracyhip_decompose_traces(tracyhip_ctx* ctx, const tracyhip_decompose_job* job, const tracyhip_params* prm, int mem,
                               const tracyhip_decompose_result* out);
 
@@ -518,6 +546,9 @@ typedef struct {
   uint32_t kmer;             /* must be the index's k (every trace is deferred otherwise) */
   uint32_t min_support;
   uint32_t maxindel;
+  const uint32_t* trim_left_each;  /* HOST arrays [consensus->count], or both NULL: trace t's own trims in place of the scalars above, */
+  const uint32_t* trim_right_each; /* each value truncated to 16 bits like them (per-trace trims, above); the deferral rules (a trim
+                                      shorter than k - 1, a consensus shorter than a trim) are then decided per trace */
 } tracyhip_seed_params;
 
 /* per trace t: status[t] (TRACYHIP_SEED_*); for anchored traces forward, kmersupport, pos (window start in the contig), contig and

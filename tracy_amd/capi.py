@@ -39,7 +39,27 @@ class Pairs(C.Structure):
 class AlignJob(C.Structure):
     _fields_ = [("ntraces", C.c_uint32), ("profiles", SeqSet), ("refs", SeqSet), ("ref_index", C.POINTER(C.c_uint32)),
                 ("trim_left", C.c_uint32), ("trim_right", C.c_uint32), ("oriented", C.POINTER(C.c_uint8)),
-                ("strand_by_certificate", C.c_uint32)]
+                ("strand_by_certificate", C.c_uint32), ("trim_left_each", C.POINTER(C.c_uint32)),
+                ("trim_right_each", C.POINTER(C.c_uint32))]
+
+
+def trims_each(job, trim_left, trim_right, nt):
+    """Fill a job's trims (AlignJob, DecomposeJob.dprm's scalars, SeedParams) from ints -- the scalar pair, as ever -- or from per-trace
+    array-likes of length nt (trim_left_each / trim_right_each; an int beside an array is repeated).  Returns what must stay alive."""
+    scalars = job.dprm if hasattr(job, "dprm") else job
+    if np.ndim(trim_left) == 0 and np.ndim(trim_right) == 0:
+        scalars.trim_left, scalars.trim_right = int(trim_left), int(trim_right)
+        return ()
+    arrs = []
+    for v in (trim_left, trim_right):
+        a = np.full(nt, v, dtype=np.uint32) if np.ndim(v) == 0 else np.ascontiguousarray(v, dtype=np.uint32)
+        if a.shape != (nt,):
+            raise ValueError("per-trace trims: expected %d values, got shape %s" % (nt, a.shape))
+        arrs.append(a)
+    scalars.trim_left, scalars.trim_right = 0, 0
+    job.trim_left_each = arrs[0].ctypes.data_as(C.POINTER(C.c_uint32))
+    job.trim_right_each = arrs[1].ctypes.data_as(C.POINTER(C.c_uint32))
+    return tuple(arrs)
 
 
 class AlignResult(C.Structure):
@@ -312,8 +332,7 @@ class PreparedAlign:
             self.keep.append(ref_index)
         else:
             rlen = pr.length[:nt]
-        job.trim_left = trim_left
-        job.trim_right = trim_right
+        self.keep.extend(trims_each(job, trim_left, trim_right, nt))  # ints, or per-trace array-likes
         job.strand_by_certificate = 0 if exact_scores else 1  # opt-in: the losing strand may carry a certified upper bound
         if oriented is not None:
             oriented = np.ascontiguousarray(oriented, dtype=np.uint8)
@@ -350,6 +369,7 @@ class PreparedAlign:
 def _align_traces(self, profiles, refs, params, trim_left=50, trim_right=50, ref_index=None, oriented=None, exact_scores=True, device=False):
     """tracyhip_align_traces with host buffers.  profiles: list of float32 [6][mf]; refs: list of bytes.
     oriented: None, or rs.forward per trace when the references are already oriented (indexed-genome path).
+    trim_left / trim_right: ints, or per-trace array-likes (e.g. PreparedBasecall.trims() of a run with a trim stringency).
     device=True: payloads and result arrays in device memory (torch tensors, TRACYHIP_MEM_DEVICE), copied back afterwards.
     Returns a dict of numpy arrays + the list of final traceback strings (push order)."""
     p = PreparedAlign(profiles, refs, params, trim_left, trim_right, ref_index, oriented, exact_scores)
@@ -932,7 +952,8 @@ Context.allelic_fraction = _allelic_fraction
 class DecomposeJob(C.Structure):
     _fields_ = [("ntraces", C.c_uint32), ("profiles", SeqSet), ("bc", BaseCallsBatch), ("refs", SeqSet),
                 ("ref_index", C.POINTER(C.c_uint32)), ("dprm", DecompParams), ("oriented", C.POINTER(C.c_uint8)), ("ref_profiles", SeqSet),
-                ("strand_by_certificate", C.c_uint32)]
+                ("strand_by_certificate", C.c_uint32), ("trim_left_each", C.POINTER(C.c_uint32)),
+                ("trim_right_each", C.POINTER(C.c_uint32))]
 
 
 class DecomposeResult(C.Structure):
@@ -954,6 +975,7 @@ def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_righ
                       ref_profiles=None, exact_scores=True, peaks_only=False, device_bc=None):
     """tracyhip_decompose_traces with host buffers; hbc: HostBaseCalls (primary/secondary rewritten in place);
     oriented: None, or rs.forward per trace when the references are already oriented (indexed-genome path).
+    trim_left / trim_right: ints, or per-trace array-likes (Context.decompose_variants reads them from the job this call keeps).
     device_bc: a PreparedBasecall(device=True) that has run -- profiles, basecalls and peak table are taken from its device tensors as they
     stand (profiles and hbc may be None), references and results live on the device too (TRACYHIP_MEM_DEVICE) and are copied back."""
     dev = device_bc is not None
@@ -993,7 +1015,8 @@ def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_righ
         mf = pp.length[:nt].astype(np.uint64)
         nbases = len(hbc.primary)
     job.ntraces = nt
-    job.dprm = DecompParams(trim_left, trim_right, maxindel, madc)
+    job.dprm = DecompParams(0, 0, maxindel, madc)
+    trim_arrays = trims_each(job, trim_left, trim_right, nt)
     job.strand_by_certificate = 0 if exact_scores else 1  # opt-in: the losing strand may carry a certified upper bound
     if oriented is not None:
         oriented = np.ascontiguousarray(oriented, dtype=np.uint8)
@@ -1056,7 +1079,7 @@ def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_righ
     res = DecomposeOutcome(res)
     # what Context.decompose_variants needs of this call: the structs and everything they point to
     res.call = dict(job=job, out=out, prm=prm, mem=MEM_DEVICE if dev else MEM_HOST, nt=nt,
-                    keep=(pr, pp, prp, d_refs, hbc, doff, keep, oriented, mirrors, device_bc, dict(res)))
+                    keep=(pr, pp, prp, d_refs, hbc, doff, keep, oriented, mirrors, device_bc, dict(res), trim_arrays))
     if dev:  # the decomposed basecalls as the call left them in the device tensors
         rows = device_bc.results(fill_deferred=False)
         res["primary"] = [r["primary"] for r in rows]
@@ -1198,7 +1221,7 @@ class GenomeDesc(C.Structure):
 
 class SeedParams(C.Structure):
     _fields_ = [("trim_left", C.c_uint32), ("trim_right", C.c_uint32), ("kmer", C.c_uint32), ("min_support", C.c_uint32),
-                ("maxindel", C.c_uint32)]
+                ("maxindel", C.c_uint32), ("trim_left_each", C.POINTER(C.c_uint32)), ("trim_right_each", C.POINTER(C.c_uint32))]
 
 
 class SeedResult(C.Structure):
@@ -1344,6 +1367,11 @@ class PreparedBasecall:
         s.data = self.payload["profiles"].data_ptr() if self.device else self.payload["profiles"].ctypes.data
         s.offset, s.length, s.count = _u64p(self._prof_off), _u32p(self.meta["bc_len"]), self.nt
         return s
+
+    def trims(self):
+        """(trim_left, trim_right) of a finished run as the per-trace arrays Context.align_traces, PreparedAlign and
+        Context.decompose_traces take for their trims: the chain signals -> basecalls -> alignments with a trim stringency set"""
+        return self.meta["trim_left"][:self.nt].copy(), self.meta["trim_right"][:self.nt].copy()
 
     def basecalls_struct(self, peaks_only=True):
         """tracyhip_basecalls of the batch (bcpos / primary / secondary / the peak table as the call left them)"""

@@ -552,7 +552,7 @@ bool alignment_rows(tracyhip_ctx* ctx, tracyhip_seqset const& s1, tracyhip_seqse
   return true;
 }
 
-// FASTA references: sage.h:233-260 + :311 for every job sharing one (trimLeft, trimRight)
+// FASTA references: sage.h:233-260 + :311 for the jobs of a block in one call, every trace with its own (trimLeft, trimRight)
 bool align_fasta_group(Device& dev, tracyhip_params const& prm, std::vector<Job*> const& jobs, uint32_t nthreads) {
   PhaseClock pc;  // (on the calling thread: pack / device_call / unpack are wall seconds of the device stage)
   tracyhip_ctx* ctx = dev.ctx;
@@ -584,8 +584,10 @@ bool align_fasta_group(Device& dev, tracyhip_params const& prm, std::vector<Job*
   job.ntraces = nt;
   job.profiles = tracyhip_seqset{TRACYHIP_SEQ_PROFILE, prof.get(), poff.data(), plen.data(), nt};
   job.refs = tracyhip_seqset{TRACYHIP_SEQ_CHAR, refs.get(), roff.data(), rlen.data(), nt};
-  job.trim_left = jobs[0]->trimLeft;
-  job.trim_right = jobs[0]->trimRight;
+  std::vector<uint32_t> trim_l(nt), trim_r(nt);  // -t gives every trace its own pair (trimTrace): the per-trace arrays of the job
+  for (uint32_t i = 0; i < nt; ++i) { trim_l[i] = jobs[i]->trimLeft; trim_r[i] = jobs[i]->trimRight; }
+  job.trim_left_each = trim_l.data();
+  job.trim_right_each = trim_r.data();
   const bool seeded = jobs[0]->rs.filetype == 0;  // groups never mix seeded and FASTA references
   std::vector<uint8_t> orient(nt);
   for (uint32_t i = 0; i < nt; ++i) orient[i] = jobs[i]->rs.forward ? 1 : 0;
@@ -799,22 +801,24 @@ int align_main(int argc, char** argv) {
       dev_open = true;
     }
     Stopwatch sw;
-    std::map<std::pair<uint32_t, uint32_t>, std::vector<Job*>> fasta_groups, seeded_groups;
-    std::vector<Job*> wildtype;
+    std::vector<Job*> fasta_group, seeded_group, wildtype;  // by reference kind alone: the trims travel per trace
     for (uint32_t i = lo; i < hi; ++i) {
       Job& j = jobs[i];
       if (!j.ok) continue;
-      if (j.rs.filetype == 1) fasta_groups[std::make_pair(j.trimLeft, j.trimRight)].push_back(&j);
-      else if (j.rs.filetype == 0) seeded_groups[std::make_pair(j.trimLeft, j.trimRight)].push_back(&j);
+      if (j.rs.filetype == 1) fasta_group.push_back(&j);
+      else if (j.rs.filetype == 0) seeded_group.push_back(&j);
       else wildtype.push_back(&j);
     }
     if (!said) std::cout << stamp() << "Alignment" << std::endl;
     said = true;
     fatal = -1;
-    for (auto& g : fasta_groups)
-      if (!align_fasta_group(dev, prm, g.second, nthreads)) return false;
-    for (auto& g : seeded_groups)
-      if (!align_fasta_group(dev, prm, g.second, nthreads)) return false;
+    uint32_t device_calls = 0;
+    for (auto* g : {&fasta_group, &seeded_group}) {
+      if (g->empty()) continue;
+      if (!align_fasta_group(dev, prm, *g, nthreads)) return false;
+      ++device_calls;
+    }
+    times.add("device_calls", (double)device_calls);  // align_traces calls of the run
     if (!wildtype.empty() && !align_wildtype_group(dev.ctx, prm, wildtype)) return false;
     fatal = 0;
     times.add("device_s", sw.seconds());
@@ -947,8 +951,8 @@ bool orient_wildtype(tracyhip_ctx* ctx, tracyhip_params const& prm, std::vector<
   return true;
 }
 
-// indigo.h:190-388 for every job sharing one (trimLeft, trimRight): the whole chain runs on the device
-// One group of a block (same reference kind and trims) on its way through tracyhip_decompose_traces: pack() lays the batch out as
+// indigo.h:190-388 for the jobs of a block that share a reference kind: the whole chain runs on the device, every trace with its own trims
+// One group of a block (same reference kind) on its way through tracyhip_decompose_traces: pack() lays the batch out as
 // packed payloads and sizes the result arrays -- host work, done by the stage that prepares the block (for wildtype references by
 // the device stage, once the device has oriented them); run() is the call, the results back into the jobs and the alignment rows.
 struct DecomposeGroup {
@@ -956,7 +960,7 @@ struct DecomposeGroup {
   uint32_t nt = 0;
   bool wildtype = false, seeded = false, packed = false;
   std::vector<uint64_t> poff, roff, boff, dcpoff, ooff[3], wpoff;
-  std::vector<uint32_t> plen, rlen, blen, sb[2], sl[2], rp[2], olen[3];
+  std::vector<uint32_t> plen, rlen, blen, sb[2], sl[2], rp[2], olen[3], trim_l, trim_r;
   uint32_t dcap = 0;
   uint64_t ocap[3] = {0, 0, 0}, btot = 0;
   struct Packed {
@@ -1031,7 +1035,11 @@ struct DecomposeGroup {
     job.profiles = tracyhip_seqset{TRACYHIP_SEQ_PROFILE, prof_p, poff.data(), plen.data(), nt};
     job.bc = tracyhip_basecalls{nt, nullptr, nullptr, nullptr, nullptr, pri_p, sec_p, boff.data(), blen.data(), pk.peaks.get()};
     job.refs = tracyhip_seqset{TRACYHIP_SEQ_CHAR, refs_p, roff.data(), rlen.data(), nt};
-    job.dprm = tracyhip_decomp_params{(int32_t)jobs[0]->trimLeft, (int32_t)jobs[0]->trimRight, (int32_t)c.maxindel, (int32_t)c.madc};
+    job.dprm = tracyhip_decomp_params{0, 0, (int32_t)c.maxindel, (int32_t)c.madc};
+    trim_l.resize(nt); trim_r.resize(nt);  // -t gives every trace its own pair (trimTrace): the per-trace arrays of the job
+    for (uint32_t i = 0; i < nt; ++i) { trim_l[i] = jobs[i]->trimLeft; trim_r[i] = jobs[i]->trimRight; }
+    job.trim_left_each = trim_l.data();
+    job.trim_right_each = trim_r.data();
     job.strand_by_certificate = 1;  // the orientation scores are not written anywhere (indigo.h:235-247 keeps only rs.forward)
     seeded = jobs[0]->rs.filetype == 0 || wildtype;  // the reference arrives oriented
     orient.assign(nt, 0);
@@ -1298,11 +1306,11 @@ int decompose_main(int argc, char** argv) {
         jobs[i].ok = true;
       }
     }
-    // the block's groups (reference kind, trims), packed for the device here -- host work that the device stage would otherwise do
+    // the block's groups (by reference kind), packed for the device here -- host work that the device stage would otherwise do
     // between two calls, on the one thread every block has to pass
-    std::map<std::pair<uint32_t, std::pair<uint32_t, uint32_t>>, std::vector<Job*>> groups;
+    std::map<uint32_t, std::vector<Job*>> groups;
     for (uint32_t i = lo; i < hi; ++i)
-      if (jobs[i].ok) groups[std::make_pair((uint32_t)jobs[i].rs.filetype, std::make_pair(jobs[i].trimLeft, jobs[i].trimRight))].push_back(&jobs[i]);
+      if (jobs[i].ok) groups[(uint32_t)jobs[i].rs.filetype].push_back(&jobs[i]);
     std::vector<std::unique_ptr<DecomposeGroup>>& mine = block_groups[lo / blk];
     for (auto& g : groups) {
       mine.emplace_back(new DecomposeGroup(std::move(g.second)));
@@ -1338,6 +1346,7 @@ int decompose_main(int argc, char** argv) {
     say("Alignment");
     for (auto& g : block_groups[lo / blk])
       if (!g->run(dev, c, prm, nthreads)) return false;
+    times.add("device_calls", (double)block_groups[lo / blk].size());  // decompose_traces calls of the run
     say("InDel Search");
     std::vector<Job*> good;
     for (uint32_t i = lo; i < hi; ++i) {

@@ -61,6 +61,8 @@ struct DecompDesc {
   uint32_t nbc;          // bc.consensus.size()
   uint32_t refslice_len; // rs.refslice.size()
   uint32_t breakpoint;   // bp.breakpoint (trimmed-trace coordinates)
+  uint32_t trim_left, trim_right;  // the trace's requested trims (the bits of IndigoConfig's int32 values): the kernels run the phases with
+                                   // these in place of DecompArgs::prm's pair -- a scalar call writes its pair into every record
 };
 
 struct DecompOut {       // per trace
@@ -86,6 +88,11 @@ struct DecompArgs {
                          // host-planned tiers redo them from the untouched basecalls)
   const uint32_t* only;  // or null: only traces with a non-zero word are decomposed (what decompose_wave.h left to this kernel)
 };
+// prm as a trace sees it: its record's own pair (the phase functions and the wave body read a.prm alone; the kernels call this first)
+TR_HD void decomp_trace_trims(DecompArgs& a, const DecompDesc& d) {
+  a.prm.trimLeft = (int32_t)d.trim_left;
+  a.prm.trimRight = (int32_t)d.trim_right;
+}
 
 constexpr int kMaxIndelDev = 1024;  // maxindel handled in LDS (CLI default 1000)
 

@@ -38,6 +38,7 @@ __global__ __launch_bounds__(64) void decompose_kernel(DecompArgs a, const Break
   if (a.skip && a.skip[t]) return;
   if (a.only && !a.only[t]) return;
   DecompDesc d = a.desc[t];
+  decomp_trace_trims(a, d);
   d.breakpoint = bps[t].breakpoint;
   if (a.lens) d.L = a.lens[t];
   const uint32_t lane = threadIdx.x;
@@ -86,6 +87,7 @@ struct DecompDevWave {
 };
 __global__ __launch_bounds__(64) void decompose_wave_kernel(DecompWaveArgs wa) {
   DecompDevWave w;
+  decomp_trace_trims(wa.a, wa.a.desc[blockIdx.x]);
   decomp_wave_body(w, wa, blockIdx.x);
 }
 
@@ -96,6 +98,7 @@ __global__ __launch_bounds__(64) void decompose_kernel_global(DecompArgs a, cons
   for (uint32_t t = blockIdx.x; t < a.ntraces; t += gridDim.x) {
     if (a.skip && a.skip[t]) continue;
     DecompDesc d = a.desc[t];
+    decomp_trace_trims(a, d);
     d.breakpoint = bps[t].breakpoint;
     if (a.lens) d.L = a.lens[t];
     DecompOut out{};
@@ -396,8 +399,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 
 template <bool GLOBAL>
 __global__ __launch_bounds__(AF_THREADS) void allelic_fraction_kernel(const BcDesc* desc, const int4* peaks, const uint8_t* pri_all,
-                                                                      const uint8_t* sec_all, uint32_t trimLeft,
-                                                                      uint32_t trimRight, AfGrid grid, double* fractions,
+                                                                      const uint8_t* sec_all, AfGrid grid, double* fractions,
                                                                       char* scratch, size_t stride) {
   extern __shared__ __attribute__((aligned(16))) char lds_stage[];
   char* smem = GLOBAL ? scratch + (size_t)blockIdx.x * stride : lds_stage;  // tp / cls of a trace too long for LDS: global scratch
@@ -413,6 +415,7 @@ __global__ __launch_bounds__(AF_THREADS) void allelic_fraction_kernel(const BcDe
   const BcDesc d = desc[blockIdx.x];
   const uint8_t* pri = pri_all + d.bc_off;
   const uint8_t* sec = sec_all + d.bc_off;
+  const uint32_t trimLeft = d.trim_left, trimRight = d.trim_right;  // the trace's own pair, from its record (wave-uniform)
   // trimmedSeq (abif.h:68-75)
   uint32_t off = trimLeft, len;
   if ((uint64_t)(uint32_t)(trimLeft + trimRight + 1) >= (uint64_t)d.nbc) { off = 0; len = d.nbc; }
@@ -637,10 +640,11 @@ __device__ __forceinline__ double wave_min_all(double v) {
 // positions among them are consecutive addresses (a ballot gives every het lane its place).  Two passes over the basecall bytes: tp is
 // laid out [channel][het position] -- the reference's summation order, decompose.h:596-606 -- so the count comes first.
 __global__ __launch_bounds__(64) void af_prepare_kernel(const BcDesc* __restrict__ desc, const int4* __restrict__ peaks, const uint8_t* __restrict__ pri_all,
-                                                        const uint8_t* __restrict__ sec_all, uint32_t trimLeft, uint32_t trimRight, AfScratch sc,
+                                                        const uint8_t* __restrict__ sec_all, AfScratch sc,
                                                         double* __restrict__ fractions) {
   const uint32_t t = blockIdx.x, lane = threadIdx.x;
   const BcDesc d = desc[t];
+  const uint32_t trimLeft = d.trim_left, trimRight = d.trim_right;  // the trace's own pair, from its record (wave-uniform)
   const uint8_t* pri = pri_all + d.bc_off;
   const uint8_t* sec = sec_all + d.bc_off;
   uint32_t off = trimLeft, len;  // trimmedSeq (abif.h:68-75)
@@ -1042,7 +1046,7 @@ static int ensure_af_grid(tracyhip_ctx* ctx, AfGrid& g) {
 }
 
 int launch_allelic_fraction(tracyhip_ctx* ctx, const BcDesc* d_desc, uint32_t n, uint32_t maxbc, const int32_t* d_peaks_, const uint8_t* d_pri, const uint8_t* d_sec,
-                            uint32_t trim_left, uint32_t trim_right, double* d_out, uint64_t work_bytes, uint64_t bext) {
+                            double* d_out, uint64_t work_bytes, uint64_t bext) {
   const int4* d_peaks = reinterpret_cast<const int4*>(d_peaks_);
   if (n == 0) return TRACYHIP_OK;
   const size_t lds = (((size_t)maxbc * 36 + 64) + 15) & ~(size_t)15;  // tp (4 doubles per basecall) + class bytes
@@ -1065,16 +1069,14 @@ int launch_allelic_fraction(tracyhip_ctx* ctx, const BcDesc* d_desc, uint32_t n,
   }
   { int trc_ = timing_begin(ctx, TRACYHIP_TIMER_AFRAC, 0, work_bytes); if (trc_) return trc_; }
   if (split) {
-    hipLaunchKernelGGL(af_prepare_kernel, dim3(n), dim3(64), 0, ctx->stream, d_desc, d_peaks, d_pri, d_sec, trim_left, trim_right, sc, d_out);
+    hipLaunchKernelGGL(af_prepare_kernel, dim3(n), dim3(64), 0, ctx->stream, d_desc, d_peaks, d_pri, d_sec, sc, d_out);
     hipLaunchKernelGGL(af_search_kernel, dim3(n), dim3(64), 0, ctx->stream, d_desc, sc.tp, sc.cls, sc.hdr, grid, d_out);
   } else if (global) {
     HIP_TRY(ctx->dev[DB_BITS].ensure(lds * (size_t)n));
-    hipLaunchKernelGGL(allelic_fraction_kernel<true>, dim3(n), dim3(AF_THREADS), 0, ctx->stream, d_desc, d_peaks, d_pri, d_sec, trim_left,
-                       trim_right, grid, d_out, static_cast<char*>(ctx->dev[DB_BITS].p), lds);
+    hipLaunchKernelGGL(allelic_fraction_kernel<true>, dim3(n), dim3(AF_THREADS), 0, ctx->stream, d_desc, d_peaks, d_pri, d_sec, grid, d_out, static_cast<char*>(ctx->dev[DB_BITS].p), lds);
   } else {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(allelic_fraction_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(allelic_fraction_kernel<false>, dim3(n), dim3(AF_THREADS), lds, ctx->stream, d_desc, d_peaks, d_pri, d_sec, trim_left,
-                       trim_right, grid, d_out, nullptr, (size_t)0);
+    hipLaunchKernelGGL(allelic_fraction_kernel<false>, dim3(n), dim3(AF_THREADS), lds, ctx->stream, d_desc, d_peaks, d_pri, d_sec, grid, d_out, nullptr, (size_t)0);
   }
   HIP_TRY(hipGetLastError());
   { int trc_ = timing_end(ctx); if (trc_) return trc_; }
@@ -1159,7 +1161,7 @@ int tracyhip_decompose_alleles(tracyhip_ctx* ctx, const tracyhip_basecalls* bc, 
   std::vector<DecompDesc> hd(n);
   for (uint32_t i = 0; i < n; ++i) {
 
-    hd[i] = DecompDesc{rows_offset[i], bc->bc_offset[i], dcp_offset[i], rows_len[i], bc->bc_len[i], refslice_len[i], 0};
+    hd[i] = DecompDesc{rows_offset[i], bc->bc_offset[i], dcp_offset[i], rows_len[i], bc->bc_len[i], refslice_len[i], 0, (uint32_t)prm->trim_left, (uint32_t)prm->trim_right};
     dext = std::max<uint64_t>(dext, dcp_offset[i] + 2ull * prm->maxindel + 2);
   }
   const void *d_r0, *d_r1, *d_bp;
@@ -1199,7 +1201,9 @@ int tracyhip_decompose_alleles(tracyhip_ctx* ctx, const tracyhip_basecalls* bc, 
   return TRACYHIP_OK;
 }
 
-static int bc_descs(tracyhip_ctx* ctx, const tracyhip_basecalls* bc, int mem, const BcDesc** dd, const int32_t** d_peaks, uint64_t* bext) {
+// trim_left / trim_right: the stage call's scalar pair, written into every record (allelicFraction alone reads it)
+static int bc_descs(tracyhip_ctx* ctx, const tracyhip_basecalls* bc, int mem, const BcDesc** dd, const int32_t** d_peaks, uint64_t* bext,
+                    uint32_t trim_left = 0, uint32_t trim_right = 0) {
   // descriptors + the peak table of the batch: the caller's (tracyhip_basecalls::peaks), or built here from the chromatograms
   const uint32_t n = bc->ntraces;
   if (!bc->bc_offset || !bc->bc_len) return set_error(TRACYHIP_ERR_ARG, "null basecall arrays");
@@ -1209,7 +1213,7 @@ static int bc_descs(tracyhip_ctx* ctx, const tracyhip_basecalls* bc, int mem, co
   uint64_t sext = 0;
   uint32_t maxbc = 0;
   for (uint32_t i = 0; i < n; ++i) {
-    hd[i] = BcDesc{bc->peaks ? 0ull : bc->signal_offset[i], bc->bc_offset[i], bc->peaks ? 0u : bc->nsamples[i], bc->bc_len[i]};
+    hd[i] = BcDesc{bc->peaks ? 0ull : bc->signal_offset[i], bc->bc_offset[i], bc->peaks ? 0u : bc->nsamples[i], bc->bc_len[i], trim_left, trim_right};
     if (!bc->peaks) sext = std::max<uint64_t>(sext, bc->signal_offset[i] + 4ull * bc->nsamples[i]);
     maxbc = std::max(maxbc, bc->bc_len[i]);
   }
@@ -1270,7 +1274,7 @@ int tracyhip_allelic_fraction(tracyhip_ctx* ctx, const tracyhip_basecalls* bc, c
   const void *d_pri, *d_sec;
   const int32_t* d_peaks;
   uint64_t bext;
-  if ((rc = bc_descs(ctx, bc, mem, &dd, &d_peaks, &bext))) return rc;
+  if ((rc = bc_descs(ctx, bc, mem, &dd, &d_peaks, &bext, trim_left, trim_right))) return rc;
   if ((rc = stage_in(ctx, ctx->dev[DB_PRIMARY_STAGE], bc->primary, bext, mem, &d_pri))) return rc;
   if ((rc = stage_in(ctx, ctx->dev[DB_SECONDARY_STAGE], secdecomp, bext, mem, &d_sec))) return rc;
   void* d_out;
@@ -1278,7 +1282,7 @@ int tracyhip_allelic_fraction(tracyhip_ctx* ctx, const tracyhip_basecalls* bc, c
   uint32_t maxbc = 0;
   for (uint32_t i = 0; i < n; ++i) maxbc = std::max(maxbc, bc->bc_len[i]);
   if ((rc = launch_allelic_fraction(ctx, dd, n, maxbc, d_peaks,
-                                    static_cast<const uint8_t*>(d_pri), static_cast<const uint8_t*>(d_sec), trim_left, trim_right,
+                                    static_cast<const uint8_t*>(d_pri), static_cast<const uint8_t*>(d_sec),
                                     static_cast<double*>(d_out), 0, bext)))
     return rc;
   if ((rc = unstage(ctx, fractions, d_out, sizeof(double) * 2 * (size_t)n, mem))) return rc;

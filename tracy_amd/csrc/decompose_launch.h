@@ -10,7 +10,10 @@ namespace tracyhip {
 
 struct BpDesc { uint64_t off; uint32_t stride; uint32_t ncol; };     // profile view: p[k][j] at off + k*stride + j
 struct RowsDesc { uint64_t off; uint32_t L; uint32_t pad; };
-struct BcDesc { uint64_t sig_off; uint64_t bc_off; uint32_t nsamples; uint32_t nbc; };
+struct BcDesc {
+  uint64_t sig_off; uint64_t bc_off; uint32_t nsamples; uint32_t nbc;
+  uint32_t trim_left, trim_right;  // the trace's requested trims (allelicFraction reads them: trimmedSeq, bcPos[i + trimLeft]) -- a scalar call writes its pair into every record
+};
 
 int launch_breakpoint(tracyhip_ctx* ctx, const BpDesc* d_desc, uint32_t n, uint32_t maxcol, const float* d_prof, BreakpointOut* d_out);
 int launch_homozygous(tracyhip_ctx* ctx, const RowsDesc* d_desc, const uint8_t* d_rows0, const uint8_t* d_rows1, uint32_t n,
@@ -26,7 +29,7 @@ int launch_peaks(tracyhip_ctx* ctx, const BcDesc* d_desc, uint32_t n, uint32_t m
 int launch_secdecomp(tracyhip_ctx* ctx, const BcDesc* d_desc, uint32_t n, uint32_t maxbc, const int32_t* d_peaks, const uint8_t* d_pri, const uint8_t* d_sec,
                      uint8_t* d_out);
 int launch_allelic_fraction(tracyhip_ctx* ctx, const BcDesc* d_desc, uint32_t n, uint32_t maxbc, const int32_t* d_peaks, const uint8_t* d_pri, const uint8_t* d_sec,
-                            uint32_t trim_left, uint32_t trim_right, double* d_out, uint64_t work_bytes = 0, uint64_t bext = 0);  // bext: extent of the basecall arrays (max of
+                            double* d_out, uint64_t work_bytes = 0, uint64_t bext = 0);  // bext: extent of the basecall arrays (max of
                             // bc_off + nbc; 0 = not known): with it the two-launch form runs (af_prepare_kernel / af_search_kernel, scratch of 36 bext bytes)
 
 }  // namespace tracyhip

@@ -12,6 +12,19 @@ namespace tracyhip {
 // a launch reported values outside its proven range; nothing was written, the host-planned pipeline takes the whole call
 constexpr int kStreamNo = 3;
 
+// the trims a job REQUESTS for trace t: its per-trace arrays (trim_left_each / trim_right_each) or, without them, the scalar pair for
+// every trace.  Both pipelines read a job's trims through this alone, so the two forms share every line behind it.
+struct TrimSrc {
+  const uint32_t *l_each, *r_each;
+  uint32_t l, r;
+  uint32_t left(uint32_t t) const { return l_each ? l_each[t] : l; }
+  uint32_t right(uint32_t t) const { return r_each ? r_each[t] : r; }
+};
+inline TrimSrc trims_of(const tracyhip_align_job* j) { return TrimSrc{j->trim_left_each, j->trim_right_each, j->trim_left, j->trim_right}; }
+inline TrimSrc trims_of(const tracyhip_decompose_job* j) {
+  return TrimSrc{j->trim_left_each, j->trim_right_each, (uint32_t)j->dprm.trim_left, (uint32_t)j->dprm.trim_right};
+}
+
 // sage.h:191-311 / indigo.h:190-388 for one context (no lanes), planned by the host between launches: every tier, every fallback
 int align_traces_legacy(tracyhip_ctx* ctx, const tracyhip_align_job* job, const tracyhip_params* prm, int mem, const tracyhip_align_result* out);
 int decompose_traces_legacy(tracyhip_ctx* ctx, const tracyhip_decompose_job* job, const tracyhip_params* prm, int mem,

@@ -19,10 +19,11 @@ using namespace tracyhip;
 // reference bases before s (ri) and inside [s, e) (risize).  Every column before s and from e on is an
 // 'h' (a reference base), and the alignment consumes all n reference bases, so ri = s and
 // risize = n - s - (L - e): only the two ends of the string have to be looked at.  One wave per trace.
+// trim_left / trim_right: the REQUESTED pair of every trace (R9 takes them unclamped), arrays that travel with ref_len in one block.
 __global__ __launch_bounds__(64) void trim_kernel(const uint8_t* __restrict__ ops, const uint64_t* __restrict__ ops_off,
                                                   const uint32_t* __restrict__ ops_len, const uint32_t* __restrict__ ref_len,
-                                                  const uint8_t* __restrict__ forward, uint32_t trim_left,
-                                                  uint32_t trim_right, uint32_t ntraces, TrimRec* __restrict__ out) {
+                                                  const uint8_t* __restrict__ forward, const uint32_t* __restrict__ trim_left,
+                                                  const uint32_t* __restrict__ trim_right, uint32_t ntraces, TrimRec* __restrict__ out) {
   const uint32_t t = blockIdx.x;
   if (t >= ntraces) return;
   const uint8_t* o = ops + ops_off[t];
@@ -64,19 +65,19 @@ __global__ __launch_bounds__(64) void trim_kernel(const uint8_t* __restrict__ op
     else { for (int32_t j = s; j < e; ++j) refcols += (o[L - 1 - j] != 'v'); inside = refcols; }
     risize = inside;
   }
-  out[t] = s_trim_finish(ri, risize, n, trim_left, trim_right, forward[t] != 0);
+  out[t] = s_trim_finish(ri, risize, n, trim_left[t], trim_right[t], forward[t] != 0);
 }
 
 // trimReferenceSlice from the two ends of the alignment alone (origin-tracking sweep, dp_kernels.h gotoh_origin_body):
 // ends[2t] = leading 'h' columns, ends[2t+1] = last column that is not a trailing 'h'; every reference base in between
 // belongs to the slice.
 __global__ void trim_from_ends_kernel(const uint32_t* __restrict__ ends, const uint32_t* __restrict__ ref_len,
-                                      const uint8_t* __restrict__ forward, uint32_t trim_left, uint32_t trim_right, uint32_t ntraces,
-                                      TrimRec* __restrict__ out) {
+                                      const uint8_t* __restrict__ forward, const uint32_t* __restrict__ trim_left,
+                                      const uint32_t* __restrict__ trim_right, uint32_t ntraces, TrimRec* __restrict__ out) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= ntraces) return;
   const uint32_t lead = ends[2 * t], ce = ends[2 * t + 1];
-  out[t] = s_trim_finish(lead, ce >= lead ? ce - lead : 0u, ref_len[t], trim_left, trim_right, forward[t] != 0);
+  out[t] = s_trim_finish(lead, ce >= lead ? ce - lead : 0u, ref_len[t], trim_left[t], trim_right[t], forward[t] != 0);
 }
 
 // c_e of a pair from the row-m values the 16-bit sweep left behind ({H, E - goe} per column): the last column whose H(m, c) is
@@ -103,10 +104,9 @@ __global__ void ends_shift_kernel(uint32_t* __restrict__ ends, const uint32_t* _
 
 // trimReferenceSlice (fmindex.h:429-463) on the two alignment rows themselves, as the reference scans them: s / e = first / last + 1
 // column holding a trace base, ri = reference bases before s, risize = reference bases in [s, e).  One wave per trace.
-struct TrimRowsDesc { uint64_t off; uint32_t L, n; uint8_t forward, pad[7]; };
+struct TrimRowsDesc { uint64_t off; uint32_t L, n, trim_left, trim_right; uint8_t forward, pad[7]; };  // (trim_*: the trace's requested pair)
 __global__ __launch_bounds__(64) void trim_rows_kernel(const TrimRowsDesc* __restrict__ desc, const uint8_t* __restrict__ rows0,
-                                                       const uint8_t* __restrict__ rows1, uint32_t trim_left, uint32_t trim_right,
-                                                       uint32_t ntraces, TrimRec* __restrict__ out) {
+                                                       const uint8_t* __restrict__ rows1, uint32_t ntraces, TrimRec* __restrict__ out) {
   const uint32_t t = blockIdx.x;
   if (t >= ntraces) return;
   const TrimRowsDesc d = desc[t];
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(64) void trim_rows_kernel(const TrimRowsDesc* __res
       risize += (uint32_t)__popcll(__ballot(j < (uint32_t)e && r1[j] != '-'));
     }
   }
-  if (lane == 0) out[t] = s_trim_finish(ri, risize, d.n, trim_left, trim_right, d.forward != 0);
+  if (lane == 0) out[t] = s_trim_finish(ri, risize, d.n, d.trim_left, d.trim_right, d.forward != 0);
 }
 
 // (loadSingleFasta hands over upper-case [ACGTN] only (fasta.h:54-95); anything else makes the string and profile reverse

@@ -785,15 +785,14 @@ int orient_and_align(tracyhip_ctx* ctx, const tracyhip_params& p, const OrientIn
 
 }  // namespace
 
-// what every form of the call checks first; *empty: nothing to do
-static int align_check_args(tracyhip_ctx* ctx, const tracyhip_align_job* job, const tracyhip_params* prm, int mem, const tracyhip_align_result* out, bool* empty) {
-  int rc = ctx_begin(ctx);
-  if (rc) return rc;
-  *empty = false;
+// what every form of the call checks before it plans, on the host alone
+extern "C" int tracyhip_align_validate(const tracyhip_align_job* job, const tracyhip_params* prm, int mem, const tracyhip_align_result* out) {
   if (!job || !out || !prm) return set_error(TRACYHIP_ERR_ARG, "null job/result/params");
   if (mem != TRACYHIP_MEM_HOST && mem != TRACYHIP_MEM_DEVICE) return set_error(TRACYHIP_ERR_ARG, "bad mem kind");
+  if ((job->trim_left_each == nullptr) != (job->trim_right_each == nullptr))
+    return set_error(TRACYHIP_ERR_ARG, "trim_left_each and trim_right_each must be given together");
   const uint32_t nt = job->ntraces;
-  if (nt == 0) { *empty = true; return TRACYHIP_OK; }
+  if (nt == 0) return TRACYHIP_OK;
   const tracyhip_seqset& sp = job->profiles;
   const tracyhip_seqset& sr = job->refs;
   if (sp.kind != TRACYHIP_SEQ_PROFILE || sr.kind != TRACYHIP_SEQ_CHAR) return set_error(TRACYHIP_ERR_ARG, "profiles must be PROFILE, refs CHAR");
@@ -801,6 +800,15 @@ static int align_check_args(tracyhip_ctx* ctx, const tracyhip_align_job* job, co
   if (!out->score_fwd || !out->score_rev || !out->forward || !out->slice_begin || !out->slice_len || !out->ref_pos ||
       !out->score_final || !out->ops || !out->ops_offset || !out->ops_len)
     return set_error(TRACYHIP_ERR_ARG, "null result array");
+  return TRACYHIP_OK;
+}
+// ... and then the context; *empty: nothing to do
+static int align_check_args(tracyhip_ctx* ctx, const tracyhip_align_job* job, const tracyhip_params* prm, int mem, const tracyhip_align_result* out, bool* empty) {
+  *empty = false;
+  int rc = tracyhip_align_validate(job, prm, mem, out);
+  if (rc) return rc;
+  if ((rc = ctx_begin(ctx))) return rc;
+  *empty = job->ntraces == 0;
   return TRACYHIP_OK;
 }
 
@@ -829,6 +837,7 @@ struct AlignRun {
   const void *d_prof = nullptr, *d_ref = nullptr;
   int32_t* d_verr = nullptr;
   std::vector<uint32_t> mf, mt, tl, rn, ridx;
+  const TrimSrc trims;           // the pair the job requests per trace (tl / mt: createProfile's clamped view of it)
   std::vector<B16TableDesc> td;  // substitution tables of the full profiles (band kernels)
   bool b16 = false;
   OrientOut oo;
@@ -837,7 +846,7 @@ struct AlignRun {
   uint64_t ops_total = 0;
 
   AlignRun(tracyhip_ctx* c, const tracyhip_align_job* j, const tracyhip_params* q, int m, const tracyhip_align_result* o)
-      : ctx(c), job(j), prm(q), mem(m), out(o), nt(j->ntraces), sp(j->profiles), sr(j->refs), st(c->stream), p(*q) {
+      : ctx(c), job(j), prm(q), mem(m), out(o), nt(j->ntraces), sp(j->profiles), sr(j->refs), st(c->stream), p(*q), trims(trims_of(j)) {
     p.hfree = 1;  // AlignConfig<true,false> semiglobal (sage.h:165)
     p.vfree = 0;
   }
@@ -869,8 +878,8 @@ struct AlignRun {
       if (ridx[t] >= sr.count) return set_error(TRACYHIP_ERR_ARG, "ref_index[%u] out of range", t);
       mf[t] = sp.length[t];
       rn[t] = sr.length[ridx[t]];
-      uint32_t l = job->trim_left, r = job->trim_right;
-      if ((uint64_t)l + r >= mf[t]) { l = 0; r = 0; }  // createProfile, profile.h:24-27
+      uint32_t l = trims.left(t), r = trims.right(t);
+      if ((uint64_t)l + r >= mf[t]) { l = 0; r = 0; }  // createProfile, profile.h:24-27 (per trace: its own pair)
       tl[t] = l;
       mt[t] = mf[t] - (l + r);
       max_mn = std::max<uint64_t>(max_mn, (uint64_t)mf[t] + rn[t]);
@@ -891,7 +900,7 @@ struct AlignRun {
     HIP_TRY(ensure_into(ctx->dev[DB_PRELIM_OFF], nt, oi.d_ops_off));           // their offsets
     HIP_TRY(ensure_into(ctx->dev[DB_PRELIM_LEN], nt, oi.d_ops_len));           // their lengths
     HIP_TRY(ensure_into(ctx->dev[DB_PRELIM_SCORE], nt, oi.d_score));           // preliminary scores
-    HIP_TRY(ctx->pin[PB_TMP].ensure(sizeof(uint64_t) * (size_t)nt + (size_t)nt * 8));
+    HIP_TRY(ctx->pin[PB_TMP].ensure(sizeof(uint64_t) * (size_t)nt + (size_t)nt * 16));  // (the offsets, then trim()'s block of 13 bytes per trace)
     std::memcpy(ctx->pin[PB_TMP].p, off1.data(), sizeof(uint64_t) * (size_t)nt);
     HIP_TRY(hipMemcpyAsync(ctx->dev[DB_PRELIM_OFF].p, ctx->pin[PB_TMP].p, sizeof(uint64_t) * (size_t)nt, hipMemcpyHostToDevice, st));
     std::vector<uint64_t> a1o(nt), a2o(nt);
@@ -915,22 +924,26 @@ struct AlignRun {
   int trim() {
     // ---- 3. trimReferenceSlice (sage.h:259) ----
     HIP_TRY(ctx->dev[DB_TRIMREC].ensure(sizeof(TrimRec) * (size_t)nt));
-    HIP_TRY(ctx->dev[DB_TRIM_IN].ensure(sizeof(uint32_t) * (size_t)nt + (size_t)nt));
+    // one block, one copy: window lengths, each trace's requested trims, strands
+    HIP_TRY(ctx->dev[DB_TRIM_IN].ensure(3 * sizeof(uint32_t) * (size_t)nt + (size_t)nt));
     uint32_t* d_rn = static_cast<uint32_t*>(ctx->dev[DB_TRIM_IN].p);
-    uint8_t* d_fwd = reinterpret_cast<uint8_t*>(d_rn + nt);
+    const uint32_t *d_tl = d_rn + nt, *d_tr = d_rn + 2 * (size_t)nt;
+    uint8_t* d_fwd = reinterpret_cast<uint8_t*>(d_rn + 3 * (size_t)nt);
     {
       uint8_t* hp = static_cast<uint8_t*>(ctx->pin[PB_TMP].p) + sizeof(uint64_t) * (size_t)nt;
-      std::memcpy(hp, rn.data(), sizeof(uint32_t) * (size_t)nt);
-      std::memcpy(hp + sizeof(uint32_t) * (size_t)nt, oo.fwd.data(), nt);
-      HIP_TRY(hipMemcpyAsync(d_rn, hp, sizeof(uint32_t) * (size_t)nt + nt, hipMemcpyHostToDevice, st));
+      uint32_t* hw = reinterpret_cast<uint32_t*>(hp);
+      std::memcpy(hw, rn.data(), sizeof(uint32_t) * (size_t)nt);
+      for (uint32_t t = 0; t < nt; ++t) { hw[nt + t] = trims.left(t); hw[2 * (size_t)nt + t] = trims.right(t); }
+      std::memcpy(hp + 3 * sizeof(uint32_t) * (size_t)nt, oo.fwd.data(), nt);
+      HIP_TRY(hipMemcpyAsync(d_rn, hp, 3 * sizeof(uint32_t) * (size_t)nt + nt, hipMemcpyHostToDevice, st));
     }
     if (oo.d_ends)  // the two ends of the preliminary alignment (origin-tracking sweep) instead of its ops
       hipLaunchKernelGGL(trim_from_ends_kernel, dim3((nt + 255) / 256), dim3(256), 0, st, oo.d_ends, static_cast<const uint32_t*>(d_rn),
-                         static_cast<const uint8_t*>(d_fwd), (uint32_t)job->trim_left, (uint32_t)job->trim_right, nt, static_cast<TrimRec*>(ctx->dev[DB_TRIMREC].p));
+                         static_cast<const uint8_t*>(d_fwd), d_tl, d_tr, nt, static_cast<TrimRec*>(ctx->dev[DB_TRIMREC].p));
     else
       hipLaunchKernelGGL(trim_kernel, dim3(nt), dim3(64), 0, st, static_cast<const uint8_t*>(ctx->dev[DB_PRELIM_OPS].p),
                          static_cast<const uint64_t*>(ctx->dev[DB_PRELIM_OFF].p), static_cast<const uint32_t*>(ctx->dev[DB_PRELIM_LEN].p), d_rn, d_fwd,
-                         job->trim_left, job->trim_right, nt, static_cast<TrimRec*>(ctx->dev[DB_TRIMREC].p));
+                         d_tl, d_tr, nt, static_cast<TrimRec*>(ctx->dev[DB_TRIMREC].p));
     HIP_TRY(hipGetLastError());
     h_trim.resize(nt);
     HIP_TRY(hipMemcpyAsync(h_trim.data(), ctx->dev[DB_TRIMREC].p, sizeof(TrimRec) * (size_t)nt, hipMemcpyDeviceToHost, st));
@@ -1256,6 +1269,7 @@ struct AlignChunk {
     if (job->ref_index) j.ref_index = job->ref_index + lo;  // shared references: the whole set goes with every chunk
     else { sub_seqset(job->refs, lo, k, 1, sr); j.refs = sr.s; }
     j.oriented = shifted(job->oriented, lo);
+    j.trim_left_each = shifted(job->trim_left_each, lo); j.trim_right_each = shifted(job->trim_right_each, lo);
     sub_offsets(out->ops_offset, lo, k, so);
     AlignFields::each(o, *out, [&](auto& mine, auto& theirs, uint32_t per) { mine = shifted(theirs, (uint64_t)per * lo); });
     o.ops = shifted(out->ops, so.base); o.ops_offset = so.off.data();
@@ -1302,15 +1316,18 @@ struct DevOut {  // a result array: the user's (DEVICE) or a staging buffer (HOS
 
 }  // namespace
 
-static int decompose_check_args(tracyhip_ctx* ctx, const tracyhip_decompose_job* job, const tracyhip_params* prm, int mem, const tracyhip_decompose_result* out,
-                                bool* empty) {
-  int rc = ctx_begin(ctx);
-  if (rc) return rc;
-  *empty = false;
+// what every form of the call checks before it plans, on the host alone
+extern "C" int tracyhip_decompose_validate(const tracyhip_decompose_job* job, const tracyhip_params* prm, int mem, const tracyhip_decompose_result* out) {
   if (!job || !out || !prm) return set_error(TRACYHIP_ERR_ARG, "null job/result/params");
   if (mem != TRACYHIP_MEM_HOST && mem != TRACYHIP_MEM_DEVICE) return set_error(TRACYHIP_ERR_ARG, "bad mem kind");
+  if ((job->trim_left_each == nullptr) != (job->trim_right_each == nullptr))
+    return set_error(TRACYHIP_ERR_ARG, "trim_left_each and trim_right_each must be given together");
   const uint32_t nt = job->ntraces;
-  if (nt == 0) { *empty = true; return TRACYHIP_OK; }
+  if (nt == 0) return TRACYHIP_OK;
+  if (job->trim_left_each)  // (IndigoConfig holds the trims as int: a negative one, per trace)
+    for (uint32_t t = 0; t < nt; ++t)
+      if (job->trim_left_each[t] > 0x7fffffffu || job->trim_right_each[t] > 0x7fffffffu)
+        return set_error(TRACYHIP_ERR_ARG, "trim of trace %u above INT32_MAX", t);
   const tracyhip_seqset& sp = job->profiles;
   const tracyhip_seqset& sr = job->refs;
   const tracyhip_basecalls& bc = job->bc;
@@ -1327,6 +1344,16 @@ static int decompose_check_args(tracyhip_ctx* ctx, const tracyhip_decompose_job*
     if (!out->score[k] || !out->ops[k] || !out->ops_offset[k] || !out->ops_len[k]) return set_error(TRACYHIP_ERR_ARG, "null allele alignment arrays");
   for (int k = 0; k < 2; ++k)
     if (!out->slice_begin[k] || !out->slice_len[k] || !out->ref_pos[k]) return set_error(TRACYHIP_ERR_ARG, "null allele slice arrays");
+  return TRACYHIP_OK;
+}
+// ... and then the context; *empty: nothing to do
+static int decompose_check_args(tracyhip_ctx* ctx, const tracyhip_decompose_job* job, const tracyhip_params* prm, int mem, const tracyhip_decompose_result* out,
+                                bool* empty) {
+  *empty = false;
+  int rc = tracyhip_decompose_validate(job, prm, mem, out);
+  if (rc) return rc;
+  if ((rc = ctx_begin(ctx))) return rc;
+  *empty = job->ntraces == 0;
   return TRACYHIP_OK;
 }
 
@@ -1355,7 +1382,7 @@ struct DecomposeRun {
   const tracyhip_seqset& srp;  // wildtype-trace reference (indigo.h:249-289), or data == null
   hipStream_t st;
   tracyhip_params p, pglobal;
-  const uint32_t TL, TR;
+  const TrimSrc trims;  // the pair the job requests per trace
   const bool wildtype, given, shared_stages;
   StageClock stage_clock, sc6;
   std::vector<uint32_t> mf, mt, tl, rn, ridx, sl, soff;  // sl / soff: trimmedSeq(length, offset)
@@ -1398,7 +1425,7 @@ struct DecomposeRun {
 
   DecomposeRun(tracyhip_ctx* c, const tracyhip_decompose_job* j, const tracyhip_params* q, int m, const tracyhip_decompose_result* o)
       : ctx(c), job(j), prm(q), mem(m), out(o), nt(j->ntraces), sp(j->profiles), sr(j->refs), bc(j->bc), dp(j->dprm), srp(j->ref_profiles), st(c->stream),
-        p(*q), pglobal(*q), TL((uint32_t)j->dprm.trim_left), TR((uint32_t)j->dprm.trim_right), wildtype(j->ref_profiles.data != nullptr),
+        p(*q), pglobal(*q), trims(trims_of(j)), wildtype(j->ref_profiles.data != nullptr),
         given(j->oriented != nullptr), shared_stages(j->ref_profiles.data == nullptr), b_sc2(buf()), b_ops1(buf()), b_len1(buf()),
         b_r0(buf()), b_r1(buf()), b_hst(buf()), b_cq1(buf()), b_cq2(buf()), b_cqf(buf()), b_opsA(buf()),
         b_lenA(buf()), b_trimA(buf()), b_rnfw(buf()), b_ends(buf()) {  // (the first fourteen of the range, in the order of their declaration)
@@ -1439,6 +1466,7 @@ struct DecomposeRun {
       rn[t] = sr.length[ridx[t]];
       if (bc.bc_len[t] != mf[t]) return set_error(TRACYHIP_ERR_ARG, "trace %u: profile has %u columns but %u basecalls", t, mf[t], bc.bc_len[t]);
       if (bc.bc_len[t] >= 2u * kMaxIndelGlobal) return set_error(TRACYHIP_ERR_RANGE, "trace %u has %u basecalls; the scan tables hold < %d", t, bc.bc_len[t], 2 * kMaxIndelGlobal);
+      const uint32_t TL = trims.left(t), TR = trims.right(t);  // this trace's own pair
       uint32_t l = TL, r = TR;
       if ((uint64_t)l + r >= mf[t]) { l = 0; r = 0; }  // createProfile, profile.h:24-27
       tl[t] = l;
@@ -1650,7 +1678,7 @@ struct DecomposeRun {
     // ---- 5. decomposeAlleles, generateSecondaryDecomposed, allelicFraction (indigo.h:340-350) ----
     {
       std::vector<DecompDesc> hd(nt);
-      for (uint32_t t = 0; t < nt; ++t) hd[t] = DecompDesc{off1[t], bc.bc_offset[t], out->dcp_offset[t], 0, mf[t], rn[t], 0};
+      for (uint32_t t = 0; t < nt; ++t) hd[t] = DecompDesc{off1[t], bc.bc_offset[t], out->dcp_offset[t], 0, mf[t], rn[t], 0, trims.left(t), trims.right(t)};
       const DecompDesc* dd;
       if ((rc = upload(ctx, buf(), hd, &dd))) return rc;
       DecompArgs a{};
@@ -1667,7 +1695,7 @@ struct DecomposeRun {
       a.lens = d_len1;
       if ((rc = launch_decompose(ctx, a, static_cast<const BreakpointOut*>(d_bp), maxbc, 0, 0))) return rc;  // accounted below, once the lengths are here
       std::vector<BcDesc> hb(nt);
-      for (uint32_t t = 0; t < nt; ++t) hb[t] = BcDesc{bc.peaks ? 0ull : bc.signal_offset[t], bc.bc_offset[t], bc.peaks ? 0u : bc.nsamples[t], mf[t]};
+      for (uint32_t t = 0; t < nt; ++t) hb[t] = BcDesc{bc.peaks ? 0ull : bc.signal_offset[t], bc.bc_offset[t], bc.peaks ? 0u : bc.nsamples[t], mf[t], trims.left(t), trims.right(t)};
       const BcDesc* db;
       if ((rc = upload(ctx, buf(), hb, &db))) return rc;
       if (!d_peaks) {  // no table from the caller: built once, read by both kernels below
@@ -1680,7 +1708,7 @@ struct DecomposeRun {
                                  static_cast<const uint8_t*>(d_pri), static_cast<const uint8_t*>(d_sec), static_cast<uint8_t*>(d_sd))))
         return rc;
       if ((rc = launch_allelic_fraction(ctx, db, nt, maxbc, static_cast<const int32_t*>(d_peaks),
-                                        static_cast<const uint8_t*>(d_pri), static_cast<const uint8_t*>(d_sd), TL, TR,
+                                        static_cast<const uint8_t*>(d_pri), static_cast<const uint8_t*>(d_sd),
                                         static_cast<double*>(d_fr), 18ull * std::accumulate(mf.begin(), mf.end(), 0ull),
                                         [&] { uint64_t e = 0; for (uint32_t t = 0; t < nt; ++t) e = std::max<uint64_t>(e, bc.bc_offset[t] + mf[t]); return e; }())))
         return rc;
@@ -1740,20 +1768,30 @@ struct DecomposeRun {
     return TRACYHIP_OK;
   }
 
+  // b_rnfw: [window lengths | requested left trims | right trims | strands (bytes)], by trace
+  const uint32_t* rnfw_tl() const { return static_cast<const uint32_t*>(b_rnfw.p) + nt; }
+  const uint32_t* rnfw_tr() const { return static_cast<const uint32_t*>(b_rnfw.p) + 2 * (size_t)nt; }
+  const uint8_t* rnfw_fwd() const { return reinterpret_cast<const uint8_t*>(static_cast<const uint32_t*>(b_rnfw.p) + 3 * (size_t)nt); }
   int allele_setup() {
     int rc;
     stage_clock.mark("decompose.6_allele");
     // ---- 6. allele-specific alignments (indigo.h:355-387): string x string Gotoh ----
     // allele k in {0: primary, 1: secDecompose}: gotoh(seq, rs.refslice) -> trimReferenceSlice -> gotoh(seq, slice)
     HIP_TRY(b_ends.ensure(sizeof(uint32_t) * 2 * (size_t)nt));
-    HIP_TRY(b_opsA.ensure(tot1 + 2ull * TL * nt + 16));
+    {  // ops of gotoh(allele, window): sl + rn bytes per trace (sl exceeds mt where trimmedSeq keeps a string createProfile trims)
+      uint64_t totA = 0;
+      for (uint32_t t = 0; t < nt; ++t) totA += (uint64_t)sl[t] + rn[t];
+      HIP_TRY(b_opsA.ensure(std::max(tot1, totA) + 2ull * std::accumulate(tl.begin(), tl.end(), 0ull) + 16));
+    }
     HIP_TRY(b_lenA.ensure(sizeof(uint32_t) * (size_t)nt));
     HIP_TRY(b_trimA.ensure(sizeof(TrimRec) * (size_t)nt));
-    HIP_TRY(b_rnfw.ensure(sizeof(uint32_t) * (size_t)nt + nt));
-    {
-      std::vector<uint8_t> tmp(sizeof(uint32_t) * (size_t)nt + nt);
-      std::memcpy(tmp.data(), rn.data(), sizeof(uint32_t) * (size_t)nt);
-      std::memcpy(tmp.data() + sizeof(uint32_t) * (size_t)nt, h_fwd.data(), nt);
+    HIP_TRY(b_rnfw.ensure(3 * sizeof(uint32_t) * (size_t)nt + nt));
+    {  // one block, one copy: window lengths, each trace's requested trims, strands
+      std::vector<uint8_t> tmp(3 * sizeof(uint32_t) * (size_t)nt + nt);
+      uint32_t* w = reinterpret_cast<uint32_t*>(tmp.data());
+      std::memcpy(w, rn.data(), sizeof(uint32_t) * (size_t)nt);
+      for (uint32_t t = 0; t < nt; ++t) { w[nt + t] = trims.left(t); w[2 * (size_t)nt + t] = trims.right(t); }
+      std::memcpy(tmp.data() + 3 * sizeof(uint32_t) * (size_t)nt, h_fwd.data(), nt);
       HIP_TRY(hipMemcpy(b_rnfw.p, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
     }
     offA.resize(nt);
@@ -2005,8 +2043,7 @@ struct DecomposeRun {
                          static_cast<const uint32_t*>(A.d_shift), nt);
     }
     hipLaunchKernelGGL(trim_from_ends_kernel, dim3((nt + 255) / 256), dim3(256), 0, st, static_cast<const uint32_t*>(b_ends.p),
-                       static_cast<const uint32_t*>(b_rnfw.p), reinterpret_cast<const uint8_t*>(static_cast<const uint32_t*>(b_rnfw.p) + nt),
-                       TL, TR, nt, static_cast<TrimRec*>(b_trimA.p));
+                       static_cast<const uint32_t*>(b_rnfw.p), rnfw_fwd(), rnfw_tl(), rnfw_tr(), nt, static_cast<TrimRec*>(b_trimA.p));
     return TRACYHIP_OK;
   }
 
@@ -2016,8 +2053,7 @@ struct DecomposeRun {
     if ((rc = run_dp(ctx, A.pb, &p, false, true, nullptr, static_cast<uint8_t*>(b_opsA.p), d_offA, static_cast<uint32_t*>(b_lenA.p)))) return rc;
     hipLaunchKernelGGL(trim_kernel, dim3(nt), dim3(64), 0, st, static_cast<const uint8_t*>(b_opsA.p), d_offA,
                        static_cast<const uint32_t*>(b_lenA.p), static_cast<const uint32_t*>(b_rnfw.p),
-                       reinterpret_cast<const uint8_t*>(static_cast<const uint32_t*>(b_rnfw.p) + nt), TL, TR, nt,
-                       static_cast<TrimRec*>(b_trimA.p));
+                       rnfw_fwd(), rnfw_tl(), rnfw_tr(), nt, static_cast<TrimRec*>(b_trimA.p));
     return TRACYHIP_OK;
   }
 
@@ -2225,6 +2261,7 @@ struct DecomposeChunk {
       if (job->ref_profiles.data) { sub_seqset(job->ref_profiles, lo, k, sizeof(float), srp); j.ref_profiles = srp.s; }
     }
     j.oriented = shifted(job->oriented, lo);
+    j.trim_left_each = shifted(job->trim_left_each, lo); j.trim_right_each = shifted(job->trim_right_each, lo);
     // Trace + BaseCalls: signal by signal_offset, the per-base arrays by bc_offset
     sub_offsets(job->bc.bc_offset, lo, k, bco);
     j.bc.ntraces = k;
@@ -2421,7 +2458,7 @@ extern "C" int tracyhip_trim_reference_slice(tracyhip_ctx* ctx, uint32_t ntraces
   std::vector<TrimRowsDesc> hd(ntraces);
   for (uint32_t t = 0; t < ntraces; ++t) {
     ext = std::max<uint64_t>(ext, rows_offset[t] + rows_len[t]);
-    hd[t] = TrimRowsDesc{rows_offset[t], rows_len[t], refslice_len[t], (uint8_t)(forward[t] ? 1 : 0), {0, 0, 0, 0, 0, 0, 0}};
+    hd[t] = TrimRowsDesc{rows_offset[t], rows_len[t], refslice_len[t], trim_left, trim_right, (uint8_t)(forward[t] ? 1 : 0), {0, 0, 0, 0, 0, 0, 0}};
   }
   const void *d_r0, *d_r1;
   if ((rc = stage_in(ctx, ctx->dev[DB_ROWS0], rows0, ext, mem, &d_r0))) return rc;
@@ -2430,7 +2467,7 @@ extern "C" int tracyhip_trim_reference_slice(tracyhip_ctx* ctx, uint32_t ntraces
   HIP_TRY(hipMemcpyAsync(ctx->dev[DB_DESC].p, hd.data(), sizeof(TrimRowsDesc) * (size_t)ntraces, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx->dev[DB_TRIMREC].ensure(sizeof(TrimRec) * (size_t)ntraces));
   hipLaunchKernelGGL(trim_rows_kernel, dim3(ntraces), dim3(64), 0, st, static_cast<const TrimRowsDesc*>(ctx->dev[DB_DESC].p),
-                     static_cast<const uint8_t*>(d_r0), static_cast<const uint8_t*>(d_r1), trim_left, trim_right, ntraces,
+                     static_cast<const uint8_t*>(d_r0), static_cast<const uint8_t*>(d_r1), ntraces,
                      static_cast<TrimRec*>(ctx->dev[DB_TRIMREC].p));
   HIP_TRY(hipGetLastError());
   std::vector<TrimRec> h(ntraces);

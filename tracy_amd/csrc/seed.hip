@@ -41,7 +41,8 @@ struct SeedArgs {
   uint8_t* slices;       // trace i's window at slices + i * slice_cap
   uint64_t slice_cap;
   uint32_t n, P, cap;    // P: LDS list capacity per strand (power of two >= cap)
-  uint32_t trim_left, trim_right, kmer, min_support, maxindel;  // (16-bit values)
+  const uint32_t* trims;  // [n] each trace's own trims, left in the low and right in the high 16 bits (a scalar call: its pair n times)
+  uint32_t kmer, min_support, maxindel;  // (16-bit values)
 };
 
 __device__ __forceinline__ void write_status(const SeedArgs& a, uint32_t t, int32_t st) {
@@ -65,7 +66,8 @@ __global__ __launch_bounds__(kSeedThreads) void seed_traces_kernel(SeedArgs a) {
   const uint32_t t = blockIdx.x, tid = threadIdx.x;
   const uint32_t S = a.len[t];
   const uint8_t* c = a.cons + a.off[t];
-  const uint32_t k = a.kmer, TL = a.trim_left, TR = a.trim_right;
+  const uint32_t trims = a.trims[t];  // (indexed by the block: a scalar load)
+  const uint32_t k = a.kmer, TL = trims & 0xffffu, TR = trims >> 16;
   // the domain of scanBothStrands (seed.hpp:614-619); outside it the host runs its two scans
   if (k != a.g.k || k < 1 || k > 32 || (uint64_t)S + k >= 65536u || TL + 1 < k || TR + 1 < k || S < TL || S < TR) {
     if (tid == 0) write_status(a, t, TRACYHIP_SEED_DEFERRED);
@@ -407,6 +409,8 @@ int tracyhip_seed_traces(tracyhip_ctx* ctx, const tracyhip_genome* genome, const
   if (!genome || !cons || !prm || !out) return set_error(TRACYHIP_ERR_ARG, "null genome / consensus / params / result");
   if (cons->kind != TRACYHIP_SEQ_CHAR) return set_error(TRACYHIP_ERR_ARG, "consensus must be a CHAR set");
   if (mem != TRACYHIP_MEM_HOST && mem != TRACYHIP_MEM_DEVICE) return set_error(TRACYHIP_ERR_ARG, "bad mem");
+  if ((prm->trim_left_each == nullptr) != (prm->trim_right_each == nullptr))
+    return set_error(TRACYHIP_ERR_ARG, "trim_left_each and trim_right_each must be given together");
   const uint32_t n = cons->count;
   if (n == 0) return TRACYHIP_OK;
   if (!cons->data || !cons->offset || !cons->length) return set_error(TRACYHIP_ERR_ARG, "null consensus arrays");
@@ -439,13 +443,20 @@ int tracyhip_seed_traces(tracyhip_ctx* ctx, const tracyhip_genome* genome, const
     } else {
       lo = 0;
     }
-    // per-trace inputs and results: offsets (u64), lengths (u32), SeedOut
-    const size_t b_off = 0, b_len = b_off + 8ull * m, b_out = (b_len + 4ull * m + 15) & ~15ull, b_end = b_out + sizeof(SeedOut) * m;
-    off.resize((size_t)m + (m + 1) / 2);
+    // per-trace inputs and results: offsets (u64), lengths (u32), trims (two 16-bit values in a u32), SeedOut -- the inputs in one copy
+    const size_t b_off = 0, b_len = b_off + 8ull * m, b_trim = b_len + 4ull * m, b_out = (b_trim + 4ull * m + 15) & ~15ull, b_end = b_out + sizeof(SeedOut) * m;
+    off.resize(2 * (size_t)m);
     for (uint32_t i = 0; i < m; ++i) off[i] = cons->offset[t0 + i] - lo;
     std::memcpy(off.data() + m, cons->length + t0, 4ull * m);
+    {
+      uint32_t* tw = reinterpret_cast<uint32_t*>(off.data() + m) + m;
+      for (uint32_t i = 0; i < m; ++i) {  // each value truncated to 16 bits as SageConfig holds it
+        const uint32_t l = prm->trim_left_each ? prm->trim_left_each[t0 + i] : prm->trim_left, r = prm->trim_right_each ? prm->trim_right_each[t0 + i] : prm->trim_right;
+        tw[i] = (l & 0xffffu) | ((r & 0xffffu) << 16);
+      }
+    }
     uint8_t* d0; HIP_TRY(ensure_into(ctx->dev[DB_SEED_TRACES], b_end, d0));
-    HIP_TRY(hipMemcpyAsync(d0, off.data(), 12ull * m, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d0, off.data(), 16ull * m, hipMemcpyHostToDevice, ctx->stream));
     uint8_t* d_slices = out->slices + (uint64_t)t0 * out->slice_cap;
     if (mem == TRACYHIP_MEM_HOST) {
       HIP_TRY(ensure_into(ctx->dev[DB_SEED_WINDOWS], (uint64_t)m * row, d_slices));
@@ -462,8 +473,7 @@ int tracyhip_seed_traces(tracyhip_ctx* ctx, const tracyhip_genome* genome, const
     a.n = m;
     a.P = P;
     a.cap = cap;
-    a.trim_left = (uint16_t)prm->trim_left;
-    a.trim_right = (uint16_t)prm->trim_right;
+    a.trims = reinterpret_cast<const uint32_t*>(d0 + b_trim);
     a.kmer = (uint16_t)prm->kmer;
     a.min_support = (uint16_t)prm->min_support;
     a.maxindel = (uint16_t)prm->maxindel;

@@ -443,7 +443,7 @@ __global__ void s_align_final_plan_kernel(SParams p, int early, const SGeom* __r
   if (dead[t]) return;
   const SGeom G = geom[t];
   const uint32_t lead = ends[2 * t] + S.shift, ce = ends[2 * t + 1] + S.shift;
-  S.trim = s_trim_finish(lead, ce >= lead ? ce - lead : 0u, G.rn, p.trim_left, p.trim_right, S.fwd != 0);
+  S.trim = s_trim_finish(lead, ce >= lead ? ce - lead : 0u, G.rn, G.rl, G.rr, S.fwd != 0);
   s_count(lc, SC_PRELIM_BANDED);
   if (early) S.mark |= ST_COUNTED_PRELIM;
   const uint32_t m = G.mf, n = S.trim.len;
@@ -982,7 +982,7 @@ struct PlanHooks {
   std::function<void(uint32_t lo, uint32_t hi, uint32_t tid)> records_slice;  // after the records of traces [lo, hi) are written (trace order)
 };
 int plan_common(tracyhip_ctx* ctx, const tracyhip_params& p, const tracyhip_seqset& sp, const tracyhip_seqset& sr, const uint32_t* ref_index, uint32_t nt,
-                uint32_t trim_l, uint32_t trim_r, StreamHost& h, SGeom* geom, const PlanHooks* hooks = nullptr) {
+                const TrimSrc& trims, StreamHost& h, SGeom* geom, const PlanHooks* hooks = nullptr) {
   h = StreamHost{std::move(h.mf), std::move(h.mt), std::move(h.tl), std::move(h.rn), std::move(h.ridx)};  // (the vectors keep their pages between calls)
   h.nt = nt;
   h.mf.resize(nt); h.mt.resize(nt); h.tl.resize(nt); h.rn.resize(nt); h.ridx.resize(nt);
@@ -1006,8 +1006,8 @@ int plan_common(tracyhip_ctx* ctx, const tracyhip_params& p, const tracyhip_seqs
         if (h.ridx[t] >= sr.count) { x.bad = std::min(x.bad, t); h.ridx[t] = 0; if (sr.count == 0) continue; }
         h.mf[t] = sp.length[t];
         h.rn[t] = sr.length[h.ridx[t]];
-        uint32_t l = trim_l, r = trim_r;
-        if ((uint64_t)l + r >= h.mf[t]) { l = 0; r = 0; }  // createProfile, profile.h:24-27
+        uint32_t l = trims.left(t), r = trims.right(t);
+        if ((uint64_t)l + r >= h.mf[t]) { l = 0; r = 0; }  // createProfile, profile.h:24-27 (per trace: its own pair)
         h.tl[t] = l;
         h.mt[t] = h.mf[t] - (l + r);
         x.max_mn = std::max<uint64_t>(x.max_mn, (uint64_t)h.mf[t] + h.rn[t]);
@@ -1064,6 +1064,7 @@ int plan_common(tracyhip_ctx* ctx, const tracyhip_params& p, const tracyhip_seqs
     G.prof_off = sp.offset[t];
     G.ref_off = sr.offset[h.ridx[t]];
     G.mf = h.mf[t]; G.mt = h.mt[t]; G.tl = h.tl[t]; G.rn = h.rn[t];
+    G.rl = trims.left(t); G.rr = trims.right(t);
     G.full_a = 2 * cls->lo + (i - cls->lo);
     G.full_b = 2 * cls->lo + (cls->hi - cls->lo) + (i - cls->lo);
     const bool front_ok = s_front_ok(&p, G.mt, G.rn);
@@ -1223,7 +1224,7 @@ struct StreamCall {
   const tracyhip_seqset &sp, &sr;
   hipStream_t st;
   tracyhip_params p;
-  const uint32_t TL, TR;
+  const TrimSrc trims;  // what the job requests per trace (plan_common writes them into the records: SGeom::rl / rr)
   const bool exact, host;
   StreamHost& h;
   SGeom* geom = nullptr;
@@ -1236,11 +1237,11 @@ struct StreamCall {
   ReadBack rb;
   std::vector<uint32_t> dl;  // the traces the device could not give their tier
   std::vector<uint64_t> sub_poff;  // ... as a sub-job: profile offsets, lengths, reference indices
-  std::vector<uint32_t> sub_plen, sub_ridx;
+  std::vector<uint32_t> sub_plen, sub_ridx, sub_tl, sub_tr;  // (sub_tl / sub_tr: each dead trace's own requested pair)
 
   template <class Job>
-  StreamCall(tracyhip_ctx* c, const Job* j, const tracyhip_params* q, int m, uint32_t trim_l, uint32_t trim_r, StreamHost& h_)
-      : ctx(c), prm(q), mem(m), kn(c->knobs), nt(j->ntraces), sp(j->profiles), sr(j->refs), st(c->stream), p(*q), TL(trim_l), TR(trim_r),
+  StreamCall(tracyhip_ctx* c, const Job* j, const tracyhip_params* q, int m, StreamHost& h_)
+      : ctx(c), prm(q), mem(m), kn(c->knobs), nt(j->ntraces), sp(j->profiles), sr(j->refs), st(c->stream), p(*q), trims(trims_of(j)),
         exact(j->strand_by_certificate == 0), host(m == TRACYHIP_MEM_HOST), h(h_), g256((j->ntraces + 255) / 256), b256(256) {
     p.hfree = 1;  // AlignConfig<true,false> semiglobal (sage.h:165, indigo.h:164)
     p.vfree = 0;
@@ -1279,7 +1280,7 @@ struct StreamCall {
   // what the planning kernels know of the call, and the buffers every stage reads
   void fill_params() {
     spm.match = p.match; spm.mismatch = p.mismatch; spm.go = p.go; spm.ge = p.ge; spm.nt = nt; spm.exact = exact ? 1u : 0u; spm.ncap = ncap - 8u;
-    spm.trim_left = TL; spm.trim_right = TR; spm.use_votes = 1u;
+    spm.use_votes = 1u;
     spm.split_prefix = kn.sweeps_alone ? 1u : 0u;
     d_qp = static_cast<const int16_t*>(ctx->dev[DB_B16TAB_PROFILE].p);
     d_lastrow = static_cast<int32_t*>(ctx->dev[DB_LASTROW].p);
@@ -1323,12 +1324,17 @@ struct StreamCall {
   template <class Job>
   void sub_job(Job& j, const void* d_prof, const void* d_ref) {
     const uint32_t nd = (uint32_t)dl.size();
-    sub_poff.resize(nd); sub_plen.resize(nd); sub_ridx.resize(nd);
-    for (uint32_t i = 0; i < nd; ++i) { const uint32_t t = dl[i]; sub_poff[i] = sp.offset[t]; sub_plen[i] = sp.length[t]; sub_ridx[i] = h.ridx[t]; }
+    sub_poff.resize(nd); sub_plen.resize(nd); sub_ridx.resize(nd); sub_tl.resize(nd); sub_tr.resize(nd);
+    for (uint32_t i = 0; i < nd; ++i) {
+      const uint32_t t = dl[i];
+      sub_poff[i] = sp.offset[t]; sub_plen[i] = sp.length[t]; sub_ridx[i] = h.ridx[t];
+      sub_tl[i] = trims.left(t); sub_tr[i] = trims.right(t);
+    }
     j.ntraces = nd;
     j.profiles.data = d_prof; j.profiles.offset = sub_poff.data(); j.profiles.length = sub_plen.data(); j.profiles.count = nd;
     j.refs.data = d_ref;
     j.ref_index = sub_ridx.data();
+    j.trim_left_each = sub_tl.data(); j.trim_right_each = sub_tr.data();
   }
 
   // run() is the host-planned pipeline on the sub-job: the call's statistics stay the stream-ordered call's, only its synchronisations count
@@ -1381,7 +1387,7 @@ struct AlignStream : StreamCall {
   uint32_t* hlen = nullptr;  // the slice lengths (host-memory results: they size the copy of the ops)
 
   AlignStream(tracyhip_ctx* c, const tracyhip_align_job* j, const tracyhip_params* q, int m, const tracyhip_align_result* o_, StreamHost& h_)
-      : StreamCall(c, j, q, m, j->trim_left, j->trim_right, h_), job(j), out(o_) {}
+      : StreamCall(c, j, q, m, h_), job(j), out(o_) {}
 
   // geometry and the ops offsets are laid out in the pinned block they travel from: one copy, no staging
   int pin_records() {
@@ -1389,7 +1395,7 @@ struct AlignStream : StreamCall {
     geom = static_cast<SGeom*>(ctx->pin[PB_DESC].p);
     return TRACYHIP_OK;
   }
-  int plan_geometry() { return plan_common(ctx, p, sp, sr, job->ref_index, nt, TL, TR, h, geom); }
+  int plan_geometry() { return plan_common(ctx, p, sp, sr, job->ref_index, nt, trims, h, geom); }
 
   // what the host knows before anything runs, beside the geometry: where the ops go, the workspace
   int plan() {
@@ -1563,8 +1569,8 @@ __global__ void s_expand_d_kernel(const SGeom* __restrict__ geom, const SGeomD* 
   ops2_off[t] = D.opsk_off[2];
   bp[t] = BpDesc{G.prof_off + G.tl, G.mf, G.mt};
   rows[t] = RowsDesc{G.ops_off, 0u, 0u};
-  dd[t] = DecompDesc{G.ops_off, D.bc_off, D.dcp_off, 0u, G.mf, G.rn, 0u};
-  bc[t] = BcDesc{D.sig_off, D.bc_off, D.nsamples, G.mf};
+  dd[t] = DecompDesc{G.ops_off, D.bc_off, D.dcp_off, 0u, G.mf, G.rn, 0u, G.rl, G.rr};
+  bc[t] = BcDesc{D.sig_off, D.bc_off, D.nsamples, G.mf, G.rl, G.rr};
   for (uint32_t k = 0; k < 2; ++k) atd[k * nt + t] = B16TableDesc{k * bext + D.bc_off + D.soff, D.atab_off[k], 0u, D.sl, D.atab_stride, 0u};
 }
 
@@ -1723,7 +1729,7 @@ __global__ void s_allele_plan2_kernel(SParams p, const SGeom* __restrict__ geom,
   SAllele A = al[q];
   const STrace S = tr[t];
   const uint32_t lead = ends[2 * q] + A.shift, cend = ends[2 * q + 1] + A.shift;
-  A.trim = s_trim_finish(lead, cend >= lead ? cend - lead : 0u, G.rn, p.trim_left, p.trim_right, S.fwd != 0);
+  A.trim = s_trim_finish(lead, cend >= lead ? cend - lead : 0u, G.rn, G.rl, G.rr, S.fwd != 0);
   al[q] = A;
   const uint32_t m = D.sl, n = A.trim.len;
   const int64_t ce = (int64_t)cend - (int64_t)A.trim.ri;  // last column of the alignment, in the slice
@@ -1927,7 +1933,7 @@ struct DecStream : StreamCall {
   bool encoded_early = false;
 
   DecStream(tracyhip_ctx* c, const tracyhip_decompose_job* j, const tracyhip_params* q, int m, const tracyhip_decompose_result* o_, StreamHost& h_)
-      : StreamCall(c, j, q, m, (uint32_t)j->dprm.trim_left, (uint32_t)j->dprm.trim_right, h_), job(j), out(o_), bc(j->bc), dp(j->dprm), pglobal(*q),
+      : StreamCall(c, j, q, m, h_), job(j), out(o_), bc(j->bc), dp(j->dprm), pglobal(*q),
         g256x2((2 * j->ntraces + 255) / 256) {
     pglobal.hfree = 0;  // AlignConfig<false,false> (indigo.h:381)
     pglobal.vfree = 0;
@@ -1975,8 +1981,9 @@ struct DecStream : StreamCall {
     };
     Part part[kHostThreads];
     auto trimmed = [&](uint32_t t, uint32_t& soff, uint32_t& sl) {  // trimmedSeq, abif.h:68-75
-      if ((uint64_t)(uint32_t)(TL + TR + 1) >= (uint64_t)h.mf[t]) { soff = 0; sl = h.mf[t]; }
-      else { soff = TL; sl = h.mf[t] - TL - TR; }
+      const uint32_t l = trims.left(t), r = trims.right(t);
+      if ((uint64_t)(uint32_t)(l + r + 1) >= (uint64_t)h.mf[t]) { soff = 0; sl = h.mf[t]; }
+      else { soff = l; sl = h.mf[t] - l - r; }
     };
     auto front_ok = [&](uint32_t t, uint32_t sl) { return s_front_ok(&p, sl, h.rn[t]); };
     uint64_t base_atab[kHostThreads], base_alr[kHostThreads], base_tot1[kHostThreads];
@@ -2047,7 +2054,7 @@ struct DecStream : StreamCall {
         tot1 += (uint64_t)h.mt[t] + h.rn[t];
       }
     };
-    TRY(plan_common(ctx, p, sp, sr, job->ref_index, nt, TL, TR, h, geom, &hooks));
+    TRY(plan_common(ctx, p, sp, sr, job->ref_index, nt, trims, h, geom, &hooks));
     if (max_arest == 0 || !front_tiers_fit(max_arest)) return kStreamNo;
     TRY(decompose_limits(dp.maxindel, maxbc));
     z.ep = seqset_extent(sp); z.er = seqset_extent(sr);
@@ -2232,7 +2239,7 @@ struct DecStream : StreamCall {
       HIP_TRY(hipStreamWaitEvent(ctx->b16_fork.side[3], ctx->b16_fork.ready[0], 0));
       ctx->stream = ctx->b16_fork.side[3];
     }
-    const int rc = launch_allelic_fraction(ctx, A.bcd, nt, maxbc, d_peaks, d_pri, d_sd, TL, TR, o.fractions, 18ull * std::accumulate(h.mf.begin(), h.mf.end(), 0ull), z.bext);
+    const int rc = launch_allelic_fraction(ctx, A.bcd, nt, maxbc, d_peaks, d_pri, d_sd, o.fractions, 18ull * std::accumulate(h.mf.begin(), h.mf.end(), 0ull), z.bext);
     ctx->stream = st;
     if (fork) {
       HIP_TRY(hipEventRecord(ctx->b16_fork.joined[3], ctx->b16_fork.side[3]));

@@ -67,6 +67,8 @@ struct SGeom {          // one trace: what the host knows before anything runs
   uint32_t tab_stride;
   uint32_t full_a, full_b;  // its two slots in the list of full sweeps (sorted by strip height, then size)
   uint32_t flags;       // SG_FRONT_OK
+  uint32_t rl, rr;      // the trims the job REQUESTS for this trace (its per-trace arrays, else the scalar pair): what trimReferenceSlice
+                        // (R9), trimmedSeq and the decompose stages take -- tl / mt above are createProfile's clamped view of them
 };
 struct SGeomD {         // `tracy decompose`: the rest
   uint64_t bc_off;      // basecalls (primary / secondary / secDecompose / bcPos)
@@ -115,7 +117,6 @@ struct SParams {        // scoring + switches every planning kernel sees
   uint32_t nt;
   uint32_t exact;       // both orientation scores exact (no strand by certificate)
   uint32_t ncap;        // longest sub-window the band launches staged LDS for
-  uint32_t trim_left, trim_right;
   uint32_t use_votes;   // the full sweeps skip row m of the likely loser (DpArgs::votes)
   uint32_t split_prefix;  // the voted strands' prefixes run in a launch of their own beside the full sweeps (timed and credited with the pruned sweep)
 };

@@ -21,6 +21,7 @@
 #include "../../include/tracy_hip.h"
 #include "capi_internal.h"
 #include "launch.h"
+#include "pipe_internal.h"
 #include "variants_wave.h"
 
 using namespace tracyhip;
@@ -58,10 +59,11 @@ struct VarDesc {  // one trace
   uint32_t forward, bc_len;
   uint32_t skip;  // no variants are called (status != 0): var_n 0, flags 0
   uint32_t out;   // its index in the result arrays
+  uint32_t trim_left, trim_right;  // the trace's own pair (variantCallIndex; a scalar call writes its pair into every record)
 };
 struct VarArgs {
   const VarDesc* desc;
-  uint32_t n, trim_left, trim_right, max_variants, max_text;
+  uint32_t n, max_variants, max_text;
   VarEvent* ev;
   tracyhip_variant* var;
   uint8_t* text;
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(64) void variants_kernel(VarArgs a) {
       t.row0[k] = d.a[k].row0; t.row1[k] = d.a[k].row1; t.len[k] = *d.a[k].len; t.pos0[k] = d.a[k].pos;
     }
     t.forward = d.forward; t.bc_len = d.bc_len;
-    variants_wave(w, t, a.trim_left, a.trim_right, a.max_variants, a.max_text, ev, a.var + (size_t)d.out * a.max_variants,
+    variants_wave(w, t, d.trim_left, d.trim_right, a.max_variants, a.max_text, ev, a.var + (size_t)d.out * a.max_variants,
                   a.text + (size_t)d.out * a.max_text, a.var_n + d.out, a.var_flags + d.out);
   }
 }
@@ -187,12 +189,11 @@ int var_out_begin(tracyhip_ctx* ctx, uint32_t nt, const tracyhip_variants_result
   o.flags = o.n + nt;
   return TRACYHIP_OK;
 }
-int launch_variants(tracyhip_ctx* ctx, const VarDesc* d_desc, uint32_t n, uint32_t trim_left, uint32_t trim_right, const tracyhip_variants_result& r,
-                    const VarOut& o) {
+int launch_variants(tracyhip_ctx* ctx, const VarDesc* d_desc, uint32_t n, const tracyhip_variants_result& r, const VarOut& o) {
   if (n == 0) return TRACYHIP_OK;
   const uint32_t grid = std::min(n, kVarWaves);
   VarArgs a{};
-  a.desc = d_desc; a.n = n; a.trim_left = trim_left; a.trim_right = trim_right; a.max_variants = r.max_variants; a.max_text = r.max_text;
+  a.desc = d_desc; a.n = n; a.max_variants = r.max_variants; a.max_text = r.max_text;
   HIP_TRY(ensure_into(ctx->dev[VB_EVENTS], (size_t)kVarWaves * 2u * r.max_variants, a.ev));
   a.var = o.var; a.text = o.text; a.var_n = o.n; a.var_flags = o.flags;
   int trc;
@@ -263,7 +264,13 @@ int variants_validate(const tracyhip_decompose_job* job, const tracyhip_decompos
   if (job->ntraces == 0) return TRACYHIP_OK;
   if (!out->var || !out->text || !out->var_n || !out->var_flags) return set_error(TRACYHIP_ERR_ARG, "null result arrays (var / text / var_n / var_flags)");
   if (!slice_pos) return set_error(TRACYHIP_ERR_ARG, "null slice_pos");
-  if (job->dprm.trim_left < 0 || job->dprm.trim_right < 0) return set_error(TRACYHIP_ERR_ARG, "negative trim");
+  if ((job->trim_left_each == nullptr) != (job->trim_right_each == nullptr))
+    return set_error(TRACYHIP_ERR_ARG, "job: trim_left_each and trim_right_each must be given together");
+  if (job->trim_left_each) {
+    for (uint32_t t = 0; t < job->ntraces; ++t)
+      if (job->trim_left_each[t] > 0x7fffffffu || job->trim_right_each[t] > 0x7fffffffu)
+        return set_error(TRACYHIP_ERR_ARG, "job: trim of trace %u above INT32_MAX", t);
+  } else if (job->dprm.trim_left < 0 || job->dprm.trim_right < 0) return set_error(TRACYHIP_ERR_ARG, "negative trim");
   if (!job->bc.primary || !job->bc.bc_offset || !job->bc.bc_len) return set_error(TRACYHIP_ERR_ARG, "job: null primary / bc_offset / bc_len");
   if (job->refs.kind != TRACYHIP_SEQ_CHAR || !job->refs.data || !job->refs.offset || !job->refs.length)
     return set_error(TRACYHIP_ERR_ARG, "job: refs must be a CHAR set with data / offset / length");
@@ -327,13 +334,14 @@ int variants_run(tracyhip_ctx* ctx, const tracyhip_decompose_job* job, const tra
   }
 
   // ---- per trace: the trimmed allele (trimmedSeq), its reference, whether it is called and on which strand ----
-  const uint32_t tl = (uint32_t)job->dprm.trim_left, tr = (uint32_t)job->dprm.trim_right;
+  const TrimSrc trims = trims_of(job);
   struct Tr { uint64_t a_off, r_off; uint32_t m, r_len; bool usable, rev; };
   std::vector<Tr> T(nt);
   uint32_t usable = 0, nrev = 0;
   uint64_t ext_bc = 0, ext_ops[2] = {0, 0}, max_mn = 0;
   for (uint32_t t = 0; t < nt; ++t) {
     const uint32_t L = job->bc.bc_len[t], ri = job->ref_index ? job->ref_index[t] : t;
+    const uint32_t tl = trims.left(t), tr = trims.right(t);
     const bool trim = !((uint64_t)tl + tr + 1 >= L);
     Tr x{};
     x.a_off = job->bc.bc_offset[t] + (trim ? tl : 0u);
@@ -465,6 +473,7 @@ int variants_run(tracyhip_ctx* ctx, const tracyhip_decompose_job* job, const tra
       const Tr& x = T[t];
       VarDesc d{};
       d.forward = h_fwd[t] ? 1u : 0u; d.bc_len = job->bc.bc_len[t]; d.skip = x.usable ? 0u : 1u; d.out = t;
+      d.trim_left = trims.left(t); d.trim_right = trims.right(t);
       if (x.usable && !x.rev) {
         for (int k = 0; k < 2; ++k) {
           PairDesc p{};
@@ -546,7 +555,7 @@ int variants_run(tracyhip_ctx* ctx, const tracyhip_decompose_job* job, const tra
       HIP_TRY(launch_alignment_rows(ra, st));
     }
     if ((trc = timing_end(ctx))) return trc;
-    if ((rc = launch_variants(ctx, d_desc, n, tl, tr, *out, o))) return rc;
+    if ((rc = launch_variants(ctx, d_desc, n, *out, o))) return rc;
     // the chunk's one wait, behind its scan: the next traceback batch reuses the context's pinned descriptors.  The last chunk's is the
     // first wait of var_out_end.
     if (verdict_due && &c != &chunks.back()) {
@@ -604,7 +613,7 @@ int tracyhip_call_variants(tracyhip_ctx* ctx, uint32_t ntraces, const uint8_t* r
       const size_t i = 2 * (size_t)t + k;
       d.a[k] = VarAln{static_cast<const uint8_t*>(d_r0) + rows_offset[i], static_cast<const uint8_t*>(d_r1) + rows_offset[i], d_len + i, pos[i], 0u};
     }
-    d.forward = forward[t] ? 1u : 0u; d.bc_len = bc_len[t]; d.skip = 0; d.out = t;
+    d.forward = forward[t] ? 1u : 0u; d.bc_len = bc_len[t]; d.skip = 0; d.out = t; d.trim_left = trim_left; d.trim_right = trim_right;
     hd[t] = d;
   }
   VarDesc* d_desc; HIP_TRY(ensure_into(ctx->dev[VB_DESC], (size_t)ntraces, d_desc));
@@ -612,7 +621,7 @@ int tracyhip_call_variants(tracyhip_ctx* ctx, uint32_t ntraces, const uint8_t* r
   const tracyhip_variants_result r{var, text, var_n, var_flags, max_variants, max_text};
   VarOut o;
   if ((rc = var_out_begin(ctx, ntraces, r, mem, o))) return rc;
-  if ((rc = launch_variants(ctx, d_desc, ntraces, trim_left, trim_right, r, o))) return rc;
+  if ((rc = launch_variants(ctx, d_desc, ntraces, r, o))) return rc;
   uint32_t truncated = 0;
   rc = var_out_end(ctx, ntraces, r, mem, o, &truncated);  // (waits for the stream: hd has been read)
   timing_collect(ctx);

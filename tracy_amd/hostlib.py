@@ -504,7 +504,8 @@ class DeviceGenome:
         ss.kind, ss.data, ss.count = capi.SEQ_CHAR, data, n
         ss.offset = packed["offs"].ctypes.data_as(C.POINTER(C.c_uint64))
         ss.length = packed["lens"].ctypes.data_as(C.POINTER(C.c_uint32))
-        prm = capi.SeedParams(trim_left, trim_right, self.kmer, min_support, maxindel)
+        prm = capi.SeedParams(0, 0, self.kmer, min_support, maxindel)
+        trim_arrays = capi.trims_each(prm, trim_left, trim_right, n)  # ints, or per-trace array-likes (kept alive over the call)
         r = capi.SeedResult()
         for k in ("status", "forward", "kmersupport", "pos", "contig", "slice_len"):
             setattr(r, k, out[k].ctypes.data)
@@ -515,23 +516,26 @@ class DeviceGenome:
         if len(dfr) and not self.host_table:
             raise RuntimeError("tracy_amd: %d trace(s) deferred to host seeding, but the genome was built on the device without "
                                "copy_back: there is no host table to seed them with" % len(dfr))
-        if len(dfr):  # the host's answer for exactly those traces
-            sub = Genome.pack_consensus([blob[int(packed["offs"][i]):int(packed["offs"][i]) + int(packed["lens"][i])] for i in dfr])
-            h = self.genome.seed_packed(sub, trim_left, trim_right, min_support, maxindel, nthreads)
+        # the host's answer for exactly those traces; with per-trace trims the host, which takes one pair per call, seeds them pair by pair
+        pair_of = (lambda i: (int(trim_arrays[0][i]) & 0xFFFF, int(trim_arrays[1][i]) & 0xFFFF)) if trim_arrays else (lambda i: (trim_left, trim_right))
+        for (tl, tr) in sorted({pair_of(i) for i in dfr}):
+            sel = np.array([i for i in dfr if pair_of(i) == (tl, tr)], dtype=dfr.dtype)
+            sub = Genome.pack_consensus([blob[int(packed["offs"][i]):int(packed["offs"][i]) + int(packed["lens"][i])] for i in sel])
+            h = self.genome.seed_packed(sub, tl, tr, min_support, maxindel, nthreads)
             hs = h["slices_2d"]
             if hs.shape[1] < cap:
                 hs = np.pad(hs, ((0, 0), (0, cap - hs.shape[1])))
             for k in ("status", "slice_len"):
-                out[k][dfr] = h[k][:len(dfr)]
-            ok = h["status"][:len(dfr)] == 1
+                out[k][sel] = h[k][:len(sel)]
+            ok = h["status"][:len(sel)] == 1
             for k in ("forward", "kmersupport", "pos", "contig"):
-                out[k][dfr[ok]] = h[k][:len(dfr)][ok]
+                out[k][sel[ok]] = h[k][:len(sel)][ok]
             if mem == capi.MEM_DEVICE:
                 import torch
-                idx = torch.from_numpy(dfr.astype(np.int64)).to(out["slices_2d"].device)
-                out["slices_2d"][idx] = torch.from_numpy(np.ascontiguousarray(hs[:len(dfr), :cap])).to(out["slices_2d"].device)
+                idx = torch.from_numpy(sel.astype(np.int64)).to(out["slices_2d"].device)
+                out["slices_2d"][idx] = torch.from_numpy(np.ascontiguousarray(hs[:len(sel), :cap])).to(out["slices_2d"].device)
             else:
-                out["slices_2d"][dfr] = hs[:len(dfr), :cap]
+                out["slices_2d"][sel] = hs[:len(sel), :cap]
         return out
 
     def seed(self, consensus, trim_left=50, trim_right=50, min_support=3, maxindel=1000, nthreads=0, raw=False):
