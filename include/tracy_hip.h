@@ -128,7 +128,9 @@ int tracyhip_synchronize(tracyhip_ctx* ctx);
      band_w  (half width of the certified band of the final alignments; -1 = from the preliminary alignment, 0 = whole matrices)
      ckpt_b  (steps between wavefront checkpoints, 32 .. 1024)      verbose  (one line per pipeline stage on stderr)
      seed_vote_cap  (tracyhip_seed_traces: votes one trace may collect per strand and pass on the device, 1 .. 2048, default 2048;
-                    a trace with more is DEFERRED to host seeding -- the caller's results stay the same)
+                    a trace with more is DEFERRED to host seeding -- the caller's results stay the same -- or, with seed_spill, spills)
+     seed_spill     ("0" / "1", default "0": a trace over seed_vote_cap is answered on the device by the spill launch of tracyhip_seed_traces,
+                    its votes counted in device memory, instead of DEFERRED; any other value is refused)
      quad_tier_min  (stream-ordered pipelines: traces / alleles from which a pruned sweep gets its narrow first tier; default 32768)
      front_list_min (... from which its later tiers, and the allele prefixes of `tracy decompose`, run over device-side lists of the units
                     that are left instead of skipping the others in place; default 1024)
@@ -179,6 +181,9 @@ typedef struct {
   uint32_t band_list_pairs[2][4]; /* stream-ordered pipelines: pairs the scan of a band stage filed under strip height 12 / 8 / 4 / the quad form, summed
                                      over the call's band stages; [0]: traceback stages, [1]: origin sweeps.  0 in a call planned by the host */
   uint32_t band_large_launches;  /* ... band stages of more than b16_multi_max units: strip height 12 in a launch of its own beside the other three lists */
+  uint32_t seed_spilled;         /* tracyhip_seed_traces with seed_spill (which sets these three and no other counter): traces answered by the spill kernel */
+  uint32_t seed_spill_launches;  /* ... spill launches the call made (one more synchronisation each) */
+  uint32_t seed_spill_deferred;  /* ... spilled traces handed to the host because their tables did not fit the workspace limit */
 } tracyhip_call_stats;
 int tracyhip_last_call_stats(tracyhip_ctx* ctx, tracyhip_call_stats* out);
 const char* tracyhip_last_error(void);
@@ -570,7 +575,13 @@ typedef struct {
  * (kind CHAR; offsets / lengths HOST arrays, bytes where `mem` says).  Results are identical to tracyhost_seed_batch's for every trace
  * the device answers.  DEFERRED: letters other than A C G T N among the windows, |consensus| + k >= 65536, a trim shorter than k - 1,
  * a consensus shorter than a trim, a kmer that is not the index's, or more votes on one strand in one pass than the option
- * seed_vote_cap allows (default and maximum 2048: the vote lists live in LDS). */
+ * seed_vote_cap allows (default and maximum 2048: the vote lists live in LDS).
+ * With the option seed_spill = 1 that last reason is gone: a trace over seed_vote_cap -- an amplicon in a gene family or an interspersed
+ * repeat, a trace of more than ~2 100 windows -- is answered on the device by a second launch that counts its votes in hash tables in
+ * device memory (16 bytes per slot, at least two slots per vote of the larger pass, per strand), with the same results.  The tables
+ * of a launch are sized within the workspace limit (tracyhip_set_workspace_limit), spilled traces running in several launches where it
+ * is tight; only a trace whose own tables exceed the limit is still DEFERRED.  tracyhip_last_call_stats: seed_spilled,
+ * seed_spill_launches, seed_spill_deferred.  A batch without such a trace costs what it costs with the option off. */
 int tracyhip_seed_traces(tracyhip_ctx* ctx, const tracyhip_genome* genome, const tracyhip_seqset* consensus, const tracyhip_seed_params* prm,
                          int mem, const tracyhip_seed_result* out);
 

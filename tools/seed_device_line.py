@@ -6,6 +6,14 @@ whether all were bit-identical, and seed + extend traces/s with device seeding (
 the reverse strand, 1 % substitutions.  Step times end in a device synchronisation; warm-up steps are not timed.
 
     python tools/seed_device_line.py [--traces 1000000] [--genome-mb 50] [--steps 3] [--warmup 1] [--extend-traces 125000]
+
+The repeat workload (--repeat-copies N --repeat-unit L): the same genome with one dispersed exact family -- N copies of a random unit of
+L bases (L >= 1000) written over it at random places -- and every trace drawn from inside the unit, so no trace has a unique k-mer and
+each casts ~N votes per window in the second pass.  With --spill the context runs with the option seed_spill and such traces are
+answered on the device; without it they are deferred and seeded on the host inside the timed call.  Every line has n_deferred, n_spilled and
+the spill launches of the last call; the repeat workload leaves the extend part out.
+
+    python tools/seed_device_line.py --traces 100000 --repeat-copies 30 --repeat-unit 2000 --spill
 """
 import argparse
 import ctypes as C
@@ -56,6 +64,30 @@ def build_data(total, genome_mb, mf=1000, block=62500):
     return seq.tobytes(), packed, codes
 
 
+def build_repeat_data(total, genome_mb, copies, unit, mf=1000):
+    """a random genome with `copies` exact copies of one random unit of `unit` bases at random places that do not touch each other, and
+    the packed consensus of traces drawn from inside the unit: every other one from the reverse strand, 1 % substitutions"""
+    rng = np.random.default_rng(24)
+    n = int(genome_mb * 1e6)
+    if unit < mf or copies < 1 or copies * 2 * unit > n:
+        raise SystemExit("--repeat-unit must be at least %d and the copies must fit the genome" % mf)
+    lut = np.frombuffer(b"ACGT", dtype=np.uint8)
+    codes = rng.integers(0, 4, size=n, dtype=np.uint8)
+    fam = rng.integers(0, 4, size=unit, dtype=np.uint8)
+    cells = rng.choice(n // (2 * unit), size=copies, replace=False)  # one copy per cell of 2 x unit bases: apart from each other
+    for cell in cells:
+        at = int(cell) * 2 * unit + int(rng.integers(0, unit))
+        codes[at:at + unit] = fam
+    starts = rng.integers(0, unit - mf + 1, size=total)
+    c = fam[starts[:, None].astype(np.int64) + np.arange(mf, dtype=np.int64)[None, :]]
+    odd = (np.arange(total) % 2).astype(bool)
+    c[odd] = (3 - c[odd])[:, ::-1]
+    flip = np.random.default_rng(25).random(c.shape) < 0.01
+    c = np.where(flip, (c + 1) % 4, c).astype(np.uint8)
+    packed = dict(n=total, blob=lut[c].tobytes() + b"\0", offs=np.arange(total, dtype=np.uint64) * np.uint64(mf), lens=np.full(total, mf, np.uint32))
+    return lut[codes].tobytes(), packed, None
+
+
 def sub_pack(packed, lo, hi, mf=1000):
     return dict(n=hi - lo, blob=packed["blob"][lo * mf:hi * mf] + b"\0", offs=np.arange(hi - lo, dtype=np.uint64) * np.uint64(mf),
                 lens=np.full(hi - lo, mf, np.uint32))
@@ -69,6 +101,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--extend-traces", type=int, default=125000)
     ap.add_argument("--no-host", action="store_true", help="skip host seeding (and the comparison)")
+    ap.add_argument("--repeat-copies", type=int, default=0, help="the repeat workload: copies of one dispersed exact family (0: the random genome)")
+    ap.add_argument("--repeat-unit", type=int, default=2000, help="... bases of its unit; the traces are drawn from inside it")
+    ap.add_argument("--spill", action="store_true", help="run with the option seed_spill: traces over the LDS vote lists are answered on the device")
     a = ap.parse_args()
     import tracy_amd
     from tracy_amd import capi, hostlib
@@ -76,10 +111,15 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     t0 = time.perf_counter()
-    text, packed, codes = build_data(a.traces, a.genome_mb)
+    if a.repeat_copies:
+        text, packed, codes = build_repeat_data(a.traces, a.genome_mb, a.repeat_copies, a.repeat_unit)
+    else:
+        text, packed, codes = build_data(a.traces, a.genome_mb)
     data_s = time.perf_counter() - t0
     tmp = tempfile.mkdtemp(prefix="tracy_seed_line_")
-    out = dict(metric="seed_device_line", traces=a.traces, genome_mb=a.genome_mb, trace_len=1000, host_threads=threads)
+    out = dict(metric="seed_device_line", traces=a.traces, genome_mb=a.genome_mb, trace_len=1000, host_threads=threads, seed_spill=int(a.spill))
+    if a.repeat_copies:
+        out.update(repeat_copies=a.repeat_copies, repeat_unit=a.repeat_unit)
     try:
         gpath = os.path.join(tmp, "genome.fa")
         with open(gpath, "wb") as f:
@@ -88,6 +128,7 @@ def main():
         g = hostlib.Genome(gpath, 15, threads)
         out["index_build_s"] = round(time.perf_counter() - t0, 3)
         ctx = tracy_amd.Context(0)
+        ctx.set_option("seed_spill", 1 if a.spill else 0)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         dg = g.to_device(ctx)
@@ -105,7 +146,9 @@ def main():
                 times.append(time.perf_counter() - t0)
         out["device_seed_s"] = [round(x, 4) for x in times]
         out["device_seed_traces_per_s"] = round(a.traces / float(np.median(times)), 1)
-        out["deferred"] = int(sd["n_deferred"])
+        out["deferred"] = out["n_deferred"] = int(sd["n_deferred"])
+        out["n_spilled"] = int(sd["n_spilled"])
+        out["seed_spill_launches"] = ctx.last_call_stats()["seed_spill_launches"]
         out["anchored"] = int((sd["status"][:a.traces] == 1).sum())
         if not a.no_host:
             t0 = time.perf_counter()
@@ -123,7 +166,7 @@ def main():
             del hs
         del sd
         # seed + extend: device seeding (MEM_DEVICE) -> tracyhip_align_traces(oriented, MEM_DEVICE), block by block
-        E = min(a.extend_traces, a.traces)
+        E = 0 if a.repeat_copies else min(a.extend_traces, a.traces)
         if E > 0:
             blocks = [(lo, min(E, lo + 62500)) for lo in range(0, E, 62500)]
             packs = [sub_pack(packed, lo, hi) for lo, hi in blocks]

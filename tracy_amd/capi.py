@@ -82,7 +82,7 @@ class CallStats(C.Structure):
 class CallStatsVariants(CallStats):
     """CallStats (the counters through denovo_steps, kept as it was: tests pin its tail) with the four counters of
     tracyhip_decompose_variants appended -- ctypes lays a subclass's fields out behind its base's, as the C struct grew.  The struct
-    has grown since: CallStatsBands below is THE mirror of tracyhip_call_stats, and the only one to hand to
+    has grown since: CallStatsSeed below is THE mirror of tracyhip_call_stats, and the only one to hand to
     tracyhip_last_call_stats -- anything shorter is an out-of-bounds write.  Context.last_call_stats uses it."""
     _fields_ = [("var_traces", C.c_uint32), ("var_realigned", C.c_uint32), ("var_truncated", C.c_uint32), ("var_chunks", C.c_uint32)]
 
@@ -94,8 +94,14 @@ class CallStatsSweeps(CallStatsVariants):
 
 class CallStatsBands(CallStatsSweeps):
     """CallStatsSweeps with the band stages' list sizes ([kind][strip height 12 / 8 / 4 / quad form]) and the count of stages that took
-    the large-batch form behind it, as the C struct grew: what Context.last_call_stats hands to the library."""
+    the large-batch form behind it, as the C struct grew."""
     _fields_ = [("band_list_pairs", (C.c_uint32 * 4) * 2), ("band_large_launches", C.c_uint32)]
+
+
+class CallStatsSeed(CallStatsBands):
+    """CallStatsBands with the three counters of tracyhip_seed_traces under the option seed_spill behind it, as the C struct grew: THE
+    mirror of tracyhip_call_stats now, and what Context.last_call_stats hands to the library."""
+    _fields_ = [("seed_spilled", C.c_uint32), ("seed_spill_launches", C.c_uint32), ("seed_spill_deferred", C.c_uint32)]
 
 
 def library_path():
@@ -210,10 +216,11 @@ class Context:
 
     def last_call_stats(self):
         """tiers the traces of the last align_traces / decompose_traces call took (tracyhip_last_call_stats)"""
-        st = CallStatsBands()
+        st = CallStatsSeed()
         _check(lib().tracyhip_last_call_stats(self._h, C.byref(st)))
         out = {}
-        for name, ty in CallStats._fields_ + CallStatsVariants._fields_ + CallStatsSweeps._fields_ + CallStatsBands._fields_:
+        for name, ty in (CallStats._fields_ + CallStatsVariants._fields_ + CallStatsSweeps._fields_ + CallStatsBands._fields_
+                         + CallStatsSeed._fields_):
             v = getattr(st, name)
             if name == "band_list_pairs":
                 out[name] = [list(row) for row in v]

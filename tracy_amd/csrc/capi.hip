@@ -285,6 +285,11 @@ bool knobs_set(CtxKnobs& k, const char* name, const char* value) {
     k.seed_vote_cap = (uint32_t)v;
     return true;
   }
+  if (same_name(name, "seed_spill")) {  // "0" / "1" and nothing else, from the environment as well: the option changes which traces the device answers
+    if ((value[0] != '0' && value[0] != '1') || value[1]) return false;
+    k.seed_spill = value[0] == '1';
+    return true;
+  }
   if (same_name(name, "sweep_diag_period")) {  // 0 = the range rule's own; else a multiple of 4 from 64 on, clamped to the rule's at a launch
     const long v = atol(value);
     if (v != 0 && (v < 64 || v > 32768 || v % 4 != 0)) return false;
@@ -318,6 +323,7 @@ void knobs_from_env(CtxKnobs& k) {
   if (const char* e = getenv("TRACYHIP_FRONT_LIST_MIN")) knobs_set(k, "front_list_min", e);
   if (const char* e = getenv("TRACYHIP_B16_MULTI_MAX")) knobs_set(k, "b16_multi_max", e);
   if (const char* e = getenv("TRACYHIP_SEED_VOTE_CAP")) knobs_set(k, "seed_vote_cap", e);
+  if (const char* e = getenv("TRACYHIP_SEED_SPILL")) knobs_set(k, "seed_spill", e);
   if (const char* e = getenv("TRACYHIP_SWEEP_DIAG_PERIOD")) knobs_set(k, "sweep_diag_period", e);
 }
 std::string knobs_describe(const CtxKnobs& k) {
@@ -329,6 +335,7 @@ std::string knobs_describe(const CtxKnobs& k) {
   s += "front_list_min=" + std::to_string(k.front_list_min) + "\n";
   s += "b16_multi_max=" + std::to_string(k.b16_multi_max) + "\n";
   s += "seed_vote_cap=" + std::to_string(k.seed_vote_cap) + "\n";
+  s += k.seed_spill ? "seed_spill=1\n" : "seed_spill=0\n";
   s += "sweep_diag_period=" + std::to_string(k.sweep_diag_period) + "\n";
   s += "host_threads=" + std::to_string(host_pool_threads()) + "\n";
   return s;

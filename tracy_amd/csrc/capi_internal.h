@@ -103,6 +103,7 @@ enum CtxDev : int {
   DB_SEED_TRACES = DB_PIPE_END,  // tracyhip_seed_traces (seed.hip): per-trace inputs up, results of seed_traces_kernel back
   DB_SEED_CONS,     // consensus staged from the host, read by the seeding kernels
   DB_SEED_WINDOWS,  // reference windows written by the seeding kernels for a host caller, copied back
+  DB_SEED_SPILL,    // option seed_spill: descriptors (uploaded) and counting tables of the traces of one spill launch, cleared and read by seed_spill_kernel
   DB_BCALL_TRACES,   // tracyhip_basecall_traces (basecall.hip): per-trace inputs up, per-trace results back
   DB_BCALL_SCRATCH,  // working words of basecall_kernel
   DB_BCALL_SIGNAL,   // signal staged from the host
@@ -238,7 +239,8 @@ struct CtxKnobs {
   uint32_t sweep_diag_period = 0; // offset form of the sweeps: steps between re-bases, clamped to what sweep_diag_period() allows; 0 = that
   uint32_t b16_multi_max = TRACY_B16_MULTI_MAX; // stream-ordered pipelines: units up to which a band stage is one launch over its four lists (launch_band16_counted)
   uint32_t front_list_min = 1024; // stream-ordered pipelines: units from which the later tiers of a pruned sweep (and the allele prefixes) run over device-side lists
-  uint32_t seed_vote_cap = 2048;  // tracyhip_seed_traces: votes per trace, strand and pass held in LDS (seed.hip); more: the trace is deferred
+  uint32_t seed_vote_cap = 2048;  // tracyhip_seed_traces: votes per trace, strand and pass held in LDS (seed.hip); more: the trace is deferred, or spills
+  bool seed_spill = false;        // tracyhip_seed_traces: a trace over seed_vote_cap is answered by the spill kernel (votes counted in device memory) instead of deferred
   uint32_t quad_tier_min = 32768;  // stream-ordered pipelines: units (traces, or alleles) from which the pruned sweeps get their narrow quad tier          // steps between wavefront checkpoints [32, 1024]
 };
 void knobs_from_env(CtxKnobs& k);
@@ -409,6 +411,9 @@ int check_params(const tracyhip_params* prm, uint64_t max_mn);
 // is free on the device now plus `held`, the bytes it already holds for the purpose.  (A driver call: each site has its own
 // precondition for asking at all.)
 int workspace_limit(tracyhip_ctx* ctx, uint64_t held, uint64_t* limit);
+// ... with the driver's answer kept for as long as the context holds what it held when it asked (stream.hip; from_cache: the answer
+// was a kept one)
+int workspace_budget(tracyhip_ctx* ctx, uint64_t held, uint64_t* out, bool* from_cache = nullptr);
 // a seqset of profiles as the batch calls take one: its kind and arrays; then that the profiles [lo, hi) have columns.  false: the
 // error is set (`name` opens the message)
 bool check_profile_set(const tracyhip_seqset& s, const char* name);

@@ -43,6 +43,89 @@ struct SeedOut {
   uint32_t forward, kmersupport, pos, contig, slice_len;
 };
 
+// Internal status of the first kernel (never returned to a caller: 0 .. 2 are the public values): the trace collected more votes
+// than the LDS lists hold and the context's seed_spill is on.  Its SeedOut then reads as a SeedSpillOut.
+constexpr int32_t kSeedSpill = 3;
+struct SeedSpillOut {
+  int32_t status;        // kSeedSpill
+  uint32_t pass;         // the pass whose lists overflowed: 0 = unique k-mers, 1 = every k-mer below 1000 occurrences
+  uint32_t votes[2][2];  // [pass][strand]: the exact votes of the pass that overflowed and, where that was pass 0, of pass 1 as well
+};
+static_assert(sizeof(SeedSpillOut) == sizeof(SeedOut), "a spilled trace reports in its own result record");
+
+// ---- vote counting beyond LDS: findMaxFreq (fmindex.h:173-198) over a counting hash table ----
+// One table per strand: slots of {value, count}, a power of two >= 2 x the votes inserted (so never full), linear probing.  A slot
+// is claimed by a compare-and-swap on its value and counted by an add, so the final table -- and with the tie rule below the
+// answer -- does not depend on the order of the inserts.  Memory goes through a policy `Mem` (load / claim / add): atomics on the
+// device (seed.hip), plain accesses in SeedMemPlain for one thread on the host.
+struct SeedSlot {
+  int64_t value;
+  uint32_t count, pad;
+};
+// a vote is position - offset with position >= 0 and offset < 65 536: never this value
+constexpr int64_t kSeedSlotEmpty = INT64_MIN;
+constexpr uint64_t kSeedTableMin = 64;
+
+SEED_HD uint64_t seed_table_capacity(uint64_t votes) {
+  uint64_t c = kSeedTableMin;
+  while (c < 2 * votes) c <<= 1;
+  return c;
+}
+// the slot a value's probe starts at (mask = capacity - 1)
+SEED_HD uint64_t seed_slot_of(int64_t v, uint64_t mask) {
+  uint64_t h = (uint64_t)v * 0x9e3779b97f4a7c15ull;
+  h ^= h >> 32;
+  return h & mask;
+}
+struct SeedMemPlain {
+  static SEED_HD int64_t load(const int64_t* p) { return *p; }
+  static SEED_HD uint32_t load(const uint32_t* p) { return *p; }
+  static SEED_HD void store(int64_t* p, int64_t v) { *p = v; }
+  static SEED_HD void store(uint32_t* p, uint32_t v) { *p = v; }
+  static SEED_HD int64_t claim(int64_t* p, int64_t expected, int64_t v) {  // compare-and-swap: what *p held before
+    const int64_t old = *p;
+    if (old == expected) *p = v;
+    return old;
+  }
+  static SEED_HD void add(uint32_t* p, uint32_t n) { *p += n; }
+};
+// slots lo, lo + step, ... of a table set to empty
+template <class Mem>
+SEED_HD void seed_table_clear(SeedSlot* tab, uint64_t capacity, uint64_t lo, uint64_t step) {
+  for (uint64_t i = lo; i < capacity; i += step) {
+    Mem::store(&tab[i].value, kSeedSlotEmpty);
+    Mem::store(&tab[i].count, 0u);
+  }
+}
+// one vote: probe from the value's slot to its own slot or the first empty one, which it claims.  false: no slot within `capacity`
+// probes (a table smaller than its votes: not reached with seed_table_capacity)
+template <class Mem>
+SEED_HD bool seed_table_insert(SeedSlot* tab, uint64_t capacity, int64_t v) {
+  const uint64_t mask = capacity - 1;
+  uint64_t s = seed_slot_of(v, mask);
+  for (uint64_t probes = 0; probes < capacity; ++probes, s = (s + 1) & mask) {
+    int64_t held = Mem::load(&tab[s].value);
+    if (held == kSeedSlotEmpty) held = Mem::claim(&tab[s].value, kSeedSlotEmpty, v);
+    if (held == kSeedSlotEmpty || held == v) {
+      Mem::add(&tab[s].count, 1u);
+      return true;
+    }
+  }
+  return false;
+}
+// best (length, value) of two runs: the longer, on ties the smaller value (findMaxFreq keeps the first of the sorted runs)
+SEED_HD void seed_better(uint32_t& bl, int64_t& bv, uint32_t l, int64_t v) {
+  if (l > bl || (l == bl && l != 0 && v < bv)) { bl = l; bv = v; }
+}
+// findMaxFreq over slots lo, lo + step, ... of a table: folded into (bl, bv), which start at (0, 0)
+template <class Mem>
+SEED_HD void seed_table_best(const SeedSlot* tab, uint64_t capacity, uint64_t lo, uint64_t step, uint32_t& bl, int64_t& bv) {
+  for (uint64_t i = lo; i < capacity; i += step) {
+    const int64_t v = Mem::load(&tab[i].value);
+    if (v != kSeedSlotEmpty) seed_better(bl, bv, Mem::load(&tab[i].count), v);
+  }
+}
+
 // the reverse complement of a k-mer code (two bits per letter, first letter in the highest pair): GenomeIndex::revcomp_code
 SEED_HD uint64_t seed_revcomp(uint64_t x, uint32_t k) {
   x = ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);

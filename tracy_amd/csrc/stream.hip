@@ -633,8 +633,9 @@ bool stream_options_ok(const CtxKnobs& k) {
          !k.no_subwindow && !k.no_prelim_origin && !k.no_cq && k.band_w < 0;
 }
 
+}  // namespace
 // workspace one context may plan with (run_dp's rule): the caller's limit, or its share of what is free plus what it holds
-int workspace_budget(tracyhip_ctx* ctx, uint64_t held, uint64_t* out, bool* from_cache = nullptr) {
+int tracyhip::workspace_budget(tracyhip_ctx* ctx, uint64_t held, uint64_t* out, bool* from_cache) {
   if (from_cache) *from_cache = false;
   if (ctx->ws_limit) { *out = ctx->ws_limit; return TRACYHIP_OK; }
   // (hipMemGetInfo is a driver round trip, paid while the device waits for the call to be planned: the answer is kept for as long as
@@ -650,6 +651,7 @@ int workspace_budget(tracyhip_ctx* ctx, uint64_t held, uint64_t* out, bool* from
   ctx->ws_cache_budget = *out; ctx->ws_cache_held = held; ctx->ws_cache_share = ctx->mem_share;
   return TRACYHIP_OK;
 }
+namespace {
 // plan(&from_cache) sizes and allocates a call's workspace from workspace_budget's answer: when the answer was a kept one and an
 // allocation fails, the kept answer is dropped and the plan is made once more from what the driver says is free now
 template <class Plan>

@@ -299,7 +299,10 @@ class Genome:
         """the index built on the device of `ctx` (tracyhip_genome_build) from a plain or gzip-compressed multi-FASTA -> (Genome, DeviceGenome).
         The Genome holds the text; with copy_back it also holds the device-built table (tracyhip_genome_download + tracyhost_genome_adopt:
         word for word the table Genome(path, kmer) builds), so save(), view() and host seeding work and DeviceGenome seeds DEFERRED traces
-        on the host as usual.  Without copy_back the Genome has no table and DeviceGenome.seed raises on a deferred trace.
+        on the host as usual.  Without copy_back the Genome has no table and DeviceGenome.seed raises on a deferred trace: one with
+        letters other than ACGTN, a trim shorter than k - 1, |consensus| + k >= 65536 -- and one whose vote lists exceed the context's
+        seed_vote_cap (a read inside a gene family or repeat, a read of more than ~2 100 windows) unless the context runs with
+        set_option("seed_spill", 1), which answers those on the device.
         bucket_bits: None = the host build's choice (tracyhost_default_bucket_bits)."""
         from . import capi
         fn = lib().tracyhost_genome_load
@@ -436,8 +439,9 @@ class Genome:
 class DeviceGenome:
     """a Genome's index on one device (tracyhip_genome_upload): getReferenceSlice for batches of traces by tracyhip_seed_traces.  seed() /
     seed_packed() return what Genome.seed() / seed_packed() return, plus n_deferred: the traces outside what the device answers
-    (TRACYHIP_SEED_DEFERRED: letters other than ACGTN, short trims, long traces, vote lists over the context's seed_vote_cap), which are
-    seeded on the host (tracyhost_seed_batch) and merged in."""
+    (TRACYHIP_SEED_DEFERRED: letters other than ACGTN, short trims, long traces, and -- unless the context's option seed_spill is on --
+    vote lists over its seed_vote_cap), which are seeded on the host (tracyhost_seed_batch) and merged in; and n_spilled: the traces over
+    seed_vote_cap that the spill launch answered on the device (seed_spill on; 0 otherwise)."""
 
     def __init__(self, genome, ctx):
         from . import capi
@@ -513,6 +517,7 @@ class DeviceGenome:
         capi.seed_traces(self.ctx, self._h, ss, prm, mem, r)
         dfr = np.nonzero(out["status"][:n] == capi.SEED_DEFERRED)[0]
         out["n_deferred"] = int(len(dfr))
+        out["n_spilled"] = int(self.ctx.last_call_stats()["seed_spilled"])
         if len(dfr) and not self.host_table:
             raise RuntimeError("tracy_amd: %d trace(s) deferred to host seeding, but the genome was built on the device without "
                                "copy_back: there is no host table to seed them with" % len(dfr))
@@ -539,12 +544,12 @@ class DeviceGenome:
         return out
 
     def seed(self, consensus, trim_left=50, trim_right=50, min_support=3, maxindel=1000, nthreads=0, raw=False):
-        """Genome.seed on the device: the same dict (plus n_deferred)"""
+        """Genome.seed on the device: the same dict (plus n_deferred and n_spilled)"""
         packed = Genome.pack_consensus(consensus)
         n = packed["n"]
         o = self.seed_packed(packed, trim_left, trim_right, min_support, maxindel, nthreads)
         out = {k: o[k][:n] for k in ("status", "forward", "kmersupport", "pos", "contig", "slice_len")}
-        out["n_deferred"] = o["n_deferred"]
+        out["n_deferred"], out["n_spilled"] = o["n_deferred"], o["n_spilled"]
         if raw:
             out["slices_2d"] = o["slices_2d"]
         else:
