@@ -105,16 +105,17 @@ __global__ __launch_bounds__(64) void consensus_kernel(ConsArgs a) {
     const uint64_t t0 = __ballot(!g0), t1 = __ballot(!g1);
     const uint32_t my1 = s1 + (uint32_t)__popcll(t0 & below), my2 = s2 + (uint32_t)__popcll(t1 & below);
     const bool al = !g0 && !g1;
-    // letters this column emits: one for an aligned column, else one per non-gap side with computeUnion
-    const uint32_t k0 = al ? 1u : a.use_union ? (uint32_t)!g0 + (uint32_t)!g1 : 0u;
-    const uint64_t o1 = __ballot(k0 >= 1), o2 = __ballot(k0 >= 2);
-    uint32_t out = slot + (uint32_t)__popcll(o1 & below) + (uint32_t)__popcll(o2 & below);
-    for (uint32_t e = 0; e < k0; ++e) {
+    // an aligned column emits one letter; a column with a gap on one side emits the other side's with computeUnion (never two:
+    // a column with both sides present is aligned)
+    const bool emit = al || (a.use_union && (!g0 || !g1));
+    const uint64_t o1 = __ballot(emit);
+    const uint32_t out = slot + (uint32_t)__popcll(o1 & below);
+    if (emit) {
       double cl[6];
       float f[6];
       if (al) {
         for (int k = 0; k < 6; ++k) f[k] = __fadd_rn(p1[k * m + my1], p2[k * n + my2]);  // float + float (consensus.h:177)
-      } else if (e == 0 && !g0) {
+      } else if (!g0) {
         for (int k = 0; k < 6; ++k) f[k] = p1[k * m + my1];
       } else {
         for (int k = 0; k < 6; ++k) f[k] = p2[k * n + my2];
@@ -137,11 +138,10 @@ __global__ __launch_bounds__(64) void consensus_kernel(ConsArgs a) {
           a.fix[w] = fx;
         }
       }
-      ++out;
     }
     s1 += (uint32_t)__popcll(t0);
     s2 += (uint32_t)__popcll(t1);
-    slot += (uint32_t)__popcll(o1) + (uint32_t)__popcll(o2);
+    slot += (uint32_t)__popcll(o1);
   }
   if (lane == 0) a.cons_len[t] = slot;
 }
