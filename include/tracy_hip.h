@@ -136,11 +136,18 @@ int tracyhip_synchronize(tracyhip_ctx* ctx);
                     that are left instead of skipping the others in place; default 1024)
      b16_multi_max  (stream-ordered pipelines: units up to which a band stage is ONE launch over its four lists; above, strip height 12 gets a
                     launch of its own beside the other three; 0 .. 2147483647, default 49152, 0 = every band stage takes the large form)
+     chain_prio     (stream-ordered orientation stage: wave priority of what runs on the voted strand's side stream beside the other strand's
+                    full sweeps.  "0" none, "1" the tiers of the pruned sweep and the early decision, "2" also the early preliminary / final
+                    alignments of `tracy align`; any other value is refused; default "1")
    Every option selects another EXACT path (A/B measurements, tests of the fallback tiers); none changes a result.  Lanes inherit.
    TRACYHIP_HOST_THREADS, TRACYHIP_HOST_TIMERS, TRACYHIP_LDS_PAD and TRACYHIP_LDS_STAGE_LIMIT are per process (read once).
-   tracyhip_describe writes the current settings as "name=value" lines (at most cap - 1 bytes) and returns the length needed. */
+   tracyhip_describe writes the current settings as "name=value" lines (at most cap - 1 bytes) and returns the length needed.
+   tracyhip_describe_options does so without a context or a device: the options a context created NOW would start with (the defaults and
+   the TRACYHIP_* environment) with name = value set on top (name NULL: nothing set); TRACYHIP_ERR_ARG for an option or value that
+   tracyhip_set_option would refuse. */
 int tracyhip_set_option(tracyhip_ctx* ctx, const char* name, const char* value);
 int tracyhip_describe(tracyhip_ctx* ctx, char* buf, size_t cap);
+int tracyhip_describe_options(const char* name, const char* value, char* buf, size_t cap);
 /* glibc allocator settings that keep the descriptor vectors of the HOST-PLANNED pipelines (no_stream, and the fallback tiers) on the
    heap: M_MMAP_THRESHOLD 32 MB, M_TRIM_THRESHOLD 1 GB, M_TOP_PAD 64 MB.  Process-wide, therefore opt-in: a command-line tool or a
    benchmark calls it once; a library loaded into somebody else's process does not touch the allocator.  (TRACYHIP_MALLOPT=1 in the

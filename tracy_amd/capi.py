@@ -175,6 +175,19 @@ class PackedSeqs:
         return s
 
 
+def describe_options(name=None, value=None):
+    """tracyhip_describe_options: the options a context created now would start with (defaults + TRACYHIP_* environment), with
+    name = value set on top; needs no device.  Raises where tracyhip_set_option would refuse."""
+    nm = None if name is None else str(name).encode()
+    val = None if value is None else str(int(value) if isinstance(value, bool) else value).encode()
+    n = lib().tracyhip_describe_options(nm, val, None, C.c_size_t(0))
+    if n < 0:
+        _check(n)
+    buf = C.create_string_buffer(n)
+    lib().tracyhip_describe_options(nm, val, buf, C.c_size_t(n))
+    return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
+
+
 class Context:
     def __init__(self, device=0):
         self._h = C.c_void_p()

@@ -57,6 +57,8 @@ struct Band16Args {
   // *count (null: npairs) -- the grid is sized for the worst case and the waves past the count leave at once
   const uint32_t* index;
   const uint32_t* count;
+  // nonzero: the launch's waves raise their issue priority on entry (band16_launch.h wave_prio; the kernels' wrappers, not the bodies)
+  int32_t prio;
 };
 constexpr uint32_t kB16RowCap = 200;  // CONT: row-R entries staged per pair (the window of strip 0 and the column before it)
 constexpr uint32_t kB16QuadRowCap = 24;  // ... of the quad form: a window of at most fifteen steps

@@ -32,6 +32,7 @@ struct DeviceWave16 {
 template <int K, int KIND>
 __global__ __launch_bounds__(64) void band16_kernel(Band16Args a) {
   DeviceWave16 w;
+  wave_prio(a.prio);
   band16_body<DeviceWave16, K, KIND>(w, a, blockIdx.x);
 }
 // One launch for the three strip heights of a small job: blocks [0, w12) sweep a12's pairs on K = 12 strips, the next w8 a8's on
@@ -52,6 +53,7 @@ __global__ __launch_bounds__(64) void band16_multi_kernel(Band16Args a12, uint32
 template <int KIND>
 __global__ __launch_bounds__(64) void band16_multi_counted_kernel(Band16Args a12, Band16Args a8, Band16Args a4, Band16Args aq) {
   DeviceWave16 w;
+  wave_prio(a12.prio);  // (the four jobs are copies of one launch's arguments)
   const uint32_t w12 = (*a12.count + 3u) / 4u, w8 = (*a8.count + 3u) / 4u, w4 = (*a4.count + 3u) / 4u, wq = (*aq.count + 15u) / 16u;
   if (blockIdx.x < w12) band16_body<DeviceWave16, 12, KIND>(w, a12, blockIdx.x);
   else if (blockIdx.x < w12 + w8) band16_body<DeviceWave16, 8, KIND>(w, a8, blockIdx.x - w12);
@@ -64,6 +66,7 @@ __global__ __launch_bounds__(64) void band16_multi_counted_kernel(Band16Args a12
 template <int KIND>
 __global__ __launch_bounds__(64) void band16_multi3_counted_kernel(Band16Args a8, Band16Args a4, Band16Args aq) {
   DeviceWave16 w;
+  wave_prio(a8.prio);
   const uint32_t w8 = (*a8.count + 3u) / 4u, w4 = (*a4.count + 3u) / 4u, wq = (*aq.count + 15u) / 16u;
   if (blockIdx.x < w8) band16_body<DeviceWave16, 8, KIND>(w, a8, blockIdx.x);
   else if (blockIdx.x < w8 + w4) band16_body<DeviceWave16, 4, KIND>(w, a4, blockIdx.x - w8);
@@ -73,18 +76,21 @@ __global__ __launch_bounds__(64) void band16_multi3_counted_kernel(Band16Args a8
 template <int K>
 __global__ __launch_bounds__(64) void band16_cont_kernel(Band16Args a) {
   DeviceWave16 w;
+  wave_prio(a.prio);
   band16_body<DeviceWave16, K, 1, true>(w, a, blockIdx.x);
 }
 
 template <int K>
 __global__ __launch_bounds__(64) void band16_cont16_kernel(Band16Args a) {
   DeviceWave16 w;
+  wave_prio(a.prio);
   band16_cont16_body<DeviceWave16, K>(w, a, blockIdx.x);
 }
 
 // the narrow first tier of the pruned sweeps: strips of four rows, four lanes per pair
 __global__ __launch_bounds__(64) void band16_cont16_quad_kernel(Band16Args a) {
   DeviceWave16 w;
+  wave_prio(a.prio);
   band16_cont16_body<DeviceWave16, 4, 4>(w, a, blockIdx.x);
 }
 
@@ -92,8 +98,9 @@ __global__ __launch_bounds__(64) void band16_cont16_quad_kernel(Band16Args a) {
 // prev (or null): the verdicts of an earlier, narrower tier over the same descriptors -- what certified there is an empty slot here
 __global__ __launch_bounds__(64) void front_place_kernel(const FrontDesc* __restrict__ desc, const uint32_t* __restrict__ row, int32_t goe, int32_t halfw,
                                                          PairDesc* __restrict__ pairs, FrontOut* __restrict__ fo, const FrontOut* __restrict__ prev,
-                                                         const uint32_t* __restrict__ index, const uint32_t* __restrict__ count) {
+                                                         const uint32_t* __restrict__ index, const uint32_t* __restrict__ count, int prio) {
   DeviceWave16 w;
+  wave_prio(prio);
   // (a later tier's units as a list laid out on the device: the grid holds the worst case, the workgroups past the count leave)
   uint32_t u = blockIdx.x;
   if (index) {
@@ -110,8 +117,9 @@ __global__ __launch_bounds__(64) void front_place_kernel(const FrontDesc* __rest
 __global__ __launch_bounds__(64) void front_certify_kernel(const FrontDesc* __restrict__ desc, const uint32_t* __restrict__ row, int32_t go, int32_t ge,
                                                            int32_t halfw, const int32_t* __restrict__ scores, const uint32_t* __restrict__ ends,
                                                            FrontOut* __restrict__ fo, const FrontOut* __restrict__ prev,
-                                                           const uint32_t* __restrict__ index, const uint32_t* __restrict__ count) {
+                                                           const uint32_t* __restrict__ index, const uint32_t* __restrict__ count, int prio) {
   DeviceWave16 w;
+  wave_prio(prio);
   uint32_t u = blockIdx.x;
   if (index) {
     if (u >= *count) return;
@@ -283,17 +291,17 @@ hipError_t launch_band16_cont(int K, const Band16Args& a, hipStream_t s, bool na
 }
 
 hipError_t launch_front_place(const FrontDesc* d_desc, uint32_t n, const uint32_t* row, int32_t goe, int32_t halfw, PairDesc* d_pairs, FrontOut* d_fo,
-                              hipStream_t s, const FrontOut* d_prev, const uint32_t* d_index, const uint32_t* d_count) {
+                              hipStream_t s, const FrontOut* d_prev, const uint32_t* d_index, const uint32_t* d_count, int prio) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(front_place_kernel, dim3(n), dim3(64), 0, s, d_desc, row, goe, halfw, d_pairs, d_fo, d_prev, d_index, d_count);
+  hipLaunchKernelGGL(front_place_kernel, dim3(n), dim3(64), 0, s, d_desc, row, goe, halfw, d_pairs, d_fo, d_prev, d_index, d_count, prio);
   return hipGetLastError();
 }
 
 hipError_t launch_front_certify(const FrontDesc* d_desc, uint32_t n, const uint32_t* row, int32_t go, int32_t ge, int32_t halfw, const int32_t* d_scores,
                                 const uint32_t* d_ends, FrontOut* d_fo, hipStream_t s, const FrontOut* d_prev, const uint32_t* d_index,
-                                const uint32_t* d_count) {
+                                const uint32_t* d_count, int prio) {
   if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(front_certify_kernel, dim3(n), dim3(64), 0, s, d_desc, row, go, ge, halfw, d_scores, d_ends, d_fo, d_prev, d_index, d_count);
+  hipLaunchKernelGGL(front_certify_kernel, dim3(n), dim3(64), 0, s, d_desc, row, go, ge, halfw, d_scores, d_ends, d_fo, d_prev, d_index, d_count, prio);
   return hipGetLastError();
 }
 

@@ -31,6 +31,16 @@ hipError_t launch_band16_multi(int kind, const Band16Args& a12, const Band16Args
 // copies of the call's stream do not queue behind its hundred thousand waves).  A high priority for side[0] was measured: the voted strand's
 // prefixes finish in 10 ms instead of 20, but the band tiers behind them ask for 15-20 KB of LDS per workgroup and find no room while the
 // full sweeps' 7.5 KB workgroups fill the CUs, whatever the priority -- they run when the sweeps drain, as before.
+// Wave priority (wave_prio below, option chain_prio) does what stream priority could not for the kernels that are short of issue slots,
+// not of room: front_place_kernel beside the sweeps 1.1 -> 0.1 ms; the band tiers, which wait for LDS round trips, stay as they were.
+// The issue priority of a wave (s_setprio): a SIMD picks the next VALU instruction by priority, then by age, so the waves of a short
+// launch that starts beside a device-filling one are the youngest on their SIMDs and get the slots the older ones leave.  Called once
+// per wave at the top of a kernel, with a kernel argument (wave-uniform: a scalar branch around one scalar instruction).  One level:
+// anything above the 0 every other wave runs at outranks age.
+constexpr int kChainWavePrio = 1;
+__device__ __forceinline__ void wave_prio(int level) {
+  if (level) __builtin_amdgcn_s_setprio(kChainWavePrio);
+}
 struct B16Fork {
   static constexpr int kSide = 4;  // three for the lists of a band stage (and the voted strand's chain), one for work that runs beside whole stages
   hipStream_t side[kSide] = {nullptr, nullptr, nullptr, nullptr};
@@ -57,11 +67,13 @@ struct FrontOut;
 // d_prev (or null): verdicts of an earlier tier over the same descriptors; what certified there is skipped
 // d_index / d_count (or null): workgroup i takes unit d_index[i], and only *d_count of them do (a list laid out on the device, n = its
 // worst case); results stay in the units' own slots
+// prio: as Band16Args::prio
 hipError_t launch_front_place(const FrontDesc* d_desc, uint32_t n, const uint32_t* row, int32_t goe, int32_t halfw, PairDesc* d_pairs, FrontOut* d_fo,
-                              hipStream_t s, const FrontOut* d_prev = nullptr, const uint32_t* d_index = nullptr, const uint32_t* d_count = nullptr);
+                              hipStream_t s, const FrontOut* d_prev = nullptr, const uint32_t* d_index = nullptr, const uint32_t* d_count = nullptr,
+                              int prio = 0);
 hipError_t launch_front_certify(const FrontDesc* d_desc, uint32_t n, const uint32_t* row, int32_t go, int32_t ge, int32_t halfw, const int32_t* d_scores,
                                 const uint32_t* d_ends, FrontOut* d_fo, hipStream_t s, const FrontOut* d_prev = nullptr, const uint32_t* d_index = nullptr,
-                                const uint32_t* d_count = nullptr);
+                                const uint32_t* d_count = nullptr, int prio = 0);
 
 }  // namespace tracyhip
 #endif

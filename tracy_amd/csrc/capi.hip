@@ -279,6 +279,11 @@ bool knobs_set(CtxKnobs& k, const char* name, const char* value) {
     k.b16_multi_max = (uint32_t)v;
     return true;
   }
+  if (same_name(name, "chain_prio")) {  // 0, 1 or 2 and nothing else
+    if (value[0] < '0' || value[0] > '2' || value[1]) return false;
+    k.chain_prio = (uint32_t)(value[0] - '0');
+    return true;
+  }
   if (same_name(name, "seed_vote_cap")) {
     const long v = atol(value);
     if (v < 1 || v > 2048) return false;
@@ -322,6 +327,7 @@ void knobs_from_env(CtxKnobs& k) {
   if (const char* e = getenv("TRACYHIP_QUAD_TIER_MIN")) knobs_set(k, "quad_tier_min", e);
   if (const char* e = getenv("TRACYHIP_FRONT_LIST_MIN")) knobs_set(k, "front_list_min", e);
   if (const char* e = getenv("TRACYHIP_B16_MULTI_MAX")) knobs_set(k, "b16_multi_max", e);
+  if (const char* e = getenv("TRACYHIP_CHAIN_PRIO")) knobs_set(k, "chain_prio", e);
   if (const char* e = getenv("TRACYHIP_SEED_VOTE_CAP")) knobs_set(k, "seed_vote_cap", e);
   if (const char* e = getenv("TRACYHIP_SEED_SPILL")) knobs_set(k, "seed_spill", e);
   if (const char* e = getenv("TRACYHIP_SWEEP_DIAG_PERIOD")) knobs_set(k, "sweep_diag_period", e);
@@ -334,6 +340,7 @@ std::string knobs_describe(const CtxKnobs& k) {
   s += "quad_tier_min=" + std::to_string(k.quad_tier_min) + "\n";
   s += "front_list_min=" + std::to_string(k.front_list_min) + "\n";
   s += "b16_multi_max=" + std::to_string(k.b16_multi_max) + "\n";
+  s += "chain_prio=" + std::to_string(k.chain_prio) + "\n";
   s += "seed_vote_cap=" + std::to_string(k.seed_vote_cap) + "\n";
   s += k.seed_spill ? "seed_spill=1\n" : "seed_spill=0\n";
   s += "sweep_diag_period=" + std::to_string(k.sweep_diag_period) + "\n";
@@ -1455,6 +1462,18 @@ int tracyhip_describe(tracyhip_ctx* c, char* buf, size_t cap) {
   if (!c) return set_error(TRACYHIP_ERR_ARG, "null context");
   const std::string s = knobs_describe(c->knobs) + "device=" + std::to_string(c->device) + "\nlanes=" + std::to_string(c->lanes.size() + 1) +
                         "\nworkspace_limit=" + std::to_string(c->ws_limit) + "\n";
+  if (buf && cap) {
+    const size_t n = std::min(cap - 1, s.size());
+    std::memcpy(buf, s.data(), n);
+    buf[n] = 0;
+  }
+  return (int)s.size() + 1;
+}
+int tracyhip_describe_options(const char* name, const char* value, char* buf, size_t cap) {
+  CtxKnobs k;
+  knobs_from_env(k);
+  if (name && !knobs_set(k, name, value)) return set_error(TRACYHIP_ERR_ARG, "unknown option or bad value: %s=%s", name, value ? value : "(null)");
+  const std::string s = knobs_describe(k);
   if (buf && cap) {
     const size_t n = std::min(cap - 1, s.size());
     std::memcpy(buf, s.data(), n);

@@ -236,6 +236,9 @@ struct CtxKnobs {
   int32_t band_w = -1;            // half width of the certified band of the final alignments: -1 = from the preliminary alignment (default),
                                   // 0 = whole matrices, else [1, 4096]
   uint32_t ckpt_b = 256;
+  uint32_t chain_prio = 1;        // stream-ordered orientation stage: wave priority (band16_launch.h wave_prio) of what is queued on the voted strand's side stream beside
+                                  // the other strand's full sweeps.  0 = none; 1 = the tiers of the pruned sweep (place, band, certify, lists, fold) and the early
+                                  // decision; 2 = also the early tail's stages (plans, scans, band launches).  Never the prefixes, the sweeps or the pass behind the decision
   uint32_t sweep_diag_period = 0; // offset form of the sweeps: steps between re-bases, clamped to what sweep_diag_period() allows; 0 = that
   uint32_t b16_multi_max = TRACY_B16_MULTI_MAX; // stream-ordered pipelines: units up to which a band stage is one launch over its four lists (launch_band16_counted)
   uint32_t front_list_min = 1024; // stream-ordered pipelines: units from which the later tiers of a pruned sweep (and the allele prefixes) run over device-side lists
@@ -274,6 +277,8 @@ struct DpProblem {
 struct tracyhip_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
+  uint32_t queue_prio = 0;  // CtxKnobs::chain_prio while `stream` is the voted strand's side stream beside the full sweeps (stream.hip queue_orientation), else 0:
+                            // the launch helpers read it (stream.hip queued_prio)
   hipStream_t own_stream = nullptr;
   uint64_t ws_limit = 0;
   tracyhip::DevBuf dev[tracyhip::DB_COUNT];  // every device buffer the context keeps, by role (CtxDev)

@@ -68,6 +68,12 @@ __device__ __forceinline__ void with_counters(unsigned long long* cnt, Body body
     if (lc[i]) atomicAdd(cnt + i, lc[i]);
 }
 
+// Wave priority (band16_launch.h wave_prio) of a launch that is being queued: tier 1 -- the tiers of the pruned sweep and the early
+// decision -- from option chain_prio = 1 on, tier 2 -- the early tail's stages -- at 2; nonzero only while queue_orientation queues the voted
+// strand's chain on its side stream beside the full sweeps (tracyhip_ctx::queue_prio), so the pass behind the decision launches the same
+// kernels unraised.
+inline int queued_prio(const tracyhip_ctx* ctx, uint32_t tier) { return ctx->queue_prio >= tier ? 1 : 0; }
+
 // ---- geometry -> descriptor lists of the fixed-shape kernels (vote, row maxima, substitution tables) ----
 __global__ void s_expand_kernel(const SGeom* __restrict__ geom, uint32_t nt, VoteDesc* __restrict__ vd, RowMaxDesc* __restrict__ rm_rest,
                                 RowMaxDesc* __restrict__ rm_trim, RowMaxDesc* __restrict__ rm_full, B16TableDesc* __restrict__ td) {
@@ -177,7 +183,8 @@ __device__ __forceinline__ uint32_t s_front_result(uint32_t t, const FrontOut* _
 // Every other trace is left alone: it is decided, and its alignments are queued, behind the sweeps. ----
 __global__ void s_orient_early_kernel(SParams p, const FrontOut* __restrict__ fo1,
                                       const int32_t* __restrict__ fs1, const uint32_t* __restrict__ fe1, const FrontOut* __restrict__ fo2,
-                                      const int32_t* __restrict__ fs2, const uint32_t* __restrict__ fe2, STrace* __restrict__ tr) {
+                                      const int32_t* __restrict__ fs2, const uint32_t* __restrict__ fe2, STrace* __restrict__ tr, int prio) {
+  wave_prio(prio);
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= p.nt) return;
   STrace S = tr[t];
@@ -186,7 +193,10 @@ __global__ void s_orient_early_kernel(SParams p, const FrontOut* __restrict__ fo
   int64_t s_g = 0;
   const uint32_t fce = s_front_result(t, fo1, fs1, fe1, fo2, fs2, fe2, &s_g);
   if (fce == 0u) return;
-  S.sc[g] = (int32_t)s_g;
+  // (not S.sc[g]: a record indexed by a variable is no longer kept in registers -- the compiler moved all of it to LDS, 52 KB per
+  // workgroup, which no CU has free while the sweeps' workgroups fill it: this kernel, 10 us on its own, then waited 0.2-0.6 ms for room)
+  if (g == 0u) S.sc[0] = (int32_t)s_g;
+  else S.sc[1] = (int32_t)s_g;
   S.fwd = g == 0u ? 1 : 0;
   S.rc = (uint8_t)g;
   S.sstar = (int32_t)s_g;
@@ -269,7 +279,8 @@ __global__ void s_orient_decide_kernel(SParams p, const SGeom* __restrict__ geom
 // early: the pass over the traces marked ST_EARLY (1) or over all the others (0); a trace of the other pass is an empty slot ----
 __global__ void s_prelim_plan_kernel(SParams p, int mode, int early, const SGeom* __restrict__ geom, STrace* __restrict__ tr, const uint32_t* __restrict__ d_ce,
                                      const int32_t* __restrict__ top, uint32_t* __restrict__ dead, PairDesc* __restrict__ cand,
-                                     uint8_t* __restrict__ kc) {
+                                     uint8_t* __restrict__ kc, int prio) {
+  wave_prio(prio);
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= p.nt) return;
   kc[t] = 0;
@@ -326,7 +337,8 @@ __device__ __forceinline__ unsigned long long s_word_bytes(const PairDesc& d, in
   return kind == 0 ? ((b16_store_words(d.m, d.n, K, band_dmin(d), band_dmax(d)) * b16_word_bytes(K) + 15ull) & ~15ull) : 0ull;
 }
 __global__ __launch_bounds__(kScanBlock) void s_scan_partial_kernel(const PairDesc* __restrict__ cand, const uint8_t* __restrict__ kc, uint32_t n, int kind,
-                                                                    int quads, ScanPart* __restrict__ part) {
+                                                                    int quads, ScanPart* __restrict__ part, int prio) {
+  wave_prio(prio);
   __shared__ uint32_t s_n[4];
   __shared__ unsigned long long s_b;
   if (threadIdx.x < 4) s_n[threadIdx.x] = 0;
@@ -345,7 +357,8 @@ __global__ __launch_bounds__(kScanBlock) void s_scan_partial_kernel(const PairDe
 // exclusive scan over the blocks' totals (in place), the lists' sizes (count: for the launch; stat: added up for the call's statistics --
 // `tracy align` runs a stage twice, over the early traces and over the rest)
 __global__ __launch_bounds__(kScanTop) void s_scan_top_kernel(ScanPart* __restrict__ part, uint32_t nb, uint32_t* __restrict__ count,
-                                                              unsigned long long* __restrict__ stat) {
+                                                              unsigned long long* __restrict__ stat, int prio) {
+  wave_prio(prio);
   __shared__ uint32_t s_n[4][kScanTop];
   __shared__ unsigned long long s_b[kScanTop];
   const uint32_t tid = threadIdx.x;
@@ -383,7 +396,8 @@ __global__ __launch_bounds__(kScanTop) void s_scan_top_kernel(ScanPart* __restri
 }
 __global__ __launch_bounds__(kScanBlock) void s_scan_place_kernel(PairDesc* __restrict__ cand, uint8_t* __restrict__ kc, uint32_t n, uint32_t unit_mod, int kind,
                                                                   int quads, unsigned long long cap_bytes, const ScanPart* __restrict__ part, uint32_t* __restrict__ idx,
-                                                                  uint32_t* __restrict__ dead, unsigned long long* __restrict__ stat) {
+                                                                  uint32_t* __restrict__ dead, unsigned long long* __restrict__ stat, int prio) {
+  wave_prio(prio);
   __shared__ uint32_t s_n[4][kScanBlock];
   __shared__ unsigned long long s_b[kScanBlock];
   __shared__ unsigned long long s_stat[SB_LIST];  // (the lists' sizes are the top kernel's)
@@ -433,7 +447,8 @@ __global__ __launch_bounds__(kScanBlock) void s_scan_place_kernel(PairDesc* __re
 // trimmed slice) on its certified band (sage.h:311; pipeline.hip step 4; s_final_band, s_final_certified); `early` as above ----
 __global__ void s_align_final_plan_kernel(SParams p, int early, const SGeom* __restrict__ geom, STrace* __restrict__ tr, const uint32_t* __restrict__ ends,
                                           uint32_t* __restrict__ dead, PairDesc* __restrict__ cand, uint8_t* __restrict__ kc,
-                                          unsigned long long* __restrict__ cnt) {
+                                          unsigned long long* __restrict__ cnt, int prio) {
+  wave_prio(prio);
   with_counters(cnt, [&](unsigned long long* lc) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= p.nt) return;
@@ -693,14 +708,16 @@ int front_tier(tracyhip_ctx* ctx, const tracyhip_params& p, const FrontDesc* fd,
   Band16Args a{};
   a.pairs = pairs; a.npairs = n; a.index = list; a.count = list_count; a.qp = d_qp; a.codes = d_codes; a.scores = fs; a.ends = fe;
   a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p); a.go = p.go; a.ge = p.ge; a.hfree = 1; a.row = d_row;
+  const int prio = queued_prio(ctx, 1);
+  a.prio = prio;
   a.code_cap = (max_rest + 2u * (uint32_t)halfw + 16u) & ~3u;  // front_place_body: a sub-window is at most m_rest + 2 halfw + 2 columns
   if (KB == 0) {
     if (b16_cont_quad_lds(a.code_cap) > 64u * 1024u) return kStreamNo;  // (front_tiers_run goes on with the wide tiers: nothing was queued for this one)
   } else if (!front_tier_fits(KB, halfw, max_rest)) return set_error(TRACYHIP_ERR_ARG, "pruned-sweep tier without LDS room (front_tiers_fit not consulted)");
-  HIP_TRY(launch_front_place(fd, n, d_row, p.go + p.ge, halfw, pairs, fo, st, prev, list, list_count));
+  HIP_TRY(launch_front_place(fd, n, d_row, p.go + p.ge, halfw, pairs, fo, st, prev, list, list_count, prio));
   if (KB == 0) HIP_TRY(launch_band16_cont_quad(a, st));
   else HIP_TRY(launch_band16_cont(KB, a, st, !ctx->knobs.no_cont16));
-  HIP_TRY(launch_front_certify(fd, n, d_row, p.go, p.ge, halfw, fs, fe, fo, st, prev, list, list_count));
+  HIP_TRY(launch_front_certify(fd, n, d_row, p.go, p.ge, halfw, fs, fe, fo, st, prev, list, list_count, prio));
   return TRACYHIP_OK;
 }
 
@@ -727,7 +744,8 @@ __device__ __forceinline__ void s_list_append(bool take, uint32_t i, uint32_t* _
 // (a unit left off the list is not visited by the next tier's place / band / certify launches: its slot of that tier is marked "not
 // certified here" explicitly -- consumers read the earlier tier's verdict first, but the slot must not keep a verdict of another call)
 __global__ __launch_bounds__(256) void s_front_list_kernel(uint32_t n, const FrontOut* __restrict__ prev, uint32_t* __restrict__ list, uint32_t* __restrict__ count,
-                                                           FrontOut* __restrict__ next) {
+                                                           FrontOut* __restrict__ next, int prio) {
+  wave_prio(prio);
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   const bool take = i < n && !prev[i].ok;
   if (i < n && !take) next[i].ok = 0u;
@@ -739,13 +757,14 @@ __global__ __launch_bounds__(256) void s_pair_list_kernel(uint32_t n, const Pair
   s_list_append(i < n && !(pairs[i].flags & PAIR_SKIP), i, list, count);
 }
 hipError_t front_list(tracyhip_ctx* ctx, uint32_t n, const FrontOut* prev, uint32_t* list, uint32_t* count, FrontOut* next) {
-  hipLaunchKernelGGL(s_front_list_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, prev, list, count, next);
+  hipLaunchKernelGGL(s_front_list_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, prev, list, count, next, queued_prio(ctx, 1));
   return hipGetLastError();
 }
 
 // what the narrow tier certified goes into the first wide tier's slots (which skipped it): everything after reads two tiers
 __global__ void s_front_fold_kernel(uint32_t n, const FrontOut* __restrict__ fo0, const int32_t* __restrict__ fs0, const uint32_t* __restrict__ fe0,
-                                    FrontOut* __restrict__ fo1, int32_t* __restrict__ fs1, uint32_t* __restrict__ fe1) {
+                                    FrontOut* __restrict__ fo1, int32_t* __restrict__ fs1, uint32_t* __restrict__ fe1, int prio) {
+  wave_prio(prio);
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n || !fo0[i].ok) return;
   fo1[i] = fo0[i];
@@ -764,7 +783,7 @@ int front_tiers_run_wide(tracyhip_ctx* ctx, const tracyhip_params& p, StreamComm
                       list1 ? sc.flist : nullptr, list1 ? sc.fcount : nullptr);
   if (rc) return rc;
   if (after_quads) {
-    hipLaunchKernelGGL(s_front_fold_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, sc.fo0, sc.fs0, sc.fe0, sc.fo1, sc.fs1, sc.fe1);
+    hipLaunchKernelGGL(s_front_fold_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, sc.fo0, sc.fs0, sc.fe0, sc.fo1, sc.fs1, sc.fe1, queued_prio(ctx, 1));
     HIP_TRY(hipGetLastError());
   }
   // (the first list has been read by the tier above: the same array holds the second)
@@ -806,12 +825,14 @@ int band_stage(tracyhip_ctx* ctx, const tracyhip_params& p, StreamCommon& sc, ui
   uint32_t* count = sc.count + 4 * stage_no;
   const uint32_t nb = (n + kScanBlock - 1) / kScanBlock;
   const int quads = (!ctx->knobs.no_quads && b16_quad_lds(bl.code_cap) <= 64u * 1024u) ? 1 : 0;  // the narrow bands four lanes to a pair, where sixteen code rows fit
-  hipLaunchKernelGGL(s_scan_partial_kernel, dim3(nb), dim3(kScanBlock), 0, st, sc.cand, sc.kc, n, bl.kind, quads, sc.part);
-  hipLaunchKernelGGL(s_scan_top_kernel, dim3(1), dim3(kScanTop), 0, st, sc.part, nb, count, sc.bstat + SB_COUNT * stage_no);
+  const int prio = queued_prio(ctx, 2);
+  hipLaunchKernelGGL(s_scan_partial_kernel, dim3(nb), dim3(kScanBlock), 0, st, sc.cand, sc.kc, n, bl.kind, quads, sc.part, prio);
+  hipLaunchKernelGGL(s_scan_top_kernel, dim3(1), dim3(kScanTop), 0, st, sc.part, nb, count, sc.bstat + SB_COUNT * stage_no, prio);
   hipLaunchKernelGGL(s_scan_place_kernel, dim3(nb), dim3(kScanBlock), 0, st, sc.cand, sc.kc, n, unit_mod, bl.kind, quads, (unsigned long long)cap_bytes, sc.part, sc.idx, sc.dead,
-                     sc.bstat + SB_COUNT * stage_no);
+                     sc.bstat + SB_COUNT * stage_no, prio);
   HIP_TRY(hipGetLastError());
   Band16Args a{};
+  a.prio = prio;
   a.pairs = sc.cand; a.npairs = n; a.qp = bl.qp; a.codes = bl.codes; a.bits = static_cast<uint8_t*>(ctx->dev[DB_BITS].p); a.scores = bl.scores; a.ends = bl.ends;
   a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p); a.go = p.go; a.ge = p.ge; a.hfree = bl.hfree;
   a.ops = bl.ops; a.ops_off = bl.ops_off; a.ops_len = bl.ops_len; a.code_cap = bl.code_cap;
@@ -848,8 +869,8 @@ struct OrientStage {
   std::function<int()> filler;
   // or stages of the call that need nothing of a trace but its voted strand's certified pruned sweep (`tracy align`: the preliminary and
   // final alignments of the traces s_orient_early_kernel marks): queued on the voted strand's side stream behind its tiers, with the
-  // context's stream set to it, BEFORE the call's stream waits for that chain -- so they run beside the end of the full sweeps instead
-  // of on a drained device behind them.  Only called with side streams; the caller queues the same stages for the other traces itself,
+  // context's stream set to it (and its queue priority: what the hook queues there is tier 2 of queued_prio), BEFORE the call's stream
+  // waits for that chain -- so they run beside the end of the full sweeps instead of on a drained device behind them.  Only called with side streams; the caller queues the same stages for the other traces itself,
   // behind the decision.
   std::function<int()> early_tail;
 };
@@ -924,12 +945,17 @@ int queue_orientation(tracyhip_ctx* ctx, const tracyhip_params& p, const SParams
       launch_diag_periods(ctx, &p, h.classes[0].K, 0u, npre_all, true, af, apl);
       if (launch_gotoh_ckpt_front(h.classes[0].K, af, 0u, apl, npre_all, fk.side[0]) != hipSuccess) rc = set_error(TRACYHIP_ERR_HIP, "prefix launch failed");
     }
+    // What is queued on the side stream from here on raises its waves' priority as option chain_prio says (queued_prio): the waves of
+    // the tiers and of the early tail are the youngest on SIMDs the sweeps keep busy, and a SIMD issues by priority, then by age.  The
+    // prefixes above stay at the sweeps' priority, and so does everything queued behind the decision.
+    ctx->queue_prio = ctx->knobs.chain_prio;
     if (!rc) rc = front_tiers();
     if (!rc && os.early_tail) {
-      hipLaunchKernelGGL(s_orient_early_kernel, g256, b256, 0, fk.side[0], sp, sc.fo1, sc.fs1, sc.fe1, sc.fo2, sc.fs2, sc.fe2, sc.tr);
+      hipLaunchKernelGGL(s_orient_early_kernel, g256, b256, 0, fk.side[0], sp, sc.fo1, sc.fs1, sc.fe1, sc.fo2, sc.fs2, sc.fe2, sc.tr, queued_prio(ctx, 1));
       if (hipGetLastError() != hipSuccess) rc = set_error(TRACYHIP_ERR_HIP, "early decision launch failed");
       else rc = os.early_tail();
     }
+    ctx->queue_prio = 0;  // (with the stream, on every way out: front_tiers and early_tail hand their status back)
     ctx->stream = st;
     HIP_TRY(hipEventRecord(fk.joined[0], fk.side[0]));
     if (rc) {  // (whoever takes the call from here finds nothing of it running beside the call's stream)
@@ -1450,13 +1476,13 @@ struct AlignStream : StreamCall {
     StreamCommon& sc = A.sc;
     hipStream_t s = ctx->stream;
     // ---- 2. preliminary alignment (sage.h:258) by its two ends, 3. trimReferenceSlice (sage.h:259) ----
-    hipLaunchKernelGGL(s_prelim_plan_kernel, g256, b256, 0, s, spm, 0, early, sc.geom, sc.tr, sc.ce, sc.top_trim, sc.dead, sc.cand, sc.kc);
+    hipLaunchKernelGGL(s_prelim_plan_kernel, g256, b256, 0, s, spm, 0, early, sc.geom, sc.tr, sc.ce, sc.top_trim, sc.dead, sc.cand, sc.kc, queued_prio(ctx, 2));
     HIP_TRY(hipGetLastError());
     BandLaunch b1;
     b1.kind = 1; b1.qp = d_qp; b1.codes = ctx->codes(); b1.ends = sc.ends; b1.code_cap = ncap; b1.hfree = 1;
     TRY(band_stage(ctx, p, sc, nt, nt, 0, b1, ~0ull));
     // ---- 4. final alignment gotoh(full profile, trimmed slice) (sage.h:311) on its certified band ----
-    hipLaunchKernelGGL(s_align_final_plan_kernel, g256, b256, 0, s, spm, early, sc.geom, sc.tr, sc.ends, sc.dead, sc.cand, sc.kc, sc.cnt);
+    hipLaunchKernelGGL(s_align_final_plan_kernel, g256, b256, 0, s, spm, early, sc.geom, sc.tr, sc.ends, sc.dead, sc.cand, sc.kc, sc.cnt, queued_prio(ctx, 2));
     HIP_TRY(hipGetLastError());
     BandLaunch b2;
     b2.kind = 0; b2.qp = d_qp; b2.codes = ctx->codes(); b2.scores = o.score_final; b2.ops = d_ops; b2.ops_off = A.ops_off; b2.ops_len = o.ops_len; b2.code_cap = ncap;
@@ -2164,7 +2190,7 @@ struct DecStream : StreamCall {
         return encode_windows_cq();
       };
     TRY(give_up(queue_orientation(ctx, p, spm, h, sc, os)));
-    hipLaunchKernelGGL(s_prelim_plan_kernel, g256, b256, 0, st, spm, 1, 0, sc.geom, sc.tr, sc.ce, sc.top_trim, sc.dead, sc.cand, sc.kc);
+    hipLaunchKernelGGL(s_prelim_plan_kernel, g256, b256, 0, st, spm, 1, 0, sc.geom, sc.tr, sc.ce, sc.top_trim, sc.dead, sc.cand, sc.kc, 0);
     HIP_TRY(hipGetLastError());
     BandLaunch b0;
     b0.kind = 0; b0.qp = d_qp; b0.codes = ctx->codes(); b0.scores = A.sb; b0.ops = A.ops1; b0.ops_off = A.off1; b0.ops_len = A.len1; b0.code_cap = ncap; b0.hfree = 1;
