@@ -191,6 +191,8 @@ typedef struct {
   uint32_t seed_spilled;         /* tracyhip_seed_traces with seed_spill (which sets these three and no other counter): traces answered by the spill kernel */
   uint32_t seed_spill_launches;  /* ... spill launches the call made (one more synchronisation each) */
   uint32_t seed_spill_deferred;  /* ... spilled traces handed to the host because their tables did not fit the workspace limit */
+  uint32_t wt_chunks;            /* tracyhip_align_traces, wildtype job: chunks of traces the batch was cut into to fit the workspace limit (like
+                                    every counter summed over the lanes of the call; 0 when the call failed) */
 } tracyhip_call_stats;
 int tracyhip_last_call_stats(tracyhip_ctx* ctx, tracyhip_call_stats* out);
 const char* tracyhip_last_error(void);
@@ -244,7 +246,10 @@ int tracyhip_alignment_rows(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, int 
 typedef struct {
   uint32_t ntraces;
   tracyhip_seqset profiles; /* kind PROFILE, one full profile per trace */
-  tracyhip_seqset refs;     /* kind CHAR */
+  tracyhip_seqset refs;     /* kind CHAR: reference windows (FASTA / indexed genome).  kind PROFILE: a WILDTYPE job (sage.h:261-300 + :311),
+                               the reference of every trace is a second chromatogram -- the FORWARD profile of every distinct wildtype
+                               (createProfile(gtr, gbc)), host or device per `mem`; without ref_index count >= ntraces.  See "wildtype
+                               jobs" below.  (The struct does not grow for it: its size and every offset are what they were.) */
   const uint32_t* ref_index; /* HOST array or NULL (= identity) */
   uint32_t trim_left;       /* SageConfig.trimLeft  (sage.h:88) */
   uint32_t trim_right;      /* SageConfig.trimRight (sage.h:89) */
@@ -261,6 +266,21 @@ typedef struct {
   const uint32_t* trim_right_each; /* scalars above).  Given: trace t uses trim_left_each[t] / trim_right_each[t] wherever the scalars
                                are used, and the scalars are ignored (per-trace trims, below).  One without the other: TRACYHIP_ERR_ARG. */
 } tracyhip_align_job;
+
+/* ---- wildtype jobs (tracyhip_align_job::refs of kind PROFILE) ---------------------------------------------------------------------
+ * Per trace t with wildtype W (n columns), all on the device and in stream order:
+ *   trimmed = columns [l, mf - r) of the full profile (rule 1 of the per-trace trims below; scalars or trim_*_each)
+ *   gsFwd = gotohScore(trimmed, W), gsRev = gotohScore(trimmed, revcomp W)   (sage.h:289-290; revcomp once per DISTINCT wildtype)
+ *   forward = gsFwd > gsRev: a tie is reverse (sage.h:293)
+ *   score_final / ops / ops_len = gotoh(full profile, chosen strand of W), push order, capacity mf + n at ops_offset[t]   (sage.h:311)
+ *   rows0 / rows1 (optional) = the _createAlignment rows of that alignment
+ * score_fwd / score_rev are both exact: strand_by_certificate is IGNORED for wildtype jobs.  There is no preliminary alignment and no
+ * trimReferenceSlice in this branch: score_prelim (if non-NULL) receives the chosen strand's orientation score, slice_begin = 0,
+ * slice_len = n, ref_pos = 0.  With `oriented` non-NULL the profiles are taken as already oriented: one score per trace goes into both
+ * score_fwd and score_rev (as on the indexed-genome path) and forward[t] = oriented[t].
+ * The traceback planes are chunked by traces to the workspace limit (tracyhip_call_stats::wt_chunks); the call synchronises twice
+ * (the profile classes, the end) whatever ntraces or the number of chunks is, and twice that when a 16-bit score launch met an
+ * un-normalised profile and the call repeats on int32. */
 
 /* ---- per-trace trims (`-t`: trimTrace gives every trace its own trimLeft / trimRight, sage.h:39-40, trim.h:35-73) ----------------
  * tracyhip_align_job, tracyhip_decompose_job (which tracyhip_decompose_variants reads) and tracyhip_seed_params carry two optional
@@ -291,10 +311,16 @@ typedef struct {
                              voted strand and discarded when the other strand's exact score won */
   const uint64_t* ops_offset; /* HOST array */
   uint32_t* ops_len;      /* [ntraces] */
+  uint8_t* rows0;         /* OPTIONAL, both or neither; wildtype jobs only (TRACYHIP_ERR_ARG otherwise).  The _createAlignment rows of the final */
+  uint8_t* rows1;         /* alignment (align.h:254-293: consensus characters of the trace profile / of the chosen strand of the wildtype),
+                             ops_len[t] bytes each at ops_offset[t].  The chosen strand exists on the device only, so tracyhip_alignment_rows
+                             could not give them without the reverse complement being made again */
 } tracyhip_align_result;
 
 /* what tracyhip_align_traces checks before it plans, on the host (no device is touched): job / prm / out and the result arrays it
- * always writes non-NULL, `mem` one of the two kinds, ops_offset given, both or neither of trim_left_each / trim_right_each.
+ * always writes non-NULL, `mem` one of the two kinds, ops_offset given, both or neither of trim_left_each / trim_right_each; for a
+ * wildtype job (refs of kind PROFILE) a non-NULL payload and, without ref_index, count >= ntraces; rows0 / rows1 both or neither, and
+ * neither on a job whose refs are of kind CHAR; any other kind of refs.
  * TRACYHIP_ERR_ARG (with the reason) otherwise.  The compute call runs it first. */
 int tracyhip_align_validate(const tracyhip_align_job* job, const tracyhip_params* prm, int mem, const tracyhip_align_result* out);
 int tracyhip_align_traces(tracyhip_ctx* ctx, const tracyhip_align_job* job, const tracyhip_params* prm,
@@ -396,9 +422,13 @@ typedef struct {
   tracyhip_decomp_params dprm;
   const uint8_t* oriented;       /* HOST array or NULL; as in tracyhip_align_job: refs already oriented by k-mer seeding
                                     (indigo.h:213-218), oriented[t] = rs.forward; score_fwd / score_rev are then zero */
-  tracyhip_seqset ref_profiles;  /* data NULL = unused.  Wildtype-trace reference (indigo.h:249-289): profile of the wildtype
-                                    trace, oriented by the caller (needs `oriented`), parallel to refs, which then hold the
-                                    wildtype's (oriented) primary basecalls = rs.refslice */
+  tracyhip_seqset ref_profiles;  /* data NULL = unused.  Wildtype-trace reference (indigo.h:249-289): kind PROFILE, the profile of every
+                                    wildtype trace, parallel to refs (same count, same lengths), which then hold the wildtype's primary
+                                    basecalls = rs.refslice.  With `oriented`: both already oriented by the caller.  Without: both are
+                                    the FORWARD wildtype and the call chooses the strand (indigo.h:276-277): gsFwd / gsRev =
+                                    gotohScore(trimmed trace profile, W / revcomp W), forward = gsFwd > gsRev, all three written to
+                                    score_fwd / score_rev / forward; everything from indigo.h:302 on runs against the chosen strand (the
+                                    reverse complement of the profile, made on the device once per distinct wildtype, and of refs) */
   uint32_t strand_by_certificate; /* as in tracyhip_align_job: 0 (default) = both orientation scores exact; 1 = the losing
                                     orientation's score may be a certified upper bound */
   const uint32_t* trim_left_each;  /* HOST arrays [ntraces], or both NULL: as in tracyhip_align_job, in place of dprm.trim_left / */
@@ -433,6 +463,7 @@ typedef struct {
 
 /* what tracyhip_decompose_traces checks before it plans, on the host (no device is touched): NULL arguments and result arrays,
  * `mem`, the basecall arrays, maxindel (TRACYHIP_ERR_RANGE), both or neither of the per-trace trim arrays and their range.
+ * With ref_profiles: its kind, offset / length arrays, the same count and lengths as refs, and count >= ntraces without ref_index.
  * TRACYHIP_ERR_ARG (with the reason) otherwise.  The compute call runs it first. */
 int tracyhip_decompose_validate(const tracyhip_decompose_job* job, const tracyhip_params* prm, int mem, const tracyhip_decompose_result* out);
 int tracyhip_decompose_traces(tracyhip_ctx* ctx, const tracyhip_decompose_job* job, const tracyhip_params* prm, int mem,

@@ -66,7 +66,7 @@ class AlignResult(C.Structure):
     _fields_ = [("score_fwd", C.c_void_p), ("score_rev", C.c_void_p), ("forward", C.c_void_p),
                 ("score_prelim", C.c_void_p), ("slice_begin", C.c_void_p), ("slice_len", C.c_void_p),
                 ("ref_pos", C.c_void_p), ("score_final", C.c_void_p), ("ops", C.c_void_p),
-                ("ops_offset", C.POINTER(C.c_uint64)), ("ops_len", C.c_void_p)]
+                ("ops_offset", C.POINTER(C.c_uint64)), ("ops_len", C.c_void_p), ("rows0", C.c_void_p), ("rows1", C.c_void_p)]
 
 
 class CallStats(C.Structure):
@@ -82,7 +82,7 @@ class CallStats(C.Structure):
 class CallStatsVariants(CallStats):
     """CallStats (the counters through denovo_steps, kept as it was: tests pin its tail) with the four counters of
     tracyhip_decompose_variants appended -- ctypes lays a subclass's fields out behind its base's, as the C struct grew.  The struct
-    has grown since: CallStatsSeed below is THE mirror of tracyhip_call_stats, and the only one to hand to
+    has grown since: CallStatsWildtype below is THE mirror of tracyhip_call_stats, and the only one to hand to
     tracyhip_last_call_stats -- anything shorter is an out-of-bounds write.  Context.last_call_stats uses it."""
     _fields_ = [("var_traces", C.c_uint32), ("var_realigned", C.c_uint32), ("var_truncated", C.c_uint32), ("var_chunks", C.c_uint32)]
 
@@ -99,9 +99,14 @@ class CallStatsBands(CallStatsSweeps):
 
 
 class CallStatsSeed(CallStatsBands):
-    """CallStatsBands with the three counters of tracyhip_seed_traces under the option seed_spill behind it, as the C struct grew: THE
-    mirror of tracyhip_call_stats now, and what Context.last_call_stats hands to the library."""
+    """CallStatsBands with the three counters of tracyhip_seed_traces under the option seed_spill behind it, as the C struct grew."""
     _fields_ = [("seed_spilled", C.c_uint32), ("seed_spill_launches", C.c_uint32), ("seed_spill_deferred", C.c_uint32)]
+
+
+class CallStatsWildtype(CallStatsSeed):
+    """CallStatsSeed with the chunk counter of the wildtype jobs of tracyhip_align_traces behind it, as the C struct grew: THE mirror of
+    tracyhip_call_stats now, and what Context.last_call_stats hands to the library."""
+    _fields_ = [("wt_chunks", C.c_uint32)]
 
 
 def library_path():
@@ -229,11 +234,11 @@ class Context:
 
     def last_call_stats(self):
         """tiers the traces of the last align_traces / decompose_traces call took (tracyhip_last_call_stats)"""
-        st = CallStatsSeed()
+        st = CallStatsWildtype()
         _check(lib().tracyhip_last_call_stats(self._h, C.byref(st)))
         out = {}
         for name, ty in (CallStats._fields_ + CallStatsVariants._fields_ + CallStatsSweeps._fields_ + CallStatsBands._fields_
-                         + CallStatsSeed._fields_):
+                         + CallStatsSeed._fields_ + CallStatsWildtype._fields_):
             v = getattr(st, name)
             if name == "band_list_pairs":
                 out[name] = [list(row) for row in v]
@@ -336,14 +341,21 @@ def _align_banded(self, a1, a2, params, band_lo, band_hi, origin=False):
 class PreparedAlign:
     """host-buffer job / result structs of tracyhip_align_traces (everything they point to is kept alive by this object)"""
 
-    def __init__(self, profiles, refs, params, trim_left=50, trim_right=50, ref_index=None, oriented=None, exact_scores=True):
+    def __init__(self, profiles, refs, params, trim_left=50, trim_right=50, ref_index=None, oriented=None, exact_scores=True,
+                 ref_profiles=None, rows=False):
+        """ref_profiles (a list of float32 [6][n] or a PackedSeqs): a wildtype job -- the FORWARD profile of every wildtype, indexed by
+        ref_index; refs is then not read (pass None).  rows: rows0 / rows1 of the final alignment as well (wildtype jobs only)."""
         pp = profiles if isinstance(profiles, PackedSeqs) else PackedSeqs(profiles, SEQ_PROFILE)
-        pr = refs if isinstance(refs, PackedSeqs) else PackedSeqs(refs, SEQ_CHAR)
+        self.wildtype = ref_profiles is not None
+        if self.wildtype:
+            pr = ref_profiles if isinstance(ref_profiles, PackedSeqs) else PackedSeqs(ref_profiles, SEQ_PROFILE)
+        else:
+            pr = refs if isinstance(refs, PackedSeqs) else PackedSeqs(refs, SEQ_CHAR)
         nt = self.nt = pp.count
         job = self.job = AlignJob()
         job.ntraces = nt
         job.profiles = pp.seqset()
-        job.refs = pr.seqset()
+        job.refs = pr.seqset()  # (kind PROFILE makes it a wildtype job)
         self.keep = [pp, pr]
         if ref_index is not None:
             ref_index = np.ascontiguousarray(ref_index, dtype=np.uint32)
@@ -369,30 +381,37 @@ class PreparedAlign:
             "ref_pos": np.zeros(max(nt, 1), np.uint32), "score_final": np.zeros(max(nt, 1), np.int32),
             "ops": np.zeros(max(int(cap.sum()) if nt else 0, 1), np.uint8), "ops_len": np.zeros(max(nt, 1), np.uint32),
         }
+        if rows:
+            res["rows0"], res["rows1"] = np.zeros_like(res["ops"]), np.zeros_like(res["ops"])
         out = self.out = AlignResult()
-        for k in ("score_fwd", "score_rev", "forward", "score_prelim", "slice_begin", "slice_len", "ref_pos",
-                  "score_final", "ops", "ops_len"):
+        for k in res:
             setattr(out, k, res[k].ctypes.data)
         out.ops_offset = off.ctypes.data_as(C.POINTER(C.c_uint64))
         self.prm = Params(params[0], params[1], params[2], params[3], 1, 0)
 
     def results(self):
         res, off, nt = dict(self.res), self.off, self.nt
-        btr = [res["ops"][int(off[i]):int(off[i]) + int(res["ops_len"][i])].tobytes() for i in range(nt)]
+        cut = lambda a: [a[int(off[i]):int(off[i]) + int(res["ops_len"][i])].tobytes() for i in range(nt)]
+        btr = cut(res["ops"])
+        if "rows0" in res:
+            res["rows0"], res["rows1"] = cut(res["rows0"]), cut(res["rows1"])
         for k in list(res):
-            if k != "ops":
+            if k not in ("ops", "rows0", "rows1"):
                 res[k] = res[k][:nt]
         res["btr"] = btr
         return res
 
 
-def _align_traces(self, profiles, refs, params, trim_left=50, trim_right=50, ref_index=None, oriented=None, exact_scores=True, device=False):
+def _align_traces(self, profiles, refs, params, trim_left=50, trim_right=50, ref_index=None, oriented=None, exact_scores=True, device=False,
+                  ref_profiles=None, rows=False):
     """tracyhip_align_traces with host buffers.  profiles: list of float32 [6][mf]; refs: list of bytes.
+    ref_profiles: a wildtype job (refs None) -- the forward profile of every wildtype, a list of float32 [6][n] or a PackedSeqs, joined
+    through ref_index; the strand is chosen on the device.  rows=True adds "rows0" / "rows1" (bytes per trace) to the result.
     oriented: None, or rs.forward per trace when the references are already oriented (indexed-genome path).
     trim_left / trim_right: ints, or per-trace array-likes (e.g. PreparedBasecall.trims() of a run with a trim stringency).
     device=True: payloads and result arrays in device memory (torch tensors, TRACYHIP_MEM_DEVICE), copied back afterwards.
     Returns a dict of numpy arrays + the list of final traceback strings (push order)."""
-    p = PreparedAlign(profiles, refs, params, trim_left, trim_right, ref_index, oriented, exact_scores)
+    p = PreparedAlign(profiles, refs, params, trim_left, trim_right, ref_index, oriented, exact_scores, ref_profiles, rows)
     if device:
         import torch
         pp, pr = p.keep[0], p.keep[1]
@@ -992,10 +1011,12 @@ class DecomposeOutcome(dict):
 
 
 def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_right=50, maxindel=1000, madc=5, oriented=None,
-                      ref_profiles=None, exact_scores=True, peaks_only=False, device_bc=None):
+                      ref_profiles=None, exact_scores=True, peaks_only=False, device_bc=None, ref_index=None):
     """tracyhip_decompose_traces with host buffers; hbc: HostBaseCalls (primary/secondary rewritten in place);
     oriented: None, or rs.forward per trace when the references are already oriented (indexed-genome path).
     trim_left / trim_right: ints, or per-trace array-likes (Context.decompose_variants reads them from the job this call keeps).
+    ref_profiles: wildtype-trace references, parallel to refs (the wildtypes' primary calls); without `oriented` the call chooses the strand.
+    ref_index: reference (and wildtype profile) of every trace, for shared references; None = identity.
     device_bc: a PreparedBasecall(device=True) that has run -- profiles, basecalls and peak table are taken from its device tensors as they
     stand (profiles and hbc may be None), references and results live on the device too (TRACYHIP_MEM_DEVICE) and are copied back."""
     dev = device_bc is not None
@@ -1041,12 +1062,24 @@ def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_righ
     if oriented is not None:
         oriented = np.ascontiguousarray(oriented, dtype=np.uint8)
         job.oriented = oriented.ctypes.data_as(C.POINTER(C.c_uint8))
-    if ref_profiles is not None:  # wildtype-trace reference: oriented profiles parallel to refs (= oriented primary calls)
+    if ref_profiles is not None:
+        # wildtype-trace reference: profiles parallel to refs (= the wildtypes' primary calls).  With `oriented` both are already oriented;
+        # without, both are the FORWARD wildtype and the call chooses the strand (score_fwd / score_rev / forward are filled)
         prp = ref_profiles if isinstance(ref_profiles, PackedSeqs) else PackedSeqs(ref_profiles, SEQ_PROFILE)
-        job.ref_profiles = prp.seqset()
+        if dev:
+            d_refprof = torch.from_numpy(prp.data).cuda()
+            d_refs = (d_refs, d_refprof)  # (kept alive by the returned call)
+            job.ref_profiles = prp.seqset(d_refprof.data_ptr())
+        else:
+            job.ref_profiles = prp.seqset()
     cap = 2 * maxindel + 2
     doff = np.arange(max(nt, 1), dtype=np.uint64) * np.uint64(cap)
-    rn = pr.length[:nt].astype(np.uint64)
+    if ref_index is not None:
+        ref_index = np.ascontiguousarray(ref_index, dtype=np.uint32)
+        job.ref_index = ref_index.ctypes.data_as(C.POINTER(C.c_uint32))
+        rn = pr.length[ref_index].astype(np.uint64)
+    else:
+        rn = pr.length[:nt].astype(np.uint64)
     res = {
         "bp": (Breakpoint * max(nt, 1))(), "status": np.zeros(max(nt, 1), np.int32),
         "score_fwd": np.zeros(max(nt, 1), np.int32), "score_rev": np.zeros(max(nt, 1), np.int32),
@@ -1099,7 +1132,7 @@ def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_righ
     res = DecomposeOutcome(res)
     # what Context.decompose_variants needs of this call: the structs and everything they point to
     res.call = dict(job=job, out=out, prm=prm, mem=MEM_DEVICE if dev else MEM_HOST, nt=nt,
-                    keep=(pr, pp, prp, d_refs, hbc, doff, keep, oriented, mirrors, device_bc, dict(res), trim_arrays))
+                    keep=(pr, pp, prp, d_refs, hbc, doff, keep, oriented, mirrors, device_bc, dict(res), trim_arrays, ref_index))
     if dev:  # the decomposed basecalls as the call left them in the device tensors
         rows = device_bc.results(fill_deferred=False)
         res["primary"] = [r["primary"] for r in rows]

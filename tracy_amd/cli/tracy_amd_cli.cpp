@@ -477,12 +477,29 @@ int prepare(SageConfig const& c, Job& j, bool decompose = false) {
     }
     j.rs.chr = name;
   } else {
-    Trace gtr;
-    if (!load_trace(j.ref_path, gtr)) return -1;
-    BaseCalls gbc;
-    basecall(gtr, gbc, c.pratio);
-    createProfile(gtr, gbc, j.wt_fwd);
-    j.wt_primary = gbc.primary;
+    // a wildtype trace: read, basecalled and profiled once per distinct file of the run (a plate names one control read many times)
+    struct WildtypeRef { Profile fwd; std::string primary; };
+    static std::mutex wt_mutex;
+    static std::map<std::string, std::shared_ptr<const WildtypeRef>> wt_cache;
+    std::shared_ptr<const WildtypeRef> wt;
+    {
+      std::lock_guard<std::mutex> lk(wt_mutex);
+      auto it = wt_cache.find(j.ref_path);
+      if (it != wt_cache.end()) wt = it->second;
+      else {
+        Trace gtr;
+        if (!load_trace(j.ref_path, gtr)) return -1;  // (not kept: every line that names the file reports it)
+        BaseCalls gbc;
+        basecall(gtr, gbc, c.pratio);
+        auto fresh = std::make_shared<WildtypeRef>();
+        createProfile(gtr, gbc, fresh->fwd);
+        fresh->primary = gbc.primary;
+        wt = fresh;
+        wt_cache.emplace(j.ref_path, wt);
+      }
+    }
+    j.wt_fwd = wt->fwd;
+    j.wt_primary = wt->primary;
     j.rs.chr = "wildtype";
   }
   return 0;
@@ -623,64 +640,56 @@ bool align_fasta_group(Device& dev, tracyhip_params const& prm, std::vector<Job*
   return alignment_rows(ctx, job.profiles, s2, ops, ooff, olen, jobs, nthreads);
 }
 
-// wildtype-trace references: sage.h:261-301 + :311 (profile x profile)
-bool align_wildtype_group(tracyhip_ctx* ctx, tracyhip_params const& prm, std::vector<Job*> const& jobs) {
+// wildtype-trace references: sage.h:261-301 + :311 (profile x profile) for the jobs of a block in ONE call.  The forward profile of
+// every DISTINCT wildtype file of the block is uploaded once, joined to its traces through ref_index; the reverse complement, both
+// strand scores, the strand decision, the final alignment and its rows are the device's (tracyhip_align_job::refs of kind PROFILE).
+bool align_wildtype_group(Device& dev, tracyhip_params const& prm, std::vector<Job*> const& jobs) {
   const uint32_t nt = (uint32_t)jobs.size();
-  std::vector<Profile> trimmed(nt), wrev(nt);
-  std::vector<float> ptrim, pfull, pref;  // pref: forward then reverse-complement wildtype profile per job
-  std::vector<uint64_t> toff(nt), foff(nt), woff(2 * nt), ooff(nt);
-  std::vector<uint32_t> tlen(nt), flen(nt), wlen(2 * nt), idx1(2 * nt), idx2(2 * nt);
-  for (uint32_t i = 0; i < nt; ++i) {
-    Job& j = *jobs[i];
-    createProfile(j.tr, j.bc, trimmed[i], (int32_t)j.trimLeft, (int32_t)j.trimRight);
-    reverseComplementProfile(j.wt_fwd, wrev[i]);
-    toff[i] = ptrim.size(); tlen[i] = (uint32_t)trimmed[i].cols;
-    ptrim.insert(ptrim.end(), trimmed[i].v.begin(), trimmed[i].v.end());
-    foff[i] = pfull.size(); flen[i] = (uint32_t)j.full.cols;
-    pfull.insert(pfull.end(), j.full.v.begin(), j.full.v.end());
-    for (int r = 0; r < 2; ++r) {
-      Profile const& p = r ? wrev[i] : j.wt_fwd;
-      woff[2 * i + r] = pref.size(); wlen[2 * i + r] = (uint32_t)p.cols;
-      pref.insert(pref.end(), p.v.begin(), p.v.end());
-      idx1[2 * i + r] = i; idx2[2 * i + r] = 2 * i + r;
-    }
-  }
-  tracyhip_pairs sp{};
-  sp.npairs = 2 * nt;
-  sp.a1 = tracyhip_seqset{TRACYHIP_SEQ_PROFILE, ptrim.data(), toff.data(), tlen.data(), nt};
-  sp.a2 = tracyhip_seqset{TRACYHIP_SEQ_PROFILE, pref.data(), woff.data(), wlen.data(), 2 * nt};
-  sp.a1_index = idx1.data(); sp.a2_index = idx2.data();
-  std::vector<int32_t> gs(2 * nt);
-  if (tracyhip_gotoh_score(ctx, &sp, &prm, TRACYHIP_MEM_HOST, gs.data()) != TRACYHIP_OK) return gpu_fail("orientation scores");
-  std::vector<uint32_t> pick(nt), olen(nt);
+  std::vector<float> pfull, pref;
+  std::vector<uint64_t> foff(nt), woff, ooff(nt);
+  std::vector<uint32_t> flen(nt), wlen, ridx(nt), trim_l(nt), trim_r(nt);
+  std::map<std::string, uint32_t> seen;  // wildtype file -> its entry of refs
   uint64_t ocap = 0;
   for (uint32_t i = 0; i < nt; ++i) {
     Job& j = *jobs[i];
-    j.rs.forward = gs[2 * i] > gs[2 * i + 1];
+    foff[i] = pfull.size(); flen[i] = (uint32_t)j.full.cols;
+    pfull.insert(pfull.end(), j.full.v.begin(), j.full.v.end());
+    auto it = seen.find(j.ref_path);
+    if (it == seen.end()) {
+      it = seen.emplace(j.ref_path, (uint32_t)woff.size()).first;
+      woff.push_back(pref.size()); wlen.push_back((uint32_t)j.wt_fwd.cols);
+      pref.insert(pref.end(), j.wt_fwd.v.begin(), j.wt_fwd.v.end());
+    }
+    ridx[i] = it->second;
+    trim_l[i] = j.trimLeft; trim_r[i] = j.trimRight;
+    ooff[i] = ocap;
+    ocap += (uint64_t)flen[i] + wlen[ridx[i]];
+  }
+  tracyhip_align_job job{};
+  job.ntraces = nt;
+  job.profiles = tracyhip_seqset{TRACYHIP_SEQ_PROFILE, pfull.data(), foff.data(), flen.data(), nt};
+  job.refs = tracyhip_seqset{TRACYHIP_SEQ_PROFILE, pref.data(), woff.data(), wlen.data(), (uint32_t)woff.size()};
+  job.ref_index = ridx.data();
+  job.trim_left_each = trim_l.data();
+  job.trim_right_each = trim_r.data();
+  std::vector<int32_t> sf(nt), sr(nt), sc(nt);
+  std::vector<uint8_t> fwd(nt), ops(ocap ? ocap : 1), r0(ops.size()), r1(ops.size());
+  std::vector<uint32_t> sb(nt), sl(nt), rp(nt), olen(nt);
+  tracyhip_align_result res{};
+  res.score_fwd = sf.data(); res.score_rev = sr.data(); res.forward = fwd.data();
+  res.slice_begin = sb.data(); res.slice_len = sl.data(); res.ref_pos = rp.data();
+  res.score_final = sc.data(); res.ops = ops.data(); res.ops_offset = ooff.data(); res.ops_len = olen.data();
+  res.rows0 = r0.data(); res.rows1 = r1.data();
+  if (dev.align_traces(&job, &prm, &res) != TRACYHIP_OK) return gpu_fail("align");
+  for (uint32_t i = 0; i < nt; ++i) {
+    Job& j = *jobs[i];
+    j.rs.forward = fwd[i] != 0;
     j.rs.refslice = j.wt_primary;
     if (!j.rs.forward) reverseComplement(j.rs.refslice);
     j.rs.pos = 0;
-    pick[i] = 2 * i + (j.rs.forward ? 0 : 1);
-    ooff[i] = ocap;
-    ocap += (uint64_t)flen[i] + wlen[pick[i]];
-  }
-  tracyhip_pairs fp{};
-  fp.npairs = nt;
-  fp.a1 = tracyhip_seqset{TRACYHIP_SEQ_PROFILE, pfull.data(), foff.data(), flen.data(), nt};
-  fp.a2 = sp.a2;
-  fp.a2_index = pick.data();
-  std::vector<int32_t> sc(nt);
-  std::vector<uint8_t> ops(ocap ? ocap : 1);
-  if (tracyhip_gotoh_align(ctx, &fp, &prm, TRACYHIP_MEM_HOST, sc.data(), ops.data(), ooff.data(), olen.data()) != TRACYHIP_OK)
-    return gpu_fail("final alignment");
-  tracyhip_pairs rp = fp;
-  std::vector<uint8_t> r0(ops.size()), r1(ops.size());
-  if (tracyhip_alignment_rows(ctx, &rp, TRACYHIP_MEM_HOST, ops.data(), ooff.data(), olen.data(), r0.data(), r1.data()) != TRACYHIP_OK)
-    return gpu_fail("alignment rows");
-  for (uint32_t i = 0; i < nt; ++i) {
-    jobs[i]->score = sc[i];
-    jobs[i]->rows.row0.assign(reinterpret_cast<char*>(r0.data()) + ooff[i], olen[i]);
-    jobs[i]->rows.row1.assign(reinterpret_cast<char*>(r1.data()) + ooff[i], olen[i]);
+    j.score = sc[i];
+    j.rows.row0.assign(reinterpret_cast<char*>(r0.data()) + ooff[i], olen[i]);
+    j.rows.row1.assign(reinterpret_cast<char*>(r1.data()) + ooff[i], olen[i]);
   }
   return true;
 }
@@ -819,7 +828,7 @@ int align_main(int argc, char** argv) {
       ++device_calls;
     }
     times.add("device_calls", (double)device_calls);  // align_traces calls of the run
-    if (!wildtype.empty() && !align_wildtype_group(dev.ctx, prm, wildtype)) return false;
+    if (!wildtype.empty() && !align_wildtype_group(dev, prm, wildtype)) return false;
     fatal = 0;
     times.add("device_s", sw.seconds());
     return true;
@@ -914,47 +923,9 @@ bool rows_from_ops(tracyhip_ctx* ctx, std::vector<std::string> const& a1, std::v
   return true;
 }
 
-// wildtype-trace references (indigo.h:249-289): strand by gotohScore(trimmed trace, wildtype profile / its reverse
-// complement); leaves the oriented profile in j.wt_fwd and the oriented primary calls in j.fasta
-bool orient_wildtype(tracyhip_ctx* ctx, tracyhip_params const& prm, std::vector<Job*> const& jobs) {
-  const uint32_t nt = (uint32_t)jobs.size();
-  std::vector<Profile> trimmed(nt), wrev(nt);
-  std::vector<float> ptrim, pref;
-  std::vector<uint64_t> toff(nt), woff(2 * nt);
-  std::vector<uint32_t> tlen(nt), wlen(2 * nt), idx1(2 * nt), idx2(2 * nt);
-  for (uint32_t i = 0; i < nt; ++i) {
-    Job& j = *jobs[i];
-    createProfile(j.tr, j.bc, trimmed[i], (int32_t)j.trimLeft, (int32_t)j.trimRight);
-    reverseComplementProfile(j.wt_fwd, wrev[i]);
-    toff[i] = ptrim.size(); tlen[i] = (uint32_t)trimmed[i].cols;
-    ptrim.insert(ptrim.end(), trimmed[i].v.begin(), trimmed[i].v.end());
-    for (int r = 0; r < 2; ++r) {
-      Profile const& p = r ? wrev[i] : j.wt_fwd;
-      woff[2 * i + r] = pref.size(); wlen[2 * i + r] = (uint32_t)p.cols;
-      pref.insert(pref.end(), p.v.begin(), p.v.end());
-      idx1[2 * i + r] = i; idx2[2 * i + r] = 2 * i + r;
-    }
-  }
-  tracyhip_pairs sp{};
-  sp.npairs = 2 * nt;
-  sp.a1 = tracyhip_seqset{TRACYHIP_SEQ_PROFILE, ptrim.data(), toff.data(), tlen.data(), nt};
-  sp.a2 = tracyhip_seqset{TRACYHIP_SEQ_PROFILE, pref.data(), woff.data(), wlen.data(), 2 * nt};
-  sp.a1_index = idx1.data(); sp.a2_index = idx2.data();
-  std::vector<int32_t> gs(2 * nt);
-  if (tracyhip_gotoh_score(ctx, &sp, &prm, TRACYHIP_MEM_HOST, gs.data()) != TRACYHIP_OK) return gpu_fail("orientation scores");
-  for (uint32_t i = 0; i < nt; ++i) {
-    Job& j = *jobs[i];
-    j.rs.forward = gs[2 * i] > gs[2 * i + 1];
-    j.fasta = j.wt_primary;
-    if (!j.rs.forward) { reverseComplement(j.fasta); j.wt_fwd = wrev[i]; }
-  }
-  return true;
-}
-
 // indigo.h:190-388 for the jobs of a block that share a reference kind: the whole chain runs on the device, every trace with its own trims
 // One group of a block (same reference kind) on its way through tracyhip_decompose_traces: pack() lays the batch out as
-// packed payloads and sizes the result arrays -- host work, done by the stage that prepares the block (for wildtype references by
-// the device stage, once the device has oriented them); run() is the call, the results back into the jobs and the alignment rows.
+// packed payloads and sizes the result arrays -- host work, done by the stage that prepares the block; run() is the call, the results back into the jobs and the alignment rows.
 struct DecomposeGroup {
   std::vector<Job*> jobs;
   uint32_t nt = 0;
@@ -997,6 +968,7 @@ struct DecomposeGroup {
     for (uint32_t i = 0; i < nt; ++i) {
       Job& j = *jobs[i];
       poff[i] = ptot; plen[i] = (uint32_t)j.full.cols; ptot += j.full.v.size();
+      if (wildtype) j.fasta = j.wt_primary;  // the FORWARD primary calls of the wildtype: the call chooses the strand (indigo.h:276-277)
       roff[i] = rtot; rlen[i] = (uint32_t)j.fasta.size(); rtot += j.fasta.size();
       boff[i] = btot; blen[i] = (uint32_t)j.bc.bcPos.size(); btot += blen[i];
       dcpoff[i] = (uint64_t)i * dcap;
@@ -1041,7 +1013,7 @@ struct DecomposeGroup {
     job.trim_left_each = trim_l.data();
     job.trim_right_each = trim_r.data();
     job.strand_by_certificate = 1;  // the orientation scores are not written anywhere (indigo.h:235-247 keeps only rs.forward)
-    seeded = jobs[0]->rs.filetype == 0 || wildtype;  // the reference arrives oriented
+    seeded = jobs[0]->rs.filetype == 0;  // the reference arrives oriented
     orient.assign(nt, 0);
     for (uint32_t i = 0; i < nt; ++i) orient[i] = jobs[i]->rs.forward ? 1 : 0;
     if (seeded) job.oriented = orient.data();
@@ -1079,7 +1051,6 @@ struct DecomposeGroup {
   bool run(Device& dev, SageConfig const& c, tracyhip_params const& prm, uint32_t nthreads) {
     PhaseClock pc;  // (on the calling thread: device_call / unpack are wall seconds of the device stage)
     tracyhip_ctx* ctx = dev.ctx;
-    if (wildtype && !orient_wildtype(ctx, prm, jobs)) return false;
     if (!packed) pack(c, nthreads);
     pc.lap(CpuPhases::PACK);
     if (dev.decompose_traces(&job, &prm, &res) != TRACYHIP_OK) return gpu_fail("decompose");
@@ -1314,7 +1285,7 @@ int decompose_main(int argc, char** argv) {
     std::vector<std::unique_ptr<DecomposeGroup>>& mine = block_groups[lo / blk];
     for (auto& g : groups) {
       mine.emplace_back(new DecomposeGroup(std::move(g.second)));
-      if (!mine.back()->wildtype) mine.back()->pack(c, nthreads);
+      mine.back()->pack(c, nthreads);
     }
     times.add("read_basecall_profile_s", sw.seconds());
   };

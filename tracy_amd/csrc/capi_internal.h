@@ -176,9 +176,21 @@ enum CtxDev : int {
   VB_PACK_OFF,  // var_pack_scan_kernel: where every trace's records and text begin in the packed copies
   VB_PACK_REC,  // the used records of every trace back to back: written by var_pack_copy_kernel, copied to the host
   VB_PACK_TEXT, // the used text likewise
-  DB_COUNT
+  // ---- tracyhip_align_traces with a wildtype-trace reference (wildtype.hip wildtype_run) ----
+  WB_ORIENTED,  // caller-oriented jobs: the strand byte of every trace, uploaded; read by wt_decide_kernel (the one slot of its own,
+                // before the aliases: they do not advance the count)
+  // the same stages as consensus_run over the same kinds of data, and a context runs one call at a time: the roles that match share a slot
+  WB_W = CB_A2,          // both strands of every DISTINCT wildtype profile: copied in, the reverse written by prof_revcomp_kernel
+  WB_SEQS = CB_SEQS,     // ProfSeq list (traces, then wildtypes), uploaded
+  WB_CLASS = CB_CLASS,   // "row 4 is all zero" byte per trace and wildtype, read back
+  WB_COLCLASS = CB_COLCLASS,  // column classes of both strands of the wildtypes, read by the screened score sweeps
+  WB_SC2 = CB_SC2,       // the strand scores per trace (two, or one for caller-oriented jobs): written by the score sweeps, read by wt_decide_kernel
+  WB_OFF = CB_OFF,       // offsets of the op strings / rows, uploaded
+  WB_PAIR = CB_PAIR,     // per-trace results staged for a host caller (and score_prelim where the caller wants none)
+  WB_PAY = CB_PAY,       // ops / rows0 / rows1 staged for a host caller
+  DB_COUNT = WB_ORIENTED + 1
 };
-static_assert(DN_CNT + 1 == VB_DESC && VB_PACK_TEXT + 1 == DB_COUNT && DN_PAY < DB_COUNT,
+static_assert(DN_CNT + 1 == VB_DESC && VB_PACK_TEXT + 1 == WB_ORIENTED && DN_PAY < DB_COUNT && WB_PAY < DB_COUNT,
               "an alias does not advance the count: every slot of its own comes after the aliases");
 // pinned host buffers of a context: tracyhip_ctx::pin[]
 enum CtxPin : int {
@@ -489,8 +501,9 @@ hipError_t launch_prof_classify(const ProfSeq* seqs, uint32_t n, const float* da
 // walk pointers.
 // score form, two descriptors per unit (both strands): 16-bit cells where !wide, !no_narrow and arith16_ok hold for the run's largest
 // m + n, which is then appended to narrow_launches for range_verdict; timed as TRACYHIP_TIMER_SCORE
+// (per: descriptors per unit -- 1 where the caller's profiles are already oriented and only one strand is scored)
 int prof_score_runs(tracyhip_ctx* ctx, const tracyhip_params* prm, bool wide, const DpArgs& args, const PairDesc* hd, const PairDesc* dd,
-                    const int* k, uint32_t lo, uint32_t hi, std::vector<std::pair<uint32_t, int>>& narrow_launches);
+                    const int* k, uint32_t lo, uint32_t hi, std::vector<std::pair<uint32_t, int>>& narrow_launches, uint32_t per = 2);
 // traceback form, one descriptor per unit: the sweep walks its pairs itself (ops / ops_off / ops_len by PairDesc::out), or with
 // no_fused_walk a walk launch follows each sweep; timed as TRACYHIP_TIMER_TRACE / TRACYHIP_TIMER_WALK
 int prof_trace_runs(tracyhip_ctx* ctx, const DpArgs& args, const PairDesc* hd, const PairDesc* dd, const int* k, uint32_t lo, uint32_t hi,

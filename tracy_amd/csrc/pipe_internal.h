@@ -29,6 +29,8 @@ inline TrimSrc trims_of(const tracyhip_decompose_job* j) {
 int align_traces_legacy(tracyhip_ctx* ctx, const tracyhip_align_job* job, const tracyhip_params* prm, int mem, const tracyhip_align_result* out);
 int decompose_traces_legacy(tracyhip_ctx* ctx, const tracyhip_decompose_job* job, const tracyhip_params* prm, int mem,
                             const tracyhip_decompose_result* out);
+// tracyhip_align_traces with a wildtype-trace reference (job->refs of kind PROFILE; wildtype.hip) for one context: stream-ordered, its own stages
+int wildtype_align(tracyhip_ctx* ctx, const tracyhip_align_job* job, const tracyhip_params* prm, int mem, const tracyhip_align_result* out);
 // the same stage orders with the planning on the device; traces whose tier the device cannot give them go through the functions
 // above afterwards.  TRACYHIP_OK, an error, or kStreamNo.
 int stream_align(tracyhip_ctx* ctx, const tracyhip_align_job* job, const tracyhip_params* prm, int mem, const tracyhip_align_result* out);

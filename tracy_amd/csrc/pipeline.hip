@@ -791,12 +791,20 @@ extern "C" int tracyhip_align_validate(const tracyhip_align_job* job, const trac
   if (mem != TRACYHIP_MEM_HOST && mem != TRACYHIP_MEM_DEVICE) return set_error(TRACYHIP_ERR_ARG, "bad mem kind");
   if ((job->trim_left_each == nullptr) != (job->trim_right_each == nullptr))
     return set_error(TRACYHIP_ERR_ARG, "trim_left_each and trim_right_each must be given together");
+  const bool wildtype = job->refs.kind == TRACYHIP_SEQ_PROFILE;  // a wildtype-trace reference (wildtype.hip)
+  if ((out->rows0 == nullptr) != (out->rows1 == nullptr)) return set_error(TRACYHIP_ERR_ARG, "rows0 and rows1 must be given together");
+  if (out->rows0 && !wildtype) return set_error(TRACYHIP_ERR_ARG, "rows0 / rows1 are written for wildtype jobs (refs of kind PROFILE) only");
   const uint32_t nt = job->ntraces;
   if (nt == 0) return TRACYHIP_OK;
   const tracyhip_seqset& sp = job->profiles;
   const tracyhip_seqset& sr = job->refs;
-  if (sp.kind != TRACYHIP_SEQ_PROFILE || sr.kind != TRACYHIP_SEQ_CHAR) return set_error(TRACYHIP_ERR_ARG, "profiles must be PROFILE, refs CHAR");
+  if (sp.kind != TRACYHIP_SEQ_PROFILE || (sr.kind != TRACYHIP_SEQ_CHAR && !wildtype))
+    return set_error(TRACYHIP_ERR_ARG, "profiles must be PROFILE, refs CHAR (or PROFILE: wildtype traces)");
   if (!sp.offset || !sp.length || !sr.offset || !sr.length || sp.count < nt) return set_error(TRACYHIP_ERR_ARG, "bad sequence sets");
+  if (wildtype) {
+    if (!sr.data) return set_error(TRACYHIP_ERR_ARG, "refs: wildtype profiles without a payload");
+    if (!job->ref_index && sr.count < nt) return set_error(TRACYHIP_ERR_ARG, "refs: %u wildtype profiles for %u traces without ref_index", sr.count, nt);
+  }
   if (!out->score_fwd || !out->score_rev || !out->forward || !out->slice_begin || !out->slice_len || !out->ref_pos ||
       !out->score_final || !out->ops || !out->ops_offset || !out->ops_len)
     return set_error(TRACYHIP_ERR_ARG, "null result array");
@@ -817,6 +825,7 @@ static int align_traces_one(tracyhip_ctx* ctx, const tracyhip_align_job* job, co
   bool empty = false;
   int rc = align_check_args(ctx, job, prm, mem, out, &empty);
   if (rc || empty) return rc;
+  if (job->refs.kind == TRACYHIP_SEQ_PROFILE) return wildtype_align(ctx, job, prm, mem, out);  // a wildtype-trace reference: its own stages (wildtype.hip)
   rc = stream_align(ctx, job, prm, mem, out);
   if (rc != kStreamNo) return rc;
   return align_traces_legacy(ctx, job, prm, mem, out);
@@ -1266,13 +1275,14 @@ struct AlignChunk {
     j.ntraces = k;
     sub_seqset(job->profiles, lo, k, sizeof(float), sp);
     j.profiles = sp.s;
-    if (job->ref_index) j.ref_index = job->ref_index + lo;  // shared references: the whole set goes with every chunk
-    else { sub_seqset(job->refs, lo, k, 1, sr); j.refs = sr.s; }
+    if (job->ref_index) j.ref_index = job->ref_index + lo;  // shared references (strings or wildtype profiles): the whole set goes with every chunk
+    else { sub_seqset(job->refs, lo, k, job->refs.kind == TRACYHIP_SEQ_PROFILE ? sizeof(float) : 1, sr); j.refs = sr.s; }
     j.oriented = shifted(job->oriented, lo);
     j.trim_left_each = shifted(job->trim_left_each, lo); j.trim_right_each = shifted(job->trim_right_each, lo);
     sub_offsets(out->ops_offset, lo, k, so);
     AlignFields::each(o, *out, [&](auto& mine, auto& theirs, uint32_t per) { mine = shifted(theirs, (uint64_t)per * lo); });
     o.ops = shifted(out->ops, so.base); o.ops_offset = so.off.data();
+    o.rows0 = shifted(out->rows0, so.base); o.rows1 = shifted(out->rows1, so.base);  // (wildtype jobs; laid out like ops)
   }
 };
 }  // namespace
@@ -1337,6 +1347,14 @@ extern "C" int tracyhip_decompose_validate(const tracyhip_decompose_job* job, co
   if (!bc.primary || !bc.secondary || !bc.bc_offset || !bc.bc_len || (!bc.peaks && (!bc.signal || !bc.signal_offset || !bc.nsamples || !bc.bcpos)))
     return set_error(TRACYHIP_ERR_ARG, "null basecall arrays");  // (the peak table, or signal + bcpos to build it from)
   if (dp.maxindel < 1 || dp.maxindel > kMaxIndelGlobal) return set_error(TRACYHIP_ERR_RANGE, "maxindel must be in [1, %d]", kMaxIndelGlobal);
+  if (job->ref_profiles.data) {  // wildtype-trace reference: a PROFILE set parallel to refs (its primary basecalls)
+    const tracyhip_seqset& srp = job->ref_profiles;
+    if (srp.kind != TRACYHIP_SEQ_PROFILE || srp.count != sr.count || !srp.offset || !srp.length || !sr.length)
+      return set_error(TRACYHIP_ERR_ARG, "ref_profiles must be a PROFILE set parallel to refs");
+    if (!job->ref_index && srp.count < nt) return set_error(TRACYHIP_ERR_ARG, "ref_profiles: %u wildtypes for %u traces without ref_index", srp.count, nt);
+    for (uint32_t i = 0; i < sr.count; ++i)
+      if (srp.length[i] != sr.length[i]) return set_error(TRACYHIP_ERR_ARG, "ref_profiles[%u] and refs[%u] differ in length", i, i);
+  }
   if (!out->bp || !out->status || !out->score_fwd || !out->score_rev || !out->forward || !out->score_trim || !out->dcp_indel ||
       !out->dcp_err || !out->dcp_offset || !out->dstatus || !out->secdecomp || !out->fractions)
     return set_error(TRACYHIP_ERR_ARG, "null result array");
@@ -1387,6 +1405,7 @@ struct DecomposeRun {
   StageClock stage_clock, sc6;
   std::vector<uint32_t> mf, mt, tl, rn, ridx, sl, soff;  // sl / soff: trimmedSeq(length, offset)
   uint64_t max_mn = 0, ep = 0, er = 0, sext = 0, bext = 0, dext = 0, tot1 = 0;
+  uint64_t wt_rev_base = 0;  // wildtype reference without `oriented`: where the reverse strands start in d_refprof
   uint32_t maxbc = 0, maxcol = 0;
   int nbuf = 0;
   DevBuf &b_sc2, &b_ops1, &b_len1, &b_r0, &b_r1, &b_hst, &b_cq1, &b_cq2, &b_cqf, &b_opsA, &b_lenA, &b_trimA, &b_rnfw, &b_ends;
@@ -1485,18 +1504,25 @@ struct DecomposeRun {
       if (!bc.peaks) sext = std::max<uint64_t>(sext, bc.signal_offset[t] + 4ull * bc.nsamples[t]);
       bext = std::max<uint64_t>(bext, bc.bc_offset[t] + bc.bc_len[t]);
     }
-    // wildtype-trace reference (indigo.h:249-289): the alignment of the trimmed trace runs against the wildtype PROFILE
-    // (already oriented by the caller), everything after it against its primary basecalls (refs)
-    if (wildtype) {
-      if (!job->oriented) return set_error(TRACYHIP_ERR_ARG, "ref_profiles needs `oriented` (the caller picks the strand)");
-      if (srp.kind != TRACYHIP_SEQ_PROFILE || srp.count != sr.count || !srp.offset || !srp.length)
-        return set_error(TRACYHIP_ERR_ARG, "ref_profiles must be a PROFILE set parallel to refs");
-      for (uint32_t i = 0; i < sr.count; ++i)
-        if (srp.length[i] != sr.length[i]) return set_error(TRACYHIP_ERR_ARG, "ref_profiles[%u] and refs[%u] differ in length", i, i);
-    }
+    // wildtype-trace reference (indigo.h:249-289): the alignment of the trimmed trace runs against the wildtype PROFILE, everything
+    // after it against its primary basecalls (refs).  With `oriented` both are already oriented by the caller; without, they are the
+    // FORWARD wildtype and the strand is chosen here (orientation()): the reverse complement of every distinct wildtype profile is
+    // written behind the forward set, once, and a reverse trace reads that copy and refs through PAIR_A2_REVCOMP
     if ((rc = stage_in(ctx, buf(), sp.data, ep * 4, mem, &d_prof))) return rc;
     if ((rc = stage_in(ctx, buf(), sr.data, er, mem, &d_ref))) return rc;
-    if (wildtype && (rc = stage_in(ctx, buf(), srp.data, seqset_extent(srp) * 4, mem, &d_refprof))) return rc;
+    if (wildtype && given && (rc = stage_in(ctx, buf(), srp.data, seqset_extent(srp) * 4, mem, &d_refprof))) return rc;
+    if (wildtype && !given) {
+      wt_rev_base = seqset_extent(srp);
+      DevBuf& bw = buf();
+      float* d_w; HIP_TRY(ensure_into(bw, std::max<uint64_t>(2 * wt_rev_base, 1), d_w));
+      HIP_TRY(hipMemcpyAsync(d_w, srp.data, wt_rev_base * 4, mem == TRACYHIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, st));
+      std::vector<ProfSeq> hs(srp.count);
+      for (uint32_t i = 0; i < srp.count; ++i) hs[i] = ProfSeq{srp.offset[i], srp.length[i], 0};
+      const ProfSeq* ds;
+      if ((rc = upload(ctx, buf(), hs, &ds))) return rc;
+      HIP_TRY(launch_prof_revcomp(ds, srp.count, d_w, d_w, wt_rev_base, st));
+      d_refprof = d_w;
+    }
     // the chromatogram is read at the basecalls' peak positions only: the caller's peak table, or signal + bcpos to build it from
     if (bc.peaks) { if ((rc = stage_in(ctx, buf(), bc.peaks, bext * 16, mem, &d_peaks))) return rc; }
     else {
@@ -1549,16 +1575,19 @@ struct DecomposeRun {
     // Wildtype-trace reference: profile x profile, full-matrix traceback (the caller picked the strand).
     h_sc2.assign(2 * (size_t)nt, 0);
     if (!given && !shared_stages) {
+      // wildtype trace, strand not given (indigo.h:276-277): gotohScore(trimmed profile, W) and gotohScore(trimmed profile, revcomp W),
+      // profile x profile, both strands of every trace in one batch against [W | revcomp W]
       DpProblem pb;
       DpProblemLease lease(ctx, pb);
-      pb.mode = MODE_QP; pb.a1_profile = true; pb.d_a1 = d_prof; pb.d_a2 = ctx->codes();
+      pb.mode = MODE_PROF; pb.a1_profile = true; pb.a2_profile = true; pb.d_a1 = d_prof; pb.d_a2 = d_refprof;
       pb.desc.resize(2 * (size_t)nt); pb.k.resize(2 * (size_t)nt);
       for (uint32_t t = 0; t < nt; ++t) {
         PairDesc d = qp_desc(t, true);
+        d.a2_off = srp.offset[ridx[t]];
         pb.desc[t] = d;
-        d.out = nt + t; d.flags = PAIR_A2_REVCOMP;
+        d.out = nt + t; d.a2_off += wt_rev_base;
         pb.desc[nt + t] = d;
-        pb.k[t] = pb.k[nt + t] = choose_k(d.m, MODE_QP);
+        pb.k[t] = pb.k[nt + t] = choose_k(d.m, MODE_PROF);
       }
       if ((rc = run_dp(ctx, pb, &p, false, false, static_cast<int32_t*>(b_sc2.p), nullptr, nullptr, nullptr))) return rc;
       HIP_TRY(hipMemcpy(h_sc2.data(), b_sc2.p, sizeof(int32_t) * 2 * (size_t)nt, hipMemcpyDeviceToHost));
@@ -1615,7 +1644,10 @@ struct DecomposeRun {
       for (uint32_t t = 0; t < nt; ++t) {
         PairDesc d = qp_desc(t, true);
         d.flags = h_rc[t] ? PAIR_A2_REVCOMP : 0;
-        if (wildtype) d.a2_off = srp.offset[ridx[t]];
+        if (wildtype) {  // a reverse trace reads the reverse copy of the profile (the flag is for strings)
+          d.flags = 0;
+          d.a2_off = srp.offset[ridx[t]] + (h_rc[t] ? wt_rev_base : 0);
+        }
         pb.desc[t] = d;
         desc_trim[t] = d;
         pb.k[t] = choose_k(d.m, pb.mode);

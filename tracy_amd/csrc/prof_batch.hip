@@ -74,23 +74,23 @@ hipError_t launch_prof_classify(const ProfSeq* seqs, uint32_t n, const float* da
 }
 
 int prof_score_runs(tracyhip_ctx* ctx, const tracyhip_params* prm, bool wide, const DpArgs& args, const PairDesc* hd, const PairDesc* dd,
-                    const int* k, uint32_t lo, uint32_t hi, std::vector<std::pair<uint32_t, int>>& narrow_launches) {
+                    const int* k, uint32_t lo, uint32_t hi, std::vector<std::pair<uint32_t, int>>& narrow_launches, uint32_t per) {
   DpArgs a = args;
   a.walk_ops = nullptr; a.walk_ops_off = nullptr; a.walk_ops_len = nullptr;
   int trc;
   for (uint32_t j = lo; j < hi;) {
-    const uint32_t e = run_end(hd, 2, k, j, hi);
+    const uint32_t e = run_end(hd, per, k, j, hi);
     uint64_t mn = 0, cells = 0;
     for (uint32_t u = j; u < e; ++u) {
-      const PairDesc& d = hd[2 * (size_t)u];
+      const PairDesc& d = hd[per * (size_t)u];
       mn = std::max<uint64_t>(mn, (uint64_t)d.m + d.n);
-      cells += 2ull * d.m * d.n;
+      cells += (uint64_t)per * d.m * d.n;
     }
     const bool a16 = !wide && !ctx->knobs.no_narrow && arith16_ok(prm, mn, 0);
     if (a16) narrow_launches.emplace_back((uint32_t)mn, 0);
-    a.pairs = dd + 2 * (size_t)j;
+    a.pairs = dd + per * (size_t)j;
     if ((trc = timing_begin(ctx, TRACYHIP_TIMER_SCORE, cells, 0))) return trc;
-    HIP_TRY(launch_gotoh_prof(k[j], false, (hd[2 * (size_t)j].flags & PAIR_ROW4_ZERO) != 0, a16, a, 2 * (e - j), ctx->stream));
+    HIP_TRY(launch_gotoh_prof(k[j], false, (hd[per * (size_t)j].flags & PAIR_ROW4_ZERO) != 0, a16, a, per * (e - j), ctx->stream));
     if ((trc = timing_end(ctx))) return trc;
     j = e;
   }
