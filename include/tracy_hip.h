@@ -123,7 +123,7 @@ int tracyhip_synchronize(tracyhip_ctx* ctx);
 /* Options.  Every switch of the library is read from the environment ONCE, when a context is created (TRACYHIP_<NAME>, e.g.
    TRACYHIP_NO_STREAM=1), and changed afterwards only through this call; name is the variable without the prefix, in any case:
      no_stream (pipelines planned by the host between launches instead of stream-ordered), no_narrow, no_compact, no_screen,
-     no_band, no_band16, no_front, no_prefix, no_vote, no_origin, no_subwindow, no_prelim_origin, no_cq, no_fused_walk, no_cont16, no_quads, no_fork, no_early_tail (`tracy align`: no alignment queued before both orientation scores are known), no_decomp_wave, no_af_split, no_front_lists, no_origin_band, sweeps_alone (measurement: the full sweeps of the orientation stage on a device of their own), no_sweep_diag (16-bit sweeps on values as they are instead of the diagonal-offset form)   "0" / "1"
+     no_band, no_band16, no_front, no_prefix, no_vote, no_origin, no_subwindow, no_prelim_origin, no_cq, no_fused_walk, no_cont16, no_quads, no_fork, no_early_tail (`tracy align`: no alignment queued before both orientation scores are known), no_decomp_wave, no_af_split, no_front_lists, no_origin_band, sweeps_alone (measurement: the full sweeps of the orientation stage on a device of their own), no_sweep_diag (16-bit sweeps on values as they are instead of the diagonal-offset form), no_prefix_tall_beside (see prefix_tall_min)   "0" / "1"
      sweep_diag_period  (steps between re-bases of the offset form: 0 = what the range rule allows, else a multiple of 4 from 64 on, clamped to that)
      band_w  (half width of the certified band of the final alignments; -1 = from the preliminary alignment, 0 = whole matrices)
      ckpt_b  (steps between wavefront checkpoints, 32 .. 1024)      verbose  (one line per pipeline stage on stderr)
@@ -132,6 +132,9 @@ int tracyhip_synchronize(tracyhip_ctx* ctx);
      seed_spill     ("0" / "1", default "0": a trace over seed_vote_cap is answered on the device by the spill launch of tracyhip_seed_traces,
                     its votes counted in device memory, instead of DEFERRED; any other value is refused)
      quad_tier_min  (stream-ordered pipelines: traces / alleles from which a pruned sweep gets its narrow first tier; default 32768)
+     prefix_tall_min (pairs from which a launch of the pruned sweeps' prefix rows alone runs as eight lanes of sixteen rows instead of sixteen
+                    of eight; 0 .. 2147483647, default 40000.  The voted strands' prefixes that the stream-ordered orientation stage queues beside
+                    the other strands' full sweeps take the sixteen-row shape whatever their number, unless no_prefix_tall_beside is "1")
      front_list_min (... from which its later tiers, and the allele prefixes of `tracy decompose`, run over device-side lists of the units
                     that are left instead of skipping the others in place; default 1024)
      b16_multi_max  (stream-ordered pipelines: units up to which a band stage is ONE launch over its four lists; above, strip height 12 gets a

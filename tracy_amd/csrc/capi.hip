@@ -244,7 +244,7 @@ const KnobField kKnobFlags[] = {
     {"no_screen", &CtxKnobs::no_screen}, {"no_band", &CtxKnobs::no_band}, {"no_band16", &CtxKnobs::no_band16},
     {"no_front", &CtxKnobs::no_front}, {"no_prefix", &CtxKnobs::no_prefix}, {"no_vote", &CtxKnobs::no_vote},
     {"no_origin", &CtxKnobs::no_origin}, {"no_subwindow", &CtxKnobs::no_subwindow}, {"no_prelim_origin", &CtxKnobs::no_prelim_origin},
-    {"no_cq", &CtxKnobs::no_cq}, {"no_fused_walk", &CtxKnobs::no_fused_walk}, {"no_cont16", &CtxKnobs::no_cont16}, {"no_decomp_wave", &CtxKnobs::no_decomp_wave}, {"no_af_split", &CtxKnobs::no_af_split}, {"no_front_lists", &CtxKnobs::no_front_lists}, {"no_origin_band", &CtxKnobs::no_origin_band}, {"no_quads", &CtxKnobs::no_quads}, {"no_fork", &CtxKnobs::no_fork}, {"no_early_tail", &CtxKnobs::no_early_tail}, {"sweeps_alone", &CtxKnobs::sweeps_alone}, {"no_sweep_diag", &CtxKnobs::no_sweep_diag}, {"verbose", &CtxKnobs::verbose}};
+    {"no_cq", &CtxKnobs::no_cq}, {"no_fused_walk", &CtxKnobs::no_fused_walk}, {"no_cont16", &CtxKnobs::no_cont16}, {"no_decomp_wave", &CtxKnobs::no_decomp_wave}, {"no_af_split", &CtxKnobs::no_af_split}, {"no_front_lists", &CtxKnobs::no_front_lists}, {"no_origin_band", &CtxKnobs::no_origin_band}, {"no_quads", &CtxKnobs::no_quads}, {"no_fork", &CtxKnobs::no_fork}, {"no_early_tail", &CtxKnobs::no_early_tail}, {"sweeps_alone", &CtxKnobs::sweeps_alone}, {"no_sweep_diag", &CtxKnobs::no_sweep_diag}, {"no_prefix_tall_beside", &CtxKnobs::no_prefix_tall_beside}, {"verbose", &CtxKnobs::verbose}};
 bool same_name(const char* a, const char* b) {
   for (; *a && *b; ++a, ++b)
     if (std::tolower((unsigned char)*a) != std::tolower((unsigned char)*b)) return false;
@@ -264,6 +264,13 @@ bool knobs_set(CtxKnobs& k, const char* name, const char* value) {
     const long v = atol(value);
     if (v < 0) return false;
     k.quad_tier_min = (uint32_t)std::min<long>(v, 0x7fffffffl);
+    return true;
+  }
+  if (same_name(name, "prefix_tall_min")) {
+    char* end = nullptr;
+    const long v = strtol(value, &end, 10);
+    if (end == value || *end || v < 0 || v > 0x7fffffffl) return false;
+    k.prefix_tall_min = (uint32_t)v;
     return true;
   }
   if (same_name(name, "front_list_min")) {
@@ -326,6 +333,7 @@ void knobs_from_env(CtxKnobs& k) {
   if (const char* e = getenv("TRACYHIP_CKPT_B")) knobs_set(k, "ckpt_b", e);
   if (const char* e = getenv("TRACYHIP_QUAD_TIER_MIN")) knobs_set(k, "quad_tier_min", e);
   if (const char* e = getenv("TRACYHIP_FRONT_LIST_MIN")) knobs_set(k, "front_list_min", e);
+  if (const char* e = getenv("TRACYHIP_PREFIX_TALL_MIN")) knobs_set(k, "prefix_tall_min", e);
   if (const char* e = getenv("TRACYHIP_B16_MULTI_MAX")) knobs_set(k, "b16_multi_max", e);
   if (const char* e = getenv("TRACYHIP_CHAIN_PRIO")) knobs_set(k, "chain_prio", e);
   if (const char* e = getenv("TRACYHIP_SEED_VOTE_CAP")) knobs_set(k, "seed_vote_cap", e);
@@ -339,6 +347,7 @@ std::string knobs_describe(const CtxKnobs& k) {
   s += "ckpt_b=" + std::to_string(k.ckpt_b) + "\n";
   s += "quad_tier_min=" + std::to_string(k.quad_tier_min) + "\n";
   s += "front_list_min=" + std::to_string(k.front_list_min) + "\n";
+  s += "prefix_tall_min=" + std::to_string(k.prefix_tall_min) + "\n";
   s += "b16_multi_max=" + std::to_string(k.b16_multi_max) + "\n";
   s += "chain_prio=" + std::to_string(k.chain_prio) + "\n";
   s += "seed_vote_cap=" + std::to_string(k.seed_vote_cap) + "\n";
@@ -1107,7 +1116,7 @@ int run_prefix_keep_cq(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, co
   for (uint32_t t = 0; t < kHostThreads; ++t) { tc += cells[t]; tb += bytes[t]; }
   int trc;
   if ((trc = timing_begin(ctx, TRACYHIP_TIMER_SCORE, tc, tb))) return trc;
-  HIP_TRY(launch_gotoh_front_prefix_cq(a, (uint32_t)np, st));
+  HIP_TRY(launch_gotoh_front_prefix_cq(a, (uint32_t)np, st, ctx->knobs.prefix_tall_min));
   if ((trc = timing_end(ctx))) return trc;
   return TRACYHIP_OK;
 }
@@ -1354,7 +1363,7 @@ int run_ckpt_prefix(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, const
     af.pairs = static_cast<const PairDesc*>(ctx->dev[DB_DESC].p) + lo;
     DpArgs apl = ap;
     launch_diag_periods(ctx, prm, K, (uint32_t)(hi - lo), npre, front_shape, af, apl);
-    if (front_shape) HIP_TRY(launch_gotoh_ckpt_front(K, af, (uint32_t)(hi - lo), apl, npre, st));
+    if (front_shape) HIP_TRY(launch_gotoh_ckpt_front(K, af, (uint32_t)(hi - lo), apl, npre, st, ctx->knobs.prefix_tall_min));
     else HIP_TRY(launch_gotoh_ckpt_prefix(K, af, (uint32_t)(hi - lo), apl, npre, st));
     if ((trc = timing_end(ctx))) return trc;
     if (hi > lo) narrow_launches.emplace_back(maxm, narrow_launch_diag(K, af.diag_period));

@@ -256,6 +256,10 @@ struct CtxKnobs {
   uint32_t front_list_min = 1024; // stream-ordered pipelines: units from which the later tiers of a pruned sweep (and the allele prefixes) run over device-side lists
   uint32_t seed_vote_cap = 2048;  // tracyhip_seed_traces: votes per trace, strand and pass held in LDS (seed.hip); more: the trace is deferred, or spills
   bool seed_spill = false;        // tracyhip_seed_traces: a trace over seed_vote_cap is answered by the spill kernel (votes counted in device memory) instead of deferred
+  bool no_prefix_tall_beside = false;  // stream-ordered orientation stage, both scores exact: the voted strands' prefixes beside the other strands' full sweeps take
+                                  // their shape by prefix_tall_min like every other prefix launch, instead of the tall one whatever their number
+  uint32_t prefix_tall_min = 40000;  // pairs from which a launch of prefix rows alone (front.h: kFrontRows rows, one row kept) runs as eight lanes of sixteen rows
+                                  // instead of sixteen of eight (launch_gotoh_ckpt_front, launch_gotoh_front_prefix_cq)
   uint32_t quad_tier_min = 32768;  // stream-ordered pipelines: units (traces, or alleles) from which the pruned sweeps get their narrow quad tier          // steps between wavefront checkpoints [32, 1024]
 };
 void knobs_from_env(CtxKnobs& k);

@@ -33,7 +33,7 @@ struct RowsArgs {
 hipError_t launch_gotoh(int mode, int K, bool trace, bool narrow, const DpArgs& a, uint32_t npairs, hipStream_t s, bool rawtab = false);
 // profile x profile with the substitution-term count fixed per launch: row4_zero = every pair of the launch carries PAIR_ROW4_ZERO
 // arith16 (score only): 16-bit cells -- the caller has checked the value range (arith16_ok)
-hipError_t launch_gotoh_front_prefix_cq(const DpArgs& a, uint32_t npairs, hipStream_t s);
+hipError_t launch_gotoh_front_prefix_cq(const DpArgs& a, uint32_t npairs, hipStream_t s, uint32_t tall_min);
 hipError_t launch_gotoh_prof(int K, bool trace, bool row4_zero, bool arith16, const DpArgs& a, uint32_t npairs, hipStream_t s);
 // checkpointed score pass / band traceback (single-pass problems, MODE_CHAR or MODE_QP)
 hipError_t launch_gotoh_ckpt(int mode, int K, bool narrow, const DpArgs& a, uint32_t npairs, hipStream_t s);
@@ -42,7 +42,8 @@ hipError_t launch_band_trace(int mode, int K, const DpArgs& a, const WalkArgs& w
 hipError_t launch_gotoh_origin(int K, int table, int codes, const DpArgs& a, uint32_t npairs, hipStream_t s);  // table: 0 strings by byte compare, 1 MODE_CQ, 2 MODE_QP (profile rows); codes (MODE_CQ): 4 = columns of A C G T only, 5 = with N, 6 = any
 hipError_t launch_gotoh_ckpt_prefix(int K, const DpArgs& full, uint32_t nfull, const DpArgs& pre, uint32_t npre, hipStream_t s);
 hipError_t launch_gotoh_prefix(int K, const DpArgs& a, uint32_t npairs, hipStream_t s);
-hipError_t launch_gotoh_ckpt_front(int K, const DpArgs& full, uint32_t nfull, const DpArgs& pre, uint32_t npre, hipStream_t s);
+// tall_min: prefix pairs from which a launch without full sweeps takes the prefix rows as eight lanes of sixteen rows (0: always)
+hipError_t launch_gotoh_ckpt_front(int K, const DpArgs& full, uint32_t nfull, const DpArgs& pre, uint32_t npre, hipStream_t s, uint32_t tall_min);
 hipError_t launch_needle(int mode, int K, bool trace, const DpArgs& a, uint32_t npairs, hipStream_t s);
 hipError_t launch_gotoh_walk(const WalkArgs& a, hipStream_t s);
 hipError_t launch_needle_walk(const WalkArgs& a, const uint32_t* bits32, hipStream_t s);

@@ -322,11 +322,12 @@ __global__ void s_prelim_plan_kernel(SParams p, int mode, int early, const SGeom
   if (dd) dead[t] |= dd;
 }
 
-// ---- lists per strip height for a band launch: the candidates (kc[i] = 0 / 4 / 8 / 12) are counted per block of 256, one workgroup
-// scans the blocks' totals, and every block then hands its pairs their places in their lists (in unit order) and the bytes of their
-// traceback words (KIND 0).  A pair whose words do not fit the workspace planned for the launch becomes an empty slot and its trace
-// is marked (SD_MEM). ----
-constexpr uint32_t kScanBlock = 256, kScanTop = 1024;
+// ---- lists per strip height for a band launch: the candidates (kc[i] = 0 / 4 / 8 / 12) are counted per block of 256 (ballots per
+// wave), and every block then sums the totals of the blocks before it and hands its pairs their places in their lists (in unit order)
+// and the bytes of their traceback words (KIND 0).  No block waits for another, and neither launch holds more than a few hundred bytes
+// of LDS: beside the sweeps they fit wherever a wave slot is free.  A pair whose words do not fit the workspace planned for the launch
+// becomes an empty slot and its trace is marked (SD_MEM). ----
+constexpr uint32_t kScanBlock = 256, kScanWaves = kScanBlock / 64;
 struct ScanPart { uint32_t n[4]; unsigned long long bytes; };
 // lists: strip height 12, 8, 4, and the quad form (strip height 4, four lanes per pair) for the narrow bands when the launch has room for it
 __device__ __forceinline__ int s_bucket(int K, const PairDesc& d, int quads) {
@@ -336,96 +337,96 @@ __device__ __forceinline__ unsigned long long s_word_bytes(const PairDesc& d, in
   if (words) *words = b16_words(d.m, d.n, K, band_dmin(d), band_dmax(d));
   return kind == 0 ? ((b16_store_words(d.m, d.n, K, band_dmin(d), band_dmax(d)) * b16_word_bytes(K) + 15ull) & ~15ull) : 0ull;
 }
-__global__ __launch_bounds__(kScanBlock) void s_scan_partial_kernel(const PairDesc* __restrict__ cand, const uint8_t* __restrict__ kc, uint32_t n, int kind,
-                                                                    int quads, ScanPart* __restrict__ part, int prio) {
+// sums over the 64 lanes of a wave (every lane gets the sum); the totals of a block's four waves, which lane 0 of each left in LDS
+__device__ __forceinline__ uint32_t s_wave_sum(uint32_t v) {
+  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+  return v;
+}
+__device__ __forceinline__ unsigned long long s_wave_sum(unsigned long long v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ ScanPart s_waves_before(const ScanPart* __restrict__ w, uint32_t upto) {
+  ScanPart t{{0, 0, 0, 0}, 0};
+  for (uint32_t k = 0; k < upto; ++k) { for (int b = 0; b < 4; ++b) t.n[b] += w[k].n[b]; t.bytes += w[k].bytes; }
+  return t;
+}
+__global__ __launch_bounds__(kScanBlock) void s_scan_count_kernel(const PairDesc* __restrict__ cand, const uint8_t* __restrict__ kc, uint32_t n, int kind,
+                                                                  int quads, ScanPart* __restrict__ part, int prio) {
   wave_prio(prio);
-  __shared__ uint32_t s_n[4];
-  __shared__ unsigned long long s_b;
-  if (threadIdx.x < 4) s_n[threadIdx.x] = 0;
-  if (threadIdx.x == 4) s_b = 0;
-  __syncthreads();
-  const uint32_t i = blockIdx.x * kScanBlock + threadIdx.x;
+  __shared__ ScanPart s_w[kScanWaves];
+  const uint32_t tid = threadIdx.x, wv = tid >> 6, L = tid & 63u;
+  const uint32_t i = blockIdx.x * kScanBlock + tid;
   const int K = i < n ? kc[i] : 0;
+  int bucket = -1;
+  unsigned long long mine = 0;
   if (K) {
     const PairDesc d = cand[i];
-    atomicAdd(&s_n[s_bucket(K, d, quads)], 1u);
-    if (kind == 0) atomicAdd(&s_b, s_word_bytes(d, K, kind));
+    bucket = s_bucket(K, d, quads);
+    mine = s_word_bytes(d, K, kind);
   }
+  ScanPart w;
+  for (int b = 0; b < 4; ++b) w.n[b] = (uint32_t)__popcll(__ballot(bucket == b));
+  w.bytes = s_wave_sum(mine);
+  if (L == 0) s_w[wv] = w;
   __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = ScanPart{{s_n[0], s_n[1], s_n[2], s_n[3]}, s_b};
+  if (tid == 0) part[blockIdx.x] = s_waves_before(s_w, kScanWaves);
 }
-// exclusive scan over the blocks' totals (in place), the lists' sizes (count: for the launch; stat: added up for the call's statistics --
-// `tracy align` runs a stage twice, over the early traces and over the rest)
-__global__ __launch_bounds__(kScanTop) void s_scan_top_kernel(ScanPart* __restrict__ part, uint32_t nb, uint32_t* __restrict__ count,
-                                                              unsigned long long* __restrict__ stat, int prio) {
-  wave_prio(prio);
-  __shared__ uint32_t s_n[4][kScanTop];
-  __shared__ unsigned long long s_b[kScanTop];
-  const uint32_t tid = threadIdx.x;
-  const uint32_t per = (nb + kScanTop - 1) / kScanTop;
-  const uint32_t lo = tid * per < nb ? tid * per : nb, hi = lo + per < nb ? lo + per : nb;
-  uint32_t c[4] = {0, 0, 0, 0};
-  unsigned long long bytes = 0;
-  for (uint32_t i = lo; i < hi; ++i) { for (int b = 0; b < 4; ++b) c[b] += part[i].n[b]; bytes += part[i].bytes; }
-  for (int b = 0; b < 4; ++b) s_n[b][tid] = c[b];
-  s_b[tid] = bytes;
-  __syncthreads();
-  for (uint32_t d = 1; d < kScanTop; d <<= 1) {  // inclusive scans over the threads (Hillis-Steele: ten rounds)
-    uint32_t v[4] = {0, 0, 0, 0};
-    unsigned long long vb = 0;
-    if (tid >= d) { for (int b = 0; b < 4; ++b) v[b] = s_n[b][tid - d]; vb = s_b[tid - d]; }
-    __syncthreads();
-    for (int b = 0; b < 4; ++b) s_n[b][tid] += v[b];
-    s_b[tid] += vb;
-    __syncthreads();
-  }
-  uint32_t at[4];
-  for (int b = 0; b < 4; ++b) at[b] = s_n[b][tid] - c[b];
-  unsigned long long off = s_b[tid] - bytes;
-  for (uint32_t i = lo; i < hi; ++i) {
-    const ScanPart x = part[i];
-    part[i] = ScanPart{{at[0], at[1], at[2], at[3]}, off};
-    for (int b = 0; b < 4; ++b) at[b] += x.n[b];
-    off += x.bytes;
-  }
-  if (tid == 0)
-    for (int b = 0; b < 4; ++b) {
-      count[b] = s_n[b][kScanTop - 1];
-      stat[SB_LIST + b] += s_n[b][kScanTop - 1];
-    }
-}
+// count: the lists' sizes for the launch; stat: added up for the call's statistics -- `tracy align` runs a stage twice, over the early
+// traces and over the rest (both written by the last block, whose base plus its own totals they are)
 __global__ __launch_bounds__(kScanBlock) void s_scan_place_kernel(PairDesc* __restrict__ cand, uint8_t* __restrict__ kc, uint32_t n, uint32_t unit_mod, int kind,
                                                                   int quads, unsigned long long cap_bytes, const ScanPart* __restrict__ part, uint32_t* __restrict__ idx,
-                                                                  uint32_t* __restrict__ dead, unsigned long long* __restrict__ stat, int prio) {
+                                                                  uint32_t* __restrict__ dead, uint32_t* __restrict__ count, unsigned long long* __restrict__ stat,
+                                                                  int prio) {
   wave_prio(prio);
-  __shared__ uint32_t s_n[4][kScanBlock];
-  __shared__ unsigned long long s_b[kScanBlock];
-  __shared__ unsigned long long s_stat[SB_LIST];  // (the lists' sizes are the top kernel's)
-  const uint32_t tid = threadIdx.x;
+  __shared__ ScanPart s_base[kScanWaves];  // per wave: its share of the totals of the blocks before this one ...
+  __shared__ ScanPart s_w[kScanWaves];     // ... and what its own 64 units add
+  __shared__ unsigned long long s_stat[SB_LIST];  // (the lists' sizes are the last block's)
+  const uint32_t tid = threadIdx.x, wv = tid >> 6, L = tid & 63u;
   if (tid < SB_LIST) s_stat[tid] = 0;
+  ScanPart before{{0, 0, 0, 0}, 0};
+  for (uint32_t j = tid; j < blockIdx.x; j += kScanBlock) {
+    const ScanPart x = part[j];
+    for (int b = 0; b < 4; ++b) before.n[b] += x.n[b];
+    before.bytes += x.bytes;
+  }
+  for (int b = 0; b < 4; ++b) before.n[b] = s_wave_sum(before.n[b]);
+  before.bytes = s_wave_sum(before.bytes);
   const uint32_t i = blockIdx.x * kScanBlock + tid;
   const int K = i < n ? kc[i] : 0;
   PairDesc d{};
   unsigned long long words = 0, mine = 0;
   if (K) { d = cand[i]; mine = s_word_bytes(d, K, kind, &words); }
   const int bucket = K ? s_bucket(K, d, quads) : -1;
-  for (int b = 0; b < 4; ++b) s_n[b][tid] = bucket == b ? 1u : 0u;
-  s_b[tid] = mine;
+  const unsigned long long below = (1ull << L) - 1ull;
+  ScanPart w;
+  uint32_t rank = 0;  // pairs of my list in the lanes below me
+  for (int b = 0; b < 4; ++b) {
+    const unsigned long long bal = __ballot(bucket == b);
+    w.n[b] = (uint32_t)__popcll(bal);
+    if (bucket == b) rank = (uint32_t)__popcll(bal & below);
+  }
+  unsigned long long incl = mine;  // inclusive scan of the bytes over the wave
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long y = __shfl_up(incl, o, 64);
+    if (L >= (uint32_t)o) incl += y;
+  }
+  w.bytes = __shfl(incl, 63, 64);
+  if (L == 0) { s_base[wv] = before; s_w[wv] = w; }
   __syncthreads();
-  for (uint32_t dd = 1; dd < kScanBlock; dd <<= 1) {
-    uint32_t v[4] = {0, 0, 0, 0};
-    unsigned long long vb = 0;
-    if (tid >= dd) { for (int b = 0; b < 4; ++b) v[b] = s_n[b][tid - dd]; vb = s_b[tid - dd]; }
-    __syncthreads();
-    for (int b = 0; b < 4; ++b) s_n[b][tid] += v[b];
-    s_b[tid] += vb;
-    __syncthreads();
+  const ScanPart base = s_waves_before(s_base, kScanWaves), lower = s_waves_before(s_w, wv);
+  if (blockIdx.x == gridDim.x - 1 && tid == 0) {
+    const ScanPart all = s_waves_before(s_w, kScanWaves);
+    for (int b = 0; b < 4; ++b) {
+      count[b] = base.n[b] + all.n[b];
+      stat[SB_LIST + b] += base.n[b] + all.n[b];
+    }
   }
   if (K) {
-    const ScanPart base = part[blockIdx.x];
     const int b = bucket;
-    const uint32_t pos = base.n[b] + s_n[b][tid] - 1u;
-    const unsigned long long off = base.bytes + s_b[tid] - mine;
+    uint32_t pos = rank;  // (not base.n[b]: a record indexed by a variable moves to LDS, s_orient_early_kernel)
+    for (int k = 0; k < 4; ++k) pos += b == k ? base.n[k] + lower.n[k] : 0u;
+    const unsigned long long off = base.bytes + lower.bytes + incl - mine;
     idx[(size_t)b * n + pos] = i;  // (the list stays dense: a dropped pair keeps its slot as an empty one)
     if (off + mine > cap_bytes) {  // (never for kind 1)
       kc[i] = 0;
@@ -484,7 +485,11 @@ __global__ void s_align_final_plan_kernel(SParams p, int early, const SGeom* __r
     s_count(lc, SC_FINAL_BANDED);
     if (early) S.mark |= ST_COUNTED_FINAL;
   }
-  tr[t] = S;
+  // (not tr[t] = S: the fields this kernel only carries -- sc, sstar, ce -- then stay a 16-byte record per thread that the compiler
+  // keeps in LDS, 16 KB per workgroup of a kernel that declares 184 bytes: see s_orient_early_kernel)
+  tr[t].bw = S.bw;
+  tr[t].mark = S.mark;
+  tr[t].trim = S.trim;
   if (dd) dead[t] |= dd;
   });
 }
@@ -826,10 +831,9 @@ int band_stage(tracyhip_ctx* ctx, const tracyhip_params& p, StreamCommon& sc, ui
   const uint32_t nb = (n + kScanBlock - 1) / kScanBlock;
   const int quads = (!ctx->knobs.no_quads && b16_quad_lds(bl.code_cap) <= 64u * 1024u) ? 1 : 0;  // the narrow bands four lanes to a pair, where sixteen code rows fit
   const int prio = queued_prio(ctx, 2);
-  hipLaunchKernelGGL(s_scan_partial_kernel, dim3(nb), dim3(kScanBlock), 0, st, sc.cand, sc.kc, n, bl.kind, quads, sc.part, prio);
-  hipLaunchKernelGGL(s_scan_top_kernel, dim3(1), dim3(kScanTop), 0, st, sc.part, nb, count, sc.bstat + SB_COUNT * stage_no, prio);
+  hipLaunchKernelGGL(s_scan_count_kernel, dim3(nb), dim3(kScanBlock), 0, st, sc.cand, sc.kc, n, bl.kind, quads, sc.part, prio);
   hipLaunchKernelGGL(s_scan_place_kernel, dim3(nb), dim3(kScanBlock), 0, st, sc.cand, sc.kc, n, unit_mod, bl.kind, quads, (unsigned long long)cap_bytes, sc.part, sc.idx, sc.dead,
-                     sc.bstat + SB_COUNT * stage_no, prio);
+                     count, sc.bstat + SB_COUNT * stage_no, prio);
   HIP_TRY(hipGetLastError());
   Band16Args a{};
   a.prio = prio;
@@ -943,7 +947,9 @@ int queue_orientation(tracyhip_ctx* ctx, const tracyhip_params& p, const SParams
     {
       DpArgs af = a, apl = ap;
       launch_diag_periods(ctx, &p, h.classes[0].K, 0u, npre_all, true, af, apl);
-      if (launch_gotoh_ckpt_front(h.classes[0].K, af, 0u, apl, npre_all, fk.side[0]) != hipSuccess) rc = set_error(TRACYHIP_ERR_HIP, "prefix launch failed");
+      // (beside the other strands' full sweeps the device is full whatever this launch's depth: the shape with fewer instructions per cell)
+      const uint32_t tall_min = (os.exact && !ctx->knobs.no_prefix_tall_beside) ? 0u : ctx->knobs.prefix_tall_min;
+      if (launch_gotoh_ckpt_front(h.classes[0].K, af, 0u, apl, npre_all, fk.side[0], tall_min) != hipSuccess) rc = set_error(TRACYHIP_ERR_HIP, "prefix launch failed");
     }
     // What is queued on the side stream from here on raises its waves' priority as option chain_prio says (queued_prio): the waves of
     // the tiers and of the early tail are the youngest on SIMDs the sweeps keep busy, and a SIMD issues by priority, then by age.  The
@@ -970,7 +976,7 @@ int queue_orientation(tracyhip_ctx* ctx, const tracyhip_params& p, const SParams
         DpArgs apl = ap;
         launch_diag_periods(ctx, &p, c.K, 2 * (c.hi - c.lo), 0u, true, af, apl);
         TRY(timing_begin(ctx, TRACYHIP_TIMER_SCORE, 0, 0));
-        const hipError_t e = launch_gotoh_ckpt_front(c.K, af, 2 * (c.hi - c.lo), apl, 0u, st);
+        const hipError_t e = launch_gotoh_ckpt_front(c.K, af, 2 * (c.hi - c.lo), apl, 0u, st, ctx->knobs.prefix_tall_min);
         TRY(timing_end(ctx));
         HIP_TRY(e);
       }
@@ -987,7 +993,7 @@ int queue_orientation(tracyhip_ctx* ctx, const tracyhip_params& p, const SParams
       DpArgs apl = ap;
       launch_diag_periods(ctx, &p, c.K, 2 * (c.hi - c.lo), pre_done ? 0u : npre_all, true, af, apl);
       TRY(timing_begin(ctx, TRACYHIP_TIMER_SCORE, 0, 0));
-      HIP_TRY(launch_gotoh_ckpt_front(c.K, af, 2 * (c.hi - c.lo), apl, pre_done ? 0u : npre_all, st));
+      HIP_TRY(launch_gotoh_ckpt_front(c.K, af, 2 * (c.hi - c.lo), apl, pre_done ? 0u : npre_all, st, ctx->knobs.prefix_tall_min));
       TRY(timing_end(ctx));
       pre_done = true;
     }
@@ -2317,7 +2323,7 @@ struct DecStream : StreamCall {
       // (the side stream starts where the call's stream is NOW: allelicFraction begins with the prefixes, not with the fills and copies)
       if (af_pending) HIP_TRY(hipEventRecord(ctx->b16_fork.ready[0], st));
       TRY(timing_begin(ctx, TRACYHIP_TIMER_SCORE, 0, 0));
-      HIP_TRY(launch_gotoh_front_prefix_cq(a, 2 * nt, st));
+      HIP_TRY(launch_gotoh_front_prefix_cq(a, 2 * nt, st, ctx->knobs.prefix_tall_min));
       TRY(timing_end(ctx));
     }
     if (af_pending) TRY(give_up(queue_allelic_fraction()));
