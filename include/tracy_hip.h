@@ -726,6 +726,77 @@ int tracyhip_basecall_validate(const tracyhip_basecall_job* job, int mem, const 
  * job); host payloads are staged in chunks of about 256 MB of chromatogram, with a second synchronisation each for the copy back. */
 int tracyhip_basecall_traces(tracyhip_ctx* ctx, const tracyhip_basecall_job* job, int mem, const tracyhip_basecall_result* out);
 
+/* ---- gapped chromatograms: a batch of traces re-spaced along their alignment rows (the last step of `tracy align`, sage.h:321, and
+ * the per-trace output step of both assemble modes, assemble.h:352-368, 527-542) ------------------------------------------------
+ * Per trace t, in this order:
+ *   trimTrace(tr, bc, l, r, nbc)           trim.h:77-99, with trim_left_each / trim_right_each: the basecalls [l, bc_len - r) are kept,
+ *                                          the chromatogram is untouched
+ *   reverseComplementTrace                 trim.h:125-150 (letters trim.h:102-123), where reverse[t] != 0: sample x -> ns - 1 - x, channel
+ *                                          k -> 3 - k, the kept calls in reverse order with bcPos -> ns - 1 - bcPos; estQual travels with
+ *                                          its call (Trace::qual is not produced)
+ *   alignmentTracePadding(row, ...)        json.h:383-472 along the trace's own row of an alignment (only '-' against anything else is
+ *                                          read): every gap run between two letters inserts gap-many pseudo calls ('-', quality 0) of
+ *                                          `step` samples of -99 each; the runs at the ends are counted in leading_gaps / trailing_gaps
+ * Every field equals tracy_amd/host (assemble_out.hpp, sage_out.hpp alignmentTracePadding).  The device answers a trace when bc_len is in
+ * 1 .. 131071, nsamples in 1 .. 2^23, the positions (trimmed ones included) are strictly increasing inside [0, nsamples), l + r < bc_len,
+ * the row holds at most as many letters as calls are kept and the padded sizes stay below 2^31.  Any other trace is DEFERRED: status and
+ * zero sizes are written, nothing else, and the caller runs the host chain (the convention of tracyhip_basecall_traces).
+ * Rows are addressed by row_offset / row_len, so the rows of tracyhip_align_result::rows0 (ops_offset, ops_len), of
+ * tracyhip_alignment_rows and row r of group g of an assemble / de novo result (rows_offset[g] + r * ncol[g], ncol[g]) are taken as
+ * they stand. */
+#define TRACYHIP_PAD_OK 0
+#define TRACYHIP_PAD_DEFERRED 1
+#define TRACYHIP_PAD_TOO_SMALL 2 /* a capacity is too small: the sizes are reported, no payload is written */
+typedef struct {
+  uint32_t ntraces;
+  const void* signal;            /* payload, as tracyhip_basecall_job (may be NULL where the padded signal is not wanted) */
+  const uint64_t* signal_offset; /* HOST array, elements */
+  const uint32_t* nsamples;      /* HOST array */
+  uint32_t sample_bytes;         /* 4 or 2: of signal here and in the result */
+  const int32_t* bcpos;          /* payload, as tracyhip_basecall_result: trace t owns bc_len[t] entries from bc_offset[t] on */
+  const uint8_t *primary, *secondary, *consensus, *estqual; /* payload; each needed only where its result is wanted */
+  const uint64_t* bc_offset;     /* HOST array */
+  const uint32_t* bc_len;        /* HOST array */
+  const uint8_t* rows;           /* payload: the row of trace t is row_len[t] bytes from row_offset[t] on */
+  const uint64_t* row_offset;    /* HOST array */
+  const uint32_t* row_len;       /* HOST array */
+  const uint32_t *trim_left_each, *trim_right_each; /* HOST arrays, both or neither; NULL = no hard trim */
+  const uint8_t* reverse;        /* HOST array or NULL */
+} tracyhip_pad_job;
+/* The six per-trace arrays are HOST [ntraces] and required.  The payload results live where `mem` says and each may be NULL.  With all of
+ * them NULL the call is the sizes-only form: it needs no offsets or capacities, reads no chromatogram and fills the per-trace arrays
+ * (step depends on bcpos, which may live on the device only: this is how a caller sizes its buffers). */
+typedef struct {
+  int32_t* status;         /* TRACYHIP_PAD_* */
+  uint32_t* nsamples_out;  /* samples per channel of the padded trace */
+  uint32_t* ncalls_out;    /* calls and pseudo calls */
+  uint32_t* leading_gaps;
+  uint32_t* trailing_gaps;
+  uint32_t* step;          /* samples per pseudo call */
+  void* signal;            /* sample_bytes as the job; trace t: channel k at sample_offset[t] + k * nsamples_out[t] */
+  const uint64_t* sample_offset; /* HOST array, elements */
+  const uint32_t* sample_cap;    /* HOST array: samples per channel that trace t may take (4 * sample_cap[t] elements are its region) */
+  int32_t* bcpos;
+  uint8_t *primary, *secondary, *consensus, *estqual;
+  const uint64_t* call_offset;   /* HOST array */
+  const uint32_t* call_cap;      /* HOST array */
+} tracyhip_pad_result;
+/* what tracyhip_pad_traces refuses before it touches a device (none is needed here): NULL job / result / required arrays, mem,
+ * sample_bytes other than 2 or 4, misaligned signal / bcpos, one trim array without the other, a payload result without its offsets and
+ * capacities or without its input.  TRACYHIP_ERR_ARG (with the reason) otherwise TRACYHIP_OK. */
+int tracyhip_pad_validate(const tracyhip_pad_job* job, int mem, const tracyhip_pad_result* out);
+/* Device payloads: ONE host synchronisation per call.  Host payloads are staged in chunks of consecutive traces within the workspace
+ * limit (tracyhip_set_workspace_limit; 256 MB without one), with a second synchronisation each for the copy back of exactly what was
+ * reported. */
+int tracyhip_pad_traces(tracyhip_ctx* ctx, const tracyhip_pad_job* job, int mem, const tracyhip_pad_result* out);
+/* counters of the last tracyhip_pad_traces call of a context.  (A struct of their own: the layout of tracyhip_call_stats is pinned.) */
+typedef struct {
+  uint32_t pad_chunks;    /* chunks of traces the batch was cut into */
+  uint32_t pad_deferred;  /* traces with TRACYHIP_PAD_DEFERRED */
+  uint32_t pad_too_small; /* traces with TRACYHIP_PAD_TOO_SMALL */
+} tracyhip_pad_stats;
+int tracyhip_last_pad_stats(tracyhip_ctx* ctx, tracyhip_pad_stats* out);
+
 /* ---- reference-guided assembly (`tracy assemble -r`, assemble.h:219-288) for a batch of trace groups --------------------------
  * Group g owns the traces group_first[g] .. group_first[g + 1] - 1 (K of them) and the reference references[ref_index[g]].  Per group:
  *   1. the reverse complement of every trace (profile.h:74-90) and gotohScore(trace, reference), gotohScore(revcomp, reference)
@@ -866,6 +937,7 @@ int tracyhip_decompose_traces_async(tracyhip_ctx* ctx, const tracyhip_decompose_
 int tracyhip_consensus_traces_async(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tracyhip_params* prm, int mem,
                                     const tracyhip_consensus_result* out);
 int tracyhip_basecall_traces_async(tracyhip_ctx* ctx, const tracyhip_basecall_job* job, int mem, const tracyhip_basecall_result* out);
+int tracyhip_pad_traces_async(tracyhip_ctx* ctx, const tracyhip_pad_job* job, int mem, const tracyhip_pad_result* out);
 int tracyhip_assemble_traces_async(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem,
                                    const tracyhip_assemble_result* out);
 int tracyhip_denovo_traces_async(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip_params* prm, int mem,
@@ -932,7 +1004,7 @@ int tracyhip_pack_ragged(tracyhip_ctx* ctx, const void* src, uint64_t stride_byt
 #define TRACYHIP_TIMER_ORIGIN 5 /* origin-tracking sweeps (gotoh() whose alignment only trimReferenceSlice reads) */
 #define TRACYHIP_TIMER_DECOMP 6 /* decomposeAlleles kernel; cells = alignment columns, bytes = rows + basecalls + table */
 #define TRACYHIP_TIMER_AFRAC 7  /* allelicFraction kernel; cells = grid points x diffnuc bound, bytes = signal windows read */
-#define TRACYHIP_TIMER_MISC 8   /* findBreakpoint, findHomozygousBreakpoint, generateSecondaryDecomposed, alignment rows, trims */
+#define TRACYHIP_TIMER_MISC 8   /* findBreakpoint, findHomozygousBreakpoint, generateSecondaryDecomposed, alignment rows, trims, trace padding */
 #define TRACYHIP_TIMER_FRONT 9  /* pruned orientation sweep of `tracy align` (front.h): band placement, the band sweep below the prefix
                                    rows, certificate; cells = the band's, bytes = tables + codes + the kept row (read twice) */
 #define TRACYHIP_TIMER_COUNT 10

@@ -109,6 +109,12 @@ class CallStatsWildtype(CallStatsSeed):
     _fields_ = [("wt_chunks", C.c_uint32)]
 
 
+class PadStats(C.Structure):
+    """tracyhip_pad_stats: the counters of tracyhip_pad_traces.  Not a further CallStats subclass: tracyhip_call_stats keeps its layout,
+    which tests pin against the header; Context.last_call_stats reports both under one dict."""
+    _fields_ = [("pad_chunks", C.c_uint32), ("pad_deferred", C.c_uint32), ("pad_too_small", C.c_uint32)]
+
+
 def library_path():
     return os.path.join(_HERE, "lib", "libtracy_hip.so")
 
@@ -244,6 +250,9 @@ class Context:
                 out[name] = [list(row) for row in v]
                 continue
             out[name] = list(v) if hasattr(v, "__len__") else int(v)
+        ps = PadStats()  # (tracyhip_pad_traces counts in a struct of its own: tracyhip_last_pad_stats)
+        _check(lib().tracyhip_last_pad_stats(self._h, C.byref(ps)))
+        out.update({name: int(getattr(ps, name)) for name, _ in PadStats._fields_})
         return out
 
     # ---- host-buffer convenience wrappers (lists in, numpy out) -----------------------------------
@@ -1484,3 +1493,200 @@ def _basecall_traces(self, signals, positions, sigratio=0.33, trim_stringency=0,
 
 
 Context.basecall_traces = _basecall_traces
+
+
+# ---- gapped chromatograms along alignment rows on the device (tracyhip_pad_traces) -----------------------------------------------------
+PAD_OK, PAD_DEFERRED, PAD_TOO_SMALL = 0, 1, 2
+
+
+class PadJob(C.Structure):
+    _fields_ = [("ntraces", C.c_uint32), ("signal", C.c_void_p), ("signal_offset", C.POINTER(C.c_uint64)), ("nsamples", C.POINTER(C.c_uint32)),
+                ("sample_bytes", C.c_uint32), ("bcpos", C.c_void_p), ("primary", C.c_void_p), ("secondary", C.c_void_p), ("consensus", C.c_void_p),
+                ("estqual", C.c_void_p), ("bc_offset", C.POINTER(C.c_uint64)), ("bc_len", C.POINTER(C.c_uint32)), ("rows", C.c_void_p),
+                ("row_offset", C.POINTER(C.c_uint64)), ("row_len", C.POINTER(C.c_uint32)), ("trim_left_each", C.POINTER(C.c_uint32)),
+                ("trim_right_each", C.POINTER(C.c_uint32)), ("reverse", C.POINTER(C.c_uint8))]
+
+
+class PadResult(C.Structure):
+    _fields_ = [("status", C.POINTER(C.c_int32)), ("nsamples_out", C.POINTER(C.c_uint32)), ("ncalls_out", C.POINTER(C.c_uint32)),
+                ("leading_gaps", C.POINTER(C.c_uint32)), ("trailing_gaps", C.POINTER(C.c_uint32)), ("step", C.POINTER(C.c_uint32)),
+                ("signal", C.c_void_p), ("sample_offset", C.POINTER(C.c_uint64)), ("sample_cap", C.POINTER(C.c_uint32)), ("bcpos", C.c_void_p),
+                ("primary", C.c_void_p), ("secondary", C.c_void_p), ("consensus", C.c_void_p), ("estqual", C.c_void_p),
+                ("call_offset", C.POINTER(C.c_uint64)), ("call_cap", C.POINTER(C.c_uint32))]
+
+
+_PAD_BC = ("bcpos", "primary", "secondary", "consensus", "estqual")
+_PAD_META = ("nsamples_out", "ncalls_out", "leading_gaps", "trailing_gaps", "step")
+
+
+class PreparedPad:
+    """job / result structs of tracyhip_pad_traces.  signals: int32 or int16 [4][ns] per trace; bc: per trace a dict of bcpos, primary,
+    secondary, consensus, estqual; rows: the row of each trace as bytes, or (data, row_offset, row_len) with data a numpy array or a torch
+    tensor on the GPU holding rows of some alignment result as they stand.  device_bc: a PreparedBasecall(device=True) that has run -- its
+    chromatogram and basecall tensors are taken as they stand (signals and bc are then ignored).  With device=True (implied by device_bc)
+    the payloads are torch tensors on the GPU.  Everything the structs point to is kept alive by this object.
+
+    The result side starts as the sizes-only form; with_capacity() allocates the payload results."""
+
+    def __init__(self, signals, bc, rows, trim_left=None, trim_right=None, reverse=None, device=False, device_bc=None, sample_dtype=None):
+        self.device = device = bool(device or device_bc is not None)
+        self.device_bc = device_bc
+        f = self.flat = {}  # host copies in the layout of hostlib.pad_batch (of a device_bc: fetched when a deferred trace needs them)
+        if device_bc is not None:
+            nt = self.nt = device_bc.nt
+            self.sample_dtype = device_bc.sample_dtype
+            f.update(sig_off=device_bc.sig_off, nsamples=device_bc.nsamples, bc_off=device_bc.pos_off, bc_len=device_bc.meta["bc_len"])
+            self.d = dict(signal=device_bc.d_signal, **{k: device_bc.payload[k] for k in _PAD_BC})
+        else:
+            nt = self.nt = len(signals)
+            if sample_dtype is None:
+                sample_dtype = np.int16 if nt and all(np.asarray(s).dtype == np.int16 for s in signals) else np.int32
+            self.sample_dtype = np.dtype(sample_dtype)
+            f["nsamples"] = np.array([np.asarray(s).shape[1] for s in signals] + [0], dtype=np.uint32)
+            f["bc_len"] = np.array([len(b["bcpos"]) for b in bc] + [0], dtype=np.uint32)
+            f["sig_off"] = np.zeros(nt + 1, np.uint64)
+            f["bc_off"] = np.zeros(nt + 1, np.uint64)
+            f["sig_off"][1:] = np.cumsum(4 * f["nsamples"][:nt].astype(np.uint64))
+            f["bc_off"][1:] = np.cumsum(f["bc_len"][:nt].astype(np.uint64))
+            f["signal"] = np.concatenate([np.ascontiguousarray(s, dtype=self.sample_dtype).reshape(-1) for s in signals] + [np.zeros(1, self.sample_dtype)])
+            f["bcpos"] = np.concatenate([np.ascontiguousarray(b["bcpos"], dtype=np.int32).reshape(-1) for b in bc] + [np.zeros(1, np.int32)])
+            for k in _PAD_BC[1:]:
+                f[k] = np.concatenate([np.frombuffer(bytes(b[k]), np.uint8) if isinstance(b[k], (bytes, bytearray))
+                                       else np.ascontiguousarray(b[k], dtype=np.uint8).reshape(-1) for b in bc] + [np.zeros(1, np.uint8)])
+        f["nt"] = nt
+        if isinstance(rows, tuple):
+            data, roff, rlen = rows
+            f["row_off"] = np.append(np.ascontiguousarray(roff, dtype=np.uint64)[:nt], np.uint64(0))
+            f["row_len"] = np.append(np.ascontiguousarray(rlen, dtype=np.uint32)[:nt], np.uint32(0))
+            self._rows_in = data
+            if isinstance(data, np.ndarray):
+                f["rows"] = np.ascontiguousarray(data, dtype=np.uint8)
+        else:
+            f["row_len"] = np.array([len(r) for r in rows] + [0], dtype=np.uint32)
+            f["row_off"] = np.zeros(nt + 1, np.uint64)
+            f["row_off"][1:] = np.cumsum(f["row_len"][:nt].astype(np.uint64))
+            f["rows"] = np.frombuffer(b"".join(bytes(r) for r in rows) + b"\0", np.uint8).copy()
+            self._rows_in = f["rows"]
+        if (trim_left is None) != (trim_right is None):
+            raise ValueError("trim_left and trim_right go together: both or neither")
+        if trim_left is not None:
+            f["trim_l"] = np.append(np.ascontiguousarray(trim_left, dtype=np.uint32)[:nt], np.uint32(0))
+            f["trim_r"] = np.append(np.ascontiguousarray(trim_right, dtype=np.uint32)[:nt], np.uint32(0))
+        if reverse is not None:
+            f["reverse"] = np.append(np.array([1 if x else 0 for x in reverse], dtype=np.uint8)[:nt], np.uint8(0))
+        if device:
+            import torch
+            if device_bc is None:
+                self.d = {k: torch.from_numpy(f[k]).cuda() for k in ("signal",) + _PAD_BC}
+            self.d["rows"] = self._rows_in if not isinstance(self._rows_in, np.ndarray) else torch.from_numpy(f["rows"]).cuda()
+            torch.cuda.synchronize()
+            ptr = lambda k: self.d[k].data_ptr()
+        else:
+            if not isinstance(self._rows_in, np.ndarray):
+                raise ValueError("rows on the device need device=True")
+            ptr = lambda k: f[k].ctypes.data
+        job = self.job = PadJob()
+        job.ntraces = nt
+        job.signal, job.sample_bytes = ptr("signal"), self.sample_dtype.itemsize
+        job.signal_offset, job.nsamples = _u64p(f["sig_off"]), _u32p(f["nsamples"])
+        for k in _PAD_BC:
+            setattr(job, k, ptr(k))
+        job.bc_offset, job.bc_len = _u64p(f["bc_off"]), _u32p(f["bc_len"])
+        job.rows, job.row_offset, job.row_len = ptr("rows"), _u64p(f["row_off"]), _u32p(f["row_len"])
+        if trim_left is not None:
+            job.trim_left_each, job.trim_right_each = _u32p(f["trim_l"]), _u32p(f["trim_r"])
+        if reverse is not None:
+            job.reverse = f["reverse"].ctypes.data_as(C.POINTER(C.c_uint8))
+        self.mem = MEM_DEVICE if device else MEM_HOST
+        self.o = None
+        self._bind(None)
+
+    def _bind(self, o):
+        """the result struct over the arrays of `o` (hostlib.pad_alloc layout; None: the sizes-only form)"""
+        self.meta = {k: np.zeros(max(self.nt, 1), np.uint32) for k in _PAD_META}
+        self.meta["status"] = np.zeros(max(self.nt, 1), np.int32)
+        out = self.out = PadResult()
+        out.status = self.meta["status"].ctypes.data_as(C.POINTER(C.c_int32))
+        for k in _PAD_META:
+            setattr(out, k, _u32p(self.meta[k]))
+        self.o = o
+        if o is None:
+            return
+        out.sample_offset, out.sample_cap = _u64p(o["sample_offset"]), _u32p(o["sample_cap"])
+        out.call_offset, out.call_cap = _u64p(o["call_offset"]), _u32p(o["call_cap"])
+        for k in ("signal",) + _PAD_BC:
+            setattr(out, k, o[k].data_ptr() if self.device else o[k].ctypes.data)
+
+    def sizes(self, ctx):
+        """the sizes-only call: (nsamples_out, ncalls_out) per trace, 0 for deferred traces"""
+        self._bind(None)
+        _check(lib().tracyhip_pad_traces(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
+        return self.meta["nsamples_out"][:self.nt].copy(), self.meta["ncalls_out"][:self.nt].copy()
+
+    def with_capacity(self, sample_cap, call_cap, fill=None):
+        """payload results with room for sample_cap[t] samples per channel and call_cap[t] calls of trace t (fill: a value every payload
+        element starts with, for tests that check what a call leaves untouched)"""
+        from . import hostlib
+        o = hostlib.pad_alloc(dict(nt=self.nt, signal=np.zeros(0, self.sample_dtype)), sample_cap, call_cap)
+        if fill is not None:
+            for k in ("signal",) + _PAD_BC:
+                o[k][:] = fill
+        if self.device:
+            import torch
+            for k in ("signal",) + _PAD_BC:
+                o[k] = torch.from_numpy(o[k]).cuda()
+            torch.cuda.synchronize()
+        self._bind(o)
+        return self
+
+    def run(self, ctx, asynchronous=False):
+        fn = lib().tracyhip_pad_traces_async if asynchronous else lib().tracyhip_pad_traces
+        _check(fn(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
+        return self
+
+    def host_arrays(self):
+        """the result arrays on the host in the layout of hostlib.pad_alloc (device payloads are copied back)"""
+        o = dict(self.o)
+        if self.device:
+            for k in ("signal",) + _PAD_BC:
+                o[k] = o[k].cpu().numpy()
+        o.update(self.meta)
+        return o
+
+    def host_flat(self):
+        """the inputs on the host in the layout of hostlib.pad_batch"""
+        f = dict(self.flat)
+        for k in ("signal",) + _PAD_BC + ("rows",):
+            if k not in f:
+                f[k] = self.d[k].cpu().numpy()
+        return f
+
+    def results(self, fill_deferred=True):
+        """per trace: dict(status, signal [4][ns'], bcPos, primary, secondary, consensus, estQual, leadingGaps, trailingGaps, step).  Deferred
+        traces are filled in by the host chain (hostlib.pad_batch), except those the reference's loops cannot run either (`unreadable`:
+        status stays DEFERRED)"""
+        from . import hostlib
+        o = self.host_arrays()
+        res = [hostlib.pad_unpack(o, t) for t in range(self.nt)]
+        sel = np.array([t for t in range(self.nt) if res[t]["status"] == PAD_DEFERRED], dtype=np.int64)
+        if fill_deferred and len(sel):
+            f = self.host_flat()
+            sub = dict(f, nt=len(sel))
+            for k in ("sig_off", "nsamples", "bc_off", "bc_len", "row_off", "row_len", "trim_l", "trim_r", "reverse"):
+                if k in f:
+                    sub[k] = np.append(f[k][sel], f[k].dtype.type(0))
+            for t, r in zip(sel, hostlib.pad_batch(sub)):
+                res[t] = r if r["status"] == 0 else dict(res[t], unreadable=True)
+        return res
+
+
+def _pad_traces(self, signals, bc, rows, trim_left=None, trim_right=None, reverse=None, device=False, device_bc=None, asynchronous=False):
+    """tracyhip_pad_traces: the sizes-only call, buffers of exactly those sizes, the call.  device=False: host buffers, returns the
+    per-trace results (PreparedPad.results).  device=True or device_bc: returns the PreparedPad holding torch tensors on the GPU.
+    asynchronous: the second call is queued (tracyhip_pad_traces_async); results are final after Context.synchronize()."""
+    p = PreparedPad(signals, bc, rows, trim_left, trim_right, reverse, device, device_bc)
+    p.with_capacity(*p.sizes(self)).run(self, asynchronous)
+    return p if (p.device or asynchronous) else p.results()
+
+
+Context.pad_traces = _pad_traces

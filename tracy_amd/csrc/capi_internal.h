@@ -188,7 +188,12 @@ enum CtxDev : int {
   WB_OFF = CB_OFF,       // offsets of the op strings / rows, uploaded
   WB_PAIR = CB_PAIR,     // per-trace results staged for a host caller (and score_prelim where the caller wants none)
   WB_PAY = CB_PAY,       // ops / rows0 / rows1 staged for a host caller
-  DB_COUNT = WB_ORIENTED + 1
+  // ---- tracyhip_pad_traces (pad.hip) ----
+  PD_TRACES = WB_ORIENTED + 1,  // PadTrace per trace up, PadOut per trace back
+  PD_SCRATCH,   // the insert lists of pad_kernel, one region per trace of a chunk
+  PD_IN,        // a host caller's chromatograms, basecall arrays and rows of a chunk, staged in
+  PD_OUT,       // padded chromatograms and basecall arrays of a chunk staged for a host caller
+  DB_COUNT = PD_OUT + 1
 };
 static_assert(DN_CNT + 1 == VB_DESC && VB_PACK_TEXT + 1 == WB_ORIENTED && DN_PAY < DB_COUNT && WB_PAY < DB_COUNT,
               "an alias does not advance the count: every slot of its own comes after the aliases");
@@ -334,6 +339,7 @@ struct tracyhip_ctx {
   bool timing = false;
   tracyhip::CtxKnobs knobs;  // (the fields below it used to be: no_narrow, no_compact, no_screen)
   tracyhip_call_stats stats = {};  // tiers of the last pipeline call (tracyhip_last_call_stats)
+  tracyhip_pad_stats pad_stats = {};  // of the last tracyhip_pad_traces call (tracyhip_last_pad_stats)
   std::vector<Pending> pending;
   std::vector<hipEvent_t> free_events;
   tracyhip_kernel_timing acc[TRACYHIP_TIMER_COUNT] = {};

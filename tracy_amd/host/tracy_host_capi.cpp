@@ -7,6 +7,7 @@
 #include <thread>
 #include <vector>
 
+#include "assemble_out.hpp"
 #include "bcf_out.hpp"
 #include "indigo_out.hpp"
 #include "sage_out.hpp"
@@ -736,6 +737,94 @@ int tracyhost_call_variants_batch(uint32_t n, const uint8_t* rows0, const uint8_
           r += 8;
         }
         var_n[t] = (uint32_t)var.size();
+      }
+    });
+  for (auto& t : th) t.join();
+  return 0;
+}
+
+// ---- the gapped chromatograms of a batch as the command line produces them, one trace after the other per thread: trimTrace(tr, bc, l,
+// r, nbc), reverseComplementTrace, alignmentTracePadding (assemble_out.hpp, sage_out.hpp) over the flattened arrays of
+// tracyhip_pad_traces (the fallback for its deferred traces; tools/pad_device_line.py times it beside the device call) ----
+// status: 0 answered; 1 refused -- the reference's loops stall or read outside their arrays (no call, a position outside [0, nsamples)
+// or not above its neighbour, trims that leave no call, more letters in the row than calls kept); 2 a capacity is too small (sizes
+// reported).  Payload results may be null (all null: sizes only); trim_l / trim_r / reverse may be null.
+int tracyhost_pad_batch(uint32_t n, const void* signal, const uint64_t* signal_offset, const uint32_t* nsamples, uint32_t sample_bytes,
+                        const int32_t* bcpos, const uint8_t* primary, const uint8_t* secondary, const uint8_t* consensus, const uint8_t* estqual,
+                        const uint64_t* bc_offset, const uint32_t* bc_len, const uint8_t* rows, const uint64_t* row_offset, const uint32_t* row_len,
+                        const uint32_t* trim_l, const uint32_t* trim_r, const uint8_t* reverse, int32_t* status, uint32_t* nsamples_out,
+                        uint32_t* ncalls_out, uint32_t* leading, uint32_t* trailing, uint32_t* step, void* o_signal, const uint64_t* sample_offset,
+                        const uint32_t* sample_cap, int32_t* o_bcpos, uint8_t* o_primary, uint8_t* o_secondary, uint8_t* o_consensus, uint8_t* o_estqual,
+                        const uint64_t* call_offset, const uint32_t* call_cap, uint32_t nthreads) {
+  const bool want_calls = o_bcpos || o_primary || o_secondary || o_consensus || o_estqual;
+  if (n && (!signal || !signal_offset || !nsamples || !bcpos || !primary || !secondary || !consensus || !estqual || !bc_offset || !bc_len || !rows ||
+            !row_offset || !row_len || !status || !nsamples_out || !ncalls_out || !leading || !trailing || !step))
+    return -1;
+  if ((sample_bytes != 2 && sample_bytes != 4) || (o_signal && (!sample_offset || !sample_cap)) || (want_calls && (!call_offset || !call_cap))) return -1;
+  if (nthreads == 0) nthreads = tracy_amd::usable_threads();
+  std::vector<std::thread> th;
+  for (uint32_t w = 0; w < nthreads; ++w)
+    th.emplace_back([=]() {
+      for (uint32_t t = (uint32_t)((uint64_t)n * w / nthreads); t < (uint32_t)((uint64_t)n * (w + 1) / nthreads); ++t) {
+        const uint32_t ns = nsamples[t], nc = bc_len[t], l = trim_l ? trim_l[t] : 0, r = trim_r ? trim_r[t] : 0;
+        const int32_t* pos = bcpos + bc_offset[t];
+        status[t] = 1;
+        nsamples_out[t] = ncalls_out[t] = 0;
+        bool ok = nc >= 1 && ns >= 1 && (uint64_t)l + r < nc;
+        for (uint32_t i = 0; ok && i < nc; ++i) ok = pos[i] >= 0 && (uint32_t)pos[i] < ns && (i == 0 || pos[i] > pos[i - 1]);
+        const std::string row(reinterpret_cast<const char*>(rows) + row_offset[t], row_len[t]);
+        if (ok) ok = (uint64_t)(row.size() - (std::size_t)std::count(row.begin(), row.end(), '-')) <= (uint64_t)(nc - l - r);
+        if (!ok) continue;
+        Trace tr;
+        BaseCalls bc;
+        tr.traceACGT.resize(4);
+        for (int k = 0; k < 4; ++k) {
+          tr.traceACGT[k].resize(ns);
+          const uint64_t at = signal_offset[t] + (uint64_t)k * ns;
+          if (sample_bytes == 4) std::memcpy(tr.traceACGT[k].data(), static_cast<const int32_t*>(signal) + at, 4ull * ns);
+          else
+            for (uint32_t x = 0; x < ns; ++x) tr.traceACGT[k][x] = static_cast<const int16_t*>(signal)[at + x];
+        }
+        bc.bcPos.assign(pos, pos + nc);
+        bc.primary.assign(reinterpret_cast<const char*>(primary) + bc_offset[t], nc);
+        bc.secondary.assign(reinterpret_cast<const char*>(secondary) + bc_offset[t], nc);
+        bc.consensus.assign(reinterpret_cast<const char*>(consensus) + bc_offset[t], nc);
+        bc.estQual.assign(estqual + bc_offset[t], estqual + bc_offset[t] + nc);
+        BaseCalls nbc;
+        trimTrace(tr, bc, l, r, nbc);
+        PaddedTrace padded;
+        Trace ttr;
+        BaseCalls tbc;
+        const bool rev = reverse && reverse[t];
+        if (rev) reverseComplementTrace(tr, nbc, ttr, tbc);
+        BaseCalls const& used = rev ? tbc : nbc;
+        alignmentTracePadding(row, rev ? ttr : tr, used, padded);
+        const uint32_t nso = (uint32_t)padded.tr.traceACGT[0].size(), nco = (uint32_t)padded.bc.bcPos.size();
+        nsamples_out[t] = nso; ncalls_out[t] = nco;
+        leading[t] = padded.leadingGaps; trailing[t] = padded.trailingGaps;
+        step[t] = 6;  // as alignmentTracePadding computes it (json.h:386-392)
+        if (used.bcPos.size() > 1) {
+          double avg = 0;
+          for (uint32_t i = 1; i < used.bcPos.size(); ++i) avg += (used.bcPos[i] - used.bcPos[i - 1]);
+          avg /= (used.bcPos.size() - 1);
+          step[t] = (uint32_t)avg;
+        }
+        if ((o_signal && nso > sample_cap[t]) || (want_calls && nco > call_cap[t])) { status[t] = 2; continue; }
+        status[t] = 0;
+        if (o_signal)
+          for (int k = 0; k < 4; ++k) {
+            const uint64_t at = sample_offset[t] + (uint64_t)k * nso;
+            if (sample_bytes == 4) std::memcpy(static_cast<int32_t*>(o_signal) + at, padded.tr.traceACGT[k].data(), 4ull * nso);
+            else
+              for (uint32_t x = 0; x < nso; ++x) static_cast<int16_t*>(o_signal)[at + x] = (int16_t)padded.tr.traceACGT[k][x];
+          }
+        if (!want_calls) continue;
+        const uint64_t co = call_offset[t];
+        if (o_bcpos) std::memcpy(o_bcpos + co, padded.bc.bcPos.data(), 4ull * nco);
+        if (o_primary) std::memcpy(o_primary + co, padded.bc.primary.data(), nco);
+        if (o_secondary) std::memcpy(o_secondary + co, padded.bc.secondary.data(), nco);
+        if (o_consensus) std::memcpy(o_consensus + co, padded.bc.consensus.data(), nco);
+        if (o_estqual) std::memcpy(o_estqual + co, padded.bc.estQual.data(), nco);
       }
     });
   for (auto& t : th) t.join();

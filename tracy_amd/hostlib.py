@@ -555,3 +555,64 @@ class DeviceGenome:
         else:
             out["slices"] = [o["slices_2d"][i, :out["slice_len"][i]].tobytes() for i in range(n)]
         return out
+
+
+# ---- gapped chromatograms on the host (tracyhost_pad_batch): the fallback and the baseline of tracyhip_pad_traces ------------------------
+PAD_KINDS = (("signal", None), ("bcpos", np.int32), ("primary", np.uint8), ("secondary", np.uint8), ("consensus", np.uint8), ("estqual", np.uint8))
+
+
+def pad_alloc(flat, nsamples_out, ncalls_out):
+    """result arrays of a padding call sized by the per-trace sizes (samples per channel, calls): dict with the six per-trace arrays, the
+    payload arrays and their offsets / capacities"""
+    nt = flat["nt"]
+    scap = np.ascontiguousarray(nsamples_out, dtype=np.uint32)[:nt].copy() if nt else np.zeros(0, np.uint32)
+    ccap = np.ascontiguousarray(ncalls_out, dtype=np.uint32)[:nt].copy() if nt else np.zeros(0, np.uint32)
+    o = dict(sample_cap=np.append(scap, np.uint32(0)), call_cap=np.append(ccap, np.uint32(0)))
+    o["sample_offset"] = np.zeros(nt + 1, np.uint64)
+    o["call_offset"] = np.zeros(nt + 1, np.uint64)
+    o["sample_offset"][1:] = np.cumsum(4 * scap.astype(np.uint64))
+    o["call_offset"][1:] = np.cumsum(ccap.astype(np.uint64))
+    o["signal"] = np.zeros(max(int(o["sample_offset"][nt]), 1), flat["signal"].dtype)
+    for k, dt in PAD_KINDS[1:]:
+        o[k] = np.zeros(max(int(o["call_offset"][nt]), 1), dt)
+    o["status"] = np.zeros(max(nt, 1), np.int32)
+    for k in ("nsamples_out", "ncalls_out", "leading_gaps", "trailing_gaps", "step"):
+        o[k] = np.zeros(max(nt, 1), np.uint32)
+    return o
+
+
+def pad_batch_raw(flat, out, nthreads=0, sizes_only=False):
+    """one tracyhost_pad_batch call over the flattened arrays of a PreparedPad (capi.py) into `out` (pad_alloc)"""
+    p = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+    pay = (lambda k: None) if sizes_only else (lambda k: p(out[k]))
+    rc = lib().tracyhost_pad_batch(C.c_uint32(flat["nt"]), p(flat["signal"]), p(flat["sig_off"]), p(flat["nsamples"]), C.c_uint32(flat["signal"].dtype.itemsize),
+                                   p(flat["bcpos"]), p(flat["primary"]), p(flat["secondary"]), p(flat["consensus"]), p(flat["estqual"]),
+                                   p(flat["bc_off"]), p(flat["bc_len"]), p(flat["rows"]), p(flat["row_off"]), p(flat["row_len"]),
+                                   p(flat.get("trim_l")), p(flat.get("trim_r")), p(flat.get("reverse")), p(out["status"]), p(out["nsamples_out"]),
+                                   p(out["ncalls_out"]), p(out["leading_gaps"]), p(out["trailing_gaps"]), p(out["step"]), pay("signal"),
+                                   p(out["sample_offset"]), p(out["sample_cap"]), pay("bcpos"), pay("primary"), pay("secondary"), pay("consensus"),
+                                   pay("estqual"), p(out["call_offset"]), p(out["call_cap"]), C.c_uint32(nthreads))
+    if rc != 0:
+        raise ValueError("tracyhost_pad_batch: bad arguments")
+    return out
+
+
+def pad_unpack(out, t):
+    """trace t of a finished padding call (pad_alloc layout, host arrays) as the dict the tests compare"""
+    st, nso, nco = int(out["status"][t]), int(out["nsamples_out"][t]), int(out["ncalls_out"][t])
+    r = dict(status=st, nsamples_out=nso, ncalls_out=nco)
+    if st != 0:
+        return r
+    so, co = int(out["sample_offset"][t]), int(out["call_offset"][t])
+    r.update(signal=out["signal"][so:so + 4 * nso].reshape(4, nso), bcPos=out["bcpos"][co:co + nco], primary=out["primary"][co:co + nco].tobytes(),
+             secondary=out["secondary"][co:co + nco].tobytes(), consensus=out["consensus"][co:co + nco].tobytes(), estQual=out["estqual"][co:co + nco],
+             leadingGaps=int(out["leading_gaps"][t]), trailingGaps=int(out["trailing_gaps"][t]), step=int(out["step"][t]))
+    return r
+
+
+def pad_batch(flat, nthreads=0):
+    """trim, reverse and pad a batch on host threads: a sizes-only call, buffers of exactly those sizes, the call; per-trace dicts (status 1:
+    the reference's loops cannot run the trace)"""
+    sizes = pad_batch_raw(flat, pad_alloc(flat, np.zeros(flat["nt"], np.uint32), np.zeros(flat["nt"], np.uint32)), nthreads, sizes_only=True)
+    out = pad_batch_raw(flat, pad_alloc(flat, sizes["nsamples_out"], sizes["ncalls_out"]), nthreads)
+    return [pad_unpack(out, t) for t in range(flat["nt"])]
