@@ -208,6 +208,15 @@ def with_n_row(rng, p, every=7):
     return p
 
 
+def with_gap_row(rng, p, every=11):
+    """half of every `every`-th column moved to row 5 (gap): column sums stay 1"""
+    p = p.copy()
+    cols = np.arange(int(rng.integers(0, every)), p.shape[1], every)
+    p[:5, cols] *= np.float32(0.5)
+    p[5, cols] = np.float32(0.5)
+    return p
+
+
 def make_runs(seed=913):
     import pyoracle as orc
     rng = np.random.default_rng(seed)
