@@ -723,7 +723,10 @@ typedef struct {
  * TRACYHIP_ERR_ARG (with the reason) otherwise TRACYHIP_OK. */
 int tracyhip_basecall_validate(const tracyhip_basecall_job* job, int mem, const tracyhip_basecall_result* out);
 /* One launch and ONE host synchronisation per call with device payloads (bc_len is metadata the caller needs on the host to build the next
- * job); host payloads are staged in chunks of about 256 MB of chromatogram, with a second synchronisation each for the copy back. */
+ * job); host payloads are staged in chunks of consecutive traces whose chromatogram fits the workspace limit (tracyhip_set_workspace_limit;
+ * 256 MB without one), with a second synchronisation each for the copy back; the results are the same for any limit.  A trace whose
+ * signal_offset + 4 * nsamples or pos_offset + npos leaves 64 bits is refused with TRACYHIP_ERR_RANGE (the error names the trace) before
+ * the first launch: nothing is written. */
 int tracyhip_basecall_traces(tracyhip_ctx* ctx, const tracyhip_basecall_job* job, int mem, const tracyhip_basecall_result* out);
 
 /* ---- gapped chromatograms: a batch of traces re-spaced along their alignment rows (the last step of `tracy align`, sage.h:321, and

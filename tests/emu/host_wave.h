@@ -1,6 +1,7 @@
 // host_wave.h -- the 64-lane host "wave" of the emulators (TEST INFRASTRUCTURE ONLY): one fiber (ucontext) per lane on ONE thread,
 // every cross-lane operation a barrier at which the lane yields to the next one.  Lanes run round-robin from barrier to barrier: all
 // lanes of a wave pass the same sequence of barriers, which is all a barrier promises.
+// What each member of HostWave must mean is listed at the top of tracy_amd/csrc/dev_wave.h.
 #ifndef TRACY_AMD_TESTS_HOST_WAVE_H
 #define TRACY_AMD_TESTS_HOST_WAVE_H
 #include <ucontext.h>

@@ -157,3 +157,19 @@ def test_argument_validation_needs_no_device():
     job, res, keep = _job()  # an empty batch is fine
     job.ntraces = 0
     assert lib.tracyhip_basecall_validate(C.byref(job), 0, C.byref(res)) == 0
+
+
+# ---- basecall_plan.h and ragged_plan.h (chunk cut, descriptors, checks, run-merger) as a program of its own, plain and under the sanitizers ----
+
+PLAN_FLAGS = {"plain": ["-O2"], "sanitized": ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]}
+
+
+@pytest.mark.parametrize("build", sorted(PLAN_FLAGS))
+def test_basecall_plan_program(tmp_path, build):
+    exe = tmp_path / ("basecall_plan_" + build)
+    # (-Wno-unknown-pragmas: the headers of the wave body, which the plan shares its descriptors with, carry `#pragma unroll` for hipcc)
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-Wno-unknown-pragmas"] + PLAN_FLAGS[build] + ["-o", str(exe), os.path.join(ROOT, "tests", "cpp", "basecall_plan.cpp")],
+                   check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "basecall_plan: ok" in r.stdout

@@ -99,6 +99,61 @@ def test_untouched_outside_the_results_and_optional_payloads(ctx, batch):
             assert np.array_equal(q.payload[k][a:b].view(np.uint8), p.payload[k][a:b].view(np.uint8)), (batch[t][0], k)  # (bits: a profile may hold NaN)
 
 
+def _prefilled(items, int16):
+    from tracy_amd import capi
+    p = capi.PreparedBasecall([s.astype(np.int16) if int16 else s for _, s, _, _ in items], [q for _, _, q, _ in items], 0.33, 4)
+    for v in p.payload.values():
+        v.view(np.uint8)[:] = 0x7e
+    return p
+
+
+@pytest.mark.parametrize("int16", [False, True])
+def test_chunked_run_equals_the_unlimited_run(ctx, batch, want_cache, int16):
+    """host payloads under a workspace limit of a quarter of the staged chromatogram: four chunks or more, every byte as without a limit"""
+    from tracy_amd import capi
+    items = batch[:40]
+    assert any(d for _, _, _, d in items[1:-1])  # deferred traces between answered ones
+    syncs = lambda: ctx.last_call_stats()["host_syncs"]
+    whole = _prefilled(items, int16)
+    s0 = syncs()
+    whole.run(ctx)
+    assert syncs() - s0 == 2  # one chunk: the results, the copy back
+    check(whole, items, 0.33, 4, want_cache)
+    cut = _prefilled(items, int16)
+    staged = int((4 * cut.nsamples[:cut.nt].astype(np.uint64)).sum()) * cut.job.sample_bytes
+    try:
+        ctx.set_workspace_limit(staged // 4)
+        s0 = syncs()
+        cut.run(ctx)
+        nsync = syncs() - s0
+    finally:
+        ctx.set_workspace_limit(0)
+    assert nsync >= 8 and nsync % 2 == 0, nsync  # two per chunk
+    check(cut, items, 0.33, 4, want_cache)
+    for k in ("status", "bc_len", "trim_left", "trim_right", "best_section"):
+        assert np.array_equal(cut.meta[k], whole.meta[k]), k
+    for k, _, w in capi._BC_PAYLOADS:
+        assert np.array_equal(cut.payload[k].view(np.uint8), whole.payload[k].view(np.uint8)), k
+        for t in range(cut.nt):
+            o, n, cap = int(cut.pos_off[t]), int(cut.meta["bc_len"][t]), int(cut.npos[t])
+            assert (cut.payload[k][w * (o + n):w * (o + cap)].view(np.uint8) == 0x7e).all(), (items[t][0], k)
+
+
+def test_an_offset_that_leaves_64_bits_is_refused(ctx, batch):
+    from tracy_amd import capi
+    import ctypes as C
+    p = _prefilled(batch[:40], False)
+    for v in p.meta.values():
+        v[:] = 77
+    p.pos_off[6] = 2**64 - 8
+    rc = capi.lib().tracyhip_basecall_traces(ctx._h, C.byref(p.job), p.mem, C.byref(p.out))
+    assert rc == capi.ERR_RANGE
+    for k, v in p.meta.items():
+        assert (v == 77).all(), k
+    for k, v in p.payload.items():
+        assert (v.view(np.uint8) == 0x7e).all(), k
+
+
 def test_context_method_fills_deferred_traces_from_the_host(ctx, batch):
     from tracy_amd import hostlib
     items = batch[:40]

@@ -4,19 +4,17 @@
 
 #include "band16.h"
 #include "band16_launch.h"
+#include "dev_wave.h"
 #include "front.h"
 
 namespace tracyhip {
 
-struct DeviceWave16 {
-  __device__ __forceinline__ uint32_t lane() const { return threadIdx.x; }
+struct DeviceWave16 : DevWaveOps<true> {
   // lane j of a row of 16 <- lane j - 1 of the same row, lane 0 <- lane 15 (row_ror:1)
   __device__ __forceinline__ int32_t rot16(int32_t x) const { return __builtin_amdgcn_update_dpp(0, x, 0x121, 0xf, 0xf, false); }
   __device__ __forceinline__ int32_t rot(int32_t x, std::integral_constant<int, 16>) const { return rot16(x); }
   // lane j of a quad <- lane j - 1 of the same quad, lane 0 <- lane 3 (quad_perm:[3,0,1,2])
   __device__ __forceinline__ int32_t rot(int32_t x, std::integral_constant<int, 4>) const { return __builtin_amdgcn_update_dpp(0, x, 0x93, 0xf, 0xf, false); }
-  __device__ __forceinline__ uint64_t ballot(bool p) const { return __ballot(p); }
-  __device__ __forceinline__ uint32_t bcast(uint32_t x, uint32_t src_lane) const { return (uint32_t)__shfl((int)x, (int)src_lane, 64); }
   __device__ __forceinline__ void sync() const { __syncthreads(); }
   __device__ __forceinline__ void sync_global() const {  // words written by lanes of this wave, read by others of it (dp_kernels.hip)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");

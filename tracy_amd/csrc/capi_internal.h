@@ -424,6 +424,17 @@ int timing_collect(tracyhip_ctx* ctx);                                          
 int ctx_begin(tracyhip_ctx* ctx);
 // hipStreamSynchronize(ctx->stream), counted in tracyhip_call_stats::host_syncs
 inline hipError_t ctx_sync(tracyhip_ctx* ctx) { ctx->stats.host_syncs += 1; return hipStreamSynchronize(ctx->stream); }
+// what a RunMerger (ragged_plan.h) does with a finished run on the device side: array k's bytes from its part of a staging buffer
+// into the caller's array, queued on the context's stream
+template <int N>
+struct CopyBackRun {
+  tracyhip_ctx* ctx;
+  const uint8_t* src[N];
+  uint8_t* dst[N];
+  hipError_t operator()(int k, uint64_t s, uint64_t d, uint64_t bytes) const {
+    return hipMemcpyAsync(dst[k] + d, src[k] + s, bytes, hipMemcpyDeviceToHost, ctx->stream);
+  }
+};
 int async_submit(tracyhip_ctx* ctx, std::function<int()> fn);  // queue a call on the context's worker thread
 int async_drain(tracyhip_ctx* ctx);                           // wait for the queue; returns (and clears) the first error
 // Staging of a caller's array.  MEM_DEVICE: it is used in place.  MEM_HOST: it goes through a grow-only buffer of the context.
@@ -520,10 +531,6 @@ int prof_trace_runs(tracyhip_ctx* ctx, const DpArgs& args, const PairDesc* hd, c
                     uint8_t* ops, const uint64_t* ops_off, uint32_t* ops_len);
 
 // ---- row blocks of `tracy assemble` (msa_batch.hip over assemble_wave.h): what assemble_run and denovo_run share ----
-struct MsaDevWave {    // the wave of assemble_wave.h on the device: one workgroup of 64 threads
-  __device__ __forceinline__ uint32_t lane() const { return threadIdx.x; }
-  __device__ __forceinline__ uint64_t ballot(bool p) const { return __ballot(p); }
-};
 struct AsmStep {       // one merge: a chain step of a group (assemble.hip) or a tree node (denovo.hip)
   MsaSide left, right; // the rows above / below in the merged block: an input profile (rows == null) or a block of rows
   uint64_t ops_off;    // the merge's op string in the ops buffer

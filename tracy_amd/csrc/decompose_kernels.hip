@@ -11,6 +11,7 @@
 #include "decompose_kernels.h"
 #include "decompose_launch.h"
 #include "decompose_wave.h"
+#include "dev_wave.h"
 
 using namespace tracyhip;
 
@@ -51,9 +52,8 @@ __global__ __launch_bounds__(64) void decompose_kernel(DecompArgs a, const Break
 }
 
 // ---- decomposeAlleles, one wave per trace with its working set in LDS (decompose_wave.h) ----
-struct DecompDevWave {
-  __device__ __forceinline__ uint32_t lane() const { return threadIdx.x; }
-  __device__ __forceinline__ uint64_t ballot(bool p) const { return __ballot(p); }
+struct DecompDevWave : DevWaveOps<true> {
+  // v_readlane: src_lane must be wave-uniform, which decompose_wave.h guarantees at every call (the shuffle form of the base does not need it)
   __device__ __forceinline__ uint32_t bcast(uint32_t x, uint32_t src_lane) const { return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)src_lane); }
   __device__ __forceinline__ void sync() const { wg_sync(); }
   __device__ __forceinline__ char* lds() const {
@@ -72,18 +72,10 @@ struct DecompDevWave {
     const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)x, 32), d = (uint32_t)__builtin_amdgcn_readlane((int)x, 48);
     return f(f(a, b), f(c, d));
   }
+  // (over this reduce, not the base's)
   __device__ __forceinline__ uint32_t sum(uint32_t x) const { return reduce(x, [](uint32_t a, uint32_t b) { return a + b; }); }
   __device__ __forceinline__ uint32_t umin(uint32_t x) const { return reduce(x, [](uint32_t a, uint32_t b) { return a < b ? a : b; }); }
   __device__ __forceinline__ uint32_t umax(uint32_t x) const { return reduce(x, [](uint32_t a, uint32_t b) { return a > b ? a : b; }); }
-  __device__ __forceinline__ uint32_t excl_sum(uint32_t x) const {  // sum of the lanes below (Hillis-Steele, six shuffles)
-    uint32_t v = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t y = (uint32_t)__shfl_up((int)v, o, 64);
-      if ((int)threadIdx.x >= o) v += y;
-    }
-    return v - x;
-  }
 };
 __global__ __launch_bounds__(64) void decompose_wave_kernel(DecompWaveArgs wa) {
   DecompDevWave w;

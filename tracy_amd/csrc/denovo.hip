@@ -27,6 +27,7 @@
 #include "assemble_wave.h"
 #include "capi_internal.h"
 #include "denovo_plan.h"
+#include "dev_wave.h"
 
 using namespace tracyhip;
 

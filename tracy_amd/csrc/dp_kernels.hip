@@ -7,6 +7,7 @@
 
 #include <cstdlib>
 
+#include "dev_wave.h"
 #include "dp_kernels.h"
 #include "launch.h"
 
@@ -19,8 +20,7 @@ static uint32_t lds_pad() {
   return (uint32_t)v;
 }
 
-struct DeviceWave {
-  __device__ __forceinline__ uint32_t lane() const { return threadIdx.x; }
+struct DeviceWave : DevWaveOps<true> {
   // lane L <- lane L-1 (wave_shr:1); lane 0 has no source lane and reads 0 (bound_ctrl), the caller overwrites it
   __device__ __forceinline__ int32_t shift_up(int32_t x) const {
     return __builtin_amdgcn_update_dpp(0, x, 0x138, 0xf, 0xf, true);
@@ -33,8 +33,6 @@ struct DeviceWave {
   __device__ __forceinline__ int32_t shift_up_or(int32_t x, int32_t first) const {
     return __builtin_amdgcn_update_dpp(first, x, 0x138, 0xf, 0xf, false);
   }
-  __device__ __forceinline__ uint64_t ballot(bool p) const { return __ballot(p); }
-  __device__ __forceinline__ uint32_t bcast(uint32_t x, uint32_t src_lane) const { return (uint32_t)__shfl((int)x, (int)src_lane, 64); }
   __device__ __forceinline__ void sync() const { __syncthreads(); }
   // global memory written by some lanes of this wave is read by others afterwards (band buffer, pass hand-over): the
   // workgroup IS the wave, so workgroup scope is all that is needed.  An agent-scope fence (__threadfence) writes back

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "dev_wave.h"
 
 using namespace tracyhip;
 

@@ -3,9 +3,8 @@
 // for every trace it answers; the rest is DEFERRED to the host.
 //
 // One wave per trace, four traces per workgroup; the per-trace body and its closed forms are pad_wave.h's (compiled for the host wave by
-// tests/emu/emu_pad.cpp).  Each wave owns 3 KB of the workgroup's LDS, the moving tile of its insert list.  Waves never wait for each
-// other: a wave's sync is a memory fence and a wave barrier.  What is refused before a device is touched, the cut into chunks and the
-// descriptors are pad_plan.h's.
+// tests/emu/emu_pad.cpp), the wave dev_wave.h's SoloWave.  Each wave owns 3 KB of the workgroup's LDS, the moving tile of its insert
+// list.  What is refused before a device is touched, the cut into chunks and the descriptors are pad_plan.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +13,7 @@
 
 #include "../../include/tracy_hip.h"
 #include "capi_internal.h"
+#include "dev_wave.h"
 #include "pad_plan.h"
 #include "pad_wave.h"
 
@@ -25,44 +25,11 @@ namespace {
 
 constexpr uint32_t kPadWaves = 4;  // traces per workgroup
 
-struct PadDevWave {
-  __device__ __forceinline__ uint32_t lane() const { return threadIdx.x & 63u; }
-  __device__ __forceinline__ uint64_t ballot(bool p) const { return __ballot(p); }
-  __device__ __forceinline__ uint32_t bcast(uint32_t x, uint32_t src_lane) const { return (uint32_t)__shfl((int)x, (int)src_lane, 64); }
-  // the wave's own LDS and global writes become visible to its own lanes: no other wave shares them
-  __device__ __forceinline__ void sync() const {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-  }
-  __device__ __forceinline__ void sync_global() const { sync(); }
-  __device__ __forceinline__ char* lds() const {
-    __shared__ __attribute__((aligned(16))) char pad_smem[kPadWaves * kPadLdsBytes];
-    return pad_smem + (threadIdx.x >> 6) * kPadLdsBytes;
-  }
-  template <class F>
-  __device__ __forceinline__ uint32_t reduce(uint32_t x, F f) const {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = f(x, (uint32_t)__shfl_xor((int)x, o, 64));
-    return x;
-  }
-  __device__ __forceinline__ uint32_t sum(uint32_t x) const { return reduce(x, [](uint32_t a, uint32_t b) { return a + b; }); }
-  __device__ __forceinline__ uint32_t umax(uint32_t x) const { return reduce(x, [](uint32_t a, uint32_t b) { return a > b ? a : b; }); }
-  __device__ __forceinline__ uint32_t excl_sum(uint32_t x) const {  // sum of the lanes below (Hillis-Steele, six shuffles)
-    uint32_t v = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t y = (uint32_t)__shfl_up((int)v, o, 64);
-      if ((int)lane() >= o) v += y;
-    }
-    return v - x;
-  }
-};
-
 template <bool S16>
 __global__ __launch_bounds__(64 * kPadWaves) void pad_kernel(PadArgs a) {
   const uint32_t t = blockIdx.x * kPadWaves + (threadIdx.x >> 6);
   if (t >= a.ntraces) return;  // (the whole wave)
-  PadDevWave w;
+  SoloWave<kPadWaves, kPadLdsBytes> w;
   pad_wave_body<S16>(w, a, t);
 }
 
@@ -70,38 +37,6 @@ int validate(const tracyhip_pad_job* job, int mem, const tracyhip_pad_result* ou
   const char* why = pad_validate(job, mem, out);
   return why ? set_error(TRACYHIP_ERR_ARG, "tracyhip_pad_traces: %s", why) : TRACYHIP_OK;
 }
-
-// byte offsets of the parts of a staging buffer, each aligned to 16
-struct Layout {
-  uint64_t at[8] = {0};
-  int n = 0;
-  uint64_t add(uint64_t bytes) { at[n + 1] = at[n] + ((bytes + 15) & ~15ull); return at[n++]; }
-  uint64_t total() const { return at[n] + 16; }
-};
-
-// copies of consecutive regions of one staged result array back to the caller's, merged while both sides continue
-struct Runs {
-  tracyhip_ctx* ctx;
-  const uint8_t* dev;
-  uint8_t* user;
-  uint32_t width;
-  uint64_t rel = 0, dst = 0, len = 0;
-  hipError_t flush() {
-    hipError_t e = hipSuccess;
-    if (len && user) e = hipMemcpyAsync(user + dst * width, dev + rel * width, len * width, hipMemcpyDeviceToHost, ctx->stream);
-    len = 0;
-    return e;
-  }
-  hipError_t add(uint64_t r, uint64_t d, uint64_t l) {
-    if (len && (r != rel + len || d != dst + len)) {
-      const hipError_t e = flush();
-      if (e != hipSuccess) return e;
-    }
-    if (!len) { rel = r; dst = d; }
-    len += l;
-    return hipSuccess;
-  }
-};
 
 }  // namespace
 
@@ -226,22 +161,21 @@ int tracyhip_pad_traces(tracyhip_ctx* ctx, const tracyhip_pad_job* job, int mem,
     timing_collect(ctx);
     // exactly what was reported goes back, straight into the caller's arrays; regions that follow each other on both sides travel as one copy
     const uint8_t* dout = static_cast<const uint8_t*>(ctx->dev[PD_OUT].p);
-    Runs rs{ctx, dout + o_sig, static_cast<uint8_t*>(out->signal), sb}, rp{ctx, dout + o_pos, reinterpret_cast<uint8_t*>(out->bcpos), 4};
-    Runs rb[4] = {{ctx, dout + o_byte[0], want_byte[0], 1}, {ctx, dout + o_byte[1], want_byte[1], 1}, {ctx, dout + o_byte[2], want_byte[2], 1},
-                  {ctx, dout + o_byte[3], want_byte[3], 1}};
+    RunMerger<1, CopyBackRun<1>> rs{{samples ? sb : 0}, {ctx, {dout + o_sig}, {static_cast<uint8_t*>(out->signal)}}};
+    RunMerger<5, CopyBackRun<5>> rcall{{out->bcpos ? 4u : 0u}, {ctx, {dout + o_pos}, {reinterpret_cast<uint8_t*>(out->bcpos)}}};
+    for (int k = 0; k < 4; ++k) {
+      rcall.width[1 + k] = want_byte[k] ? 1 : 0;
+      rcall.emit.src[1 + k] = dout + o_byte[k]; rcall.emit.dst[1 + k] = want_byte[k];
+    }
     for (uint32_t t = c.t0; t < c.t1; ++t) {
       report(t);
       if (res[t].status != TRACYHIP_PAD_OK) continue;
       if (samples) HIP_TRY(rs.add(meta[t].out_sig_off, out->sample_offset[t], 4ull * res[t].nsamples_out));
-      if (calls) {
-        HIP_TRY(rp.add(meta[t].out_call_off, out->call_offset[t], res[t].ncalls_out));
-        for (auto& r : rb) HIP_TRY(r.add(meta[t].out_call_off, out->call_offset[t], res[t].ncalls_out));
-      }
+      if (calls) HIP_TRY(rcall.add(meta[t].out_call_off, out->call_offset[t], res[t].ncalls_out));
     }
     if (samples || calls) {
       HIP_TRY(rs.flush());
-      HIP_TRY(rp.flush());
-      for (auto& r : rb) HIP_TRY(r.flush());
+      HIP_TRY(rcall.flush());
       HIP_TRY(ctx_sync(ctx));
     }
   }

@@ -10,6 +10,7 @@
 
 #include "../../include/tracy_hip.h"
 #include "pad_wave.h"
+#include "ragged_plan.h"
 
 namespace tracyhip {
 
@@ -43,15 +44,10 @@ inline const char* pad_validate(const tracyhip_pad_job* job, int mem, const trac
   return nullptr;
 }
 
-struct PadSpan {  // elements [lo, hi) of one payload array that a chunk touches
-  uint64_t lo = ~0ull, hi = 0;
-  void add(uint64_t a, uint64_t len) { lo = std::min(lo, a); hi = std::max(hi, a + len); }
-  uint64_t size() const { return hi > lo ? hi - lo : 0; }
-  PadSpan with(uint64_t a, uint64_t len) const { PadSpan s = *this; s.add(a, len); return s; }
-};
+using PadSpan = Span;  // (the name tests/cpp/pad_plan.cpp knows it by)
 struct PadChunk {
   uint32_t t0 = 0, t1 = 0;
-  PadSpan sig, bc, row, osig, ocall;
+  Span sig, bc, row, osig, ocall;  // of the input and the result arrays
   uint64_t scratch_words = 0;
 };
 
@@ -78,9 +74,9 @@ inline bool pad_cut_chunks(const tracyhip_pad_job* job, const tracyhip_pad_resul
   PadChunk cur;
   for (uint32_t t = 0; t < job->ntraces; ++t) {
     const uint64_t ns = job->nsamples[t];
-    auto fits = [](uint64_t off, uint64_t len) { return off <= ~0ull - len; };
-    if (!fits(job->bc_offset[t], job->bc_len[t]) || !fits(job->row_offset[t], job->row_len[t]) || (samples && !fits(job->signal_offset[t], 4 * ns)) ||
-        (samples && !fits(out->sample_offset[t], 4ull * out->sample_cap[t])) || (calls && !fits(out->call_offset[t], out->call_cap[t]))) {
+    if (!offset_fits(job->bc_offset[t], job->bc_len[t]) || !offset_fits(job->row_offset[t], job->row_len[t]) ||
+        (samples && !offset_fits(job->signal_offset[t], 4 * ns)) || (samples && !offset_fits(out->sample_offset[t], 4ull * out->sample_cap[t])) ||
+        (calls && !offset_fits(out->call_offset[t], out->call_cap[t]))) {
       *bad_t = t;
       return false;
     }

@@ -20,6 +20,7 @@
 
 #include "../../include/tracy_hip.h"
 #include "capi_internal.h"
+#include "dev_wave.h"
 #include "launch.h"
 #include "pipe_internal.h"
 #include "variants_wave.h"
@@ -31,20 +32,8 @@ namespace {
 constexpr uint32_t kVarMaxVariants = 1024;
 constexpr uint32_t kVarWaves = 2048;  // resident workgroups of variants_kernel: eight per CU, each with its two event lists in VB_EVENTS
 
-struct VarDevWave {  // the wave of variants_wave.h on the device: one workgroup of 64 threads
-  __device__ __forceinline__ uint32_t lane() const { return threadIdx.x; }
-  __device__ __forceinline__ uint64_t ballot(bool p) const { return __ballot(p); }
-  __device__ __forceinline__ uint32_t bcast(uint32_t x, uint32_t src_lane) const { return (uint32_t)__shfl((int)x, (int)src_lane, 64); }
+struct VarDevWave : DevWaveOps<true> {  // the wave of variants_wave.h: one workgroup of 64 threads
   __device__ __forceinline__ void sync() const { __syncthreads(); }
-  __device__ __forceinline__ uint32_t excl_sum(uint32_t x) const {  // sum of the lanes below (Hillis-Steele, six shuffles)
-    uint32_t v = x;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t y = (uint32_t)__shfl_up((int)v, o, 64);
-      if ((int)threadIdx.x >= o) v += y;
-    }
-    return v - x;
-  }
 };
 
 struct VarAln {  // one two-row alignment
