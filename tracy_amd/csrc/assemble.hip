@@ -197,37 +197,26 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   }
 
   // ---- chunks of groups: the traceback planes (and boundary rows) of a step of all its groups fit the workspace ----
-  struct Chunk { uint32_t lo, hi; uint64_t words, scratch; uint32_t steps; };
-  std::vector<Chunk> chunks;
-  {
-    Chunk c{0, 0, 0, 0, 0};
-    for (uint32_t g = 0; g < ng; ++g) {
-      if (matched[g].empty()) { c.hi = g + 1; continue; }
-      uint64_t words = 0, scr = 0;
-      for (const Match& mt : matched[g]) {
-        const uint32_t m = sT.length[t0 + mt.idx];
-        const uint32_t P = num_passes(m, KS[mt.idx]);
-        words = std::max(words, (uint64_t)P * steps_per_pass((uint32_t)bound[g]) * 64);
-        if (P > 1) scr = bound[g] + 2;
-      }
-      const uint64_t need = words * 8 + scr * 8;
-      if (need > limit)
-        return set_error(TRACYHIP_ERR_OOM, "group %u needs %llu bytes of traceback planes, workspace limit is %llu", g, (unsigned long long)need,
-                         (unsigned long long)limit);
-      if (c.steps && (c.words + words) * 8 + (c.scratch + scr) * 8 > limit) {
-        c.hi = g;
-        chunks.push_back(c);
-        c = Chunk{g, g, 0, 0, 0};
-      }
-      c.words += words;
-      c.scratch += scr;
-      c.steps = std::max<uint32_t>(c.steps, (uint32_t)matched[g].size());
-      c.hi = g + 1;
+  ChunkCut cut(limit);
+  std::vector<uint32_t> chunk_steps(1, 0);  // per chunk: the most matches of one of its groups
+  for (uint32_t g = 0; g < ng; ++g) {
+    if (matched[g].empty()) { cut.ride(g); continue; }
+    uint64_t words = 0, scr = 0;
+    for (const Match& mt : matched[g]) {
+      const uint32_t m = sT.length[t0 + mt.idx];
+      const uint32_t P = num_passes(m, KS[mt.idx]);
+      words = std::max(words, (uint64_t)P * steps_per_pass((uint32_t)bound[g]) * 64);
+      if (P > 1) scr = bound[g] + 2;
     }
-    chunks.push_back(c);
+    if (!cut.add(g, words * 8 + scr * 8, words, scr))
+      return set_error(TRACYHIP_ERR_OOM, "group %u needs %llu bytes of traceback planes, workspace limit is %llu", g,
+                       (unsigned long long)cut.refused_bytes, (unsigned long long)limit);
+    chunk_steps.resize(cut.chunks.size() + 1, 0);
+    chunk_steps.back() = std::max<uint32_t>(chunk_steps.back(), (uint32_t)matched[g].size());
   }
+  const std::vector<CutChunk>& chunks = cut.finish();
   uint64_t max_words = 0, max_scr = sc_scratch;
-  for (const Chunk& c : chunks) { max_words = std::max(max_words, c.words); max_scr = std::max(max_scr, c.scratch); }
+  for (const CutChunk& c : chunks) { max_words = std::max(max_words, c.words); max_scr = std::max(max_scr, c.scratch); }
   HIP_TRY(ctx->dev[DB_BITS].ensure(std::max<uint64_t>(max_words * 8, 8)));
   if (max_scr) HIP_TRY(ctx->dev[DB_SCRATCH].ensure(max_scr * 8));
 
@@ -266,8 +255,8 @@ int assemble_run(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const trac
   std::vector<uint32_t> act;
   TraceBatch tb{hd, dd, d_ops, d_off, d_len, limit};  // (the planes above hold every step of every chunk: its upload grows nothing)
 
-  for (const Chunk& c : chunks) {
-    for (uint32_t k = 0; k < c.steps; ++k) {
+  for (const CutChunk& c : chunks) {
+    for (uint32_t k = 0, steps = chunk_steps[&c - chunks.data()]; k < steps; ++k) {
       // the groups with a trace of rank k, by strip height and term count (one launch per run)
       act.clear();
       for (uint32_t g = c.lo; g < c.hi; ++g)

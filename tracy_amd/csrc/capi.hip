@@ -606,31 +606,8 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
   hipStream_t st = ctx->stream;
   TRACYHIP_HOST_SCOPE(hs_all, "run_dp");
 
-  // order: strip height, then longest first (long problems start early, short ones fill the tail)
+  // the plan (dp_plan.h): order, chunks of consecutive pairs whose traceback words fit the limit, offsets, runs
   auto hs_plan = std::make_unique<HostScope>("run_dp.plan");
-  std::vector<uint32_t> order(np);
-  for (uint32_t i = 0; i < np; ++i) order[i] = i;
-  auto before = [&](uint32_t x, uint32_t y) {
-    if (pb.k[x] != pb.k[y]) return pb.k[x] > pb.k[y];
-    const uint32_t fx = pb.desc[x].flags & PAIR_ROW4_ZERO, fy = pb.desc[y].flags & PAIR_ROW4_ZERO;
-    if (fx != fy) return fx > fy;  // profile x profile: 16-term pairs and 25-term pairs go to different launches
-    return (uint64_t)pb.desc[x].m * pb.desc[x].n > (uint64_t)pb.desc[y].m * pb.desc[y].n;
-  };
-  // (the order only balances the tail of a launch: batches of one strip height whose sizes lie within 25 % of each other --
-  // the final alignments of a `tracy align` batch -- keep the caller's order and save the host the sort between two kernels)
-  bool similar = true;
-  {
-    uint64_t lo = ~0ull, hi = 0;
-    for (uint32_t i = 0; i < np && similar; ++i) {
-      const uint64_t c = (uint64_t)pb.desc[i].m * pb.desc[i].n;
-      lo = std::min(lo, c); hi = std::max(hi, c);
-      similar = pb.k[i] == pb.k[0] && (pb.desc[i].flags & PAIR_ROW4_ZERO) == (pb.desc[0].flags & PAIR_ROW4_ZERO);
-    }
-    similar = similar && hi <= lo + lo / 4;
-  }
-  if (!similar && !std::is_sorted(order.begin(), order.end(), before)) std::stable_sort(order.begin(), order.end(), before);
-
-  // workspace plan: chunks of consecutive (sorted) pairs whose traceback words fit the limit
   const uint64_t word_bytes = needle ? 4 : 8;
   uint64_t limit = ~0ull;
   if (ctx->ws_limit || (trace && stage == DP_PLAIN)) {  // without a caller's limit only the full-matrix traceback needs a workspace plan
@@ -638,83 +615,20 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
     if (lrc) return lrc;
   }
   PairDesc* hd; HIP_TRY(ensure_into(ctx->pin[PB_DESC], (size_t)np, hd));
-  struct Chunk { uint32_t lo, hi; uint64_t words, scratch; };
-  std::vector<Chunk> chunks;
-  if (!(trace && stage == DP_PLAIN) && np >= (1u << 16)) {
-    // no traceback words: one chunk, and the only running total is the boundary-row scratch of multi-pass pairs.  Long lists
-    // (an all-pairs job: 36 MB of descriptors) are laid out by a few threads: sizes, a scan over the threads' totals, the copy.
-    constexpr uint32_t NT = 8;
-    uint64_t tsum[NT + 1] = {0};
-    auto range = [&](uint32_t t) { return std::make_pair((uint32_t)((uint64_t)np * t / NT), (uint32_t)((uint64_t)np * (t + 1) / NT)); };
-    auto scr_of = [&](uint32_t j) -> uint64_t {
-      const PairDesc& d = pb.desc[order[j]];
-      return (d.m && d.n && num_passes(d.m, pb.k[order[j]]) > 1) ? (uint64_t)d.n + 2 : 0;
-    };
-    {
-      std::vector<std::thread> th;
-      for (uint32_t t = 0; t < NT; ++t)
-        th.emplace_back([&, t]() { uint64_t a = 0; for (uint32_t j = range(t).first; j < range(t).second; ++j) a += scr_of(j); tsum[t + 1] = a; });
-      for (auto& x : th) x.join();
-    }
-    for (uint32_t t = 0; t < NT; ++t) tsum[t + 1] += tsum[t];
-    {
-      std::vector<std::thread> th;
-      for (uint32_t t = 0; t < NT; ++t)
-        th.emplace_back([&, t]() {
-          uint64_t a = tsum[t];
-          for (uint32_t j = range(t).first; j < range(t).second; ++j) {
-            PairDesc d = pb.desc[order[j]];
-            d.bits_off = 0;
-            d.scratch_off = a;
-            a += scr_of(j);
-            hd[j] = d;
-          }
-        });
-      for (auto& x : th) x.join();
-    }
-    chunks.push_back(Chunk{0, np, 0, tsum[NT]});
-  } else {
-    Chunk c{0, 0, 0, 0};
-    for (uint32_t j = 0; j < np; ++j) {
-      PairDesc d = pb.desc[order[j]];
-      const int K = pb.k[order[j]];
-      const uint32_t P = (d.m && d.n) ? num_passes(d.m, K) : 0;
-      const uint64_t words = (trace && stage == DP_PLAIN) ? (uint64_t)P * steps_per_pass(d.n) * 64 : 0;
-      const uint64_t scr = (P > 1) ? (uint64_t)d.n + 2 : 0;
-      if (words * word_bytes > limit)
-        return set_error(TRACYHIP_ERR_OOM, "one pair needs %llu bytes of traceback planes, workspace limit is %llu",
-                         (unsigned long long)(words * word_bytes), (unsigned long long)limit);
-      if (c.hi > c.lo && (c.words + words) * word_bytes > limit) {
-        chunks.push_back(c);
-        c = Chunk{j, j, 0, 0};
-      }
-      d.bits_off = c.words;
-      d.scratch_off = c.scratch;
-      c.words += words;
-      c.scratch += scr;
-      c.hi = j + 1;
-      hd[j] = d;
-    }
-    chunks.push_back(c);
-  }
+  SweepPlan plan;
+  if (!sweep_plan(pb.desc.data(), pb.k.data(), np, trace, needle, stage, limit, hd, plan, [](uint32_t n, auto fn) { parallel_for(n, fn); }))
+    return set_error(TRACYHIP_ERR_OOM, "one pair needs %llu bytes of traceback planes, workspace limit is %llu",
+                     (unsigned long long)plan.need, (unsigned long long)limit);
   hs_plan.reset();  // the planning part ends here
-  uint64_t max_words = 0, max_scr = 0;
-  for (const Chunk& c : chunks) { max_words = std::max(max_words, c.words); max_scr = std::max(max_scr, c.scratch); }
   HIP_TRY(ctx->dev[DB_DESC].ensure(sizeof(PairDesc) * (size_t)np));
   HIP_TRY(hipMemcpyAsync(ctx->dev[DB_DESC].p, hd, sizeof(PairDesc) * (size_t)np, hipMemcpyHostToDevice, st));
-  if (trace && stage == DP_PLAIN) HIP_TRY(ctx->dev[DB_BITS].ensure(max_words * word_bytes));
-  if (stage == DP_BAND) {
-    uint32_t maxrun = 0;
-    for (const Chunk& c : chunks) maxrun = std::max(maxrun, c.hi - c.lo);
-    HIP_TRY(ctx->dev[DB_BAND].ensure((size_t)maxrun * ck->B * 64 * 8));
-  }
-  if (max_scr) HIP_TRY(ctx->dev[DB_SCRATCH].ensure(max_scr * 8));
+  if (trace && stage == DP_PLAIN) HIP_TRY(ctx->dev[DB_BITS].ensure(plan.max_words * word_bytes));
+  if (stage == DP_BAND) HIP_TRY(ctx->dev[DB_BAND].ensure((size_t)plan.max_pairs * ck->B * 64 * 8));
+  if (plan.max_scratch) HIP_TRY(ctx->dev[DB_SCRATCH].ensure(plan.max_scratch * 8));
   HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
   HIP_TRY(hipMemsetAsync(ctx->dev[DB_ERR].p, 0, sizeof(int32_t) * kErrWords, st));
   std::vector<std::pair<uint32_t, int>> narrow_launches;  // (tallest problem, K) of every 16-bit launch, for range_verdict
   uint64_t band_cells_credited = 0;                       // m * n of the band launches (replaced by the swept cells after the sync)
-  uint64_t max_mn = 0;
-  for (uint32_t j = 0; j < np; ++j) max_mn = std::max<uint64_t>(max_mn, (uint64_t)pb.desc[j].m + pb.desc[j].n);
 
   DpArgs a = scoring_args(ctx, prm);
   a.a1 = pb.d_a1;
@@ -739,89 +653,70 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
   if (ck) { a.ckpt = ck->d_ckpt; a.lastrow = ck->d_lastrow; a.ckpt_B = ck->B; a.band = static_cast<uint64_t*>(ctx->dev[DB_BAND].p); a.ckpt_narrow = ck->narrow ? 1 : 0; }
   const PairDesc* dd = static_cast<const PairDesc*>(ctx->dev[DB_DESC].p);
 
-  for (const Chunk& c : chunks) {
-    uint32_t j = c.lo;
-    while (j < c.hi) {  // one launch per run of equal K (and, profile x profile, equal term count)
-      uint32_t e = j;
-      const int K = pb.k[order[j]];
-      const uint32_t row4 = hd[j].flags & PAIR_ROW4_ZERO;
-      while (e < c.hi && pb.k[order[e]] == K && (hd[e].flags & PAIR_ROW4_ZERO) == row4) ++e;
-      a.pairs = dd + j;
-      int trc;
-      if (ctx->timing) {
-        uint64_t cells = 0, bytes = 0;
-        for (uint32_t q = j; q < e; ++q) {
-          const PairDesc& d = hd[q];
-          uint64_t mn = (uint64_t)(stage == DP_PREFIX ? std::min<uint32_t>(d.m, (uint32_t)kPrefixLanes * K) : d.m) * d.n;
-          if (trace && stage == DP_PLAIN && (d.flags & PAIR_BANDED)) {  // multi-pass band form: the cells its passes sweep, not the matrix
-            mn = 0;
-            for (uint32_t base = 0; base < d.m; base += 64u * K) {
-              const uint32_t rows_here = std::min<uint32_t>(d.m - base, 64u * K);
-              const int64_t c_lo = std::max<int64_t>(1, (int64_t)base + 1 + band_dmin(d)), c_hi = std::min<int64_t>(d.n, (int64_t)(base + rows_here) + band_dmax(d));
-              if (c_hi >= c_lo) mn += (uint64_t)rows_here * (uint64_t)(c_hi - c_lo + 1);
-            }
-          }
-          cells += mn;
-          bytes += (trace ? mn / 2 : 0) + (pb.a1_profile ? 24ull * d.m : d.m) + (pb.a2_profile ? 24ull * d.n : d.n) + 4;
-        }
-        if (stage == DP_BAND) { bytes = 0; band_cells_credited += cells; }  // (bytes: the bands live in a per-pair buffer, no matrix-sized traffic)
-        if ((trc = timing_begin(ctx, stage == DP_BAND ? TRACYHIP_TIMER_BAND : stage == DP_PREFIX ? TRACYHIP_TIMER_PREFIX : stage == DP_ORIGIN ? TRACYHIP_TIMER_ORIGIN
-                                     : trace ? TRACYHIP_TIMER_TRACE : TRACYHIP_TIMER_SCORE, cells, bytes))) return trc;
+  for (const SweepRun& run : plan.runs) {  // one launch per run of equal K (and, profile x profile, equal term count)
+    const uint32_t j = run.lo, e = run.hi;
+    const int K = run.K;
+    a.pairs = dd + j;
+    int trc;
+    if (ctx->timing) {
+      uint64_t cells, bytes;
+      sweep_credit(hd, j, e, K, trace, stage, pb.a1_profile, pb.a2_profile, cells, bytes);
+      if (stage == DP_BAND) band_cells_credited += cells;
+      if ((trc = timing_begin(ctx, stage == DP_BAND ? TRACYHIP_TIMER_BAND : stage == DP_PREFIX ? TRACYHIP_TIMER_PREFIX : stage == DP_ORIGIN ? TRACYHIP_TIMER_ORIGIN
+                                   : trace ? TRACYHIP_TIMER_TRACE : TRACYHIP_TIMER_SCORE, cells, bytes))) return trc;
+    }
+    bool narrow = false;
+    if (!needle && !trace && (pb.mode == MODE_QP || pb.mode == MODE_CHAR) && !ctx->knobs.no_narrow) {
+      uint32_t maxm = 0;
+      for (uint32_t q = j; q < e; ++q) maxm = std::max(maxm, hd[q].m);
+      narrow = narrow_ok(prm, maxm, K);
+    }
+    a.diag_period = 0;
+    if (stage == DP_PREFIX || (stage == DP_CKPT && ck->narrow) || (stage == DP_PLAIN && narrow)) {
+      uint32_t maxm = 0;
+      for (uint32_t q = j; q < e; ++q) maxm = std::max(maxm, hd[q].m);
+      if (stage != DP_PREFIX && pb.mode == MODE_QP && (a.diag_period = ctx_sweep_diag(ctx, prm, K, 64))) ++ctx->stats.sweep_diag_launches;
+      narrow_launches.emplace_back(maxm, narrow_launch_diag(K, a.diag_period));
+    }
+    if (stage == DP_PREFIX) {
+      HIP_TRY(launch_gotoh_prefix(K, a, e - j, st));
+    } else if (stage == DP_ORIGIN) {
+      HIP_TRY(launch_gotoh_origin(K, pb.mode == MODE_CQ ? 1 : pb.mode == MODE_QP ? 2 : 0, pb.cq_codes, a, e - j, st));
+    } else if (stage == DP_CKPT) {
+      // one representation for the whole batch: the caller checks narrow_ok for the largest problem
+      narrow = ck->narrow;
+      HIP_TRY(launch_gotoh_ckpt(pb.mode, K, narrow, a, e - j, st));
+    }
+    else if (stage == DP_BAND) {
+      WalkArgs wa{};
+      wa.pairs = dd + j; wa.ops = d_ops; wa.ops_off = d_ops_off; wa.ops_len = d_ops_len; wa.err = a.err; wa.npairs = e - j; wa.K = K;
+      HIP_TRY(launch_band_trace(pb.mode, K, a, wa, e - j, st));
+    } else if (!needle && pb.mode == MODE_PROF) {
+      bool a16 = false;
+      if (!trace && !ctx->knobs.no_narrow) {
+        uint64_t mn = 0;
+        for (uint32_t q = j; q < e; ++q) mn = std::max<uint64_t>(mn, (uint64_t)hd[q].m + hd[q].n);
+        if ((a16 = arith16_ok(prm, mn, 0))) narrow_launches.emplace_back((uint32_t)mn, 0);
       }
-      bool narrow = false;
-      if (!needle && !trace && (pb.mode == MODE_QP || pb.mode == MODE_CHAR) && !ctx->knobs.no_narrow) {
-        uint32_t maxm = 0;
-        for (uint32_t q = j; q < e; ++q) maxm = std::max(maxm, hd[q].m);
-        narrow = narrow_ok(prm, maxm, K);
-      }
-      a.diag_period = 0;
-      if (stage == DP_PREFIX || (stage == DP_CKPT && ck->narrow) || (stage == DP_PLAIN && narrow)) {
-        uint32_t maxm = 0;
-        for (uint32_t q = j; q < e; ++q) maxm = std::max(maxm, hd[q].m);
-        if (stage != DP_PREFIX && pb.mode == MODE_QP && (a.diag_period = ctx_sweep_diag(ctx, prm, K, 64))) ++ctx->stats.sweep_diag_launches;
-        narrow_launches.emplace_back(maxm, narrow_launch_diag(K, a.diag_period));
-      }
-      if (stage == DP_PREFIX) {
-        HIP_TRY(launch_gotoh_prefix(K, a, e - j, st));
-      } else if (stage == DP_ORIGIN) {
-        HIP_TRY(launch_gotoh_origin(K, pb.mode == MODE_CQ ? 1 : pb.mode == MODE_QP ? 2 : 0, pb.cq_codes, a, e - j, st));
-      } else if (stage == DP_CKPT) {
-        // one representation for the whole batch: the caller checks narrow_ok for the largest problem
-        narrow = ck->narrow;
-        HIP_TRY(launch_gotoh_ckpt(pb.mode, K, narrow, a, e - j, st));
-      }
-      else if (stage == DP_BAND) {
-        WalkArgs wa{};
-        wa.pairs = dd + j; wa.ops = d_ops; wa.ops_off = d_ops_off; wa.ops_len = d_ops_len; wa.err = a.err; wa.npairs = e - j; wa.K = K;
-        HIP_TRY(launch_band_trace(pb.mode, K, a, wa, e - j, st));
-      } else if (!needle && pb.mode == MODE_PROF) {
-        bool a16 = false;
-        if (!trace && !ctx->knobs.no_narrow) {
-          uint64_t mn = 0;
-          for (uint32_t q = j; q < e; ++q) mn = std::max<uint64_t>(mn, (uint64_t)hd[q].m + hd[q].n);
-          if ((a16 = arith16_ok(prm, mn, 0))) narrow_launches.emplace_back((uint32_t)mn, 0);
-        }
-        HIP_TRY(launch_gotoh_prof(K, trace, row4 != 0, a16, a, e - j, st));
-      }
-      else
-        HIP_TRY(needle ? launch_needle(pb.mode, K, trace, a, e - j, st)
-                       : launch_gotoh(pb.mode, K, trace, narrow, a, e - j, st, trace && pb.mode == MODE_QP && sub_limit(prm) > kWideScore));
+      HIP_TRY(launch_gotoh_prof(K, trace, run.row4 != 0, a16, a, e - j, st));
+    }
+    else
+      HIP_TRY(needle ? launch_needle(pb.mode, K, trace, a, e - j, st)
+                     : launch_gotoh(pb.mode, K, trace, narrow, a, e - j, st, trace && pb.mode == MODE_QP && sub_limit(prm) > kWideScore));
+    if ((trc = timing_end(ctx))) return trc;
+    if (trace && stage == DP_PLAIN && !fused_walk) {
+      WalkArgs wa{};
+      wa.pairs = dd + j;
+      wa.bits = a.bits;
+      wa.ops = d_ops;
+      wa.ops_off = d_ops_off;
+      wa.ops_len = d_ops_len;
+      wa.err = a.err;
+      wa.npairs = e - j;
+      wa.K = K;
+      if ((trc = timing_begin(ctx, TRACYHIP_TIMER_WALK, 0, 0))) return trc;
+      HIP_TRY(needle ? launch_needle_walk(wa, a.bits32, st) : launch_gotoh_walk(wa, st));
       if ((trc = timing_end(ctx))) return trc;
-      if (trace && stage == DP_PLAIN && !fused_walk) {
-        WalkArgs wa{};
-        wa.pairs = dd + j;
-        wa.bits = a.bits;
-        wa.ops = d_ops;
-        wa.ops_off = d_ops_off;
-        wa.ops_len = d_ops_len;
-        wa.err = a.err;
-        wa.npairs = e - j;
-        wa.K = K;
-        if ((trc = timing_begin(ctx, TRACYHIP_TIMER_WALK, 0, 0))) return trc;
-        HIP_TRY(needle ? launch_needle_walk(wa, a.bits32, st) : launch_gotoh_walk(wa, st));
-        if ((trc = timing_end(ctx))) return trc;
-      }
-      j = e;
     }
   }
   if (defer_herr) {  // the caller waits and judges (strings, traceback: nothing here can ask for the wider kernels)
@@ -840,7 +735,7 @@ int run_dp(tracyhip_ctx* ctx, const DpProblem& pb, const tracyhip_params* prm, b
   }
   // the packed score field of the origin-tracking sweep is sized for substitution scores of normalised profiles
   if (stage == DP_ORIGIN && pb.mode == MODE_QP && herr[1] > sub_limit(prm)) return kWiden;
-  const int verdict = range_verdict(prm, herr, narrow_launches, max_mn, trace ? (needle ? 2 : kTagShift) : 0);
+  const int verdict = range_verdict(prm, herr, narrow_launches, plan.max_mn, trace ? (needle ? 2 : kTagShift) : 0);
   if (verdict == kWiden && stage == DP_PLAIN) {  // the 16-bit score kernel met an un-normalised profile: same work on the int32 kernel
     const bool keep = ctx->knobs.no_narrow;
     ctx->knobs.no_narrow = true;
@@ -885,110 +780,28 @@ int run_band16(tracyhip_ctx* ctx, Band16Job& job, const tracyhip_params* prm, in
   if (nall == 0) return TRACYHIP_OK;
   TRACYHIP_HOST_SCOPE(hs_all, "run_band16");
   hipStream_t st = ctx->stream;
+  // the plan (dp_plan.h): pairs by strip height (12, 8, 4), chunks whose traceback words fit the limit, offsets, the launches --
+  // descriptors go straight into the pinned staging block
   auto hs_plan = std::make_unique<HostScope>("run_band16.plan");
+  auto pool = [](uint32_t n, auto fn) { parallel_for(n, fn); };
+  BandPlan plan;
+  band_sizes(job.desc.data(), job.k.data(), nall, job.kind, ctx->timing, plan, pool);
+  if (plan.bad) return set_error(TRACYHIP_ERR_ARG, "run_band16: pair outside the band kernels' domain");
+  const uint32_t np = plan.np;
+  if (np == 0) return TRACYHIP_OK;
   uint64_t limit = ctx->ws_limit;
-  // Order: strip height (12, 8, 4), the caller's order within one (the pairs of a pipeline stage are of a size).  Laid out by a
-  // few threads: per-thread counts per strip height, a scan, the fill -- descriptors go straight into the pinned staging block.
-  constexpr int NB = 3;
-  auto bucket_of = [](int K) { return K == 12 ? 0 : K == 8 ? 1 : K == 4 ? 2 : -1; };
-  static const int bucket_k[NB] = {12, 8, 4};
-  struct Part { uint32_t n[NB]; uint64_t bytes[NB]; uint32_t nmax[NB]; uint64_t cells[NB], tbytes[NB]; bool bad; };  // (cells / tbytes: what the timers credit)
-  Part part[kHostThreads] = {};
-  std::vector<uint64_t> wb(nall);  // bytes of traceback words per pair (kind 0)
-  parallel_for(nall, [&](uint32_t lo, uint32_t hi, uint32_t tid) {
-    Part& pt = part[tid];
-    for (uint32_t i = lo; i < hi; ++i) {
-      const int K = job.k[i];
-      if (K == 0) { wb[i] = 0; continue; }
-      const PairDesc& d = job.desc[i];
-      const int b = bucket_of(K);
-      if (b < 0 || d.m == 0 || d.n == 0 || b16_window(K, band_dmin(d), band_dmax(d)) > b16_max_window(K)) { pt.bad = true; continue; }
-      const uint64_t wds = (job.kind == 0 || ctx->timing) ? b16_words(d.m, d.n, K, band_dmin(d), band_dmax(d)) : 0;
-      const uint64_t bytes = job.kind == 0 ? ((b16_store_words(d.m, d.n, K, band_dmin(d), band_dmax(d)) * b16_word_bytes(K) + 15u) & ~15ull) : 0;
-      wb[i] = bytes;
-      pt.n[b] += 1;
-      pt.bytes[b] += bytes;
-      pt.nmax[b] = std::max(pt.nmax[b], d.n);
-      pt.cells[b] += wds * (uint64_t)K;
-      pt.tbytes[b] += (job.kind == 0 ? wds * b16_word_bytes(K) : 0) + 12ull * d.m + d.n + 4;
-    }
-  });
-  uint32_t bn[NB] = {0, 0, 0}, bnmax[NB] = {0, 0, 0};
-  uint64_t total_bytes = 0, bcells[NB] = {0, 0, 0}, btbytes[NB] = {0, 0, 0};
-  for (uint32_t t = 0; t < kHostThreads; ++t) {
-    if (part[t].bad) { return set_error(TRACYHIP_ERR_ARG, "run_band16: pair outside the band kernels' domain"); }
-    for (int b = 0; b < NB; ++b) {
-      bn[b] += part[t].n[b]; total_bytes += part[t].bytes[b];
-      bnmax[b] = std::max(bnmax[b], part[t].nmax[b]); bcells[b] += part[t].cells[b]; btbytes[b] += part[t].tbytes[b];
-    }
-  }
-  const uint32_t np = bn[0] + bn[1] + bn[2];
-  if (np == 0) { return TRACYHIP_OK; }
   if (limit == 0) {
     int lrc;
-    if (job.kind != 0 || total_bytes + 64 <= ctx->dev[DB_BITS].cap) limit = ~0ull;  // (the words fit what is there: no driver call)
+    if (job.kind != 0 || plan.total_bytes + 64 <= ctx->dev[DB_BITS].cap) limit = ~0ull;  // (the words fit what is there: no driver call)
     else if ((lrc = workspace_limit(ctx, ctx->dev[DB_BITS].cap, &limit))) return lrc;
   }
   PairDesc* hd; HIP_TRY(ensure_into(ctx->pin[PB_DESC], (size_t)np, hd));
-  std::vector<int> hk(np);
-  struct Chunk { uint32_t lo, hi; uint64_t bytes; };
-  std::vector<Chunk> chunks;
-  uint64_t max_mn = 0;
-  if (total_bytes <= limit) {
-    // one chunk: positions and word offsets from the scan over (strip height, thread)
-    uint32_t pos0[NB][kHostThreads];
-    uint64_t off0[NB][kHostThreads];
-    uint32_t p = 0;
-    uint64_t o = 0;
-    for (int b = 0; b < NB; ++b)
-      for (uint32_t t = 0; t < kHostThreads; ++t) { pos0[b][t] = p; off0[b][t] = o; p += part[t].n[b]; o += part[t].bytes[b]; }
-    uint64_t tmax[kHostThreads] = {};
-    parallel_for(nall, [&](uint32_t lo, uint32_t hi, uint32_t tid) {
-      uint32_t pp[NB];
-      uint64_t oo[NB];
-      for (int b = 0; b < NB; ++b) { pp[b] = pos0[b][tid]; oo[b] = off0[b][tid]; }
-      uint64_t mx = 0;
-      for (uint32_t i = lo; i < hi; ++i) {
-        const int K = job.k[i];
-        if (K == 0) continue;
-        const int b = bucket_of(K);
-        PairDesc d = job.desc[i];
-        d.bits_off = oo[b];
-        oo[b] += wb[i];
-        hd[pp[b]] = d;
-        hk[pp[b]] = K;
-        ++pp[b];
-        mx = std::max<uint64_t>(mx, (uint64_t)d.m + d.n);
-      }
-      tmax[tid] = mx;
-    });
-    for (uint32_t t = 0; t < kHostThreads; ++t) max_mn = std::max(max_mn, tmax[t]);
-    chunks.push_back(Chunk{0, np, total_bytes});
-  } else {
-    // the words do not fit the workspace at once: chunks of consecutive pairs (serial; rare)
-    uint32_t pos = 0;
-    Chunk c{0, 0, 0};
-    for (int b = 0; b < NB; ++b)
-      for (uint32_t i = 0; i < nall; ++i) {
-        if (job.k[i] != bucket_k[b]) continue;
-        if (wb[i] > limit) { return set_error(TRACYHIP_ERR_OOM, "one pair needs %llu bytes of traceback words, workspace limit is %llu", (unsigned long long)wb[i], (unsigned long long)limit); }
-        if (c.hi > c.lo && c.bytes + wb[i] > limit) { chunks.push_back(c); c = Chunk{pos, pos, 0}; }
-        PairDesc d = job.desc[i];
-        d.bits_off = c.bytes;
-        c.bytes += wb[i];
-        hd[pos] = d;
-        hk[pos] = bucket_k[b];
-        c.hi = ++pos;
-        max_mn = std::max<uint64_t>(max_mn, (uint64_t)d.m + d.n);
-      }
-    chunks.push_back(c);
-  }
-  uint64_t max_bytes = 0;
-  for (const Chunk& ch : chunks) max_bytes = std::max(max_bytes, ch.bytes);
+  if (!band_place(job.desc.data(), job.k.data(), nall, job.kind, ctx->timing, limit, hd, plan, pool))
+    return set_error(TRACYHIP_ERR_OOM, "one pair needs %llu bytes of traceback words, workspace limit is %llu", (unsigned long long)plan.need, (unsigned long long)limit);
   hs_plan.reset();  // the planning part ends here
   HIP_TRY(ctx->dev[DB_DESC].ensure(sizeof(PairDesc) * (size_t)np));
   HIP_TRY(hipMemcpyAsync(ctx->dev[DB_DESC].p, hd, sizeof(PairDesc) * (size_t)np, hipMemcpyHostToDevice, st));
-  if (job.kind == 0) HIP_TRY(ctx->dev[DB_BITS].ensure(max_bytes + 64));
+  if (job.kind == 0) HIP_TRY(ctx->dev[DB_BITS].ensure(plan.max_bytes + 64));
   HIP_TRY(ctx->dev[DB_ERR].ensure(kErrBytes));
   // (the error words are NOT cleared here: the table kernel of this stage may have reported into them; the caller cleared them)
   Band16Args a{};
@@ -996,86 +809,14 @@ int run_band16(tracyhip_ctx* ctx, Band16Job& job, const tracyhip_params* prm, in
   a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p); a.go = prm->go; a.ge = prm->ge; a.hfree = prm->hfree;
   a.ops = d_ops; a.ops_off = d_ops_off; a.ops_len = d_ops_len;
   const PairDesc* dd = static_cast<const PairDesc*>(ctx->dev[DB_DESC].p);
-  if (chunks.size() == 1) {
-    // the whole job at once: per strip height the pairs [first, first + count) and the sums of the planning pass (no walk over the list)
-    uint32_t first[NB];
-    for (int b = 0, q = 0; b < NB; ++b) { first[b] = (uint32_t)q; q += (int)bn[b]; }
-    const int used = (bn[0] != 0) + (bn[1] != 0) + (bn[2] != 0);
-    const uint32_t nmax_all = std::max(bnmax[0], std::max(bnmax[1], bnmax[2]));
-    const uint32_t cap_all = (nmax_all + 7u) & ~3u;
+  for (const BandLaunch& l : plan.launches) {
+    if (!l.fits) return set_error(TRACYHIP_ERR_RANGE, "run_band16: reference of %u columns does not fit the staging area", l.nmax);
+    Band16Args ak[kBandHeights] = {a, a, a};  // 12, 8, 4
+    for (int b = 0; b < kBandHeights; ++b) { ak[b].pairs = dd + l.first[b]; ak[b].npairs = l.count[b]; ak[b].code_cap = l.code_cap; }
     int trc;
-    if (np <= 24576u && used > 1 && 4ull * cap_all + b16_table_bytes(12) <= 64u * 1024u) {  // few waves, several heights: band16_multi_kernel
-      Band16Args ak[3] = {a, a, a};  // 12, 8, 4
-      for (int b = 0; b < NB; ++b) { ak[b].pairs = dd + first[b]; ak[b].npairs = bn[b]; ak[b].code_cap = cap_all; }
-      if ((trc = timing_begin(ctx, job.kind == 0 ? TRACYHIP_TIMER_TRACE : TRACYHIP_TIMER_ORIGIN, bcells[0] + bcells[1] + bcells[2], btbytes[0] + btbytes[1] + btbytes[2]))) return trc;
-      HIP_TRY(launch_band16_multi(job.kind, ak[0], ak[1], ak[2], st));
-      if ((trc = timing_end(ctx))) return trc;
-    } else {
-      for (int b = 0; b < NB; ++b) {
-        if (bn[b] == 0) continue;
-        a.pairs = dd + first[b];
-        a.npairs = bn[b];
-        a.code_cap = (bnmax[b] + 7u) & ~3u;
-        if (4ull * a.code_cap + b16_table_bytes(bucket_k[b]) > 64u * 1024u) return set_error(TRACYHIP_ERR_RANGE, "run_band16: reference of %u columns does not fit the staging area", bnmax[b]);
-        if ((trc = timing_begin(ctx, job.kind == 0 ? TRACYHIP_TIMER_TRACE : TRACYHIP_TIMER_ORIGIN, bcells[b], btbytes[b]))) return trc;
-        HIP_TRY(launch_band16(bucket_k[b], job.kind, a, st));
-        if ((trc = timing_end(ctx))) return trc;
-      }
-    }
-  } else
-  for (const Chunk& ch : chunks) {
-    uint32_t j = ch.lo;
-    // a chunk of few waves with more than one strip height: one launch for all of them (band16_multi_kernel)
-    if (ch.hi - ch.lo <= 24576u && hk[ch.lo] != hk[ch.hi - 1]) {
-      Band16Args ak[3] = {a, a, a};  // 12, 8, 4
-      uint32_t nmax = 0;
-      uint64_t cells = 0, bytes = 0;
-      for (int b = 0; b < 3; ++b) { ak[b].pairs = dd + ch.lo; ak[b].npairs = 0; }
-      for (uint32_t e = ch.lo; e < ch.hi; ++e) {
-        const int K = hk[e], b = bucket_of(K);
-        if (ak[b].npairs == 0) ak[b].pairs = dd + e;
-        ak[b].npairs += 1;
-        nmax = std::max(nmax, hd[e].n);
-        if (ctx->timing) {
-          const uint64_t wds = b16_words(hd[e].m, hd[e].n, K, band_dmin(hd[e]), band_dmax(hd[e]));
-          cells += wds * (uint64_t)K;
-          bytes += (job.kind == 0 ? wds * b16_word_bytes(K) : 0) + 12ull * hd[e].m + hd[e].n + 4;
-        }
-      }
-      const uint32_t cap = (nmax + 7u) & ~3u;
-      if (4ull * cap + b16_table_bytes(12) <= 64u * 1024u) {
-        for (int b = 0; b < 3; ++b) ak[b].code_cap = cap;
-        int trc;
-        if ((trc = timing_begin(ctx, job.kind == 0 ? TRACYHIP_TIMER_TRACE : TRACYHIP_TIMER_ORIGIN, cells, bytes))) return trc;
-        HIP_TRY(launch_band16_multi(job.kind, ak[0], ak[1], ak[2], st));
-        if ((trc = timing_end(ctx))) return trc;
-        continue;
-      }
-    }
-    while (j < ch.hi) {
-      uint32_t e = j;
-      const int K = hk[j];
-      uint32_t nmax = 0;
-      uint64_t cells = 0, bytes = 0;
-      while (e < ch.hi && hk[e] == K) {
-        nmax = std::max(nmax, hd[e].n);
-        if (ctx->timing) {
-          const uint64_t wds = b16_words(hd[e].m, hd[e].n, K, band_dmin(hd[e]), band_dmax(hd[e]));
-          cells += wds * (uint64_t)K;
-          bytes += (job.kind == 0 ? wds * b16_word_bytes(K) : 0) + 12ull * hd[e].m + hd[e].n + 4;
-        }
-        ++e;
-      }
-      a.pairs = dd + j;
-      a.npairs = e - j;
-      a.code_cap = (nmax + 7u) & ~3u;
-      if (4ull * a.code_cap + b16_table_bytes(K) > 64u * 1024u) return set_error(TRACYHIP_ERR_RANGE, "run_band16: reference of %u columns does not fit the staging area", nmax);
-      int trc;
-      if ((trc = timing_begin(ctx, job.kind == 0 ? TRACYHIP_TIMER_TRACE : TRACYHIP_TIMER_ORIGIN, cells, bytes))) return trc;
-      HIP_TRY(launch_band16(K, job.kind, a, st));
-      if ((trc = timing_end(ctx))) return trc;
-      j = e;
-    }
+    if ((trc = timing_begin(ctx, job.kind == 0 ? TRACYHIP_TIMER_TRACE : TRACYHIP_TIMER_ORIGIN, l.cells, l.bytes))) return trc;
+    HIP_TRY(l.K ? launch_band16(l.K, job.kind, ak[band_bucket(l.K)], st) : launch_band16_multi(job.kind, ak[0], ak[1], ak[2], st));
+    if ((trc = timing_end(ctx))) return trc;
   }
   int32_t herr[kErrWords] = {};
   HIP_TRY(hipMemcpyAsync(herr, ctx->dev[DB_ERR].p, sizeof(herr), hipMemcpyDeviceToHost, st));

@@ -17,6 +17,7 @@
 #include "../../include/tracy_hip.h"
 #include "assemble_wave.h"
 #include "dp_kernels.h"
+#include "dp_plan.h"
 #include "band16_launch.h"
 #include "front.h"
 
@@ -366,6 +367,7 @@ namespace tracyhip {
 // The per-trace host loops of the pipelines (descriptors, bands, verdicts of 10^5 traces between two launches) on a few threads:
 // fn(lo, hi, tid) over [0, n) in contiguous slices; small n runs inline.
 constexpr uint32_t kHostThreads = 8;
+static_assert(kHostThreads <= kPlanSlices, "the plans of dp_plan.h keep one partial sum per slice");
 // Workers that stay alive between calls (starting seven threads costs ~0.3 ms, and a decompose call of 10^5 traces runs forty of
 // these loops between its launches).  One job at a time: a second caller (another lane) gets `false` and starts its own threads.
 bool host_pool_run(const std::function<void(uint32_t)>& job);  // job(slice) for slice = 0 .. kHostThreads - 1, worked off by the pool + the caller
@@ -456,12 +458,7 @@ int workspace_budget(tracyhip_ctx* ctx, uint64_t held, uint64_t* out, bool* from
 // error is set (`name` opens the message)
 bool check_profile_set(const tracyhip_seqset& s, const char* name);
 bool check_profile_columns(const tracyhip_seqset& s, const char* name, uint32_t lo, uint32_t hi);
-// stage: DP_PLAIN = score-only or full-matrix traceback; DP_CKPT = score-only pass that also writes wavefront
-// checkpoints + last-row values (PairDesc::ckpt_off / lastrow_off set by the caller); DP_BAND = band traceback
-// from those checkpoints (trace must be true); DP_PREFIX = prefix bound of the semiglobal score (rows 1 .. kPrefixLanes*K of
-// profile x code pairs, 16-bit domain): d_scores receives max_j max(H, F) of that row.
-// DP_ORIGIN = origin-tracking sweep of string x string pairs (DpCkpt::d_ends receives {lead, end} per pair, d_scores H(m,n)).
-enum { DP_PLAIN = 0, DP_CKPT = 1, DP_BAND = 2, DP_PREFIX = 3, DP_ORIGIN = 4 };
+// (the stages of run_dp -- DP_PLAIN, DP_CKPT, DP_BAND, DP_PREFIX, DP_ORIGIN -- are dp_plan.h's)
 struct DpCkpt {
   int32_t* d_ckpt = nullptr;
   int32_t* d_lastrow = nullptr;

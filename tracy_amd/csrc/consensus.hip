@@ -240,52 +240,40 @@ int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tr
   // descriptors: score pairs (2 per pair, in chunk order) then traceback pairs (1 per pair)
   PairDesc* hsd; HIP_TRY(ensure_into(ctx->pin[PB_DESC], 3 * (size_t)np, hsd));
   PairDesc* htd = hsd + 2 * (size_t)np;
-  struct Chunk { uint32_t lo, hi; uint64_t words, scratch; };
-  std::vector<Chunk> chunks;
-  {
-    Chunk c{0, 0, 0, 0};
-    for (uint32_t j = 0; j < np; ++j) {
-      const uint32_t i = order[j];
-      const uint32_t m = s1.length[i], n = s2.length[i];
-      const uint32_t P = num_passes(m, K[i]);
-      const uint64_t words = (uint64_t)P * steps_per_pass(n) * 64;
-      const uint64_t scr = P > 1 ? 2ull * ((uint64_t)n + 2) : 0;  // one boundary row per strand of the score launch (the traceback reuses the first)
-      const uint64_t need = words * 8 + scr * 8;
-      if (need > limit)
-        return set_error(TRACYHIP_ERR_OOM, "pair %u needs %llu bytes of traceback planes, workspace limit is %llu", i, (unsigned long long)need,
-                         (unsigned long long)limit);
-      if (c.hi > c.lo && (c.words + words) * 8 + (c.scratch + scr) * 8 > limit) {
-        chunks.push_back(c);
-        c = Chunk{j, j, 0, 0};
-      }
-      PairDesc d{};
-      d.a1_off = s1.offset[i];
-      d.a2_off = s2.offset[i];
-      d.m = m;
-      d.n = n;
-      d.a1_stride = m;
-      d.a2_stride = n;
-      d.flags = row4(i) ? PAIR_ROW4_ZERO : 0u;
-      d.scratch_off = c.scratch;
-      d.out = 2 * i;
-      hsd[2 * (size_t)j] = d;
-      d.a2_off = s2.offset[i] + rev_base;
-      d.scratch_off = c.scratch + (P > 1 ? (uint64_t)n + 2 : 0);
-      d.out = 2 * i + 1;
-      hsd[2 * (size_t)j + 1] = d;
-      d.a2_off = s2.offset[i];
-      d.scratch_off = c.scratch;
-      d.bits_off = c.words;
-      d.out = i;
-      htd[j] = d;
-      c.words += words;
-      c.scratch += scr;
-      c.hi = j + 1;
-    }
-    chunks.push_back(c);
+  ChunkCut cut(limit);
+  for (uint32_t j = 0; j < np; ++j) {
+    const uint32_t i = order[j];
+    const uint32_t m = s1.length[i], n = s2.length[i];
+    const uint32_t P = num_passes(m, K[i]);
+    const uint64_t words = (uint64_t)P * steps_per_pass(n) * 64;
+    const uint64_t scr = P > 1 ? 2ull * ((uint64_t)n + 2) : 0;  // one boundary row per strand of the score launch (the traceback reuses the first)
+    if (!cut.add(j, words * 8 + scr * 8, words, scr))
+      return set_error(TRACYHIP_ERR_OOM, "pair %u needs %llu bytes of traceback planes, workspace limit is %llu", i,
+                       (unsigned long long)cut.refused_bytes, (unsigned long long)limit);
+    PairDesc d{};
+    d.a1_off = s1.offset[i];
+    d.a2_off = s2.offset[i];
+    d.m = m;
+    d.n = n;
+    d.a1_stride = m;
+    d.a2_stride = n;
+    d.flags = row4(i) ? PAIR_ROW4_ZERO : 0u;
+    d.scratch_off = cut.scratch_off;
+    d.out = 2 * i;
+    hsd[2 * (size_t)j] = d;
+    d.a2_off = s2.offset[i] + rev_base;
+    d.scratch_off = cut.scratch_off + (P > 1 ? (uint64_t)n + 2 : 0);
+    d.out = 2 * i + 1;
+    hsd[2 * (size_t)j + 1] = d;
+    d.a2_off = s2.offset[i];
+    d.scratch_off = cut.scratch_off;
+    d.bits_off = cut.words_off;
+    d.out = i;
+    htd[j] = d;
   }
+  const std::vector<CutChunk>& chunks = cut.finish();
   uint64_t max_words = 0, max_scr = 0;
-  for (const Chunk& c : chunks) { max_words = std::max(max_words, c.words); max_scr = std::max(max_scr, c.scratch); }
+  for (const CutChunk& c : chunks) { max_words = std::max(max_words, c.words); max_scr = std::max(max_scr, c.scratch); }
   PairDesc* dsd; HIP_TRY(ensure_into(ctx->dev[DB_DESC], 3 * (size_t)np, dsd));
   HIP_TRY(hipMemcpyAsync(dsd, hsd, sizeof(PairDesc) * 3 * (size_t)np, hipMemcpyHostToDevice, st));
   PairDesc* dtd = dsd + 2 * (size_t)np;
@@ -345,7 +333,7 @@ int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tr
   ca.min_overlap = job->min_overlap;
   ca.match_fraction = (double)job->match_fraction;
 
-  for (const Chunk& c : chunks) {
+  for (const CutChunk& c : chunks) {
     // orientation scores: both strands of every pair of the chunk, one launch per run of equal strip height / term count
     a.scores = d_sc2;
     if ((rc = prof_score_runs(ctx, prm, wide, a, hsd, dsd, k_sorted.data(), c.lo, c.hi, narrow_launches))) return rc;
@@ -408,7 +396,7 @@ int consensus_run(tracyhip_ctx* ctx, const tracyhip_consensus_job* job, const tr
     ca.nfix = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(B[CB_FIX].p) + sizeof(ConsFixup) * (size_t)nfix);
     ca.fix_cap = nfix;
     HIP_TRY(hipMemsetAsync(ca.nfix, 0, sizeof(uint32_t), st));
-    for (const Chunk& c : chunks) {
+    for (const CutChunk& c : chunks) {
       ca.pairs = dtd + c.lo;
       hipLaunchKernelGGL(consensus_kernel, dim3(c.hi - c.lo), dim3(64), 0, st, ca);
       HIP_TRY(hipGetLastError());

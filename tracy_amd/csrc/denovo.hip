@@ -231,34 +231,23 @@ int denovo_run(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip
   // A round aligns every trace of a group with one partner.  The nodes of one height have disjoint leaves, so their sides m_k, n_k
   // sum to at most S; a sweep takes at most m / 256 + 1 passes of (n + 63) x 64 words: the planes of a height are bounded by
   // (S^2 / 1024 + 63 S / 256 + S + 32 K + 2) x 64 words (m n <= S^2 / 4 summed over the nodes), its boundary rows by S + K.
-  struct Chunk { uint32_t lo, hi; uint64_t bytes; };
-  std::vector<Chunk> chunks;
-  {
-    Chunk c{0, 0, 0};
-    for (uint32_t g = 0; g < ng; ++g) {
-      const uint64_t K = gf[g + 1] - gf[g];
-      uint64_t round_words = 0, round_scr = 0;
-      for (uint32_t i = gf[g] - t0; i < gf[g + 1] - t0; ++i) {
-        const uint32_t P = num_passes(len_of(i), KS[i]);
-        round_words += (uint64_t)P * steps_per_pass((uint32_t)maxlen[g]) * 64;
-        if (P > 1) round_scr += maxlen[g] + 2;
-      }
-      const uint64_t s = S[g];
-      const uint64_t tree_words = (s * s / 1024 + 63 * s / 256 + s + 32 * K + 2) * 64, tree_scr = s + K;
-      const uint64_t need = K < 2 ? 0 : std::max(round_words * 8 + round_scr * 8, tree_words * 8 + tree_scr * 8);
-      if (need > limit)
-        return set_error(TRACYHIP_ERR_OOM, "group %u needs %llu bytes of traceback planes, workspace limit is %llu", g, (unsigned long long)need,
-                         (unsigned long long)limit);
-      if (c.bytes && c.bytes + need > limit) {
-        c.hi = g;
-        chunks.push_back(c);
-        c = Chunk{g, g, 0};
-      }
-      c.bytes += need;
-      c.hi = g + 1;
+  ChunkCut cut(limit);
+  for (uint32_t g = 0; g < ng; ++g) {
+    const uint64_t K = gf[g + 1] - gf[g];
+    uint64_t round_words = 0, round_scr = 0;
+    for (uint32_t i = gf[g] - t0; i < gf[g + 1] - t0; ++i) {
+      const uint32_t P = num_passes(len_of(i), KS[i]);
+      round_words += (uint64_t)P * steps_per_pass((uint32_t)maxlen[g]) * 64;
+      if (P > 1) round_scr += maxlen[g] + 2;
     }
-    chunks.push_back(c);
+    const uint64_t s = S[g];
+    const uint64_t tree_words = (s * s / 1024 + 63 * s / 256 + s + 32 * K + 2) * 64, tree_scr = s + K;
+    const uint64_t need = K < 2 ? 0 : std::max(round_words * 8 + round_scr * 8, tree_words * 8 + tree_scr * 8);
+    if (!cut.add(g, need))
+      return set_error(TRACYHIP_ERR_OOM, "group %u needs %llu bytes of traceback planes, workspace limit is %llu", g, (unsigned long long)need,
+                       (unsigned long long)limit);
   }
+  const std::vector<CutChunk>& chunks = cut.finish();
 
   // ---- the call's own buffers ----
   uint8_t* d_ops; HIP_TRY(ensure_into(B[DN_OPS], std::max<uint64_t>(ob[ng], 1), d_ops));
@@ -290,7 +279,7 @@ int denovo_run(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip
   uint32_t total_rounds = 0, total_steps = 0;
   TraceBatch batch{hd, dd, d_ops, d_off, d_len, limit};  // the sweeps of an overlap round or a tree height: upload() sizes the planes for them
 
-  for (const Chunk& c : chunks) {
+  for (const CutChunk& c : chunks) {
     const uint32_t clo = gf[c.lo] - t0, chi = gf[c.hi] - t0;  // the chunk's traces
     // ---- the overlap test (assemble.h:425-456), one partner per undecided trace and round ----
     t_stage = clock_now();

@@ -16,6 +16,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "chunk_cut.h"
+
 namespace tracyhip {
 
 // choose_k (capi.hip) for profile x profile: the cheaper of 8 and 4 rows per lane by passes x height, 8 on a tie
@@ -66,28 +68,20 @@ inline bool wildtype_plan(const WtTrace* tr, uint32_t nt, uint64_t limit, uint32
   });
   p.bits_off.assign(nt, 0);
   p.scratch_off.assign(nt, 0);
-  WtChunk c{0, 0, 0, 0};
+  ChunkCut cut(limit);
   for (uint32_t j = 0; j < nt; ++j) {
     const WtTrace& t = tr[p.trace_order[j]];
     const uint64_t words = wt_plane_words(t.mf, t.n);
     const uint64_t scr = wt_boundary_rows(t.mf, t.mt, t.n, strands);
-    const uint64_t need = words * 8 + scr * 8;
-    if (need > limit) {
+    if (!cut.add(j, words * 8 + scr * 8, words, scr)) {
       p.too_large = p.trace_order[j];
-      p.need = need;
+      p.need = cut.refused_bytes;
       return false;
     }
-    if (c.hi > c.lo && (c.words + words) * 8 + (c.scratch + scr) * 8 > limit) {
-      p.chunks.push_back(c);
-      c = WtChunk{j, j, 0, 0};
-    }
-    p.bits_off[p.trace_order[j]] = c.words;
-    p.scratch_off[p.trace_order[j]] = c.scratch;
-    c.words += words;
-    c.scratch += scr;
-    c.hi = j + 1;
+    p.bits_off[p.trace_order[j]] = cut.words_off;
+    p.scratch_off[p.trace_order[j]] = cut.scratch_off;
   }
-  if (nt) p.chunks.push_back(c);
+  for (const CutChunk& c : cut.finish()) p.chunks.push_back(WtChunk{c.lo, c.hi, c.words, c.scratch});
   p.score_order = p.trace_order;
   for (const WtChunk& ch : p.chunks)
     std::stable_sort(p.score_order.begin() + ch.lo, p.score_order.begin() + ch.hi, [&](uint32_t x, uint32_t y) {
