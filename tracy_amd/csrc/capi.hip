@@ -841,8 +841,9 @@ int run_prefix_keep_cq(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, co
     uint64_t c = 0, b = 0;
     for (uint32_t i = lo; i < hi; ++i) {
       hd[i] = pre[i];
-      c += (uint64_t)std::min<uint32_t>(pre[i].m, kFrontRows) * pre[i].n;
-      b += (uint64_t)kFrontRows + pre[i].n + 4ull * pre[i].n;
+      const Credit x = prefix_credit(pre[i].m, pre[i].n, kFrontRows);
+      c += x.cells;
+      b += x.bytes;
     }
     cells[tid] = c; bytes[tid] = b;
   });
@@ -894,8 +895,9 @@ static int run_front_once(tracyhip_ctx* ctx, const std::vector<FrontDesc>& fd, c
       for (uint32_t i = lo; i < hi; ++i) {
         const FrontDesc& f = fd[i];
         m0 = std::max(m0, f.m_rest);
-        c0 += (uint64_t)b16_strips(f.m_rest, KB) * KB * (uint64_t)(KB + 2 * halfw);
-        b0 += 12ull * f.m_rest + f.m_rest + 2ull * halfw + 4ull * (2 * halfw + KB) + 8ull * f.n;  // tables, codes, the kept row (twice: place, certify)
+        const Credit x = front_credit(f.m_rest, f.n, KB, halfw);
+        c0 += x.cells;
+        b0 += x.bytes;
       }
       mr[tid] = m0; cs[tid] = c0; bs[tid] = b0;
     });
@@ -904,8 +906,8 @@ static int run_front_once(tracyhip_ctx* ctx, const std::vector<FrontDesc>& fd, c
   Band16Args a{};
   a.pairs = d_pairs; a.npairs = (uint32_t)nf; a.qp = d_qp; a.codes = d_codes ? d_codes : ctx->codes(); a.scores = d_fs; a.ends = d_fe;
   a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p); a.go = prm->go; a.ge = prm->ge; a.hfree = 1; a.row = d_row;
-  a.code_cap = (max_rest + 2u * (uint32_t)halfw + 16u) & ~3u;  // front_place_body: a sub-window is at most m_rest + 2 halfw + 2 columns
-  if (4ull * a.code_cap + b16_table_bytes(KB) + 32ull * kB16RowCap > 64u * 1024u)
+  a.code_cap = front_code_cap(max_rest, halfw);
+  if (!front_tier_fits(KB, halfw, max_rest))
     return set_error(TRACYHIP_ERR_RANGE, "run_front: traces of %u rows do not fit the staging area", max_rest);
   int trc;
   if ((trc = timing_begin(ctx, TRACYHIP_TIMER_FRONT, cells, bytes))) return trc;
@@ -932,7 +934,7 @@ static int run_front_once(tracyhip_ctx* ctx, const std::vector<FrontDesc>& fd, c
 int run_front(tracyhip_ctx* ctx, const std::vector<FrontDesc>& fd, const int16_t* d_qp, const uint32_t* d_row, const tracyhip_params* prm,
               FrontResult& out, const uint8_t* d_codes, bool keep_err) {
   int rc;
-  if ((rc = run_front_once(ctx, fd, d_qp, d_row, prm, out, d_codes, keep_err, 8, 60))) return rc;
+  if ((rc = run_front_once(ctx, fd, d_qp, d_row, prm, out, d_codes, keep_err, kFrontK1, kFrontHalfW1))) return rc;
   std::vector<FrontDesc> again;
   std::vector<uint32_t> idx;
   for (size_t i = 0; i < fd.size(); ++i)
@@ -1005,13 +1007,13 @@ int build_problem(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, int mem, bool 
   // strip height per a1 sequence (not per pair: an all-pairs list names every sequence a thousand times)
   std::vector<int> kseq(s1.count);
   for (uint32_t i = 0; i < s1.count; ++i) kseq[i] = choose_k(s1.length[i], pb.mode, needle);
-  // long pair lists are filled by a few threads (the list of an all-pairs job is 36 MB of descriptors)
+  // long pair lists are filled in slices on the host pool (the list of an all-pairs job is 36 MB of descriptors); a slice ends at its
+  // first bad pair, so the first slice that has one names the first of the list
   const uint32_t npairs = pairs->npairs;
-  const uint32_t nthr = npairs >= (1u << 16) ? 8u : 1u;
-  std::vector<uint64_t> tmax(nthr, 0);
-  std::vector<uint32_t> tbad(nthr, ~0u);
-  auto fill = [&](uint32_t tid) {
-    const uint32_t lo = (uint32_t)((uint64_t)npairs * tid / nthr), hi = (uint32_t)((uint64_t)npairs * (tid + 1) / nthr);
+  uint64_t tmax[kHostThreads] = {};
+  uint32_t tbad[kHostThreads];
+  for (uint32_t& b : tbad) b = ~0u;
+  auto fill = [&](uint32_t lo, uint32_t hi, uint32_t tid) {
     uint64_t mx = 0;
     for (uint32_t i = lo; i < hi; ++i) {
       const uint32_t i1 = pairs->a1_index ? pairs->a1_index[i] : i;
@@ -1032,13 +1034,9 @@ int build_problem(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, int mem, bool 
     }
     tmax[tid] = mx;
   };
-  if (nthr == 1) fill(0);
-  else {
-    std::vector<std::thread> th;
-    for (uint32_t t = 0; t < nthr; ++t) th.emplace_back(fill, t);
-    for (auto& t : th) t.join();
-  }
-  for (uint32_t t = 0; t < nthr; ++t) {
+  if (npairs >= (1u << 16)) parallel_for(npairs, fill);
+  else fill(0u, npairs, 0u);
+  for (uint32_t t = 0; t < kHostThreads; ++t) {
     if (tbad[t] != ~0u) return set_error(TRACYHIP_ERR_ARG, "pair %u indexes past the sequence sets", tbad[t]);
     *max_mn = std::max(*max_mn, tmax[t]);
   }
@@ -1058,15 +1056,10 @@ int run_ckpt_prefix(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, const
   if (nf + np == 0) return TRACYHIP_OK;
   auto hs1 = std::make_unique<HostScope>("run_ckpt_prefix.plan");
   PairDesc* hd; HIP_TRY(ensure_into(ctx->pin[PB_DESC], nf + np, hd));
-  // the sweeps by strip height (one launch each; the prefix workgroups ride with the first), longest first inside a launch, as
-  // run_dp orders them
-  std::vector<uint32_t> order(nf);
-  for (uint32_t i = 0; i < nf; ++i) order[i] = i;
-  auto before = [&](uint32_t x, uint32_t y) {
-    if (fullk[x] != fullk[y]) return fullk[x] > fullk[y];
-    return (uint64_t)full[x].m * full[x].n > (uint64_t)full[y].m * full[y].n;
-  };
-  if (!std::is_sorted(order.begin(), order.end(), before)) std::stable_sort(order.begin(), order.end(), before);
+  // the sweeps by strip height (one launch each; the prefix workgroups ride with the first), longest first inside a launch: run_dp's
+  // order without the flag (profile x code), and sorted even when the list is of a size
+  std::vector<uint32_t> order;
+  order_sweeps((uint32_t)nf, [&](uint32_t i) { return SweepKey{fullk[i], 0u, (uint64_t)full[i].m * full[i].n}; }, false, order);
   for (size_t i = 0; i < nf; ++i) hd[i] = full[order[i]];
   for (size_t i = 0; i < np; ++i) hd[nf + i] = pre[i];
   HIP_TRY(ctx->dev[DB_DESC].ensure(sizeof(PairDesc) * (nf + np)));
@@ -1094,8 +1087,8 @@ int run_ckpt_prefix(tracyhip_ctx* ctx, const void* d_a1, const void* d_a2, const
     uint32_t maxm = 0;
     if (ctx->timing) {
       uint64_t cells = 0, bytes = 0;
-      for (size_t i = lo; i < hi; ++i) { cells += (uint64_t)hd[i].m * hd[i].n; bytes += 24ull * hd[i].m + hd[i].n + 4; }
-      for (size_t i = 0; i < npre; ++i) cells += (uint64_t)std::min<uint32_t>(hd[nf + i].m, prows) * hd[nf + i].n;
+      for (size_t i = lo; i < hi; ++i) { const Credit x = sweep_pair_credit(hd[i].m, hd[i].n, true, false); cells += x.cells; bytes += x.bytes; }
+      for (size_t i = 0; i < npre; ++i) cells += prefix_credit(hd[nf + i].m, hd[nf + i].n, prows).cells;  // (their bytes: with the tiers they begin, or none)
       if ((trc = timing_begin(ctx, TRACYHIP_TIMER_SCORE, cells, bytes))) return trc;
     }
     for (size_t i = lo; i < hi; ++i) { maxm = std::max(maxm, hd[i].m); max_mn = std::max<uint64_t>(max_mn, (uint64_t)hd[i].m + hd[i].n); }

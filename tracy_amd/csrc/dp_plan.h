@@ -16,6 +16,7 @@
 #include "band16.h"
 #include "chunk_cut.h"
 #include "dp_kernels.h"
+#include "launch_rules.h"
 
 namespace tracyhip {
 
@@ -49,27 +50,22 @@ struct SweepPlan {
 inline uint64_t sweep_words(const PairDesc& d, int K, bool planes) { return (planes && d.m && d.n) ? (uint64_t)num_passes(d.m, K) * steps_per_pass(d.n) * 64 : 0; }
 inline uint64_t sweep_scratch(const PairDesc& d, int K) { return (d.m && d.n && num_passes(d.m, K) > 1) ? (uint64_t)d.n + 2 : 0; }
 
-// order: strip height, then longest first (long problems start early, short ones fill the tail)
+// order[i] = i, then sorted by sweep_before (launch_rules.h) over key(i): stably, and only a list that is not in order already.
+// keep: the caller's order stays (a list "of a size")
+template <class Key>
+void order_sweeps(uint32_t n, Key key, bool keep, std::vector<uint32_t>& order) {
+  order.resize(n);
+  for (uint32_t i = 0; i < n; ++i) order[i] = i;
+  auto before = [&](uint32_t x, uint32_t y) { return sweep_before(key(x), key(y)); };
+  if (!keep && !std::is_sorted(order.begin(), order.end(), before)) std::stable_sort(order.begin(), order.end(), before);
+}
+// run_dp's order.  Batches of a size -- the final alignments of a `tracy align` batch -- keep the caller's and save the host the sort
+// between two kernels (profile x profile: 16-term pairs and 25-term pairs go to different launches, hence the flag)
 inline void sweep_order(const PairDesc* desc, const int* k, uint32_t np, std::vector<uint32_t>& order) {
-  order.resize(np);
-  for (uint32_t i = 0; i < np; ++i) order[i] = i;
-  auto before = [&](uint32_t x, uint32_t y) {
-    if (k[x] != k[y]) return k[x] > k[y];
-    const uint32_t fx = desc[x].flags & PAIR_ROW4_ZERO, fy = desc[y].flags & PAIR_ROW4_ZERO;
-    if (fx != fy) return fx > fy;  // profile x profile: 16-term pairs and 25-term pairs go to different launches
-    return (uint64_t)desc[x].m * desc[x].n > (uint64_t)desc[y].m * desc[y].n;
-  };
-  // (the order only balances the tail of a launch: batches of one strip height whose sizes lie within 25 % of each other --
-  // the final alignments of a `tracy align` batch -- keep the caller's order and save the host the sort between two kernels)
-  bool similar = true;
-  uint64_t lo = ~0ull, hi = 0;
-  for (uint32_t i = 0; i < np && similar; ++i) {
-    const uint64_t c = (uint64_t)desc[i].m * desc[i].n;
-    lo = std::min(lo, c); hi = std::max(hi, c);
-    similar = k[i] == k[0] && (desc[i].flags & PAIR_ROW4_ZERO) == (desc[0].flags & PAIR_ROW4_ZERO);
-  }
-  similar = similar && hi <= lo + lo / 4;
-  if (!similar && !std::is_sorted(order.begin(), order.end(), before)) std::stable_sort(order.begin(), order.end(), before);
+  auto key = [&](uint32_t i) { return SweepKey{k[i], desc[i].flags & PAIR_ROW4_ZERO, (uint64_t)desc[i].m * desc[i].n}; };
+  SizeSpan span;
+  for (uint32_t i = 0; i < np && span.one; ++i) span.add(key(i));
+  order_sweeps(np, key, span.of_a_size(), order);
 }
 
 // The plan of one run_dp call.  hd (np entries: the pinned staging block) receives the descriptors in launch order with bits_off and
@@ -148,7 +144,8 @@ inline void sweep_credit(const PairDesc* hd, uint32_t lo, uint32_t hi, int K, bo
   cells = bytes = 0;
   for (uint32_t q = lo; q < hi; ++q) {
     const PairDesc& d = hd[q];
-    uint64_t mn = (uint64_t)(stage == DP_PREFIX ? std::min<uint32_t>(d.m, (uint32_t)kPrefixLanes * K) : d.m) * d.n;
+    const Credit full = sweep_pair_credit(d.m, d.n, a1_profile, a2_profile);
+    uint64_t mn = stage == DP_PREFIX ? prefix_credit(d.m, d.n, (uint32_t)kPrefixLanes * K).cells : full.cells;
     if (trace && stage == DP_PLAIN && (d.flags & PAIR_BANDED)) {  // multi-pass band form: the cells its passes sweep, not the matrix
       mn = 0;
       for (uint32_t base = 0; base < d.m; base += 64u * K) {
@@ -158,7 +155,7 @@ inline void sweep_credit(const PairDesc* hd, uint32_t lo, uint32_t hi, int K, bo
       }
     }
     cells += mn;
-    bytes += (trace ? mn / 2 : 0) + (a1_profile ? 24ull * d.m : d.m) + (a2_profile ? 24ull * d.n : d.n) + 4;
+    bytes += (trace ? mn / 2 : 0) + full.bytes;
   }
   if (stage == DP_BAND) bytes = 0;  // (the bands live in a per-pair buffer, no matrix-sized traffic)
 }
@@ -166,18 +163,9 @@ inline void sweep_credit(const PairDesc* hd, uint32_t lo, uint32_t hi, int K, bo
 // ---- the band kernels (run_band16) ----------------------------------------------------------------------------------
 constexpr int kBandHeights = 3;
 constexpr int kBandK[kBandHeights] = {12, 8, 4};  // launch order: the caller's order within one height (the pairs of a pipeline stage are of a size)
-inline int band_bucket(int K) { return K == 12 ? 0 : K == 8 ? 1 : K == 4 ? 2 : -1; }
 constexpr uint32_t kBandMultiMax = 24576;  // pairs: up to here a launch of several heights is few waves, and band16_multi_kernel takes them at once
 
 inline bool band_in_domain(const PairDesc& d, int K) { return band_bucket(K) >= 0 && d.m != 0 && d.n != 0 && b16_window(K, band_dmin(d), band_dmax(d)) <= b16_max_window(K); }
-// bytes of traceback words of a pair (kind 0; the origin form keeps none), rounded to 16
-inline uint64_t band_word_bytes(const PairDesc& d, int K, int kind) {
-  return kind == 0 ? ((b16_store_words(d.m, d.n, K, band_dmin(d), band_dmax(d)) * b16_word_bytes(K) + 15u) & ~15ull) : 0;
-}
-// code rows of a launch whose longest reference has nmax columns, and whether four of them fit the 64 KB of LDS beside the tables
-inline uint32_t band_code_cap(uint32_t nmax) { return (nmax + 7u) & ~3u; }
-inline bool band_lds_fits(uint32_t code_cap, int K) { return 4ull * code_cap + b16_table_bytes(K) <= 64u * 1024u; }
-
 struct BandTally {  // the pairs of one height in one launch: count, longest reference, word bytes, and what the timers are credited
   uint32_t n = 0, nmax = 0;
   uint64_t word_bytes = 0, cells = 0, bytes = 0;
@@ -186,9 +174,9 @@ struct BandTally {  // the pairs of one height in one launch: count, longest ref
     nmax = std::max(nmax, d.n);
     word_bytes += wb;
     if (!credit) return;
-    const uint64_t wds = b16_words(d.m, d.n, K, band_dmin(d), band_dmax(d));
-    cells += wds * (uint64_t)K;
-    bytes += (kind == 0 ? wds * b16_word_bytes(K) : 0) + 12ull * d.m + d.n + 4;
+    const Credit c = band_credit(d, K, kind);
+    cells += c.cells;
+    bytes += c.bytes;
   }
   void add(const BandTally& o) { n += o.n; nmax = std::max(nmax, o.nmax); word_bytes += o.word_bytes; cells += o.cells; bytes += o.bytes; }
 };
@@ -219,7 +207,7 @@ inline void band_launches(const BandTally* t, uint32_t lo, std::vector<BandLaunc
   BandTally sum;
   for (int b = 0; b < kBandHeights; ++b) { first[b] = lo + sum.n; used += t[b].n != 0; sum.add(t[b]); }
   const uint32_t cap_all = band_code_cap(sum.nmax);
-  if (sum.n <= kBandMultiMax && used > 1 && band_lds_fits(cap_all, 12)) {  // few waves, several heights: band16_multi_kernel
+  if (sum.n <= kBandMultiMax && used > 1 && band_lds_fits(cap_all, 12, kBandLdsHard)) {  // few waves, several heights: band16_multi_kernel
     BandLaunch l{0, {first[0], first[1], first[2]}, {t[0].n, t[1].n, t[2].n}, sum.nmax, cap_all, sum.cells, sum.bytes, true};
     out.push_back(l);
     return;
@@ -228,7 +216,7 @@ inline void band_launches(const BandTally* t, uint32_t lo, std::vector<BandLaunc
     if (t[b].n == 0) continue;
     BandLaunch l{kBandK[b], {first[b], first[b], first[b]}, {0, 0, 0}, t[b].nmax, band_code_cap(t[b].nmax), t[b].cells, t[b].bytes, false};
     l.count[b] = t[b].n;
-    l.fits = band_lds_fits(l.code_cap, l.K);
+    l.fits = band_lds_fits(l.code_cap, l.K, kBandLdsHard);
     out.push_back(l);
   }
 }

@@ -24,7 +24,9 @@
 
 namespace tracyhip {
 
-constexpr int kFrontK = 12;
+constexpr int kFrontK1 = 8;  // the first tier: strips of 8 rows on c* +- 60 (a step of 8 cells costs two thirds of a step of 12)
+constexpr int32_t kFrontHalfW1 = 60;
+constexpr int kFrontK = 12;  // the tier for what the first did not certify
 constexpr int32_t kFrontHalfW = 90;  // 2 * 90 + 12 <= 15 * 13: the widest band one period of the K = 12 strips holds
 
 struct FrontDesc {

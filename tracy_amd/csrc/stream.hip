@@ -67,6 +67,12 @@ __device__ __forceinline__ void with_counters(unsigned long long* cnt, Body body
   for (uint32_t i = threadIdx.x; i < (uint32_t)SC_COUNT; i += blockDim.x)
     if (lc[i]) atomicAdd(cnt + i, lc[i]);
 }
+// the first tier of a pruned sweep (TRACYHIP_TIMER_FRONT: what run_front_once credits for the same tier)
+__device__ __forceinline__ void s_count_front(unsigned long long* lc, const FrontDesc& f) {
+  const Credit c = front_credit(f.m_rest, f.n, kFrontK1, kFrontHalfW1);
+  s_count(lc, SC_FRONT_CELLS, c.cells);
+  s_count(lc, SC_FRONT_BYTES, c.bytes);
+}
 
 // Wave priority (band16_launch.h wave_prio) of a launch that is being queued: tier 1 -- the tiers of the pruned sweep and the early
 // decision -- from option chain_prio = 1 on, tier 2 -- the early tail's stages -- at 2; nonzero only while queue_orientation queues the voted
@@ -121,7 +127,8 @@ __global__ void s_orient_plan_kernel(SParams p, const SGeom* __restrict__ geom, 
   f.flags = PAIR_SKIP;
   f.out = t;
   uint64_t cells = 0, bytes = 0, pcells = 0;
-  const uint64_t full_cells = (uint64_t)G.mt * G.rn, pre_cells = (uint64_t)(G.mt < R ? G.mt : R) * G.rn, full_bytes = 24ull * G.mt + G.rn + 4;
+  const Credit full_c = sweep_pair_credit(G.mt, G.rn, true, false), pre_c = prefix_credit(G.mt, G.rn, R);
+  const uint64_t full_cells = full_c.cells, pre_cells = pre_c.cells, full_bytes = full_c.bytes;
   if (cls == 0u) {
     pa = s_stage1_desc(G, t, p.nt, g);
     pa.flags |= PAIR_KEEP_ROW;
@@ -138,8 +145,7 @@ __global__ void s_orient_plan_kernel(SParams p, const SGeom* __restrict__ geom, 
     f.R = R;
     f.rest = ub[t];
     f.tight = (p.ge <= -2 && ub1[t] <= ub[t]) ? (uint32_t)(ub[t] - ub1[t]) + 1u : 0u;
-    s_count(lc, SC_FRONT_CELLS, s_front_cells(f.m_rest));
-    s_count(lc, SC_FRONT_BYTES, s_front_bytes(f.m_rest, f.n));
+    s_count_front(lc, f);
   } else if (cls == 1u) {
     fa = s_stage1_desc(G, t, p.nt, g);
     fb = s_stage1_desc(G, t, p.nt, 1u - g);
@@ -150,7 +156,7 @@ __global__ void s_orient_plan_kernel(SParams p, const SGeom* __restrict__ geom, 
     cells += full_cells; pcells += pre_cells; bytes += full_bytes;
   }
   // the prefixes: part of the sweep launch, or -- in a launch of their own beside it -- of the pruned sweep they begin
-  if (p.split_prefix) { s_count(lc, SC_FRONT_CELLS, pcells); s_count(lc, SC_FRONT_BYTES, pcells ? (uint64_t)R + 5ull * G.rn : 0ull); }
+  if (p.split_prefix) { s_count(lc, SC_FRONT_CELLS, pcells); s_count(lc, SC_FRONT_BYTES, pcells ? pre_c.bytes : 0ull); }
   else cells += pcells;
   full[G.full_a] = fa;
   full[G.full_b] = fb;
@@ -331,11 +337,8 @@ constexpr uint32_t kScanBlock = 256, kScanWaves = kScanBlock / 64;
 struct ScanPart { uint32_t n[4]; unsigned long long bytes; };
 // lists: strip height 12, 8, 4, and the quad form (strip height 4, four lanes per pair) for the narrow bands when the launch has room for it
 __device__ __forceinline__ int s_bucket(int K, const PairDesc& d, int quads) {
-  return K == 12 ? 0 : K == 8 ? 1 : (quads && b16_narrow_ok(band_dmin(d), band_dmax(d))) ? 3 : 2;
-}
-__device__ __forceinline__ unsigned long long s_word_bytes(const PairDesc& d, int K, int kind, unsigned long long* words = nullptr) {
-  if (words) *words = b16_words(d.m, d.n, K, band_dmin(d), band_dmax(d));
-  return kind == 0 ? ((b16_store_words(d.m, d.n, K, band_dmin(d), band_dmax(d)) * b16_word_bytes(K) + 15ull) & ~15ull) : 0ull;
+  const int b = band_bucket(K);  // (kc holds 12, 8 or 4: every other value lands in the lists of height 4, never outside them)
+  return (b == 0 || b == 1) ? b : (quads && b16_narrow_ok(band_dmin(d), band_dmax(d))) ? 3 : 2;
 }
 // sums over the 64 lanes of a wave (every lane gets the sum); the totals of a block's four waves, which lane 0 of each left in LDS
 __device__ __forceinline__ uint32_t s_wave_sum(uint32_t v) {
@@ -363,7 +366,7 @@ __global__ __launch_bounds__(kScanBlock) void s_scan_count_kernel(const PairDesc
   if (K) {
     const PairDesc d = cand[i];
     bucket = s_bucket(K, d, quads);
-    mine = s_word_bytes(d, K, kind);
+    mine = band_word_bytes(d, K, kind);
   }
   ScanPart w;
   for (int b = 0; b < 4; ++b) w.n[b] = (uint32_t)__popcll(__ballot(bucket == b));
@@ -395,8 +398,9 @@ __global__ __launch_bounds__(kScanBlock) void s_scan_place_kernel(PairDesc* __re
   const uint32_t i = blockIdx.x * kScanBlock + tid;
   const int K = i < n ? kc[i] : 0;
   PairDesc d{};
-  unsigned long long words = 0, mine = 0;
-  if (K) { d = cand[i]; mine = s_word_bytes(d, K, kind, &words); }
+  unsigned long long mine = 0;
+  Credit credit{0, 0};  // (what BandTally::add credits a pair of run_band16; before the word bytes, which then share its divisions)
+  if (K) { d = cand[i]; credit = band_credit(d, K, kind); mine = band_word_bytes(d, K, kind); }
   const int bucket = K ? s_bucket(K, d, quads) : -1;
   const unsigned long long below = (1ull << L) - 1ull;
   ScanPart w;
@@ -434,8 +438,8 @@ __global__ __launch_bounds__(kScanBlock) void s_scan_place_kernel(PairDesc* __re
       atomicOr(dead + (i % unit_mod), SD_MEM);
     } else {
       cand[i].bits_off = off;
-      atomicAdd(&s_stat[0], words * (unsigned long long)K);
-      atomicAdd(&s_stat[1], (kind == 0 ? words * b16_word_bytes(K) : 0ull) + 12ull * d.m + d.n + 4ull);
+      atomicAdd(&s_stat[SB_CELLS], (unsigned long long)credit.cells);
+      atomicAdd(&s_stat[SB_BYTES], (unsigned long long)credit.bytes);
       atomicAdd(&s_stat[2], mine);
       atomicAdd(&s_stat[SB_HIST + s_width_bucket(band_dmin(d), band_dmax(d))], 1ull);
     }
@@ -622,9 +626,8 @@ struct StreamHost {
   uint64_t max_mn = 0;
 };
 
-// the order of the full sweeps: strip height, then longest first (long problems start early, short ones fill the tail) -- as run_dp
-// and run_ckpt_prefix order them, and like them without a sort when the batch is of a size (`similar`, found by the caller's pass over
-// the lengths: then the order is the traces' own and `order` stays empty)
+// the order of the full sweeps: run_dp's (order_sweeps, dp_plan.h; no flag: profile x code), and like it none when the batch is of a
+// size (`similar`: the SizeSpan of the caller's pass over the lengths) -- then the order is the traces' own and `order` stays empty
 void sweep_order(StreamHost& h, std::vector<uint32_t>& order, const std::vector<int>& kof, bool similar) {
   const uint32_t nt = h.nt;
   h.classes.clear();
@@ -633,13 +636,7 @@ void sweep_order(StreamHost& h, std::vector<uint32_t>& order, const std::vector<
     if (nt) h.classes.push_back(SweepClass{kof[0], 0u, nt});
     return;
   }
-  order.resize(nt);
-  for (uint32_t t = 0; t < nt; ++t) order[t] = t;
-  auto before = [&](uint32_t x, uint32_t y) {
-    if (kof[x] != kof[y]) return kof[x] > kof[y];
-    return (uint64_t)h.mt[x] * h.rn[x] > (uint64_t)h.mt[y] * h.rn[y];
-  };
-  if (!std::is_sorted(order.begin(), order.end(), before)) std::stable_sort(order.begin(), order.end(), before);
+  order_sweeps(nt, [&](uint32_t t) { return SweepKey{kof[t], 0u, (uint64_t)h.mt[t] * h.rn[t]}; }, false, order);
   for (uint32_t i = 0; i < nt;) {
     uint32_t e = i;
     while (e < nt && kof[order[e]] == kof[order[i]]) ++e;
@@ -696,13 +693,9 @@ DpArgs sweep_args(tracyhip_ctx* ctx, const tracyhip_params& p, const void* d_a1,
   return a;
 }
 
-// LDS of a wide tier's band launch for the longest rest of the batch: tested by the planners BEFORE anything of a call is queued (a tier
-// that finds no room once launches are in flight would hand the call back with the workspace still in use)
-bool front_tier_fits(int KB, int32_t halfw, uint32_t max_rest) {
-  const uint64_t code_cap = (max_rest + 2u * (uint32_t)halfw + 16u) & ~3u;
-  return 4ull * code_cap + b16_table_bytes(KB) + 32ull * kB16RowCap <= 64u * 1024u;
-}
-bool front_tiers_fit(uint32_t max_rest) { return front_tier_fits(8, 60, max_rest) && front_tier_fits(kFrontK, kFrontHalfW, max_rest); }
+// LDS of the wide tiers' band launches for the longest rest of the batch: tested by the planners BEFORE anything of a call is queued (a
+// tier that finds no room once launches are in flight would hand the call back with the workspace still in use)
+bool front_tiers_fit(uint32_t max_rest) { return front_tier_fits(kFrontK1, kFrontHalfW1, max_rest) && front_tier_fits(kFrontK, kFrontHalfW, max_rest); }
 
 // one tier of the pruned sweep over fixed slots: place, band below the kept row, certify (capi.hip run_front_once)
 // KB = 0: the quad form (strips of four rows, four lanes per pair) -- the narrow tier ahead of the others
@@ -715,9 +708,9 @@ int front_tier(tracyhip_ctx* ctx, const tracyhip_params& p, const FrontDesc* fd,
   a.err = static_cast<int32_t*>(ctx->dev[DB_ERR].p); a.go = p.go; a.ge = p.ge; a.hfree = 1; a.row = d_row;
   const int prio = queued_prio(ctx, 1);
   a.prio = prio;
-  a.code_cap = (max_rest + 2u * (uint32_t)halfw + 16u) & ~3u;  // front_place_body: a sub-window is at most m_rest + 2 halfw + 2 columns
+  a.code_cap = front_code_cap(max_rest, halfw);
   if (KB == 0) {
-    if (b16_cont_quad_lds(a.code_cap) > 64u * 1024u) return kStreamNo;  // (front_tiers_run goes on with the wide tiers: nothing was queued for this one)
+    if (b16_cont_quad_lds(a.code_cap) > kBandLdsHard) return kStreamNo;  // (front_tiers_run goes on with the wide tiers: nothing was queued for this one)
   } else if (!front_tier_fits(KB, halfw, max_rest)) return set_error(TRACYHIP_ERR_ARG, "pruned-sweep tier without LDS room (front_tiers_fit not consulted)");
   HIP_TRY(launch_front_place(fd, n, d_row, p.go + p.ge, halfw, pairs, fo, st, prev, list, list_count, prio));
   if (KB == 0) HIP_TRY(launch_band16_cont_quad(a, st));
@@ -784,7 +777,7 @@ int front_tiers_run_wide(tracyhip_ctx* ctx, const tracyhip_params& p, StreamComm
   if (lists) HIP_TRY(hipMemsetAsync(sc.fcount, 0, 2 * sizeof(uint32_t), ctx->stream));
   const bool list1 = lists && after_quads;
   if (list1) HIP_TRY(front_list(ctx, n, sc.fo0, sc.flist, sc.fcount, sc.fo1));  // (what the quads certified is folded into fo1 below)
-  int rc = front_tier(ctx, p, sc.fd, n, d_qp, d_codes, d_row, 8, 60, max_rest, sc.fpairs1, sc.fo1, sc.fs1, sc.fe1, after_quads ? sc.fo0 : nullptr,
+  int rc = front_tier(ctx, p, sc.fd, n, d_qp, d_codes, d_row, kFrontK1, kFrontHalfW1, max_rest, sc.fpairs1, sc.fo1, sc.fs1, sc.fe1, after_quads ? sc.fo0 : nullptr,
                       list1 ? sc.flist : nullptr, list1 ? sc.fcount : nullptr);
   if (rc) return rc;
   if (after_quads) {
@@ -813,7 +806,7 @@ int front_tiers_run(tracyhip_ctx* ctx, const tracyhip_params& p, StreamCommon& s
 }
 
 // a band launch over the candidates of `n` units: lists per strip height (scan), the three heights (sizes read on the device)
-struct BandLaunch {
+struct BandStageArgs {
   int kind = 0;
   const int16_t* qp = nullptr;
   const uint8_t* codes = nullptr;
@@ -825,11 +818,11 @@ struct BandLaunch {
   uint32_t code_cap = 0;
   int hfree = 1;
 };
-int band_stage(tracyhip_ctx* ctx, const tracyhip_params& p, StreamCommon& sc, uint32_t n, uint32_t unit_mod, int stage_no, const BandLaunch& bl, uint64_t cap_bytes) {
+int band_stage(tracyhip_ctx* ctx, const tracyhip_params& p, StreamCommon& sc, uint32_t n, uint32_t unit_mod, int stage_no, const BandStageArgs& bl, uint64_t cap_bytes) {
   hipStream_t st = ctx->stream;
   uint32_t* count = sc.count + 4 * stage_no;
   const uint32_t nb = (n + kScanBlock - 1) / kScanBlock;
-  const int quads = (!ctx->knobs.no_quads && b16_quad_lds(bl.code_cap) <= 64u * 1024u) ? 1 : 0;  // the narrow bands four lanes to a pair, where sixteen code rows fit
+  const int quads = (!ctx->knobs.no_quads && b16_quad_lds(bl.code_cap) <= kBandLdsHard) ? 1 : 0;  // the narrow bands four lanes to a pair, where sixteen code rows fit
   const int prio = queued_prio(ctx, 2);
   hipLaunchKernelGGL(s_scan_count_kernel, dim3(nb), dim3(kScanBlock), 0, st, sc.cand, sc.kc, n, bl.kind, quads, sc.part, prio);
   hipLaunchKernelGGL(s_scan_place_kernel, dim3(nb), dim3(kScanBlock), 0, st, sc.cand, sc.kc, n, unit_mod, bl.kind, quads, (unsigned long long)cap_bytes, sc.part, sc.idx, sc.dead,
@@ -1023,18 +1016,18 @@ int plan_common(tracyhip_ctx* ctx, const tracyhip_params& p, const tracyhip_seqs
   static thread_local std::vector<int> kof_tls;  // (kept between calls; the worker threads reach the CALLER's vector through the reference)
   std::vector<int>& kof = kof_tls;
   kof.resize(nt);
-  bool odd_shape = false, similar = true;
+  bool odd_shape = false, similar = false;
   uint64_t lr_base[kHostThreads], tab_base[kHostThreads];  // workspace offsets of the slices' first traces (trace order)
   {
     // ONE pass over the job's length arrays (the device waits while the host plans: round 6 measured 2.3 ms per 100 000-trace call in
     // seven passes): lengths, trims, extremes, the strip height of every trace's sweep, whether the batch is of the one-pass shape and
     // whether it is "of a size" (one strip height, cell counts within a quarter of each other: the sweeps then run in the traces' order)
     TRACYHIP_HOST_SCOPE(hs1, "plan_common.lengths");
-    struct Part { uint64_t max_mn, cmin, cmax, lr, tab; uint32_t maxmt, maxmf, bad; int k0; bool odd, onek; };
+    struct Part { uint64_t max_mn, lr, tab; uint32_t maxmt, maxmf, bad; bool odd; SizeSpan span; };
     Part part[kHostThreads];
-    for (auto& x : part) x = Part{0, ~0ull, 0, 0, 0, 0, 0, ~0u, 0, false, true};
+    for (auto& x : part) x = Part{0, 0, 0, 0, 0, ~0u, false, SizeSpan()};
     parallel_for(nt, [&](uint32_t lo, uint32_t hi, uint32_t tid) {
-      Part x{0, ~0ull, 0, 0, 0, 0, 0, ~0u, 0, false, true};
+      Part x{0, 0, 0, 0, 0, ~0u, false, SizeSpan()};
       for (uint32_t t = lo; t < hi; ++t) {
         h.ridx[t] = ref_index ? ref_index[t] : t;
         if (h.ridx[t] >= sr.count) { x.bad = std::min(x.bad, t); h.ridx[t] = 0; if (sr.count == 0) continue; }
@@ -1049,11 +1042,8 @@ int plan_common(tracyhip_ctx* ctx, const tracyhip_params& p, const tracyhip_seqs
         x.maxmf = std::max(x.maxmf, h.mf[t]);
         const int K = choose_k(h.mt[t], MODE_QP);
         kof[t] = K;
-        if (t == lo) x.k0 = K;
-        x.onek = x.onek && K == x.k0;
         x.odd = x.odd || h.mt[t] == 0 || h.rn[t] == 0 || num_passes(h.mt[t], K) != 1;
-        const uint64_t c = (uint64_t)h.mt[t] * h.rn[t];
-        x.cmin = std::min(x.cmin, c); x.cmax = std::max(x.cmax, c);
+        x.span.add(SweepKey{K, 0u, (uint64_t)h.mt[t] * h.rn[t]});
         x.lr += 4ull * ((uint64_t)h.rn[t] + 1);  // (workspace of the slice's traces: row-m words of both strands, substitution tables)
         x.tab += (uint64_t)kB16Codes * b16_table_stride(h.mf[t]);
       }
@@ -1062,17 +1052,13 @@ int plan_common(tracyhip_ctx* ctx, const tracyhip_params& p, const tracyhip_seqs
     });
     for (uint32_t i = 0; i < kHostThreads; ++i) { lr_base[i] = h.lr_tot; tab_base[i] = h.tab_tot; h.lr_tot += part[i].lr; h.tab_tot += part[i].tab; }
     uint32_t bad = ~0u;
-    uint64_t cmin = ~0ull, cmax = 0;
-    int k0 = 0;
+    SizeSpan span;
     for (const Part& x : part) {
       h.max_mn = std::max(h.max_mn, x.max_mn); h.maxmt = std::max(h.maxmt, x.maxmt); h.maxmf = std::max(h.maxmf, x.maxmf); bad = std::min(bad, x.bad);
       odd_shape = odd_shape || x.odd;
-      if (x.cmax == 0 && x.cmin == ~0ull) continue;  // (a slice without traces)
-      if (!k0) k0 = x.k0;
-      similar = similar && x.onek && x.k0 == k0;
-      cmin = std::min(cmin, x.cmin); cmax = std::max(cmax, x.cmax);
+      span.add(x.span);
     }
-    similar = similar && cmax <= cmin + cmin / 4;
+    similar = span.of_a_size();
     if (bad != ~0u) return set_error(TRACYHIP_ERR_ARG, "ref_index[%u] out of range", bad);
   }
   TRY(check_params(&p, h.max_mn));
@@ -1283,8 +1269,8 @@ struct StreamCall {
 
   // columns the band launches stage per pair (the longest trace and its margins): beside the widest substitution table they must fit the LDS
   int size_ncap() {
-    ncap = (h.maxmf + 200u + 7u) & ~3u;
-    return 4ull * ncap + b16_table_bytes(12) > 64u * 1024u ? kStreamNo : TRACYHIP_OK;
+    ncap = band_code_cap(h.maxmf + 200u);
+    return band_lds_fits(ncap, 12, kBandLdsHard) ? TRACYHIP_OK : kStreamNo;
   }
 
   // verdict words cleared, the reference windows encoded to profile-row codes (with their block map and the validation verdict)
@@ -1484,13 +1470,13 @@ struct AlignStream : StreamCall {
     // ---- 2. preliminary alignment (sage.h:258) by its two ends, 3. trimReferenceSlice (sage.h:259) ----
     hipLaunchKernelGGL(s_prelim_plan_kernel, g256, b256, 0, s, spm, 0, early, sc.geom, sc.tr, sc.ce, sc.top_trim, sc.dead, sc.cand, sc.kc, queued_prio(ctx, 2));
     HIP_TRY(hipGetLastError());
-    BandLaunch b1;
+    BandStageArgs b1;
     b1.kind = 1; b1.qp = d_qp; b1.codes = ctx->codes(); b1.ends = sc.ends; b1.code_cap = ncap; b1.hfree = 1;
     TRY(band_stage(ctx, p, sc, nt, nt, 0, b1, ~0ull));
     // ---- 4. final alignment gotoh(full profile, trimmed slice) (sage.h:311) on its certified band ----
     hipLaunchKernelGGL(s_align_final_plan_kernel, g256, b256, 0, s, spm, early, sc.geom, sc.tr, sc.ends, sc.dead, sc.cand, sc.kc, sc.cnt, queued_prio(ctx, 2));
     HIP_TRY(hipGetLastError());
-    BandLaunch b2;
+    BandStageArgs b2;
     b2.kind = 0; b2.qp = d_qp; b2.codes = ctx->codes(); b2.scores = o.score_final; b2.ops = d_ops; b2.ops_off = A.ops_off; b2.ops_len = o.ops_len; b2.code_cap = ncap;
     b2.hfree = 1;
     return band_stage(ctx, p, sc, nt, nt, 1, b2, words_cap);
@@ -1694,11 +1680,11 @@ __global__ void s_allele_plan0_kernel(SParams p, SParamsD pd, const SGeom* __res
   f.rest = (int32_t)((int64_t)pd.best * (int64_t)(D.sl - R));  // a row of a string scores `match` at most
   fd[q] = f;
   s_count(lc, SC_ALLELE_PRUNED0 + (int)k);
-  s_count(lc, SC_FRONT_CELLS, s_front_cells(f.m_rest));
-  s_count(lc, SC_FRONT_BYTES, s_front_bytes(f.m_rest, f.n));
+  s_count_front(lc, f);
   if (kept == k) {
-    s_count(lc, SC_SWEEP_CELLS, (uint64_t)R * G.rn);
-    s_count(lc, SC_SWEEP_BYTES, (uint64_t)R + 5ull * G.rn);
+    const Credit c = prefix_credit(D.sl, G.rn, R);
+    s_count(lc, SC_SWEEP_CELLS, c.cells);
+    s_count(lc, SC_SWEEP_BYTES, c.bytes);
   }
   });
 }
@@ -2198,7 +2184,7 @@ struct DecStream : StreamCall {
     TRY(give_up(queue_orientation(ctx, p, spm, h, sc, os)));
     hipLaunchKernelGGL(s_prelim_plan_kernel, g256, b256, 0, st, spm, 1, 0, sc.geom, sc.tr, sc.ce, sc.top_trim, sc.dead, sc.cand, sc.kc, 0);
     HIP_TRY(hipGetLastError());
-    BandLaunch b0;
+    BandStageArgs b0;
     b0.kind = 0; b0.qp = d_qp; b0.codes = ctx->codes(); b0.scores = A.sb; b0.ops = A.ops1; b0.ops_off = A.off1; b0.ops_len = A.len1; b0.code_cap = ncap; b0.hfree = 1;
     TRY(band_stage(ctx, p, sc, nt, nt, 0, b0, words_cap));
     hipLaunchKernelGGL(s_prelim_check_kernel, g256, b256, 0, st, spm, sc.tr, A.sb, A.len1, sc.kc, o.score_trim, sc.dead, sc.cnt);
@@ -2336,18 +2322,18 @@ struct DecStream : StreamCall {
     hipLaunchKernelGGL(s_allele_plan1_kernel, g256x2, b256, 0, st, spm, spd, sc.geom, A.geomd, sc.tr, sc.fo1, sc.fs1, sc.fe1, sc.fo2, sc.fs2, sc.fe2, A.al, sc.dead, sc.cand,
                        sc.kc, sc.cnt);
     HIP_TRY(hipGetLastError());
-    BandLaunch b1;
+    BandStageArgs b1;
     b1.kind = 1; b1.qp = d_aqp; b1.codes = d_cq_ref; b1.ends = sc.ends; b1.code_cap = ncap; b1.hfree = 1;
     TRY(band_stage(ctx, p, sc, 2 * nt, nt, 1, b1, ~0ull));
     hipLaunchKernelGGL(s_allele_plan2_kernel, g256x2, b256, 0, st, spm, sc.geom, A.geomd, sc.tr, sc.ends, A.al, sc.dead, sc.cand, sc.kc, kn.no_origin_band ? 0 : 1, sc.cnt);
     HIP_TRY(hipGetLastError());
-    BandLaunch b2;
+    BandStageArgs b2;
     b2.kind = 0; b2.qp = d_aqp; b2.codes = d_cq_ref; b2.scores = A.ascore; b2.ops = d_opsK[0]; b2.ops_off = A.aops_off; b2.ops_len = A.alen; b2.code_cap = ncap; b2.hfree = 1;
     TRY(band_stage(ctx, p, sc, 2 * nt, nt, 2, b2, words_cap));
     hipLaunchKernelGGL(s_allele_check_kernel, g256x2, b256, 0, st, spm, A.al, A.ascore, A.alen, sc.dead, sc.cnt);
     hipLaunchKernelGGL(s_a12_plan_kernel, g256, b256, 0, st, spm, spd, A.geomd, A.ascore, sc.dead, sc.cand, sc.kc, A.bound, sc.cnt);
     HIP_TRY(hipGetLastError());
-    BandLaunch b3;
+    BandStageArgs b3;
     b3.kind = 0; b3.qp = d_aqp; b3.codes = d_cq_sd; b3.scores = o.score[2]; b3.ops = d_opsK[2]; b3.ops_off = A.ops2_off; b3.ops_len = o.ops_len[2]; b3.code_cap = ncap; b3.hfree = 0;
     TRY(band_stage(ctx, pglobal, sc, nt, nt, 3, b3, words_cap));
     const DecompOutDev& ko = o;  // (the kernels' part of o: bp / dstatus / fractions are written by the decompose kernels through their own arguments)

@@ -12,6 +12,7 @@
 #include "../../include/tracy_hip.h"
 #include "band16.h"
 #include "front.h"
+#include "launch_rules.h"
 
 namespace tracyhip {
 
@@ -210,8 +211,8 @@ TR_HD SubWindow s_sub_window(uint32_t m, uint32_t ce, int64_t top, int64_t sstar
   s.K = b.K;
   return s;
 }
-// R4. LDS of a band launch: the codes of four pairs + the tables (the planners' limit; run_band16 refuses a launch past 64 KiB)
-TR_HD bool s_fits_lds(uint32_t n, int K) { return 4ull * ((n + 7u) & ~3u) + b16_table_bytes(K) <= 60u * 1024u; }
+// R4. LDS of a band launch, asked of one pair of n columns: the launches' rule (launch_rules.h) at the planners' limit
+TR_HD bool s_fits_lds(uint32_t n, int K) { return band_lds_fits(band_code_cap(n), K, kBandLdsPlan); }
 
 // R5. `tracy align`, final alignment gotoh(full profile, trimmed slice) of m x n on a band of half width w: the gap columns the
 // preliminary alignment's score allowed + 48 for what the trimmed ends add, within [32, 96] ...
@@ -295,10 +296,6 @@ TR_HD bool s_exact_certified(int32_t sb, int32_t sstar, uint32_t ops_len) { retu
 // R13. certificate of allele 1 vs allele 2: the banded score beats the bound of s_a12_band (R8) -- what any path that leaves the band
 // scores at most -- and the walk stayed inside (ops_len != 0)
 TR_HD bool s_a12_certified(int64_t sb, int64_t bound, uint32_t ops_len) { return sb > bound && ops_len != 0u; }
-
-// what the first tier of a pruned sweep over m_rest rows below the kept row and n columns is credited with (run_front_once's sums)
-TR_HD uint64_t s_front_cells(uint32_t m_rest) { return (uint64_t)b16_strips(m_rest, 8) * 8u * (8u + 2u * 60u); }
-TR_HD uint64_t s_front_bytes(uint32_t m_rest, uint32_t n) { return 12ull * m_rest + m_rest + 2ull * 60 + 4ull * (2 * 60 + 8) + 8ull * n; }
 
 TR_HD PairDesc s_skip_pair(uint32_t out) {
   PairDesc d{};
