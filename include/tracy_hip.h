@@ -800,6 +800,59 @@ typedef struct {
 } tracyhip_pad_stats;
 int tracyhip_last_pad_stats(tracyhip_ctx* ctx, tracyhip_pad_stats* out);
 
+/* ---- the text of a batch of traces: what the three writers of the commands print per trace, byte for byte (tracy_amd/host trace_io.hpp
+ * traceTxtOut, indigo_out.hpp traceJsonBody, sage_out.hpp assemblyTrace) ----------------------------------------------------------
+ * The chromatograms and basecall arrays are read where they lie: the payloads of tracyhip_basecall_result (bc_offset = pos_offset,
+ * bc_len) and of tracyhip_pad_result (signal_offset = sample_offset, nsamples = nsamples_out, bc_offset = call_offset, bc_len =
+ * ncalls_out) are taken as they stand.  Integers are decimal with a leading '-'; the letters are printed as the bytes they are.
+ * The device answers a trace when bc_len is in 1 .. 131071, nsamples in 1 .. 2^23 and the positions are strictly increasing inside
+ * [0, nsamples) (the reference's cursor loop then visits every call; its text stays below 2^31 bytes).  Any other trace is DEFERRED:
+ * status and text_len = 0 are written, nothing else. */
+#define TRACYHIP_RENDER_TSV    0 /* traceTxtOut, abif.h:513-533: the whole file, header line included */
+#define TRACYHIP_RENDER_JSON   1 /* _traceJsonOut, json.h:37-105: from "\"pos\": [" through the secondarySeq line and its '\n' */
+#define TRACYHIP_RENDER_GAPPED 2 /* assemblyTrace, json.h:130-192: from "\"peakA\": [" through "\"basecalls\": {...}\n"; the lines before
+                                    it (file name, leadingGaps, trailingGaps) and the closing "}\n" stay with the caller */
+#define TRACYHIP_RENDER_OK 0
+#define TRACYHIP_RENDER_DEFERRED 1
+#define TRACYHIP_RENDER_TOO_SMALL 2 /* text_cap is too small: text_len is reported, no text is written */
+typedef struct {
+  uint32_t ntraces, form;
+  const void* signal;            /* payload, as tracyhip_pad_job: trace t, channel k at signal_offset[t] + k * nsamples[t] */
+  const uint64_t* signal_offset; /* HOST array, elements */
+  const uint32_t* nsamples;      /* HOST array */
+  uint32_t sample_bytes;         /* 4 or 2 */
+  const int32_t* bcpos;          /* payload: trace t owns bc_len[t] entries from bc_offset[t] on, here and in the four below */
+  const uint8_t *primary, *secondary, *consensus, *estqual; /* payload; consensus: TSV only (may be NULL otherwise) */
+  const uint64_t* bc_offset;     /* HOST array */
+  const uint32_t* bc_len;        /* HOST array */
+  const uint32_t *trim_left_each, *trim_right_each; /* HOST, both or neither, TSV only: the leftTrim / rightTrim of the trim column; NULL = 0 / 0 */
+} tracyhip_render_job;
+typedef struct {
+  int32_t* status;             /* HOST [ntraces], required: TRACYHIP_RENDER_* */
+  uint32_t* text_len;          /* HOST [ntraces], required */
+  uint8_t* text;               /* payload: trace t writes exactly text_len[t] bytes from text_offset[t] on; NULL = sizes only */
+  const uint64_t* text_offset; /* HOST array, bytes, any value: the text is not aligned */
+  const uint64_t* text_cap;    /* HOST array: bytes trace t may take */
+} tracyhip_render_result;
+/* what tracyhip_render_traces refuses before it touches a device (none is needed here): NULL job / result / required arrays, mem, form,
+ * sample_bytes other than 2 or 4, misaligned signal / bcpos, one trim array without the other, a TSV without consensus, a text without its
+ * offsets and capacities.  TRACYHIP_ERR_ARG (with the reason) otherwise TRACYHIP_OK. */
+int tracyhip_render_validate(const tracyhip_render_job* job, int mem, const tracyhip_render_result* out);
+/* Three launches (count the bytes of every tile, scan them per trace, emit), the first two alone in the sizes-only form, which reads the
+ * chromatograms too.  Device payloads: ONE host synchronisation per call.  Host payloads are staged in chunks of consecutive traces within
+ * the workspace limit (tracyhip_set_workspace_limit; 256 MB without one), with a second synchronisation each for the copy back of exactly
+ * the bytes that were reported. */
+int tracyhip_render_traces(tracyhip_ctx* ctx, const tracyhip_render_job* job, int mem, const tracyhip_render_result* out);
+/* an upper bound of text_len for a trace of these sizes, whatever its values; needs no device.  0: no such form. */
+uint64_t tracyhip_render_bound(uint32_t form, uint32_t nsamples, uint32_t bc_len, uint32_t sample_bytes);
+/* counters of the last tracyhip_render_traces call of a context.  (A struct of their own: the layout of tracyhip_call_stats is pinned.) */
+typedef struct {
+  uint32_t render_chunks;    /* chunks of traces the batch was cut into */
+  uint32_t render_deferred;  /* traces with TRACYHIP_RENDER_DEFERRED */
+  uint32_t render_too_small; /* traces with TRACYHIP_RENDER_TOO_SMALL */
+} tracyhip_render_stats;
+int tracyhip_last_render_stats(tracyhip_ctx* ctx, tracyhip_render_stats* out);
+
 /* ---- reference-guided assembly (`tracy assemble -r`, assemble.h:219-288) for a batch of trace groups --------------------------
  * Group g owns the traces group_first[g] .. group_first[g + 1] - 1 (K of them) and the reference references[ref_index[g]].  Per group:
  *   1. the reverse complement of every trace (profile.h:74-90) and gotohScore(trace, reference), gotohScore(revcomp, reference)
@@ -941,6 +994,7 @@ int tracyhip_consensus_traces_async(tracyhip_ctx* ctx, const tracyhip_consensus_
                                     const tracyhip_consensus_result* out);
 int tracyhip_basecall_traces_async(tracyhip_ctx* ctx, const tracyhip_basecall_job* job, int mem, const tracyhip_basecall_result* out);
 int tracyhip_pad_traces_async(tracyhip_ctx* ctx, const tracyhip_pad_job* job, int mem, const tracyhip_pad_result* out);
+int tracyhip_render_traces_async(tracyhip_ctx* ctx, const tracyhip_render_job* job, int mem, const tracyhip_render_result* out);
 int tracyhip_assemble_traces_async(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem,
                                    const tracyhip_assemble_result* out);
 int tracyhip_denovo_traces_async(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip_params* prm, int mem,

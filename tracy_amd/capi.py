@@ -115,6 +115,11 @@ class PadStats(C.Structure):
     _fields_ = [("pad_chunks", C.c_uint32), ("pad_deferred", C.c_uint32), ("pad_too_small", C.c_uint32)]
 
 
+class RenderStats(C.Structure):
+    """tracyhip_render_stats: the counters of tracyhip_render_traces, in a struct of their own as PadStats"""
+    _fields_ = [("render_chunks", C.c_uint32), ("render_deferred", C.c_uint32), ("render_too_small", C.c_uint32)]
+
+
 def library_path():
     return os.path.join(_HERE, "lib", "libtracy_hip.so")
 
@@ -133,6 +138,7 @@ def lib():
         _LIB.tracyhip_last_error.restype = C.c_char_p
         _LIB.tracyhip_version.restype = C.c_char_p
         _LIB.tracyhip_group_context.restype = C.c_void_p
+        _LIB.tracyhip_render_bound.restype = C.c_uint64
     return _LIB
 
 
@@ -253,6 +259,9 @@ class Context:
         ps = PadStats()  # (tracyhip_pad_traces counts in a struct of its own: tracyhip_last_pad_stats)
         _check(lib().tracyhip_last_pad_stats(self._h, C.byref(ps)))
         out.update({name: int(getattr(ps, name)) for name, _ in PadStats._fields_})
+        rs = RenderStats()  # (and so does tracyhip_render_traces: tracyhip_last_render_stats)
+        _check(lib().tracyhip_last_render_stats(self._h, C.byref(rs)))
+        out.update({name: int(getattr(rs, name)) for name, _ in RenderStats._fields_})
         return out
 
     # ---- host-buffer convenience wrappers (lists in, numpy out) -----------------------------------
@@ -1690,3 +1699,185 @@ def _pad_traces(self, signals, bc, rows, trim_left=None, trim_right=None, revers
 
 
 Context.pad_traces = _pad_traces
+
+
+# ---- the text of the writers on the device (tracyhip_render_traces) ---------------------------------------------------------------------
+RENDER_TSV, RENDER_JSON, RENDER_GAPPED = 0, 1, 2
+RENDER_OK, RENDER_DEFERRED, RENDER_TOO_SMALL = 0, 1, 2
+
+
+class RenderJob(C.Structure):
+    _fields_ = [("ntraces", C.c_uint32), ("form", C.c_uint32), ("signal", C.c_void_p), ("signal_offset", C.POINTER(C.c_uint64)),
+                ("nsamples", C.POINTER(C.c_uint32)), ("sample_bytes", C.c_uint32), ("bcpos", C.c_void_p), ("primary", C.c_void_p),
+                ("secondary", C.c_void_p), ("consensus", C.c_void_p), ("estqual", C.c_void_p), ("bc_offset", C.POINTER(C.c_uint64)),
+                ("bc_len", C.POINTER(C.c_uint32)), ("trim_left_each", C.POINTER(C.c_uint32)), ("trim_right_each", C.POINTER(C.c_uint32))]
+
+
+class RenderResult(C.Structure):
+    _fields_ = [("status", C.POINTER(C.c_int32)), ("text_len", C.POINTER(C.c_uint32)), ("text", C.c_void_p),
+                ("text_offset", C.POINTER(C.c_uint64)), ("text_cap", C.POINTER(C.c_uint64))]
+
+
+def render_bound(form, nsamples, bc_len, sample_bytes):
+    """tracyhip_render_bound: an upper bound of text_len for a trace of these sizes; needs no device"""
+    return int(lib().tracyhip_render_bound(C.c_uint32(form), C.c_uint32(nsamples), C.c_uint32(bc_len), C.c_uint32(sample_bytes)))
+
+
+class PreparedRender:
+    """job / result structs of tracyhip_render_traces.  form: RENDER_TSV / RENDER_JSON / RENDER_GAPPED.  The traces come from one of
+      signals, bc   int32 or int16 [4][ns] per trace; per trace a dict of bcpos, primary, secondary, consensus, estqual (host arrays;
+                    device=True uploads them once)
+      device_bc     a PreparedBasecall(device=True) that has run: its chromatogram and basecall tensors are taken as they stand
+      device_pad    a PreparedPad(device=True) that has run with payload results: the padded chromatograms and basecalls as they stand
+    No payload is copied to the host for the last two.  trim_left / trim_right: the per-trace trims of the TSV's trim column.
+    Everything the structs point to is kept alive by this object.
+
+    The result side starts as the sizes-only form; with_capacity() allocates the text."""
+
+    def __init__(self, form, signals=None, bc=None, trim_left=None, trim_right=None, device=False, device_bc=None, device_pad=None,
+                 sample_dtype=None):
+        self.form = int(form)
+        self.device = device = bool(device or device_bc is not None or device_pad is not None)
+        f = self.flat = {}  # host copies in the layout of hostlib.render_batch (device sources: fetched when a deferred trace needs them)
+        if device_bc is not None:
+            nt = self.nt = device_bc.nt
+            self.sample_dtype = device_bc.sample_dtype
+            f.update(sig_off=device_bc.sig_off, nsamples=device_bc.nsamples, bc_off=device_bc.pos_off, bc_len=device_bc.meta["bc_len"])
+            self.d = dict(signal=device_bc.d_signal, **{k: device_bc.payload[k] for k in _PAD_BC})
+        elif device_pad is not None:
+            if not device_pad.device or device_pad.o is None:
+                raise ValueError("device_pad: a PreparedPad(device=True) with payload results")
+            nt = self.nt = device_pad.nt
+            self.sample_dtype = device_pad.sample_dtype
+            f.update(sig_off=device_pad.o["sample_offset"], nsamples=device_pad.meta["nsamples_out"], bc_off=device_pad.o["call_offset"],
+                     bc_len=device_pad.meta["ncalls_out"])
+            self.d = {k: device_pad.o[k] for k in ("signal",) + _PAD_BC}
+        else:
+            nt = self.nt = len(signals)
+            if sample_dtype is None:
+                sample_dtype = np.int16 if nt and all(np.asarray(s).dtype == np.int16 for s in signals) else np.int32
+            self.sample_dtype = np.dtype(sample_dtype)
+            f["nsamples"] = np.array([np.asarray(s).shape[1] for s in signals] + [0], dtype=np.uint32)
+            f["bc_len"] = np.array([len(b["bcpos"]) for b in bc] + [0], dtype=np.uint32)
+            f["sig_off"] = np.zeros(nt + 1, np.uint64)
+            f["bc_off"] = np.zeros(nt + 1, np.uint64)
+            f["sig_off"][1:] = np.cumsum(4 * f["nsamples"][:nt].astype(np.uint64))
+            f["bc_off"][1:] = np.cumsum(f["bc_len"][:nt].astype(np.uint64))
+            f["signal"] = np.concatenate([np.ascontiguousarray(s, dtype=self.sample_dtype).reshape(-1) for s in signals] + [np.zeros(1, self.sample_dtype)])
+            f["bcpos"] = np.concatenate([np.ascontiguousarray(b["bcpos"], dtype=np.int32).reshape(-1) for b in bc] + [np.zeros(1, np.int32)])
+            for k in _PAD_BC[1:]:
+                f[k] = np.concatenate([np.frombuffer(bytes(b[k]), np.uint8) if isinstance(b[k], (bytes, bytearray))
+                                       else np.ascontiguousarray(b[k], dtype=np.uint8).reshape(-1) for b in bc] + [np.zeros(1, np.uint8)])
+            if device:
+                import torch
+                self.d = {k: torch.from_numpy(f[k]).cuda() for k in ("signal",) + _PAD_BC}
+                torch.cuda.synchronize()
+        f["nt"] = nt
+        if (trim_left is None) != (trim_right is None):
+            raise ValueError("trim_left and trim_right go together: both or neither")
+        if trim_left is not None:
+            f["trim_l"] = np.append(np.ascontiguousarray(trim_left, dtype=np.uint32)[:nt], np.uint32(0))
+            f["trim_r"] = np.append(np.ascontiguousarray(trim_right, dtype=np.uint32)[:nt], np.uint32(0))
+        ptr = (lambda k: self.d[k].data_ptr()) if device else (lambda k: f[k].ctypes.data)
+        job = self.job = RenderJob()
+        job.ntraces, job.form = nt, self.form
+        job.signal, job.sample_bytes = ptr("signal"), self.sample_dtype.itemsize
+        job.signal_offset, job.nsamples = _u64p(f["sig_off"]), _u32p(f["nsamples"])
+        for k in _PAD_BC:
+            setattr(job, k, ptr(k))
+        job.bc_offset, job.bc_len = _u64p(f["bc_off"]), _u32p(f["bc_len"])
+        if trim_left is not None:
+            job.trim_left_each, job.trim_right_each = _u32p(f["trim_l"]), _u32p(f["trim_r"])
+        self.mem = MEM_DEVICE if device else MEM_HOST
+        self._bind(None)
+
+    def _bind(self, o):
+        """the result struct over the arrays of `o` (hostlib.render_alloc layout; None: the sizes-only form)"""
+        self.meta = dict(status=np.zeros(max(self.nt, 1), np.int32), text_len=np.zeros(max(self.nt, 1), np.uint32))
+        out = self.out = RenderResult()
+        out.status = self.meta["status"].ctypes.data_as(C.POINTER(C.c_int32))
+        out.text_len = _u32p(self.meta["text_len"])
+        self.o = o
+        if o is None:
+            return
+        out.text_offset, out.text_cap = _u64p(o["text_offset"]), _u64p(o["text_cap"])
+        out.text = o["text"].data_ptr() if self.device else o["text"].ctypes.data
+
+    def sizes(self, ctx):
+        """the sizes-only call: text_len per trace, 0 for deferred traces"""
+        self._bind(None)
+        _check(lib().tracyhip_render_traces(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
+        return self.meta["text_len"][:self.nt].copy()
+
+    def bounds(self):
+        """tracyhip_render_bound per trace: capacities that need no sizes-only call"""
+        f = self.flat
+        return np.array([render_bound(self.form, int(f["nsamples"][t]), int(f["bc_len"][t]), self.sample_dtype.itemsize) for t in range(self.nt)],
+                        dtype=np.uint64)
+
+    def with_capacity(self, text_cap, fill=None, offsets=None):
+        """a text buffer with room for text_cap[t] bytes of trace t (fill: a byte the buffer starts with, for tests that check what a
+        call leaves untouched; offsets: text_offset of every trace and the buffer's size behind them, instead of back to back)"""
+        from . import hostlib
+        o = hostlib.render_alloc(self.nt, text_cap, fill)
+        if offsets is not None:
+            o["text_offset"] = np.ascontiguousarray(offsets, dtype=np.uint64)
+            o["text"] = np.full(max(int(o["text_offset"][self.nt]), 1), 0 if fill is None else fill, np.uint8)
+        if self.device:
+            import torch
+            o["text"] = torch.from_numpy(o["text"]).cuda()
+            torch.cuda.synchronize()
+        self._bind(o)
+        return self
+
+    def run(self, ctx, asynchronous=False):
+        fn = lib().tracyhip_render_traces_async if asynchronous else lib().tracyhip_render_traces
+        _check(fn(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
+        return self
+
+    def host_arrays(self):
+        """the result arrays on the host in the layout of hostlib.render_alloc (a device text is copied back)"""
+        o = dict(self.o)
+        if self.device:
+            o["text"] = o["text"].cpu().numpy()
+        o.update(self.meta)
+        return o
+
+    def host_flat(self):
+        """the inputs on the host in the layout of hostlib.render_batch"""
+        f = dict(self.flat)
+        for k in ("signal",) + _PAD_BC:
+            if k not in f:
+                f[k] = self.d[k].cpu().numpy()
+        return f
+
+    def results(self, fill_deferred=True):
+        """per trace: dict(status, text_len, text).  Deferred traces are printed by the host writers (hostlib.render_batch), except those
+        the reference's loops cannot run either (`unreadable`: status stays DEFERRED)"""
+        from . import hostlib
+        o = self.host_arrays()
+        res = [hostlib.render_unpack(o, t) for t in range(self.nt)]
+        sel = np.array([t for t in range(self.nt) if res[t]["status"] == RENDER_DEFERRED], dtype=np.int64)
+        if fill_deferred and len(sel):
+            f = self.host_flat()
+            sub = dict(f, nt=len(sel))
+            for k in ("sig_off", "nsamples", "bc_off", "bc_len", "trim_l", "trim_r"):
+                if k in f:
+                    sub[k] = np.append(f[k][sel], f[k].dtype.type(0))
+            for t, r in zip(sel, hostlib.render_batch(sub, self.form)):
+                res[t] = r if r["status"] == 0 else dict(res[t], unreadable=True)
+        return res
+
+
+def _render_traces(self, form, signals=None, bc=None, trim_left=None, trim_right=None, device=False, device_bc=None, device_pad=None,
+                   asynchronous=False):
+    """tracyhip_render_traces: the sizes-only call, a buffer of exactly those sizes, the call.  Host arrays with device=False: returns the
+    per-trace results (PreparedRender.results).  device=True, device_bc or device_pad: returns the PreparedRender holding the text as a
+    torch tensor on the GPU.  asynchronous: the second call is queued (tracyhip_render_traces_async); results are final after
+    Context.synchronize()."""
+    p = PreparedRender(form, signals, bc, trim_left, trim_right, device, device_bc, device_pad)
+    p.with_capacity(p.sizes(self)).run(self, asynchronous)
+    return p if (p.device or asynchronous) else p.results()
+
+
+Context.render_traces = _render_traces

@@ -194,7 +194,13 @@ enum CtxDev : int {
   PD_SCRATCH,   // the insert lists of pad_kernel, one region per trace of a chunk
   PD_IN,        // a host caller's chromatograms, basecall arrays and rows of a chunk, staged in
   PD_OUT,       // padded chromatograms and basecall arrays of a chunk staged for a host caller
-  DB_COUNT = PD_OUT + 1
+  // ---- tracyhip_render_traces (render.hip) ----
+  DB_RENDER_TRACES,  // RenderTrace per trace up, RenderOut per trace back
+  DB_RENDER_TILES,   // bytes (then offset) and aux word of every tile of a chunk: written by render_count_kernel, scanned in place by
+                     // render_scan_kernel, read by render_emit_kernel
+  DB_RENDER_IN,      // a host caller's chromatograms and basecall arrays of a chunk, staged in
+  DB_RENDER_OUT,     // the text of a chunk staged for a host caller
+  DB_COUNT = DB_RENDER_OUT + 1
 };
 static_assert(DN_CNT + 1 == VB_DESC && VB_PACK_TEXT + 1 == WB_ORIENTED && DN_PAY < DB_COUNT && WB_PAY < DB_COUNT,
               "an alias does not advance the count: every slot of its own comes after the aliases");
@@ -341,6 +347,7 @@ struct tracyhip_ctx {
   tracyhip::CtxKnobs knobs;  // (the fields below it used to be: no_narrow, no_compact, no_screen)
   tracyhip_call_stats stats = {};  // tiers of the last pipeline call (tracyhip_last_call_stats)
   tracyhip_pad_stats pad_stats = {};  // of the last tracyhip_pad_traces call (tracyhip_last_pad_stats)
+  tracyhip_render_stats render_stats = {};  // of the last tracyhip_render_traces call (tracyhip_last_render_stats)
   std::vector<Pending> pending;
   std::vector<hipEvent_t> free_events;
   tracyhip_kernel_timing acc[TRACYHIP_TIMER_COUNT] = {};

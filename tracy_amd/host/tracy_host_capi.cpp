@@ -831,6 +831,75 @@ int tracyhost_pad_batch(uint32_t n, const void* signal, const uint64_t* signal_o
   return 0;
 }
 
+// ---- the per-trace text of a batch as the command line prints it, one trace after the other per thread: traceTxtOut (trace_io.hpp),
+// traceJsonBody (indigo_out.hpp) and assemblyTrace (sage_out.hpp) into a TextBuf over the flattened arrays of tracyhip_render_traces (the
+// fallback for its deferred traces; tools/render_device_line.py times it beside the device call) ----
+// form: 0 the .abif table, 1 the trace body of the decompose / basecall JSON, 2 the gapped trace from "peakA" through the "basecalls" line.
+// status: 0 answered; 1 refused -- the reference's cursor loop stalls or reads outside its arrays (no call, no sample, a position outside
+// [0, nsamples) or not above its neighbour) or the trace is beyond what the device answers (more than 131071 calls, more than 2^23
+// samples); 2 text_cap is too small (text_len reported).  text may be null (sizes only); consensus is read by form 0 alone; trim_l / trim_r
+// may be null.
+int tracyhost_render_batch(uint32_t n, uint32_t form, const void* signal, const uint64_t* signal_offset, const uint32_t* nsamples, uint32_t sample_bytes,
+                           const int32_t* bcpos, const uint8_t* primary, const uint8_t* secondary, const uint8_t* consensus, const uint8_t* estqual,
+                           const uint64_t* bc_offset, const uint32_t* bc_len, const uint32_t* trim_l, const uint32_t* trim_r, int32_t* status,
+                           uint32_t* text_len, uint8_t* text, const uint64_t* text_offset, const uint64_t* text_cap, uint32_t nthreads) {
+  if (n && (!signal || !signal_offset || !nsamples || !bcpos || !primary || !secondary || !estqual || !bc_offset || !bc_len || !status || !text_len))
+    return -1;
+  if (form > 2 || (n && form == 0 && !consensus) || (sample_bytes != 2 && sample_bytes != 4) || (text && (!text_offset || !text_cap))) return -1;
+  if (nthreads == 0) nthreads = tracy_amd::usable_threads();
+  std::vector<std::thread> th;
+  for (uint32_t w = 0; w < nthreads; ++w)
+    th.emplace_back([=]() {
+      PaddedTrace p;  // (form 2 prints a padded trace; the other two its two members)
+      Trace& tr = p.tr;
+      BaseCalls& bc = p.bc;
+      tr.traceACGT.resize(4);
+      for (uint32_t t = (uint32_t)((uint64_t)n * w / nthreads); t < (uint32_t)((uint64_t)n * (w + 1) / nthreads); ++t) {
+        const uint32_t ns = nsamples[t], nc = bc_len[t];
+        const int32_t* pos = bcpos + bc_offset[t];
+        status[t] = 1;
+        text_len[t] = 0;
+        bool ok = nc >= 1 && nc <= 131071u && ns >= 1 && ns <= (1u << 23);
+        for (uint32_t i = 0; ok && i < nc; ++i) ok = pos[i] >= 0 && (uint32_t)pos[i] < ns && (i == 0 || pos[i] > pos[i - 1]);
+        if (!ok) continue;
+        for (int k = 0; k < 4; ++k) {
+          tr.traceACGT[k].resize(ns);
+          const uint64_t at = signal_offset[t] + (uint64_t)k * ns;
+          if (sample_bytes == 4) std::memcpy(tr.traceACGT[k].data(), static_cast<const int32_t*>(signal) + at, 4ull * ns);
+          else
+            for (uint32_t x = 0; x < ns; ++x) tr.traceACGT[k][x] = static_cast<const int16_t*>(signal)[at + x];
+        }
+        bc.bcPos.assign(pos, pos + nc);
+        bc.primary.assign(reinterpret_cast<const char*>(primary) + bc_offset[t], nc);
+        bc.secondary.assign(reinterpret_cast<const char*>(secondary) + bc_offset[t], nc);
+        if (form == 0) bc.consensus.assign(reinterpret_cast<const char*>(consensus) + bc_offset[t], nc);
+        bc.estQual.assign(estqual + bc_offset[t], estqual + bc_offset[t] + nc);
+        TextBuf out((std::size_t)48 * ns + 4096);
+        std::size_t from = 0, to = 0;
+        if (form == 0) {
+          traceTxtOut(out, bc, tr, trim_l ? trim_l[t] : 0u, trim_r ? trim_r[t] : 0u);
+          to = out.size();
+        } else if (form == 1) {
+          traceJsonBody(out, bc, tr);
+          to = out.size();
+        } else {
+          p.leadingGaps = p.trailingGaps = 0;
+          assemblyTrace(out, p, "");
+          static const char head[] = "{\n\"traceFileName\": \"\",\n\"leadingGaps\": 0,\n\"trailingGaps\": 0,\n";
+          from = sizeof(head) - 1;  // the lines in front of "peakA" ...
+          to = out.size() - 2;      // ... and the closing "}\n" stay with the caller
+        }
+        if (to - from > 0x7fffffffull) continue;
+        text_len[t] = (uint32_t)(to - from);
+        if (text && to - from > text_cap[t]) { status[t] = 2; continue; }
+        status[t] = 0;
+        if (text) std::memcpy(text + text_offset[t], out.data() + from, to - from);
+      }
+    });
+  for (auto& t : th) t.join();
+  return 0;
+}
+
 // threads the batch entry points start when the caller passes nthreads = 0
 uint32_t tracyhost_usable_threads() { return tracy_amd::usable_threads(); }
 

@@ -616,3 +616,49 @@ def pad_batch(flat, nthreads=0):
     sizes = pad_batch_raw(flat, pad_alloc(flat, np.zeros(flat["nt"], np.uint32), np.zeros(flat["nt"], np.uint32)), nthreads, sizes_only=True)
     out = pad_batch_raw(flat, pad_alloc(flat, sizes["nsamples_out"], sizes["ncalls_out"]), nthreads)
     return [pad_unpack(out, t) for t in range(flat["nt"])]
+
+
+# ---- the per-trace text of the writers on the host (tracyhost_render_batch): the fallback and the baseline of tracyhip_render_traces -----
+RENDER_TSV, RENDER_JSON, RENDER_GAPPED = 0, 1, 2
+
+
+def render_alloc(nt, text_cap, fill=None):
+    """result arrays of a printing call with room for text_cap[t] bytes of trace t: status, text_len, text, text_offset, text_cap"""
+    cap = np.ascontiguousarray(text_cap, dtype=np.uint64)[:nt].copy() if nt else np.zeros(0, np.uint64)
+    o = dict(text_cap=np.append(cap, np.uint64(0)), text_offset=np.zeros(nt + 1, np.uint64))
+    o["text_offset"][1:] = np.cumsum(cap)
+    o["text"] = np.zeros(max(int(o["text_offset"][nt]), 1), np.uint8) if fill is None else np.full(max(int(o["text_offset"][nt]), 1), fill, np.uint8)
+    o["status"] = np.zeros(max(nt, 1), np.int32)
+    o["text_len"] = np.zeros(max(nt, 1), np.uint32)
+    return o
+
+
+def render_batch_raw(flat, form, out, nthreads=0, sizes_only=False):
+    """one tracyhost_render_batch call over the flattened arrays of a PreparedRender (capi.py) into `out` (render_alloc)"""
+    p = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+    rc = lib().tracyhost_render_batch(C.c_uint32(flat["nt"]), C.c_uint32(form), p(flat["signal"]), p(flat["sig_off"]), p(flat["nsamples"]),
+                                      C.c_uint32(flat["signal"].dtype.itemsize), p(flat["bcpos"]), p(flat["primary"]), p(flat["secondary"]),
+                                      p(flat.get("consensus")), p(flat["estqual"]), p(flat["bc_off"]), p(flat["bc_len"]), p(flat.get("trim_l")),
+                                      p(flat.get("trim_r")), p(out["status"]), p(out["text_len"]), None if sizes_only else p(out["text"]),
+                                      p(out["text_offset"]), p(out["text_cap"]), C.c_uint32(nthreads))
+    if rc != 0:
+        raise ValueError("tracyhost_render_batch: bad arguments")
+    return out
+
+
+def render_unpack(out, t):
+    """trace t of a finished printing call (render_alloc layout, host arrays): dict(status, text_len[, text])"""
+    st, n = int(out["status"][t]), int(out["text_len"][t])
+    r = dict(status=st, text_len=n)
+    if st == 0:
+        o = int(out["text_offset"][t])
+        r["text"] = out["text"][o:o + n].tobytes()
+    return r
+
+
+def render_batch(flat, form, nthreads=0):
+    """print a batch on host threads: a sizes-only call, a buffer of exactly those sizes, the call; per-trace dicts (status 1: the
+    reference's loops cannot run the trace, or it is beyond what the device answers)"""
+    sizes = render_batch_raw(flat, form, render_alloc(flat["nt"], np.zeros(flat["nt"], np.uint64)), nthreads, sizes_only=True)
+    out = render_batch_raw(flat, form, render_alloc(flat["nt"], sizes["text_len"]), nthreads)
+    return [render_unpack(out, t) for t in range(flat["nt"])]
