@@ -66,6 +66,27 @@ def test_needle_vs_fullmatrix(cfg):
         want = npref.needle_full(m, n, lambda r, c: npref.sub_prof_double(p1, p2, r, c, sc), cfg[0], cfg[1], sc)
         assert orc.needle_prof(p1, p2, cfg[0], cfg[1], sc) == want
         assert orc.needle_score_prof(p1, p2, cfg[0], cfg[1], sc) == want[0]
+    # the kinds of input tests/needle_cases.py holds the kernels against the oracle on: ties everywhere (a homopolymer, the all-zero
+    # scoring), mismatch = 2 ge, arbitrary bytes; dyadic and negative profile entries, weight in the gap row
+    import needle_cases as nc
+    odd = bytes([0x00, 0xff, 0x80, 0x7f]) + b"aAcCgN-"
+    strings = [(b"A" * m, b"A" * n) for (m, n) in [(1, 1), (7, 7), (5, 19), (33, 12), (40, 40)]]
+    for alpha, (m, n) in [(b"AC", (17, 23)), (b"ACGTN", (38, 31)), (odd, (40, 36)), (odd, (9, 30))]:
+        s2 = nc.rand_bytes(rng, n, alpha)
+        strings += [(nc.noisy_copy(rng, s2, m, alpha), s2), (nc.rand_bytes(rng, m, alpha), s2)]
+    for s1, s2 in strings:
+        for sc in nc.SCORINGS:
+            want = npref.needle_full(len(s1), len(s2), lambda r, c: npref.sub_str(s1, s2, r, c, sc), cfg[0], cfg[1], sc)
+            assert orc.needle_str(s1, s2, cfg[0], cfg[1], sc) == want, (s1, s2, cfg, sc)
+            assert orc.needle_score_str(s1, s2, cfg[0], cfg[1], sc) == want[0]
+    for it, kind in enumerate(("dyadic", "minus0.3", "row5", "x37.5", "onehot")):
+        m, n = [(23, 31), (30, 17), (12, 40)][it % 3]
+        p1 = nc.profile_of_kind(rng, m, kind)
+        p2 = nc.resampled(rng, p1, n) if it % 2 else nc.profile_of_kind(rng, n, kind)
+        for sc in nc.SCORINGS[it % 2::2]:
+            want = npref.needle_full(m, n, lambda r, c: npref.sub_prof_double(p1, p2, r, c, sc), cfg[0], cfg[1], sc)
+            assert orc.needle_prof(p1, p2, cfg[0], cfg[1], sc) == want, (kind, cfg, sc)
+            assert orc.needle_score_prof(p1, p2, cfg[0], cfg[1], sc) == want[0]
 
 
 def test_known_answers():
