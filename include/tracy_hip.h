@@ -853,6 +853,69 @@ typedef struct {
 } tracyhip_render_stats;
 int tracyhip_last_render_stats(tracyhip_ctx* ctx, tracyhip_render_stats* out);
 
+/* ---- chromatogram files: a batch of ABIF / SCF file images turned into the arrays the readers produce (readab abif.h:286-405, traceFormat
+ * scf.h:18-34, readscf scf.h:38-102) -- the first step of every command ----------------------------------------------------------
+ * The images lie one after another in `bytes`, file t at file_offset[t] (any alignment), file_len[t] bytes long.  Every field of an
+ * answered trace equals tracy_amd/host/trace_io.hpp (readab / readscf) for the same bytes: the four channels as A, C, G, T (ABIF: channel
+ * i of DATA.9-12 is the letter FWO_.1[i]; PLOC and DATA are big-endian int16, sign-extended; SCF: second differences integrated twice
+ * with a 16-bit carry), the call positions, basecalls1 / basecalls2 (letters other than ACGT become 'N'; NULs when P2BA is absent) and
+ * qual (the PCON bytes), cut to the common length n = min(|PBAS|, |P2BA| unless absent, |PCON|, |PLOC|) where the character payloads are
+ * taken one byte past their declared length, clipped at the end of the file.  For SCF basecalls1, basecalls2 and qual are zeros.
+ * The device answers an ABIF file when the header and every directory slot (28 bytes each) lie inside the file, each of the nine keys
+ * readab uses occurs at most once under the element type it is read under, with its natural element size and its payload inside the
+ * file (in the slot itself iff the slot's dsize is <= 4), FWO_.1 starts with a permutation of ACGT, DATA.9-12 are all present with one
+ * common count in 3 .. 2^23 that the file has room for (8 bytes a sample) and n is in 1 .. 131071; an SCF file when its version bytes
+ * are [3-9].[0-9][0-9], samples is in 3 .. 2^23, bases in 1 .. 131071, both blocks lie inside the file and, with sample_bytes 2, every
+ * integrated sample fits int16.  Any other file is DEFERRED: status and format are written, the sizes are zero, no payload is promised,
+ * and the caller runs the host reader (the convention of tracyhip_basecall_traces). */
+#define TRACYHIP_READ_OK 0
+#define TRACYHIP_READ_DEFERRED 1
+#define TRACYHIP_READ_TOO_SMALL 2 /* a capacity is too small: the sizes are reported, no payload is written */
+typedef struct {
+  uint32_t ntraces;
+  const uint8_t* bytes;          /* payload: the file images */
+  const uint64_t* file_offset;   /* HOST array, bytes, any alignment */
+  const uint32_t* file_len;      /* HOST array */
+  uint32_t sample_bytes;         /* 2 or 4: the width of the result signal */
+} tracyhip_read_job;
+/* The four per-trace arrays are HOST [ntraces] and required.  The payload results live where `mem` says and each may be NULL; with all of
+ * them NULL the call is the sizes-only form, which needs no offsets or capacities.  With TRACYHIP_MEM_DEVICE the results are the inputs of
+ * tracyhip_basecall_job as they stand: signal, signal_offset = sample_offset, nsamples, basecallpos, pos_offset = call_offset, npos =
+ * ncalls. */
+typedef struct {
+  int32_t* status;         /* TRACYHIP_READ_* */
+  int32_t* format;         /* 0 ABIF, 1 SCF, -1 neither, as traceFormat returns */
+  uint32_t* nsamples;      /* samples per channel */
+  uint32_t* ncalls;        /* the common length of positions, letters and qualities */
+  void* signal;            /* sample_bytes as the job; trace t: channel k (A, C, G, T) at sample_offset[t] + k * nsamples[t] */
+  const uint64_t* sample_offset; /* HOST array, elements */
+  const uint32_t* sample_cap;    /* HOST array: samples per channel that trace t may take (4 * sample_cap[t] elements are its region) */
+  int32_t* basecallpos;    /* ncalls[t] entries from call_offset[t] on, here and in the three below */
+  uint8_t *basecalls1, *basecalls2, *qual;
+  const uint64_t* call_offset;   /* HOST array */
+  const uint32_t* call_cap;      /* HOST array */
+} tracyhip_read_result;
+/* what tracyhip_read_traces refuses before it touches a device (none is needed here): NULL job / result / required arrays, mem,
+ * sample_bytes other than 2 or 4, a misaligned signal / basecallpos, a payload result without its offsets and capacities.
+ * TRACYHIP_ERR_ARG (with the reason) otherwise TRACYHIP_OK. */
+int tracyhip_read_validate(const tracyhip_read_job* job, int mem, const tracyhip_read_result* out);
+/* capacities that any answered file of file_len bytes fits (four channels take at least 8 * nsamples bytes of the file, the positions at
+ * least 2 * ncalls): with them a caller makes one call without the sizes-only pass.  Needs no device. */
+int tracyhip_read_bound(uint32_t file_len, uint32_t* nsamples_max, uint32_t* ncalls_max);
+/* Two launches: one wave per file scans header and directory (the sizes-only form ends here), one wave per (file, tile) writes the
+ * payloads.  Device payloads: ONE host synchronisation per call.  Host payloads are staged in chunks of consecutive files within the
+ * workspace limit (tracyhip_set_workspace_limit; 256 MB without one), with a second synchronisation each for the copy back of exactly what
+ * was reported.  A file whose file_offset + file_len (or a result offset + capacity) leaves 64 bits is refused with TRACYHIP_ERR_RANGE
+ * before the first launch. */
+int tracyhip_read_traces(tracyhip_ctx* ctx, const tracyhip_read_job* job, int mem, const tracyhip_read_result* out);
+/* counters of the last tracyhip_read_traces call of a context.  (A struct of their own: the layout of tracyhip_call_stats is pinned.) */
+typedef struct {
+  uint32_t read_chunks;    /* chunks of files the batch was cut into */
+  uint32_t read_deferred;  /* traces with TRACYHIP_READ_DEFERRED */
+  uint32_t read_too_small; /* traces with TRACYHIP_READ_TOO_SMALL */
+} tracyhip_read_stats;
+int tracyhip_last_read_stats(tracyhip_ctx* ctx, tracyhip_read_stats* out);
+
 /* ---- reference-guided assembly (`tracy assemble -r`, assemble.h:219-288) for a batch of trace groups --------------------------
  * Group g owns the traces group_first[g] .. group_first[g + 1] - 1 (K of them) and the reference references[ref_index[g]].  Per group:
  *   1. the reverse complement of every trace (profile.h:74-90) and gotohScore(trace, reference), gotohScore(revcomp, reference)
@@ -975,6 +1038,14 @@ int tracyhip_denovo_validate(const tracyhip_denovo_job* job, const tracyhip_para
 int tracyhip_denovo_traces(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip_params* prm, int mem,
                            const tracyhip_denovo_result* out);
 
+/* ---- device memory for a caller without a HIP runtime of its own (the command line): buffers for the payloads of the calls that take
+ * TRACYHIP_MEM_DEVICE, so that a chain of them (tracyhip_read_traces -> tracyhip_basecall_traces -> tracyhip_render_traces) keeps every
+ * intermediate on the device.  tracyhip_device_copy is synchronous on the context's stream: it runs behind the calls issued before it
+ * and has finished when it returns (to_device != 0: host -> device, else device -> host). */
+int tracyhip_device_alloc(tracyhip_ctx* ctx, uint64_t bytes, void** out);
+int tracyhip_device_free(tracyhip_ctx* ctx, void* p);
+int tracyhip_device_copy(tracyhip_ctx* ctx, void* dst, const void* src, uint64_t bytes, int to_device);
+
 /* ---- asynchronous forms (SURVEY.md 8b "Threading": synchronous by default with an async variant) ---------------------
  * Same arguments and results as the call without the suffix; the call returns as soon as the work is queued on the
  * context.  A context executes its calls in issue order on its own worker thread and stream (the pipelines need the
@@ -995,6 +1066,7 @@ int tracyhip_consensus_traces_async(tracyhip_ctx* ctx, const tracyhip_consensus_
 int tracyhip_basecall_traces_async(tracyhip_ctx* ctx, const tracyhip_basecall_job* job, int mem, const tracyhip_basecall_result* out);
 int tracyhip_pad_traces_async(tracyhip_ctx* ctx, const tracyhip_pad_job* job, int mem, const tracyhip_pad_result* out);
 int tracyhip_render_traces_async(tracyhip_ctx* ctx, const tracyhip_render_job* job, int mem, const tracyhip_render_result* out);
+int tracyhip_read_traces_async(tracyhip_ctx* ctx, const tracyhip_read_job* job, int mem, const tracyhip_read_result* out);
 int tracyhip_assemble_traces_async(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem,
                                    const tracyhip_assemble_result* out);
 int tracyhip_denovo_traces_async(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip_params* prm, int mem,

@@ -120,6 +120,11 @@ class RenderStats(C.Structure):
     _fields_ = [("render_chunks", C.c_uint32), ("render_deferred", C.c_uint32), ("render_too_small", C.c_uint32)]
 
 
+class ReadStats(C.Structure):
+    """tracyhip_read_stats: the counters of tracyhip_read_traces, in a struct of their own as PadStats"""
+    _fields_ = [("read_chunks", C.c_uint32), ("read_deferred", C.c_uint32), ("read_too_small", C.c_uint32)]
+
+
 def library_path():
     return os.path.join(_HERE, "lib", "libtracy_hip.so")
 
@@ -262,6 +267,9 @@ class Context:
         rs = RenderStats()  # (and so does tracyhip_render_traces: tracyhip_last_render_stats)
         _check(lib().tracyhip_last_render_stats(self._h, C.byref(rs)))
         out.update({name: int(getattr(rs, name)) for name, _ in RenderStats._fields_})
+        ds = ReadStats()  # (and tracyhip_read_traces: tracyhip_last_read_stats)
+        _check(lib().tracyhip_last_read_stats(self._h, C.byref(ds)))
+        out.update({name: int(getattr(ds, name)) for name, _ in ReadStats._fields_})
         return out
 
     # ---- host-buffer convenience wrappers (lists in, numpy out) -----------------------------------
@@ -1380,6 +1388,9 @@ class PreparedBasecall:
     consensus and decompose jobs without a host copy.  Everything the structs point to is kept alive by this object."""
 
     def __init__(self, signals, positions, sigratio=0.33, trim_stringency=0, device=False, sample_dtype=None):
+        if isinstance(signals, PreparedRead):
+            self._from_read(signals, sigratio, trim_stringency)
+            return
         nt = self.nt = len(signals)
         if sample_dtype is None:
             sample_dtype = np.int16 if nt and all(np.asarray(s).dtype == np.int16 for s in signals) else np.int32
@@ -1425,6 +1436,42 @@ class PreparedBasecall:
                 setattr(out, k, self.payload[k].ctypes.data)
         self.mem = MEM_DEVICE if device else MEM_HOST
 
+    def _from_read(self, rd, sigratio, trim_stringency):
+        """over the results of a PreparedRead(device=True) that has run with payload results: its chromatograms and positions are the job's
+        signal and basecallpos as they stand (signal_offset = sample_offset, pos_offset = call_offset, npos = ncalls); no payload is
+        copied.  A trace the reader deferred has no samples and no positions here: the call defers it too."""
+        import torch
+        if not rd.device or rd.o is None:
+            raise ValueError("basecall_traces: a PreparedRead(device=True) with payload results")
+        nt = self.nt = rd.nt
+        self.read = rd
+        self.device = True
+        self.sample_dtype = rd.sample_dtype
+        self.nsamples, self.npos = rd.meta["nsamples"], rd.meta["ncalls"]
+        self.sig_off, self.pos_off = rd.o["sample_offset"], rd.o["call_offset"]
+        self.d_signal, self.d_positions = rd.o["signal"], rd.o["basecallpos"]
+        self.signal = self.positions = None  # (on the device only: results() fetches them when a deferred trace needs the host chain)
+        total = self.total = int(rd.o["call_offset"][nt])
+        self.meta = {k: np.zeros(max(nt, 1), np.int32 if k == "status" else np.uint32)
+                     for k in ("status", "bc_len", "trim_left", "trim_right", "best_section")}
+        job = self.job = BasecallJob()
+        job.ntraces = nt
+        job.signal_offset, job.nsamples = _u64p(self.sig_off), _u32p(self.nsamples)
+        job.pos_offset, job.npos = _u64p(self.pos_off), _u32p(self.npos)
+        job.sample_bytes = self.sample_dtype.itemsize
+        job.sigratio = sigratio
+        job.trim_stringency = trim_stringency
+        out = self.out = BasecallResult()
+        out.status = self.meta["status"].ctypes.data_as(C.POINTER(C.c_int32))
+        for k in ("bc_len", "trim_left", "trim_right", "best_section"):
+            setattr(out, k, _u32p(self.meta[k]))
+        self.payload = {k: torch.zeros(max(total, 1) * w, dtype=getattr(torch, np.dtype(dt).name), device="cuda") for k, dt, w in _BC_PAYLOADS}
+        job.signal, job.basecallpos = self.d_signal.data_ptr(), self.d_positions.data_ptr()
+        for k, _, _ in _BC_PAYLOADS:
+            setattr(out, k, self.payload[k].data_ptr())
+        torch.cuda.synchronize()
+        self.mem = MEM_DEVICE
+
     def run(self, ctx, asynchronous=False):
         fn = lib().tracyhip_basecall_traces_async if asynchronous else lib().tracyhip_basecall_traces
         _check(fn(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
@@ -1464,6 +1511,8 @@ class PreparedBasecall:
         with a position outside their chromatogram (`unreadable`: status stays DEFERRED, bc_len 0)"""
         from . import hostlib
         pay = {k: (v.cpu().numpy() if self.device else v) for k, v in self.payload.items()}
+        if self.signal is None and fill_deferred and (self.meta["status"][:self.nt] == BASECALL_DEFERRED).any():
+            self.signal, self.positions = self.d_signal.cpu().numpy(), self.d_positions.cpu().numpy()
         out = []
         for t in range(self.nt):
             o, n = int(self.pos_off[t]), int(self.meta["bc_len"][t])
@@ -1492,16 +1541,154 @@ class PreparedBasecall:
         return out
 
 
-def _basecall_traces(self, signals, positions, sigratio=0.33, trim_stringency=0, device=False):
-    """tracyhip_basecall_traces.  signals: int32 or int16 [4][ns] per trace (all int16: uploaded as int16); positions: Trace::basecallpos per
+def _basecall_traces(self, signals, positions=None, sigratio=0.33, trim_stringency=0, device=False):
+    """tracyhip_basecall_traces.  signals may be the PreparedRead that Context.read_traces(device=True) returned: its chromatograms and
+    positions are taken where they lie on the GPU (positions is then ignored, device implied).  signals: int32 or int16 [4][ns] per trace (all int16: uploaded as int16); positions: Trace::basecallpos per
     trace.  device=False: host buffers, returns the per-trace results (PreparedBasecall.results).  device=True: returns the PreparedBasecall
     holding torch tensors on the GPU; .profiles_seqset() / .basecalls_struct() feed the align / consensus / decompose jobs, .results()
     copies back."""
     p = PreparedBasecall(signals, positions, sigratio, trim_stringency, device).run(self)
-    return p if device else p.results()
+    return p if p.device else p.results()
 
 
 Context.basecall_traces = _basecall_traces
+
+
+# ---- chromatogram files read on the device (tracyhip_read_traces) ---------------------------------------------------------------------
+READ_OK, READ_DEFERRED, READ_TOO_SMALL = 0, 1, 2
+
+
+class ReadJob(C.Structure):
+    _fields_ = [("ntraces", C.c_uint32), ("bytes", C.c_void_p), ("file_offset", C.POINTER(C.c_uint64)), ("file_len", C.POINTER(C.c_uint32)),
+                ("sample_bytes", C.c_uint32)]
+
+
+class ReadResult(C.Structure):
+    _fields_ = [("status", C.POINTER(C.c_int32)), ("format", C.POINTER(C.c_int32)), ("nsamples", C.POINTER(C.c_uint32)),
+                ("ncalls", C.POINTER(C.c_uint32)), ("signal", C.c_void_p), ("sample_offset", C.POINTER(C.c_uint64)),
+                ("sample_cap", C.POINTER(C.c_uint32)), ("basecallpos", C.c_void_p), ("basecalls1", C.c_void_p), ("basecalls2", C.c_void_p),
+                ("qual", C.c_void_p), ("call_offset", C.POINTER(C.c_uint64)), ("call_cap", C.POINTER(C.c_uint32))]
+
+
+_READ_PAY = ("signal", "basecallpos", "basecalls1", "basecalls2", "qual")
+
+
+def read_bound(file_len):
+    """tracyhip_read_bound: (nsamples_max, ncalls_max) that any answered file of this length fits; needs no device"""
+    ns, nc = C.c_uint32(0), C.c_uint32(0)
+    _check(lib().tracyhip_read_bound(C.c_uint32(file_len), C.byref(ns), C.byref(nc)))
+    return ns.value, nc.value
+
+
+class PreparedRead:
+    """job / result structs of tracyhip_read_traces.  files: per trace a path (read here, once) or the file image as bytes.  With
+    device=True the images and the payload results are torch tensors on the GPU and stay there: Context.basecall_traces takes this object
+    as it stands.  Everything the structs point to is kept alive by this object.
+
+    The result side starts as the sizes-only form; with_capacity() allocates the payload results, bounds() gives capacities that need no
+    sizes-only call."""
+
+    def __init__(self, files, sample_dtype=np.int16, device=False):
+        from . import hostlib
+        self.device = bool(device)
+        self.sample_dtype = np.dtype(sample_dtype)
+        f = self.flat = files if isinstance(files, dict) else hostlib.read_pack(files)
+        nt = self.nt = f["nt"]
+        job = self.job = ReadJob()
+        job.ntraces = nt
+        job.file_offset, job.file_len = _u64p(f["file_off"]), _u32p(f["file_len"])
+        job.sample_bytes = self.sample_dtype.itemsize
+        if self.device:
+            import torch
+            self.d_bytes = torch.from_numpy(f["bytes"]).cuda()
+            torch.cuda.synchronize()
+            job.bytes = self.d_bytes.data_ptr()
+        else:
+            job.bytes = f["bytes"].ctypes.data
+        self.mem = MEM_DEVICE if self.device else MEM_HOST
+        self._bind(None)
+
+    def _bind(self, o):
+        """the result struct over the arrays of `o` (hostlib.read_alloc layout; None: the sizes-only form)"""
+        self.meta = dict(status=np.zeros(max(self.nt, 1), np.int32), format=np.zeros(max(self.nt, 1), np.int32),
+                         nsamples=np.zeros(max(self.nt, 1), np.uint32), ncalls=np.zeros(max(self.nt, 1), np.uint32))
+        out = self.out = ReadResult()
+        out.status = self.meta["status"].ctypes.data_as(C.POINTER(C.c_int32))
+        out.format = self.meta["format"].ctypes.data_as(C.POINTER(C.c_int32))
+        out.nsamples, out.ncalls = _u32p(self.meta["nsamples"]), _u32p(self.meta["ncalls"])
+        self.o = o
+        if o is None:
+            return
+        out.sample_offset, out.sample_cap = _u64p(o["sample_offset"]), _u32p(o["sample_cap"])
+        out.call_offset, out.call_cap = _u64p(o["call_offset"]), _u32p(o["call_cap"])
+        for k in _READ_PAY:
+            setattr(out, k, o[k].data_ptr() if self.device else o[k].ctypes.data)
+
+    def sizes(self, ctx):
+        """the sizes-only call: (nsamples, ncalls) per trace, 0 for deferred traces"""
+        self._bind(None)
+        _check(lib().tracyhip_read_traces(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
+        return self.meta["nsamples"][:self.nt].copy(), self.meta["ncalls"][:self.nt].copy()
+
+    def bounds(self):
+        """tracyhip_read_bound per file: (sample_cap, call_cap) arrays"""
+        b = [read_bound(int(n)) for n in self.flat["file_len"][:self.nt]]
+        return np.array([x[0] for x in b], dtype=np.uint32), np.array([x[1] for x in b], dtype=np.uint32)
+
+    def with_capacity(self, sample_cap, call_cap, fill=None):
+        """payload results with room for sample_cap[t] samples per channel and call_cap[t] calls of trace t (fill: a value every payload
+        element starts with, for tests that check what a call leaves untouched)"""
+        from . import hostlib
+        o = hostlib.read_alloc(self.nt, self.sample_dtype, sample_cap, call_cap, fill)
+        if self.device:
+            import torch
+            for k in _READ_PAY:
+                o[k] = torch.from_numpy(o[k]).cuda()
+            torch.cuda.synchronize()
+        self._bind(o)
+        return self
+
+    def run(self, ctx, asynchronous=False):
+        fn = lib().tracyhip_read_traces_async if asynchronous else lib().tracyhip_read_traces
+        _check(fn(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
+        return self
+
+    def host_arrays(self):
+        """the result arrays on the host in the layout of hostlib.read_alloc (device payloads are copied back)"""
+        o = dict(self.o)
+        if self.device:
+            for k in _READ_PAY:
+                o[k] = o[k].cpu().numpy()
+        o.update(self.meta)
+        return o
+
+    def results(self, fill_deferred=True):
+        """per trace: dict(status, format, nsamples, ncalls, signal [4][ns], basecallpos, basecalls1, basecalls2, qual).  Deferred traces are
+        read by the host readers (hostlib.read_batch), except those they refuse too (`unreadable`: status stays DEFERRED)"""
+        from . import hostlib
+        o = self.host_arrays()
+        res = [hostlib.read_unpack(o, t) for t in range(self.nt)]
+        sel = [t for t in range(self.nt) if res[t]["status"] == READ_DEFERRED]
+        if fill_deferred and sel:
+            f = self.flat
+            imgs = [f["bytes"][int(f["file_off"][t]):int(f["file_off"][t]) + int(f["file_len"][t])].tobytes() for t in sel]
+            for t, r in zip(sel, hostlib.read_batch(imgs, self.sample_dtype)):
+                res[t] = r if r["status"] == 0 else dict(res[t], unreadable=True)
+        return res
+
+
+def _read_traces(self, files, sample_dtype=np.int16, device=False, asynchronous=False):
+    """tracyhip_read_traces.  files: paths or file images (bytes).  device=False: host buffers -- the sizes-only call, buffers of exactly
+    those sizes (regions that follow each other come back as one copy), the call; returns the per-trace results (PreparedRead.results).
+    device=True: capacities from tracyhip_read_bound, one call and one synchronisation; returns the PreparedRead holding torch tensors on
+    the GPU, which Context.basecall_traces takes as it stands.  asynchronous: the call is queued (tracyhip_read_traces_async); results
+    are final after Context.synchronize()."""
+    p = PreparedRead(files, sample_dtype, device)
+    p.with_capacity(*(p.bounds() if p.device else p.sizes(self))).run(self, asynchronous)
+    return p if (p.device or asynchronous) else p.results()
+
+
+Context.read_traces = _read_traces
 
 
 # ---- gapped chromatograms along alignment rows on the device (tracyhip_pad_traces) -----------------------------------------------------

@@ -1384,13 +1384,286 @@ int decompose_main(int argc, char** argv) {
   return rc_out;
 }
 
-// ---- `tracy basecall` (teal.h:24-117): host only, no device needed -------------------------------------------
-int basecall_main(int argc, char** argv) {
+// ---- `tracy basecall` (teal.h:24-117).  One file: host only, no device needed.  --batch manifest.tsv (lines: trace <TAB> output): the
+// one-file chain per line on host threads, or with -d the whole batch on the device -- the files read once into one buffer, then
+// tracyhip_read_traces -> tracyhip_basecall_traces -> tracyhip_render_traces (.abif table, JSON body) with every intermediate resident;
+// fasta / fastq are written by the host from the device's basecalls.  What a stage defers takes the one-file chain. ------------------
+struct BasecallOpts {
   float pratio = 0.33f, trimStringency = 0;
   uint16_t trimLeft = 0, trimRight = 0;
-  std::string format = "json", otype = "primary", outfile = "out.json", tracein;
+  std::string format = "json", otype = "primary";
+};
+
+bool basecall_trims_fit(uint32_t tl, uint32_t tr, std::size_t ncalls) {
+  if (tl + tr < ncalls) return true;
+  std::cerr << "The sum of the left and right trim size is larger than the trace!" << std::endl;
+  return false;
+}
+
+// traceFastaOut / traceFastqOut, fasta.h:98-155 (ns: samples per channel)
+void basecall_fastx(BasecallOpts const& o, BaseCalls const& bc, int32_t ns, uint16_t trimLeft, uint16_t trimRight, std::string const& outfile) {
+  std::ofstream f(outfile.c_str());
+  std::string const* seq = o.otype == "primary" ? &bc.primary : o.otype == "secondary" ? &bc.secondary : o.otype == "consensus" ? &bc.consensus : nullptr;
+  if (seq) {
+    f << (o.format == "fasta" ? ">" : "@") << o.otype << std::endl;
+    for (uint32_t i = trimLeft; i < seq->size() - trimRight; ++i) f << (*seq)[i];
+    f << std::endl;
+  }
+  if (o.format == "fastq") {
+    f << "+" << std::endl;
+    uint32_t call = 0;
+    int32_t next = bc.bcPos[0];
+    for (int32_t x = 0; x < ns; ++x) {
+      if (next != x) continue;
+      if (call >= trimLeft && call < bc.primary.size() - trimRight) f << (char)(bc.estQual[call] + 33);
+      if (call < bc.bcPos.size() - 1) next = bc.bcPos[++call];
+    }
+    f << std::endl;
+  }
+}
+
+// the command for one file, after its options: the exit code
+int basecall_file(BasecallOpts const& o, std::string const& tracein, std::string const& outfile) {
+  if (!regular_nonempty(tracein)) {
+    std::cerr << "Input trace file is missing: " << tracein << std::endl;
+    return 1;
+  }
+  Trace tr;
+  if (!load_trace(tracein, tr)) return -1;
+  BaseCalls bc;
+  basecall(tr, bc, o.pratio);
+  uint16_t trimLeft = o.trimLeft, trimRight = o.trimRight;
+  if (o.trimStringency >= 1) {
+    uint32_t l = 0, r = 0;
+    trimTrace(o.trimStringency, bc, l, r);
+    trimLeft = (uint16_t)l;
+    trimRight = (uint16_t)r;
+  }
+  if (!basecall_trims_fit(trimLeft, trimRight, bc.bcPos.size())) return -1;
+  if (o.format == "tsv") {
+    traceTxtOut(std::string(outfile), bc, tr, trimLeft, trimRight);
+  } else if (o.format == "fasta" || o.format == "fastq") {
+    basecall_fastx(o, bc, (int32_t)tr.traceACGT[0].size(), trimLeft, trimRight, outfile);
+  } else {  // traceJsonOut, json.h:96-105
+    std::ofstream f(outfile.c_str());
+    f << "{" << std::endl;
+    traceJsonBody(f, bc, tr);
+    f << std::endl << "}" << std::endl;
+  }
+  return 0;
+}
+
+struct BasecallLine {
+  std::string trace, output;
+  int rc = 0;
+  bool done = false;  // answered (or refused with its message) by the device path; the rest takes basecall_file
+};
+
+// device buffers of one block, freed with it
+struct DeviceBuffers {
+  tracyhip_ctx* ctx;
+  std::vector<void*> held;
+  explicit DeviceBuffers(tracyhip_ctx* c) : ctx(c) {}
+  ~DeviceBuffers() { for (void* p : held) tracyhip_device_free(ctx, p); }
+  template <class T>
+  bool get(uint64_t count, T*& p) {
+    void* q = nullptr;
+    if (tracyhip_device_alloc(ctx, count * sizeof(T) + 16, &q) != TRACYHIP_OK) return false;
+    held.push_back(q);
+    p = static_cast<T*>(q);
+    return true;
+  }
+};
+
+// lines [lo, hi) on the device.  false: a device call failed (the command ends); true: every line the device answered is done.
+bool basecall_block_on_device(tracyhip_ctx* ctx, BasecallOpts const& o, std::vector<BasecallLine>& lines, uint32_t lo, uint32_t hi, uint32_t nthreads) {
+  const uint32_t m = hi - lo;
+  // the files, read once into one buffer (a file that is missing or cannot be read has no bytes here: the device defers it and the
+  // one-file chain says why)
+  std::vector<uint64_t> file_off(m + 1, 0);
+  std::vector<uint32_t> file_len(m, 0);
+  for (uint32_t i = 0; i < m; ++i) {
+    struct stat st;
+    if (regular_nonempty(lines[lo + i].trace) && ::stat(lines[lo + i].trace.c_str(), &st) == 0 && (uint64_t)st.st_size <= 0x7fffffffull)
+      file_len[i] = (uint32_t)st.st_size;
+    file_off[i + 1] = file_off[i] + file_len[i];
+  }
+  std::unique_ptr<uint8_t[]> bytes(new uint8_t[file_off[m] + 16]);
+  for_each_index(m, nthreads, [&](uint32_t i) {
+    if (!file_len[i]) return;
+    std::FILE* f = std::fopen(lines[lo + i].trace.c_str(), "rb");
+    const std::size_t got = f ? std::fread(bytes.get() + file_off[i], 1, file_len[i], f) : 0;
+    if (f) std::fclose(f);
+    if (got != file_len[i]) std::memset(bytes.get() + file_off[i], 0, file_len[i]);  // (no magic: neither format)
+  });
+  DeviceBuffers dev(ctx);
+  uint8_t* d_bytes;
+  if (!dev.get(file_off[m], d_bytes) || tracyhip_device_copy(ctx, d_bytes, bytes.get(), file_off[m], 1) != TRACYHIP_OK) return gpu_fail("upload");
+  bytes.reset();
+
+  // file bytes -> chromatograms (int16, what ABIF stores) and call positions, capacities from the bound: one call
+  std::vector<uint64_t> sample_off(m + 1, 0), call_off(m + 1, 0);
+  std::vector<uint32_t> sample_cap(m), call_cap(m), nsamples(m), ncalls(m);
+  std::vector<int32_t> rstatus(m), format(m);
+  for (uint32_t i = 0; i < m; ++i) {
+    tracyhip_read_bound(file_len[i], &sample_cap[i], &call_cap[i]);
+    sample_off[i + 1] = sample_off[i] + 4ull * sample_cap[i];
+    call_off[i + 1] = call_off[i] + call_cap[i];
+  }
+  int16_t* d_signal;
+  int32_t* d_pos;
+  if (!dev.get(sample_off[m], d_signal) || !dev.get(call_off[m], d_pos)) return gpu_fail("device memory");
+  tracyhip_read_job rj{};
+  rj.ntraces = m; rj.bytes = d_bytes; rj.file_offset = file_off.data(); rj.file_len = file_len.data(); rj.sample_bytes = 2;
+  tracyhip_read_result rr{};
+  rr.status = rstatus.data(); rr.format = format.data(); rr.nsamples = nsamples.data(); rr.ncalls = ncalls.data();
+  rr.signal = d_signal; rr.sample_offset = sample_off.data(); rr.sample_cap = sample_cap.data();
+  rr.basecallpos = d_pos; rr.call_offset = call_off.data(); rr.call_cap = call_cap.data();
+  if (tracyhip_read_traces(ctx, &rj, TRACYHIP_MEM_DEVICE, &rr) != TRACYHIP_OK) return gpu_fail("read");
+
+  // chromatograms -> basecalls, where they lie (a trace the reader deferred has no samples: deferred here too)
+  std::vector<int32_t> bstatus(m);
+  std::vector<uint32_t> bc_len(m), trim_l(m), trim_r(m), best(m);
+  uint8_t *d_pri, *d_sec, *d_con, *d_q;
+  int32_t* d_bcpos;
+  if (!dev.get(call_off[m], d_pri) || !dev.get(call_off[m], d_sec) || !dev.get(call_off[m], d_con) || !dev.get(call_off[m], d_q) ||
+      !dev.get(call_off[m], d_bcpos))
+    return gpu_fail("device memory");
+  tracyhip_basecall_job bj{};
+  bj.ntraces = m; bj.signal = d_signal; bj.signal_offset = sample_off.data(); bj.nsamples = nsamples.data(); bj.sample_bytes = 2;
+  bj.basecallpos = d_pos; bj.pos_offset = call_off.data(); bj.npos = ncalls.data();
+  bj.sigratio = o.pratio; bj.trim_stringency = o.trimStringency >= 1 ? o.trimStringency : 0;
+  tracyhip_basecall_result br{};
+  br.status = bstatus.data(); br.bc_len = bc_len.data(); br.trim_left = trim_l.data(); br.trim_right = trim_r.data(); br.best_section = best.data();
+  br.primary = d_pri; br.secondary = d_sec; br.consensus = d_con; br.bcpos = d_bcpos; br.estqual = d_q;
+  if (tracyhip_basecall_traces(ctx, &bj, TRACYHIP_MEM_DEVICE, &br) != TRACYHIP_OK) return gpu_fail("basecall");
+  std::vector<uint8_t> answered(m, 0);
+  for (uint32_t i = 0; i < m; ++i) {
+    if (rstatus[i] != TRACYHIP_READ_OK || bstatus[i] != TRACYHIP_BASECALL_OK) continue;
+    if (o.trimStringency < 1) { trim_l[i] = o.trimLeft; trim_r[i] = o.trimRight; }
+    answered[i] = 1;
+    if (!basecall_trims_fit(trim_l[i], trim_r[i], bc_len[i])) {
+      lines[lo + i].rc = -1;
+      lines[lo + i].done = true;
+      answered[i] = 0;
+    }
+  }
+
+  if (o.format == "fasta" || o.format == "fastq") {
+    // the basecalls come back; the few lines of text are the host's
+    const uint64_t nc = call_off[m];
+    std::vector<uint8_t> pri(nc + 1), sec(nc + 1), con(nc + 1), q(nc + 1);
+    std::vector<int32_t> pos(nc + 1);
+    if (tracyhip_device_copy(ctx, pri.data(), d_pri, nc, 0) != TRACYHIP_OK || tracyhip_device_copy(ctx, sec.data(), d_sec, nc, 0) != TRACYHIP_OK ||
+        tracyhip_device_copy(ctx, con.data(), d_con, nc, 0) != TRACYHIP_OK || tracyhip_device_copy(ctx, q.data(), d_q, nc, 0) != TRACYHIP_OK ||
+        tracyhip_device_copy(ctx, pos.data(), d_bcpos, 4 * nc, 0) != TRACYHIP_OK)
+      return gpu_fail("copy back");
+    for_each_index(m, nthreads, [&](uint32_t i) {
+      if (!answered[i]) return;
+      const uint64_t at = call_off[i];
+      BaseCalls bc;
+      bc.primary.assign(reinterpret_cast<const char*>(pri.data()) + at, bc_len[i]);
+      bc.secondary.assign(reinterpret_cast<const char*>(sec.data()) + at, bc_len[i]);
+      bc.consensus.assign(reinterpret_cast<const char*>(con.data()) + at, bc_len[i]);
+      bc.bcPos.assign(pos.begin() + at, pos.begin() + at + bc_len[i]);
+      bc.estQual.assign(q.begin() + at, q.begin() + at + bc_len[i]);
+      basecall_fastx(o, bc, (int32_t)nsamples[i], (uint16_t)trim_l[i], (uint16_t)trim_r[i], lines[lo + i].output);
+      lines[lo + i].done = true;
+    });
+    return true;
+  }
+
+  // the .abif table / the JSON body: sizes first, then a text buffer of exactly those sizes, then one copy back
+  const bool tsv = o.format == "tsv";
+  tracyhip_render_job nj{};
+  nj.ntraces = m; nj.form = tsv ? TRACYHIP_RENDER_TSV : TRACYHIP_RENDER_JSON;
+  nj.signal = d_signal; nj.signal_offset = sample_off.data(); nj.nsamples = nsamples.data(); nj.sample_bytes = 2;
+  nj.bcpos = d_bcpos; nj.primary = d_pri; nj.secondary = d_sec; nj.consensus = d_con; nj.estqual = d_q;
+  nj.bc_offset = call_off.data(); nj.bc_len = bc_len.data();
+  if (tsv) { nj.trim_left_each = trim_l.data(); nj.trim_right_each = trim_r.data(); }
+  std::vector<int32_t> tstatus(m);
+  std::vector<uint32_t> text_len(m);
+  tracyhip_render_result nr{};
+  nr.status = tstatus.data(); nr.text_len = text_len.data();
+  if (tracyhip_render_traces(ctx, &nj, TRACYHIP_MEM_DEVICE, &nr) != TRACYHIP_OK) return gpu_fail("render");
+  std::vector<uint64_t> text_off(m + 1, 0), text_cap(m);
+  for (uint32_t i = 0; i < m; ++i) {
+    text_cap[i] = answered[i] ? text_len[i] : 0;  // (a line that is already settled gets no text: TOO_SMALL, nothing written)
+    text_off[i + 1] = text_off[i] + text_cap[i];
+  }
+  uint8_t* d_text;
+  if (!dev.get(text_off[m], d_text)) return gpu_fail("device memory");
+  nr.text = d_text; nr.text_offset = text_off.data(); nr.text_cap = text_cap.data();
+  if (tracyhip_render_traces(ctx, &nj, TRACYHIP_MEM_DEVICE, &nr) != TRACYHIP_OK) return gpu_fail("render");
+  std::unique_ptr<uint8_t[]> text(new uint8_t[text_off[m] + 1]);
+  if (tracyhip_device_copy(ctx, text.get(), d_text, text_off[m], 0) != TRACYHIP_OK) return gpu_fail("copy back");
+  for_each_index(m, nthreads, [&](uint32_t i) {
+    if (!answered[i] || tstatus[i] != TRACYHIP_RENDER_OK) return;
+    std::ofstream f(lines[lo + i].output.c_str(), std::ios::binary);
+    if (!tsv) f << "{" << std::endl;
+    f.write(reinterpret_cast<const char*>(text.get()) + text_off[i], (std::streamsize)text_len[i]);
+    if (!tsv) f << std::endl << "}" << std::endl;
+    lines[lo + i].done = true;
+  });
+  return true;
+}
+
+int basecall_batch(BasecallOpts const& o, std::string const& manifest, bool on_device, std::string const& devices, uint32_t threads) {
+  std::ifstream mf(manifest.c_str());
+  if (!mf) {
+    std::cerr << "Manifest is missing: " << manifest << std::endl;
+    return 1;
+  }
+  std::vector<BasecallLine> lines;
+  std::string line;
+  while (std::getline(mf, line)) {
+    if (line.empty() || line[0] == '#') continue;
+    std::istringstream ss(line);
+    BasecallLine l;
+    if (!std::getline(ss, l.trace, '\t') || !std::getline(ss, l.output, '\t')) {
+      std::cerr << "Malformed manifest line: " << line << std::endl;
+      return 1;
+    }
+    lines.push_back(std::move(l));
+  }
+  const uint32_t n = (uint32_t)lines.size(), nthreads = threads ? threads : usable_cores();
+  // the device answers what the one-file command computes for -t 0 and -t 1 .. 9 (above 9 trimTrace is called unclamped there)
+  if (on_device && n && o.trimStringency <= 9) {
+    Device dev;
+    if (dev.open(devices, 1) != 0) {
+      gpu_fail("no usable GPU");
+      return -1;
+    }
+    const uint32_t block = 2048;  // lines whose files, chromatograms and text are resident together
+    for (uint32_t lo = 0; lo < n; lo += block)
+      if (!basecall_block_on_device(dev.ctx, o, lines, lo, std::min(n, lo + block), nthreads)) return -1;
+    uint32_t answered = 0;
+    for (BasecallLine const& l : lines) answered += l.done && l.rc == 0;
+    std::cout << stamp() << "Device: " << answered << " of " << n << " traces read, basecalled and written" << std::endl;
+  }
+  // the one-file chain for what is left; a handful of lines goes one after the other, so that their messages do not run into each other
+  uint32_t left = 0;
+  for (BasecallLine const& l : lines) left += !l.done;
+  for_each_index(n, left <= 64 ? 1 : nthreads, [&](uint32_t i) {
+    if (!lines[i].done) lines[i].rc = basecall_file(o, lines[i].trace, lines[i].output);
+  });
+  uint32_t failed = 0;
+  for (BasecallLine const& l : lines)
+    if (l.rc != 0) {
+      std::cerr << "skipping " << l.trace << std::endl;
+      ++failed;
+    }
+  std::cout << stamp() << "Done." << std::endl;
+  return failed ? 2 : 0;
+}
+
+int basecall_main(int argc, char** argv) {
+  BasecallOpts o;
+  std::string outfile = "out.json", tracein, batch, devices;
+  uint32_t threads = 0;
   static const std::map<std::string, char> longs = {{"help", '?'}, {"pratio", 'p'}, {"format", 'f'}, {"otype", 'y'}, {"trim", 't'},
-                                                    {"trimLeft", 'q'}, {"trimRight", 'u'}, {"output", 'o'}};
+                                                    {"trimLeft", 'q'}, {"trimRight", 'u'}, {"output", 'o'}, {"batch", 'b'}, {"device", 'd'},
+                                                    {"threads", 'T'}};
   bool bad = false;
   for (int i = 1; i < argc && !bad; ++i) {
     std::string a = argv[i], val;
@@ -1416,18 +1689,22 @@ int basecall_main(int argc, char** argv) {
       val = argv[++i];
     }
     switch (opt) {
-      case 'p': pratio = std::strtof(val.c_str(), nullptr); break;
-      case 'f': format = val; break;
-      case 'y': otype = val; break;
-      case 't': trimStringency = std::strtof(val.c_str(), nullptr); break;
-      case 'q': trimLeft = (uint16_t)std::atoi(val.c_str()); break;
-      case 'u': trimRight = (uint16_t)std::atoi(val.c_str()); break;
+      case 'p': o.pratio = std::strtof(val.c_str(), nullptr); break;
+      case 'f': o.format = val; break;
+      case 'y': o.otype = val; break;
+      case 't': o.trimStringency = std::strtof(val.c_str(), nullptr); break;
+      case 'q': o.trimLeft = (uint16_t)std::atoi(val.c_str()); break;
+      case 'u': o.trimRight = (uint16_t)std::atoi(val.c_str()); break;
       case 'o': outfile = val; break;
+      case 'b': batch = val; break;
+      case 'd': devices = val; break;
+      case 'T': threads = (uint32_t)std::atoi(val.c_str()); break;
       default: std::cerr << "unrecognised option '" << a << "'" << std::endl; bad = true; break;
     }
   }
-  if (bad || tracein.empty()) {
+  if (bad || (tracein.empty() && batch.empty())) {
     std::cout << "Usage: tracy " << argv[0] << " [OPTIONS] trace.ab1" << std::endl;
+    std::cout << "       tracy " << argv[0] << " [OPTIONS] --batch manifest.tsv" << std::endl;
     std::cout << "Generic options:\n"
                  "  -? [ --help ]                    show help message\n"
                  "  -p [ --pratio ] arg (=0.33)      peak ratio to call a base\n"
@@ -1436,55 +1713,17 @@ int basecall_main(int argc, char** argv) {
                  "  -t [ --trim ] arg (=0)           trimming stringency [1:9], 0: use trimLeft and trimRight\n"
                  "  -q [ --trimLeft ] arg (=0)       trim size left\n"
                  "  -u [ --trimRight ] arg (=0)      trim size right\n"
-                 "  -o [ --output ] arg (=out.json)  basecalling output\n\n";
+                 "  -o [ --output ] arg (=out.json)  basecalling output\n"
+                 "  -b [ --batch ] arg               manifest: trace<TAB>output per line\n"
+                 "  --threads arg (=0)               host threads of a --batch run (0 = all usable cores)\n"
+                 "  -d [ --device ] arg              GPU ordinal: a --batch run reads, basecalls and prints on the device\n"
+                 "                                   (without it: host threads, no device needed)\n\n";
     return -1;
   }
   echo_command(argc, argv);
-  if (!regular_nonempty(tracein)) {
-    std::cerr << "Input trace file is missing: " << tracein << std::endl;
-    return 1;
-  }
-  Trace tr;
-  if (!load_trace(tracein, tr)) return -1;
-  BaseCalls bc;
-  basecall(tr, bc, pratio);
-  if (trimStringency >= 1) {
-    uint32_t l = 0, r = 0;
-    trimTrace(trimStringency, bc, l, r);
-    trimLeft = (uint16_t)l;
-    trimRight = (uint16_t)r;
-  }
-  if ((uint32_t)trimLeft + trimRight >= bc.bcPos.size()) {
-    std::cerr << "The sum of the left and right trim size is larger than the trace!" << std::endl;
-    return -1;
-  }
-  if (format == "tsv") {
-    traceTxtOut(std::string(outfile), bc, tr, trimLeft, trimRight);
-  } else if (format == "fasta" || format == "fastq") {  // traceFastaOut / traceFastqOut, fasta.h:98-155
-    std::ofstream f(outfile.c_str());
-    std::string const* seq = otype == "primary" ? &bc.primary : otype == "secondary" ? &bc.secondary : otype == "consensus" ? &bc.consensus : nullptr;
-    if (seq) {
-      f << (format == "fasta" ? ">" : "@") << otype << std::endl;
-      for (uint32_t i = trimLeft; i < seq->size() - trimRight; ++i) f << (*seq)[i];
-      f << std::endl;
-    }
-    if (format == "fastq") {
-      f << "+" << std::endl;
-      uint32_t call = 0;
-      int32_t next = bc.bcPos[0];
-      for (int32_t x = 0; x < (int32_t)tr.traceACGT[0].size(); ++x) {
-        if (next != x) continue;
-        if (call >= trimLeft && call < bc.primary.size() - trimRight) f << (char)(bc.estQual[call] + 33);
-        if (call < bc.bcPos.size() - 1) next = bc.bcPos[++call];
-      }
-      f << std::endl;
-    }
-  } else {  // traceJsonOut, json.h:96-105
-    std::ofstream f(outfile.c_str());
-    f << "{" << std::endl;
-    traceJsonBody(f, bc, tr);
-    f << std::endl << "}" << std::endl;
-  }
+  if (!batch.empty()) return basecall_batch(o, batch, !devices.empty(), devices, threads);
+  const int rc = basecall_file(o, tracein, outfile);
+  if (rc != 0) return rc;
   std::cout << stamp() << "Done." << std::endl;
   return 0;
 }

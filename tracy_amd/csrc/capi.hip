@@ -1316,6 +1316,32 @@ int tracyhip_synchronize(tracyhip_ctx* c) {
   return TRACYHIP_OK;
 }
 
+int tracyhip_device_alloc(tracyhip_ctx* c, uint64_t bytes, void** out) {
+  if (!out) return set_error(TRACYHIP_ERR_ARG, "tracyhip_device_alloc: null out");
+  *out = nullptr;
+  int rc = ctx_begin(c);
+  if (rc) return rc;
+  HIP_TRY(hipMalloc(out, bytes ? bytes : 1));
+  return TRACYHIP_OK;
+}
+
+int tracyhip_device_free(tracyhip_ctx* c, void* p) {
+  int rc = ctx_begin(c);
+  if (rc) return rc;
+  if (p) HIP_TRY(hipFree(p));
+  return TRACYHIP_OK;
+}
+
+int tracyhip_device_copy(tracyhip_ctx* c, void* dst, const void* src, uint64_t bytes, int to_device) {
+  int rc = ctx_begin(c);
+  if (rc) return rc;
+  if (bytes == 0) return TRACYHIP_OK;
+  if (!dst || !src) return set_error(TRACYHIP_ERR_ARG, "tracyhip_device_copy: null dst / src");
+  HIP_TRY(hipMemcpyAsync(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return TRACYHIP_OK;
+}
+
 int tracyhip_gotoh_score_async(tracyhip_ctx* ctx, const tracyhip_pairs* pairs, const tracyhip_params* prm, int mem, int32_t* scores) {
   if (!ctx || !pairs || !prm) return set_error(TRACYHIP_ERR_ARG, "null context / pairs / params");
   const tracyhip_pairs p = *pairs;

@@ -200,7 +200,11 @@ enum CtxDev : int {
                      // render_scan_kernel, read by render_emit_kernel
   DB_RENDER_IN,      // a host caller's chromatograms and basecall arrays of a chunk, staged in
   DB_RENDER_OUT,     // the text of a chunk staged for a host caller
-  DB_COUNT = DB_RENDER_OUT + 1
+  // ---- tracyhip_read_traces (read.hip) ----
+  DB_READ_FILES,     // ReadFile per file up, ReadDesc per file written by read_scan_kernel and brought back
+  DB_READ_IN,        // a host caller's file images of a chunk, staged in
+  DB_READ_OUT,       // chromatograms and call arrays of a chunk staged for a host caller
+  DB_COUNT = DB_READ_OUT + 1
 };
 static_assert(DN_CNT + 1 == VB_DESC && VB_PACK_TEXT + 1 == WB_ORIENTED && DN_PAY < DB_COUNT && WB_PAY < DB_COUNT,
               "an alias does not advance the count: every slot of its own comes after the aliases");
@@ -348,6 +352,7 @@ struct tracyhip_ctx {
   tracyhip_call_stats stats = {};  // tiers of the last pipeline call (tracyhip_last_call_stats)
   tracyhip_pad_stats pad_stats = {};  // of the last tracyhip_pad_traces call (tracyhip_last_pad_stats)
   tracyhip_render_stats render_stats = {};  // of the last tracyhip_render_traces call (tracyhip_last_render_stats)
+  tracyhip_read_stats read_stats = {};  // of the last tracyhip_read_traces call (tracyhip_last_read_stats)
   std::vector<Pending> pending;
   std::vector<hipEvent_t> free_events;
   tracyhip_kernel_timing acc[TRACYHIP_TIMER_COUNT] = {};

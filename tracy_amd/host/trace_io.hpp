@@ -36,13 +36,15 @@ namespace tracy_amd {
 
 namespace detail {
 
-// big-endian view of a whole file
+// big-endian view of a whole file: one it loaded and owns, or an image in memory that somebody else keeps (view)
 class FileBytes {
  public:
+  void view(const uint8_t* image, std::size_t n) { b_.reset(); d_ = image; n_ = n; }
   // one open / fstat / read (a manifest is 10^4 files of 100 KB: no stream object, no seek, no zero fill of the buffer); anything
   // that is not a regular file (a pipe) is read to its end in growing steps
   bool load(std::string const& filename) {
     n_ = 0;
+    d_ = nullptr;
     const int fd = ::open(filename.c_str(), O_RDONLY | O_CLOEXEC);
     if (fd < 0) return false;
     struct stat st;
@@ -64,22 +66,24 @@ class FileBytes {
       got += (std::size_t)r;
     }
     ::close(fd);
+    d_ = b_.get();
     n_ = got;
     return true;
   }
   std::size_t size() const { return n_; }
   bool has(std::size_t pos, std::size_t len) const { return pos <= n_ && len <= n_ - pos; }
-  uint8_t u8(std::size_t p) const { return b_[p]; }
-  int16_t i16(std::size_t p) const { return (int16_t)(uint16_t)((b_[p] << 8) | b_[p + 1]); }
+  uint8_t u8(std::size_t p) const { return d_[p]; }
+  int16_t i16(std::size_t p) const { return (int16_t)(uint16_t)((d_[p] << 8) | d_[p + 1]); }
   int32_t i32(std::size_t p) const {
-    return (int32_t)(((uint32_t)b_[p] << 24) | ((uint32_t)b_[p + 1] << 16) | ((uint32_t)b_[p + 2] << 8) | (uint32_t)b_[p + 3]);
+    return (int32_t)(((uint32_t)d_[p] << 24) | ((uint32_t)d_[p + 1] << 16) | ((uint32_t)d_[p + 2] << 8) | (uint32_t)d_[p + 3]);
   }
-  std::string str(std::size_t p, std::size_t len) const { return std::string(reinterpret_cast<const char*>(b_.get()) + p, len); }
-  const char* chars() const { return reinterpret_cast<const char*>(b_.get()); }
-  bool starts_with(const char* magic4) const { return n_ >= 4 && std::memcmp(b_.get(), magic4, 4) == 0; }
+  std::string str(std::size_t p, std::size_t len) const { return std::string(reinterpret_cast<const char*>(d_) + p, len); }
+  const char* chars() const { return reinterpret_cast<const char*>(d_); }
+  bool starts_with(const char* magic4) const { return n_ >= 4 && std::memcmp(d_, magic4, 4) == 0; }
 
  private:
   std::unique_ptr<uint8_t[]> b_;
+  const uint8_t* d_ = nullptr;  // b_.get(), or the viewed image
   std::size_t n_ = 0;
 };
 

@@ -900,6 +900,68 @@ int tracyhost_render_batch(uint32_t n, uint32_t form, const void* signal, const 
   return 0;
 }
 
+// ---- the readers over a batch of file images, one file after the other per thread: traceFormat, readab / readscf (trace_io.hpp) into the
+// flattened arrays of tracyhip_read_traces (the fallback for its deferred traces; tools and the command line time it beside the device
+// call) ----
+// status: 0 read; 1 the reader refuses the image, or a sample does not fit sample_bytes = 2; 2 a capacity is too small (sizes reported).
+// format is traceFormat's.  Channels shorter than the longest are zero padded, as tracyhost_trace_get does.  Payload results may be null
+// (all null: sizes only).
+int tracyhost_read_batch(uint32_t n, const uint8_t* bytes, const uint64_t* file_offset, const uint32_t* file_len, uint32_t sample_bytes, int32_t* status,
+                         int32_t* format, uint32_t* nsamples, uint32_t* ncalls, void* o_signal, const uint64_t* sample_offset, const uint32_t* sample_cap,
+                         int32_t* o_pos, uint8_t* o_b1, uint8_t* o_b2, uint8_t* o_qual, const uint64_t* call_offset, const uint32_t* call_cap,
+                         uint32_t nthreads) {
+  const bool want_calls = o_pos || o_b1 || o_b2 || o_qual;
+  if (n && (!bytes || !file_offset || !file_len || !status || !format || !nsamples || !ncalls)) return -1;
+  if ((sample_bytes != 2 && sample_bytes != 4) || (o_signal && (!sample_offset || !sample_cap)) || (want_calls && (!call_offset || !call_cap))) return -1;
+  if (nthreads == 0) nthreads = tracy_amd::usable_threads();
+  std::vector<std::thread> th;
+  for (uint32_t w = 0; w < nthreads; ++w)
+    th.emplace_back([=]() {
+      for (uint32_t t = (uint32_t)((uint64_t)n * w / nthreads); t < (uint32_t)((uint64_t)n * (w + 1) / nthreads); ++t) {
+        detail::FileBytes f;
+        f.view(bytes + file_offset[t], file_len[t]);
+        status[t] = 1;
+        nsamples[t] = ncalls[t] = 0;
+        const int32_t ft = format[t] = traceFormat(f);
+        Trace tr;
+        if (!(ft == 0 ? readab(f, tr) : ft == 1 ? readscf(f, tr) : false)) continue;
+        size_t ns = 0;
+        for (auto const& c : tr.traceACGT) ns = std::max(ns, c.size());
+        const size_t nc = tr.basecallpos.size();
+        bool fits = ns <= 0xffffffffull && nc <= 0xffffffffull;
+        if (fits && sample_bytes == 2)
+          for (auto const& c : tr.traceACGT)
+            for (int32_t v : c) fits = fits && v >= -32768 && v <= 32767;
+        if (!fits) continue;
+        nsamples[t] = (uint32_t)ns; ncalls[t] = (uint32_t)nc;
+        if ((o_signal && ns > sample_cap[t]) || (want_calls && nc > call_cap[t])) { status[t] = 2; continue; }
+        status[t] = 0;
+        if (o_signal)
+          for (size_t k = 0; k < 4; ++k) {
+            const uint64_t at = sample_offset[t] + (uint64_t)k * ns;
+            for (size_t x = 0; x < ns; ++x) {
+              const int32_t v = (k < tr.traceACGT.size() && x < tr.traceACGT[k].size()) ? tr.traceACGT[k][x] : 0;
+              if (sample_bytes == 4) static_cast<int32_t*>(o_signal)[at + x] = v;
+              else static_cast<int16_t*>(o_signal)[at + x] = (int16_t)v;
+            }
+          }
+        if (!want_calls) continue;
+        const uint64_t co = call_offset[t];
+        if (o_pos && nc) std::memcpy(o_pos + co, tr.basecallpos.data(), 4 * nc);
+        auto put = [&](uint8_t* dst, const void* src, size_t have) {  // (nc bytes: what the Trace holds, zeros behind it)
+          if (!dst) return;
+          std::memset(dst + co, 0, nc);
+          if (have) std::memcpy(dst + co, src, std::min(nc, have));
+        };
+        put(o_b1, tr.basecalls1.data(), tr.basecalls1.size());
+        put(o_b2, tr.basecalls2.data(), tr.basecalls2.size());
+        put(o_qual, tr.qual.data(), tr.qual.size());
+      }
+    });
+  for (auto& t : th) t.join();
+  return 0;
+}
+
 // threads the batch entry points start when the caller passes nthreads = 0
 uint32_t tracyhost_usable_threads() { return tracy_amd::usable_threads(); }
 

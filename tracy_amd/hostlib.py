@@ -662,3 +662,77 @@ def render_batch(flat, form, nthreads=0):
     sizes = render_batch_raw(flat, form, render_alloc(flat["nt"], np.zeros(flat["nt"], np.uint64)), nthreads, sizes_only=True)
     out = render_batch_raw(flat, form, render_alloc(flat["nt"], sizes["text_len"]), nthreads)
     return [render_unpack(out, t) for t in range(flat["nt"])]
+
+
+# ---- the readers over a batch of file images on the host (tracyhost_read_batch): the fallback and the baseline of tracyhip_read_traces ---
+READ_KINDS = (("signal", None), ("basecallpos", np.int32), ("basecalls1", np.uint8), ("basecalls2", np.uint8), ("qual", np.uint8))
+
+
+def read_pack(files):
+    """file images (bytes, or paths that are read here) one after another: dict(nt, bytes, file_off, file_len)"""
+    imgs = []
+    for f in files:
+        if isinstance(f, (bytes, bytearray, memoryview)):
+            imgs.append(bytes(f))
+        else:
+            with open(f, "rb") as fh:
+                imgs.append(fh.read())
+    nt = len(imgs)
+    flen = np.array([len(b) for b in imgs] + [0], dtype=np.uint32)
+    off = np.zeros(nt + 1, np.uint64)
+    off[1:] = np.cumsum(flen[:nt].astype(np.uint64))
+    return dict(nt=nt, bytes=np.frombuffer(b"".join(imgs) + b"\0" * 4, np.uint8).copy(), file_off=off, file_len=flen)
+
+
+def read_alloc(nt, sample_dtype, nsamples, ncalls, fill=None):
+    """result arrays of a reading call with room for nsamples[t] samples per channel and ncalls[t] calls of trace t"""
+    scap = np.ascontiguousarray(nsamples, dtype=np.uint32)[:nt].copy() if nt else np.zeros(0, np.uint32)
+    ccap = np.ascontiguousarray(ncalls, dtype=np.uint32)[:nt].copy() if nt else np.zeros(0, np.uint32)
+    o = dict(sample_cap=np.append(scap, np.uint32(0)), call_cap=np.append(ccap, np.uint32(0)))
+    o["sample_offset"] = np.zeros(nt + 1, np.uint64)
+    o["call_offset"] = np.zeros(nt + 1, np.uint64)
+    o["sample_offset"][1:] = np.cumsum(4 * scap.astype(np.uint64))
+    o["call_offset"][1:] = np.cumsum(ccap.astype(np.uint64))
+    for k, dt in READ_KINDS:
+        size = max(int(o["sample_offset" if k == "signal" else "call_offset"][nt]), 1)
+        o[k] = np.zeros(size, dt or sample_dtype) if fill is None else np.full(size, fill, dt or sample_dtype)
+    o["status"] = np.zeros(max(nt, 1), np.int32)
+    o["format"] = np.zeros(max(nt, 1), np.int32)
+    o["nsamples"] = np.zeros(max(nt, 1), np.uint32)
+    o["ncalls"] = np.zeros(max(nt, 1), np.uint32)
+    return o
+
+
+def read_batch_raw(flat, out, nthreads=0, sizes_only=False):
+    """one tracyhost_read_batch call over packed file images (read_pack) into `out` (read_alloc)"""
+    p = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+    pay = (lambda k: None) if sizes_only else (lambda k: p(out[k]))
+    rc = lib().tracyhost_read_batch(C.c_uint32(flat["nt"]), p(flat["bytes"]), p(flat["file_off"]), p(flat["file_len"]),
+                                    C.c_uint32(out["signal"].dtype.itemsize), p(out["status"]), p(out["format"]), p(out["nsamples"]), p(out["ncalls"]),
+                                    pay("signal"), p(out["sample_offset"]), p(out["sample_cap"]), pay("basecallpos"), pay("basecalls1"),
+                                    pay("basecalls2"), pay("qual"), p(out["call_offset"]), p(out["call_cap"]), C.c_uint32(nthreads))
+    if rc != 0:
+        raise ValueError("tracyhost_read_batch: bad arguments")
+    return out
+
+
+def read_unpack(out, t):
+    """trace t of a finished reading call (read_alloc layout, host arrays) in the fields of read_trace, with its status"""
+    st, ns, nc = int(out["status"][t]), int(out["nsamples"][t]), int(out["ncalls"][t])
+    r = dict(status=st, format=int(out["format"][t]), nsamples=ns, ncalls=nc)
+    if st != 0:
+        return r
+    so, co = int(out["sample_offset"][t]), int(out["call_offset"][t])
+    r.update(signal=out["signal"][so:so + 4 * ns].reshape(4, ns), basecallpos=out["basecallpos"][co:co + nc],
+             basecalls1=out["basecalls1"][co:co + nc].tobytes(), basecalls2=out["basecalls2"][co:co + nc].tobytes(), qual=out["qual"][co:co + nc])
+    return r
+
+
+def read_batch(files, sample_dtype=np.int32, nthreads=0):
+    """read a batch of file images on host threads: a sizes-only call, buffers of exactly those sizes, the call; per-trace dicts (status 1:
+    the reader refuses the image, or a sample does not fit the sample type)"""
+    flat = files if isinstance(files, dict) else read_pack(files)
+    nt = flat["nt"]
+    sizes = read_batch_raw(flat, read_alloc(nt, sample_dtype, np.zeros(nt, np.uint32), np.zeros(nt, np.uint32)), nthreads, sizes_only=True)
+    out = read_batch_raw(flat, read_alloc(nt, sample_dtype, sizes["nsamples"], sizes["ncalls"]), nthreads)
+    return [read_unpack(out, t) for t in range(nt)]
