@@ -853,6 +853,88 @@ typedef struct {
 } tracyhip_render_stats;
 int tracyhip_last_render_stats(tracyhip_ctx* ctx, tracyhip_render_stats* out);
 
+/* ---- the text of a batch of alignments: what the writers of `align` and `decompose` print from the two gapped rows, byte for byte
+ * (tracy_amd/host sage_out.hpp plotAlignment, alignFastaOut, the tail of traceAlignJsonOut) -- where tracyhip_render_traces' GAPPED form
+ * stops ------------------------------------------------------------------------------------------------------------------------
+ * Alignment i owns cols[i] bytes of rows0 and of rows1 from rows_offset[i] on: the rows of tracyhip_align_result (ops_offset, ops_len) and
+ * of tracyhip_alignment_rows are taken as they stand.  Rows may hold any byte; only '-' is a gap.  The two names are the caller's text,
+ * printed byte for byte (never escaped, as the writers do not escape):
+ *   PLOT   name0 = the first header line without its newline (">Alt", ">Alt1 (Estimated allelic Fraction: 0.5)": the double stays the
+ *          caller's), name1 = the second (">Ref chr:a-b forward", ...).  Everything else is the device's: the two ungapped rows broken
+ *          every linelimit + 14 letters, the score line, the rules, one block per linelimit columns with its two counters (the row-1
+ *          counter runs upward from ref_pos + 1; forward == 0 and key != 3 prints ref_pos + ref_len - (letters of row 1 in front)), the
+ *          spacer of 4 x (6 - blocks) newlines, the tail.  key: 0 .. 2 label "Alt" / "Ref" at setw(10), 3 "Alt1" / "Alt2" at setw(9).
+ *   FASTA  ">" name0 "\n" row0 "\n>" name1 " (forward)" | " (reverse)" "\n" row1 "\n"  (name0 the trace stem, name1 rs.chr)
+ *   JSON   from the ",\n\"refchr\": \"" behind assemblyTrace's closing brace through "\"forward\": 0|1\n}\n"; name1 = rs.chr (name0 is
+ *          not read), refpos = ref_pos + 1.
+ * The device answers an alignment when cols <= 2^22, both names are at most 65535 bytes, ref_pos >= 0 and
+ * ref_pos + max(ref_len, cols) + 1 < 2^31, and -- PLOT with forward == 0 and key != 3 -- row 1 holds at most ref_len letters (found from
+ * the data).  Any other alignment is DEFERRED: status and text_len = 0 are written, nothing else; tracyhost_alntext_batch prints it. */
+#define TRACYHIP_ALNTEXT_PLOT  0
+#define TRACYHIP_ALNTEXT_FASTA 1
+#define TRACYHIP_ALNTEXT_JSON  2
+#define TRACYHIP_ALNTEXT_OK 0
+#define TRACYHIP_ALNTEXT_DEFERRED 1
+#define TRACYHIP_ALNTEXT_TOO_SMALL 2 /* text_cap is too small: text_len is reported, no text is written */
+typedef struct {
+  uint32_t n, form;
+  uint32_t key;                /* PLOT only: 0 .. 3 */
+  uint32_t linelimit;          /* PLOT only: 1 .. 65535 */
+  const uint8_t *rows0, *rows1; /* payload */
+  const uint64_t* rows_offset; /* HOST array */
+  const uint32_t* cols;        /* HOST array */
+  const uint8_t* names;        /* payload: name0 of alignment i is name0_len[i] bytes at name0_offset[i], name1 likewise */
+  const uint64_t* name0_offset; /* HOST arrays */
+  const uint32_t* name0_len;
+  const uint64_t* name1_offset;
+  const uint32_t* name1_len;
+  const int32_t* ref_pos;      /* HOST array: rs.pos */
+  const uint32_t* ref_len;     /* HOST array: rs.refslice.size() */
+  const uint8_t* forward;      /* HOST array: rs.forward */
+  const int32_t* score;        /* HOST array (PLOT) */
+} tracyhip_alntext_job;
+typedef tracyhip_render_result tracyhip_alntext_result; /* status (TRACYHIP_ALNTEXT_*), text_len, text, text_offset, text_cap */
+/* what tracyhip_render_alignments refuses before it touches a device (none is needed here): NULL job / result / required arrays, mem, form,
+ * a PLOT with key > 3 or linelimit outside 1 .. 65535, a text without its offsets and capacities.  TRACYHIP_ERR_ARG (with the reason)
+ * otherwise TRACYHIP_OK. */
+int tracyhip_render_alignments_validate(const tracyhip_alntext_job* job, int mem, const tracyhip_alntext_result* out);
+/* Three launches (count the bytes of every tile, scan them per alignment, emit) behind one that counts the letters of a plot's rows per
+ * tile of columns; all but the last in the sizes-only form (text NULL).  Device payloads: ONE host synchronisation per call.  Host payloads are staged in chunks of consecutive
+ * alignments within the workspace limit, with a second synchronisation each for the copy back of exactly the bytes that were reported.
+ * An offset + length that leaves 64 bits is TRACYHIP_ERR_RANGE before any launch. */
+int tracyhip_render_alignments(tracyhip_ctx* ctx, const tracyhip_alntext_job* job, int mem, const tracyhip_alntext_result* out);
+/* an upper bound of text_len of an alignment of these sizes, whatever its bytes and numbers; needs no device.  0: no such form, or a
+ * linelimit outside 1 .. 65535 for a PLOT. */
+uint64_t tracyhip_render_alignments_bound(uint32_t form, uint32_t linelimit, uint32_t cols, uint32_t name0_len, uint32_t name1_len);
+/* counters of the last tracyhip_render_alignments call of a context */
+typedef struct {
+  uint32_t alntext_chunks;    /* chunks of alignments the batch was cut into */
+  uint32_t alntext_deferred;  /* alignments with TRACYHIP_ALNTEXT_DEFERRED */
+  uint32_t alntext_too_small; /* alignments with TRACYHIP_ALNTEXT_TOO_SMALL */
+} tracyhip_alntext_stats;
+int tracyhip_last_alntext_stats(tracyhip_ctx* ctx, tracyhip_alntext_stats* out);
+
+/* ---- the oriented reference slice of a CHAR-reference align job on the device: what the caller of tracyhip_align_traces does on the
+ * host today between that call and tracyhip_alignment_rows ----------------------------------------------------------------------
+ * Slice i = oriented.substr(slice_begin[i], slice_len[i]) at out + out_offset[i], where oriented is refs[ref_index ? ref_index[i] : i]
+ * itself when forward[i] != 0 and otherwise its reverse complement by the byte rule of reverseComplement (fmindex.h:11-25: A C G T N in
+ * either case complement to upper case; at any other letter the output position keeps the byte the reference has THERE).  forward,
+ * slice_begin and slice_len are the arrays tracyhip_align_traces returned.  refs (kind CHAR) and out lie where `mem` says; the index and
+ * offset arrays are HOST arrays.  Checked on the host before any launch: NULL arrays, refs of another kind, a ref_index out of range
+ * (TRACYHIP_ERR_ARG); slice_begin + slice_len beyond the reference (TRACYHIP_ERR_RANGE).  One launch, one wave per tile of output bytes;
+ * one host synchronisation.  The chain align_traces(MEM_DEVICE) -> reference_slices -> alignment_rows(MEM_DEVICE) ->
+ * pad_traces / render_alignments then needs no payload on the host. */
+typedef struct {
+  uint32_t n;
+  tracyhip_seqset refs;        /* kind CHAR */
+  const uint32_t* ref_index;   /* HOST array or NULL (= identity) */
+  const uint8_t* forward;      /* HOST arrays [n] */
+  const uint32_t* slice_begin;
+  const uint32_t* slice_len;
+} tracyhip_slices_job;
+int tracyhip_reference_slices_validate(const tracyhip_slices_job* job, int mem, const uint8_t* out, const uint64_t* out_offset);
+int tracyhip_reference_slices(tracyhip_ctx* ctx, const tracyhip_slices_job* job, int mem, uint8_t* out, const uint64_t* out_offset);
+
 /* ---- chromatogram files: a batch of ABIF / SCF file images turned into the arrays the readers produce (readab abif.h:286-405, traceFormat
  * scf.h:18-34, readscf scf.h:38-102) -- the first step of every command ----------------------------------------------------------
  * The images lie one after another in `bytes`, file t at file_offset[t] (any alignment), file_len[t] bytes long.  Every field of an
@@ -1067,6 +1149,8 @@ int tracyhip_basecall_traces_async(tracyhip_ctx* ctx, const tracyhip_basecall_jo
 int tracyhip_pad_traces_async(tracyhip_ctx* ctx, const tracyhip_pad_job* job, int mem, const tracyhip_pad_result* out);
 int tracyhip_render_traces_async(tracyhip_ctx* ctx, const tracyhip_render_job* job, int mem, const tracyhip_render_result* out);
 int tracyhip_read_traces_async(tracyhip_ctx* ctx, const tracyhip_read_job* job, int mem, const tracyhip_read_result* out);
+int tracyhip_render_alignments_async(tracyhip_ctx* ctx, const tracyhip_alntext_job* job, int mem, const tracyhip_alntext_result* out);
+int tracyhip_reference_slices_async(tracyhip_ctx* ctx, const tracyhip_slices_job* job, int mem, uint8_t* out, const uint64_t* out_offset);
 int tracyhip_assemble_traces_async(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem,
                                    const tracyhip_assemble_result* out);
 int tracyhip_denovo_traces_async(tracyhip_ctx* ctx, const tracyhip_denovo_job* job, const tracyhip_params* prm, int mem,

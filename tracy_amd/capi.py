@@ -120,6 +120,11 @@ class RenderStats(C.Structure):
     _fields_ = [("render_chunks", C.c_uint32), ("render_deferred", C.c_uint32), ("render_too_small", C.c_uint32)]
 
 
+class AlnTextStats(C.Structure):
+    """tracyhip_alntext_stats: the counters of tracyhip_render_alignments, in a struct of their own as RenderStats"""
+    _fields_ = [("alntext_chunks", C.c_uint32), ("alntext_deferred", C.c_uint32), ("alntext_too_small", C.c_uint32)]
+
+
 class ReadStats(C.Structure):
     """tracyhip_read_stats: the counters of tracyhip_read_traces, in a struct of their own as PadStats"""
     _fields_ = [("read_chunks", C.c_uint32), ("read_deferred", C.c_uint32), ("read_too_small", C.c_uint32)]
@@ -144,6 +149,7 @@ def lib():
         _LIB.tracyhip_version.restype = C.c_char_p
         _LIB.tracyhip_group_context.restype = C.c_void_p
         _LIB.tracyhip_render_bound.restype = C.c_uint64
+        _LIB.tracyhip_render_alignments_bound.restype = C.c_uint64
     return _LIB
 
 
@@ -270,6 +276,9 @@ class Context:
         ds = ReadStats()  # (and tracyhip_read_traces: tracyhip_last_read_stats)
         _check(lib().tracyhip_last_read_stats(self._h, C.byref(ds)))
         out.update({name: int(getattr(ds, name)) for name, _ in ReadStats._fields_})
+        ts = AlnTextStats()  # (and tracyhip_render_alignments: tracyhip_last_alntext_stats)
+        _check(lib().tracyhip_last_alntext_stats(self._h, C.byref(ts)))
+        out.update({name: int(getattr(ts, name)) for name, _ in AlnTextStats._fields_})
         return out
 
     # ---- host-buffer convenience wrappers (lists in, numpy out) -----------------------------------
@@ -2068,3 +2077,239 @@ def _render_traces(self, form, signals=None, bc=None, trim_left=None, trim_right
 
 
 Context.render_traces = _render_traces
+
+
+# ---- the text printed from alignment rows on the device (tracyhip_render_alignments) and the oriented reference slices in front of the
+# rows (tracyhip_reference_slices) -------------------------------------------------------------------------------------------------------
+ALNTEXT_PLOT, ALNTEXT_FASTA, ALNTEXT_JSON = 0, 1, 2
+ALNTEXT_OK, ALNTEXT_DEFERRED, ALNTEXT_TOO_SMALL = 0, 1, 2
+
+
+class AlnTextJob(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("form", C.c_uint32), ("key", C.c_uint32), ("linelimit", C.c_uint32), ("rows0", C.c_void_p), ("rows1", C.c_void_p),
+                ("rows_offset", C.POINTER(C.c_uint64)), ("cols", C.POINTER(C.c_uint32)), ("names", C.c_void_p),
+                ("name0_offset", C.POINTER(C.c_uint64)), ("name0_len", C.POINTER(C.c_uint32)), ("name1_offset", C.POINTER(C.c_uint64)),
+                ("name1_len", C.POINTER(C.c_uint32)), ("ref_pos", C.POINTER(C.c_int32)), ("ref_len", C.POINTER(C.c_uint32)),
+                ("forward", C.POINTER(C.c_uint8)), ("score", C.POINTER(C.c_int32))]
+
+
+class SlicesJob(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("refs", SeqSet), ("ref_index", C.POINTER(C.c_uint32)), ("forward", C.POINTER(C.c_uint8)),
+                ("slice_begin", C.POINTER(C.c_uint32)), ("slice_len", C.POINTER(C.c_uint32))]
+
+
+def alntext_bound(form, linelimit, cols, name0_len, name1_len):
+    """tracyhip_render_alignments_bound: an upper bound of text_len for an alignment of these sizes; needs no device"""
+    return int(lib().tracyhip_render_alignments_bound(C.c_uint32(form), C.c_uint32(linelimit), C.c_uint32(cols), C.c_uint32(name0_len),
+                                                      C.c_uint32(name1_len)))
+
+
+class PreparedAlnText:
+    """job / result structs of tracyhip_render_alignments.  form: ALNTEXT_PLOT / ALNTEXT_FASTA / ALNTEXT_JSON.  The rows come from
+      rows0, rows1   lists of bytes, one pair per alignment (device=True uploads them once), or
+      device_rows    (rows0, rows1, rows_offset, cols): two torch tensors on the GPU as tracyhip_alignment_rows / tracyhip_align_traces
+                     left them and their two host arrays; taken as they stand (no payload is copied to the host)
+    name0 / name1: lists of bytes, the caller's text (hostlib.alntext_pack says which per form).  ref_pos, ref_len, forward, score: per
+    alignment.  Everything the structs point to is kept alive by this object.
+
+    The result side starts as the sizes-only form; with_capacity() allocates the text."""
+
+    def __init__(self, form, rows0=None, rows1=None, name0=None, name1=None, ref_pos=None, ref_len=None, forward=None, score=None, key=0,
+                 linelimit=60, device=False, device_rows=None):
+        from . import hostlib
+        self.form, self.key, self.linelimit = int(form), int(key), int(linelimit)
+        self.device = device = bool(device or device_rows is not None)
+        if device_rows is not None:
+            d0, d1, roff, cols = device_rows
+            nt = len(name1)
+            f = self.flat = hostlib.alntext_pack([b""] * nt, [b""] * nt, name0 if name0 is not None else [b""] * nt, name1, ref_pos, ref_len,
+                                                 forward, score)
+            del f["rows0"], f["rows1"]  # (host copies: fetched when a deferred alignment needs them)
+            f["rows_off"] = np.append(np.ascontiguousarray(roff, dtype=np.uint64)[:nt], np.uint64(0))
+            f["cols"] = np.append(np.ascontiguousarray(cols, dtype=np.uint32)[:nt], np.uint32(0))
+            self.d = dict(rows0=d0, rows1=d1)
+        else:
+            nt = len(rows0)
+            f = self.flat = hostlib.alntext_pack(rows0, rows1, name0 if name0 is not None else [b""] * nt, name1, ref_pos, ref_len, forward, score)
+            self.d = {}
+        self.nt = nt
+        if device:
+            import torch
+            for k in ("rows0", "rows1", "names"):
+                if k not in self.d:
+                    self.d[k] = torch.from_numpy(f[k]).cuda()
+            torch.cuda.synchronize()
+        ptr = (lambda k: self.d[k].data_ptr()) if device else (lambda k: f[k].ctypes.data)
+        job = self.job = AlnTextJob()
+        job.n, job.form, job.key, job.linelimit = nt, self.form, self.key, self.linelimit
+        job.rows0, job.rows1, job.names = ptr("rows0"), ptr("rows1"), ptr("names")
+        job.rows_offset, job.cols = _u64p(f["rows_off"]), _u32p(f["cols"])
+        job.name0_offset, job.name0_len = _u64p(f["name0_off"]), _u32p(f["name0_len"])
+        job.name1_offset, job.name1_len = _u64p(f["name1_off"]), _u32p(f["name1_len"])
+        job.ref_pos = f["ref_pos"].ctypes.data_as(C.POINTER(C.c_int32))
+        job.ref_len = _u32p(f["ref_len"])
+        job.forward = f["forward"].ctypes.data_as(C.POINTER(C.c_uint8))
+        job.score = f["score"].ctypes.data_as(C.POINTER(C.c_int32))
+        self.mem = MEM_DEVICE if device else MEM_HOST
+        self._bind(None)
+
+    def _bind(self, o):
+        """the result struct over the arrays of `o` (hostlib.alntext_alloc layout; None: the sizes-only form)"""
+        self.meta = dict(status=np.zeros(max(self.nt, 1), np.int32), text_len=np.zeros(max(self.nt, 1), np.uint32))
+        out = self.out = RenderResult()
+        out.status = self.meta["status"].ctypes.data_as(C.POINTER(C.c_int32))
+        out.text_len = _u32p(self.meta["text_len"])
+        self.o = o
+        if o is None:
+            return
+        out.text_offset, out.text_cap = _u64p(o["text_offset"]), _u64p(o["text_cap"])
+        out.text = o["text"].data_ptr() if self.device else o["text"].ctypes.data
+
+    def sizes(self, ctx):
+        """the sizes-only call: text_len per alignment, 0 for deferred ones"""
+        self._bind(None)
+        _check(lib().tracyhip_render_alignments(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
+        return self.meta["text_len"][:self.nt].copy()
+
+    def bounds(self):
+        """tracyhip_render_alignments_bound per alignment: capacities that need no sizes-only call"""
+        f = self.flat
+        return np.array([alntext_bound(self.form, self.linelimit, int(f["cols"][t]), int(f["name0_len"][t]), int(f["name1_len"][t]))
+                         for t in range(self.nt)], dtype=np.uint64)
+
+    def with_capacity(self, text_cap, fill=None, offsets=None):
+        """a text buffer with room for text_cap[t] bytes of alignment t (fill: a byte the buffer starts with, for tests that check what
+        a call leaves untouched; offsets: text_offset of every alignment and the buffer's size behind them, instead of back to back)"""
+        from . import hostlib
+        o = hostlib.alntext_alloc(self.nt, text_cap, fill)
+        if offsets is not None:
+            o["text_offset"] = np.ascontiguousarray(offsets, dtype=np.uint64)
+            o["text"] = np.full(max(int(o["text_offset"][self.nt]), 1), 0 if fill is None else fill, np.uint8)
+        if self.device:
+            import torch
+            o["text"] = torch.from_numpy(o["text"]).cuda()
+            torch.cuda.synchronize()
+        self._bind(o)
+        return self
+
+    def run(self, ctx, asynchronous=False):
+        fn = lib().tracyhip_render_alignments_async if asynchronous else lib().tracyhip_render_alignments
+        _check(fn(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
+        return self
+
+    def stats(self, ctx):
+        st = AlnTextStats()
+        _check(lib().tracyhip_last_alntext_stats(ctx._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in AlnTextStats._fields_}
+
+    def host_arrays(self):
+        """the result arrays on the host in the layout of hostlib.alntext_alloc (a device text is copied back)"""
+        o = dict(self.o)
+        if self.device:
+            o["text"] = o["text"].cpu().numpy()
+        o.update(self.meta)
+        return o
+
+    def host_flat(self):
+        """the inputs on the host in the layout of hostlib.alntext_batch"""
+        f = dict(self.flat)
+        for k in ("rows0", "rows1"):
+            if k not in f:
+                f[k] = self.d[k].cpu().numpy()
+        return f
+
+    def results(self, fill_deferred=True):
+        """per alignment: dict(status, text_len, text).  Deferred alignments are printed by the host writers (hostlib.alntext_batch)."""
+        from . import hostlib
+        o = self.host_arrays()
+        res = [hostlib.alntext_unpack(o, t) for t in range(self.nt)]
+        sel = np.array([t for t in range(self.nt) if res[t]["status"] == ALNTEXT_DEFERRED], dtype=np.int64)
+        if fill_deferred and len(sel):
+            f = self.host_flat()
+            sub = dict(f, nt=len(sel))
+            for k in ("rows_off", "cols", "name0_off", "name0_len", "name1_off", "name1_len", "ref_pos", "ref_len", "forward", "score"):
+                sub[k] = np.append(f[k][sel], f[k].dtype.type(0))
+            for t, r in zip(sel, hostlib.alntext_batch(sub, self.form, self.key, self.linelimit)):
+                res[t] = dict(r, deferred=True) if r["status"] == 0 else res[t]
+        return res
+
+
+def _render_alignments(self, form, rows0=None, rows1=None, name0=None, name1=None, ref_pos=None, ref_len=None, forward=None, score=None, key=0,
+                       linelimit=60, device=False, device_rows=None, asynchronous=False):
+    """tracyhip_render_alignments: the sizes-only call, a buffer of exactly those sizes, the call.  Host rows with device=False: returns
+    the per-alignment results (PreparedAlnText.results: deferred alignments are filled in by the host batch).  device=True or
+    device_rows: returns the PreparedAlnText holding the text as a torch tensor on the GPU.  asynchronous: the second call is queued
+    (tracyhip_render_alignments_async); results are final after Context.synchronize()."""
+    p = PreparedAlnText(form, rows0, rows1, name0, name1, ref_pos, ref_len, forward, score, key, linelimit, device, device_rows)
+    p.with_capacity(p.sizes(self)).run(self, asynchronous)
+    return p if (p.device or asynchronous) else p.results()
+
+
+Context.render_alignments = _render_alignments
+
+
+class PreparedSlices:
+    """job of tracyhip_reference_slices: refs a list of bytes or a PackedSeqs of kind CHAR (device_refs: a torch tensor that holds its
+    data on the GPU already); forward, slice_begin, slice_len the arrays tracyhip_align_traces returned.  The slices lie back to back in
+    `out` (a numpy array, or a torch tensor with device=True) at out_offset."""
+
+    def __init__(self, refs, forward, slice_begin, slice_len, ref_index=None, device=False, device_refs=None):
+        pr = self.refs = refs if isinstance(refs, PackedSeqs) else PackedSeqs(refs, SEQ_CHAR)
+        self.device = device = bool(device or device_refs is not None)
+        nt = self.nt = len(forward)
+        self.forward = np.append(np.ascontiguousarray(forward, dtype=np.uint8)[:nt], np.uint8(0))
+        self.begin = np.append(np.ascontiguousarray(slice_begin, dtype=np.uint32)[:nt], np.uint32(0))
+        self.len = np.append(np.ascontiguousarray(slice_len, dtype=np.uint32)[:nt], np.uint32(0))
+        self.out_offset = np.zeros(nt + 1, np.uint64)
+        self.out_offset[1:] = np.cumsum(self.len[:nt].astype(np.uint64))
+        job = self.job = SlicesJob()
+        job.n = nt
+        if device:
+            import torch
+            self.d_refs = device_refs if device_refs is not None else torch.from_numpy(pr.data).cuda()
+            self.out = torch.zeros(max(int(self.out_offset[nt]), 1), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            job.refs = pr.seqset(self.d_refs.data_ptr())
+        else:
+            self.out = np.zeros(max(int(self.out_offset[nt]), 1), np.uint8)
+            job.refs = pr.seqset()
+        if ref_index is not None:
+            self.ref_index = np.ascontiguousarray(ref_index, dtype=np.uint32)
+            job.ref_index = _u32p(self.ref_index)
+        job.forward = self.forward.ctypes.data_as(C.POINTER(C.c_uint8))
+        job.slice_begin, job.slice_len = _u32p(self.begin), _u32p(self.len)
+        self.mem = MEM_DEVICE if device else MEM_HOST
+
+    def out_ptr(self):
+        return self.out.data_ptr() if self.device else self.out.ctypes.data
+
+    def validate(self):
+        return lib().tracyhip_reference_slices_validate(C.byref(self.job), self.mem, C.c_void_p(self.out_ptr()), _u64p(self.out_offset))
+
+    def run(self, ctx, asynchronous=False):
+        fn = lib().tracyhip_reference_slices_async if asynchronous else lib().tracyhip_reference_slices
+        _check(fn(ctx._h, C.byref(self.job), self.mem, C.c_void_p(self.out_ptr()), _u64p(self.out_offset)))
+        return self
+
+    def slices(self):
+        """the slices as bytes (a device result is copied back)"""
+        o = self.out.cpu().numpy() if self.device else self.out
+        return [o[int(self.out_offset[t]):int(self.out_offset[t]) + int(self.len[t])].tobytes() for t in range(self.nt)]
+
+    def seqset(self):
+        """the slices as the CHAR seqset tracyhip_alignment_rows takes them by (kept alive by this object)"""
+        s = SeqSet()
+        s.kind, s.data, s.count = SEQ_CHAR, self.out_ptr(), self.nt
+        s.offset, s.length = _u64p(self.out_offset), _u32p(self.len)
+        return s
+
+
+def _reference_slices(self, refs, forward, slice_begin, slice_len, ref_index=None, device=False, device_refs=None, asynchronous=False):
+    """tracyhip_reference_slices.  Host references with device=False: returns the slices as a list of bytes.  device=True or
+    device_refs: returns the PreparedSlices holding them as a torch tensor on the GPU (PreparedSlices.seqset() hands them to
+    tracyhip_alignment_rows).  asynchronous: queued; final after Context.synchronize()."""
+    p = PreparedSlices(refs, forward, slice_begin, slice_len, ref_index, device, device_refs).run(self, asynchronous)
+    return p if (p.device or asynchronous) else p.slices()
+
+
+Context.reference_slices = _reference_slices

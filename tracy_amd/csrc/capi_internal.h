@@ -204,7 +204,14 @@ enum CtxDev : int {
   DB_READ_FILES,     // ReadFile per file up, ReadDesc per file written by read_scan_kernel and brought back
   DB_READ_IN,        // a host caller's file images of a chunk, staged in
   DB_READ_OUT,       // chromatograms and call arrays of a chunk staged for a host caller
-  DB_COUNT = DB_READ_OUT + 1
+  // ---- tracyhip_render_alignments, tracyhip_reference_slices (alntext.hip) ----
+  DB_ALNTEXT_DESC,   // AlnDesc per alignment up, AlnOut per alignment back; SliceDesc per slice up
+  DB_ALNTEXT_TILES,  // bytes (then offset) and the two letter counts of every tile of a chunk: written by alntext_count_kernel, scanned in
+                     // place by alntext_scan_kernel, read by alntext_emit_kernel; behind them the letters of every column tile
+                     // (alntext_letters_kernel)
+  DB_ALNTEXT_IN,     // a host caller's rows and names of a chunk, staged in; a host caller's references (slices)
+  DB_ALNTEXT_OUT,    // the text of a chunk staged for a host caller; the slices staged for a host caller
+  DB_COUNT = DB_ALNTEXT_OUT + 1
 };
 static_assert(DN_CNT + 1 == VB_DESC && VB_PACK_TEXT + 1 == WB_ORIENTED && DN_PAY < DB_COUNT && WB_PAY < DB_COUNT,
               "an alias does not advance the count: every slot of its own comes after the aliases");
@@ -353,6 +360,7 @@ struct tracyhip_ctx {
   tracyhip_pad_stats pad_stats = {};  // of the last tracyhip_pad_traces call (tracyhip_last_pad_stats)
   tracyhip_render_stats render_stats = {};  // of the last tracyhip_render_traces call (tracyhip_last_render_stats)
   tracyhip_read_stats read_stats = {};  // of the last tracyhip_read_traces call (tracyhip_last_read_stats)
+  tracyhip_alntext_stats alntext_stats = {};  // of the last tracyhip_render_alignments call (tracyhip_last_alntext_stats)
   std::vector<Pending> pending;
   std::vector<hipEvent_t> free_events;
   tracyhip_kernel_timing acc[TRACYHIP_TIMER_COUNT] = {};

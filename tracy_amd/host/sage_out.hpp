@@ -183,12 +183,15 @@ inline void trimTrace(float trimStringency, BaseCalls const& bc, uint32_t& leftT
 
 // plotAlignment, fmindex.h:329-427.  key 0: ">Alt" vs ">Ref"; 1 / 2: allele 1 / 2 vs reference with the
 // allelic fraction in the header; 3: allele 1 vs allele 2.
-template <class Out, typename std::enable_if<!std::is_same<Out, std::string>::value, int>::type = 0>  // (a stream, not a file name)
-inline void plotAlignment(Out& out, AlignRows const& al, ReferenceSlice const& rs, int32_t key, int32_t score,
-                          std::pair<double, double> const& a1a2, uint32_t linelimit) {
+// plotAlignmentLines is the writer with its two header lines handed in: head0(out) / head1(out, ri, riend, mirrored) print the line in
+// front of each ungapped row, newline included (tracyhost_alntext_batch prints a caller's lines there).  pos, reflen and forward are
+// rs.pos, rs.refslice.size() and rs.forward: all the writer reads of the slice beyond its headers.
+template <class Out, class Head0, class Head1>
+inline void plotAlignmentLines(Out& out, AlignRows const& al, uint32_t pos, std::size_t reflen, bool forward, int32_t key, int32_t score, uint32_t linelimit, Head0&& head0,
+                               Head1&& head1) {
   const int64_t cols = (int64_t)al.cols();
-  int32_t ri = rs.pos + 1;
-  const int32_t riend = rs.pos + rs.refslice.size();
+  int32_t ri = pos + 1;
+  const int32_t riend = pos + reflen;
   int32_t vi = 1;
   const uint32_t fald = linelimit + 14;
   auto ungapped = [&](std::string const& row) {
@@ -207,15 +210,11 @@ inline void plotAlignment(Out& out, AlignRows const& al, ReferenceSlice const& r
     out << std::endl;
   };
   // position of reference base `r` (1-based, forward numbering) when the slice is the reverse complement
-  auto mirrored = [&](int32_t r) { return rs.pos + rs.refslice.size() - (r - rs.pos) + 1; };
+  auto mirrored = [&](int32_t r) { return pos + reflen - (r - pos) + 1; };
 
-  if (key == 0) out << ">Alt" << std::endl;
-  else if (key == 2) out << ">Alt2 (Estimated allelic Fraction: " << a1a2.second << ")" << std::endl;
-  else out << ">Alt1 (Estimated allelic Fraction: " << a1a2.first << ")" << std::endl;
+  head0(out);
   ungapped(al.row0);
-  if (key == 3) out << ">Alt2 (Estimated allelic Fraction: " << a1a2.second << ")" << std::endl;
-  else if (rs.forward) out << ">Ref " << rs.chr << ":" << ri << "-" << riend << " forward" << std::endl;
-  else out << ">Ref " << rs.chr << ":" << mirrored(riend) << "-" << mirrored(ri) << " reversecomplement" << std::endl;
+  head1(out, ri, riend, mirrored);
   ungapped(al.row1);
   out << std::endl;
   out << "Alignment score: " << score << std::endl;
@@ -236,7 +235,7 @@ inline void plotAlignment(Out& out, AlignRows const& al, ReferenceSlice const& r
     for (int64_t j = s; j < e; ++j) out << (al.row0[j] == al.row1[j] ? "|" : " ");
     out << std::endl;
     if (key == 3) out << "Alt2" << std::setw(9) << ri << ' ';
-    else if (rs.forward) out << "Ref" << std::setw(10) << ri << ' ';
+    else if (forward) out << "Ref" << std::setw(10) << ri << ' ';
     else out << "Ref" << std::setw(10) << mirrored(ri) << ' ';
     for (int64_t j = s; j < e; ++j) {
       out << al.row1[j];
@@ -251,6 +250,23 @@ inline void plotAlignment(Out& out, AlignRows const& al, ReferenceSlice const& r
   rule();
   out << std::endl;
   out << std::endl;
+}
+
+template <class Out, typename std::enable_if<!std::is_same<Out, std::string>::value, int>::type = 0>  // (a stream, not a file name)
+inline void plotAlignment(Out& out, AlignRows const& al, ReferenceSlice const& rs, int32_t key, int32_t score,
+                          std::pair<double, double> const& a1a2, uint32_t linelimit) {
+  plotAlignmentLines(
+      out, al, rs.pos, rs.refslice.size(), rs.forward, key, score, linelimit,
+      [&](Out& o) {
+        if (key == 0) o << ">Alt" << std::endl;
+        else if (key == 2) o << ">Alt2 (Estimated allelic Fraction: " << a1a2.second << ")" << std::endl;
+        else o << ">Alt1 (Estimated allelic Fraction: " << a1a2.first << ")" << std::endl;
+      },
+      [&](Out& o, int32_t ri, int32_t riend, auto&& mirrored) {
+        if (key == 3) o << ">Alt2 (Estimated allelic Fraction: " << a1a2.second << ")" << std::endl;
+        else if (rs.forward) o << ">Ref " << rs.chr << ":" << ri << "-" << riend << " forward" << std::endl;
+        else o << ">Ref " << rs.chr << ":" << mirrored(riend) << "-" << mirrored(ri) << " reversecomplement" << std::endl;
+      });
 }
 
 inline void plotAlignment(std::string const& filename, AlignRows const& al, ReferenceSlice const& rs, int32_t score, uint32_t linelimit) {
@@ -380,12 +396,9 @@ inline void assemblyTrace(Out& out, PaddedTrace const& p, std::string const& tra
   out << "}" << std::endl;
 }
 
-// traceAlignJsonOut, json.h:197-217
-template <class Out, typename std::enable_if<!std::is_same<Out, std::string>::value, int>::type = 0>  // (a stream, not a file name)
-inline void traceAlignJsonOut(Out& out, PaddedTrace const& p, ReferenceSlice const& rs, AlignRows const& al) {
-  out << "{" << std::endl;
-  out << "\"gappedTrace\":" << std::endl;
-  assemblyTrace(out, p, "trace");
+// traceAlignJsonOut, json.h:197-217; traceAlignJsonTail is what it prints behind the gapped trace
+template <class Out>
+inline void traceAlignJsonTail(Out& out, ReferenceSlice const& rs, AlignRows const& al) {
   out << "," << std::endl;
   out << "\"refchr\": \"" << rs.chr << "\"," << std::endl;
   out << "\"refpos\": " << (rs.pos + 1) << "," << std::endl;
@@ -393,6 +406,14 @@ inline void traceAlignJsonOut(Out& out, PaddedTrace const& p, ReferenceSlice con
   out << "\"refalign\": \"" << al.row1 << "\"," << std::endl;
   out << "\"forward\": " << rs.forward << std::endl;
   out << "}" << std::endl;
+}
+
+template <class Out, typename std::enable_if<!std::is_same<Out, std::string>::value, int>::type = 0>  // (a stream, not a file name)
+inline void traceAlignJsonOut(Out& out, PaddedTrace const& p, ReferenceSlice const& rs, AlignRows const& al) {
+  out << "{" << std::endl;
+  out << "\"gappedTrace\":" << std::endl;
+  assemblyTrace(out, p, "trace");
+  traceAlignJsonTail(out, rs, al);
 }
 
 inline void traceAlignJsonOut(std::string const& outfile, PaddedTrace const& p, ReferenceSlice const& rs, AlignRows const& al) {

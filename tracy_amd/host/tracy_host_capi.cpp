@@ -900,6 +900,60 @@ int tracyhost_render_batch(uint32_t n, uint32_t form, const void* signal, const 
   return 0;
 }
 
+// ---- the text printed from the two gapped rows of an alignment, one alignment after the other per thread: plotAlignmentLines,
+// alignFastaOut and the tail of traceAlignJsonOut (sage_out.hpp) into a TextBuf over the flattened arrays of tracyhip_render_alignments
+// (the fallback for its deferred alignments; tools/alntext_device_line.py times it beside the device call) ----
+// form: 0 the plot (name0 / name1 are its two header lines), 1 the FASTA (name0 the trace stem, name1 rs.chr), 2 the JSON from
+// ",\n\"refchr\"" through "}\n" (name1 rs.chr; name0 is not read).  Every alignment is printed, also those the device defers: ref_pos is
+// rs.pos (taken as the uint32 it is there), ref_len rs.refslice.size().  status: 0 answered; 1 the text does not fit 32 bits; 2 text_cap
+// is too small (text_len reported).  text may be null (sizes only).
+int tracyhost_alntext_batch(uint32_t n, uint32_t form, uint32_t key, uint32_t linelimit, const uint8_t* rows0, const uint8_t* rows1,
+                            const uint64_t* rows_offset, const uint32_t* cols, const uint8_t* names, const uint64_t* name0_offset,
+                            const uint32_t* name0_len, const uint64_t* name1_offset, const uint32_t* name1_len, const int32_t* ref_pos,
+                            const uint32_t* ref_len, const uint8_t* forward, const int32_t* score, int32_t* status, uint32_t* text_len, uint8_t* text,
+                            const uint64_t* text_offset, const uint64_t* text_cap, uint32_t nthreads) {
+  if (form > 2 || (form == 0 && (key > 3 || linelimit < 1 || linelimit > 65535u)) || (text && (!text_offset || !text_cap))) return -1;
+  if (n && (!rows0 || !rows1 || !rows_offset || !cols || !names || !name1_offset || !name1_len || !ref_pos || !ref_len || !forward || !status || !text_len))
+    return -1;
+  if (n && ((form != 2 && (!name0_offset || !name0_len)) || (form == 0 && !score))) return -1;
+  if (nthreads == 0) nthreads = tracy_amd::usable_threads();
+  std::vector<std::thread> th;
+  for (uint32_t w = 0; w < nthreads; ++w)
+    th.emplace_back([=]() {
+      AlignRows al;
+      ReferenceSlice rs;
+      for (uint32_t t = (uint32_t)((uint64_t)n * w / nthreads); t < (uint32_t)((uint64_t)n * (w + 1) / nthreads); ++t) {
+        status[t] = 1;
+        text_len[t] = 0;
+        al.row0.assign(reinterpret_cast<const char*>(rows0) + rows_offset[t], cols[t]);
+        al.row1.assign(reinterpret_cast<const char*>(rows1) + rows_offset[t], cols[t]);
+        const std::string name1(reinterpret_cast<const char*>(names) + name1_offset[t], name1_len[t]);
+        std::string name0;
+        if (form != 2) name0.assign(reinterpret_cast<const char*>(names) + name0_offset[t], name0_len[t]);
+        rs.forward = forward[t] != 0;
+        rs.pos = (uint32_t)ref_pos[t];
+        rs.chr = name1;
+        TextBuf out((std::size_t)8 * cols[t] + 4096);
+        if (form == 0) {
+          plotAlignmentLines(out, al, rs.pos, (std::size_t)ref_len[t], rs.forward, (int32_t)key, score[t], linelimit,
+                             [&](TextBuf& o) { o << name0 << std::endl; },
+                             [&](TextBuf& o, int32_t, int32_t, auto&&) { o << name1 << std::endl; });
+        } else if (form == 1) {
+          alignFastaOut(out, name0, rs, al);
+        } else {
+          traceAlignJsonTail(out, rs, al);
+        }
+        if (out.size() > 0xffffffffull) continue;
+        text_len[t] = (uint32_t)out.size();
+        if (text && out.size() > text_cap[t]) { status[t] = 2; continue; }
+        status[t] = 0;
+        if (text) std::memcpy(text + text_offset[t], out.data(), out.size());
+      }
+    });
+  for (auto& t : th) t.join();
+  return 0;
+}
+
 // ---- the readers over a batch of file images, one file after the other per thread: traceFormat, readab / readscf (trace_io.hpp) into the
 // flattened arrays of tracyhip_read_traces (the fallback for its deferred traces; tools and the command line time it beside the device
 // call) ----

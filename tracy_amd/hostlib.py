@@ -664,6 +664,59 @@ def render_batch(flat, form, nthreads=0):
     return [render_unpack(out, t) for t in range(flat["nt"])]
 
 
+# ---- the text printed from alignment rows on the host (tracyhost_alntext_batch): the fallback and the baseline of
+# tracyhip_render_alignments ---------------------------------------------------------------------------------------------------------------
+ALNTEXT_PLOT, ALNTEXT_FASTA, ALNTEXT_JSON = 0, 1, 2
+alntext_alloc = render_alloc  # (the result arrays of a printing call: status, text_len, text, text_offset, text_cap)
+alntext_unpack = render_unpack
+
+
+def alntext_pack(rows0, rows1, name0, name1, ref_pos, ref_len, forward, score=None):
+    """per-alignment rows (bytes), names (bytes) and numbers as the flattened arrays of a PreparedAlnText (capi.py): rows back to back,
+    the names of an alignment behind each other in one array"""
+    nt = len(rows0)
+    z = lambda dt: np.zeros(nt + 1, dt)
+    f = dict(nt=nt, cols=z(np.uint32), rows_off=z(np.uint64), name0_off=z(np.uint64), name0_len=z(np.uint32), name1_off=z(np.uint64),
+             name1_len=z(np.uint32))
+    if any(len(a) != len(b) for a, b in zip(rows0, rows1)):
+        raise ValueError("the two rows of an alignment have one length")
+    f["cols"][:nt] = [len(r) for r in rows0]
+    f["rows_off"][1:] = np.cumsum(f["cols"][:nt].astype(np.uint64))
+    f["rows0"] = np.frombuffer(b"".join(bytes(r) for r in rows0) + b"\0", np.uint8).copy()
+    f["rows1"] = np.frombuffer(b"".join(bytes(r) for r in rows1) + b"\0", np.uint8).copy()
+    f["name0_len"][:nt] = [len(x) for x in name0]
+    f["name1_len"][:nt] = [len(x) for x in name1]
+    both = f["name0_len"][:nt].astype(np.uint64) + f["name1_len"][:nt].astype(np.uint64)
+    f["name0_off"][1:] = np.cumsum(both)
+    f["name1_off"][:nt] = f["name0_off"][:nt] + f["name0_len"][:nt]
+    f["names"] = np.frombuffer(b"".join(bytes(a) + bytes(b) for a, b in zip(name0, name1)) + b"\0", np.uint8).copy()
+    f["ref_pos"] = np.append(np.asarray(ref_pos, dtype=np.int64).astype(np.int32)[:nt], np.int32(0))
+    f["ref_len"] = np.append(np.asarray(ref_len, dtype=np.uint32)[:nt], np.uint32(0))
+    f["forward"] = np.append(np.asarray(forward, dtype=np.uint8)[:nt], np.uint8(0))
+    f["score"] = np.append(np.asarray(score if score is not None else np.zeros(nt), dtype=np.int64).astype(np.int32)[:nt], np.int32(0))
+    return f
+
+
+def alntext_batch_raw(flat, form, out, key=0, linelimit=60, nthreads=0, sizes_only=False):
+    """one tracyhost_alntext_batch call over the flattened arrays of a PreparedAlnText (capi.py) into `out` (alntext_alloc)"""
+    p = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+    rc = lib().tracyhost_alntext_batch(C.c_uint32(flat["nt"]), C.c_uint32(form), C.c_uint32(key), C.c_uint32(linelimit), p(flat["rows0"]),
+                                       p(flat["rows1"]), p(flat["rows_off"]), p(flat["cols"]), p(flat["names"]), p(flat["name0_off"]),
+                                       p(flat["name0_len"]), p(flat["name1_off"]), p(flat["name1_len"]), p(flat["ref_pos"]), p(flat["ref_len"]),
+                                       p(flat["forward"]), p(flat["score"]), p(out["status"]), p(out["text_len"]),
+                                       None if sizes_only else p(out["text"]), p(out["text_offset"]), p(out["text_cap"]), C.c_uint32(nthreads))
+    if rc != 0:
+        raise ValueError("tracyhost_alntext_batch: bad arguments")
+    return out
+
+
+def alntext_batch(flat, form, key=0, linelimit=60, nthreads=0):
+    """print a batch of alignments on host threads: a sizes-only call, a buffer of exactly those sizes, the call; per-alignment dicts"""
+    sizes = alntext_batch_raw(flat, form, alntext_alloc(flat["nt"], np.zeros(flat["nt"], np.uint64)), key, linelimit, nthreads, sizes_only=True)
+    out = alntext_batch_raw(flat, form, alntext_alloc(flat["nt"], sizes["text_len"]), key, linelimit, nthreads)
+    return [alntext_unpack(out, t) for t in range(flat["nt"])]
+
+
 # ---- the readers over a batch of file images on the host (tracyhost_read_batch): the fallback and the baseline of tracyhip_read_traces ---
 READ_KINDS = (("signal", None), ("basecallpos", np.int32), ("basecalls1", np.uint8), ("basecalls2", np.uint8), ("qual", np.uint8))
 
