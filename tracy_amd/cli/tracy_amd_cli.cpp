@@ -44,6 +44,7 @@
 #include "../host/indigo_out.hpp"
 #include "../host/sage_out.hpp"
 #include "../host/seed.hpp"
+#include "align_resident_plan.h"
 
 using namespace tracy_amd;
 
@@ -58,6 +59,7 @@ struct SageConfig {  // sage.h:37-56 + the extra fields of IndigoConfig (indigo.
   int device = 0;
   std::string devices = "0";  // -d: one ordinal, a comma-separated list, or "all" (batches are cut into blocks, one per GPU)
   uint32_t threads = 0;        // --threads: host threads of the --batch stages (read, basecall, profile, writers); 0 = every core this process may use
+  bool resident = false;       // --resident (align --batch): files in, text out, every stage between on the device (align_resident.inc)
 };
 
 struct Job {
@@ -290,6 +292,9 @@ void usage_options(bool decompose) {
                "  --threads arg (=0)               host threads of the --batch stages (0 = all usable cores)\n"
                "  -d [ --device ] arg (=0)         GPU ordinal, a list (0,1,2,3) or all: --batch manifests are cut into\n"
                "                                   contiguous blocks of traces, one per GPU\n";
+  if (!decompose)
+    std::cout << "  --resident                       with --batch: trace files to output files on the device (read, basecall,\n"
+                 "                                   align, print; the first GPU of -d); what it cannot answer takes the host path\n";
   if (decompose)
     std::cout << "  -i [ --maxindel ] arg (=1000)    max. indel size in Sanger trace\n"
                  "  -v [ --callVariants ]            call variants in trace\n";
@@ -313,7 +318,7 @@ void usage(const char* cmd) {
 }
 
 // returns 0 ok, 1 show usage
-int parse(int argc, char** argv, SageConfig& c) {
+int parse(int argc, char** argv, SageConfig& c, bool decompose = false) {
   static const std::map<std::string, char> longs = {
       {"help", '?'}, {"reference", 'r'}, {"pratio", 'p'}, {"batch", 'b'}, {"device", 'd'}, {"threads", 'T'}, {"gapopen", 'g'}, {"gapext", 'e'},
       {"match", 'm'}, {"mismatch", 'n'}, {"trim", 't'}, {"trimLeft", 'q'}, {"trimRight", 'u'}, {"linelimit", 'l'}, {"outprefix", 'o'},
@@ -328,6 +333,7 @@ int parse(int argc, char** argv, SageConfig& c) {
       std::string name = a.substr(2);
       const std::size_t eq = name.find('=');
       if (eq != std::string::npos) { val = name.substr(eq + 1); name = name.substr(0, eq); has_val = true; }
+      if (name == "resident" && !has_val && !decompose) { c.resident = true; continue; }  // (no short form, no value)
       auto it = longs.find(name);
       if (it == longs.end()) { std::cerr << "unrecognised option '" << a << "'" << std::endl; return 1; }
       opt = it->second;
@@ -746,6 +752,8 @@ void echo_command(int argc, char** argv) {
   std::cout << std::endl;
 }
 
+int align_resident_main(SageConfig const& c, std::vector<Job>& jobs, int argc, char** argv);  // align_resident.inc
+
 int align_main(int argc, char** argv) {
   SageConfig c;
   if (parse(argc, argv, c)) {
@@ -755,6 +763,10 @@ int align_main(int argc, char** argv) {
   if (c.trimStringency > 9) c.trimStringency = 9;
   std::vector<Job> jobs;
   const bool batch = !c.batch.empty();
+  if (c.resident && !batch) {  // (before a file or a device is touched)
+    std::cerr << "--resident needs --batch" << std::endl;
+    return -1;
+  }
   if (int rc = collect_jobs(c, jobs)) return rc;
   for (Job const& j : jobs) {
     if (!regular_nonempty(j.ref_path)) {
@@ -766,6 +778,7 @@ int align_main(int argc, char** argv) {
       return 1;
     }
   }
+  if (c.resident) return align_resident_main(c, jobs, argc, argv);
   echo_command(argc, argv);
 
   std::cout << stamp() << "Load ab1 file" << std::endl;
@@ -1233,7 +1246,7 @@ void write_decompose_outputs(SageConfig const& c, Job& j) {
 
 int decompose_main(int argc, char** argv) {
   SageConfig c;
-  if (parse(argc, argv, c)) {
+  if (parse(argc, argv, c, true)) {
     std::cout << "Usage: tracy " << argv[0] << " [OPTIONS] trace.ab1" << std::endl;
     usage_options(true);
     return -1;
@@ -1814,6 +1827,7 @@ int index_main(int argc, char** argv) {
   return 0;
 }
 
+#include "align_resident.inc"
 #include "assemble_cli.inc"
 #include "consensus_cli.inc"
 

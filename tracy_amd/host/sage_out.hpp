@@ -82,8 +82,9 @@ inline int32_t genomeType(std::string const& path) {
 }
 
 // loadSingleFasta, fasta.h:54-95: one record, upper-cased, IUPAC codes -> N, anything else is an error;
-// the record name loses the characters VCF dislikes (fasta.h:16-35)
-inline bool loadSingleFasta(std::string const& filename, std::string& faname, std::string& seq) {
+// the record name loses the characters VCF dislikes (fasta.h:16-35).  quiet: the two messages are left to a later call on the same
+// file (the resident chain of `align --batch`, whose refused lines take the host path and are reported there)
+inline bool loadSingleFasta(std::string const& filename, std::string& faname, std::string& seq, bool quiet = false) {
   faname.clear();
   // what a letter of the record becomes: itself (A C G T N, either case), 'N' (the other IUPAC codes), 0 = not a nucleotide code
   static const struct Letters {
@@ -108,7 +109,7 @@ inline bool loadSingleFasta(std::string const& filename, std::string& faname, st
         const std::size_t len = (std::size_t)(le - p) - (le[-1] == '\r' ? 1 : 0);
         if (*p == '>') {
           if (!faname.empty()) {
-            std::cerr << "Only single-chromosome FASTA files are supported." << std::endl;
+            if (!quiet) std::cerr << "Only single-chromosome FASTA files are supported." << std::endl;
             return false;
           }
           faname.assign(p + 1, len ? len - 1 : 0);
@@ -124,7 +125,7 @@ inline bool loadSingleFasta(std::string const& filename, std::string& faname, st
     }
   }
   if (foreign) {
-    std::cerr << "FASTA file contains non-IUPAC characters." << std::endl;
+    if (!quiet) std::cerr << "FASTA file contains non-IUPAC characters." << std::endl;
     return false;
   }
   seq += body;

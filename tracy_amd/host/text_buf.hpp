@@ -173,19 +173,20 @@ struct TextBuf {
   // files that could not be written in full (a missing directory, a full disk): counted for the command's exit code
   static std::atomic<int>& write_errors() { static std::atomic<int> n{0}; return n; }
   // to_file + the error message and the count: what the writers of the commands call
-  bool write(std::string const& path) const {
-    if (to_file(path)) return true;
+  bool write(std::string const& path) const { return write_bytes(path, b, size()); }
+  // the same for text that lies elsewhere (rendered on the device and copied back in one piece): no copy into a buffer of its own
+  static bool write_bytes(std::string const& path, const char* q, std::size_t n) {
+    if (bytes_to_file(path, q, n)) return true;
     ++write_errors();
     const std::string msg = "Could not write output file " + path + ": " + std::strerror(errno) + "\n";
     (void)!::write(2, msg.data(), msg.size());
     return false;
   }
   // one open / write / close (no stdio buffer in between)
-  bool to_file(std::string const& path) const {
+  bool to_file(std::string const& path) const { return bytes_to_file(path, b, size()); }
+  static bool bytes_to_file(std::string const& path, const char* q, std::size_t left) {
     const int fd = ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
     if (fd < 0) return false;
-    const char* q = b;
-    std::size_t left = size();
     bool ok = true;
     while (left) {
       const ssize_t w = ::write(fd, q, left);
