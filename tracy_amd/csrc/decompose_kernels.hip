@@ -958,7 +958,7 @@ int launch_decompose(tracyhip_ctx* ctx, const DecompArgs& a, const BreakpointOut
   const DecompArgs& a_ = rest;
   if (global) {
     // scan state in global memory: up to 512 workgroups in flight, each with a slot of its own (0.7 GB)
-    const uint32_t slots = std::min<uint32_t>(a.ntraces, 512u);
+    const uint32_t slots = std::min<uint32_t>(a.ntraces, 512u);  // (tests/test_gpu_batch_rounds.py builds its batch sizes on 512 and reads it from this line)
     HIP_TRY(ctx->dev[DB_BAND].ensure((size_t)slots * sizeof(DecompSharedT<kMaxIndelGlobal>)));
     hipLaunchKernelGGL(decompose_kernel_global, dim3(slots), dim3(64), 0, ctx->stream, a_, d_bps, static_cast<char*>(ctx->dev[DB_BAND].p));
   } else if (large) {

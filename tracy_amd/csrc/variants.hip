@@ -30,6 +30,7 @@ using namespace tracyhip;
 namespace {
 
 constexpr uint32_t kVarMaxVariants = 1024;
+// (tests/test_gpu_batch_rounds.py builds its batch sizes on 2048 and reads it from this line)
 constexpr uint32_t kVarWaves = 2048;  // resident workgroups of variants_kernel: eight per CU, each with its two event lists in VB_EVENTS
 
 struct VarDevWave : DevWaveOps<true> {  // the wave of variants_wave.h: one workgroup of 64 threads
@@ -113,6 +114,7 @@ __global__ __launch_bounds__(256) void var_revcomp_kernel(const VarRcDesc* __res
 
 // where every trace's used records / text bytes begin when they are packed back to back: off[0 .. nt] records, off[nt + 1 .. 2 nt + 1]
 // bytes (the last of each: the totals).  One workgroup; a thread sums a contiguous stretch of traces.
+// (tests/test_gpu_batch_rounds.py builds its batch sizes on the 1024 threads and reads them from the next line)
 __global__ __launch_bounds__(1024) void var_pack_scan_kernel(const uint32_t* __restrict__ var_n, const tracyhip_variant* __restrict__ var, uint32_t max_variants,
                                                              uint32_t nt, uint64_t* __restrict__ off) {
   __shared__ uint64_t srec[1024], stext[1024];
