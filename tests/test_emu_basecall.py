@@ -173,3 +173,14 @@ def test_basecall_plan_program(tmp_path, build):
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "basecall_plan: ok" in r.stdout
+
+
+@pytest.mark.parametrize("build", sorted(PLAN_FLAGS))
+def test_span_cut_program(tmp_path, build):
+    """cut_spans of ragged_plan.h, the one cut behind the five *_cut_chunks, over a toy chunk whose answers can be read off the items"""
+    exe = tmp_path / ("span_cut_" + build)
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror"] + PLAN_FLAGS[build] + ["-o", str(exe), os.path.join(ROOT, "tests", "cpp", "span_cut.cpp")],
+                   check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "span_cut: ok" in r.stdout

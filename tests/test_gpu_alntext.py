@@ -200,6 +200,34 @@ def test_host_staging_in_at_least_three_chunks(ctx):
         assert ctx.last_call_stats()["alntext_chunks"] == 1
 
 
+DEVICE_CHUNK_LIMIT = {ac.PLOT: 256, ac.FASTA: 128, ac.JSON: 128}  # bytes: five chunks of these eight alignments in every form
+
+
+def test_device_payloads_in_at_least_three_chunks(ctx):
+    """A device call stages nothing: its tile scratch alone (12 bytes a tile, 8 a column tile) cuts it.  The launches of all chunks follow
+    each other over their slices of one descriptor buffer, and the results of all of them come back behind the last launch, in the one
+    wait of the call."""
+    from tracy_amd import hostlib
+    pick = [it for it in main_set() if it[1] == 0 and it[2] == 60 and len(it[3]["row0"]) <= 1100][:8]
+    cases = [it[3] for it in pick]
+    for form in ac.FORMS:
+        p = prepared(cases, form, 0, 60, device=True)
+        ctx.set_workspace_limit(DEVICE_CHUNK_LIMIT[form])
+        try:
+            rows = run_checked(ctx, p)
+            st = ctx.last_call_stats()
+        finally:
+            ctx.set_workspace_limit(0)
+        assert 3 <= st["alntext_chunks"] < len(cases)  # (some chunks hold several alignments)
+        assert (st["alntext_deferred"], st["alntext_too_small"]) == (0, 0)  # a deferral cannot hide a failure
+        assert st["host_syncs"] == 1  # as measured on the commit before the drivers shared one chunk loop: one wait, however many chunks
+        whole = run_checked(ctx, prepared(cases, form, 0, 60, device=True))
+        assert ctx.last_call_stats()["alntext_chunks"] == 1
+        host = hostlib.alntext_batch(p.host_flat(), form, 0, 60, 4)
+        for it, got, one, h in zip(pick, rows, whole, host):
+            assert got["status"] == ac.OK and got["text"] == one["text"] == h["text"] == it[4][form], (it[0], form)
+
+
 def test_the_queued_call(ctx):
     pick = [it for it in main_set() if it[1] == 3 and it[2] == 7][:20]
     assert len(pick) >= 5

@@ -159,6 +159,31 @@ def test_host_staging_in_several_chunks(ctx, answered):
         assert np.array_equal(a["signal"], b["signal"]) and np.array_equal(a["bcPos"], b["bcPos"]) and a["primary"] == b["primary"]
 
 
+def test_device_payloads_in_several_chunks(ctx, answered):
+    """A device call stages nothing: the insert scratch of its rows alone cuts it, and only in the call with payloads.  The launches of
+    all chunks follow each other over their slices of one descriptor buffer, and the results of all of them come back behind the last
+    launch, in the one wait of the call."""
+    from tracy_amd import hostlib
+    pick = answered[20:28]  # (the crafted rows with inserts: 1 KB of scratch holds some of them in pairs, none of them all)
+    cases = [c for _, c, _ in pick]
+    ctx.set_workspace_limit(1 << 10)
+    try:
+        p, rows = run_checked(ctx, cases, device=True)
+        st = ctx.last_call_stats()
+    finally:
+        ctx.set_workspace_limit(0)
+    assert 3 <= st["pad_chunks"] < len(cases)
+    assert (st["pad_deferred"], st["pad_too_small"]) == (0, 0)  # a deferral cannot hide a failure
+    assert st["host_syncs"] == 1  # as measured on the commit before the drivers shared one chunk loop: one wait, however many chunks
+    _, whole = run_checked(ctx, cases, device=True)
+    assert ctx.last_call_stats()["pad_chunks"] == 1
+    host = hostlib.pad_batch(p.host_flat(), 4)
+    for (name, _, want), got, one, h in zip(pick, rows, whole, host):
+        pc.compare(got, want, (name, "chunks"))
+        pc.compare(one, want, (name, "whole"))
+        pc.compare(h, want, (name, "host"))
+
+
 def _synth(seed, mf):
     from tracy_amd import hostlib
     ref, sig, pos, _ = hostlib.synth_decompose(seed, mf + 400, mf, 30, seed % 4, 0.6)

@@ -162,6 +162,33 @@ def test_host_staging_in_at_least_three_chunks(ctx):
         assert ctx.last_call_stats()["render_chunks"] == 1
 
 
+DEVICE_CHUNK_LIMIT = {rc.TSV: 64, rc.JSON: 256, rc.GAPPED: 128}  # bytes: five chunks of these eight traces in every form
+
+
+def test_device_payloads_in_at_least_three_chunks(ctx):
+    """A device call stages nothing: its tile scratch alone (8 bytes a tile) cuts it.  The launches of all chunks follow each other over
+    their slices of one descriptor buffer, and the results of all of them come back behind the last launch, in the one wait of the call."""
+    from tracy_amd import hostlib
+    pick = main_set(False)[:8]
+    cases = [c for _, c, _ in pick]
+    for form in rc.FORMS:
+        p = prepared(cases, form, device=True)
+        ctx.set_workspace_limit(DEVICE_CHUNK_LIMIT[form])
+        try:
+            rows = run_checked(ctx, p)
+            st = ctx.last_call_stats()
+        finally:
+            ctx.set_workspace_limit(0)
+        assert 3 <= st["render_chunks"] < len(cases)  # (some chunks hold several traces)
+        assert (st["render_deferred"], st["render_too_small"]) == (0, 0)  # a deferral cannot hide a failure
+        assert st["host_syncs"] == 1  # as measured on the commit before the drivers shared one chunk loop: one wait, however many chunks
+        whole = run_checked(ctx, prepared(cases, form, device=True))
+        assert ctx.last_call_stats()["render_chunks"] == 1
+        host = hostlib.render_batch(p.host_flat(), form, 4)
+        for (name, _, want), got, one, h in zip(pick, rows, whole, host):
+            assert got["status"] == rc.OK and got["text"] == one["text"] == h["text"] == want[form], (name, form)
+
+
 def _synth(seed, mf):
     from tracy_amd import hostlib
     ref, sig, pos, _ = hostlib.synth_decompose(seed, mf + 400, mf, 30, seed % 4, 0.6)

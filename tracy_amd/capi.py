@@ -1563,6 +1563,120 @@ def _basecall_traces(self, signals, positions=None, sigratio=0.33, trim_stringen
 Context.basecall_traces = _basecall_traces
 
 
+# ---- the frame of the prepared two-pass calls (read, pad, render, render_alignments) -----------------------------------------------------
+class _TwoPassCall:
+    """What PreparedRead, PreparedPad, PreparedRender and PreparedAlnText share: a job struct built by the subclass, and a result struct
+    that starts as the sizes-only form (per-item arrays alone) and takes payload arrays with with_capacity().  A subclass sets
+      _stem      tracyhip_<stem> and tracyhip_<stem>_async are the calls
+      _result    the result struct; the element types of its arrays are read from its fields
+      _meta      its per-item arrays, which this object owns (self.meta)
+      _sizes     those of them that sizes() returns: one array, or a tuple of several
+      _caps      its offset / capacity arrays and _pay its payload arrays, both from the dict `o` of the hostlib <_host>_alloc layout
+      _host      hostlib.<_host>_unpack reads one item of host_arrays()
+      DEFERRED   the status of an item left to the host
+      _flat_dev  the arrays of `flat` (the inputs in the layout of the hostlib batch) that may lie on the device alone, in self.d
+      _gather    the per-item arrays of `flat` that a sub-batch of deferred items takes rows of (a missing one is an error), and
+      _gather_opt  those a job may do without (trims, strands): gathered where `flat` holds them
+    and _batch(sub): the hostlib batch over such a sub-batch."""
+    _meta = _sizes = _caps = _pay = _flat_dev = _gather = _gather_opt = ()
+
+    def _bind(self, o):
+        """the result struct over the arrays of `o` (None: the sizes-only form)"""
+        types = dict(self._result._fields_)
+        self.meta = {k: np.zeros(max(self.nt, 1), np.dtype(types[k]._type_)) for k in self._meta}
+        out = self.out = self._result()
+        for k in self._meta:
+            setattr(out, k, self.meta[k].ctypes.data_as(types[k]))
+        self.o = o
+        if o is None:
+            return
+        for k in self._caps:
+            setattr(out, k, o[k].ctypes.data_as(types[k]))
+        for k in self._pay:
+            setattr(out, k, o[k].data_ptr() if self.device else o[k].ctypes.data)
+
+    def _take(self, o):
+        """binds freshly allocated host arrays `o`, their payloads uploaded first with device=True"""
+        if self.device:
+            import torch
+            for k in self._pay:
+                o[k] = torch.from_numpy(o[k]).cuda()
+            torch.cuda.synchronize()
+        self._bind(o)
+        return self
+
+    def sizes(self, ctx):
+        """the sizes-only call: the sizes per item, 0 for deferred items"""
+        self._bind(None)
+        self.run(ctx)
+        s = tuple(self.meta[k][:self.nt].copy() for k in self._sizes)
+        return s if len(s) > 1 else s[0]
+
+    def run(self, ctx, asynchronous=False):
+        fn = getattr(lib(), "tracyhip_" + self._stem + ("_async" if asynchronous else ""))
+        _check(fn(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
+        return self
+
+    def host_arrays(self):
+        """the result arrays on the host in the layout of the hostlib alloc (device payloads are copied back)"""
+        o = dict(self.o)
+        if self.device:
+            for k in self._pay:
+                o[k] = o[k].cpu().numpy()
+        o.update(self.meta)
+        return o
+
+    def host_flat(self):
+        """the inputs on the host in the layout of the hostlib batch"""
+        f = dict(self.flat)
+        for k in self._flat_dev:
+            if k not in f:
+                f[k] = self.d[k].cpu().numpy()
+        return f
+
+    def results(self, fill_deferred=True):
+        """per item the dict of hostlib's unpack; deferred items are filled in by the host (_host_batch, _filled)"""
+        from . import hostlib
+        o = self.host_arrays()
+        unpack = getattr(hostlib, self._host + "_unpack")
+        res = [unpack(o, t) for t in range(self.nt)]
+        sel = np.array([t for t in range(self.nt) if res[t]["status"] == self.DEFERRED], dtype=np.int64)
+        if fill_deferred and len(sel):
+            for t, r in zip(sel, self._host_batch(sel)):
+                res[t] = self._filled(res[t], r)
+        return res
+
+    def _host_batch(self, sel):
+        """the host's answers for the items `sel`: a sub-batch over the same payload arrays"""
+        f = self.host_flat()
+        sub = dict(f, nt=len(sel))
+        for k in self._gather + tuple(k for k in self._gather_opt if k in f):
+            sub[k] = np.append(f[k][sel], f[k].dtype.type(0))
+        return self._batch(sub)
+
+    def _filled(self, mine, r):
+        """the result of a deferred item given the host's answer r: the answer, or `unreadable` with the status left DEFERRED"""
+        return r if r["status"] == 0 else dict(mine, unreadable=True)
+
+
+class _TextCall(_TwoPassCall):
+    """the two calls that print: one text buffer, RenderResult, the layout of hostlib.render_alloc"""
+    _meta = ("status", "text_len")
+    _sizes = ("text_len",)
+    _caps = ("text_offset", "text_cap")
+    _pay = ("text",)
+
+    def with_capacity(self, text_cap, fill=None, offsets=None):
+        """a text buffer with room for text_cap[t] bytes of item t (fill: a byte the buffer starts with, for tests that check what a
+        call leaves untouched; offsets: text_offset of every item and the buffer's size behind them, instead of back to back)"""
+        from . import hostlib
+        o = hostlib.render_alloc(self.nt, text_cap, fill)
+        if offsets is not None:
+            o["text_offset"] = np.ascontiguousarray(offsets, dtype=np.uint64)
+            o["text"] = np.full(max(int(o["text_offset"][self.nt]), 1), 0 if fill is None else fill, np.uint8)
+        return self._take(o)
+
+
 # ---- chromatogram files read on the device (tracyhip_read_traces) ---------------------------------------------------------------------
 READ_OK, READ_DEFERRED, READ_TOO_SMALL = 0, 1, 2
 
@@ -1589,13 +1703,20 @@ def read_bound(file_len):
     return ns.value, nc.value
 
 
-class PreparedRead:
+class PreparedRead(_TwoPassCall):
     """job / result structs of tracyhip_read_traces.  files: per trace a path (read here, once) or the file image as bytes.  With
     device=True the images and the payload results are torch tensors on the GPU and stay there: Context.basecall_traces takes this object
     as it stands.  Everything the structs point to is kept alive by this object.
 
     The result side starts as the sizes-only form; with_capacity() allocates the payload results, bounds() gives capacities that need no
-    sizes-only call."""
+    sizes-only call.  sizes(): (nsamples, ncalls).  results(): per trace dict(status, format, nsamples, ncalls, signal [4][ns],
+    basecallpos, basecalls1, basecalls2, qual); deferred traces are read by the host readers, except those they refuse too
+    (`unreadable`: status stays DEFERRED)."""
+    _stem, _result, _host, DEFERRED = "read_traces", ReadResult, "read", READ_DEFERRED
+    _meta = ("status", "format", "nsamples", "ncalls")
+    _sizes = ("nsamples", "ncalls")
+    _caps = ("sample_offset", "sample_cap", "call_offset", "call_cap")
+    _pay = _READ_PAY
 
     def __init__(self, files, sample_dtype=np.int16, device=False):
         from . import hostlib
@@ -1617,28 +1738,6 @@ class PreparedRead:
         self.mem = MEM_DEVICE if self.device else MEM_HOST
         self._bind(None)
 
-    def _bind(self, o):
-        """the result struct over the arrays of `o` (hostlib.read_alloc layout; None: the sizes-only form)"""
-        self.meta = dict(status=np.zeros(max(self.nt, 1), np.int32), format=np.zeros(max(self.nt, 1), np.int32),
-                         nsamples=np.zeros(max(self.nt, 1), np.uint32), ncalls=np.zeros(max(self.nt, 1), np.uint32))
-        out = self.out = ReadResult()
-        out.status = self.meta["status"].ctypes.data_as(C.POINTER(C.c_int32))
-        out.format = self.meta["format"].ctypes.data_as(C.POINTER(C.c_int32))
-        out.nsamples, out.ncalls = _u32p(self.meta["nsamples"]), _u32p(self.meta["ncalls"])
-        self.o = o
-        if o is None:
-            return
-        out.sample_offset, out.sample_cap = _u64p(o["sample_offset"]), _u32p(o["sample_cap"])
-        out.call_offset, out.call_cap = _u64p(o["call_offset"]), _u32p(o["call_cap"])
-        for k in _READ_PAY:
-            setattr(out, k, o[k].data_ptr() if self.device else o[k].ctypes.data)
-
-    def sizes(self, ctx):
-        """the sizes-only call: (nsamples, ncalls) per trace, 0 for deferred traces"""
-        self._bind(None)
-        _check(lib().tracyhip_read_traces(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
-        return self.meta["nsamples"][:self.nt].copy(), self.meta["ncalls"][:self.nt].copy()
-
     def bounds(self):
         """tracyhip_read_bound per file: (sample_cap, call_cap) arrays"""
         b = [read_bound(int(n)) for n in self.flat["file_len"][:self.nt]]
@@ -1648,42 +1747,14 @@ class PreparedRead:
         """payload results with room for sample_cap[t] samples per channel and call_cap[t] calls of trace t (fill: a value every payload
         element starts with, for tests that check what a call leaves untouched)"""
         from . import hostlib
-        o = hostlib.read_alloc(self.nt, self.sample_dtype, sample_cap, call_cap, fill)
-        if self.device:
-            import torch
-            for k in _READ_PAY:
-                o[k] = torch.from_numpy(o[k]).cuda()
-            torch.cuda.synchronize()
-        self._bind(o)
-        return self
+        return self._take(hostlib.read_alloc(self.nt, self.sample_dtype, sample_cap, call_cap, fill))
 
-    def run(self, ctx, asynchronous=False):
-        fn = lib().tracyhip_read_traces_async if asynchronous else lib().tracyhip_read_traces
-        _check(fn(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
-        return self
-
-    def host_arrays(self):
-        """the result arrays on the host in the layout of hostlib.read_alloc (device payloads are copied back)"""
-        o = dict(self.o)
-        if self.device:
-            for k in _READ_PAY:
-                o[k] = o[k].cpu().numpy()
-        o.update(self.meta)
-        return o
-
-    def results(self, fill_deferred=True):
-        """per trace: dict(status, format, nsamples, ncalls, signal [4][ns], basecallpos, basecalls1, basecalls2, qual).  Deferred traces are
-        read by the host readers (hostlib.read_batch), except those they refuse too (`unreadable`: status stays DEFERRED)"""
+    def _host_batch(self, sel):
+        """the deferred files are read again from their packed images, not from a sub-batch"""
         from . import hostlib
-        o = self.host_arrays()
-        res = [hostlib.read_unpack(o, t) for t in range(self.nt)]
-        sel = [t for t in range(self.nt) if res[t]["status"] == READ_DEFERRED]
-        if fill_deferred and sel:
-            f = self.flat
-            imgs = [f["bytes"][int(f["file_off"][t]):int(f["file_off"][t]) + int(f["file_len"][t])].tobytes() for t in sel]
-            for t, r in zip(sel, hostlib.read_batch(imgs, self.sample_dtype)):
-                res[t] = r if r["status"] == 0 else dict(res[t], unreadable=True)
-        return res
+        f = self.flat
+        imgs = [f["bytes"][int(f["file_off"][t]):int(f["file_off"][t]) + int(f["file_len"][t])].tobytes() for t in sel]
+        return hostlib.read_batch(imgs, self.sample_dtype)
 
 
 def _read_traces(self, files, sample_dtype=np.int16, device=False, asynchronous=False):
@@ -1724,14 +1795,74 @@ _PAD_BC = ("bcpos", "primary", "secondary", "consensus", "estqual")
 _PAD_META = ("nsamples_out", "ncalls_out", "leading_gaps", "trailing_gaps", "step")
 
 
-class PreparedPad:
+def _flatten_traces(signals, bc, sample_dtype):
+    """signals (int32 or int16 [4][ns] per trace; sample_dtype None: int16 if all are, else int32) and bc (per trace a dict of bcpos,
+    primary, secondary, consensus, estqual) as the flattened input arrays of hostlib.pad_batch / render_batch: (sample dtype, dict)"""
+    nt = len(signals)
+    if sample_dtype is None:
+        sample_dtype = np.int16 if nt and all(np.asarray(s).dtype == np.int16 for s in signals) else np.int32
+    dt = np.dtype(sample_dtype)
+    f = {}
+    f["nsamples"] = np.array([np.asarray(s).shape[1] for s in signals] + [0], dtype=np.uint32)
+    f["bc_len"] = np.array([len(b["bcpos"]) for b in bc] + [0], dtype=np.uint32)
+    f["sig_off"] = np.zeros(nt + 1, np.uint64)
+    f["bc_off"] = np.zeros(nt + 1, np.uint64)
+    f["sig_off"][1:] = np.cumsum(4 * f["nsamples"][:nt].astype(np.uint64))
+    f["bc_off"][1:] = np.cumsum(f["bc_len"][:nt].astype(np.uint64))
+    f["signal"] = np.concatenate([np.ascontiguousarray(s, dtype=dt).reshape(-1) for s in signals] + [np.zeros(1, dt)])
+    f["bcpos"] = np.concatenate([np.ascontiguousarray(b["bcpos"], dtype=np.int32).reshape(-1) for b in bc] + [np.zeros(1, np.int32)])
+    for k in _PAD_BC[1:]:
+        f[k] = np.concatenate([np.frombuffer(bytes(b[k]), np.uint8) if isinstance(b[k], (bytes, bytearray))
+                               else np.ascontiguousarray(b[k], dtype=np.uint8).reshape(-1) for b in bc] + [np.zeros(1, np.uint8)])
+    return dt, f
+
+
+def _adopt_basecalls(f, device_bc):
+    """the input side over a PreparedBasecall(device=True) that has run: its offsets and lengths into `f`; returns its chromatogram and
+    basecall tensors as they stand"""
+    f.update(sig_off=device_bc.sig_off, nsamples=device_bc.nsamples, bc_off=device_bc.pos_off, bc_len=device_bc.meta["bc_len"])
+    return dict(signal=device_bc.d_signal, **{k: device_bc.payload[k] for k in _PAD_BC})
+
+
+def _flat_trims(f, nt, trim_left, trim_right):
+    """the per-trace trims into `f` (trim_l, trim_r), both or neither"""
+    if (trim_left is None) != (trim_right is None):
+        raise ValueError("trim_left and trim_right go together: both or neither")
+    if trim_left is not None:
+        f["trim_l"] = np.append(np.ascontiguousarray(trim_left, dtype=np.uint32)[:nt], np.uint32(0))
+        f["trim_r"] = np.append(np.ascontiguousarray(trim_right, dtype=np.uint32)[:nt], np.uint32(0))
+
+
+def _point_at_traces(job, f, ptr, sample_dtype):
+    """the chromatogram, basecall and trim fields that PadJob and RenderJob share, over `f` and the payload pointers ptr(key)"""
+    job.signal, job.sample_bytes = ptr("signal"), sample_dtype.itemsize
+    job.signal_offset, job.nsamples = _u64p(f["sig_off"]), _u32p(f["nsamples"])
+    for k in _PAD_BC:
+        setattr(job, k, ptr(k))
+    job.bc_offset, job.bc_len = _u64p(f["bc_off"]), _u32p(f["bc_len"])
+    if "trim_l" in f:
+        job.trim_left_each, job.trim_right_each = _u32p(f["trim_l"]), _u32p(f["trim_r"])
+
+
+class PreparedPad(_TwoPassCall):
     """job / result structs of tracyhip_pad_traces.  signals: int32 or int16 [4][ns] per trace; bc: per trace a dict of bcpos, primary,
     secondary, consensus, estqual; rows: the row of each trace as bytes, or (data, row_offset, row_len) with data a numpy array or a torch
     tensor on the GPU holding rows of some alignment result as they stand.  device_bc: a PreparedBasecall(device=True) that has run -- its
     chromatogram and basecall tensors are taken as they stand (signals and bc are then ignored).  With device=True (implied by device_bc)
     the payloads are torch tensors on the GPU.  Everything the structs point to is kept alive by this object.
 
-    The result side starts as the sizes-only form; with_capacity() allocates the payload results."""
+    The result side starts as the sizes-only form; with_capacity() allocates the payload results.  sizes(): (nsamples_out, ncalls_out).
+    results(): per trace dict(status, signal [4][ns'], bcPos, primary, secondary, consensus, estQual, leadingGaps, trailingGaps, step);
+    deferred traces are filled in by the host chain (hostlib.pad_batch), except those the reference's loops cannot run either
+    (`unreadable`: status stays DEFERRED)."""
+    _stem, _result, _host, DEFERRED = "pad_traces", PadResult, "pad", PAD_DEFERRED
+    _meta = _PAD_META + ("status",)
+    _sizes = ("nsamples_out", "ncalls_out")
+    _caps = ("sample_offset", "sample_cap", "call_offset", "call_cap")
+    _pay = ("signal",) + _PAD_BC
+    _flat_dev = ("signal",) + _PAD_BC + ("rows",)
+    _gather = ("sig_off", "nsamples", "bc_off", "bc_len", "row_off", "row_len")
+    _gather_opt = ("trim_l", "trim_r", "reverse")
 
     def __init__(self, signals, bc, rows, trim_left=None, trim_right=None, reverse=None, device=False, device_bc=None, sample_dtype=None):
         self.device = device = bool(device or device_bc is not None)
@@ -1740,24 +1871,11 @@ class PreparedPad:
         if device_bc is not None:
             nt = self.nt = device_bc.nt
             self.sample_dtype = device_bc.sample_dtype
-            f.update(sig_off=device_bc.sig_off, nsamples=device_bc.nsamples, bc_off=device_bc.pos_off, bc_len=device_bc.meta["bc_len"])
-            self.d = dict(signal=device_bc.d_signal, **{k: device_bc.payload[k] for k in _PAD_BC})
+            self.d = _adopt_basecalls(f, device_bc)
         else:
             nt = self.nt = len(signals)
-            if sample_dtype is None:
-                sample_dtype = np.int16 if nt and all(np.asarray(s).dtype == np.int16 for s in signals) else np.int32
-            self.sample_dtype = np.dtype(sample_dtype)
-            f["nsamples"] = np.array([np.asarray(s).shape[1] for s in signals] + [0], dtype=np.uint32)
-            f["bc_len"] = np.array([len(b["bcpos"]) for b in bc] + [0], dtype=np.uint32)
-            f["sig_off"] = np.zeros(nt + 1, np.uint64)
-            f["bc_off"] = np.zeros(nt + 1, np.uint64)
-            f["sig_off"][1:] = np.cumsum(4 * f["nsamples"][:nt].astype(np.uint64))
-            f["bc_off"][1:] = np.cumsum(f["bc_len"][:nt].astype(np.uint64))
-            f["signal"] = np.concatenate([np.ascontiguousarray(s, dtype=self.sample_dtype).reshape(-1) for s in signals] + [np.zeros(1, self.sample_dtype)])
-            f["bcpos"] = np.concatenate([np.ascontiguousarray(b["bcpos"], dtype=np.int32).reshape(-1) for b in bc] + [np.zeros(1, np.int32)])
-            for k in _PAD_BC[1:]:
-                f[k] = np.concatenate([np.frombuffer(bytes(b[k]), np.uint8) if isinstance(b[k], (bytes, bytearray))
-                                       else np.ascontiguousarray(b[k], dtype=np.uint8).reshape(-1) for b in bc] + [np.zeros(1, np.uint8)])
+            self.sample_dtype, flat = _flatten_traces(signals, bc, sample_dtype)
+            f.update(flat)
         f["nt"] = nt
         if isinstance(rows, tuple):
             data, roff, rlen = rows
@@ -1772,11 +1890,7 @@ class PreparedPad:
             f["row_off"][1:] = np.cumsum(f["row_len"][:nt].astype(np.uint64))
             f["rows"] = np.frombuffer(b"".join(bytes(r) for r in rows) + b"\0", np.uint8).copy()
             self._rows_in = f["rows"]
-        if (trim_left is None) != (trim_right is None):
-            raise ValueError("trim_left and trim_right go together: both or neither")
-        if trim_left is not None:
-            f["trim_l"] = np.append(np.ascontiguousarray(trim_left, dtype=np.uint32)[:nt], np.uint32(0))
-            f["trim_r"] = np.append(np.ascontiguousarray(trim_right, dtype=np.uint32)[:nt], np.uint32(0))
+        _flat_trims(f, nt, trim_left, trim_right)
         if reverse is not None:
             f["reverse"] = np.append(np.array([1 if x else 0 for x in reverse], dtype=np.uint8)[:nt], np.uint8(0))
         if device:
@@ -1792,41 +1906,12 @@ class PreparedPad:
             ptr = lambda k: f[k].ctypes.data
         job = self.job = PadJob()
         job.ntraces = nt
-        job.signal, job.sample_bytes = ptr("signal"), self.sample_dtype.itemsize
-        job.signal_offset, job.nsamples = _u64p(f["sig_off"]), _u32p(f["nsamples"])
-        for k in _PAD_BC:
-            setattr(job, k, ptr(k))
-        job.bc_offset, job.bc_len = _u64p(f["bc_off"]), _u32p(f["bc_len"])
+        _point_at_traces(job, f, ptr, self.sample_dtype)
         job.rows, job.row_offset, job.row_len = ptr("rows"), _u64p(f["row_off"]), _u32p(f["row_len"])
-        if trim_left is not None:
-            job.trim_left_each, job.trim_right_each = _u32p(f["trim_l"]), _u32p(f["trim_r"])
         if reverse is not None:
             job.reverse = f["reverse"].ctypes.data_as(C.POINTER(C.c_uint8))
         self.mem = MEM_DEVICE if device else MEM_HOST
-        self.o = None
         self._bind(None)
-
-    def _bind(self, o):
-        """the result struct over the arrays of `o` (hostlib.pad_alloc layout; None: the sizes-only form)"""
-        self.meta = {k: np.zeros(max(self.nt, 1), np.uint32) for k in _PAD_META}
-        self.meta["status"] = np.zeros(max(self.nt, 1), np.int32)
-        out = self.out = PadResult()
-        out.status = self.meta["status"].ctypes.data_as(C.POINTER(C.c_int32))
-        for k in _PAD_META:
-            setattr(out, k, _u32p(self.meta[k]))
-        self.o = o
-        if o is None:
-            return
-        out.sample_offset, out.sample_cap = _u64p(o["sample_offset"]), _u32p(o["sample_cap"])
-        out.call_offset, out.call_cap = _u64p(o["call_offset"]), _u32p(o["call_cap"])
-        for k in ("signal",) + _PAD_BC:
-            setattr(out, k, o[k].data_ptr() if self.device else o[k].ctypes.data)
-
-    def sizes(self, ctx):
-        """the sizes-only call: (nsamples_out, ncalls_out) per trace, 0 for deferred traces"""
-        self._bind(None)
-        _check(lib().tracyhip_pad_traces(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
-        return self.meta["nsamples_out"][:self.nt].copy(), self.meta["ncalls_out"][:self.nt].copy()
 
     def with_capacity(self, sample_cap, call_cap, fill=None):
         """payload results with room for sample_cap[t] samples per channel and call_cap[t] calls of trace t (fill: a value every payload
@@ -1834,55 +1919,13 @@ class PreparedPad:
         from . import hostlib
         o = hostlib.pad_alloc(dict(nt=self.nt, signal=np.zeros(0, self.sample_dtype)), sample_cap, call_cap)
         if fill is not None:
-            for k in ("signal",) + _PAD_BC:
+            for k in self._pay:
                 o[k][:] = fill
-        if self.device:
-            import torch
-            for k in ("signal",) + _PAD_BC:
-                o[k] = torch.from_numpy(o[k]).cuda()
-            torch.cuda.synchronize()
-        self._bind(o)
-        return self
+        return self._take(o)
 
-    def run(self, ctx, asynchronous=False):
-        fn = lib().tracyhip_pad_traces_async if asynchronous else lib().tracyhip_pad_traces
-        _check(fn(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
-        return self
-
-    def host_arrays(self):
-        """the result arrays on the host in the layout of hostlib.pad_alloc (device payloads are copied back)"""
-        o = dict(self.o)
-        if self.device:
-            for k in ("signal",) + _PAD_BC:
-                o[k] = o[k].cpu().numpy()
-        o.update(self.meta)
-        return o
-
-    def host_flat(self):
-        """the inputs on the host in the layout of hostlib.pad_batch"""
-        f = dict(self.flat)
-        for k in ("signal",) + _PAD_BC + ("rows",):
-            if k not in f:
-                f[k] = self.d[k].cpu().numpy()
-        return f
-
-    def results(self, fill_deferred=True):
-        """per trace: dict(status, signal [4][ns'], bcPos, primary, secondary, consensus, estQual, leadingGaps, trailingGaps, step).  Deferred
-        traces are filled in by the host chain (hostlib.pad_batch), except those the reference's loops cannot run either (`unreadable`:
-        status stays DEFERRED)"""
+    def _batch(self, sub):
         from . import hostlib
-        o = self.host_arrays()
-        res = [hostlib.pad_unpack(o, t) for t in range(self.nt)]
-        sel = np.array([t for t in range(self.nt) if res[t]["status"] == PAD_DEFERRED], dtype=np.int64)
-        if fill_deferred and len(sel):
-            f = self.host_flat()
-            sub = dict(f, nt=len(sel))
-            for k in ("sig_off", "nsamples", "bc_off", "bc_len", "row_off", "row_len", "trim_l", "trim_r", "reverse"):
-                if k in f:
-                    sub[k] = np.append(f[k][sel], f[k].dtype.type(0))
-            for t, r in zip(sel, hostlib.pad_batch(sub)):
-                res[t] = r if r["status"] == 0 else dict(res[t], unreadable=True)
-        return res
+        return hostlib.pad_batch(sub)
 
 
 def _pad_traces(self, signals, bc, rows, trim_left=None, trim_right=None, reverse=None, device=False, device_bc=None, asynchronous=False):
@@ -1919,7 +1962,7 @@ def render_bound(form, nsamples, bc_len, sample_bytes):
     return int(lib().tracyhip_render_bound(C.c_uint32(form), C.c_uint32(nsamples), C.c_uint32(bc_len), C.c_uint32(sample_bytes)))
 
 
-class PreparedRender:
+class PreparedRender(_TextCall):
     """job / result structs of tracyhip_render_traces.  form: RENDER_TSV / RENDER_JSON / RENDER_GAPPED.  The traces come from one of
       signals, bc   int32 or int16 [4][ns] per trace; per trace a dict of bcpos, primary, secondary, consensus, estqual (host arrays;
                     device=True uploads them once)
@@ -1928,7 +1971,13 @@ class PreparedRender:
     No payload is copied to the host for the last two.  trim_left / trim_right: the per-trace trims of the TSV's trim column.
     Everything the structs point to is kept alive by this object.
 
-    The result side starts as the sizes-only form; with_capacity() allocates the text."""
+    The result side starts as the sizes-only form; with_capacity() allocates the text.  sizes(): text_len.  results(): per trace
+    dict(status, text_len, text); deferred traces are printed by the host writers (hostlib.render_batch), except those the reference's
+    loops cannot run either (`unreadable`: status stays DEFERRED)."""
+    _stem, _result, _host, DEFERRED = "render_traces", RenderResult, "render", RENDER_DEFERRED
+    _flat_dev = ("signal",) + _PAD_BC
+    _gather = ("sig_off", "nsamples", "bc_off", "bc_len")
+    _gather_opt = ("trim_l", "trim_r")
 
     def __init__(self, form, signals=None, bc=None, trim_left=None, trim_right=None, device=False, device_bc=None, device_pad=None,
                  sample_dtype=None):
@@ -1938,8 +1987,7 @@ class PreparedRender:
         if device_bc is not None:
             nt = self.nt = device_bc.nt
             self.sample_dtype = device_bc.sample_dtype
-            f.update(sig_off=device_bc.sig_off, nsamples=device_bc.nsamples, bc_off=device_bc.pos_off, bc_len=device_bc.meta["bc_len"])
-            self.d = dict(signal=device_bc.d_signal, **{k: device_bc.payload[k] for k in _PAD_BC})
+            self.d = _adopt_basecalls(f, device_bc)
         elif device_pad is not None:
             if not device_pad.device or device_pad.o is None:
                 raise ValueError("device_pad: a PreparedPad(device=True) with payload results")
@@ -1950,60 +1998,19 @@ class PreparedRender:
             self.d = {k: device_pad.o[k] for k in ("signal",) + _PAD_BC}
         else:
             nt = self.nt = len(signals)
-            if sample_dtype is None:
-                sample_dtype = np.int16 if nt and all(np.asarray(s).dtype == np.int16 for s in signals) else np.int32
-            self.sample_dtype = np.dtype(sample_dtype)
-            f["nsamples"] = np.array([np.asarray(s).shape[1] for s in signals] + [0], dtype=np.uint32)
-            f["bc_len"] = np.array([len(b["bcpos"]) for b in bc] + [0], dtype=np.uint32)
-            f["sig_off"] = np.zeros(nt + 1, np.uint64)
-            f["bc_off"] = np.zeros(nt + 1, np.uint64)
-            f["sig_off"][1:] = np.cumsum(4 * f["nsamples"][:nt].astype(np.uint64))
-            f["bc_off"][1:] = np.cumsum(f["bc_len"][:nt].astype(np.uint64))
-            f["signal"] = np.concatenate([np.ascontiguousarray(s, dtype=self.sample_dtype).reshape(-1) for s in signals] + [np.zeros(1, self.sample_dtype)])
-            f["bcpos"] = np.concatenate([np.ascontiguousarray(b["bcpos"], dtype=np.int32).reshape(-1) for b in bc] + [np.zeros(1, np.int32)])
-            for k in _PAD_BC[1:]:
-                f[k] = np.concatenate([np.frombuffer(bytes(b[k]), np.uint8) if isinstance(b[k], (bytes, bytearray))
-                                       else np.ascontiguousarray(b[k], dtype=np.uint8).reshape(-1) for b in bc] + [np.zeros(1, np.uint8)])
+            self.sample_dtype, flat = _flatten_traces(signals, bc, sample_dtype)
+            f.update(flat)
             if device:
                 import torch
                 self.d = {k: torch.from_numpy(f[k]).cuda() for k in ("signal",) + _PAD_BC}
                 torch.cuda.synchronize()
         f["nt"] = nt
-        if (trim_left is None) != (trim_right is None):
-            raise ValueError("trim_left and trim_right go together: both or neither")
-        if trim_left is not None:
-            f["trim_l"] = np.append(np.ascontiguousarray(trim_left, dtype=np.uint32)[:nt], np.uint32(0))
-            f["trim_r"] = np.append(np.ascontiguousarray(trim_right, dtype=np.uint32)[:nt], np.uint32(0))
-        ptr = (lambda k: self.d[k].data_ptr()) if device else (lambda k: f[k].ctypes.data)
+        _flat_trims(f, nt, trim_left, trim_right)
         job = self.job = RenderJob()
         job.ntraces, job.form = nt, self.form
-        job.signal, job.sample_bytes = ptr("signal"), self.sample_dtype.itemsize
-        job.signal_offset, job.nsamples = _u64p(f["sig_off"]), _u32p(f["nsamples"])
-        for k in _PAD_BC:
-            setattr(job, k, ptr(k))
-        job.bc_offset, job.bc_len = _u64p(f["bc_off"]), _u32p(f["bc_len"])
-        if trim_left is not None:
-            job.trim_left_each, job.trim_right_each = _u32p(f["trim_l"]), _u32p(f["trim_r"])
+        _point_at_traces(job, f, (lambda k: self.d[k].data_ptr()) if device else (lambda k: f[k].ctypes.data), self.sample_dtype)
         self.mem = MEM_DEVICE if device else MEM_HOST
         self._bind(None)
-
-    def _bind(self, o):
-        """the result struct over the arrays of `o` (hostlib.render_alloc layout; None: the sizes-only form)"""
-        self.meta = dict(status=np.zeros(max(self.nt, 1), np.int32), text_len=np.zeros(max(self.nt, 1), np.uint32))
-        out = self.out = RenderResult()
-        out.status = self.meta["status"].ctypes.data_as(C.POINTER(C.c_int32))
-        out.text_len = _u32p(self.meta["text_len"])
-        self.o = o
-        if o is None:
-            return
-        out.text_offset, out.text_cap = _u64p(o["text_offset"]), _u64p(o["text_cap"])
-        out.text = o["text"].data_ptr() if self.device else o["text"].ctypes.data
-
-    def sizes(self, ctx):
-        """the sizes-only call: text_len per trace, 0 for deferred traces"""
-        self._bind(None)
-        _check(lib().tracyhip_render_traces(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
-        return self.meta["text_len"][:self.nt].copy()
 
     def bounds(self):
         """tracyhip_render_bound per trace: capacities that need no sizes-only call"""
@@ -2011,58 +2018,9 @@ class PreparedRender:
         return np.array([render_bound(self.form, int(f["nsamples"][t]), int(f["bc_len"][t]), self.sample_dtype.itemsize) for t in range(self.nt)],
                         dtype=np.uint64)
 
-    def with_capacity(self, text_cap, fill=None, offsets=None):
-        """a text buffer with room for text_cap[t] bytes of trace t (fill: a byte the buffer starts with, for tests that check what a
-        call leaves untouched; offsets: text_offset of every trace and the buffer's size behind them, instead of back to back)"""
+    def _batch(self, sub):
         from . import hostlib
-        o = hostlib.render_alloc(self.nt, text_cap, fill)
-        if offsets is not None:
-            o["text_offset"] = np.ascontiguousarray(offsets, dtype=np.uint64)
-            o["text"] = np.full(max(int(o["text_offset"][self.nt]), 1), 0 if fill is None else fill, np.uint8)
-        if self.device:
-            import torch
-            o["text"] = torch.from_numpy(o["text"]).cuda()
-            torch.cuda.synchronize()
-        self._bind(o)
-        return self
-
-    def run(self, ctx, asynchronous=False):
-        fn = lib().tracyhip_render_traces_async if asynchronous else lib().tracyhip_render_traces
-        _check(fn(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
-        return self
-
-    def host_arrays(self):
-        """the result arrays on the host in the layout of hostlib.render_alloc (a device text is copied back)"""
-        o = dict(self.o)
-        if self.device:
-            o["text"] = o["text"].cpu().numpy()
-        o.update(self.meta)
-        return o
-
-    def host_flat(self):
-        """the inputs on the host in the layout of hostlib.render_batch"""
-        f = dict(self.flat)
-        for k in ("signal",) + _PAD_BC:
-            if k not in f:
-                f[k] = self.d[k].cpu().numpy()
-        return f
-
-    def results(self, fill_deferred=True):
-        """per trace: dict(status, text_len, text).  Deferred traces are printed by the host writers (hostlib.render_batch), except those
-        the reference's loops cannot run either (`unreadable`: status stays DEFERRED)"""
-        from . import hostlib
-        o = self.host_arrays()
-        res = [hostlib.render_unpack(o, t) for t in range(self.nt)]
-        sel = np.array([t for t in range(self.nt) if res[t]["status"] == RENDER_DEFERRED], dtype=np.int64)
-        if fill_deferred and len(sel):
-            f = self.host_flat()
-            sub = dict(f, nt=len(sel))
-            for k in ("sig_off", "nsamples", "bc_off", "bc_len", "trim_l", "trim_r"):
-                if k in f:
-                    sub[k] = np.append(f[k][sel], f[k].dtype.type(0))
-            for t, r in zip(sel, hostlib.render_batch(sub, self.form)):
-                res[t] = r if r["status"] == 0 else dict(res[t], unreadable=True)
-        return res
+        return hostlib.render_batch(sub, self.form)
 
 
 def _render_traces(self, form, signals=None, bc=None, trim_left=None, trim_right=None, device=False, device_bc=None, device_pad=None,
@@ -2104,7 +2062,7 @@ def alntext_bound(form, linelimit, cols, name0_len, name1_len):
                                                       C.c_uint32(name1_len)))
 
 
-class PreparedAlnText:
+class PreparedAlnText(_TextCall):
     """job / result structs of tracyhip_render_alignments.  form: ALNTEXT_PLOT / ALNTEXT_FASTA / ALNTEXT_JSON.  The rows come from
       rows0, rows1   lists of bytes, one pair per alignment (device=True uploads them once), or
       device_rows    (rows0, rows1, rows_offset, cols): two torch tensors on the GPU as tracyhip_alignment_rows / tracyhip_align_traces
@@ -2112,7 +2070,12 @@ class PreparedAlnText:
     name0 / name1: lists of bytes, the caller's text (hostlib.alntext_pack says which per form).  ref_pos, ref_len, forward, score: per
     alignment.  Everything the structs point to is kept alive by this object.
 
-    The result side starts as the sizes-only form; with_capacity() allocates the text."""
+    The result side starts as the sizes-only form; with_capacity() allocates the text.  sizes(): text_len.  results(): per alignment
+    dict(status, text_len, text); deferred alignments are printed by the host writers (hostlib.alntext_batch) and marked
+    deferred=True."""
+    _stem, _result, _host, DEFERRED = "render_alignments", RenderResult, "alntext", ALNTEXT_DEFERRED
+    _flat_dev = ("rows0", "rows1")
+    _gather = ("rows_off", "cols", "name0_off", "name0_len", "name1_off", "name1_len", "ref_pos", "ref_len", "forward", "score")
 
     def __init__(self, form, rows0=None, rows1=None, name0=None, name1=None, ref_pos=None, ref_len=None, forward=None, score=None, key=0,
                  linelimit=60, device=False, device_rows=None):
@@ -2153,85 +2116,24 @@ class PreparedAlnText:
         self.mem = MEM_DEVICE if device else MEM_HOST
         self._bind(None)
 
-    def _bind(self, o):
-        """the result struct over the arrays of `o` (hostlib.alntext_alloc layout; None: the sizes-only form)"""
-        self.meta = dict(status=np.zeros(max(self.nt, 1), np.int32), text_len=np.zeros(max(self.nt, 1), np.uint32))
-        out = self.out = RenderResult()
-        out.status = self.meta["status"].ctypes.data_as(C.POINTER(C.c_int32))
-        out.text_len = _u32p(self.meta["text_len"])
-        self.o = o
-        if o is None:
-            return
-        out.text_offset, out.text_cap = _u64p(o["text_offset"]), _u64p(o["text_cap"])
-        out.text = o["text"].data_ptr() if self.device else o["text"].ctypes.data
-
-    def sizes(self, ctx):
-        """the sizes-only call: text_len per alignment, 0 for deferred ones"""
-        self._bind(None)
-        _check(lib().tracyhip_render_alignments(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
-        return self.meta["text_len"][:self.nt].copy()
-
     def bounds(self):
         """tracyhip_render_alignments_bound per alignment: capacities that need no sizes-only call"""
         f = self.flat
         return np.array([alntext_bound(self.form, self.linelimit, int(f["cols"][t]), int(f["name0_len"][t]), int(f["name1_len"][t]))
                          for t in range(self.nt)], dtype=np.uint64)
 
-    def with_capacity(self, text_cap, fill=None, offsets=None):
-        """a text buffer with room for text_cap[t] bytes of alignment t (fill: a byte the buffer starts with, for tests that check what
-        a call leaves untouched; offsets: text_offset of every alignment and the buffer's size behind them, instead of back to back)"""
-        from . import hostlib
-        o = hostlib.alntext_alloc(self.nt, text_cap, fill)
-        if offsets is not None:
-            o["text_offset"] = np.ascontiguousarray(offsets, dtype=np.uint64)
-            o["text"] = np.full(max(int(o["text_offset"][self.nt]), 1), 0 if fill is None else fill, np.uint8)
-        if self.device:
-            import torch
-            o["text"] = torch.from_numpy(o["text"]).cuda()
-            torch.cuda.synchronize()
-        self._bind(o)
-        return self
-
-    def run(self, ctx, asynchronous=False):
-        fn = lib().tracyhip_render_alignments_async if asynchronous else lib().tracyhip_render_alignments
-        _check(fn(ctx._h, C.byref(self.job), self.mem, C.byref(self.out)))
-        return self
-
     def stats(self, ctx):
         st = AlnTextStats()
         _check(lib().tracyhip_last_alntext_stats(ctx._h, C.byref(st)))
         return {k: getattr(st, k) for k, _ in AlnTextStats._fields_}
 
-    def host_arrays(self):
-        """the result arrays on the host in the layout of hostlib.alntext_alloc (a device text is copied back)"""
-        o = dict(self.o)
-        if self.device:
-            o["text"] = o["text"].cpu().numpy()
-        o.update(self.meta)
-        return o
-
-    def host_flat(self):
-        """the inputs on the host in the layout of hostlib.alntext_batch"""
-        f = dict(self.flat)
-        for k in ("rows0", "rows1"):
-            if k not in f:
-                f[k] = self.d[k].cpu().numpy()
-        return f
-
-    def results(self, fill_deferred=True):
-        """per alignment: dict(status, text_len, text).  Deferred alignments are printed by the host writers (hostlib.alntext_batch)."""
+    def _batch(self, sub):
         from . import hostlib
-        o = self.host_arrays()
-        res = [hostlib.alntext_unpack(o, t) for t in range(self.nt)]
-        sel = np.array([t for t in range(self.nt) if res[t]["status"] == ALNTEXT_DEFERRED], dtype=np.int64)
-        if fill_deferred and len(sel):
-            f = self.host_flat()
-            sub = dict(f, nt=len(sel))
-            for k in ("rows_off", "cols", "name0_off", "name0_len", "name1_off", "name1_len", "ref_pos", "ref_len", "forward", "score"):
-                sub[k] = np.append(f[k][sel], f[k].dtype.type(0))
-            for t, r in zip(sel, hostlib.alntext_batch(sub, self.form, self.key, self.linelimit)):
-                res[t] = dict(r, deferred=True) if r["status"] == 0 else res[t]
-        return res
+        return hostlib.alntext_batch(sub, self.form, self.key, self.linelimit)
+
+    def _filled(self, mine, r):
+        """the host writers answer whatever the device defers: the answer marked, else the item as it was"""
+        return dict(r, deferred=True) if r["status"] == 0 else mine
 
 
 def _render_alignments(self, form, rows0=None, rows1=None, name0=None, name1=None, ref_pos=None, ref_len=None, forward=None, score=None, key=0,

@@ -8,7 +8,8 @@
 // counts the letters of both rows, which the line breaks and the counters of every later tile depend on.  Four waves per workgroup, each with
 // its own kAlnLdsBytes of LDS; the bodies are alntext_wave.h's (compiled for the host wave by tests/emu/emu_alntext.cpp), the wave
 // dev_wave.h's SoloWave.  What is refused before a device is touched, the bound, the cut into chunks and the descriptors are
-// alntext_plan.h's.
+// alntext_plan.h's; the frame of tracyhip_render_alignments -- chunk loop, descriptor and result buffer, waits -- is two_pass.h's
+// (tracyhip_reference_slices is a single pass over stage_in / stage_out and stays outside it).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +21,7 @@
 #include "alntext_wave.h"
 #include "capi_internal.h"
 #include "dev_wave.h"
+#include "two_pass.h"
 
 using namespace tracyhip;
 
@@ -94,127 +96,97 @@ uint64_t tracyhip_render_alignments_bound(uint32_t form, uint32_t linelimit, uin
   return alntext_bound(form, linelimit, cols, name0_len, name1_len);
 }
 
-int tracyhip_last_alntext_stats(tracyhip_ctx* ctx, tracyhip_alntext_stats* out) {
-  if (!ctx || !out) return set_error(TRACYHIP_ERR_ARG, "null context / out");
-  *out = ctx->alntext_stats;
-  return TRACYHIP_OK;
-}
+int tracyhip_last_alntext_stats(tracyhip_ctx* ctx, tracyhip_alntext_stats* out) { return last_stats(ctx, &tracyhip_ctx::alntext_stats, out); }
 
 int tracyhip_render_alignments(tracyhip_ctx* ctx, const tracyhip_alntext_job* job, int mem, const tracyhip_alntext_result* out) {
   int rc = validate(job, mem, out);  // before any device call
   if (rc != TRACYHIP_OK) return rc;
-  const uint32_t n = job->n;
-  if (n == 0) return TRACYHIP_OK;
-  rc = ctx_begin(ctx);
-  if (rc != TRACYHIP_OK) return rc;
-  ctx->stats = tracyhip_call_stats{};
-  ctx->stats.traces = n;
-  ctx->alntext_stats = tracyhip_alntext_stats{};
   const bool host = mem == TRACYHIP_MEM_HOST, payload = out->text != nullptr;
-  std::vector<AlnChunk> chunks;
-  uint32_t bad_t = 0;
-  if (!alntext_cut_chunks(job, out, host, ctx->ws_limit ? ctx->ws_limit : 256ull << 20, chunks, &bad_t))
-    return set_error(TRACYHIP_ERR_RANGE, "tracyhip_render_alignments: an offset + length of alignment %u leaves 64 bits", bad_t);
-  ctx->alntext_stats.alntext_chunks = (uint32_t)chunks.size();
-
-  // descriptors up and results back for the whole batch in one buffer; a chunk launches over its slice
-  const size_t b_out = (sizeof(AlnDesc) * n + 15) & ~size_t(15);
-  uint8_t* d0; HIP_TRY(ensure_into(ctx->dev[DB_ALNTEXT_DESC], b_out + sizeof(AlnOut) * n, d0));
-  std::vector<AlnDesc> meta(n);
-  std::vector<AlnOut> res(n);
+  TwoPass<AlnDesc, AlnOut, AlnChunk> f{ctx, job->n, host};
+  rc = f.begin("tracyhip_render_alignments", "alignment", DB_ALNTEXT_DESC, &tracyhip_ctx::alntext_stats, &tracyhip_alntext_stats::alntext_chunks,
+               [&](uint64_t limit, std::vector<AlnChunk>& chunks, uint32_t* bad_t) { return alntext_cut_chunks(job, out, host, limit, chunks, bad_t); });
+  if (rc != TRACYHIP_OK || f.chunks.empty()) return rc;
   uint64_t max_tiles = 1, max_coltiles = 1;  // sized once for the largest chunk: the launches of a device call follow each other without a wait
-  for (const AlnChunk& c : chunks) { max_tiles = std::max(max_tiles, c.tiles); max_coltiles = std::max(max_coltiles, c.coltiles); }
+  for (const AlnChunk& c : f.chunks) { max_tiles = std::max(max_tiles, c.tiles); max_coltiles = std::max(max_coltiles, c.coltiles); }
   uint32_t* d_tiles; HIP_TRY(ensure_into(ctx->dev[DB_ALNTEXT_TILES], 3 * max_tiles + 2 * max_coltiles, d_tiles));
-  auto report = [&](uint32_t t) {
-    out->status[t] = res[t].status;
-    out->text_len[t] = res[t].text_len;
-    if (res[t].status == TRACYHIP_ALNTEXT_DEFERRED) ctx->alntext_stats.alntext_deferred += 1;
-    if (res[t].status == TRACYHIP_ALNTEXT_TOO_SMALL) ctx->alntext_stats.alntext_too_small += 1;
-  };
-  for (const AlnChunk& c : chunks) {
-    const uint32_t m = c.t1 - c.t0;
-    uint32_t tile_first = 0, col_first = 0;
-    uint64_t moved = 0;
-    for (uint32_t t = c.t0; t < c.t1; ++t) {
-      meta[t] = alntext_desc(job, out, c, host, t, tile_first, col_first);
-      tile_first += alntext_tiles(job, t);
-      col_first += alntext_coltiles(job, t);
-      moved += 2ull * job->cols[t] * (payload ? 2 : 1);  // (both rows, once per pass)
-    }
-    HIP_TRY(hipMemcpyAsync(d0 + sizeof(AlnDesc) * c.t0, meta.data() + c.t0, sizeof(AlnDesc) * m, hipMemcpyHostToDevice, ctx->stream));
-    AlnArgs a{};
-    a.al = reinterpret_cast<const AlnDesc*>(d0) + c.t0;
-    a.out = reinterpret_cast<AlnOut*>(d0 + b_out) + c.t0;
-    a.n = m; a.ntiles = tile_first; a.ncoltiles = col_first; a.form = job->form;
-    a.key = job->form == TRACYHIP_ALNTEXT_PLOT ? job->key : 0u;
-    a.linelimit = job->form == TRACYHIP_ALNTEXT_PLOT ? job->linelimit : 1u;
-    a.tile_bytes = d_tiles; a.tile_aux = d_tiles + max_tiles; a.col_letters = d_tiles + 3 * max_tiles;
-    if (host) {
-      // inputs: the bytes of each span, first byte at the part's start
-      Layout li;
-      const uint64_t i_r0 = li.add(c.rows.size()), i_r1 = li.add(c.rows.size()), i_nm = li.add(c.names.size());
-      uint8_t* din; HIP_TRY(ensure_into(ctx->dev[DB_ALNTEXT_IN], li.total(), din));
-      auto up = [&](uint64_t at, const void* src, uint64_t bytes) {
-        return bytes ? hipMemcpyAsync(din + at, src, bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
-      };
-      HIP_TRY(up(i_r0, job->rows0 + c.rows.lo, c.rows.size()));
-      HIP_TRY(up(i_r1, job->rows1 + c.rows.lo, c.rows.size()));
-      HIP_TRY(up(i_nm, job->names + c.names.lo, c.names.size()));
-      a.rows0 = din + i_r0; a.rows1 = din + i_r1; a.names = din + i_nm;
-      if (payload) {
-        uint8_t* dout; HIP_TRY(ensure_into(ctx->dev[DB_ALNTEXT_OUT], c.text.size() + 16, dout));
-        a.text = dout;
-      }
-    } else {
-      a.rows0 = job->rows0; a.rows1 = job->rows1; a.names = job->names;
-      a.text = out->text;
-    }
-    if (ctx->timing && (rc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, moved))) return rc;
-    const dim3 block(64 * kAlnWaves), tgrid((a.ntiles + kAlnWaves - 1) / kAlnWaves), sgrid((m + kAlnWaves - 1) / kAlnWaves);
-    if (a.ncoltiles) {
-      hipLaunchKernelGGL(alntext_letters_kernel, dim3((a.ncoltiles + kAlnWaves - 1) / kAlnWaves), block, 0, ctx->stream, a);
-      HIP_TRY(hipGetLastError());
-    }
-    if (a.ntiles) {
-      hipLaunchKernelGGL(alntext_count_kernel, tgrid, block, 0, ctx->stream, a);
-      HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(alntext_scan_kernel, sgrid, block, 0, ctx->stream, a);
-    HIP_TRY(hipGetLastError());
-    if (payload && a.ntiles) {
-      hipLaunchKernelGGL(alntext_emit_kernel, tgrid, block, 0, ctx->stream, a);
-      HIP_TRY(hipGetLastError());
-    }
-    if ((rc = timing_end(ctx))) return rc;
-    if (!host) continue;  // device payloads: the results of all chunks come back behind the last launch
-    HIP_TRY(hipMemcpyAsync(res.data() + c.t0, a.out, sizeof(AlnOut) * m, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx_sync(ctx));
-    timing_collect(ctx);
-    // exactly what was reported goes back, straight into the caller's array; regions that follow each other on both sides travel as one copy
-    RunMerger<1, CopyBackRun<1>> rt{{payload ? 1u : 0u}, {ctx, {a.text}, {out->text}}};
-    for (uint32_t t = c.t0; t < c.t1; ++t) {
-      report(t);
-      if (payload && res[t].status == TRACYHIP_ALNTEXT_OK) HIP_TRY(rt.add(meta[t].text_off, out->text_offset[t], res[t].text_len));
-    }
-    if (payload) {
-      HIP_TRY(rt.flush());
-      HIP_TRY(ctx_sync(ctx));
-    }
-  }
-  if (!host) {
-    HIP_TRY(hipMemcpyAsync(res.data(), d0 + b_out, sizeof(AlnOut) * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx_sync(ctx));  // the one synchronisation of a device call: the sizes are what the caller allocates by
-    timing_collect(ctx);
-    for (uint32_t t = 0; t < n; ++t) report(t);
-  }
-  return TRACYHIP_OK;
+  const uint8_t* d_text = nullptr;  // the staged text of a host chunk
+  return f.run(
+      payload,
+      [&](const AlnChunk& c) {
+        const uint32_t m = c.t1 - c.t0;
+        uint32_t tile_first = 0, col_first = 0;
+        uint64_t moved = 0;
+        for (uint32_t t = c.t0; t < c.t1; ++t) {
+          f.meta[t] = alntext_desc(job, out, c, host, t, tile_first, col_first);
+          tile_first += alntext_tiles(job, t);
+          col_first += alntext_coltiles(job, t);
+          moved += 2ull * job->cols[t] * (payload ? 2 : 1);  // (both rows, once per pass)
+        }
+        HIP_TRY(f.upload(c));
+        AlnArgs a{};
+        a.al = f.desc_ptr(c);
+        a.out = f.out_ptr(c);
+        a.n = m; a.ntiles = tile_first; a.ncoltiles = col_first; a.form = job->form;
+        a.key = job->form == TRACYHIP_ALNTEXT_PLOT ? job->key : 0u;
+        a.linelimit = job->form == TRACYHIP_ALNTEXT_PLOT ? job->linelimit : 1u;
+        a.tile_bytes = d_tiles; a.tile_aux = d_tiles + max_tiles; a.col_letters = d_tiles + 3 * max_tiles;
+        if (host) {
+          // inputs: the bytes of each span, first byte at the part's start
+          Layout li;
+          const uint64_t i_r0 = li.add(c.rows.size()), i_r1 = li.add(c.rows.size()), i_nm = li.add(c.names.size());
+          uint8_t* din; HIP_TRY(ensure_into(ctx->dev[DB_ALNTEXT_IN], li.total(), din));
+          auto up = [&](uint64_t at, const void* src, uint64_t bytes) {
+            return bytes ? hipMemcpyAsync(din + at, src, bytes, hipMemcpyHostToDevice, ctx->stream) : hipSuccess;
+          };
+          HIP_TRY(up(i_r0, job->rows0 + c.rows.lo, c.rows.size()));
+          HIP_TRY(up(i_r1, job->rows1 + c.rows.lo, c.rows.size()));
+          HIP_TRY(up(i_nm, job->names + c.names.lo, c.names.size()));
+          a.rows0 = din + i_r0; a.rows1 = din + i_r1; a.names = din + i_nm;
+          if (payload) {
+            uint8_t* dout; HIP_TRY(ensure_into(ctx->dev[DB_ALNTEXT_OUT], c.text.size() + 16, dout));
+            a.text = dout;
+          }
+          d_text = a.text;
+        } else {
+          a.rows0 = job->rows0; a.rows1 = job->rows1; a.names = job->names;
+          a.text = out->text;
+        }
+        int rc;
+        if (ctx->timing && (rc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, moved))) return rc;
+        const dim3 block(64 * kAlnWaves), tgrid((a.ntiles + kAlnWaves - 1) / kAlnWaves), sgrid((m + kAlnWaves - 1) / kAlnWaves);
+        if (a.ncoltiles) {
+          hipLaunchKernelGGL(alntext_letters_kernel, dim3((a.ncoltiles + kAlnWaves - 1) / kAlnWaves), block, 0, ctx->stream, a);
+          HIP_TRY(hipGetLastError());
+        }
+        if (a.ntiles) {
+          hipLaunchKernelGGL(alntext_count_kernel, tgrid, block, 0, ctx->stream, a);
+          HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(alntext_scan_kernel, sgrid, block, 0, ctx->stream, a);
+        HIP_TRY(hipGetLastError());
+        if (payload && a.ntiles) {
+          hipLaunchKernelGGL(alntext_emit_kernel, tgrid, block, 0, ctx->stream, a);
+          HIP_TRY(hipGetLastError());
+        }
+        return timing_end(ctx);
+      },
+      [&](uint32_t t) {
+        out->status[t] = f.res[t].status;
+        out->text_len[t] = f.res[t].text_len;
+        if (f.res[t].status == TRACYHIP_ALNTEXT_DEFERRED) ctx->alntext_stats.alntext_deferred += 1;
+        if (f.res[t].status == TRACYHIP_ALNTEXT_TOO_SMALL) ctx->alntext_stats.alntext_too_small += 1;
+      },
+      [&](const AlnChunk& c) {
+        RunMerger<1, CopyBackRun<1>> rt{{1u}, {ctx, {d_text}, {out->text}}};
+        for (uint32_t t = c.t0; t < c.t1; ++t)
+          if (f.res[t].status == TRACYHIP_ALNTEXT_OK) HIP_TRY(rt.add(f.meta[t].text_off, out->text_offset[t], f.res[t].text_len));
+        HIP_TRY(rt.flush());
+        return TRACYHIP_OK;
+      });
 }
 
 int tracyhip_render_alignments_async(tracyhip_ctx* ctx, const tracyhip_alntext_job* job, int mem, const tracyhip_alntext_result* out) {
-  if (!ctx || !job || !out) return set_error(TRACYHIP_ERR_ARG, "null context / job / result");
-  const tracyhip_alntext_job j = *job;
-  const tracyhip_alntext_result o = *out;
-  return async_submit(ctx, [=]() { return tracyhip_render_alignments(ctx, &j, mem, &o); });
+  return async_twin(tracyhip_render_alignments, ctx, job, mem, out);
 }
 
 int tracyhip_reference_slices_validate(const tracyhip_slices_job* job, int mem, const uint8_t* out, const uint64_t* out_offset) {

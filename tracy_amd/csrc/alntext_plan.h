@@ -86,33 +86,21 @@ inline uint64_t alntext_chunk_bytes(const AlnChunk& c, bool host, bool payload) 
 inline bool alntext_cut_chunks(const tracyhip_alntext_job* job, const tracyhip_alntext_result* out, bool host, uint64_t limit,
                                std::vector<AlnChunk>& chunks, uint32_t* bad_t) {
   const bool payload = out->text != nullptr;
-  chunks.clear();
-  AlnChunk cur;
-  for (uint32_t t = 0; t < job->n; ++t) {
-    if (!offset_fits(job->rows_offset[t], job->cols[t]) || !offset_fits(alntext_name0_off(job, t), alntext_name0_len(job, t)) ||
-        !offset_fits(job->name1_offset[t], job->name1_len[t]) || (payload && !offset_fits(out->text_offset[t], out->text_cap[t]))) {
-      *bad_t = t;
-      return false;
-    }
-    AlnChunk nx = cur;
-    nx.t1 = t + 1;
-    nx.rows.add(job->rows_offset[t], job->cols[t]);
-    nx.names.add(alntext_name0_off(job, t), alntext_name0_len(job, t));
-    nx.names.add(job->name1_offset[t], job->name1_len[t]);
-    if (payload) nx.text.add(out->text_offset[t], out->text_cap[t]);
-    nx.tiles += alntext_tiles(job, t);
-    nx.coltiles += alntext_coltiles(job, t);
-    if (cur.t1 > cur.t0 && (alntext_chunk_bytes(nx, host, payload) > limit || nx.tiles > kAlnMaxChunkTiles)) {
-      chunks.push_back(cur);
-      cur = AlnChunk{};
-      cur.t0 = t;
-      --t;  // the alignment opens the next chunk (alone it goes whatever it takes)
-      continue;
-    }
-    cur = nx;
-  }
-  if (cur.t1 > cur.t0) chunks.push_back(cur);
-  return true;
+  return cut_spans(
+      job->n, limit, chunks, bad_t,
+      [=](uint32_t t) {
+        return offset_fits(job->rows_offset[t], job->cols[t]) && offset_fits(alntext_name0_off(job, t), alntext_name0_len(job, t)) &&
+               offset_fits(job->name1_offset[t], job->name1_len[t]) && (!payload || offset_fits(out->text_offset[t], out->text_cap[t]));
+      },
+      [=](AlnChunk& c, uint32_t t) {
+        c.rows.add(job->rows_offset[t], job->cols[t]);
+        c.names.add(alntext_name0_off(job, t), alntext_name0_len(job, t));
+        c.names.add(job->name1_offset[t], job->name1_len[t]);
+        if (payload) c.text.add(out->text_offset[t], out->text_cap[t]);
+        c.tiles += alntext_tiles(job, t);
+        c.coltiles += alntext_coltiles(job, t);
+      },
+      [=](const AlnChunk& c, uint64_t lim) { return alntext_chunk_bytes(c, host, payload) > lim || c.tiles > kAlnMaxChunkTiles; });
 }
 
 // the descriptor of alignment t of chunk c: host payloads are staged from each span's first byte, device payloads used in place

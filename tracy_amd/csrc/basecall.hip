@@ -56,7 +56,8 @@ int tracyhip_basecall_validate(const tracyhip_basecall_job* job, int mem, const 
 // Host payloads go through in chunks of consecutive traces whose staged chromatogram fits the workspace limit
 // (tracyhip_set_workspace_limit; 256 MB without one) -- the results are the same for any limit -- device payloads in one.  A trace
 // whose signal_offset + 4 * nsamples or pos_offset + npos leaves 64 bits is refused with TRACYHIP_ERR_RANGE before the first launch:
-// nothing is written.
+// nothing is written.  (The cut is ragged_plan.h's cut_spans.  The frame is not two_pass.h's: this call keeps its descriptors per chunk and
+// waits per chunk with device payloads too, so folding it in would change its stream order.)
 int tracyhip_basecall_traces(tracyhip_ctx* ctx, const tracyhip_basecall_job* job, int mem, const tracyhip_basecall_result* out) {
   int rc = validate(job, mem, out);  // before any device call
   if (rc != TRACYHIP_OK) return rc;
@@ -150,10 +151,7 @@ int tracyhip_basecall_traces(tracyhip_ctx* ctx, const tracyhip_basecall_job* job
 }
 
 int tracyhip_basecall_traces_async(tracyhip_ctx* ctx, const tracyhip_basecall_job* job, int mem, const tracyhip_basecall_result* out) {
-  if (!ctx || !job || !out) return set_error(TRACYHIP_ERR_ARG, "null context / job / result");
-  const tracyhip_basecall_job j = *job;
-  const tracyhip_basecall_result o = *out;
-  return async_submit(ctx, [=]() { return tracyhip_basecall_traces(ctx, &j, mem, &o); });
+  return async_twin(tracyhip_basecall_traces, ctx, job, mem, out);
 }
 
 }  // extern "C"

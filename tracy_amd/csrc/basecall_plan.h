@@ -45,27 +45,14 @@ inline uint64_t basecall_scratch_words(const tracyhip_basecall_job* job, uint32_
 // Host payloads: a chunk closes when the chromatogram span it stages would exceed `limit` bytes (a trace alone goes whatever it takes).
 // Device payloads: one chunk.  false: an offset + length of trace *bad_t leaves 64 bits
 inline bool basecall_cut_chunks(const tracyhip_basecall_job* job, bool host, uint64_t limit, std::vector<BasecallChunk>& chunks, uint32_t* bad_t) {
-  chunks.clear();
-  BasecallChunk cur;
-  for (uint32_t t = 0; t < job->ntraces; ++t) {
-    if (!offset_fits(job->signal_offset[t], 4ull * job->nsamples[t]) || !offset_fits(job->pos_offset[t], job->npos[t])) {
-      *bad_t = t;
-      return false;
-    }
-    const Span sig = cur.sig.with(job->signal_offset[t], 4ull * job->nsamples[t]);
-    if (host && cur.t1 > cur.t0 && sig.size() * job->sample_bytes > limit) {
-      chunks.push_back(cur);
-      cur = BasecallChunk{};
-      cur.t0 = t;
-      --t;  // the trace opens the next chunk
-      continue;
-    }
-    cur.t1 = t + 1;
-    cur.sig = sig;
-    cur.pos.add(job->pos_offset[t], job->npos[t]);
-  }
-  if (cur.t1 > cur.t0) chunks.push_back(cur);
-  return true;
+  return cut_spans(
+      job->ntraces, limit, chunks, bad_t,
+      [=](uint32_t t) { return offset_fits(job->signal_offset[t], 4ull * job->nsamples[t]) && offset_fits(job->pos_offset[t], job->npos[t]); },
+      [=](BasecallChunk& c, uint32_t t) {
+        c.sig.add(job->signal_offset[t], 4ull * job->nsamples[t]);
+        c.pos.add(job->pos_offset[t], job->npos[t]);
+      },
+      [=](const BasecallChunk& c, uint64_t lim) { return host && c.sig.size() * job->sample_bytes > lim; });
 }
 
 // the descriptor of trace t of chunk c: host payloads are staged from each span's first element, device payloads used in place

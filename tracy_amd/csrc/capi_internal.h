@@ -459,6 +459,22 @@ struct CopyBackRun {
 };
 int async_submit(tracyhip_ctx* ctx, std::function<int()> fn);  // queue a call on the context's worker thread
 int async_drain(tracyhip_ctx* ctx);                           // wait for the queue; returns (and clears) the first error
+// the _async twin of a batch call fn(ctx, job, mem, out): job and result structs are copied now (the arrays they point to stay the
+// caller's until the queue has drained), the call is queued
+template <class Job, class Res>
+int async_twin(int (*fn)(tracyhip_ctx*, const Job*, int, const Res*), tracyhip_ctx* ctx, const Job* job, int mem, const Res* out) {
+  if (!ctx || !job || !out) return set_error(TRACYHIP_ERR_ARG, "null context / job / result");
+  const Job j = *job;
+  const Res o = *out;
+  return async_submit(ctx, [=]() { return fn(ctx, &j, mem, &o); });
+}
+// a tracyhip_last_*_stats getter over the counters a call keeps in its context
+template <class Stats>
+int last_stats(tracyhip_ctx* ctx, Stats tracyhip_ctx::*stats, Stats* out) {
+  if (!ctx || !out) return set_error(TRACYHIP_ERR_ARG, "null context / out");
+  *out = ctx->*stats;
+  return TRACYHIP_OK;
+}
 // Staging of a caller's array.  MEM_DEVICE: it is used in place.  MEM_HOST: it goes through a grow-only buffer of the context.
 // stage_in: a read-only input, uploaded (zero bytes: the caller's pointer, nothing allocated).
 // stage_out: a result array, optionally uploaded first (zero bytes: one byte allocated, so the pointer is a device pointer);

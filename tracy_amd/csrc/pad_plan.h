@@ -70,34 +70,21 @@ inline uint64_t pad_chunk_bytes(const PadChunk& c, uint32_t sb, bool host, bool 
 inline bool pad_cut_chunks(const tracyhip_pad_job* job, const tracyhip_pad_result* out, bool host, uint64_t limit, std::vector<PadChunk>& chunks,
                            uint32_t* bad_t) {
   const bool samples = pad_wants_samples(out), calls = pad_wants_calls(out), payload = samples || calls;
-  chunks.clear();
-  PadChunk cur;
-  for (uint32_t t = 0; t < job->ntraces; ++t) {
-    const uint64_t ns = job->nsamples[t];
-    if (!offset_fits(job->bc_offset[t], job->bc_len[t]) || !offset_fits(job->row_offset[t], job->row_len[t]) ||
-        (samples && !offset_fits(job->signal_offset[t], 4 * ns)) || (samples && !offset_fits(out->sample_offset[t], 4ull * out->sample_cap[t])) ||
-        (calls && !offset_fits(out->call_offset[t], out->call_cap[t]))) {
-      *bad_t = t;
-      return false;
-    }
-    PadChunk nx = cur;
-    nx.t1 = t + 1;
-    nx.bc.add(job->bc_offset[t], job->bc_len[t]);
-    nx.row.add(job->row_offset[t], job->row_len[t]);
-    if (samples) { nx.sig.add(job->signal_offset[t], 4 * ns); nx.osig.add(out->sample_offset[t], 4ull * out->sample_cap[t]); }
-    if (calls) nx.ocall.add(out->call_offset[t], out->call_cap[t]);
-    if (payload) nx.scratch_words += pad_scratch_words(job, t);
-    if (cur.t1 > cur.t0 && pad_chunk_bytes(nx, job->sample_bytes, host, samples, calls) > limit) {
-      chunks.push_back(cur);
-      cur = PadChunk{};
-      cur.t0 = t;
-      --t;  // the trace opens the next chunk (alone it goes whatever it takes)
-      continue;
-    }
-    cur = nx;
-  }
-  if (cur.t1 > cur.t0) chunks.push_back(cur);
-  return true;
+  return cut_spans(
+      job->ntraces, limit, chunks, bad_t,
+      [=](uint32_t t) {
+        return offset_fits(job->bc_offset[t], job->bc_len[t]) && offset_fits(job->row_offset[t], job->row_len[t]) &&
+               (!samples || (offset_fits(job->signal_offset[t], 4ull * job->nsamples[t]) && offset_fits(out->sample_offset[t], 4ull * out->sample_cap[t]))) &&
+               (!calls || offset_fits(out->call_offset[t], out->call_cap[t]));
+      },
+      [=](PadChunk& c, uint32_t t) {
+        c.bc.add(job->bc_offset[t], job->bc_len[t]);
+        c.row.add(job->row_offset[t], job->row_len[t]);
+        if (samples) { c.sig.add(job->signal_offset[t], 4ull * job->nsamples[t]); c.osig.add(out->sample_offset[t], 4ull * out->sample_cap[t]); }
+        if (calls) c.ocall.add(out->call_offset[t], out->call_cap[t]);
+        if (payload) c.scratch_words += pad_scratch_words(job, t);
+      },
+      [=](const PadChunk& c, uint64_t lim) { return pad_chunk_bytes(c, job->sample_bytes, host, samples, calls) > lim; });
 }
 
 // the descriptor of trace t of chunk c: host payloads are staged from each span's first element, device payloads used in place

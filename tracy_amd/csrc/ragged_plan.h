@@ -1,13 +1,19 @@
-// ragged_plan.h -- the HIP-free pieces of a batch call over ragged traces with host payloads (basecall_plan.h, pad_plan.h and their .hip
-// files): the span of an array that a chunk of consecutive traces touches, the test that an offset + length stays within 64 bits, the
-// layout of a staging buffer, and the merger of the copies that bring each trace's reported entries back.  tests/cpp/basecall_plan.cpp
-// and tests/cpp/pad_plan.cpp run them under the sanitizers.
+// ragged_plan.h -- the HIP-free pieces of a batch call over ragged items (traces, files, alignments) with host payloads (basecall_plan.h,
+// pad_plan.h, render_plan.h, read_plan.h, alntext_plan.h and their .hip files): the span of an array that a chunk of consecutive items
+// touches, the test that an offset + length stays within 64 bits, the cut of a batch into chunks by their spans, the layout of a staging
+// buffer, and the merger of the copies that bring each item's reported entries back.  tests/cpp/span_cut.cpp and the *_plan.cpp programs
+// beside it run them under the sanitizers.
+//
+// There are two cuts.  chunk_cut.h's ChunkCut adds up a size per item: what a chunk holds is the sum over its items.  cut_spans here is
+// for chunks whose size is that of the spans they touch: items may overlap, repeat or leave gaps in the caller's arrays, so the size of a
+// chunk is not a sum over its items and the open chunk has to be widened and measured anew for every item.
 #ifndef TRACY_AMD_RAGGED_PLAN_H
 #define TRACY_AMD_RAGGED_PLAN_H
 
 #include <algorithm>
 #include <cstdint>
 #include <utility>
+#include <vector>
 
 namespace tracyhip {
 
@@ -20,6 +26,38 @@ struct Span {  // elements [lo, hi) of one array that a chunk touches
 
 // off + len stays within 64 bits
 inline bool offset_fits(uint64_t off, uint64_t len) { return off <= ~0ull - len; }
+
+// The greedy cut of items 0 .. n-1 into chunks of consecutive items.  Chunk: any struct with t0, t1 (items [t0, t1)) that starts empty.
+// fits(t): the offsets + lengths of item t stay within 64 bits; widen(chunk, t): the chunk's spans and counters with item t in it;
+// over(chunk, limit): the chunk is more than one launch may take (its bytes pass the limit, or its tiles a cap).  A chunk closes in front
+// of the item that would put it over; an item alone goes whatever it takes.  false: item *bad_t does not fit (the chunks closed in
+// front of it stay in the list, the open one does not join them).  The cut runs per item in front of every launch: the callers' lambdas
+// capture by value (a few pointers and flags, which then sit in registers across the loop) and the template is `inline`, so that a cut
+// costs what the written-out loops did.
+template <class Chunk, class Fits, class Widen, class Over>
+inline bool cut_spans(uint32_t n, uint64_t limit, std::vector<Chunk>& chunks, uint32_t* bad_t, Fits fits, Widen widen, Over over) {
+  chunks.clear();
+  Chunk cur;
+  for (uint32_t t = 0; t < n; ++t) {
+    if (!fits(t)) {
+      *bad_t = t;
+      return false;
+    }
+    Chunk nx = cur;
+    nx.t1 = t + 1;
+    widen(nx, t);
+    if (cur.t1 > cur.t0 && over(nx, limit)) {
+      chunks.push_back(cur);
+      cur = Chunk{};
+      cur.t0 = t;
+      --t;  // the item opens the next chunk
+      continue;
+    }
+    cur = nx;
+  }
+  if (cur.t1 > cur.t0) chunks.push_back(cur);
+  return true;
+}
 
 // byte offsets of the parts of a staging buffer, each aligned to 16; total() has 16 spare bytes
 struct Layout {

@@ -5,7 +5,7 @@
 // Two launches: one wave per file scans header and directory into a descriptor (the sizes-only form ends here), one wave per (file, tile)
 // writes the payloads.  Four waves per workgroup; the bodies are read_wave.h's (compiled for the host wave by tests/emu/emu_read.cpp), the
 // wave dev_wave.h's SoloWave without LDS of its own.  What is refused before a device is touched, the bound, the cut into chunks and the
-// descriptors are read_plan.h's.
+// descriptors are read_plan.h's; the frame of the call -- chunk loop, descriptor and result buffer, waits -- is two_pass.h's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +17,7 @@
 #include "dev_wave.h"
 #include "read_plan.h"
 #include "read_wave.h"
+#include "two_pass.h"
 
 using namespace tracyhip;
 
@@ -61,128 +62,97 @@ int tracyhip_read_bound(uint32_t file_len, uint32_t* nsamples_max, uint32_t* nca
   return TRACYHIP_OK;
 }
 
-int tracyhip_last_read_stats(tracyhip_ctx* ctx, tracyhip_read_stats* out) {
-  if (!ctx || !out) return set_error(TRACYHIP_ERR_ARG, "null context / out");
-  *out = ctx->read_stats;
-  return TRACYHIP_OK;
-}
+int tracyhip_last_read_stats(tracyhip_ctx* ctx, tracyhip_read_stats* out) { return last_stats(ctx, &tracyhip_ctx::read_stats, out); }
 
 int tracyhip_read_traces(tracyhip_ctx* ctx, const tracyhip_read_job* job, int mem, const tracyhip_read_result* out) {
   int rc = validate(job, mem, out);  // before any device call
   if (rc != TRACYHIP_OK) return rc;
-  const uint32_t n = job->ntraces;
-  if (n == 0) return TRACYHIP_OK;
-  rc = ctx_begin(ctx);
-  if (rc != TRACYHIP_OK) return rc;
-  ctx->stats = tracyhip_call_stats{};
-  ctx->stats.traces = n;
-  ctx->read_stats = tracyhip_read_stats{};
   const bool host = mem == TRACYHIP_MEM_HOST;
+  TwoPass<ReadFile, ReadDesc, ReadChunk> f{ctx, job->ntraces, host};
+  rc = f.begin("tracyhip_read_traces", "trace", DB_READ_FILES, &tracyhip_ctx::read_stats, &tracyhip_read_stats::read_chunks,
+               [&](uint64_t limit, std::vector<ReadChunk>& chunks, uint32_t* bad_t) { return read_cut_chunks(job, out, host, limit, chunks, bad_t); });
+  if (rc != TRACYHIP_OK || f.chunks.empty()) return rc;
   const uint32_t sb = job->sample_bytes;
   const bool samples = read_wants_samples(out), calls = read_wants_calls(out);
-  std::vector<ReadChunk> chunks;
-  uint32_t bad_t = 0;
-  if (!read_cut_chunks(job, out, host, ctx->ws_limit ? ctx->ws_limit : 256ull << 20, chunks, &bad_t))
-    return set_error(TRACYHIP_ERR_RANGE, "tracyhip_read_traces: an offset + length of trace %u leaves 64 bits", bad_t);
-  ctx->read_stats.read_chunks = (uint32_t)chunks.size();
-
-  // descriptors up and results back for the whole batch in one buffer; a chunk launches over its slice
-  const size_t b_out = (sizeof(ReadFile) * n + 15) & ~size_t(15);
-  uint8_t* d0; HIP_TRY(ensure_into(ctx->dev[DB_READ_FILES], b_out + sizeof(ReadDesc) * n, d0));
-  std::vector<ReadFile> meta(n);
-  std::vector<ReadDesc> res(n);
-  auto report = [&](uint32_t t) {
-    const ReadDesc& o = res[t];
-    out->status[t] = o.status; out->format[t] = o.format;
-    out->nsamples[t] = o.nsamples; out->ncalls[t] = o.ncalls;
-    if (o.status == TRACYHIP_READ_DEFERRED) ctx->read_stats.read_deferred += 1;
-    if (o.status == TRACYHIP_READ_TOO_SMALL) ctx->read_stats.read_too_small += 1;
-  };
-  for (const ReadChunk& c : chunks) {
-    const uint32_t m = c.t1 - c.t0;
-    uint32_t tile_first = 0;
-    for (uint32_t t = c.t0; t < c.t1; ++t) {
-      meta[t] = read_file_desc(job, out, c, host, t, tile_first);
-      tile_first += read_file_tiles(job->file_len[t]);
-    }
-    HIP_TRY(hipMemcpyAsync(d0 + sizeof(ReadFile) * c.t0, meta.data() + c.t0, sizeof(ReadFile) * m, hipMemcpyHostToDevice, ctx->stream));
-    ReadArgs a{};
-    a.fl = reinterpret_cast<const ReadFile*>(d0) + c.t0;
-    a.desc = reinterpret_cast<ReadDesc*>(d0 + b_out) + c.t0;
-    a.ntraces = m; a.ntiles = tile_first; a.sample_bytes = sb;
-    uint8_t* const want_byte[3] = {out->basecalls1, out->basecalls2, out->qual};
-    uint64_t o_sig = 0, o_pos = 0, o_byte[3] = {0, 0, 0};
-    if (host) {
-      uint8_t* din; HIP_TRY(ensure_into(ctx->dev[DB_READ_IN], c.in.size() + 16, din));
-      if (c.in.size()) HIP_TRY(hipMemcpyAsync(din, job->bytes + c.in.lo, c.in.size(), hipMemcpyHostToDevice, ctx->stream));
-      a.bytes = din;
-      Layout lo;
-      o_sig = lo.add(samples ? c.osig.size() * sb : 0);
-      o_pos = lo.add(out->basecallpos ? c.ocall.size() * 4 : 0);
-      for (int k = 0; k < 3; ++k) o_byte[k] = lo.add(want_byte[k] ? c.ocall.size() : 0);
-      uint8_t* dout; HIP_TRY(ensure_into(ctx->dev[DB_READ_OUT], lo.total(), dout));
-      if (samples) a.o_signal = dout + o_sig;
-      if (out->basecallpos) a.o_pos = reinterpret_cast<int32_t*>(dout + o_pos);
-      if (want_byte[0]) a.o_b1 = dout + o_byte[0];
-      if (want_byte[1]) a.o_b2 = dout + o_byte[1];
-      if (want_byte[2]) a.o_qual = dout + o_byte[2];
-    } else {
-      a.bytes = job->bytes;
-      a.o_signal = out->signal; a.o_pos = out->basecallpos;
-      a.o_b1 = out->basecalls1; a.o_b2 = out->basecalls2; a.o_qual = out->qual;
-    }
-    if (ctx->timing) {
-      uint64_t moved = 0;  // (the images read once; what is written is about as much again at 16 bits, twice at 32)
-      for (uint32_t t = c.t0; t < c.t1; ++t) moved += (uint64_t)job->file_len[t] * (samples ? 1 + sb / 2 : 1);
-      if ((rc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, moved))) return rc;
-    }
-    const dim3 block(64 * kReadWaves), sgrid((m + kReadWaves - 1) / kReadWaves), tgrid((a.ntiles + kReadWaves - 1) / kReadWaves);
-    hipLaunchKernelGGL(read_scan_kernel, sgrid, block, 0, ctx->stream, a);
-    HIP_TRY(hipGetLastError());
-    if (samples || calls) {
-      if (sb == 2) hipLaunchKernelGGL(read_emit_kernel<true>, tgrid, block, 0, ctx->stream, a);
-      else hipLaunchKernelGGL(read_emit_kernel<false>, tgrid, block, 0, ctx->stream, a);
-      HIP_TRY(hipGetLastError());
-    }
-    if ((rc = timing_end(ctx))) return rc;
-    if (!host) continue;  // device payloads: the results of all chunks come back behind the last launch
-    HIP_TRY(hipMemcpyAsync(res.data() + c.t0, a.desc, sizeof(ReadDesc) * m, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx_sync(ctx));
-    timing_collect(ctx);
-    // exactly what was reported goes back, straight into the caller's arrays; regions that follow each other on both sides travel as one copy
-    const uint8_t* dout = static_cast<const uint8_t*>(ctx->dev[DB_READ_OUT].p);
-    RunMerger<1, CopyBackRun<1>> rs{{samples ? sb : 0}, {ctx, {dout + o_sig}, {static_cast<uint8_t*>(out->signal)}}};
-    RunMerger<4, CopyBackRun<4>> rcall{{out->basecallpos ? 4u : 0u}, {ctx, {dout + o_pos}, {reinterpret_cast<uint8_t*>(out->basecallpos)}}};
-    for (int k = 0; k < 3; ++k) {
-      rcall.width[1 + k] = want_byte[k] ? 1 : 0;
-      rcall.emit.src[1 + k] = dout + o_byte[k]; rcall.emit.dst[1 + k] = want_byte[k];
-    }
-    for (uint32_t t = c.t0; t < c.t1; ++t) {
-      report(t);
-      if (res[t].status != TRACYHIP_READ_OK) continue;
-      if (samples) HIP_TRY(rs.add(meta[t].out_sig_off, out->sample_offset[t], 4ull * res[t].nsamples));
-      if (calls) HIP_TRY(rcall.add(meta[t].out_call_off, out->call_offset[t], res[t].ncalls));
-    }
-    if (samples || calls) {
-      HIP_TRY(rs.flush());
-      HIP_TRY(rcall.flush());
-      HIP_TRY(ctx_sync(ctx));
-    }
-  }
-  if (!host) {
-    HIP_TRY(hipMemcpyAsync(res.data(), d0 + b_out, sizeof(ReadDesc) * n, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx_sync(ctx));  // the one synchronisation of a device call: the sizes are what the caller builds the next job by
-    timing_collect(ctx);
-    for (uint32_t t = 0; t < n; ++t) report(t);
-  }
-  return TRACYHIP_OK;
+  uint8_t* const want_byte[3] = {out->basecalls1, out->basecalls2, out->qual};
+  uint64_t o_sig = 0, o_pos = 0, o_byte[3] = {0, 0, 0};  // the staged results of a host chunk
+  return f.run(
+      samples || calls,
+      [&](const ReadChunk& c) {
+        const uint32_t m = c.t1 - c.t0;
+        uint32_t tile_first = 0;
+        for (uint32_t t = c.t0; t < c.t1; ++t) {
+          f.meta[t] = read_file_desc(job, out, c, host, t, tile_first);
+          tile_first += read_file_tiles(job->file_len[t]);
+        }
+        HIP_TRY(f.upload(c));
+        ReadArgs a{};
+        a.fl = f.desc_ptr(c);
+        a.desc = f.out_ptr(c);
+        a.ntraces = m; a.ntiles = tile_first; a.sample_bytes = sb;
+        if (host) {
+          uint8_t* din; HIP_TRY(ensure_into(ctx->dev[DB_READ_IN], c.in.size() + 16, din));
+          if (c.in.size()) HIP_TRY(hipMemcpyAsync(din, job->bytes + c.in.lo, c.in.size(), hipMemcpyHostToDevice, ctx->stream));
+          a.bytes = din;
+          Layout lo;
+          o_sig = lo.add(samples ? c.osig.size() * sb : 0);
+          o_pos = lo.add(out->basecallpos ? c.ocall.size() * 4 : 0);
+          for (int k = 0; k < 3; ++k) o_byte[k] = lo.add(want_byte[k] ? c.ocall.size() : 0);
+          uint8_t* dout; HIP_TRY(ensure_into(ctx->dev[DB_READ_OUT], lo.total(), dout));
+          if (samples) a.o_signal = dout + o_sig;
+          if (out->basecallpos) a.o_pos = reinterpret_cast<int32_t*>(dout + o_pos);
+          if (want_byte[0]) a.o_b1 = dout + o_byte[0];
+          if (want_byte[1]) a.o_b2 = dout + o_byte[1];
+          if (want_byte[2]) a.o_qual = dout + o_byte[2];
+        } else {
+          a.bytes = job->bytes;
+          a.o_signal = out->signal; a.o_pos = out->basecallpos;
+          a.o_b1 = out->basecalls1; a.o_b2 = out->basecalls2; a.o_qual = out->qual;
+        }
+        int rc;
+        if (ctx->timing) {
+          uint64_t moved = 0;  // (the images read once; what is written is about as much again at 16 bits, twice at 32)
+          for (uint32_t t = c.t0; t < c.t1; ++t) moved += (uint64_t)job->file_len[t] * (samples ? 1 + sb / 2 : 1);
+          if ((rc = timing_begin(ctx, TRACYHIP_TIMER_MISC, 0, moved))) return rc;
+        }
+        const dim3 block(64 * kReadWaves), sgrid((m + kReadWaves - 1) / kReadWaves), tgrid((a.ntiles + kReadWaves - 1) / kReadWaves);
+        hipLaunchKernelGGL(read_scan_kernel, sgrid, block, 0, ctx->stream, a);
+        HIP_TRY(hipGetLastError());
+        if (samples || calls) {
+          if (sb == 2) hipLaunchKernelGGL(read_emit_kernel<true>, tgrid, block, 0, ctx->stream, a);
+          else hipLaunchKernelGGL(read_emit_kernel<false>, tgrid, block, 0, ctx->stream, a);
+          HIP_TRY(hipGetLastError());
+        }
+        return timing_end(ctx);
+      },
+      [&](uint32_t t) {
+        const ReadDesc& o = f.res[t];
+        out->status[t] = o.status; out->format[t] = o.format;
+        out->nsamples[t] = o.nsamples; out->ncalls[t] = o.ncalls;
+        if (o.status == TRACYHIP_READ_DEFERRED) ctx->read_stats.read_deferred += 1;
+        if (o.status == TRACYHIP_READ_TOO_SMALL) ctx->read_stats.read_too_small += 1;
+      },
+      [&](const ReadChunk& c) {
+        const uint8_t* dout = static_cast<const uint8_t*>(ctx->dev[DB_READ_OUT].p);
+        RunMerger<1, CopyBackRun<1>> rs{{samples ? sb : 0}, {ctx, {dout + o_sig}, {static_cast<uint8_t*>(out->signal)}}};
+        RunMerger<4, CopyBackRun<4>> rcall{{out->basecallpos ? 4u : 0u}, {ctx, {dout + o_pos}, {reinterpret_cast<uint8_t*>(out->basecallpos)}}};
+        for (int k = 0; k < 3; ++k) {
+          rcall.width[1 + k] = want_byte[k] ? 1 : 0;
+          rcall.emit.src[1 + k] = dout + o_byte[k]; rcall.emit.dst[1 + k] = want_byte[k];
+        }
+        for (uint32_t t = c.t0; t < c.t1; ++t) {
+          if (f.res[t].status != TRACYHIP_READ_OK) continue;
+          if (samples) HIP_TRY(rs.add(f.meta[t].out_sig_off, out->sample_offset[t], 4ull * f.res[t].nsamples));
+          if (calls) HIP_TRY(rcall.add(f.meta[t].out_call_off, out->call_offset[t], f.res[t].ncalls));
+        }
+        HIP_TRY(rs.flush());
+        HIP_TRY(rcall.flush());
+        return TRACYHIP_OK;
+      });
 }
 
 int tracyhip_read_traces_async(tracyhip_ctx* ctx, const tracyhip_read_job* job, int mem, const tracyhip_read_result* out) {
-  if (!ctx || !job || !out) return set_error(TRACYHIP_ERR_ARG, "null context / job / result");
-  const tracyhip_read_job j = *job;
-  const tracyhip_read_result o = *out;
-  return async_submit(ctx, [=]() { return tracyhip_read_traces(ctx, &j, mem, &o); });
+  return async_twin(tracyhip_read_traces, ctx, job, mem, out);
 }
 
 }  // extern "C"

@@ -50,31 +50,19 @@ inline uint64_t read_chunk_bytes(const ReadChunk& c, uint32_t sb, bool host, boo
 inline bool read_cut_chunks(const tracyhip_read_job* job, const tracyhip_read_result* out, bool host, uint64_t limit, std::vector<ReadChunk>& chunks,
                             uint32_t* bad_t) {
   const bool samples = read_wants_samples(out), calls = read_wants_calls(out);
-  chunks.clear();
-  ReadChunk cur;
-  for (uint32_t t = 0; t < job->ntraces; ++t) {
-    if (!offset_fits(job->file_offset[t], job->file_len[t]) || (samples && !offset_fits(out->sample_offset[t], 4ull * out->sample_cap[t])) ||
-        (calls && !offset_fits(out->call_offset[t], out->call_cap[t]))) {
-      *bad_t = t;
-      return false;
-    }
-    ReadChunk nx = cur;
-    nx.t1 = t + 1;
-    nx.in.add(job->file_offset[t], job->file_len[t]);
-    if (samples) nx.osig.add(out->sample_offset[t], 4ull * out->sample_cap[t]);
-    if (calls) nx.ocall.add(out->call_offset[t], out->call_cap[t]);
-    nx.tiles += read_file_tiles(job->file_len[t]);
-    if (cur.t1 > cur.t0 && (read_chunk_bytes(nx, job->sample_bytes, host, calls) > limit || nx.tiles > 0x7fffffffull)) {
-      chunks.push_back(cur);
-      cur = ReadChunk{};
-      cur.t0 = t;
-      --t;  // the file opens the next chunk (alone it goes whatever it takes)
-      continue;
-    }
-    cur = nx;
-  }
-  if (cur.t1 > cur.t0) chunks.push_back(cur);
-  return true;
+  return cut_spans(
+      job->ntraces, limit, chunks, bad_t,
+      [=](uint32_t t) {
+        return offset_fits(job->file_offset[t], job->file_len[t]) && (!samples || offset_fits(out->sample_offset[t], 4ull * out->sample_cap[t])) &&
+               (!calls || offset_fits(out->call_offset[t], out->call_cap[t]));
+      },
+      [=](ReadChunk& c, uint32_t t) {
+        c.in.add(job->file_offset[t], job->file_len[t]);
+        if (samples) c.osig.add(out->sample_offset[t], 4ull * out->sample_cap[t]);
+        if (calls) c.ocall.add(out->call_offset[t], out->call_cap[t]);
+        c.tiles += read_file_tiles(job->file_len[t]);
+      },
+      [=](const ReadChunk& c, uint64_t lim) { return read_chunk_bytes(c, job->sample_bytes, host, calls) > lim || c.tiles > 0x7fffffffull; });
 }
 
 // the descriptor of file t of chunk c: host payloads are staged from each span's first element, device payloads used in place

@@ -75,32 +75,21 @@ inline uint64_t render_chunk_bytes(const RenderChunk& c, uint32_t sb, bool host,
 inline bool render_cut_chunks(const tracyhip_render_job* job, const tracyhip_render_result* out, bool host, uint64_t limit,
                               std::vector<RenderChunk>& chunks, uint32_t* bad_t) {
   const bool payload = out->text != nullptr, consensus = job->form == TRACYHIP_RENDER_TSV;
-  chunks.clear();
-  RenderChunk cur;
-  for (uint32_t t = 0; t < job->ntraces; ++t) {
-    const uint64_t ns = job->nsamples[t];
-    if (!offset_fits(job->signal_offset[t], 4 * ns) || !offset_fits(job->bc_offset[t], job->bc_len[t]) ||
-        (payload && !offset_fits(out->text_offset[t], out->text_cap[t]))) {
-      *bad_t = t;
-      return false;
-    }
-    RenderChunk nx = cur;
-    nx.t1 = t + 1;
-    nx.sig.add(job->signal_offset[t], 4 * ns);
-    nx.bc.add(job->bc_offset[t], job->bc_len[t]);
-    if (payload) nx.text.add(out->text_offset[t], out->text_cap[t]);
-    nx.tiles += render_trace_tiles(job, t);
-    if (cur.t1 > cur.t0 && (render_chunk_bytes(nx, job->sample_bytes, host, consensus, payload) > limit || nx.tiles > kRenderMaxChunkTiles)) {
-      chunks.push_back(cur);
-      cur = RenderChunk{};
-      cur.t0 = t;
-      --t;  // the trace opens the next chunk (alone it goes whatever it takes)
-      continue;
-    }
-    cur = nx;
-  }
-  if (cur.t1 > cur.t0) chunks.push_back(cur);
-  return true;
+  return cut_spans(
+      job->ntraces, limit, chunks, bad_t,
+      [=](uint32_t t) {
+        return offset_fits(job->signal_offset[t], 4ull * job->nsamples[t]) && offset_fits(job->bc_offset[t], job->bc_len[t]) &&
+               (!payload || offset_fits(out->text_offset[t], out->text_cap[t]));
+      },
+      [=](RenderChunk& c, uint32_t t) {
+        c.sig.add(job->signal_offset[t], 4ull * job->nsamples[t]);
+        c.bc.add(job->bc_offset[t], job->bc_len[t]);
+        if (payload) c.text.add(out->text_offset[t], out->text_cap[t]);
+        c.tiles += render_trace_tiles(job, t);
+      },
+      [=](const RenderChunk& c, uint64_t lim) {
+        return render_chunk_bytes(c, job->sample_bytes, host, consensus, payload) > lim || c.tiles > kRenderMaxChunkTiles;
+      });
 }
 
 // the descriptor of trace t of chunk c: host payloads are staged from each span's first element, device payloads used in place
