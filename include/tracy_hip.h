@@ -914,6 +914,90 @@ typedef struct {
 } tracyhip_alntext_stats;
 int tracyhip_last_alntext_stats(tracyhip_ctx* ctx, tracyhip_alntext_stats* out);
 
+/* ---- the text `tracy decompose` prints from the decompose results themselves, byte for byte (tracy_amd/host indigo_out.hpp
+ * writeDecomposition, traceAlleleAlignJsonTail, vcfRecordLines) -- where tracyhip_render_traces' JSON form and tracyhip_render_alignments
+ * with key 3 stop -------------------------------------------------------------------------------------------------------------
+ * The results are read where they lie: dcp_indel / dcp_err / dcp_offset of tracyhip_decompose_result, rows0 / rows1 of
+ * tracyhip_alignment_rows for the three allele alignments, bcpos / estqual of the basecalls and the four arrays of
+ * tracyhip_variants_result are taken as they stand.
+ *   DECOMP  "indel\tdecomp\n", then one line indel "\t" err "\n" per table row (reads the table alone).
+ *   JSON    from the ",\n\"chartConfig\": " behind the trace body through the final "}\n}\n": the viewport of the breakpoint, both allele
+ *           blocks, the fractions, the alt-vs-alt rows, hetindel, the decomposition arrays, the variant rows and their x ranges.
+ *   VCF     one record line per variant (no header: the date and the contig list are the caller's).  qual is 0 when the alt holds n / N;
+ *           the GQ field carries estQual all the same.  Reads the basecalls, the variants and chr1.
+ * Names are the caller's bytes, printed as they are (never escaped): chr1 / chr2 (rs.chr of the two alleles; v.chr of every variant
+ * is chr1) and the two allelic fractions as the caller has printed them -- no floating-point number is formatted here.  v.id is ".".
+ * trim_left / trim_right and qual_cut are truncated to 16 bits, as the writers' configuration holds them.  Computed here:
+ * xWindowViewport of the breakpoint and of every variant, variantCallIndex from basenum (the records' call_index is not read),
+ * variantType, the genotype words, LowQual / PASS, basepos, bcPos[q] + 1, every separator and the forms of empty lists.
+ * A trace whose var_flags bit 0 is set, or whose decompose status is not 0, is the caller's to leave out of the batch: neither is
+ * read here.  A dcp_rows, cols or var_n of 0 is legal and prints the empty forms.
+ * DEFERRED (status and text_len = 0 are written, nothing else) -- JSON and VCF: a chr name longer than 65535 bytes (JSON: a fraction
+ * too), bc_len = 0 (or beyond 2^31 - 1), var_n > max_variants, a variant whose call index is at or beyond bc_len (the host writer indexes unchecked) or
+ * whose ref or alt range leaves its text region; JSON alone: trim_left + breakpoint at or beyond bc_len, cols > 2^22. */
+#define TRACYHIP_DCPTEXT_DECOMP 0
+#define TRACYHIP_DCPTEXT_JSON   1
+#define TRACYHIP_DCPTEXT_VCF    2
+#define TRACYHIP_DCPTEXT_OK 0
+#define TRACYHIP_DCPTEXT_DEFERRED 1
+#define TRACYHIP_DCPTEXT_TOO_SMALL 2 /* text_cap is too small: text_len is reported, no text is written */
+typedef struct {
+  uint32_t n, form;
+  uint32_t qual_cut;              /* JSON, VCF */
+  const int32_t *dcp_indel, *dcp_err; /* payload (DECOMP, JSON): trace t owns dcp_rows[t] entries from dcp_offset[t] on */
+  const uint64_t* dcp_offset;     /* HOST array */
+  const uint32_t* dcp_rows;       /* HOST array: rows of the table (tracyhip_decomp_status::dcp_n), at most 2^22 */
+  const uint8_t* rows0[3];        /* payload (JSON): allele alignment k = 0, 1, 2 of trace t owns cols[k][t] bytes of rows0[k] and */
+  const uint8_t* rows1[3];        /* of rows1[k] from rows_offset[k][t] on */
+  const uint64_t* rows_offset[3]; /* HOST arrays */
+  const uint32_t* cols[3];        /* HOST arrays */
+  const int32_t* bcpos;           /* payload (JSON, VCF): trace t owns bc_len[t] entries from bc_offset[t] on, here and in estqual */
+  const uint8_t* estqual;
+  const uint64_t* bc_offset;      /* HOST array */
+  const uint32_t* bc_len;         /* HOST array */
+  const tracyhip_variant* var;    /* payload (JSON, VCF): as tracyhip_variants_result holds them */
+  const uint8_t* var_text;
+  const uint32_t* var_n;
+  uint32_t max_variants;          /* 1 .. 1024 */
+  uint32_t max_text;              /* 2 .. 2^19 */
+  const uint32_t* var_index;      /* HOST array or NULL: the place of trace t in var (x max_variants), var_text (x max_text) and var_n; NULL: t.
+                                     A batch that leaves traces of the variants call out says here where the others lie. */
+  const uint32_t* ref_pos[2];     /* HOST arrays (JSON): rs.pos of the two alleles; ref1pos / ref2pos print it + 1 */
+  const uint8_t* forward;         /* HOST array (JSON, VCF): rs.forward */
+  const int32_t* score[3];        /* HOST arrays (JSON) */
+  const uint32_t* breakpoint;     /* HOST array (JSON): bp.breakpoint as the report holds it */
+  const uint8_t* indelshift;      /* HOST array (JSON) */
+  const uint32_t *trim_left, *trim_right; /* HOST arrays (JSON, VCF), per trace */
+  const uint8_t* names;           /* payload (JSON, VCF) */
+  const uint64_t* chr_offset[2];  /* HOST arrays: chr1 (JSON, VCF), chr2 (JSON) */
+  const uint32_t* chr_len[2];
+  const uint64_t* frac_offset[2]; /* HOST arrays (JSON): the printed allele1fraction / allele2fraction */
+  const uint32_t* frac_len[2];
+} tracyhip_dcptext_job;
+typedef tracyhip_render_result tracyhip_dcptext_result; /* status (TRACYHIP_DCPTEXT_*), text_len, text, text_offset, text_cap */
+/* what tracyhip_render_decompositions refuses before it touches a device (none is needed here): NULL job / result / arrays its form reads,
+ * mem, form, misaligned dcp_indel / dcp_err / bcpos / var / var_n, a text without its offsets and capacities (TRACYHIP_ERR_ARG);
+ * max_variants outside 1 .. 1024, max_text outside 2 .. 2^19, a table of more than 2^22 rows (TRACYHIP_ERR_RANGE). */
+int tracyhip_render_decompositions_validate(const tracyhip_dcptext_job* job, int mem, const tracyhip_dcptext_result* out);
+/* Three launches (count the bytes of every tile, scan them per trace, emit); the first two alone in the sizes-only form (text NULL).
+ * Device payloads: ONE host synchronisation per call.  Host payloads are staged in chunks of consecutive traces within the workspace
+ * limit, with a second synchronisation each for the copy back of exactly the bytes that were reported.  The text does not depend on
+ * the limit.  An offset + length that leaves 64 bits is TRACYHIP_ERR_RANGE before any launch. */
+int tracyhip_render_decompositions(tracyhip_ctx* ctx, const tracyhip_dcptext_job* job, int mem, const tracyhip_dcptext_result* out);
+/* the sizes a bound depends on; fields a form does not read are ignored */
+typedef struct {
+  uint32_t dcp_rows, cols[3], chr_len[2], frac_len[2], max_variants, max_text;
+} tracyhip_dcptext_shape;
+/* an upper bound of text_len of a trace of these sizes, whatever its bytes and numbers; needs no device.  0: no such form. */
+uint64_t tracyhip_render_decompositions_bound(uint32_t form, const tracyhip_dcptext_shape* shape);
+/* counters of the last tracyhip_render_decompositions call of a context */
+typedef struct {
+  uint32_t dcptext_chunks;    /* chunks of traces the batch was cut into */
+  uint32_t dcptext_deferred;  /* traces with TRACYHIP_DCPTEXT_DEFERRED */
+  uint32_t dcptext_too_small; /* traces with TRACYHIP_DCPTEXT_TOO_SMALL */
+} tracyhip_dcptext_stats;
+int tracyhip_last_dcptext_stats(tracyhip_ctx* ctx, tracyhip_dcptext_stats* out);
+
 /* ---- the oriented reference slice of a CHAR-reference align job on the device: what the caller of tracyhip_align_traces does on the
  * host today between that call and tracyhip_alignment_rows ----------------------------------------------------------------------
  * Slice i = oriented.substr(slice_begin[i], slice_len[i]) at out + out_offset[i], where oriented is refs[ref_index ? ref_index[i] : i]
@@ -1150,6 +1234,7 @@ int tracyhip_pad_traces_async(tracyhip_ctx* ctx, const tracyhip_pad_job* job, in
 int tracyhip_render_traces_async(tracyhip_ctx* ctx, const tracyhip_render_job* job, int mem, const tracyhip_render_result* out);
 int tracyhip_read_traces_async(tracyhip_ctx* ctx, const tracyhip_read_job* job, int mem, const tracyhip_read_result* out);
 int tracyhip_render_alignments_async(tracyhip_ctx* ctx, const tracyhip_alntext_job* job, int mem, const tracyhip_alntext_result* out);
+int tracyhip_render_decompositions_async(tracyhip_ctx* ctx, const tracyhip_dcptext_job* job, int mem, const tracyhip_dcptext_result* out);
 int tracyhip_reference_slices_async(tracyhip_ctx* ctx, const tracyhip_slices_job* job, int mem, uint8_t* out, const uint64_t* out_offset);
 int tracyhip_assemble_traces_async(tracyhip_ctx* ctx, const tracyhip_assemble_job* job, const tracyhip_params* prm, int mem,
                                    const tracyhip_assemble_result* out);

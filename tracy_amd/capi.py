@@ -1044,6 +1044,13 @@ class DecomposeOutcome(dict):
     Context.decompose_variants"""
     call = None
 
+    def device_tensor(self, key):
+        """result array `key` as a call with device_bc left it on the device: the uint8 tensor the host copy was read from (None for a
+        call with host buffers).  Context.render_decompositions takes the decomposition tables from here."""
+        host = self.call["keep"][10][key]
+        addr = C.addressof(host) if isinstance(host, C.Array) else host.ctypes.data
+        return next((t for t, a, _ in self.call["keep"][8] if a == addr), None)
+
 
 def _decompose_traces(self, profiles, hbc, refs, params, trim_left=50, trim_right=50, maxindel=1000, madc=5, oriented=None,
                       ref_profiles=None, exact_scores=True, peaks_only=False, device_bc=None, ref_index=None):
@@ -1563,10 +1570,10 @@ def _basecall_traces(self, signals, positions=None, sigratio=0.33, trim_stringen
 Context.basecall_traces = _basecall_traces
 
 
-# ---- the frame of the prepared two-pass calls (read, pad, render, render_alignments) -----------------------------------------------------
+# ---- the frame of the prepared two-pass calls (read, pad, render, render_alignments, render_decompositions) -----------------------------
 class _TwoPassCall:
-    """What PreparedRead, PreparedPad, PreparedRender and PreparedAlnText share: a job struct built by the subclass, and a result struct
-    that starts as the sizes-only form (per-item arrays alone) and takes payload arrays with with_capacity().  A subclass sets
+    """What PreparedRead, PreparedPad, PreparedRender, PreparedAlnText and PreparedDcpText share: a job struct built by the subclass, and a
+    result struct that starts as the sizes-only form (per-item arrays alone) and takes payload arrays with with_capacity().  A subclass sets
       _stem      tracyhip_<stem> and tracyhip_<stem>_async are the calls
       _result    the result struct; the element types of its arrays are read from its fields
       _meta      its per-item arrays, which this object owns (self.meta)
@@ -1660,7 +1667,7 @@ class _TwoPassCall:
 
 
 class _TextCall(_TwoPassCall):
-    """the two calls that print: one text buffer, RenderResult, the layout of hostlib.render_alloc"""
+    """the three calls that print: one text buffer, RenderResult, the layout of hostlib.render_alloc"""
     _meta = ("status", "text_len")
     _sizes = ("text_len",)
     _caps = ("text_offset", "text_cap")
@@ -2215,3 +2222,111 @@ def _reference_slices(self, refs, forward, slice_begin, slice_len, ref_index=Non
 
 
 Context.reference_slices = _reference_slices
+
+
+# ---- the text printed from the decompose results on the device (tracyhip_render_decompositions) ------------------------------------------
+DCPTEXT_DECOMP, DCPTEXT_JSON, DCPTEXT_VCF = 0, 1, 2
+DCPTEXT_OK, DCPTEXT_DEFERRED, DCPTEXT_TOO_SMALL = 0, 1, 2
+
+
+class DcpTextJob(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("form", C.c_uint32), ("qual_cut", C.c_uint32), ("dcp_indel", C.c_void_p), ("dcp_err", C.c_void_p),
+                ("dcp_offset", C.POINTER(C.c_uint64)), ("dcp_rows", C.POINTER(C.c_uint32)), ("rows0", C.c_void_p * 3), ("rows1", C.c_void_p * 3),
+                ("rows_offset", C.POINTER(C.c_uint64) * 3), ("cols", C.POINTER(C.c_uint32) * 3), ("bcpos", C.c_void_p), ("estqual", C.c_void_p),
+                ("bc_offset", C.POINTER(C.c_uint64)), ("bc_len", C.POINTER(C.c_uint32)), ("var", C.c_void_p), ("var_text", C.c_void_p),
+                ("var_n", C.c_void_p), ("max_variants", C.c_uint32), ("max_text", C.c_uint32), ("var_index", C.POINTER(C.c_uint32)), ("ref_pos", C.POINTER(C.c_uint32) * 2),
+                ("forward", C.POINTER(C.c_uint8)), ("score", C.POINTER(C.c_int32) * 3), ("breakpoint", C.POINTER(C.c_uint32)),
+                ("indelshift", C.POINTER(C.c_uint8)), ("trim_left", C.POINTER(C.c_uint32)), ("trim_right", C.POINTER(C.c_uint32)),
+                ("names", C.c_void_p), ("chr_offset", C.POINTER(C.c_uint64) * 2), ("chr_len", C.POINTER(C.c_uint32) * 2),
+                ("frac_offset", C.POINTER(C.c_uint64) * 2), ("frac_len", C.POINTER(C.c_uint32) * 2)]
+
+
+class DcpTextShape(C.Structure):
+    _fields_ = [("dcp_rows", C.c_uint32), ("cols", C.c_uint32 * 3), ("chr_len", C.c_uint32 * 2), ("frac_len", C.c_uint32 * 2),
+                ("max_variants", C.c_uint32), ("max_text", C.c_uint32)]
+
+
+class DcpTextStats(C.Structure):
+    """tracyhip_dcptext_stats: the counters of tracyhip_render_decompositions, in a struct of their own as RenderStats"""
+    _fields_ = [("dcptext_chunks", C.c_uint32), ("dcptext_deferred", C.c_uint32), ("dcptext_too_small", C.c_uint32)]
+
+
+def dcptext_bound(form, dcp_rows=0, cols=(0, 0, 0), chr_len=(0, 0), frac_len=(0, 0), max_variants=1, max_text=2):
+    """tracyhip_render_decompositions_bound: an upper bound of text_len for a trace of these sizes; needs no device"""
+    fn = lib().tracyhip_render_decompositions_bound
+    fn.restype = C.c_uint64
+    sh = DcpTextShape(dcp_rows, (C.c_uint32 * 3)(*cols), (C.c_uint32 * 2)(*chr_len), (C.c_uint32 * 2)(*frac_len), max_variants, max_text)
+    return int(fn(C.c_uint32(form), C.byref(sh)))
+
+
+class PreparedDcpText(_TextCall):
+    """job / result structs of tracyhip_render_decompositions.  form: DCPTEXT_DECOMP / DCPTEXT_JSON / DCPTEXT_VCF.  flat: the arrays of
+    hostlib.dcptext_pack (host metadata and host payloads).  device=True uploads the payloads once; device_arrays: torch tensors on the
+    GPU by payload name (hostlib.DCPTEXT_PAYLOADS) that are taken as they stand in place of flat's -- the tables of
+    decompose_traces(device_bc=...), the rows of tracyhip_alignment_rows, the basecalls, the four arrays of a VariantBuffers(device=True);
+    no payload is copied to the host for them, and flat need not hold them.  Everything the structs point to is kept alive by this object.
+
+    The result side starts as the sizes-only form; with_capacity() allocates the text.  sizes(): text_len.  results(): per trace
+    dict(status, text_len, text); deferred traces are printed by the host writers (hostlib.dcptext_batch) and marked deferred=True, except
+    those the writers cannot index either (`unreadable`: status stays DEFERRED)."""
+    _stem, _result, _host, DEFERRED = "render_decompositions", RenderResult, "dcptext", DCPTEXT_DEFERRED
+
+    def __init__(self, form, flat, qual_cut=45, device=False, device_arrays=None):
+        from . import hostlib
+        self.form, self.qual_cut = int(form), int(qual_cut)
+        self.device = device = bool(device or device_arrays)
+        self.flat = f = dict(flat)
+        self.nt = f["nt"]
+        self.d = dict(device_arrays or {})
+        self._flat_dev = hostlib.DCPTEXT_PAYLOADS
+        if device:
+            import torch
+            for k in hostlib.DCPTEXT_PAYLOADS:
+                if k not in self.d:
+                    self.d[k] = torch.from_numpy(np.ascontiguousarray(f[k]).view(np.uint8)).cuda()  # (bytes: the job takes addresses)
+            torch.cuda.synchronize()
+        self.job = hostlib.dcptext_job(f, self.form, self.qual_cut, (lambda k: self.d[k].data_ptr()) if device else (lambda k: f[k].ctypes.data))
+        self.mem = MEM_DEVICE if device else MEM_HOST
+        self._bind(None)
+
+    def bounds(self):
+        """tracyhip_render_decompositions_bound per trace: capacities that need no sizes-only call"""
+        f = self.flat
+        return np.array([dcptext_bound(self.form, int(f["dcp_rows"][t]), [int(f["cols_%d" % k][t]) for k in range(3)],
+                                       [int(f["chr%d_len" % k][t]) for k in (1, 2)], [int(f["frac%d_len" % k][t]) for k in (1, 2)],
+                                       f["max_variants"], f["max_text"]) for t in range(self.nt)], dtype=np.uint64)
+
+    def stats(self, ctx):
+        st = DcpTextStats()
+        _check(lib().tracyhip_last_dcptext_stats(ctx._h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in DcpTextStats._fields_}
+
+    def host_flat(self):
+        f = dict(self.flat)
+        for k, v in self.d.items():
+            h = v.cpu().numpy()
+            f[k] = h.view(VARIANT_DTYPE) if k == "var" else h.view(np.int32) if k in ("dcp_indel", "dcp_err", "bcpos") else \
+                h.view(np.uint32) if k == "var_n" else h
+        return f
+
+    def _host_batch(self, sel):
+        """(the variants of a trace lie at its index: the host prints the batch and the deferred traces are picked)"""
+        from . import hostlib
+        res = hostlib.dcptext_batch(self.host_flat(), self.form, self.qual_cut)
+        return [res[t] for t in sel]
+
+    def _filled(self, mine, r):
+        return dict(r, deferred=True) if r["status"] == 0 else dict(mine, unreadable=True)
+
+
+def _render_decompositions(self, form, flat, qual_cut=45, device=False, device_arrays=None, asynchronous=False):
+    """tracyhip_render_decompositions: the sizes-only call, a buffer of exactly those sizes, the call.  Host arrays with device=False:
+    returns the per-trace results (PreparedDcpText.results: deferred traces are filled in by the host batch).  device=True or
+    device_arrays: returns the PreparedDcpText holding the text as a torch tensor on the GPU.  asynchronous: the second call is queued
+    (tracyhip_render_decompositions_async); results are final after Context.synchronize()."""
+    p = PreparedDcpText(form, flat, qual_cut, device, device_arrays)
+    p.with_capacity(p.sizes(self)).run(self, asynchronous)
+    return p if (p.device or asynchronous) else p.results()
+
+
+Context.render_decompositions = _render_decompositions

@@ -211,7 +211,13 @@ enum CtxDev : int {
                      // (alntext_letters_kernel)
   DB_ALNTEXT_IN,     // a host caller's rows and names of a chunk, staged in; a host caller's references (slices)
   DB_ALNTEXT_OUT,    // the text of a chunk staged for a host caller; the slices staged for a host caller
-  DB_COUNT = DB_ALNTEXT_OUT + 1
+  // ---- tracyhip_render_decompositions (dcptext.hip) ----
+  DB_DCPTEXT_DESC,   // DcpDesc per trace up, DcpOut per trace back
+  DB_DCPTEXT_TILES,  // bytes (then offset) and the check word of every tile of a chunk: written by dcptext_count_kernel, scanned in place by
+                     // dcptext_scan_kernel, read by dcptext_emit_kernel
+  DB_DCPTEXT_IN,     // a host caller's tables, rows, basecalls, variants and names of a chunk, staged in
+  DB_DCPTEXT_OUT,    // the text of a chunk staged for a host caller
+  DB_COUNT = DB_DCPTEXT_OUT + 1
 };
 static_assert(DN_CNT + 1 == VB_DESC && VB_PACK_TEXT + 1 == WB_ORIENTED && DN_PAY < DB_COUNT && WB_PAY < DB_COUNT,
               "an alias does not advance the count: every slot of its own comes after the aliases");
@@ -361,6 +367,7 @@ struct tracyhip_ctx {
   tracyhip_render_stats render_stats = {};  // of the last tracyhip_render_traces call (tracyhip_last_render_stats)
   tracyhip_read_stats read_stats = {};  // of the last tracyhip_read_traces call (tracyhip_last_read_stats)
   tracyhip_alntext_stats alntext_stats = {};  // of the last tracyhip_render_alignments call (tracyhip_last_alntext_stats)
+  tracyhip_dcptext_stats dcptext_stats = {};  // of the last tracyhip_render_decompositions call (tracyhip_last_dcptext_stats)
   std::vector<Pending> pending;
   std::vector<hipEvent_t> free_events;
   tracyhip_kernel_timing acc[TRACYHIP_TIMER_COUNT] = {};

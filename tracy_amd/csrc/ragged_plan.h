@@ -61,7 +61,7 @@ inline bool cut_spans(uint32_t n, uint64_t limit, std::vector<Chunk>& chunks, ui
 
 // byte offsets of the parts of a staging buffer, each aligned to 16; total() has 16 spare bytes
 struct Layout {
-  uint64_t at[8] = {0};
+  uint64_t at[16] = {0};
   int n = 0;
   uint64_t add(uint64_t bytes) { at[n + 1] = at[n] + ((bytes + 15) & ~15ull); return at[n++]; }
   uint64_t total() const { return at[n] + 16; }

@@ -198,12 +198,10 @@ struct AlleleReport {
   std::vector<Variant> var;
 };
 
-// traceAlleleAlignJsonOut, json.h:260-381
-template <class Out, typename std::enable_if<!std::is_same<Out, std::string>::value, int>::type = 0>  // (a stream, not a file name)
-inline void traceAlleleAlignJsonOut(Out& out, ReportConfig const& c, BaseCalls const& bc, Trace const& tr, AlleleReport const& r) {
-  out << "{" << std::endl;
-  metaOut(out, c);
-  traceJsonBody(out, bc, tr);
+// the report behind the trace body, json.h:327-381: from the "," line through the closing braces.  fraction(out, k): prints
+// allele k's fraction (traceAlleleAlignJsonOut: the double; tracyhost_dcptext_batch: the caller's bytes)
+template <class Out, class Fraction, typename std::enable_if<!std::is_same<Out, std::string>::value, int>::type = 0>  // (a stream, not a file name)
+inline void traceAlleleAlignJsonTail(Out& out, ReportConfig const& c, BaseCalls const& bc, AlleleReport const& r, Fraction fraction) {
   out << "," << std::endl;
   const std::pair<int32_t, int32_t> xwin = xWindowViewport(bc, (int32_t)(c.trimLeft + r.bp.breakpoint));
   out << "\"chartConfig\": { \"x\": { \"axis\": { \"range\": [" << xwin.first << ", " << xwin.second << "] }}}," << std::endl;
@@ -217,9 +215,13 @@ inline void traceAlleleAlignJsonOut(Out& out, ReportConfig const& c, BaseCalls c
   };
   allele("1", r.rs1, r.align1, r.a1Score);
   allele("2", r.rs2, r.align2, r.a2Score);
-  out << "\"allele1fraction\": " << r.a1a2.first << "," << std::endl;
+  out << "\"allele1fraction\": ";
+  fraction(out, 0);
+  out << "," << std::endl;
   out << "\"allele1align\": \"" << r.align3.row0 << "\"," << std::endl;
-  out << "\"allele2fraction\": " << r.a1a2.second << "," << std::endl;
+  out << "\"allele2fraction\": ";
+  fraction(out, 1);
+  out << "," << std::endl;
   out << "\"allele2align\": \"" << r.align3.row1 << "\"," << std::endl;
   out << "\"align3score\": " << r.a3Score << "," << std::endl;
   out << "\"hetindel\": " << r.bp.indelshift << "," << std::endl;
@@ -259,6 +261,29 @@ inline void traceAlleleAlignJsonOut(Out& out, ReportConfig const& c, BaseCalls c
   out << "}" << std::endl;
 }
 
+// traceAlleleAlignJsonOut, json.h:260-381
+template <class Out, typename std::enable_if<!std::is_same<Out, std::string>::value, int>::type = 0>  // (a stream, not a file name)
+inline void traceAlleleAlignJsonOut(Out& out, ReportConfig const& c, BaseCalls const& bc, Trace const& tr, AlleleReport const& r) {
+  out << "{" << std::endl;
+  metaOut(out, c);
+  traceJsonBody(out, bc, tr);
+  traceAlleleAlignJsonTail(out, c, bc, r, [&](Out& o, int k) { o << (k == 0 ? r.a1a2.first : r.a1a2.second); });
+}
+
+// the record lines of vcfTextOutput: one line per variant, in the columns of its header
+template <class Out, typename std::enable_if<!std::is_same<Out, std::string>::value, int>::type = 0>  // (a stream, not a file name)
+inline void vcfRecordLines(Out& out, ReportConfig const& c, BaseCalls const& bc, std::vector<Variant> const& var, bool forward) {
+  for (Variant const& v : var) {
+    const uint32_t q = variantCallIndex(c, bc, forward, v.basenum);
+    const int32_t qual = strInclN(v.alt) ? 0 : (int32_t)bc.estQual[q];
+    const int64_t basepos = forward ? (int64_t)c.trimLeft + v.basenum : (int64_t)bc.primary.size() - (c.trimRight + v.basenum) + 1;
+    static const char* gt[3] = {"0/0", "0/1", "1/1"};
+    out << v.chr << "\t" << v.pos << "\t" << v.id << "\t" << v.ref << "\t" << v.alt << "\t" << qual << "\t" << (qual < c.qualCut ? "LowQual" : "PASS")
+        << "\tTYPE=" << variantType(v.ref, v.alt) << ";METHOD=EMBL.TRACYv" << kTracyVersion << ";BASEPOS=" << basepos << ";SIGNALPOS=" << bc.bcPos[q] + 1
+        << "\tGT:GQ\t" << ((v.gt >= 0 && v.gt <= 2) ? gt[v.gt] : "./.") << ":" << (int32_t)bc.estQual[q] << "\n";
+  }
+}
+
 // variants as VCF text: the header lines, columns, INFO and FORMAT values vcfOutput (variants.h:141-261)
 // puts into its BCF
 // contigs: (name, length + 1) of every sequence of an indexed genome (rs.filetype == 0, variants.h:176-186); NULL
@@ -286,15 +311,7 @@ inline void vcfTextOutput(Out& out, ReportConfig const& c, BaseCalls const& bc, 
     out << "##contig=<ID=" << rs.chr << ",length=" << rs.refslice.size() << ">\n";
   }
   out << "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsample\n";
-  for (Variant const& v : var) {
-    const uint32_t q = variantCallIndex(c, bc, rs.forward, v.basenum);
-    const int32_t qual = strInclN(v.alt) ? 0 : (int32_t)bc.estQual[q];
-    const int64_t basepos = rs.forward ? (int64_t)c.trimLeft + v.basenum : (int64_t)bc.primary.size() - (c.trimRight + v.basenum) + 1;
-    static const char* gt[3] = {"0/0", "0/1", "1/1"};
-    out << v.chr << "\t" << v.pos << "\t" << v.id << "\t" << v.ref << "\t" << v.alt << "\t" << qual << "\t" << (qual < c.qualCut ? "LowQual" : "PASS")
-        << "\tTYPE=" << variantType(v.ref, v.alt) << ";METHOD=EMBL.TRACYv" << kTracyVersion << ";BASEPOS=" << basepos << ";SIGNALPOS=" << bc.bcPos[q] + 1
-        << "\tGT:GQ\t" << ((v.gt >= 0 && v.gt <= 2) ? gt[v.gt] : "./.") << ":" << (int32_t)bc.estQual[q] << "\n";
-  }
+  vcfRecordLines(out, c, bc, var, rs.forward);
 }
 
 }  // namespace tracy_amd

@@ -7,6 +7,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/tracy_hip.h"  // tracyhip_dcptext_job, tracyhip_render_result, tracyhip_variant: declarations alone
 #include "assemble_out.hpp"
 #include "bcf_out.hpp"
 #include "indigo_out.hpp"
@@ -1010,6 +1011,109 @@ int tracyhost_read_batch(uint32_t n, const uint8_t* bytes, const uint64_t* file_
         put(o_b1, tr.basecalls1.data(), tr.basecalls1.size());
         put(o_b2, tr.basecalls2.data(), tr.basecalls2.size());
         put(o_qual, tr.qual.data(), tr.qual.size());
+      }
+    });
+  for (auto& t : th) t.join();
+  return 0;
+}
+
+// ---- the text printed from the decompose results, one trace after the other per thread: writeDecomposition, traceAlleleAlignJsonTail
+// and vcfRecordLines (indigo_out.hpp) into a TextBuf over the job of tracyhip_render_decompositions, host arrays throughout (the
+// fallback for its deferred traces; tools/dcptext_device_line.py times it beside the device call) ----
+// The forms and what each reads are the device call's (include/tracy_hip.h).  Long names, rows beyond 2^22 columns and any number of
+// basecalls are printed.  status: 0 answered; 1 the writers would index outside an array (no basecall, trim_left + breakpoint or a
+// variant's call index at or beyond bc_len, var_n > max_variants, a ref or alt outside the trace's text region) or the text does not
+// fit 32 bits; 2 text_cap is too small (text_len reported).  out->text may be null (sizes only).
+int tracyhost_dcptext_batch(const tracyhip_dcptext_job* job, const tracyhip_render_result* res, uint32_t nthreads) {
+  if (!job || !res || job->form > 2 || (res->text && (!res->text_offset || !res->text_cap))) return -1;
+  const uint32_t n = job->n, form = job->form;
+  const bool table = form != TRACYHIP_DCPTEXT_VCF, calls = form != TRACYHIP_DCPTEXT_DECOMP, json = form == TRACYHIP_DCPTEXT_JSON;
+  if (n && (!res->status || !res->text_len)) return -1;
+  if (n && table && (!job->dcp_indel || !job->dcp_err || !job->dcp_offset || !job->dcp_rows)) return -1;
+  if (n && calls && (!job->bcpos || !job->estqual || !job->bc_offset || !job->bc_len || !job->var || !job->var_text || !job->var_n || !job->forward ||
+                     !job->trim_left || !job->trim_right || !job->names || !job->chr_offset[0] || !job->chr_len[0] || job->max_variants < 1 || job->max_text < 2))
+    return -1;
+  if (n && json) {
+    for (int k = 0; k < 3; ++k)
+      if (!job->rows0[k] || !job->rows1[k] || !job->rows_offset[k] || !job->cols[k] || !job->score[k]) return -1;
+    if (!job->ref_pos[0] || !job->ref_pos[1] || !job->breakpoint || !job->indelshift || !job->chr_offset[1] || !job->chr_len[1] || !job->frac_offset[0] ||
+        !job->frac_len[0] || !job->frac_offset[1] || !job->frac_len[1])
+      return -1;
+  }
+  if (nthreads == 0) nthreads = tracy_amd::usable_threads();
+  const tracyhip_dcptext_job j = *job;
+  const tracyhip_render_result o = *res;
+  std::vector<std::thread> th;
+  for (uint32_t w = 0; w < nthreads; ++w)
+    th.emplace_back([=]() {
+      BaseCalls bc;
+      AlleleReport r;
+      ReportConfig c;
+      c.qualCut = (uint16_t)j.qual_cut;
+      auto name = [&](const uint64_t* off, const uint32_t* len, uint32_t t) { return std::string(reinterpret_cast<const char*>(j.names) + off[t], len[t]); };
+      for (uint32_t t = (uint32_t)((uint64_t)n * w / nthreads); t < (uint32_t)((uint64_t)n * (w + 1) / nthreads); ++t) {
+        o.status[t] = 1;
+        o.text_len[t] = 0;
+        std::size_t room = 4096;
+        if (table) {
+          r.dcp.clear();
+          for (uint32_t i = 0; i < j.dcp_rows[t]; ++i) r.dcp.emplace_back(j.dcp_indel[j.dcp_offset[t] + i], j.dcp_err[j.dcp_offset[t] + i]);
+          room += (std::size_t)48 * j.dcp_rows[t];
+        }
+        if (calls) {
+          const uint32_t nc = j.bc_len[t];
+          if (nc == 0) continue;
+          c.trimLeft = (uint16_t)j.trim_left[t];
+          c.trimRight = (uint16_t)j.trim_right[t];
+          bc.bcPos.assign(j.bcpos + j.bc_offset[t], j.bcpos + j.bc_offset[t] + nc);
+          bc.estQual.assign(j.estqual + j.bc_offset[t], j.estqual + j.bc_offset[t] + nc);
+          bc.primary.assign(nc, 'N');  // (the writers read its size alone)
+          r.rs1.forward = r.rs2.forward = j.forward[t] != 0;
+          r.rs1.chr = name(j.chr_offset[0], j.chr_len[0], t);
+          const uint32_t at = j.var_index ? j.var_index[t] : t;
+          const uint32_t nv = j.var_n[at];
+          if (nv > j.max_variants) continue;
+          const tracyhip_variant* rec = j.var + (uint64_t)at * j.max_variants;
+          const char* vt = reinterpret_cast<const char*>(j.var_text) + (uint64_t)at * j.max_text;
+          r.var.clear();
+          bool ok = true;
+          for (uint32_t i = 0; ok && i < nv; ++i) {
+            ok = variantCallIndex(c, bc, r.rs1.forward, rec[i].basenum) < nc && (uint64_t)rec[i].ref_off + rec[i].ref_len <= j.max_text &&
+                 (uint64_t)rec[i].alt_off + rec[i].alt_len <= j.max_text;
+            if (ok)
+              r.var.push_back(Variant{rec[i].pos, rec[i].basenum, rec[i].gt, r.rs1.chr, std::string(vt + rec[i].ref_off, rec[i].ref_len),
+                                      std::string(vt + rec[i].alt_off, rec[i].alt_len), "."});
+            room += 256 + r.rs1.chr.size() + rec[i].ref_len + rec[i].alt_len;
+          }
+          if (!ok) continue;
+        }
+        std::string frac[2];
+        if (json) {
+          r.bp.breakpoint = j.breakpoint[t];
+          r.bp.indelshift = j.indelshift[t] != 0;
+          if ((uint32_t)(c.trimLeft + r.bp.breakpoint) >= j.bc_len[t]) continue;
+          r.rs2.chr = name(j.chr_offset[1], j.chr_len[1], t);
+          r.rs1.pos = j.ref_pos[0][t];
+          r.rs2.pos = j.ref_pos[1][t];
+          AlignRows* al[3] = {&r.align1, &r.align2, &r.align3};
+          for (int k = 0; k < 3; ++k) {
+            al[k]->row0.assign(reinterpret_cast<const char*>(j.rows0[k]) + j.rows_offset[k][t], j.cols[k][t]);
+            al[k]->row1.assign(reinterpret_cast<const char*>(j.rows1[k]) + j.rows_offset[k][t], j.cols[k][t]);
+            room += (std::size_t)2 * j.cols[k][t];
+          }
+          r.a1Score = j.score[0][t]; r.a2Score = j.score[1][t]; r.a3Score = j.score[2][t];
+          for (int k = 0; k < 2; ++k) frac[k] = name(j.frac_offset[k], j.frac_len[k], t);
+          room += r.rs1.chr.size() + r.rs2.chr.size() + frac[0].size() + frac[1].size();
+        }
+        TextBuf out(room);
+        if (form == TRACYHIP_DCPTEXT_DECOMP) writeDecomposition(out, r.dcp);
+        else if (json) traceAlleleAlignJsonTail(out, c, bc, r, [&](TextBuf& b, int k) { b << frac[k]; });
+        else vcfRecordLines(out, c, bc, r.var, r.rs1.forward);
+        if (out.size() > 0xffffffffull) continue;
+        o.text_len[t] = (uint32_t)out.size();
+        if (o.text && out.size() > o.text_cap[t]) { o.status[t] = 2; continue; }
+        o.status[t] = 0;
+        if (o.text) std::memcpy(o.text + o.text_offset[t], out.data(), out.size());
       }
     });
   for (auto& t : th) t.join();

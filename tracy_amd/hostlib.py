@@ -789,3 +789,123 @@ def read_batch(files, sample_dtype=np.int32, nthreads=0):
     sizes = read_batch_raw(flat, read_alloc(nt, sample_dtype, np.zeros(nt, np.uint32), np.zeros(nt, np.uint32)), nthreads, sizes_only=True)
     out = read_batch_raw(flat, read_alloc(nt, sample_dtype, sizes["nsamples"], sizes["ncalls"]), nthreads)
     return [read_unpack(out, t) for t in range(nt)]
+
+
+# ---- the text printed from the decompose results on the host (tracyhost_dcptext_batch): the fallback and the baseline of
+# tracyhip_render_decompositions ----------------------------------------------------------------------------------------------------------
+DCPTEXT_DECOMP, DCPTEXT_JSON, DCPTEXT_VCF = 0, 1, 2
+dcptext_alloc = render_alloc  # (the result arrays of a printing call: status, text_len, text, text_offset, text_cap)
+dcptext_unpack = render_unpack
+DCPTEXT_PAYLOADS = ("dcp_indel", "dcp_err", "rows0_0", "rows1_0", "rows0_1", "rows1_1", "rows0_2", "rows1_2", "bcpos", "estqual", "var", "var_text",
+                    "var_n", "names")
+
+
+def dcptext_pack(traces, max_variants=16, max_text=256):
+    """per-trace dicts as the flattened arrays of a PreparedDcpText (capi.py).  A trace: dcp [(indel, err)], rows 3 x (row0, row1), bcpos,
+    estqual, variants [dict(pos, basenum, gt, ref, alt)] (or var_n and records of its own: raw_var_n, raw_records [8 numbers each]),
+    ref_pos (2), forward, score (3), breakpoint, indelshift, trim_left, trim_right, chr1, chr2, frac1, frac2 (bytes)"""
+    from .capi import VARIANT_DTYPE
+    nt = len(traces)
+    z = lambda dt, n=nt + 1: np.zeros(n, dt)
+    cum = lambda lens: np.concatenate([[0], np.cumsum(np.asarray(lens, dtype=np.uint64))]).astype(np.uint64)
+    f = dict(nt=nt, max_variants=int(max_variants), max_text=int(max_text))
+    f["dcp_rows"] = np.array([len(t["dcp"]) for t in traces] + [0], np.uint32)
+    f["dcp_off"] = cum(f["dcp_rows"][:nt])
+    flat = [p for t in traces for p in t["dcp"]]
+    f["dcp_indel"] = np.array([a for a, _ in flat] + [0], np.int32)
+    f["dcp_err"] = np.array([b for _, b in flat] + [0], np.int32)
+    for k in range(3):
+        f["cols_%d" % k] = np.array([len(t["rows"][k][0]) for t in traces] + [0], np.uint32)
+        f["rows_off_%d" % k] = cum(f["cols_%d" % k][:nt])
+        for r in range(2):
+            f["rows%d_%d" % (r, k)] = np.frombuffer(b"".join(bytes(t["rows"][k][r]) for t in traces) + b"\0" * 4, np.uint8).copy()
+    f["bc_len"] = np.array([len(t["bcpos"]) for t in traces] + [0], np.uint32)
+    f["bc_off"] = cum(f["bc_len"][:nt])
+    f["bcpos"] = np.concatenate([np.asarray(t["bcpos"], dtype=np.int32) for t in traces] + [np.zeros(1, np.int32)])
+    f["estqual"] = np.concatenate([np.asarray(t["estqual"], dtype=np.uint8) for t in traces] + [np.zeros(1, np.uint8)])
+    f["var"] = np.zeros(max(nt, 1) * max_variants, VARIANT_DTYPE)
+    f["var_text"] = np.zeros(max(nt, 1) * max_text, np.uint8)
+    f["var_n"] = z(np.uint32, max(nt, 1))
+    for i, t in enumerate(traces):
+        if "raw_records" in t:
+            f["var_n"][i] = t["raw_var_n"]
+            for j, rec in enumerate(t["raw_records"]):
+                f["var"][i * max_variants + j] = tuple(rec)
+            text = bytes(t.get("raw_text", b""))
+            f["var_text"][i * max_text:i * max_text + len(text)] = np.frombuffer(text, np.uint8)
+            continue
+        at = 0
+        f["var_n"][i] = len(t["variants"])
+        for j, v in enumerate(t["variants"]):
+            ref, alt = bytes(v["ref"]), bytes(v["alt"])
+            f["var"][i * max_variants + j] = (v["pos"], v["basenum"], v["gt"], v.get("call_index", 0), at, len(ref), at + len(ref), len(alt))
+            f["var_text"][i * max_text + at:i * max_text + at + len(ref) + len(alt)] = np.frombuffer(ref + alt, np.uint8)
+            at += len(ref) + len(alt)
+    for k in range(2):
+        f["ref_pos_%d" % k] = np.array([t["ref_pos"][k] for t in traces] + [0], np.uint32)
+    for k in range(3):
+        f["score_%d" % k] = np.array([t["score"][k] for t in traces] + [0], np.int32)
+    f["forward"] = np.array([1 if t["forward"] else 0 for t in traces] + [0], np.uint8)
+    f["indelshift"] = np.array([1 if t["indelshift"] else 0 for t in traces] + [0], np.uint8)
+    for k in ("breakpoint", "trim_left", "trim_right"):
+        f[k] = np.array([t[k] for t in traces] + [0], np.uint32)
+    parts = ("chr1", "chr2", "frac1", "frac2")
+    lens = np.array([[len(t[p]) for p in parts] for t in traces], np.uint64).reshape(nt, 4)
+    offs = cum(lens.reshape(-1))
+    for j, p in enumerate(parts):
+        f[p + "_len"] = np.append(lens[:, j].astype(np.uint32), np.uint32(0))
+        f[p + "_off"] = np.append(offs[j:4 * nt:4], np.uint64(0)).astype(np.uint64)
+    f["names"] = np.frombuffer(b"".join(bytes(t[p]) for t in traces for p in parts) + b"\0" * 4, np.uint8).copy()
+    return f
+
+
+def dcptext_job(flat, form, qual_cut, ptr):
+    """a tracyhip_dcptext_job (capi.DcpTextJob) over the flattened arrays; ptr(key): the address of payload array `key`"""
+    from . import capi
+    u64, u32 = capi._u64p, capi._u32p
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    u8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))
+    job = capi.DcpTextJob()
+    job.n, job.form, job.qual_cut = flat["nt"], form, qual_cut
+    job.dcp_indel, job.dcp_err = ptr("dcp_indel"), ptr("dcp_err")
+    job.dcp_offset, job.dcp_rows = u64(flat["dcp_off"]), u32(flat["dcp_rows"])
+    for k in range(3):
+        job.rows0[k], job.rows1[k] = ptr("rows0_%d" % k), ptr("rows1_%d" % k)
+        job.rows_offset[k], job.cols[k] = u64(flat["rows_off_%d" % k]), u32(flat["cols_%d" % k])
+        job.score[k] = i32(flat["score_%d" % k])
+    job.bcpos, job.estqual = ptr("bcpos"), ptr("estqual")
+    job.bc_offset, job.bc_len = u64(flat["bc_off"]), u32(flat["bc_len"])
+    job.var, job.var_text, job.var_n = ptr("var"), ptr("var_text"), ptr("var_n")
+    job.max_variants, job.max_text = flat["max_variants"], flat["max_text"]
+    if flat.get("var_index") is not None:  # (the place of every trace in the variant arrays; without it trace t lies at t)
+        job.var_index = u32(flat["var_index"])
+    for k in range(2):
+        job.ref_pos[k] = u32(flat["ref_pos_%d" % k])
+        job.chr_offset[k], job.chr_len[k] = u64(flat["chr%d_off" % (k + 1)]), u32(flat["chr%d_len" % (k + 1)])
+        job.frac_offset[k], job.frac_len[k] = u64(flat["frac%d_off" % (k + 1)]), u32(flat["frac%d_len" % (k + 1)])
+    job.forward, job.indelshift = u8(flat["forward"]), u8(flat["indelshift"])
+    job.breakpoint, job.trim_left, job.trim_right = u32(flat["breakpoint"]), u32(flat["trim_left"]), u32(flat["trim_right"])
+    job.names = ptr("names")
+    return job
+
+
+def dcptext_batch_raw(flat, form, out, qual_cut=45, nthreads=0, sizes_only=False):
+    """one tracyhost_dcptext_batch call over the flattened arrays of a PreparedDcpText (capi.py) into `out` (dcptext_alloc)"""
+    from . import capi
+    job = dcptext_job(flat, form, qual_cut, lambda k: flat[k].ctypes.data)
+    res = capi.RenderResult()
+    res.status = out["status"].ctypes.data_as(C.POINTER(C.c_int32))
+    res.text_len = capi._u32p(out["text_len"])
+    res.text = None if sizes_only else out["text"].ctypes.data
+    res.text_offset, res.text_cap = capi._u64p(out["text_offset"]), capi._u64p(out["text_cap"])
+    if lib().tracyhost_dcptext_batch(C.byref(job), C.byref(res), C.c_uint32(nthreads)) != 0:
+        raise ValueError("tracyhost_dcptext_batch: bad arguments")
+    return out
+
+
+def dcptext_batch(flat, form, qual_cut=45, nthreads=0):
+    """print a batch of decompose reports on host threads: a sizes-only call, a buffer of exactly those sizes, the call; per-trace dicts
+    (status 1: the writers would index outside an array)"""
+    sizes = dcptext_batch_raw(flat, form, dcptext_alloc(flat["nt"], np.zeros(flat["nt"], np.uint64)), qual_cut, nthreads, sizes_only=True)
+    out = dcptext_batch_raw(flat, form, dcptext_alloc(flat["nt"], sizes["text_len"]), qual_cut, nthreads)
+    return [dcptext_unpack(out, t) for t in range(flat["nt"])]
